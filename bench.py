@@ -12,11 +12,14 @@ One "step" = one optimisation step (pack -> fwd -> Dice+Focal -> bwd -> [all-red
 of 32 synthetic images already resident in HBM (BASELINE.json configs[1]; weak scaling: global batch = 32*N).
 Default compute mode is the one configs[1] names: bf16 MFMA operands (3x3 convs, k=2 ConvT), stored once in the MFMA's
 16-bit channel-blocked layout; the conv outputs in front of InstanceNorm are stored in 16 bits too (fp16, 11 significant
-bits); accumulators, gradient sums, norm statistics, parameters, losses and Adam are fp32.  At N=1 the same step is also
-timed in the fp32 parity mode (`fp32_parity_mode`: the reference's arithmetic, the mode the 1e-4 parity tests run in).
-Rank 0 prints ONE JSON line; `roofline` is measured live with HIP events around the dominant kernel family (the
-implicit-GEMM conv3x3, forward + dgrad launches) and priced against the roof the kernel's arithmetic intensity puts it
-under (fp32: MFMA; bf16: HBM); `cpu_baseline` times the CPU oracle on the host cores.
+bits); accumulators, gradient sums, norm statistics, parameters, losses and Adam are fp32.
+Rank 0 prints ONE JSON line.  A plain run measures the headline only: set up, warm up, time `--steps` steps, print.
+`--full` adds the other measurements to the same line: at N=1 the same step timed in the fp32 parity mode
+(`fp32_parity_mode`: the reference's arithmetic, the mode the 1e-4 parity tests run in); `roofline`, measured live with
+HIP events around the dominant kernel family (the implicit-GEMM conv3x3, forward + dgrad launches) and priced against the
+roof the kernel's arithmetic intensity puts it under (fp32: MFMA; bf16: HBM); `cpu_baseline`, the CPU oracle timed on
+the host cores.  `--dump-outputs DIR` writes what the last timed step computed as float32 .npy files (dump_outputs()):
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -83,6 +86,32 @@ def note(msg: str) -> None:
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_MAX_ELEMS = 1 << 21        # per file (8 MB of float32): the five files of a dump stay under 64 MB
+
+
+def write_dump(out_dir: str, arrays: dict) -> None:
+    """Each tensor as out_dir/<name>.npy in float32.  One with more than DUMP_MAX_ELEMS elements is replaced by a fixed
+    sample of its flattened elements: the same seeded, sorted positions in every run with the same number of elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            pos = np.sort(np.random.default_rng(1993).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(pos).to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.float().cpu().numpy())
+
+
+def dump_outputs(out_dir: str, step, model) -> None:
+    """What the timed path computed in its last step: the losses the step returns, the forward pass's classification
+    logits and last segmentation head, and the model's flat fp32 parameters (after the Adam update) and gradients."""
+    st = step._st
+    write_dump(out_dir, {"losses": step.losses,                         # [total, seg, cls, NaN flag]
+                         "cls_logits": st.logits.data.view(st.N, -1),
+                         "seg_logits": st.segs[-1].data,                 # the head a caller without deep supervision receives
+                         "params": model.flat_p, "grads": model.flat_g})
+
+
 def conv_bytes(op, kind, L) -> float:
     """Algorithmic HBM bytes of one conv3x3 launch: every operand plane once, in the storage the launch is
     handed -- fp32 planes, or 2-byte elements for the tensors an operand_layout = C8 launch reads."""
@@ -111,8 +140,9 @@ def time_op(prog, i, reps=3) -> float:
     return ms / reps / 1e3
 
 
-def run_mode(args, dtype, dev, rank, world, dist, want_roofline):
-    """Build the model in one compute mode, time `steps` optimisation steps, optionally price the kernels."""
+def run_mode(args, dtype, dev, rank, world, dist, want_roofline, dump_dir=None):
+    """Build the model in one compute mode, time `steps` optimisation steps, optionally write what the last one computed
+    (before anything else runs the step's programs again) and price the kernels."""
     from multi_task_breast_cancer_amd import _lib
     from multi_task_breast_cancer_amd.experiment_init import init_multitask_model, init_optimizer
     from multi_task_breast_cancer_amd.miscellany import seed_everything
@@ -150,6 +180,9 @@ def run_mode(args, dtype, dev, rank, world, dist, want_roofline):
     step.check_nan()
     losses = step.losses.cpu().tolist()
     note(f"[{dtype}] timed {args.steps} steps in {dt:.3f} s; loss {losses[0]:.5f}")
+    if dump_dir is not None:
+        dump_outputs(dump_dir, step, model)
+        note(f"[{dtype}] outputs of the last timed step written to {dump_dir}")
     res = {"value": round(args.batch * world * args.steps / dt, 2), "ms_per_step": round(dt / args.steps * 1e3, 3),
            "final_loss": round(losses[0], 6)}
     if not want_roofline:
@@ -323,13 +356,15 @@ def stub_main(args, rank: int, world: int) -> None:
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        y = step()
     if world > 1:
         dist.barrier()
     t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+    if rank == 0 and args.dump_outputs is not None:
+        write_dump(args.dump_outputs, {"stand_in": y, "stand_in_weights": w})
     metric, tail, idx = workload_labels(args, world)
     if rank == 0:
         print(json.dumps({"metric": metric, "value": round(args.batch * world * args.steps / dt, 2), "unit": "images/sec", "n_gpus": world,
@@ -355,9 +390,15 @@ def main() -> None:
                     help="MFMA operand type of the 3x3 convs / k=2 ConvT (BASELINE.json configs[1] names bf16); in the 16-bit modes "
                          "operand tensors and conv outputs are STORED in 16 bits, accumulation, norm statistics, gradient sums, "
                          "losses and Adam stay fp32; f32 = the reference-arithmetic parity mode")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-parity-mode", action="store_true", help="skip the extra fp32 (parity mode) measurement at N=1")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline, in the same JSON line: the fp32 parity mode at N=1, the rooflines "
+                         "(per-launch HIP-event timing of the step's kernels) and the CPU oracle baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the rooflines")
+    ap.add_argument("--no-parity-mode", action="store_true", help="with --full: skip the extra fp32 (parity mode) measurement at N=1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (losses, logits, last segmentation head, "
+                         "parameters, gradients; a fixed sample of the large ones) as DIR/<name>.npy in float32 (rank 0)")
     ap.add_argument("--host-input", action="store_true",
                     help="feed pinned HOST batches (H2D copy inside the timed step): the PCIe-inclusive rate, never the headline")
     ap.add_argument("--allow-probes", action="store_true",
@@ -367,6 +408,8 @@ def main() -> None:
                     help="launcher / contract rehearsal WITHOUT a GPU: gloo backend and a stand-in step (tests/test_bench_cli_cpu.py); "
                          "the line is marked not_reportable")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # bare `python bench.py --gpus N`: one fresh process per GPU through torch.distributed.run, started before this
@@ -398,7 +441,8 @@ def main() -> None:
         dist = dist_
         dist.init_process_group("nccl", device_id=dev)
 
-    main_res = run_mode(args, args.dtype, dev, rank, world, dist, rank == 0 and not args.no_roofline)
+    main_res = run_mode(args, args.dtype, dev, rank, world, dist, args.full and rank == 0 and not args.no_roofline,
+                        dump_dir=args.dump_outputs if rank == 0 else None)
     metric, tail, cfg_idx = workload_labels(args, world)
     out = {
         "metric": metric, "value": main_res["value"],
@@ -422,13 +466,13 @@ def main() -> None:
     for k in ("roofline", "roofline_hbm"):
         if k in main_res:
             out[k] = main_res[k]
-    if rank == 0 and world == 1 and args.dtype != "f32" and not args.no_parity_mode:
+    if args.full and rank == 0 and world == 1 and args.dtype != "f32" and not args.no_parity_mode:
         # the same step in the reference-parity arithmetic (exact fp32 MFMA), same run, same box
         torch.cuda.empty_cache()
         r = run_mode(args, "f32", dev, rank, world, dist, not args.no_roofline)
         out["fp32_parity_mode"] = {"value": r["value"], "unit": "images/sec", "ms_per_step": r["ms_per_step"], "dtype": "f32",
                                    "final_loss": r["final_loss"], **({"roofline": r["roofline"]} if "roofline" in r else {})}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         note("cpu baseline (oracle on host cores)")
         out["cpu_baseline"] = cpu_baseline(args.arch, args.size, 8, 3)
     if rank == 0:

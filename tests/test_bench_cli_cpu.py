@@ -67,3 +67,42 @@ def test_gpus_8_is_labelled_as_baseline_configs_3():
     assert out["n_gpus"] == 8 and out["config"]["baseline_config_index"] == 3
     assert out["config"]["global_batch"] == 256 and out["config"]["parallelism"] == "dp8" and out["scaling"] == "weak"
     assert "configs[3]" in out["config"]["workload"]
+
+
+def test_dump_keeps_small_arrays_and_samples_large_ones_the_same_way_every_time(tmp_path):
+    """--dump-outputs: float32 .npy files; an array above DUMP_MAX_ELEMS becomes a fixed, seeded sample of its elements (the same
+    positions in every run), so that two builds' dumps can be compared element for element within the 64 MB budget."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = bench.DUMP_MAX_ELEMS * 3 + 5
+    big = torch.arange(n, dtype=torch.float64)
+    small = torch.arange(12, dtype=torch.float32).reshape(3, 4)
+    for d in ("a", "b"):
+        bench.write_dump(str(tmp_path / d), {"big": big, "small": small})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX_ELEMS,)
+    assert np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < n               # distinct elements of the array, in order
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.numpy())
+    assert 6 * bench.DUMP_MAX_ELEMS * 4 <= 64 * 2 ** 20                     # the five files of a dump (+ slack) fit the budget
+
+
+def test_cpu_stub_dump_outputs_repeat_and_full_is_accepted(tmp_path):
+    import numpy as np
+    outs = []
+    for d in ("a", "b"):
+        r, lines = _run("--gpus", "1", "--steps", "2", "--warmup", "1", "--cpu-stub", "--full", "--dump-outputs", str(tmp_path / d))
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert len(lines) == 1 and json.loads(lines[0])["steps"] == 2
+        outs.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    assert sorted(outs[0]) == ["stand_in.npy", "stand_in_weights.npy"]
+    for f, a in outs[0].items():
+        assert a.dtype == np.float32 and np.array_equal(a, outs[1][f]), f
+
+
+def test_steps_must_be_positive():
+    r, lines = _run("--gpus", "1", "--steps", "0", "--cpu-stub")
+    assert r.returncode != 0 and not lines and "--steps" in r.stderr
