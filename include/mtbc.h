@@ -191,6 +191,13 @@ int32_t mtbc_conv3x3_stats_slots(const mtbc_conv3x3_args* a);
 size_t mtbc_conv3x3_wgrad_workspace(const mtbc_conv3x3_args* a);
 /* bytes of zeroed counters mtbc_conv3x3_args.wgrad_sync needs for these arguments (0: this launch has no in-kernel reduction) */
 size_t mtbc_conv3x3_wgrad_sync_bytes(const mtbc_conv3x3_args* a);
+/* Host-only plan query: the kernel instance mtbc_conv3x3_fwd / _dgrad / _wgrad (op = MTBC_OP_CONV3_FWD / _DGRAD / _WGRAD) would
+ * launch for these arguments, written to buf (NUL-terminated) as a profiler spells it without namespace and argument list, e.g.
+ * "conv3x3_igemm_c8_kernel<3, 0, false, 4, 3>"; for the weight gradient followed by its reduction: " + splitk_reduce" (a reduction
+ * launch), " + splitk_fixup" (in the kernel, mtbc_conv3x3_args.wgrad_sync), " + channel_sums" (the bias gradient's launch).
+ * Launches nothing, never synchronises, never dereferences a tensor pointer; returns the code the real call would return when it
+ * refuses the arguments, MTBC_E_BADARG for an unknown op or a buffer shorter than the name. */
+int mtbc_conv3x3_kernel_name(const mtbc_conv3x3_args* a, int32_t op, char* buf, int32_t len);
 int mtbc_conv3x3_fwd(const mtbc_conv3x3_args* a, void* stream);
 int mtbc_conv3x3_dgrad(const mtbc_conv3x3_args* a, void* stream);
 int mtbc_conv3x3_wgrad(const mtbc_conv3x3_args* a, void* stream);

@@ -11,6 +11,8 @@
 #include <type_traits>
 #include <utility>
 #include <cstdlib>
+#include <cstdio>
+#include <cstring>
 
 namespace {
 
@@ -3335,16 +3337,12 @@ bool mfma_ok(const mtbc_seg* segs, int nseg, int H, int W) {
 int pick_geo(int H, int W) { return (W == 8 && H == 8) ? 2 : (W <= 16 ? 1 : 0); }
 
 template <int MT, int GEO>
-int launch_igemm(const ConvP& p, int mblocks, hipStream_t st) {
+int launch_igemm(const ConvP& p, int mblocks, int ring, hipStream_t st) {      // ring: 2 / 3 = conv3x3_igemm_dma_kernel<MT, GEO, ring>, 0 = conv3x3_igemm_kernel
     using G = Geo<GEO>;
-    static const bool nodma = mtbc_probe_set("MTBC_NODMA");
     // persistent grid: gridDim.x a multiple of 8 so that the channel blocks of one pixel tile (same blockIdx.x)
     // land on one XCD and share its L2
     if constexpr (GEO != 2) {
-        if (!nodma) {
-            constexpr int RING = 2;     // measured: occupancy (3 blocks/CU) beats the deeper 3-slot prefetch on every layer
-            static const int ring_env = mtbc_probe_int("MTBC_RING", 0);
-            const int ring = ring_env ? ring_env : RING;
+        if (ring) {
             const size_t lds = ((size_t)ring * (KC * G::PS + MT * KC * 144) + SEGL_FLOATS + MT * 16) * sizeof(float);
             MTBC_ENSURE_DYN_LDS((&conv3x3_igemm_dma_kernel<MT, GEO, 2>), 160 * 1024);      // > 64 KiB of dynamic LDS: opt-in per kernel and device
             MTBC_ENSURE_DYN_LDS((&conv3x3_igemm_dma_kernel<MT, GEO, 3>), 160 * 1024);
@@ -3367,11 +3365,11 @@ int launch_igemm(const ConvP& p, int mblocks, hipStream_t st) {
     return MTBC_OK;
 }
 template <int GEO>
-int launch_igemm_mt(int MT, const ConvP& p, int mblocks, hipStream_t st) {
+int launch_igemm_mt(int MT, const ConvP& p, int mblocks, int ring, hipStream_t st) {
     switch (MT) {
-        case 1: return launch_igemm<1, GEO>(p, mblocks, st);
-        case 2: return launch_igemm<2, GEO>(p, mblocks, st);
-        default: return launch_igemm<3, GEO>(p, mblocks, st);
+        case 1: return launch_igemm<1, GEO>(p, mblocks, ring, st);
+        case 2: return launch_igemm<2, GEO>(p, mblocks, ring, st);
+        default: return launch_igemm<3, GEO>(p, mblocks, ring, st);
     }
 }
 
@@ -3458,6 +3456,15 @@ int launch_igemm_c8_mt(int MT, const ConvP& p, int mblocks, bool f16, hipStream_
     if (MT == 3) return launch_igemm_c8<3, GEO, 4, O8>(p, mblocks, f16, st);
     return launch_igemm_c8<2, GEO, 4, O8>(p, mblocks, f16, st);
 }
+template <int GEO>
+int launch_igemm_c8_o8(int MT, int O8, const ConvP& p, int mblocks, bool f16, hipStream_t st) {
+    switch (O8) {
+        case 0: return launch_igemm_c8_mt<GEO, 0>(MT, p, mblocks, f16, st);
+        case 1: return launch_igemm_c8_mt<GEO, 1>(MT, p, mblocks, f16, st);
+        case 2: return launch_igemm_c8_mt<GEO, 2>(MT, p, mblocks, f16, st);
+        default: return launch_igemm_c8_mt<GEO, 3>(MT, p, mblocks, f16, st);
+    }
+}
 
 template <int MT, int GEO, int O8>
 int launch_igemm_c8_ring(const ConvP& p, int mblocks, bool f16, hipStream_t st) {
@@ -3508,6 +3515,43 @@ int launch_igemm_c8_ring_mt(int MT, const ConvP& p, int mblocks, bool f16, hipSt
     if (MT == 1) return launch_igemm_c8_ring<1, GEO, O8>(p, mblocks, f16, st);
     if (MT == 3) return launch_igemm_c8_ring<3, GEO, O8>(p, mblocks, f16, st);
     return launch_igemm_c8_ring<2, GEO, O8>(p, mblocks, f16, st);
+}
+
+// Which kernel instance a conv3x3 call launches: the family, its template arguments and the split-K reduction behind it.  Every
+// dispatcher below (run_igemm, conv_fwd, conv_dgrad, conv_wgrad) builds ONE of these first; its launch code then reads the kernel
+// from it, and mtbc_conv3x3_kernel_name() -- the same dispatcher called without a stream -- prints it: the name cannot drift from the launch.
+enum KernelFamily {
+    KF_IGEMM, KF_IGEMM_DMA, KF_IGEMM_LP, KF_IGEMM_C8, KF_IGEMM_C8_RING, KF_STEM_FWD, KF_STEM_FWD_C8, KF_DIRECT,
+    KF_WGRAD_STEM_C8, KF_WGRAD_C8, KF_WGRAD_C8W, KF_WGRAD_C8I, KF_WGRAD_MFMA, KF_WGRAD_LP, KF_WGRAD_LP2, KF_WGRAD_SMALLCIN, KF_WGRAD_DIRECT
+};
+struct KernelFamilyInfo { const char* name; int nargs; unsigned bools; };      // bools: bit i = template argument i is a bool
+constexpr KernelFamilyInfo KFAM[] = {
+    {"conv3x3_igemm_kernel", 2, 0}, {"conv3x3_igemm_dma_kernel", 3, 0}, {"conv3x3_igemm_lp_kernel", 3, 4}, {"conv3x3_igemm_c8_kernel", 5, 4},
+    {"conv3x3_igemm_c8_ring_kernel", 5, 4}, {"conv3x3_stem_fwd_kernel", 0, 0}, {"conv3x3_stem_fwd_c8_kernel", 1, 1}, {"conv3x3_direct_kernel", 0, 0},
+    {"conv3x3_wgrad_stem_c8_kernel", 1, 1}, {"conv3x3_wgrad_c8_kernel", 2, 1}, {"conv3x3_wgrad_c8w_kernel", 3, 5}, {"conv3x3_wgrad_c8i_kernel", 3, 5},
+    {"conv3x3_wgrad_mfma_kernel", 3, 4}, {"conv3x3_wgrad_lp_kernel", 3, 4}, {"conv3x3_wgrad_lp2_kernel", 1, 1}, {"conv3x3_wgrad_smallcin_kernel", 0, 0},
+    {"conv3x3_wgrad_direct_kernel", 0, 0},
+};
+enum { KR_SPLITK = 1, KR_FIXUP = 2, KR_CHANNEL_SUMS = 4 };      // the weight gradient's reduction: a reduction launch / in the kernel / + dbias launch
+struct KernelChoice { int fam; int t[5]; int red; };
+inline KernelChoice kchoice(int fam, int t0 = 0, int t1 = 0, int t2 = 0, int t3 = 0, int t4 = 0) { return KernelChoice{fam, {t0, t1, t2, t3, t4}, 0}; }
+// "conv3x3_igemm_c8_kernel<3, 0, false, 4, 3>" (rocprofv3's spelling of the instance), + " + splitk_reduce" / " + splitk_fixup" / " + channel_sums"
+int kernel_name(const KernelChoice& k, char* buf, int len) {
+    const KernelFamilyInfo& f = KFAM[k.fam];
+    char tmp[160];
+    int n = snprintf(tmp, sizeof tmp, "%s", f.name);
+    for (int i = 0; i < f.nargs; ++i) {
+        const char* sep = i ? ", " : "<";
+        if (f.bools >> i & 1) n += snprintf(tmp + n, sizeof tmp - n, "%s%s", sep, k.t[i] ? "true" : "false");
+        else n += snprintf(tmp + n, sizeof tmp - n, "%s%d", sep, k.t[i]);
+    }
+    if (f.nargs) n += snprintf(tmp + n, sizeof tmp - n, ">");
+    if (k.red & KR_SPLITK) n += snprintf(tmp + n, sizeof tmp - n, " + splitk_reduce");
+    if (k.red & KR_FIXUP) n += snprintf(tmp + n, sizeof tmp - n, " + splitk_fixup");
+    if (k.red & KR_CHANNEL_SUMS) n += snprintf(tmp + n, sizeof tmp - n, " + channel_sums");
+    if (!buf || len <= n) return MTBC_E_BADARG;
+    memcpy(buf, tmp, (size_t)n + 1);
+    return MTBC_OK;
 }
 
 // geometry of an igemm launch: map geometry, pixel tiles, channel tiles per block, 8-wave (16 x 32 pixel) blocks, LDS-ring kernel
@@ -3564,7 +3608,7 @@ IgemmPlan plan_igemm(int N, int H, int W, int rows, int compute, bool c8, bool a
 // c8: the tensor read is 16-bit channel-blocked (MTBC_LAYOUT_C8); o8: so is the tensor written (+ optional epilogue statistics)
 int run_igemm(int N, int H, int W, int red, int rows, const SegTable& in, const SegTable& out, const float* wp,
               const float* bias, int compute, hipStream_t st, bool c8 = false, int o8 = 0, float* stats = nullptr,
-              const mtbc_conv3x3_args* nb = nullptr) {
+              const mtbc_conv3x3_args* nb = nullptr, KernelChoice* query = nullptr) {
     ConvP p;
 #ifdef MTBC_PROBES
     p.ts = nullptr;
@@ -3580,41 +3624,48 @@ int run_igemm(int N, int H, int W, int red, int rows, const SegTable& in, const 
     const IgemmPlan q = plan_igemm(N, H, W, rows, compute, c8, o8 != 2, red);      // (the norm-backward epilogue: neither the 8-wave nor the ring variant)
     const int geo = q.geo, MT = q.MT, mblocks = q.mblocks;
     p.mtiles = q.mtiles; p.tiles_x = q.tiles_x; p.tiles_y = q.tiles_y; p.ntiles = q.ntiles;
-    if (c8 && q.ring) {
-        if (o8 == 3) return geo == 0 ? launch_igemm_c8_ring_mt<0, 3>(MT, p, mblocks, false, st) : launch_igemm_c8_ring_mt<1, 3>(MT, p, mblocks, false, st);
-        if (o8 == 1) return geo == 0 ? launch_igemm_c8_ring_mt<0, 1>(MT, p, mblocks, compute == 2, st) : launch_igemm_c8_ring_mt<1, 1>(MT, p, mblocks, compute == 2, st);
-        return geo == 0 ? launch_igemm_c8_ring_mt<0, 0>(MT, p, mblocks, compute == 2, st) : launch_igemm_c8_ring_mt<1, 0>(MT, p, mblocks, compute == 2, st);
+    // the instance: O8 = 3 reads bf16 operands (F16 = false) and stores fp16
+    const bool f16 = compute == 2 && o8 != 3;
+    KernelChoice k;
+    if (c8 && q.ring) k = kchoice(KF_IGEMM_C8_RING, MT, geo, f16, o8, 3);
+    else if (c8 && q.nw8) k = kchoice(KF_IGEMM_C8, 2, 0, f16, 8, o8);
+    else if (c8) k = kchoice(KF_IGEMM_C8, MT, geo, f16, 4, o8);
+    else if (compute != 0) k = kchoice(KF_IGEMM_LP, MT, geo, f16);
+    else {
+        static const bool nodma = mtbc_probe_set("MTBC_NODMA");
+        static const int ring_env = mtbc_probe_int("MTBC_RING", 0);
+        constexpr int RING = 2;     // measured: occupancy (3 blocks/CU) beats the deeper 3-slot prefetch on every layer
+        k = (geo != 2 && !nodma) ? kchoice(KF_IGEMM_DMA, MT, geo, ring_env ? ring_env : RING) : kchoice(KF_IGEMM, MT, geo);
     }
-    if (c8) {
-        if (q.nw8) return o8 == 3 ? launch_igemm_c8<2, 0, 8, 3>(p, mblocks, false, st)
-                        : o8 == 1 ? launch_igemm_c8<2, 0, 8, 1>(p, mblocks, compute == 2, st) : launch_igemm_c8<2, 0, 8, 0>(p, mblocks, compute == 2, st);
-        if (o8 == 3) {
-            if (geo == 0) return launch_igemm_c8_mt<0, 3>(MT, p, mblocks, false, st);
-            if (geo == 1) return launch_igemm_c8_mt<1, 3>(MT, p, mblocks, false, st);
-            return launch_igemm_c8_mt<2, 3>(MT, p, mblocks, false, st);
-        }
-        if (o8 == 2) {
-            if (geo == 0) return launch_igemm_c8_mt<0, 2>(MT, p, mblocks, compute == 2, st);
-            if (geo == 1) return launch_igemm_c8_mt<1, 2>(MT, p, mblocks, compute == 2, st);
-            return launch_igemm_c8_mt<2, 2>(MT, p, mblocks, compute == 2, st);
-        }
-        if (o8 == 1) {
-            if (geo == 0) return launch_igemm_c8_mt<0, 1>(MT, p, mblocks, compute == 2, st);
-            if (geo == 1) return launch_igemm_c8_mt<1, 1>(MT, p, mblocks, compute == 2, st);
-            return launch_igemm_c8_mt<2, 1>(MT, p, mblocks, compute == 2, st);
-        }
-        if (geo == 0) return launch_igemm_c8_mt<0, 0>(MT, p, mblocks, compute == 2, st);
-        if (geo == 1) return launch_igemm_c8_mt<1, 0>(MT, p, mblocks, compute == 2, st);
-        return launch_igemm_c8_mt<2, 0>(MT, p, mblocks, compute == 2, st);
+    if (query) { *query = k; return MTBC_OK; }
+    const int kMT = k.t[0], kgeo = k.t[1];
+    const bool kf16 = k.t[2] != 0;
+    switch (k.fam) {
+    case KF_IGEMM_C8_RING: {
+        const int O8 = k.t[3];
+        if (O8 == 3) return kgeo == 0 ? launch_igemm_c8_ring_mt<0, 3>(kMT, p, mblocks, kf16, st) : launch_igemm_c8_ring_mt<1, 3>(kMT, p, mblocks, kf16, st);
+        if (O8 == 1) return kgeo == 0 ? launch_igemm_c8_ring_mt<0, 1>(kMT, p, mblocks, kf16, st) : launch_igemm_c8_ring_mt<1, 1>(kMT, p, mblocks, kf16, st);
+        return kgeo == 0 ? launch_igemm_c8_ring_mt<0, 0>(kMT, p, mblocks, kf16, st) : launch_igemm_c8_ring_mt<1, 0>(kMT, p, mblocks, kf16, st);
     }
-    if (compute != 0) {
-        if (geo == 0) return launch_igemm_lp_mt<0>(MT, p, mblocks, compute == 2, st);
-        if (geo == 1) return launch_igemm_lp_mt<1>(MT, p, mblocks, compute == 2, st);
-        return launch_igemm_lp_mt<2>(MT, p, mblocks, compute == 2, st);
+    case KF_IGEMM_C8: {
+        const int NW = k.t[3], O8 = k.t[4];
+        if (NW == 8) return O8 == 3 ? launch_igemm_c8<2, 0, 8, 3>(p, mblocks, kf16, st)
+                          : O8 == 1 ? launch_igemm_c8<2, 0, 8, 1>(p, mblocks, kf16, st) : launch_igemm_c8<2, 0, 8, 0>(p, mblocks, kf16, st);
+        if (kgeo == 0) return launch_igemm_c8_o8<0>(kMT, O8, p, mblocks, kf16, st);
+        if (kgeo == 1) return launch_igemm_c8_o8<1>(kMT, O8, p, mblocks, kf16, st);
+        return launch_igemm_c8_o8<2>(kMT, O8, p, mblocks, kf16, st);
     }
-    if (geo == 0) return launch_igemm_mt<0>(MT, p, mblocks, st);
-    if (geo == 1) return launch_igemm_mt<1>(MT, p, mblocks, st);
-    return launch_igemm_mt<2>(MT, p, mblocks, st);
+    case KF_IGEMM_LP:
+        if (kgeo == 0) return launch_igemm_lp_mt<0>(kMT, p, mblocks, kf16, st);
+        if (kgeo == 1) return launch_igemm_lp_mt<1>(kMT, p, mblocks, kf16, st);
+        return launch_igemm_lp_mt<2>(kMT, p, mblocks, kf16, st);
+    default: {
+        const int ring = k.fam == KF_IGEMM_DMA ? k.t[2] : 0;
+        if (kgeo == 0) return launch_igemm_mt<0>(kMT, p, mblocks, ring, st);
+        if (kgeo == 1) return launch_igemm_mt<1>(kMT, p, mblocks, ring, st);
+        return launch_igemm_mt<2>(kMT, p, mblocks, ring, st);
+    }
+    }
 }
 
 struct WgPlan { bool mfma; bool smallcin; int cot; int geo, tiles_x, tiles_y, total_tiles, nsplit, tiles_per_split, coblocks, ciblocks; size_t partial_elems, dbias_elems; bool c8w, c8i, pack24; int cit, segs, seg_tiles, depth; };
@@ -3857,14 +3908,14 @@ static int check_conv(const mtbc_conv3x3_args* a) {
     return MTBC_OK;
 }
 
-int mtbc_conv3x3_fwd(const mtbc_conv3x3_args* a, void* stream) {
+// query != NULL: validate, fill in the kernel choice and return without touching the device (mtbc_conv3x3_kernel_name)
+static int conv_fwd(const mtbc_conv3x3_args* a, hipStream_t st, KernelChoice* query) {
     int rc = check_conv(a); if (rc) return rc;
     if (!a->out || (!a->w && !a->w_packed)) return MTBC_E_BADARG;
     SegTable in, out;
     rc = make_segtable(a->in, a->n_in, a->Cin, &in); if (rc) return rc;
     mtbc_seg o{a->out, (int64_t)a->Cout * a->H * a->W, a->Cout, a->out_accumulate ? 1 : 0};
     rc = make_segtable(&o, 1, a->Cout, &out); if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
     if (a->out_accumulate && a->operand_layout != MTBC_LAYOUT_C8) return MTBC_E_UNSUPPORTED;
     const bool stem = a->Cin == 1 && a->n_in == 1 && !a->force_direct && a->W % 4 == 0 && a->in[0].batch_stride % 4 == 0 &&
                       (reinterpret_cast<uintptr_t>(a->in[0].ptr) & 15) == 0 && (reinterpret_cast<uintptr_t>(a->out) & 15) == 0;
@@ -3875,7 +3926,9 @@ int mtbc_conv3x3_fwd(const mtbc_conv3x3_args* a, void* stream) {
         if (a->stats_partial && (reinterpret_cast<uintptr_t>(a->stats_partial) & 15)) return MTBC_E_BADARG;
         const dim3 grid(cdiv(a->H * (a->W / 4), 128), a->Cout / 8, a->N);
         unsigned short* o16 = reinterpret_cast<unsigned short*>(a->out);
-        if (a->compute == 2 || a->out_type == 2)
+        const KernelChoice k = kchoice(KF_STEM_FWD_C8, a->compute == 2 || a->out_type == 2);
+        if (query) { *query = k; return MTBC_OK; }
+        if (k.t[0])
             hipLaunchKernelGGL(conv3x3_stem_fwd_c8_kernel<true>, grid, dim3(128), 0, st, a->in[0].ptr, (long long)a->in[0].batch_stride, a->w, a->bias, o16, a->stats_partial, a->N, a->H, a->W, a->Cout);
         else
             hipLaunchKernelGGL(conv3x3_stem_fwd_c8_kernel<false>, grid, dim3(128), 0, st, a->in[0].ptr, (long long)a->in[0].batch_stride, a->w, a->bias, o16, a->stats_partial, a->N, a->H, a->W, a->Cout);
@@ -3898,21 +3951,23 @@ int mtbc_conv3x3_fwd(const mtbc_conv3x3_args* a, void* stream) {
             if (!o8 || of16 || !a->norm_z || !a->norm_mean || !a->norm_rstd || !a->stats_partial || a->bias || (a->norm_gamma == nullptr) != (a->norm_beta == nullptr)) return MTBC_E_BADARG;
             if ((reinterpret_cast<uintptr_t>(a->norm_z) | reinterpret_cast<uintptr_t>(a->norm_mean) | reinterpret_cast<uintptr_t>(a->norm_rstd) |
                  reinterpret_cast<uintptr_t>(a->norm_gamma) | reinterpret_cast<uintptr_t>(a->norm_beta)) & 15) return MTBC_E_BADARG;
-            return run_igemm(a->N, a->H, a->W, a->Cin, a->Cout, in, out, a->w_packed, nullptr, a->compute, st, true, 2, a->stats_partial, a);
+            return run_igemm(a->N, a->H, a->W, a->Cin, a->Cout, in, out, a->w_packed, nullptr, a->compute, st, true, 2, a->stats_partial, a, query);
         }
-        return run_igemm(a->N, a->H, a->W, a->Cin, a->Cout, in, out, a->w_packed, a->bias, a->compute, st, true, of16 ? 3 : (o8 ? 1 : 0), a->stats_partial);
+        return run_igemm(a->N, a->H, a->W, a->Cin, a->Cout, in, out, a->w_packed, a->bias, a->compute, st, true, of16 ? 3 : (o8 ? 1 : 0), a->stats_partial, nullptr, query);
     }
     if (a->stats_partial || a->norm_z || a->out_partial) return MTBC_E_UNSUPPORTED;
     if (a->operand_layout != MTBC_LAYOUT_PLANAR) return MTBC_E_BADARG;
     if (a->w_packed && !a->force_direct && mfma_ok(a->in, a->n_in, a->H, a->W))
-        return run_igemm(a->N, a->H, a->W, a->Cin, a->Cout, in, out, a->w_packed, a->bias, a->compute, st);
+        return run_igemm(a->N, a->H, a->W, a->Cin, a->Cout, in, out, a->w_packed, a->bias, a->compute, st, false, 0, nullptr, nullptr, query);
     if (!a->w) return MTBC_E_BADARG;
     if (stem) {
+        if (query) { *query = kchoice(KF_STEM_FWD); return MTBC_OK; }
         hipLaunchKernelGGL(conv3x3_stem_fwd_kernel, dim3(cdiv(a->H * (a->W / 4), 128), cdiv(a->Cout, 8), a->N), dim3(128), 0, st,
                            a->in[0].ptr, (long long)a->in[0].batch_stride, a->w, a->bias, a->out, a->N, a->H, a->W, a->Cout);
         MTBC_CHECK_LAUNCH();
         return MTBC_OK;
     }
+    if (query) { *query = kchoice(KF_DIRECT); return MTBC_OK; }
     DirP p; p.N = a->N; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout; p.in = in; p.out = out;
     p.w = a->w; p.bias = a->bias; p.mode = 0; p.wCin = a->Cin;
     hipLaunchKernelGGL(conv3x3_direct_kernel, dim3(cdiv(a->H * a->W, 128), cdiv(a->Cout, 8), a->N), dim3(128), 0, st, p);
@@ -3920,14 +3975,15 @@ int mtbc_conv3x3_fwd(const mtbc_conv3x3_args* a, void* stream) {
     return MTBC_OK;
 }
 
-int mtbc_conv3x3_dgrad(const mtbc_conv3x3_args* a, void* stream) {
+int mtbc_conv3x3_fwd(const mtbc_conv3x3_args* a, void* stream) { return conv_fwd(a, (hipStream_t)stream, nullptr); }
+
+static int conv_dgrad(const mtbc_conv3x3_args* a, hipStream_t st, KernelChoice* query) {
     int rc = check_conv(a); if (rc) return rc;
     if (!a->dout || (!a->w && !a->w_packed)) return MTBC_E_BADARG;
     SegTable in, out;
     mtbc_seg g{const_cast<float*>(a->dout), (int64_t)a->Cout * a->H * a->W, a->Cout, 0};
     rc = make_segtable(&g, 1, a->Cout, &in); if (rc) return rc;
     rc = make_segtable(a->in, a->n_in, a->Cin, &out); if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
     if (a->operand_layout == MTBC_LAYOUT_C8) {
         if (!a->w_packed || (a->compute != 1 && a->compute != 2) || !c8_segs_ok(&g, 1)) return MTBC_E_BADARG;
         if (!mfma_ok(a->in, a->n_in, a->H, a->W)) return MTBC_E_UNSUPPORTED;      // the fp32 planar dx segments: 16-byte stores
@@ -3937,21 +3993,24 @@ int mtbc_conv3x3_dgrad(const mtbc_conv3x3_args* a, void* stream) {
             if (a->in[i].accumulate == 3) ++n3;
         }
         if (n3 != 0 && (n3 != a->n_in || !c8_segs_ok(a->in, a->n_in))) return MTBC_E_BADARG;      // channel-blocked dx: every segment or none
-        return run_igemm(a->N, a->H, a->W, a->Cout, a->Cin, in, out, a->w_packed, nullptr, a->compute, st, true, n3 != 0 ? 1 : 0);
+        return run_igemm(a->N, a->H, a->W, a->Cout, a->Cin, in, out, a->w_packed, nullptr, a->compute, st, true, n3 != 0 ? 1 : 0, nullptr, nullptr, query);
     }
     if (a->operand_layout != MTBC_LAYOUT_PLANAR) return MTBC_E_BADARG;
     for (int i = 0; i < a->n_in; ++i)
         if (a->in[i].accumulate >= 2) return MTBC_E_UNSUPPORTED;      // 16-bit dx segments: channel-blocked dgrad only
     bool ok = a->w_packed && !a->force_direct && mfma_ok(&g, 1, a->H, a->W) && a->Cout % KC == 0;
     for (int i = 0; ok && i < a->n_in; ++i) ok = a->in[i].ptr != nullptr && a->in[i].channels % 4 == 0;
-    if (ok) return run_igemm(a->N, a->H, a->W, a->Cout, a->Cin, in, out, a->w_packed, nullptr, a->compute, st);
+    if (ok) return run_igemm(a->N, a->H, a->W, a->Cout, a->Cin, in, out, a->w_packed, nullptr, a->compute, st, false, 0, nullptr, nullptr, query);
     if (!a->w) return MTBC_E_BADARG;
+    if (query) { *query = kchoice(KF_DIRECT); return MTBC_OK; }
     DirP p; p.N = a->N; p.H = a->H; p.W = a->W; p.Cin = a->Cout; p.Cout = a->Cin; p.in = in; p.out = out;
     p.w = a->w; p.bias = nullptr; p.mode = 1; p.wCin = a->Cin;
     hipLaunchKernelGGL(conv3x3_direct_kernel, dim3(cdiv(a->H * a->W, 128), cdiv(a->Cin, 8), a->N), dim3(128), 0, st, p);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
+
+int mtbc_conv3x3_dgrad(const mtbc_conv3x3_args* a, void* stream) { return conv_dgrad(a, (hipStream_t)stream, nullptr); }
 
 int32_t mtbc_conv3x3_stats_slots(const mtbc_conv3x3_args* a) {
     if (check_conv(a) || a->out_layout != MTBC_LAYOUT_C8 || (a->compute != 1 && a->compute != 2)) return 0;
@@ -3976,14 +4035,13 @@ size_t mtbc_conv3x3_wgrad_sync_bytes(const mtbc_conv3x3_args* a) {
     return (size_t)splitk_fix_plan(w.nsplit, &f) * w.coblocks * w.ciblocks * sizeof(int);
 }
 
-int mtbc_conv3x3_wgrad(const mtbc_conv3x3_args* a, void* stream) {
+static int conv_wgrad(const mtbc_conv3x3_args* a, hipStream_t st, KernelChoice* query) {
     int rc = check_conv(a); if (rc) return rc;
     if (!a->dout || !a->dw) return MTBC_E_BADARG;
     SegTable in;
     rc = make_segtable(a->in, a->n_in, a->Cin, &in); if (rc) return rc;
     WgPlan w = plan_wgrad(a);
     if (!a->workspace || a->workspace_bytes < (w.partial_elems + w.dbias_elems) * sizeof(float)) return MTBC_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
     float* partial = reinterpret_cast<float*>(a->workspace);
     const size_t wel = (size_t)a->Cout * a->Cin * 9;
     if (a->operand_layout == MTBC_LAYOUT_C8 && a->Cin == 1) {
@@ -3993,7 +4051,10 @@ int mtbc_conv3x3_wgrad(const mtbc_conv3x3_args* a, void* stream) {
         const int S = w.nsplit / a->N;
         const dim3 grid(a->N * (a->Cout / 8) * S);
         const unsigned short* dz8 = reinterpret_cast<const unsigned short*>(a->dout);
-        if (a->compute == 2) hipLaunchKernelGGL(conv3x3_wgrad_stem_c8_kernel<true>, grid, dim3(256), 0, st, a->in[0].ptr, (long long)a->in[0].batch_stride, dz8, partial, a->N, a->H, a->W, a->Cout, S);
+        KernelChoice k = kchoice(KF_WGRAD_STEM_C8, a->compute == 2);
+        k.red = KR_SPLITK;
+        if (query) { *query = k; return MTBC_OK; }
+        if (k.t[0]) hipLaunchKernelGGL(conv3x3_wgrad_stem_c8_kernel<true>, grid, dim3(256), 0, st, a->in[0].ptr, (long long)a->in[0].batch_stride, dz8, partial, a->N, a->H, a->W, a->Cout, S);
         else hipLaunchKernelGGL(conv3x3_wgrad_stem_c8_kernel<false>, grid, dim3(256), 0, st, a->in[0].ptr, (long long)a->in[0].batch_stride, dz8, partial, a->N, a->H, a->W, a->Cout, S);
         MTBC_CHECK_LAUNCH();
         return mtbc_i_splitk_reduce(partial, a->dw, w.nsplit, wel, a->accumulate_dw, st);
@@ -4020,6 +4081,10 @@ int mtbc_conv3x3_wgrad(const mtbc_conv3x3_args* a, void* stream) {
         p.ciblocks = w.ciblocks; p.coblocks = w.coblocks; p.cit = w.cit; p.segs = w.segs; p.seg_tiles = w.seg_tiles; p.depth = w.depth;
         { static const int hk = mtbc_probe_int("MTBC_C8W_HACK", 0); p.hack = hk; }
         const dim3 grid = (w.c8w || w.c8i) ? dim3(w.nsplit * w.coblocks * w.ciblocks) : dim3(w.nsplit, w.coblocks * w.ciblocks);
+        const bool f16 = a->compute == 2, bias = a->dbias != nullptr;
+        KernelChoice k = w.c8i ? kchoice(KF_WGRAD_C8I, f16, w.cot, bias) : w.c8w ? kchoice(KF_WGRAD_C8W, f16, w.cot, bias) : kchoice(KF_WGRAD_C8, f16, w.geo);
+        k.red = direct ? 0 : p.fix.ctr ? KR_FIXUP : KR_SPLITK;
+        if (query) { *query = k; return MTBC_OK; }
 #ifdef MTBC_PROBES
         // MTBC_WG_TS=1: phase timestamps of every block (thread 0) of the 32 x 32 / wide-block weight-gradient kernels, printed after the launch
         static const int wts_env = mtbc_probe_int("MTBC_WG_TS", 0);
@@ -4032,7 +4097,7 @@ int mtbc_conv3x3_wgrad(const mtbc_conv3x3_args* a, void* stream) {
             p.ts = wdts;
         }
 #endif
-        if (w.c8i) {
+        if (k.fam == KF_WGRAD_C8I) {
             const size_t lds = c8i_lds_bytes(w.cit, w.cot);
             const dim3 gridi(w.nsplit * w.coblocks * w.ciblocks);
 #define MTBC_C8I_LAUNCH(F16_, COT_, BIAS_)                                                                                             \
@@ -4040,7 +4105,7 @@ int mtbc_conv3x3_wgrad(const mtbc_conv3x3_args* a, void* stream) {
                 MTBC_ENSURE_DYN_LDS((&conv3x3_wgrad_c8i_kernel<F16_, COT_, BIAS_>), 160 * 1024);                                      \
                 hipLaunchKernelGGL((conv3x3_wgrad_c8i_kernel<F16_, COT_, BIAS_>), gridi, dim3(512), lds, st, p);                      \
             } while (0)
-            const int sel = (a->compute == 2 ? 4 : 0) + (w.cot == 3 ? 2 : 0) + (a->dbias ? 1 : 0);
+            const int sel = (k.t[0] ? 4 : 0) + (k.t[1] == 3 ? 2 : 0) + (k.t[2] ? 1 : 0);
             switch (sel) {
             case 0: MTBC_C8I_LAUNCH(false, 2, false); break;
             case 1: MTBC_C8I_LAUNCH(false, 2, true); break;
@@ -4052,14 +4117,14 @@ int mtbc_conv3x3_wgrad(const mtbc_conv3x3_args* a, void* stream) {
             default: MTBC_C8I_LAUNCH(true, 3, true); break;
             }
 #undef MTBC_C8I_LAUNCH
-        } else if (w.c8w) {
+        } else if (k.fam == KF_WGRAD_C8W) {
             const size_t lds = c8w_lds_bytes(w.cit, w.cot, w.depth);
 #define MTBC_C8W_LAUNCH(F16_, COT_, BIAS_)                                                                                             \
             do {                                                                                                                       \
                 MTBC_ENSURE_DYN_LDS((&conv3x3_wgrad_c8w_kernel<F16_, COT_, BIAS_>), 160 * 1024);      /* up to 160 KB of dynamic LDS */   \
                 hipLaunchKernelGGL((conv3x3_wgrad_c8w_kernel<F16_, COT_, BIAS_>), grid, dim3(512), lds, st, p);                       \
             } while (0)
-            const int sel = (a->compute == 2 ? 4 : 0) + (w.cot == 3 ? 2 : 0) + (a->dbias ? 1 : 0);
+            const int sel = (k.t[0] ? 4 : 0) + (k.t[1] == 3 ? 2 : 0) + (k.t[2] ? 1 : 0);
             switch (sel) {
             case 0: MTBC_C8W_LAUNCH(false, 2, false); break;
             case 1: MTBC_C8W_LAUNCH(false, 2, true); break;
@@ -4071,11 +4136,11 @@ int mtbc_conv3x3_wgrad(const mtbc_conv3x3_args* a, void* stream) {
             default: MTBC_C8W_LAUNCH(true, 3, true); break;
             }
 #undef MTBC_C8W_LAUNCH
-        } else if (w.geo == 1) {
-            if (a->compute == 2) hipLaunchKernelGGL((conv3x3_wgrad_c8_kernel<true, 1>), grid, dim3(256), C8W_LDS, st, p);
+        } else if (k.t[1] == 1) {
+            if (k.t[0]) hipLaunchKernelGGL((conv3x3_wgrad_c8_kernel<true, 1>), grid, dim3(256), C8W_LDS, st, p);
             else hipLaunchKernelGGL((conv3x3_wgrad_c8_kernel<false, 1>), grid, dim3(256), C8W_LDS, st, p);
         } else {
-            if (a->compute == 2) hipLaunchKernelGGL((conv3x3_wgrad_c8_kernel<true, 0>), grid, dim3(256), C8W_LDS, st, p);
+            if (k.t[0]) hipLaunchKernelGGL((conv3x3_wgrad_c8_kernel<true, 0>), grid, dim3(256), C8W_LDS, st, p);
             else hipLaunchKernelGGL((conv3x3_wgrad_c8_kernel<false, 0>), grid, dim3(256), C8W_LDS, st, p);
         }
         MTBC_CHECK_LAUNCH();
@@ -4105,11 +4170,21 @@ int mtbc_conv3x3_wgrad(const mtbc_conv3x3_args* a, void* stream) {
             }
         }
 #endif
-        if (direct || p.fix.ctr) return MTBC_OK;
+        if (!(k.red & KR_SPLITK)) return MTBC_OK;
         // one row per split = the weight-gradient partial followed by the bias-gradient partial: ONE reduction launch for both
         return mtbc_i_splitk_reduce2(partial, a->dw, a->dbias, w.nsplit, wel, a->dbias ? (size_t)a->Cout : 0, a->accumulate_dw, st);
     }
     if (a->operand_layout != MTBC_LAYOUT_PLANAR) return MTBC_E_BADARG;
+    static const int lowp_env = mtbc_probe_int("MTBC_LOWP", -1);
+    const int lowp = lowp_env >= 0 ? lowp_env : a->compute;       // 0 fp32 (exact), 1 bf16, 2 fp16 MFMA operands
+    static const bool lp1 = mtbc_probe_set("MTBC_WGRAD_LP1");      // A/B: first-generation 16-bit wgrad
+    KernelChoice k;
+    if (!w.mfma) k = kchoice(w.smallcin ? KF_WGRAD_SMALLCIN : KF_WGRAD_DIRECT);
+    else if (w.geo == 0 && w.cot == 2 && lowp != 0 && !lp1) k = kchoice(KF_WGRAD_LP2, lowp == 2);
+    else if (lowp == 1 || lowp == 2) k = kchoice(KF_WGRAD_LP, w.geo, w.cot, lowp == 2);
+    else k = kchoice(KF_WGRAD_MFMA, w.geo, w.cot, w.pack24);
+    k.red = KR_SPLITK | (a->dbias ? KR_CHANNEL_SUMS : 0);
+    if (query) { *query = k; return MTBC_OK; }
     if (w.mfma) {
         WgP p; p.N = a->N; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout; p.in = in; p.dz = a->dout;
         p.partial = partial; p.tiles_x = w.tiles_x; p.tiles_y = w.tiles_y; p.total_tiles = w.total_tiles;
@@ -4131,29 +4206,26 @@ int mtbc_conv3x3_wgrad(const mtbc_conv3x3_args* a, void* stream) {
 #endif
         const int zch = 16 * w.cot;
         const dim3 blk(128 * w.cot);
-        static const int lowp_env = mtbc_probe_int("MTBC_LOWP", -1);
-        const int lowp = lowp_env >= 0 ? lowp_env : a->compute;       // 0 fp32 (exact), 1 bf16, 2 fp16 MFMA operands
 #define MTBC_WG_LAUNCH(GEO_, COT_)                                                                                         \
         do {                                                                                                               \
-            if (lowp == 1) hipLaunchKernelGGL((conv3x3_wgrad_lp_kernel<GEO_, COT_, false>), grid, blk,                     \
+            if (k.fam == KF_WGRAD_LP && !k.t[2]) hipLaunchKernelGGL((conv3x3_wgrad_lp_kernel<GEO_, COT_, false>), grid, blk, \
                                               (32 * WGeoLP<GEO_>::PSX + zch * PSZ_LP) * sizeof(float), st, p);            \
-            else if (lowp == 2) hipLaunchKernelGGL((conv3x3_wgrad_lp_kernel<GEO_, COT_, true>), grid, blk,                 \
+            else if (k.fam == KF_WGRAD_LP) hipLaunchKernelGGL((conv3x3_wgrad_lp_kernel<GEO_, COT_, true>), grid, blk,       \
                                                    (32 * WGeoLP<GEO_>::PSX + zch * PSZ_LP) * sizeof(float), st, p);       \
-            else if (w.pack24) hipLaunchKernelGGL((conv3x3_wgrad_mfma_kernel<GEO_, COT_, true>), grid, blk,                \
+            else if (k.t[2]) hipLaunchKernelGGL((conv3x3_wgrad_mfma_kernel<GEO_, COT_, true>), grid, blk,                  \
                                                   (32 * WGeo<GEO_>::PSX + zch * PSZ) * sizeof(float), st, p);              \
             else hipLaunchKernelGGL((conv3x3_wgrad_mfma_kernel<GEO_, COT_, false>), grid, blk,                             \
                                     (32 * WGeo<GEO_>::PSX + zch * PSZ) * sizeof(float), st, p);                            \
         } while (0)
-        static const bool lp1 = mtbc_probe_set("MTBC_WGRAD_LP1");      // A/B: first-generation 16-bit wgrad
-        if (w.geo == 0 && w.cot == 2 && lowp != 0 && !lp1) {
+        if (k.fam == KF_WGRAD_LP2) {
             MTBC_ENSURE_DYN_LDS((&conv3x3_wgrad_lp2_kernel<false>), 64 * 1024);
             MTBC_ENSURE_DYN_LDS((&conv3x3_wgrad_lp2_kernel<true>), 64 * 1024);
-            if (lowp == 2) hipLaunchKernelGGL((conv3x3_wgrad_lp2_kernel<true>), grid, dim3(256), W2_LDS, st, p);
+            if (k.t[0]) hipLaunchKernelGGL((conv3x3_wgrad_lp2_kernel<true>), grid, dim3(256), W2_LDS, st, p);
             else hipLaunchKernelGGL((conv3x3_wgrad_lp2_kernel<false>), grid, dim3(256), W2_LDS, st, p);
-        } else if (w.cot == 2) {
-            if (w.geo == 0) MTBC_WG_LAUNCH(0, 2); else if (w.geo == 1) MTBC_WG_LAUNCH(1, 2); else MTBC_WG_LAUNCH(2, 2);
+        } else if (k.t[1] == 2) {
+            if (k.t[0] == 0) MTBC_WG_LAUNCH(0, 2); else if (k.t[0] == 1) MTBC_WG_LAUNCH(1, 2); else MTBC_WG_LAUNCH(2, 2);
         } else {
-            if (w.geo == 0) MTBC_WG_LAUNCH(0, 3); else if (w.geo == 1) MTBC_WG_LAUNCH(1, 3); else MTBC_WG_LAUNCH(2, 3);
+            if (k.t[0] == 0) MTBC_WG_LAUNCH(0, 3); else if (k.t[0] == 1) MTBC_WG_LAUNCH(1, 3); else MTBC_WG_LAUNCH(2, 3);
         }
 #undef MTBC_WG_LAUNCH
         MTBC_CHECK_LAUNCH();
@@ -4176,18 +4248,31 @@ int mtbc_conv3x3_wgrad(const mtbc_conv3x3_args* a, void* stream) {
     } else {
         DirWgP p; p.N = a->N; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout; p.nsplit = w.nsplit;
         p.in = in; p.dz = a->dout; p.partial = partial;
-        if (w.smallcin)
+        if (k.fam == KF_WGRAD_SMALLCIN)
             hipLaunchKernelGGL(conv3x3_wgrad_smallcin_kernel, dim3(w.nsplit * a->Cout), dim3(256), 0, st, p);
         else
             hipLaunchKernelGGL(conv3x3_wgrad_direct_kernel, dim3(a->Cout * a->Cin, w.nsplit), dim3(256), 0, st, p);
         MTBC_CHECK_LAUNCH();
     }
     rc = mtbc_i_splitk_reduce(partial, a->dw, w.nsplit, wel, a->accumulate_dw, st); if (rc) return rc;
-    if (a->dbias) {
+    if (k.red & KR_CHANNEL_SUMS) {
         rc = mtbc_i_channel_sums(a->dout, partial + w.partial_elems, a->dbias, a->N, a->Cout, a->H * a->W, a->accumulate_dw, st);
         if (rc) return rc;
     }
     return MTBC_OK;
+}
+
+int mtbc_conv3x3_wgrad(const mtbc_conv3x3_args* a, void* stream) { return conv_wgrad(a, (hipStream_t)stream, nullptr); }
+
+int mtbc_conv3x3_kernel_name(const mtbc_conv3x3_args* a, int32_t op, char* buf, int32_t len) {
+    KernelChoice k{};
+    int rc;
+    if (op == MTBC_OP_CONV3_FWD) rc = conv_fwd(a, nullptr, &k);
+    else if (op == MTBC_OP_CONV3_DGRAD) rc = conv_dgrad(a, nullptr, &k);
+    else if (op == MTBC_OP_CONV3_WGRAD) rc = conv_wgrad(a, nullptr, &k);
+    else return MTBC_E_BADARG;
+    if (rc) return rc;
+    return kernel_name(k, buf, len);
 }
 
 int mtbc_c8_pack(const float* src, int64_t src_batch_stride, void* dst, int32_t N, int32_t C, int32_t HW, int32_t compute, void* stream) {

@@ -45,6 +45,65 @@ def _ws(nbytes: int, dev) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------ conv3x3
+def conv3x3_kernel_name(a: "L.Conv3x3Args", op: int) -> str:
+    """The kernel instance (+ weight-gradient reduction) that mtbc_conv3x3_fwd / _dgrad / _wgrad -- op = L.OP_CONV3_FWD / _DGRAD /
+    _WGRAD -- would launch for `a`: mtbc_conv3x3_kernel_name, host-only (no launch, no device access); raises what the call would."""
+    buf = C.create_string_buffer(256)
+    L.check(L.load().mtbc_conv3x3_kernel_name(C.byref(a), op, buf, len(buf)), "conv3x3_kernel_name")
+    return buf.value.decode()
+
+
+def conv3x3_case_args(op: int, N: int, segs: Sequence[int], Cout: int, H: int, W: int, compute: int = 0, c8: bool = False,
+                      out_c8: bool = False, out_fp16: bool = False, dx_c8: bool = False, bias: bool = True,
+                      in_kernel_reduce: bool = False) -> "L.Conv3x3Args":
+    """The argument struct the wrappers below fill for one call (fwd: conv3x3_fwd / conv3x3_fwd_c8 / conv3x3_stem_fwd_c8, dgrad:
+    conv3x3_dgrad / conv3x3_dgrad_c8 with the first segment overwritten and the others accumulated, wgrad: conv3x3_wgrad /
+    conv3x3_wgrad_c8), its tensor pointers distinct 16-byte aligned dummies that nothing may dereference: for conv3x3_kernel_name.
+    c8: operands in MTBC_LAYOUT_C8 (a 1-channel input stays fp32 planar: the stem); bias: fwd bias / wgrad dbias."""
+    lib = L.load()
+    ptr = iter(range(1 << 20, 1 << 30, 1 << 20))
+    a = L.Conv3x3Args()
+    a.N, a.H, a.W, a.Cin, a.Cout, a.n_in = N, H, W, sum(segs), Cout, len(segs)
+    for i, c in enumerate(segs):
+        a.in_[i].ptr, a.in_[i].batch_stride, a.in_[i].channels = next(ptr), c * H * W, c
+        if op == L.OP_CONV3_DGRAD:
+            a.in_[i].accumulate = 3 if dx_c8 else (1 if i else 0)
+    a.w, a.compute = next(ptr), compute
+    stem = sum(segs) == 1
+    if c8 and not (stem and op == L.OP_CONV3_FWD):
+        a.operand_layout = L.LAYOUT_C8
+    if op == L.OP_CONV3_FWD:
+        a.out, a.bias = next(ptr), (next(ptr) if bias else None)
+        if not stem:
+            a.w_packed = next(ptr)
+        if out_c8:
+            a.out_layout = L.LAYOUT_C8
+            a.out_type = 2 if out_fp16 else 0
+    elif op == L.OP_CONV3_DGRAD:
+        a.w_packed, a.dout = next(ptr), next(ptr)
+    else:
+        a.dout, a.dw, a.dbias = next(ptr), next(ptr), (next(ptr) if bias else None)
+        a.workspace, a.workspace_bytes = next(ptr), int(lib.mtbc_conv3x3_wgrad_workspace(C.byref(a)))
+        nsync = int(lib.mtbc_conv3x3_wgrad_sync_bytes(C.byref(a))) if in_kernel_reduce else 0
+        if nsync:
+            a.wgrad_sync, a.wgrad_sync_bytes = next(ptr), nsync
+    return a
+
+
+def conv3x3_case_kernel(op: int, *shape, **mode) -> str:
+    """conv3x3_kernel_name of conv3x3_case_args(op, *shape, **mode)."""
+    return conv3x3_kernel_name(conv3x3_case_args(op, *shape, **mode), op)
+
+
+# (op, instance) of every conv3x3 launch made through the wrappers below while this is a list (the reference tests record what they ran)
+launched: Optional[list] = None
+
+
+def _note(a, op: int) -> None:
+    if launched is not None:
+        launched.append((op, conv3x3_kernel_name(a, op)))
+
+
 def conv3x3_pack(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     _chk(w)
     lib = L.load()
@@ -111,6 +170,7 @@ def conv3x3_fwd(xs: Sequence[torch.Tensor], w: torch.Tensor, bias: Optional[torc
     out = torch.empty(N, w.shape[0], H, W, dtype=torch.float32, device=w.device)
     a.w_packed, a.bias, a.out, a.force_direct = _p(packed), _p(bias), out.data_ptr(), int(force_direct)
     a.compute = compute
+    _note(a, L.OP_CONV3_FWD)
     L.check(L.load().mtbc_conv3x3_fwd(C.byref(a), _s()), "conv3x3_fwd")
     return out
 
@@ -133,6 +193,7 @@ def conv3x3_stem_fwd_c8(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.T
             raise L.MtbcError("conv3x3_fwd: no epilogue statistics for this launch")
         part = torch.full((N, slots, w.shape[0], 2), float("nan"), dtype=torch.float32, device=w.device)
         a.stats_partial = part.data_ptr()
+    _note(a, L.OP_CONV3_FWD)
     L.check(L.load().mtbc_conv3x3_fwd(C.byref(a), _s()), "conv3x3_fwd(stem c8)")
     z = C8(out, (N, w.shape[0], H, W), 2 if out_fp16 else compute)
     return (z, part) if stats else z
@@ -146,6 +207,7 @@ def conv3x3_dgrad(dz: torch.Tensor, w: torch.Tensor, dxs: Sequence[torch.Tensor]
     _fill_segs(a.in_, dxs, accumulate)
     a.w_packed, a.dout, a.force_direct = _p(packed), dz.data_ptr(), int(force_direct)
     a.compute = compute
+    _note(a, L.OP_CONV3_DGRAD)
     L.check(L.load().mtbc_conv3x3_dgrad(C.byref(a), _s()), "conv3x3_dgrad")
 
 
@@ -166,6 +228,7 @@ def conv3x3_wgrad(xs: Sequence[torch.Tensor], dz: torch.Tensor, w_shape, want_bi
     nb = L.load().mtbc_conv3x3_wgrad_workspace(C.byref(a))
     ws = _ws(nb, dev)
     a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    _note(a, L.OP_CONV3_WGRAD)
     L.check(L.load().mtbc_conv3x3_wgrad(C.byref(a), _s()), "conv3x3_wgrad")
     return dw, db
 
@@ -240,6 +303,7 @@ def conv3x3_fwd_c8(xs: Sequence["C8"], w: torch.Tensor, bias: Optional[torch.Ten
             raise L.MtbcError("conv3x3_fwd: no epilogue statistics for this launch")
         part = torch.full((N, slots, w.shape[0], 2), float("nan"), dtype=torch.float32, device=w.device)
         a.stats_partial = part.data_ptr()
+    _note(a, L.OP_CONV3_FWD)
     L.check(L.load().mtbc_conv3x3_fwd(C.byref(a), _s()), "conv3x3_fwd(c8)")
     z = C8(out, (N, w.shape[0], H, W), 2 if out_fp16 else xs[0].compute) if out_c8 else out
     return (z, part) if stats else z
@@ -258,6 +322,7 @@ def conv3x3_dgrad_c8(dz: "C8", w: torch.Tensor, dxs: Sequence[torch.Tensor], acc
             a.in_[i].accumulate = 3
         a.w_packed, a.dout = packed.data_ptr(), dz.data.data_ptr()
         a.compute, a.operand_layout = dz.compute, L.LAYOUT_C8
+        _note(a, L.OP_CONV3_DGRAD)
         L.check(L.load().mtbc_conv3x3_dgrad(C.byref(a), _s()), "conv3x3_dgrad(c8 -> c8)")
         return
     _chk(w, *[d for i, d in enumerate(dxs) if not (i < len(accumulate) and accumulate[i] == 2)])
@@ -266,6 +331,7 @@ def conv3x3_dgrad_c8(dz: "C8", w: torch.Tensor, dxs: Sequence[torch.Tensor], acc
     _fill_segs(a.in_, dxs, accumulate)
     a.w_packed, a.dout = packed.data_ptr(), dz.data.data_ptr()
     a.compute, a.operand_layout = dz.compute, L.LAYOUT_C8
+    _note(a, L.OP_CONV3_DGRAD)
     L.check(L.load().mtbc_conv3x3_dgrad(C.byref(a), _s()), "conv3x3_dgrad(c8)")
 
 
@@ -304,6 +370,7 @@ def conv3x3_wgrad_c8(xs: Sequence["C8"], dz: "C8", w_shape, want_bias: bool = Fa
     if nsync:
         sync = wgrad_sync_buffer(dev, nsync)
         a.wgrad_sync, a.wgrad_sync_bytes = sync.data_ptr(), sync.numel() * 4
+    _note(a, L.OP_CONV3_WGRAD)
     L.check(L.load().mtbc_conv3x3_wgrad(C.byref(a), _s()), "conv3x3_wgrad(c8)")
     return dw, db
 

@@ -132,3 +132,100 @@ def test_adam_dynamic_scalars_are_torch_adams_scalar_path(lib):
     bad = L.AdamArgs()
     bad.step = 0
     assert lib.mtbc_adam_dynamic(C.byref(bad), C.byref((C.c_float * 3)())) != 0        # t >= 1, as mtbc_adam_step
+
+
+# (op, N, segs, Cout, H, W, mode) -> the instance mtbc_conv3x3_kernel_name names: the selection of plan_igemm / plan_wgrad made visible.
+# mode: compute, c8 (channel-blocked operands), out_c8 / out_fp16 (forward output channel-blocked / stored as fp16), bias, in-kernel reduce
+_BF16_O3 = dict(compute=1, c8=True, out_c8=True, out_fp16=True)
+_BF16 = dict(compute=1, c8=True)
+_F16_O1 = dict(compute=2, c8=True, out_c8=True)
+_F16 = dict(compute=2, c8=True)
+SELECTION = [
+    # configs[1] (U-Net++, bf16, N = 32): forward into fp16-stored outputs, dgrad / gathered-dgrad outputs in fp32 planes
+    ("fwd", 32, [24], 24, 256, 256, _BF16_O3, "conv3x3_igemm_c8_kernel<2, 0, false, 8, 3>"),
+    ("fwd", 32, [48], 48, 128, 128, _BF16_O3, "conv3x3_igemm_c8_kernel<3, 0, false, 4, 3>"),
+    ("fwd", 32, [96], 96, 64, 64, _BF16_O3, "conv3x3_igemm_c8_kernel<3, 0, false, 4, 3>"),
+    ("fwd", 32, [192], 192, 32, 32, _BF16_O3, "conv3x3_igemm_c8_kernel<3, 0, false, 4, 3>"),
+    ("fwd", 32, [384], 384, 16, 16, _BF16_O3, "conv3x3_igemm_c8_ring_kernel<3, 1, false, 3, 3>"),
+    ("fwd", 32, [384, 384, 384], 512, 16, 16, _BF16_O3, "conv3x3_igemm_c8_kernel<2, 1, false, 4, 3>"),
+    ("fwd", 32, [24, 24], 24, 256, 256, _BF16, "conv3x3_igemm_c8_kernel<2, 0, false, 8, 0>"),
+    ("dgrad", 32, [24], 24, 256, 256, _BF16, "conv3x3_igemm_c8_kernel<2, 0, false, 8, 0>"),
+    ("dgrad", 32, [48], 48, 128, 128, _BF16, "conv3x3_igemm_c8_kernel<3, 0, false, 4, 0>"),
+    ("dgrad", 32, [384, 384, 384], 512, 16, 16, _BF16, "conv3x3_igemm_c8_kernel<3, 1, false, 4, 0>"),
+    ("dgrad", 32, [384], 384, 16, 16, _BF16, "conv3x3_igemm_c8_ring_kernel<3, 1, false, 0, 3>"),
+    ("wgrad", 32, [24], 24, 256, 256, _BF16, "conv3x3_wgrad_c8_kernel<false, 0> + splitk_reduce"),
+    ("wgrad", 32, [48, 48], 48, 128, 128, dict(_BF16, bias=False), "conv3x3_wgrad_c8w_kernel<false, 3, false> + splitk_reduce"),
+    ("wgrad", 32, [48, 48], 48, 128, 128, dict(_BF16, in_kernel_reduce=True), "conv3x3_wgrad_c8w_kernel<false, 3, true> + splitk_fixup"),
+    ("wgrad", 32, [384], 384, 16, 16, dict(_BF16, bias=False), "conv3x3_wgrad_c8i_kernel<false, 3, false> + splitk_reduce"),
+    ("wgrad", 1, [64], 48, 16, 16, dict(_BF16, bias=False), "conv3x3_wgrad_c8i_kernel<false, 3, false>"),         # one split: stored into dw
+    ("fwd", 32, [1], 24, 256, 256, _BF16_O3, "conv3x3_stem_fwd_c8_kernel<true>"),
+    ("wgrad", 32, [1], 24, 256, 256, dict(_BF16, bias=False), "conv3x3_wgrad_stem_c8_kernel<false> + splitk_reduce"),
+    # configs[4] (fp16, N = 16, 512 x 512): conv outputs in fp16 channel-blocked (O8 = 1)
+    ("fwd", 16, [24], 24, 512, 512, _F16_O1, "conv3x3_igemm_c8_kernel<2, 0, true, 8, 1>"),
+    ("fwd", 16, [48], 48, 256, 256, _F16_O1, "conv3x3_igemm_c8_kernel<3, 0, true, 4, 1>"),
+    ("fwd", 16, [96, 96], 96, 32, 32, _F16_O1, "conv3x3_igemm_c8_ring_kernel<3, 0, true, 1, 3>"),
+    ("dgrad", 16, [24], 24, 512, 512, _F16, "conv3x3_igemm_c8_kernel<2, 0, true, 8, 0>"),
+    ("wgrad", 16, [24], 24, 512, 512, dict(_F16, bias=False), "conv3x3_wgrad_c8_kernel<true, 0> + splitk_reduce"),
+    # fp32 parity mode (N = 32): the DMA kernels, 2-slot ring
+    ("fwd", 32, [24], 24, 256, 256, {}, "conv3x3_igemm_dma_kernel<2, 0, 2>"),
+    ("fwd", 32, [48], 48, 128, 128, {}, "conv3x3_igemm_dma_kernel<3, 0, 2>"),
+    ("dgrad", 32, [384, 384, 384], 512, 16, 16, {}, "conv3x3_igemm_dma_kernel<3, 1, 2>"),
+    ("fwd", 32, [384, 384, 384], 512, 16, 16, {}, "conv3x3_igemm_dma_kernel<2, 1, 2>"),
+    ("fwd", 32, [384], 384, 16, 16, {}, "conv3x3_igemm_dma_kernel<1, 1, 2>"),
+    ("fwd", 5, [32], 80, 8, 8, {}, "conv3x3_igemm_kernel<1, 2>"),                     # 2 blocks of 4 images: MT lowered to 1
+    ("wgrad", 32, [24], 24, 256, 256, {}, "conv3x3_wgrad_mfma_kernel<0, 2, true> + splitk_reduce + channel_sums"),
+    ("wgrad", 32, [48], 48, 128, 128, {}, "conv3x3_wgrad_mfma_kernel<0, 3, true> + splitk_reduce + channel_sums"),
+    ("wgrad", 32, [96], 96, 64, 64, {}, "conv3x3_wgrad_mfma_kernel<0, 2, false> + splitk_reduce + channel_sums"),
+    ("fwd", 32, [1], 24, 256, 256, {}, "conv3x3_stem_fwd_kernel"),
+    ("wgrad", 32, [1], 24, 256, 256, {}, "conv3x3_wgrad_smallcin_kernel + splitk_reduce + channel_sums"),
+    # 16-bit operands in fp32 planes (the planar-staging kernels)
+    ("fwd", 2, [48], 48, 128, 128, dict(compute=1), "conv3x3_igemm_lp_kernel<1, 0, false>"),
+    ("wgrad", 2, [48], 48, 128, 128, dict(compute=2), "conv3x3_wgrad_lp2_kernel<true> + splitk_reduce + channel_sums"),
+    # edges: ntiles * mblocks just below / at 512 lowers MT (48 channels = 3 tiles; 32 x 8k maps: ntiles = N * k)
+    ("fwd", 7, [48], 48, 584, 32, _BF16_O3, "conv3x3_igemm_c8_kernel<2, 0, false, 4, 3>"),      # 511 tiles
+    ("fwd", 8, [48], 48, 512, 32, _BF16_O3, "conv3x3_igemm_c8_kernel<3, 0, false, 4, 3>"),      # 512
+    ("fwd", 7, [48], 48, 128, 128, _BF16_O3, "conv3x3_igemm_c8_kernel<2, 0, false, 4, 3>"),     # 448
+    ("fwd", 8, [48], 48, 128, 128, _BF16_O3, "conv3x3_igemm_c8_kernel<3, 0, false, 4, 3>"),     # 512
+    ("fwd", 7, [48], 48, 584, 32, {}, "conv3x3_igemm_dma_kernel<2, 0, 2>"),
+    ("fwd", 8, [48], 48, 512, 32, {}, "conv3x3_igemm_dma_kernel<3, 0, 2>"),
+    # t16 * mblocks at 2048 switches to the 8-wave blocks (MT = 2, 256 x 256: t16 = 128 N)
+    ("fwd", 15, [32], 32, 256, 256, _BF16_O3, "conv3x3_igemm_c8_kernel<2, 0, false, 4, 3>"),
+    ("fwd", 16, [32], 32, 256, 256, _BF16_O3, "conv3x3_igemm_c8_kernel<2, 0, false, 8, 3>"),
+    ("fwd", 16, [32], 32, 240, 256, _BF16_O3, "conv3x3_igemm_c8_kernel<2, 0, false, 4, 3>"),    # H = 240: t16 = 1920
+    ("fwd", 16, [32], 32, 248, 256, _BF16_O3, "conv3x3_igemm_c8_kernel<2, 0, false, 8, 3>"),    # H = 248: a ragged 16-row tile, t16 = 2048
+    ("fwd", 16, [32], 32, 264, 256, _BF16_O3, "conv3x3_igemm_c8_kernel<2, 0, false, 8, 3>"),    # H not a multiple of 16
+    # the ring kernel at ntiles * mb = 256 / 257 (16 x 16 maps: ntiles = N; 48 channels: mb = 1; reads >= 96 channels)
+    ("fwd", 256, [96], 48, 16, 16, _BF16_O3, "conv3x3_igemm_c8_ring_kernel<3, 1, false, 3, 3>"),
+    ("fwd", 257, [96], 48, 16, 16, _BF16_O3, "conv3x3_igemm_c8_kernel<2, 1, false, 4, 3>"),
+    ("fwd", 256, [64], 48, 16, 16, _BF16_O3, "conv3x3_igemm_c8_kernel<2, 1, false, 4, 3>"),     # reads < 96 channels: never the ring
+    # 8 x 8 maps, N % 4 != 0 (4 images per block)
+    ("fwd", 5, [32], 80, 8, 8, _BF16_O3, "conv3x3_igemm_c8_kernel<1, 2, false, 4, 3>"),
+    ("dgrad", 6, [64, 64], 320, 8, 8, _F16, "conv3x3_igemm_c8_kernel<1, 2, true, 4, 0>"),
+    ("fwd", 33, [320], 320, 8, 8, _F16_O1, "conv3x3_igemm_c8_kernel<1, 2, true, 4, 1>"),
+]
+
+
+@pytest.mark.parametrize("op,N,segs,Cout,H,W,mode,want", SELECTION)
+def test_conv3x3_kernel_selection(lib, op, N, segs, Cout, H, W, mode, want):
+    """mtbc_conv3x3_kernel_name (host only: the dummy tensor pointers are never dereferenced) names the instance each call launches;
+    a change of the selection shows up here, in review."""
+    from multi_task_breast_cancer_amd import ops
+    kind = {"fwd": L.OP_CONV3_FWD, "dgrad": L.OP_CONV3_DGRAD, "wgrad": L.OP_CONV3_WGRAD}[op]
+    assert ops.conv3x3_case_kernel(kind, N, segs, Cout, H, W, **mode) == want
+
+
+def test_conv3x3_kernel_name_refuses_what_the_call_refuses(lib):
+    from multi_task_breast_cancer_amd import ops
+    buf = C.create_string_buffer(256)
+    a = ops.conv3x3_case_args(L.OP_CONV3_FWD, 2, [8], 8, 8, 10, **_BF16)           # channel-blocked operands need W % 4 == 0
+    assert lib.mtbc_conv3x3_kernel_name(C.byref(a), L.OP_CONV3_FWD, buf, 256) == -5
+    a = ops.conv3x3_case_args(L.OP_CONV3_FWD, 2, [8], 12, 16, 16, **_BF16_O3)      # channel-blocked output needs Cout % 8 == 0
+    assert lib.mtbc_conv3x3_kernel_name(C.byref(a), L.OP_CONV3_FWD, buf, 256) == -2
+    a = ops.conv3x3_case_args(L.OP_CONV3_WGRAD, 2, [48], 48, 32, 32, **_BF16)
+    a.workspace_bytes -= 4                                                         # one float short
+    assert lib.mtbc_conv3x3_kernel_name(C.byref(a), L.OP_CONV3_WGRAD, buf, 256) == -3
+    a = ops.conv3x3_case_args(L.OP_CONV3_FWD, 2, [48], 48, 32, 32, **_BF16)
+    assert lib.mtbc_conv3x3_kernel_name(C.byref(a), L.OP_CONV3_FWD, buf, 256) == 0
+    assert lib.mtbc_conv3x3_kernel_name(C.byref(a), L.OP_CONV3_PACK_FWD, buf, 256) == -2
+    assert lib.mtbc_conv3x3_kernel_name(C.byref(a), L.OP_CONV3_FWD, buf, 8) == -2        # shorter than the name
+    assert lib.mtbc_conv3x3_kernel_name(None, L.OP_CONV3_FWD, buf, 256) == -2

@@ -1334,3 +1334,203 @@ def test_focal_gamma_zero_is_cross_entropy():
         _close(dx, xr.grad.float(), 1e-5, 1e-7, "d CE / d logits")
         if w is None:
             assert abs(loss.item() - torch.nn.CrossEntropyLoss()(x, t).item()) < 1e-6
+
+
+# ------------------------------------------------------------------ the instances the benchmark's step programs launch, element by element
+# (N, segs, Cout, H, W, mode, wgrad): mode "bf16" = compute 1, conv output stored as fp16 (O8 = 3) and in fp32 planes (O8 = 0);
+# "f16" = compute 2, output fp16 channel-blocked (O8 = 1) and fp32 planes; "f32" = the parity mode (fp32 planar operands).  Every
+# case also runs the dgrad into multi-segment fp32 planes (first segment overwritten, the others accumulated) and, with `wgrad`,
+# the weight gradient.  The smallest batch that reaches each instance; the kernel always runs the whole batch.
+BENCH_CASES = [
+    (16, [24], 24, 256, 256, "bf16", False),               # 8-wave blocks (t16 * mblocks = 2048), configs[1] level 0
+    (16, [24, 24], 24, 264, 256, "bf16", False),           # 8-wave blocks, H not a multiple of 16 (a half 16-row tile), two segments
+    (8, [48], 48, 128, 128, "bf16", True),                 # MT = 3 at 128 x 128 (ntiles * mblocks = 512)
+    (8, [48, 48], 40, 128, 128, "bf16", False),            # MT = 3, Cout = 40: the last 16-channel tile of the block 8 / 16 full
+    (16, [96], 96, 64, 64, "bf16", True),                  # MT = 3, two channel blocks at 64 x 64
+    (32, [192], 192, 32, 32, "bf16", False),               # configs[1] level 3
+    (32, [384, 384, 384], 512, 16, 16, "bf16", False),     # 16 x 16 maps past the ring budget: MT = 2 forward, MT = 3 dgrad (K = 1152 x 9)
+    (32, [384], 384, 16, 16, "bf16", True),                # the ring kernel at bench batch
+    (16, [192], 192, 32, 32, "bf16", False),               # the ring kernel on 32 x 32 maps (a half-batch launch of configs[1])
+    (64, [48], 384, 16, 16, "bf16", False),                # 16 x 16 maps, MT = 3 without the ring (reads < 96 channels)
+    (16, [24], 24, 512, 512, "f16", False),                # configs[4] level 0: 8-wave blocks, fp16 channel-blocked output
+    (8, [48, 48], 40, 128, 128, "f16", False),             # MT = 3, ragged last channel tile, O8 = 1
+    (16, [96, 96], 96, 32, 32, "f16", True),               # the ring kernel with fp16 operands
+    (16, [24], 32, 128, 128, "f16", False),                # MT = 2 in 4-wave blocks (t16 * mblocks = 512), O8 = 1
+    (8, [24], 24, 256, 256, "f32", True),                  # conv3x3_igemm_dma_kernel<2, 0, 2>
+    (8, [48], 40, 128, 128, "f32", False),                 # <3, 0, 2>, Cout = 40: a half-empty last channel tile
+    (8, [24, 24], 48, 128, 128, "f32", True),              # <3, 0, 2>, two segments
+    (8, [96], 48, 64, 64, "f32", True),                    # the 48-channel (3-tile) weight-gradient blocks without the 24-channel packing
+    (32, [384, 384, 384], 512, 16, 16, "f32", False),      # <2, 1, 2> forward, <3, 1, 2> dgrad
+    (4, [1], 24, 256, 256, "f32", True),                   # the fp32 stem: stem forward kernel, direct dgrad, small-Cin wgrad + bias sums
+]
+_BENCH_MODE = {"bf16": dict(compute=1, c8=True), "f16": dict(compute=2, c8=True), "f32": {}}
+
+
+def _bench_case_calls(N, segs, Cout, H, W, mode, wgrad):
+    """(op, conv3x3_case_args keywords) of every launch test_conv3x3_bench_instances_match_fp64 makes for this case, in order."""
+    m = _BENCH_MODE[mode]
+    calls = []
+    if mode != "f32":
+        calls.append((ops.L.OP_CONV3_FWD, dict(m, out_c8=True, out_fp16=mode == "bf16")))
+    calls += [(ops.L.OP_CONV3_FWD, m), (ops.L.OP_CONV3_DGRAD, m)]
+    if wgrad:
+        calls.append((ops.L.OP_CONV3_WGRAD, m))
+    return calls
+
+
+def _ulp16(v, compute):
+    """Spacing of the 16-bit type (1 bf16, 2 fp16) at |v| (fp64 tensor)."""
+    mant, emin = (7, -126) if compute == 1 else (10, -14)
+    e = torch.floor(torch.log2(v.abs().clamp_min(2.0 ** emin)))
+    return torch.pow(2.0, e - mant)
+
+
+def _ref_images(N, H, W):
+    """Images the fp64 reference is computed for: the first two, the last, and every image of the last block (4 images per
+    block on 8 x 8 maps, one elsewhere)."""
+    per = 4 if (H, W) == (8, 8) else 1
+    return sorted({0, min(1, N - 1), N - 1} | set(range((N - 1) // per * per, N)))
+
+
+@pytest.mark.parametrize("N,segs,Cout,H,W,mode,wgrad", BENCH_CASES)
+def test_conv3x3_bench_instances_match_fp64(N, segs, Cout, H, W, mode, wgrad):
+    """The forward / dgrad / wgrad instances of the benchmark's step programs (tests/test_ops_gpu.py::test_step_programs_launch_only_
+    reference_tested_conv3x3_instances) against an fp64 conv on the operands the MFMA reads (rounded RNE to its 16-bit type, or fp32):
+    fp32 results within 1e-5 of the output scale, 16-bit stored outputs within one unit in the last place of the stored type of the
+    fp64 result (+ the same accumulation allowance).  fwd / dgrad are per image: the reference covers _ref_images, every other image
+    must be finite.  The launches made are exactly the instances mtbc_conv3x3_kernel_name plans for the case."""
+    m = _BENCH_MODE[mode]
+    compute = m.get("compute", 0)
+    g = _g(N * 7919 + Cout * 31 + H + compute)
+    Cin = sum(segs)
+    xs = [torch.randn(N, c, H, W, generator=g) for c in segs]
+    w = torch.randn(Cout, Cin, 3, 3, generator=g) * (2.0 / (9 * Cin)) ** 0.5
+    b = torch.randn(Cout, generator=g)
+    dz = torch.randn(N, Cout, H, W, generator=g)
+    rnd = (lambda t: _round16(t, compute)) if compute else (lambda t: t)
+    idx = _ref_images(N, H, W)
+    xr, wr, dzr = rnd(torch.cat(xs, 1)).double(), rnd(w).double(), rnd(dz).double()
+    z_ref = F.conv2d(xr[idx], wr, b.double(), padding=1)
+    dx_ref = torch.nn.grad.conv2d_input((len(idx), Cin, H, W), wr, dzr[idx], padding=1)
+    zs, ds = z_ref.abs().max().item(), dx_ref.abs().max().item()
+
+    xd = [x.to(DEV) for x in xs]
+    wd, bd, dzd = w.to(DEV), b.to(DEV), dz.to(DEV)
+    pre = [torch.randn(N, c, H, W, generator=g) for c in segs]
+    acc = [0] + [1] * (len(segs) - 1)
+    dx = [p.to(DEV) for p in pre]
+    ops.launched = []
+    try:
+        if compute:
+            pf, pd = ops.conv3x3_pack_lp(wd, compute)
+            x8 = [ops.C8.pack(x, compute) for x in xd]
+            dz8 = ops.C8.pack(dzd, compute)
+            ops.launched.clear()                   # (packing is no conv3x3 launch; keep the list to the checked calls)
+            z16 = ops.conv3x3_fwd_c8(x8, wd, bd, pf, out_c8=True, out_fp16=mode == "bf16")
+            z = ops.conv3x3_fwd_c8(x8, wd, bd, pf)
+            ops.conv3x3_dgrad_c8(dz8, wd, dx, acc, pd)
+            if wgrad:
+                dw, db = ops.conv3x3_wgrad_c8(x8, dz8, (Cout, Cin, 3, 3), want_bias=True, in_kernel_reduce=False)
+        else:
+            pf, pd = ops.conv3x3_pack(wd)
+            z = ops.conv3x3_fwd(xd, wd, bd, packed=pf)
+            ops.conv3x3_dgrad(dzd, wd, dx, acc, packed=pd)
+            if wgrad:
+                dw, db = ops.conv3x3_wgrad(xd, dzd, (Cout, Cin, 3, 3), want_bias=True)
+        torch.cuda.synchronize()
+        made = list(ops.launched)
+    finally:
+        ops.launched = None
+    planned = [(op, ops.conv3x3_case_kernel(op, N, segs, Cout, H, W, **kw)) for op, kw in _bench_case_calls(N, segs, Cout, H, W, mode, wgrad)]
+    assert made == planned, (made, planned)
+
+    z = z.cpu()
+    assert bool(torch.isfinite(z).all()), "fwd: non-finite output"
+    err = (z[idx].double() - z_ref).abs().max().item()
+    assert err <= 1e-5 * zs, f"fwd ({planned[1 if compute else 0][1]}): max err {err:.3e} vs scale {zs:.3e}"
+    if compute:
+        st = 2 if mode == "bf16" else compute           # the stored type: fp16 for the bf16 mode's conv outputs
+        s = z16.unpack().cpu()
+        assert bool(torch.isfinite(s).all()), "stored fwd: non-finite output"
+        d = (s[idx].double() - z_ref).abs()
+        bound = _ulp16(z_ref, st) + 1e-5 * zs
+        worst = (d / bound).max().item()
+        assert worst <= 1.0, f"stored fwd ({planned[0][1]}): {worst:.3f} x (one ulp of the stored type + 1e-5 x scale)"
+    dx_ref = torch.split(dx_ref, segs, dim=1)
+    for i in range(len(segs)):
+        got = dx[i].cpu()
+        assert bool(torch.isfinite(got).all()), f"dgrad seg {i}: non-finite"
+        want = dx_ref[i] + (pre[i][idx].double() if acc[i] else 0)
+        err = (got[idx].double() - want).abs().max().item()
+        assert err <= 1e-5 * max(ds, want.abs().max().item()), f"dgrad seg {i}: max err {err:.3e} vs scale {ds:.3e}"
+    if wgrad:
+        ref = torch.nn.grad.conv2d_weight(xr, (Cout, Cin, 3, 3), dzr, padding=1)
+        dbr = dzr.sum((0, 2, 3))
+        scale = max(1.0, ref.abs().max().item())          # the wgrad tests' standard (test_conv3x3_c8_operands)
+        _close(dw, ref.float(), 1e-5, 2e-5 * scale, f"wgrad ({planned[-1][1]})")
+        _close(db, dbr.float(), 1e-5, 2e-5 * max(1.0, dbr.abs().max().item()), "dbias")
+
+
+def _reference_tested_instances():
+    """The conv3x3 instances the element-wise reference tests of this file launch, from their own case tables through
+    mtbc_conv3x3_kernel_name (kernel instance only: the split-K reductions behind the weight gradients are one kernel, checked with all of them)."""
+    F_, D_, W_ = ops.L.OP_CONV3_FWD, ops.L.OP_CONV3_DGRAD, ops.L.OP_CONV3_WGRAD
+    calls = []
+    for case in BENCH_CASES:
+        calls += [(op, case[:5], kw) for op, kw in _bench_case_calls(*case)]
+    for case in CONV_CASES:                                      # test_conv3x3_mfma_fwd_dgrad_wgrad (fp32)
+        calls += [(F_, case, {}), (D_, case, {}), (W_, case, {}), (W_, case, dict(bias=False))]
+    extra16 = [(2, [24, 24, 24, 24, 24, 24], 24, 256, 256), (1, [384, 384, 384], 512, 16, 16), (16, [24, 24], 24, 256, 256)]
+    for compute in (1, 2):
+        m = dict(compute=compute, c8=True)
+        for case in C8_CASES:                                    # test_conv3x3_c8_operands
+            calls += [(F_, case, m), (D_, case, m), (W_, case, dict(m, in_kernel_reduce=True)), (W_, case, dict(m, bias=False, in_kernel_reduce=True))]
+        for case in C8_CASES + extra16:                          # test_conv3x3_16bit_fwd_dgrad_match_fp64_on_rounded_operands
+            calls += [(F_, case, m), (D_, case, m), (F_, case, dict(compute=compute)), (D_, case, dict(compute=compute))]
+        for case in C8W_CASES + C8I_CASES:                       # test_conv3x3_wgrad_c8_wide_blocks
+            calls += [(W_, case, dict(m, in_kernel_reduce=True)), (W_, case, dict(m, bias=False, in_kernel_reduce=True))]
+        for case in FIXUP_CASES:                                 # test_conv3x3_wgrad_c8_in_kernel_split_k_reduction
+            calls += [(W_, case, dict(m, in_kernel_reduce=r)) for r in (True, False)]
+        for N, Cout, H, W in [(2, 24, 256, 256), (3, 32, 40, 24), (1, 8, 8, 12), (2, 24, 96, 96)]:     # test_stem_conv_on_the_16bit_path
+            for out_fp16 in ((True, False) if compute == 1 else (False,)):
+                calls.append((F_, (N, [1], Cout, H, W), dict(m, out_c8=True, out_fp16=out_fp16, bias=True)))
+            calls.append((W_, (N, [1], Cout, H, W), dict(m, bias=False, in_kernel_reduce=True)))
+    for case in [(2, [24], 24, 256, 256), (2, [48], 48, 128, 128), (3, [96], 96, 64, 64), (2, [96, 96], 96, 16, 16), (5, [32], 80, 8, 8)]:
+        calls.append((F_, case, dict(compute=1, c8=True, out_c8=True, out_fp16=True)))      # test_bf16_mode_conv_output_stored_as_fp16
+    return {ops.conv3x3_case_kernel(op, *case, **kw).split(" + ")[0] for op, case, kw in calls}
+
+
+# the benchmark's step programs (bench.py run_mode): (arch, dtype, N, size) of BASELINE.json configs[1], configs[4] (its per-GPU shape),
+# configs[2], and the fp32 parity mode
+STEP_PROGRAMS = [("MTUNetPlusPlus", "bf16", 32, 256), ("MTUNetPlusPlus", "f16", 16, 512), ("MTnnUNet", "bf16", 64, 256), ("MTUNetPlusPlus", "f32", 32, 256)]
+
+
+def test_step_programs_launch_only_reference_tested_conv3x3_instances():
+    """Builds (does not run) the step programs of the benchmark's configurations with bench.py's constructor path and asks
+    mtbc_conv3x3_kernel_name for the instance of every 3x3 conv launch: each must be one an element-wise reference test of this
+    file launches.  A new dispatch path that no reference test reaches fails here."""
+    from multi_task_breast_cancer_amd.experiment_init import init_multitask_model, init_optimizer
+    from multi_task_breast_cancer_amd.miscellany import seed_everything
+    from multi_task_breast_cancer_amd.trainer import FusedTrainStep
+    L = ops.L
+    tested = _reference_tested_instances()
+    missing = {}
+    for arch, dtype, N, size in STEP_PROGRAMS:
+        seed_everything(1993)
+        model = init_multitask_model(arch, sequences=1, regions=1, n_classes=3, deep_supervision=True).to(DEV)
+        model.set_compute(dtype)
+        step = FusedTrainStep(model, init_optimizer(model, "Adam", 1e-4), alpha=0.5, inversely_weighted=True)
+        st = step._compiled(N, size, size)
+        seen = set()
+        for prog in st.programs.values():
+            for i in range(getattr(prog, "n", 0)):
+                op = prog.array[i]
+                if op.kind in (L.OP_CONV3_FWD, L.OP_CONV3_DGRAD, L.OP_CONV3_WGRAD):
+                    seen.add(ops.conv3x3_kernel_name(op.u.conv3, op.kind).split(" + ")[0])
+        print(f"{arch} {dtype} N={N} {size}x{size}: {sorted(seen)}")
+        assert seen, f"{arch} {dtype}: no 3x3 conv launch found"
+        if seen - tested:
+            missing[(arch, dtype, N, size)] = sorted(seen - tested)
+        del st, step, model
+        torch.cuda.empty_cache()
+    assert not missing, f"conv3x3 instances of the step programs that no element-wise reference test launches: {missing}"
