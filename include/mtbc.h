@@ -516,6 +516,47 @@ int mtbc_adam_step(const mtbc_adam_args* a, void* stream);
  * as torch.optim.Adam's scalar path -- for the caller to place in `dynamic`. */
 int mtbc_adam_dynamic(const mtbc_adam_args* a, float out3[3]);
 
+/* ------------------------------------------------------------------------------------ dynamic loss scale
+ * torch.amp.GradScaler's rule, stream-ordered on the device (no host read in the step).  One step is
+ *   mtbc_loss_scale_begin -> forward, losses, backward [, all-reduce] -> mtbc_loss_scale_check -> mtbc_loss_scale_adam
+ * The state is 64 bytes of DEVICE memory owned by the caller (zero-filled, then `scale` set); every field is written by ordinary
+ * vector stores / atomics, kernel boundaries order them.                                                                        */
+typedef struct {
+    float    scale;                  /* the loss scale: a power of two as long as the factors are */
+    int32_t  growth_tracker;         /* clean steps since the scale last changed */
+    uint32_t found_inf;              /* set by _check when a gradient is inf / NaN, cleared by _adam's update */
+    int32_t  t;                      /* Adam updates actually APPLIED (a skipped step does not count) */
+    int32_t  skipped;                /* steps skipped so far */
+    float    lr;                     /* the caller writes the learning rate of the step here, in stream order, before _begin */
+    float    shard_weight;           /* the caller's factor on dL (1, or this rank's share of an unequal global batch times world) */
+    float    adam[3];                /* _begin: {inv_world / scale, lr / (1-b1^(t+1)), 1 / sqrt(1-b2^(t+1))} = mtbc_adam_args.dynamic of the step */
+    int32_t  reserved[6];
+} mtbc_loss_scale_state;
+typedef struct {
+    mtbc_loss_scale_state* state;    /* DEVICE memory (HOST memory for mtbc_loss_scale_update_host), 4-byte aligned */
+    float* gscale_out;               /* _begin: *gscale_out = shard_weight * scale -- the word mtbc_dice_args / mtbc_focal_args.gscale_dev point at */
+    const float* g; int64_t n;       /* _check: the flat gradient buffer (16-byte aligned), every element of [0, n) is read */
+    double growth_factor, backoff_factor;      /* the scale is multiplied in double and rounded once, as torch._amp_update_scale_ does */
+    int32_t growth_interval;         /* >= 1 */
+    float inv_world;                 /* 1 / world size: Adam's grad_scale is inv_world / scale */
+    float beta1, beta2;              /* the bias corrections of step t + 1 are evaluated on the device, in double */
+} mtbc_loss_scale_args;
+/* one thread: the loss kernels' device factor and Adam's three scalars for the step that follows (state->t + 1) */
+int mtbc_loss_scale_begin(const mtbc_loss_scale_args* a, void* stream);
+/* one streaming pass over g (float4 loads, grid-stride, grid sized like mtbc_adam_step's): found_inf = 1 when any element has an all-ones exponent */
+int mtbc_loss_scale_check(const mtbc_loss_scale_args* a, void* stream);
+/* mtbc_adam_step(adam) with dynamic = state->adam, and every thread returns before touching p / m / v when found_inf is set
+ * (zero_grad still clears g); then one thread applies the update rule below to the state and clears found_inf.  `adam->lr`,
+ * `step`, `grad_scale` and `dynamic` are not read.  Two launches, no grid-wide barrier.                                        */
+int mtbc_loss_scale_adam(const mtbc_loss_scale_args* a, const mtbc_adam_args* adam, void* stream);
+/* host only, no GPU call: the update rule of _adam on a HOST copy of the state (the device kernel runs the same inline function):
+ *   found_inf: scale *= backoff_factor, growth_tracker = 0, skipped += 1
+ *   else     : t += 1, growth_tracker += 1, and at growth_interval: scale *= growth_factor (kept when that is not finite), growth_tracker = 0
+ *   found_inf = 0                                                                                                               */
+int mtbc_loss_scale_update_host(const mtbc_loss_scale_args* a);
+/* host only: what _begin writes into state->adam for the `t`, `scale` and `lr` of a HOST copy of the state */
+int mtbc_loss_scale_begin_host(const mtbc_loss_scale_args* a);
+
 /* Whole-batch TP/FP/FN of (sigmoid(x) > .5) vs target, the train-loop Dice metric of
  * metrics.py:255-267 (training_multitask.py:66-71).  out3 = {tp, fp, fn} as float64.        */
 int mtbc_dice_counts(const float* logits, const float* target, int64_t n, double* out3, void* stream);

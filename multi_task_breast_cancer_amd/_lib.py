@@ -124,6 +124,17 @@ class AdamArgs(C.Structure):
                 ("grad_scale", C.c_float), ("step", C.c_int32), ("zero_grad", C.c_int32), ("dynamic", C.c_void_p)]
 
 
+class LossScaleState(C.Structure):
+    _fields_ = [("scale", C.c_float), ("growth_tracker", C.c_int32), ("found_inf", C.c_uint32), ("t", C.c_int32), ("skipped", C.c_int32),
+                ("lr", C.c_float), ("shard_weight", C.c_float), ("adam", C.c_float * 3), ("reserved", C.c_int32 * 6)]
+
+
+class LossScaleArgs(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("gscale_out", C.c_void_p), ("g", C.c_void_p), ("n", C.c_int64),
+                ("growth_factor", C.c_double), ("backoff_factor", C.c_double), ("growth_interval", C.c_int32),
+                ("inv_world", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float)]
+
+
 class _PackArgs(C.Structure):
     _fields_ = [("w", C.c_void_p), ("packed", C.c_void_p), ("Cin", C.c_int32), ("Cout", C.c_int32),
                 ("dgrad", C.c_int32), ("compute", C.c_int32)]
@@ -223,7 +234,8 @@ EXPORTS = [
     "mtbc_maxpool2_bwd", "mtbc_convT_wgrad_workspace", "mtbc_convT_fwd_c8_supported", "mtbc_convT_fwd", "mtbc_convT_dgrad", "mtbc_convT_wgrad",
     "mtbc_conv1x1_wgrad_workspace", "mtbc_conv1x1_fwd", "mtbc_conv1x1_dgrad", "mtbc_conv1x1_wgrad",
     "mtbc_gap_fwd", "mtbc_gap_bwd", "mtbc_linear_fwd", "mtbc_linear_bwd", "mtbc_dice_fwd", "mtbc_dice_bwd",
-    "mtbc_focal_fwd_bwd", "mtbc_loss_mix", "mtbc_adam_step", "mtbc_adam_dynamic", "mtbc_dice_counts", "mtbc_program_run",
+    "mtbc_focal_fwd_bwd", "mtbc_loss_mix", "mtbc_adam_step", "mtbc_adam_dynamic", "mtbc_loss_scale_begin", "mtbc_loss_scale_check", "mtbc_loss_scale_adam",
+    "mtbc_loss_scale_update_host", "mtbc_loss_scale_begin_host", "mtbc_dice_counts", "mtbc_program_run",
     "mtbc_program_run_ms", "mtbc_event_create", "mtbc_event_destroy",
 ]
 
@@ -320,6 +332,14 @@ def load() -> C.CDLL:
     lib.mtbc_dice_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.mtbc_adam_dynamic.restype = C.c_int
     lib.mtbc_adam_dynamic.argtypes = [C.POINTER(AdamArgs), C.POINTER(C.c_float * 3)]
+    for name in ("mtbc_loss_scale_begin", "mtbc_loss_scale_check"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(LossScaleArgs), C.c_void_p]
+    lib.mtbc_loss_scale_adam.restype = C.c_int
+    lib.mtbc_loss_scale_adam.argtypes = [C.POINTER(LossScaleArgs), C.POINTER(AdamArgs), C.c_void_p]
+    for name in ("mtbc_loss_scale_update_host", "mtbc_loss_scale_begin_host"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(LossScaleArgs)]
     lib.mtbc_program_run.restype = C.c_int
     lib.mtbc_program_run.argtypes = [C.POINTER(Op), C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]
     lib.mtbc_program_run_ms.restype = C.c_int

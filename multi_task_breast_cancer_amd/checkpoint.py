@@ -4,6 +4,7 @@
   'optimizer_state_dict', 'scheduler', 'val_loss'); model keys are the reference's, the optimizer state is in
   torch.optim.Adam's layout (optim.FusedAdam.state_dict), so files interchange with the reference in both directions.
 * `load_pretrained_model` is src/utils/models.py:19-36 (same name, same ValueError on a missing file).
+* both take an optional `scaler=`: the dynamic loss scale's state (torch.amp.GradScaler's keys) under 'loss_scaler_state_dict'.
 * `write_metrics_file` (src/utils/miscellany.py:155-169), `METRICS_HEADER` (training_multitask.py:216-217) and
   `metrics_row` (:271-275, including the stray blank before Validation_dice that the reference's f-string emits).
 * `EarlyStopping` is the patience logic of :238-251, :277-280.
@@ -19,17 +20,23 @@ import torch
 METRICS_HEADER = "epoch,LR,Train_loss,Validation_loss,Train_dice,Validation_dice,Train_acc,Train_F1,Validation_acc,Validation_F1"   # training_multitask.py:216-217
 
 
-def save_checkpoint(path: str, epoch: int, model, optimizer, val_loss: float) -> None:
-    torch.save({"epoch": epoch, "model_state_dict": model.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
-                "scheduler": "scheduler", "val_loss": val_loss}, path)
+def save_checkpoint(path: str, epoch: int, model, optimizer, val_loss: float, scaler=None) -> None:
+    """`scaler` (a loss_scale.DynamicLossScale or a torch.amp.GradScaler): its state goes under the extra key 'loss_scaler_state_dict'."""
+    ckpt = {"epoch": epoch, "model_state_dict": model.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
+            "scheduler": "scheduler", "val_loss": val_loss}
+    if scaler is not None:
+        ckpt["loss_scaler_state_dict"] = scaler.state_dict()
+    torch.save(ckpt, path)
 
 
-def load_pretrained_model(model, ckpt_path: str, optimizer=None):
+def load_pretrained_model(model, ckpt_path: str, optimizer=None, scaler=None):
     if os.path.isfile(ckpt_path):
         checkpoint = torch.load(ckpt_path, map_location="cpu", weights_only=False)
         model.load_state_dict(checkpoint["model_state_dict"])
         if optimizer is not None and checkpoint.get("optimizer_state_dict") is not None:
             optimizer.load_state_dict(checkpoint["optimizer_state_dict"])
+        if scaler is not None and checkpoint.get("loss_scaler_state_dict"):      # files written without a scaler load as before: the scaler keeps its state
+            scaler.load_state_dict(checkpoint["loss_scaler_state_dict"])
         logging.info(f"Loaded checkpoint '{ckpt_path}'. Last epoch: {checkpoint['epoch']}")
     else:
         raise ValueError(f"\n\t-> No checkpoint found at '{ckpt_path}'")

@@ -255,7 +255,7 @@ __global__ void loss_mix_kernel(const float* seg, const float* cls, float alpha,
 }
 
 // ------------------------------------------------------------------ Adam
-struct AdamP { long long n; float* p; float* g; float* m; float* v; float gs, b1, b2, eps, step_size, inv_bc2_sqrt; int zero; const float* dyn; };
+struct AdamP { long long n; float* p; float* g; float* m; float* v; float gs, b1, b2, eps, step_size, inv_bc2_sqrt; int zero; const float* dyn; const unsigned* skip; };
 __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamP& a) {
     g *= a.gs;
     m = m + (g - m) * (1.0f - a.b1);                     // lerp, as torch
@@ -264,9 +264,13 @@ __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, con
     p = p - a.step_size * (m / denom);
 }
 __global__ void adam_kernel(AdamP a) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    if (a.skip && *a.skip) {                     // dynamic loss scale: a gradient overflowed -> p, m, v are not touched (uniform load, every thread takes the same way)
+        if (a.zero) for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) a.g[i] = 0.f;
+        return;
+    }
     if (a.dyn) { a.gs = a.dyn[0]; a.step_size = a.dyn[1]; a.inv_bc2_sqrt = a.dyn[2]; }      // the per-step scalars from memory (graph replay), uniform loads
     const long long n4 = a.n >> 2;
-    const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         float4 p = reinterpret_cast<float4*>(a.p)[i], g = reinterpret_cast<float4*>(a.g)[i];
         float4 m = reinterpret_cast<float4*>(a.m)[i], v = reinterpret_cast<float4*>(a.v)[i];
@@ -278,6 +282,56 @@ __global__ void adam_kernel(AdamP a) {
         adam1(a.p[i], a.g[i], a.m[i], a.v[i], a);
         if (a.zero) a.g[i] = 0.f;
     }
+}
+
+// ------------------------------------------------------------------ dynamic loss scale (torch.amp.GradScaler's rule on the device)
+// The two single-thread halves are plain functions shared by the kernels and by the host-only entry points, so that the rule a machine without a GPU
+// tests is the rule the device runs.
+__host__ __device__ inline void loss_scale_begin(mtbc_loss_scale_state* s, float* gscale_out, float inv_world, float b1, float b2) {
+    if (gscale_out) *gscale_out = s->shard_weight * s->scale;
+    const double t1 = (double)(s->t + 1);                      // the step this update would be, if it is applied
+    const double bc1 = 1.0 - pow((double)b1, t1);              // as adam_scalars() below: in double, rounded once
+    const double bc2 = 1.0 - pow((double)b2, t1);
+    s->adam[0] = (float)((double)inv_world / (double)s->scale);
+    s->adam[1] = (float)((double)s->lr / bc1);
+    s->adam[2] = (float)(1.0 / sqrt(bc2));
+}
+__host__ __device__ inline void loss_scale_update(mtbc_loss_scale_state* s, double growth, double backoff, int interval) {
+    if (s->found_inf) {
+        s->scale = (float)((double)s->scale * backoff);
+        s->growth_tracker = 0;
+        s->skipped += 1;
+    } else {
+        s->t += 1;
+        const int ok = s->growth_tracker + 1;
+        if (ok == interval) {
+            const float grown = (float)((double)s->scale * growth);
+            if (grown - grown == 0.f) s->scale = grown;         // finite: torch._amp_update_scale_ keeps the scale rather than let it become inf
+            s->growth_tracker = 0;
+        } else {
+            s->growth_tracker = ok;
+        }
+    }
+    s->found_inf = 0u;
+}
+__global__ void loss_scale_begin_kernel(mtbc_loss_scale_state* s, float* gscale_out, float inv_world, float b1, float b2) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) loss_scale_begin(s, gscale_out, inv_world, b1, b2);
+}
+__global__ void loss_scale_update_kernel(mtbc_loss_scale_state* s, double growth, double backoff, int interval) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) loss_scale_update(s, growth, backoff, interval);
+}
+__device__ __forceinline__ unsigned nonfinite_bits(unsigned u) { return (u & 0x7f800000u) == 0x7f800000u; }
+__global__ void found_inf_kernel(const float* __restrict__ g, long long n, unsigned* flag) {
+    const long long n4 = n >> 2;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    unsigned bad = 0;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const uint4 v = reinterpret_cast<const uint4*>(g)[i];
+        bad |= nonfinite_bits(v.x) | nonfinite_bits(v.y) | nonfinite_bits(v.z) | nonfinite_bits(v.w);
+    }
+    for (long long i = (n4 << 2) + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        bad |= nonfinite_bits(reinterpret_cast<const unsigned*>(g)[i]);
+    if (bad) atomicOr(flag, 1u);                                // rare (an overflowing step), so no wave reduction in front of it
 }
 
 // ------------------------------------------------------------------ Dice metric counters (integer, exact)
@@ -429,10 +483,64 @@ int mtbc_adam_step(const mtbc_adam_args* a, void* stream) {
     p.inv_bc2_sqrt = dyn[2];
     p.zero = a->zero_grad;
     p.dyn = a->dynamic;
+    p.skip = nullptr;
     long long blocks = cdiv64(a->n / 4 + 1, 256);
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
     MTBC_CHECK_LAUNCH();
+    return MTBC_OK;
+}
+
+static int loss_scale_args_ok(const mtbc_loss_scale_args* a) {
+    if (!a || !a->state || (reinterpret_cast<uintptr_t>(a->state) & 3)) return 0;
+    return a->growth_interval >= 1 && a->growth_factor > 0.0 && a->backoff_factor > 0.0 && a->inv_world > 0.f;
+}
+int mtbc_loss_scale_begin(const mtbc_loss_scale_args* a, void* stream) {
+    if (!loss_scale_args_ok(a) || !a->gscale_out) return MTBC_E_BADARG;
+    hipLaunchKernelGGL(loss_scale_begin_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a->state, a->gscale_out, a->inv_world, a->beta1, a->beta2);
+    MTBC_CHECK_LAUNCH();
+    return MTBC_OK;
+}
+int mtbc_loss_scale_check(const mtbc_loss_scale_args* a, void* stream) {
+    if (!loss_scale_args_ok(a) || !a->g) return MTBC_E_BADARG;
+    if (a->n <= 0) return MTBC_E_BADSHAPE;
+    if (reinterpret_cast<uintptr_t>(a->g) & 15) return MTBC_E_UNSUPPORTED;
+    long long blocks = cdiv64(a->n / 4 + 1, 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(found_inf_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a->g, (long long)a->n, &a->state->found_inf);
+    MTBC_CHECK_LAUNCH();
+    return MTBC_OK;
+}
+int mtbc_loss_scale_adam(const mtbc_loss_scale_args* a, const mtbc_adam_args* adam, void* stream) {
+    if (!loss_scale_args_ok(a)) return MTBC_E_BADARG;
+    if (!adam || adam->n <= 0) return MTBC_E_BADSHAPE;
+    if (!adam->p || !adam->g || !adam->m || !adam->v) return MTBC_E_BADARG;
+    if ((reinterpret_cast<uintptr_t>(adam->p) | reinterpret_cast<uintptr_t>(adam->g) | reinterpret_cast<uintptr_t>(adam->m) |
+         reinterpret_cast<uintptr_t>(adam->v)) & 15)
+        return MTBC_E_UNSUPPORTED;
+    AdamP p;
+    p.n = adam->n; p.p = adam->p; p.g = const_cast<float*>(adam->g); p.m = adam->m; p.v = adam->v;
+    p.gs = 0.f; p.step_size = 0.f; p.inv_bc2_sqrt = 0.f;                   // the kernel takes all three from state->adam
+    p.b1 = adam->beta1; p.b2 = adam->beta2; p.eps = adam->eps;
+    p.zero = adam->zero_grad;
+    p.dyn = a->state->adam;
+    p.skip = &a->state->found_inf;
+    long long blocks = cdiv64(adam->n / 4 + 1, 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+    MTBC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a->state, a->growth_factor, a->backoff_factor, a->growth_interval);
+    MTBC_CHECK_LAUNCH();
+    return MTBC_OK;
+}
+int mtbc_loss_scale_update_host(const mtbc_loss_scale_args* a) {
+    if (!loss_scale_args_ok(a)) return MTBC_E_BADARG;
+    loss_scale_update(a->state, a->growth_factor, a->backoff_factor, a->growth_interval);
+    return MTBC_OK;
+}
+int mtbc_loss_scale_begin_host(const mtbc_loss_scale_args* a) {
+    if (!loss_scale_args_ok(a)) return MTBC_E_BADARG;
+    loss_scale_begin(a->state, a->gscale_out, a->inv_world, a->beta1, a->beta2);
     return MTBC_OK;
 }
 

@@ -262,7 +262,7 @@ class CompiledStep:
             self.mask = plan.alloc(N, self.segs[0].C, H, W)
             self.onehot = plan.alloc(N, self.logits.C)
             heads = self.segs if net.deep_supervision_outputs else self.segs[-1:]
-            self.loss_scale = float(net.loss_scale)
+            self.loss_scale = float(fused_loss.get("loss_scale", net.loss_scale))     # baked into the loss ops; 1.0 under a dynamic scale (the device word carries it)
             plan.fused_losses(heads, self.logits, self.mask, self.onehot, fused_loss["alpha"],
                               fused_loss["inversely_weighted"], fused_loss.get("focal_weight"), loss_scale=self.loss_scale,
                               binary=bool(fused_loss.get("binary")), cls_gamma=float(fused_loss.get("cls_gamma", 2.0)))
@@ -332,8 +332,9 @@ class HipMultiTaskNet(nn.Module):
         # (tests/studies/design_error_cpu.py, profiles/r04_fp16_design_error.txt): at initialisation the scale does not matter, but dz shrinks as
         # training goes on -- after 1500 steps 2^12 leaves 13 - 23 % error in the gradients of conv_4_0 (bf16 mode: 1.5 - 3.4 %) and a median of 0.65 %
         # over all tensors, 2^16 leaves 0.7 - 2.3 % and 0.07 % (2^20: 0.3 - 2.0 %, 0.07 %: nothing left to gain, and 16 x less room below 65504).
-        # No overflow in 4 x 12000 training steps on the hard task at 2^16 (an inf would reach the NaN guard).  The real fix is a dynamic scale
-        # with a found-inf skip in the Adam launch.
+        # No overflow in 4 x 12000 training steps on the hard task at 2^16 (an inf would reach the NaN guard).  This static value stays the default;
+        # the overflow-safe alternative is the opt-in dynamic scale with a found-inf skip of the Adam launch, `FusedTrainStep(loss_scale="dynamic")`
+        # (loss_scale.DynamicLossScale): the plan is then compiled with a baked scale of 1 and this value is not used.
         self.loss_scale = 65536.0 if self.compute == 2 else 1.0
         self._steps.clear()
         return self
@@ -411,7 +412,7 @@ class HipMultiTaskNet(nn.Module):
                 # its raw pointer is baked into the FOCAL op: validate once, key on identity, keep it alive with the plan
                 if fw.dtype != torch.float32 or not fw.is_contiguous() or fw.device != self.flat_p.device or fw.numel() != self.n_classes:
                     raise ValueError("focal_weight must be a contiguous float32 tensor of n_classes values on the model's device")
-            fkey = (fused_loss["alpha"], fused_loss["inversely_weighted"], self.loss_scale,
+            fkey = (fused_loss["alpha"], fused_loss["inversely_weighted"], float(fused_loss.get("loss_scale", self.loss_scale)),
                     None if fw is None else (fw.data_ptr(), fw._version), bool(fused_loss.get("binary")), float(fused_loss.get("cls_gamma", 2.0)))
         key = (N, H, W, self.compute, self.coop_reserve_cus, fkey)
         st = self._steps.get(key)

@@ -816,6 +816,45 @@ def adam_step(p, g, m, v, lr, step, beta1=0.9, beta2=0.999, eps=1e-4, grad_scale
     L.check(L.load().mtbc_adam_step(C.byref(a), _s()), "adam")
 
 
+# ------------------------------------------------------------------ dynamic loss scale (op level; `state` = 16 int32 words on the device = mtbc_loss_scale_state)
+def _loss_scale_args(state, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, world=1, beta1=0.9, beta2=0.999, gscale_out=None, g=None):
+    if state.device.type != "cuda":
+        L.require_gpu()
+        raise L.MtbcError("device tensors required")
+    if state.dtype != torch.int32 or not state.is_contiguous() or state.numel() * 4 < C.sizeof(L.LossScaleState):
+        raise ValueError("loss-scale state: 16 contiguous int32 words on the device")
+    a = L.LossScaleArgs()
+    a.state = state.data_ptr()
+    a.gscale_out = gscale_out.data_ptr() if gscale_out is not None else None
+    if g is not None:
+        a.g, a.n = g.data_ptr(), g.numel()
+    a.growth_factor, a.backoff_factor, a.growth_interval = growth_factor, backoff_factor, growth_interval
+    a.inv_world, a.beta1, a.beta2 = 1.0 / world, beta1, beta2
+    return a
+
+
+def loss_scale_begin(state, gscale_out, world=1, beta1=0.9, beta2=0.999):
+    """*gscale_out = shard_weight * scale; state.adam = Adam's three scalars of step t + 1 (state.lr, state.scale, 1 / world)."""
+    _chk(gscale_out)
+    L.check(L.load().mtbc_loss_scale_begin(C.byref(_loss_scale_args(state, world=world, beta1=beta1, beta2=beta2, gscale_out=gscale_out)), _s()), "loss scale begin")
+
+
+def loss_scale_check(state, g):
+    """state.found_inf |= any(g is inf or NaN)."""
+    _chk(g)
+    L.check(L.load().mtbc_loss_scale_check(C.byref(_loss_scale_args(state, g=g)), _s()), "loss scale check")
+
+
+def loss_scale_adam(state, p, g, m, v, beta1=0.9, beta2=0.999, eps=1e-4, zero_grad=False, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
+    """Adam with the scalars `loss_scale_begin` left, skipped when state.found_inf is set; then the scale / tracker / t / skipped update."""
+    _chk(p, g, m, v)
+    ad = L.AdamArgs()
+    ad.n, ad.p, ad.g, ad.m, ad.v = p.numel(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
+    ad.beta1, ad.beta2, ad.eps, ad.step, ad.zero_grad = beta1, beta2, eps, 1, int(zero_grad)
+    a = _loss_scale_args(state, growth_factor, backoff_factor, growth_interval, beta1=beta1, beta2=beta2)
+    L.check(L.load().mtbc_loss_scale_adam(C.byref(a), C.byref(ad), _s()), "loss scale adam")
+
+
 # ------------------------------------------------------------------ fused ConvT + 1x1 head (MTnnUNet deep supervision)
 def convT_head_fwd_bwd(x, wT, bT, w1, b1, k, dout):
     """Forward and backward of Conv2d_1x1(ConvTranspose2d_k(x)) through the combined-weight path

@@ -25,6 +25,7 @@ class FusedAdam(torch.optim.Optimizer):
         self.exp_avg = None
         self.exp_avg_sq = None
         self.grad_scale = 1.0            # set to 1/world_size by the data-parallel trainer
+        self._loss_scaler = None         # a loss_scale.DynamicLossScale (set by the trainer): the step count then lives on the device, a skipped step does not advance it
 
     def _ensure_state(self) -> None:
         m = self.model
@@ -84,17 +85,23 @@ class FusedAdam(torch.optim.Optimizer):
         a.dynamic = self._dyn.data_ptr()
         L.check(L.load().mtbc_adam_step(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "adam")
 
-    def graph_key(self):
-        """What a captured launch_dynamic holds by address."""
-        return (self.model.flat_p.data_ptr(), self.model.flat_g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self._dyn.data_ptr(),
-                self.param_groups[0]["betas"], float(self.param_groups[0]["eps"]))
+    def graph_key(self, dynamic: bool = True):
+        """What a captured launch_dynamic holds by address (dynamic=False: without the 12 bytes of scalars, which a dynamic loss scale keeps in its own state)."""
+        return (self.model.flat_p.data_ptr(), self.model.flat_g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                self._dyn.data_ptr() if dynamic else None, self.param_groups[0]["betas"], float(self.param_groups[0]["eps"]))
+
+    def applied_steps(self) -> int:
+        """Adam updates applied so far: the host's count, or the device's under a dynamic loss scale (one read-back; skipped steps do not count)."""
+        if self._loss_scaler is not None:
+            self.step_count = int(self._loss_scaler.stats()["t"])
+        return self.step_count
 
     # ---- checkpoint interchange (training_multitask.py:243-249 saves `optimizer.state_dict()`): the layout is the one
     #      torch.optim.Adam writes -- per-parameter {'step', 'exp_avg', 'exp_avg_sq'} keyed by parameter index -- so a
     #      reference checkpoint resumes here and a checkpoint written here resumes under torch.optim.Adam.
     def state_dict(self):
         sd = super().state_dict()
-        if self.exp_avg is not None and self.step_count > 0:
+        if self.exp_avg is not None and self.applied_steps() > 0:
             m = self.model
             state = {}
             for i, name in enumerate(n for n, _ in m.named_parameters()):
@@ -125,8 +132,12 @@ class FusedAdam(torch.optim.Optimizer):
             if len(steps) > 1:
                 raise ValueError(f"per-parameter step counts differ ({sorted(steps)}): not an Adam state this optimizer can hold")
             self.step_count = steps.pop() if steps else 0
+            if self._loss_scaler is not None:
+                self._loss_scaler.set_t(self.step_count)
         elif legacy is not None:
             self.step_count = int(legacy["step"])
+            if self._loss_scaler is not None:
+                self._loss_scaler.set_t(self.step_count)
             if legacy["exp_avg"] is not None:
                 self._ensure_state()
                 self.exp_avg.copy_(legacy["exp_avg"])

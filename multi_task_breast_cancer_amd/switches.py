@@ -34,6 +34,10 @@ PLAN_SWITCHES: Dict[str, tuple] = {
                         "and replays it from then on: the host issues a step in 0.1 ms instead of 8.4 (profiles/r04_graph_replay.txt); the GPU time is the same, the results are the same bits "
                         "(Adam's per-step scalars travel through device memory, mtbc_adam_args.dynamic)",
                    "tests/test_model_gpu.py::test_graph_replayed_steps_are_the_eager_steps"),
+    "MTBC_DYN_SCALE": ("0", "trainer.FusedTrainStep(loss_scale=None) trains with the device-side dynamic loss scale (loss_scale.DynamicLossScale(): start 2^16, found-inf check "
+                            "over the flat gradients, skip + halve on overflow, double after 2000 clean steps) instead of the static scale baked into the loss ops: three more "
+                            "launches per step; without an overflow the same bits as the static 2^16 of fp16 mode",
+                       "tests/test_loss_scale_gpu.py::test_dynamic_steps_without_overflow_are_the_static_steps"),
     "MTBC_COOP_RESERVE_CUS": ("64", "CUs kept out of the cooperative InstanceNorm grids under data parallel",
                               "tests/test_coop_safety_gpu.py::test_cooperative_step_beside_a_cu_hogging_kernel"),
 }

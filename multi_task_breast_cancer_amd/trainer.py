@@ -99,12 +99,25 @@ class FusedTrainStep:
 
     def __init__(self, model, optimizer, alpha: float, inversely_weighted: bool = True, n_classes: int = 3,
                  distributed: bool = False, n_buckets: int = 4, focal_weight: Optional[torch.Tensor] = None,
-                 cls_criterion: str = "Focal", graph: Optional[bool] = None):
+                 cls_criterion: str = "Focal", graph: Optional[bool] = None, loss_scale=None):
         # graph: replay each compiled step as ONE hipGraph from its third call on (None: the MTBC_GRAPH switch).  The step is a static list of ~380
         # launches with every pointer resolved at plan time -- exactly what a graph holds; what changes from step to step (the batch, the learning
         # rate, Adam's bias corrections, the shard weight) lives in device buffers written BEFORE the replay.  Not under data parallel (the bucket
         # all-reduces are issued between program ranges by the host).
         self.graph = _sw.flag("MTBC_GRAPH") if graph is None else bool(graph)
+        # loss_scale: None = the model's static scale baked into the loss ops (65536 in fp16 mode, 1 otherwise; None + the MTBC_DYN_SCALE switch = "dynamic");
+        # "dynamic" or a loss_scale.DynamicLossScale = torch.amp.GradScaler's rule on the device: three more launches per step (begin, found-inf check over
+        # the flat gradients, state update behind Adam), an overflowing backward skips the update and halves the scale instead of ending the run.
+        if loss_scale is None and _sw.flag("MTBC_DYN_SCALE"):
+            loss_scale = "dynamic"
+        if isinstance(loss_scale, str):
+            if loss_scale != "dynamic":
+                raise ValueError(f"unknown loss_scale {loss_scale!r} (None | 'dynamic' | a DynamicLossScale)")
+            from .loss_scale import DynamicLossScale
+            loss_scale = DynamicLossScale()
+        self.scaler = loss_scale
+        if self.scaler is not None:
+            self.scaler.attach(optimizer)
         self._graphs = {}
         self.binary = n_classes == 2
         if self.binary != (getattr(model, "n_classes", n_classes) == 1):
@@ -144,7 +157,8 @@ class FusedTrainStep:
 
     def _compiled(self, N: int, H: int, W: int):
         st = self.model.compiled(N, H, W, fused_loss={"alpha": self.alpha, "inversely_weighted": self.iw, "focal_weight": self.focal_weight,
-                                                      "binary": self.binary, "cls_gamma": self.cls_gamma})
+                                                      "binary": self.binary, "cls_gamma": self.cls_gamma,
+                                                      **({} if self.scaler is None else {"loss_scale": 1.0})})
         if st is not self._st:
             self._st = st
             self.model.grads_as_views()
@@ -168,8 +182,31 @@ class FusedTrainStep:
         else:
             st.onehot.zero_()
             st.onehot.scatter_(1, lab.to(torch.int64).view(-1, 1), 1.0)
-        st.grad_weight.fill_(1.0 if weight is None else float(weight) * self.world)
+        w = 1.0 if weight is None else float(weight) * self.world
+        if self.scaler is None:
+            st.grad_weight.fill_(w)
+        else:                       # `begin` writes shard weight x scale into st.grad_weight on the device; the weight has a word of its own in the scaler's state
+            self.scaler.ensure(st.grad_weight.device)
+            self.scaler.set_shard_weight(w)
         return st
+
+    def _apply_update(self, st) -> None:
+        """Adam on the (all-reduced) flat gradients: the static path divides the baked loss scale out, the dynamic path checks, skips or applies, and
+        moves its scale -- all in stream order."""
+        if self.scaler is None:
+            self.opt.grad_scale = (1.0 / self.world) / getattr(st, "loss_scale", 1.0)
+            self.opt.step(grads_in_flat=True)
+        else:
+            self.scaler.check(self.model.flat_g)
+            self.scaler.adam(self.opt, self.world)
+
+    def _begin_dynamic(self, st, fills: bool = True) -> None:
+        sc = self.scaler
+        if fills:                   # the learning rate of the day, in stream order, outside a captured graph
+            sc.ensure(st.grad_weight.device)
+            sc.set_lr(self.opt.param_groups[0]["lr"])
+        else:
+            sc.begin(st.grad_weight, self.world, self.opt.param_groups[0]["betas"])
 
     def _reduce_all(self) -> None:
         allreduce_buckets(self.model.flat_g, self._st.buckets if self._st is not None and self._st.buckets else
@@ -179,17 +216,27 @@ class FusedTrainStep:
         """The step as a hipGraph replay: eager for the first two calls of a compiled step (lazily created buffers, kernel attributes), captured at the
         third, replayed afterwards.  A graph holds addresses: it is keyed by the compiled step and by the optimizer's buffers and dropped when they move."""
         opt = self.opt
-        opt.grad_scale = (1.0 / self.world) / getattr(st, "loss_scale", 1.0)
-        opt.advance_dynamic()                     # step count, lr, bias corrections -> 12 bytes of device memory, in stream order, outside the graph
+        sc = self.scaler
+        if sc is None:
+            opt.grad_scale = (1.0 / self.world) / getattr(st, "loss_scale", 1.0)
+            opt.advance_dynamic()                 # step count, lr, bias corrections -> 12 bytes of device memory, in stream order, outside the graph
+        else:
+            opt._ensure_state()
+            self._begin_dynamic(st)               # lr -> the scaler's state; step count, scale and bias corrections are the device's own business
 
         def body():
             P = st.programs
+            if sc is not None:
+                self._begin_dynamic(st, fills=False)
             P["pack"].run(); P["fwd"].run(); P["loss"].run(); P["bwd"].run()
-            opt.launch_dynamic()
+            if sc is None:
+                opt.launch_dynamic()
+            else:
+                self._apply_update(st)
 
         # the entry lives ON the compiled step (a dropped step takes its graph along; no address or id() can be reused under a stale graph)
         ents = st.__dict__.setdefault("_graph_ents", {})
-        key = (id(self), opt.graph_key())
+        key = (id(self), opt.graph_key() if sc is None else (opt.graph_key(dynamic=False), sc.graph_key()))
         ent = ents.get(id(self))
         if ent is None or ent[0] != key:
             ents[id(self)] = ent = [key, 0, None]
@@ -217,6 +264,9 @@ class FusedTrainStep:
         if self.graph and not self.distributed:
             return self._run_graph(st)
         P = st.programs
+        if self.scaler is not None:
+            self._begin_dynamic(st)
+            self._begin_dynamic(st, fills=False)
         P["pack"].run()
         P["fwd"].run()
         P["loss"].run()
@@ -238,8 +288,7 @@ class FusedTrainStep:
             if done < P["bwd"].n:
                 P["bwd"].run(done, P["bwd"].n - done)
             cur.wait_stream(self.comm_stream)
-        self.opt.grad_scale = (1.0 / self.world) / getattr(st, "loss_scale", 1.0)
-        self.opt.step(grads_in_flat=True)
+        self._apply_update(st)
         self.losses = st.plan.loss_out
         self._coop_err = self.model.coop_error_word()      # ONE word per model: every compiled step's kernels set it
         return self.losses
@@ -251,11 +300,13 @@ class FusedTrainStep:
             return
         if self._st is None:
             raise L.MtbcError("run_empty() before any real step: the bucket layout is not known yet")
+        if self.scaler is not None:
+            self._begin_dynamic(self._st)
+            self._begin_dynamic(self._st, fills=False)
         self.model.flat_g.zero_()
         for b in self._st.buckets:
             allreduce_buckets(self.model.flat_g, [b])
-        self.opt.grad_scale = (1.0 / self.world) / getattr(self._st, "loss_scale", 1.0)
-        self.opt.step(grads_in_flat=True)
+        self._apply_update(self._st)
 
     def __call__(self, image, mask, label, weight: Optional[float] = None) -> torch.Tensor:
         return self.run(self.load_batch(image, mask, label, weight))
