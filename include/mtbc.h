@@ -561,6 +561,42 @@ int mtbc_loss_scale_begin_host(const mtbc_loss_scale_args* a);
  * metrics.py:255-267 (training_multitask.py:66-71).  out3 = {tp, fp, fn} as float64.        */
 int mtbc_dice_counts(const float* logits, const float* target, int64_t n, double* out3, void* stream);
 
+/* ------------------------------------------------------------------ per-image test-phase metrics
+ * The integer table behind `results_segmentation.csv` / `results_classification.csv` of the testing phase
+ * (utils/models.py:273-397; metrics.py:26-74 calculate_metrics, :238-252 haussdorf_distance; images.py:41-55): one row of
+ * MTBC_SEGM_COLS int64 values per image, every one exact.  In the reference's order: raw mask = sigmoid(seg_logits) > .5 (the
+ * predicate of the Dice counters above); pixel_threshold > 0 and raw_pixels <= pixel_threshold clears the mask; seg_from_class
+ * and cls_raw == normal_class clears the mask; cls_final = normal_class when class_from_seg and raw_pixels == 0 (the RAW count),
+ * else cls_raw.  The two class rules need n_cls >= 2: the binary head (n_cls == 1, cls = sigmoid > .5) has none (:186-270).
+ *   hd_rows_sq  the square of what the reference reports as "Haussdorf distance": scipy's directed_hausdorff takes each image ROW
+ *               as one point, so it is max over rows of one mask of the smallest Hamming distance to a row of the other (both ways)
+ *   hd_px_sq    the squared Hausdorff distance between the two pixel sets, over every pixel of each set
+ *   both: 0 when both masks are empty, -1 when exactly one is (the reference gives NaN).
+ * H and W: multiples of 16 in [16, 512].  Two launches on `stream`; `out` and `workspace` need no initialisation and are 8-byte
+ * aligned; results are bit-reproducible (integer atomics only).                                                          */
+#define MTBC_SEGM_COLS 9
+#define MTBC_SEGM_TP 0               /* tp, tn, fp, fn of the FINAL predicted mask against the target */
+#define MTBC_SEGM_TN 1
+#define MTBC_SEGM_FP 2
+#define MTBC_SEGM_FN 3
+#define MTBC_SEGM_RAW_PIXELS 4       /* tumour pixels of the raw prediction */
+#define MTBC_SEGM_HD_ROWS_SQ 5
+#define MTBC_SEGM_HD_PX_SQ 6
+#define MTBC_SEGM_CLS_RAW 7          /* argmax of cls_logits (first maximum); -1 without cls_logits */
+#define MTBC_SEGM_CLS_FINAL 8
+typedef struct {
+    int32_t N, H, W, n_cls;          /* n_cls: columns of cls_logits (1 .. 64), unread when cls_logits is NULL */
+    const float* seg_logits;         /* (N,1,H,W) logits of the last segmentation head */
+    const float* target;             /* (N,1,H,W) mask, != 0 is tumour */
+    const float* cls_logits;         /* (N,n_cls) or NULL */
+    int32_t pixel_threshold, seg_from_class, class_from_seg, normal_class;
+    int64_t* out;                    /* (N, MTBC_SEGM_COLS) */
+    void* workspace; size_t workspace_bytes;
+} mtbc_seg_metrics_args;
+/* host only, no GPU call; 0 for a shape the call refuses */
+size_t mtbc_seg_metrics_workspace_size(const mtbc_seg_metrics_args* a);
+int mtbc_seg_metrics(const mtbc_seg_metrics_args* a, void* stream);
+
 /* ---------------------------------------------------------------------------- step program
  * A training step is a static list of the ops above with every pointer resolved at plan
  * time; mtbc_program_run issues them back-to-back on one stream (no host work in between). */

@@ -135,6 +135,19 @@ class LossScaleArgs(C.Structure):
                 ("inv_world", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float)]
 
 
+class SegMetricsArgs(C.Structure):
+    """mtbc_seg_metrics_args (include/mtbc.h)."""
+    _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("n_cls", C.c_int32),
+                ("seg_logits", C.c_void_p), ("target", C.c_void_p), ("cls_logits", C.c_void_p),
+                ("pixel_threshold", C.c_int32), ("seg_from_class", C.c_int32), ("class_from_seg", C.c_int32), ("normal_class", C.c_int32),
+                ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+# columns of the mtbc_seg_metrics table -- keep in sync with the MTBC_SEGM_* defines of include/mtbc.h
+SEGM_COLS = 9
+(SEGM_TP, SEGM_TN, SEGM_FP, SEGM_FN, SEGM_RAW_PIXELS, SEGM_HD_ROWS_SQ, SEGM_HD_PX_SQ, SEGM_CLS_RAW, SEGM_CLS_FINAL) = range(SEGM_COLS)
+
+
 class _PackArgs(C.Structure):
     _fields_ = [("w", C.c_void_p), ("packed", C.c_void_p), ("Cin", C.c_int32), ("Cout", C.c_int32),
                 ("dgrad", C.c_int32), ("compute", C.c_int32)]
@@ -237,6 +250,7 @@ EXPORTS = [
     "mtbc_focal_fwd_bwd", "mtbc_loss_mix", "mtbc_adam_step", "mtbc_adam_dynamic", "mtbc_loss_scale_begin", "mtbc_loss_scale_check", "mtbc_loss_scale_adam",
     "mtbc_loss_scale_update_host", "mtbc_loss_scale_begin_host", "mtbc_dice_counts", "mtbc_program_run",
     "mtbc_program_run_ms", "mtbc_event_create", "mtbc_event_destroy",
+    "mtbc_seg_metrics_workspace_size", "mtbc_seg_metrics",
 ]
 
 ABI_VERSION = 202          # MTBC_VERSION of include/mtbc.h these mirrors follow
@@ -348,6 +362,10 @@ def load() -> C.CDLL:
     lib.mtbc_event_create.argtypes = [C.POINTER(C.c_void_p)]
     lib.mtbc_event_destroy.restype = C.c_int
     lib.mtbc_event_destroy.argtypes = [C.c_void_p]
+    lib.mtbc_seg_metrics_workspace_size.restype = C.c_size_t
+    lib.mtbc_seg_metrics_workspace_size.argtypes = [C.POINTER(SegMetricsArgs)]
+    lib.mtbc_seg_metrics.restype = C.c_int
+    lib.mtbc_seg_metrics.argtypes = [C.POINTER(SegMetricsArgs), C.c_void_p]
     _lib = lib
     return lib
 

@@ -119,6 +119,10 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
+// The sigmoid of the losses and of every `sigmoid(x) > .5` predicate (head_loss.hip: Dice, dice_counts_kernel; seg_metrics.hip): one
+// definition, so a pixel is tumour for all of them or for none.
+__device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
+
 // Block-wide sum; every thread gets the result.  `red` = shared float[17+].  Deterministic.
 __device__ __forceinline__ float block_sum(float v, float* red) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;

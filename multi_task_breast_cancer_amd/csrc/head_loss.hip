@@ -89,7 +89,6 @@ struct DiceP {
     float* stats; float* loss; float* dx[4];
     float gscale; const float* gscale_dev;
 };
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 // block = (plane, head): I = sum p t, P2 = sum p^2, T2 = sum t^2
 __global__ void dice_stats_kernel(const DiceP p) {

@@ -1,21 +1,43 @@
-"""Test-time prediction refining of the multi-task model (second half).
+"""Test-time prediction refining and the testing phase's result tables (second half).
 
 `inference_multitask_multiclass_classification_segmentation` (src/utils/models.py:270-400) runs the model twice
 over the batch-1 test loader and applies two cross-task rules, each on the RAW prediction of the other task:
 
   * overlap_seg_based_on_class (:325-332): predicted class == 2 ("normal") -> the predicted mask is cleared;
-  * overlap_class_based_on_seg (:366-376): no tumour pixel in sigmoid(last head) > .5 -> the predicted class becomes 2.
+  * overlap_class_based_on_seg (:366-376): no tumour pixel in sigmoid(last head) > .5 -> the predicted class becomes 2,
 
-Here both rules are tensor ops on the device for a whole batch (the forward pass is the HIP step program); Hausdorff /
-sensitivity tables and PNG dumps stay the reference's code.
+after the optional `threshold_postprocessing` (images.py:41-55: a raw mask of at most `threshold` pixels is cleared), and writes
+`results_segmentation.csv` (one row per image: metrics.py:26-74) and `results_classification.csv`.
+
+`refine_predictions` / `predict` are the two rules as tensor ops for a whole batch.  `FusedTestStep` is the whole testing
+phase on the device: the compiled forward programs, then `seg_metrics` (csrc/seg_metrics.hip) turns the last head's logits,
+the mask and the class logits into an exact integer table per image -- confusion counts of the final mask, the raw pixel
+count, the reference's row-wise "Haussdorf distance" and the Hausdorff distance of the pixel sets, the class before and after
+its rule -- with no host round trip per image or per batch; `metrics_from_table` turns it into the reference's columns and
+`write_csv` into its two files.  `classification_report` restates the sklearn summaries of metrics.py:387-458 in numpy.
+PNG dumps and the xlsx aggregation are not covered (the reference's own `save_*_results` reads the two CSV files).
 """
 from __future__ import annotations
 
-from typing import List, Sequence, Tuple, Union
+import csv
+import math
+import os
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
+import numpy as np
 import torch
 
+from . import _lib as L
+
 NORMAL_CLASS = 2
+_E_BADSHAPE = -1       # MTBC_E_BADSHAPE
+
+# results_segmentation.csv (utils/models.py:297-298); the pixel-set Hausdorff distance goes last, after the reference's columns
+SEG_METRIC_COLUMNS = ("Haussdorf distance", "DICE", "Sensitivity", "Specificity", "Accuracy", "Jaccard index", "Precision")
+HAUSDORFF_PIXELS = "Hausdorff (pixels)"
+SEG_CSV_COLUMNS = ("patient_id",) + SEG_METRIC_COLUMNS + ("class", HAUSDORFF_PIXELS)
+# results_classification.csv (:389-394; the binary head writes the first three, :262-266)
+CLS_CSV_COLUMNS = ("patient_id", "ground_truth", "predicted_label", "prob_benign", "prob_malignant", "prob_normal")
 
 
 def _last(x):
@@ -52,3 +74,221 @@ def predict(model, images: torch.Tensor, overlap_seg_based_on_class: bool = True
     seg, cls = refine_predictions(logits, segs, overlap_seg_based_on_class, overlap_class_based_on_seg)
     lg = _mean_logits(logits)
     return seg, cls, torch.softmax(lg.view(lg.shape[0], -1), dim=1)
+
+
+# ------------------------------------------------------------------------------------------------
+# the testing phase: per-image tables on the device
+# ------------------------------------------------------------------------------------------------
+def seg_metrics(seg_logits: torch.Tensor, target: torch.Tensor, cls_logits: Optional[torch.Tensor] = None,
+                pixel_threshold: int = 0, seg_from_class: bool = False, class_from_seg: bool = False) -> torch.Tensor:
+    """mtbc_seg_metrics: (N,1,H,W) logits of the last head, (N,1,H,W) mask, optional (N,K) class logits -> int64 (N, SEGM_COLS)
+    on the device (columns `_lib.SEGM_*`).  Two launches on the current stream, nothing is read back."""
+    import ctypes as C
+    if seg_logits.dim() != 4 or seg_logits.shape[1] != 1 or tuple(target.shape) != tuple(seg_logits.shape):
+        raise ValueError(f"expected (N,1,H,W) logits and a mask of the same shape, got {tuple(seg_logits.shape)} / {tuple(target.shape)}")
+    if seg_logits.device.type != "cuda":
+        L.require_gpu()
+        raise L.MtbcError("seg_metrics needs device tensors (no CPU path)")
+    x, t = seg_logits.contiguous().float(), target.contiguous().float()
+    a = L.SegMetricsArgs()
+    a.N, a.H, a.W = x.shape[0], x.shape[2], x.shape[3]
+    a.seg_logits, a.target = x.data_ptr(), t.data_ptr()
+    lg = None
+    if cls_logits is not None:
+        lg = cls_logits.reshape(x.shape[0], -1).contiguous().float()
+        a.n_cls, a.cls_logits = lg.shape[1], lg.data_ptr()
+    a.pixel_threshold, a.seg_from_class, a.class_from_seg, a.normal_class = int(pixel_threshold), int(bool(seg_from_class)), int(bool(class_from_seg)), NORMAL_CLASS
+    lib = L.load()
+    nbytes = lib.mtbc_seg_metrics_workspace_size(C.byref(a))
+    if nbytes == 0:
+        L.check(_E_BADSHAPE, f"seg_metrics (N, H, W) = ({a.N}, {a.H}, {a.W}): H and W must be multiples of 16 in [16, 512]")
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=x.device)
+    out = torch.empty(x.shape[0], L.SEGM_COLS, dtype=torch.int64, device=x.device)
+    a.out, a.workspace, a.workspace_bytes = out.data_ptr(), ws.data_ptr(), nbytes
+    L.check(lib.mtbc_seg_metrics(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "seg_metrics")
+    return out
+
+
+
+def metrics_from_table(table) -> Dict[str, np.ndarray]:
+    """Integer table (M, SEGM_COLS) -> the reference's per-image columns as float64 arrays, its conventions included
+    (metrics.py:175-252): sensitivity / precision NaN when tp == 0; DICE / Jaccard 1 or 0 on an empty ground truth; Hausdorff 0 for
+    two empty masks and NaN for exactly one.  The same integers through the same formula, so the values equal the reference's bit
+    for bit.  (Specificity of a mask with no background pixel is NaN here; the reference divides by zero and raises.)"""
+    t = np.asarray(table.cpu() if isinstance(table, torch.Tensor) else table).astype(np.int64).reshape(-1, L.SEGM_COLS)
+    tp, tn, fp, fn = (t[:, c].astype(np.float64) for c in (L.SEGM_TP, L.SEGM_TN, L.SEGM_FP, L.SEGM_FN))
+    nan = np.full(tp.shape, np.nan)
+
+    def div(num, den, where, other):
+        return np.where(where, np.divide(num, den, out=np.zeros_like(num), where=where & (den != 0)), other)
+
+    def root(sq):
+        sq = sq.astype(np.float64)
+        return np.where(sq < 0, np.nan, np.sqrt(np.maximum(sq, 0.0)))
+
+    gt_empty, seg_empty = (tp + fn) == 0, (tp + fp) == 0
+    empty_score = np.where(seg_empty, 1.0, 0.0)
+    return {
+        "Haussdorf distance": root(t[:, L.SEGM_HD_ROWS_SQ]),
+        "DICE": div(2 * tp, 2 * tp + fp + fn, ~gt_empty, empty_score),
+        "Sensitivity": div(tp, tp + fn, tp != 0, nan),
+        "Specificity": div(tn, tn + fp, (tn + fp) != 0, nan),
+        "Accuracy": div(tp + tn, tp + tn + fp + fn, np.ones(tp.shape, bool), nan),
+        "Jaccard index": div(tp, tp + fp + fn, ~gt_empty, empty_score),
+        "Precision": div(tp, tp + fp, tp != 0, nan),
+        HAUSDORFF_PIXELS: root(t[:, L.SEGM_HD_PX_SQ]),
+    }
+
+
+def classification_report(ground_truth, predicted, labels: Sequence[int] = (0, 1, 2)) -> Dict[str, float]:
+    """`multiclass_classification_metrics` (metrics.py:407-458: sklearn precision / recall / f1 per class, macro, micro, weighted, and
+    accuracy_score) from the confusion counts, a zero denominator giving 0 as sklearn's zero_division default does; with two labels the
+    five keys of `binary_classification_metrics` (:387-400, the reference's own NaN conventions; label 1 is the positive class)."""
+    gt = np.asarray(ground_truth).astype(np.int64).reshape(-1)
+    pr = np.asarray(predicted).astype(np.int64).reshape(-1)
+    if gt.shape != pr.shape or gt.size == 0:
+        raise ValueError("ground_truth and predicted must be non-empty and of equal length")
+    labels = list(labels)
+
+    def safe(num, den):
+        num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
+        return np.divide(num, den, out=np.zeros(np.broadcast(num, den).shape), where=den != 0)
+
+    if len(labels) == 2:
+        neg, pos = labels
+        tp, tn = float(np.sum((gt == pos) & (pr == pos))), float(np.sum((gt == neg) & (pr == neg)))
+        fp, fn = float(np.sum((gt == neg) & (pr == pos))), float(np.sum((gt == pos) & (pr == neg)))
+        return {"Precision": tp / (tp + fp) if tp else math.nan, "Sensitivity": tp / (tp + fn) if tp else math.nan,
+                "Specificity": tn / (tn + fp) if tn + fp else math.nan, "Accuracy": (tp + tn) / (tp + tn + fp + fn),
+                "F1 score": 2 * tp / (2 * tp + fp + fn) if 2 * tp + fp + fn else math.nan}
+    tp = np.array([np.sum((gt == c) & (pr == c)) for c in labels], np.float64)
+    pred_sum = np.array([np.sum(pr == c) for c in labels], np.float64)
+    true_sum = np.array([np.sum(gt == c) for c in labels], np.float64)
+    out: Dict[str, float] = {}
+    for name, per_class, micro in (("precision", safe(tp, pred_sum), safe(tp.sum(), pred_sum.sum())),
+                                   ("recall", safe(tp, true_sum), safe(tp.sum(), true_sum.sum())),
+                                   ("f1", safe(2 * tp, pred_sum + true_sum), safe(2 * tp.sum(), pred_sum.sum() + true_sum.sum()))):
+        for n, v in enumerate(per_class):
+            out[f"{name}_class_{n}"] = float(v)
+        out[f"{name}_macro"] = float(per_class.mean())
+        out[f"{name}_micro"] = float(micro)
+        out[f"{name}_weighted"] = float(safe((per_class * true_sum).sum(), true_sum.sum()))
+    out["accuracy"] = float(np.mean(gt == pr))
+    return out
+
+
+def _csv_value(v):
+    if isinstance(v, (float, np.floating)):
+        return "" if math.isnan(v) else repr(float(v))          # an empty field is how pandas writes (and reads back) NaN
+    if isinstance(v, (np.integer,)):
+        return int(v)
+    return v
+
+
+def write_result_csvs(path: str, segmentation_rows: Sequence[dict], classification_rows: Sequence[dict]) -> Tuple[str, str]:
+    """`results_segmentation.csv` and `results_classification.csv` under `path`, the reference's columns in its order."""
+    os.makedirs(path, exist_ok=True)
+    seg_file, cls_file = os.path.join(path, "results_segmentation.csv"), os.path.join(path, "results_classification.csv")
+    cls_cols = [c for c in CLS_CSV_COLUMNS if not classification_rows or c in classification_rows[0]]
+    for file, cols, rows in ((seg_file, SEG_CSV_COLUMNS, segmentation_rows), (cls_file, cls_cols, classification_rows)):
+        with open(file, "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(cols)
+            for r in rows:
+                w.writerow([_csv_value(r[c]) for c in cols])
+    return seg_file, cls_file
+
+
+class FusedTestStep:
+    """The testing phase of a fold (training_multitask.py:296-308 -> utils/models.py:273-397; binary head: :186-270) in batches on the
+    device.  Per batch: the compiled `pack` + `fwd` programs of the batch shape, then `seg_metrics` on the last segmentation head and
+    the class logits where the programs left them; the (N, SEGM_COLS) integer table, the class logits and the labels stay on the
+    device.  `result()` reads everything back once and returns `(segmentation_rows, classification_rows)`, lists of dicts keyed by
+    the reference's CSV columns; `write_csv(path)` writes its two files.  The arguments default to the reference's signature
+    defaults (config keys `threshold_postprocessing`, `overlap_seg_based_on_class`, `overlap_class_based_on_seg`); the binary head
+    (model.n_classes == 1) has no rules in the reference and takes none here."""
+
+    def __init__(self, model, pixel_threshold: int = 0, overlap_seg_based_on_class: bool = False,
+                 overlap_class_based_on_seg: bool = False):
+        self.model = model
+        self.binary = getattr(model, "n_classes", 3) == 1
+        if self.binary and (pixel_threshold or overlap_seg_based_on_class or overlap_class_based_on_seg):
+            raise ValueError("the binary head's testing phase has no post-processing rules (utils/models.py:186-270)")
+        if int(pixel_threshold) < 0:
+            raise ValueError("pixel_threshold must be >= 0 (0 = off)")
+        self.pixel_threshold = int(pixel_threshold)
+        self.seg_from_class, self.class_from_seg = bool(overlap_seg_based_on_class), bool(overlap_class_based_on_seg)
+        self.reset()
+
+    def reset(self) -> None:
+        self._tables: List[torch.Tensor] = []      # device int64 (N, SEGM_COLS) per batch
+        self._logits: List[torch.Tensor] = []      # device float32 (N, K) per batch
+        self._labels: List[torch.Tensor] = []      # device int64 (N,) per batch
+        self._ids: list = []
+        self._classes: list = []
+        self._coop_err = None
+
+    @staticmethod
+    def _as_list(v, n: int) -> list:
+        if isinstance(v, torch.Tensor):
+            v = v.reshape(-1).tolist()
+        elif isinstance(v, np.ndarray):
+            v = v.reshape(-1).tolist()
+        elif isinstance(v, (str, bytes)) or not hasattr(v, "__len__"):
+            v = [v]
+        v = list(v)
+        if len(v) != n:
+            raise ValueError(f"expected {n} values per batch, got {len(v)}")
+        return v
+
+    @torch.no_grad()
+    def __call__(self, image: torch.Tensor, mask: torch.Tensor, label: torch.Tensor, patient_id=None, class_name=None) -> None:
+        N, _, H, W = image.shape
+        st = self.model.compiled(N, H, W)
+        st.x.data.copy_(image, non_blocking=True)
+        dev = st.x.data.device
+        st.programs["pack"].run()
+        st.programs["fwd"].run()
+        self._coop_err = self.model.coop_error_word()
+        logits = st.logits.data.view(N, -1)
+        table = seg_metrics(st.segs[-1].data, mask.to(dev, non_blocking=True), logits, self.pixel_threshold,
+                            self.seg_from_class, self.class_from_seg)
+        self._tables.append(table)
+        self._logits.append(logits.clone())                      # the plan's buffer is rewritten by the next batch of this shape
+        self._labels.append(label.to(dev, non_blocking=True).reshape(-1).to(torch.int64))
+        first = len(self._ids)
+        self._ids += list(range(first, first + N)) if patient_id is None else self._as_list(patient_id, N)
+        self._classes += [None] * N if class_name is None else self._as_list(class_name, N)
+
+    def result(self) -> Tuple[List[dict], List[dict]]:
+        if not self._tables:
+            raise L.MtbcError("FusedTestStep.result() before any batch was evaluated")
+        table, logits, labels = torch.cat(self._tables), torch.cat(self._logits), torch.cat(self._labels)
+        M, K = logits.shape
+        err = self._coop_err
+        flat = torch.cat([table.double().flatten(), logits.double().flatten(), labels.double(),
+                          (err if err is not None else labels[:1] * 0).double().flatten()]).cpu().numpy()     # the one read-back
+        if flat[-1] != 0.0:
+            raise L.MtbcError("cooperative InstanceNorm: a mailbox poll timed out (team members were not co-resident): the "
+                              "activations of this evaluation are invalid")
+        table = flat[:M * L.SEGM_COLS].astype(np.int64).reshape(M, L.SEGM_COLS)
+        logits = flat[M * L.SEGM_COLS:M * (L.SEGM_COLS + K)].reshape(M, K)
+        labels = flat[M * (L.SEGM_COLS + K):M * (L.SEGM_COLS + K + 1)].astype(np.int64)
+        self.table = table                                        # the integers behind the rows
+        cols = metrics_from_table(table)
+        seg_rows, cls_rows = [], []
+        for i in range(M):
+            row = {"patient_id": self._ids[i]}
+            row.update({c: float(cols[c][i]) for c in SEG_METRIC_COLUMNS})
+            row["class"] = int(labels[i]) if self._classes[i] is None else self._classes[i]
+            row[HAUSDORFF_PIXELS] = float(cols[HAUSDORFF_PIXELS][i])
+            seg_rows.append(row)
+            crow = {"patient_id": self._ids[i], "ground_truth": int(labels[i]), "predicted_label": int(table[i, L.SEGM_CLS_FINAL])}
+            if not self.binary:                                   # the reference's "prob_*" columns hold the mean class LOGITS (:363)
+                crow.update({c: float(v) for c, v in zip(CLS_CSV_COLUMNS[3:], logits[i])})
+            cls_rows.append(crow)
+        return seg_rows, cls_rows
+
+    def write_csv(self, path: str) -> Tuple[str, str]:
+        seg_rows, cls_rows = self.result()
+        return write_result_csvs(path, seg_rows, cls_rows)
