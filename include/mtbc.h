@@ -644,6 +644,32 @@ int mtbc_convT_head_expand(const mtbc_head_fuse_args* a, void* stream);
 int mtbc_augment_flip_rotate(const float* src, float* dst, const float* params, int32_t N, int32_t C, int32_t H, int32_t W,
                              void* stream);
 
+/* ---- batch assembly from a device-resident uint8 dataset: ONE launch from a device index array to the fp32
+ * input buffers of a step.  Sample n of the batch is store row index[n] (BUSI_dataset.py:97-158, training_multitask.py:82-84):
+ *   out_image (N, 1 + K, H, W)   channel 0 = the raw image, channel 1 + k = luts[k][pixel] (the intensity variants of
+ *                                `data.augmentation`, BUSI_dataset.py:123-139, in the reference's append order)
+ *   out_mask  (N, 1, H, W)
+ *   out_target                   n_onehot == 3: one-hot (N, 3) of the label; n_onehot == 0: the float label (N, 1) of the binary head
+ * params (N, 4) = {cos a, sin a, flip_h, flip_v} per sample as for the augmentation call above, applied jointly to every plane
+ * with the same source pixel and zero fill outside the rotated frame (the LUT planes too); NULL = identity (validation, test).
+ * Every output element is written by this launch alone (no atomics, no workspace); any H, W > 0.  An index outside [0, M) never
+ * reads the stores: that sample's planes and target are written as zeros.  MTBC_E_BADARG: a null pointer (luts may be NULL with
+ * K == 0) or an output that overlaps another buffer; MTBC_E_BADSHAPE: a non-positive size, K outside [0, MTBC_BATCH_MAX_LUTS],
+ * n_onehot outside {0, 3}.                                                                                                 */
+#define MTBC_BATCH_MAX_LUTS 4
+typedef struct {
+    int32_t M, N, H, W;              /* store rows, batch size, plane size */
+    int32_t K, n_onehot;             /* look-up tables (0 .. MTBC_BATCH_MAX_LUTS); 3 = one-hot target, 0 = float label */
+    const uint8_t* images;           /* (M, H, W) */
+    const uint8_t* masks;            /* (M, H, W), values {0, 1} */
+    const int32_t* labels;           /* (M) */
+    const int32_t* index;            /* (N) device array of store rows */
+    const float* params;             /* (N, 4) or NULL */
+    const uint8_t* luts;             /* (K, 256) */
+    float* out_image; float* out_mask; float* out_target;
+} mtbc_batch_args;
+int mtbc_batch_assemble(const mtbc_batch_args* a, void* stream);
+
 typedef struct {
     int32_t kind;
     int32_t tag;                     /* free for the caller (layer id) */

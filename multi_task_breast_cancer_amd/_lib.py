@@ -143,6 +143,16 @@ class SegMetricsArgs(C.Structure):
                 ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+class BatchArgs(C.Structure):
+    """mtbc_batch_args (include/mtbc.h)."""
+    _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("K", C.c_int32), ("n_onehot", C.c_int32),
+                ("images", C.c_void_p), ("masks", C.c_void_p), ("labels", C.c_void_p), ("index", C.c_void_p),
+                ("params", C.c_void_p), ("luts", C.c_void_p),
+                ("out_image", C.c_void_p), ("out_mask", C.c_void_p), ("out_target", C.c_void_p)]
+
+
+BATCH_MAX_LUTS = 4         # MTBC_BATCH_MAX_LUTS of include/mtbc.h
+
 # columns of the mtbc_seg_metrics table -- keep in sync with the MTBC_SEGM_* defines of include/mtbc.h
 SEGM_COLS = 9
 (SEGM_TP, SEGM_TN, SEGM_FP, SEGM_FN, SEGM_RAW_PIXELS, SEGM_HD_ROWS_SQ, SEGM_HD_PX_SQ, SEGM_CLS_RAW, SEGM_CLS_FINAL) = range(SEGM_COLS)
@@ -250,7 +260,7 @@ EXPORTS = [
     "mtbc_focal_fwd_bwd", "mtbc_loss_mix", "mtbc_adam_step", "mtbc_adam_dynamic", "mtbc_loss_scale_begin", "mtbc_loss_scale_check", "mtbc_loss_scale_adam",
     "mtbc_loss_scale_update_host", "mtbc_loss_scale_begin_host", "mtbc_dice_counts", "mtbc_program_run",
     "mtbc_program_run_ms", "mtbc_event_create", "mtbc_event_destroy",
-    "mtbc_seg_metrics_workspace_size", "mtbc_seg_metrics",
+    "mtbc_seg_metrics_workspace_size", "mtbc_seg_metrics", "mtbc_batch_assemble",
 ]
 
 ABI_VERSION = 202          # MTBC_VERSION of include/mtbc.h these mirrors follow
@@ -366,6 +376,8 @@ def load() -> C.CDLL:
     lib.mtbc_seg_metrics_workspace_size.argtypes = [C.POINTER(SegMetricsArgs)]
     lib.mtbc_seg_metrics.restype = C.c_int
     lib.mtbc_seg_metrics.argtypes = [C.POINTER(SegMetricsArgs), C.c_void_p]
+    lib.mtbc_batch_assemble.restype = C.c_int
+    lib.mtbc_batch_assemble.argtypes = [C.POINTER(BatchArgs), C.c_void_p]
     _lib = lib
     return lib
 

@@ -28,16 +28,8 @@ __global__ void augment_flip_rotate_kernel(const AugP p) {
     const int rem = (int)(idx % HW), y = rem / p.W, x = rem % p.W;
     const float ca = p.params[4 * n], sa = p.params[4 * n + 1];
     const bool fh = p.params[4 * n + 2] != 0.f, fv = p.params[4 * n + 3] != 0.f;
-    const float xo = (float)x - 0.5f * (float)p.W + 0.5f, yo = (float)y - 0.5f * (float)p.H + 0.5f;
-    const float hw = 0.5f * (float)p.W, hh = 0.5f * (float)p.H;
-    const float gx = fmaf(yo, -sa / hw, xo * (ca / hw));
-    const float gy = fmaf(yo, ca / hh, xo * (sa / hh));
-    const float ix = ((gx + 1.f) * (float)p.W - 1.f) * 0.5f, iy = ((gy + 1.f) * (float)p.H - 1.f) * 0.5f;
-    const float rx = nearbyintf(ix), ry = nearbyintf(iy);
-    const bool inb = rx >= 0.f && rx < (float)p.W && ry >= 0.f && ry < (float)p.H;
-    int xs = inb ? (int)rx : 0, ys = inb ? (int)ry : 0;
-    if (fh) xs = p.W - 1 - xs;
-    if (fv) ys = p.H - 1 - ys;
+    int xs, ys;
+    const bool inb = flip_rotate_src(x, y, p.H, p.W, ca, sa, fh, fv, xs, ys);
     const float* s = p.src + (size_t)n * p.C * HW + (size_t)ys * p.W + xs;
     float* d = p.dst + (size_t)n * p.C * HW + rem;
     for (int c = 0; c < p.C; ++c) d[(size_t)c * HW] = inb ? s[(size_t)c * HW] : 0.f;

@@ -123,6 +123,23 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 // definition, so a pixel is tumour for all of them or for none.
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
 
+// Source pixel of output pixel (x, y) under RandomHorizontalFlip -> RandomVerticalFlip -> RandomRotation (torchvision: nearest, zero fill,
+// centre rotation; the derivation is at the top of augment.hip): false = outside the rotated frame (the output is 0), else (xs, ys) is the pixel to
+// read.  ONE definition for augment.hip and batch_loader.hip: the two kernels gather the same pixel, operation for operation.
+__device__ __forceinline__ bool flip_rotate_src(int x, int y, int H, int W, float ca, float sa, bool fh, bool fv, int& xs, int& ys) {
+    const float xo = (float)x - 0.5f * (float)W + 0.5f, yo = (float)y - 0.5f * (float)H + 0.5f;
+    const float hw = 0.5f * (float)W, hh = 0.5f * (float)H;
+    const float gx = fmaf(yo, -sa / hw, xo * (ca / hw));
+    const float gy = fmaf(yo, ca / hh, xo * (sa / hh));
+    const float ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f, iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
+    const float rx = nearbyintf(ix), ry = nearbyintf(iy);
+    const bool inb = rx >= 0.f && rx < (float)W && ry >= 0.f && ry < (float)H;
+    xs = inb ? (int)rx : 0; ys = inb ? (int)ry : 0;
+    if (fh) xs = W - 1 - xs;
+    if (fv) ys = H - 1 - ys;
+    return inb;
+}
+
 // Block-wide sum; every thread gets the result.  `red` = shared float[17+].  Deterministic.
 __device__ __forceinline__ float block_sum(float v, float* red) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;

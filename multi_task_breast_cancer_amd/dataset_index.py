@@ -81,6 +81,11 @@ class EpochIndex:
         lo = rank * per + min(rank, extra)
         return lo, lo + per + (1 if rank < extra else 0)
 
+    def shard_bounds(self, n_batch: int, rank: Optional[int] = None):
+        """[lo, hi) of rank `rank` (default: this rank) inside a global batch of `n_batch` rows -- the cut `batches` and `weights` make; whatever is
+        laid out per row of the global epoch order (augmentation parameters, device_data.EpochTables) is cut with the same bounds."""
+        return self._bounds(int(n_batch), self.rank if rank is None else int(rank))
+
     def batches(self, epoch: int) -> Iterator[np.ndarray]:
         perm = self.permutation(epoch)
         for b in range(len(self)):

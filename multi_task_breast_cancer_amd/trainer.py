@@ -182,12 +182,29 @@ class FusedTrainStep:
         else:
             st.onehot.zero_()
             st.onehot.scatter_(1, lab.to(torch.int64).view(-1, 1), 1.0)
+        self._set_shard_weight(st, weight)
+        return st
+
+    def _set_shard_weight(self, st, weight: Optional[float]) -> None:
+        """The shard weight (and, under a dynamic loss scale, its word of the scaler's state) of the batch just loaded: fills in stream order."""
         w = 1.0 if weight is None else float(weight) * self.world
         if self.scaler is None:
             st.grad_weight.fill_(w)
         else:                       # `begin` writes shard weight x scale into st.grad_weight on the device; the weight has a word of its own in the scaler's state
             self.scaler.ensure(st.grad_weight.device)
             self.scaler.set_shard_weight(w)
+
+    def load_indexed(self, dataset, index, params, weight: Optional[float] = None):
+        """`load_batch` from a device-resident dataset (device_data.DeviceDataset): ONE launch gathers rows `index` of the uint8 stores under the
+        per-sample flip / rotation `params` (None = identity) straight into the plan's static buffers -- image and its intensity channels, mask,
+        class target -- with no intermediate tensor and no host-to-device transfer when `index` / `params` are device tensors (EpochTables.batch).
+        In stream order in front of the step and, with graph=True, outside the replayed region, where `load_batch` sits.  `weight` as in `load_batch`."""
+        if self.model.in_channels != 1 + dataset.n_augments:
+            raise ValueError(f"the model reads {self.model.in_channels} input channels, the dataset gives 1 + {dataset.n_augments}: build the model with "
+                             f"sequences + dataset.n_augments (experiment_init.load_multitask_experiment_artefacts(n_augments=...))")
+        st = self._compiled(len(index), dataset.H, dataset.W)
+        dataset.assemble(index, params, n_onehot=0 if self.binary else 3, out=(st.x.data, st.mask, st.onehot))
+        self._set_shard_weight(st, weight)
         return st
 
     def _apply_update(self, st) -> None:
@@ -387,8 +404,7 @@ class FusedEvalStep:
     @torch.no_grad()
     def __call__(self, image: torch.Tensor, mask: torch.Tensor, label: torch.Tensor) -> None:
         N, _, H, W = image.shape
-        st = self.model.compiled(N, H, W, fused_loss={"alpha": self.alpha, "inversely_weighted": self.iw,
-                                                      "focal_weight": self.focal_weight, "binary": self.binary, "cls_gamma": self.cls_gamma})
+        st = self._compiled(N, H, W)
         st.x.data.copy_(image, non_blocking=True)
         st.mask.copy_(mask, non_blocking=True)
         dev = st.plan.loss_out.device
@@ -398,6 +414,25 @@ class FusedEvalStep:
         else:
             st.onehot.zero_()
             st.onehot.scatter_(1, lab.to(torch.int64).view(-1, 1), 1.0)
+        self._evaluate(st, lab.to(torch.int64) if self.binary else None)
+
+    def _compiled(self, N: int, H: int, W: int):
+        return self.model.compiled(N, H, W, fused_loss={"alpha": self.alpha, "inversely_weighted": self.iw,
+                                                        "focal_weight": self.focal_weight, "binary": self.binary, "cls_gamma": self.cls_gamma})
+
+    @torch.no_grad()
+    def indexed(self, dataset, index) -> None:
+        """`__call__` from a device-resident dataset (device_data.DeviceDataset): rows `index` go into the plan's buffers in one launch (identity
+        transform), then the same step program and the same device accumulators."""
+        if self.model.in_channels != 1 + dataset.n_augments:
+            raise ValueError(f"the model reads {self.model.in_channels} input channels, the dataset gives 1 + {dataset.n_augments}")
+        st = self._compiled(len(index), dataset.H, dataset.W)
+        dataset.assemble(index, None, n_onehot=0 if self.binary else 3, out=(st.x.data, st.mask, st.onehot))
+        self._evaluate(st, st.onehot[:, 0].to(torch.int64) if self.binary else None)
+
+    def _evaluate(self, st, gt_binary: Optional[torch.Tensor]) -> None:
+        """Forward + losses + metrics of the batch resident in the plan's buffers; gt_binary = the {0, 1} labels of the binary head."""
+        N, dev = st.N, st.plan.loss_out.device
         P = st.programs
         P["pack"].run()
         P["fwd"].run()
@@ -415,7 +450,7 @@ class FusedEvalStep:
         self._acc[:3] += st.plan.loss_out[:3].double()
         if self.binary:
             pred = (torch.sigmoid(logit[:, 0]) > 0.5).to(torch.int64)
-            gt = lab.to(torch.int64)
+            gt = gt_binary
         else:
             pred = logit.argmax(dim=1)
             gt = st.onehot.argmax(dim=1)
@@ -449,4 +484,66 @@ def validate_one_epoch(step: FusedEvalStep, loader, device) -> tuple:
     step.reset()
     for data in loader:
         step(data["image"].to(device), data["mask"].to(device), data["label"].to(device))
+    return step.result()
+
+
+# ------------------------------------------------------------------------------------------------
+# epochs from a device-resident dataset (device_data.py, csrc/batch_loader.hip)
+# ------------------------------------------------------------------------------------------------
+def _check_tables(dataset, tables) -> None:
+    if len(tables.batches) and (tables.index_min < 0 or tables.index_max >= len(dataset)):      # host copies kept by EpochTables: no transfer
+        raise ValueError(f"epoch tables hold indices in [{tables.index_min}, {tables.index_max}], the dataset has {len(dataset)} rows")
+
+
+def train_one_epoch(step: FusedTrainStep, dataset, tables, lr: Optional[float] = None) -> tuple:
+    """The batch loop of training_multitask.py:74-103 on the fused step with no host work per batch: `dataset` is a
+    device_data.DeviceDataset, `tables` the epoch's device_data.EpochTables.  Per batch: one assembly launch into the plan's buffers
+    (`load_indexed`) and the step; the loss words are summed on the device in float64, read back once at the end of the epoch together
+    with ONE `check_nan()` (a NaN in any step's loss ends the run like the reference's guard, criterions.py:72-76).  Nothing is copied
+    from host to device inside the loop.  The short last batch of drop_last=False compiles (once) a second plan.  Under data parallel
+    each batch carries this rank's share `weight`, and a rank whose shard of the last batch is empty calls `run_empty()`.
+    `lr`: written into the optimizer's parameter groups first (the scheduler's value of the epoch).
+
+    Returns (avg_total, avg_seg, avg_cls): means over the batches this rank ran, as `training_loss / len(training_loader)` (:110).
+    The reference's training-time Dice, accuracy and F1 (:107-113) are NOT returned: they need the step's outputs to survive the
+    backward pass, which reuses their memory -- a change of its own."""
+    _check_tables(dataset, tables)
+    if lr is not None:
+        for group in step.opt.param_groups:
+            group["lr"] = float(lr)
+    acc = None                    # device float64: [sum total, sum seg, sum cls, sum of the steps' NaN flags]
+    ran = 0
+    for b in range(len(tables)):
+        index, params, n_local, weight = tables.batch(b)
+        if n_local == 0:
+            step.run_empty()
+            continue
+        losses = step.run(step.load_indexed(dataset, index, params, weight if step.distributed else None))
+        if acc is None:
+            acc = torch.zeros(4, dtype=torch.float64, device=losses.device)
+        acc += losses[:4].double()
+        ran += 1
+    if acc is None:
+        return 0.0, 0.0, 0.0
+    step.check_nan()
+    total, seg, cls, nan = acc.cpu().tolist()
+    if nan != 0.0 or total != total:
+        import logging
+        import sys
+        logging.info("NaN in model loss!!")
+        sys.exit(1)
+    return total / ran, seg / ran, cls / ran
+
+
+def validate_one_epoch_indexed(step: FusedEvalStep, dataset, tables) -> tuple:
+    """`validate_one_epoch` from a device-resident dataset: the batches of `tables` (built without transforms: the identity path), one
+    assembly launch each; the reference's 6-tuple, read back once."""
+    _check_tables(dataset, tables)
+    if tables.params is not None:
+        raise ValueError("validation runs without transforms (training_multitask.py:199-201): build the tables with transforms=None")
+    step.reset()
+    for b in range(len(tables)):
+        index, _, n_local, _ = tables.batch(b)
+        if n_local:
+            step.indexed(dataset, index)
     return step.result()
