@@ -597,6 +597,34 @@ typedef struct {
 size_t mtbc_seg_metrics_workspace_size(const mtbc_seg_metrics_args* a);
 int mtbc_seg_metrics(const mtbc_seg_metrics_args* a, void* stream);
 
+/* ------------------------------------------------------------------ training-time metrics
+ * The counts behind the Train_dice / Train_acc / Train_F1 columns of the reference's epoch loop (training_multitask.py:105-113),
+ * appended on the device by a call that sits between a step's loss ops and its backward ops (the backward reuses the outputs'
+ * memory).  Two stream-ordered launches, no host involvement, integer atomics only (bit-reproducible):
+ *   pixels   tp / fp / fn of (sigmoid(seg_logits) > .5 -- the predicate of the Dice counters above) against mask != 0 over the
+ *            WHOLE batch (process_segmentation_predicted, :65-71), added to table[cursor][0..2]
+ *   samples  predicted class = first maximum of the logits row, a NaN counting as the maximum (torch.argmax of the softmax,
+ *            :41-46), true class = first maximum of the target row; n_logits == 1: sigmoid(logit) > .5 against target != 0
+ *            (:53-61).  conf[true][predicted] += 1, table[cursor][3] += N, then cursor += 1.
+ * The row index lives in device memory (state[0]) because a replayed hipGraph holds fixed arguments.  With cursor >= capacity
+ * nothing is added to `table` or `conf`; state[1] counts such calls (with N > 0) and the cursor still advances.  N == 0 with
+ * n_seg == 0 is the empty shard of a data-parallel rank: the cursor advances and nothing else happens, so that row b is global
+ * batch b on every rank (the data pointers may then be NULL).  The caller zeroes table, conf and state before the first call.
+ * MTBC_E_BADARG: a null pointer; MTBC_E_BADSHAPE: n_logits outside 1 .. 3, a negative count, N == 0 without n_seg == 0.     */
+typedef struct {
+    const float* seg_logits;         /* last segmentation head, fp32, n_seg = N*C*H*W elements */
+    const float* mask;               /* the step's mask buffer, same element count */
+    int64_t      n_seg;
+    const float* cls_logits;         /* (N, n_logits) fp32 */
+    const float* target;             /* (N, n_logits): one-hot rows, or the {0,1} label when n_logits == 1 */
+    int32_t      N, n_logits;
+    int64_t*     table;              /* [capacity][4]: tp, fp, fn, samples -- one row per batch */
+    int64_t*     conf;               /* [3][3] rows = ground truth, cols = prediction */
+    int32_t*     state;              /* [0] cursor = batches seen, [1] batches dropped (cursor >= capacity) */
+    int32_t      capacity;
+} mtbc_train_metrics_args;
+int mtbc_train_metrics(const mtbc_train_metrics_args* a, void* stream);
+
 /* ---------------------------------------------------------------------------- step program
  * A training step is a static list of the ops above with every pointer resolved at plan
  * time; mtbc_program_run issues them back-to-back on one stream (no host work in between). */

@@ -151,6 +151,13 @@ class BatchArgs(C.Structure):
                 ("out_image", C.c_void_p), ("out_mask", C.c_void_p), ("out_target", C.c_void_p)]
 
 
+class TrainMetricsArgs(C.Structure):
+    """mtbc_train_metrics_args (include/mtbc.h)."""
+    _fields_ = [("seg_logits", C.c_void_p), ("mask", C.c_void_p), ("n_seg", C.c_int64), ("cls_logits", C.c_void_p), ("target", C.c_void_p),
+                ("N", C.c_int32), ("n_logits", C.c_int32), ("table", C.c_void_p), ("conf", C.c_void_p), ("state", C.c_void_p),
+                ("capacity", C.c_int32)]
+
+
 BATCH_MAX_LUTS = 4         # MTBC_BATCH_MAX_LUTS of include/mtbc.h
 
 # columns of the mtbc_seg_metrics table -- keep in sync with the MTBC_SEGM_* defines of include/mtbc.h
@@ -260,7 +267,7 @@ EXPORTS = [
     "mtbc_focal_fwd_bwd", "mtbc_loss_mix", "mtbc_adam_step", "mtbc_adam_dynamic", "mtbc_loss_scale_begin", "mtbc_loss_scale_check", "mtbc_loss_scale_adam",
     "mtbc_loss_scale_update_host", "mtbc_loss_scale_begin_host", "mtbc_dice_counts", "mtbc_program_run",
     "mtbc_program_run_ms", "mtbc_event_create", "mtbc_event_destroy",
-    "mtbc_seg_metrics_workspace_size", "mtbc_seg_metrics", "mtbc_batch_assemble",
+    "mtbc_seg_metrics_workspace_size", "mtbc_seg_metrics", "mtbc_batch_assemble", "mtbc_train_metrics",
 ]
 
 ABI_VERSION = 202          # MTBC_VERSION of include/mtbc.h these mirrors follow
@@ -378,6 +385,8 @@ def load() -> C.CDLL:
     lib.mtbc_seg_metrics.argtypes = [C.POINTER(SegMetricsArgs), C.c_void_p]
     lib.mtbc_batch_assemble.restype = C.c_int
     lib.mtbc_batch_assemble.argtypes = [C.POINTER(BatchArgs), C.c_void_p]
+    lib.mtbc_train_metrics.restype = C.c_int
+    lib.mtbc_train_metrics.argtypes = [C.POINTER(TrainMetricsArgs), C.c_void_p]
     _lib = lib
     return lib
 

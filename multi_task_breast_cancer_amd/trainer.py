@@ -11,7 +11,7 @@ No host synchronisation happens inside a step: the loss scalars and the NaN flag
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import os
 
@@ -88,6 +88,77 @@ def allreduce_buckets(flat_g: torch.Tensor, buckets: Sequence[Bucket], group=Non
     return works
 
 
+# ---- training-time metrics (training_multitask.py:105-113) from the integer counts of mtbc_train_metrics: pure functions of (table, conf)
+class TrainMetrics(NamedTuple):
+    dice: float             # mean over the batches of the per-batch Dice (`training_dice / len(training_loader)`, :111)
+    accuracy: float         # accuracy_score over every sample of the epoch (:112)
+    f1: float               # f1_score(labels=[0, 1, 2], average='weighted') (:113)
+    batches: int
+    conf: np.ndarray        # (3, 3) int64, rows = ground truth, cols = prediction
+    table: np.ndarray       # (batches, 4) int64: tp, fp, fn, samples of each (global) batch
+
+
+def _dice(tp: float, fp: float, fn: float) -> float:
+    """metrics.py:255-267 on float64 counts: an empty ground truth scores 1 with an empty prediction, else 0."""
+    if tp + fn == 0:
+        return 1.0 if tp + fp == 0 else 0.0
+    return 2 * tp / (2 * tp + fp + fn)
+
+
+def classification_scores(conf: np.ndarray) -> Tuple[float, float]:
+    """(accuracy_score, f1_score(labels=[0, 1, 2], average='weighted')) of a float64 3 x 3 confusion matrix, rows = ground truth
+    (training_multitask.py:112-113, :155-156): per-class F1 weighted by support; a class with no support has weight 0, one that is never
+    predicted scores 0."""
+    total = conf.sum()
+    accuracy = float(np.trace(conf) / total) if total else 0.0
+    support = conf.sum(axis=1)
+    tp = np.diag(conf)
+    denom = conf.sum(axis=0) + support
+    f1c = np.divide(2 * tp, denom, out=np.zeros_like(tp), where=denom > 0)
+    f1w = float((f1c * support).sum() / support.sum()) if support.sum() else 0.0
+    return accuracy, f1w
+
+
+def train_metrics_from_counts(table, conf) -> TrainMetrics:
+    """The reference's training-time metrics from the rows the device appended: `table` (batches, 4) = tp, fp, fn, samples per batch,
+    `conf` (3, 3).  Dice: the per-batch score of `dice_score_from_tensor`, summed in batch order in float64 and divided by the number of
+    batches, as the reference's `training_dice += ...; training_dice / len(training_loader)`."""
+    table = np.asarray(table, dtype=np.int64).reshape(-1, 4)
+    conf = np.asarray(conf, dtype=np.int64).reshape(3, 3)
+    total = 0.0
+    for tp, fp, fn, _ in table.tolist():
+        total += _dice(float(tp), float(fp), float(fn))
+    accuracy, f1w = classification_scores(conf.astype(np.float64))
+    return TrainMetrics(total / len(table) if len(table) else 0.0, accuracy, f1w, len(table), conf, table)
+
+
+def reduce_train_metrics(table: torch.Tensor, conf: torch.Tensor, state: torch.Tensor, distributed: bool = False, group=None) -> np.ndarray:
+    """The accumulators of one rank -> ONE int64 host array [table | conf | sum cursor, sum cursor^2, sum dropped] with, under
+    `distributed`, ONE sum-all-reduce in front of the ONE device-to-host read.  The ranks' shards of global batch b all sit in row b, so
+    the summed row holds the GLOBAL batch's tp / fp / fn: the Dice of the union, not a mean of shard Dices.  The accumulators themselves
+    are not modified (the sum works on a copy)."""
+    s = state.to(torch.int64)
+    packed = torch.cat([table.reshape(-1), conf.reshape(-1), torch.stack([s[0], s[0] * s[0], s[1]])])
+    if distributed:
+        import torch.distributed as dist
+        dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
+    return packed.cpu().numpy()
+
+
+def train_metrics_from_packed(packed: np.ndarray, capacity: int, world: int = 1) -> TrainMetrics:
+    """`reduce_train_metrics`' array -> TrainMetrics, or MtbcError (and no number) when a batch found the table full or the ranks did not
+    see the same number of batches.  Every rank holds the same sums, so every rank raises or none does."""
+    c_sum, c_sq, dropped = (int(v) for v in packed[capacity * 4 + 9:capacity * 4 + 12])
+    if world * c_sq != c_sum * c_sum:              # Cauchy-Schwarz: equality only when all cursors are equal
+        raise L.MtbcError(f"training metrics: the ranks appended different numbers of batches (sum {c_sum} over {world} ranks): every rank must "
+                          f"call run() or run_empty() once per global batch; rows of the metrics_capacity = {capacity} table do not line up")
+    cursor = c_sum // world
+    if dropped != 0 or cursor > capacity:
+        raise L.MtbcError(f"training metrics: {cursor} batches since begin_epoch_metrics() but metrics_capacity = {capacity} rows "
+                          f"({dropped} dropped): build the FusedTrainStep with a larger metrics_capacity")
+    return train_metrics_from_counts(packed[:cursor * 4].reshape(cursor, 4), packed[capacity * 4:capacity * 4 + 9].reshape(3, 3))
+
+
 # ------------------------------------------------------------------------------------------------
 # the fused step (HIP)
 # ------------------------------------------------------------------------------------------------
@@ -95,11 +166,25 @@ class FusedTrainStep:
     """One optimisation step of training_multitask.py:87-103 as ONE stream-ordered program.  `cls_criterion`: "Focal" (config.yaml's
     default, FocalLoss alpha 1 gamma 2), "CE" (CrossEntropyLoss = gamma 0) -- experiment_init.py:232-262; with n_classes == 2 the model has
     ONE logit and the reference trains it with BCEWithLogitsLoss on the {0, 1} label (`:241-242`, training_multitask.py:83-84 leaves the
-    label (N, 1)): the same program with the focal kernel's one-logit form."""
+    label (N, 1)): the same program with the focal kernel's one-logit form.
+
+    metrics=True: the counts behind the reference's Train_dice / Train_acc / Train_F1 (:105-113) are appended on the device by every step --
+    `mtbc_train_metrics`, two small launches between the loss program and the backward program (which reuses the outputs' memory) --
+    one table row per batch; `begin_epoch_metrics()` starts an epoch, `epoch_metrics()` reads it back once."""
 
     def __init__(self, model, optimizer, alpha: float, inversely_weighted: bool = True, n_classes: int = 3,
                  distributed: bool = False, n_buckets: int = 4, focal_weight: Optional[torch.Tensor] = None,
-                 cls_criterion: str = "Focal", graph: Optional[bool] = None, loss_scale=None):
+                 cls_criterion: str = "Focal", graph: Optional[bool] = None, loss_scale=None, metrics: bool = False,
+                 metrics_capacity: int = 4096):
+        # metrics: off = exactly the launches of a step without it.  metrics_capacity: rows (= batches per epoch) of the device table, 32 bytes each;
+        # allocated once and never moved, so a captured graph stays valid across epochs.
+        self.metrics = bool(metrics)
+        self.metrics_capacity = int(metrics_capacity)
+        if self.metrics and self.metrics_capacity < 1:
+            raise ValueError("metrics_capacity must be at least 1 row")
+        self._tm = None             # device int64 [capacity * 4 + 9]: the table, then the confusion matrix
+        self._tm_state = None       # device int32 [2]: cursor, dropped
+        self._tm_args = {}          # id(compiled step) -> (the step, its mtbc_train_metrics_args); None -> the empty shard's
         # graph: replay each compiled step as ONE hipGraph from its third call on (None: the MTBC_GRAPH switch).  The step is a static list of ~380
         # launches with every pointer resolved at plan time -- exactly what a graph holds; what changes from step to step (the batch, the learning
         # rate, Adam's bias corrections, the shard weight) lives in device buffers written BEFORE the replay.  Not under data parallel (the bucket
@@ -207,6 +292,55 @@ class FusedTrainStep:
         self._set_shard_weight(st, weight)
         return st
 
+    # ---- training-time metrics ----------------------------------------------------------------------------------------------
+    def _metrics_buffers(self):
+        if not self.metrics:
+            raise ValueError("this FusedTrainStep was built with metrics=False")
+        if self._tm is None:
+            dev = next(self.model.parameters()).device
+            self._tm = torch.zeros(self.metrics_capacity * 4 + 9, dtype=torch.int64, device=dev)
+            self._tm_state = torch.zeros(2, dtype=torch.int32, device=dev)
+        return self._tm, self._tm_state
+
+    def _append_metrics(self, st) -> None:
+        """The metrics call on the outputs of the forward that has just run (st = None: the empty shard, which only advances the cursor).  Behind the
+        loss program the buffers hold what FusedEvalStep reads there: fp32 NCHW logits of the last head, the mask, the class logits and their target,
+        in every compute mode.  Two launches on the current stream, capturable."""
+        import ctypes as C
+        key = None if st is None else id(st)
+        ent = self._tm_args.get(key)
+        if ent is None or ent[0] is not st:         # the arguments of a compiled step never change: buffers and accumulators stay where they are
+            tm, state = self._metrics_buffers()
+            a = L.TrainMetricsArgs()
+            if st is None:
+                a.N, a.n_seg, a.n_logits = 0, 0, self._st.logits.C
+            else:
+                seg, logits = st.segs[-1].data, st.logits.data
+                for t in (seg, st.mask, logits, st.onehot):
+                    if t.dtype != torch.float32 or not t.is_contiguous():
+                        raise L.MtbcError("training metrics: the step's outputs are not contiguous fp32 buffers")
+                if seg.numel() != st.mask.numel() or logits.numel() != st.onehot.numel():
+                    raise L.MtbcError("training metrics: outputs and targets differ in size")
+                a.seg_logits, a.mask, a.n_seg = seg.data_ptr(), st.mask.data_ptr(), seg.numel()
+                a.cls_logits, a.target, a.N, a.n_logits = logits.data_ptr(), st.onehot.data_ptr(), st.N, st.logits.C
+            a.table, a.conf, a.state, a.capacity = tm.data_ptr(), tm.data_ptr() + self.metrics_capacity * 32, state.data_ptr(), self.metrics_capacity
+            self._tm_args[key] = ent = (st, a)
+        L.check(L.load().mtbc_train_metrics(C.byref(ent[1]), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "train_metrics")
+
+    def begin_epoch_metrics(self) -> None:
+        """Zero the table, the confusion matrix and the cursor in stream order (outside any replayed graph: the buffers stay where they are)."""
+        tm, state = self._metrics_buffers()
+        tm.zero_()
+        state.zero_()
+
+    def epoch_metrics(self) -> TrainMetrics:
+        """The epoch so far as the reference's numbers: under data parallel ONE sum-all-reduce of the table and the confusion matrix (row b of the sum is
+        GLOBAL batch b), then ONE device-to-host read.  MtbcError when the table was too small or the ranks' cursors disagree."""
+        tm, state = self._metrics_buffers()
+        cap = self.metrics_capacity
+        packed = reduce_train_metrics(tm[:cap * 4], tm[cap * 4:], state, distributed=self.distributed)
+        return train_metrics_from_packed(packed, cap, self.world)
+
     def _apply_update(self, st) -> None:
         """Adam on the (all-reduced) flat gradients: the static path divides the baked loss scale out, the dynamic path checks, skips or applies, and
         moves its scale -- all in stream order."""
@@ -245,7 +379,10 @@ class FusedTrainStep:
             P = st.programs
             if sc is not None:
                 self._begin_dynamic(st, fills=False)
-            P["pack"].run(); P["fwd"].run(); P["loss"].run(); P["bwd"].run()
+            P["pack"].run(); P["fwd"].run(); P["loss"].run()
+            if self.metrics:                      # a linear chain on the capturing stream: replayed with the step, appending at the device cursor
+                self._append_metrics(st)
+            P["bwd"].run()
             if sc is None:
                 opt.launch_dynamic()
             else:
@@ -253,7 +390,7 @@ class FusedTrainStep:
 
         # the entry lives ON the compiled step (a dropped step takes its graph along; no address or id() can be reused under a stale graph)
         ents = st.__dict__.setdefault("_graph_ents", {})
-        key = (id(self), opt.graph_key() if sc is None else (opt.graph_key(dynamic=False), sc.graph_key()))
+        key = (id(self), opt.graph_key() if sc is None else (opt.graph_key(dynamic=False), sc.graph_key()), self.metrics)
         ent = ents.get(id(self))
         if ent is None or ent[0] != key:
             ents[id(self)] = ent = [key, 0, None]
@@ -287,6 +424,8 @@ class FusedTrainStep:
         P["pack"].run()
         P["fwd"].run()
         P["loss"].run()
+        if self.metrics:            # before the (first range of the) backward, which reuses the outputs' memory; on the compute stream
+            self._append_metrics(st)
         if not self.distributed:
             P["bwd"].run()
         else:
@@ -320,6 +459,8 @@ class FusedTrainStep:
         if self.scaler is not None:
             self._begin_dynamic(self._st)
             self._begin_dynamic(self._st, fills=False)
+        if self.metrics:            # row b is global batch b on every rank: the empty shard advances the cursor
+            self._append_metrics(None)
         self.model.flat_g.zero_()
         for b in self._st.buckets:
             allreduce_buckets(self.model.flat_g, [b])
@@ -350,9 +491,7 @@ class FusedTrainStep:
 def dice_score_from_counts(counts: torch.Tensor) -> float:
     """metrics.py:255-267 from {tp, fp, fn} float64 counts (mtbc_dice_counts)."""
     tp, fp, fn = (float(v) for v in counts.tolist())
-    if tp + fn == 0:
-        return 1.0 if tp + fp == 0 else 0.0
-    return 2 * tp / (2 * tp + fp + fn)
+    return _dice(tp, fp, fn)
 
 
 def dice_counts(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
@@ -468,14 +607,7 @@ class FusedEvalStep:
         acc = self._acc.cpu().tolist()
         conf = self._conf.cpu().numpy().astype(np.float64)
         nb = max(acc[4], 1.0)
-        total = conf.sum()
-        accuracy = float(np.trace(conf) / total) if total else 0.0
-        # sklearn f1_score(labels=[0,1,2], average='weighted') (:155): per-class F1 weighted by support
-        support = conf.sum(axis=1)
-        tp = np.diag(conf)
-        denom = conf.sum(axis=0) + support
-        f1c = np.divide(2 * tp, denom, out=np.zeros_like(tp), where=denom > 0)
-        f1w = float((f1c * support).sum() / support.sum()) if support.sum() else 0.0
+        accuracy, f1w = classification_scores(conf)       # sklearn accuracy_score / f1_score(labels=[0,1,2], average='weighted') (:155-156)
         return acc[0] / nb, acc[3] / nb, accuracy, f1w, acc[1] / nb, acc[2] / nb
 
 
@@ -495,18 +627,8 @@ def _check_tables(dataset, tables) -> None:
         raise ValueError(f"epoch tables hold indices in [{tables.index_min}, {tables.index_max}], the dataset has {len(dataset)} rows")
 
 
-def train_one_epoch(step: FusedTrainStep, dataset, tables, lr: Optional[float] = None) -> tuple:
-    """The batch loop of training_multitask.py:74-103 on the fused step with no host work per batch: `dataset` is a
-    device_data.DeviceDataset, `tables` the epoch's device_data.EpochTables.  Per batch: one assembly launch into the plan's buffers
-    (`load_indexed`) and the step; the loss words are summed on the device in float64, read back once at the end of the epoch together
-    with ONE `check_nan()` (a NaN in any step's loss ends the run like the reference's guard, criterions.py:72-76).  Nothing is copied
-    from host to device inside the loop.  The short last batch of drop_last=False compiles (once) a second plan.  Under data parallel
-    each batch carries this rank's share `weight`, and a rank whose shard of the last batch is empty calls `run_empty()`.
-    `lr`: written into the optimizer's parameter groups first (the scheduler's value of the epoch).
-
-    Returns (avg_total, avg_seg, avg_cls): means over the batches this rank ran, as `training_loss / len(training_loader)` (:110).
-    The reference's training-time Dice, accuracy and F1 (:107-113) are NOT returned: they need the step's outputs to survive the
-    backward pass, which reuses their memory -- a change of its own."""
+def _train_epoch(step: FusedTrainStep, dataset, tables, lr: Optional[float]) -> tuple:
+    """The loop `train_one_epoch` and `train_one_epoch_with_metrics` share: (avg_total, avg_seg, avg_cls) over the batches this rank ran."""
     _check_tables(dataset, tables)
     if lr is not None:
         for group in step.opt.param_groups:
@@ -535,6 +657,33 @@ def train_one_epoch(step: FusedTrainStep, dataset, tables, lr: Optional[float] =
     return total / ran, seg / ran, cls / ran
 
 
+def train_one_epoch(step: FusedTrainStep, dataset, tables, lr: Optional[float] = None) -> tuple:
+    """The batch loop of training_multitask.py:74-103 on the fused step with no host work per batch: `dataset` is a
+    device_data.DeviceDataset, `tables` the epoch's device_data.EpochTables.  Per batch: one assembly launch into the plan's buffers
+    (`load_indexed`) and the step; the loss words are summed on the device in float64, read back once at the end of the epoch together
+    with ONE `check_nan()` (a NaN in any step's loss ends the run like the reference's guard, criterions.py:72-76).  Nothing is copied
+    from host to device inside the loop.  The short last batch of drop_last=False compiles (once) a second plan.  Under data parallel
+    each batch carries this rank's share `weight`, and a rank whose shard of the last batch is empty calls `run_empty()`.
+    `lr`: written into the optimizer's parameter groups first (the scheduler's value of the epoch).
+
+    Returns (avg_total, avg_seg, avg_cls): means over the batches this rank ran, as `training_loss / len(training_loader)` (:110).
+    The reference's training-time Dice, accuracy and F1 (:107-113) come from `train_one_epoch_with_metrics` on a step built with metrics=True."""
+    return _train_epoch(step, dataset, tables, lr)
+
+
+def train_one_epoch_with_metrics(step: FusedTrainStep, dataset, tables, lr: Optional[float] = None) -> tuple:
+    """`train_one_epoch` plus the training-time metrics of training_multitask.py:105-113, still with no host read inside the batch loop: the step
+    (built with metrics=True) appends each batch's counts on the device; `begin_epoch_metrics()` in front, `epoch_metrics()` behind (one all-reduce
+    under data parallel, one read).  Returns the reference's 4-tuple (avg_training_loss, avg_training_dice, training_acc, training_f1) (:116).
+    Under data parallel Dice, accuracy and F1 are those of the GLOBAL batches (the same on every rank); the loss is this rank's mean, as above."""
+    if not getattr(step, "metrics", False):
+        raise ValueError("train_one_epoch_with_metrics needs a FusedTrainStep built with metrics=True")
+    step.begin_epoch_metrics()
+    total, _, _ = _train_epoch(step, dataset, tables, lr)
+    m = step.epoch_metrics()
+    return total, m.dice, m.accuracy, m.f1
+
+
 def validate_one_epoch_indexed(step: FusedEvalStep, dataset, tables) -> tuple:
     """`validate_one_epoch` from a device-resident dataset: the batches of `tables` (built without transforms: the identity path), one
     assembly launch each; the reference's 6-tuple, read back once."""
@@ -547,3 +696,65 @@ def validate_one_epoch_indexed(step: FusedEvalStep, dataset, tables) -> tuple:
         if n_local:
             step.indexed(dataset, index)
     return step.result()
+
+
+# ------------------------------------------------------------------------------------------------
+# one fold of the reference's training script (training_multitask.py:216-280) on the indexed epochs
+# ------------------------------------------------------------------------------------------------
+def fit_fold(step: FusedTrainStep, eval_step: FusedEvalStep, dataset, train_index, val_index, scheduler, run_dir: str, epochs: int,
+             max_patience: int, transforms: Optional[dict], seed: int, plateau: bool, checkpoint_name: str = "model_best") -> List[tuple]:
+    """The epoch loop of training_multitask.py:216-280: `train_index` / `val_index` are dataset_index.EpochIndex objects over the rows of
+    `dataset` (a device_data.DeviceDataset), `scheduler` a torch scheduler on `step.opt` stepped once per epoch -- with the validation loss
+    when `plateau` (:234-237).  Per epoch: the learning rate of the day, the epoch's device tables (`transforms`, `seed`), training with
+    metrics, validation, the scheduler, a checkpoint under run_dir/checkpoint_name on a new best validation loss, the patience rule, one row of
+    run_dir/metrics.csv under METRICS_HEADER and the reference's log line.  Files are written by rank 0 only under data parallel.
+    Returns the rows as tuples (epoch, lr, train_loss, val_loss, train_dice, val_dice, train_acc, train_f1, val_acc, val_f1)."""
+    import logging
+    import time
+    from . import checkpoint as CK
+    from .device_data import EpochTables
+    writer = True
+    if step.distributed:
+        import torch.distributed as dist
+        writer = dist.get_rank() == 0
+    os.makedirs(run_dir, exist_ok=True)
+    metrics_path = os.path.join(run_dir, "metrics.csv")
+    if writer:
+        CK.write_metrics_file(metrics_path, CK.METRICS_HEADER)
+    stopper = CK.EarlyStopping(max_patience)
+    val_tables = EpochTables(val_index, 0, None, device=dataset.device)        # no shuffle that matters, no transforms (:199-201)
+    rows = []
+    for epoch in range(int(epochs)):
+        current_lr = step.opt.param_groups[0]["lr"]
+        t0 = time.perf_counter()
+        tables = EpochTables(train_index, epoch, transforms, seed=seed, device=dataset.device)
+        train_loss, train_dice, train_acc, train_f1 = train_one_epoch_with_metrics(step, dataset, tables)
+        val_loss, val_dice, val_acc, val_f1, seg_val_loss, cls_val_loss = validate_one_epoch_indexed(eval_step, dataset, val_tables)
+        if plateau:
+            scheduler.step(val_loss)
+        else:
+            scheduler.step()
+        if stopper.update(val_loss) and writer:
+            CK.save_checkpoint(os.path.join(run_dir, checkpoint_name), epoch, step.model, step.opt, val_loss, scaler=step.scaler)
+        logging.info(f'EPOCH {epoch} --> '
+                     f'|| Training loss {train_loss:.4f} '
+                     f'|| Validation loss {val_loss:.4f} '
+                     f'|| Segmentation val loss {seg_val_loss:.4f} '
+                     f'|| Classification val loss {cls_val_loss:.4f} '
+                     f'|| Training DICE {train_dice:.4f} '
+                     f'|| Validation DICE  {val_dice:.4f} '
+                     f'|| Training ACC {train_acc:.4f} '
+                     f'|| Training F1 {train_f1:.4f} '
+                     f'|| Validation ACC {val_acc:.4f} '
+                     f'|| Validation F1 {val_f1:.4f} '
+                     f'|| Patience: {stopper.patience} '
+                     f'|| Epoch time: {time.perf_counter() - t0:.4f}'
+                     f'|| Best validation performance: {stopper.best:.4f}')
+        row = (epoch, current_lr, train_loss, val_loss, train_dice, val_dice, train_acc, train_f1, val_acc, val_f1)
+        rows.append(row)
+        if writer:
+            CK.write_metrics_file(metrics_path, CK.metrics_row(*row))
+        if stopper.should_stop:
+            logging.info(f"\nValidation loss did not improve over the last {stopper.patience} epochs. Stopping training")
+            break
+    return rows

@@ -1,0 +1,217 @@
+"""Training-time metrics without a GPU: the host arithmetic on (table, conf) against a restatement of the reference's
+`dice_score_from_tensor` (metrics.py:255-267) and against sklearn (training_multitask.py:112-113), the merge of the ranks' accumulators
+over gloo (world 2), and the export."""
+import os
+import re
+import socket
+
+import numpy as np
+import pytest
+import torch
+import torch.distributed as dist
+import torch.multiprocessing as mp
+
+from multi_task_breast_cancer_amd import _lib as L
+from multi_task_breast_cancer_amd import trainer as T
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def dice_score_from_tensor(gt: torch.Tensor, seg: torch.Tensor):
+    """metrics.py:255-267, restated."""
+    gt = gt.double()
+    seg = seg.double()
+    tp = torch.sum(torch.logical_and(seg, gt)).double()
+    fp = torch.sum(torch.logical_and(seg, torch.logical_not(gt))).double()
+    fn = torch.sum(torch.logical_and(torch.logical_not(seg), gt)).double()
+    if torch.sum(gt) == 0:
+        dice = 1 if torch.sum(seg) == 0 else 0
+    else:
+        dice = 2 * tp / (2 * tp + fp + fn)
+    return dice
+
+
+def counts_row(gt: torch.Tensor, seg: torch.Tensor, n: int):
+    g, s = gt.bool(), seg.bool()
+    return [int((s & g).sum()), int((s & ~g).sum()), int((~s & g).sum()), n]
+
+
+def confusion(gt, pred) -> np.ndarray:
+    conf = np.zeros((3, 3), dtype=np.int64)
+    for g, p in zip(gt, pred):
+        conf[int(g), int(p)] += 1
+    return conf
+
+
+def mask_batches(seed: int):
+    """Per-batch (ground truth, prediction) masks: random ones, an empty pair (Dice 1), an empty ground truth under a non-empty prediction
+    (Dice 0), a non-empty ground truth under an empty prediction, a perfect one."""
+    g = torch.Generator().manual_seed(seed)
+    out = []
+    for n, p_gt, p_seg in [(3, .3, .3), (2, .5, .1), (4, .02, .6), (1, .9, .9)]:
+        out.append((n, torch.rand(n, 1, 17, 30, generator=g) < p_gt, torch.rand(n, 1, 17, 30, generator=g) < p_seg))
+    z = torch.zeros(2, 1, 17, 30, dtype=torch.bool)
+    some = torch.rand(2, 1, 17, 30, generator=g) < .2
+    out += [(2, z, z), (2, z, some), (2, some, z), (2, some, some)]
+    return out
+
+
+def test_dice_rows_equal_the_reference_expression_to_the_last_bit():
+    batches = mask_batches(3)
+    table = np.array([counts_row(gt, seg, n) for n, gt, seg in batches], dtype=np.int64)
+    want_rows = [dice_score_from_tensor(gt, seg) for _, gt, seg in batches]
+    assert [float(w) for w in want_rows[4:]] == [1.0, 0.0, 0.0, 1.0]
+    for row, w in zip(table.tolist(), want_rows):
+        assert T._dice(float(row[0]), float(row[1]), float(row[2])) == float(w), (row, float(w))
+    training_dice = 0.                                  # training_multitask.py:75, :107, :111
+    for w in want_rows:
+        training_dice += w
+    want = float(training_dice / len(batches))
+    m = T.train_metrics_from_counts(table, np.zeros((3, 3), dtype=np.int64))
+    assert m.dice == want and m.batches == len(batches) and np.array_equal(m.table, table)
+    assert (m.accuracy, m.f1) == (0.0, 0.0)             # no sample counted: the evaluation step's convention
+    assert T.train_metrics_from_counts(np.zeros((0, 4), dtype=np.int64), np.zeros((3, 3))).dice == 0.0
+    # the float64-counts entry point of the evaluation step goes through the same expression
+    assert T.dice_score_from_counts(torch.tensor([3.0, 1.0, 2.0], dtype=torch.float64)) == 2 * 3.0 / (2 * 3.0 + 1.0 + 2.0)
+
+
+LABEL_CASES = {
+    "all three": lambda r: (r.integers(0, 3, 200), r.integers(0, 3, 200)),
+    "class 2 never occurs": lambda r: (r.integers(0, 2, 150), r.integers(0, 3, 150)),
+    "class 1 never predicted": lambda r: (r.integers(0, 3, 150), r.choice([0, 2], 150)),
+    "binary head": lambda r: (r.integers(0, 2, 97), r.integers(0, 2, 97)),
+    "one class only, all right": lambda r: (np.ones(10, dtype=np.int64), np.ones(10, dtype=np.int64)),
+    "nothing right": lambda r: (np.zeros(12, dtype=np.int64), r.integers(1, 3, 12)),
+    "one sample": lambda r: (np.array([2]), np.array([0])),
+}
+
+
+@pytest.mark.parametrize("case", sorted(LABEL_CASES))
+@pytest.mark.filterwarnings("ignore")                   # sklearn warns where a class has no predicted samples (and scores it 0)
+def test_accuracy_and_weighted_f1_against_sklearn(case):
+    from sklearn.metrics import accuracy_score, f1_score
+    for seed in range(3):
+        gt, pred = LABEL_CASES[case](np.random.default_rng(seed))
+        conf = confusion(gt, pred)
+        acc, f1w = T.classification_scores(conf.astype(np.float64))
+        want_acc = accuracy_score(gt.tolist(), pred.tolist())
+        want_f1 = f1_score(y_true=gt.tolist(), y_pred=pred.tolist(), labels=[0, 1, 2], average='weighted')
+        assert abs(acc - want_acc) <= 1e-12 and abs(f1w - want_f1) <= 1e-12, (case, acc, want_acc, f1w, want_f1)
+        m = T.train_metrics_from_counts(np.array([[1, 0, 0, len(gt)]]), conf)
+        assert (m.accuracy, m.f1) == (acc, f1w) and np.array_equal(m.conf, conf)
+
+
+def test_packed_counts_refuse_a_full_table_and_unequal_cursors():
+    cap = 3
+    table = torch.tensor([[5, 1, 2, 4], [0, 0, 0, 4], [0, 0, 0, 0]], dtype=torch.int64)
+    conf = torch.tensor([[3, 0, 0], [1, 2, 0], [0, 0, 2]], dtype=torch.int64)
+    packed = T.reduce_train_metrics(table, conf, torch.tensor([2, 0], dtype=torch.int32))
+    assert packed.dtype == np.int64 and packed.shape == (cap * 4 + 12,) and packed[-3:].tolist() == [2, 4, 0]
+    m = T.train_metrics_from_packed(packed, cap)
+    assert m.batches == 2 and m.table.tolist() == table[:2].tolist() and m.dice == (2 * 5 / (2 * 5 + 1 + 2) + 1.0) / 2
+    with pytest.raises(L.MtbcError, match="metrics_capacity"):
+        T.train_metrics_from_packed(T.reduce_train_metrics(table, conf, torch.tensor([4, 1], dtype=torch.int32)), cap)
+    two = packed.copy()
+    two[-3:] = [2 + 3, 4 + 9, 0]                         # what the sum over a rank at cursor 2 and one at cursor 3 looks like
+    with pytest.raises(L.MtbcError, match="metrics_capacity"):
+        T.train_metrics_from_packed(two, cap, world=2)
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _rank_accumulators(rank: int, cap: int, short: bool):
+    """What each rank's device would hold after two global batches of 4 + 3 samples cut 2+2 and 2+1 (`short`: rank 1 misses a call)."""
+    g = torch.Generator().manual_seed(11)
+    gt = torch.rand(7, 1, 17, 30, generator=g) < .3
+    seg = torch.rand(7, 1, 17, 30, generator=g) < .3
+    gt[4:] = False                                       # global batch 1: no tumour on any rank's shard ...
+    seg[4:6] = False                                     # ... and a non-empty prediction on rank 1's shard only: the UNION scores 0, rank 0 alone would score 1
+    assert bool(seg[6].any())
+    labels, preds = [0, 1, 2, 2, 1, 1, 0], [0, 2, 2, 1, 1, 0, 0]
+    cuts = [(0, 2, 4), (4, 6, 7)]
+    table = torch.zeros(cap, 4, dtype=torch.int64)
+    conf = torch.zeros(3, 3, dtype=torch.int64)
+    for b, c in enumerate(cuts):
+        lo, hi = c[rank], c[rank + 1]
+        table[b] = torch.tensor(counts_row(gt[lo:hi], seg[lo:hi], hi - lo))
+        conf += torch.from_numpy(confusion(labels[lo:hi], preds[lo:hi]))
+    state = torch.tensor([1 if (short and rank == 1) else 2, 0], dtype=torch.int32)
+    whole = [dice_score_from_tensor(gt[c[0]:c[2]], seg[c[0]:c[2]]) for c in cuts]
+    return table, conf, state, whole, confusion(labels, preds)
+
+
+def _worker(rank, world, port, q):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        cap = 5
+        table, conf, state, whole, conf_all = _rank_accumulators(rank, cap, short=False)
+        before = (table.clone(), conf.clone(), state.clone())
+        m = T.train_metrics_from_packed(T.reduce_train_metrics(table, conf, state, distributed=True), cap, world)
+        assert all(torch.equal(a, b) for a, b in zip(before, (table, conf, state)))        # the accumulators are left as they were
+        assert m.batches == 2 and m.table[:, 3].tolist() == [4, 3]
+        assert float(whole[1]) == 0.0
+        assert m.dice == float((0. + whole[0] + whole[1]) / 2), (m.dice, whole)            # the Dice of the union, batch by batch
+        assert np.array_equal(m.conf, conf_all)
+        assert (m.accuracy, m.f1) == T.classification_scores(conf_all.astype(np.float64))
+        # rank 1 one call short: every rank raises (both hold the same sums), nobody returns a number
+        table, conf, state, _, _ = _rank_accumulators(rank, cap, short=True)
+        try:
+            T.train_metrics_from_packed(T.reduce_train_metrics(table, conf, state, distributed=True), cap, world)
+            raised = ""
+        except L.MtbcError as e:
+            raised = str(e)
+        assert "metrics_capacity" in raised
+        q.put((rank, "ok"))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_two_ranks_merge_into_the_global_batches_over_gloo():
+    world, port = 2, _free_port()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(120)
+        assert p.exitcode == 0
+    got = sorted(q.get(timeout=5) for _ in range(world))
+    assert got == [(0, "ok"), (1, "ok")]
+
+
+def test_export_is_declared_and_bound():
+    src = open(os.path.join(ROOT, "include", "mtbc.h")).read()
+    assert re.search(r"\bint\s+mtbc_train_metrics\s*\(\s*const\s+mtbc_train_metrics_args\s*\*", src)
+    assert "mtbc_train_metrics" in L.EXPORTS and L.ABI_VERSION == 202
+    # the ctypes mirror against the header's struct, field by field (LP64: pointers and int64_t 8 bytes, 8-byte aligned)
+    body = src[src.index("typedef struct {", src.index("training-time metrics")):src.index("} mtbc_train_metrics_args;")]
+    names = re.findall(r"(\w+)\s*[;,]", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+    assert names == [f[0] for f in L.TrainMetricsArgs._fields_], names
+    import ctypes as C
+    assert C.sizeof(L.TrainMetricsArgs) == 80 and L.TrainMetricsArgs.capacity.offset == 72 and L.TrainMetricsArgs.N.offset == 40
+    lib = L.load()
+    assert hasattr(lib, "mtbc_train_metrics")
+    # argument checks are host code: they answer before any GPU call
+    a = L.TrainMetricsArgs()
+    assert lib.mtbc_train_metrics(None, None) == -2 and lib.mtbc_train_metrics(C.byref(a), None) == -2          # MTBC_E_BADARG: null accumulators
+    buf = (C.c_int64 * 16)()
+    a.table = a.conf = a.state = C.addressof(buf)
+    a.capacity, a.N, a.n_seg = 1, 0, 0
+    for bad in (0, 4, -1):
+        a.n_logits = bad
+        assert lib.mtbc_train_metrics(C.byref(a), None) == -1, bad                                           # MTBC_E_BADSHAPE
+    a.n_logits, a.N = 3, -1
+    assert lib.mtbc_train_metrics(C.byref(a), None) == -1
+    a.N, a.n_seg = 2, 0
+    assert lib.mtbc_train_metrics(C.byref(a), None) == -1                                                    # samples without pixels
+    a.N, a.n_seg = 2, 64
+    assert lib.mtbc_train_metrics(C.byref(a), None) == -2                                                    # null data pointers with N > 0
