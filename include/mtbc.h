@@ -455,18 +455,42 @@ int mtbc_linear_bwd(const mtbc_linear_args* a, void* stream);
  * fwd : stats[h][n*C+c] = {I, P2, T2};  loss[h] = loss_h (unweighted);
  *       loss[n_heads] = sum_h head_weight[h] * loss_h
  * bwd : dx_h = gscale * head_weight[h] / (N*C) * d f / d x   (gscale: host scalar times an
- *       optional device scalar *gscale_dev, e.g. the upstream autograd gradient)            */
+ *       optional device scalar *gscale_dev, e.g. the upstream autograd gradient)
+ *
+ * `kind` selects the segmentation criterion (experiment_init.py:199-232, config key loss.function); the two calls, the head
+ * weights, gscale, *gscale_dev and the layout of `loss` are the same for all of them.  p = sigmoid(x), HW = H * W, a plane = (n, c):
+ *   MTBC_SEG_DICE (0)   the formula above.  A zero-initialised `kind` / `focal_gamma` is exactly the call as it was before they existed.
+ *   MTBC_SEG_BCE        torch.nn.BCEWithLogitsLoss() (:225-226): loss_h = mean over N*C*HW of (1 - t) x + softplus(-x);
+ *                       dx_h = gscale * head_weight[h] * (p - t) / (N*C*HW).  smooth_* unused.
+ *   MTBC_SEG_FOCALDICE  MONAI 1.3.0 DiceFocalLoss(include_background, sigmoid, squared_pred, smooth_nr, smooth_dr) (:214-216):
+ *                       the Dice formula above PLUS the mean over N*C*HW of m * bce, bce as for BCE, s = 2 t - 1,
+ *                       m = exp(focal_gamma * logsigmoid(-x s)) (MONAI's sigmoid focal loss on the raw logits, gamma 2, no alpha,
+ *                       lambda_dice = lambda_focal = 1).
+ *   MTBC_SEG_JACCARD    MONAI DiceLoss(include_background, sigmoid, jaccard=True, reduction="sum") (:221-222; squared_pred=False,
+ *                       smooth 1e-5 are MONAI's defaults -- the caller passes them in smooth_*): I = sum p t, P = sum p, T = sum t,
+ *                       loss_h = SUM_{n,c}( 1 - (2 I + nr) / (2 (P + T - I) + dr) ); no 1/(N*C) in the loss or in dx_h.
+ * (The two MONAI criteria are restated from knowledge of MONAI 1.3.0, as DiceLoss is: re-verify against a MONAI checkout.)
+ * Statistics per (head, plane), MTBC_SEG_STATS_STRIDE(kind) floats each -- the caller sizes `stats` as n_heads * N*C * stride:
+ *   DICE {I, sum p^2, sum t^2} (3) ; BCE {sum bce} (1) ; FOCALDICE {I, sum p^2, sum t^2, sum m bce} (4) ; JACCARD {I, P, T} (3)
+ * MTBC_E_UNSUPPORTED: a kind outside the four.                                                                              */
+#define MTBC_SEG_DICE 0
+#define MTBC_SEG_BCE 1
+#define MTBC_SEG_FOCALDICE 2
+#define MTBC_SEG_JACCARD 3
+#define MTBC_SEG_STATS_STRIDE(kind) ((kind) == MTBC_SEG_BCE ? 1 : (kind) == MTBC_SEG_FOCALDICE ? 4 : 3)
 typedef struct {
     int32_t n_heads, N, C, H, W;
     float smooth_nr, smooth_dr;
     const float* x[4];               /* logits per head (N,C,H,W) */
     const float* target;             /* (N,C,H,W) */
     float head_weight[4];
-    float* stats;                    /* n_heads * N*C * 3 floats */
+    float* stats;                    /* n_heads * N*C * MTBC_SEG_STATS_STRIDE(kind) floats */
     float* loss;                     /* n_heads + 1 floats */
     float* dx[4];
     float gscale;
     const float* gscale_dev;         /* may be NULL */
+    int32_t kind;                    /* MTBC_SEG_*; 0 = Dice */
+    float focal_gamma;               /* MTBC_SEG_FOCALDICE only (the reference: 2) */
 } mtbc_dice_args;
 int mtbc_dice_fwd(const mtbc_dice_args* a, void* stream);
 int mtbc_dice_bwd(const mtbc_dice_args* a, void* stream);

@@ -109,7 +109,16 @@ class DiceArgs(C.Structure):
                 ("smooth_nr", C.c_float), ("smooth_dr", C.c_float),
                 ("x", C.c_void_p * 4), ("target", C.c_void_p), ("head_weight", C.c_float * 4),
                 ("stats", C.c_void_p), ("loss", C.c_void_p), ("dx", C.c_void_p * 4),
-                ("gscale", C.c_float), ("gscale_dev", C.c_void_p)]
+                ("gscale", C.c_float), ("gscale_dev", C.c_void_p),
+                ("kind", C.c_int32), ("focal_gamma", C.c_float)]      # appended: zero = the Dice call as it was
+
+
+# mtbc_dice_args.kind (MTBC_SEG_*) and the floats of statistics each keeps per (head, plane) -- MTBC_SEG_STATS_STRIDE
+SEG_DICE, SEG_BCE, SEG_FOCALDICE, SEG_JACCARD = 0, 1, 2, 3
+SEG_STATS_STRIDE = {SEG_DICE: 3, SEG_BCE: 1, SEG_FOCALDICE: 4, SEG_JACCARD: 3}
+# the reference's `loss.function` names (experiment_init.py:199-232) that are on HIP -> kind, smooth_nr, smooth_dr, focal_gamma, summed over planes
+SEG_CRITERIA = {"DICE": (SEG_DICE, 1.0, 1.0, 0.0, False), "BCE": (SEG_BCE, 0.0, 0.0, 0.0, False),
+                "FocalDICE": (SEG_FOCALDICE, 1.0, 1.0, 2.0, False), "Jaccard": (SEG_JACCARD, 1e-5, 1e-5, 0.0, True)}
 
 
 class FocalArgs(C.Structure):

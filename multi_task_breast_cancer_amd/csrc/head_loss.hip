@@ -80,7 +80,17 @@ __global__ void linear_dw_kernel(const float* __restrict__ g, const float* __res
     }
 }
 
-// ------------------------------------------------------------------ Dice
+// ------------------------------------------------------------------ segmentation criteria (Dice, BCE, Dice+Focal, Jaccard)
+// One pair of launches for every criterion; the criterion is a compile-time KIND (mtbc_dice_args.kind):
+//   0 DICE       monai DiceLoss(sigmoid, squared_pred, smooth nr/dr): stats {I = sum p t, sum p^2, sum t^2}, mean over planes
+//   1 BCE        torch.nn.BCEWithLogitsLoss(): stats {sum bce}, bce = (1 - t) x + softplus(-x), mean over all elements
+//   2 FocalDICE  monai 1.3.0 DiceFocalLoss(sigmoid, squared_pred, smooth nr/dr, gamma, no alpha, lambda 1/1): kind 0's term plus the mean over all
+//                elements of m * bce, m = exp(gamma * logsigmoid(-x s)), s = 2 t - 1: stats {I, sum p^2, sum t^2, sum focal}
+//   3 Jaccard    monai DiceLoss(sigmoid, jaccard=True, reduction="sum"): stats {I, P = sum p, T = sum t}, f = 1 - (2 I + nr) / (2 (P + T - I) + dr),
+//                SUMMED over planes (no 1 / planes in the loss or in the gradient)
+// The MONAI formulas are restated from knowledge of MONAI 1.3.0 (no MONAI checkout here): re-verify against one, as DESIGN.md says for DiceLoss.
+// Kind 0 is the Dice kernel as it was, operation for operation; the others keep its structure (16-byte loads, four rounds in flight, a scalar
+// fallback, one block per (plane, head), block_sum reductions, an elementwise backward that reads the plane's statistics).
 struct DiceP {
     int n_heads, planes, HW;
     float nr, dr;
@@ -88,15 +98,75 @@ struct DiceP {
     float hw[4];
     float* stats; float* loss; float* dx[4];
     float gscale; const float* gscale_dev;
+    float gamma;
 };
+enum { SEG_DICE = 0, SEG_BCE = 1, SEG_FOCALDICE = 2, SEG_JACCARD = 3 };
+template <int K> struct SegStride { static constexpr int v = K == SEG_BCE ? 1 : (K == SEG_FOCALDICE ? 4 : 3); };
 
-// block = (plane, head): I = sum p t, P2 = sum p^2, T2 = sum t^2
+// softplus(-|x|) = log1p(exp(-|x|)) and exp(-|x|) itself.  The focal term needs five of these per element over 4 x N x H x W elements a step, so
+// they are the hardware's v_exp_f32 / v_log_f32 (__expf, __logf) rather than the library's expf / log1pf (a dozen and more instructions each):
+// e in (0, 1], so 1 + e in (1, 2] and the absolute error of log(1 + e) stays at ~1e-7 (one rounding of 1 + e, one of the logarithm) -- a relative
+// error only where the term itself is below 1e-3 of a unit; __expf's relative error is |arg| * 2^-24 (2e-6 at a logit of 30).
+__device__ __forceinline__ float softplus_nabs(float ax, float& e) { e = __expf(-ax); return __logf(1.0f + e); }
+__device__ __forceinline__ float bce_logits(float x, float t, float sp) { return (1.0f - t) * x + (fmaxf(-x, 0.f) + sp); }
+// focal = m * bce and (want_grad) d focal / d x = -s gamma m (1 - sigmoid(z)) bce + m (p - t), z = -x s; p = sigmoid(x) is returned too
+__device__ __forceinline__ float focal_elem(float x, float t, float gamma, float& p, float* grad) {
+    float e, ez;
+    const float sp = softplus_nabs(fabsf(x), e);
+    const float r = 1.0f / (1.0f + e);
+    p = x >= 0.f ? r : e * r;
+    const float bce = bce_logits(x, t, sp);
+    const float s = 2.0f * t - 1.0f, z = -x * s;
+    const float spz = softplus_nabs(fabsf(z), ez);          // soft targets: |z| != |x|
+    const float m = __expf(gamma * (fminf(z, 0.f) - spz));
+    if (grad) {
+        const float rz = 1.0f / (1.0f + ez);
+        const float nsz = z >= 0.f ? ez * rz : rz;          // 1 - sigmoid(z) = sigmoid(-z)
+        *grad = -s * gamma * m * nsz * bce + m * (p - t);
+    }
+    return m * bce;
+}
+
+// one element into the running sums (a0 .. a3: the kind's statistics, in their order)
+template <int K>
+__device__ __forceinline__ void seg_acc(float x, float t, float gamma, float& a0, float& a1, float& a2, float& a3) {
+    if constexpr (K == SEG_BCE) {
+        float e;
+        const float sp = softplus_nabs(fabsf(x), e);
+        a0 += bce_logits(x, t, sp);
+    } else if constexpr (K == SEG_FOCALDICE) {
+        float pr;
+        const float f = focal_elem(x, t, gamma, pr, nullptr);
+        a0 = fmaf(pr, t, a0); a1 = fmaf(pr, pr, a1); a2 = fmaf(t, t, a2); a3 += f;
+    } else if constexpr (K == SEG_JACCARD) {
+        const float pr = sigmoidf_(x);
+        a0 = fmaf(pr, t, a0); a1 += pr; a2 += t;
+    } else {
+        const float pr = sigmoidf_(x);
+        a0 = fmaf(pr, t, a0); a1 = fmaf(pr, pr, a1); a2 = fmaf(t, t, a2);
+    }
+}
+template <int K>
+__device__ __forceinline__ void seg_acc4(const float4& xv, const float4& tv, float gamma, float& si, float& sp, float& stt, float& a3) {
+    if constexpr (K == SEG_DICE) {
+        const float px = sigmoidf_(xv.x), py = sigmoidf_(xv.y), pz = sigmoidf_(xv.z), pw = sigmoidf_(xv.w);
+        si = fmaf(px, tv.x, si); si = fmaf(py, tv.y, si); si = fmaf(pz, tv.z, si); si = fmaf(pw, tv.w, si);
+        sp = fmaf(px, px, sp); sp = fmaf(py, py, sp); sp = fmaf(pz, pz, sp); sp = fmaf(pw, pw, sp);
+        stt = fmaf(tv.x, tv.x, stt); stt = fmaf(tv.y, tv.y, stt); stt = fmaf(tv.z, tv.z, stt); stt = fmaf(tv.w, tv.w, stt);
+    } else {
+        seg_acc<K>(xv.x, tv.x, gamma, si, sp, stt, a3); seg_acc<K>(xv.y, tv.y, gamma, si, sp, stt, a3);
+        seg_acc<K>(xv.z, tv.z, gamma, si, sp, stt, a3); seg_acc<K>(xv.w, tv.w, gamma, si, sp, stt, a3);
+    }
+}
+
+// block = (plane, head): the kind's per-plane sums (kind 0: I = sum p t, P2 = sum p^2, T2 = sum t^2)
+template <int K>
 __global__ void dice_stats_kernel(const DiceP p) {
     __shared__ float red[32];
     const int plane = blockIdx.x, h = blockIdx.y;
     const float* xs = p.x[h] + (size_t)plane * p.HW;
     const float* ts = p.target + (size_t)plane * p.HW;
-    float si = 0.f, sp = 0.f, stt = 0.f;
+    float si = 0.f, sp = 0.f, stt = 0.f, sf = 0.f;
     if ((p.HW & 3) == 0 && ((reinterpret_cast<uintptr_t>(xs) | reinterpret_cast<uintptr_t>(ts)) & 15) == 0) {
         // 16-byte loads, four rounds in flight per thread (the scalar loop below was one dependent 4-byte round trip per element pair:
         // 40 us for the four 256 x 256 heads of a step -- 128 blocks pulling 512 KB each)
@@ -109,53 +179,88 @@ __global__ void dice_stats_kernel(const DiceP p) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) { xv[u] = x4[i + u * B]; tv[u] = t4[i + u * B]; }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float px = sigmoidf_(xv[u].x), py = sigmoidf_(xv[u].y), pz = sigmoidf_(xv[u].z), pw = sigmoidf_(xv[u].w);
-                si = fmaf(px, tv[u].x, si); si = fmaf(py, tv[u].y, si); si = fmaf(pz, tv[u].z, si); si = fmaf(pw, tv[u].w, si);
-                sp = fmaf(px, px, sp); sp = fmaf(py, py, sp); sp = fmaf(pz, pz, sp); sp = fmaf(pw, pw, sp);
-                stt = fmaf(tv[u].x, tv[u].x, stt); stt = fmaf(tv[u].y, tv[u].y, stt); stt = fmaf(tv[u].z, tv[u].z, stt); stt = fmaf(tv[u].w, tv[u].w, stt);
-            }
+            for (int u = 0; u < 4; ++u) seg_acc4<K>(xv[u], tv[u], p.gamma, si, sp, stt, sf);
         }
         for (; i < n4; i += B) {
             const float4 xv = x4[i], tv = t4[i];
-            const float px = sigmoidf_(xv.x), py = sigmoidf_(xv.y), pz = sigmoidf_(xv.z), pw = sigmoidf_(xv.w);
-            si = fmaf(px, tv.x, si); si = fmaf(py, tv.y, si); si = fmaf(pz, tv.z, si); si = fmaf(pw, tv.w, si);
-            sp = fmaf(px, px, sp); sp = fmaf(py, py, sp); sp = fmaf(pz, pz, sp); sp = fmaf(pw, pw, sp);
-            stt = fmaf(tv.x, tv.x, stt); stt = fmaf(tv.y, tv.y, stt); stt = fmaf(tv.z, tv.z, stt); stt = fmaf(tv.w, tv.w, stt);
+            seg_acc4<K>(xv, tv, p.gamma, si, sp, stt, sf);
         }
     } else {
-        for (int i = threadIdx.x; i < p.HW; i += blockDim.x) {
-            const float pr = sigmoidf_(xs[i]), t = ts[i];
-            si = fmaf(pr, t, si); sp = fmaf(pr, pr, sp); stt = fmaf(t, t, stt);
-        }
+        for (int i = threadIdx.x; i < p.HW; i += blockDim.x) seg_acc<K>(xs[i], ts[i], p.gamma, si, sp, stt, sf);
     }
-    si = block_sum(si, red); sp = block_sum(sp, red); stt = block_sum(stt, red);
+    constexpr int S = SegStride<K>::v;
+    si = block_sum(si, red);
+    if constexpr (S >= 3) { sp = block_sum(sp, red); stt = block_sum(stt, red); }
+    if constexpr (S >= 4) sf = block_sum(sf, red);
     if (threadIdx.x == 0) {
-        float* s = p.stats + ((size_t)h * p.planes + plane) * 3;
-        s[0] = si; s[1] = sp; s[2] = stt;
+        float* s = p.stats + ((size_t)h * p.planes + plane) * S;
+        s[0] = si;
+        if constexpr (S >= 3) { s[1] = sp; s[2] = stt; }
+        if constexpr (S >= 4) s[3] = sf;
     }
 }
-// one block: loss[h] = mean_plane(1 - (2I+nr)/(P2+T2+dr)); loss[n_heads] = sum_h hw[h] loss[h]
+// one block: loss[h] = the head's loss (kind 0: mean_plane(1 - (2I+nr)/(P2+T2+dr))); loss[n_heads] = sum_h hw[h] loss[h]
+template <int K>
 __global__ void dice_finalize_kernel(const DiceP p) {
     __shared__ float red[32];
+    constexpr int S = SegStride<K>::v;
     float total = 0.f;
     for (int h = 0; h < p.n_heads; ++h) {
         float s = 0.f;
         for (int i = threadIdx.x; i < p.planes; i += blockDim.x) {
-            const float* st = p.stats + ((size_t)h * p.planes + i) * 3;
-            s += 1.0f - (2.0f * st[0] + p.nr) / (st[1] + st[2] + p.dr);
+            const float* st = p.stats + ((size_t)h * p.planes + i) * S;
+            if constexpr (K == SEG_BCE) s += st[0] / (float)p.HW;
+            else if constexpr (K == SEG_JACCARD) s += 1.0f - (2.0f * st[0] + p.nr) / (2.0f * (st[1] + st[2] - st[0]) + p.dr);
+            else if constexpr (K == SEG_FOCALDICE) s += (1.0f - (2.0f * st[0] + p.nr) / (st[1] + st[2] + p.dr)) + st[3] / (float)p.HW;
+            else s += 1.0f - (2.0f * st[0] + p.nr) / (st[1] + st[2] + p.dr);
         }
-        s = block_sum(s, red) / (float)p.planes;
+        s = block_sum(s, red);
+        if constexpr (K != SEG_JACCARD) s = s / (float)p.planes;
         if (threadIdx.x == 0) p.loss[h] = s;
         total += p.hw[h] * s;
     }
     if (threadIdx.x == 0) p.loss[p.n_heads] = total;
 }
-// dx = scale * d f / d p * p (1 - p),  d f / d p = -(2 t (D+dr) - (2I+nr) 2 p) / (D+dr)^2
+// one element of the gradient.  den / num: the plane's constants; scale = gscale * hw[h] (/ planes for the means), scale_e = scale / HW
+//   kind 0: dx = scale * d f / d p * p (1 - p),  d f / d p = -(2 t (D+dr) - (2I+nr) 2 p) / (D+dr)^2
+//   Jaccard: den = 2 (P + T - I) + dr, d den / d p = 2 (1 - t): d f / d p = -(2 t den - num 2 (1 - t)) / den^2
+template <int K>
+__device__ __forceinline__ float seg_grad(float x, float t, float den, float num, float scale, float scale_e, float gamma) {
+    if constexpr (K == SEG_BCE) {
+        return scale_e * (sigmoidf_(x) - t);
+    } else if constexpr (K == SEG_FOCALDICE) {
+        float pr, g;
+        focal_elem(x, t, gamma, pr, &g);
+        const float dfdp = -(2.0f * t * den - num * 2.0f * pr) / (den * den);
+        return scale * dfdp * pr * (1.0f - pr) + scale_e * g;
+    } else if constexpr (K == SEG_JACCARD) {
+        const float pr = sigmoidf_(x);
+        const float dfdp = -(2.0f * t * den - num * 2.0f * (1.0f - t)) / (den * den);
+        return scale * dfdp * pr * (1.0f - pr);
+    } else {
+        const float pr = sigmoidf_(x);
+        const float dfdp = -(2.0f * t * den - num * 2.0f * pr) / (den * den);
+        return scale * dfdp * pr * (1.0f - pr);
+    }
+}
+template <int K>
+__device__ __forceinline__ void seg_plane_consts(const DiceP& p, int h, int plane, float& den, float& num) {
+    if constexpr (K == SEG_BCE) {
+        den = 1.f; num = 0.f;                               // the gradient of a mean of elementwise terms reads no statistic
+    } else {
+        const float* st = p.stats + ((size_t)h * p.planes + plane) * SegStride<K>::v;
+        if constexpr (K == SEG_JACCARD) den = 2.0f * (st[1] + st[2] - st[0]) + p.dr;
+        else den = st[1] + st[2] + p.dr;
+        num = 2.0f * st[0] + p.nr;
+    }
+}
+template <int K>
 __global__ void dice_bwd_kernel(const DiceP p) {
     const int h = blockIdx.y;
     const size_t total = (size_t)p.planes * p.HW;
-    const float scale = p.gscale * (p.gscale_dev ? *p.gscale_dev : 1.f) * p.hw[h] / (float)p.planes;
+    const float scale = K == SEG_JACCARD ? p.gscale * (p.gscale_dev ? *p.gscale_dev : 1.f) * p.hw[h]
+                                         : p.gscale * (p.gscale_dev ? *p.gscale_dev : 1.f) * p.hw[h] / (float)p.planes;
+    const float scale_e = scale / (float)p.HW;
     if ((p.HW & 3) == 0 && ((reinterpret_cast<uintptr_t>(p.x[h]) | reinterpret_cast<uintptr_t>(p.target) | reinterpret_cast<uintptr_t>(p.dx[h])) & 15) == 0) {
         // four pixels of one plane per thread: 16-byte loads / stores, the plane's constants once per four elements (same formula per element)
         const float4* x4 = reinterpret_cast<const float4*>(p.x[h]);
@@ -164,28 +269,22 @@ __global__ void dice_bwd_kernel(const DiceP p) {
         const int hw4 = p.HW >> 2;
         for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (total >> 2); i += (size_t)gridDim.x * blockDim.x) {
             const int plane = (int)(i / hw4);
-            const float* st = p.stats + ((size_t)h * p.planes + plane) * 3;
-            const float den = st[1] + st[2] + p.dr, num = 2.0f * st[0] + p.nr;
+            float den, num;
+            seg_plane_consts<K>(p, h, plane, den, num);
             const float4 xv = x4[i], tv = t4[i];
             const float xe[4] = {xv.x, xv.y, xv.z, xv.w}, te[4] = {tv.x, tv.y, tv.z, tv.w};
             float o[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float pr = sigmoidf_(xe[e]);
-                const float dfdp = -(2.0f * te[e] * den - num * 2.0f * pr) / (den * den);
-                o[e] = scale * dfdp * pr * (1.0f - pr);
-            }
+            for (int e = 0; e < 4; ++e) o[e] = seg_grad<K>(xe[e], te[e], den, num, scale, scale_e, p.gamma);
             d4[i] = make_float4(o[0], o[1], o[2], o[3]);
         }
         return;
     }
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int plane = i / p.HW;
-        const float* st = p.stats + ((size_t)h * p.planes + plane) * 3;
-        const float den = st[1] + st[2] + p.dr, num = 2.0f * st[0] + p.nr;
-        const float pr = sigmoidf_(p.x[h][i]), t = p.target[i];
-        const float dfdp = -(2.0f * t * den - num * 2.0f * pr) / (den * den);
-        p.dx[h][i] = scale * dfdp * pr * (1.0f - pr);
+        float den, num;
+        seg_plane_consts<K>(p, h, plane, den, num);
+        p.dx[h][i] = seg_grad<K>(p.x[h][i], p.target[i], den, num, scale, scale_e, p.gamma);
     }
 }
 
@@ -355,6 +454,23 @@ __global__ void counts_to_double_kernel(double* out3) {
     }
 }
 
+template <int K>
+int dice_fwd_launch(const DiceP& p, hipStream_t st) {
+    hipLaunchKernelGGL(dice_stats_kernel<K>, dim3(p.planes, p.n_heads), dim3(p.HW >= 16384 ? 1024 : 256), 0, st, p);
+    MTBC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(dice_finalize_kernel<K>, dim3(1), dim3(256), 0, st, p);
+    MTBC_CHECK_LAUNCH();
+    return MTBC_OK;
+}
+template <int K>
+int dice_bwd_launch(const DiceP& p, hipStream_t st) {
+    const size_t total = (size_t)p.planes * p.HW;
+    size_t blocks = cdiv64(total, 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(dice_bwd_kernel<K>, dim3((unsigned)blocks, p.n_heads), dim3(256), 0, st, p);
+    MTBC_CHECK_LAUNCH();
+    return MTBC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -410,8 +526,10 @@ int mtbc_linear_bwd(const mtbc_linear_args* a, void* stream) {
 static int fill_dice(const mtbc_dice_args* a, DiceP* p) {
     if (!a || a->n_heads < 1 || a->n_heads > 4 || a->N <= 0 || a->C <= 0 || a->H <= 0 || a->W <= 0) return MTBC_E_BADSHAPE;
     if (!a->target || !a->stats) return MTBC_E_BADARG;
+    if (a->kind < MTBC_SEG_DICE || a->kind > MTBC_SEG_JACCARD) return MTBC_E_UNSUPPORTED;
     p->n_heads = a->n_heads; p->planes = a->N * a->C; p->HW = a->H * a->W; p->nr = a->smooth_nr; p->dr = a->smooth_dr;
     p->target = a->target; p->stats = a->stats; p->loss = a->loss; p->gscale = a->gscale; p->gscale_dev = a->gscale_dev;
+    p->gamma = a->focal_gamma;
     for (int h = 0; h < 4; ++h) { p->x[h] = a->x[h]; p->dx[h] = a->dx[h]; p->hw[h] = a->head_weight[h]; }
     for (int h = 0; h < a->n_heads; ++h) if (!a->x[h]) return MTBC_E_BADARG;
     return MTBC_OK;
@@ -420,21 +538,23 @@ int mtbc_dice_fwd(const mtbc_dice_args* a, void* stream) {
     DiceP p; int rc = fill_dice(a, &p); if (rc) return rc;
     if (!p.loss) return MTBC_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(dice_stats_kernel, dim3(p.planes, p.n_heads), dim3(p.HW >= 16384 ? 1024 : 256), 0, st, p);
-    MTBC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(256), 0, st, p);
-    MTBC_CHECK_LAUNCH();
-    return MTBC_OK;
+    switch (a->kind) {
+        case MTBC_SEG_BCE: return dice_fwd_launch<SEG_BCE>(p, st);
+        case MTBC_SEG_FOCALDICE: return dice_fwd_launch<SEG_FOCALDICE>(p, st);
+        case MTBC_SEG_JACCARD: return dice_fwd_launch<SEG_JACCARD>(p, st);
+        default: return dice_fwd_launch<SEG_DICE>(p, st);
+    }
 }
 int mtbc_dice_bwd(const mtbc_dice_args* a, void* stream) {
     DiceP p; int rc = fill_dice(a, &p); if (rc) return rc;
     for (int h = 0; h < a->n_heads; ++h) if (!a->dx[h]) return MTBC_E_BADARG;
-    const size_t total = (size_t)p.planes * p.HW;
-    size_t blocks = cdiv64(total, 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(dice_bwd_kernel, dim3((unsigned)blocks, p.n_heads), dim3(256), 0, (hipStream_t)stream, p);
-    MTBC_CHECK_LAUNCH();
-    return MTBC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    switch (a->kind) {
+        case MTBC_SEG_BCE: return dice_bwd_launch<SEG_BCE>(p, st);
+        case MTBC_SEG_FOCALDICE: return dice_bwd_launch<SEG_FOCALDICE>(p, st);
+        case MTBC_SEG_JACCARD: return dice_bwd_launch<SEG_JACCARD>(p, st);
+        default: return dice_bwd_launch<SEG_DICE>(p, st);
+    }
 }
 
 int mtbc_focal_fwd_bwd(const mtbc_focal_args* a, void* stream) {

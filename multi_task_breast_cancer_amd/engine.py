@@ -1089,13 +1089,19 @@ class StepPlan:
     # ------------------------------------------------------------------ losses (fused-step path)
     def fused_losses(self, seg_heads: Sequence[Act], logits: Act, mask: torch.Tensor, onehot: torch.Tensor,
                      alpha: float, inversely_weighted: bool, focal_weight: Optional[torch.Tensor] = None,
-                     loss_scale: float = 1.0, binary: bool = False, cls_gamma: float = 2.0):
-        """criterions.py:52-76 + training_multitask.py:98 on device: Dice over the heads (weights 1/(j+1) from the
-        LAST head backwards), Focal on the logits, alpha-mix, NaN flag.  Gradients land in the heads' grad buffers."""
+                     loss_scale: float = 1.0, binary: bool = False, cls_gamma: float = 2.0, seg_criterion: str = "DICE"):
+        """criterions.py:52-76 + training_multitask.py:98 on device: the segmentation criterion over the heads (weights 1/(j+1) from
+        the LAST head backwards), Focal on the logits, alpha-mix, NaN flag.  Gradients land in the heads' grad buffers.
+        `seg_criterion`: the reference's `loss.function` name -- "DICE" | "BCE" | "FocalDICE" | "Jaccard" (_lib.SEG_CRITERIA): the same two
+        ops with another mtbc_dice_args.kind.  Jaccard is a SUM over the planes (reduction="sum"): the kernel leaves the 1 / planes out,
+        the head weights are passed as they are."""
         nh = len(seg_heads)
         assert 1 <= nh <= 4
         N, C_, H, W = seg_heads[0].data.shape
-        self.dice_stats = self.alloc(nh * N * C_ * 3)
+        if seg_criterion not in L.SEG_CRITERIA:
+            raise ValueError(f"unknown segmentation criterion {seg_criterion!r} ({' | '.join(L.SEG_CRITERIA)})")
+        seg_kind, seg_nr, seg_dr, seg_gamma, _ = L.SEG_CRITERIA[seg_criterion]
+        self.dice_stats = self.alloc(nh * N * C_ * L.SEG_STATS_STRIDE[seg_kind])
         self.dice_loss = self.alloc(nh + 1)
         self.focal_loss = self.alloc(1)
         self.loss_out = self.alloc(4)
@@ -1108,7 +1114,8 @@ class StepPlan:
         def dice_base(kind: int) -> L.Op:
             op = _mk(kind)
             a = op.u.dice
-            a.n_heads, a.N, a.C, a.H, a.W, a.smooth_nr, a.smooth_dr = nh, N, C_, H, W, 1.0, 1.0
+            a.n_heads, a.N, a.C, a.H, a.W, a.smooth_nr, a.smooth_dr = nh, N, C_, H, W, seg_nr, seg_dr
+            a.kind, a.focal_gamma = seg_kind, seg_gamma
             for i, h in enumerate(seg_heads):
                 a.x[i] = h.data.data_ptr()
                 a.head_weight[i] = weights[i]

@@ -10,7 +10,7 @@ from pathlib import Path
 import torch
 from torch.optim.lr_scheduler import CosineAnnealingLR, ReduceLROnPlateau
 
-from .criterions import DiceLoss, FocalLoss
+from .criterions import DiceFocalLoss, DiceLoss, FocalLoss
 from .nets import MTnnUNet, MTUNetPlusPlus
 from .optim import FusedAdam
 
@@ -54,14 +54,19 @@ def init_optimizer(model: torch.nn.Module, optimizer: str, learning_rate: float 
 
 
 def init_criterion_segmentation(loss_function: str = "dice") -> torch.nn.Module:
-    """experiment_init.py:199-232.  'DICE' (config.yaml) is the HIP kernel; 'BCE' is torch's module as in the
-    reference; the remaining names are MONAI losses (not installed here, not on the hot path) -> same exit as the
-    reference takes for an unknown name."""
+    """experiment_init.py:199-232.  'DICE', 'FocalDICE' and 'Jaccard' are the HIP kernels (the fused step has them and 'BCE' under
+    seg_criterion=...); 'BCE' is torch's module as in the reference; the remaining names ('CrossentropyDICE', 'GeneralizedDICE',
+    'Hausdorff', 'FocalLoss') are MONAI losses whose arithmetic cannot be pinned here (not installed, point-release dependent) -> the
+    same exit as the reference takes for an unknown name."""
     if loss_function == "DICE":
         return DiceLoss(include_background=True, sigmoid=True, smooth_dr=1, smooth_nr=1, squared_pred=True)
+    if loss_function == "FocalDICE":
+        return DiceFocalLoss(include_background=True, sigmoid=True, smooth_dr=1, smooth_nr=1, squared_pred=True)
+    if loss_function == "Jaccard":
+        return DiceLoss(include_background=True, sigmoid=True, jaccard=True, reduction="sum")
     if loss_function == "BCE":
         return torch.nn.BCEWithLogitsLoss()
-    logging.info("Select a loss function allowed on the MI355X hot path: ['DICE', 'BCE']")
+    logging.info("Select a loss function allowed on the MI355X hot path: ['DICE', 'FocalDICE', 'Jaccard', 'BCE']")
     sys.exit()
 
 

@@ -778,17 +778,22 @@ def linear_bwd(x, w, y, dy, relu=False):
 
 
 # ------------------------------------------------------------------ losses / optimiser
-def dice_multihead(xs: Sequence[torch.Tensor], target, weights: Sequence[float], gscale: float = 1.0):
-    """returns (loss[n_heads+1], [dx per head])"""
+def dice_multihead(xs: Sequence[torch.Tensor], target, weights: Sequence[float], gscale: float = 1.0, kind: int = 0,
+                   smooth: Optional[Tuple[float, float]] = None, focal_gamma: float = 2.0):
+    """returns (loss[n_heads+1], [dx per head]).  kind: L.SEG_DICE (0, the default) | SEG_BCE | SEG_FOCALDICE | SEG_JACCARD; `smooth` = (nr, dr),
+    default the reference's for the kind (1 / 1; Jaccard: MONAI's 1e-5 / 1e-5)."""
     _chk(*xs, target)
     nh = len(xs)
     N, Cc, H, W = xs[0].shape
     dev = target.device
-    stats = torch.empty(nh * N * Cc * 3, dtype=torch.float32, device=dev)
+    stats = torch.empty(nh * N * Cc * L.SEG_STATS_STRIDE[kind], dtype=torch.float32, device=dev)
     loss = torch.empty(nh + 1, dtype=torch.float32, device=dev)
     dxs = [torch.empty_like(x) for x in xs]
     a = L.DiceArgs()
-    a.n_heads, a.N, a.C, a.H, a.W, a.smooth_nr, a.smooth_dr = nh, N, Cc, H, W, 1.0, 1.0
+    nr, dr = smooth if smooth is not None else ((1e-5, 1e-5) if kind == L.SEG_JACCARD else (1.0, 1.0))
+    a.n_heads, a.N, a.C, a.H, a.W, a.smooth_nr, a.smooth_dr = nh, N, Cc, H, W, nr, dr
+    if kind != L.SEG_DICE:
+        a.kind, a.focal_gamma = kind, (focal_gamma if kind == L.SEG_FOCALDICE else 0.0)
     for i in range(nh):
         a.x[i], a.dx[i], a.head_weight[i] = xs[i].data_ptr(), dxs[i].data_ptr(), weights[i]
     a.target, a.stats, a.loss, a.gscale = target.data_ptr(), stats.data_ptr(), loss.data_ptr(), gscale

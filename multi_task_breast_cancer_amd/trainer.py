@@ -162,6 +162,19 @@ def train_metrics_from_packed(packed: np.ndarray, capacity: int, world: int = 1)
 # ------------------------------------------------------------------------------------------------
 # the fused step (HIP)
 # ------------------------------------------------------------------------------------------------
+def _check_seg_criterion(name: str, distributed: bool) -> str:
+    if name not in L.SEG_CRITERIA:
+        raise ValueError(f"unknown segmentation criterion {name!r} ({' | '.join(L.SEG_CRITERIA)}; the other `loss.function` names of the "
+                         f"reference are not on HIP)")
+    if distributed and L.SEG_CRITERIA[name][4]:
+        # the shard-weight mechanism makes the all-reduced gradient that of the global batch for a MEAN over the batch (weight = n_local / n_batch
+        # times world, then 1 / world); a SUM over the batch would need the factor 1 / world undone, i.e. a factor that depends on each step's
+        # global batch, which the ranks' step programs do not carry
+        raise NotImplementedError(f"seg_criterion={name!r} sums over the batch (reduction='sum'): the data-parallel step averages the ranks' gradients, "
+                                  f"which is exact for a mean over the batch only -- train it on one device, or use a mean criterion")
+    return name
+
+
 class FusedTrainStep:
     """One optimisation step of training_multitask.py:87-103 as ONE stream-ordered program.  `cls_criterion`: "Focal" (config.yaml's
     default, FocalLoss alpha 1 gamma 2), "CE" (CrossEntropyLoss = gamma 0) -- experiment_init.py:232-262; with n_classes == 2 the model has
@@ -175,7 +188,10 @@ class FusedTrainStep:
     def __init__(self, model, optimizer, alpha: float, inversely_weighted: bool = True, n_classes: int = 3,
                  distributed: bool = False, n_buckets: int = 4, focal_weight: Optional[torch.Tensor] = None,
                  cls_criterion: str = "Focal", graph: Optional[bool] = None, loss_scale=None, metrics: bool = False,
-                 metrics_capacity: int = 4096):
+                 metrics_capacity: int = 4096, seg_criterion: str = "DICE"):
+        # seg_criterion: the reference's `loss.function` (experiment_init.py:199-232) -- "DICE" | "BCE" | "FocalDICE" | "Jaccard", all in the same
+        # two loss ops of the step program (mtbc_dice_args.kind); the remaining names are not on HIP (experiment_init.init_criterion_segmentation).
+        self.seg_criterion = _check_seg_criterion(seg_criterion, distributed)
         # metrics: off = exactly the launches of a step without it.  metrics_capacity: rows (= batches per epoch) of the device table, 32 bytes each;
         # allocated once and never moved, so a captured graph stays valid across epochs.
         self.metrics = bool(metrics)
@@ -242,7 +258,7 @@ class FusedTrainStep:
 
     def _compiled(self, N: int, H: int, W: int):
         st = self.model.compiled(N, H, W, fused_loss={"alpha": self.alpha, "inversely_weighted": self.iw, "focal_weight": self.focal_weight,
-                                                      "binary": self.binary, "cls_gamma": self.cls_gamma,
+                                                      "binary": self.binary, "cls_gamma": self.cls_gamma, "seg_criterion": self.seg_criterion,
                                                       **({} if self.scaler is None else {"loss_scale": 1.0})})
         if st is not self._st:
             self._st = st
@@ -520,8 +536,9 @@ class FusedEvalStep:
     (avg_val_loss, avg_val_dice, val_acc, val_f1, avg_seg_val_loss, avg_cls_val_loss)."""
 
     def __init__(self, model, alpha: float, inversely_weighted: bool = True, n_classes: int = 3,
-                 focal_weight: Optional[torch.Tensor] = None, cls_criterion: str = "Focal"):
+                 focal_weight: Optional[torch.Tensor] = None, cls_criterion: str = "Focal", seg_criterion: str = "DICE"):
         self.model, self.alpha, self.iw, self.n_classes = model, float(alpha), bool(inversely_weighted), n_classes
+        self.seg_criterion = _check_seg_criterion(seg_criterion, False)      # as `cls_criterion`: the criterion the run trains with
         self.binary = n_classes == 2
         if cls_criterion not in ("Focal", "CE"):
             raise ValueError(f"unknown classification criterion {cls_criterion!r} (Focal | CE; the binary head always evaluates BCEWithLogits)")
@@ -557,7 +574,8 @@ class FusedEvalStep:
 
     def _compiled(self, N: int, H: int, W: int):
         return self.model.compiled(N, H, W, fused_loss={"alpha": self.alpha, "inversely_weighted": self.iw,
-                                                        "focal_weight": self.focal_weight, "binary": self.binary, "cls_gamma": self.cls_gamma})
+                                                        "focal_weight": self.focal_weight, "binary": self.binary, "cls_gamma": self.cls_gamma,
+                                                        "seg_criterion": self.seg_criterion})
 
     @torch.no_grad()
     def indexed(self, dataset, index) -> None:
