@@ -28,6 +28,8 @@ extern "C" {
 #define MTBC_VERSION 202            /* 0.2.2 (round 4: mtbc_adam_args.dynamic appended + mtbc_adam_dynamic); 0.2.1: mtbc_conv3x3_args.wgrad_sync appended; 0.2.0: the argument structs grew in round 2 (fields appended); a binding compiled against
                                        another version must refuse the library (mtbc_version()) -- layouts are not negotiated */
 #define MTBC_MAX_SEGS 6
+#define MTBC_STEM_MAX_CIN 5         /* the stem kernels of mtbc_conv3x3_*: ONE fp32 planar input segment of 1 .. 5 channels -- the image plus the four
+                                       intensity channels of data.augmentation (experiment_init.py:97, n_augments) */
 
 enum {
     MTBC_OK = 0,
@@ -96,7 +98,10 @@ typedef struct {
     int32_t out_accumulate;          /* fwd with operand_layout C8 only: 1 = add the result to `out` instead of overwriting
                                         it.  A forward launch over the dz of ALL 3x3 consumers of a tensor, with
                                         mtbc_conv3x3_weight_view(mode 1) weights, is that tensor's gathered dgrad.  */
-    int32_t out_layout;              /* fwd with operand_layout C8 only: MTBC_LAYOUT_C8 = `out` is written as a 16-bit
+    int32_t out_layout;              /* fwd with operand_layout C8 -- or the stem: operand_layout 0, n_in = 1, Cin <= MTBC_STEM_MAX_CIN, W % 4 == 0,
+                                        16-byte aligned, batch_stride % 4 == 0, compute 1 | 2, exact fp32 arithmetic; with planar operands anything
+                                        else (Cin > MTBC_STEM_MAX_CIN, n_in > 1) is MTBC_E_UNSUPPORTED; the stem's weight gradient takes its dz in
+                                        MTBC_LAYOUT_C8 with the same fp32 planar segment in `in` -- : MTBC_LAYOUT_C8 = `out` is written as a 16-bit
                                         channel-blocked tensor [N][Cout/8][H*W][8] of the type of `compute` (fp32 accumulate,
                                         + bias, ONE round-to-nearest-even) instead of fp32 planes: the conv output of the
                                         16-bit modes, read by mtbc_instnorm_args.z_layout = C8 (what torch.autocast stores

@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MTBC_LIB") or os.path.join(_HERE, "libmtbc_hip.so")   # MTBC_LIB: A/B builds of the same ABI
 
 MAX_SEGS = 6
+STEM_MAX_CIN = 5           # MTBC_STEM_MAX_CIN of include/mtbc.h: the image + the four intensity channels of data.augmentation
 c_float_p = C.POINTER(C.c_float)
 
 

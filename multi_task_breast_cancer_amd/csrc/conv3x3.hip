@@ -3240,6 +3240,200 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_stem_c8_kernel(const float*
     }
 }
 
+// ------------------------------------------------------------------ the stem with intensity channels (Cin = 2 .. MTBC_STEM_MAX_CIN)
+// data.augmentation puts up to four intensity channels beside the image: the first conv then reads ONE fp32 planar segment of CIN planes.
+// Separate instances (the 1-channel kernels above stay as they are): same tiling and epilogues, the 3 x 6 window of one input plane at a
+// time, and the accumulation order of conv3x3_direct_kernel -- ci outer, taps 0..8 inner, fmaf(w, v, acc), bias last -- so that the
+// fp32 result is the direct kernel's bit for bit and the 16-bit result is that value rounded once.
+__device__ __forceinline__ void stem_window(const float* __restrict__ plane, int H, int W, int y, int x0, bool live, float (&v)[3][6]) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const int yy = y + r - 1;
+        const bool rowok = live && yy >= 0 && yy < H;
+        const float4 mid = rowok ? *reinterpret_cast<const float4*>(plane + (size_t)yy * W + x0) : make_float4(0.f, 0.f, 0.f, 0.f);
+        v[r][0] = (rowok && x0 > 0) ? plane[(size_t)yy * W + x0 - 1] : 0.f;
+        v[r][1] = mid.x; v[r][2] = mid.y; v[r][3] = mid.z; v[r][4] = mid.w;
+        v[r][5] = (rowok && x0 + 4 < W) ? plane[(size_t)yy * W + x0 + 4] : 0.f;
+    }
+}
+// a[i][e]: output channel cog + i, pixel x0 + e.  A channel past Cout (fp32 kernel only: Cout % 8 != 0) is never stored.  BRANCH: skip it with a
+// (uniform) branch per channel instead of repeating the last channel's weights.  Which form hipcc compiles well differs per kernel
+// (tools/kres.py): without the branches it hoists all 72 x CIN scalar weight loads to the top -- in the 16-bit kernel 120 .. 690 SGPRs spilled
+// into VGPR lanes --, with them the fp32 kernel's register allocation falls apart (256 VGPRs + 100 AGPRs, one wave per SIMD).
+template <int CIN, bool BRANCH>
+__device__ __forceinline__ void stem_mc_accumulate(const float* __restrict__ src, const float* __restrict__ w, int H, int W, int Cout, int cog,
+                                                   int y, int x0, bool live, float (&a)[8][4]) {
+    const size_t HW = (size_t)H * W;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a[i][e] = 0.f;
+#pragma unroll
+    for (int ci = 0; ci < CIN; ++ci) {
+        float v[3][6];
+        stem_window(src + (size_t)ci * HW, H, W, y, x0, live, v);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            if (BRANCH && cog + i >= Cout) continue;
+            const int co = cog + i < Cout ? cog + i : Cout - 1;
+            float wk[9];
+#pragma unroll
+            for (int t = 0; t < 9; ++t) wk[t] = w[((size_t)co * CIN + ci) * 9 + t];
+#pragma unroll
+            for (int t = 0; t < 9; ++t)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) a[i][e] = fmaf(wk[t], v[t / 3][e + t % 3], a[i][e]);
+        }
+    }
+}
+
+// fp32: the counterpart of conv3x3_stem_fwd_kernel -- 4 pixels x 8 output channels per thread, float4 stores
+template <int CIN>
+__global__ __launch_bounds__(128) void conv3x3_stem_mc_fwd_kernel(const float* __restrict__ x, long long xbs, const float* __restrict__ w,
+                                                                  const float* __restrict__ bias, float* __restrict__ out, int N, int H, int W, int Cout) {
+    const int w4 = W >> 2;
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;           // float4 index inside a plane
+    const int cog = blockIdx.y * 8, n = blockIdx.z;
+    const bool live = q < H * w4;              // (no early return: the weight reads stay in uniform control flow -- scalar loads)
+    const int y = live ? q / w4 : 0, x0 = live ? (q % w4) * 4 : 0;
+    float a[8][4];
+    stem_mc_accumulate<CIN, false>(x + (size_t)n * xbs, w, H, W, Cout, cog, y, x0, live, a);
+    const size_t HW = (size_t)H * W;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int co = cog + i;
+        if (co >= Cout) break;
+        const float b = bias ? bias[co] : 0.f;
+        if (live) *reinterpret_cast<float4*>(out + ((size_t)n * Cout + co) * HW + (size_t)y * W + x0) = make_float4(a[i][0] + b, a[i][1] + b, a[i][2] + b, a[i][3] + b);
+    }
+}
+
+// 16-bit modes: the counterpart of conv3x3_stem_fwd_c8_kernel -- one 16-byte channel-blocked piece per pixel (OF16: fp16, saturated at
+// +-65504; else bf16) + the per-block InstanceNorm {sum, sum of squares} of the STORED values -> stats[n][blockIdx.x][co][2]
+template <int CIN, bool OF16>
+__global__ __launch_bounds__(128) void conv3x3_stem_mc_fwd_c8_kernel(const float* __restrict__ x, long long xbs, const float* __restrict__ w,
+                                                                     const float* __restrict__ bias, unsigned short* __restrict__ out,
+                                                                     float* __restrict__ stats, int N, int H, int W, int Cout) {
+    using TO = LP<OF16>;
+    typedef unsigned st_u32x4 __attribute__((ext_vector_type(4)));
+    __shared__ float red[2][16];
+    const int w4 = W >> 2;
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;           // 4-pixel group inside a plane
+    const int cog = blockIdx.y * 8, n = blockIdx.z;                // Cout % 8 == 0
+    const bool live = q < H * w4;
+    const int y = live ? q / w4 : 0, x0 = live ? (q % w4) * 4 : 0;
+    float a[8][4];
+    stem_mc_accumulate<CIN, true>(x + (size_t)n * xbs, w, H, W, Cout, cog, y, x0, live, a);
+    const size_t HW = (size_t)H * W;
+    float ss[8], sq[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { ss[i] = 0.f; sq[i] = 0.f; }
+    float bv[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) bv[i] = bias ? bias[cog + i] : 0.f;
+    unsigned short* dst = out + (((size_t)n * (Cout / 8) + blockIdx.y) * HW + (size_t)y * W + x0) * 8;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float o[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] = OF16 ? __builtin_amdgcn_fmed3f(a[i][e] + bv[i], -65504.f, 65504.f) : a[i][e] + bv[i];
+        const st_u32x4 u = __builtin_bit_cast(st_u32x4, TO::pack(o));
+        if (live) *reinterpret_cast<st_u32x4*>(dst + e * 8) = u;
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const unsigned uu = u[h];
+            const float lo = live ? TO::lo(uu) : 0.f, hi = live ? TO::hi(uu) : 0.f;
+            ss[2 * h] += lo; sq[2 * h] += lo * lo; ss[2 * h + 1] += hi; sq[2 * h + 1] += hi * hi;
+        }
+    }
+    if (stats) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { ss[i] = wave_sum_rows(ss[i]); sq[i] = wave_sum_rows(sq[i]); }
+        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { red[wv][2 * i] = ss[i]; red[wv][2 * i + 1] = sq[i]; }
+        }
+        __syncthreads();
+        if (threadIdx.x < 16)
+            stats[(((size_t)n * gridDim.x + blockIdx.x) * Cout + cog) * 2 + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x];
+    }
+}
+
+// The weight gradient of that stem: dz 16-bit channel-blocked, the CIN input planes fp32.  8 x CIN x 9 sums per 4-pixel group are too many
+// for one thread's registers (360 at CIN = 5), so the TAP ROWS are dealt to waves: block = (image, 8-channel group, band) as in
+// conv3x3_wgrad_stem_c8_kernel, 6 waves = 2 pixel streams x 3 tap rows.  A thread loads each 16-byte piece of dz of its pixels once and
+// uses it for all CIN input channels (dz is the large operand: Cout 16-bit values per pixel against CIN floats; the three tap-row waves of
+// a stream run side by side on one CU and share the piece in its vector cache), and of the input it loads only ITS row of the window:
+// 8 x CIN x 3 sums and CIN x 6 input values in registers.  A tap row that lies outside the image (first / last image row) is skipped.
+// partial[(n * S + band)][co][ci][9]; fixed order: thread, wave (DPP row sums), stream 0 + stream 1.
+template <int CIN, bool F16>
+__global__ __launch_bounds__(384) void conv3x3_wgrad_stem_mc_c8_kernel(const float* __restrict__ x, long long xbs, const unsigned short* __restrict__ dz8,
+                                                                       float* __restrict__ partial, int N, int H, int W, int Cout, int S) {
+    using T = LP<F16>;
+    typedef unsigned st_u32x4 __attribute__((ext_vector_type(4)));
+    __shared__ float wsum[6][8 * CIN * 3];
+    const int G8 = Cout / 8;
+    int b = blockIdx.x;
+    const int band = b % S; b /= S;
+    const int g = b % G8, n = b / G8;
+    const int HW = H * W, W4 = W >> 2, n4 = HW >> 2;
+    const int q_lo = (int)((long long)n4 * band / S), q_hi = (int)((long long)n4 * (band + 1) / S);
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r = wid % 3, stream = wid / 3;
+    const float* src = x + (size_t)n * xbs;
+    const unsigned short* gz = dz8 + ((size_t)n * G8 + g) * (size_t)HW * 8;
+    float acc[8][CIN][3];
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+#pragma unroll
+        for (int ci = 0; ci < CIN; ++ci)
+#pragma unroll
+            for (int s = 0; s < 3; ++s) acc[c][ci][s] = 0.f;
+    for (int q = q_lo + stream * 64 + lane; q < q_hi; q += 128) {
+        const int y = q / W4, x4 = (q % W4) * 4;
+        const int yy = y + r - 1;
+        if (yy < 0 || yy >= H) continue;
+        float xv[CIN][6];
+#pragma unroll
+        for (int ci = 0; ci < CIN; ++ci) {
+            const float* row = src + (size_t)ci * HW + (size_t)yy * W;
+            const float4 c = *reinterpret_cast<const float4*>(row + x4);
+            xv[ci][1] = c.x; xv[ci][2] = c.y; xv[ci][3] = c.z; xv[ci][4] = c.w;
+            xv[ci][0] = x4 > 0 ? row[x4 - 1] : 0.f;
+            xv[ci][5] = x4 + 4 < W ? row[x4 + 4] : 0.f;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const st_u32x4 u = *reinterpret_cast<const st_u32x4*>(gz + ((size_t)y * W + x4 + e) * 8);
+            float ge[8];
+#pragma unroll
+            for (int h = 0; h < 4; ++h) { const unsigned uu = u[h]; ge[2 * h] = T::lo(uu); ge[2 * h + 1] = T::hi(uu); }
+#pragma unroll
+            for (int c = 0; c < 8; ++c)
+#pragma unroll
+                for (int ci = 0; ci < CIN; ++ci)
+#pragma unroll
+                    for (int s = 0; s < 3; ++s) acc[c][ci][s] = fmaf(ge[c], xv[ci][e + s], acc[c][ci][s]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+#pragma unroll
+        for (int ci = 0; ci < CIN; ++ci)
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+                const float v = wave_sum_rows(acc[c][ci][s]);
+                if (lane == 0) wsum[wid][(c * CIN + ci) * 3 + s] = v;
+            }
+    __syncthreads();
+    if (threadIdx.x < 72 * CIN) {
+        const int t = threadIdx.x % 9, cc = threadIdx.x / 9;            // cc = c * CIN + ci
+        const int k = cc * 3 + t % 3;
+        partial[(((size_t)n * S + band) * Cout + 8 * g) * (CIN * 9) + threadIdx.x] = wsum[t / 3][k] + wsum[3 + t / 3][k];
+    }
+}
+
 // wgrad direct: block = (co, ci, split over n); 9 sums per thread, block-reduced.  partial[split][co][ci][9]
 struct DirWgP {
     int N, H, W, Cin, Cout, nsplit;
@@ -3522,7 +3716,8 @@ int launch_igemm_c8_ring_mt(int MT, const ConvP& p, int mblocks, bool f16, hipSt
 // from it, and mtbc_conv3x3_kernel_name() -- the same dispatcher called without a stream -- prints it: the name cannot drift from the launch.
 enum KernelFamily {
     KF_IGEMM, KF_IGEMM_DMA, KF_IGEMM_LP, KF_IGEMM_C8, KF_IGEMM_C8_RING, KF_STEM_FWD, KF_STEM_FWD_C8, KF_DIRECT,
-    KF_WGRAD_STEM_C8, KF_WGRAD_C8, KF_WGRAD_C8W, KF_WGRAD_C8I, KF_WGRAD_MFMA, KF_WGRAD_LP, KF_WGRAD_LP2, KF_WGRAD_SMALLCIN, KF_WGRAD_DIRECT
+    KF_WGRAD_STEM_C8, KF_WGRAD_C8, KF_WGRAD_C8W, KF_WGRAD_C8I, KF_WGRAD_MFMA, KF_WGRAD_LP, KF_WGRAD_LP2, KF_WGRAD_SMALLCIN, KF_WGRAD_DIRECT,
+    KF_STEM_MC_FWD, KF_STEM_MC_FWD_C8, KF_WGRAD_STEM_MC_C8          // the stem with intensity channels: <CIN>, <CIN, OF16>, <CIN, F16>
 };
 struct KernelFamilyInfo { const char* name; int nargs; unsigned bools; };      // bools: bit i = template argument i is a bool
 constexpr KernelFamilyInfo KFAM[] = {
@@ -3530,7 +3725,7 @@ constexpr KernelFamilyInfo KFAM[] = {
     {"conv3x3_igemm_c8_ring_kernel", 5, 4}, {"conv3x3_stem_fwd_kernel", 0, 0}, {"conv3x3_stem_fwd_c8_kernel", 1, 1}, {"conv3x3_direct_kernel", 0, 0},
     {"conv3x3_wgrad_stem_c8_kernel", 1, 1}, {"conv3x3_wgrad_c8_kernel", 2, 1}, {"conv3x3_wgrad_c8w_kernel", 3, 5}, {"conv3x3_wgrad_c8i_kernel", 3, 5},
     {"conv3x3_wgrad_mfma_kernel", 3, 4}, {"conv3x3_wgrad_lp_kernel", 3, 4}, {"conv3x3_wgrad_lp2_kernel", 1, 1}, {"conv3x3_wgrad_smallcin_kernel", 0, 0},
-    {"conv3x3_wgrad_direct_kernel", 0, 0},
+    {"conv3x3_wgrad_direct_kernel", 0, 0}, {"conv3x3_stem_mc_fwd_kernel", 1, 0}, {"conv3x3_stem_mc_fwd_c8_kernel", 2, 2}, {"conv3x3_wgrad_stem_mc_c8_kernel", 2, 2},
 };
 enum { KR_SPLITK = 1, KR_FIXUP = 2, KR_CHANNEL_SUMS = 4 };      // the weight gradient's reduction: a reduction launch / in the kernel / + dbias launch
 struct KernelChoice { int fam; int t[5]; int red; };
@@ -3695,12 +3890,12 @@ bool c8_segs_ok(const mtbc_seg* segs, int nseg) {
 }
 WgPlan plan_wgrad(const mtbc_conv3x3_args* a) {
     WgPlan w{};
-    if (a->operand_layout == MTBC_LAYOUT_C8 && a->Cin == 1) {      // conv3x3_wgrad_stem_c8_kernel: (image, band) splits
+    if (a->operand_layout == MTBC_LAYOUT_C8 && a->Cin <= MTBC_STEM_MAX_CIN) {      // conv3x3_wgrad_stem_c8_kernel / conv3x3_wgrad_stem_mc_c8_kernel: (image, band) splits
         // (image, 8-channel group, band) blocks: 16 bands on 256 x 256 planes -- with 4 a step's stem launch was 384 blocks = 1.5 waves per SIMD,
         // each walking 16 iterations of {load, wait, 288 FMAs}: nobody to run while a wave waits (87 us for 110 MB)
         const int bands = (a->H * a->W >= 65536) ? 16 : (a->H * a->W >= 16384) ? 4 : 1;
         w.nsplit = a->N * bands;
-        w.partial_elems = (size_t)w.nsplit * a->Cout * 9;
+        w.partial_elems = (size_t)w.nsplit * a->Cout * a->Cin * 9;
         w.dbias_elems = 0;
         return w;
     }
@@ -3824,7 +4019,7 @@ WgPlan plan_wgrad(const mtbc_conv3x3_args* a) {
         bool al = a->W % 4 == 0 && (reinterpret_cast<uintptr_t>(a->dout) & 15) == 0;
         for (int i = 0; al && i < a->n_in; ++i)
             al = (reinterpret_cast<uintptr_t>(a->in[i].ptr) & 15) == 0 && a->in[i].batch_stride % 4 == 0;
-        w.smallcin = !a->force_direct && a->Cin <= 4 && al;
+        w.smallcin = !a->force_direct && a->Cin <= MTBC_STEM_MAX_CIN && al;
         const int bands = (a->H * a->W >= 16384) ? 4 : 1;
         w.nsplit = w.smallcin ? a->N * bands : (a->N < 16 ? a->N : 16);
     }
@@ -3917,18 +4112,32 @@ static int conv_fwd(const mtbc_conv3x3_args* a, hipStream_t st, KernelChoice* qu
     mtbc_seg o{a->out, (int64_t)a->Cout * a->H * a->W, a->Cout, a->out_accumulate ? 1 : 0};
     rc = make_segtable(&o, 1, a->Cout, &out); if (rc) return rc;
     if (a->out_accumulate && a->operand_layout != MTBC_LAYOUT_C8) return MTBC_E_UNSUPPORTED;
-    const bool stem = a->Cin == 1 && a->n_in == 1 && !a->force_direct && a->W % 4 == 0 && a->in[0].batch_stride % 4 == 0 &&
+    const bool stem = a->Cin <= MTBC_STEM_MAX_CIN && a->n_in == 1 && !a->force_direct && a->W % 4 == 0 && a->in[0].batch_stride % 4 == 0 &&
                       (reinterpret_cast<uintptr_t>(a->in[0].ptr) & 15) == 0 && (reinterpret_cast<uintptr_t>(a->out) & 15) == 0;
     if (a->out_layout == MTBC_LAYOUT_C8 && a->operand_layout == MTBC_LAYOUT_PLANAR) {
-        // the stem (Cin == 1) of the 16-bit modes: fp32 operands, output channel-blocked 16-bit (+ InstanceNorm statistics)
+        // the stem (Cin <= MTBC_STEM_MAX_CIN, one segment) of the 16-bit modes: fp32 operands, output channel-blocked 16-bit (+ InstanceNorm statistics)
         if (!stem || !a->w || a->Cout % 8 || (a->compute != 1 && a->compute != 2) || a->out_accumulate) return MTBC_E_UNSUPPORTED;
         if (a->out_type != 0 && a->out_type != a->compute && !(a->out_type == 2 && a->compute == 1)) return MTBC_E_BADARG;
         if (a->stats_partial && (reinterpret_cast<uintptr_t>(a->stats_partial) & 15)) return MTBC_E_BADARG;
         const dim3 grid(cdiv(a->H * (a->W / 4), 128), a->Cout / 8, a->N);
         unsigned short* o16 = reinterpret_cast<unsigned short*>(a->out);
-        const KernelChoice k = kchoice(KF_STEM_FWD_C8, a->compute == 2 || a->out_type == 2);
+        const bool of16 = a->compute == 2 || a->out_type == 2;
+        const KernelChoice k = a->Cin == 1 ? kchoice(KF_STEM_FWD_C8, of16) : kchoice(KF_STEM_MC_FWD_C8, a->Cin, of16);
         if (query) { *query = k; return MTBC_OK; }
-        if (k.t[0])
+        if (k.fam == KF_STEM_MC_FWD_C8) {
+#define MTBC_STEM_MC_C8(CIN_)                                                                                                                  \
+            do {                                                                                                                               \
+                if (of16) hipLaunchKernelGGL((conv3x3_stem_mc_fwd_c8_kernel<CIN_, true>), grid, dim3(128), 0, st, a->in[0].ptr, (long long)a->in[0].batch_stride, a->w, a->bias, o16, a->stats_partial, a->N, a->H, a->W, a->Cout); \
+                else hipLaunchKernelGGL((conv3x3_stem_mc_fwd_c8_kernel<CIN_, false>), grid, dim3(128), 0, st, a->in[0].ptr, (long long)a->in[0].batch_stride, a->w, a->bias, o16, a->stats_partial, a->N, a->H, a->W, a->Cout); \
+            } while (0)
+            switch (a->Cin) {
+            case 2: MTBC_STEM_MC_C8(2); break;
+            case 3: MTBC_STEM_MC_C8(3); break;
+            case 4: MTBC_STEM_MC_C8(4); break;
+            default: MTBC_STEM_MC_C8(5); break;
+            }
+#undef MTBC_STEM_MC_C8
+        } else if (k.t[0])
             hipLaunchKernelGGL(conv3x3_stem_fwd_c8_kernel<true>, grid, dim3(128), 0, st, a->in[0].ptr, (long long)a->in[0].batch_stride, a->w, a->bias, o16, a->stats_partial, a->N, a->H, a->W, a->Cout);
         else
             hipLaunchKernelGGL(conv3x3_stem_fwd_c8_kernel<false>, grid, dim3(128), 0, st, a->in[0].ptr, (long long)a->in[0].batch_stride, a->w, a->bias, o16, a->stats_partial, a->N, a->H, a->W, a->Cout);
@@ -3960,6 +4169,20 @@ static int conv_fwd(const mtbc_conv3x3_args* a, hipStream_t st, KernelChoice* qu
     if (a->w_packed && !a->force_direct && mfma_ok(a->in, a->n_in, a->H, a->W))
         return run_igemm(a->N, a->H, a->W, a->Cin, a->Cout, in, out, a->w_packed, a->bias, a->compute, st, false, 0, nullptr, nullptr, query);
     if (!a->w) return MTBC_E_BADARG;
+    if (stem && a->Cin > 1) {
+        if (query) { *query = kchoice(KF_STEM_MC_FWD, a->Cin); return MTBC_OK; }
+        const dim3 grid(cdiv(a->H * (a->W / 4), 128), cdiv(a->Cout, 8), a->N);
+#define MTBC_STEM_MC(CIN_) hipLaunchKernelGGL((conv3x3_stem_mc_fwd_kernel<CIN_>), grid, dim3(128), 0, st, a->in[0].ptr, (long long)a->in[0].batch_stride, a->w, a->bias, a->out, a->N, a->H, a->W, a->Cout)
+        switch (a->Cin) {
+        case 2: MTBC_STEM_MC(2); break;
+        case 3: MTBC_STEM_MC(3); break;
+        case 4: MTBC_STEM_MC(4); break;
+        default: MTBC_STEM_MC(5); break;
+        }
+#undef MTBC_STEM_MC
+        MTBC_CHECK_LAUNCH();
+        return MTBC_OK;
+    }
     if (stem) {
         if (query) { *query = kchoice(KF_STEM_FWD); return MTBC_OK; }
         hipLaunchKernelGGL(conv3x3_stem_fwd_kernel, dim3(cdiv(a->H * (a->W / 4), 128), cdiv(a->Cout, 8), a->N), dim3(128), 0, st,
@@ -4015,7 +4238,7 @@ int mtbc_conv3x3_dgrad(const mtbc_conv3x3_args* a, void* stream) { return conv_d
 int32_t mtbc_conv3x3_stats_slots(const mtbc_conv3x3_args* a) {
     if (check_conv(a) || a->out_layout != MTBC_LAYOUT_C8 || (a->compute != 1 && a->compute != 2)) return 0;
     if (a->operand_layout == MTBC_LAYOUT_PLANAR)          // the stem: one subset per 512-pixel block
-        return (a->Cin == 1 && a->n_in == 1 && a->W % 4 == 0 && a->Cout % 8 == 0) ? cdiv(a->H * (a->W / 4), 128) : 0;
+        return (a->Cin <= MTBC_STEM_MAX_CIN && a->n_in == 1 && a->W % 4 == 0 && a->Cout % 8 == 0) ? cdiv(a->H * (a->W / 4), 128) : 0;
     if (a->operand_layout != MTBC_LAYOUT_C8) return 0;
     if (a->W % 4 || a->W < 8 || a->H < 8 || a->Cout % 8) return 0;
     const IgemmPlan q = plan_igemm(a->N, a->H, a->W, a->Cout, a->compute, true, a->norm_z == nullptr, a->Cin);
@@ -4029,7 +4252,7 @@ size_t mtbc_conv3x3_wgrad_workspace(const mtbc_conv3x3_args* a) {
 }
 
 size_t mtbc_conv3x3_wgrad_sync_bytes(const mtbc_conv3x3_args* a) {
-    if (check_conv(a) || a->operand_layout != MTBC_LAYOUT_C8 || a->Cin == 1) return 0;      // (only the channel-blocked kernels reduce in-kernel)
+    if (check_conv(a) || a->operand_layout != MTBC_LAYOUT_C8 || a->Cin <= MTBC_STEM_MAX_CIN) return 0;      // (only the channel-blocked kernels reduce in-kernel)
     const WgPlan w = plan_wgrad(a);
     SplitKFix f{};
     return (size_t)splitk_fix_plan(w.nsplit, &f) * w.coblocks * w.ciblocks * sizeof(int);
@@ -4044,17 +4267,30 @@ static int conv_wgrad(const mtbc_conv3x3_args* a, hipStream_t st, KernelChoice* 
     if (!a->workspace || a->workspace_bytes < (w.partial_elems + w.dbias_elems) * sizeof(float)) return MTBC_E_WORKSPACE;
     float* partial = reinterpret_cast<float*>(a->workspace);
     const size_t wel = (size_t)a->Cout * a->Cin * 9;
-    if (a->operand_layout == MTBC_LAYOUT_C8 && a->Cin == 1) {
-        // the stem: dz channel-blocked 16-bit, the 1-channel input fp32 planar (it has no channel-blocked form)
+    if (a->operand_layout == MTBC_LAYOUT_C8 && a->Cin <= MTBC_STEM_MAX_CIN) {
+        // the stem: dz channel-blocked 16-bit, the input (the image + up to four intensity channels, one segment) fp32 planar (it has no channel-blocked form)
         if ((a->compute != 1 && a->compute != 2) || a->n_in != 1 || a->Cout % 8 || a->W % 4 || a->dbias || a->in[0].batch_stride % 4 ||
             ((reinterpret_cast<uintptr_t>(a->in[0].ptr) | reinterpret_cast<uintptr_t>(a->dout)) & 15)) return MTBC_E_UNSUPPORTED;
         const int S = w.nsplit / a->N;
         const dim3 grid(a->N * (a->Cout / 8) * S);
         const unsigned short* dz8 = reinterpret_cast<const unsigned short*>(a->dout);
-        KernelChoice k = kchoice(KF_WGRAD_STEM_C8, a->compute == 2);
+        KernelChoice k = a->Cin == 1 ? kchoice(KF_WGRAD_STEM_C8, a->compute == 2) : kchoice(KF_WGRAD_STEM_MC_C8, a->Cin, a->compute == 2);
         k.red = KR_SPLITK;
         if (query) { *query = k; return MTBC_OK; }
-        if (k.t[0]) hipLaunchKernelGGL(conv3x3_wgrad_stem_c8_kernel<true>, grid, dim3(256), 0, st, a->in[0].ptr, (long long)a->in[0].batch_stride, dz8, partial, a->N, a->H, a->W, a->Cout, S);
+        if (k.fam == KF_WGRAD_STEM_MC_C8) {
+#define MTBC_WG_STEM_MC(CIN_)                                                                                                                  \
+            do {                                                                                                                               \
+                if (k.t[1]) hipLaunchKernelGGL((conv3x3_wgrad_stem_mc_c8_kernel<CIN_, true>), grid, dim3(384), 0, st, a->in[0].ptr, (long long)a->in[0].batch_stride, dz8, partial, a->N, a->H, a->W, a->Cout, S); \
+                else hipLaunchKernelGGL((conv3x3_wgrad_stem_mc_c8_kernel<CIN_, false>), grid, dim3(384), 0, st, a->in[0].ptr, (long long)a->in[0].batch_stride, dz8, partial, a->N, a->H, a->W, a->Cout, S); \
+            } while (0)
+            switch (a->Cin) {
+            case 2: MTBC_WG_STEM_MC(2); break;
+            case 3: MTBC_WG_STEM_MC(3); break;
+            case 4: MTBC_WG_STEM_MC(4); break;
+            default: MTBC_WG_STEM_MC(5); break;
+            }
+#undef MTBC_WG_STEM_MC
+        } else if (k.t[0]) hipLaunchKernelGGL(conv3x3_wgrad_stem_c8_kernel<true>, grid, dim3(256), 0, st, a->in[0].ptr, (long long)a->in[0].batch_stride, dz8, partial, a->N, a->H, a->W, a->Cout, S);
         else hipLaunchKernelGGL(conv3x3_wgrad_stem_c8_kernel<false>, grid, dim3(256), 0, st, a->in[0].ptr, (long long)a->in[0].batch_stride, dz8, partial, a->N, a->H, a->W, a->Cout, S);
         MTBC_CHECK_LAUNCH();
         return mtbc_i_splitk_reduce(partial, a->dw, w.nsplit, wel, a->accumulate_dw, st);

@@ -25,6 +25,7 @@ _NO_COOP = _sw.flag("MTBC_NO_COOP")
 _NO_GATHER = _sw.flag("MTBC_NO_GATHER")
 _NO_Z16 = _sw.flag("MTBC_NO_Z16")
 _Z_BF16 = _sw.flag("MTBC_Z_BF16")
+_NO_STEM_MC = _sw.flag("MTBC_NO_STEM_MC")    # the first conv with intensity channels (Cin 2 .. 5) as before the multi-channel stem kernels
 _DA16 = _sw.flag("MTBC_DA16")            # 16-bit gathered activation gradients: opt-in again since round 4 (switches.py)
 # measured crossovers of the cooperative (split-plane) InstanceNorm kernels on fp32 conv outputs (the MTBC_NO_Z16 arm): they win on
 # planes >= 128x128 forward / 256x256 backward; on small planes their barriers and 512-thread workgroups lose to one-plane kernels + pack
@@ -106,6 +107,7 @@ class _Cell:
     c8: bool = False                          # the MFMAs read channel-blocked 16-bit operands
     c8_bwd: bool = False
     stem16: bool = False
+    old_mc: bool = False                      # MTBC_NO_STEM_MC: a first conv with intensity channels on the launches it took before the multi-channel stem kernels
     z16: bool = False                         # conv output stored in 16 bits, channel-blocked
     zf16: bool = False                        # ... as fp16 (also in the bf16 mode)
     z: Optional[torch.Tensor] = None
@@ -173,6 +175,7 @@ class StepPlan:
         self.N = N
         self.pv, self.gv, self.slots = param_view, grad_view, slots
         self.force_direct = 1 if force_direct else 0
+        self.cells: List[_Cell] = []      # every conv cell of the tape, in forward order (tests and tools read the plan's decisions here)
         self.keep: list = []
         self.fwd_ops: List[L.Op] = []
         self.pack_ops: List[L.Op] = []
@@ -429,9 +432,13 @@ class StepPlan:
         # 16-bit modes: the conv output z is stored once, in 16 bits, channel-blocked (what torch.autocast keeps between a
         # convolution and its normalisation): written by the igemm's epilogue (fp32 accumulate + bias, one RNE), read by the
         # InstanceNorm forward and backward as 16-byte pieces -- 2 + 2 + 2 instead of 4 + 4 + 4 bytes per element.  Needs the
-        # channel-group InstanceNorm kernels in both directions (norm_coop.hip).  The stem (Cin = 1: fp32 operands, no MFMA) takes
+        # channel-group InstanceNorm kernels in both directions (norm_coop.hip).  The stem (the image + up to four intensity channels, Cin <= STEM_MAX_CIN: fp32 operands, no MFMA) takes
         # part: its forward writes z in the same layout and leaves the same statistics, its weight gradient reads the channel-blocked dz
-        stem16 = bool(self.compute) and cin == 1 and len(inputs) == 1 and cout % 8 == 0 and not self.force_direct and W % 4 == 0 \
+        # MTBC_NO_STEM_MC: a first conv with intensity channels (Cin 2 .. 5) takes the launches it took before the multi-channel stem kernels --
+        # conv3x3_direct_kernel, fp32 z, one-plane InstanceNorm, the small-Cin (Cin = 5: the direct) weight gradient from fp32 dz
+        old_mc = _NO_STEM_MC and 1 < cin <= L.STEM_MAX_CIN and len(inputs) == 1
+        cell.old_mc = old_mc
+        stem16 = bool(self.compute) and 1 <= cin <= L.STEM_MAX_CIN and not old_mc and len(inputs) == 1 and cout % 8 == 0 and not self.force_direct and W % 4 == 0 \
             and H >= 8 and W >= 8 and inputs[0].planar_valid and not inputs[0].needs_grad
         z16 = False
         if (c8_bwd or stem16) and not _NO_Z16 and not _NO_COOP:      # (the one-plane InstanceNorm kernels read fp32 planes)
@@ -447,6 +454,7 @@ class StepPlan:
         y.dy8_ok = z16 and _DA16 and not stem16
         y.z16 = z16
         cell.c8, cell.c8_bwd, cell.stem16, cell.z16, cell.zf16, cell.z = c8, c8_bwd, stem16, z16, zf16, z
+        self.cells.append(cell)
         if not c8 and not all(a_.planar_valid for a_ in inputs):
             raise NotImplementedError(f"{out_name}: an input exists only in the channel-blocked 16-bit layout")
         for a_ in inputs:
@@ -464,6 +472,8 @@ class StepPlan:
         op.u.conv3.w_packed = _ptr(wp_f)
         op.u.conv3.bias = _ptr(self.pv(bname)) if bname else None
         op.u.conv3.out = z.data_ptr()
+        if old_mc:
+            op.u.conv3.force_direct = 1
         stats_slots = 0
         if stem16:
             op.u.conv3.compute = self.compute
@@ -668,12 +678,14 @@ class StepPlan:
         if c8_bwd:
             self._segs_c8(a.in_, inputs)
             a.dout, a.operand_layout = dz8.data_ptr(), L.LAYOUT_C8
-        elif cell.stem16:          # fp32 planar 1-channel input, channel-blocked dz
+        elif cell.stem16:          # fp32 planar input of 1 .. STEM_MAX_CIN channels, channel-blocked dz
             self._segs(a.in_, inputs)
             a.dout, a.operand_layout, a.compute = dz8.data_ptr(), L.LAYOUT_C8, self.compute
         else:
             self._segs(a.in_, inputs)
             a.dout = dy.data_ptr()
+            if cell.old_mc and cell.cin > 4:      # (the small-Cin kernel stopped at 4 channels)
+                a.force_direct = 1
         a.accumulate_dw = self._mark_param(cell.wname)
         a.dw = self.gv(cell.wname).data_ptr()
         # (batching the ~40 split-K reductions of a step into a few launches was built and measured: 15.20 vs 14.54 ms -- the

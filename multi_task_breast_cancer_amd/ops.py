@@ -59,7 +59,7 @@ def conv3x3_case_args(op: int, N: int, segs: Sequence[int], Cout: int, H: int, W
     """The argument struct the wrappers below fill for one call (fwd: conv3x3_fwd / conv3x3_fwd_c8 / conv3x3_stem_fwd_c8, dgrad:
     conv3x3_dgrad / conv3x3_dgrad_c8 with the first segment overwritten and the others accumulated, wgrad: conv3x3_wgrad /
     conv3x3_wgrad_c8), its tensor pointers distinct 16-byte aligned dummies that nothing may dereference: for conv3x3_kernel_name.
-    c8: operands in MTBC_LAYOUT_C8 (a 1-channel input stays fp32 planar: the stem); bias: fwd bias / wgrad dbias."""
+    c8: operands in MTBC_LAYOUT_C8 (one segment of at most L.STEM_MAX_CIN channels stays fp32 planar: the stem); bias: fwd bias / wgrad dbias."""
     lib = L.load()
     ptr = iter(range(1 << 20, 1 << 30, 1 << 20))
     a = L.Conv3x3Args()
@@ -69,7 +69,7 @@ def conv3x3_case_args(op: int, N: int, segs: Sequence[int], Cout: int, H: int, W
         if op == L.OP_CONV3_DGRAD:
             a.in_[i].accumulate = 3 if dx_c8 else (1 if i else 0)
     a.w, a.compute = next(ptr), compute
-    stem = sum(segs) == 1
+    stem = len(segs) == 1 and segs[0] <= L.STEM_MAX_CIN
     if c8 and not (stem and op == L.OP_CONV3_FWD):
         a.operand_layout = L.LAYOUT_C8
     if op == L.OP_CONV3_FWD:
@@ -176,9 +176,11 @@ def conv3x3_fwd(xs: Sequence[torch.Tensor], w: torch.Tensor, bias: Optional[torc
 
 
 def conv3x3_stem_fwd_c8(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], compute: int, out_fp16: bool = False, stats: bool = False):
-    """The 1-channel stem conv of the 16-bit modes: fp32 operands, the output channel-blocked 16-bit (out_layout = C8 with
-    operand_layout = planar) + optional InstanceNorm statistics partials."""
+    """The stem conv of the 16-bit modes (1 .. L.STEM_MAX_CIN input channels: the image + intensity channels): fp32 operands, the output
+    channel-blocked 16-bit (out_layout = C8 with operand_layout = planar) + optional InstanceNorm statistics partials."""
     _chk(x, w, bias)
+    if not 1 <= w.shape[1] <= L.STEM_MAX_CIN or x.shape[1] != w.shape[1]:
+        raise ValueError(f"the stem takes 1 .. {L.STEM_MAX_CIN} input channels")
     N, _, H, W = x.shape
     a = _conv_args([x], w, N, H, W)
     _fill_segs(a.in_, [x])
@@ -357,7 +359,7 @@ def conv3x3_wgrad_c8(xs: Sequence["C8"], dz: "C8", w_shape, want_bias: bool = Fa
     db = torch.empty(w_shape[0], dtype=torch.float32, device=dev) if want_bias else None
     a = L.Conv3x3Args()
     a.N, a.H, a.W, a.Cin, a.Cout, a.n_in = N, H, W, w_shape[1], w_shape[0], len(xs)
-    if w_shape[1] == 1 and isinstance(xs[0], torch.Tensor):      # the stem: fp32 planar 1-channel input, channel-blocked dz
+    if w_shape[1] <= L.STEM_MAX_CIN and isinstance(xs[0], torch.Tensor):      # the stem: ONE fp32 planar input of 1 .. STEM_MAX_CIN channels, channel-blocked dz
         _fill_segs(a.in_, xs)
     else:
         _fill_segs_c8(a.in_, xs)

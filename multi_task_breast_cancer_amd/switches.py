@@ -38,6 +38,10 @@ PLAN_SWITCHES: Dict[str, tuple] = {
                             "over the flat gradients, skip + halve on overflow, double after 2000 clean steps) instead of the static scale baked into the loss ops: three more "
                             "launches per step; without an overflow the same bits as the static 2^16 of fp16 mode",
                        "tests/test_loss_scale_gpu.py::test_dynamic_steps_without_overflow_are_the_static_steps"),
+    "MTBC_NO_STEM_MC": ("0", "a first conv with intensity channels (data.augmentation: Cin 2 .. 5) takes the launches it took before the multi-channel stem kernels: "
+                             "conv3x3_direct_kernel, an fp32 conv output under the one-plane InstanceNorm, the small-Cin (Cin = 5: the direct) weight gradient from fp32 dz -- "
+                             "the A arm of tools/stem_cost.py",
+                        "tests/test_stem_multichannel_gpu.py::test_whole_model_against_the_emulation[...-no_stem_mc]"),
     "MTBC_COOP_RESERVE_CUS": ("64", "CUs kept out of the cooperative InstanceNorm grids under data parallel",
                               "tests/test_coop_safety_gpu.py::test_cooperative_step_beside_a_cu_hogging_kernel"),
 }
