@@ -586,6 +586,45 @@ int mtbc_loss_scale_update_host(const mtbc_loss_scale_args* a);
 /* host only: what _begin writes into state->adam for the `t`, `scale` and `lr` of a HOST copy of the state */
 int mtbc_loss_scale_begin_host(const mtbc_loss_scale_args* a);
 
+/* ------------------------------------------------------------------------------------ SGD (Nesterov) and AdamW
+ * replaces torch.optim.SGD(lr, momentum=0.9, nesterov=True).step() and torch.optim.AdamW(lr).step() of experiment_init.py:188-195 --
+ * one fused launch over the flat parameter buffer, shaped like the Adam launch above (whose struct, kernel and bits stay as they are).
+ *   g' = grad_scale * g
+ *   SGD   : buf = momentum buf + g' ; d = nesterov ? g' + momentum buf : buf ; p -= lr d            (dampening 0, weight_decay 0; buf starts at 0)
+ *   AdamW : p *= (float)(1 - (double)lr (double)weight_decay) ; then Adam's update above, operation for operation
+ * Every element goes through ONE inline function compiled for host and device without floating-point contraction (the fused operations are
+ * spelled fmaf), so mtbc_optim_step_host gives the kernel's bits.  AdamW with weight_decay = 0 gives the Adam launch's bits on every
+ * element: as in the Adam kernel, v is fma(g', (1-b2) g', b2 v) on the elements below n & ~3 and the two products summed on the rest.     */
+#define MTBC_OPT_SGD   0
+#define MTBC_OPT_ADAMW 1
+typedef struct {
+    int32_t kind;                    /* MTBC_OPT_SGD | MTBC_OPT_ADAMW */
+    int64_t n;
+    float* p; const float* g;
+    float* m;                        /* SGD: the momentum buffer; AdamW: exp_avg */
+    float* v;                        /* AdamW: exp_avg_sq; SGD: not read (may be NULL) */
+    float lr, beta1, beta2, eps, momentum, weight_decay, grad_scale;
+    int32_t step;                    /* t >= 1 (AdamW's bias corrections; SGD does not use it) */
+    int32_t zero_grad;               /* 1 = also clear g */
+    int32_t nesterov;                /* SGD */
+    const float* dynamic;            /* optional, DEVICE memory, 4 floats as mtbc_optim_dynamic writes them: read instead of lr / step / grad_scale
+                                        (a step replayed as a hipGraph).  NULL: the launch arguments.  Same arithmetic, same bits. */
+    const uint32_t* skip;            /* optional: a found-inf word.  Non-zero: every thread returns before touching p / m / v (zero_grad still clears g) */
+    const mtbc_loss_scale_state* scale_state;   /* optional: the scalars come from a dynamic loss scale's state instead -- grad_scale = adam[0],
+                                        AdamW: adam[1], adam[2] and the decay factor from state->lr, SGD: lr = state->lr.  Goes before `dynamic`. */
+} mtbc_optim_args;
+/* 16-byte alignment of p, g, m (and v for AdamW) required, else MTBC_E_UNSUPPORTED.  Grid-stride, float4 body and a scalar tail. */
+int mtbc_optim_step(const mtbc_optim_args* a, void* stream);
+/* host only, no GPU call: out4 = {grad_scale, SGD: lr | AdamW: lr / (1-b1^t), AdamW: 1 / sqrt(1-b2^t) | SGD: 1,
+ *                                 AdamW: (float)(1 - (double)lr (double)weight_decay) | SGD: 1}, bias corrections in double as mtbc_adam_dynamic's */
+int mtbc_optim_dynamic(const mtbc_optim_args* a, float out4[4]);
+/* the counterpart of mtbc_loss_scale_adam: the optimizer launch with skip = &state->found_inf and scale_state = state, then the same update
+ * of the state.  `opt->lr`, `step`, `grad_scale`, `dynamic`, `skip` and `scale_state` are not read.  SGD ignores state->adam[1..2]. */
+int mtbc_loss_scale_optim(const mtbc_loss_scale_args* a, const mtbc_optim_args* opt, void* stream);
+/* host only, no GPU call: the same update on HOST pointers (p, g, m, v, and dynamic / skip / scale_state where set), a plain loop over the
+ * inline element function the kernel runs. */
+int mtbc_optim_step_host(const mtbc_optim_args* a);
+
 /* Whole-batch TP/FP/FN of (sigmoid(x) > .5) vs target, the train-loop Dice metric of
  * metrics.py:255-267 (training_multitask.py:66-71).  out3 = {tp, fp, fn} as float64.        */
 int mtbc_dice_counts(const float* logits, const float* target, int64_t n, double* out3, void* stream);

@@ -134,6 +134,17 @@ class AdamArgs(C.Structure):
                 ("grad_scale", C.c_float), ("step", C.c_int32), ("zero_grad", C.c_int32), ("dynamic", C.c_void_p)]
 
 
+OPT_SGD, OPT_ADAMW = 0, 1        # mtbc_optim_args.kind
+
+
+class OptimArgs(C.Structure):
+    """mtbc_optim_args (include/mtbc.h): the fused SGD / AdamW launch."""
+    _fields_ = [("kind", C.c_int32), ("n", C.c_int64), ("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p),
+                ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("momentum", C.c_float),
+                ("weight_decay", C.c_float), ("grad_scale", C.c_float), ("step", C.c_int32), ("zero_grad", C.c_int32), ("nesterov", C.c_int32),
+                ("dynamic", C.c_void_p), ("skip", C.c_void_p), ("scale_state", C.c_void_p)]
+
+
 class LossScaleState(C.Structure):
     _fields_ = [("scale", C.c_float), ("growth_tracker", C.c_int32), ("found_inf", C.c_uint32), ("t", C.c_int32), ("skipped", C.c_int32),
                 ("lr", C.c_float), ("shard_weight", C.c_float), ("adam", C.c_float * 3), ("reserved", C.c_int32 * 6)]
@@ -275,7 +286,8 @@ EXPORTS = [
     "mtbc_conv1x1_wgrad_workspace", "mtbc_conv1x1_fwd", "mtbc_conv1x1_dgrad", "mtbc_conv1x1_wgrad",
     "mtbc_gap_fwd", "mtbc_gap_bwd", "mtbc_linear_fwd", "mtbc_linear_bwd", "mtbc_dice_fwd", "mtbc_dice_bwd",
     "mtbc_focal_fwd_bwd", "mtbc_loss_mix", "mtbc_adam_step", "mtbc_adam_dynamic", "mtbc_loss_scale_begin", "mtbc_loss_scale_check", "mtbc_loss_scale_adam",
-    "mtbc_loss_scale_update_host", "mtbc_loss_scale_begin_host", "mtbc_dice_counts", "mtbc_program_run",
+    "mtbc_loss_scale_update_host", "mtbc_loss_scale_begin_host", "mtbc_optim_step", "mtbc_optim_dynamic", "mtbc_loss_scale_optim", "mtbc_optim_step_host",
+    "mtbc_dice_counts", "mtbc_program_run",
     "mtbc_program_run_ms", "mtbc_event_create", "mtbc_event_destroy",
     "mtbc_seg_metrics_workspace_size", "mtbc_seg_metrics", "mtbc_batch_assemble", "mtbc_train_metrics",
 ]
@@ -381,6 +393,14 @@ def load() -> C.CDLL:
     for name in ("mtbc_loss_scale_update_host", "mtbc_loss_scale_begin_host"):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [C.POINTER(LossScaleArgs)]
+    lib.mtbc_optim_step.restype = C.c_int
+    lib.mtbc_optim_step.argtypes = [C.POINTER(OptimArgs), C.c_void_p]
+    lib.mtbc_optim_dynamic.restype = C.c_int
+    lib.mtbc_optim_dynamic.argtypes = [C.POINTER(OptimArgs), C.POINTER(C.c_float * 4)]
+    lib.mtbc_loss_scale_optim.restype = C.c_int
+    lib.mtbc_loss_scale_optim.argtypes = [C.POINTER(LossScaleArgs), C.POINTER(OptimArgs), C.c_void_p]
+    lib.mtbc_optim_step_host.restype = C.c_int
+    lib.mtbc_optim_step_host.argtypes = [C.POINTER(OptimArgs)]
     lib.mtbc_program_run.restype = C.c_int
     lib.mtbc_program_run.argtypes = [C.POINTER(Op), C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]
     lib.mtbc_program_run_ms.restype = C.c_int

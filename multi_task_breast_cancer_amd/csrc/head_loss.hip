@@ -1,5 +1,5 @@
 // Pooled classification head (GAP + Linear), fused Dice / Focal losses, loss mix + NaN flag,
-// fused Adam and the train-loop Dice counters.  All HBM-/latency-bound; reductions use wavefront
+// fused Adam / SGD / AdamW and the train-loop Dice counters.  All HBM-/latency-bound; reductions use wavefront
 // shuffles (64 lanes) then LDS across waves -- deterministic, no float atomics.
 #include "common.h"
 
@@ -432,6 +432,75 @@ __global__ void found_inf_kernel(const float* __restrict__ g, long long n, unsig
     if (bad) atomicOr(flag, 1u);                                // rare (an overflowing step), so no wave reduction in front of it
 }
 
+// ------------------------------------------------------------------ SGD (Nesterov) and AdamW
+// One element function for the kernel and for mtbc_optim_step_host: no contraction is left to the compiler (host and device would choose
+// differently), every fused operation is an fmaf.  The AdamW branch is adam1 above as the compiler contracts it in adam_kernel: g' - m as
+// fma(gs, g, -m), the denominator and the last line as one fma each, and v in the TWO forms adam_kernel has -- fma(g', (1-b2) g', b2 v) in its
+// float4 body, the product g' ((1-b2) g') plus the product b2 v in its scalar tail (TAIL: the elements from n & ~3 on).  The rule is therefore
+// position-dependent for AdamW's v on at most three elements of a buffer; that is what makes AdamW with weight_decay = 0 FusedAdam bit for bit.
+struct OptimS { float gs, step, inv_bc2_sqrt, decay, omb1, omb2, b2, eps, momentum; int nesterov; };     // step: SGD lr | AdamW lr / (1 - b1^t)
+struct OptimP { long long n; float* p; float* g; float* m; float* v; OptimS s; float wd; int kind, zero;
+                const float* dyn; const unsigned* skip; const mtbc_loss_scale_state* st; };
+template <int KIND, bool TAIL> __host__ __device__ inline void optim1(float& p, float g, float& m, float& v, const OptimS& s) {
+#pragma clang fp contract(off)
+    const float gp = s.gs * g;
+    if (KIND == MTBC_OPT_SGD) {
+        m = fmaf(s.momentum, m, gp);
+        const float d = s.nesterov ? fmaf(s.momentum, m, gp) : m;
+        p = fmaf(-s.step, d, p);
+    } else {
+        p = p * s.decay;
+        m = fmaf(s.omb1, fmaf(s.gs, g, -m), m);
+        if (TAIL) v = gp * (s.omb2 * gp) + s.b2 * v; else v = fmaf(gp, s.omb2 * gp, s.b2 * v);
+        const float denom = fmaf(sqrtf(v), s.inv_bc2_sqrt, s.eps);
+        p = fmaf(-s.step, m / denom, p);
+    }
+}
+__host__ __device__ inline float adamw_decay(float lr, float wd) {
+#pragma clang fp contract(off)
+    return (float)(1.0 - (double)lr * (double)wd);
+}
+// the per-step scalars from memory, where the caller put them there: a dynamic loss scale's state first, else the 4 floats of a replayed step
+__host__ __device__ inline void optim_resolve(OptimP& a) {
+    if (a.st) {
+        a.s.gs = a.st->adam[0];
+        if (a.kind == MTBC_OPT_SGD) { a.s.step = a.st->lr; }
+        else { a.s.step = a.st->adam[1]; a.s.inv_bc2_sqrt = a.st->adam[2]; a.s.decay = adamw_decay(a.st->lr, a.wd); }
+    } else if (a.dyn) {
+        a.s.gs = a.dyn[0]; a.s.step = a.dyn[1]; a.s.inv_bc2_sqrt = a.dyn[2]; a.s.decay = a.dyn[3];
+    }
+}
+template <int KIND> __device__ __forceinline__ void optim_range(const OptimP& a) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long n4 = a.n >> 2;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        float4 p = reinterpret_cast<float4*>(a.p)[i], g = reinterpret_cast<float4*>(a.g)[i], m = reinterpret_cast<float4*>(a.m)[i];
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (KIND == MTBC_OPT_ADAMW) v = reinterpret_cast<float4*>(a.v)[i];
+        optim1<KIND, false>(p.x, g.x, m.x, v.x, a.s); optim1<KIND, false>(p.y, g.y, m.y, v.y, a.s);
+        optim1<KIND, false>(p.z, g.z, m.z, v.z, a.s); optim1<KIND, false>(p.w, g.w, m.w, v.w, a.s);
+        reinterpret_cast<float4*>(a.p)[i] = p; reinterpret_cast<float4*>(a.m)[i] = m;
+        if (KIND == MTBC_OPT_ADAMW) reinterpret_cast<float4*>(a.v)[i] = v;
+        if (a.zero) reinterpret_cast<float4*>(a.g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    for (long long i = (n4 << 2) + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
+        float v = 0.f;
+        if (KIND == MTBC_OPT_ADAMW) v = a.v[i];
+        optim1<KIND, true>(a.p[i], a.g[i], a.m[i], v, a.s);
+        if (KIND == MTBC_OPT_ADAMW) a.v[i] = v;
+        if (a.zero) a.g[i] = 0.f;
+    }
+}
+__global__ void optim_kernel(OptimP a) {
+    if (a.skip && *a.skip) {                     // as adam_kernel: a gradient overflowed -> p, m, v are not touched (uniform load)
+        const long long stride = (long long)gridDim.x * blockDim.x;
+        if (a.zero) for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) a.g[i] = 0.f;
+        return;
+    }
+    optim_resolve(a);                            // uniform loads
+    if (a.kind == MTBC_OPT_SGD) optim_range<MTBC_OPT_SGD>(a); else optim_range<MTBC_OPT_ADAMW>(a);
+}
+
 // ------------------------------------------------------------------ Dice metric counters (integer, exact)
 __global__ void dice_counts_kernel(const float* __restrict__ x, const float* __restrict__ t, long long n,
                                    unsigned long long* cnt) {
@@ -660,6 +729,87 @@ int mtbc_loss_scale_update_host(const mtbc_loss_scale_args* a) {
 int mtbc_loss_scale_begin_host(const mtbc_loss_scale_args* a) {
     if (!loss_scale_args_ok(a)) return MTBC_E_BADARG;
     loss_scale_begin(a->state, a->gscale_out, a->inv_world, a->beta1, a->beta2);
+    return MTBC_OK;
+}
+
+// SGD / AdamW: the four per-step scalars, AdamW's bias corrections in double exactly as adam_scalars
+static void optim_scalars(const mtbc_optim_args* a, float out4[4]) {
+    out4[0] = a->grad_scale;
+    if (a->kind == MTBC_OPT_SGD) { out4[1] = a->lr; out4[2] = 1.f; out4[3] = 1.f; return; }
+    const double bc1 = 1.0 - pow((double)a->beta1, (double)a->step);
+    const double bc2 = 1.0 - pow((double)a->beta2, (double)a->step);
+    out4[1] = (float)((double)a->lr / bc1);
+    out4[2] = (float)(1.0 / sqrt(bc2));
+    out4[3] = adamw_decay(a->lr, a->weight_decay);
+}
+static int optim_kind_ok(const mtbc_optim_args* a) { return a->kind == MTBC_OPT_SGD || a->kind == MTBC_OPT_ADAMW; }
+// validation and the kernel's parameter block; `scaled`: under a dynamic loss scale (lr / step / grad_scale are not read)
+static int optim_params(const mtbc_optim_args* a, bool scaled, OptimP* p) {
+    if (!a || a->n <= 0 || (!scaled && a->step < 1)) return MTBC_E_BADSHAPE;
+    if (!optim_kind_ok(a)) return MTBC_E_UNSUPPORTED;
+    const bool adamw = a->kind == MTBC_OPT_ADAMW;
+    if (!a->p || !a->g || !a->m || (adamw && !a->v)) return MTBC_E_BADARG;
+    if ((reinterpret_cast<uintptr_t>(a->p) | reinterpret_cast<uintptr_t>(a->g) | reinterpret_cast<uintptr_t>(a->m) |
+         (adamw ? reinterpret_cast<uintptr_t>(a->v) : 0)) & 15)
+        return MTBC_E_UNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(a->dynamic) | reinterpret_cast<uintptr_t>(a->skip) | reinterpret_cast<uintptr_t>(a->scale_state)) & 3) return MTBC_E_BADARG;
+    float s4[4] = {0.f, 0.f, 0.f, 0.f};                         // scaled: the kernel takes them from the state
+    if (!scaled) optim_scalars(a, s4);
+    p->n = a->n; p->p = a->p; p->g = const_cast<float*>(a->g); p->m = a->m; p->v = adamw ? a->v : nullptr;
+    p->s.gs = s4[0]; p->s.step = s4[1]; p->s.inv_bc2_sqrt = s4[2]; p->s.decay = s4[3];
+    p->s.omb1 = 1.0f - a->beta1; p->s.omb2 = 1.0f - a->beta2; p->s.b2 = a->beta2; p->s.eps = a->eps;
+    p->s.momentum = a->momentum; p->s.nesterov = a->nesterov;
+    p->wd = a->weight_decay; p->kind = a->kind; p->zero = a->zero_grad;
+    p->dyn = a->dynamic; p->skip = a->skip; p->st = a->scale_state;
+    return MTBC_OK;
+}
+static int optim_launch(const OptimP& p, hipStream_t stream) {
+    long long blocks = cdiv64(p.n / 4 + 1, 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(optim_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p);
+    MTBC_CHECK_LAUNCH();
+    return MTBC_OK;
+}
+int mtbc_optim_dynamic(const mtbc_optim_args* a, float out4[4]) {
+    if (!a || !out4 || a->step < 1 || !optim_kind_ok(a)) return MTBC_E_BADARG;
+    optim_scalars(a, out4);
+    return MTBC_OK;
+}
+int mtbc_optim_step(const mtbc_optim_args* a, void* stream) {
+    OptimP p;
+    const int rc = optim_params(a, a && a->scale_state, &p);
+    return rc != MTBC_OK ? rc : optim_launch(p, (hipStream_t)stream);
+}
+int mtbc_loss_scale_optim(const mtbc_loss_scale_args* a, const mtbc_optim_args* opt, void* stream) {
+    if (!loss_scale_args_ok(a)) return MTBC_E_BADARG;
+    if (!opt) return MTBC_E_BADARG;
+    mtbc_optim_args o = *opt;
+    o.dynamic = nullptr; o.skip = &a->state->found_inf; o.scale_state = a->state;
+    OptimP p;
+    int rc = optim_params(&o, true, &p);
+    if (rc == MTBC_OK) rc = optim_launch(p, (hipStream_t)stream);
+    if (rc != MTBC_OK) return rc;
+    hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a->state, a->growth_factor, a->backoff_factor, a->growth_interval);
+    MTBC_CHECK_LAUNCH();
+    return MTBC_OK;
+}
+int mtbc_optim_step_host(const mtbc_optim_args* a) {
+    OptimP p;
+    const int rc = optim_params(a, a && a->scale_state, &p);
+    if (rc != MTBC_OK) return rc;
+    if (p.skip && *p.skip) {
+        if (p.zero) for (long long i = 0; i < p.n; ++i) p.g[i] = 0.f;
+        return MTBC_OK;
+    }
+    optim_resolve(p);
+    const long long body = p.n & ~3LL;                          // the kernel's float4 body; the rest is its scalar tail
+    for (long long i = 0; i < p.n; ++i) {
+        float v = 0.f;
+        if (p.kind == MTBC_OPT_SGD) optim1<MTBC_OPT_SGD, false>(p.p[i], p.g[i], p.m[i], v, p.s);
+        else if (i < body) optim1<MTBC_OPT_ADAMW, false>(p.p[i], p.g[i], p.m[i], p.v[i], p.s);
+        else optim1<MTBC_OPT_ADAMW, true>(p.p[i], p.g[i], p.m[i], p.v[i], p.s);
+        if (p.zero) p.g[i] = 0.f;
+    }
     return MTBC_OK;
 }
 

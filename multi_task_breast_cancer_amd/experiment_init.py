@@ -12,7 +12,7 @@ from torch.optim.lr_scheduler import CosineAnnealingLR, ReduceLROnPlateau
 
 from .criterions import DiceFocalLoss, DiceLoss, FocalLoss
 from .nets import MTnnUNet, MTUNetPlusPlus
-from .optim import FusedAdam
+from .optim import FusedAdam, FusedAdamW, FusedSGD
 
 
 def count_parameters(model: torch.nn.Module) -> int:
@@ -40,16 +40,23 @@ def init_multitask_model(architecture: str, sequences: int = 1, regions: int = 1
     return model
 
 
-def init_optimizer(model: torch.nn.Module, optimizer: str, learning_rate: float = 0.001):
-    """experiment_init.py:177-196.  'Adam' (config.yaml) is the fused HIP optimizer; 'SGD' / 'AdamW' / the reference's
-    SGD fallback for unknown names are torch's own optimizers over the same parameters (drop-in loop only)."""
+def init_optimizer(model: torch.nn.Module, optimizer: str, learning_rate: float = 0.001, fused: bool = False):
+    """experiment_init.py:177-196.  'Adam' (config.yaml) is the fused HIP optimizer.  'SGD' / 'AdamW' / the reference's SGD fallback for unknown
+    names: by default torch's own optimizers over the same parameters (drop-in loop only); `fused=True` the HIP optimizers FusedSGD / FusedAdamW
+    with the same hyper-parameters, which trainer.FusedTrainStep drives like FusedAdam."""
     if optimizer == "Adam":
         return FusedAdam(model, lr=learning_rate, eps=1e-4)          # experiment_init.py:187: eps=1e-4
     if optimizer == "SGD":
+        if fused:
+            return FusedSGD(model, lr=learning_rate, momentum=0.9, nesterov=True)
         return torch.optim.SGD(model.parameters(), lr=learning_rate, momentum=0.9, nesterov=True)
     if optimizer == "AdamW":
+        if fused:
+            return FusedAdamW(model, lr=learning_rate)
         return torch.optim.AdamW(model.parameters(), lr=learning_rate)
     logging.info(f"The optimizer '{optimizer}' is not recognized. SGD will be used instead.")
+    if fused:
+        return FusedSGD(model, lr=0.001, momentum=0.9, nesterov=True)
     return torch.optim.SGD(model.parameters(), lr=0.001, momentum=0.9, nesterov=True)
 
 
@@ -96,8 +103,8 @@ def init_lr_scheduler(optimizer, scheduler: str = "cosine", t_max: int = 20, fac
     sys.exit()
 
 
-def load_multitask_experiment_artefacts(config_data, config_model, config_opt, config_loss, n_augments, run_path):
-    """experiment_init.py:301-318 -> (model, optimizer, segmentation_criterion, classification_criterion, scheduler)"""
+def load_multitask_experiment_artefacts(config_data, config_model, config_opt, config_loss, n_augments, run_path, fused: bool = False):
+    """experiment_init.py:301-318 -> (model, optimizer, segmentation_criterion, classification_criterion, scheduler).  `fused`: init_optimizer's."""
     model = init_multitask_model(architecture=config_model["architecture"],
                                  sequences=config_model["sequences"] + n_augments,
                                  width=config_model["width"],
@@ -108,7 +115,7 @@ def load_multitask_experiment_artefacts(config_data, config_model, config_opt, c
     #   model: {compute_dtype: bf16}   -> bf16 MFMA operands in the 3x3 convs, everything else fp32
     if config_model.get("compute_dtype") is not None and hasattr(model, "set_compute"):
         model.set_compute(str(config_model["compute_dtype"]))
-    optimizer = init_optimizer(model=model, optimizer=config_opt["opt"], learning_rate=config_opt["lr"])
+    optimizer = init_optimizer(model=model, optimizer=config_opt["opt"], learning_rate=config_opt["lr"], fused=fused)
     segmentation_criterion = init_criterion_segmentation(loss_function=config_loss["function"])
     classification_criterion = init_criterion_classification(
         n_classes=len(config_data["classes"]), classes_weighted=config_data["classes_weighted"],

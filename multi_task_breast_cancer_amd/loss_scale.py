@@ -6,7 +6,7 @@ device memory (`mtbc_loss_scale_state`), and three small launches per step work 
 
     begin : *gscale = shard_weight * scale (the word the loss-gradient kernels multiply by); Adam's three scalars for step t + 1, in double
     check : one pass over the flat gradient buffer, found_inf = 1 on any inf / NaN (after the all-reduce under data parallel: every rank sees it)
-    adam  : the fused Adam launch, every thread returning at once when found_inf is set; then the update rule on the state
+    adam  : the fused optimizer launch (Adam, SGD or AdamW), every thread returning at once when found_inf is set; then the update rule on the state
 
 State dicts use torch.amp.GradScaler's keys, so the two interchange.
 """
@@ -20,6 +20,11 @@ import torch
 from . import _lib as L
 
 _LR, _SHARD = 5, 6        # float word index of mtbc_loss_scale_state.lr / .shard_weight
+
+
+def betas_of(optimizer):
+    """The betas `begin` evaluates the bias corrections with: the optimizer's, where it has any (FusedSGD: torch.optim.Adam's defaults, not read)."""
+    return tuple(optimizer.param_groups[0].get("betas", (0.9, 0.999)))
 
 
 class DynamicLossScale:
@@ -107,12 +112,14 @@ class DynamicLossScale:
     def check(self, flat_g: torch.Tensor) -> None:
         L.check(L.load().mtbc_loss_scale_check(C.byref(self.args(g=flat_g)), self._stream()), "loss scale check")
 
-    def adam(self, optimizer, world: int) -> None:
-        """The optimizer's fused launch under the found-inf word, then the update of the state."""
+    def apply(self, optimizer, world: int) -> None:
+        """The optimizer's fused launch under the found-inf word, then the update of the state.  The optimizer names its entry point and brings its
+        arguments (`_scaled_launch`): mtbc_loss_scale_adam for FusedAdam, mtbc_loss_scale_optim for FusedSGD / FusedAdamW."""
         optimizer._ensure_state()
-        ad = optimizer._args()
-        ad.step = 1                       # not read: the bias corrections come from the device's t
-        L.check(L.load().mtbc_loss_scale_adam(C.byref(self.args(world, optimizer.param_groups[0]["betas"])), C.byref(ad), self._stream()), "loss scale adam")
+        entry, ad = optimizer._scaled_launch()
+        L.check(getattr(L.load(), entry)(C.byref(self.args(world, betas_of(optimizer))), C.byref(ad), self._stream()), "loss scale " + entry[len("mtbc_loss_scale_"):])
+
+    adam = apply                          # the name from when FusedAdam was the only optimizer of the fused step
 
     # ---- torch.amp.GradScaler's state dict ---------------------------------------------------------------------------------------
     def state_dict(self) -> dict:

@@ -862,6 +862,27 @@ def loss_scale_adam(state, p, g, m, v, beta1=0.9, beta2=0.999, eps=1e-4, zero_gr
     L.check(L.load().mtbc_loss_scale_adam(C.byref(a), C.byref(ad), _s()), "loss scale adam")
 
 
+# ------------------------------------------------------------------ fused SGD (Nesterov) / AdamW (op level)
+def optim_args(kind, n, p, g, m, v=None, lr=1e-3, step=1, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.9, weight_decay=0.0, grad_scale=1.0,
+               zero_grad=False, nesterov=True, dynamic=None, skip=None, scale_state=None):
+    """mtbc_optim_args from ADDRESSES (device pointers for optim_step, host pointers for mtbc_optim_step_host)."""
+    a = L.OptimArgs()
+    a.kind, a.n, a.p, a.g, a.m, a.v = kind, n, p, g, m, v
+    a.lr, a.beta1, a.beta2, a.eps, a.momentum, a.weight_decay, a.grad_scale = lr, beta1, beta2, eps, momentum, weight_decay, grad_scale
+    a.step, a.zero_grad, a.nesterov = step, int(zero_grad), int(nesterov)
+    a.dynamic, a.skip, a.scale_state = dynamic, skip, scale_state
+    return a
+
+
+def optim_step(kind, p, g, m, v=None, dynamic=None, skip=None, **hyper):
+    """One fused SGD (kind = L.OPT_SGD; `m` is the momentum buffer) or AdamW (L.OPT_ADAMW) launch on device tensors; `dynamic`: 4 device floats as
+    mtbc_optim_dynamic writes them, `skip`: a device int32 word."""
+    _chk(p, g, m, v, dynamic)
+    a = optim_args(kind, p.numel(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr() if v is not None else None,
+                   dynamic=dynamic.data_ptr() if dynamic is not None else None, skip=skip.data_ptr() if skip is not None else None, **hyper)
+    L.check(L.load().mtbc_optim_step(C.byref(a), _s()), "optim")
+
+
 # ------------------------------------------------------------------ fused ConvT + 1x1 head (MTnnUNet deep supervision)
 def convT_head_fwd_bwd(x, wT, bT, w1, b1, k, dout):
     """Forward and backward of Conv2d_1x1(ConvTranspose2d_k(x)) through the combined-weight path

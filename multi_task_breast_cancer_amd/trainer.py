@@ -20,6 +20,8 @@ import torch
 
 from . import _lib as L
 from . import switches as _sw
+from .loss_scale import betas_of
+from .optim import FUSED_OPTIMIZERS
 
 
 # ------------------------------------------------------------------------------------------------
@@ -216,6 +218,10 @@ class FusedTrainStep:
                 raise ValueError(f"unknown loss_scale {loss_scale!r} (None | 'dynamic' | a DynamicLossScale)")
             from .loss_scale import DynamicLossScale
             loss_scale = DynamicLossScale()
+        if not isinstance(optimizer, FUSED_OPTIMIZERS):
+            # torch's own optimizers do not work on the flat buffers this step fills (no gather of p.grad, no device-side scalars): the drop-in loop is theirs
+            raise TypeError(f"FusedTrainStep drives FusedAdam, FusedSGD or FusedAdamW (multi_task_breast_cancer_amd.optim), not {type(optimizer).__name__}: "
+                            "build it with experiment_init.init_optimizer(..., fused=True)")
         self.scaler = loss_scale
         if self.scaler is not None:
             self.scaler.attach(optimizer)
@@ -365,7 +371,7 @@ class FusedTrainStep:
             self.opt.step(grads_in_flat=True)
         else:
             self.scaler.check(self.model.flat_g)
-            self.scaler.adam(self.opt, self.world)
+            self.scaler.apply(self.opt, self.world)
 
     def _begin_dynamic(self, st, fills: bool = True) -> None:
         sc = self.scaler
@@ -373,7 +379,7 @@ class FusedTrainStep:
             sc.ensure(st.grad_weight.device)
             sc.set_lr(self.opt.param_groups[0]["lr"])
         else:
-            sc.begin(st.grad_weight, self.world, self.opt.param_groups[0]["betas"])
+            sc.begin(st.grad_weight, self.world, betas_of(self.opt))
 
     def _reduce_all(self) -> None:
         allreduce_buckets(self.model.flat_g, self._st.buckets if self._st is not None and self._st.buckets else
