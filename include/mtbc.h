@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MTBC_VERSION 202            /* 0.2.2 (round 4: mtbc_adam_args.dynamic appended + mtbc_adam_dynamic); 0.2.1: mtbc_conv3x3_args.wgrad_sync appended; 0.2.0: the argument structs grew in round 2 (fields appended); a binding compiled against
+#define MTBC_VERSION 203            /* 0.2.3: Adam's own struct and its three entry points removed -- Adam is mtbc_optim_args with kind = MTBC_OPT_ADAMW and weight_decay = 0 -- and MTBC_OP_ADAM became MTBC_OP_OPTIM; 0.2.2 (round 4): Adam's `dynamic` scalars appended; 0.2.1: mtbc_conv3x3_args.wgrad_sync appended; 0.2.0: the argument structs grew in round 2 (fields appended); a binding compiled against
                                        another version must refuse the library (mtbc_version()) -- layouts are not negotiated */
 #define MTBC_MAX_SEGS 6
 #define MTBC_STEM_MAX_CIN 5         /* the stem kernels of mtbc_conv3x3_*: ONE fp32 planar input segment of 1 .. 5 channels -- the image plus the four
@@ -524,41 +524,20 @@ int mtbc_focal_fwd_bwd(const mtbc_focal_args* a, void* stream);
  *   out[0] = alpha*seg + (1-alpha)*cls, out[1] = seg, out[2] = cls, out[3] = nan flag (0/1)  */
 int mtbc_loss_mix(const float* seg, const float* cls, float alpha, float* out4, void* stream);
 
-/* ------------------------------------------------------------------------------------ Adam
- * replaces torch.optim.Adam(lr, betas=(.9,.999), eps=1e-4).step(): experiment_init.py:187,
- * training_multitask.py:103 -- one fused launch over the flat parameter buffer.
- *   g' = grad_scale * g ; m = m + (1-b1)(g'-m) ; v = b2 v + (1-b2) g'^2
- *   p -= (lr / (1-b1^t)) * m / (sqrt(v)/sqrt(1-b2^t) + eps)                                 */
-typedef struct {
-    int64_t n;
-    float* p; const float* g; float* m; float* v;
-    float lr, beta1, beta2, eps, grad_scale;
-    int32_t step;                    /* t >= 1 */
-    int32_t zero_grad;               /* 1 = also clear g (optimizer.zero_grad) */
-    const float* dynamic;            /* optional, DEVICE memory, 3 floats {grad_scale, lr / (1-b1^t), 1 / sqrt(1-b2^t)} as mtbc_adam_dynamic writes them: the kernel
-                                        reads the three per-step scalars from here instead of taking them from lr / step / grad_scale as launch arguments --
-                                        a step captured into a hipGraph is then replayed with the learning rate and step count of the DAY (the caller
-                                        refreshes the 12 bytes in stream order before every replay).  NULL: the launch arguments.  Same arithmetic, same bits. */
-} mtbc_adam_args;
-int mtbc_adam_step(const mtbc_adam_args* a, void* stream);
-/* host only, no GPU call: the three per-step scalars of `a` (lr, betas, step, grad_scale) exactly as mtbc_adam_step computes them -- bias corrections in double,
- * as torch.optim.Adam's scalar path -- for the caller to place in `dynamic`. */
-int mtbc_adam_dynamic(const mtbc_adam_args* a, float out3[3]);
-
 /* ------------------------------------------------------------------------------------ dynamic loss scale
  * torch.amp.GradScaler's rule, stream-ordered on the device (no host read in the step).  One step is
- *   mtbc_loss_scale_begin -> forward, losses, backward [, all-reduce] -> mtbc_loss_scale_check -> mtbc_loss_scale_adam
+ *   mtbc_loss_scale_begin -> forward, losses, backward [, all-reduce] -> mtbc_loss_scale_check -> mtbc_loss_scale_optim
  * The state is 64 bytes of DEVICE memory owned by the caller (zero-filled, then `scale` set); every field is written by ordinary
  * vector stores / atomics, kernel boundaries order them.                                                                        */
 typedef struct {
     float    scale;                  /* the loss scale: a power of two as long as the factors are */
     int32_t  growth_tracker;         /* clean steps since the scale last changed */
-    uint32_t found_inf;              /* set by _check when a gradient is inf / NaN, cleared by _adam's update */
+    uint32_t found_inf;              /* set by _check when a gradient is inf / NaN, cleared by _optim's update */
     int32_t  t;                      /* Adam updates actually APPLIED (a skipped step does not count) */
     int32_t  skipped;                /* steps skipped so far */
     float    lr;                     /* the caller writes the learning rate of the step here, in stream order, before _begin */
     float    shard_weight;           /* the caller's factor on dL (1, or this rank's share of an unequal global batch times world) */
-    float    adam[3];                /* _begin: {inv_world / scale, lr / (1-b1^(t+1)), 1 / sqrt(1-b2^(t+1))} = mtbc_adam_args.dynamic of the step */
+    float    adam[3];                /* _begin: {inv_world / scale, lr / (1-b1^(t+1)), 1 / sqrt(1-b2^(t+1))} = the first three words of mtbc_optim_args.dynamic for that step */
     int32_t  reserved[6];
 } mtbc_loss_scale_state;
 typedef struct {
@@ -572,13 +551,9 @@ typedef struct {
 } mtbc_loss_scale_args;
 /* one thread: the loss kernels' device factor and Adam's three scalars for the step that follows (state->t + 1) */
 int mtbc_loss_scale_begin(const mtbc_loss_scale_args* a, void* stream);
-/* one streaming pass over g (float4 loads, grid-stride, grid sized like mtbc_adam_step's): found_inf = 1 when any element has an all-ones exponent */
+/* one streaming pass over g (float4 loads, grid-stride, grid sized like mtbc_optim_step's): found_inf = 1 when any element has an all-ones exponent */
 int mtbc_loss_scale_check(const mtbc_loss_scale_args* a, void* stream);
-/* mtbc_adam_step(adam) with dynamic = state->adam, and every thread returns before touching p / m / v when found_inf is set
- * (zero_grad still clears g); then one thread applies the update rule below to the state and clears found_inf.  `adam->lr`,
- * `step`, `grad_scale` and `dynamic` are not read.  Two launches, no grid-wide barrier.                                        */
-int mtbc_loss_scale_adam(const mtbc_loss_scale_args* a, const mtbc_adam_args* adam, void* stream);
-/* host only, no GPU call: the update rule of _adam on a HOST copy of the state (the device kernel runs the same inline function):
+/* host only, no GPU call: the update rule of mtbc_loss_scale_optim (below) on a HOST copy of the state (the device kernel runs the same inline function):
  *   found_inf: scale *= backoff_factor, growth_tracker = 0, skipped += 1
  *   else     : t += 1, growth_tracker += 1, and at growth_interval: scale *= growth_factor (kept when that is not finite), growth_tracker = 0
  *   found_inf = 0                                                                                                               */
@@ -586,15 +561,18 @@ int mtbc_loss_scale_update_host(const mtbc_loss_scale_args* a);
 /* host only: what _begin writes into state->adam for the `t`, `scale` and `lr` of a HOST copy of the state */
 int mtbc_loss_scale_begin_host(const mtbc_loss_scale_args* a);
 
-/* ------------------------------------------------------------------------------------ SGD (Nesterov) and AdamW
- * replaces torch.optim.SGD(lr, momentum=0.9, nesterov=True).step() and torch.optim.AdamW(lr).step() of experiment_init.py:188-195 --
- * one fused launch over the flat parameter buffer, shaped like the Adam launch above (whose struct, kernel and bits stay as they are).
+/* ------------------------------------------------------------------------------------ Adam, SGD (Nesterov) and AdamW
+ * replaces torch.optim.Adam(lr, betas=(.9,.999), eps=1e-4).step(), torch.optim.SGD(lr, momentum=0.9, nesterov=True).step() and
+ * torch.optim.AdamW(lr).step() of experiment_init.py:186-195, training_multitask.py:103 -- one fused launch over the flat parameter buffer.
  *   g' = grad_scale * g
  *   SGD   : buf = momentum buf + g' ; d = nesterov ? g' + momentum buf : buf ; p -= lr d            (dampening 0, weight_decay 0; buf starts at 0)
- *   AdamW : p *= (float)(1 - (double)lr (double)weight_decay) ; then Adam's update above, operation for operation
+ *   AdamW : p *= (float)(1 - (double)lr (double)weight_decay) ;
+ *           m = m + (1-b1)(g'-m) ; v = b2 v + (1-b2) g'^2 ; p -= (lr / (1-b1^t)) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
+ *   Adam  : kind = MTBC_OPT_ADAMW with weight_decay = 0 -- the decay factor is then exactly 1.0f and p * 1.0f is p.  There is no third kind and
+ *           no Adam struct or entry point of its own (there was until version 202; the words that kernel wrote are what this one writes).
  * Every element goes through ONE inline function compiled for host and device without floating-point contraction (the fused operations are
- * spelled fmaf), so mtbc_optim_step_host gives the kernel's bits.  AdamW with weight_decay = 0 gives the Adam launch's bits on every
- * element: as in the Adam kernel, v is fma(g', (1-b2) g', b2 v) on the elements below n & ~3 and the two products summed on the rest.     */
+ * spelled fmaf), so mtbc_optim_step_host gives the kernel's bits.  v is fma(g', (1-b2) g', b2 v) on the elements below n & ~3 and the two
+ * products summed on the rest (at most three elements; none when n is a multiple of four).                                                  */
 #define MTBC_OPT_SGD   0
 #define MTBC_OPT_ADAMW 1
 typedef struct {
@@ -616,10 +594,12 @@ typedef struct {
 /* 16-byte alignment of p, g, m (and v for AdamW) required, else MTBC_E_UNSUPPORTED.  Grid-stride, float4 body and a scalar tail. */
 int mtbc_optim_step(const mtbc_optim_args* a, void* stream);
 /* host only, no GPU call: out4 = {grad_scale, SGD: lr | AdamW: lr / (1-b1^t), AdamW: 1 / sqrt(1-b2^t) | SGD: 1,
- *                                 AdamW: (float)(1 - (double)lr (double)weight_decay) | SGD: 1}, bias corrections in double as mtbc_adam_dynamic's */
+ *                                 AdamW: (float)(1 - (double)lr (double)weight_decay) | SGD: 1}, bias corrections in double as torch.optim.Adam's scalar path */
 int mtbc_optim_dynamic(const mtbc_optim_args* a, float out4[4]);
-/* the counterpart of mtbc_loss_scale_adam: the optimizer launch with skip = &state->found_inf and scale_state = state, then the same update
- * of the state.  `opt->lr`, `step`, `grad_scale`, `dynamic`, `skip` and `scale_state` are not read.  SGD ignores state->adam[1..2]. */
+/* the last launch of a step under the dynamic loss scale: mtbc_optim_step(opt) with skip = &state->found_inf and scale_state = state -- every
+ * thread returns before touching p / m / v when found_inf is set (zero_grad still clears g) -- then one thread applies the update rule (see
+ * mtbc_loss_scale_update_host) to the state and clears found_inf.  `opt->lr`, `step`, `grad_scale`, `dynamic`, `skip` and `scale_state` are not
+ * read.  SGD ignores state->adam[1..2].  Two launches, no grid-wide barrier.                                                              */
 int mtbc_loss_scale_optim(const mtbc_loss_scale_args* a, const mtbc_optim_args* opt, void* stream);
 /* host only, no GPU call: the same update on HOST pointers (p, g, m, v, and dynamic / skip / scale_state where set), a plain loop over the
  * inline element function the kernel runs. */
@@ -703,7 +683,7 @@ enum {
     MTBC_OP_CONVT_FWD, MTBC_OP_CONVT_DGRAD, MTBC_OP_CONVT_WGRAD,
     MTBC_OP_CONV1_FWD, MTBC_OP_CONV1_DGRAD, MTBC_OP_CONV1_WGRAD,
     MTBC_OP_GAP_FWD, MTBC_OP_GAP_BWD, MTBC_OP_LINEAR_FWD, MTBC_OP_LINEAR_BWD,
-    MTBC_OP_DICE_FWD, MTBC_OP_DICE_BWD, MTBC_OP_FOCAL, MTBC_OP_LOSS_MIX, MTBC_OP_ADAM,
+    MTBC_OP_DICE_FWD, MTBC_OP_DICE_BWD, MTBC_OP_FOCAL, MTBC_OP_LOSS_MIX, MTBC_OP_OPTIM,
     MTBC_OP_MEMSET, MTBC_OP_DICE_COUNTS, MTBC_OP_CONV3_PACK_LP, MTBC_OP_HEAD_COMBINE, MTBC_OP_HEAD_EXPAND,
     MTBC_OP_C8_PACK, MTBC_OP_C8_PACK16, MTBC_OP_CONV3_WVIEW,
     MTBC_OP_SET_STREAM, MTBC_OP_EVENT_RECORD, MTBC_OP_EVENT_WAIT,
@@ -779,7 +759,7 @@ typedef struct {
         mtbc_linear_args linear;
         mtbc_dice_args dice;
         mtbc_focal_args focal;
-        mtbc_adam_args adam;
+        mtbc_optim_args optim;
         struct { const float* w; float* packed; int32_t Cin, Cout; int32_t dgrad, compute; } pack;
         struct { const float* seg; const float* cls; float alpha; float* out4; } mix;
         struct { void* ptr; size_t bytes; } memset0;

@@ -128,17 +128,11 @@ class FocalArgs(C.Structure):
                 ("loss", C.c_void_p), ("dx", C.c_void_p), ("gscale", C.c_float), ("gscale_dev", C.c_void_p)]
 
 
-class AdamArgs(C.Structure):
-    _fields_ = [("n", C.c_int64), ("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p),
-                ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
-                ("grad_scale", C.c_float), ("step", C.c_int32), ("zero_grad", C.c_int32), ("dynamic", C.c_void_p)]
-
-
 OPT_SGD, OPT_ADAMW = 0, 1        # mtbc_optim_args.kind
 
 
 class OptimArgs(C.Structure):
-    """mtbc_optim_args (include/mtbc.h): the fused SGD / AdamW launch."""
+    """mtbc_optim_args (include/mtbc.h): the fused Adam (ADAMW, weight_decay 0) / SGD / AdamW launch."""
     _fields_ = [("kind", C.c_int32), ("n", C.c_int64), ("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p),
                 ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("momentum", C.c_float),
                 ("weight_decay", C.c_float), ("grad_scale", C.c_float), ("step", C.c_int32), ("zero_grad", C.c_int32), ("nesterov", C.c_int32),
@@ -235,7 +229,7 @@ class HeadFuseArgs(C.Structure):
 class _OpUnion(C.Union):
     _fields_ = [("conv3", Conv3x3Args), ("inorm", InstNormArgs), ("pool", MaxPoolArgs), ("convT", ConvTArgs),
                 ("conv1", Conv1x1Args), ("gap", GapArgs), ("linear", LinearArgs), ("dice", DiceArgs),
-                ("focal", FocalArgs), ("adam", AdamArgs), ("pack", _PackArgs), ("mix", _MixArgs),
+                ("focal", FocalArgs), ("optim", OptimArgs), ("pack", _PackArgs), ("mix", _MixArgs),
                 ("memset0", _MemsetArgs), ("counts", _CountsArgs), ("head", HeadFuseArgs), ("c8pack", _C8PackArgs), ("wview", _WViewArgs), ("dparam", DparamDesc), ("sync", _SyncArgs)]
 
 
@@ -247,7 +241,7 @@ class Op(C.Structure):
 (OP_CONV3_FWD, OP_CONV3_DGRAD, OP_CONV3_WGRAD, OP_CONV3_PACK_FWD, OP_CONV3_PACK_DGRAD,
  OP_IN_FWD, OP_IN_BWD, OP_POOL_FWD, OP_POOL_BWD, OP_CONVT_FWD, OP_CONVT_DGRAD, OP_CONVT_WGRAD,
  OP_CONV1_FWD, OP_CONV1_DGRAD, OP_CONV1_WGRAD, OP_GAP_FWD, OP_GAP_BWD, OP_LINEAR_FWD, OP_LINEAR_BWD,
- OP_DICE_FWD, OP_DICE_BWD, OP_FOCAL, OP_LOSS_MIX, OP_ADAM, OP_MEMSET, OP_DICE_COUNTS, OP_CONV3_PACK_LP,
+ OP_DICE_FWD, OP_DICE_BWD, OP_FOCAL, OP_LOSS_MIX, OP_OPTIM, OP_MEMSET, OP_DICE_COUNTS, OP_CONV3_PACK_LP,
  OP_HEAD_COMBINE, OP_HEAD_EXPAND, OP_C8_PACK, OP_C8_PACK16, OP_CONV3_WVIEW,
  OP_SET_STREAM, OP_EVENT_RECORD, OP_EVENT_WAIT, OP_IN_DPARAM) = range(1, 37)
 
@@ -258,7 +252,7 @@ OP_UNION_FIELD = {
     OP_CONVT_FWD: "convT", OP_CONVT_DGRAD: "convT", OP_CONVT_WGRAD: "convT",
     OP_CONV1_FWD: "conv1", OP_CONV1_DGRAD: "conv1", OP_CONV1_WGRAD: "conv1",
     OP_GAP_FWD: "gap", OP_GAP_BWD: "gap", OP_LINEAR_FWD: "linear", OP_LINEAR_BWD: "linear",
-    OP_DICE_FWD: "dice", OP_DICE_BWD: "dice", OP_FOCAL: "focal", OP_LOSS_MIX: "mix", OP_ADAM: "adam",
+    OP_DICE_FWD: "dice", OP_DICE_BWD: "dice", OP_FOCAL: "focal", OP_LOSS_MIX: "mix", OP_OPTIM: "optim",
     OP_MEMSET: "memset0", OP_DICE_COUNTS: "counts", OP_CONV3_PACK_LP: "pack",
     OP_HEAD_COMBINE: "head", OP_HEAD_EXPAND: "head", OP_C8_PACK: "c8pack", OP_C8_PACK16: "c8pack", OP_CONV3_WVIEW: "wview",
     OP_SET_STREAM: "sync", OP_EVENT_RECORD: "sync", OP_EVENT_WAIT: "sync", OP_IN_DPARAM: "dparam",
@@ -285,14 +279,14 @@ EXPORTS = [
     "mtbc_maxpool2_bwd", "mtbc_convT_wgrad_workspace", "mtbc_convT_fwd_c8_supported", "mtbc_convT_fwd", "mtbc_convT_dgrad", "mtbc_convT_wgrad",
     "mtbc_conv1x1_wgrad_workspace", "mtbc_conv1x1_fwd", "mtbc_conv1x1_dgrad", "mtbc_conv1x1_wgrad",
     "mtbc_gap_fwd", "mtbc_gap_bwd", "mtbc_linear_fwd", "mtbc_linear_bwd", "mtbc_dice_fwd", "mtbc_dice_bwd",
-    "mtbc_focal_fwd_bwd", "mtbc_loss_mix", "mtbc_adam_step", "mtbc_adam_dynamic", "mtbc_loss_scale_begin", "mtbc_loss_scale_check", "mtbc_loss_scale_adam",
+    "mtbc_focal_fwd_bwd", "mtbc_loss_mix", "mtbc_loss_scale_begin", "mtbc_loss_scale_check",
     "mtbc_loss_scale_update_host", "mtbc_loss_scale_begin_host", "mtbc_optim_step", "mtbc_optim_dynamic", "mtbc_loss_scale_optim", "mtbc_optim_step_host",
     "mtbc_dice_counts", "mtbc_program_run",
     "mtbc_program_run_ms", "mtbc_event_create", "mtbc_event_destroy",
     "mtbc_seg_metrics_workspace_size", "mtbc_seg_metrics", "mtbc_batch_assemble", "mtbc_train_metrics",
 ]
 
-ABI_VERSION = 202          # MTBC_VERSION of include/mtbc.h these mirrors follow
+ABI_VERSION = 203          # MTBC_VERSION of include/mtbc.h these mirrors follow
 _lib: Optional[C.CDLL] = None
 
 
@@ -363,8 +357,7 @@ def load() -> C.CDLL:
                       ("mtbc_conv1x1_fwd", Conv1x1Args), ("mtbc_conv1x1_dgrad", Conv1x1Args),
                       ("mtbc_conv1x1_wgrad", Conv1x1Args), ("mtbc_gap_fwd", GapArgs), ("mtbc_gap_bwd", GapArgs),
                       ("mtbc_linear_fwd", LinearArgs), ("mtbc_linear_bwd", LinearArgs),
-                      ("mtbc_dice_fwd", DiceArgs), ("mtbc_dice_bwd", DiceArgs), ("mtbc_focal_fwd_bwd", FocalArgs),
-                      ("mtbc_adam_step", AdamArgs)):
+                      ("mtbc_dice_fwd", DiceArgs), ("mtbc_dice_bwd", DiceArgs), ("mtbc_focal_fwd_bwd", FocalArgs)):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [C.POINTER(typ), C.c_void_p]
     lib.mtbc_instnorm_coop_state_bytes.restype = C.c_size_t
@@ -383,13 +376,9 @@ def load() -> C.CDLL:
     lib.mtbc_loss_mix.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
     lib.mtbc_dice_counts.restype = C.c_int
     lib.mtbc_dice_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.mtbc_adam_dynamic.restype = C.c_int
-    lib.mtbc_adam_dynamic.argtypes = [C.POINTER(AdamArgs), C.POINTER(C.c_float * 3)]
     for name in ("mtbc_loss_scale_begin", "mtbc_loss_scale_check"):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [C.POINTER(LossScaleArgs), C.c_void_p]
-    lib.mtbc_loss_scale_adam.restype = C.c_int
-    lib.mtbc_loss_scale_adam.argtypes = [C.POINTER(LossScaleArgs), C.POINTER(AdamArgs), C.c_void_p]
     for name in ("mtbc_loss_scale_update_host", "mtbc_loss_scale_begin_host"):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [C.POINTER(LossScaleArgs)]

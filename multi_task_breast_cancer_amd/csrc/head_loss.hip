@@ -1,5 +1,5 @@
 // Pooled classification head (GAP + Linear), fused Dice / Focal losses, loss mix + NaN flag,
-// fused Adam / SGD / AdamW and the train-loop Dice counters.  All HBM-/latency-bound; reductions use wavefront
+// fused Adam / SGD / AdamW (one kernel) and the train-loop Dice counters.  All HBM-/latency-bound; reductions use wavefront
 // shuffles (64 lanes) then LDS across waves -- deterministic, no float atomics.
 #include "common.h"
 
@@ -352,43 +352,13 @@ __global__ void loss_mix_kernel(const float* seg, const float* cls, float alpha,
     out4[3] = (s != s || c != c) ? 1.f : 0.f;
 }
 
-// ------------------------------------------------------------------ Adam
-struct AdamP { long long n; float* p; float* g; float* m; float* v; float gs, b1, b2, eps, step_size, inv_bc2_sqrt; int zero; const float* dyn; const unsigned* skip; };
-__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamP& a) {
-    g *= a.gs;
-    m = m + (g - m) * (1.0f - a.b1);                     // lerp, as torch
-    v = v * a.b2 + (1.0f - a.b2) * g * g;
-    const float denom = sqrtf(v) * a.inv_bc2_sqrt + a.eps;
-    p = p - a.step_size * (m / denom);
-}
-__global__ void adam_kernel(AdamP a) {
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    if (a.skip && *a.skip) {                     // dynamic loss scale: a gradient overflowed -> p, m, v are not touched (uniform load, every thread takes the same way)
-        if (a.zero) for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) a.g[i] = 0.f;
-        return;
-    }
-    if (a.dyn) { a.gs = a.dyn[0]; a.step_size = a.dyn[1]; a.inv_bc2_sqrt = a.dyn[2]; }      // the per-step scalars from memory (graph replay), uniform loads
-    const long long n4 = a.n >> 2;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        float4 p = reinterpret_cast<float4*>(a.p)[i], g = reinterpret_cast<float4*>(a.g)[i];
-        float4 m = reinterpret_cast<float4*>(a.m)[i], v = reinterpret_cast<float4*>(a.v)[i];
-        adam1(p.x, g.x, m.x, v.x, a); adam1(p.y, g.y, m.y, v.y, a); adam1(p.z, g.z, m.z, v.z, a); adam1(p.w, g.w, m.w, v.w, a);
-        reinterpret_cast<float4*>(a.p)[i] = p; reinterpret_cast<float4*>(a.m)[i] = m; reinterpret_cast<float4*>(a.v)[i] = v;
-        if (a.zero) reinterpret_cast<float4*>(a.g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    for (long long i = (n4 << 2) + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
-        adam1(a.p[i], a.g[i], a.m[i], a.v[i], a);
-        if (a.zero) a.g[i] = 0.f;
-    }
-}
-
 // ------------------------------------------------------------------ dynamic loss scale (torch.amp.GradScaler's rule on the device)
 // The two single-thread halves are plain functions shared by the kernels and by the host-only entry points, so that the rule a machine without a GPU
 // tests is the rule the device runs.
 __host__ __device__ inline void loss_scale_begin(mtbc_loss_scale_state* s, float* gscale_out, float inv_world, float b1, float b2) {
     if (gscale_out) *gscale_out = s->shard_weight * s->scale;
     const double t1 = (double)(s->t + 1);                      // the step this update would be, if it is applied
-    const double bc1 = 1.0 - pow((double)b1, t1);              // as adam_scalars() below: in double, rounded once
+    const double bc1 = 1.0 - pow((double)b1, t1);              // as optim_scalars() below: in double, rounded once
     const double bc2 = 1.0 - pow((double)b2, t1);
     s->adam[0] = (float)((double)inv_world / (double)s->scale);
     s->adam[1] = (float)((double)s->lr / bc1);
@@ -432,12 +402,13 @@ __global__ void found_inf_kernel(const float* __restrict__ g, long long n, unsig
     if (bad) atomicOr(flag, 1u);                                // rare (an overflowing step), so no wave reduction in front of it
 }
 
-// ------------------------------------------------------------------ SGD (Nesterov) and AdamW
+// ------------------------------------------------------------------ Adam, SGD (Nesterov) and AdamW
 // One element function for the kernel and for mtbc_optim_step_host: no contraction is left to the compiler (host and device would choose
-// differently), every fused operation is an fmaf.  The AdamW branch is adam1 above as the compiler contracts it in adam_kernel: g' - m as
-// fma(gs, g, -m), the denominator and the last line as one fma each, and v in the TWO forms adam_kernel has -- fma(g', (1-b2) g', b2 v) in its
-// float4 body, the product g' ((1-b2) g') plus the product b2 v in its scalar tail (TAIL: the elements from n & ~3 on).  The rule is therefore
-// position-dependent for AdamW's v on at most three elements of a buffer; that is what makes AdamW with weight_decay = 0 FusedAdam bit for bit.
+// differently), every fused operation is an fmaf.  Adam is the AdamW branch with weight_decay 0: decay = (float)(1 - lr 0) = 1 and p * 1.0f is p.
+// The branch DEFINES the rule: g' - m as fma(gs, g, -m), the denominator and the last line as one fma each, and v in two forms --
+// fma(g', (1-b2) g', b2 v) in the float4 body, the product g' ((1-b2) g') plus the product b2 v in the scalar tail (TAIL: the elements from
+// n & ~3 on).  The two forms are how the compiler contracted the kernel Adam had to itself until ABI 203; tests/golden/adam_steps.npz holds its words.
+// The rule is therefore position-dependent for v on at most three elements of a buffer (none in training: the flat buffer is a multiple of four).
 struct OptimS { float gs, step, inv_bc2_sqrt, decay, omb1, omb2, b2, eps, momentum; int nesterov; };     // step: SGD lr | AdamW lr / (1 - b1^t)
 struct OptimP { long long n; float* p; float* g; float* m; float* v; OptimS s; float wd; int kind, zero;
                 const float* dyn; const unsigned* skip; const mtbc_loss_scale_state* st; };
@@ -492,7 +463,7 @@ template <int KIND> __device__ __forceinline__ void optim_range(const OptimP& a)
     }
 }
 __global__ void optim_kernel(OptimP a) {
-    if (a.skip && *a.skip) {                     // as adam_kernel: a gradient overflowed -> p, m, v are not touched (uniform load)
+    if (a.skip && *a.skip) {                     // dynamic loss scale: a gradient overflowed -> p, m, v are not touched (uniform load, every thread takes the same way)
         const long long stride = (long long)gridDim.x * blockDim.x;
         if (a.zero) for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) a.g[i] = 0.f;
         return;
@@ -642,43 +613,6 @@ int mtbc_loss_mix(const float* seg, const float* cls, float alpha, float* out4, 
     return MTBC_OK;
 }
 
-// bias corrections in double on the host, exactly as torch.optim.Adam's scalar path
-static void adam_scalars(const mtbc_adam_args* a, float out3[3]) {
-    const double bc1 = 1.0 - pow((double)a->beta1, (double)a->step);
-    const double bc2 = 1.0 - pow((double)a->beta2, (double)a->step);
-    out3[0] = a->grad_scale;
-    out3[1] = (float)((double)a->lr / bc1);
-    out3[2] = (float)(1.0 / sqrt(bc2));
-}
-int mtbc_adam_dynamic(const mtbc_adam_args* a, float out3[3]) {
-    if (!a || !out3 || a->step < 1) return MTBC_E_BADARG;
-    adam_scalars(a, out3);
-    return MTBC_OK;
-}
-int mtbc_adam_step(const mtbc_adam_args* a, void* stream) {
-    if (!a || a->n <= 0 || a->step < 1) return MTBC_E_BADSHAPE;
-    if (!a->p || !a->g || !a->m || !a->v) return MTBC_E_BADARG;
-    if ((reinterpret_cast<uintptr_t>(a->p) | reinterpret_cast<uintptr_t>(a->g) | reinterpret_cast<uintptr_t>(a->m) |
-         reinterpret_cast<uintptr_t>(a->v)) & 15)
-        return MTBC_E_UNSUPPORTED;
-    if (a->dynamic && (reinterpret_cast<uintptr_t>(a->dynamic) & 3)) return MTBC_E_BADARG;
-    float dyn[3];
-    adam_scalars(a, dyn);
-    AdamP p;
-    p.n = a->n; p.p = a->p; p.g = const_cast<float*>(a->g); p.m = a->m; p.v = a->v; p.gs = dyn[0];
-    p.b1 = a->beta1; p.b2 = a->beta2; p.eps = a->eps;
-    p.step_size = dyn[1];
-    p.inv_bc2_sqrt = dyn[2];
-    p.zero = a->zero_grad;
-    p.dyn = a->dynamic;
-    p.skip = nullptr;
-    long long blocks = cdiv64(a->n / 4 + 1, 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
-    MTBC_CHECK_LAUNCH();
-    return MTBC_OK;
-}
-
 static int loss_scale_args_ok(const mtbc_loss_scale_args* a) {
     if (!a || !a->state || (reinterpret_cast<uintptr_t>(a->state) & 3)) return 0;
     return a->growth_interval >= 1 && a->growth_factor > 0.0 && a->backoff_factor > 0.0 && a->inv_world > 0.f;
@@ -699,28 +633,6 @@ int mtbc_loss_scale_check(const mtbc_loss_scale_args* a, void* stream) {
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
-int mtbc_loss_scale_adam(const mtbc_loss_scale_args* a, const mtbc_adam_args* adam, void* stream) {
-    if (!loss_scale_args_ok(a)) return MTBC_E_BADARG;
-    if (!adam || adam->n <= 0) return MTBC_E_BADSHAPE;
-    if (!adam->p || !adam->g || !adam->m || !adam->v) return MTBC_E_BADARG;
-    if ((reinterpret_cast<uintptr_t>(adam->p) | reinterpret_cast<uintptr_t>(adam->g) | reinterpret_cast<uintptr_t>(adam->m) |
-         reinterpret_cast<uintptr_t>(adam->v)) & 15)
-        return MTBC_E_UNSUPPORTED;
-    AdamP p;
-    p.n = adam->n; p.p = adam->p; p.g = const_cast<float*>(adam->g); p.m = adam->m; p.v = adam->v;
-    p.gs = 0.f; p.step_size = 0.f; p.inv_bc2_sqrt = 0.f;                   // the kernel takes all three from state->adam
-    p.b1 = adam->beta1; p.b2 = adam->beta2; p.eps = adam->eps;
-    p.zero = adam->zero_grad;
-    p.dyn = a->state->adam;
-    p.skip = &a->state->found_inf;
-    long long blocks = cdiv64(adam->n / 4 + 1, 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
-    MTBC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a->state, a->growth_factor, a->backoff_factor, a->growth_interval);
-    MTBC_CHECK_LAUNCH();
-    return MTBC_OK;
-}
 int mtbc_loss_scale_update_host(const mtbc_loss_scale_args* a) {
     if (!loss_scale_args_ok(a)) return MTBC_E_BADARG;
     loss_scale_update(a->state, a->growth_factor, a->backoff_factor, a->growth_interval);
@@ -732,7 +644,7 @@ int mtbc_loss_scale_begin_host(const mtbc_loss_scale_args* a) {
     return MTBC_OK;
 }
 
-// SGD / AdamW: the four per-step scalars, AdamW's bias corrections in double exactly as adam_scalars
+// the four per-step scalars, Adam's / AdamW's bias corrections in double on the host, exactly as torch.optim.Adam's scalar path
 static void optim_scalars(const mtbc_optim_args* a, float out4[4]) {
     out4[0] = a->grad_scale;
     if (a->kind == MTBC_OPT_SGD) { out4[1] = a->lr; out4[2] = 1.f; out4[3] = 1.f; return; }

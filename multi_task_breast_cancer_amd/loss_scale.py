@@ -6,7 +6,7 @@ device memory (`mtbc_loss_scale_state`), and three small launches per step work 
 
     begin : *gscale = shard_weight * scale (the word the loss-gradient kernels multiply by); Adam's three scalars for step t + 1, in double
     check : one pass over the flat gradient buffer, found_inf = 1 on any inf / NaN (after the all-reduce under data parallel: every rank sees it)
-    adam  : the fused optimizer launch (Adam, SGD or AdamW), every thread returning at once when found_inf is set; then the update rule on the state
+    apply : the fused optimizer launch (Adam, SGD or AdamW; mtbc_loss_scale_optim), every thread returning at once when found_inf is set; then the update rule on the state
 
 State dicts use torch.amp.GradScaler's keys, so the two interchange.
 """
@@ -85,7 +85,7 @@ class DynamicLossScale:
     def graph_key(self):
         return (self._state.data_ptr(), self.growth_factor, self.backoff_factor, self.growth_interval)
 
-    # ---- the per-step launches (all stream-ordered; begin / check / adam are capturable, the two fills are not meant to be) ---------------------------
+    # ---- the per-step launches (all stream-ordered; begin / check / apply are capturable, the two fills are not meant to be) ---------------------------
     def set_lr(self, lr: float) -> None:
         self._f[_LR:_LR + 1].fill_(float(lr))
 
@@ -113,13 +113,9 @@ class DynamicLossScale:
         L.check(L.load().mtbc_loss_scale_check(C.byref(self.args(g=flat_g)), self._stream()), "loss scale check")
 
     def apply(self, optimizer, world: int) -> None:
-        """The optimizer's fused launch under the found-inf word, then the update of the state.  The optimizer names its entry point and brings its
-        arguments (`_scaled_launch`): mtbc_loss_scale_adam for FusedAdam, mtbc_loss_scale_optim for FusedSGD / FusedAdamW."""
+        """The optimizer's fused launch under the found-inf word, then the update of the state (lr, step and grad_scale of the arguments are not read)."""
         optimizer._ensure_state()
-        entry, ad = optimizer._scaled_launch()
-        L.check(getattr(L.load(), entry)(C.byref(self.args(world, betas_of(optimizer))), C.byref(ad), self._stream()), "loss scale " + entry[len("mtbc_loss_scale_"):])
-
-    adam = apply                          # the name from when FusedAdam was the only optimizer of the fused step
+        L.check(L.load().mtbc_loss_scale_optim(C.byref(self.args(world, betas_of(optimizer))), C.byref(optimizer._args()), self._stream()), "loss scale optim")
 
     # ---- torch.amp.GradScaler's state dict ---------------------------------------------------------------------------------------
     def state_dict(self) -> dict:

@@ -816,11 +816,8 @@ def focal(x, t, alpha=1.0, gamma=2.0, weight=None, gscale=1.0):
 
 
 def adam_step(p, g, m, v, lr, step, beta1=0.9, beta2=0.999, eps=1e-4, grad_scale=1.0, zero_grad=False):
-    _chk(p, g, m, v)
-    a = L.AdamArgs()
-    a.n, a.p, a.g, a.m, a.v = p.numel(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
-    a.lr, a.beta1, a.beta2, a.eps, a.grad_scale, a.step, a.zero_grad = lr, beta1, beta2, eps, grad_scale, step, int(zero_grad)
-    L.check(L.load().mtbc_adam_step(C.byref(a), _s()), "adam")
+    """Adam on the shared optimizer launch: the AdamW rule with weight_decay 0 (a decay factor of exactly 1)."""
+    optim_step(L.OPT_ADAMW, p, g, m, v, lr=lr, step=step, beta1=beta1, beta2=beta2, eps=eps, weight_decay=0.0, grad_scale=grad_scale, zero_grad=zero_grad)
 
 
 # ------------------------------------------------------------------ dynamic loss scale (op level; `state` = 16 int32 words on the device = mtbc_loss_scale_state)
@@ -855,14 +852,13 @@ def loss_scale_check(state, g):
 def loss_scale_adam(state, p, g, m, v, beta1=0.9, beta2=0.999, eps=1e-4, zero_grad=False, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
     """Adam with the scalars `loss_scale_begin` left, skipped when state.found_inf is set; then the scale / tracker / t / skipped update."""
     _chk(p, g, m, v)
-    ad = L.AdamArgs()
-    ad.n, ad.p, ad.g, ad.m, ad.v = p.numel(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
-    ad.beta1, ad.beta2, ad.eps, ad.step, ad.zero_grad = beta1, beta2, eps, 1, int(zero_grad)
+    ad = optim_args(L.OPT_ADAMW, p.numel(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), beta1=beta1, beta2=beta2, eps=eps, weight_decay=0.0,
+                    zero_grad=zero_grad)
     a = _loss_scale_args(state, growth_factor, backoff_factor, growth_interval, beta1=beta1, beta2=beta2)
-    L.check(L.load().mtbc_loss_scale_adam(C.byref(a), C.byref(ad), _s()), "loss scale adam")
+    L.check(L.load().mtbc_loss_scale_optim(C.byref(a), C.byref(ad), _s()), "loss scale adam")
 
 
-# ------------------------------------------------------------------ fused SGD (Nesterov) / AdamW (op level)
+# ------------------------------------------------------------------ fused Adam / SGD (Nesterov) / AdamW (op level)
 def optim_args(kind, n, p, g, m, v=None, lr=1e-3, step=1, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.9, weight_decay=0.0, grad_scale=1.0,
                zero_grad=False, nesterov=True, dynamic=None, skip=None, scale_state=None):
     """mtbc_optim_args from ADDRESSES (device pointers for optim_step, host pointers for mtbc_optim_step_host)."""
@@ -875,7 +871,7 @@ def optim_args(kind, n, p, g, m, v=None, lr=1e-3, step=1, beta1=0.9, beta2=0.999
 
 
 def optim_step(kind, p, g, m, v=None, dynamic=None, skip=None, **hyper):
-    """One fused SGD (kind = L.OPT_SGD; `m` is the momentum buffer) or AdamW (L.OPT_ADAMW) launch on device tensors; `dynamic`: 4 device floats as
+    """One fused SGD (kind = L.OPT_SGD; `m` is the momentum buffer) or AdamW (L.OPT_ADAMW; Adam with weight_decay 0) launch on device tensors; `dynamic`: 4 device floats as
     mtbc_optim_dynamic writes them, `skip`: a device int32 word."""
     _chk(p, g, m, v, dynamic)
     a = optim_args(kind, p.numel(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr() if v is not None else None,

@@ -392,7 +392,7 @@ class FusedTrainStep:
         sc = self.scaler
         if sc is None:
             opt.grad_scale = (1.0 / self.world) / getattr(st, "loss_scale", 1.0)
-            opt.advance_dynamic()                 # step count, lr, bias corrections -> 12 bytes of device memory, in stream order, outside the graph
+            opt.advance_dynamic()                 # step count, lr, bias corrections, decay factor -> 16 bytes of device memory, in stream order, outside the graph
         else:
             opt._ensure_state()
             self._begin_dynamic(st)               # lr -> the scaler's state; step count, scale and bias corrections are the device's own business

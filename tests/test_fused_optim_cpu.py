@@ -1,6 +1,7 @@
-"""Fused SGD (Nesterov) / AdamW on a machine without a GPU: the C-ABI additions (exports, the struct's layout against the header through gcc), the
-per-step scalars, the update rule -- `mtbc_optim_step_host` runs the same inline element function as the device kernel -- against torch.optim.SGD /
-torch.optim.AdamW (experiment_init.py:188-191), and the factory's `fused=True`."""
+"""Fused Adam / SGD (Nesterov) / AdamW on a machine without a GPU: the C-ABI additions (exports, the struct's layout against the header through gcc),
+the per-step scalars, the update rule -- `mtbc_optim_step_host` runs the same inline element function as the device kernel -- against torch.optim.Adam /
+torch.optim.SGD / torch.optim.AdamW (experiment_init.py:186-191), the words Adam's own kernel wrote before it moved onto the shared launch
+(tests/golden/adam_steps.npz), and the factory's `fused=True`."""
 import ctypes as C
 import math
 import os
@@ -18,7 +19,10 @@ from multi_task_breast_cancer_amd import _lib as L   # noqa: E402
 from multi_task_breast_cancer_amd import ops   # noqa: E402
 
 NEW = ("mtbc_optim_step", "mtbc_optim_dynamic", "mtbc_loss_scale_optim", "mtbc_optim_step_host")
-KINDS = {"SGD": L.OPT_SGD, "AdamW": L.OPT_ADAMW}
+KINDS = {"SGD": L.OPT_SGD, "AdamW": L.OPT_ADAMW, "Adam": L.OPT_ADAMW}
+# the hyper-parameters that tell the names apart: Adam is the AdamW rule without decay, at the eps the reference runs it with (experiment_init.py:187)
+RULE = {"SGD": dict(weight_decay=1e-2, eps=1e-8), "AdamW": dict(weight_decay=1e-2, eps=1e-8), "Adam": dict(weight_decay=0.0, eps=1e-4)}
+GOLDEN = os.path.join(ROOT, "tests", "golden", "adam_steps.npz")
 
 
 @pytest.fixture(scope="module")
@@ -36,7 +40,7 @@ def test_optim_symbols_are_declared_bound_and_exported(lib):
     for name in NEW:
         assert name in declared and name in L.EXPORTS, name
         assert hasattr(lib, name), name
-    assert lib.mtbc_version() == 202 == L.ABI_VERSION           # new symbols and a new struct only: no existing layout moved
+    assert lib.mtbc_version() == 203 == L.ABI_VERSION           # 203: Adam's own struct and entry points left, Adam is mtbc_optim_args (ADAMW, weight_decay 0)
     assert (L.OPT_SGD, L.OPT_ADAMW) == tuple(int(re.search(rf"#define\s+MTBC_OPT_{k}\s+(\d+)", src).group(1)) for k in ("SGD", "ADAMW"))
 
 
@@ -44,7 +48,7 @@ def test_optim_args_ctypes_layout_matches_header(tmp_path):
     offs = [("mtbc_optim_args", f, getattr(L.OptimArgs, f).offset) for f, _ in L.OptimArgs._fields_]
     assert {"kind", "dynamic", "skip", "scale_state"} <= {f for _, f, _ in offs}
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){",
-             'printf("mtbc_optim_args %zu\\n", sizeof(mtbc_optim_args));', 'printf("mtbc_adam_args %zu\\n", sizeof(mtbc_adam_args));']
+             'printf("mtbc_optim_args %zu\\n", sizeof(mtbc_optim_args));']
     for s, f, _ in offs:
         lines.append(f'printf("{s}.{f} %zu\\n", offsetof({s}, {f}));')
     lines.append("return 0;}")
@@ -54,7 +58,6 @@ def test_optim_args_ctypes_layout_matches_header(tmp_path):
     subprocess.check_call(["gcc", "-std=c11", "-o", str(exe), str(src)])
     got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().splitlines())
     assert int(got["mtbc_optim_args"]) == C.sizeof(L.OptimArgs)
-    assert int(got["mtbc_adam_args"]) == C.sizeof(L.AdamArgs)   # Adam's struct is where it was
     for s, f, off in offs:
         assert int(got[f"{s}.{f}"]) == off, (s, f)
 
@@ -76,17 +79,13 @@ def test_optim_dynamic_scalars_are_the_double_precision_expressions(lib, wd):
                 np.float32(1.0 - f32(lr) * f32(wd)))
         assert tuple(np.float32(v) for v in out) == want, (lr, b1, b2, t, list(out), want)
         if wd == 0.0:
-            ad = L.AdamArgs()
-            ad.lr, ad.beta1, ad.beta2, ad.eps, ad.grad_scale, ad.step = lr, b1, b2, 1e-4, gs, t
-            out3 = (C.c_float * 3)()
-            assert lib.mtbc_adam_dynamic(C.byref(ad), C.byref(out3)) == 0
-            assert list(out)[:3] == list(out3) and out[3] == 1.0
+            assert out[3] == 1.0                                  # Adam: the decay factor is exactly one
         a.kind = L.OPT_SGD
         assert lib.mtbc_optim_dynamic(C.byref(a), C.byref(out)) == 0
         assert tuple(np.float32(v) for v in out) == (np.float32(gs), np.float32(lr), np.float32(1.0), np.float32(1.0))
-    for kind in KINDS.values():
+    for kind in set(KINDS.values()):
         bad = ops.optim_args(kind, 0, None, None, None, step=0)
-        assert lib.mtbc_optim_dynamic(C.byref(bad), C.byref((C.c_float * 4)())) != 0        # t >= 1, as mtbc_adam_dynamic
+        assert lib.mtbc_optim_dynamic(C.byref(bad), C.byref((C.c_float * 4)())) != 0        # t >= 1
     assert lib.mtbc_optim_dynamic(C.byref(ops.optim_args(2, 0, None, None, None)), C.byref((C.c_float * 4)())) != 0   # no such kind
 
 
@@ -123,11 +122,13 @@ def aligned_copy(x):
 def _torch_opt(name, params, lr):
     if name == "SGD":
         return torch.optim.SGD(params, lr=lr, momentum=0.9, nesterov=True, foreach=False)
+    if name == "Adam":
+        return torch.optim.Adam(params, lr=lr, eps=1e-4, foreach=False)
     return torch.optim.AdamW(params, lr=lr, foreach=False)
 
 
 @pytest.mark.parametrize("n", [1, 3, 4, 1027])
-@pytest.mark.parametrize("name", ["SGD", "AdamW"])
+@pytest.mark.parametrize("name", ["SGD", "AdamW", "Adam"])
 def test_host_rule_matches_torch(lib, name, n):
     """Four steps on gradients of four magnitudes (test_adam_matches_torch's) against torch's own optimizer in float32 AND its float64 twin on the same
     float32 gradients.  Per step: max |host - t64| <= 2 max |t32 - t64| + 2^-23 max |p| -- twice the reference's own rounding distance plus one ulp at the
@@ -139,7 +140,7 @@ def test_host_rule_matches_torch(lib, name, n):
     p32, p64 = p0.clone().requires_grad_(True), p0.double().requires_grad_(True)
     o32, o64 = _torch_opt(name, [p32], lr), _torch_opt(name, [p64], lr)
     g0 = o32.param_groups[0]
-    p, m, v = aligned_copy(p0.numpy()), aligned(n), (aligned(n) if name == "AdamW" else None)
+    p, m, v = aligned_copy(p0.numpy()), aligned(n), (aligned(n) if name != "SGD" else None)
     hyper = dict(lr=lr, momentum=0.9, nesterov=True) if name == "SGD" else \
         dict(lr=lr, beta1=g0["betas"][0], beta2=g0["betas"][1], eps=g0["eps"], weight_decay=g0["weight_decay"])
     worst = 0.0
@@ -169,6 +170,25 @@ def test_host_rule_matches_torch(lib, name, n):
         assert np.abs(mine.astype(np.float64) - ref).max() <= rel[key] * np.abs(ref).max(), key
 
 
+# ------------------------------------------------------------------------------------------------ 3b. Adam: the words of the kernel it had to itself
+@pytest.mark.parametrize("n", [1, 3, 4, 1027])
+def test_host_adam_reproduces_the_words_recorded_from_adams_own_kernel(lib, n):
+    """tests/golden/adam_steps.npz (tools/make_adam_fixture.py) holds p, exp_avg, exp_avg_sq and g after each of five ops.adam_step launches, recorded on
+    the GPU at the last commit at which Adam had its own kernel.  The shared element function -- AdamW, weight_decay 0 -- gives every one of those words,
+    on the tail elements (n = 1 and 3 are all tail) as on the float4 body; the fifth step clears g."""
+    z = np.load(GOLDEN)
+    f32 = lambda words: aligned_copy(np.ascontiguousarray(words).view(np.float32))
+    p, m, v = f32(z[f"n{n}_p0"]), aligned(n), aligned(n)
+    grads = z[f"n{n}_grads"]
+    assert grads.shape == (5, n) and grads.dtype == np.int32
+    for t in range(1, 6):
+        g = f32(grads[t - 1])
+        assert host_step(lib, L.OPT_ADAMW, p, g, m, v, lr=1e-4, step=t, eps=1e-4, weight_decay=0.0, grad_scale=0.25, zero_grad=(t == 5)) == 0
+        for key, mine in (("p", p), ("m", m), ("v", v), ("g", g)):
+            assert np.array_equal(mine.view(np.int32), z[f"n{n}_{key}"][t - 1]), (n, t, key)
+    assert not g.any() and v.any()
+
+
 # ------------------------------------------------------------------------------------------------ 4. exact statements on the host path
 def _case(n=1027, seed=5):
     rng = np.random.default_rng(seed)
@@ -176,12 +196,12 @@ def _case(n=1027, seed=5):
     return mk(), mk(1e-2), mk(0.1), aligned_copy(np.abs(rng.standard_normal(n) * 1e-3).astype(np.float32))
 
 
-@pytest.mark.parametrize("name", ["SGD", "AdamW"])
+@pytest.mark.parametrize("name", ["SGD", "AdamW", "Adam"])
 def test_host_grad_scale_zero_grad_and_skip_are_exact(lib, name):
     kind = KINDS[name]
-    hyper = dict(lr=1e-3, step=3, weight_decay=1e-2, eps=1e-8)
+    hyper = dict(lr=1e-3, step=3, **RULE[name])
     p0, g0, m0, v0 = _case()
-    use_v = lambda v: v if name == "AdamW" else None
+    use_v = lambda v: v if name != "SGD" else None
     # grad_scale = 1/8 on 8 g is grad_scale = 1 on g (a power of two: g' is the same float)
     p1, g1, m1, v1 = (aligned_copy(x) for x in (p0, g0 * np.float32(8.0), m0, v0))
     p2, g2, m2, v2 = (aligned_copy(x) for x in (p0, g0, m0, v0))
@@ -203,14 +223,14 @@ def test_host_grad_scale_zero_grad_and_skip_are_exact(lib, name):
     assert np.array_equal(p3, p2) and np.array_equal(m3, m2)     # a clear word: the plain step
 
 
-@pytest.mark.parametrize("name", ["SGD", "AdamW"])
+@pytest.mark.parametrize("name", ["SGD", "AdamW", "Adam"])
 def test_host_scalars_from_memory_give_the_launch_arguments_bits(lib, name):
     """`dynamic` (4 floats from mtbc_optim_dynamic) and `scale_state` (what mtbc_loss_scale_begin_host leaves) against the plain arguments."""
     kind = KINDS[name]
-    hyper = dict(lr=2.5e-4, step=7, weight_decay=1e-2, eps=1e-8, grad_scale=1.0 / 4096.0)
+    hyper = dict(lr=2.5e-4, step=7, grad_scale=1.0 / 4096.0, **RULE[name])
     p0, g0, m0, v0 = _case(259, seed=9)
     g0 = aligned_copy(g0 * np.float32(4096.0))
-    use_v = lambda v: v if name == "AdamW" else None
+    use_v = lambda v: v if name != "SGD" else None
     pa, ga, ma, va = (aligned_copy(x) for x in (p0, g0, m0, v0))
     assert host_step(lib, kind, pa, ga, ma, use_v(va), **hyper) == 0
     out = (C.c_float * 4)()

@@ -1,4 +1,5 @@
-"""Fused SGD (Nesterov) / AdamW on the GPU: the kernel against the host function that runs the same element function, bit for bit; whole training
+"""Fused Adam / SGD (Nesterov) / AdamW on the GPU: the kernel against the host function that runs the same element function, bit for bit; Adam
+against the words its own kernel wrote before it moved onto the shared launch (tests/golden/adam_steps.npz); whole training
 steps under FusedTrainStep against the oracle with torch.optim.SGD / torch.optim.AdamW (experiment_init.py:188-191); hipGraph replay, the dynamic
 loss scale, data parallel at world 1 with real RCCL launches, and checkpoint interchange with torch's optimizers in both directions."""
 import ctypes as C
@@ -22,6 +23,10 @@ from oracle import torch_oracle as O
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 KINDS = {"SGD": L.OPT_SGD, "AdamW": L.OPT_ADAMW}
+# the op-level rules by name -> (kind, the hyper-parameters that tell them apart): Adam is the AdamW rule without decay at the reference's eps
+RULES = {"SGD": (L.OPT_SGD, dict(weight_decay=1e-2, eps=1e-8)), "AdamW": (L.OPT_ADAMW, dict(weight_decay=1e-2, eps=1e-8)),
+         "Adam": (L.OPT_ADAMW, dict(weight_decay=0.0, eps=1e-4))}
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "adam_steps.npz")
 BIG = 2.0 ** 40           # a loss scale under which the first fp16 backward overflows (asserted below, not assumed)
 
 
@@ -50,12 +55,13 @@ def _host(lib, kind, arrs, dyn=None, skip=None, **hyper):
 
 
 @pytest.mark.parametrize("n", [1, 3, 4, 1027, 2_098_179])          # the last: 2048 blocks x 256 threads x 4 + 1027 -- the grid-stride loop and the tail
-@pytest.mark.parametrize("name", ["SGD", "AdamW"])
+@pytest.mark.parametrize("name", ["SGD", "AdamW", "Adam"])
 def test_kernel_is_the_host_function_bit_for_bit(name, n):
     """Four steps with the scalars in the launch arguments and four with `dynamic` set; then a step under a set skip word (nothing but g moves) and one
     under a clear word.  Every buffer is compared as bits after every launch."""
     lib = L.load()
-    kind = KINDS[name]
+    kind, rule = RULES[name]
+    adamw = kind == L.OPT_ADAMW
     gen = torch.Generator().manual_seed(n)
     host = [torch.randn(n, generator=gen), None, torch.zeros(n), torch.zeros(n)]
     grads = [torch.randn(n, generator=gen) * 10 ** float(e) for e in (-6, -3, 0, -2)]
@@ -71,7 +77,7 @@ def test_kernel_is_the_host_function_bit_for_bit(name, n):
     for use_dyn in (False, True):
         for gr in grads:
             t += 1
-            hyper = dict(lr=1e-3 / t, step=t, weight_decay=1e-2, eps=1e-8, grad_scale=0.5, zero_grad=(t % 2 == 0))
+            hyper = dict(lr=1e-3 / t, step=t, grad_scale=0.5, zero_grad=(t % 2 == 0), **rule)
             host[1] = gr.clone()
             arrs[1] = host[1].numpy()
             dev[1] = gr.to(DEV)
@@ -82,21 +88,21 @@ def test_kernel_is_the_host_function_bit_for_bit(name, n):
                 dyn_dev.copy_(torch.from_numpy(dyn_host))
                 wrong = dict(hyper, lr=1.0, step=1, grad_scale=3.0)          # not read when `dynamic` is set
                 _host(lib, kind, arrs, dyn=dyn_host, **wrong)
-                ops.optim_step(kind, dev[0], dev[1], dev[2], dev[3] if name == "AdamW" else None, dynamic=dyn_dev, **wrong)
+                ops.optim_step(kind, dev[0], dev[1], dev[2], dev[3] if adamw else None, dynamic=dyn_dev, **wrong)
             else:
                 _host(lib, kind, arrs, **hyper)
-                ops.optim_step(kind, dev[0], dev[1], dev[2], dev[3] if name == "AdamW" else None, **hyper)
+                ops.optim_step(kind, dev[0], dev[1], dev[2], dev[3] if adamw else None, **hyper)
             compare(f"step {t} dynamic {use_dyn}")
-    assert bool(dev[2].any()) and (name == "SGD" or bool(dev[3].any()))
+    assert bool(dev[2].any()) and (not adamw or bool(dev[3].any()))
     before = [x.clone() for x in dev]
     for word, zero in ((1, True), (1, False), (0, True)):
-        hyper = dict(lr=1e-3, step=9, weight_decay=1e-2, eps=1e-8, zero_grad=zero)
+        hyper = dict(lr=1e-3, step=9, zero_grad=zero, **rule)
         host[1] = grads[2].clone()
         arrs[1] = host[1].numpy()
         dev[1] = grads[2].to(DEV)
         skip_dev = torch.tensor([word], dtype=torch.int32, device=DEV)
         _host(lib, kind, arrs, skip=np.array([word], dtype=np.uint32), **hyper)
-        ops.optim_step(kind, dev[0], dev[1], dev[2], dev[3] if name == "AdamW" else None, skip=skip_dev, **hyper)
+        ops.optim_step(kind, dev[0], dev[1], dev[2], dev[3] if adamw else None, skip=skip_dev, **hyper)
         compare(f"skip word {word} zero_grad {zero}")
         if word:
             assert torch.equal(dev[0], before[0]) and torch.equal(dev[2], before[2]) and torch.equal(dev[3], before[3])
@@ -119,9 +125,9 @@ def test_misaligned_pointers_are_refused():
 
 @pytest.mark.parametrize("n", [1, 3, 4, 1027, 2_098_179])
 def test_adamw_without_decay_is_fused_adam(n):
-    """AdamW (weight_decay 0, eps 1e-4) against ops.adam_step over four steps: torch.equal on every element.  adam_kernel sums v fused in its float4
-    body and as two products and an add in its scalar tail (the last n % 4 elements; n = 1 and 3 are all tail); the shared element function spells
-    both forms and takes the tail's from n & ~3 on, on the device and on the host."""
+    """ops.adam_step against an explicit AdamW launch (weight_decay 0, eps 1e-4) over four steps: torch.equal on every element.  Both are the shared
+    kernel today, so this holds the wrapper's arguments to the explicit call's, the grid-stride size included; that the words are the ones Adam's own
+    kernel wrote is the next test's statement."""
     gen = torch.Generator().manual_seed(21)
     p0 = torch.randn(n, generator=gen)
     grads = [torch.randn(n, generator=gen) * 10 ** float(e) for e in (-6, -3, 0, -2)]
@@ -133,6 +139,23 @@ def test_adamw_without_decay_is_fused_adam(n):
         ops.optim_step(L.OPT_ADAMW, pw, g, mw, vw, lr=1e-4, step=t, eps=1e-4, weight_decay=0.0, grad_scale=0.25)
         for a, w, what in ((pa, pw, "p"), (ma, mw, "exp_avg"), (va, vw, "exp_avg_sq")):
             assert torch.equal(a, w), (t, what)
+
+
+@pytest.mark.parametrize("n", [1, 3, 4, 1027])
+def test_adam_step_reproduces_the_words_recorded_from_adams_own_kernel(n):
+    """ops.adam_step -- the shared kernel as AdamW with weight_decay 0 -- against tests/golden/adam_steps.npz (tools/make_adam_fixture.py): p, exp_avg,
+    exp_avg_sq and g after each of five launches, recorded at the last commit at which Adam had its own kernel.  Every word is equal: v fused in the
+    float4 body, two products and an add on the tail (n = 1 and 3 are all tail); the fifth step clears g.  The grid-stride size is
+    test_kernel_is_the_host_function_bit_for_bit[Adam-2098179]'s."""
+    z = np.load(GOLDEN)
+    dev = lambda words: torch.from_numpy(np.ascontiguousarray(words).view(np.float32).copy()).to(DEV)
+    p, m, v = dev(z[f"n{n}_p0"]), torch.zeros(n, device=DEV), torch.zeros(n, device=DEV)
+    for t in range(1, 6):
+        g = dev(z[f"n{n}_grads"][t - 1])
+        ops.adam_step(p, g, m, v, lr=1e-4, step=t, eps=1e-4, grad_scale=0.25, zero_grad=(t == 5))
+        for key, mine in (("p", p), ("m", m), ("v", v), ("g", g)):
+            assert np.array_equal(mine.cpu().view(torch.int32).numpy(), z[f"n{n}_{key}"][t - 1]), (n, t, key)
+    assert not bool(g.any()) and bool(v.any())
 
 
 # ------------------------------------------------------------------------------------------------ 7. the whole step against the oracle

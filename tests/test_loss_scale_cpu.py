@@ -15,7 +15,7 @@ HEADER = os.path.join(ROOT, "include", "mtbc.h")
 
 from multi_task_breast_cancer_amd import _lib as L   # noqa: E402
 
-NEW = ("mtbc_loss_scale_begin", "mtbc_loss_scale_check", "mtbc_loss_scale_adam", "mtbc_loss_scale_update_host", "mtbc_loss_scale_begin_host")
+NEW = ("mtbc_loss_scale_begin", "mtbc_loss_scale_check", "mtbc_loss_scale_optim", "mtbc_loss_scale_update_host", "mtbc_loss_scale_begin_host")
 
 
 @pytest.fixture(scope="module")
@@ -32,11 +32,11 @@ def test_loss_scale_symbols_are_declared_bound_and_exported(lib):
     for name in NEW:
         assert name in declared and name in L.EXPORTS, name
         assert hasattr(lib, name), name
-    assert lib.mtbc_version() == 202 == L.ABI_VERSION           # new symbols and new structs only: no existing layout moved
+    assert lib.mtbc_version() == 203 == L.ABI_VERSION
 
 
 def test_loss_scale_ctypes_layout_matches_header(tmp_path):
-    structs = {"mtbc_loss_scale_state": L.LossScaleState, "mtbc_loss_scale_args": L.LossScaleArgs, "mtbc_adam_args": L.AdamArgs}
+    structs = {"mtbc_loss_scale_state": L.LossScaleState, "mtbc_loss_scale_args": L.LossScaleArgs}
     offs = [("mtbc_loss_scale_state", f, getattr(L.LossScaleState, f).offset) for f, _ in L.LossScaleState._fields_]
     offs += [("mtbc_loss_scale_args", f, getattr(L.LossScaleArgs, f).offset) for f, _ in L.LossScaleArgs._fields_]
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){"]
@@ -97,20 +97,21 @@ def test_update_rule_keeps_a_scale_that_would_grow_to_inf(lib):
     assert st.scale == scale.item() == 2.0 ** 127 and st.growth_tracker == tracker.item() == 0 and st.t == 1
 
 
-def test_begin_scalars_on_the_host_are_mtbc_adam_dynamics(lib):
-    """What `begin` leaves for the Adam launch of step t + 1, evaluated by the shared inline function on the host: bit-equal to mtbc_adam_dynamic (the static
-    path's scalars), with grad_scale = (1 / world) / scale."""
+def test_begin_scalars_on_the_host_are_mtbc_optim_dynamics(lib):
+    """What `begin` leaves for the Adam launch of step t + 1, evaluated by the shared inline function on the host: bit-equal to the first three scalars
+    of mtbc_optim_dynamic (the static path's), with grad_scale = (1 / world) / scale."""
     for t in (0, 1, 2, 9, 99, 999, 11999):
         st = L.LossScaleState()
         st.scale, st.lr, st.t, st.shard_weight = 4096.0, 1e-3, t, 1.0
         a = _args(st, 2.0, 0.5, 2000)
         a.inv_world = 0.5
         assert lib.mtbc_loss_scale_begin_host(C.byref(a)) == 0
-        ad = L.AdamArgs()
+        ad = L.OptimArgs()
+        ad.kind, ad.weight_decay = L.OPT_ADAMW, 0.0
         ad.lr, ad.beta1, ad.beta2, ad.eps, ad.grad_scale, ad.step = 1e-3, 0.9, 0.999, 1e-4, 0.5 / 4096.0, t + 1
-        out = (C.c_float * 3)()
-        assert lib.mtbc_adam_dynamic(C.byref(ad), C.byref(out)) == 0
-        assert list(st.adam) == list(out), (t, list(st.adam), list(out))
+        out = (C.c_float * 4)()
+        assert lib.mtbc_optim_dynamic(C.byref(ad), C.byref(out)) == 0
+        assert list(st.adam) == list(out)[:3], (t, list(st.adam), list(out))
         assert st.t == t
 
 

@@ -105,10 +105,11 @@ def test_update_applies_adam_or_skips_it():
             ops.loss_scale_begin(state, gscale, world=world, beta1=b1, beta2=b2)
             h = _read(state)
             assert gscale.item() == 0.75 * scale
-            ad = L.AdamArgs()
+            ad = L.OptimArgs()
+            ad.kind, ad.weight_decay = L.OPT_ADAMW, 0.0
             ad.lr, ad.beta1, ad.beta2, ad.eps, ad.grad_scale, ad.step = lr, b1, b2, eps, (1.0 / world) / scale, t
-            want = (C.c_float * 3)()
-            assert lib.mtbc_adam_dynamic(C.byref(ad), C.byref(want)) == 0
+            want = (C.c_float * 4)()
+            assert lib.mtbc_optim_dynamic(C.byref(ad), C.byref(want)) == 0
             assert h.adam[0] == want[0], (t, world)
             d = [_ulps(h.adam[i], want[i]) for i in (1, 2)]
             if any(d):

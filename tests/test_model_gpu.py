@@ -231,7 +231,7 @@ def test_graph_replayed_steps_are_the_eager_steps(arch, dtype, N, size):
     """FusedTrainStep(graph=True) (the MTBC_GRAPH switch): the step is captured into ONE hipGraph at its third call and replayed afterwards.  Seven steps
     over changing batches, with the learning rate changed in between (a scheduler) and a second batch size appearing mid-way (its own graph), must leave
     the parameters, Adam's moments and the losses bit-identical to the eager, stream-ordered steps: what differs from step to step reaches the replayed
-    kernels through device memory only (mtbc_adam_args.dynamic; the plan's static input buffers).  training_multitask.py:87-103."""
+    kernels through device memory only (mtbc_optim_args.dynamic; the plan's static input buffers).  training_multitask.py:87-103."""
     res = []
     for graph in (False, True):
         seed_everything(1993)

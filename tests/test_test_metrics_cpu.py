@@ -229,7 +229,7 @@ def test_seg_metrics_names_in_header_binding_and_library(lib):
     assert int(re.search(r"#define\s+MTBC_SEGM_COLS\s+(\d+)", src).group(1)) == L.SEGM_COLS
     for name in ("TP", "TN", "FP", "FN", "RAW_PIXELS", "HD_ROWS_SQ", "HD_PX_SQ", "CLS_RAW", "CLS_FINAL"):
         assert int(re.search(rf"#define\s+MTBC_SEGM_{name}\s+(\d+)", src).group(1)) == getattr(L, "SEGM_" + name)
-    assert lib.mtbc_version() == 202 and "MTBC_OP_SEG" not in src                    # additive: no new version, no new op kind
+    assert lib.mtbc_version() == 203 and "MTBC_OP_SEG" not in src                    # additive: no new version, no new op kind
 
 
 def test_seg_metrics_args_layout(tmp_path):

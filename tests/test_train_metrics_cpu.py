@@ -191,7 +191,7 @@ def test_two_ranks_merge_into_the_global_batches_over_gloo():
 def test_export_is_declared_and_bound():
     src = open(os.path.join(ROOT, "include", "mtbc.h")).read()
     assert re.search(r"\bint\s+mtbc_train_metrics\s*\(\s*const\s+mtbc_train_metrics_args\s*\*", src)
-    assert "mtbc_train_metrics" in L.EXPORTS and L.ABI_VERSION == 202
+    assert "mtbc_train_metrics" in L.EXPORTS and L.ABI_VERSION == 203
     # the ctypes mirror against the header's struct, field by field (LP64: pointers and int64_t 8 bytes, 8-byte aligned)
     body = src[src.index("typedef struct {", src.index("training-time metrics")):src.index("} mtbc_train_metrics_args;")]
     names = re.findall(r"(\w+)\s*[;,]", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
