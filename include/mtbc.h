@@ -328,6 +328,19 @@ int mtbc_instnorm_dparam_many(const mtbc_dparam_desc* descs, int32_t n, void* st
 /* workspace bytes the forward can use for planes > 64K elements (chunked statistics: 2 reads + 1 write instead of the
  * streaming kernel's 3 + 1); 0 for smaller planes.  Passing no workspace is valid (streaming kernel). */
 size_t mtbc_instnorm_fwd_workspace(const mtbc_instnorm_args* a);
+/* Plan query: every launch mtbc_instnorm_lrelu_fwd (backward = 0) / mtbc_instnorm_lrelu_bwd (backward != 0) would make for these
+ * arguments, in order and joined with " + ", written to buf (NUL-terminated).  Each kernel is spelled as a profiler spells the instance,
+ * without namespace and argument list; where the dispatcher and not the template chooses the block size, " [threads=256]" follows; a
+ * cooperative (team) launch carries its plan, e.g. "in_bwd_c8_kernel<512, 4, false, true, 2, 0> [T=32 rounds=4] + in_r1_finalize_kernel +
+ * in_dparam_kernel" (T workgroups per team, rounds = items per resident team).  The follow-up launches are named too: in_stats_finalize_kernel,
+ * in_bstats_finalize_kernel, in_r1_finalize_kernel, in_dparam_kernel (absent with defer_dparams: mtbc_instnorm_dparam_many reduces later).
+ * It is the dispatcher of the real call, stopped in front of its launches: launches nothing, never synchronises, never dereferences a
+ * tensor pointer (pointer VALUES are looked at: NULL selects branches, alignment the vector kernels); returns the code the real call
+ * would return when it refuses the arguments, MTBC_E_BADARG for a buffer shorter than the name.  Device access: for planes above 64 x 64
+ * with y8 / dz8 the team plan comes from the occupancy of the kernel on the current device and its CU count, asked once per device as the
+ * launch asks them; without a GPU that plan does not exist and the query returns what the launch would, MTBC_E_UNSUPPORTED.  Everything
+ * else is host arithmetic. */
+int mtbc_instnorm_kernel_name(const mtbc_instnorm_args* a, int32_t backward, char* buf, int32_t len);
 int mtbc_instnorm_lrelu_fwd(const mtbc_instnorm_args* a, void* stream);
 int mtbc_instnorm_lrelu_bwd(const mtbc_instnorm_args* a, void* stream);
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "../../include/mtbc.h"
 
 #define MTBC_WAVE 64
@@ -152,9 +153,28 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return s;
 }
 
+// Which launches an InstanceNorm + LeakyReLU call makes: the kernel instances (family + template arguments), the block size where the
+// dispatcher and not the template fixes it, and the team plan of a cooperative launch.  Every dispatcher of norm.hip / norm_coop.hip
+// fills ONE NormChoice first; its launch code then reads the kernels from it, and mtbc_instnorm_kernel_name() -- the same dispatcher
+// called with `query` -- prints it: the name cannot drift from the launch (KernelChoice of conv3x3.hip).
+enum NormKernel {
+    NK_FWD_C8, NK_BWD_C8,                                   // <THREADS, PPT, F16, COOP, ZC8[, DY8]>
+    NK_STATS_FIN, NK_APPLY_FWD, NK_BSTATS_FIN, NK_APPLY_BWD,      // the streaming passes: <F16, FIN, ZF16, POOL>, <F16, ZF16>
+    NK_R1_FIN, NK_DPARAM,
+    NK_FWD_REG, NK_CHUNK_STATS, NK_CHUNK_APPLY, NK_FWD_STREAM, NK_BWD, NK_BWD_REG      // norm.hip: <VPT>, <VEC>, <VPT, BOTH>
+};
+struct NormLaunch { int k; int t[6]; int threads; int T, rounds; };      // threads > 0: printed as [threads=..]; T > 0: a team launch, [T=.. rounds=..]
+struct NormChoice {
+    static constexpr int MAX = 4;          // (a call makes at most 3 launches today; one more is a programming error)
+    int n; NormLaunch l[MAX];
+    void add(int k, int t0 = 0, int t1 = 0, int t2 = 0, int t3 = 0, int t4 = 0, int t5 = 0) { if (n == MAX) abort(); l[n++] = NormLaunch{k, {t0, t1, t2, t3, t4, t5}, 0, 0, 0}; }
+    void add(const NormLaunch& k) { if (n == MAX) abort(); l[n++] = k; }
+    NormLaunch& last() { return l[n - 1]; }
+};
 // norm_coop.hip: InstanceNorm straight into the 16-bit channel-blocked layout
-extern "C" int mtbc_i_instnorm_fwd_c8(const mtbc_instnorm_args* a, hipStream_t st);
-extern "C" int mtbc_i_instnorm_bwd_c8(const mtbc_instnorm_args* a, float* part, hipStream_t st);
+// query != NULL: validate, append the launches to *query and return without touching the stream
+extern "C" int mtbc_i_instnorm_fwd_c8(const mtbc_instnorm_args* a, hipStream_t st, NormChoice* query);
+extern "C" int mtbc_i_instnorm_bwd_c8(const mtbc_instnorm_args* a, float* part, hipStream_t st, NormChoice* query);
 extern "C" int mtbc_i_instnorm_bwd_c8_team(const mtbc_instnorm_args* a);
 // c8_ops.hip: max-pool and 1x1 conv on 16-bit channel-blocked tensors
 int mtbc_i_maxpool_c8_fwd(const mtbc_maxpool_args* a, hipStream_t st);

@@ -5,6 +5,8 @@
 // Replaces nn.InstanceNorm2d + nn.LeakyReLU (MTnnUNet.py:35-36) and MONAI ADN "NDA" (MTUNetPlusPlus.py:20-22).
 #include "common.h"
 #include <cstdlib>
+#include <cstdio>
+#include <cstring>
 
 namespace {
 
@@ -376,6 +378,39 @@ int fill(const mtbc_instnorm_args* a, InP* p) {
 }
 bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
+
+// "in_bwd_c8_kernel<512, 4, false, true, 2, 0> [T=32 rounds=4]": the instance as a profiler spells it (no namespace, no argument list), the
+// block size where the dispatcher chooses it, the team plan of a cooperative launch; the launches of a call joined with " + "
+struct NormKernelInfo { const char* name; int nargs; unsigned bools; };      // bools: bit i = template argument i is a bool
+constexpr NormKernelInfo NKINFO[] = {
+    {"in_fwd_c8_kernel", 5, 12}, {"in_bwd_c8_kernel", 6, 12},
+    {"in_stats_finalize_kernel", 0, 0}, {"in_apply_fwd_c8_kernel", 4, 15}, {"in_bstats_finalize_kernel", 0, 0}, {"in_apply_bwd_c8_kernel", 2, 3},
+    {"in_r1_finalize_kernel", 0, 0}, {"in_dparam_kernel", 0, 0},
+    {"in_fwd_reg_kernel", 1, 0}, {"in_fwd_chunk_stats_kernel", 0, 0}, {"in_fwd_chunk_apply_kernel", 0, 0}, {"in_fwd_stream_kernel", 0, 0},
+    {"in_bwd_kernel", 1, 1}, {"in_bwd_reg_kernel", 2, 2},
+};
+int norm_choice_name(const NormChoice& ch, char* buf, int len) {
+    char tmp[512];
+    int n = 0;
+    tmp[0] = 0;
+    for (int j = 0; j < ch.n; ++j) {
+        const NormLaunch& k = ch.l[j];
+        const NormKernelInfo& f = NKINFO[k.k];
+        n += snprintf(tmp + n, sizeof tmp - n, "%s%s", j ? " + " : "", f.name);
+        for (int i = 0; i < f.nargs; ++i) {
+            const char* sep = i ? ", " : "<";
+            if (f.bools >> i & 1) n += snprintf(tmp + n, sizeof tmp - n, "%s%s", sep, k.t[i] ? "true" : "false");
+            else n += snprintf(tmp + n, sizeof tmp - n, "%s%d", sep, k.t[i]);
+        }
+        if (f.nargs) n += snprintf(tmp + n, sizeof tmp - n, ">");
+        if (k.threads > 0) n += snprintf(tmp + n, sizeof tmp - n, " [threads=%d]", k.threads);
+        if (k.T > 0) n += snprintf(tmp + n, sizeof tmp - n, " [T=%d rounds=%d]", k.T, k.rounds);
+    }
+    if (!buf || len <= n) return MTBC_E_BADARG;
+    memcpy(buf, tmp, (size_t)n + 1);
+    return MTBC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -388,32 +423,45 @@ size_t mtbc_instnorm_fwd_workspace(const mtbc_instnorm_args* a) {
     return (size_t)a->N * a->C * cdiv64(n4, IN_CHUNK4) * 3 * sizeof(float);
 }
 
-int mtbc_instnorm_lrelu_fwd(const mtbc_instnorm_args* a, void* stream) {
-    if (a && a->y8) return mtbc_i_instnorm_fwd_c8(a, (hipStream_t)stream);
+// query != NULL: validate, fill in the launches and return without touching the device (mtbc_instnorm_kernel_name)
+static int norm_fwd(const mtbc_instnorm_args* a, hipStream_t st, NormChoice* query) {
+    if (a && a->y8) return mtbc_i_instnorm_fwd_c8(a, st, query);
     InP p; int rc = fill(a, &p); if (rc) return rc;
     if (!p.z || (!p.y && !p.y16) || !p.mean || !p.rstd) return MTBC_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
     const int planes = a->N * a->C, HW = p.HW, n4 = HW / 4;
     const bool vec = HW % 4 == 0 && al16(p.z) && (p.y16 ? (reinterpret_cast<uintptr_t>(p.y16) & 7) == 0 : al16(p.y) && p.ybs % 4 == 0);
     if (p.y16 && !(vec && n4 <= 16 * 1024)) return MTBC_E_UNSUPPORTED;
+    NormChoice ch{};
     if (vec && n4 <= 16 * 1024) {
-        if (n4 <= 64) hipLaunchKernelGGL(in_fwd_reg_kernel<1>, dim3(planes), dim3(64), 0, st, p);
-        else if (n4 <= 4 * 64) hipLaunchKernelGGL(in_fwd_reg_kernel<4>, dim3(planes), dim3(64), 0, st, p);
-        else if (n4 <= 4 * 256) hipLaunchKernelGGL(in_fwd_reg_kernel<4>, dim3(planes), dim3(256), 0, st, p);
-        else if (n4 <= 16 * 256) hipLaunchKernelGGL(in_fwd_reg_kernel<16>, dim3(planes), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(in_fwd_reg_kernel<16>, dim3(planes), dim3(1024), 0, st, p);
+        if (n4 <= 64) { ch.add(NK_FWD_REG, 1); ch.last().threads = 64; }
+        else if (n4 <= 4 * 64) { ch.add(NK_FWD_REG, 4); ch.last().threads = 64; }
+        else if (n4 <= 4 * 256) { ch.add(NK_FWD_REG, 4); ch.last().threads = 256; }
+        else if (n4 <= 16 * 256) { ch.add(NK_FWD_REG, 16); ch.last().threads = 256; }
+        else { ch.add(NK_FWD_REG, 16); ch.last().threads = 1024; }
     } else if (vec && a->workspace && a->workspace_bytes >= mtbc_instnorm_fwd_workspace(a)) {
-        const int S = cdiv(n4, IN_CHUNK4);
-        float* part = reinterpret_cast<float*>(a->workspace);
-        hipLaunchKernelGGL(in_fwd_chunk_stats_kernel, dim3(planes * S), dim3(1024), 0, st, p, part, S);
-        MTBC_CHECK_LAUNCH();
-        hipLaunchKernelGGL(in_fwd_chunk_apply_kernel, dim3(planes * S), dim3(1024), 0, st, p, part, S);
+        ch.add(NK_CHUNK_STATS); ch.add(NK_CHUNK_APPLY);
     } else {
-        hipLaunchKernelGGL(in_fwd_stream_kernel, dim3(planes), dim3(HW >= 4096 ? 1024 : 256), 0, st, p);
+        ch.add(NK_FWD_STREAM); ch.last().threads = HW >= 4096 ? 1024 : 256;
     }
-    MTBC_CHECK_LAUNCH();
+    if (query) { for (int i = 0; i < ch.n; ++i) query->add(ch.l[i]); return MTBC_OK; }
+    const int S = cdiv(n4, IN_CHUNK4);
+    float* part = reinterpret_cast<float*>(a->workspace);
+    for (int i = 0; i < ch.n; ++i) {
+        const NormLaunch& k = ch.l[i];
+        const dim3 g(planes);
+        if (k.k == NK_FWD_REG) {
+            const dim3 b(k.threads);
+            if (k.t[0] == 1) hipLaunchKernelGGL(in_fwd_reg_kernel<1>, g, b, 0, st, p);
+            else if (k.t[0] == 4) hipLaunchKernelGGL(in_fwd_reg_kernel<4>, g, b, 0, st, p);
+            else hipLaunchKernelGGL(in_fwd_reg_kernel<16>, g, b, 0, st, p);
+        } else if (k.k == NK_CHUNK_STATS) hipLaunchKernelGGL(in_fwd_chunk_stats_kernel, dim3(planes * S), dim3(1024), 0, st, p, part, S);
+        else if (k.k == NK_CHUNK_APPLY) hipLaunchKernelGGL(in_fwd_chunk_apply_kernel, dim3(planes * S), dim3(1024), 0, st, p, part, S);
+        else hipLaunchKernelGGL(in_fwd_stream_kernel, g, dim3(k.threads), 0, st, p);
+        MTBC_CHECK_LAUNCH();
+    }
     return MTBC_OK;
 }
+int mtbc_instnorm_lrelu_fwd(const mtbc_instnorm_args* a, void* stream) { return norm_fwd(a, (hipStream_t)stream, nullptr); }
 
 int32_t mtbc_instnorm_bwd_team(const mtbc_instnorm_args* a) { return mtbc_i_instnorm_bwd_c8_team(a); }
 
@@ -441,7 +489,7 @@ int mtbc_instnorm_dparam_many(const mtbc_dparam_desc* descs, int32_t n, void* st
     return MTBC_OK;
 }
 
-int mtbc_instnorm_lrelu_bwd(const mtbc_instnorm_args* a, void* stream) {
+static int norm_bwd(const mtbc_instnorm_args* a, hipStream_t st, NormChoice* query) {
     InP p; int rc = fill(a, &p); if (rc) return rc;
     if (!p.z || (!p.dy && !(a->dz8 && (a->dy_rank1 || a->dy_pool))) || (!p.dz && !p.dz16 && !a->dz8) || !p.mean || !p.rstd) return MTBC_E_BADARG;
     if ((a->dy_rank1 || a->dy_pool) && !a->dz8) return MTBC_E_UNSUPPORTED;      // the rank-1 head / pooled terms: channel-group kernels only
@@ -453,16 +501,16 @@ int mtbc_instnorm_lrelu_bwd(const mtbc_instnorm_args* a, void* stream) {
         if (!a->workspace || a->workspace_bytes < (size_t)planes * 3 * sizeof(float)) return MTBC_E_WORKSPACE;
         p.part = reinterpret_cast<float*>(a->workspace);
     }
-    hipStream_t st = (hipStream_t)stream;
     if (a->dz8) {
         const bool epi = a->stats_partial != nullptr;      // reductions from the gathered dgrad's epilogue: no team, no per-member partials
         const int T = epi ? 2 : mtbc_i_instnorm_bwd_c8_team(a);
         if (T < 1) return MTBC_E_UNSUPPORTED;
         if ((want || epi) && (!a->workspace || a->workspace_bytes < (size_t)planes * (3 + T) * sizeof(float))) return MTBC_E_WORKSPACE;
         if (epi && !want) p.part = reinterpret_cast<float*>(a->workspace);
-        rc = mtbc_i_instnorm_bwd_c8(a, want ? p.part : nullptr, st); if (rc) return rc;
+        rc = mtbc_i_instnorm_bwd_c8(a, want ? p.part : nullptr, st, query); if (rc) return rc;
         if (a->defer_dparams && (epi || !want)) return MTBC_E_UNSUPPORTED;
         if (want && !a->defer_dparams) {
+            if (query) { query->add(NK_DPARAM); return MTBC_OK; }
             hipLaunchKernelGGL(in_dparam_kernel, dim3(a->C), dim3(64), 0, st, p.part, a->dgamma, a->dbeta,
                                a->dbias_pre, a->N, a->C, a->accumulate_dparams, epi ? nullptr : p.part + (size_t)3 * planes, epi ? 0 : T);
             MTBC_CHECK_LAUNCH();
@@ -476,22 +524,43 @@ int mtbc_instnorm_lrelu_bwd(const mtbc_instnorm_args* a, void* stream) {
     static const bool stream_only = mtbc_probe_set("MTBC_IN_BWD_STREAM");      // A/B switch
     const int vpt = vec ? cdiv(p.HW / 4, threads) : 0;
     if (p.dz16 && !(vec && !stream_only && vpt <= 16)) return MTBC_E_UNSUPPORTED;
+    NormChoice ch{};
     if (vec && !stream_only && vpt <= 16) {
-        const dim3 g(planes), b(threads);
-        if (vpt <= 1) hipLaunchKernelGGL((in_bwd_reg_kernel<1, true>), g, b, 0, st, p);
-        else if (vpt <= 2) hipLaunchKernelGGL((in_bwd_reg_kernel<2, true>), g, b, 0, st, p);
-        else if (vpt <= 4) hipLaunchKernelGGL((in_bwd_reg_kernel<4, true>), g, b, 0, st, p);
-        else if (vpt <= 8) hipLaunchKernelGGL((in_bwd_reg_kernel<8, true>), g, b, 0, st, p);
-        else hipLaunchKernelGGL((in_bwd_reg_kernel<16, false>), g, b, 0, st, p);
-    } else if (vec) hipLaunchKernelGGL(in_bwd_kernel<true>, dim3(planes), dim3(threads), 0, st, p);
-    else hipLaunchKernelGGL(in_bwd_kernel<false>, dim3(planes), dim3(threads), 0, st, p);
-    MTBC_CHECK_LAUNCH();
-    if (want) {
-        hipLaunchKernelGGL(in_dparam_kernel, dim3(a->C), dim3(64), 0, st, p.part, a->dgamma, a->dbeta,
-                           a->dbias_pre, a->N, a->C, a->accumulate_dparams);
+        if (vpt <= 1) ch.add(NK_BWD_REG, 1, true);
+        else if (vpt <= 2) ch.add(NK_BWD_REG, 2, true);
+        else if (vpt <= 4) ch.add(NK_BWD_REG, 4, true);
+        else if (vpt <= 8) ch.add(NK_BWD_REG, 8, true);
+        else ch.add(NK_BWD_REG, 16, false);
+    } else ch.add(NK_BWD, vec);
+    ch.last().threads = threads;
+    if (want) ch.add(NK_DPARAM);
+    if (query) { for (int i = 0; i < ch.n; ++i) query->add(ch.l[i]); return MTBC_OK; }
+    for (int i = 0; i < ch.n; ++i) {
+        const NormLaunch& k = ch.l[i];
+        const dim3 g(planes);
+        if (k.k == NK_BWD_REG) {
+            const dim3 b(k.threads);
+            if (k.t[0] == 1) hipLaunchKernelGGL((in_bwd_reg_kernel<1, true>), g, b, 0, st, p);
+            else if (k.t[0] == 2) hipLaunchKernelGGL((in_bwd_reg_kernel<2, true>), g, b, 0, st, p);
+            else if (k.t[0] == 4) hipLaunchKernelGGL((in_bwd_reg_kernel<4, true>), g, b, 0, st, p);
+            else if (k.t[0] == 8) hipLaunchKernelGGL((in_bwd_reg_kernel<8, true>), g, b, 0, st, p);
+            else hipLaunchKernelGGL((in_bwd_reg_kernel<16, false>), g, b, 0, st, p);
+        } else if (k.k == NK_BWD) {
+            if (k.t[0]) hipLaunchKernelGGL(in_bwd_kernel<true>, g, dim3(k.threads), 0, st, p);
+            else hipLaunchKernelGGL(in_bwd_kernel<false>, g, dim3(k.threads), 0, st, p);
+        } else hipLaunchKernelGGL(in_dparam_kernel, dim3(a->C), dim3(64), 0, st, p.part, a->dgamma, a->dbeta,
+                                  a->dbias_pre, a->N, a->C, a->accumulate_dparams);
         MTBC_CHECK_LAUNCH();
     }
     return MTBC_OK;
+}
+int mtbc_instnorm_lrelu_bwd(const mtbc_instnorm_args* a, void* stream) { return norm_bwd(a, (hipStream_t)stream, nullptr); }
+
+int mtbc_instnorm_kernel_name(const mtbc_instnorm_args* a, int32_t backward, char* buf, int32_t len) {
+    NormChoice ch{};
+    const int rc = backward ? norm_bwd(a, nullptr, &ch) : norm_fwd(a, nullptr, &ch);
+    if (rc) return rc;
+    return norm_choice_name(ch, buf, len);
 }
 
 }  // extern "C"

@@ -843,9 +843,8 @@ template <bool BWD> CoPlan plan_team(int items, int HW, const Var& v, int reserv
 Var var_of(const mtbc_instnorm_args* a) { return Var{a->out16_type == 2, a->z_layout == MTBC_LAYOUT_C8 ? ((a->z_type == 2 && a->out16_type == 1) ? 2 : 1) : 0, a->dy_layout == MTBC_LAYOUT_C8 ? (a->n_dy_extra ? 2 : 1) : 0}; }
 
 template <bool BWD, int THREADS, int PPT, bool COOP>
-void launch_c8(const CoP& p0, int grid, hipStream_t st) {
+void launch_c8(const CoP& p0, const Var& v, int grid, hipStream_t st) {
     CoP p = p0;
-    const Var v{p.f16 != 0, p.z8 ? (p.zf16 && !p.f16 ? 2 : 1) : 0, p.dy8 ? (p.dyx ? 2 : 1) : 0};      // (planar dy: a second planar contribution is a runtime branch)
 #ifdef MTBC_PROBES
     // MTBC_INB_TS=1: phase timestamps of every workgroup (thread 0) of the channel-group backward, printed after the launch
     static const int ts_env = mtbc_probe_int("MTBC_INB_TS", 0);
@@ -877,19 +876,42 @@ void launch_c8(const CoP& p0, int grid, hipStream_t st) {
     }
 #endif
 }
-// one workgroup per item, sized to the plane
-template <bool BWD> void launch_solo(CoP& p, hipStream_t st) {
-    p.T = 1; p.nteams = p.items;
-    if (p.HW <= 64) launch_c8<BWD, 64, 1, false>(p, p.items, st);
-    else if (p.HW <= 256) launch_c8<BWD, 256, 1, false>(p, p.items, st);
-    else if (p.HW <= 1024) launch_c8<BWD, 256, 4, false>(p, p.items, st);
-    else launch_c8<BWD, 1024, 4, false>(p, p.items, st);
+// The channel-group instance of a call: one workgroup per item sized to the plane (`pl` NULL: planes up to 64 x 64), or the team plan
+void choose_c8(NormChoice* ch, bool bwd, int HW, int items, const Var& v, const CoPlan* pl) {
+    int threads, ppt;
+    if (pl) { threads = CO_THREADS; ppt = pl->ppt; }
+    else if (HW <= 64) { threads = 64; ppt = 1; }
+    else if (HW <= 256) { threads = 256; ppt = 1; }
+    else if (HW <= 1024) { threads = 256; ppt = 4; }
+    else { threads = 1024; ppt = 4; }
+    ch->add(bwd ? NK_BWD_C8 : NK_FWD_C8, threads, ppt, v.f16, pl != nullptr, v.zc8, bwd ? v.dy8 : 0);
+    if (pl) { ch->last().T = pl->T; ch->last().rounds = (items + pl->nteams - 1) / pl->nteams; }
 }
-template <bool BWD> void launch_team(CoP& p, const CoPlan& pl, hipStream_t st) {
-    p.T = pl.T; p.nteams = pl.nteams;
-    if (pl.ppt == 4) launch_c8<BWD, CO_THREADS, 4, true>(p, pl.grid, st);
-    else if (pl.ppt == 2) launch_c8<BWD, CO_THREADS, 2, true>(p, pl.grid, st);
-    else launch_c8<BWD, CO_THREADS, 1, true>(p, pl.grid, st);
+// ... and its launch, read back from the choice
+template <bool BWD> void launch_chosen_c8(const NormLaunch& k, CoP& p, const CoPlan& pl, hipStream_t st) {
+    const Var v{k.t[2] != 0, k.t[4], k.t[5]};
+    const int threads = k.t[0], ppt = k.t[1];
+    if (k.t[3]) {
+        p.T = pl.T; p.nteams = pl.nteams;
+        if (ppt == 4) launch_c8<BWD, CO_THREADS, 4, true>(p, v, pl.grid, st);
+        else if (ppt == 2) launch_c8<BWD, CO_THREADS, 2, true>(p, v, pl.grid, st);
+        else launch_c8<BWD, CO_THREADS, 1, true>(p, v, pl.grid, st);
+    } else {
+        p.T = 1; p.nteams = p.items;
+        if (threads == 64) launch_c8<BWD, 64, 1, false>(p, v, p.items, st);
+        else if (threads == 256 && ppt == 1) launch_c8<BWD, 256, 1, false>(p, v, p.items, st);
+        else if (threads == 256) launch_c8<BWD, 256, 4, false>(p, v, p.items, st);
+        else launch_c8<BWD, 1024, 4, false>(p, v, p.items, st);
+    }
+}
+void launch_apply_fwd(const NormLaunch& k, const dim3 g, hipStream_t st, const CoP& p, const float* part, int slots) {
+    const bool f16 = k.t[0], fin = k.t[1], zf16 = k.t[2], pool = k.t[3];
+#define MTBC_AP(F16_, FIN_, ZF_, POOL_) hipLaunchKernelGGL((in_apply_fwd_c8_kernel<F16_, FIN_, ZF_, POOL_>), g, dim3(AP_THREADS), 0, st, p, part, slots)
+#define MTBC_APT(FIN_, POOL_) do { if (f16) MTBC_AP(true, FIN_, true, POOL_); else if (zf16) MTBC_AP(false, FIN_, true, POOL_); else MTBC_AP(false, FIN_, false, POOL_); } while (0)
+    if (pool) { if (fin) MTBC_APT(true, true); else MTBC_APT(false, true); }
+    else { if (fin) MTBC_APT(true, false); else MTBC_APT(false, false); }
+#undef MTBC_APT
+#undef MTBC_AP
 }
 
 }  // namespace
@@ -909,52 +931,39 @@ int mtbc_instnorm_c8_supported(const mtbc_instnorm_args* a, int32_t backward) {
     return pl.ok ? 1 : 0;
 }
 
-int mtbc_i_instnorm_fwd_c8(const mtbc_instnorm_args* a, hipStream_t st) {
+int mtbc_i_instnorm_fwd_c8(const mtbc_instnorm_args* a, hipStream_t st, NormChoice* query) {
     CoP p; int rc = fill_coop(a, &p); if (rc) return rc;
     if ((!p.z && !p.z8) || !p.y8 || !p.mean || !p.rstd || (reinterpret_cast<uintptr_t>(p.y8) & 15)) return MTBC_E_BADARG;
     if (p.y16 && !a->stats_partial) return MTBC_E_UNSUPPORTED;       // 16-bit planes beside y8: the streaming pass only
+    NormChoice ch{};
+    CoPlan pl{false, 0, 0, 0, 0};
+    dim3 g(1);
+    const int planes = a->N * a->C;
     if (a->stats_partial) {         // statistics from the conv epilogue: finalize (one wave per plane) + one streaming pass
         if (!p.z8 || a->stats_slots <= 0) return MTBC_E_BADARG;
-        const int planes = a->N * a->C;
         if (p.py8) {           // the activation's 2 x 2 max-pool written by the same pass (one thread per window)
             if (((a->H | a->W) & 1) || (reinterpret_cast<uintptr_t>(p.py8) & 15)) return MTBC_E_BADARG;
             int gx = cdiv(p.HW / 4, AP_THREADS * 2); if (gx < 1) gx = 1;
-            const dim3 gp(gx, p.items);
-            const bool fin = a->stats_slots <= 64;
-            if (!fin) {
-                hipLaunchKernelGGL(in_stats_finalize_kernel, dim3(cdiv(planes, 4)), dim3(256), 0, st, a->stats_partial, a->stats_slots, a->C, p.HW, a->eps, a->mean, a->rstd, planes);
-                MTBC_CHECK_LAUNCH();
-            }
-#define MTBC_AP(F16_, FIN_, ZF_) hipLaunchKernelGGL((in_apply_fwd_c8_kernel<F16_, FIN_, ZF_, true>), gp, dim3(AP_THREADS), 0, st, p, a->stats_partial, a->stats_slots)
-            if (p.f16) { if (fin) MTBC_AP(true, true, true); else MTBC_AP(true, false, true); }
-            else if (p.zf16) { if (fin) MTBC_AP(false, true, true); else MTBC_AP(false, false, true); }
-            else { if (fin) MTBC_AP(false, true, false); else MTBC_AP(false, false, false); }
-#undef MTBC_AP
-            MTBC_CHECK_LAUNCH();
-            return MTBC_OK;
-        }
-        const dim3 g(cdiv(p.HW, AP_THREADS * AP_PPT), p.items);
-        if (a->stats_slots <= 64) {          // few subsets per plane: every workgroup finalizes its own 8 channels (one launch)
-            if (p.f16) hipLaunchKernelGGL((in_apply_fwd_c8_kernel<true, true, true>), g, dim3(AP_THREADS), 0, st, p, a->stats_partial, a->stats_slots);
-            else if (p.zf16) hipLaunchKernelGGL((in_apply_fwd_c8_kernel<false, true, true>), g, dim3(AP_THREADS), 0, st, p, a->stats_partial, a->stats_slots);
-            else hipLaunchKernelGGL((in_apply_fwd_c8_kernel<false, true, false>), g, dim3(AP_THREADS), 0, st, p, a->stats_partial, a->stats_slots);
-            MTBC_CHECK_LAUNCH();
-            return MTBC_OK;
-        }
-        hipLaunchKernelGGL(in_stats_finalize_kernel, dim3(cdiv(planes, 4)), dim3(256), 0, st, a->stats_partial, a->stats_slots, a->C, p.HW, a->eps, a->mean, a->rstd, planes);
-        MTBC_CHECK_LAUNCH();
-        if (p.f16) hipLaunchKernelGGL((in_apply_fwd_c8_kernel<true, false, true>), g, dim3(AP_THREADS), 0, st, p, a->stats_partial, a->stats_slots);
-        else if (p.zf16) hipLaunchKernelGGL((in_apply_fwd_c8_kernel<false, false, true>), g, dim3(AP_THREADS), 0, st, p, a->stats_partial, a->stats_slots);
-        else hipLaunchKernelGGL((in_apply_fwd_c8_kernel<false, false, false>), g, dim3(AP_THREADS), 0, st, p, a->stats_partial, a->stats_slots);
-        MTBC_CHECK_LAUNCH();
-        return MTBC_OK;
+            g = dim3(gx, p.items);
+        } else g = dim3(cdiv(p.HW, AP_THREADS * AP_PPT), p.items);
+        const bool fin = a->stats_slots <= 64;       // few subsets per plane: every workgroup finalizes its own 8 channels (one launch)
+        if (!fin) ch.add(NK_STATS_FIN);
+        ch.add(NK_APPLY_FWD, p.f16, fin, p.f16 || p.zf16, p.py8 != nullptr);
+    } else if (p.HW <= SOLO_MAX_HW) choose_c8(&ch, false, p.HW, p.items, var_of(a), nullptr);
+    else {
+        if (!p.state) return MTBC_E_BADARG;
+        pl = plan_team<false>(p.items, p.HW, var_of(a), a->coop_reserve_cus);
+        if (!pl.ok) return MTBC_E_UNSUPPORTED;
+        choose_c8(&ch, false, p.HW, p.items, var_of(a), &pl);
     }
-    if (p.HW <= SOLO_MAX_HW) { launch_solo<false>(p, st); MTBC_CHECK_LAUNCH(); return MTBC_OK; }
-    if (!p.state) return MTBC_E_BADARG;
-    const CoPlan pl = plan_team<false>(p.items, p.HW, var_of(a), a->coop_reserve_cus);
-    if (!pl.ok) return MTBC_E_UNSUPPORTED;
-    launch_team<false>(p, pl, st);
-    MTBC_CHECK_LAUNCH();
+    if (query) { for (int i = 0; i < ch.n; ++i) query->add(ch.l[i]); return MTBC_OK; }
+    for (int i = 0; i < ch.n; ++i) {
+        const NormLaunch& k = ch.l[i];
+        if (k.k == NK_STATS_FIN) hipLaunchKernelGGL(in_stats_finalize_kernel, dim3(cdiv(planes, 4)), dim3(256), 0, st, a->stats_partial, a->stats_slots, a->C, p.HW, a->eps, a->mean, a->rstd, planes);
+        else if (k.k == NK_APPLY_FWD) launch_apply_fwd(k, g, st, p, a->stats_partial, a->stats_slots);
+        else launch_chosen_c8<false>(k, p, pl, st);
+        MTBC_CHECK_LAUNCH();
+    }
     return MTBC_OK;
 }
 
@@ -965,7 +974,7 @@ int mtbc_i_instnorm_bwd_c8_team(const mtbc_instnorm_args* a) {
     const CoPlan pl = plan_team<true>(a->N * (a->C / 8), a->H * a->W, var_of(a), a->coop_reserve_cus);
     return pl.ok ? pl.T : 0;
 }
-int mtbc_i_instnorm_bwd_c8(const mtbc_instnorm_args* a, float* part, hipStream_t st) {
+int mtbc_i_instnorm_bwd_c8(const mtbc_instnorm_args* a, float* part, hipStream_t st, NormChoice* query) {
     CoP p; int rc = fill_coop(a, &p); if (rc) return rc;
     if ((!p.z && !p.z8) || (!p.dy && !p.r1 && !p.pg) || !p.dz8 || !p.mean || !p.rstd || (reinterpret_cast<uintptr_t>(p.dz8) & 15)) return MTBC_E_BADARG;
     if (!p.dy && a->dy_layout == MTBC_LAYOUT_C8) return MTBC_E_BADARG;
@@ -980,41 +989,40 @@ int mtbc_i_instnorm_bwd_c8(const mtbc_instnorm_args* a, float* part, hipStream_t
     } else if (a->n_dy_extra != 0) return MTBC_E_BADARG;
     p.part = part;
     const bool head_dw = a->dy_rank1 && a->dy_rank1_dw;
-    const int planes_ = a->N * a->C;
-    int T_ = 1;
-    if (p.HW > SOLO_MAX_HW) { const CoPlan pl0 = plan_team<true>(p.items, p.HW, var_of(a), a->coop_reserve_cus); if (!pl0.ok) return MTBC_E_UNSUPPORTED; T_ = pl0.T; }
+    const int planes = a->N * a->C;
+    CoPlan pl{false, 0, 1, 0, 0};
+    if (p.HW > SOLO_MAX_HW) { pl = plan_team<true>(p.items, p.HW, var_of(a), a->coop_reserve_cus); if (!pl.ok) return MTBC_E_UNSUPPORTED; }
+    const int T_ = pl.T;
     if (head_dw) {       // partials behind the parameter-gradient regions of the workspace: [3 * planes][planes * T] | [planes * T][N * T]
-        const size_t need = ((size_t)planes_ * (3 + 2 * T_) + (size_t)a->N * T_) * sizeof(float);
+        const size_t need = ((size_t)planes * (3 + 2 * T_) + (size_t)a->N * T_) * sizeof(float);
         if (!a->workspace || a->workspace_bytes < need || a->stats_partial) return MTBC_E_WORKSPACE;
-        p.r1dw = reinterpret_cast<float*>(a->workspace) + (size_t)planes_ * (3 + T_);
-        p.r1db = p.r1dw + (size_t)planes_ * T_;
+        p.r1dw = reinterpret_cast<float*>(a->workspace) + (size_t)planes * (3 + T_);
+        p.r1db = p.r1dw + (size_t)planes * T_;
     }
+    NormChoice ch{};
+    float* m12 = nullptr;
     if (a->stats_partial) {         // {sum g, sum g * xhat} from the gathered dgrad's epilogue: finalize + one streaming pass
         if (!p.z8 || !p.dy8 || p.dyx || a->stats_slots <= 0 || !a->workspace || a->workspace_bytes < (size_t)a->N * a->C * 5 * sizeof(float)) return MTBC_E_BADARG;
-        const int planes = a->N * a->C;
-        float* m12 = reinterpret_cast<float*>(a->workspace) + (size_t)3 * planes;
-        hipLaunchKernelGGL(in_bstats_finalize_kernel, dim3(cdiv(planes, 4)), dim3(256), 0, st, a->stats_partial, a->stats_slots, a->C, p.HW, m12, part, planes);
-        MTBC_CHECK_LAUNCH();
-        const dim3 g(cdiv(p.HW, AP_THREADS * AP_PPT), p.items);
-        if (p.f16) hipLaunchKernelGGL((in_apply_bwd_c8_kernel<true, true>), g, dim3(AP_THREADS), 0, st, p, m12);
-        else if (p.zf16) hipLaunchKernelGGL((in_apply_bwd_c8_kernel<false, true>), g, dim3(AP_THREADS), 0, st, p, m12);
-        else hipLaunchKernelGGL((in_apply_bwd_c8_kernel<false, false>), g, dim3(AP_THREADS), 0, st, p, m12);
-        MTBC_CHECK_LAUNCH();
-        return MTBC_OK;
-    }
-    if (p.HW <= SOLO_MAX_HW) {
-        p.part3 = part ? part + (size_t)3 * a->N * a->C : nullptr;
-        launch_solo<true>(p, st); MTBC_CHECK_LAUNCH();
+        m12 = reinterpret_cast<float*>(a->workspace) + (size_t)3 * planes;
+        ch.add(NK_BSTATS_FIN);
+        ch.add(NK_APPLY_BWD, p.f16, p.f16 || p.zf16);
     } else {
-        if (!p.state) return MTBC_E_BADARG;
-        const CoPlan pl = plan_team<true>(p.items, p.HW, var_of(a), a->coop_reserve_cus);
-        if (!pl.ok) return MTBC_E_UNSUPPORTED;
+        if (p.HW > SOLO_MAX_HW && !p.state) return MTBC_E_BADARG;
         p.part3 = part ? part + (size_t)3 * a->N * a->C : nullptr;
-        launch_team<true>(p, pl, st);
-        MTBC_CHECK_LAUNCH();
+        choose_c8(&ch, true, p.HW, p.items, var_of(a), p.HW > SOLO_MAX_HW ? &pl : nullptr);
+        if (head_dw) ch.add(NK_R1_FIN);
     }
-    if (head_dw) {
-        hipLaunchKernelGGL(in_r1_finalize_kernel, dim3(a->C + 1), dim3(64), 0, st, p.r1dw, p.r1db, a->dy_rank1_dw, a->dy_rank1_db, a->N, a->C, T_, a->dy_rank1_accumulate);
+    if (query) { for (int i = 0; i < ch.n; ++i) query->add(ch.l[i]); return MTBC_OK; }
+    for (int i = 0; i < ch.n; ++i) {
+        const NormLaunch& k = ch.l[i];
+        if (k.k == NK_BSTATS_FIN) hipLaunchKernelGGL(in_bstats_finalize_kernel, dim3(cdiv(planes, 4)), dim3(256), 0, st, a->stats_partial, a->stats_slots, a->C, p.HW, m12, part, planes);
+        else if (k.k == NK_APPLY_BWD) {
+            const dim3 g(cdiv(p.HW, AP_THREADS * AP_PPT), p.items);
+            if (k.t[0]) hipLaunchKernelGGL((in_apply_bwd_c8_kernel<true, true>), g, dim3(AP_THREADS), 0, st, p, m12);
+            else if (k.t[1]) hipLaunchKernelGGL((in_apply_bwd_c8_kernel<false, true>), g, dim3(AP_THREADS), 0, st, p, m12);
+            else hipLaunchKernelGGL((in_apply_bwd_c8_kernel<false, false>), g, dim3(AP_THREADS), 0, st, p, m12);
+        } else if (k.k == NK_R1_FIN) hipLaunchKernelGGL(in_r1_finalize_kernel, dim3(a->C + 1), dim3(64), 0, st, p.r1dw, p.r1db, a->dy_rank1_dw, a->dy_rank1_db, a->N, a->C, T_, a->dy_rank1_accumulate);
+        else launch_chosen_c8<true>(k, p, pl, st);
         MTBC_CHECK_LAUNCH();
     }
     return MTBC_OK;

@@ -95,7 +95,8 @@ def conv3x3_case_kernel(op: int, *shape, **mode) -> str:
     return conv3x3_kernel_name(conv3x3_case_args(op, *shape, **mode), op)
 
 
-# (op, instance) of every conv3x3 launch made through the wrappers below while this is a list (the reference tests record what they ran)
+# (op, instance) of every conv3x3 launch -- and (op, launches) of every InstanceNorm call -- made through the wrappers below while this is
+# a list (the reference tests record what they ran)
 launched: Optional[list] = None
 
 
@@ -378,6 +379,122 @@ def conv3x3_wgrad_c8(xs: Sequence["C8"], dz: "C8", w_shape, want_bias: bool = Fa
 
 
 # ------------------------------------------------------------------ instance norm + leaky relu
+def instnorm_kernel_name(a: "L.InstNormArgs", backward: bool) -> str:
+    """Every launch mtbc_instnorm_lrelu_fwd / _bwd would make for `a`, joined with " + ": mtbc_instnorm_kernel_name (launches nothing; planes
+    above 64 x 64 with y8 / dz8 ask the device for the team plan, as the call does); raises what the call would."""
+    buf = C.create_string_buffer(512)
+    L.check(L.load().mtbc_instnorm_kernel_name(C.byref(a), 1 if backward else 0, buf, len(buf)), "instnorm_kernel_name")
+    return buf.value.decode()
+
+
+def instnorm_case_args(backward: bool, N: int, Cc: int, H: int, W: int, ptrs: Optional[dict] = None, compute: int = 0, out: str = "f32",
+                       z: str = "f32", affine: bool = True, eps: float = 1e-5, slope: float = 0.01, reserve_cus: int = 0, stats_slots: int = 0,
+                       planar: bool = False, planar16: bool = False, pool: bool = False, pool_arg: bool = True, chunk_ws: bool = True,
+                       dy: Optional[str] = "f32", n_extra: int = 0, rank1: bool = False, rank1_grads: bool = False, rank1_acc: bool = False,
+                       dbias: bool = False, acc: bool = False, defer: bool = False, inplace: bool = False) -> "L.InstNormArgs":
+    """The argument struct of ONE InstanceNorm + LeakyReLU call, every field the step programs set (engine._conv_cell / _conv_cell_backward).
+    ptrs: field name -> tensor (dy_extra0 .. dy_extra3 for the fan-in); None = distinct 16-byte aligned dummies that nothing may dereference
+    (for instnorm_kernel_name).  compute: 0 = the fp32 kernels of norm.hip, 1 / 2 = out16_type.  out: "f32" planes, "p16" 16-bit planes
+    (y16 / dz16), "c8" channel-blocked (y8 / dz8).  z: "f32" planes, "c8" channel-blocked of the output type, "c8f16" channel-blocked fp16
+    under a bf16 output.  Forward: planar / planar16 = fp32 / 16-bit planes beside y8, stats_slots > 0 = statistics from the conv epilogue,
+    pool (+ pool_arg) = the pooled output (+ argmax codes), chunk_ws = offer the chunked-statistics workspace.  Backward: dy "f32" / "c8" /
+    None, n_extra planar partials, rank1 (+ the head's own gradients, accumulated or not), pool = the routed max-pool gradient, dbias =
+    dbias_pre, acc = accumulate_dparams, defer = defer_dparams, inplace = dz over dy (fp32 planes)."""
+    dummy = iter(range(1 << 20, 1 << 30, 1 << 20))
+
+    def ptr(name):
+        return next(dummy) if ptrs is None else ptrs[name].data_ptr()
+
+    a = L.InstNormArgs()
+    a.N, a.C, a.H, a.W, a.eps, a.slope = N, Cc, H, W, eps, slope
+    a.z, a.mean, a.rstd = ptr("z"), ptr("mean"), ptr("rstd")
+    if affine:
+        a.gamma, a.beta = ptr("gamma"), ptr("beta")
+    a.out16_type, a.coop_reserve_cus = compute, reserve_cus
+    if z != "f32":
+        a.z_layout, a.z_type = L.LAYOUT_C8, (2 if z == "c8f16" else 0)
+    a.y_batch_stride = a.dy_batch_stride = Cc * H * W
+    if stats_slots:
+        a.stats_partial, a.stats_slots = ptr("stats_partial"), stats_slots
+    if out == "c8":
+        a.coop_state = ptr("coop_state")
+    if not backward:
+        if out == "c8":
+            a.y8 = ptr("y8")
+            if planar16:
+                a.y16 = ptr("y16")
+            elif planar:
+                a.y = ptr("y")
+            if pool:
+                a.pool_y8, a.pool_arg = ptr("pool_y8"), (ptr("pool_arg") if pool_arg else None)
+        elif out == "p16":
+            a.y16 = ptr("y16")
+        else:
+            a.y = ptr("y")
+        nb = L.load().mtbc_instnorm_fwd_workspace(C.byref(a))
+        if nb and chunk_ws:
+            a.workspace, a.workspace_bytes = ptr("workspace"), (nb if ptrs is None else ptrs["workspace"].numel() * 4)
+        return a
+    if dy is not None:
+        a.dy = ptr("dy")
+        a.dy_layout = L.LAYOUT_C8 if dy == "c8" else L.LAYOUT_PLANAR
+    a.n_dy_extra = n_extra
+    for k_ in range(n_extra):
+        a.dy_extra[k_] = ptr(f"dy_extra{k_}")
+    if out == "c8":
+        a.dz8 = ptr("dz8")
+    elif out == "p16":
+        a.dz16 = ptr("dz16")
+    else:
+        a.dz = a.dy if inplace else ptr("dz")
+    if rank1:
+        a.dy_rank1, a.dy_rank1_w = ptr("dy_rank1"), ptr("dy_rank1_w")
+        if rank1_grads:
+            a.dy_rank1_dw, a.dy_rank1_db, a.dy_rank1_accumulate = ptr("dy_rank1_dw"), ptr("dy_rank1_db"), int(rank1_acc)
+    if pool:
+        a.dy_pool, a.dy_pool_arg = ptr("dy_pool"), ptr("dy_pool_arg")
+    if affine:
+        a.dgamma, a.dbeta = ptr("dgamma"), ptr("dbeta")
+    if dbias:
+        a.dbias_pre = ptr("dbias_pre")
+    a.accumulate_dparams, a.defer_dparams = int(acc), int(defer)
+    a.workspace, a.workspace_bytes = ptr("workspace"), (N * (Cc + 1) * 262 * 4 if ptrs is None else ptrs["workspace"].numel() * 4)
+    return a
+
+
+def instnorm_case_kernel(backward: bool, *shape, **mode) -> str:
+    """instnorm_kernel_name of instnorm_case_args(backward, *shape, **mode)."""
+    return instnorm_kernel_name(instnorm_case_args(backward, *shape, **mode), backward)
+
+
+def _note_norm(a, backward: bool) -> None:
+    if launched is not None:
+        launched.append((L.OP_IN_BWD if backward else L.OP_IN_FWD, instnorm_kernel_name(a, backward)))
+
+
+def instnorm_launch(a: "L.InstNormArgs", backward: bool) -> None:
+    """mtbc_instnorm_lrelu_fwd / _bwd on the current stream for an argument struct of instnorm_case_args(ptrs=...)."""
+    _note_norm(a, backward)
+    lib = L.load()
+    L.check((lib.mtbc_instnorm_lrelu_bwd if backward else lib.mtbc_instnorm_lrelu_fwd)(C.byref(a), _s()), "instnorm_bwd" if backward else "instnorm_fwd")
+
+
+def instnorm_dparam_desc(a: "L.InstNormArgs", part: int):
+    """The descriptor (an array of one) that reduces the partials a backward call with defer_dparams left at address `part` (= its workspace),
+    as the step programs build it (MTBC_OP_IN_DPARAM, engine._conv_cell_backward)."""
+    d = (L.DparamDesc * 1)()
+    d[0].part, d[0].dgamma, d[0].dbeta, d[0].dbias_pre = part, a.dgamma, a.dbeta, a.dbias_pre
+    d[0].N, d[0].C, d[0].T, d[0].accumulate = a.N, a.C, L.load().mtbc_instnorm_bwd_team(C.byref(a)), a.accumulate_dparams
+    return d
+
+
+def instnorm_dparam_many(d) -> None:
+    """mtbc_instnorm_dparam_many over an array of descriptors on the current stream."""
+    if launched is not None:
+        launched.extend((L.OP_IN_DPARAM, "in_dparam_many_kernel") for _ in d)
+    L.check(L.load().mtbc_instnorm_dparam_many(d, len(d), _s()), "instnorm_dparam_many")
+
+
 def instnorm_lrelu_fwd(z, gamma=None, beta=None, eps=1e-5, slope=0.01, out16: int = 0):
     """out16 = 1 (bf16) / 2 (fp16): the activation comes back as 16-bit planes (int16 storage), y16 of the C-ABI."""
     _chk(z, gamma, beta)
@@ -395,6 +512,7 @@ def instnorm_lrelu_fwd(z, gamma=None, beta=None, eps=1e-5, slope=0.01, out16: in
     if nb:
         ws = _ws(nb, z.device)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    _note_norm(a, False)
     L.check(L.load().mtbc_instnorm_lrelu_fwd(C.byref(a), _s()), "instnorm_fwd")
     return y, mean, rstd
 
@@ -418,6 +536,7 @@ def instnorm_lrelu_bwd(z, dy, mean, rstd, gamma=None, beta=None, eps=1e-5, slope
     for k_, t_ in enumerate(dy_extra):
         a.dy_extra[k_] = t_.data_ptr()
     a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    _note_norm(a, True)
     L.check(L.load().mtbc_instnorm_lrelu_bwd(C.byref(a), _s()), "instnorm_bwd")
     return dz, dg, db
 
@@ -435,10 +554,10 @@ def coop_state(dev) -> torch.Tensor:
 
 
 def instnorm_lrelu_fwd_c8(z, gamma=None, beta=None, eps=1e-5, slope=0.01, compute: Optional[int] = None, want_planar: bool = False,
-                          stats: Optional[torch.Tensor] = None, want_pool: bool = False, planar16: bool = False):
+                          stats: Optional[torch.Tensor] = None, want_pool: bool = False, planar16: bool = False, reserve_cus: int = 0):
     """InstanceNorm + LeakyReLU straight into the 16-bit channel-blocked layout (y8 of the C-ABI).  z: fp32 planes, or a
     C8 tensor (z_layout = C8: the conv output of the 16-bit modes).  planar16 (with stats): the planar copy is an int16
-    (N,C,H,W) tensor of the output type (y16 beside y8)."""
+    (N,C,H,W) tensor of the output type (y16 beside y8).  reserve_cus: coop_reserve_cus of the C-ABI."""
     z8 = z if isinstance(z, C8) else None
     if compute is None:         # output type: given, else the type of a channel-blocked z, else bf16
         compute = z8.compute if z8 is not None else 1
@@ -459,7 +578,7 @@ def instnorm_lrelu_fwd_c8(z, gamma=None, beta=None, eps=1e-5, slope=0.01, comput
     if z8 is not None and z8.compute != compute:
         a.z_type = z8.compute           # fp16 z with bf16 outputs
     a.mean, a.rstd = mean.data_ptr(), rstd.data_ptr()
-    a.y8, a.out16_type, a.coop_state = y8.data_ptr(), compute, coop_state(dev).data_ptr()
+    a.y8, a.out16_type, a.coop_state, a.coop_reserve_cus = y8.data_ptr(), compute, coop_state(dev).data_ptr(), reserve_cus
     if stats is not None:       # [N][slots][C][2] from conv3x3_fwd_c8(stats=True)
         a.stats_partial, a.stats_slots = stats.data_ptr(), stats.shape[1]
     yp8 = parg = None
@@ -469,6 +588,7 @@ def instnorm_lrelu_fwd_c8(z, gamma=None, beta=None, eps=1e-5, slope=0.01, comput
         a.pool_y8, a.pool_arg = yp8.data_ptr(), parg.data_ptr()
     if not L.load().mtbc_instnorm_c8_supported(C.byref(a), 0):
         raise L.MtbcError("instnorm_fwd: shape not supported with a channel-blocked output")
+    _note_norm(a, False)
     L.check(L.load().mtbc_instnorm_lrelu_fwd(C.byref(a), _s()), "instnorm_fwd(c8)")
     if want_pool:
         return C8(y8, z.shape, compute), mean, rstd, y, C8(yp8, (N, Cc, H // 2, W // 2), compute), parg
@@ -477,10 +597,10 @@ def instnorm_lrelu_fwd_c8(z, gamma=None, beta=None, eps=1e-5, slope=0.01, comput
 
 def instnorm_lrelu_bwd_c8(z, dy, mean, rstd, gamma=None, beta=None, eps=1e-5, slope=0.01, dbias_pre=None, compute: Optional[int] = None,
                           dy_extra: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None, rank1=None, rank1_grads: bool = False,
-                          pool=None, defer_dparams: bool = False):
+                          pool=None, defer_dparams: bool = False, reserve_cus: int = 0):
     """z / dy: fp32 planes or C8 tensors (z_layout / dy_layout = C8); dy_extra (with a C8 dy only): an fp32 planar partial
     gradient added while loading; rank1 = (dyhead (N,1,H,W), w (C)): the rank-1 gradient term of a one-output 1x1 head (dy may
-    then be None)."""
+    then be None).  reserve_cus: coop_reserve_cus of the C-ABI."""
     zt = z.data if isinstance(z, C8) else z
     dyt = dy.data if isinstance(dy, C8) else dy
     if compute is None:         # output (and channel-blocked dy) type: given, else dy's, else z's, else bf16
@@ -513,7 +633,7 @@ def instnorm_lrelu_bwd_c8(z, dy, mean, rstd, gamma=None, beta=None, eps=1e-5, sl
     if dy_extra is not None:
         a.n_dy_extra = 1
         a.dy_extra[0] = dy_extra.data_ptr()
-    a.dz8, a.out16_type, a.coop_state = dz8.data_ptr(), compute, coop_state(dev).data_ptr()
+    a.dz8, a.out16_type, a.coop_state, a.coop_reserve_cus = dz8.data_ptr(), compute, coop_state(dev).data_ptr(), reserve_cus
     a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
     if stats is not None:       # {sum g, sum g * xhat} partials from conv3x3_fwd_c8(norm=...)
         a.stats_partial, a.stats_slots = stats.data_ptr(), stats.shape[1]
@@ -521,12 +641,10 @@ def instnorm_lrelu_bwd_c8(z, dy, mean, rstd, gamma=None, beta=None, eps=1e-5, sl
         raise L.MtbcError("instnorm_bwd: shape not supported with a channel-blocked output")
     if defer_dparams:           # leave the partials in the workspace, reduce them with the batched entry point afterwards
         a.defer_dparams = 1
+    _note_norm(a, True)
     L.check(L.load().mtbc_instnorm_lrelu_bwd(C.byref(a), _s()), "instnorm_bwd(c8)")
     if defer_dparams:
-        d = (L.DparamDesc * 1)()
-        d[0].part, d[0].dgamma, d[0].dbeta, d[0].dbias_pre = ws.data_ptr(), _p(dg), _p(db), _p(dbias_pre)
-        d[0].N, d[0].C, d[0].T, d[0].accumulate = N, Cc, L.load().mtbc_instnorm_bwd_team(C.byref(a)), 0
-        L.check(L.load().mtbc_instnorm_dparam_many(d, 1, _s()), "instnorm_dparam_many")
+        instnorm_dparam_many(instnorm_dparam_desc(a, ws.data_ptr()))
     if rank1_grads:
         return C8(dz8, z.shape, compute), dg, db, hdw, hdb
     return C8(dz8, z.shape, compute), dg, db

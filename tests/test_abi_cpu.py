@@ -231,3 +231,99 @@ def test_conv3x3_kernel_name_refuses_what_the_call_refuses(lib):
     assert lib.mtbc_conv3x3_kernel_name(C.byref(a), L.OP_CONV3_PACK_FWD, buf, 256) == -2
     assert lib.mtbc_conv3x3_kernel_name(C.byref(a), L.OP_CONV3_FWD, buf, 8) == -2        # shorter than the name
     assert lib.mtbc_conv3x3_kernel_name(None, L.OP_CONV3_FWD, buf, 256) == -2
+
+
+# (backward, N, C, H, W, mode) -> what mtbc_instnorm_kernel_name names: the selection of norm.hip / norm_coop.hip made visible where it needs
+# no device (planes up to 64 x 64 with a channel-blocked output, the streaming passes, the fp32 kernels).  mode: ops.instnorm_case_args
+_IN_BF = dict(compute=1, out="c8", z="c8f16")
+_IN_FP = dict(compute=2, out="c8", z="c8")
+NORM_SELECTION = [
+    # one workgroup per (image, channel group): block sizes at H*W = 64 / 65, 256 / 257, 1024 / 1025, 4096
+    (False, 2, 16, 8, 8, _IN_BF, "in_fwd_c8_kernel<64, 1, false, false, 2>"),
+    (False, 2, 16, 5, 13, _IN_BF, "in_fwd_c8_kernel<256, 1, false, false, 2>"),
+    (False, 2, 16, 16, 16, _IN_BF, "in_fwd_c8_kernel<256, 1, false, false, 2>"),
+    (False, 2, 16, 257, 1, _IN_BF, "in_fwd_c8_kernel<256, 4, false, false, 2>"),
+    (False, 2, 16, 32, 32, _IN_BF, "in_fwd_c8_kernel<256, 4, false, false, 2>"),
+    (False, 2, 16, 25, 41, _IN_BF, "in_fwd_c8_kernel<1024, 4, false, false, 2>"),
+    (False, 2, 16, 64, 64, _IN_BF, "in_fwd_c8_kernel<1024, 4, false, false, 2>"),
+    (True, 2, 16, 8, 8, dict(_IN_BF, dy="c8"), "in_bwd_c8_kernel<64, 1, false, false, 2, 1> + in_dparam_kernel"),
+    (True, 2, 16, 5, 13, dict(_IN_BF, dy="c8"), "in_bwd_c8_kernel<256, 1, false, false, 2, 1> + in_dparam_kernel"),
+    (True, 2, 16, 16, 16, dict(_IN_BF, dy="c8"), "in_bwd_c8_kernel<256, 1, false, false, 2, 1> + in_dparam_kernel"),
+    (True, 2, 16, 257, 1, dict(_IN_BF, dy="c8"), "in_bwd_c8_kernel<256, 4, false, false, 2, 1> + in_dparam_kernel"),
+    (True, 2, 16, 32, 32, dict(_IN_BF, dy="c8"), "in_bwd_c8_kernel<256, 4, false, false, 2, 1> + in_dparam_kernel"),
+    (True, 2, 16, 25, 41, dict(_IN_BF, dy="c8"), "in_bwd_c8_kernel<1024, 4, false, false, 2, 1> + in_dparam_kernel"),
+    (True, 2, 16, 64, 64, dict(_IN_BF, dy="c8"), "in_bwd_c8_kernel<1024, 4, false, false, 2, 1> + in_dparam_kernel"),
+    # var_of: ZC8 = 0 fp32 planar z, 1 channel-blocked of the output's type, 2 channel-blocked fp16 under a bf16 output;
+    #         DY8 = 0 fp32 planar dy, 1 channel-blocked, 2 channel-blocked + an fp32 planar partial
+    (False, 2, 16, 16, 16, dict(compute=1, out="c8"), "in_fwd_c8_kernel<256, 1, false, false, 0>"),
+    (False, 2, 16, 16, 16, dict(compute=1, out="c8", z="c8"), "in_fwd_c8_kernel<256, 1, false, false, 1>"),
+    (False, 2, 16, 16, 16, dict(compute=2, out="c8"), "in_fwd_c8_kernel<256, 1, true, false, 0>"),
+    (False, 2, 16, 16, 16, _IN_FP, "in_fwd_c8_kernel<256, 1, true, false, 1>"),
+    (True, 2, 16, 16, 16, dict(compute=1, out="c8", affine=False), "in_bwd_c8_kernel<256, 1, false, false, 0, 0>"),
+    (True, 2, 16, 16, 16, dict(compute=1, out="c8", n_extra=1), "in_bwd_c8_kernel<256, 1, false, false, 0, 0> + in_dparam_kernel"),
+    (True, 2, 16, 16, 16, dict(_IN_BF, dy="c8", n_extra=1), "in_bwd_c8_kernel<256, 1, false, false, 2, 2> + in_dparam_kernel"),
+    (True, 2, 16, 16, 16, dict(_IN_FP, dy="c8", n_extra=1, defer=True), "in_bwd_c8_kernel<256, 1, true, false, 1, 2>"),
+    (True, 2, 16, 16, 16, dict(_IN_FP, dy=None, rank1=True, rank1_grads=True, affine=False, dbias=True),
+     "in_bwd_c8_kernel<256, 1, true, false, 1, 0> + in_r1_finalize_kernel + in_dparam_kernel"),
+    # the streaming passes: every workgroup finalizes its own channels up to 64 pixel subsets, a finalize launch above
+    (False, 2, 16, 64, 64, dict(_IN_BF, stats_slots=64), "in_apply_fwd_c8_kernel<false, true, true, false>"),
+    (False, 2, 16, 64, 64, dict(_IN_BF, stats_slots=65), "in_stats_finalize_kernel + in_apply_fwd_c8_kernel<false, false, true, false>"),
+    (False, 2, 16, 64, 64, dict(_IN_BF, stats_slots=64, pool=True), "in_apply_fwd_c8_kernel<false, true, true, true>"),
+    (False, 2, 16, 64, 64, dict(_IN_BF, stats_slots=65, pool=True, planar16=True), "in_stats_finalize_kernel + in_apply_fwd_c8_kernel<false, false, true, true>"),
+    (False, 2, 16, 512, 512, dict(_IN_FP, stats_slots=4096), "in_stats_finalize_kernel + in_apply_fwd_c8_kernel<true, false, true, false>"),
+    (False, 2, 16, 64, 64, dict(compute=1, out="c8", z="c8", stats_slots=1), "in_apply_fwd_c8_kernel<false, true, false, false>"),
+    (True, 2, 16, 64, 64, dict(_IN_BF, dy="c8", stats_slots=65), "in_bstats_finalize_kernel + in_apply_bwd_c8_kernel<false, true> + in_dparam_kernel"),
+    # the fp32 kernels of norm.hip (H*W % 4 == 0 and 16-byte aligned: the register-resident planes)
+    (False, 2, 5, 16, 16, {}, "in_fwd_reg_kernel<1> [threads=64]"),
+    (False, 2, 5, 32, 32, {}, "in_fwd_reg_kernel<4> [threads=64]"),
+    (False, 2, 5, 64, 64, {}, "in_fwd_reg_kernel<4> [threads=256]"),
+    (False, 2, 5, 128, 128, {}, "in_fwd_reg_kernel<16> [threads=256]"),
+    (False, 2, 5, 256, 256, {}, "in_fwd_reg_kernel<16> [threads=1024]"),
+    (False, 2, 5, 256, 256, dict(compute=1, out="p16"), "in_fwd_reg_kernel<16> [threads=1024]"),
+    (False, 2, 5, 512, 512, {}, "in_fwd_chunk_stats_kernel + in_fwd_chunk_apply_kernel"),
+    (False, 2, 5, 512, 512, dict(chunk_ws=False), "in_fwd_stream_kernel [threads=1024]"),
+    (False, 2, 5, 7, 9, {}, "in_fwd_stream_kernel [threads=256]"),
+    (True, 2, 5, 16, 16, {}, "in_bwd_reg_kernel<1, true> [threads=64] + in_dparam_kernel"),
+    (True, 2, 5, 32, 32, dict(inplace=True), "in_bwd_reg_kernel<1, true> [threads=256] + in_dparam_kernel"),
+    (True, 2, 5, 64, 64, dict(affine=False), "in_bwd_reg_kernel<4, true> [threads=256]"),
+    (True, 2, 5, 64, 64, dict(affine=False, dbias=True, n_extra=2), "in_bwd_reg_kernel<4, true> [threads=256] + in_dparam_kernel"),
+    (True, 2, 5, 128, 128, {}, "in_bwd_reg_kernel<4, true> [threads=1024] + in_dparam_kernel"),
+    (True, 2, 5, 128, 256, {}, "in_bwd_reg_kernel<8, true> [threads=1024] + in_dparam_kernel"),
+    (True, 2, 5, 256, 256, dict(compute=2, out="p16"), "in_bwd_reg_kernel<16, false> [threads=1024] + in_dparam_kernel"),
+    (True, 2, 5, 512, 512, {}, "in_bwd_kernel<true> [threads=1024] + in_dparam_kernel"),
+    (True, 2, 5, 7, 9, {}, "in_bwd_kernel<false> [threads=64] + in_dparam_kernel"),
+]
+
+
+@pytest.mark.parametrize("backward,N,Cc,H,W,mode,want", NORM_SELECTION)
+def test_instnorm_kernel_selection(lib, backward, N, Cc, H, W, mode, want):
+    """mtbc_instnorm_kernel_name (the dummy tensor pointers are never dereferenced) names every launch of a call; a change of the
+    selection shows up here, in review."""
+    from multi_task_breast_cancer_amd import ops
+    assert ops.instnorm_case_kernel(backward, N, Cc, H, W, **mode) == want
+
+
+def test_instnorm_kernel_name_refuses_what_the_call_refuses(lib):
+    from multi_task_breast_cancer_amd import ops
+    buf = C.create_string_buffer(512)
+    name = lambda a, b: lib.mtbc_instnorm_kernel_name(C.byref(a), b, buf, 512)      # noqa: E731
+    assert name(ops.instnorm_case_args(False, 2, 12, 16, 16, **_IN_BF), 0) == -2                           # C % 8
+    assert name(ops.instnorm_case_args(True, 2, 12, 16, 16, **dict(_IN_BF, dy="c8")), 1) == -5             # ... backward: no team size
+    assert name(ops.instnorm_case_args(False, 2, 16, 16, 16, **dict(_IN_BF, planar16=True)), 0) == -5      # y16 beside y8 without stats_partial
+    assert name(ops.instnorm_case_args(False, 2, 16, 16, 16, **dict(_IN_BF, planar16=True, stats_slots=4)), 0) == 0
+    assert name(ops.instnorm_case_args(True, 2, 16, 16, 16, **dict(_IN_BF, dy="c8", rank1=True, stats_slots=4)), 1) == -5      # rank-1 with stats_partial
+    assert name(ops.instnorm_case_args(True, 2, 16, 16, 16, **dict(_IN_BF, dy="c8", pool=True, stats_slots=4)), 1) == -5
+    assert name(ops.instnorm_case_args(True, 2, 16, 16, 16, **dict(_IN_BF, dy=None)), 1) == -2             # no gradient at all
+    assert name(ops.instnorm_case_args(True, 2, 16, 16, 16, **dict(_IN_BF, dy="c8", affine=False, defer=True)), 1) == -5       # nothing to defer
+    assert name(ops.instnorm_case_args(True, 2, 5, 16, 16, **dict(defer=True)), 1) == -5                   # the fp32 kernels do not defer
+    assert name(ops.instnorm_case_args(True, 2, 5, 16, 16, **dict(rank1=True)), 1) == -5                   # rank-1 without dz8
+    a = ops.instnorm_case_args(True, 2, 16, 16, 16, **dict(_IN_BF, dy="c8"))
+    a.workspace_bytes = 2 * 16 * 4 * 4 - 4                                                                 # one float short of N*C*(3 + T)
+    assert name(a, 1) == -3
+    a = ops.instnorm_case_args(False, 2, 16, 16, 16, **_IN_BF)
+    assert name(a, 0) == 0 and buf.value == b"in_fwd_c8_kernel<256, 1, false, false, 2>"
+    assert lib.mtbc_instnorm_kernel_name(C.byref(a), 0, buf, 8) == -2                                      # shorter than the name
+    assert lib.mtbc_instnorm_kernel_name(None, 0, buf, 512) == -1 and lib.mtbc_instnorm_kernel_name(None, 1, buf, 512) == -1
+    import torch
+    if not torch.cuda.is_available():          # planes above 64 x 64: the team plan needs the device, as the launch does
+        assert name(ops.instnorm_case_args(False, 2, 24, 256, 256, **_IN_BF), 0) == -5

@@ -1,5 +1,7 @@
 """Per-op parity of the HIP kernels (through the C-ABI) against the same torch op on the CPU in fp32.
 Tolerances are written per test; integer results are bit-exact."""
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -1534,3 +1536,481 @@ def test_step_programs_launch_only_reference_tested_conv3x3_instances():
         del st, step, model
         torch.cuda.empty_cache()
     assert not missing, f"conv3x3 instances of the step programs that no element-wise reference test launches: {missing}"
+
+
+# ------------------------------------------------------------------ the InstanceNorm + LeakyReLU launches of the step programs, element by element
+def _instnorm_key(a, backward):
+    """Coverage key of ONE mtbc_instnorm_lrelu_fwd / _bwd call: the launches mtbc_instnorm_kernel_name plans (kernel instances, block sizes,
+    team size T; the number of rounds only as 1 or >1) + the branches the ARGUMENTS select inside those kernels.  The only place that
+    decides what "the same launch" means for the guard below."""
+    name = re.sub(r"rounds=(\d+)", lambda m: "rounds=1" if m.group(1) == "1" else "rounds>1", ops.instnorm_kernel_name(a, backward))
+    c8 = bool(a.dz8 if backward else a.y8)
+    f = []
+    if a.gamma and a.beta:
+        f.append("affine")
+    else:
+        f += [n for n in ("gamma", "beta") if getattr(a, n)]
+    if not backward:
+        if a.y16:                             # (beside y8: the 16-bit planes of the streaming pass; without y8: norm.hip in_fwd_reg_kernel `if (p.y16)`, in_cvt4)
+            f.append("y16")
+        if c8:
+            f += [n for n in ("pool_y8", "pool_arg") if getattr(a, n)]
+            if a.y and not a.y16:             # (norm_coop.hip fill_coop: `if (p->y16) p->y = nullptr`)
+                f.append("y")
+        # without y8: `y` is the output itself when y16 is NULL, and no kernel of norm.hip reads pool_y8 / pool_arg (norm.hip fill() copies neither into InP)
+        return name, tuple(f)
+    if not a.dy:
+        f.append("dy=NULL")
+    if a.n_dy_extra:
+        f.append(f"dy_extra={a.n_dy_extra}")
+    if a.dy_rank1:
+        f.append("rank1")
+        if a.dy_rank1_dw:
+            f.append("rank1_dw")
+            f += ["rank1_acc"] if a.dy_rank1_accumulate else []       # (read by in_r1_finalize_kernel only)
+            f += [] if a.dy_rank1_db else ["rank1_db=NULL"]
+    if a.dy_pool:
+        f.append("dy_pool")
+    f += [n for n in ("dgamma", "dbeta", "dbias_pre") if getattr(a, n)]
+    if a.accumulate_dparams and (a.dgamma or a.dbeta or a.dbias_pre) and not a.defer_dparams:
+        f.append("acc")                       # (with defer_dparams the flag is read by the MTBC_OP_IN_DPARAM descriptor only: _dparam_key)
+    if a.defer_dparams:
+        f.append("defer")
+    if a.dz16 and not a.dz8:                  # (norm.hip in_bwd_reg_kernel `if (p.dz16)`, in_cvt4; with dz8 norm_coop.hip fill_coop never copies a->dz16 into CoP)
+        f.append("dz16")
+    # dz in place over dy: only the fp32 kernels of norm.hip write `dz` (norm_coop.hip fill_coop never copies a->dz into CoP; with dz16
+    # norm.hip in_bwd_reg_kernel stores through p.dz16 and never through d4)
+    if a.dz and a.dz == a.dy and not a.dz8 and not a.dz16:
+        f.append("inplace")
+    return name, tuple(f)
+
+
+def _dparam_key(d):
+    """Coverage key of one descriptor of mtbc_instnorm_dparam_many (MTBC_OP_IN_DPARAM: the deferred parameter-gradient reduction)."""
+    return "in_dparam_many_kernel", tuple([n for n in ("dgamma", "dbeta", "dbias_pre") if getattr(d, n)] + [f"T={d.T}"] + (["acc"] if d.accumulate else []))
+
+
+def _program_instnorm_keys(arch, dtype, N, size, reserve_cus=0):
+    """Builds (does not run) one step program with bench.py's constructor path: {(op kind, key): (N, C, H, W) of one op that has it}."""
+    from multi_task_breast_cancer_amd.experiment_init import init_multitask_model, init_optimizer
+    from multi_task_breast_cancer_amd.miscellany import seed_everything
+    from multi_task_breast_cancer_amd.trainer import FusedTrainStep
+    L = ops.L
+    seed_everything(1993)
+    model = init_multitask_model(arch, sequences=1, regions=1, n_classes=3, deep_supervision=True).to(DEV)
+    model.set_compute(dtype)
+    model.coop_reserve_cus = reserve_cus          # what a data-parallel FusedTrainStep sets (trainer.py)
+    step = FusedTrainStep(model, init_optimizer(model, "Adam", 1e-4), alpha=0.5, inversely_weighted=True)
+    st = step._compiled(N, size, size)
+    seen = {}
+    for prog in st.programs.values():
+        for i in range(getattr(prog, "n", 0)):
+            op = prog.array[i]
+            if op.kind in (L.OP_IN_FWD, L.OP_IN_BWD):
+                a = op.u.inorm
+                seen.setdefault((op.kind, _instnorm_key(a, op.kind == L.OP_IN_BWD)), (a.N, a.C, a.H, a.W))
+            elif op.kind == L.OP_IN_DPARAM:
+                seen.setdefault((op.kind, _dparam_key(op.u.dparam)), (op.u.dparam.N, op.u.dparam.C))
+    del st, step, model
+    torch.cuda.empty_cache()
+    return seen
+
+
+def _bits16(t, st):
+    """fp32 / fp64 values -> int16 storage of their rounding (to nearest even) to the 16-bit type st (1 bf16, 2 fp16)."""
+    return (t.float().bfloat16() if st == 1 else t.float().half()).view(torch.int16)
+
+
+def _from16(i, st):
+    """int16 storage of the 16-bit type st -> fp64 values."""
+    return i.contiguous().view(torch.bfloat16 if st == 1 else torch.float16).double()
+
+
+def _c8_of(t, st):
+    """(N,C,H,W) values -> MTBC_LAYOUT_C8 int16 storage [N][C/8][H*W][8], built on the CPU."""
+    N, C, H, W = t.shape
+    return _bits16(t, st).reshape(N, C // 8, 8, H * W).permute(0, 1, 3, 2).contiguous()
+
+
+def _planes_of(i, shape, st):
+    """MTBC_LAYOUT_C8 int16 storage -> fp64 (N,C,H,W)."""
+    N, C, H, W = shape
+    return _from16(i.reshape(N, C // 8, H * W, 8).permute(0, 1, 3, 2).reshape(N, C, H, W), st)
+
+
+def _lrelu64(pre, slope):
+    return torch.where(pre > 0, pre, pre * slope)
+
+
+def _inorm_stats64(z, eps):
+    mean = z.mean((2, 3), keepdim=True)
+    var = ((z - mean) ** 2).mean((2, 3), keepdim=True)          # biased, over H*W
+    return mean, 1.0 / torch.sqrt(var + eps)
+
+
+def _inorm_repair_sign(z, zst, gamma, beta, eps):
+    """The kernels decide `pre > 0` in fp32: an element whose fp64 pre lies within rounding of zero could take the other branch and differ
+    by the factor slope.  Such elements are not masked; the INPUT is moved on the CPU before the launch: while any element has
+    |pre| < 1e-4 (|gamma xhat| + |beta| + 1), it moves away from its plane's mean by one step of its stored type -- or, where that step
+    cannot leave the band (fp32 z: a 2^-20 relative step changes pre by ~1e-6), by 2.5 band widths in units of z -- and the statistics
+    are recomputed.  (gamma is drawn at least 0.25 away from zero, so that step stays a few 1e-3 of the plane's spread.)  At most three
+    passes, none may remain.  Returns the repaired z (fp64, exactly representable in its stored type)."""
+    for npass in range(4):
+        mean, rstd = _inorm_stats64(z, eps)
+        xhat = (z - mean) * rstd
+        band = 1e-4 * ((gamma * xhat).abs() + beta.abs() + 1)
+        bad = (gamma * xhat + beta).abs() < band
+        if not bool(bad.any()):
+            return z
+        if npass == 3:
+            break
+        step = z.abs() * 2.0 ** -20 if zst is None else _ulp16(z, zst)
+        step = torch.maximum(step, 2.5 * band / (gamma.abs() * rstd))
+        away = torch.where(z >= mean, 1.0, -1.0)
+        moved = z + away * step
+        if zst is None:
+            moved = moved.float().double()
+        else:
+            r = _from16(_bits16(moved, zst), zst)
+            moved = torch.where((r - z) * away > 0, r, z + away * _ulp16(z, zst))      # (at least one step of the stored type)
+        z = torch.where(bad, moved, z)
+    raise AssertionError(f"{int(bad.sum())} elements still within rounding of pre = 0 after three repair passes")
+
+
+# One case = ONE mtbc_instnorm_lrelu_fwd / _bwd call (+ the deferred reduction behind it): (backward, N, C, H, W, instnorm_case_args keywords).
+# Shapes: the smallest that reach the key; the team plans (T, rounds) are those mtbc_instnorm_kernel_name reports on an MI355X and are
+# pinned by the guard below through the step programs' own keys, not computed here.
+_BF = dict(compute=1, out="c8", z="c8f16")          # the bf16 mode: conv outputs stored as fp16, everything else bf16
+_FP = dict(compute=2, out="c8", z="c8")             # the fp16 mode
+INORM_CASES = []
+_AFF = dict(affine=True, slope=0.1)            # MTUNetPlusPlus: affine norm, slope 0.1 (MONAI ADN); MTnnUNet: no affine, slope 0.01
+_NOA = dict(affine=False, slope=0.01)
+_DEF = dict(dbias=True, defer=True)            # conv bias gradient from the same pass, parameter gradients reduced later (MTBC_OP_IN_DPARAM)
+# ---- forward, the streaming pass behind the conv epilogue's statistics (every forward launch of the 16-bit step programs).
+#      stats_slots <= 64: FIN (the workgroup finalizes its own channels), above: the finalize launch in front.  Planes of one and of several
+#      workgroups (512 pixels each; 256 windows with the pool), H*W no multiple of either.
+for _m, _shapes in ((_BF, [(2, 16, 12, 20), (3, 8, 24, 36)]), (_FP, [(2, 16, 24, 36), (1, 24, 12, 20)])):
+    for _slots, _hw in ((5, 0), (64, 1), (65, 1), (130, 0)):
+        _N, _C, _H, _W = _shapes[_hw]
+        _st = dict(_m, stats_slots=_slots)
+        INORM_CASES += [
+            (False, _N, _C, _H, _W, dict(_st, **_AFF)),
+            (False, _N, _C, _H, _W, dict(_st, **_AFF, planar=True)),
+            (False, _N, _C, _H, _W, dict(_st, **_AFF, planar16=True)),
+            (False, _N, _C, _H, _W, dict(_st, **_AFF, pool=True)),
+            (False, _N, _C, _H, _W, dict(_st, **_AFF, pool=True, planar16=True)),
+        ]
+        if _m is _BF:
+            INORM_CASES += [
+                (False, _N, _C, _H, _W, dict(_st, **_NOA)),
+                (False, _N, _C, _H, _W, dict(_st, **_NOA, planar=True)),
+                (False, _N, _C, _H, _W, dict(_st, **_NOA, planar16=True)),
+                (False, _N, _C, _H, _W, dict(_st, **_NOA, pool=True)),
+            ]
+INORM_CASES += [
+    (False, 2, 8, 48, 60, dict(_BF, stats_slots=64, **_AFF, pool=True, planar16=True)),       # 2880 pixels: 6 workgroups per plane group, the last one ragged
+    (False, 2, 8, 48, 60, dict(_FP, stats_slots=90, **_AFF, planar16=True)),
+    (False, 1, 8, 8, 8, dict(_BF, stats_slots=1, **_NOA, planar=True)),                        # the deepest level: one subset, a quarter of a workgroup
+    (False, 1, 8, 6, 10, dict(_BF, stats_slots=3, **_NOA, pool=True, pool_arg=False)),         # the pooled output without argmax codes
+]
+# ---- forward, the channel-group kernels computing their own statistics (no step program launches them today; every solo block size, teams on
+#      planes that are no multiple of 2048 pixels: 96 x 96 = 9 slabs of 1024, 96 x 80 = 15 slabs of 512)
+INORM_CASES += [
+    (False, 2, 8, 6, 10, dict(compute=1, out="c8", **_AFF)),
+    (False, 2, 16, 12, 20, dict(_BF, **_AFF, planar=True)),
+    (False, 1, 8, 24, 36, dict(_FP, **_NOA)),
+    (False, 1, 8, 48, 60, dict(compute=1, out="c8", z="c8", **_AFF, planar=True)),
+    (False, 1, 8, 96, 96, dict(_BF, **_AFF, planar=True)),
+    (False, 1, 8, 96, 80, dict(_FP, **_AFF)),
+]
+# ---- forward / backward, the fp32 kernels of norm.hip (the parity mode): every (VPT, block size) the dispatcher chooses, planes that fill the
+#      last block partly.  Backward in place over dy, as the step programs run it.
+_F32B = dict(**_AFF, dbias=True, inplace=True)
+INORM_CASES += [
+    (False, 2, 3, 12, 20, _AFF), (False, 2, 3, 28, 36, _AFF), (False, 2, 3, 60, 68, _AFF), (False, 1, 3, 120, 136, _AFF), (False, 1, 2, 250, 260, _AFF),
+    (True, 2, 3, 12, 20, _F32B), (True, 2, 3, 32, 32, _F32B), (True, 2, 3, 60, 68, _F32B), (True, 1, 3, 128, 128, _F32B), (True, 1, 2, 250, 260, _F32B),
+    (True, 2, 3, 7, 9, dict(**_NOA, n_extra=2)),                     # in_bwd_kernel<false>: H*W % 4 != 0, two more gradient contributions, no parameters
+]
+# ---- backward, one workgroup per (image, channel group): planes up to 64 x 64.  bf16 mode: z stored as fp16 (ZC8 = 2); fp16 mode: ZC8 = 1.
+for _N, _C, _H, _W in ((2, 16, 12, 20), (2, 8, 24, 36), (1, 16, 48, 60)):
+    INORM_CASES += [
+        (True, _N, _C, _H, _W, dict(_BF, **_NOA)),
+        (True, _N, _C, _H, _W, dict(_BF, **_NOA, pool=True)),
+        (True, _N, _C, _H, _W, dict(_BF, **_AFF, **_DEF)),
+    ]
+INORM_CASES += [
+    (True, 2, 8, 24, 36, dict(_BF, **_AFF, **_DEF, pool=True)),
+    (True, 1, 16, 48, 60, dict(_BF, **_AFF, **_DEF, pool=True)),
+    (True, 3, 8, 6, 10, dict(_BF, **_NOA)),
+    (True, 2, 8, 24, 36, dict(_FP, **_AFF, **_DEF)),
+    (True, 1, 16, 48, 60, dict(_FP, **_AFF, **_DEF)),
+    (True, 1, 16, 48, 60, dict(_FP, **_AFF, **_DEF, pool=True)),
+    (True, 2, 8, 24, 36, dict(_BF, **_AFF, dbias=True, acc=True)),                                   # immediate reduction onto prefilled gradients (shared modules)
+    (True, 2, 8, 24, 36, dict(_BF, **_AFF, dy="c8", n_extra=1, rank1=True, rank1_grads=True, rank1_acc=True, pool=True, dbias=True)),      # DY8 = 2, every folded term at once
+    (True, 2, 8, 12, 20, dict(_FP, **_AFF, dy="c8", **_DEF)),                                        # DY8 = 1
+]
+# ---- backward, teams.  reserve_cus leaves one to three teams resident, so that a few items already take several rounds over the mailbox
+#      (the step programs: 96 .. 192 items on 24 teams and fewer); the same instance in one round beside it.
+#      "rounds" (not an argument: the test's expectation of the plan the query reports, 1 or ">1") is asserted after the launch.
+_T32, _T8, _T128 = (1, 16, 256, 256, 240), (2, 24, 128, 128, 248), (1, 16, 512, 512, 192)
+_R1 = dict(rank1=True, rank1_grads=True)
+for _m, _plans in ((_BF, (_T32, _T8)), (_FP, (_T32, _T8, _T128))):
+    for _N, _C, _H, _W, _r in _plans:
+        INORM_CASES += [
+            (True, _N, _C, _H, _W, dict(_m, **_AFF, **_DEF, reserve_cus=_r, rounds=">1")),
+            (True, _N, _C, _H, _W, dict(_m, **_AFF, **_DEF, pool=True, reserve_cus=_r, rounds=">1")),
+        ]
+        if _m is _BF:
+            INORM_CASES += [
+                (True, _N, _C, _H, _W, dict(_m, **_NOA, reserve_cus=_r, rounds=">1")),
+                (True, _N, _C, _H, _W, dict(_m, **_NOA, pool=True, reserve_cus=_r, rounds=">1")),
+            ]
+for _m, (_N, _C, _H, _W, _r) in ((_BF, _T32), (_FP, _T128)):          # the level-0 tensors a one-output 1x1 head reads: its gradient and its own dW / db from the same pass
+    INORM_CASES += [
+        (True, _N, _C, _H, _W, dict(_m, **_AFF, **_DEF, **_R1, reserve_cus=_r, rounds=">1")),
+        (True, _N, _C, _H, _W, dict(_m, **_AFF, **_DEF, **_R1, dy=None, reserve_cus=_r, rounds=">1")),
+    ]
+INORM_CASES += [
+    (True, 1, 16, 256, 256, dict(_BF, **_NOA, **_R1, dy=None, reserve_cus=240, rounds=">1")),
+    (True, 1, 16, 256, 256, dict(_BF, **_AFF, **_DEF, **_R1, rounds=1)),                              # the instance and arguments of the _T32 rank-1 case above, every team resident: ONE round
+    (True, 2, 24, 256, 256, dict(_BF, **_AFF, **_DEF, **_R1, pool=True, rounds=1)),                   # every folded term at once, 6 items in one round
+    (True, 2, 24, 256, 256, dict(_BF, **_AFF, **_DEF, **_R1, pool=True, reserve_cus=64, rounds=1)),   # ... and with the data-parallel reserve
+    (True, 1, 8, 96, 96, dict(_BF, **_AFF, **_DEF, pool=True)),                                       # planes that are no multiple of 2048 pixels
+    (True, 1, 8, 96, 80, dict(_FP, **_AFF, dbias=True, **_R1, rank1_acc=True)),
+]
+# ---- 16-bit PLANES out of the fp32-z kernels of norm.hip (y16 / dz16 without y8 / dz8: what a 16-bit cell runs when the channel-group kernels
+#      do not take its shape): the same instances as the fp32 cases above, stored through in_cvt4
+for _c in (1, 2):
+    INORM_CASES += [
+        (False, 2, 3, 12, 20, dict(compute=_c, out="p16", **_AFF)), (False, 2, 3, 60, 68, dict(compute=_c, out="p16", **_NOA)),
+        (False, 1, 2, 250, 260, dict(compute=_c, out="p16", **_AFF)),
+        (True, 2, 3, 12, 20, dict(compute=_c, out="p16", **_AFF, dbias=True)), (True, 2, 3, 60, 68, dict(compute=_c, out="p16", **_NOA, dbias=True)),
+        (True, 1, 2, 250, 260, dict(compute=_c, out="p16", **_AFF, dbias=True, n_extra=1)),
+    ]
+# ---- backward, the streaming pass behind a gathered dgrad's epilogue sums (no step program launches it today): dbias_pre is exactly zero
+INORM_CASES += [
+    (True, 2, 16, 24, 36, dict(_BF, **_AFF, dy="c8", dbias=True, stats_slots=7)),
+    (True, 1, 8, 48, 60, dict(_FP, **_NOA, dy="c8", dbias=True, stats_slots=70)),
+]
+
+
+def _inorm_case_id(case):
+    b, N, C, H, W, mode = case
+    return ("bwd" if b else "fwd") + f"-{N}x{C}x{H}x{W}-" + ",".join(f"{k}={v}" for k, v in mode.items())
+
+
+def _inorm_args(backward, N, C, H, W, mode, ptrs=None):
+    return ops.instnorm_case_args(backward, N, C, H, W, ptrs=ptrs, **{k: v for k, v in mode.items() if k != "rounds"})
+
+
+def _inorm_case_calls(case):
+    """[(op, launches as mtbc_instnorm_kernel_name plans them, coverage key)] of the calls a case makes, from dummy arguments (nothing is launched)."""
+    backward, N, C, H, W, mode = case
+    a = _inorm_args(backward, N, C, H, W, mode)
+    calls = [(ops.L.OP_IN_BWD if backward else ops.L.OP_IN_FWD, ops.instnorm_kernel_name(a, backward), _instnorm_key(a, backward))]
+    if backward and mode.get("defer"):
+        calls.append((ops.L.OP_IN_DPARAM, "in_dparam_many_kernel", _dparam_key(ops.instnorm_dparam_desc(a, 1 << 20)[0])))
+    return calls
+
+
+@pytest.mark.parametrize("case", INORM_CASES, ids=_inorm_case_id)
+def test_instnorm_step_instances_match_fp64(case):
+    """Every InstanceNorm + LeakyReLU launch of the benchmark's step programs (test_step_programs_launch_only_reference_tested_instnorm_
+    instances) against a plain fp64 computation of the WHOLE fused operation on the CPU, on the stored inputs (z / dy rounded to their 16-bit
+    types where the launch reads 16 bits; mean / rstd of the backward = the fp64 statistics rounded to fp32) -- nothing a HIP kernel computed
+    enters the reference.  Forward: biased statistics over H*W, y = lrelu(gamma xhat + beta), the 2 x 2 max-pool of the STORED y and the first
+    maximum's position.  Backward: g = (dy + dy_extra + w[c] dyhead + routed pool gradient) * (pre > 0 ? 1 : slope),
+    dz = gamma rstd (g - mean g - xhat mean(g xhat)), dgamma = sum g xhat, dbeta = sum g, dbias_pre = sum dz, head dW = sum y_stored dyhead,
+    head db = sum dyhead; "accumulate" adds onto prefilled values; deferred parameter gradients are read after mtbc_instnorm_dparam_many.
+    Bounds: 16-bit stored outputs one unit in the last place of the stored type + 1e-5 x scale, fp32 outputs 1e-5 x scale, argmax codes
+    exact, the parameter gradients as in the tests of the single features; outputs a call does not ask for stay untouched.  `made` is what
+    mtbc_instnorm_kernel_name says for the REAL arguments just before each call (ops.launched), `planned` the same query on the table's entry
+    with dummy pointers: the launches are not observed -- that name and launch agree rests on the dispatchers launching from the NormChoice
+    they print."""
+    backward, N, C, H, W, mode = case
+    L = ops.L
+    compute, out, zkind = mode.get("compute", 0), mode.get("out", "f32"), mode.get("z", "f32")
+    affine, eps, slope = mode.get("affine", True), mode.get("eps", 1e-5), mode.get("slope", 0.01)
+    zst = None if zkind == "f32" else (2 if zkind == "c8f16" else compute)
+    HW, G8 = H * W, C // 8
+    g = _g(N * 7919 + C * 131 + H * 17 + W + 3 * compute + int(backward))
+    rn = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)       # noqa: E731
+    gamma = (1.0 + 0.3 * rn(C)) if affine else torch.ones(C, dtype=torch.float64)
+    gamma = torch.where(gamma.abs() < 0.25, torch.where(gamma < 0, -0.25, 0.25), gamma)       # (the repair step divides by |gamma|)
+    beta = 0.3 * rn(C) if affine else torch.zeros(C, dtype=torch.float64)
+    gamma, beta = gamma.float().double().view(1, C, 1, 1), beta.float().double().view(1, C, 1, 1)
+    z = rn(N, C, H, W) * (0.5 + torch.rand(1, C, 1, 1, generator=g, dtype=torch.float64)) + 0.5 * rn(1, C, 1, 1)
+    z = z.float().double() if zst is None else _from16(_bits16(z, zst), zst)
+    z = _inorm_repair_sign(z, zst, gamma, beta, eps)
+    mean, rstd = _inorm_stats64(z, eps)
+
+    dev = {}            # field name -> device tensor (ops.instnorm_case_args(ptrs=...))
+    nan32 = lambda *s: torch.full(s, float("nan"), dtype=torch.float32, device=DEV)      # noqa: E731
+    nan16 = lambda *s: torch.full(s, -1, dtype=torch.int16, device=DEV)                    # noqa: E731  (0xffff: a NaN of both types)
+    dev["z"] = (z.float() if zst is None else _c8_of(z, zst)).to(DEV)
+    if affine:
+        dev["gamma"], dev["beta"] = gamma.flatten().float().to(DEV), beta.flatten().float().to(DEV)
+    if out == "c8":
+        dev["coop_state"] = ops.coop_state(DEV)
+    oH, oW = H // 2, W // 2
+    pos = ((torch.arange(H) & 1) << 1).view(H, 1) | (torch.arange(W) & 1).view(1, W)       # a pixel's position in its 2 x 2 window
+
+    if not backward:
+        dev["mean"], dev["rstd"] = nan32(N * C), nan32(N * C)
+        slots = mode.get("stats_slots", 0)
+        if slots:       # what the conv epilogue leaves: {sum, sum of squares} of the stored z per (image, pixel subset, channel), fp32
+            parts = torch.tensor_split(z.reshape(N, C, HW), slots, dim=2)
+            dev["stats_partial"] = torch.stack([torch.stack([p_.sum(2), (p_ * p_).sum(2)], dim=2) for p_ in parts], dim=1).float().to(DEV)
+        for name, shape in (("y8", (N, G8, HW, 8)), ("y16", (N, C, H, W)), ("pool_y8", (N, G8, oH * oW, 8)), ("pool_arg", (N, G8, oH * oW))):
+            dev[name] = nan16(*shape)
+        dev["y"] = nan32(N, C, H, W)
+        a = _inorm_args(False, N, C, H, W, mode)           # (dummy pointers: is the chunked-statistics workspace wanted?)
+        dev["workspace"] = torch.empty(max(4, a.workspace_bytes // 4), dtype=torch.float32, device=DEV)
+    else:
+        dev["mean"], dev["rstd"] = mean.flatten().float().to(DEV), rstd.flatten().float().to(DEV)
+        mean, rstd = mean.float().double(), rstd.float().double()       # the backward's inputs are the stored fp32 statistics
+        dykind = mode.get("dy", "f32")
+        gsum = torch.zeros(N, C, H, W, dtype=torch.float64)
+        if dykind is not None:
+            dy = rn(N, C, H, W)
+            dy = _from16(_bits16(dy, compute), compute) if dykind == "c8" else dy.float().double()
+            dev["dy"] = (_c8_of(dy, compute) if dykind == "c8" else dy.float()).to(DEV)
+            gsum += dy
+        for k in range(mode.get("n_extra", 0)):
+            e = (0.5 * rn(N, C, H, W)).float().double()
+            dev[f"dy_extra{k}"] = e.float().to(DEV)
+            gsum += e
+        if mode.get("rank1"):
+            dyh, wh = rn(N, 1, H, W).float().double(), (0.5 * rn(C)).float().double()
+            dev["dy_rank1"], dev["dy_rank1_w"] = dyh.float().to(DEV), wh.float().to(DEV)
+            gsum += wh.view(1, C, 1, 1) * dyh
+            hdw0, hdb0 = rn(C).float(), rn(1).float()               # prefilled: "accumulate" adds onto them, otherwise overwritten
+            dev["dy_rank1_dw"], dev["dy_rank1_db"] = hdw0.to(DEV), hdb0.to(DEV)
+        if mode.get("pool"):
+            pg = rn(N, C, oH, oW).float().double()
+            code = torch.randint(0, 4, (N, C, oH, oW), generator=g)
+            up = lambda t: t.repeat_interleave(2, 2).repeat_interleave(2, 3)       # noqa: E731
+            gsum += torch.where(up(code) == pos, up(pg), torch.zeros((), dtype=torch.float64))
+            packed = (code.reshape(N, G8, 8, oH * oW) << (2 * torch.arange(8)).view(1, 1, 8, 1)).sum(2)
+            dev["dy_pool"], dev["dy_pool_arg"] = pg.float().to(DEV), torch.where(packed >= 32768, packed - 65536, packed).to(torch.int16).to(DEV)
+        dg0, db0, dbp0 = rn(C).float(), rn(C).float(), rn(C).float()
+        dev["dgamma"], dev["dbeta"], dev["dbias_pre"] = dg0.to(DEV), db0.to(DEV), dbp0.to(DEV)
+        dev["dz8"], dev["dz16"], dev["dz"] = nan16(N, G8, HW, 8), nan16(N, C, H, W), nan32(N, C, H, W)
+        dev["workspace"] = torch.empty(N * (C + 1) * 262, dtype=torch.float32, device=DEV)
+
+    if backward and mode.get("stats_slots"):        # what a gathered dgrad's epilogue leaves: {sum g, sum g xhat} per (image, pixel subset, channel), fp32
+        gy_, xh_ = (gsum * torch.where(gamma * ((z - mean) * rstd) + beta > 0, 1.0, slope)).reshape(N, C, HW), ((z - mean) * rstd).reshape(N, C, HW)
+        parts = zip(torch.tensor_split(gy_, mode["stats_slots"], dim=2), torch.tensor_split(xh_, mode["stats_slots"], dim=2))
+        dev["stats_partial"] = torch.stack([torch.stack([g_.sum(2), (g_ * x_).sum(2)], dim=2) for g_, x_ in parts], dim=1).float().to(DEV)
+    a = _inorm_args(backward, N, C, H, W, mode, ptrs=dev)
+    outputs = ("y", "y8", "y16", "pool_y8", "pool_arg") if not backward else ("dz", "dz8", "dz16", "dgamma", "dbeta", "dbias_pre", "dy_rank1_dw", "dy_rank1_db")
+    unasked = {n: dev[n].clone() for n in outputs if n in dev and not getattr(a, n)}        # their pointers are NULL in `a`: nothing may write them
+    ops.launched = []
+    try:
+        ops.instnorm_launch(a, backward)
+        if backward and mode.get("defer"):
+            ops.instnorm_dparam_many(ops.instnorm_dparam_desc(a, dev["workspace"].data_ptr()))
+        torch.cuda.synchronize()
+        made = list(ops.launched)
+    finally:
+        ops.launched = None
+    planned = _inorm_case_calls(case)
+    print(_inorm_case_id(case), "->", made)
+    assert made == [(op, name) for op, name, _ in planned], (made, planned)
+    assert _instnorm_key(a, backward) == planned[0][2]          # the same argument-selected branches as the table's entry
+    assert ops.coop_error(DEV) == 0
+    if "rounds" in mode:        # the plan the case is in the table for
+        rounds = int(re.search(r"rounds=(\d+)", made[0][1]).group(1))
+        assert (rounds == 1) if mode["rounds"] == 1 else (rounds > 1), made[0][1]
+    for n, before in unasked.items():
+        assert torch.equal(dev[n].view(torch.int16), before.view(torch.int16)), f"{n} was not asked for and was written"
+
+    xhat = (z - mean) * rstd
+    pre = gamma * xhat + beta
+    y = _lrelu64(pre, slope)
+
+    def stored16(got, ref, st, what):
+        bound = _ulp16(ref, st) + 1e-5 * ref.abs().max().item()
+        worst = ((got - ref).abs() / bound).max().item()
+        print(f"  {what}: {worst:.3f} x (one ulp of the stored type + 1e-5 x scale)")
+        assert worst <= 1.0, f"{what}: {worst:.3f} x (one ulp of the stored type + 1e-5 x scale)"
+
+    def fp32(got, ref, what):
+        err, scale = (got.double() - ref).abs().max().item(), ref.abs().max().item()
+        print(f"  {what}: max err {err:.3e} vs scale {scale:.3e}")
+        assert err <= 1e-5 * scale, f"{what}: max err {err:.3e} vs scale {scale:.3e}"
+
+    if not backward:
+        _close(dev["mean"], mean.flatten().float(), 1e-5, 1e-5 * max(1.0, z.abs().max().item()), "mean")
+        _close(dev["rstd"], rstd.flatten().float(), 3e-5, 0.0, "rstd")
+        if out == "c8":
+            stored16(_planes_of(dev["y8"].cpu(), (N, C, H, W), compute), y, compute, "y8")
+            if mode.get("planar16"):
+                stored16(_from16(dev["y16"].cpu(), compute), y, compute, "y16")
+            elif mode.get("planar"):
+                fp32(dev["y"].cpu(), y, "y")
+            if mode.get("pool"):
+                win = _from16(_bits16(y, compute), compute).reshape(N, C, oH, 2, oW, 2).permute(0, 1, 2, 4, 3, 5).reshape(N, C, oH, oW, 4)
+                stored16(_planes_of(dev["pool_y8"].cpu(), (N, C, oH, oW), compute), win.max(4).values, compute, "pool_y8")
+                if mode.get("pool_arg", True):
+                    got = (dev["pool_arg"].cpu().int() & 0xffff).view(N, G8, 1, oH * oW) >> (2 * torch.arange(8, dtype=torch.int32)).view(1, 1, 8, 1) & 3
+                    assert torch.equal(got.reshape(N, C, oH, oW).long(), win.argmax(4)), "pool_arg"        # (torch.argmax: the first maximum)
+        elif out == "p16":
+            stored16(_from16(dev["y16"].cpu(), compute), y, compute, "y16")
+        else:
+            fp32(dev["y"].cpu(), y, "y")
+        return
+
+    gy = gsum * torch.where(pre > 0, 1.0, slope)
+    m1, m2 = gy.mean((2, 3), keepdim=True), (gy * xhat).mean((2, 3), keepdim=True)
+    dz = gamma * rstd * (gy - m1 - xhat * m2)
+    if out == "c8":
+        stored16(_planes_of(dev["dz8"].cpu(), (N, C, H, W), compute), dz, compute, "dz8")
+    elif out == "p16":
+        stored16(_from16(dev["dz16"].cpu(), compute), dz, compute, "dz16")
+    else:
+        fp32(dev["dy" if mode.get("inplace") else "dz"].cpu(), dz, "dz")
+    pre_acc = 1.0 if mode.get("acc") else 0.0
+    if affine:
+        dg_ref, db_ref = (gy * xhat).sum((0, 2, 3)) + pre_acc * dg0.double(), gy.sum((0, 2, 3)) + pre_acc * db0.double()
+        _close(dev["dgamma"], dg_ref.float(), 1e-4, 1e-3 * max(1.0, dg_ref.abs().max().item()), "dgamma")
+        _close(dev["dbeta"], db_ref.float(), 1e-4, 1e-3 * max(1.0, db_ref.abs().max().item()), "dbeta")
+    if mode.get("dbias"):
+        if mode.get("stats_slots"):          # in front of a norm the conv-bias gradient is mathematically zero: written as exact zeros
+            assert torch.equal(dev["dbias_pre"].cpu(), torch.zeros(C)), "dbias_pre with stats_partial"
+        ref = dz.sum((0, 2, 3)) + pre_acc * dbp0.double()
+        err, bound = (dev["dbias_pre"].cpu().double() - ref).abs().max().item(), max(1e-3, 1e-6 * dz.abs().sum((0, 2, 3)).max().item())
+        print(f"  dbias_pre: max err {err:.3e}, bound {bound:.3e}")
+        assert err <= bound, f"dbias_pre: max err {err:.3e}, bound {bound:.3e}"
+    if mode.get("rank1") and mode.get("rank1_grads"):
+        r1_acc = 1.0 if mode.get("rank1_acc") else 0.0
+        hdw = (_from16(_bits16(y, compute), compute) * dyh).sum((0, 2, 3)) + r1_acc * hdw0.double()
+        hdb = dyh.sum().view(1) + r1_acc * hdb0.double()
+        _close(dev["dy_rank1_dw"], hdw.float(), 2e-4, 2e-4 * max(1.0, hdw.abs().max().item()), "head dW")
+        _close(dev["dy_rank1_db"], hdb.float(), 2e-4, 2e-4 * max(1.0, hdb.abs().max().item()), "head db")
+
+
+def _reference_tested_instnorm_keys():
+    """(op, key) of every call test_instnorm_step_instances_match_fp64 makes, from its case table."""
+    return {(op, key) for case in INORM_CASES for op, _, key in _inorm_case_calls(case)}
+
+
+def test_step_programs_launch_only_reference_tested_instnorm_instances():
+    """Builds (does not run) the benchmark's four step programs, and the first one as a data-parallel rank builds it (coop_reserve_cus = 64),
+    and computes the coverage key of every MTBC_OP_IN_FWD / _IN_BWD / _IN_DPARAM op: each must be the key of a call that
+    test_instnorm_step_instances_match_fp64 makes.  A plan change -- another instance, team size, a second round, a new argument-selected
+    branch -- that no fp64 case reaches fails here; _instnorm_key / _dparam_key, INORM_CASES and _reference_tested_instnorm_keys are the places to edit."""
+    L = ops.L
+    tested = _reference_tested_instnorm_keys()
+    one, many = ({(k[0].replace(r, "rounds"), k[1]) for _, k in tested if r in k[0]} for r in ("rounds=1", "rounds>1"))
+    assert one & many, "no instance is tested both in one round and in several with the same arguments"
+    missing = {}
+    for (arch, dtype, N, size), reserve in [(p_, 0) for p_ in STEP_PROGRAMS] + [(STEP_PROGRAMS[0], 64)]:
+        seen = _program_instnorm_keys(arch, dtype, N, size, reserve)
+        print(f"{arch} {dtype} N={N} {size}x{size} reserve {reserve}: {len(seen)} keys")
+        assert {L.OP_IN_FWD, L.OP_IN_BWD} <= {op for op, _ in seen}, f"{arch} {dtype}: no InstanceNorm launch found"
+        for (op, key), shape in sorted(seen.items()):
+            if (op, key) not in tested:
+                missing.setdefault((arch, dtype, N, size, reserve), []).append((key, shape))
+    assert not missing, "InstanceNorm launches of the step programs that no fp64 reference case makes: " + \
+        "".join(f"\n  {p_}: {k} at (N, C, H, W) = {s}" for p_, ks in missing.items() for k, s in ks)
