@@ -686,6 +686,34 @@ typedef struct {
 } mtbc_train_metrics_args;
 int mtbc_train_metrics(const mtbc_train_metrics_args* a, void* stream);
 
+/* ---- validation-epoch metrics (training_multitask.py:119-159): mtbc_train_metrics' two launches -- the same pixel kernel and predicate, the
+ * same sample rule, the same cursor, capacity and drop counter, the same integer atomics -- plus the batch's loss words recorded in the row
+ * the call appends.  With the row in range and N > 0, one thread of the samples launch stores
+ *   loss_rows[cursor][0..3] = w * (double)loss_in[0..3]
+ * before the cursor advances: loss_in = the step's [total, seg, cls, nan_flag] words, w = *shard_weight, a word in DEVICE memory that
+ * the host fills in stream order in front of the call (a replayed hipGraph holds fixed arguments and reads the value of the day);
+ * shard_weight == NULL means 1.  Plain stores, no floating-point atomic: bit-reproducible.  With cursor >= capacity nothing is written
+ * anywhere and state[1] counts the call; the empty shard (N == 0 with n_seg == 0) advances the cursor and writes nothing, so with
+ * loss_rows zeroed beforehand (as table, conf and state are) the sum of the ranks' row b is the sum over the ranks that had samples.
+ * MTBC_E_BADARG: a null pointer -- loss_in and loss_rows may be NULL only with N == 0, as the data pointers; MTBC_E_BADSHAPE: as
+ * mtbc_train_metrics.  The first eleven fields are mtbc_train_metrics_args'.                                                       */
+typedef struct {
+    const float* seg_logits;
+    const float* mask;
+    int64_t      n_seg;
+    const float* cls_logits;
+    const float* target;
+    int32_t      N, n_logits;
+    int64_t*     table;
+    int64_t*     conf;
+    int32_t*     state;
+    int32_t      capacity;
+    const float* loss_in;            /* 4 floats: total, seg, cls, nan_flag of the batch */
+    double*      loss_rows;          /* [capacity][4] */
+    const float* shard_weight;       /* device word n_local / n_batch of this rank, or NULL = 1 */
+} mtbc_eval_metrics_args;
+int mtbc_eval_metrics(const mtbc_eval_metrics_args* a, void* stream);
+
 /* ---------------------------------------------------------------------------- step program
  * A training step is a static list of the ops above with every pointer resolved at plan
  * time; mtbc_program_run issues them back-to-back on one stream (no host work in between). */

@@ -173,6 +173,11 @@ class TrainMetricsArgs(C.Structure):
                 ("capacity", C.c_int32)]
 
 
+class EvalMetricsArgs(C.Structure):
+    """mtbc_eval_metrics_args (include/mtbc.h): TrainMetricsArgs' fields, then the loss words."""
+    _fields_ = TrainMetricsArgs._fields_ + [("loss_in", C.c_void_p), ("loss_rows", C.c_void_p), ("shard_weight", C.c_void_p)]
+
+
 BATCH_MAX_LUTS = 4         # MTBC_BATCH_MAX_LUTS of include/mtbc.h
 
 # columns of the mtbc_seg_metrics table -- keep in sync with the MTBC_SEGM_* defines of include/mtbc.h
@@ -284,6 +289,7 @@ EXPORTS = [
     "mtbc_dice_counts", "mtbc_program_run",
     "mtbc_program_run_ms", "mtbc_event_create", "mtbc_event_destroy",
     "mtbc_seg_metrics_workspace_size", "mtbc_seg_metrics", "mtbc_batch_assemble", "mtbc_train_metrics",
+    "mtbc_eval_metrics",
 ]
 
 ABI_VERSION = 203          # MTBC_VERSION of include/mtbc.h these mirrors follow
@@ -408,6 +414,8 @@ def load() -> C.CDLL:
     lib.mtbc_batch_assemble.argtypes = [C.POINTER(BatchArgs), C.c_void_p]
     lib.mtbc_train_metrics.restype = C.c_int
     lib.mtbc_train_metrics.argtypes = [C.POINTER(TrainMetricsArgs), C.c_void_p]
+    lib.mtbc_eval_metrics.restype = C.c_int
+    lib.mtbc_eval_metrics.argtypes = [C.POINTER(EvalMetricsArgs), C.c_void_p]
     _lib = lib
     return lib
 

@@ -16,6 +16,10 @@
 //   launch 2 (samples)  one block: predicted / true class per sample into a 3 x 3 LDS tile, its non-zero cells added to `conf`, N added
 //                       to table[cursor][3], cursor advanced (or, with the row out of range, the drop counter instead of the table).
 // Integer atomics only: bit-reproducible.
+//
+// mtbc_eval_metrics (the validation epoch, training_multitask.py:119-159) is the same two launches with the batch's loss words recorded in the
+// same row: the LOSS instantiation of the samples kernel has its thread 0 store loss_rows[cursor][0..3] = w * (double)loss_in[0..3] -- plain
+// 8-byte vector stores, no floating-point atomic -- before it advances the cursor.  The instantiation mtbc_train_metrics launches carries none of it.
 #include "common.h"
 
 namespace {
@@ -92,10 +96,13 @@ __device__ __forceinline__ int first_argmax(const float* v, int c) {
     return best;
 }
 
+// LOSS: the evaluation call -- loss_in = the plan's [total, seg, cls, nan_flag] words, w = *shard_weight (NULL: 1), loss_rows [capacity][4]
+template <bool LOSS>
 __global__ __launch_bounds__(TM_BLOCK) void train_metrics_samples_kernel(const float* __restrict__ logits, const float* __restrict__ target, int N,
                                                                           int n_logits, unsigned long long* __restrict__ table,
                                                                           unsigned long long* __restrict__ conf, int* __restrict__ state,
-                                                                          int capacity) {
+                                                                          int capacity, const float* __restrict__ loss_in,
+                                                                          double* __restrict__ loss_rows, const float* __restrict__ shard_weight) {
     __shared__ unsigned int tile[9];
     if (threadIdx.x < 9) tile[threadIdx.x] = 0u;
     __syncthreads();
@@ -117,38 +124,62 @@ __global__ __launch_bounds__(TM_BLOCK) void train_metrics_samples_kernel(const f
     if (in_range && threadIdx.x < 9 && tile[threadIdx.x] != 0u) atomicAdd(&conf[threadIdx.x], (unsigned long long)tile[threadIdx.x]);
     if (threadIdx.x == 0) {
         if (N > 0) {
-            if (in_range) atomicAdd(&table[(size_t)cursor * 4 + 3], (unsigned long long)N);
-            else state[1] += 1;
+            if (in_range) {
+                atomicAdd(&table[(size_t)cursor * 4 + 3], (unsigned long long)N);
+                if (LOSS) {                                    // this row is this call's alone: plain stores
+                    const double w = shard_weight ? (double)shard_weight[0] : 1.0;
+                    double* row = loss_rows + (size_t)cursor * 4;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) row[j] = w * (double)loss_in[j];
+                }
+            } else state[1] += 1;
         }
         state[0] = cursor + 1;                                 // the last thing this call does to the cursor: the next call's launches read it
     }
 }
 
-}  // namespace
-
-extern "C" int mtbc_train_metrics(const mtbc_train_metrics_args* a, void* stream) {
-    if (!a || !a->table || !a->conf || !a->state) return MTBC_E_BADARG;
-    if (a->N < 0 || a->n_seg < 0 || a->capacity < 0 || a->n_logits < 1 || a->n_logits > 3) return MTBC_E_BADSHAPE;
-    if ((a->N == 0) != (a->n_seg == 0)) return MTBC_E_BADSHAPE;                  // an empty shard has neither samples nor pixels
-    if (a->N > 0 && (!a->seg_logits || !a->mask || !a->cls_logits || !a->target)) return MTBC_E_BADARG;
+// both entry points: the argument checks they share, the pixels launch, then the samples launch of the caller's instantiation
+template <bool LOSS>
+int launch_metrics(const float* seg_logits, const float* mask, int64_t n_seg, const float* cls_logits, const float* target, int N, int n_logits,
+                   int64_t* table_, int64_t* conf, int32_t* state, int capacity, const float* loss_in, double* loss_rows, const float* shard_weight,
+                   void* stream) {
+    if (!table_ || !conf || !state) return MTBC_E_BADARG;
+    if (N < 0 || n_seg < 0 || capacity < 0 || n_logits < 1 || n_logits > 3) return MTBC_E_BADSHAPE;
+    if ((N == 0) != (n_seg == 0)) return MTBC_E_BADSHAPE;                        // an empty shard has neither samples nor pixels
+    if (N > 0 && (!seg_logits || !mask || !cls_logits || !target)) return MTBC_E_BADARG;
+    if (LOSS && N > 0 && (!loss_in || !loss_rows)) return MTBC_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* table = reinterpret_cast<unsigned long long*>(a->table);
-    if (a->n_seg > 0) {
-        const long long n = (long long)a->n_seg;
+    unsigned long long* table = reinterpret_cast<unsigned long long*>(table_);
+    if (n_seg > 0) {
+        const long long n = (long long)n_seg;
         // memory-bound and small: one unrolled pass per thread before another block is added; past 2^40 pixels a wave's 32-bit counters
         // could wrap
         if (n >= (1ll << 40)) return MTBC_E_BADSHAPE;
         long long blocks = cdiv64(n, (long long)TM_BLOCK * 4 * TM_UNROLL);
         if (blocks > TM_MAX_BLOCKS) blocks = TM_MAX_BLOCKS;
-        const bool vec = (uintptr_t)a->seg_logits % 16 == 0 && (uintptr_t)a->mask % 16 == 0;
-        if (vec) hipLaunchKernelGGL(train_metrics_pixels_kernel<true>, dim3((unsigned)blocks), dim3(TM_BLOCK), 0, st, a->seg_logits, a->mask, n, table,
-                                    (const int*)a->state, a->capacity);
-        else hipLaunchKernelGGL(train_metrics_pixels_kernel<false>, dim3((unsigned)blocks), dim3(TM_BLOCK), 0, st, a->seg_logits, a->mask, n, table,
-                                (const int*)a->state, a->capacity);
+        const bool vec = (uintptr_t)seg_logits % 16 == 0 && (uintptr_t)mask % 16 == 0;
+        if (vec) hipLaunchKernelGGL(train_metrics_pixels_kernel<true>, dim3((unsigned)blocks), dim3(TM_BLOCK), 0, st, seg_logits, mask, n, table,
+                                    (const int*)state, capacity);
+        else hipLaunchKernelGGL(train_metrics_pixels_kernel<false>, dim3((unsigned)blocks), dim3(TM_BLOCK), 0, st, seg_logits, mask, n, table,
+                                (const int*)state, capacity);
         MTBC_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(train_metrics_samples_kernel, dim3(1), dim3(TM_BLOCK), 0, st, a->cls_logits, a->target, a->N, a->n_logits, table,
-                       reinterpret_cast<unsigned long long*>(a->conf), a->state, a->capacity);
+    hipLaunchKernelGGL(train_metrics_samples_kernel<LOSS>, dim3(1), dim3(TM_BLOCK), 0, st, cls_logits, target, N, n_logits, table,
+                       reinterpret_cast<unsigned long long*>(conf), state, capacity, loss_in, loss_rows, shard_weight);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
+}
+
+}  // namespace
+
+extern "C" int mtbc_train_metrics(const mtbc_train_metrics_args* a, void* stream) {
+    if (!a) return MTBC_E_BADARG;
+    return launch_metrics<false>(a->seg_logits, a->mask, a->n_seg, a->cls_logits, a->target, a->N, a->n_logits, a->table, a->conf, a->state,
+                                 a->capacity, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int mtbc_eval_metrics(const mtbc_eval_metrics_args* a, void* stream) {
+    if (!a) return MTBC_E_BADARG;
+    return launch_metrics<true>(a->seg_logits, a->mask, a->n_seg, a->cls_logits, a->target, a->N, a->n_logits, a->table, a->conf, a->state,
+                                a->capacity, a->loss_in, a->loss_rows, a->shard_weight, stream);
 }

@@ -161,6 +161,77 @@ def train_metrics_from_packed(packed: np.ndarray, capacity: int, world: int = 1)
     return train_metrics_from_counts(packed[:cursor * 4].reshape(cursor, 4), packed[capacity * 4:capacity * 4 + 9].reshape(3, 3))
 
 
+# ---- the validation epoch (training_multitask.py:119-159) from what mtbc_eval_metrics appended: pure functions of (table, conf, loss_rows)
+def eval_result_from_counts(table, conf, loss_rows) -> tuple:
+    """The reference's 6-tuple (avg_val_loss, avg_val_dice, val_acc, val_f1, avg_seg_val_loss, avg_cls_val_loss) from one row per (global) batch:
+    `table` (batches, 4) = tp, fp, fn, samples, `conf` (3, 3), `loss_rows` (batches, 4) float64 = total, seg, cls, NaN word.  Losses: summed in row
+    order in float64 and divided by the number of rows -- `val_loss += total_loss.item()` ... `/ len(val_loader)` (:141-153); Dice: `_dice` per row,
+    summed in order, divided likewise (:140, :154).  A non-zero NaN word in any row ends the run as the reference's criterion wrapper does in
+    validation too (criterions.py:72-76): log + exit(1)."""
+    table = np.asarray(table, dtype=np.int64).reshape(-1, 4)
+    conf = np.asarray(conf, dtype=np.int64).reshape(3, 3)
+    loss_rows = np.asarray(loss_rows, dtype=np.float64).reshape(-1, 4)
+    if len(loss_rows) != len(table):
+        raise ValueError(f"{len(table)} count rows but {len(loss_rows)} loss rows")
+    total = seg = cls = dice = 0.0
+    nan = False
+    for (tp, fp, fn, _), (lt, ls, lc, flag) in zip(table.tolist(), loss_rows.tolist()):
+        total += lt
+        seg += ls
+        cls += lc
+        dice += _dice(float(tp), float(fp), float(fn))
+        nan = nan or flag != 0.0
+    if nan:
+        import logging
+        import sys
+        logging.info("NaN in model loss!!")
+        sys.exit(1)
+    nb = len(table)
+    accuracy, f1w = classification_scores(conf.astype(np.float64))
+    if nb == 0:
+        return 0.0, 0.0, accuracy, f1w, 0.0, 0.0
+    return total / nb, dice / nb, accuracy, f1w, seg / nb, cls / nb
+
+
+def reduce_eval_metrics(table: torch.Tensor, conf: torch.Tensor, state: torch.Tensor, loss_rows: torch.Tensor, coop_err: Optional[torch.Tensor] = None,
+                        distributed: bool = False, group=None) -> Tuple[np.ndarray, np.ndarray]:
+    """One rank's accumulators -> TWO host arrays: int64 [table | conf | sum cursor, sum cursor^2, sum dropped, sum coop error word] and float64
+    [loss_rows], each with, under `distributed`, ONE sum-all-reduce in front of its ONE device-to-host read.  The ranks' shards of global batch b
+    sit in row b on every rank: the summed integer row is the global batch's counts exactly, the summed loss row -- each rank's words carry its
+    share n_local / n_batch -- the global batch's mean losses.  The accumulators themselves are not modified."""
+    s = state.to(torch.int64)
+    err = s[0] * 0 if coop_err is None else (coop_err.reshape(-1)[0] != 0).to(torch.int64)
+    packed = torch.cat([table.reshape(-1), conf.reshape(-1), torch.stack([s[0], s[0] * s[0], s[1], err])])
+    losses = loss_rows.reshape(-1)
+    if distributed:
+        import torch.distributed as dist
+        losses = losses.clone()
+        dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(losses, op=dist.ReduceOp.SUM, group=group)
+    return packed.cpu().numpy(), losses.cpu().numpy()
+
+
+def eval_result_from_packed(packed: np.ndarray, losses: np.ndarray, capacity: int, world: int = 1) -> tuple:
+    """`reduce_eval_metrics`' arrays -> the 6-tuple, or MtbcError (and no number) when a cooperative kernel failed on some rank, a batch found the
+    table full or the ranks did not see the same number of batches -- the rule of `train_metrics_from_packed`.  Every rank holds the same sums,
+    so every rank raises (or exits on a NaN word) or none does."""
+    c_sum, c_sq, dropped, err = (int(v) for v in packed[capacity * 4 + 9:capacity * 4 + 13])
+    if err != 0:
+        raise L.MtbcError("cooperative InstanceNorm: a mailbox poll timed out (team members were not co-resident): the "
+                          "activations of this evaluation are invalid")
+    if world * c_sq != c_sum * c_sum:              # Cauchy-Schwarz: equality only when all cursors are equal
+        raise L.MtbcError(f"validation metrics: the ranks appended different numbers of batches (sum {c_sum} over {world} ranks): every rank must "
+                          f"evaluate its shard or call run_empty() once per global batch; rows of the capacity = {capacity} table do not line up")
+    cursor = c_sum // world
+    if dropped != 0 or cursor > capacity:
+        raise L.MtbcError(f"validation metrics: {cursor} batches since reset() but capacity = {capacity} rows "
+                          f"({dropped} dropped): build the FusedEvalStep with a larger capacity")
+    if cursor == 0:
+        raise L.MtbcError("FusedEvalStep.result() before any batch was evaluated")
+    return eval_result_from_counts(packed[:cursor * 4].reshape(cursor, 4), packed[capacity * 4:capacity * 4 + 9].reshape(3, 3),
+                                   np.asarray(losses, dtype=np.float64)[:cursor * 4].reshape(cursor, 4))
+
+
 # ------------------------------------------------------------------------------------------------
 # the fused step (HIP)
 # ------------------------------------------------------------------------------------------------
@@ -539,12 +610,41 @@ class FusedEvalStep:
     the training criterion, and `scheduler.step(val_loss)` runs on that value, training_multitask.py:234-237): with the same
     (alpha, weighting, criterion) the evaluation step shares the training step's compiled plan at equal (N, H, W).  `result()` reads
     everything back once and returns the reference's 6-tuple
-    (avg_val_loss, avg_val_dice, val_acc, val_f1, avg_seg_val_loss, avg_cls_val_loss)."""
+    (avg_val_loss, avg_val_dice, val_acc, val_f1, avg_seg_val_loss, avg_cls_val_loss).
+
+    on_device=True: launches only per batch -- pack -> forward -> losses -> `mtbc_eval_metrics` (two launches), which appends the batch's counts
+    AND its loss words as one row at a device cursor, into buffers this step owns (`capacity` rows, allocated once, never moved); `result()` is one
+    read of an int64 and a float64 array and pure host arithmetic (`eval_result_from_counts`).
+    graph (None: the MTBC_GRAPH switch; needs on_device): that chain replayed as ONE hipGraph from the third call of a compiled step on, by the
+    recipe of `FusedTrainStep._run_graph`; the fills of the batch and of the weight word stay in front of the replay.
+    distributed=True (needs on_device): every rank evaluates ITS shard of each global batch with its share `weight` = n_local / n_batch (a rank
+    with an empty shard calls `run_empty()`), `result()` sum-all-reduces the two arrays once and every rank returns the SAME six numbers: the
+    integer rows sum to the global batch's counts exactly, the weighted loss rows to its mean losses (the criteria allowed here are means over
+    samples, and total is linear in seg and cls).  The step itself issues no collective, so graph=True works under it."""
 
     def __init__(self, model, alpha: float, inversely_weighted: bool = True, n_classes: int = 3,
-                 focal_weight: Optional[torch.Tensor] = None, cls_criterion: str = "Focal", seg_criterion: str = "DICE"):
+                 focal_weight: Optional[torch.Tensor] = None, cls_criterion: str = "Focal", seg_criterion: str = "DICE",
+                 on_device: bool = False, graph: Optional[bool] = None, distributed: bool = False, capacity: int = 4096):
         self.model, self.alpha, self.iw, self.n_classes = model, float(alpha), bool(inversely_weighted), n_classes
-        self.seg_criterion = _check_seg_criterion(seg_criterion, False)      # as `cls_criterion`: the criterion the run trains with
+        self.on_device, self.distributed, self.capacity = bool(on_device), bool(distributed), int(capacity)
+        if self.distributed and not self.on_device:
+            raise ValueError("FusedEvalStep(distributed=True) needs on_device=True: the ranks' rows are merged from the device table")
+        if graph and not self.on_device:
+            raise ValueError("FusedEvalStep(graph=True) needs on_device=True: the default path's per-batch torch ops are not a static launch list")
+        if self.on_device and self.capacity < 1:
+            raise ValueError("capacity must be at least 1 row")
+        self.graph = self.on_device and (_sw.flag("MTBC_GRAPH") if graph is None else bool(graph))
+        self.world = 1
+        if self.distributed:
+            import torch.distributed as dist
+            self.world = dist.get_world_size()
+        self._graphs = {}
+        self._em = None             # device int64 [capacity * 4 + 9]: the table, then the confusion matrix
+        self._em_state = None       # device int32 [2]: cursor, dropped
+        self._em_loss = None        # device float64 [capacity][4]: (weighted) total, seg, cls, NaN word of each batch
+        self._em_weight = None      # device float32 [1]: this rank's share of the batch in flight (read by the kernel; distributed only)
+        self._em_args = {}          # id(compiled step) -> (the step, its mtbc_eval_metrics_args); None -> the empty shard's
+        self.seg_criterion = _check_seg_criterion(seg_criterion, self.distributed)      # as `cls_criterion`: the criterion the run trains with
         self.binary = n_classes == 2
         if cls_criterion not in ("Focal", "CE"):
             raise ValueError(f"unknown classification criterion {cls_criterion!r} (Focal | CE; the binary head always evaluates BCEWithLogits)")
@@ -562,9 +662,14 @@ class FusedEvalStep:
     def reset(self) -> None:
         self._acc = None          # device float64: [sum total, sum seg, sum cls, sum dice, batches]
         self._conf = None         # device int64 (3, 3): rows = ground truth, cols = prediction (f1 is asked for labels 0,1,2)
+        if self._em is not None:  # on_device: zeroed in stream order, outside any replayed graph; the buffers stay where they are
+            self._em.zero_()
+            self._em_state.zero_()
+            self._em_loss.zero_()
 
     @torch.no_grad()
-    def __call__(self, image: torch.Tensor, mask: torch.Tensor, label: torch.Tensor) -> None:
+    def __call__(self, image: torch.Tensor, mask: torch.Tensor, label: torch.Tensor, weight: Optional[float] = None) -> None:
+        """`weight`: this rank's share n_local / n_batch of the global batch (distributed=True; None = 1)."""
         N, _, H, W = image.shape
         st = self._compiled(N, H, W)
         st.x.data.copy_(image, non_blocking=True)
@@ -576,7 +681,10 @@ class FusedEvalStep:
         else:
             st.onehot.zero_()
             st.onehot.scatter_(1, lab.to(torch.int64).view(-1, 1), 1.0)
-        self._evaluate(st, lab.to(torch.int64) if self.binary else None)
+        if self.on_device:
+            self._evaluate_on_device(st, weight)
+        else:
+            self._evaluate(st, lab.to(torch.int64) if self.binary else None)
 
     def _compiled(self, N: int, H: int, W: int):
         return self.model.compiled(N, H, W, fused_loss={"alpha": self.alpha, "inversely_weighted": self.iw,
@@ -584,14 +692,17 @@ class FusedEvalStep:
                                                         "seg_criterion": self.seg_criterion})
 
     @torch.no_grad()
-    def indexed(self, dataset, index) -> None:
+    def indexed(self, dataset, index, weight: Optional[float] = None) -> None:
         """`__call__` from a device-resident dataset (device_data.DeviceDataset): rows `index` go into the plan's buffers in one launch (identity
-        transform), then the same step program and the same device accumulators."""
+        transform), then the same step program and the same device accumulators.  `weight` as in `__call__`."""
         if self.model.in_channels != 1 + dataset.n_augments:
             raise ValueError(f"the model reads {self.model.in_channels} input channels, the dataset gives 1 + {dataset.n_augments}")
         st = self._compiled(len(index), dataset.H, dataset.W)
         dataset.assemble(index, None, n_onehot=0 if self.binary else 3, out=(st.x.data, st.mask, st.onehot))
-        self._evaluate(st, st.onehot[:, 0].to(torch.int64) if self.binary else None)
+        if self.on_device:
+            self._evaluate_on_device(st, weight)
+        else:
+            self._evaluate(st, st.onehot[:, 0].to(torch.int64) if self.binary else None)
 
     def _evaluate(self, st, gt_binary: Optional[torch.Tensor]) -> None:
         """Forward + losses + metrics of the batch resident in the plan's buffers; gt_binary = the {0, 1} labels of the binary head."""
@@ -621,7 +732,98 @@ class FusedEvalStep:
         self._acc[4] += 1
         self._conf.view(-1).index_add_(0, gt * 3 + pred, torch.ones_like(gt))
 
+    # ---- on_device=True ------------------------------------------------------------------------------------------------------
+    def _eval_buffers(self):
+        if not self.on_device:
+            raise ValueError("this FusedEvalStep was built with on_device=False")
+        if self._em is None:
+            dev = next(self.model.parameters()).device
+            self._em = torch.zeros(self.capacity * 4 + 9, dtype=torch.int64, device=dev)
+            self._em_state = torch.zeros(2, dtype=torch.int32, device=dev)
+            self._em_loss = torch.zeros(self.capacity, 4, dtype=torch.float64, device=dev)
+            self._em_weight = torch.ones(1, dtype=torch.float32, device=dev)
+        return self._em, self._em_state, self._em_loss, self._em_weight
+
+    def _append_eval(self, st) -> None:
+        """`mtbc_eval_metrics` on the outputs and the loss words of the step program that has just run (st = None: the empty shard, which only advances
+        the cursor): two launches on the current stream, capturable.  The argument struct of a compiled step never changes and is built once."""
+        import ctypes as C
+        key = None if st is None else id(st)
+        ent = self._em_args.get(key)
+        if ent is None or ent[0] is not st:
+            em, state, loss_rows, weight = self._eval_buffers()
+            a = L.EvalMetricsArgs()
+            if st is None:
+                a.N, a.n_seg, a.n_logits = 0, 0, 1 if self.binary else 3
+            else:
+                seg, logits, loss_out = st.segs[-1].data, st.logits.data, st.plan.loss_out
+                for t in (seg, st.mask, logits, st.onehot, loss_out):
+                    if t.dtype != torch.float32 or not t.is_contiguous():
+                        raise L.MtbcError("validation metrics: the step's outputs are not contiguous fp32 buffers")
+                if seg.numel() != st.mask.numel() or logits.numel() != st.onehot.numel() or loss_out.numel() < 4:
+                    raise L.MtbcError("validation metrics: outputs and targets differ in size")
+                a.seg_logits, a.mask, a.n_seg = seg.data_ptr(), st.mask.data_ptr(), seg.numel()
+                a.cls_logits, a.target, a.N, a.n_logits = logits.data_ptr(), st.onehot.data_ptr(), st.N, st.logits.C
+                a.loss_in = loss_out.data_ptr()
+            a.table, a.conf, a.state, a.capacity = em.data_ptr(), em.data_ptr() + self.capacity * 32, state.data_ptr(), self.capacity
+            a.loss_rows = loss_rows.data_ptr()
+            a.shard_weight = weight.data_ptr() if self.distributed else None
+            self._em_args[key] = ent = (st, a)
+        L.check(L.load().mtbc_eval_metrics(C.byref(ent[1]), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "eval_metrics")
+
+    def _evaluate_on_device(self, st, weight: Optional[float]) -> None:
+        """The batch resident in the plan's buffers as launches only: pack -> forward -> losses -> mtbc_eval_metrics, eager or as one graph replay."""
+        self._eval_buffers()
+        if self.distributed:        # in stream order in front of the call and outside the replayed region: a replay reads the value of the day
+            self._em_weight.fill_(1.0 if weight is None else float(weight))
+        P = st.programs
+
+        def body():
+            P["pack"].run(); P["fwd"].run(); P["loss"].run()
+            self._append_eval(st)   # a linear chain on the capturing stream, appending at the device cursor
+
+        if not self.graph:
+            body()
+        else:
+            # FusedTrainStep._run_graph's recipe: eager for the first two calls of a compiled step, captured on a side stream at the third, replayed
+            # afterwards; the entry lives ON the compiled step under id(self), so a step that shares the training step's plan keeps its own graph
+            ents = st.__dict__.setdefault("_graph_ents", {})
+            key = (id(self), "eval", self._em.data_ptr(), self._em_state.data_ptr(), self._em_loss.data_ptr(), self._em_weight.data_ptr(),
+                   self.capacity, self.distributed)
+            ent = ents.get(id(self))
+            if ent is None or ent[0] != key:
+                ents[id(self)] = ent = [key, 0, None]
+            self._graphs[id(st)] = ent            # (introspection: tests, tools)
+            if ent[2] is None and ent[1] >= 2:
+                cur = torch.cuda.current_stream()
+                side = torch.cuda.Stream()
+                side.wait_stream(cur)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, stream=side):
+                    body()
+                cur.wait_stream(side)
+                ent[2] = g
+            if ent[2] is not None:
+                ent[2].replay()
+            else:
+                ent[1] += 1
+                body()
+        self._coop_err = self.model.coop_error_word()
+
+    def run_empty(self) -> None:
+        """This rank's shard of the (short, last) global batch is EMPTY: only the cursor advances, so that row b stays global batch b on every rank."""
+        if not self.on_device:
+            return
+        self._append_eval(None)
+
     def result(self):
+        if self.on_device:
+            if self._em is None:
+                raise L.MtbcError("FusedEvalStep.result() before any batch was evaluated")
+            cap = self.capacity
+            packed, losses = reduce_eval_metrics(self._em[:cap * 4], self._em[cap * 4:], self._em_state, self._em_loss, self._coop_err,
+                                                 distributed=self.distributed)
+            return eval_result_from_packed(packed, losses, cap, self.world)
         if self._acc is None:
             raise L.MtbcError("FusedEvalStep.result() before any batch was evaluated")
         err = self._coop_err
@@ -710,15 +912,22 @@ def train_one_epoch_with_metrics(step: FusedTrainStep, dataset, tables, lr: Opti
 
 def validate_one_epoch_indexed(step: FusedEvalStep, dataset, tables) -> tuple:
     """`validate_one_epoch` from a device-resident dataset: the batches of `tables` (built without transforms: the identity path), one
-    assembly launch each; the reference's 6-tuple, read back once."""
+    assembly launch each; the reference's 6-tuple, read back once.  With a distributed step (`tables` from a rank-sharded EpochIndex) each batch
+    carries this rank's share and an empty shard calls `run_empty()`: every rank returns the global validation set's numbers."""
     _check_tables(dataset, tables)
     if tables.params is not None:
         raise ValueError("validation runs without transforms (training_multitask.py:199-201): build the tables with transforms=None")
     step.reset()
+    distributed = getattr(step, "distributed", False)
     for b in range(len(tables)):
-        index, _, n_local, _ = tables.batch(b)
+        index, _, n_local, weight = tables.batch(b)
         if n_local:
-            step.indexed(dataset, index)
+            if distributed:
+                step.indexed(dataset, index, weight)
+            else:
+                step.indexed(dataset, index)
+        elif distributed:           # row b is global batch b on every rank
+            step.run_empty()
     return step.result()
 
 
@@ -738,6 +947,11 @@ def fit_fold(step: FusedTrainStep, eval_step: FusedEvalStep, dataset, train_inde
     from . import checkpoint as CK
     from .device_data import EpochTables
     writer = True
+    if step.distributed and not getattr(eval_step, "distributed", False):
+        # every rank must read the SAME val_loss: the scheduler, the checkpoint rule and early stopping below act on it, and a rank that
+        # leaves the epoch loop alone leaves the others waiting in a collective
+        raise ValueError("fit_fold: the training step is data parallel, the evaluation step is not: build it with "
+                         "FusedEvalStep(..., on_device=True, distributed=True) so that every rank sees the same validation numbers")
     if step.distributed:
         import torch.distributed as dist
         writer = dist.get_rank() == 0
