@@ -426,6 +426,11 @@ def check(rc: int, what: str = "") -> None:
         raise MtbcError(f"libmtbc_hip: {what or 'call'} failed: {msg} ({rc})")
 
 
+def raise_coop_timeout(consequence: str = "the activations of this evaluation are invalid", example: str = "") -> None:
+    """The sticky error word of the cooperative InstanceNorm kernels (engine `coop_error_word()`) was read back non-zero."""
+    raise MtbcError(f"cooperative InstanceNorm: a mailbox poll timed out (team members were not co-resident{example}): {consequence}")
+
+
 def require_gpu() -> None:
     import torch
     if not torch.cuda.is_available():

@@ -157,6 +157,12 @@ class FocalLoss(torch.nn.Module):
         return _FocalFn.apply(inputs, targets, self.alpha, self.gamma, self.weight)
 
 
+def exit_on_nan() -> None:
+    """criterions.py:72-76: a NaN loss ends the run -- here, and wherever the fused steps read a NaN word back from the device."""
+    logging.info("NaN in model loss!!")
+    sys.exit(1)
+
+
 def apply_criterion_multitask_segmentation_classification(criterion_seg, ground_truth, segmentation, criterion_class,
                                                           label, predicted_class, inversely_weighted=False):
     """criterions.py:52-76: deep-supervision heads weighted 1/(n+1) from the LAST head backwards."""
@@ -172,5 +178,4 @@ def apply_criterion_multitask_segmentation_classification(criterion_seg, ground_
         classification_loss = criterion_class(predicted_class, label)
     if not torch.isnan(segmentation_loss) and not torch.isnan(classification_loss):
         return segmentation_loss, classification_loss
-    logging.info("NaN in model loss!!")
-    sys.exit(1)
+    exit_on_nan()

@@ -269,8 +269,7 @@ class FusedTestStep:
         flat = torch.cat([table.double().flatten(), logits.double().flatten(), labels.double(),
                           (err if err is not None else labels[:1] * 0).double().flatten()]).cpu().numpy()     # the one read-back
         if flat[-1] != 0.0:
-            raise L.MtbcError("cooperative InstanceNorm: a mailbox poll timed out (team members were not co-resident): the "
-                              "activations of this evaluation are invalid")
+            L.raise_coop_timeout()
         table = flat[:M * L.SEGM_COLS].astype(np.int64).reshape(M, L.SEGM_COLS)
         logits = flat[M * L.SEGM_COLS:M * (L.SEGM_COLS + K)].reshape(M, K)
         labels = flat[M * (L.SEGM_COLS + K):M * (L.SEGM_COLS + K + 1)].astype(np.int64)

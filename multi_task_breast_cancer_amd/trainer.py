@@ -20,6 +20,7 @@ import torch
 
 from . import _lib as L
 from . import switches as _sw
+from .criterions import exit_on_nan
 from .loss_scale import betas_of
 from .optim import FUSED_OPTIMIZERS
 
@@ -134,31 +135,57 @@ def train_metrics_from_counts(table, conf) -> TrainMetrics:
     return TrainMetrics(total / len(table) if len(table) else 0.0, accuracy, f1w, len(table), conf, table)
 
 
-def reduce_train_metrics(table: torch.Tensor, conf: torch.Tensor, state: torch.Tensor, distributed: bool = False, group=None) -> np.ndarray:
-    """The accumulators of one rank -> ONE int64 host array [table | conf | sum cursor, sum cursor^2, sum dropped] with, under
-    `distributed`, ONE sum-all-reduce in front of the ONE device-to-host read.  The ranks' shards of global batch b all sit in row b, so
-    the summed row holds the GLOBAL batch's tp / fp / fn: the Dice of the union, not a mean of shard Dices.  The accumulators themselves
-    are not modified (the sum works on a copy)."""
+# ---- the device metrics table's way to the host, shared by training (mtbc_train_metrics) and validation (mtbc_eval_metrics): one pack, one decode
+# the words in which each flavour's refusals speak
+_TRAIN = {"kind": "training", "owner": "FusedTrainStep", "cap": "metrics_capacity", "since": "begin_epoch_metrics()", "per_batch": "call run() or run_empty()"}
+_EVAL = {"kind": "validation", "owner": "FusedEvalStep", "cap": "capacity", "since": "reset()", "per_batch": "evaluate its shard or call run_empty()"}
+
+
+def _reduce_packed(table: torch.Tensor, conf: torch.Tensor, state: torch.Tensor, loss_rows: Optional[torch.Tensor] = None,
+                   coop_err: Optional[torch.Tensor] = None, distributed: bool = False, group=None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    """One rank's accumulators -> the int64 host array [table | conf | sum cursor, sum cursor^2, sum dropped] and, with `loss_rows` (validation), a
+    fourth word -- the cooperative-kernel error word -- and the float64 host array [loss_rows]: each array with, under `distributed`, ONE
+    sum-all-reduce in front of its ONE device-to-host read.  The accumulators themselves are not modified (the sums work on copies)."""
     s = state.to(torch.int64)
-    packed = torch.cat([table.reshape(-1), conf.reshape(-1), torch.stack([s[0], s[0] * s[0], s[1]])])
+    words = [s[0], s[0] * s[0], s[1]]
+    losses = None
+    if loss_rows is not None:
+        words.append(s[0] * 0 if coop_err is None else (coop_err.reshape(-1)[0] != 0).to(torch.int64))
+        losses = loss_rows.reshape(-1)
+    packed = torch.cat([table.reshape(-1), conf.reshape(-1), torch.stack(words)])
     if distributed:
         import torch.distributed as dist
+        if losses is not None:
+            losses = losses.clone()
         dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
-    return packed.cpu().numpy()
+        if losses is not None:
+            dist.all_reduce(losses, op=dist.ReduceOp.SUM, group=group)
+    return packed.cpu().numpy(), None if losses is None else losses.cpu().numpy()
+
+
+def _decode_packed(packed: np.ndarray, capacity: int, world: int, f: dict) -> Tuple[np.ndarray, np.ndarray]:
+    """The int64 array of `_reduce_packed` -> (the appended rows (batches, 4), conf (3, 3)), or MtbcError (and no number) when a batch found the table
+    full or the ranks did not see the same number of batches.  Every rank holds the same sums, so every rank raises or none does."""
+    c_sum, c_sq, dropped = (int(v) for v in packed[capacity * 4 + 9:capacity * 4 + 12])
+    if world * c_sq != c_sum * c_sum:              # Cauchy-Schwarz: equality only when all cursors are equal
+        raise L.MtbcError(f"{f['kind']} metrics: the ranks appended different numbers of batches (sum {c_sum} over {world} ranks): every rank must "
+                          f"{f['per_batch']} once per global batch; rows of the {f['cap']} = {capacity} table do not line up")
+    cursor = c_sum // world
+    if dropped != 0 or cursor > capacity:
+        raise L.MtbcError(f"{f['kind']} metrics: {cursor} batches since {f['since']} but {f['cap']} = {capacity} rows "
+                          f"({dropped} dropped): build the {f['owner']} with a larger {f['cap']}")
+    return packed[:cursor * 4].reshape(cursor, 4), packed[capacity * 4:capacity * 4 + 9].reshape(3, 3)
+
+
+def reduce_train_metrics(table: torch.Tensor, conf: torch.Tensor, state: torch.Tensor, distributed: bool = False, group=None) -> np.ndarray:
+    """`_reduce_packed` for training: ONE int64 host array [table | conf | sum cursor, sum cursor^2, sum dropped].  The ranks' shards of global
+    batch b all sit in row b, so the summed row holds the GLOBAL batch's tp / fp / fn: the Dice of the union, not a mean of shard Dices."""
+    return _reduce_packed(table, conf, state, distributed=distributed, group=group)[0]
 
 
 def train_metrics_from_packed(packed: np.ndarray, capacity: int, world: int = 1) -> TrainMetrics:
-    """`reduce_train_metrics`' array -> TrainMetrics, or MtbcError (and no number) when a batch found the table full or the ranks did not
-    see the same number of batches.  Every rank holds the same sums, so every rank raises or none does."""
-    c_sum, c_sq, dropped = (int(v) for v in packed[capacity * 4 + 9:capacity * 4 + 12])
-    if world * c_sq != c_sum * c_sum:              # Cauchy-Schwarz: equality only when all cursors are equal
-        raise L.MtbcError(f"training metrics: the ranks appended different numbers of batches (sum {c_sum} over {world} ranks): every rank must "
-                          f"call run() or run_empty() once per global batch; rows of the metrics_capacity = {capacity} table do not line up")
-    cursor = c_sum // world
-    if dropped != 0 or cursor > capacity:
-        raise L.MtbcError(f"training metrics: {cursor} batches since begin_epoch_metrics() but metrics_capacity = {capacity} rows "
-                          f"({dropped} dropped): build the FusedTrainStep with a larger metrics_capacity")
-    return train_metrics_from_counts(packed[:cursor * 4].reshape(cursor, 4), packed[capacity * 4:capacity * 4 + 9].reshape(3, 3))
+    """`reduce_train_metrics`' array -> TrainMetrics, or the MtbcError of `_decode_packed`."""
+    return train_metrics_from_counts(*_decode_packed(packed, capacity, world, _TRAIN))
 
 
 # ---- the validation epoch (training_multitask.py:119-159) from what mtbc_eval_metrics appended: pure functions of (table, conf, loss_rows)
@@ -182,10 +209,7 @@ def eval_result_from_counts(table, conf, loss_rows) -> tuple:
         dice += _dice(float(tp), float(fp), float(fn))
         nan = nan or flag != 0.0
     if nan:
-        import logging
-        import sys
-        logging.info("NaN in model loss!!")
-        sys.exit(1)
+        exit_on_nan()
     nb = len(table)
     accuracy, f1w = classification_scores(conf.astype(np.float64))
     if nb == 0:
@@ -195,41 +219,21 @@ def eval_result_from_counts(table, conf, loss_rows) -> tuple:
 
 def reduce_eval_metrics(table: torch.Tensor, conf: torch.Tensor, state: torch.Tensor, loss_rows: torch.Tensor, coop_err: Optional[torch.Tensor] = None,
                         distributed: bool = False, group=None) -> Tuple[np.ndarray, np.ndarray]:
-    """One rank's accumulators -> TWO host arrays: int64 [table | conf | sum cursor, sum cursor^2, sum dropped, sum coop error word] and float64
-    [loss_rows], each with, under `distributed`, ONE sum-all-reduce in front of its ONE device-to-host read.  The ranks' shards of global batch b
-    sit in row b on every rank: the summed integer row is the global batch's counts exactly, the summed loss row -- each rank's words carry its
-    share n_local / n_batch -- the global batch's mean losses.  The accumulators themselves are not modified."""
-    s = state.to(torch.int64)
-    err = s[0] * 0 if coop_err is None else (coop_err.reshape(-1)[0] != 0).to(torch.int64)
-    packed = torch.cat([table.reshape(-1), conf.reshape(-1), torch.stack([s[0], s[0] * s[0], s[1], err])])
-    losses = loss_rows.reshape(-1)
-    if distributed:
-        import torch.distributed as dist
-        losses = losses.clone()
-        dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
-        dist.all_reduce(losses, op=dist.ReduceOp.SUM, group=group)
-    return packed.cpu().numpy(), losses.cpu().numpy()
+    """`_reduce_packed` for validation: TWO host arrays, int64 [table | conf | sum cursor, sum cursor^2, sum dropped, sum coop error word] and float64
+    [loss_rows].  The ranks' shards of global batch b sit in row b on every rank: the summed integer row is the global batch's counts exactly, the
+    summed loss row -- each rank's words carry its share n_local / n_batch -- the global batch's mean losses."""
+    return _reduce_packed(table, conf, state, loss_rows, coop_err, distributed=distributed, group=group)
 
 
 def eval_result_from_packed(packed: np.ndarray, losses: np.ndarray, capacity: int, world: int = 1) -> tuple:
-    """`reduce_eval_metrics`' arrays -> the 6-tuple, or MtbcError (and no number) when a cooperative kernel failed on some rank, a batch found the
-    table full or the ranks did not see the same number of batches -- the rule of `train_metrics_from_packed`.  Every rank holds the same sums,
-    so every rank raises (or exits on a NaN word) or none does."""
-    c_sum, c_sq, dropped, err = (int(v) for v in packed[capacity * 4 + 9:capacity * 4 + 13])
-    if err != 0:
-        raise L.MtbcError("cooperative InstanceNorm: a mailbox poll timed out (team members were not co-resident): the "
-                          "activations of this evaluation are invalid")
-    if world * c_sq != c_sum * c_sum:              # Cauchy-Schwarz: equality only when all cursors are equal
-        raise L.MtbcError(f"validation metrics: the ranks appended different numbers of batches (sum {c_sum} over {world} ranks): every rank must "
-                          f"evaluate its shard or call run_empty() once per global batch; rows of the capacity = {capacity} table do not line up")
-    cursor = c_sum // world
-    if dropped != 0 or cursor > capacity:
-        raise L.MtbcError(f"validation metrics: {cursor} batches since reset() but capacity = {capacity} rows "
-                          f"({dropped} dropped): build the FusedEvalStep with a larger capacity")
-    if cursor == 0:
+    """`reduce_eval_metrics`' arrays -> the 6-tuple, or MtbcError (and no number) when a cooperative kernel failed on some rank, or by the rule of
+    `_decode_packed`.  Every rank holds the same sums, so every rank raises (or exits on a NaN word) or none does."""
+    if int(packed[capacity * 4 + 12]) != 0:
+        L.raise_coop_timeout()
+    table, conf = _decode_packed(packed, capacity, world, _EVAL)
+    if len(table) == 0:
         raise L.MtbcError("FusedEvalStep.result() before any batch was evaluated")
-    return eval_result_from_counts(packed[:cursor * 4].reshape(cursor, 4), packed[capacity * 4:capacity * 4 + 9].reshape(3, 3),
-                                   np.asarray(losses, dtype=np.float64)[:cursor * 4].reshape(cursor, 4))
+    return eval_result_from_counts(table, conf, np.asarray(losses, dtype=np.float64)[:len(table) * 4].reshape(len(table), 4))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -246,6 +250,154 @@ def _check_seg_criterion(name: str, distributed: bool) -> str:
         raise NotImplementedError(f"seg_criterion={name!r} sums over the batch (reduction='sum'): the data-parallel step averages the ranks' gradients, "
                                   f"which is exact for a mean over the batch only -- train it on one device, or use a mean criterion")
     return name
+
+
+def _check_heads(model, n_classes: int, cls_criterion: str, focal_weight, owner: str) -> tuple:
+    """What FusedTrainStep and FusedEvalStep both require of the classification head and its criterion -> (binary, cls_gamma, focal_weight)."""
+    if n_classes > 3:       # the confusion matrix is the reference's 3 x 3 (f1_score(labels=[0, 1, 2]), training_multitask.py:155)
+        raise NotImplementedError(f"{owner} covers the reference's label set {{0, 1, 2}} (n_classes <= 3)")
+    binary = n_classes == 2
+    if binary != (getattr(model, "n_classes", n_classes) == 1):
+        raise ValueError("n_classes does not match the model's classification head (n_classes == 2 <=> ONE logit)")
+    if cls_criterion not in ("Focal", "CE"):
+        raise ValueError(f"unknown classification criterion {cls_criterion!r} (Focal | CE; the binary head always takes BCEWithLogits)")
+    if cls_criterion == "CE" and focal_weight is not None:
+        # torch.nn.CrossEntropyLoss(weight=w) divides by the sum of the samples' weights; FocalLoss (criterions.py:14-24) by N
+        raise NotImplementedError("class-weighted CrossEntropyLoss normalises by the weights' sum: use the drop-in loop for it")
+    return binary, 2.0 if cls_criterion == "Focal" else 0.0, None if binary else focal_weight
+
+
+def _fused_loss(step) -> dict:
+    """The `fused_loss` settings a step compiles its plan with.  A training and an evaluation step with the same (alpha, weighting, criteria) build
+    equal dicts and so share one compiled plan at equal (N, H, W); only a dynamic loss scale adds a key."""
+    d = {"alpha": step.alpha, "inversely_weighted": step.iw, "focal_weight": step.focal_weight, "binary": step.binary,
+         "cls_gamma": step.cls_gamma, "seg_criterion": step.seg_criterion}
+    if getattr(step, "scaler", None) is not None:
+        d["loss_scale"] = 1.0
+    return d
+
+
+def _check_in_channels(model, dataset) -> None:
+    if model.in_channels != 1 + dataset.n_augments:
+        raise ValueError(f"the model reads {model.in_channels} input channels, the dataset gives 1 + {dataset.n_augments}: build the model with "
+                         f"sequences + dataset.n_augments (experiment_init.load_multitask_experiment_artefacts(n_augments=...))")
+
+
+def fill_batch(st, image: torch.Tensor, mask: torch.Tensor, label: torch.Tensor, binary: bool) -> None:
+    """H2D / D2D of training_multitask.py:82-84 into the plan's static buffers; the class target is built on the device: the one-hot rows, or, for
+    the binary head, the (N, 1) float label itself (the target of the one-logit criterion)."""
+    st.x.data.copy_(image, non_blocking=True)
+    st.mask.copy_(mask, non_blocking=True)
+    lab = label.to(st.onehot.device, non_blocking=True).flatten()
+    if binary:
+        st.onehot.copy_(lab.view(-1, 1).to(torch.float32))
+    else:
+        st.onehot.zero_()
+        st.onehot.scatter_(1, lab.to(torch.int64).view(-1, 1), 1.0)
+
+
+def _capture(body):
+    """`body`'s launches as ONE hipGraph, captured on a fresh side stream that joins the current one on both sides."""
+    cur = torch.cuda.current_stream()
+    side = torch.cuda.Stream()
+    side.wait_stream(cur)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side):
+        body()
+    cur.wait_stream(side)
+    return g
+
+
+def run_or_replay(owner, st, key, body, capture=_capture) -> None:
+    """`body` (a static list of launches on the compiled step `st`) as a hipGraph replay: eager for the first two calls of a compiled step (lazily
+    created buffers, kernel attributes), captured at the third, replayed afterwards.  A graph holds addresses: `key` names what it depends on, and
+    a changed key drops it.  The entry [key, eager calls, graph] lives ON the compiled step under id(owner) -- a dropped step takes its graph along
+    (no address or id() can be reused under a stale graph), and two steps that share a plan keep a graph each -- and is mirrored in
+    owner._graphs[id(st)] for tests and tools."""
+    ents = st.__dict__.setdefault("_graph_ents", {})
+    ent = ents.get(id(owner))
+    if ent is None or ent[0] != key:
+        ents[id(owner)] = ent = [key, 0, None]
+    owner._graphs[id(st)] = ent
+    if ent[2] is None and ent[1] >= 2:
+        ent[2] = capture(body)
+    if ent[2] is not None:
+        ent[2].replay()
+    else:
+        ent[1] += 1
+        body()
+
+
+class MetricsTable:
+    """The device accumulator behind `mtbc_train_metrics` and, with `validation`, `mtbc_eval_metrics`: `counts` int64 [capacity * 4 + 9] --
+    one row tp, fp, fn, samples per batch, then the 3 x 3 confusion matrix -- and `state` int32 [2] = cursor, dropped; for validation also
+    `loss_rows` float64 [capacity][4] = (weighted) total, seg, cls, NaN word of each batch and `weight` float32 [1], this rank's share of the batch in
+    flight (read by the kernel under `distributed` only).  Allocated at first use, once, and never moved: captured graphs hold the addresses."""
+
+    def __init__(self, model, capacity: int, validation: bool = False, distributed: bool = False):
+        self.model, self.capacity, self.eval, self.distributed = model, int(capacity), bool(validation), bool(distributed)
+        self.words = _EVAL if self.eval else _TRAIN
+        self.counts = self.state = self.loss_rows = self.weight = None
+        self._args = {}             # id(compiled step) -> (the step, its argument struct); None -> the empty shard's
+
+    def buffers(self) -> "MetricsTable":
+        if self.counts is None:
+            dev = next(self.model.parameters()).device
+            self.counts = torch.zeros(self.capacity * 4 + 9, dtype=torch.int64, device=dev)
+            self.state = torch.zeros(2, dtype=torch.int32, device=dev)
+            if self.eval:
+                self.loss_rows = torch.zeros(self.capacity, 4, dtype=torch.float64, device=dev)
+                self.weight = torch.ones(1, dtype=torch.float32, device=dev)
+        return self
+
+    def zero(self) -> None:
+        """Rows, confusion matrix and cursor back to zero in stream order (outside any replayed graph: the buffers stay where they are)."""
+        for t in (self.counts, self.state, self.loss_rows):
+            if t is not None:
+                t.zero_()
+
+    def _arguments(self, st, n_logits):
+        """The argument struct of one compiled step (st = None: of the empty shard, N = 0), which never changes: outputs and accumulators stay where
+        they are.  Behind the loss program the plan's buffers hold fp32 NCHW logits of the last head, the mask, the class logits and their target,
+        in every compute mode."""
+        self.buffers()
+        a = L.EvalMetricsArgs() if self.eval else L.TrainMetricsArgs()
+        if st is None:
+            a.N, a.n_seg, a.n_logits = 0, 0, n_logits
+        else:
+            seg, logits = st.segs[-1].data, st.logits.data
+            loss_out = (st.plan.loss_out,) if self.eval else ()
+            for t in (seg, st.mask, logits, st.onehot) + loss_out:
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    raise L.MtbcError(f"{self.words['kind']} metrics: the step's outputs are not contiguous fp32 buffers")
+            if seg.numel() != st.mask.numel() or logits.numel() != st.onehot.numel() or any(t.numel() < 4 for t in loss_out):
+                raise L.MtbcError(f"{self.words['kind']} metrics: outputs and targets differ in size")
+            a.seg_logits, a.mask, a.n_seg = seg.data_ptr(), st.mask.data_ptr(), seg.numel()
+            a.cls_logits, a.target, a.N, a.n_logits = logits.data_ptr(), st.onehot.data_ptr(), st.N, st.logits.C
+            if self.eval:
+                a.loss_in = st.plan.loss_out.data_ptr()
+        a.table, a.conf, a.state, a.capacity = self.counts.data_ptr(), self.counts.data_ptr() + self.capacity * 32, self.state.data_ptr(), self.capacity
+        if self.eval:
+            a.loss_rows = self.loss_rows.data_ptr()
+            a.shard_weight = self.weight.data_ptr() if self.distributed else None
+        return a
+
+    def append(self, st, n_logits: int = 0) -> None:
+        """The metrics call on the outputs (validation: and the loss words) of the step program that has just run; st = None: the empty shard, which
+        only advances the cursor (`n_logits` = the head's width).  Two launches on the current stream, capturable."""
+        import ctypes as C
+        key = None if st is None else id(st)
+        ent = self._args.get(key)
+        if ent is None or ent[0] is not st:
+            self._args[key] = ent = (st, self._arguments(st, n_logits))
+        lib = L.load()
+        L.check((lib.mtbc_eval_metrics if self.eval else lib.mtbc_train_metrics)(C.byref(ent[1]), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                "eval_metrics" if self.eval else "train_metrics")
+
+    def reduce(self, coop_err: Optional[torch.Tensor] = None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        """`_reduce_packed` of these buffers: under `distributed` one sum-all-reduce per array (row b of the sum is GLOBAL batch b), one read each."""
+        cap = self.capacity
+        return _reduce_packed(self.counts[:cap * 4], self.counts[cap * 4:], self.state, self.loss_rows, coop_err, distributed=self.distributed)
 
 
 class FusedTrainStep:
@@ -271,9 +423,7 @@ class FusedTrainStep:
         self.metrics_capacity = int(metrics_capacity)
         if self.metrics and self.metrics_capacity < 1:
             raise ValueError("metrics_capacity must be at least 1 row")
-        self._tm = None             # device int64 [capacity * 4 + 9]: the table, then the confusion matrix
-        self._tm_state = None       # device int32 [2]: cursor, dropped
-        self._tm_args = {}          # id(compiled step) -> (the step, its mtbc_train_metrics_args); None -> the empty shard's
+        self._table = MetricsTable(model, self.metrics_capacity, distributed=distributed) if self.metrics else None
         # graph: replay each compiled step as ONE hipGraph from its third call on (None: the MTBC_GRAPH switch).  The step is a static list of ~380
         # launches with every pointer resolved at plan time -- exactly what a graph holds; what changes from step to step (the batch, the learning
         # rate, Adam's bias corrections, the shard weight) lives in device buffers written BEFORE the replay.  Not under data parallel (the bucket
@@ -297,22 +447,9 @@ class FusedTrainStep:
         if self.scaler is not None:
             self.scaler.attach(optimizer)
         self._graphs = {}
-        self.binary = n_classes == 2
-        if self.binary != (getattr(model, "n_classes", n_classes) == 1):
-            raise ValueError("n_classes does not match the model's classification head (n_classes == 2 <=> ONE logit)")
-        if cls_criterion not in ("Focal", "CE"):
-            raise ValueError(f"unknown classification criterion {cls_criterion!r} (Focal | CE; the binary head always trains with BCEWithLogits)")
-        self.cls_gamma = 2.0 if cls_criterion == "Focal" else 0.0
-        if cls_criterion == "CE" and focal_weight is not None:
-            # torch.nn.CrossEntropyLoss(weight=w) divides by the sum of the samples' weights; FocalLoss (criterions.py:14-24) by N
-            raise NotImplementedError("class-weighted CrossEntropyLoss normalises by the weights' sum: use the drop-in loop for it")
-        if self.binary:
-            focal_weight = None
-        if n_classes > 3:
-            raise NotImplementedError("the fused step covers the reference's label set {0, 1, 2} (n_classes <= 3)")
+        self.binary, self.cls_gamma, self.focal_weight = _check_heads(model, n_classes, cls_criterion, focal_weight, "the fused step")
         self.model, self.opt = model, optimizer
         self.alpha, self.iw, self.n_classes = float(alpha), bool(inversely_weighted), n_classes
-        self.focal_weight = focal_weight
         self.distributed = distributed
         self.n_buckets = n_buckets
         self.world = 1
@@ -334,9 +471,7 @@ class FusedTrainStep:
         self.losses: Optional[torch.Tensor] = None      # device: [total, seg, cls, nan_flag]
 
     def _compiled(self, N: int, H: int, W: int):
-        st = self.model.compiled(N, H, W, fused_loss={"alpha": self.alpha, "inversely_weighted": self.iw, "focal_weight": self.focal_weight,
-                                                      "binary": self.binary, "cls_gamma": self.cls_gamma, "seg_criterion": self.seg_criterion,
-                                                      **({} if self.scaler is None else {"loss_scale": 1.0})})
+        st = self.model.compiled(N, H, W, fused_loss=_fused_loss(self))
         if st is not self._st:
             self._st = st
             self.model.grads_as_views()
@@ -352,14 +487,7 @@ class FusedTrainStep:
         global batch's."""
         N, _, H, W = image.shape
         st = self._compiled(N, H, W)
-        st.x.data.copy_(image, non_blocking=True)
-        st.mask.copy_(mask, non_blocking=True)
-        lab = label.to(st.onehot.device, non_blocking=True).flatten()
-        if self.binary:             # the (N, 1) float label itself is the target of the one-logit criterion
-            st.onehot.copy_(lab.view(-1, 1).to(torch.float32))
-        else:
-            st.onehot.zero_()
-            st.onehot.scatter_(1, lab.to(torch.int64).view(-1, 1), 1.0)
+        fill_batch(st, image, mask, label, self.binary)
         self._set_shard_weight(st, weight)
         return st
 
@@ -377,62 +505,30 @@ class FusedTrainStep:
         per-sample flip / rotation `params` (None = identity) straight into the plan's static buffers -- image and its intensity channels, mask,
         class target -- with no intermediate tensor and no host-to-device transfer when `index` / `params` are device tensors (EpochTables.batch).
         In stream order in front of the step and, with graph=True, outside the replayed region, where `load_batch` sits.  `weight` as in `load_batch`."""
-        if self.model.in_channels != 1 + dataset.n_augments:
-            raise ValueError(f"the model reads {self.model.in_channels} input channels, the dataset gives 1 + {dataset.n_augments}: build the model with "
-                             f"sequences + dataset.n_augments (experiment_init.load_multitask_experiment_artefacts(n_augments=...))")
+        _check_in_channels(self.model, dataset)
         st = self._compiled(len(index), dataset.H, dataset.W)
         dataset.assemble(index, params, n_onehot=0 if self.binary else 3, out=(st.x.data, st.mask, st.onehot))
         self._set_shard_weight(st, weight)
         return st
 
     # ---- training-time metrics ----------------------------------------------------------------------------------------------
-    def _metrics_buffers(self):
-        if not self.metrics:
+    def _metrics_table(self) -> MetricsTable:
+        if self._table is None:
             raise ValueError("this FusedTrainStep was built with metrics=False")
-        if self._tm is None:
-            dev = next(self.model.parameters()).device
-            self._tm = torch.zeros(self.metrics_capacity * 4 + 9, dtype=torch.int64, device=dev)
-            self._tm_state = torch.zeros(2, dtype=torch.int32, device=dev)
-        return self._tm, self._tm_state
+        return self._table.buffers()
 
     def _append_metrics(self, st) -> None:
-        """The metrics call on the outputs of the forward that has just run (st = None: the empty shard, which only advances the cursor).  Behind the
-        loss program the buffers hold what FusedEvalStep reads there: fp32 NCHW logits of the last head, the mask, the class logits and their target,
-        in every compute mode.  Two launches on the current stream, capturable."""
-        import ctypes as C
-        key = None if st is None else id(st)
-        ent = self._tm_args.get(key)
-        if ent is None or ent[0] is not st:         # the arguments of a compiled step never change: buffers and accumulators stay where they are
-            tm, state = self._metrics_buffers()
-            a = L.TrainMetricsArgs()
-            if st is None:
-                a.N, a.n_seg, a.n_logits = 0, 0, self._st.logits.C
-            else:
-                seg, logits = st.segs[-1].data, st.logits.data
-                for t in (seg, st.mask, logits, st.onehot):
-                    if t.dtype != torch.float32 or not t.is_contiguous():
-                        raise L.MtbcError("training metrics: the step's outputs are not contiguous fp32 buffers")
-                if seg.numel() != st.mask.numel() or logits.numel() != st.onehot.numel():
-                    raise L.MtbcError("training metrics: outputs and targets differ in size")
-                a.seg_logits, a.mask, a.n_seg = seg.data_ptr(), st.mask.data_ptr(), seg.numel()
-                a.cls_logits, a.target, a.N, a.n_logits = logits.data_ptr(), st.onehot.data_ptr(), st.N, st.logits.C
-            a.table, a.conf, a.state, a.capacity = tm.data_ptr(), tm.data_ptr() + self.metrics_capacity * 32, state.data_ptr(), self.metrics_capacity
-            self._tm_args[key] = ent = (st, a)
-        L.check(L.load().mtbc_train_metrics(C.byref(ent[1]), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "train_metrics")
+        """`mtbc_train_metrics` on the outputs of the forward that has just run (st = None: the empty shard)."""
+        self._metrics_table().append(st, self._st.logits.C)
 
     def begin_epoch_metrics(self) -> None:
         """Zero the table, the confusion matrix and the cursor in stream order (outside any replayed graph: the buffers stay where they are)."""
-        tm, state = self._metrics_buffers()
-        tm.zero_()
-        state.zero_()
+        self._metrics_table().zero()
 
     def epoch_metrics(self) -> TrainMetrics:
         """The epoch so far as the reference's numbers: under data parallel ONE sum-all-reduce of the table and the confusion matrix (row b of the sum is
         GLOBAL batch b), then ONE device-to-host read.  MtbcError when the table was too small or the ranks' cursors disagree."""
-        tm, state = self._metrics_buffers()
-        cap = self.metrics_capacity
-        packed = reduce_train_metrics(tm[:cap * 4], tm[cap * 4:], state, distributed=self.distributed)
-        return train_metrics_from_packed(packed, cap, self.world)
+        return train_metrics_from_packed(self._metrics_table().reduce()[0], self.metrics_capacity, self.world)
 
     def _apply_update(self, st) -> None:
         """Adam on the (all-reduced) flat gradients: the static path divides the baked loss scale out, the dynamic path checks, skips or applies, and
@@ -457,8 +553,7 @@ class FusedTrainStep:
                           plan_buckets([(0, self.model.flat_numel, 0)], self.model.flat_numel, 1))
 
     def _run_graph(self, st) -> torch.Tensor:
-        """The step as a hipGraph replay: eager for the first two calls of a compiled step (lazily created buffers, kernel attributes), captured at the
-        third, replayed afterwards.  A graph holds addresses: it is keyed by the compiled step and by the optimizer's buffers and dropped when they move."""
+        """The step as a hipGraph replay (`run_or_replay`), keyed by the optimizer's buffers and dropped when they move."""
         opt = self.opt
         sc = self.scaler
         if sc is None:
@@ -481,27 +576,8 @@ class FusedTrainStep:
             else:
                 self._apply_update(st)
 
-        # the entry lives ON the compiled step (a dropped step takes its graph along; no address or id() can be reused under a stale graph)
-        ents = st.__dict__.setdefault("_graph_ents", {})
         key = (id(self), opt.graph_key() if sc is None else (opt.graph_key(dynamic=False), sc.graph_key()), self.metrics)
-        ent = ents.get(id(self))
-        if ent is None or ent[0] != key:
-            ents[id(self)] = ent = [key, 0, None]
-        self._graphs[id(st)] = ent                # (introspection: tests, tools)
-        if ent[2] is None and ent[1] >= 2:
-            cur = torch.cuda.current_stream()
-            side = torch.cuda.Stream()
-            side.wait_stream(cur)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                body()
-            cur.wait_stream(side)
-            ent[2] = g
-        if ent[2] is not None:
-            ent[2].replay()
-        else:
-            ent[1] += 1
-            body()
+        run_or_replay(self, st, key, body)
         self.losses = st.plan.loss_out
         self._coop_err = self.model.coop_error_word()
         return self.losses
@@ -571,14 +647,10 @@ class FusedTrainStep:
         err = getattr(self, "_coop_err", None)
         vals = torch.cat([self.losses[3:4].double(), (err if err is not None else self.losses[3:4] * 0).double()]).cpu().tolist()
         if vals[1] != 0.0:
-            raise L.MtbcError("cooperative InstanceNorm: a mailbox poll timed out (team members were not co-resident, e.g. "
-                              "another stream or process held the CUs): activations and gradients of this and later steps "
-                              "are invalid. Raise MTBC_COOP_RESERVE_CUS, or set MTBC_NO_COOP=1.")
+            L.raise_coop_timeout("activations and gradients of this and later steps are invalid. Raise MTBC_COOP_RESERVE_CUS, or set MTBC_NO_COOP=1.",
+                                 ", e.g. another stream or process held the CUs")
         if vals[0] != 0.0:
-            import logging
-            import sys
-            logging.info("NaN in model loss!!")
-            sys.exit(1)
+            exit_on_nan()
 
 
 def dice_score_from_counts(counts: torch.Tensor) -> float:
@@ -615,8 +687,8 @@ class FusedEvalStep:
     on_device=True: launches only per batch -- pack -> forward -> losses -> `mtbc_eval_metrics` (two launches), which appends the batch's counts
     AND its loss words as one row at a device cursor, into buffers this step owns (`capacity` rows, allocated once, never moved); `result()` is one
     read of an int64 and a float64 array and pure host arithmetic (`eval_result_from_counts`).
-    graph (None: the MTBC_GRAPH switch; needs on_device): that chain replayed as ONE hipGraph from the third call of a compiled step on, by the
-    recipe of `FusedTrainStep._run_graph`; the fills of the batch and of the weight word stay in front of the replay.
+    graph (None: the MTBC_GRAPH switch; needs on_device): that chain replayed as ONE hipGraph from the third call of a compiled step on
+    (`run_or_replay`); the fills of the batch and of the weight word stay in front of the replay.
     distributed=True (needs on_device): every rank evaluates ITS shard of each global batch with its share `weight` = n_local / n_batch (a rank
     with an empty shard calls `run_empty()`), `result()` sum-all-reduces the two arrays once and every rank returns the SAME six numbers: the
     integer rows sum to the global batch's counts exactly, the weighted loss rows to its mean losses (the criteria allowed here are means over
@@ -639,69 +711,47 @@ class FusedEvalStep:
             import torch.distributed as dist
             self.world = dist.get_world_size()
         self._graphs = {}
-        self._em = None             # device int64 [capacity * 4 + 9]: the table, then the confusion matrix
-        self._em_state = None       # device int32 [2]: cursor, dropped
-        self._em_loss = None        # device float64 [capacity][4]: (weighted) total, seg, cls, NaN word of each batch
-        self._em_weight = None      # device float32 [1]: this rank's share of the batch in flight (read by the kernel; distributed only)
-        self._em_args = {}          # id(compiled step) -> (the step, its mtbc_eval_metrics_args); None -> the empty shard's
+        self._table = MetricsTable(model, self.capacity, validation=True, distributed=self.distributed) if self.on_device else None
         self.seg_criterion = _check_seg_criterion(seg_criterion, self.distributed)      # as `cls_criterion`: the criterion the run trains with
-        self.binary = n_classes == 2
-        if cls_criterion not in ("Focal", "CE"):
-            raise ValueError(f"unknown classification criterion {cls_criterion!r} (Focal | CE; the binary head always evaluates BCEWithLogits)")
-        self.cls_gamma = 2.0 if cls_criterion == "Focal" else 0.0
-        if cls_criterion == "CE" and focal_weight is not None:       # same refusal as FusedTrainStep
-            raise NotImplementedError("class-weighted CrossEntropyLoss normalises by the weights' sum: use the drop-in loop for it")
-        if n_classes > 3:       # the confusion matrix is the reference's 3 x 3 (f1_score(labels=[0, 1, 2]), training_multitask.py:155)
-            raise NotImplementedError("FusedEvalStep covers the reference's label set {0, 1, 2} (n_classes <= 3)")
-        if self.binary != (getattr(model, "n_classes", n_classes) == 1):
-            raise ValueError("n_classes does not match the model's classification head")
-        self.focal_weight = None if self.binary else focal_weight
+        self.binary, self.cls_gamma, self.focal_weight = _check_heads(model, n_classes, cls_criterion, focal_weight, "FusedEvalStep")
         self._coop_err = None
         self.reset()
+
+    # the on_device accumulators under the names tests/test_eval_device_gpu.py and tools/eval_cost.py read them by
+    _em = property(lambda self: self._table.counts)
+    _em_state = property(lambda self: self._table.state)
+    _em_loss = property(lambda self: self._table.loss_rows)
 
     def reset(self) -> None:
         self._acc = None          # device float64: [sum total, sum seg, sum cls, sum dice, batches]
         self._conf = None         # device int64 (3, 3): rows = ground truth, cols = prediction (f1 is asked for labels 0,1,2)
-        if self._em is not None:  # on_device: zeroed in stream order, outside any replayed graph; the buffers stay where they are
-            self._em.zero_()
-            self._em_state.zero_()
-            self._em_loss.zero_()
+        if self._table is not None:
+            self._table.zero()
 
     @torch.no_grad()
     def __call__(self, image: torch.Tensor, mask: torch.Tensor, label: torch.Tensor, weight: Optional[float] = None) -> None:
         """`weight`: this rank's share n_local / n_batch of the global batch (distributed=True; None = 1)."""
         N, _, H, W = image.shape
         st = self._compiled(N, H, W)
-        st.x.data.copy_(image, non_blocking=True)
-        st.mask.copy_(mask, non_blocking=True)
-        dev = st.plan.loss_out.device
-        lab = label.to(dev, non_blocking=True).flatten()
-        if self.binary:
-            st.onehot.copy_(lab.view(-1, 1).to(torch.float32))
-        else:
-            st.onehot.zero_()
-            st.onehot.scatter_(1, lab.to(torch.int64).view(-1, 1), 1.0)
-        if self.on_device:
-            self._evaluate_on_device(st, weight)
-        else:
-            self._evaluate(st, lab.to(torch.int64) if self.binary else None)
+        fill_batch(st, image, mask, label, self.binary)
+        self._evaluate_resident(st, weight)
 
     def _compiled(self, N: int, H: int, W: int):
-        return self.model.compiled(N, H, W, fused_loss={"alpha": self.alpha, "inversely_weighted": self.iw,
-                                                        "focal_weight": self.focal_weight, "binary": self.binary, "cls_gamma": self.cls_gamma,
-                                                        "seg_criterion": self.seg_criterion})
+        return self.model.compiled(N, H, W, fused_loss=_fused_loss(self))
 
     @torch.no_grad()
     def indexed(self, dataset, index, weight: Optional[float] = None) -> None:
         """`__call__` from a device-resident dataset (device_data.DeviceDataset): rows `index` go into the plan's buffers in one launch (identity
         transform), then the same step program and the same device accumulators.  `weight` as in `__call__`."""
-        if self.model.in_channels != 1 + dataset.n_augments:
-            raise ValueError(f"the model reads {self.model.in_channels} input channels, the dataset gives 1 + {dataset.n_augments}")
+        _check_in_channels(self.model, dataset)
         st = self._compiled(len(index), dataset.H, dataset.W)
         dataset.assemble(index, None, n_onehot=0 if self.binary else 3, out=(st.x.data, st.mask, st.onehot))
+        self._evaluate_resident(st, weight)
+
+    def _evaluate_resident(self, st, weight: Optional[float]) -> None:
         if self.on_device:
             self._evaluate_on_device(st, weight)
-        else:
+        else:                       # the binary head's target column holds the {0, 1} labels themselves
             self._evaluate(st, st.onehot[:, 0].to(torch.int64) if self.binary else None)
 
     def _evaluate(self, st, gt_binary: Optional[torch.Tensor]) -> None:
@@ -733,49 +783,15 @@ class FusedEvalStep:
         self._conf.view(-1).index_add_(0, gt * 3 + pred, torch.ones_like(gt))
 
     # ---- on_device=True ------------------------------------------------------------------------------------------------------
-    def _eval_buffers(self):
-        if not self.on_device:
-            raise ValueError("this FusedEvalStep was built with on_device=False")
-        if self._em is None:
-            dev = next(self.model.parameters()).device
-            self._em = torch.zeros(self.capacity * 4 + 9, dtype=torch.int64, device=dev)
-            self._em_state = torch.zeros(2, dtype=torch.int32, device=dev)
-            self._em_loss = torch.zeros(self.capacity, 4, dtype=torch.float64, device=dev)
-            self._em_weight = torch.ones(1, dtype=torch.float32, device=dev)
-        return self._em, self._em_state, self._em_loss, self._em_weight
-
     def _append_eval(self, st) -> None:
-        """`mtbc_eval_metrics` on the outputs and the loss words of the step program that has just run (st = None: the empty shard, which only advances
-        the cursor): two launches on the current stream, capturable.  The argument struct of a compiled step never changes and is built once."""
-        import ctypes as C
-        key = None if st is None else id(st)
-        ent = self._em_args.get(key)
-        if ent is None or ent[0] is not st:
-            em, state, loss_rows, weight = self._eval_buffers()
-            a = L.EvalMetricsArgs()
-            if st is None:
-                a.N, a.n_seg, a.n_logits = 0, 0, 1 if self.binary else 3
-            else:
-                seg, logits, loss_out = st.segs[-1].data, st.logits.data, st.plan.loss_out
-                for t in (seg, st.mask, logits, st.onehot, loss_out):
-                    if t.dtype != torch.float32 or not t.is_contiguous():
-                        raise L.MtbcError("validation metrics: the step's outputs are not contiguous fp32 buffers")
-                if seg.numel() != st.mask.numel() or logits.numel() != st.onehot.numel() or loss_out.numel() < 4:
-                    raise L.MtbcError("validation metrics: outputs and targets differ in size")
-                a.seg_logits, a.mask, a.n_seg = seg.data_ptr(), st.mask.data_ptr(), seg.numel()
-                a.cls_logits, a.target, a.N, a.n_logits = logits.data_ptr(), st.onehot.data_ptr(), st.N, st.logits.C
-                a.loss_in = loss_out.data_ptr()
-            a.table, a.conf, a.state, a.capacity = em.data_ptr(), em.data_ptr() + self.capacity * 32, state.data_ptr(), self.capacity
-            a.loss_rows = loss_rows.data_ptr()
-            a.shard_weight = weight.data_ptr() if self.distributed else None
-            self._em_args[key] = ent = (st, a)
-        L.check(L.load().mtbc_eval_metrics(C.byref(ent[1]), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "eval_metrics")
+        """`mtbc_eval_metrics` on the outputs and the loss words of the step program that has just run (st = None: the empty shard)."""
+        self._table.append(st, 1 if self.binary else 3)
 
     def _evaluate_on_device(self, st, weight: Optional[float]) -> None:
         """The batch resident in the plan's buffers as launches only: pack -> forward -> losses -> mtbc_eval_metrics, eager or as one graph replay."""
-        self._eval_buffers()
+        t = self._table.buffers()
         if self.distributed:        # in stream order in front of the call and outside the replayed region: a replay reads the value of the day
-            self._em_weight.fill_(1.0 if weight is None else float(weight))
+            t.weight.fill_(1.0 if weight is None else float(weight))
         P = st.programs
 
         def body():
@@ -784,30 +800,9 @@ class FusedEvalStep:
 
         if not self.graph:
             body()
-        else:
-            # FusedTrainStep._run_graph's recipe: eager for the first two calls of a compiled step, captured on a side stream at the third, replayed
-            # afterwards; the entry lives ON the compiled step under id(self), so a step that shares the training step's plan keeps its own graph
-            ents = st.__dict__.setdefault("_graph_ents", {})
-            key = (id(self), "eval", self._em.data_ptr(), self._em_state.data_ptr(), self._em_loss.data_ptr(), self._em_weight.data_ptr(),
-                   self.capacity, self.distributed)
-            ent = ents.get(id(self))
-            if ent is None or ent[0] != key:
-                ents[id(self)] = ent = [key, 0, None]
-            self._graphs[id(st)] = ent            # (introspection: tests, tools)
-            if ent[2] is None and ent[1] >= 2:
-                cur = torch.cuda.current_stream()
-                side = torch.cuda.Stream()
-                side.wait_stream(cur)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=side):
-                    body()
-                cur.wait_stream(side)
-                ent[2] = g
-            if ent[2] is not None:
-                ent[2].replay()
-            else:
-                ent[1] += 1
-                body()
+        else:                       # a step that shares the training step's plan keeps its own graph (the entry sits under id(self))
+            key = (id(self), "eval", t.counts.data_ptr(), t.state.data_ptr(), t.loss_rows.data_ptr(), t.weight.data_ptr(), self.capacity, self.distributed)
+            run_or_replay(self, st, key, body)
         self._coop_err = self.model.coop_error_word()
 
     def run_empty(self) -> None:
@@ -817,19 +812,13 @@ class FusedEvalStep:
         self._append_eval(None)
 
     def result(self):
-        if self.on_device:
-            if self._em is None:
-                raise L.MtbcError("FusedEvalStep.result() before any batch was evaluated")
-            cap = self.capacity
-            packed, losses = reduce_eval_metrics(self._em[:cap * 4], self._em[cap * 4:], self._em_state, self._em_loss, self._coop_err,
-                                                 distributed=self.distributed)
-            return eval_result_from_packed(packed, losses, cap, self.world)
-        if self._acc is None:
+        if self._acc is None and (self._table is None or self._table.counts is None):
             raise L.MtbcError("FusedEvalStep.result() before any batch was evaluated")
+        if self.on_device:
+            return eval_result_from_packed(*self._table.reduce(self._coop_err), self.capacity, self.world)
         err = self._coop_err
         if err is not None and int(err.item()) != 0:
-            raise L.MtbcError("cooperative InstanceNorm: a mailbox poll timed out (team members were not co-resident): the "
-                              "activations of this evaluation are invalid")
+            L.raise_coop_timeout()
         acc = self._acc.cpu().tolist()
         conf = self._conf.cpu().numpy().astype(np.float64)
         nb = max(acc[4], 1.0)
@@ -876,10 +865,7 @@ def _train_epoch(step: FusedTrainStep, dataset, tables, lr: Optional[float]) -> 
     step.check_nan()
     total, seg, cls, nan = acc.cpu().tolist()
     if nan != 0.0 or total != total:
-        import logging
-        import sys
-        logging.info("NaN in model loss!!")
-        sys.exit(1)
+        exit_on_nan()
     return total / ran, seg / ran, cls / ran
 
 

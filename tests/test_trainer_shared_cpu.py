@@ -1,0 +1,143 @@
+"""What FusedTrainStep and FusedEvalStep share, without a GPU: the decode of the packed metrics arrays in both flavours, the batch fill
+on a stand-in compiled step, the bookkeeping of the graph-replay helper with the capture step replaced, and the `fused_loss` settings."""
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from multi_task_breast_cancer_amd import _lib as L
+from multi_task_breast_cancer_amd import trainer as T
+
+CAP = 3
+ROWS = [[5, 1, 2, 4], [0, 0, 0, 4]]
+CONF = [[3, 0, 0], [1, 2, 0], [0, 0, 2]]
+
+
+def packed_array(flavour, sums, rows=ROWS):
+    """[table | conf | sum cursor, sum cursor^2, sum dropped] (+ the error word of the validation flavour), built by index."""
+    a = np.zeros(CAP * 4 + (13 if flavour is T._EVAL else 12), dtype=np.int64)
+    a[:len(rows) * 4] = np.array(rows, dtype=np.int64).reshape(-1)
+    a[CAP * 4:CAP * 4 + 9] = np.array(CONF).reshape(-1)
+    a[CAP * 4 + 9:CAP * 4 + 12] = sums
+    return a
+
+
+@pytest.mark.parametrize("flavour", [T._TRAIN, T._EVAL], ids=["train", "eval"])
+def test_decode_helper_in_both_flavours(flavour):
+    table, conf = T._decode_packed(packed_array(flavour, [2, 4, 0]), CAP, 1, flavour)
+    assert table.tolist() == ROWS and conf.tolist() == CONF
+    table, conf = T._decode_packed(packed_array(flavour, [2 * 3, 2 * 9, 0], ROWS + [[1, 1, 1, 2]]), CAP, 2, flavour)       # two ranks, both at cursor 3 = capacity
+    assert table.shape == (3, 4) and table[2].tolist() == [1, 1, 1, 2]
+    with pytest.raises(L.MtbcError, match=flavour["cap"]) as e:
+        T._decode_packed(packed_array(flavour, [3, 9, 1]), CAP, 1, flavour)          # dropped = 1
+    assert "(1 dropped)" in str(e.value) and flavour["owner"] in str(e.value)
+    with pytest.raises(L.MtbcError, match=flavour["cap"]) as e:
+        T._decode_packed(packed_array(flavour, [4, 16, 0]), CAP, 1, flavour)         # cursor > capacity
+    assert "4 batches since" in str(e.value)
+    with pytest.raises(L.MtbcError, match="different numbers of batches"):
+        T._decode_packed(packed_array(flavour, [2 + 3, 4 + 9, 0]), CAP, 2, flavour)  # world 2, cursors 2 and 3
+    # the public layers decode the same arrays through it
+    if flavour is T._TRAIN:
+        m = T.train_metrics_from_packed(packed_array(flavour, [2, 4, 0]), CAP)
+        assert m.table.tolist() == ROWS and m.conf.tolist() == CONF and m.batches == 2
+        with pytest.raises(L.MtbcError, match="different numbers of batches"):
+            T.train_metrics_from_packed(packed_array(flavour, [2 + 3, 4 + 9, 0]), CAP, world=2)
+    else:
+        loss_rows = [[0.75, 0.5, 0.25, 0.0], [1.5, 1.0, 0.5, 0.0]]
+        losses = np.zeros(CAP * 4)
+        losses[:8] = np.array(loss_rows).reshape(-1)
+        assert T.eval_result_from_packed(packed_array(flavour, [2, 4, 0]), losses, CAP) == T.eval_result_from_counts(ROWS, CONF, loss_rows)
+        with pytest.raises(L.MtbcError, match="capacity"):
+            T.eval_result_from_packed(packed_array(flavour, [3, 9, 1]), losses, CAP)
+
+
+def stub_step(n, n_logits):
+    return types.SimpleNamespace(x=types.SimpleNamespace(data=torch.full((n, 1, 4, 5), -1.0)), mask=torch.full((n, 1, 4, 5), -1.0),
+                                 onehot=torch.full((n, n_logits), 7.0))
+
+
+def test_batch_fill_builds_the_target_and_leaves_nothing_stale():
+    g = torch.Generator().manual_seed(5)
+    image, mask = torch.rand(3, 1, 4, 5, generator=g), (torch.rand(3, 1, 4, 5, generator=g) < .5).float()
+    st = stub_step(3, 3)
+    T.fill_batch(st, image, mask, torch.tensor([2, 0, 1]), binary=False)
+    assert torch.equal(st.onehot, torch.nn.functional.one_hot(torch.tensor([2, 0, 1]), 3).float())
+    assert torch.equal(st.x.data, image) and torch.equal(st.mask, mask)
+    T.fill_batch(st, image, mask, torch.tensor([[1], [1], [0]]), binary=False)          # the loader's (N, 1) labels; no 1 survives from the first fill
+    assert torch.equal(st.onehot, torch.nn.functional.one_hot(torch.tensor([1, 1, 0]), 3).float())
+    sb = stub_step(3, 1)
+    T.fill_batch(sb, image, mask, torch.tensor([1, 0, 1]), binary=True)
+    assert sb.onehot.dtype == torch.float32 and torch.equal(sb.onehot, torch.tensor([[1.0], [0.0], [1.0]]))
+    assert torch.equal(sb.x.data, image) and torch.equal(sb.mask, mask)
+    T.fill_batch(sb, image, mask, torch.tensor([0, 1, 0]), binary=True)
+    assert torch.equal(sb.onehot, torch.tensor([[0.0], [1.0], [0.0]]))
+
+
+class Recorder:
+    """Stands in for `_capture`: records the capture, runs `body` once as a capture would record it, returns a graph that counts replays."""
+
+    def __init__(self):
+        self.captures = self.replays = 0
+
+    def __call__(self, body):
+        self.captures += 1
+        body()
+        return self
+
+    def replay(self):
+        self.replays += 1
+
+
+def test_graph_helper_runs_eager_twice_captures_once_then_replays():
+    owner, other = types.SimpleNamespace(_graphs={}), types.SimpleNamespace(_graphs={})
+    st = types.SimpleNamespace()
+    calls, rec = [], Recorder()
+    body = lambda: calls.append(1)
+    for n in (1, 2):
+        T.run_or_replay(owner, st, "k", body, capture=rec)
+        assert st._graph_ents[id(owner)] == ["k", n, None] and len(calls) == n and rec.captures == 0
+    assert owner._graphs[id(st)] is st._graph_ents[id(owner)]
+    T.run_or_replay(owner, st, "k", body, capture=rec)                  # the third call captures (body runs inside the capture) and replays
+    assert (rec.captures, rec.replays, len(calls)) == (1, 1, 3) and st._graph_ents[id(owner)] == ["k", 2, rec]
+    T.run_or_replay(owner, st, "k", body, capture=rec)                  # the fourth only replays
+    assert (rec.captures, rec.replays, len(calls)) == (1, 2, 3)
+    T.run_or_replay(other, st, "k", body, capture=rec)                  # a second owner on the same compiled step starts its own count
+    assert st._graph_ents[id(other)] == ["k", 1, None] and st._graph_ents[id(owner)][2] is rec and len(calls) == 4
+    assert other._graphs[id(st)] is st._graph_ents[id(other)]
+    T.run_or_replay(owner, st, "moved", body, capture=rec)              # a changed key drops the graph: eager again
+    assert st._graph_ents[id(owner)] == ["moved", 1, None] and owner._graphs[id(st)] is st._graph_ents[id(owner)]
+    assert (rec.captures, rec.replays, len(calls)) == (1, 2, 5)
+
+
+def test_train_and_eval_steps_build_the_same_fused_loss_settings():
+    w = torch.tensor([1.0, 2.0, 0.5])
+    settings = dict(alpha=0.35, iw=True, focal_weight=w, binary=False, cls_gamma=2.0, seg_criterion="FocalDICE")
+    train = T._fused_loss(types.SimpleNamespace(scaler=None, **settings))
+    evaluate = T._fused_loss(types.SimpleNamespace(**settings))          # the evaluation step has no scaler at all
+    assert train == evaluate == {"alpha": 0.35, "inversely_weighted": True, "focal_weight": w, "binary": False, "cls_gamma": 2.0,
+                                 "seg_criterion": "FocalDICE"}
+    assert list(train) == list(evaluate)
+    dynamic = T._fused_loss(types.SimpleNamespace(scaler=object(), **settings))
+    assert {k: v for k, v in dynamic.items() if k != "loss_scale"} == evaluate and dynamic["loss_scale"] == 1.0 and len(dynamic) == len(evaluate) + 1
+
+
+def test_head_and_criterion_rules_are_the_same_for_both_steps():
+    class Net:
+        n_classes = 3
+
+    class OneLogit:
+        n_classes = 1
+    w = torch.ones(3)
+    for owner in ("the fused step", "FusedEvalStep"):
+        assert T._check_heads(Net(), 3, "Focal", w, owner) == (False, 2.0, w)
+        assert T._check_heads(Net(), 3, "CE", None, owner) == (False, 0.0, None)
+        assert T._check_heads(OneLogit(), 2, "Focal", w, owner) == (True, 2.0, None)          # the binary head takes no class weights
+        with pytest.raises(ValueError, match="classification head"):
+            T._check_heads(Net(), 2, "Focal", None, owner)
+        with pytest.raises(ValueError, match="classification criterion"):
+            T._check_heads(Net(), 3, "BCE", None, owner)
+        with pytest.raises(NotImplementedError, match="CrossEntropyLoss"):
+            T._check_heads(Net(), 3, "CE", w, owner)
+        with pytest.raises(NotImplementedError, match="n_classes <= 3"):
+            T._check_heads(Net(), 4, "Focal", None, owner)
