@@ -198,4 +198,9 @@ bool mtbc_i_convT2_wgrad_ok(const mtbc_convT_args* a);
 void mtbc_i_convT2_wgrad_plan(const mtbc_convT_args* a, int* steps_per_split, int* nsplit);
 int mtbc_i_convT2_dgrad(const mtbc_convT_args* a, int compute, hipStream_t st);
 int mtbc_i_convT2_wgrad(const mtbc_convT_args* a, int compute, float* partial, float* dbias_part, int steps_per_split, int nsplit, hipStream_t st);
+// both gradients of one up-convolution from one read of dy (wg = the OP_CONVT_WGRAD arguments, dg = the OP_CONVT_DGRAD ones)
+bool mtbc_i_convT2_bwd_fused_ok(const mtbc_convT_args* wg, const mtbc_convT_args* dg);
+int mtbc_i_convT2_bwd_fused(const mtbc_convT_args* wg, const mtbc_convT_args* dg, float* partial, float* dbias_part, int steps_per_split, int nsplit, hipStream_t st);
+// pool_up.hip: a WGRAD op with the DGRAD op of the same up-convolution right behind it; *fused = false: nothing was issued, run them one by one
+int mtbc_i_convT_bwd_pair(const mtbc_convT_args* wg, const mtbc_convT_args* dg, void* stream, bool* fused);
 int mtbc_i_channel_sums(const float* x, float* planes_ws, float* out, int N, int C, int HW, int accumulate, hipStream_t st);

@@ -899,6 +899,239 @@ __global__ __launch_bounds__(256, 2) void convT2_dgrad_lds_kernel(const Ct2P p, 
     }
 }
 
+// ------------------------------------------------------------------ wgrad + dgrad from ONE read of dY (16-bit product path)
+// convT2_wgrad16_kernel and convT2_dgrad_lds_kernel each stream the same 16-bit dY, the large tensor of the pair.  Here the NW waves that
+// share one (48-input-channel block, split) of the weight gradient form a workgroup.  Every wave keeps the wgrad task it has in
+// convT2_wgrad16_kernel<LP, CT> -- same split plan, same channel tiles, same lane-group ownership of pixels 8kg .. 8kg+7, same MFMA
+// order, so the partial sums are that kernel's bit for bit -- and drops the dY registers of each 32-pixel step, as loaded, into a
+// double-buffered LDS image [(co, a)][pixel][b].  Behind one barrier per step that image IS the dgrad's fragment arrangement (lane
+// (j, kg): pixel pair j = 8 bytes of row (8s + 2kg + c, a)), the block's weight slice sits in LDS as in convT2_dgrad_lds_kernel, and
+// the waves run that kernel's chain s = 0 .. Cout/8 - 1 for the step's 32 pixels: NW == 3 -> wave = input-channel tile, both pixel
+// parities; NW == 6 -> wave = (tile, parity).  Same operands in the same order and the same store / accumulate: dx is bit-identical.
+// Slot t & 1 is written before barrier t and read after it; its previous readers (step t - 2) passed barrier t - 1 with their LDS
+// reads retired, so one barrier per step is enough.  `s_waitcnt lgkmcnt(0); s_barrier`, not __syncthreads(): the next step's global
+// loads stay in flight across it.  No branch around a load in the main loop (ACC is a template parameter for that reason); all loads
+// use the clamped indices of the two kernels.  Row strides: 160 bytes for dY rows, 8 Cout + 32 for weight rows, both == 2 (mod 4)
+// 16-byte pieces.
+constexpr int FDYROW = 80;             // 16-bit values per LDS row of dY: 32 pixels x 2 + 16 of padding
+template <int LP, int CT, int NW, bool ACC>
+__global__ __launch_bounds__(64 * NW) void convT2_bwd_fused_kernel(const Ct2P p, const int wrow) {
+    static_assert(LP != 0, "16-bit operands");
+    static_assert(NW == 3 || NW == 6, "3 input-channel tiles x 1 or 2 pixel parities");
+    constexpr int D = 2, NT = 64 * NW, NE = NW == 3 ? 2 : 1;
+    extern __shared__ __attribute__((aligned(16))) unsigned short Lf[];          // weights [48][wrow], then dY [2][2 Cout][FDYROW]
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j = lane & 15, kg = lane >> 4;
+    const int HW = p.H * p.W, oW = 2 * p.W, M4 = 4 * p.Cout;
+    const int steps_per_img = HW / 32;
+    // workgroups go to the XCDs round-robin: the mblocks blocks of a split (they read the same dY) share XCD split % 8
+    const int kb = (int)(blockIdx.x >> 3);
+    const int split = 8 * (kb / p.mblocks) + (int)(blockIdx.x & 7), mb = kb % p.mblocks;
+    if (split >= p.nsplit) return;
+    unsigned short* Wd = Lf;
+    unsigned short* Dy = Lf + 48 * wrow;
+    const int slot_elems = 2 * p.Cout * FDYROW;
+    const int ppr = M4 / 8, npieces = 48 * ppr;
+    for (int base = tid; base < npieces; base += NT * 4) {
+        float4 v[4][2];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int idx = min(base + NT * u, npieces - 1), r = idx / ppr, q = idx - r * ppr;
+            const float* src = p.w + (size_t)min(mb * 48 + r, p.Cin - 1) * M4 + 8 * q;
+            v[u][0] = ld4(src); v[u][1] = ld4(src + 4);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int idx = base + NT * u;
+            if (idx >= npieces) continue;
+            const int r = idx / ppr, q = idx - r * ppr;
+            ct_u32x4 o = {cvt_pk16<LP == 2>(v[u][0].x, v[u][0].y), cvt_pk16<LP == 2>(v[u][0].z, v[u][0].w),
+                          cvt_pk16<LP == 2>(v[u][1].x, v[u][1].y), cvt_pk16<LP == 2>(v[u][1].z, v[u][1].w)};
+            if (mb * 48 + r >= p.Cin) o = (ct_u32x4){0u, 0u, 0u, 0u};
+            *reinterpret_cast<ct_u32x4*>(Wd + (size_t)r * wrow + 8 * q) = o;
+        }
+    }
+    __syncthreads();
+
+    // ---- the wave's weight-gradient task: channel tiles wv * CT .. wv * CT + CT - 1 (all inside Cout: ctiles == NW * CT)
+    const int total_steps = p.N * steps_per_img;
+    const int g0 = split * p.steps_per_split, g1 = min(total_steps, g0 + p.steps_per_split);
+    bool rok[MT];
+    const unsigned short* xrow[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        const int ci = mb * 48 + m * 16 + j;
+        rok[m] = ci < p.Cin;
+        xrow[m] = reinterpret_cast<const unsigned short*>(p.x) + (size_t)(rok[m] ? ci : 0) * HW + 8 * kg;
+    }
+    int co[CT];
+    const unsigned short* dcol[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+        co[c] = (wv * CT + c) * 8 + (j >> 1);
+        dcol[c] = reinterpret_cast<const unsigned short*>(p.dy) + (size_t)co[c] * 4 * HW + (size_t)(j & 1) * oW;
+    }
+    f32x4 acc[CT][MT][2];
+#pragma unroll
+    for (int c = 0; c < CT; ++c)
+#pragma unroll
+        for (int m = 0; m < MT; ++m) { acc[c][m][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[c][m][1] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+    const bool want_bias = p.dbias_part != nullptr && mb == 0;      // uniform
+    float bsum[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) bsum[c] = 0.f;
+    // ---- the wave's input-gradient share: tile dm (16 input channels), NE pixel parities starting at de
+    const int dm = NW == 3 ? wv : wv % 3, de = NW == 3 ? 0 : wv / 3;
+    const unsigned short* arow = Wd + (size_t)(dm * 16 + j) * wrow + 8 * kg;
+    unsigned short* dyw = Dy + (size_t)(wv * CT * 16 + j) * FDYROW + 16 * kg;          // + c * 16 rows: this lane's 32 bytes of row (co[c], a)
+    const unsigned short* dyr = Dy + (size_t)(4 * kg) * FDYROW + 4 * j;                // + 16 s rows + (2c + a) rows
+    const int nsteps = p.Cout / 8;
+
+    ct_u32x4 rx[D][MT], rh[D][CT][2];
+    float old[4][NE];
+    auto load = [&](int g, auto SL) {
+        constexpr int slot = decltype(SL)::value;
+        const int n = g / steps_per_img, st = g % steps_per_img;
+        const int pix = st * 32 + 8 * kg;
+        const int i = pix / p.W, jx = pix % p.W;
+#pragma unroll
+        for (int m = 0; m < MT; ++m) rx[slot][m] = *reinterpret_cast<const ct_u32x4*>(xrow[m] + (size_t)n * p.xbs + st * 32);
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+            const unsigned short* q = dcol[c] + (size_t)n * p.dybs + (size_t)(2 * i) * oW + 2 * jx;
+            rh[slot][c][0] = *reinterpret_cast<const ct_u32x4*>(q); rh[slot][c][1] = *reinterpret_cast<const ct_u32x4*>(q + 8);
+        }
+    };
+    auto dx_of = [&](int g) {
+        const int n = g / steps_per_img, st = g % steps_per_img;
+        return p.dx + (size_t)n * p.dxbs + st * 32 + 2 * j + de;
+    };
+    auto load_old = [&](int g) {            // the read half of the dgrad's read-modify-write, issued a step's work ahead of its use
+        if constexpr (ACC) {
+            const float* dxn = dx_of(g);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float* q = dxn + (size_t)min(mb * 48 + dm * 16 + kg * 4 + r, p.Cin - 1) * HW;
+                if constexpr (NE == 2) { const float2 o = *reinterpret_cast<const float2*>(q); old[r][0] = o.x; old[r][1] = o.y; }
+                else old[r][0] = *q;
+            }
+        }
+    };
+    auto compute = [&](int t, auto SL) {      // step t of the split: wgrad MFMAs, and the dY registers into LDS slot t & 1
+        constexpr int cur = decltype(SL)::value;
+        Frag<LP> fa[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const ct_u32x4 w = rx[cur][m];
+            frag_from_words<LP>(fa[m], rok[m] ? w[0] : 0u, rok[m] ? w[1] : 0u, rok[m] ? w[2] : 0u, rok[m] ? w[3] : 0u);
+        }
+        unsigned short* sw = dyw + (size_t)(t & 1) * slot_elems;
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+            *reinterpret_cast<ct_u32x4*>(sw + (size_t)(c * 16) * FDYROW) = rh[cur][c][0];
+            *reinterpret_cast<ct_u32x4*>(sw + (size_t)(c * 16) * FDYROW + 8) = rh[cur][c][1];
+            unsigned d[8], w0[4], w1[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { d[k] = rh[cur][c][0][k]; d[4 + k] = rh[cur][c][1][k]; }
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                w0[m] = (d[2 * m] & 0xffffu) | (d[2 * m + 1] << 16);
+                w1[m] = (d[2 * m] >> 16) | (d[2 * m + 1] & 0xffff0000u);
+            }
+            if (want_bias) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) bsum[c] += sum2_16<LP>(d[k]);
+            }
+            Frag<LP> f0, f1;
+            frag_from_words<LP>(f0, w0[0], w0[1], w0[2], w0[3]);
+            frag_from_words<LP>(f1, w1[0], w1[1], w1[2], w1[3]);
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                acc[c][m][0] = Frag<LP>::mma(fa[m], f0, acc[c][m][0]);
+                acc[c][m][1] = Frag<LP>::mma(fa[m], f1, acc[c][m][1]);
+            }
+        }
+    };
+    auto dgrad = [&](int g, int t) {          // dx of the step's 32 pixels from LDS slot t & 1
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        const unsigned short* sr = dyr + (size_t)(t & 1) * slot_elems;
+        f32x4 da[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) da[e] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int s = 0; s < nsteps; ++s) {
+            uint2 h[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) h[r] = *reinterpret_cast<const uint2*>(sr + (size_t)(16 * s + r) * FDYROW);
+            Frag<LP> fa;
+            fa.v = __builtin_bit_cast(decltype(fa.v), *reinterpret_cast<const ct_u32x4*>(arow + 32 * s));
+            if constexpr (NE == 2) {
+                Frag<LP> fe, fo;
+                frag_from_words<LP>(fe, h[0].x, h[1].x, h[2].x, h[3].x);
+                frag_from_words<LP>(fo, h[0].y, h[1].y, h[2].y, h[3].y);
+                da[0] = Frag<LP>::mma(fa, fe, da[0]);
+                da[1] = Frag<LP>::mma(fa, fo, da[1]);
+            } else {
+                Frag<LP> fb;
+                frag_from_words<LP>(fb, de ? h[0].y : h[0].x, de ? h[1].y : h[1].x, de ? h[2].y : h[2].x, de ? h[3].y : h[3].x);
+                da[0] = Frag<LP>::mma(fa, fb, da[0]);
+            }
+        }
+        float* dxn = dx_of(g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ci = mb * 48 + dm * 16 + kg * 4 + r;
+            if (ci >= p.Cin) continue;
+            float* q = dxn + (size_t)ci * HW;
+            if constexpr (NE == 2) {
+                float2 v = make_float2(da[0][r], da[1][r]);
+                if constexpr (ACC) { v.x += old[r][0]; v.y += old[r][1]; }
+                *reinterpret_cast<float2*>(q) = v;
+            } else {
+                float v = da[0][r];
+                if constexpr (ACC) v += old[r][0];
+                *q = v;
+            }
+        }
+    };
+    {
+        const int last = g1 - 1;
+        sfor<D - 1>([&](auto U) { load(min(g0 + (int)U.value, last), U); });
+        int g = g0;
+        for (; g + D <= g1; g += D)
+            sfor<D>([&](auto U) {
+                constexpr int u = decltype(U)::value;
+                load_old(g + u);
+                load(min(g + u + D - 1, last), SC<(u + D - 1) % D>{});
+                __builtin_amdgcn_sched_barrier(0);
+                compute(g + u - g0, U);
+                dgrad(g + u, g + u - g0);
+                __builtin_amdgcn_sched_barrier(0);
+            });
+        sfor<D - 1>([&](auto U) {
+            if (g + U.value < g1) { load_old(g + U.value); compute(g + U.value - g0, U); dgrad(g + U.value, g + U.value - g0); }
+        });
+    }
+    float* part = p.partial + (size_t)split * p.Cin * p.Cout * 4;
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+        if (want_bias) {                   // lanes (co, a) x 4 pixel groups -> one value per channel, fixed shuffle tree
+            float b = bsum[c];
+            b += __shfl_xor(b, 16);
+            b += __shfl_xor(b, 32);
+            b += __shfl_xor(b, 1);
+            if (kg == 0 && (j & 1) == 0) p.dbias_part[(size_t)split * p.Cout + co[c]] = b;
+        }
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int ci = mb * 48 + m * 16 + kg * 4 + r;
+                if (ci >= p.Cin) continue;
+                *reinterpret_cast<float2*>(part + ((size_t)ci * p.Cout + co[c]) * 4 + 2 * (j & 1)) = make_float2(acc[c][m][0][r], acc[c][m][1][r]);
+            }
+    }
+}
+
 bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 void fill(const mtbc_convT_args* a, Ct2P* p) {
@@ -924,6 +1157,36 @@ bool mtbc_i_convT2_wgrad_ok(const mtbc_convT_args* a) {
     return a->k == 2 && HW % 32 == 0 && a->W % 8 == 0 && al16(a->dy) && al16(a->x) && a->dy_batch_stride % 4 == 0 &&
            a->x_batch_stride % 4 == 0;
 }
+// Both gradients from one launch (convT2_bwd_fused_kernel): the 16-bit product path only -- dy and x as 16-bit planes of the compute
+// type -- where BOTH kernels above take the shape and the dgrad would run with its weights in LDS (Cout % 8 == 0, the slice fits).  The
+// workgroup is the wgrad's wave tasks of one (input block, split): Cout / 8 channel tiles, 2 per wave when even, must make 3 or 6 waves
+// (Cout = 24, 48, 96), and the weight slice plus two dY step images must fit beside each other.  wg / dg must describe the same
+// problem; everything else keeps the two launches.
+constexpr int FUSED_MIN_BLOCKS = 256;      // one workgroup per CU of the MI355X
+static int fused_ct(const mtbc_convT_args* a) { return (a->Cout / 8) % 2 == 0 ? 2 : 1; }
+static size_t fused_lds(const mtbc_convT_args* a) { return (size_t)48 * (4 * a->Cout + 16) * 2 + (size_t)2 * 2 * a->Cout * FDYROW * 2; }
+bool mtbc_i_convT2_bwd_fused_ok(const mtbc_convT_args* wg, const mtbc_convT_args* dg) {
+    if (wg->N != dg->N || wg->H != dg->H || wg->W != dg->W || wg->Cin != dg->Cin || wg->Cout != dg->Cout || wg->k != dg->k ||
+        wg->compute != dg->compute || wg->dy != dg->dy || wg->dy_batch_stride != dg->dy_batch_stride || wg->dy_type16 != dg->dy_type16 ||
+        wg->w != dg->w) return false;
+    if (wg->compute != 1 && wg->compute != 2) return false;
+    if (wg->dy_type16 != wg->compute || wg->x_type16 != wg->compute) return false;
+    if (!mtbc_i_convT2_wgrad_ok(wg) || !mtbc_i_convT2_dgrad_ok(dg)) return false;
+    if (wg->Cout % 8 != 0) return false;
+    const int nw = wg->Cout / 8 / fused_ct(wg);
+    if (nw != 3 && nw != 6) return false;
+    if (fused_lds(wg) > 104 * 1024) return false;
+    // The fused launch has the weight gradient's parallelism only: nsplit x (blocks of 48 input channels) workgroups, each a serial chain
+    // of steps_per_split {load, barrier, dx} rounds, where the dgrad alone spreads every 32-pixel task over the chip.  With fewer workgroups
+    // than CUs AND chains longer than the plan's floor of 8 steps the pair is faster as two launches (bench plan, 192 -> 96 @32x32: 128
+    // workgroups of 32 steps, 72 us fused against 38 + 20 us; 96 -> 48 @64x64, 256 workgroups: 54 against 39 + 25; 48 -> 48 @128x128,
+    // 512 workgroups: 101 against 67 + 61).
+    static const bool all = mtbc_probe_set("MTBC_CT_FUSE_ALL");      // A/B: every eligible shape
+    int sps, ns; mtbc_i_convT2_wgrad_plan(wg, &sps, &ns);
+    if (!all && (long long)ns * cdiv(wg->Cin, 48) < FUSED_MIN_BLOCKS && sps > 8) return false;
+    return true;
+}
+
 // 32-pixel steps per split: ~4096 wave tasks in flight, at least 8 steps each (the partial sums are real traffic).  With both tensors
 // as 16-bit planes (convT2_wgrad16_kernel) the inputs are half the bytes and the partials weigh twice as much: 1536 tasks
 // (sweep 512 .. 16384 per step of the bench: 1.16 / 0.65 / 0.50 / 0.52 / 0.55 / 0.67 / 0.75 ms at 512 / 1024 / 1536 / 2048 / 4096 / 8192 / 16384).
@@ -1101,6 +1364,35 @@ int mtbc_i_convT2_wgrad(const mtbc_convT_args* a, int compute, float* partial, f
     } else if (compute == 1) hipLaunchKernelGGL(convT2_wgrad_kernel<1>, dim3(blocks), dim3(256), 0, st, p);
     else if (compute == 2) hipLaunchKernelGGL(convT2_wgrad_kernel<2>, dim3(blocks), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(convT2_wgrad_kernel<0>, dim3(blocks), dim3(256), 0, st, p);
+    MTBC_CHECK_LAUNCH();
+    return MTBC_OK;
+}
+
+int mtbc_i_convT2_bwd_fused(const mtbc_convT_args* wg, const mtbc_convT_args* dg, float* partial, float* dbias_part, int steps_per_split, int nsplit, hipStream_t st) {
+    if (!mtbc_i_convT2_bwd_fused_ok(wg, dg)) return MTBC_E_UNSUPPORTED;
+    Ct2P p; fill(wg, &p);
+    p.dx = dg->dx; p.dxbs = dg->dx_batch_stride; p.acc_dx = dg->accumulate_dx;
+    p.partial = partial; p.dbias_part = dbias_part; p.steps_per_split = steps_per_split; p.nsplit = nsplit;
+    const int ctn = fused_ct(wg), nw = p.ctiles / ctn, compute = wg->compute;
+    const int wrow = 4 * wg->Cout + 16;
+    const size_t lds = fused_lds(wg);
+    const long long nblocks = 8ll * cdiv(nsplit, 8) * p.mblocks;
+    if (nblocks >= (1ll << 31)) return MTBC_E_UNSUPPORTED;
+    const dim3 grid((unsigned)nblocks);
+    const bool acc = dg->accumulate_dx != 0;
+#define MTBC_CT2BF(LP_, CT_, NW_, ACC_)                                                                                  \
+    do {                                                                                                                 \
+        MTBC_ENSURE_DYN_LDS((&convT2_bwd_fused_kernel<LP_, CT_, NW_, ACC_>), 104 * 1024);                                \
+        hipLaunchKernelGGL((convT2_bwd_fused_kernel<LP_, CT_, NW_, ACC_>), grid, dim3(64 * NW_), lds, st, p, wrow);      \
+    } while (0)
+#define MTBC_CT2BF_SHAPE(LP_, ACC_)                                                                                      \
+    do {                                                                                                                 \
+        if (ctn == 1) MTBC_CT2BF(LP_, 1, 3, ACC_); else if (nw == 3) MTBC_CT2BF(LP_, 2, 3, ACC_); else MTBC_CT2BF(LP_, 2, 6, ACC_); \
+    } while (0)
+    if (compute == 1) { if (acc) MTBC_CT2BF_SHAPE(1, true); else MTBC_CT2BF_SHAPE(1, false); }
+    else { if (acc) MTBC_CT2BF_SHAPE(2, true); else MTBC_CT2BF_SHAPE(2, false); }
+#undef MTBC_CT2BF_SHAPE
+#undef MTBC_CT2BF
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }

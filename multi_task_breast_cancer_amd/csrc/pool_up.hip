@@ -510,6 +510,31 @@ int mtbc_conv1x1_wgrad(const mtbc_conv1x1_args* a, void* stream) {
 
 }  // extern "C"
 
+// The program runner's pair: an OP_CONVT_WGRAD with the OP_CONVT_DGRAD of the same up-convolution right behind it.  Where convt2.hip's
+// fused kernel takes the pair, dy is read once: one launch writes the split partials (the plan and the workspace layout of
+// mtbc_convT_wgrad) and dx, and the same split-K reductions follow.  Results are bit-identical to the two entry points above, so it
+// does not matter to a caller which way a pair ran.  Anything the fused path does not take -- an argument error included -- is left
+// to the two entry points: *fused stays false and nothing has been issued.
+int mtbc_i_convT_bwd_pair(const mtbc_convT_args* wg, const mtbc_convT_args* dg, void* stream, bool* fused) {
+    *fused = false;
+    CtP p;
+    if (fill_ct(wg, &p) != MTBC_OK || fill_ct(dg, &p) != MTBC_OK) return MTBC_OK;
+    if (!wg->x || !wg->dy || !wg->dw || !dg->dy || !dg->w || !dg->dx) return MTBC_OK;
+    static const bool generic = mtbc_probe_set("MTBC_CONVT_GENERIC");      // A/B switches
+    static const bool unfused = mtbc_probe_set("MTBC_CT_UNFUSED");
+    if (generic || unfused || !mtbc_i_convT2_bwd_fused_ok(wg, dg)) return MTBC_OK;
+    if (!wg->workspace || wg->workspace_bytes < mtbc_convT_wgrad_workspace(wg)) return MTBC_OK;
+    fill_ct(wg, &p);
+    hipStream_t st = (hipStream_t)stream;
+    int sps, nsplit; mtbc_i_convT2_wgrad_plan(wg, &sps, &nsplit);
+    float* partial = reinterpret_cast<float*>(wg->workspace);
+    float* bpart = wg->dbias ? partial + (size_t)nsplit * wg->Cin * p.M : nullptr;
+    *fused = true;
+    int rc = mtbc_i_convT2_bwd_fused(wg, dg, partial, bpart, sps, nsplit, st); if (rc) return rc;
+    if (bpart) { rc = mtbc_i_splitk_reduce(bpart, wg->dbias, nsplit, (size_t)wg->Cout, wg->accumulate_dw, st); if (rc) return rc; }
+    return mtbc_i_splitk_reduce(partial, wg->dw, nsplit, (size_t)wg->Cin * p.M, wg->accumulate_dw, st);
+}
+
 // ---------------------------------------------------------------- fused ConvT + 1x1 head (MTnnUNet deep supervision)
 namespace {
 __global__ void head_combine_kernel(const mtbc_head_fuse_args a) {

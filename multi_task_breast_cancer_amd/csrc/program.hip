@@ -101,6 +101,14 @@ int mtbc_program_run_ms(const mtbc_op* ops, int32_t first, int32_t count, void* 
             i += n - 1;
             continue;
         }
+        if (o->kind == MTBC_OP_CONVT_WGRAD && i + 1 < first + count && ops[i + 1].kind == MTBC_OP_CONVT_DGRAD) {
+            // ... and the two gradients of one up-convolution, both inside this range, read dy once where the fused kernel takes them
+            // (bit-identical to the two launches, so a range boundary between the two ops changes nothing but the speed)
+            bool fused = false;
+            rc = mtbc_i_convT_bwd_pair(&o->u.convT, &ops[i + 1].u.convT, stream, &fused);
+            if (rc != MTBC_OK) { if (failed_index) *failed_index = i; return rc; }
+            if (fused) { ++i; continue; }
+        }
         switch (o->kind) {
             case MTBC_OP_CONV3_FWD: rc = mtbc_conv3x3_fwd(&o->u.conv3, stream); break;
             case MTBC_OP_CONV3_DGRAD: rc = mtbc_conv3x3_dgrad(&o->u.conv3, stream); break;
