@@ -414,6 +414,18 @@ size_t mtbc_convT_wgrad_workspace(const mtbc_convT_args* a);
 int mtbc_convT_fwd(const mtbc_convT_args* a, void* stream);
 int mtbc_convT_dgrad(const mtbc_convT_args* a, void* stream);
 int mtbc_convT_wgrad(const mtbc_convT_args* a, void* stream);
+/* Host-only plan query: every launch mtbc_convT_fwd / _dgrad / _wgrad (op = MTBC_OP_CONVT_FWD / _DGRAD / _WGRAD) would make for these
+ * arguments, written to buf (NUL-terminated) and joined with " + ".  Kernels are spelled as a profiler spells the instance without
+ * namespace and argument list, e.g. "convT2_bwd_fused_kernel<1, 2, 3, true>"; the follow-up launches are "splitk_reduce" (once for dW,
+ * once more for a bias gradient the kernel summed on the way) and "channel_sums" (the bias gradient's own pass).  The plan facts that
+ * select code paths inside a split-K kernel without being template arguments follow its name in brackets: "[splits=1]" or "[splits>1]",
+ * with "xcd " in front where a split's tasks are ordered onto one XCD ("[xcd splits>1]").  dgrad_next (op = MTBC_OP_CONVT_WGRAD only, else
+ * ignored; may be NULL): the arguments of the MTBC_OP_CONVT_DGRAD right behind the weight gradient in a program -- the name is then what
+ * mtbc_program_run makes of the pair, the fused kernel where it takes it and the two calls' launches otherwise.  Launches nothing, never
+ * synchronises, needs no device and never dereferences a tensor pointer (pointer VALUES count: NULL and alignment select branches);
+ * returns the code the real call would return when it refuses the arguments, MTBC_E_BADARG for an unknown op or a buffer shorter than
+ * the name. */
+int mtbc_convT_kernel_name(const mtbc_convT_args* a, int32_t op, const mtbc_convT_args* dgrad_next, char* buf, int32_t len);
 
 /* -------------------------------------------------------------------------- conv 1x1 + bias
  * replaces nn.Conv2d(k=1): MTnnUNet.py:6-9,106-118 ; MTUNetPlusPlus.py:73-76 (Cout = regions) */

@@ -281,7 +281,7 @@ EXPORTS = [
     "mtbc_conv3x3_packed_elems", "mtbc_conv3x3_packed_dgrad_elems", "mtbc_conv3x3_pack_fwd",
     "mtbc_conv3x3_pack_dgrad", "mtbc_conv3x3_packed_lp_elems", "mtbc_conv3x3_pack_lp", "mtbc_conv3x3_pack_many", "mtbc_c8_pack", "mtbc_c8_unpack", "mtbc_c8_pack16", "mtbc_conv3x3_weight_view", "mtbc_conv3x3_weight_view_many", "mtbc_augment_flip_rotate", "mtbc_convT_head_combine", "mtbc_convT_head_expand", "mtbc_conv3x3_wgrad_workspace", "mtbc_conv3x3_wgrad_sync_bytes", "mtbc_conv3x3_stats_slots", "mtbc_conv3x3_kernel_name", "mtbc_conv3x3_fwd", "mtbc_conv3x3_dgrad",
     "mtbc_conv3x3_wgrad", "mtbc_instnorm_fwd_workspace", "mtbc_instnorm_coop_state_bytes", "mtbc_instnorm_coop_error_offset", "mtbc_instnorm_c8_supported", "mtbc_instnorm_bwd_team", "mtbc_instnorm_dparam_many", "mtbc_instnorm_kernel_name", "mtbc_instnorm_lrelu_fwd", "mtbc_instnorm_lrelu_bwd", "mtbc_maxpool2_fwd",
-    "mtbc_maxpool2_bwd", "mtbc_convT_wgrad_workspace", "mtbc_convT_fwd_c8_supported", "mtbc_convT_fwd", "mtbc_convT_dgrad", "mtbc_convT_wgrad",
+    "mtbc_maxpool2_bwd", "mtbc_convT_wgrad_workspace", "mtbc_convT_fwd_c8_supported", "mtbc_convT_kernel_name", "mtbc_convT_fwd", "mtbc_convT_dgrad", "mtbc_convT_wgrad",
     "mtbc_conv1x1_wgrad_workspace", "mtbc_conv1x1_fwd", "mtbc_conv1x1_dgrad", "mtbc_conv1x1_wgrad",
     "mtbc_gap_fwd", "mtbc_gap_bwd", "mtbc_linear_fwd", "mtbc_linear_bwd", "mtbc_dice_fwd", "mtbc_dice_bwd",
     "mtbc_focal_fwd_bwd", "mtbc_loss_mix", "mtbc_loss_scale_begin", "mtbc_loss_scale_check",
@@ -332,6 +332,8 @@ def load() -> C.CDLL:
     lib.mtbc_conv3x3_kernel_name.argtypes = [C.POINTER(Conv3x3Args), C.c_int32, C.c_char_p, C.c_int32]
     lib.mtbc_instnorm_kernel_name.restype = C.c_int
     lib.mtbc_instnorm_kernel_name.argtypes = [C.POINTER(InstNormArgs), C.c_int32, C.c_char_p, C.c_int32]
+    lib.mtbc_convT_kernel_name.restype = C.c_int
+    lib.mtbc_convT_kernel_name.argtypes = [C.POINTER(ConvTArgs), C.c_int32, C.POINTER(ConvTArgs), C.c_char_p, C.c_int32]
     lib.mtbc_instnorm_fwd_workspace.restype = C.c_size_t
     lib.mtbc_instnorm_fwd_workspace.argtypes = [C.POINTER(InstNormArgs)]
     lib.mtbc_augment_flip_rotate.restype = C.c_int

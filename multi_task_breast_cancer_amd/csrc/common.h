@@ -186,21 +186,41 @@ int mtbc_i_conv1x1_c8_wgrad(const mtbc_conv1x1_args* a, hipStream_t st);
 int mtbc_i_splitk_reduce(const float* partial, float* out, int nsplit, size_t elems, int accumulate, hipStream_t st);
 // rows of elems1 + elems2 floats per split: [0, elems1) summed into out, the rest into out2
 int mtbc_i_splitk_reduce2(const float* partial, float* out, float* out2, int nsplit, size_t elems1, size_t elems2, int accumulate, hipStream_t st);
+// Which launches a ConvTranspose call makes: the kernel instances (family + template arguments) and the plan facts that select code paths
+// inside a kernel without being template arguments.  Every dispatcher of convt2.hip and the ConvT entry points of pool_up.hip fill ONE
+// ConvTChoice first; the launch code then reads the kernels from it, and mtbc_convT_kernel_name() -- the same dispatchers called with
+// `query` -- prints it: the name cannot drift from the launch (NormChoice above, KernelChoice of conv3x3.hip).
+enum ConvTKernel {
+    CTK_FWD_LP_C8, CTK_FWD_C8, CTK_FWD_LDS,                  // convt2.hip forward: <MTC, F16>, <KI, F16>, <KI>
+    CTK_DGRAD_LDS, CTK_DGRAD2,                               // <LP, D>, <LP, DY16, D>
+    CTK_WGRAD16, CTK_WGRAD2, CTK_BWD_FUSED,                  // <LP, CT, D>, <LP, DY16, D>, <LP, CT, NW, ACC>
+    CTK_FWD, CTK_DGRAD, CTK_WGRAD,                           // pool_up.hip, the generic GEMM: <KS>
+    CTK_SPLITK, CTK_CHANNEL_SUMS                             // reduce.hip follow-ups
+};
+struct ConvTLaunch { int k; int t[4]; int xcd, splits; };      // xcd: p.xcd_tasks is set; splits > 0: a split-K kernel, printed as [splits=1] / [splits>1]
+struct ConvTChoice {
+    static constexpr int MAX = 4;          // (a pair makes at most 4 launches: two kernels and two reductions; one more is a programming error)
+    int n; ConvTLaunch l[MAX];
+    void add(int k, int t0 = 0, int t1 = 0, int t2 = 0, int t3 = 0) { if (n == MAX) abort(); l[n++] = ConvTLaunch{k, {t0, t1, t2, t3}, 0, 0}; }
+    void add(const ConvTLaunch& k) { if (n == MAX) abort(); l[n++] = k; }
+    ConvTLaunch& last() { return l[n - 1]; }
+};
 // convt2.hip: ConvTranspose k == s == 2 backward, operands straight from HBM into MFMA fragments
+// query != NULL (every launcher below): append the launch to *query and return without touching the stream or the device
 bool mtbc_i_convT2_fwd_ok(const mtbc_convT_args* a);
-int mtbc_i_convT2_fwd(const mtbc_convT_args* a, hipStream_t st);
+int mtbc_i_convT2_fwd(const mtbc_convT_args* a, hipStream_t st, ConvTChoice* query);
 bool mtbc_i_convT2_fwd_c8_ok(const mtbc_convT_args* a);
-int mtbc_i_convT2_fwd_c8(const mtbc_convT_args* a, hipStream_t st);
+int mtbc_i_convT2_fwd_c8(const mtbc_convT_args* a, hipStream_t st, ConvTChoice* query);
 bool mtbc_i_convT2_fwd_lp_c8_ok(const mtbc_convT_args* a);
-int mtbc_i_convT2_fwd_lp_c8(const mtbc_convT_args* a, hipStream_t st);
+int mtbc_i_convT2_fwd_lp_c8(const mtbc_convT_args* a, hipStream_t st, ConvTChoice* query);
 bool mtbc_i_convT2_dgrad_ok(const mtbc_convT_args* a);
 bool mtbc_i_convT2_wgrad_ok(const mtbc_convT_args* a);
 void mtbc_i_convT2_wgrad_plan(const mtbc_convT_args* a, int* steps_per_split, int* nsplit);
-int mtbc_i_convT2_dgrad(const mtbc_convT_args* a, int compute, hipStream_t st);
-int mtbc_i_convT2_wgrad(const mtbc_convT_args* a, int compute, float* partial, float* dbias_part, int steps_per_split, int nsplit, hipStream_t st);
+int mtbc_i_convT2_dgrad(const mtbc_convT_args* a, int compute, hipStream_t st, ConvTChoice* query);
+int mtbc_i_convT2_wgrad(const mtbc_convT_args* a, int compute, float* partial, float* dbias_part, int steps_per_split, int nsplit, hipStream_t st, ConvTChoice* query);
 // both gradients of one up-convolution from one read of dy (wg = the OP_CONVT_WGRAD arguments, dg = the OP_CONVT_DGRAD ones)
 bool mtbc_i_convT2_bwd_fused_ok(const mtbc_convT_args* wg, const mtbc_convT_args* dg);
-int mtbc_i_convT2_bwd_fused(const mtbc_convT_args* wg, const mtbc_convT_args* dg, float* partial, float* dbias_part, int steps_per_split, int nsplit, hipStream_t st);
+int mtbc_i_convT2_bwd_fused(const mtbc_convT_args* wg, const mtbc_convT_args* dg, float* partial, float* dbias_part, int steps_per_split, int nsplit, hipStream_t st, ConvTChoice* query);
 // pool_up.hip: a WGRAD op with the DGRAD op of the same up-convolution right behind it; *fused = false: nothing was issued, run them one by one
-int mtbc_i_convT_bwd_pair(const mtbc_convT_args* wg, const mtbc_convT_args* dg, void* stream, bool* fused);
+int mtbc_i_convT_bwd_pair(const mtbc_convT_args* wg, const mtbc_convT_args* dg, void* stream, bool* fused, ConvTChoice* query = nullptr);
 int mtbc_i_channel_sums(const float* x, float* planes_ws, float* out, int N, int C, int HW, int accumulate, hipStream_t st);

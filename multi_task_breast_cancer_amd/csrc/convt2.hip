@@ -1210,20 +1210,24 @@ bool mtbc_i_convT2_fwd_ok(const mtbc_convT_args* a) {
     return a->k == 2 && HW % 32 == 0 && a->W % 2 == 0 && a->Cin % 4 == 0 && a->Cin <= 4 * FKI && 4 * a->Cout <= 16 * FMT &&
            al16(a->x) && al16(a->y) && al16(a->w) && a->x_batch_stride % 2 == 0 && a->y_batch_stride % 4 == 0;
 }
-int mtbc_i_convT2_fwd(const mtbc_convT_args* a, hipStream_t st) {
+int mtbc_i_convT2_fwd(const mtbc_convT_args* a, hipStream_t st, ConvTChoice* query) {
+    const int ki = cdiv(a->Cin, 4);
+    ConvTChoice ch{};
+    ch.add(CTK_FWD_LDS, ki <= 8 ? 8 : ki <= 12 ? 12 : 16);
+    if (query) { query->add(ch.l[0]); return MTBC_OK; }
     Ct2P p; fill(a, &p);
     const int wstride = (4 * a->Cout + 31) / 32 * 32 + 16;             // == 16 mod 32
     const size_t lds = (size_t)a->Cin * wstride * sizeof(float);
     const long long groups = (long long)a->N * (a->H * a->W / 32);
     int blocks = (int)(groups < 4 * 512 ? cdiv64(groups, 4) : 512);      // 2 resident blocks per CU (register-limited)
-    const int ki = cdiv(a->Cin, 4);
 #define MTBC_CT2F(KI_)                                                                                                     \
     do {                                                                                                                   \
         MTBC_ENSURE_DYN_LDS((&convT2_fwd_lds_kernel<KI_>), 64 * 1024);                                                     \
         hipLaunchKernelGGL(convT2_fwd_lds_kernel<KI_>, dim3(blocks), dim3(256), lds, st, p, a->bias, a->y,                 \
                            (long long)a->y_batch_stride, wstride);                                                         \
     } while (0)
-    if (ki <= 8) MTBC_CT2F(8); else if (ki <= 12) MTBC_CT2F(12); else MTBC_CT2F(16);
+    const int kin = ch.l[0].t[0];
+    if (kin == 8) MTBC_CT2F(8); else if (kin == 12) MTBC_CT2F(12); else MTBC_CT2F(16);
 #undef MTBC_CT2F
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
@@ -1235,14 +1239,17 @@ bool mtbc_i_convT2_fwd_c8_ok(const mtbc_convT_args* a) {
     return a->k == 2 && HW % 32 == 0 && a->Cin % 4 == 0 && a->Cin <= 4 * FKI && 4 * cp <= 16 * FMT && a->Cout % 8 == 0 &&
            (a->y_type == 1 || a->y_type == 2) && al16(a->y) && a->y_batch_stride % 8 == 0;
 }
-int mtbc_i_convT2_fwd_c8(const mtbc_convT_args* a, hipStream_t st) {
+int mtbc_i_convT2_fwd_c8(const mtbc_convT_args* a, hipStream_t st, ConvTChoice* query) {
+    const int ki = cdiv(a->Cin, 4);
+    ConvTChoice ch{};
+    ch.add(CTK_FWD_C8, ki <= 8 ? 8 : ki <= 12 ? 12 : 16, a->y_type == 2);
+    if (query) { query->add(ch.l[0]); return MTBC_OK; }
     Ct2P p; fill(a, &p);
     const int cp = (a->Cout + 15) / 16 * 16;
     const int wstride = (4 * cp + 31) / 32 * 32 + 16;                  // == 16 mod 32
     const size_t lds = ((size_t)a->Cin * wstride + cp) * sizeof(float);
     const long long groups = (long long)a->N * (a->H * a->W / 32);
     int blocks = (int)(groups < 4 * 512 ? cdiv64(groups, 4) : 512);      // 2 resident blocks per CU (register-limited)
-    const int ki = cdiv(a->Cin, 4);
     unsigned short* y8 = reinterpret_cast<unsigned short*>(a->y);
 #define MTBC_CT2F8(KI_, F16_)                                                                                              \
     do {                                                                                                                   \
@@ -1250,8 +1257,9 @@ int mtbc_i_convT2_fwd_c8(const mtbc_convT_args* a, hipStream_t st) {
         hipLaunchKernelGGL((convT2_fwd_c8_kernel<KI_, F16_>), dim3(blocks), dim3(256), lds, st, p, a->bias, y8,            \
                            (long long)a->y_batch_stride, wstride, cp);                                                     \
     } while (0)
-    if (a->y_type == 2) { if (ki <= 8) MTBC_CT2F8(8, true); else if (ki <= 12) MTBC_CT2F8(12, true); else MTBC_CT2F8(16, true); }
-    else { if (ki <= 8) MTBC_CT2F8(8, false); else if (ki <= 12) MTBC_CT2F8(12, false); else MTBC_CT2F8(16, false); }
+    const int kin = ch.l[0].t[0];
+    if (ch.l[0].t[1]) { if (kin == 8) MTBC_CT2F8(8, true); else if (kin == 12) MTBC_CT2F8(12, true); else MTBC_CT2F8(16, true); }
+    else { if (kin == 8) MTBC_CT2F8(8, false); else if (kin == 12) MTBC_CT2F8(12, false); else MTBC_CT2F8(16, false); }
 #undef MTBC_CT2F8
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
@@ -1272,10 +1280,13 @@ bool mtbc_i_convT2_fwd_lp_c8_ok(const mtbc_convT_args* a) {
     return a->k == 2 && (a->H * a->W) % 32 == 0 && a->Cin % 8 == 0 && a->Cout % 8 == 0 && (a->y_type == 1 || a->y_type == 2) &&
            al16(a->y) && al16(a->x) && al16(a->w) && a->y_batch_stride % 8 == 0 && a->x_batch_stride % 8 == 0 && lp_c8_mtc(a, &kpad, &wrow, &lds) > 0;
 }
-int mtbc_i_convT2_fwd_lp_c8(const mtbc_convT_args* a, hipStream_t st) {
-    Ct2P p; fill(a, &p);
+int mtbc_i_convT2_fwd_lp_c8(const mtbc_convT_args* a, hipStream_t st, ConvTChoice* query) {
     int kpad, wrow; size_t lds;
-    const int mtc = lp_c8_mtc(a, &kpad, &wrow, &lds);
+    ConvTChoice ch{};
+    ch.add(CTK_FWD_LP_C8, lp_c8_mtc(a, &kpad, &wrow, &lds), a->y_type == 2);
+    if (query) { query->add(ch.l[0]); return MTBC_OK; }
+    Ct2P p; fill(a, &p);
+    const int mtc = ch.l[0].t[0];
     const long long tasks = (long long)a->N * (a->H * a->W / 32);
     const int yb = cdiv(a->Cout, 16 * mtc);
     int gx = 512 / yb; if (gx < 1) gx = 1;
@@ -1289,21 +1300,29 @@ int mtbc_i_convT2_fwd_lp_c8(const mtbc_convT_args* a, hipStream_t st) {
         hipLaunchKernelGGL((convT2_fwd_lp_c8_kernel<MTC_, F16_>), grid, dim3(256), lds, st, p, a->bias, x8,                \
                            (long long)a->x_batch_stride, y8, (long long)a->y_batch_stride, kpad, wrow);                    \
     } while (0)
-    if (a->y_type == 2) { if (mtc == 3) MTBC_CT2LP(3, true); else if (mtc == 2) MTBC_CT2LP(2, true); else MTBC_CT2LP(1, true); }
+    if (ch.l[0].t[1]) { if (mtc == 3) MTBC_CT2LP(3, true); else if (mtc == 2) MTBC_CT2LP(2, true); else MTBC_CT2LP(1, true); }
     else { if (mtc == 3) MTBC_CT2LP(3, false); else if (mtc == 2) MTBC_CT2LP(2, false); else MTBC_CT2LP(1, false); }
 #undef MTBC_CT2LP
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
 
-int mtbc_i_convT2_dgrad(const mtbc_convT_args* a, int compute, hipStream_t st) {
-    Ct2P p; fill(a, &p);
-    p.ntasks = (long long)p.mblocks * a->N * (a->H * a->W / 32);
-    const unsigned blocks = (unsigned)cdiv64(p.ntasks, 4);
+int mtbc_i_convT2_dgrad(const mtbc_convT_args* a, int compute, hipStream_t st, ConvTChoice* query) {
     static const bool no_lds = mtbc_probe_set("MTBC_CT_DGRAD_DIRECT");      // A/B: the direct kernel for every shape
     const int wrow = 4 * a->Cout + 16;
     const size_t lds = (size_t)48 * wrow * 2;
-    if (a->dy_type16 && !no_lds && a->Cout % 8 == 0 && lds <= 104 * 1024) {      // (Cout <= 256; one block per CU above 192)      // weights of the block's 48 input channels in LDS
+    static const int depth_env = mtbc_probe_int("MTBC_CT_DEPTH", 0);      // A/B: register sets (2 | 4), 0 = by shape
+    const bool deep = depth_env ? depth_env >= 4 : a->Cout >= 96;          // long step chains, few waves: three steps of loads in flight
+    ConvTChoice ch{};
+    if (a->dy_type16 && !no_lds && a->Cout % 8 == 0 && lds <= 104 * 1024) ch.add(CTK_DGRAD_LDS, compute == 1 ? 1 : 2, 4);      // (Cout <= 256; one block per CU above 192)      // weights of the block's 48 input channels in LDS
+    else if (a->dy_type16) ch.add(CTK_DGRAD2, compute == 1 ? 1 : 2, 1, deep ? 4 : 2);
+    else ch.add(CTK_DGRAD2, compute == 1 || compute == 2 ? compute : 0, 0, 2);
+    if (query) { query->add(ch.l[0]); return MTBC_OK; }
+    const ConvTLaunch& k = ch.l[0];
+    Ct2P p; fill(a, &p);
+    p.ntasks = (long long)p.mblocks * a->N * (a->H * a->W / 32);
+    const unsigned blocks = (unsigned)cdiv64(p.ntasks, 4);
+    if (k.k == CTK_DGRAD_LDS) {
         const long long tasks = (long long)a->N * (a->H * a->W / 32);
         int gx = 512 / p.mblocks; if (gx < 1) gx = 1;
         if ((long long)gx * 4 > tasks) gx = (int)cdiv64(tasks, 4);
@@ -1313,28 +1332,28 @@ int mtbc_i_convT2_dgrad(const mtbc_convT_args* a, int compute, hipStream_t st) {
             MTBC_ENSURE_DYN_LDS((&convT2_dgrad_lds_kernel<LP_, D_>), 104 * 1024);                                        \
             hipLaunchKernelGGL((convT2_dgrad_lds_kernel<LP_, D_>), grid, dim3(256), lds, st, p, wrow);                   \
         } while (0)
-        if (compute == 1) MTBC_CT2DG(1, 4); else MTBC_CT2DG(2, 4);
+        if (k.t[0] == 1) MTBC_CT2DG(1, 4); else MTBC_CT2DG(2, 4);
 #undef MTBC_CT2DG
         MTBC_CHECK_LAUNCH();
         return MTBC_OK;
     }
-    static const int depth_env = mtbc_probe_int("MTBC_CT_DEPTH", 0);      // A/B: register sets (2 | 4), 0 = by shape
-    const bool deep = depth_env ? depth_env >= 4 : a->Cout >= 96;          // long step chains, few waves: three steps of loads in flight
-    if (a->dy_type16) {
-        if (compute == 1) { if (deep) hipLaunchKernelGGL((convT2_dgrad_kernel<1, true, 4>), dim3(blocks), dim3(256), 0, st, p); else hipLaunchKernelGGL((convT2_dgrad_kernel<1, true>), dim3(blocks), dim3(256), 0, st, p); }
-        else { if (deep) hipLaunchKernelGGL((convT2_dgrad_kernel<2, true, 4>), dim3(blocks), dim3(256), 0, st, p); else hipLaunchKernelGGL((convT2_dgrad_kernel<2, true>), dim3(blocks), dim3(256), 0, st, p); }
-    } else if (compute == 1) hipLaunchKernelGGL(convT2_dgrad_kernel<1>, dim3(blocks), dim3(256), 0, st, p);
-    else if (compute == 2) hipLaunchKernelGGL(convT2_dgrad_kernel<2>, dim3(blocks), dim3(256), 0, st, p);
+    if (k.t[1]) {
+        const bool deep4 = k.t[2] == 4;
+        if (k.t[0] == 1) { if (deep4) hipLaunchKernelGGL((convT2_dgrad_kernel<1, true, 4>), dim3(blocks), dim3(256), 0, st, p); else hipLaunchKernelGGL((convT2_dgrad_kernel<1, true>), dim3(blocks), dim3(256), 0, st, p); }
+        else { if (deep4) hipLaunchKernelGGL((convT2_dgrad_kernel<2, true, 4>), dim3(blocks), dim3(256), 0, st, p); else hipLaunchKernelGGL((convT2_dgrad_kernel<2, true>), dim3(blocks), dim3(256), 0, st, p); }
+    } else if (k.t[0] == 1) hipLaunchKernelGGL(convT2_dgrad_kernel<1>, dim3(blocks), dim3(256), 0, st, p);
+    else if (k.t[0] == 2) hipLaunchKernelGGL(convT2_dgrad_kernel<2>, dim3(blocks), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(convT2_dgrad_kernel<0>, dim3(blocks), dim3(256), 0, st, p);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
 
-int mtbc_i_convT2_wgrad(const mtbc_convT_args* a, int compute, float* partial, float* dbias_part, int steps_per_split, int nsplit, hipStream_t st) {
+int mtbc_i_convT2_wgrad(const mtbc_convT_args* a, int compute, float* partial, float* dbias_part, int steps_per_split, int nsplit, hipStream_t st, ConvTChoice* query) {
     Ct2P p; fill(a, &p);
     p.partial = partial; p.dbias_part = dbias_part; p.steps_per_split = steps_per_split; p.nsplit = nsplit;
     p.ntasks = (long long)p.mblocks * p.ctiles * nsplit;
-    const unsigned blocks = (unsigned)cdiv64(p.ntasks, 4);
+    unsigned blocks = (unsigned)cdiv64(p.ntasks, 4);
+    ConvTChoice ch{};
     if (a->x_type16) {          // 16-bit planar x (and dy): both operands arrive as fragments
         if (!a->dy_type16 || a->x_type16 != compute) return MTBC_E_UNSUPPORTED;
         static const int ct_env = mtbc_probe_int("MTBC_CT_WG_CT", 0);      // A/B: tiles of 8 output channels per wave (1 | 2), 0 = by shape
@@ -1346,40 +1365,57 @@ int mtbc_i_convT2_wgrad(const mtbc_convT_args* a, int compute, float* partial, f
         if (xcd_env && nsplit >= 8 && per_xcd < (1ll << 30)) { p.xcd_tasks = (int)per_xcd; xblocks = 8u * (unsigned)cdiv64(per_xcd, 4); }
         if (ctn == 2) {
             p.ntasks = (long long)p.mblocks * ((p.ctiles + 1) / 2) * nsplit;
-            const unsigned b2 = xblocks ? xblocks : (unsigned)cdiv64(p.ntasks, 4);
+            blocks = xblocks ? xblocks : (unsigned)cdiv64(p.ntasks, 4);
             static const int depth_env = mtbc_probe_int("MTBC_CT_DEPTH", 2);      // A/B: register sets (2 | 4); measured 0.59 vs 0.62 ms per step
-            if (depth_env == 2) {
-                if (compute == 1) hipLaunchKernelGGL((convT2_wgrad16_kernel<1, 2, 2>), dim3(b2), dim3(256), 0, st, p);
-                else hipLaunchKernelGGL((convT2_wgrad16_kernel<2, 2, 2>), dim3(b2), dim3(256), 0, st, p);
-            } else if (compute == 1) hipLaunchKernelGGL((convT2_wgrad16_kernel<1, 2, 4>), dim3(b2), dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((convT2_wgrad16_kernel<2, 2, 4>), dim3(b2), dim3(256), 0, st, p);
+            ch.add(CTK_WGRAD16, compute == 1 ? 1 : 2, 2, depth_env == 2 ? 2 : 4);
         } else {
-            const unsigned b1 = xblocks ? xblocks : blocks;
-            if (compute == 1) hipLaunchKernelGGL((convT2_wgrad16_kernel<1, 1, 4>), dim3(b1), dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((convT2_wgrad16_kernel<2, 1, 4>), dim3(b1), dim3(256), 0, st, p);
+            if (xblocks) blocks = xblocks;
+            ch.add(CTK_WGRAD16, compute == 1 ? 1 : 2, 1, 4);
         }
-    } else if (a->dy_type16) {
-        if (compute == 1) hipLaunchKernelGGL((convT2_wgrad_kernel<1, true>), dim3(blocks), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((convT2_wgrad_kernel<2, true>), dim3(blocks), dim3(256), 0, st, p);
-    } else if (compute == 1) hipLaunchKernelGGL(convT2_wgrad_kernel<1>, dim3(blocks), dim3(256), 0, st, p);
-    else if (compute == 2) hipLaunchKernelGGL(convT2_wgrad_kernel<2>, dim3(blocks), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(convT2_wgrad_kernel<0>, dim3(blocks), dim3(256), 0, st, p);
+    } else if (a->dy_type16) ch.add(CTK_WGRAD2, compute == 1 ? 1 : 2, 1, 2);
+    else ch.add(CTK_WGRAD2, compute == 1 || compute == 2 ? compute : 0, 0, 2);
+    ConvTLaunch& k = ch.l[0];
+    k.xcd = p.xcd_tasks != 0; k.splits = nsplit > 1 ? 2 : 1;
+    if (query) { query->add(k); return MTBC_OK; }
+    const dim3 grid(blocks);
+    if (k.k == CTK_WGRAD16) {
+        if (k.t[1] == 2) {
+            if (k.t[2] == 2) {
+                if (k.t[0] == 1) hipLaunchKernelGGL((convT2_wgrad16_kernel<1, 2, 2>), grid, dim3(256), 0, st, p);
+                else hipLaunchKernelGGL((convT2_wgrad16_kernel<2, 2, 2>), grid, dim3(256), 0, st, p);
+            } else if (k.t[0] == 1) hipLaunchKernelGGL((convT2_wgrad16_kernel<1, 2, 4>), grid, dim3(256), 0, st, p);
+            else hipLaunchKernelGGL((convT2_wgrad16_kernel<2, 2, 4>), grid, dim3(256), 0, st, p);
+        } else {
+            if (k.t[0] == 1) hipLaunchKernelGGL((convT2_wgrad16_kernel<1, 1, 4>), grid, dim3(256), 0, st, p);
+            else hipLaunchKernelGGL((convT2_wgrad16_kernel<2, 1, 4>), grid, dim3(256), 0, st, p);
+        }
+    } else if (k.t[1]) {
+        if (k.t[0] == 1) hipLaunchKernelGGL((convT2_wgrad_kernel<1, true>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((convT2_wgrad_kernel<2, true>), grid, dim3(256), 0, st, p);
+    } else if (k.t[0] == 1) hipLaunchKernelGGL(convT2_wgrad_kernel<1>, grid, dim3(256), 0, st, p);
+    else if (k.t[0] == 2) hipLaunchKernelGGL(convT2_wgrad_kernel<2>, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(convT2_wgrad_kernel<0>, grid, dim3(256), 0, st, p);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
 
-int mtbc_i_convT2_bwd_fused(const mtbc_convT_args* wg, const mtbc_convT_args* dg, float* partial, float* dbias_part, int steps_per_split, int nsplit, hipStream_t st) {
+int mtbc_i_convT2_bwd_fused(const mtbc_convT_args* wg, const mtbc_convT_args* dg, float* partial, float* dbias_part, int steps_per_split, int nsplit, hipStream_t st, ConvTChoice* query) {
     if (!mtbc_i_convT2_bwd_fused_ok(wg, dg)) return MTBC_E_UNSUPPORTED;
     Ct2P p; fill(wg, &p);
-    p.dx = dg->dx; p.dxbs = dg->dx_batch_stride; p.acc_dx = dg->accumulate_dx;
-    p.partial = partial; p.dbias_part = dbias_part; p.steps_per_split = steps_per_split; p.nsplit = nsplit;
-    const int ctn = fused_ct(wg), nw = p.ctiles / ctn, compute = wg->compute;
-    const int wrow = 4 * wg->Cout + 16;
-    const size_t lds = fused_lds(wg);
     const long long nblocks = 8ll * cdiv(nsplit, 8) * p.mblocks;
     if (nblocks >= (1ll << 31)) return MTBC_E_UNSUPPORTED;
+    ConvTChoice ch{};
+    ch.add(CTK_BWD_FUSED, wg->compute == 1 ? 1 : 2, fused_ct(wg), p.ctiles / fused_ct(wg), dg->accumulate_dx != 0);
+    ch.last().splits = nsplit > 1 ? 2 : 1;
+    if (query) { query->add(ch.l[0]); return MTBC_OK; }
+    const ConvTLaunch& k = ch.l[0];
+    p.dx = dg->dx; p.dxbs = dg->dx_batch_stride; p.acc_dx = dg->accumulate_dx;
+    p.partial = partial; p.dbias_part = dbias_part; p.steps_per_split = steps_per_split; p.nsplit = nsplit;
+    const int ctn = k.t[1], nw = k.t[2], compute = k.t[0];
+    const int wrow = 4 * wg->Cout + 16;
+    const size_t lds = fused_lds(wg);
     const dim3 grid((unsigned)nblocks);
-    const bool acc = dg->accumulate_dx != 0;
+    const bool acc = k.t[3] != 0;
 #define MTBC_CT2BF(LP_, CT_, NW_, ACC_)                                                                                  \
     do {                                                                                                                 \
         MTBC_ENSURE_DYN_LDS((&convT2_bwd_fused_kernel<LP_, CT_, NW_, ACC_>), 104 * 1024);                                \

@@ -9,6 +9,8 @@
 // (MTnnUNet.py:103; MONAI Down) and the 1x1 output convs (MTnnUNet.py:106-118; MTUNetPlusPlus.py:73-76).
 #include "common.h"
 #include <cstdlib>
+#include <cstdio>
+#include <cstring>
 
 namespace {
 
@@ -322,53 +324,141 @@ __global__ void conv1x1_wgrad_kernel(const C1P p) {
 
 bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
+// ---------------------------------------------------------------- ConvTranspose: the dispatchers
+// Each fills ONE ConvTChoice and launches from it.  query != NULL: validate, append the launches to *query and return without touching
+// the stream or the device (mtbc_convT_kernel_name).
+struct ConvTKernelInfo { const char* name; int nargs; unsigned bools; };      // bools: bit i = template argument i prints as true / false
+constexpr ConvTKernelInfo CTKINFO[] = {
+    {"convT2_fwd_lp_c8_kernel", 2, 2}, {"convT2_fwd_c8_kernel", 2, 2}, {"convT2_fwd_lds_kernel", 1, 0},
+    {"convT2_dgrad_lds_kernel", 2, 0}, {"convT2_dgrad_kernel", 3, 2},
+    {"convT2_wgrad16_kernel", 3, 0}, {"convT2_wgrad_kernel", 3, 2}, {"convT2_bwd_fused_kernel", 4, 8},
+    {"convT_fwd_kernel", 1, 0}, {"convT_dgrad_kernel", 1, 0}, {"convT_wgrad_kernel", 1, 0},
+    {"splitk_reduce", 0, 0}, {"channel_sums", 0, 0},
+};
+int convT_choice_name(const ConvTChoice& ch, char* buf, int len) {
+    char tmp[512];
+    int n = 0;
+    tmp[0] = 0;
+    for (int j = 0; j < ch.n; ++j) {
+        const ConvTLaunch& k = ch.l[j];
+        const ConvTKernelInfo& f = CTKINFO[k.k];
+        n += snprintf(tmp + n, sizeof tmp - n, "%s%s", j ? " + " : "", f.name);
+        for (int i = 0; i < f.nargs; ++i) {
+            const char* sep = i ? ", " : "<";
+            if (f.bools >> i & 1) n += snprintf(tmp + n, sizeof tmp - n, "%s%s", sep, k.t[i] ? "true" : "false");
+            else n += snprintf(tmp + n, sizeof tmp - n, "%s%d", sep, k.t[i]);
+        }
+        if (f.nargs) n += snprintf(tmp + n, sizeof tmp - n, ">");
+        if (k.splits > 0) n += snprintf(tmp + n, sizeof tmp - n, " [%ssplits%s]", k.xcd ? "xcd " : "", k.splits > 1 ? ">1" : "=1");
+    }
+    if (!buf || len <= n) return MTBC_E_BADARG;
+    memcpy(buf, tmp, (size_t)n + 1);
+    return MTBC_OK;
+}
+
+int convT_fwd(const mtbc_convT_args* a, hipStream_t st, ConvTChoice* query) {
+    CtP p; int rc = fill_ct(a, &p); if (rc) return rc;
+    if (!p.x || !p.w || !p.y) return MTBC_E_BADARG;
+    if (a->x_layout == MTBC_LAYOUT_C8) {        // both tensors 16-bit channel-blocked: the 16-bit MFMA kernel or nothing
+        if (a->y_layout != MTBC_LAYOUT_C8) return MTBC_E_BADARG;
+        return mtbc_i_convT2_fwd_lp_c8_ok(a) ? mtbc_i_convT2_fwd_lp_c8(a, st, query) : MTBC_E_UNSUPPORTED;
+    }
+    if (a->x_layout != MTBC_LAYOUT_PLANAR) return MTBC_E_BADARG;
+    if (a->y_layout == MTBC_LAYOUT_C8)          // 16-bit channel-blocked output: the direct-to-fragment kernel or nothing
+        return mtbc_i_convT2_fwd_c8_ok(a) ? mtbc_i_convT2_fwd_c8(a, st, query) : MTBC_E_UNSUPPORTED;
+    if (a->y_layout != MTBC_LAYOUT_PLANAR) return MTBC_E_BADARG;
+    if (!al16(p.y) || (p.ybs & 3) || ((a->W * a->k) & 3)) return MTBC_E_UNSUPPORTED;
+    static const bool generic_f = mtbc_probe_set("MTBC_CONVT_GENERIC");      // A/B switch
+    if (!generic_f && mtbc_i_convT2_fwd_ok(a)) return mtbc_i_convT2_fwd(a, st, query);
+    ConvTChoice ch{};
+    ch.add(CTK_FWD, a->k);
+    if (query) { query->add(ch.l[0]); return MTBC_OK; }
+    dim3 grid(cdiv(a->H * a->W, 64), cdiv(p.M, 64), a->N);
+    const int ks = ch.l[0].t[0];
+    if (ks == 2) hipLaunchKernelGGL(convT_fwd_kernel<2>, grid, dim3(256), 0, st, p);
+    else if (ks == 4) hipLaunchKernelGGL(convT_fwd_kernel<4>, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(convT_fwd_kernel<8>, grid, dim3(256), 0, st, p);
+    MTBC_CHECK_LAUNCH();
+    return MTBC_OK;
+}
+int convT_dgrad(const mtbc_convT_args* a, hipStream_t st, ConvTChoice* query) {
+    CtP p; int rc = fill_ct(a, &p); if (rc) return rc;
+    if (!p.dy || !p.w || !p.dx) return MTBC_E_BADARG;
+    static const bool generic = mtbc_probe_set("MTBC_CONVT_GENERIC");      // A/B switch
+    if (a->dy_type16 && !((a->compute == 1 || a->compute == 2) && mtbc_i_convT2_dgrad_ok(a))) return MTBC_E_UNSUPPORTED;      // 16-bit dY: the direct kernel or nothing
+    if ((!generic || a->dy_type16) && mtbc_i_convT2_dgrad_ok(a)) return mtbc_i_convT2_dgrad(a, a->compute, st, query);
+    ConvTChoice ch{};
+    ch.add(CTK_DGRAD, a->k);
+    if (query) { query->add(ch.l[0]); return MTBC_OK; }
+    dim3 grid(cdiv(a->H * a->W, 64), cdiv(a->Cin, 64), a->N);
+    const int ks = ch.l[0].t[0];
+    if (ks == 2) hipLaunchKernelGGL(convT_dgrad_kernel<2>, grid, dim3(256), 0, st, p);
+    else if (ks == 4) hipLaunchKernelGGL(convT_dgrad_kernel<4>, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(convT_dgrad_kernel<8>, grid, dim3(256), 0, st, p);
+    MTBC_CHECK_LAUNCH();
+    return MTBC_OK;
+}
+int convT_wgrad(const mtbc_convT_args* a, hipStream_t st, ConvTChoice* query) {
+    CtP p; int rc = fill_ct(a, &p); if (rc) return rc;
+    if (!p.x || !p.dy || !a->dw) return MTBC_E_BADARG;
+    if (!a->workspace || a->workspace_bytes < mtbc_convT_wgrad_workspace(a)) return MTBC_E_WORKSPACE;
+    int S, cols; plan_ct_wgrad(a, &S, &cols);
+    p.partial = reinterpret_cast<float*>(a->workspace); p.S = S; p.cols_per_split = cols;
+    int nsplit = a->N * S;
+    static const bool generic = mtbc_probe_set("MTBC_CONVT_GENERIC");      // A/B switch
+    bool bias_done = false;
+    if ((a->dy_type16 || a->x_type16) && !((a->compute == 1 || a->compute == 2) && mtbc_i_convT2_wgrad_ok(a))) return MTBC_E_UNSUPPORTED;      // 16-bit dY / x: the direct kernel or nothing
+    if ((!generic || a->dy_type16) && mtbc_i_convT2_wgrad_ok(a)) {
+        int sps; mtbc_i_convT2_wgrad_plan(a, &sps, &nsplit);
+        float* bpart = a->dbias ? p.partial + (size_t)nsplit * a->Cin * p.M : nullptr;
+        rc = mtbc_i_convT2_wgrad(a, a->compute, p.partial, bpart, sps, nsplit, st, query); if (rc) return rc;
+        if (bpart) {       // the wgrad waves summed dY on the way: no second pass over the gradient
+            if (query) query->add(CTK_SPLITK);
+            else { rc = mtbc_i_splitk_reduce(bpart, a->dbias, nsplit, (size_t)a->Cout, a->accumulate_dw, st); if (rc) return rc; }
+            bias_done = true;
+        }
+    } else {
+        ConvTChoice ch{};
+        ch.add(CTK_WGRAD, a->k);
+        ch.last().splits = nsplit > 1 ? 2 : 1;
+        if (query) query->add(ch.l[0]);
+        else {
+            dim3 grid(cdiv(p.M, 64), cdiv(a->Cin, 64), nsplit);
+            const int ks = ch.l[0].t[0];
+            if (ks == 2) hipLaunchKernelGGL(convT_wgrad_kernel<2>, grid, dim3(256), 0, st, p);
+            else if (ks == 4) hipLaunchKernelGGL(convT_wgrad_kernel<4>, grid, dim3(256), 0, st, p);
+            else hipLaunchKernelGGL(convT_wgrad_kernel<8>, grid, dim3(256), 0, st, p);
+            MTBC_CHECK_LAUNCH();
+        }
+    }
+    const size_t wel = (size_t)a->Cin * p.M;
+    if (query) query->add(CTK_SPLITK);
+    else { rc = mtbc_i_splitk_reduce(p.partial, a->dw, nsplit, wel, a->accumulate_dw, st); if (rc) return rc; }
+    if (a->dbias && !bias_done) {
+        if (p.dybs != (long long)a->Cout * a->H * a->W * a->k * a->k) return MTBC_E_UNSUPPORTED;
+        if (query) query->add(CTK_CHANNEL_SUMS);
+        else {
+            rc = mtbc_i_channel_sums(p.dy, p.partial + (size_t)nsplit * wel, a->dbias, a->N, a->Cout, a->H * a->W * a->k * a->k,
+                                     a->accumulate_dw, st);
+            if (rc) return rc;
+        }
+    }
+    return MTBC_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 // ---------------------------------------------------------------- ConvTranspose
-int mtbc_convT_fwd(const mtbc_convT_args* a, void* stream) {
-    CtP p; int rc = fill_ct(a, &p); if (rc) return rc;
-    if (!p.x || !p.w || !p.y) return MTBC_E_BADARG;
-    if (a->x_layout == MTBC_LAYOUT_C8) {        // both tensors 16-bit channel-blocked: the 16-bit MFMA kernel or nothing
-        if (a->y_layout != MTBC_LAYOUT_C8) return MTBC_E_BADARG;
-        return mtbc_i_convT2_fwd_lp_c8_ok(a) ? mtbc_i_convT2_fwd_lp_c8(a, (hipStream_t)stream) : MTBC_E_UNSUPPORTED;
-    }
-    if (a->x_layout != MTBC_LAYOUT_PLANAR) return MTBC_E_BADARG;
-    if (a->y_layout == MTBC_LAYOUT_C8)          // 16-bit channel-blocked output: the direct-to-fragment kernel or nothing
-        return mtbc_i_convT2_fwd_c8_ok(a) ? mtbc_i_convT2_fwd_c8(a, (hipStream_t)stream) : MTBC_E_UNSUPPORTED;
-    if (a->y_layout != MTBC_LAYOUT_PLANAR) return MTBC_E_BADARG;
-    if (!al16(p.y) || (p.ybs & 3) || ((a->W * a->k) & 3)) return MTBC_E_UNSUPPORTED;
-    static const bool generic_f = mtbc_probe_set("MTBC_CONVT_GENERIC");      // A/B switch
-    if (!generic_f && mtbc_i_convT2_fwd_ok(a)) return mtbc_i_convT2_fwd(a, (hipStream_t)stream);
-    dim3 grid(cdiv(a->H * a->W, 64), cdiv(p.M, 64), a->N);
-    hipStream_t st = (hipStream_t)stream;
-    if (a->k == 2) hipLaunchKernelGGL(convT_fwd_kernel<2>, grid, dim3(256), 0, st, p);
-    else if (a->k == 4) hipLaunchKernelGGL(convT_fwd_kernel<4>, grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(convT_fwd_kernel<8>, grid, dim3(256), 0, st, p);
-    MTBC_CHECK_LAUNCH();
-    return MTBC_OK;
-}
+int mtbc_convT_fwd(const mtbc_convT_args* a, void* stream) { return convT_fwd(a, (hipStream_t)stream, nullptr); }
 int mtbc_convT_fwd_c8_supported(const mtbc_convT_args* a) {
     CtP p;
     if (!a || fill_ct(a, &p)) return 0;
     if (a->x_layout == MTBC_LAYOUT_C8) return a->y_layout == MTBC_LAYOUT_C8 && mtbc_i_convT2_fwd_lp_c8_ok(a) ? 1 : 0;
     return mtbc_i_convT2_fwd_c8_ok(a) ? 1 : 0;
 }
-int mtbc_convT_dgrad(const mtbc_convT_args* a, void* stream) {
-    CtP p; int rc = fill_ct(a, &p); if (rc) return rc;
-    if (!p.dy || !p.w || !p.dx) return MTBC_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    static const bool generic = mtbc_probe_set("MTBC_CONVT_GENERIC");      // A/B switch
-    if (a->dy_type16 && !((a->compute == 1 || a->compute == 2) && mtbc_i_convT2_dgrad_ok(a))) return MTBC_E_UNSUPPORTED;      // 16-bit dY: the direct kernel or nothing
-    if ((!generic || a->dy_type16) && mtbc_i_convT2_dgrad_ok(a)) return mtbc_i_convT2_dgrad(a, a->compute, st);
-    dim3 grid(cdiv(a->H * a->W, 64), cdiv(a->Cin, 64), a->N);
-    if (a->k == 2) hipLaunchKernelGGL(convT_dgrad_kernel<2>, grid, dim3(256), 0, st, p);
-    else if (a->k == 4) hipLaunchKernelGGL(convT_dgrad_kernel<4>, grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(convT_dgrad_kernel<8>, grid, dim3(256), 0, st, p);
-    MTBC_CHECK_LAUNCH();
-    return MTBC_OK;
-}
+int mtbc_convT_dgrad(const mtbc_convT_args* a, void* stream) { return convT_dgrad(a, (hipStream_t)stream, nullptr); }
 size_t mtbc_convT_wgrad_workspace(const mtbc_convT_args* a) {
     CtP p; if (fill_ct(a, &p)) return 0;
     int S, cols; plan_ct_wgrad(a, &S, &cols);
@@ -380,41 +470,22 @@ size_t mtbc_convT_wgrad_workspace(const mtbc_convT_args* a) {
     const size_t brows = splits > (size_t)a->N ? splits : (size_t)a->N;      // per-split or per-image partial bias sums
     return (splits * a->Cin * p.M + (a->dbias ? brows * a->Cout : 0)) * sizeof(float);
 }
-int mtbc_convT_wgrad(const mtbc_convT_args* a, void* stream) {
-    CtP p; int rc = fill_ct(a, &p); if (rc) return rc;
-    if (!p.x || !p.dy || !a->dw) return MTBC_E_BADARG;
-    if (!a->workspace || a->workspace_bytes < mtbc_convT_wgrad_workspace(a)) return MTBC_E_WORKSPACE;
-    int S, cols; plan_ct_wgrad(a, &S, &cols);
-    p.partial = reinterpret_cast<float*>(a->workspace); p.S = S; p.cols_per_split = cols;
-    int nsplit = a->N * S;
-    hipStream_t st = (hipStream_t)stream;
-    static const bool generic = mtbc_probe_set("MTBC_CONVT_GENERIC");      // A/B switch
-    bool bias_done = false;
-    if ((a->dy_type16 || a->x_type16) && !((a->compute == 1 || a->compute == 2) && mtbc_i_convT2_wgrad_ok(a))) return MTBC_E_UNSUPPORTED;      // 16-bit dY / x: the direct kernel or nothing
-    if ((!generic || a->dy_type16) && mtbc_i_convT2_wgrad_ok(a)) {
-        int sps; mtbc_i_convT2_wgrad_plan(a, &sps, &nsplit);
-        float* bpart = a->dbias ? p.partial + (size_t)nsplit * a->Cin * p.M : nullptr;
-        rc = mtbc_i_convT2_wgrad(a, a->compute, p.partial, bpart, sps, nsplit, st); if (rc) return rc;
-        if (bpart) {       // the wgrad waves summed dY on the way: no second pass over the gradient
-            rc = mtbc_i_splitk_reduce(bpart, a->dbias, nsplit, (size_t)a->Cout, a->accumulate_dw, st); if (rc) return rc;
-            bias_done = true;
+int mtbc_convT_wgrad(const mtbc_convT_args* a, void* stream) { return convT_wgrad(a, (hipStream_t)stream, nullptr); }
+int mtbc_convT_kernel_name(const mtbc_convT_args* a, int32_t op, const mtbc_convT_args* dgrad_next, char* buf, int32_t len) {
+    ConvTChoice ch{};
+    int rc;
+    if (op == MTBC_OP_CONVT_FWD) rc = convT_fwd(a, nullptr, &ch);
+    else if (op == MTBC_OP_CONVT_DGRAD) rc = convT_dgrad(a, nullptr, &ch);
+    else if (op == MTBC_OP_CONVT_WGRAD) {
+        bool fused = false;
+        rc = dgrad_next ? mtbc_i_convT_bwd_pair(a, dgrad_next, nullptr, &fused, &ch) : MTBC_OK;      // the program runner's order
+        if (rc == MTBC_OK && !fused) {
+            rc = convT_wgrad(a, nullptr, &ch);
+            if (rc == MTBC_OK && dgrad_next) rc = convT_dgrad(dgrad_next, nullptr, &ch);
         }
-    } else {
-        dim3 grid(cdiv(p.M, 64), cdiv(a->Cin, 64), nsplit);
-        if (a->k == 2) hipLaunchKernelGGL(convT_wgrad_kernel<2>, grid, dim3(256), 0, st, p);
-        else if (a->k == 4) hipLaunchKernelGGL(convT_wgrad_kernel<4>, grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(convT_wgrad_kernel<8>, grid, dim3(256), 0, st, p);
-        MTBC_CHECK_LAUNCH();
-    }
-    const size_t wel = (size_t)a->Cin * p.M;
-    rc = mtbc_i_splitk_reduce(p.partial, a->dw, nsplit, wel, a->accumulate_dw, st); if (rc) return rc;
-    if (a->dbias && !bias_done) {
-        if (p.dybs != (long long)a->Cout * a->H * a->W * a->k * a->k) return MTBC_E_UNSUPPORTED;
-        rc = mtbc_i_channel_sums(p.dy, p.partial + (size_t)nsplit * wel, a->dbias, a->N, a->Cout, a->H * a->W * a->k * a->k,
-                                 a->accumulate_dw, st);
-        if (rc) return rc;
-    }
-    return MTBC_OK;
+    } else return MTBC_E_BADARG;
+    if (rc) return rc;
+    return convT_choice_name(ch, buf, len);
 }
 
 // ---------------------------------------------------------------- MaxPool
@@ -515,7 +586,7 @@ int mtbc_conv1x1_wgrad(const mtbc_conv1x1_args* a, void* stream) {
 // mtbc_convT_wgrad) and dx, and the same split-K reductions follow.  Results are bit-identical to the two entry points above, so it
 // does not matter to a caller which way a pair ran.  Anything the fused path does not take -- an argument error included -- is left
 // to the two entry points: *fused stays false and nothing has been issued.
-int mtbc_i_convT_bwd_pair(const mtbc_convT_args* wg, const mtbc_convT_args* dg, void* stream, bool* fused) {
+int mtbc_i_convT_bwd_pair(const mtbc_convT_args* wg, const mtbc_convT_args* dg, void* stream, bool* fused, ConvTChoice* query) {
     *fused = false;
     CtP p;
     if (fill_ct(wg, &p) != MTBC_OK || fill_ct(dg, &p) != MTBC_OK) return MTBC_OK;
@@ -530,7 +601,8 @@ int mtbc_i_convT_bwd_pair(const mtbc_convT_args* wg, const mtbc_convT_args* dg, 
     float* partial = reinterpret_cast<float*>(wg->workspace);
     float* bpart = wg->dbias ? partial + (size_t)nsplit * wg->Cin * p.M : nullptr;
     *fused = true;
-    int rc = mtbc_i_convT2_bwd_fused(wg, dg, partial, bpart, sps, nsplit, st); if (rc) return rc;
+    int rc = mtbc_i_convT2_bwd_fused(wg, dg, partial, bpart, sps, nsplit, st, query); if (rc) return rc;
+    if (query) { if (bpart) query->add(CTK_SPLITK); query->add(CTK_SPLITK); return MTBC_OK; }
     if (bpart) { rc = mtbc_i_splitk_reduce(bpart, wg->dbias, nsplit, (size_t)wg->Cout, wg->accumulate_dw, st); if (rc) return rc; }
     return mtbc_i_splitk_reduce(partial, wg->dw, nsplit, (size_t)wg->Cin * p.M, wg->accumulate_dw, st);
 }

@@ -712,6 +712,81 @@ def maxpool2_bwd_c8(x8: "C8", dy, dx=None, accumulate=False):
 
 
 # ------------------------------------------------------------------ conv transpose (k == stride)
+def convT_kernel_name(a: "L.ConvTArgs", op: int, dgrad_next: Optional["L.ConvTArgs"] = None) -> str:
+    """Every launch mtbc_convT_fwd / _dgrad / _wgrad -- op = L.OP_CONVT_FWD / _DGRAD / _WGRAD -- would make for `a`, joined with " + ":
+    mtbc_convT_kernel_name, host-only (no launch, no device).  dgrad_next (with L.OP_CONVT_WGRAD): the arguments of the OP_CONVT_DGRAD
+    right behind it in a program; the name is then what the program runner makes of the pair.  Raises what the call would."""
+    buf = C.create_string_buffer(512)
+    nxt = None if dgrad_next is None else C.byref(dgrad_next)
+    L.check(L.load().mtbc_convT_kernel_name(C.byref(a), op, nxt, buf, len(buf)), "convT_kernel_name")
+    return buf.value.decode()
+
+
+_CT_DUMMY = {n: (i + 1) << 20 for i, n in enumerate(("x", "w", "bias", "y", "dy", "dx", "dw", "dbias", "workspace"))}
+
+
+def convT_case_args(op: int, N: int, Cin: int, Cout: int, H: int, W: int, k: int = 2, ptrs: Optional[dict] = None, compute: int = 0,
+                    dy16: bool = False, x16: bool = False, x_c8: bool = False, y_c8: bool = False, bias: bool = True,
+                    acc_dx: bool = False, acc_dw: bool = False, strides: Optional[dict] = None, workspace: bool = True) -> "L.ConvTArgs":
+    """The argument struct of ONE transposed-convolution call as the step programs fill it (engine.StepPlan.convT / convT_head).
+    ptrs: field name (x, w, bias, y, dy, dx, dw, dbias, workspace) -> tensor; None = distinct 16-byte aligned dummies that nothing may
+    dereference (for convT_kernel_name), the same address for the same field of every call so that a WGRAD and the DGRAD behind it
+    describe one problem.  Forward: x_c8 / y_c8 = 16-bit channel-blocked input / output of type `compute`; bias = with a bias.
+    Backward: `compute` = the MFMA operand type, dy16 / x16 = dy / x as 16-bit planes of that type, bias = with dbias (weight gradient),
+    acc_dx / acc_dw = accumulate.  strides: field name (x, y, dy, dx) -> batch stride in elements of that tensor where the tensor is a
+    channel-range view of a wider buffer; dense otherwise.  workspace = False leaves the weight gradient without one."""
+    strides = strides or {}
+
+    def ptr(name):
+        return _CT_DUMMY[name] if ptrs is None else ptrs[name].data_ptr()
+
+    a = L.ConvTArgs()
+    a.N, a.H, a.W, a.Cin, a.Cout, a.k = N, H, W, Cin, Cout, k
+    a.w = ptr("w")
+    a.x_batch_stride = strides.get("x", Cin * H * W)
+    a.y_batch_stride = strides.get("y", Cout * H * k * W * k)
+    if op == L.OP_CONVT_FWD:
+        a.x, a.y, a.bias = ptr("x"), ptr("y"), (ptr("bias") if bias else None)
+        if y_c8:
+            a.y_layout, a.y_type = L.LAYOUT_C8, compute
+        if x_c8:
+            a.x_layout = L.LAYOUT_C8
+        return a
+    a.compute = compute
+    a.dy, a.dy_batch_stride, a.dy_type16 = ptr("dy"), strides.get("dy", Cout * H * k * W * k), (compute if dy16 else 0)
+    if op == L.OP_CONVT_DGRAD:
+        a.dx, a.dx_batch_stride, a.accumulate_dx = ptr("dx"), strides.get("dx", Cin * H * W), int(acc_dx)
+        return a
+    a.x, a.x_type16 = ptr("x"), (compute if x16 else 0)
+    a.dw, a.dbias, a.accumulate_dw = ptr("dw"), (ptr("dbias") if bias else None), int(acc_dw)
+    if workspace:
+        nb = int(L.load().mtbc_convT_wgrad_workspace(C.byref(a)))
+        a.workspace, a.workspace_bytes = ptr("workspace"), (nb if ptrs is None else ptrs["workspace"].numel() * 4)
+    return a
+
+
+def convT_case_kernel(op: int, *shape, pair: bool = False, **mode) -> str:
+    """convT_kernel_name of convT_case_args(op, *shape, **mode); pair (with L.OP_CONVT_WGRAD): followed by the L.OP_CONVT_DGRAD of the
+    same problem and mode, as engine.StepPlan.convT emits the two."""
+    nxt = convT_case_args(L.OP_CONVT_DGRAD, *shape, **mode) if pair else None
+    return convT_kernel_name(convT_case_args(op, *shape, **mode), op, nxt)
+
+
+def convT_note(a: "L.ConvTArgs", op: int, dgrad_next: Optional["L.ConvTArgs"] = None) -> None:
+    """Records (op, launches) of a transposed-convolution call -- or of a program's WGRAD + DGRAD pair -- while `launched` is a list."""
+    if launched is not None:
+        launched.append((op, convT_kernel_name(a, op, dgrad_next)))
+
+
+def convT_launch(a: "L.ConvTArgs", op: int) -> None:
+    """mtbc_convT_fwd / _dgrad / _wgrad on the current stream for an argument struct of convT_case_args(ptrs=...)."""
+    convT_note(a, op)
+    lib = L.load()
+    fn, what = {L.OP_CONVT_FWD: (lib.mtbc_convT_fwd, "convT_fwd"), L.OP_CONVT_DGRAD: (lib.mtbc_convT_dgrad, "convT_dgrad"),
+                L.OP_CONVT_WGRAD: (lib.mtbc_convT_wgrad, "convT_wgrad")}[op]
+    L.check(fn(C.byref(a), _s()), what)
+
+
 def _ct_args(x, w, k):
     a = L.ConvTArgs()
     N, Cin, H, W = x.shape
@@ -726,6 +801,7 @@ def convT_fwd(x, w, bias, k):
     y = torch.empty(N, w.shape[1], H * k, W * k, dtype=torch.float32, device=x.device)
     a = _ct_args(x, w, k)
     a.bias, a.y, a.y_batch_stride = _p(bias), y.data_ptr(), y[0].numel()
+    convT_note(a, L.OP_CONVT_FWD)
     L.check(L.load().mtbc_convT_fwd(C.byref(a), _s()), "convT_fwd")
     return y
 
@@ -741,6 +817,7 @@ def convT_fwd_c8(x, w, bias, k, compute: int) -> "C8":
     a.y_layout, a.y_type = L.LAYOUT_C8, compute
     if not L.load().mtbc_convT_fwd_c8_supported(C.byref(a)):
         raise L.MtbcError("convT_fwd: shape not supported with a channel-blocked output")
+    convT_note(a, L.OP_CONVT_FWD)
     L.check(L.load().mtbc_convT_fwd(C.byref(a), _s()), "convT_fwd(c8)")
     return C8(y, (N, cout, H * k, W * k), compute)
 
@@ -758,6 +835,7 @@ def convT_fwd_c8_lp(x8: "C8", w, bias, k) -> "C8":
     a.y_layout, a.y_type, a.x_layout = L.LAYOUT_C8, x8.compute, L.LAYOUT_C8
     if not L.load().mtbc_convT_fwd_c8_supported(C.byref(a)):
         raise L.MtbcError("convT_fwd: shape not supported with channel-blocked input and output")
+    convT_note(a, L.OP_CONVT_FWD)
     L.check(L.load().mtbc_convT_fwd(C.byref(a), _s()), "convT_fwd(c8 -> c8)")
     return C8(y, (N, cout, H * k, W * k), x8.compute)
 
@@ -771,6 +849,7 @@ def convT_dgrad(x, w, dy, k, dx=None, accumulate=False, compute=0, dy16=False):
     a.compute = compute
     a.dy_type16 = compute if dy16 else 0
     a.dy, a.dy_batch_stride, a.dx, a.dx_batch_stride, a.accumulate_dx = dy.data_ptr(), dy[0].numel(), dx.data_ptr(), x[0].numel(), int(accumulate)
+    convT_note(a, L.OP_CONVT_DGRAD)
     L.check(L.load().mtbc_convT_dgrad(C.byref(a), _s()), "convT_dgrad")
     return dx
 
@@ -787,6 +866,7 @@ def convT_wgrad(x, w, dy, k, want_bias=True, compute=0, dy16=False, x16=False):
     a.dy, a.dy_batch_stride, a.dw, a.dbias = dy.data_ptr(), dy[0].numel(), dw.data_ptr(), _p(db)
     ws = _ws(L.load().mtbc_convT_wgrad_workspace(C.byref(a)), x.device)
     a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    convT_note(a, L.OP_CONVT_WGRAD)
     L.check(L.load().mtbc_convT_wgrad(C.byref(a), _s()), "convT_wgrad")
     return dw, db
 

@@ -327,3 +327,174 @@ def test_instnorm_kernel_name_refuses_what_the_call_refuses(lib):
     import torch
     if not torch.cuda.is_available():          # planes above 64 x 64: the team plan needs the device, as the launch does
         assert name(ops.instnorm_case_args(False, 2, 24, 256, 256, **_IN_BF), 0) == -5
+
+
+# (op, (N, Cin, Cout, H, W, k), mode, pair) -> what mtbc_convT_kernel_name names: the selection of convt2.hip and of the ConvT entry points of
+# pool_up.hip, one row per instance that tests/test_ops_gpu.py::test_convT_step_instances_match_fp64 compares with fp64, and the edges of
+# each rule.  mode: ops.convT_case_args; pair: the OP_CONVT_DGRAD of the same problem right behind the weight gradient.
+_CT_B16 = dict(compute=1, dy16=True, x16=True)
+_CT_F16 = dict(compute=2, dy16=True, x16=True)
+_CT_C8B = dict(compute=1, x_c8=True, y_c8=True)
+_CT_C8F = dict(compute=2, x_c8=True, y_c8=True)
+_RR = " + splitk_reduce + splitk_reduce"          # the bias-gradient partials, then dW
+CONVT_SELECTION = [
+    # forward on the 16-bit MFMA: MTC = min(3, Cout / 16 rounded up), lowered until 64 x MTC rows of Cin (rounded up to 32) + 16 halves fit 72 KB
+    ("fwd", (3, 96, 48, 8, 16, 2), _CT_C8B, False, "convT2_fwd_lp_c8_kernel<3, false>"),
+    ("fwd", (2, 56, 40, 16, 16, 2), _CT_C8F, False, "convT2_fwd_lp_c8_kernel<3, true>"),
+    ("fwd", (2, 160, 96, 8, 8, 2), _CT_C8B, False, "convT2_fwd_lp_c8_kernel<3, false>"),        # the last Cin with three tiles
+    ("fwd", (2, 192, 96, 8, 8, 2), _CT_C8B, False, "convT2_fwd_lp_c8_kernel<2, false>"),
+    ("fwd", (3, 40, 24, 8, 16, 2), _CT_C8F, False, "convT2_fwd_lp_c8_kernel<2, true>"),
+    ("fwd", (2, 256, 96, 8, 8, 2), _CT_C8B, False, "convT2_fwd_lp_c8_kernel<2, false>"),        # the last Cin with two
+    ("fwd", (2, 288, 96, 8, 8, 2), _CT_C8B, False, "convT2_fwd_lp_c8_kernel<1, false>"),
+    ("fwd", (1, 384, 192, 8, 8, 2), _CT_C8B, False, "convT2_fwd_lp_c8_kernel<1, false>"),
+    ("fwd", (2, 24, 8, 8, 16, 2), _CT_C8F, False, "convT2_fwd_lp_c8_kernel<1, true>"),
+    # forward, fp32 x into channel-blocked y, and fp32 into planes: KI = Cin / 4 rounded up to 8 | 12 | 16
+    ("fwd", (2, 32, 40, 16, 16, 2), dict(compute=2, y_c8=True), False, "convT2_fwd_c8_kernel<8, true>"),
+    ("fwd", (2, 24, 24, 8, 16, 2), dict(compute=1, y_c8=True), False, "convT2_fwd_c8_kernel<8, false>"),
+    ("fwd", (3, 48, 48, 8, 16, 2), dict(compute=1, y_c8=True), False, "convT2_fwd_c8_kernel<12, false>"),
+    ("fwd", (2, 36, 8, 16, 16, 2), dict(compute=2, y_c8=True), False, "convT2_fwd_c8_kernel<12, true>"),
+    ("fwd", (2, 64, 48, 8, 8, 2), dict(compute=1, y_c8=True), False, "convT2_fwd_c8_kernel<16, false>"),
+    ("fwd", (2, 52, 24, 16, 16, 2), dict(compute=2, y_c8=True), False, "convT2_fwd_c8_kernel<16, true>"),
+    ("fwd", (2, 20, 12, 8, 16, 2), {}, False, "convT2_fwd_lds_kernel<8>"),
+    ("fwd", (3, 48, 48, 16, 16, 2), {}, False, "convT2_fwd_lds_kernel<12>"),
+    ("fwd", (2, 64, 40, 8, 8, 2), {}, False, "convT2_fwd_lds_kernel<16>"),
+    ("fwd", (2, 32, 1, 8, 8, 2), {}, False, "convT2_fwd_lds_kernel<8>"),                        # a k = 2 head on a 32-pixel-multiple map
+    ("fwd", (2, 68, 48, 8, 8, 2), {}, False, "convT_fwd_kernel<2>"),                            # Cin above 64
+    ("fwd", (2, 64, 52, 8, 8, 2), {}, False, "convT_fwd_kernel<2>"),                            # Cout above 48
+    ("fwd", (2, 20, 12, 6, 10, 2), {}, False, "convT_fwd_kernel<2>"),                           # H * W % 32 != 0
+    ("fwd", (2, 64, 1, 6, 10, 4), {}, False, "convT_fwd_kernel<4>"),
+    ("fwd", (2, 128, 1, 4, 4, 8), {}, False, "convT_fwd_kernel<8>"),
+    # dgrad: 16-bit dy keeps the weights in LDS while Cout % 8 == 0 and 48 rows of 4 Cout + 16 halves fit 104 KB (Cout <= 272)
+    ("dgrad", (3, 48, 48, 8, 16, 2), dict(compute=1, dy16=True), False, "convT2_dgrad_lds_kernel<1, 4>"),
+    ("dgrad", (2, 64, 256, 8, 8, 2), dict(compute=2, dy16=True), False, "convT2_dgrad_lds_kernel<2, 4>"),
+    ("dgrad", (2, 64, 272, 8, 8, 2), dict(compute=2, dy16=True), False, "convT2_dgrad_lds_kernel<2, 4>"),          # the last multiple of 8 that fits
+    ("dgrad", (2, 64, 280, 8, 8, 2), dict(compute=2, dy16=True), False, "convT2_dgrad_kernel<2, true, 4>"),
+    ("dgrad", (2, 48, 320, 8, 8, 2), dict(compute=1, dy16=True), False, "convT2_dgrad_kernel<1, true, 4>"),
+    ("dgrad", (2, 40, 100, 8, 16, 2), dict(compute=1, dy16=True), False, "convT2_dgrad_kernel<1, true, 4>"),       # Cout % 8 != 0, D = 4 from 96
+    ("dgrad", (2, 40, 20, 8, 16, 2), dict(compute=1, dy16=True), False, "convT2_dgrad_kernel<1, true, 2>"),
+    ("dgrad", (3, 24, 12, 8, 8, 2), dict(compute=2, dy16=True), False, "convT2_dgrad_kernel<2, true, 2>"),
+    ("dgrad", (2, 48, 24, 8, 16, 2), {}, False, "convT2_dgrad_kernel<0, false, 2>"),
+    ("dgrad", (2, 56, 40, 8, 8, 2), dict(compute=1), False, "convT2_dgrad_kernel<1, false, 2>"),
+    ("dgrad", (2, 96, 48, 8, 8, 2), dict(compute=2), False, "convT2_dgrad_kernel<2, false, 2>"),
+    ("dgrad", (2, 32, 1, 8, 8, 2), {}, False, "convT_dgrad_kernel<2>"),                         # odd Cout
+    ("dgrad", (2, 20, 12, 6, 10, 2), {}, False, "convT_dgrad_kernel<2>"),
+    ("dgrad", (2, 64, 1, 6, 10, 4), {}, False, "convT_dgrad_kernel<4>"),
+    ("dgrad", (2, 128, 1, 4, 4, 8), {}, False, "convT_dgrad_kernel<8>"),
+    # wgrad: splits of at least 8 steps of 32 pixels; x and dy as 16-bit planes: two channel tiles per wave when their count is even,
+    # a split's tasks on one XCD from 8 splits
+    ("wgrad", (1, 48, 48, 16, 16, 2), _CT_B16, False, "convT2_wgrad16_kernel<1, 2, 2> [splits=1]" + _RR),
+    ("wgrad", (3, 64, 16, 16, 24, 2), dict(_CT_F16, bias=False), False, "convT2_wgrad16_kernel<2, 2, 2> [splits>1] + splitk_reduce"),
+    ("wgrad", (7, 96, 32, 16, 16, 2), _CT_B16, False, "convT2_wgrad16_kernel<1, 2, 2> [splits>1]" + _RR),          # 7 splits
+    ("wgrad", (2, 96, 32, 32, 32, 2), _CT_B16, False, "convT2_wgrad16_kernel<1, 2, 2> [xcd splits>1]" + _RR),      # 8
+    ("wgrad", (3, 48, 192, 24, 40, 2), _CT_F16, False, "convT2_wgrad16_kernel<2, 2, 2> [xcd splits>1]" + _RR),
+    ("wgrad", (2, 40, 24, 8, 16, 2), _CT_B16, False, "convT2_wgrad16_kernel<1, 1, 4> [splits=1]" + _RR),
+    ("wgrad", (3, 56, 40, 16, 24, 2), _CT_F16, False, "convT2_wgrad16_kernel<2, 1, 4> [splits>1]" + _RR),
+    ("wgrad", (3, 48, 8, 32, 32, 2), _CT_B16, False, "convT2_wgrad16_kernel<1, 1, 4> [xcd splits>1]" + _RR),
+    ("wgrad", (3, 64, 24, 24, 40, 2), _CT_F16, False, "convT2_wgrad16_kernel<2, 1, 4> [xcd splits>1]" + _RR),
+    ("wgrad", (3, 48, 24, 16, 24, 2), dict(compute=1, dy16=True), False, "convT2_wgrad_kernel<1, true, 2> [splits>1]" + _RR),
+    ("wgrad", (2, 96, 48, 8, 16, 2), dict(compute=2, dy16=True), False, "convT2_wgrad_kernel<2, true, 2> [splits=1]" + _RR),
+    ("wgrad", (3, 20, 12, 16, 24, 2), {}, False, "convT2_wgrad_kernel<0, false, 2> [splits>1]" + _RR),
+    ("wgrad", (2, 48, 48, 8, 16, 2), dict(compute=1), False, "convT2_wgrad_kernel<1, false, 2> [splits=1]" + _RR),
+    ("wgrad", (1, 96, 40, 16, 16, 2), dict(compute=2, bias=False), False, "convT2_wgrad_kernel<2, false, 2> [splits=1] + splitk_reduce"),
+    ("wgrad", (2, 32, 1, 8, 16, 2), {}, False, "convT2_wgrad_kernel<0, false, 2> [splits=1]" + _RR),               # a k = 2 head: no parity rule on Cout here
+    ("wgrad", (2, 32, 1, 8, 12, 2), {}, False, "convT_wgrad_kernel<2> [splits>1] + splitk_reduce + channel_sums"),    # W % 8 != 0
+    ("wgrad", (2, 64, 1, 6, 10, 4), {}, False, "convT_wgrad_kernel<4> [splits>1] + splitk_reduce + channel_sums"),
+    ("wgrad", (1, 128, 1, 4, 4, 8), dict(bias=False), False, "convT_wgrad_kernel<8> [splits=1] + splitk_reduce"),
+    ("wgrad", (2, 128, 1, 4, 4, 8), dict(bias=False), False, "convT_wgrad_kernel<8> [splits>1] + splitk_reduce"),      # a split per image at least
+    ("wgrad", (1, 384, 192, 8, 8, 2), _CT_F16, True, "convT2_wgrad16_kernel<2, 2, 2> [splits=1]" + _RR + " + convT2_dgrad_lds_kernel<2, 4>"),
+    # the pair: one launch where Cout is 24 (CT = 1), 48 or 96 (CT = 2; 3 or 6 waves), unless it has fewer than 256 workgroups of more than 8 steps
+    ("wgrad", (2, 64, 24, 16, 16, 2), _CT_B16, True, "convT2_bwd_fused_kernel<1, 1, 3, false> [splits>1]" + _RR),
+    ("wgrad", (3, 40, 24, 16, 24, 2), dict(_CT_B16, acc_dx=True), True, "convT2_bwd_fused_kernel<1, 1, 3, true> [splits>1]" + _RR),
+    ("wgrad", (3, 56, 24, 32, 32, 2), _CT_F16, True, "convT2_bwd_fused_kernel<2, 1, 3, false> [splits>1]" + _RR),
+    ("wgrad", (1, 48, 24, 16, 16, 2), dict(_CT_F16, acc_dx=True), True, "convT2_bwd_fused_kernel<2, 1, 3, true> [splits=1]" + _RR),
+    ("wgrad", (3, 48, 48, 32, 32, 2), _CT_B16, True, "convT2_bwd_fused_kernel<1, 2, 3, false> [splits>1]" + _RR),
+    ("wgrad", (2, 96, 48, 32, 32, 2), dict(_CT_B16, acc_dx=True), True, "convT2_bwd_fused_kernel<1, 2, 3, true> [splits>1]" + _RR),
+    ("wgrad", (3, 48, 48, 16, 24, 2), _CT_F16, True, "convT2_bwd_fused_kernel<2, 2, 3, false> [splits>1]" + _RR),
+    ("wgrad", (2, 96, 48, 8, 16, 2), dict(_CT_F16, acc_dx=True, bias=False), True, "convT2_bwd_fused_kernel<2, 2, 3, true> [splits=1] + splitk_reduce"),
+    ("wgrad", (2, 96, 48, 16, 16, 2), dict(_CT_F16, acc_dx=True), True, "convT2_bwd_fused_kernel<2, 2, 3, true> [splits>1]" + _RR),
+    ("wgrad", (1, 192, 96, 8, 8, 2), _CT_B16, True, "convT2_bwd_fused_kernel<1, 2, 6, false> [splits=1]" + _RR),
+    ("wgrad", (3, 96, 96, 16, 24, 2), dict(_CT_B16, acc_dx=True), True, "convT2_bwd_fused_kernel<1, 2, 6, true> [splits>1]" + _RR),
+    ("wgrad", (3, 64, 96, 24, 40, 2), _CT_F16, True, "convT2_bwd_fused_kernel<2, 2, 6, false> [splits>1]" + _RR),
+    ("wgrad", (2, 192, 96, 8, 16, 2), dict(_CT_F16, acc_dx=True), True, "convT2_bwd_fused_kernel<2, 2, 6, true> [splits=1]" + _RR),
+    ("wgrad", (32, 48, 48, 128, 128, 2), _CT_B16, True, "convT2_bwd_fused_kernel<1, 2, 3, false> [splits>1]" + _RR),                  # the bench: 256 workgroups
+    ("wgrad", (32, 192, 96, 32, 32, 2), _CT_B16, True, "convT2_wgrad16_kernel<1, 2, 2> [xcd splits>1]" + _RR + " + convT2_dgrad_lds_kernel<1, 4>"),   # 128 of 32 steps
+    ("wgrad", (3, 48, 192, 32, 32, 2), _CT_B16, True, "convT2_wgrad16_kernel<1, 2, 2> [xcd splits>1]" + _RR + " + convT2_dgrad_lds_kernel<1, 4>"),    # 12 waves
+    ("wgrad", (2, 64, 320, 8, 16, 2), _CT_B16, True, "convT2_wgrad16_kernel<1, 2, 2> [splits=1]" + _RR + " + convT2_dgrad_kernel<1, true, 4>"),
+    ("wgrad", (3, 48, 48, 16, 24, 2), {}, True, "convT2_wgrad_kernel<0, false, 2> [splits>1]" + _RR + " + convT2_dgrad_kernel<0, false, 2>"),
+    ("wgrad", (3, 320, 320, 8, 16, 2), dict(compute=1), True, "convT2_wgrad_kernel<1, false, 2> [splits>1]" + _RR + " + convT2_dgrad_kernel<1, false, 2>"),
+    ("wgrad", (3, 48, 48, 16, 24, 2), dict(compute=1, dy16=True), True,                               # fp32 x: never fused
+     "convT2_wgrad_kernel<1, true, 2> [splits>1]" + _RR + " + convT2_dgrad_lds_kernel<1, 4>"),
+]
+_CT_OPS = {"fwd": L.OP_CONVT_FWD, "dgrad": L.OP_CONVT_DGRAD, "wgrad": L.OP_CONVT_WGRAD}
+
+
+@pytest.mark.parametrize("op,shape,mode,pair,want", CONVT_SELECTION)
+def test_convT_kernel_selection(lib, op, shape, mode, pair, want):
+    """mtbc_convT_kernel_name (host only, no device: the dummy tensor pointers are never dereferenced) names every launch of a call, or of a
+    program's WGRAD + DGRAD pair; a change of the selection shows up here, in review."""
+    from multi_task_breast_cancer_amd import ops
+    assert ops.convT_case_kernel(_CT_OPS[op], *shape, pair=pair, **mode) == want
+
+
+def test_convT_selection_table_names_every_instance_the_fp64_test_reaches(lib):
+    """One row above per distinct launch -- instance and bracketed plan facts -- of tests/test_ops_gpu.py::CONVT_CASES (that table is importable
+    without a GPU)."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    try:
+        import test_ops_gpu as G
+    finally:
+        sys.path.pop(0)
+    from multi_task_breast_cancer_amd import ops
+    named = {part for *_, want in CONVT_SELECTION for part in want.split(" + ")}
+    reached = {part for case in G.CONVT_CASES for _, op, a, nxt in G._convT_case_calls(case) for part in ops.convT_kernel_name(a, op, nxt).split(" + ")}
+    assert len(reached) >= 50 and not reached - named, sorted(reached - named)
+
+
+def test_convT_kernel_name_refuses_what_the_call_refuses(lib):
+    from multi_task_breast_cancer_amd import ops
+    F_, D_, W_ = L.OP_CONVT_FWD, L.OP_CONVT_DGRAD, L.OP_CONVT_WGRAD
+    buf = C.create_string_buffer(512)
+    name = lambda a, op, nxt=None: lib.mtbc_convT_kernel_name(C.byref(a), op, None if nxt is None else C.byref(nxt), buf, 512)      # noqa: E731
+    shape = (2, 48, 48, 16, 16, 2)
+    a = ops.convT_case_args(D_, *shape, compute=1, dy16=True)
+    a.compute = 2                                                                           # 16-bit dy of another type than `compute`
+    assert name(a, D_) == -5
+    a = ops.convT_case_args(W_, *shape, compute=1, dy16=True)
+    a.compute = 0
+    assert name(a, W_) == -5
+    a = ops.convT_case_args(W_, *shape, compute=1, x16=True)                                # x_type16 without dy_type16
+    assert name(a, W_) == -5
+    a = ops.convT_case_args(F_, *shape, compute=1, x_c8=True)                               # channel-blocked x with planar y
+    assert name(a, F_) == -2
+    assert name(ops.convT_case_args(F_, 2, 48, 52, 16, 16, 2, compute=1, y_c8=True), F_) == -5      # channel-blocked y from fp32 x: Cout <= 48
+    assert name(ops.convT_case_args(F_, 2, 48, 48, 6, 10, 2, compute=1, x_c8=True, y_c8=True), F_) == -5      # ... H * W % 32
+    assert name(ops.convT_case_args(F_, 2, 48, 48, 16, 16, 4, compute=1, y_c8=True), F_) == -5      # ... k = 2 only
+    assert name(ops.convT_case_args(W_, *shape, workspace=False), W_) == -3                 # no workspace
+    a = ops.convT_case_args(W_, *shape)
+    a.workspace_bytes -= 4                                                                  # one float short
+    assert name(a, W_) == -3
+    wg, dg = ops.convT_case_args(W_, *shape, **_CT_B16), ops.convT_case_args(D_, *shape, **_CT_B16)
+    assert name(wg, W_, dg) == 0 and buf.value.startswith(b"convT2_bwd_fused_kernel<1, 2, 3, false>")
+    wg.workspace_bytes -= 4                                                                 # the pair leaves the refusal to the weight gradient's call
+    assert name(wg, W_, dg) == -3
+    a = ops.convT_case_args(F_, *shape)
+    assert name(a, F_) == 0 and buf.value == b"convT2_fwd_lds_kernel<12>"
+    a.y += 4                                                                                # pointer values count: a misaligned y has no kernel
+    assert name(a, F_) == -5
+    a = ops.convT_case_args(D_, *shape)
+    a.dx += 4                                                                               # ... a misaligned dx takes the generic GEMM
+    assert name(a, D_) == 0 and buf.value == b"convT_dgrad_kernel<2>"
+    a.dx = None
+    assert name(a, D_) == -2
+    assert name(ops.convT_case_args(F_, 2, 48, 48, 16, 16, 3), F_) == -5                    # k outside 2, 4, 8
+    assert name(ops.convT_case_args(F_, 0, 48, 48, 16, 16, 2), F_) == -1
+    a = ops.convT_case_args(F_, *shape)
+    assert name(a, L.OP_CONV3_FWD) == -2                                                    # not a ConvT op
+    assert lib.mtbc_convT_kernel_name(C.byref(a), F_, None, buf, 8) == -2                   # shorter than the name
+    assert lib.mtbc_convT_kernel_name(C.byref(a), F_, None, buf, len(b"convT2_fwd_lds_kernel<12>")) == -2      # no room for the NUL
+    assert lib.mtbc_convT_kernel_name(C.byref(a), F_, None, buf, len(b"convT2_fwd_lds_kernel<12>") + 1) == 0
+    for op in (F_, D_, W_):
+        assert lib.mtbc_convT_kernel_name(None, op, None, buf, 512) == -1                   # NULL args: what the calls return
+    assert lib.mtbc_convT_kernel_name(None, W_, C.byref(dg), buf, 512) == -1

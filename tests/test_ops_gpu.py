@@ -2014,3 +2014,405 @@ def test_step_programs_launch_only_reference_tested_instnorm_instances():
                 missing.setdefault((arch, dtype, N, size, reserve), []).append((key, shape))
     assert not missing, "InstanceNorm launches of the step programs that no fp64 reference case makes: " + \
         "".join(f"\n  {p_}: {k} at (N, C, H, W) = {s}" for p_, ks in missing.items() for k, s in ks)
+
+
+# ------------------------------------------------------------------ the transposed-convolution launches of the step programs, element by element
+def _convT_key(a, op, nxt=None):
+    """Coverage key of ONE mtbc_convT_fwd / _dgrad / _wgrad call, or of a program's WGRAD + DGRAD pair (nxt = the DGRAD's arguments): the
+    launches mtbc_convT_kernel_name plans + the branches the ARGUMENTS select inside those kernels -- bias / dbias, the accumulate flags,
+    which tensors are channel-range views of wider buffers (a batch stride above dense), and Cout = 1 for the generic GEMM kernels (what the
+    fused deep-supervision heads launch: a 4-, 16- or 64-row M with one output plane).  The only place that decides what "the same launch" means
+    for the guard below."""
+    L = ops.L
+    name = ops.convT_kernel_name(a, op, nxt)
+    plane, up = a.H * a.W, a.H * a.W * a.k * a.k
+    dense = dict(x=a.Cin * plane, y=a.Cout * up, dy=a.Cout * up, dx=a.Cin * plane)
+    f = []
+
+    def views(s, *names):
+        f.extend(f"{n}_strided" for n in names if getattr(s, n + "_batch_stride") != dense[n])
+
+    if op == L.OP_CONVT_FWD:
+        f += ["bias"] if a.bias else []
+        views(a, "x", "y")
+    elif op == L.OP_CONVT_DGRAD:
+        f += ["acc_dx"] if a.accumulate_dx else []
+        views(a, "dy", "dx")
+    else:
+        f += ["dbias"] if a.dbias else []
+        f += ["acc_dw"] if a.accumulate_dw else []
+        views(a, "x", "dy")
+        if nxt is not None:
+            f += ["acc_dx"] if nxt.accumulate_dx else []
+            views(nxt, "dx")
+    if re.search(r"\bconvT_(fwd|dgrad|wgrad)_kernel<", name) and a.Cout == 1:
+        f.append("Cout=1")
+    return name, tuple(f)
+
+
+def _same_upconv(wg, dg):
+    """The DGRAD behind a WGRAD belongs to the same up-convolution (engine.StepPlan.convT emits the two back to back)."""
+    return all(getattr(wg, n) == getattr(dg, n) for n in ("N", "H", "W", "Cin", "Cout", "k", "dy", "w"))
+
+
+def _program_convT_keys(arch, dtype, N, size):
+    """Builds (does not run) one step program with bench.py's constructor path: {(kind, key): (N, Cin, Cout, H, W, k) of one op that has it};
+    kind "pair" = an OP_CONVT_WGRAD with the OP_CONVT_DGRAD of the same problem right behind it in the same program."""
+    from multi_task_breast_cancer_amd.experiment_init import init_multitask_model, init_optimizer
+    from multi_task_breast_cancer_amd.miscellany import seed_everything
+    from multi_task_breast_cancer_amd.trainer import FusedTrainStep
+    L = ops.L
+    kinds = {L.OP_CONVT_FWD: "fwd", L.OP_CONVT_DGRAD: "dgrad", L.OP_CONVT_WGRAD: "wgrad"}
+    seed_everything(1993)
+    model = init_multitask_model(arch, sequences=1, regions=1, n_classes=3, deep_supervision=True).to(DEV)
+    model.set_compute(dtype)
+    step = FusedTrainStep(model, init_optimizer(model, "Adam", 1e-4), alpha=0.5, inversely_weighted=True)
+    st = step._compiled(N, size, size)
+    seen = {}
+    for prog in st.programs.values():
+        n, i = getattr(prog, "n", 0), 0
+        while i < n:
+            op = prog.array[i]
+            if op.kind in kinds:
+                a = op.u.convT
+                shape = (a.N, a.Cin, a.Cout, a.H, a.W, a.k)
+                nxt = prog.array[i + 1] if i + 1 < n else None
+                if op.kind == L.OP_CONVT_WGRAD and nxt is not None and nxt.kind == L.OP_CONVT_DGRAD and _same_upconv(a, nxt.u.convT):
+                    seen.setdefault(("pair", _convT_key(a, op.kind, nxt.u.convT)), shape)
+                    i += 1
+                else:
+                    seen.setdefault((kinds[op.kind], _convT_key(a, op.kind)), shape)
+            i += 1
+    del st, step, model
+    torch.cuda.empty_cache()
+    return seen
+
+
+# (kind, N, Cin, Cout, H, W, k, mode, strided): kind "fwd" / "dgrad" / "wgrad" = one call through ops.convT_launch, "pair" = [OP_CONVT_WGRAD,
+# OP_CONVT_DGRAD] through engine.Program (the fused kernel where the runner takes the pair, the two calls' launches otherwise).  mode: the
+# keywords of ops.convT_case_args.  strided: the activation tensors that are channel ranges [8, 8 + C) of a buffer 16 channels wider.  Each
+# row is the smallest problem that reaches its instance and still has the structure that can go wrong there: steps are 32 pixels, the weight
+# gradient's plan gives a split at least 8 steps, so N * H * W / 256 splits; input channels go in blocks of 48, output channels in tiles of 8.
+_B16 = dict(compute=1, dy16=True, x16=True)          # the 16-bit modes' backward: dy and x as 16-bit planes of the compute type
+_F16 = dict(compute=2, dy16=True, x16=True)
+_XY, _DYDX, _XDY, _ALL = ("x", "y"), ("dy", "dx"), ("x", "dy"), ("x", "dy", "dx")
+CONVT_CASES = [
+    # ---- forward, 16-bit MFMA on channel-blocked x and y: convT2_fwd_lp_c8_kernel<MTC, F16>, MTC by the LDS budget
+    ("fwd", 3, 96, 48, 8, 16, 2, dict(compute=1, x_c8=True, y_c8=True), _XY),                  # MTC = 3; 12 tasks = 3 blocks; x and y views
+    ("fwd", 2, 56, 40, 16, 16, 2, dict(compute=2, x_c8=True, y_c8=True), ()),                  # MTC = 3; Cin = 56: 8 kpad columns; Cout % 16 == 8: padded last tile with bias
+    ("fwd", 2, 128, 128, 8, 8, 2, dict(compute=1, x_c8=True, y_c8=True), ()),                  # MTC = 3, dense; MTnnUNet's 128 -> 128: the third channel block 32 of 48 wide
+    ("fwd", 2, 192, 96, 8, 8, 2, dict(compute=1, x_c8=True, y_c8=True), ()),                   # MTC = 2 by LDS (Cin = 192); three channel blocks
+    ("fwd", 2, 224, 64, 8, 8, 2, dict(compute=1, x_c8=True, y_c8=True, bias=False), _XY),      # MTC = 2 at the first Cin that needs it; views; no bias
+    ("fwd", 2, 48, 48, 8, 16, 2, dict(compute=2, x_c8=True, y_c8=True), ("y",)),               # MTC = 3, fp16: the U-Net++ 48 -> 48 into a view
+    ("fwd", 2, 256, 40, 8, 8, 2, dict(compute=2, x_c8=True, y_c8=True), ()),                   # MTC = 2 by LDS (Cin = 256), dense; Cout % 16 == 8
+    ("fwd", 3, 40, 24, 8, 16, 2, dict(compute=2, x_c8=True, y_c8=True), _XY),                  # MTC = 2 by Cout; Cin = 40: 24 kpad columns; Cout % 16 == 8
+    ("fwd", 1, 384, 192, 8, 8, 2, dict(compute=1, x_c8=True, y_c8=True), ()),                  # MTC = 1 by LDS (Cin = 384): 12 channel blocks
+    ("fwd", 2, 320, 320, 8, 8, 2, dict(compute=1, x_c8=True, y_c8=True, bias=False), _XY),     # MTC = 1, MTnnUNet's 320-wide level (kpad = 320); no bias
+    ("fwd", 1, 288, 64, 8, 8, 2, dict(compute=2, x_c8=True, y_c8=True), ()),                   # MTC = 1 by LDS at the first Cin that needs it, dense
+    ("fwd", 2, 24, 8, 8, 16, 2, dict(compute=2, x_c8=True, y_c8=True), _XY),                   # MTC = 1 by Cout = 8: half a channel tile
+    # ---- forward, fp32 x into a channel-blocked 16-bit y: convT2_fwd_c8_kernel<KI, F16>
+    ("fwd", 2, 24, 24, 8, 16, 2, dict(compute=1, y_c8=True), _XY),                             # KI = 8; Cout % 16 == 8
+    ("fwd", 2, 32, 40, 16, 16, 2, dict(compute=2, y_c8=True, bias=False), ("x",)),             # KI = 8 full; Cout % 16 == 8, no bias
+    ("fwd", 3, 48, 48, 8, 16, 2, dict(compute=1, y_c8=True), _XY),                             # KI = 12; the U-Net++ 48 -> 48
+    ("fwd", 2, 40, 8, 16, 16, 2, dict(compute=2, y_c8=True), _XY),                             # KI = 12 ragged (10 of 12); Cout = 8
+    ("fwd", 2, 64, 48, 8, 8, 2, dict(compute=1, y_c8=True), _XY),                              # KI = 16 full
+    ("fwd", 2, 56, 24, 16, 16, 2, dict(compute=2, y_c8=True), _XY),                            # KI = 16 ragged (14 of 16)
+    # ---- forward, fp32: convT2_fwd_lds_kernel<KI> and the generic GEMM convT_fwd_kernel<k>
+    ("fwd", 2, 20, 12, 8, 16, 2, {}, ()),                                                      # KI = 8 ragged
+    ("fwd", 3, 48, 48, 16, 16, 2, {}, _XY),                                                    # KI = 12
+    ("fwd", 2, 48, 24, 8, 16, 2, {}, ()),                                                      # KI = 12, dense
+    ("fwd", 2, 64, 40, 8, 8, 2, dict(bias=False), _XY),                                        # KI = 16, no bias
+    ("fwd", 2, 96, 48, 8, 8, 2, {}, _XY),                                                      # generic k = 2: Cin above the LDS kernel's 64
+    ("fwd", 2, 20, 12, 6, 10, 2, dict(bias=False), ()),                                        # generic k = 2: a 60-pixel map (one ragged 64-column block)
+    ("fwd", 2, 96, 48, 6, 10, 2, {}, ()),                                                      # generic k = 2, dense, with bias
+    ("fwd", 2, 64, 1, 8, 8, 4, {}, ()),                                                        # the fused heads, dense: Cout = 1, k = 4
+    ("fwd", 2, 32, 1, 8, 8, 2, {}, ("x",)),                                                    # the fused heads: Cout = 1, M = 4 rows
+    ("fwd", 2, 64, 1, 6, 10, 4, {}, ("x",)),                                                   # ... k = 4: M = 16
+    ("fwd", 2, 128, 1, 4, 4, 8, {}, ()),                                                       # ... k = 8: M = 64
+    ("fwd", 2, 16, 3, 4, 4, 8, {}, _XY),                                                       # generic k = 8, Cout > 1, views
+    ("fwd", 3, 24, 5, 5, 9, 4, {}, ()),                                                        # generic k = 4, Cout > 1, odd map
+    # ---- dgrad, 16-bit dy: weights in LDS (Cout % 8 == 0 and <= 256), else the direct kernel with D = 2 | 4
+    ("dgrad", 3, 48, 48, 8, 16, 2, dict(compute=1, dy16=True), _DYDX),                         # convT2_dgrad_lds_kernel<1, 4>; 12 tasks; views
+    ("dgrad", 2, 64, 256, 8, 8, 2, dict(compute=2, dy16=True, acc_dx=True), _DYDX),            # <2, 4>: the last Cout with weights in LDS; ragged second input block
+    ("dgrad", 2, 96, 192, 8, 8, 2, dict(compute=1, dy16=True, acc_dx=True), ("dy",)),          # <1, 4>, accumulate, two input blocks
+    ("dgrad", 2, 48, 320, 8, 8, 2, dict(compute=1, dy16=True), _DYDX),                         # direct <1, true, 4>: MTnnUNet's 320-wide level, past the LDS gate
+    ("dgrad", 1, 320, 320, 8, 16, 2, dict(compute=2, dy16=True, acc_dx=True), _DYDX),          # direct <2, true, 4>; ragged last input block (320 = 6 x 48 + 32)
+    ("dgrad", 2, 40, 20, 8, 16, 2, dict(compute=1, dy16=True), _DYDX),                         # direct <1, true, 2>: Cout % 8 != 0
+    ("dgrad", 3, 24, 12, 8, 8, 2, dict(compute=2, dy16=True, acc_dx=True), _DYDX),             # direct <2, true, 2>
+    # ---- dgrad, fp32 dy: convT2_dgrad_kernel<LP, false, 2> and the generic GEMM
+    ("dgrad", 2, 48, 24, 8, 16, 2, {}, _DYDX),                                                 # <0>
+    ("dgrad", 2, 56, 40, 8, 8, 2, dict(compute=1, acc_dx=True), _DYDX),                        # <1>
+    ("dgrad", 2, 96, 48, 8, 8, 2, dict(compute=2), _DYDX),                                     # <2>
+    ("dgrad", 2, 20, 12, 6, 10, 2, dict(acc_dx=True), ()),                                     # generic k = 2 (60-pixel map)
+    ("dgrad", 2, 32, 1, 8, 8, 2, {}, ("dx",)),                                                 # the fused heads: Cout = 1 (odd: never the direct kernel), K = 4
+    ("dgrad", 2, 32, 1, 8, 16, 2, {}, ()),                                                     # ... as the programs have them: dense, stored; two column blocks
+    ("dgrad", 2, 64, 1, 6, 10, 4, {}, ()),
+    ("dgrad", 2, 128, 1, 4, 4, 8, {}, ()),
+    ("dgrad", 2, 64, 1, 6, 10, 4, dict(acc_dx=True), ("dx",)),                                 # ... k = 4
+    ("dgrad", 2, 128, 1, 4, 4, 8, dict(acc_dx=True), ("dx",)),                                 # ... k = 8
+    ("dgrad", 3, 24, 5, 5, 9, 4, {}, ()),                                                      # generic k = 4, Cout > 1
+    # ---- wgrad, x and dy as 16-bit planes: convT2_wgrad16_kernel<LP, 2, 2> (even tile count) / <LP, 1, 4> (odd), XCD task order from 8 splits
+    ("wgrad", 1, 48, 48, 16, 16, 2, _B16, ()),                                                 # <1, 2, 2>, 8 steps: one split, stored straight
+    ("wgrad", 3, 64, 16, 16, 24, 2, dict(_F16, acc_dw=True, bias=False), _XDY),                # <2, 2, 2>, 36 steps: 5 splits, the last short, straddling images
+    ("wgrad", 2, 96, 32, 32, 32, 2, dict(_B16, acc_dw=True), ()),                              # <1, 2, 2> xcd: 8 splits, one per XCD
+    ("wgrad", 3, 48, 192, 24, 40, 2, dict(_F16, bias=False), _XDY),                            # <2, 2, 2> xcd: 90 steps = 12 splits (4 phantoms), the last 2 steps
+    ("wgrad", 2, 40, 24, 8, 16, 2, dict(_B16, bias=False), _XDY),                              # <1, 1, 4>: one split; ragged input block
+    ("wgrad", 3, 56, 40, 16, 24, 2, dict(_F16, acc_dw=True), ()),                              # <2, 1, 4>: 5 splits, short last
+    ("wgrad", 3, 48, 8, 32, 32, 2, dict(_B16, acc_dw=True), _XDY),                             # <1, 1, 4> xcd: 12 splits (4 phantoms); Cout = 8
+    ("wgrad", 3, 64, 24, 24, 40, 2, _F16, _XDY),                                               # <2, 1, 4> xcd: 12 splits, the last 2 steps
+    # ---- wgrad, 16-bit dy with fp32 x, fp32 operands, and the generic GEMM
+    ("wgrad", 3, 48, 24, 16, 24, 2, dict(compute=1, dy16=True), _XDY),                         # convT2_wgrad_kernel<1, true, 2>, 5 splits
+    ("wgrad", 2, 96, 48, 8, 16, 2, dict(compute=2, dy16=True, acc_dw=True, bias=False), _XDY), # <2, true, 2>, one split
+    ("wgrad", 3, 20, 12, 16, 24, 2, {}, _XDY),                                                 # <0, false, 2>: ragged input block and channel tile
+    ("wgrad", 2, 48, 48, 8, 16, 2, dict(compute=1, acc_dw=True), _XDY),                        # <1, false, 2>
+    ("wgrad", 1, 96, 40, 16, 16, 2, dict(compute=2, bias=False), ("x",)),                      # <2, false, 2>
+    ("wgrad", 2, 32, 1, 8, 16, 2, {}, ("x",)),                                                 # the k = 2 head: Cout = 1 takes the direct kernel (one eighth of a tile)
+    ("wgrad", 3, 32, 1, 16, 24, 2, {}, ()),                                                    # ... dense, 5 splits
+    ("wgrad", 2, 64, 1, 6, 10, 4, {}, ()),                                                     # the fused heads on the generic kernel as the programs have them: dense
+    ("wgrad", 2, 128, 1, 4, 4, 8, {}, ()),
+    ("wgrad", 2, 20, 12, 6, 10, 2, dict(acc_dw=True), ()),                                     # generic k = 2 + channel_sums
+    ("wgrad", 2, 32, 1, 6, 10, 2, {}, ("x",)),                                                 # the fused heads on the generic kernel: Cout = 1
+    ("wgrad", 2, 64, 1, 6, 10, 4, {}, ("x",)),                                                 # ... k = 4
+    ("wgrad", 2, 128, 1, 4, 4, 8, dict(bias=False), _XDY),                                     # ... k = 8
+    ("wgrad", 3, 24, 5, 5, 9, 4, dict(acc_dw=True), ()),                                       # generic k = 4, Cout > 1
+    # ---- the program runner's pair, fused: convT2_bwd_fused_kernel<LP, CT, NW, ACC>; the grid is 8 x cdiv(splits, 8) x input blocks
+    ("pair", 2, 64, 24, 16, 16, 2, _B16, _ALL),                                                # <1, 1, 3, false>: 2 splits; ragged second input block
+    ("pair", 3, 40, 24, 16, 24, 2, dict(_B16, acc_dx=True, acc_dw=True, bias=False), _ALL),    # <1, 1, 3, true>: 5 splits, short last, straddling images
+    ("pair", 3, 56, 24, 32, 32, 2, dict(_F16, bias=False), _ALL),                              # <2, 1, 3, false>: 12 splits, 4 phantoms
+    ("pair", 1, 48, 24, 16, 16, 2, dict(_F16, acc_dx=True), _ALL),                             # <2, 1, 3, true>: one split
+    ("pair", 3, 48, 48, 32, 32, 2, _B16, _ALL),                                                # <1, 2, 3, false>: 12 splits, 4 phantoms
+    ("pair", 2, 96, 48, 32, 32, 2, dict(_B16, acc_dx=True, acc_dw=True), _ALL),                # <1, 2, 3, true>: 8 splits
+    ("pair", 3, 48, 48, 16, 24, 2, dict(_F16, acc_dw=True), _ALL),                             # <2, 2, 3, false>: 5 splits
+    ("pair", 2, 96, 48, 8, 16, 2, dict(_F16, acc_dx=True, bias=False), _ALL),                  # <2, 2, 3, true>: one split
+    ("pair", 1, 192, 96, 8, 8, 2, dict(_B16, bias=False), _ALL),                               # <1, 2, 6, false>: the six-wave workgroup, one split of 2 steps
+    ("pair", 3, 96, 96, 16, 24, 2, dict(_B16, acc_dx=True), _ALL),                             # <1, 2, 6, true>: 5 splits
+    ("pair", 3, 64, 96, 24, 40, 2, dict(_F16, acc_dw=True), _ALL),                             # <2, 2, 6, false>: 12 splits (4 phantoms), the last 2 steps
+    ("pair", 2, 192, 96, 8, 16, 2, dict(_F16, acc_dx=True), _ALL),                             # <2, 2, 6, true>
+    # ... and the argument sets the programs have: dense tensors, dbias, dW stored
+    ("pair", 2, 48, 48, 16, 16, 2, _B16, ()),                                                  # <1, 2, 3, false>: 2 splits
+    ("pair", 3, 96, 48, 16, 24, 2, dict(_B16, acc_dx=True), ()),                               # <1, 2, 3, true>: 5 splits, short last
+    ("pair", 3, 48, 48, 32, 32, 2, _F16, ()),                                                  # <2, 2, 3, false>: 12 splits, 4 phantoms
+    ("pair", 2, 96, 48, 16, 16, 2, dict(_F16, acc_dx=True), ()),                               # <2, 2, 3, true>: 2 splits
+    # ---- the pair where the fused kernel does not take it: the two calls' launches
+    ("pair", 3, 48, 192, 24, 40, 2, _B16, ()),                                                 # wgrad16 <1, 2, 2> xcd: 12 splits, the last 2 steps + dgrad_lds; dense
+    ("pair", 2, 96, 256, 32, 32, 2, dict(_B16, acc_dx=True), ()),                              # ... 8 splits; Cout = 256, the last with weights in LDS (MTnnUNet 256 -> 256)
+    ("pair", 2, 48, 192, 32, 32, 2, _F16, ()),                                                 # wgrad16 <2, 2, 2> xcd + dgrad_lds <2, 4>
+    ("pair", 3, 96, 256, 24, 40, 2, dict(_F16, acc_dx=True), ()),
+    ("pair", 3, 320, 320, 8, 16, 2, dict(compute=1), ()),                                      # MTnnUNet's deepest up-conv: fp32 x and dy, bf16 MFMAs, 2 splits
+    ("pair", 3, 32, 32, 16, 24, 2, dict(compute=1, dy16=True, acc_dx=True), ()),               # MTnnUNet's top level: 16-bit dy, fp32 x
+    ("pair", 3, 48, 48, 16, 24, 2, {}, ()),                                                    # the fp32 mode, dense
+    ("pair", 3, 192, 96, 8, 16, 2, dict(acc_dx=True), ()),                                     # ... accumulating, two splits
+    ("pair", 3, 48, 192, 32, 32, 2, _B16, _ALL),                                               # Cout = 192 (12 waves): wgrad16 <1, 2, 2> xcd + dgrad_lds
+    ("pair", 1, 384, 192, 8, 8, 2, dict(_F16, acc_dx=True), ()),                               # the deepest U-Net++ up-conv, one split
+    ("pair", 2, 64, 320, 8, 16, 2, dict(_B16, acc_dx=True), ()),                               # MTnnUNet's 320-wide level: wgrad16 + the direct D = 4 dgrad
+    ("pair", 3, 48, 48, 16, 24, 2, dict(acc_dx=True), _ALL),                                   # fp32: convT2_wgrad_kernel<0> + convT2_dgrad_kernel<0>
+]
+
+
+def _convT_case_id(case):
+    kind, N, Cin, Cout, H, W, k, mode, strided = case
+    return f"{kind}-{N}x{Cin}>{Cout}x{H}x{W}k{k}-" + ",".join(f"{n}={int(v)}" for n, v in sorted(mode.items())) + ("-" + "+".join(strided) if strided else "")
+
+
+_CT_PAD = 8           # channels in front of and behind a view
+
+
+def _convT_case_args(case, op, ptrs=None):
+    """ops.convT_case_args of one call of a case (dummy pointers without ptrs)."""
+    kind, N, Cin, Cout, H, W, k, mode, strided = case
+    chans = dict(x=(Cin, H * W), y=(Cout, H * W * k * k), dy=(Cout, H * W * k * k), dx=(Cin, H * W))
+    strides = {n: (chans[n][0] + 2 * _CT_PAD) * chans[n][1] for n in strided}
+    return ops.convT_case_args(op, N, Cin, Cout, H, W, k, ptrs=ptrs, strides=strides, **mode)
+
+
+def _convT_case_calls(case, ptrs=None):
+    """[(kind, op, args, args of the DGRAD behind it or None)] of the launches a case makes."""
+    L = ops.L
+    kind = case[0]
+    if kind == "pair":
+        return [(kind, L.OP_CONVT_WGRAD, _convT_case_args(case, L.OP_CONVT_WGRAD, ptrs), _convT_case_args(case, L.OP_CONVT_DGRAD, ptrs))]
+    op = {"fwd": L.OP_CONVT_FWD, "dgrad": L.OP_CONVT_DGRAD, "wgrad": L.OP_CONVT_WGRAD}[kind]
+    return [(kind, op, _convT_case_args(case, op, ptrs), None)]
+
+
+class _CtTensor:
+    """One activation tensor of a case on the device: `fmt` "f32" planes, "p16" 16-bit planes, "c8" 16-bit channel-blocked of type st;
+    `view` (what the kernel is given) is channels [pad, pad + C) of `buf`.  `cpu` keeps the buffer as uploaded."""
+
+    def __init__(self, vals, fmt, st, pad, g):
+        N, C, H, W = vals.shape
+        wide = torch.randn(N, C + 2 * pad, H, W, generator=g)
+        wide[:, pad:pad + C] = vals
+        self.fmt, self.st, self.pad, self.shape = fmt, st, pad, (N, C, H, W)
+        if fmt == "f32":
+            self.cpu = wide
+        elif fmt == "p16":
+            self.cpu = _bits16(wide, st)
+        else:
+            self.cpu = _c8_of(wide, st)
+        self.buf = self.cpu.to(DEV)
+        q = pad // 8 if fmt == "c8" else pad
+        c = C // 8 if fmt == "c8" else C
+        self.view = self.buf[:, q:q + c]
+        self._sl = slice(q, q + c)
+
+    def data_ptr(self):
+        return self.view.data_ptr()
+
+    def read(self):
+        """(values of the view as fp64 (N, C, H, W), True when everything around the view still holds what was uploaded)"""
+        got = self.buf.cpu()
+        keep = torch.ones(got.shape[1], dtype=torch.bool)
+        keep[self._sl] = False
+        untouched = torch.equal(got[:, keep], self.cpu[:, keep])
+        v = got[:, self._sl]
+        if self.fmt == "f32":
+            return v.double(), untouched
+        if self.fmt == "p16":
+            return _from16(v, self.st), untouched
+        return _planes_of(v.contiguous(), self.shape, self.st), untouched
+
+
+@pytest.mark.parametrize("case", CONVT_CASES, ids=_convT_case_id)
+def test_convT_step_instances_match_fp64(case):
+    """Every transposed-convolution instance the dispatchers of convt2.hip / pool_up.hip can pick outside the A/B probe switches -- the ones
+    the benchmark's step programs launch among them (test_step_programs_launch_only_reference_tested_convT_instances) -- against the plain
+    fp64 reference of oracle/convt_reference.py on the STORED operands: inputs are drawn on the CPU and rounded RNE to the type the mode
+    stores or the MFMA reads, so the kernel's own rounding is the identity.  Every element of every output is compared:
+      fp32 forward and dx     max error <= 1e-5 x max |ref|                       (test_conv3x3_bench_instances_match_fp64)
+      16-bit stored forward   per element within one unit in the last place of the stored type at the fp64 value + 1e-5 x max |ref| (_ulp16)
+      dW, dbias               max error <= 1e-4 x max(1, max |ref|)               (test_convT_wgrad_reads_16bit_planar_x)
+      accumulate              against ref + pre-fill, the same bound on the larger of the two scales
+    Outputs are pre-filled; what a call was not asked for (no dbias, a lone WGRAD's dx, a lone DGRAD's dW) and the channels around a view
+    keep their pre-fill bit for bit.  The launches made are exactly what mtbc_convT_kernel_name plans for the case's dummy arguments."""
+    from multi_task_breast_cancer_amd.engine import Program, _mk
+    from oracle import convt_reference as R
+    L = ops.L
+    kind, N, Cin, Cout, H, W, k, mode, strided = case
+    compute = mode.get("compute", 0)
+    fwd = kind == "fwd"
+    g = _g(1993 + 7919 * N + 31 * Cin + 17 * Cout + H * W + k + 3 * compute + len(strided))
+    # operand rounding: the forward on fp32 x is exact fp32 whatever y's type; everything else with compute != 0 reads 16-bit operands
+    lp = compute if (not fwd or mode.get("x_c8")) else 0
+    rnd = (lambda t: _round16(t, lp)) if lp else (lambda t: t)
+    x = rnd(torch.randn(N, Cin, H, W, generator=g))
+    w = rnd(torch.randn(Cin, Cout, k, k, generator=g) * (1.0 / Cin) ** 0.5)
+    b = torch.randn(Cout, generator=g)
+    dy = rnd(torch.randn(N, Cout, H * k, W * k, generator=g))
+    pad = lambda n: _CT_PAD if n in strided else 0      # noqa: E731
+    xfmt = "c8" if mode.get("x_c8") else "p16" if mode.get("x16") else "f32"
+    T = dict(x=_CtTensor(x, xfmt, compute, pad("x"), g), w=w.to(DEV))
+    pre = {}
+    if fwd:
+        pre["y"] = torch.randn(N, Cout, H * k, W * k, generator=g)
+        T["y"] = _CtTensor(pre["y"], "c8" if mode.get("y_c8") else "f32", compute, pad("y"), g)
+        T["bias"] = b.to(DEV)
+    else:
+        T["dy"] = _CtTensor(dy, "p16" if mode.get("dy16") else "f32", compute, pad("dy"), g)
+        pre["dx"] = torch.randn(N, Cin, H, W, generator=g)
+        T["dx"] = _CtTensor(pre["dx"], "f32", 0, pad("dx"), g)
+        pre["dw"], pre["dbias"] = torch.randn(Cin, Cout, k, k, generator=g), torch.randn(Cout, generator=g)
+        T["dw"], T["dbias"] = pre["dw"].to(DEV), pre["dbias"].to(DEV)
+        # the workspace the library asks for, NaN so that a partial row nobody wrote shows in dW, inside a larger allocation: room for the 7
+        # phantom splits a grid rounded up to 8 x cdiv(splits, 8) can have, which must come back untouched
+        nfloat = max(4, (max(int(c[2].workspace_bytes) for c in _convT_case_calls(case)) + 3) // 4)
+        slack = torch.full((nfloat + 8 * (Cin * Cout * k * k + Cout),), float("nan"), device=DEV)
+        slack[nfloat:] = 1993.0
+        T["workspace"] = slack[:nfloat]
+    planned = [(op, ops.convT_kernel_name(a, op, nxt)) for _, op, a, nxt in _convT_case_calls(case)]
+    calls = _convT_case_calls(case, T)
+    assert [(op, ops.convT_kernel_name(a, op, nxt)) for _, op, a, nxt in calls] == planned, "the real pointers plan something else than the dummies"
+    ops.launched = []
+    try:
+        for _, op, a, nxt in calls:
+            if kind == "wgrad":
+                a.dx, a.dx_batch_stride = T["dx"].data_ptr(), Cin * H * W          # a lone WGRAD has no business with dx
+            if nxt is None:
+                ops.convT_launch(a, op)
+            else:
+                two = [_mk(L.OP_CONVT_WGRAD), _mk(L.OP_CONVT_DGRAD)]
+                two[0].u.convT, two[1].u.convT = a, nxt
+                ops.convT_note(a, op, nxt)
+                Program(two, [T]).run()
+        torch.cuda.synchronize()
+        made = list(ops.launched)
+    finally:
+        ops.launched = None
+    assert made == planned, (made, planned)
+    name = planned[0][1]
+
+    worst = {}
+
+    def check_max(what, got, ref, tol, floor, prefill=None):
+        want = ref if prefill is None else ref + prefill.double()
+        assert bool(torch.isfinite(got).all()), f"{what}: non-finite"
+        scale = max(floor, ref.abs().max().item(), want.abs().max().item())
+        err = (got - want).abs().max().item()
+        worst[what] = err / (tol * scale)
+        return f"{what} ({name}): max err {err:.3e} against {tol:g} x {scale:.3e}"
+
+    msgs = []
+    xr, wr, dyr = x.double(), w.double(), dy.double()
+    if fwd:
+        ref = R.convT_fwd64(xr, wr, b if mode.get("bias", True) else None, k)
+        got, untouched = T["y"].read()
+        assert untouched, "y: the channels around the view were written"
+        if mode.get("y_c8"):
+            assert bool(torch.isfinite(got).all()), "stored y: non-finite"
+            bound = _ulp16(ref, compute) + 1e-5 * ref.abs().max().item()
+            worst["y16"] = ((got - ref).abs() / bound).max().item()
+            msgs.append(f"stored y ({name}): {worst['y16']:.3f} x (one ulp of the stored type + 1e-5 x scale)")
+        else:
+            msgs.append(check_max("y", got, ref, 1e-5, 0.0))
+    has_dx, has_dw = kind in ("dgrad", "pair"), kind in ("wgrad", "pair")
+    if not fwd:
+        got, untouched = T["dx"].read()
+        assert untouched, "dx: the channels around the view were written"
+        if has_dx:
+            msgs.append(check_max("dx", got, R.convT_dx64(dyr, wr, k), 1e-5, 0.0, pre["dx"] if mode.get("acc_dx") else None))
+        else:
+            assert torch.equal(got.float(), pre["dx"]), "a lone WGRAD wrote dx"
+        if has_dw:
+            acc = mode.get("acc_dw")
+            msgs.append(check_max("dW", T["dw"].cpu().double(), R.convT_dw64(xr, dyr, k), 1e-4, 1.0, pre["dw"] if acc else None))
+            if mode.get("bias", True):
+                msgs.append(check_max("dbias", T["dbias"].cpu().double(), R.convT_dbias64(dyr), 1e-4, 1.0, pre["dbias"] if acc else None))
+            else:
+                assert torch.equal(T["dbias"].cpu(), pre["dbias"]), "dbias was written without being asked for"
+        else:
+            assert torch.equal(T["dw"].cpu(), pre["dw"]) and torch.equal(T["dbias"].cpu(), pre["dbias"]), "a lone DGRAD wrote dW / dbias"
+    if not fwd:
+        assert bool((slack[nfloat:] == 1993.0).all()), "the memory behind the workspace was written"
+    for n in ("x", "dy"):             # inputs, and the channels around their views, are read-only
+        if n in T:
+            assert torch.equal(T[n].buf.cpu(), T[n].cpu), f"{n} was written"
+    print(f"{_convT_case_id(case)}: {name}: worst error / bound " + ", ".join(f"{n} {v:.3f}" for n, v in worst.items()))
+    bad = [m for m, v in zip(msgs, worst.values()) if not v <= 1.0]
+    assert not bad, "; ".join(bad)
+
+
+def _reference_tested_convT_keys():
+    """(kind, key) of every call test_convT_step_instances_match_fp64 makes, from its case table's argument structs."""
+    return {(kind, _convT_key(a, op, nxt)) for case in CONVT_CASES for kind, op, a, nxt in _convT_case_calls(case)}
+
+
+def test_step_programs_launch_only_reference_tested_convT_instances():
+    """Builds (does not run) the benchmark's four step programs and computes the coverage key of every MTBC_OP_CONVT_FWD / _DGRAD / _WGRAD op
+    -- of the pair where a WGRAD has the DGRAD of the same up-convolution right behind it, which is what the program runner looks at --:
+    each must be the key of a call that test_convT_step_instances_match_fp64 makes.  A plan change -- another instance, the XCD order or the
+    fused kernel where it was not, a new argument-selected branch -- that no fp64 case reaches fails here; _convT_key, CONVT_CASES and
+    _reference_tested_convT_keys are the places to edit."""
+    tested = _reference_tested_convT_keys()
+    missing, total = {}, set()
+    for arch, dtype, N, size in STEP_PROGRAMS:
+        seen = _program_convT_keys(arch, dtype, N, size)
+        print(f"{arch} {dtype} N={N} {size}x{size}: {len(seen)} keys")
+        assert {"fwd", "pair"} <= {kind for kind, _ in seen}, f"{arch} {dtype}: no transposed-convolution launch found"
+        for (kind, key), shape in sorted(seen.items()):
+            print(f"  {kind} {key} at (N, Cin, Cout, H, W, k) = {shape}")
+            total.add((kind, key))
+            if (kind, key) not in tested:
+                missing.setdefault((arch, dtype, N, size), []).append((kind, key, shape))
+    print(f"{len(total)} distinct keys in the four programs, {len(tested)} keys tested")
+    assert not missing, "transposed-convolution launches of the step programs that no fp64 reference case makes: " + \
+        "".join(f"\n  {p_}: {kind} {k} at (N, Cin, Cout, H, W, k) = {s}" for p_, ks in missing.items() for kind, k, s in ks)
