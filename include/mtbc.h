@@ -296,7 +296,7 @@ typedef struct {
     const float* dy_pool;
     const void* dy_pool_arg;
     /* forward with stats_partial (the streaming pass): also write the activation's MaxPool2d(2,2) -- pool_y8: channel-blocked 16-bit
-       [N][C/8][H/2*W/2][8] of out16_type, the maxima of the STORED values (= mtbc_maxpool2_fwd on y8, bit for bit); pool_arg: optional
+       [N][C/8][H/2*W/2][8] of out16_type, the maxima of the STORED values (= mtbc_maxpool2_fwd on y8, bit for bit, NaN and -0 / +0 windows included: both take the scan stated at mtbc_maxpool_args); pool_arg: optional
        argmax codes (mtbc_maxpool_args.argmax).  H and W even.                                                                     */
     void* pool_y8;
     void* pool_arg;
@@ -346,7 +346,10 @@ int mtbc_instnorm_lrelu_bwd(const mtbc_instnorm_args* a, void* stream);
 
 /* --------------------------------------------------------------------- MaxPool2d(2, 2)
  * replaces nn.MaxPool2d(2,2): MTnnUNet.py:103 ; MONAI Down in MTUNetPlusPlus.py:48-51.
- * bwd routes dy to the first maximal element in (0,0),(0,1),(1,0),(1,1) order, like ATen.  */
+ * ONE definition of a window's maximum for the forward value, the argmax codes, the backward routing and the pool the streaming
+ * InstanceNorm pass writes (mtbc_instnorm_args.pool_y8) -- ATen's scan: in (0,0),(0,1),(1,0),(1,1) order an element replaces the running
+ * maximum when it is greater or a NaN.  So: the FIRST of equal maxima (-0 and +0 are equal: a window {-0, +0, ..} pools to -0), and a NaN
+ * is the maximum wherever it sits (the last of several).  fwd stores that element; bwd routes dy to it.  */
 typedef struct {
     int32_t N, C, H, W;              /* INPUT spatial size; output is H/2 x W/2              */
     const float* x;  int64_t x_batch_stride;
@@ -357,7 +360,7 @@ typedef struct {
     int32_t layout;                  /* 0 = fp32 planar x / y.  MTBC_LAYOUT_C8 (the 16-bit compute modes): x and y are 16-bit
                                         channel-blocked [N][C/8][H*W][8] of type16 (1 = bf16, 2 = fp16), batch strides in
                                         16-bit elements, C % 8 == 0 -- forward = the fp32 pool of the stored values followed
-                                        by mtbc_c8_pack, bit for bit (max commutes with rounding); backward routes on the
+                                        by mtbc_c8_pack, bit for bit (selecting a stored value commutes with rounding); backward routes on the
                                         stored values; dy / dx stay fp32 planar                                            */
     int32_t type16;
     void* argmax;                    /* fwd with layout C8, optional: (N, C/8, H/2 * W/2) 16-bit codes, bits [2c+1 : 2c] = which of the four
@@ -836,6 +839,20 @@ int mtbc_program_run_ms(const mtbc_op* ops, int32_t first, int32_t count, void* 
 /* timing-disabled HIP events for the two ops above; created when a step program is built, never inside a step */
 int mtbc_event_create(void** event);
 int mtbc_event_destroy(void* event);
+/* Host-only plan query for the small ops: every launch the call behind op->kind would make for op->u, in order and joined with " + ",
+ * written to buf (NUL-terminated).  Covers MTBC_OP_POOL_FWD / _BWD, MTBC_OP_CONV1_FWD / _DGRAD / _WGRAD, MTBC_OP_GAP_FWD / _BWD,
+ * MTBC_OP_LINEAR_FWD / _BWD and MTBC_OP_HEAD_COMBINE / _EXPAND; any other kind (the 3x3, InstanceNorm and ConvT ops have queries of their
+ * own) is MTBC_E_BADARG.  Kernels are spelled as a profiler spells the instance without namespace and argument list, e.g.
+ * "maxpool_c8_fwd_kernel<true>"; what the arguments select inside a kernel follows its name in brackets:
+ *   conv1x1_c8_wgrad_kernel<F16> [nblk=1] | [nblk>1] | [nblk=32]   pixel chunks per image (one / several, the last may be ragged / the cap)
+ *   plane_sum_k [threads=64] | [threads=256]                       the bias gradient's plane sums (256 from H*W = 4096)
+ *   linear_dx_kernel [Out>=8], linear_dw_kernel [N>=8]             the eight-wide unrolled loop runs
+ * and the planar 1x1 weight gradient's reduction is named with its instance: "splitk_reduce<4>", "<16>" (more than 32 images) or
+ * "<64, 16>" (256 images or more), e.g. "conv1x1_wgrad_kernel + splitk_reduce<4> + plane_sum_k [threads=64] + sum_over_n_k".
+ * It is the dispatcher of the real call, stopped in front of its launches: launches nothing, never synchronises, needs no device and never
+ * dereferences a tensor pointer (pointer VALUES count: NULL and alignment select branches); returns the code the real call would return
+ * when it refuses the arguments, MTBC_E_BADARG for a NULL op or a buffer shorter than the name. */
+int mtbc_op_kernel_name(const mtbc_op* op, char* buf, int32_t len);
 
 #ifdef __cplusplus
 }

@@ -287,7 +287,7 @@ EXPORTS = [
     "mtbc_focal_fwd_bwd", "mtbc_loss_mix", "mtbc_loss_scale_begin", "mtbc_loss_scale_check",
     "mtbc_loss_scale_update_host", "mtbc_loss_scale_begin_host", "mtbc_optim_step", "mtbc_optim_dynamic", "mtbc_loss_scale_optim", "mtbc_optim_step_host",
     "mtbc_dice_counts", "mtbc_program_run",
-    "mtbc_program_run_ms", "mtbc_event_create", "mtbc_event_destroy",
+    "mtbc_program_run_ms", "mtbc_event_create", "mtbc_event_destroy", "mtbc_op_kernel_name",
     "mtbc_seg_metrics_workspace_size", "mtbc_seg_metrics", "mtbc_batch_assemble", "mtbc_train_metrics",
     "mtbc_eval_metrics",
 ]
@@ -408,6 +408,8 @@ def load() -> C.CDLL:
     lib.mtbc_event_create.argtypes = [C.POINTER(C.c_void_p)]
     lib.mtbc_event_destroy.restype = C.c_int
     lib.mtbc_event_destroy.argtypes = [C.c_void_p]
+    lib.mtbc_op_kernel_name.restype = C.c_int
+    lib.mtbc_op_kernel_name.argtypes = [C.POINTER(Op), C.c_char_p, C.c_int32]
     lib.mtbc_seg_metrics_workspace_size.restype = C.c_size_t
     lib.mtbc_seg_metrics_workspace_size.argtypes = [C.POINTER(SegMetricsArgs)]
     lib.mtbc_seg_metrics.restype = C.c_int

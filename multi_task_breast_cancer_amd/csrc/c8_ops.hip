@@ -41,7 +41,10 @@ struct MpC8P {
     unsigned short* arg;                   // forward, optional: per (n, group, output pixel) the 8 two-bit positions of the maxima
 };
 // forward: one lane = one output pixel of one channel group: reads 2 rows x 32 contiguous bytes, writes one piece.
-// max commutes with the (monotonic) rounding, so this IS the fp32 pool followed by the pack.
+// The maximum is the first maximal element in (0,0),(0,1),(1,0),(1,1) order, a NaN counting as maximal (ATen's max_pool2d): the scan
+// of the backward, of the argmax codes and of the streaming InstanceNorm pass (norm_coop.hip, POOL), so value, code and routing agree for
+// every bit pattern (NaN, -0 against +0).  Selecting a stored value commutes with the (monotonic) rounding, so this IS the fp32 pool
+// followed by the pack.
 template <bool F16>
 __global__ void maxpool_c8_fwd_kernel(const MpC8P p) {
     const int oW = p.W >> 1, oH = p.H >> 1;
@@ -56,24 +59,22 @@ __global__ void maxpool_c8_fwd_kernel(const MpC8P p) {
     const u32x4 b0 = *reinterpret_cast<const u32x4*>(src + (size_t)p.W * 8), b1 = *reinterpret_cast<const u32x4*>(src + (size_t)p.W * 8 + 8);
     float va[8], vb[8], vc[8], vd[8];
     unpack8<F16>(a0, va); unpack8<F16>(a1, vb); unpack8<F16>(b0, vc); unpack8<F16>(b1, vd);
+    float mx[8];
+    unsigned code = 0;      // where the backward sends a window's gradient: the position of that first maximal element
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        float m = va[c]; unsigned arg = 0;
+        if (vb[c] > m || vb[c] != vb[c]) { m = vb[c]; arg = 1; }
+        if (vc[c] > m || vc[c] != vc[c]) { m = vc[c]; arg = 2; }
+        if (vd[c] > m || vd[c] != vd[c]) { m = vd[c]; arg = 3; }
+        mx[c] = m;
+        code |= arg << (2 * c);
+    }
     u32x4 o;
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-        o[i] = pack2<F16>(fmaxf(fmaxf(va[2 * i], vb[2 * i]), fmaxf(vc[2 * i], vd[2 * i])),
-                          fmaxf(fmaxf(va[2 * i + 1], vb[2 * i + 1]), fmaxf(vc[2 * i + 1], vd[2 * i + 1])));
+    for (int i = 0; i < 4; ++i) o[i] = pack2<F16>(mx[2 * i], mx[2 * i + 1]);
     *reinterpret_cast<u32x4*>(p.y + (size_t)n * p.ybs + ((size_t)g * oH * oW + (size_t)oy * oW + ox) * 8) = o;
-    if (p.arg) {        // where the backward sends a window's gradient: its first maximal element in (0,0),(0,1),(1,0),(1,1) order (ATen)
-        unsigned code = 0;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            float m = va[c]; unsigned arg = 0;
-            if (vb[c] > m || vb[c] != vb[c]) { m = vb[c]; arg = 1; }
-            if (vc[c] > m || vc[c] != vc[c]) { m = vc[c]; arg = 2; }
-            if (vd[c] > m || vd[c] != vd[c]) { m = vd[c]; arg = 3; }
-            code |= arg << (2 * c);
-        }
-        p.arg[((size_t)n * p.G8 + g) * oH * oW + (size_t)oy * oW + ox] = (unsigned short)code;
-    }
+    if (p.arg) p.arg[((size_t)n * p.G8 + g) * oH * oW + (size_t)oy * oW + ox] = (unsigned short)code;
 }
 // backward: the gradient of a window goes to its first maximal element in (0,0),(0,1),(1,0),(1,1) order (ATen), judged
 // on the stored (rounded) values -- the tensor the forward pooled.  dy / dx: fp32 planar.
@@ -197,24 +198,28 @@ inline int c1_blocks(int HW) { int nb = HW / 4096; if (nb < 1) nb = 1; if (nb > 
 }  // namespace
 
 // ---------------------------------------------------------------- internal entry points (called from pool_up.hip)
-int mtbc_i_maxpool_c8_fwd(const mtbc_maxpool_args* a, hipStream_t st) {
+int mtbc_i_maxpool_c8_fwd(const mtbc_maxpool_args* a, hipStream_t st, OpChoice* query) {
     if (a->C % 8 || (a->type16 != 1 && a->type16 != 2)) return MTBC_E_BADARG;
     if (!al16p(a->x) || !al16p(a->y) || (a->x_batch_stride & 7) || (a->y_batch_stride & 7)) return MTBC_E_UNSUPPORTED;
+    const bool f16 = a->type16 == 2;
+    if (query) { query->add("maxpool_c8_fwd_kernel<%s>", mtbc_tf(f16)); return MTBC_OK; }
     MpC8P p{a->N, a->C / 8, a->H, a->W, reinterpret_cast<const unsigned short*>(a->x), a->x_batch_stride,
             reinterpret_cast<unsigned short*>(a->y), a->y_batch_stride, nullptr, 0, nullptr, 0, 0, reinterpret_cast<unsigned short*>(a->argmax)};
     const size_t total = (size_t)a->N * p.G8 * (a->H / 2) * (a->W / 2);
-    if (a->type16 == 2) hipLaunchKernelGGL(maxpool_c8_fwd_kernel<true>, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, p);
+    if (f16) hipLaunchKernelGGL(maxpool_c8_fwd_kernel<true>, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(maxpool_c8_fwd_kernel<false>, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, p);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
-int mtbc_i_maxpool_c8_bwd(const mtbc_maxpool_args* a, hipStream_t st) {
+int mtbc_i_maxpool_c8_bwd(const mtbc_maxpool_args* a, hipStream_t st, OpChoice* query) {
     if (a->C % 8 || (a->type16 != 1 && a->type16 != 2)) return MTBC_E_BADARG;
     if (!al16p(a->x) || (a->x_batch_stride & 7) || (reinterpret_cast<uintptr_t>(a->dx) & 7) || (a->dx_batch_stride & 1)) return MTBC_E_UNSUPPORTED;
+    const bool f16 = a->type16 == 2;
+    if (query) { query->add("maxpool_c8_bwd_kernel<%s>", mtbc_tf(f16)); return MTBC_OK; }
     MpC8P p{a->N, a->C / 8, a->H, a->W, reinterpret_cast<const unsigned short*>(a->x), a->x_batch_stride, nullptr, 0,
             a->dy, a->dy_batch_stride, a->dx, a->dx_batch_stride, a->accumulate_dx, nullptr};
     const size_t total = (size_t)a->N * p.G8 * (a->H / 2) * (a->W / 2);
-    if (a->type16 == 2) hipLaunchKernelGGL(maxpool_c8_bwd_kernel<true>, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, p);
+    if (f16) hipLaunchKernelGGL(maxpool_c8_bwd_kernel<true>, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(maxpool_c8_bwd_kernel<false>, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, p);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
@@ -227,10 +232,12 @@ static int fill_c1c8(const mtbc_conv1x1_args* a, C1C8P* p) {
     p->dy = a->dy; p->partial = nullptr; p->nblk = c1_blocks(p->HW); p->chunk = cdiv(p->HW, p->nblk);
     return MTBC_OK;
 }
-int mtbc_i_conv1x1_c8_fwd(const mtbc_conv1x1_args* a, hipStream_t st) {
+int mtbc_i_conv1x1_c8_fwd(const mtbc_conv1x1_args* a, hipStream_t st, OpChoice* query) {
     C1C8P p; int rc = fill_c1c8(a, &p); if (rc) return rc;
+    const bool f16 = a->x_type == 2;
+    if (query) { query->add("conv1x1_c8_fwd_kernel<%s>", mtbc_tf(f16)); return MTBC_OK; }
     const dim3 grid(cdiv(p.HW, 256), a->N);
-    if (a->x_type == 2) hipLaunchKernelGGL(conv1x1_c8_fwd_kernel<true>, grid, dim3(256), 0, st, p);
+    if (f16) hipLaunchKernelGGL(conv1x1_c8_fwd_kernel<true>, grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL(conv1x1_c8_fwd_kernel<false>, grid, dim3(256), 0, st, p);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
@@ -238,12 +245,19 @@ int mtbc_i_conv1x1_c8_fwd(const mtbc_conv1x1_args* a, hipStream_t st) {
 size_t mtbc_i_conv1x1_c8_wgrad_workspace(const mtbc_conv1x1_args* a) {
     return (size_t)a->N * c1_blocks(a->H * a->W) * ((size_t)a->Cout * a->Cin + a->Cout) * sizeof(float);
 }
-int mtbc_i_conv1x1_c8_wgrad(const mtbc_conv1x1_args* a, hipStream_t st) {
+int mtbc_i_conv1x1_c8_wgrad(const mtbc_conv1x1_args* a, hipStream_t st, OpChoice* query) {
     C1C8P p; int rc = fill_c1c8(a, &p); if (rc) return rc;
     if (!a->workspace || a->workspace_bytes < mtbc_i_conv1x1_c8_wgrad_workspace(a)) return MTBC_E_WORKSPACE;
+    const bool f16 = a->x_type == 2;
+    if (query) {      // nblk = the grid's x: one block per image, several chunks (the last may be ragged), or the cap
+        query->add("conv1x1_c8_wgrad_kernel<%s> [nblk%s]", mtbc_tf(f16), p.nblk == 1 ? "=1" : p.nblk == 32 ? "=32" : ">1");
+        query->add("c8_rows_sum_kernel");
+        if (a->dbias) query->add("c8_rows_sum_kernel");
+        return MTBC_OK;
+    }
     p.partial = reinterpret_cast<float*>(a->workspace);
     const dim3 grid(p.nblk, a->N);
-    if (a->x_type == 2) hipLaunchKernelGGL(conv1x1_c8_wgrad_kernel<true>, grid, dim3(256), 0, st, p);
+    if (f16) hipLaunchKernelGGL(conv1x1_c8_wgrad_kernel<true>, grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL(conv1x1_c8_wgrad_kernel<false>, grid, dim3(256), 0, st, p);
     MTBC_CHECK_LAUNCH();
     const int rows = a->N * p.nblk, row = a->Cout * a->Cin + a->Cout, wel = a->Cout * a->Cin;

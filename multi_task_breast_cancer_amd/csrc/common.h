@@ -176,16 +176,47 @@ struct NormChoice {
 extern "C" int mtbc_i_instnorm_fwd_c8(const mtbc_instnorm_args* a, hipStream_t st, NormChoice* query);
 extern "C" int mtbc_i_instnorm_bwd_c8(const mtbc_instnorm_args* a, float* part, hipStream_t st, NormChoice* query);
 extern "C" int mtbc_i_instnorm_bwd_c8_team(const mtbc_instnorm_args* a);
+// Which launches a max-pool, 1x1 convolution, GAP, Linear or fused-head call makes: the dispatchers of pool_up.hip, c8_ops.hip, head_loss.hip
+// and the two reducers of reduce.hip take a `query`; with it they validate as the call does, append every launch they would make -- the
+// kernel as a profiler spells the instance, then in brackets what the arguments select inside it -- and return without touching the stream
+// or the device.  Each decision (the kernel, its template argument, the reducer instance, a block size) is ONE local value that both the
+// launch and the query read: mtbc_op_kernel_name() cannot drift from the launch (NormChoice / ConvTChoice below, KernelChoice of conv3x3.hip).
+#include <stdarg.h>
+#include <stdio.h>
+struct OpChoice {
+    int n, len; char s[512];
+    void add(const char* fmt, ...) __attribute__((format(printf, 2, 3))) {
+        if (n++ && len < (int)sizeof s - 4) { s[len++] = ' '; s[len++] = '+'; s[len++] = ' '; }
+        va_list ap; va_start(ap, fmt);
+        const int w = vsnprintf(s + len, sizeof s - len, fmt, ap);
+        va_end(ap);
+        if (w < 0 || w >= (int)sizeof s - len) abort();          // (a call makes at most five launches with short names; more is a programming error)
+        len += w;
+    }
+};
+static inline const char* mtbc_tf(bool b) { return b ? "true" : "false"; }
 // c8_ops.hip: max-pool and 1x1 conv on 16-bit channel-blocked tensors
-int mtbc_i_maxpool_c8_fwd(const mtbc_maxpool_args* a, hipStream_t st);
-int mtbc_i_maxpool_c8_bwd(const mtbc_maxpool_args* a, hipStream_t st);
-int mtbc_i_conv1x1_c8_fwd(const mtbc_conv1x1_args* a, hipStream_t st);
+int mtbc_i_maxpool_c8_fwd(const mtbc_maxpool_args* a, hipStream_t st, OpChoice* query);
+int mtbc_i_maxpool_c8_bwd(const mtbc_maxpool_args* a, hipStream_t st, OpChoice* query);
+int mtbc_i_conv1x1_c8_fwd(const mtbc_conv1x1_args* a, hipStream_t st, OpChoice* query);
 size_t mtbc_i_conv1x1_c8_wgrad_workspace(const mtbc_conv1x1_args* a);
-int mtbc_i_conv1x1_c8_wgrad(const mtbc_conv1x1_args* a, hipStream_t st);
-// internal (C++) helpers implemented in reduce.hip
+int mtbc_i_conv1x1_c8_wgrad(const mtbc_conv1x1_args* a, hipStream_t st, OpChoice* query);
+// the entry points of pool_up.hip / head_loss.hip with the query (the extern "C" ones pass NULL)
+int mtbc_i_maxpool2_fwd(const mtbc_maxpool_args* a, hipStream_t st, OpChoice* query);
+int mtbc_i_maxpool2_bwd(const mtbc_maxpool_args* a, hipStream_t st, OpChoice* query);
+int mtbc_i_conv1x1_fwd(const mtbc_conv1x1_args* a, hipStream_t st, OpChoice* query);
+int mtbc_i_conv1x1_dgrad(const mtbc_conv1x1_args* a, hipStream_t st, OpChoice* query);
+int mtbc_i_conv1x1_wgrad(const mtbc_conv1x1_args* a, hipStream_t st, OpChoice* query);
+int mtbc_i_head_combine(const mtbc_head_fuse_args* a, hipStream_t st, OpChoice* query);
+int mtbc_i_head_expand(const mtbc_head_fuse_args* a, hipStream_t st, OpChoice* query);
+int mtbc_i_gap_fwd(const mtbc_gap_args* a, hipStream_t st, OpChoice* query);
+int mtbc_i_gap_bwd(const mtbc_gap_args* a, hipStream_t st, OpChoice* query);
+int mtbc_i_linear_fwd(const mtbc_linear_args* a, hipStream_t st, OpChoice* query);
+int mtbc_i_linear_bwd(const mtbc_linear_args* a, hipStream_t st, OpChoice* query);
+// internal (C++) helpers implemented in reduce.hip; query != NULL: append the launch(es) and return
 int mtbc_i_splitk_reduce(const float* partial, float* out, int nsplit, size_t elems, int accumulate, hipStream_t st);
 // rows of elems1 + elems2 floats per split: [0, elems1) summed into out, the rest into out2
-int mtbc_i_splitk_reduce2(const float* partial, float* out, float* out2, int nsplit, size_t elems1, size_t elems2, int accumulate, hipStream_t st);
+int mtbc_i_splitk_reduce2(const float* partial, float* out, float* out2, int nsplit, size_t elems1, size_t elems2, int accumulate, hipStream_t st, OpChoice* query = nullptr);
 // Which launches a ConvTranspose call makes: the kernel instances (family + template arguments) and the plan facts that select code paths
 // inside a kernel without being template arguments.  Every dispatcher of convt2.hip and the ConvT entry points of pool_up.hip fill ONE
 // ConvTChoice first; the launch code then reads the kernels from it, and mtbc_convT_kernel_name() -- the same dispatchers called with
@@ -223,4 +254,4 @@ bool mtbc_i_convT2_bwd_fused_ok(const mtbc_convT_args* wg, const mtbc_convT_args
 int mtbc_i_convT2_bwd_fused(const mtbc_convT_args* wg, const mtbc_convT_args* dg, float* partial, float* dbias_part, int steps_per_split, int nsplit, hipStream_t st, ConvTChoice* query);
 // pool_up.hip: a WGRAD op with the DGRAD op of the same up-convolution right behind it; *fused = false: nothing was issued, run them one by one
 int mtbc_i_convT_bwd_pair(const mtbc_convT_args* wg, const mtbc_convT_args* dg, void* stream, bool* fused, ConvTChoice* query = nullptr);
-int mtbc_i_channel_sums(const float* x, float* planes_ws, float* out, int N, int C, int HW, int accumulate, hipStream_t st);
+int mtbc_i_channel_sums(const float* x, float* planes_ws, float* out, int N, int C, int HW, int accumulate, hipStream_t st, OpChoice* query = nullptr);

@@ -513,47 +513,56 @@ int dice_bwd_launch(const DiceP& p, hipStream_t st) {
 }
 }  // namespace
 
-extern "C" {
-
-int mtbc_gap_fwd(const mtbc_gap_args* a, void* stream) {
+// ---------------------------------------------------------------- GAP / Linear: the dispatchers
+// query != NULL: validate, append the launches to *query and return without touching the stream or the device (mtbc_op_kernel_name).
+int mtbc_i_gap_fwd(const mtbc_gap_args* a, hipStream_t st, OpChoice* query) {
     if (!a || a->N <= 0 || a->C <= 0 || a->H <= 0 || a->W <= 0) return MTBC_E_BADSHAPE;
     if (!a->x || !a->y) return MTBC_E_BADARG;
+    if (query) { query->add("gap_fwd_kernel"); return MTBC_OK; }
     const int planes = a->N * a->C;
-    hipLaunchKernelGGL(gap_fwd_kernel, dim3(cdiv(planes, 4)), dim3(256), 0, (hipStream_t)stream, a->x, a->y, planes, a->H * a->W);
+    hipLaunchKernelGGL(gap_fwd_kernel, dim3(cdiv(planes, 4)), dim3(256), 0, st, a->x, a->y, planes, a->H * a->W);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
-int mtbc_gap_bwd(const mtbc_gap_args* a, void* stream) {
+int mtbc_i_gap_bwd(const mtbc_gap_args* a, hipStream_t st, OpChoice* query) {
     if (!a || a->N <= 0 || a->C <= 0 || a->H <= 0 || a->W <= 0) return MTBC_E_BADSHAPE;
     if (!a->dy || !a->dx) return MTBC_E_BADARG;
+    if (query) { query->add("gap_bwd_kernel"); return MTBC_OK; }
     const size_t total = (size_t)a->N * a->C * a->H * a->W;
-    hipLaunchKernelGGL(gap_bwd_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, a->dy, a->dx, total, a->H * a->W);
+    hipLaunchKernelGGL(gap_bwd_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, a->dy, a->dx, total, a->H * a->W);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
-
-int mtbc_linear_fwd(const mtbc_linear_args* a, void* stream) {
+int mtbc_i_linear_fwd(const mtbc_linear_args* a, hipStream_t st, OpChoice* query) {
     if (!a || a->N <= 0 || a->In <= 0 || a->Out <= 0) return MTBC_E_BADSHAPE;
     if (!a->x || !a->w || !a->y) return MTBC_E_BADARG;
-    hipLaunchKernelGGL(linear_fwd_kernel, dim3(cdiv(a->N * a->Out, 4)), dim3(256), 0, (hipStream_t)stream, a->x, a->w, a->bias,
-                       a->y, a->N, a->In, a->Out, a->relu);
+    if (query) { query->add("linear_fwd_kernel"); return MTBC_OK; }
+    hipLaunchKernelGGL(linear_fwd_kernel, dim3(cdiv(a->N * a->Out, 4)), dim3(256), 0, st, a->x, a->w, a->bias, a->y, a->N, a->In, a->Out, a->relu);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
-int mtbc_linear_bwd(const mtbc_linear_args* a, void* stream) {
+int mtbc_i_linear_bwd(const mtbc_linear_args* a, hipStream_t st, OpChoice* query) {
     if (!a || a->N <= 0 || a->In <= 0 || a->Out <= 0) return MTBC_E_BADSHAPE;
     if (!a->x || !a->w || !a->dy || !a->dw) return MTBC_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
     const float* g = a->dy;
-    if (a->relu) {
+    const bool mask = a->relu != 0, dx = a->dx != nullptr;        // the launches: both paths read these
+    if (mask) {
         if (!a->y) return MTBC_E_BADARG;
         if (!a->workspace || a->workspace_bytes < (size_t)a->N * a->Out * sizeof(float)) return MTBC_E_WORKSPACE;
+    }
+    if (query) {      // [Out>=8] / [N>=8]: the eight-wide unrolled loops of linear_dx_kernel / linear_dw_kernel run
+        if (mask) query->add("linear_mask_kernel");
+        if (dx) query->add(a->Out >= 8 ? "linear_dx_kernel [Out>=8]" : "linear_dx_kernel");
+        query->add(a->N >= 8 ? "linear_dw_kernel [N>=8]" : "linear_dw_kernel");
+        return MTBC_OK;
+    }
+    if (mask) {
         float* gm = reinterpret_cast<float*>(a->workspace);
         hipLaunchKernelGGL(linear_mask_kernel, dim3(cdiv(a->N * a->Out, 256)), dim3(256), 0, st, a->dy, a->y, gm, a->N * a->Out);
         MTBC_CHECK_LAUNCH();
         g = gm;
     }
-    if (a->dx) {
+    if (dx) {
         hipLaunchKernelGGL(linear_dx_kernel, dim3(cdiv(a->N * a->In, 256)), dim3(256), 0, st, g, a->w, a->dx, a->N, a->In, a->Out);
         MTBC_CHECK_LAUNCH();
     }
@@ -562,6 +571,13 @@ int mtbc_linear_bwd(const mtbc_linear_args* a, void* stream) {
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
+
+extern "C" {
+
+int mtbc_gap_fwd(const mtbc_gap_args* a, void* stream) { return mtbc_i_gap_fwd(a, (hipStream_t)stream, nullptr); }
+int mtbc_gap_bwd(const mtbc_gap_args* a, void* stream) { return mtbc_i_gap_bwd(a, (hipStream_t)stream, nullptr); }
+int mtbc_linear_fwd(const mtbc_linear_args* a, void* stream) { return mtbc_i_linear_fwd(a, (hipStream_t)stream, nullptr); }
+int mtbc_linear_bwd(const mtbc_linear_args* a, void* stream) { return mtbc_i_linear_bwd(a, (hipStream_t)stream, nullptr); }
 
 static int fill_dice(const mtbc_dice_args* a, DiceP* p) {
     if (!a || a->n_heads < 1 || a->n_heads > 4 || a->N <= 0 || a->C <= 0 || a->H <= 0 || a->W <= 0) return MTBC_E_BADSHAPE;

@@ -193,6 +193,16 @@ struct MpP {
     const float* x; long long xbs; float* y; long long ybs;
     const float* dy; long long dybs; float* dx; long long dxbs; int acc;
 };
+// The maximum of a window: its first maximal element in (0,0),(0,1),(1,0),(1,1) order, a NaN counting as maximal -- ATen's max_pool2d, and
+// the scan of maxpool_bwd_kernel below, of the channel-blocked kernels (c8_ops.hip) and of the streaming InstanceNorm pass (norm_coop.hip):
+// the forward value IS the element the gradient is routed to, for every bit pattern (fmaxf drops a NaN and may answer +0 for a -0 window).
+__device__ __forceinline__ float first_max4(float v00, float v01, float v10, float v11) {
+    float m = v00;
+    if (v01 > m || v01 != v01) m = v01;
+    if (v10 > m || v10 != v10) m = v10;
+    if (v11 > m || v11 != v11) m = v11;
+    return m;
+}
 // one thread = 2 adjacent outputs (one float4 per input row)
 __global__ void maxpool_fwd_kernel(const MpP p) {
     const int oW = p.W >> 1, oH = p.H >> 1, w2 = oW >> 1;
@@ -205,8 +215,8 @@ __global__ void maxpool_fwd_kernel(const MpP p) {
     const float* r0 = p.x + (size_t)n * p.xbs + ((size_t)c * p.H + 2 * oy) * p.W + 4 * q;
     const float4 a = *reinterpret_cast<const float4*>(r0), b = *reinterpret_cast<const float4*>(r0 + p.W);
     float2 o;
-    o.x = fmaxf(fmaxf(a.x, a.y), fmaxf(b.x, b.y));
-    o.y = fmaxf(fmaxf(a.z, a.w), fmaxf(b.z, b.w));
+    o.x = first_max4(a.x, a.y, b.x, b.y);
+    o.y = first_max4(a.z, a.w, b.z, b.w);
     *reinterpret_cast<float2*>(p.y + (size_t)n * p.ybs + ((size_t)c * oH + oy) * oW + 2 * q) = o;
 }
 __global__ void maxpool_fwd_scalar_kernel(const MpP p) {
@@ -218,7 +228,7 @@ __global__ void maxpool_fwd_scalar_kernel(const MpP p) {
     const int oy = t % oH; t /= oH;
     const int c = t % p.C, n = t / p.C;
     const float* r0 = p.x + (size_t)n * p.xbs + ((size_t)c * p.H + 2 * oy) * p.W + 2 * ox;
-    p.y[(size_t)n * p.ybs + ((size_t)c * oH + oy) * oW + ox] = fmaxf(fmaxf(r0[0], r0[1]), fmaxf(r0[p.W], r0[p.W + 1]));
+    p.y[(size_t)n * p.ybs + ((size_t)c * oH + oy) * oW + ox] = first_max4(r0[0], r0[1], r0[p.W], r0[p.W + 1]);
 }
 // bwd: one thread = one output window; grad goes to the first maximal element (ATen order)
 __global__ void maxpool_bwd_kernel(const MpP p) {
@@ -489,6 +499,23 @@ int mtbc_convT_kernel_name(const mtbc_convT_args* a, int32_t op, const mtbc_conv
 }
 
 // ---------------------------------------------------------------- MaxPool
+int mtbc_maxpool2_fwd(const mtbc_maxpool_args* a, void* stream) { return mtbc_i_maxpool2_fwd(a, (hipStream_t)stream, nullptr); }
+int mtbc_maxpool2_bwd(const mtbc_maxpool_args* a, void* stream) { return mtbc_i_maxpool2_bwd(a, (hipStream_t)stream, nullptr); }
+
+// ---------------------------------------------------------------- conv1x1
+int mtbc_conv1x1_fwd(const mtbc_conv1x1_args* a, void* stream) { return mtbc_i_conv1x1_fwd(a, (hipStream_t)stream, nullptr); }
+int mtbc_conv1x1_dgrad(const mtbc_conv1x1_args* a, void* stream) { return mtbc_i_conv1x1_dgrad(a, (hipStream_t)stream, nullptr); }
+size_t mtbc_conv1x1_wgrad_workspace(const mtbc_conv1x1_args* a) {
+    if (!a) return 0;
+    if (a->x_layout == MTBC_LAYOUT_C8) return mtbc_i_conv1x1_c8_wgrad_workspace(a);
+    return ((size_t)a->N * a->Cout * a->Cin + (size_t)a->N * a->Cout) * sizeof(float);
+}
+int mtbc_conv1x1_wgrad(const mtbc_conv1x1_args* a, void* stream) { return mtbc_i_conv1x1_wgrad(a, (hipStream_t)stream, nullptr); }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- MaxPool / conv1x1: the dispatchers
+// query != NULL: validate, append the launches to *query and return without touching the stream or the device (mtbc_op_kernel_name).
 static int fill_mp(const mtbc_maxpool_args* a, MpP* p) {
     if (!a || a->N <= 0 || a->C <= 0 || a->H < 2 || a->W < 2 || (a->H & 1) || (a->W & 1)) return MTBC_E_BADSHAPE;
     p->N = a->N; p->C = a->C; p->H = a->H; p->W = a->W; p->x = a->x; p->xbs = a->x_batch_stride; p->y = a->y;
@@ -496,13 +523,14 @@ static int fill_mp(const mtbc_maxpool_args* a, MpP* p) {
     p->acc = a->accumulate_dx;
     return MTBC_OK;
 }
-int mtbc_maxpool2_fwd(const mtbc_maxpool_args* a, void* stream) {
+int mtbc_i_maxpool2_fwd(const mtbc_maxpool_args* a, hipStream_t st, OpChoice* query) {
     MpP p; int rc = fill_mp(a, &p); if (rc) return rc;
     if (!p.x || !p.y) return MTBC_E_BADARG;
-    if (a->layout == MTBC_LAYOUT_C8) return mtbc_i_maxpool_c8_fwd(a, (hipStream_t)stream);
+    if (a->layout == MTBC_LAYOUT_C8) return mtbc_i_maxpool_c8_fwd(a, st, query);
     if (a->layout != MTBC_LAYOUT_PLANAR) return MTBC_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    if ((a->W & 3) == 0 && al16(p.x) && (p.xbs & 3) == 0 && (reinterpret_cast<uintptr_t>(p.y) & 7) == 0 && (p.ybs & 1) == 0) {
+    const bool vec = (a->W & 3) == 0 && al16(p.x) && (p.xbs & 3) == 0 && (reinterpret_cast<uintptr_t>(p.y) & 7) == 0 && (p.ybs & 1) == 0;
+    if (query) { query->add(vec ? "maxpool_fwd_kernel" : "maxpool_fwd_scalar_kernel"); return MTBC_OK; }
+    if (vec) {
         const size_t total = (size_t)a->N * a->C * (a->H / 2) * (a->W / 4);
         hipLaunchKernelGGL(maxpool_fwd_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, p);
     } else {
@@ -512,20 +540,20 @@ int mtbc_maxpool2_fwd(const mtbc_maxpool_args* a, void* stream) {
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
-int mtbc_maxpool2_bwd(const mtbc_maxpool_args* a, void* stream) {
+int mtbc_i_maxpool2_bwd(const mtbc_maxpool_args* a, hipStream_t st, OpChoice* query) {
     MpP p; int rc = fill_mp(a, &p); if (rc) return rc;
     if (!p.x || !p.dy || !p.dx) return MTBC_E_BADARG;
-    if (a->layout == MTBC_LAYOUT_C8) return mtbc_i_maxpool_c8_bwd(a, (hipStream_t)stream);
+    if (a->layout == MTBC_LAYOUT_C8) return mtbc_i_maxpool_c8_bwd(a, st, query);
     if (a->layout != MTBC_LAYOUT_PLANAR) return MTBC_E_BADARG;
     if ((reinterpret_cast<uintptr_t>(p.x) & 7) || (reinterpret_cast<uintptr_t>(p.dx) & 7) || (p.xbs & 1) || (p.dxbs & 1))
         return MTBC_E_UNSUPPORTED;
+    if (query) { query->add("maxpool_bwd_kernel"); return MTBC_OK; }
     const size_t total = (size_t)a->N * a->C * (a->H / 2) * (a->W / 2);
-    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, p);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
 
-// ---------------------------------------------------------------- conv1x1
 static int fill_c1(const mtbc_conv1x1_args* a, C1P* p) {
     if (!a || a->N <= 0 || a->H <= 0 || a->W <= 0 || a->Cin <= 0 || a->Cout <= 0) return MTBC_E_BADSHAPE;
     if ((a->H * a->W) & 3) return MTBC_E_UNSUPPORTED;
@@ -534,52 +562,49 @@ static int fill_c1(const mtbc_conv1x1_args* a, C1P* p) {
     p->acc_dx = a->accumulate_dx; p->partial = nullptr;
     return MTBC_OK;
 }
-int mtbc_conv1x1_fwd(const mtbc_conv1x1_args* a, void* stream) {
+int mtbc_i_conv1x1_fwd(const mtbc_conv1x1_args* a, hipStream_t st, OpChoice* query) {
     C1P p; int rc = fill_c1(a, &p); if (rc) return rc;
     if (!p.x || !p.w || !p.y) return MTBC_E_BADARG;
-    if (a->x_layout == MTBC_LAYOUT_C8) return mtbc_i_conv1x1_c8_fwd(a, (hipStream_t)stream);
+    if (a->x_layout == MTBC_LAYOUT_C8) return mtbc_i_conv1x1_c8_fwd(a, st, query);
     if (a->x_layout != MTBC_LAYOUT_PLANAR) return MTBC_E_BADARG;
     if (!al16(p.x) || !al16(p.y) || (p.xbs & 3)) return MTBC_E_UNSUPPORTED;
+    if (query) { query->add("conv1x1_fwd_kernel"); return MTBC_OK; }
     dim3 grid(cdiv(p.HW / 4, 256), cdiv(a->Cout, 8), a->N);
-    hipLaunchKernelGGL(conv1x1_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(conv1x1_fwd_kernel, grid, dim3(256), 0, st, p);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
-int mtbc_conv1x1_dgrad(const mtbc_conv1x1_args* a, void* stream) {
+int mtbc_i_conv1x1_dgrad(const mtbc_conv1x1_args* a, hipStream_t st, OpChoice* query) {
     C1P p; int rc = fill_c1(a, &p); if (rc) return rc;
     if (!p.dy || !p.w || !p.dx) return MTBC_E_BADARG;
     if (!al16(p.dy) || !al16(p.dx) || (p.dxbs & 3)) return MTBC_E_UNSUPPORTED;
+    if (query) { query->add("conv1x1_dgrad_kernel"); return MTBC_OK; }
     dim3 grid(cdiv(p.HW / 4, 256), 1, a->N);
-    hipLaunchKernelGGL(conv1x1_dgrad_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(conv1x1_dgrad_kernel, grid, dim3(256), 0, st, p);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
-size_t mtbc_conv1x1_wgrad_workspace(const mtbc_conv1x1_args* a) {
-    if (!a) return 0;
-    if (a->x_layout == MTBC_LAYOUT_C8) return mtbc_i_conv1x1_c8_wgrad_workspace(a);
-    return ((size_t)a->N * a->Cout * a->Cin + (size_t)a->N * a->Cout) * sizeof(float);
-}
-int mtbc_conv1x1_wgrad(const mtbc_conv1x1_args* a, void* stream) {
+int mtbc_i_conv1x1_wgrad(const mtbc_conv1x1_args* a, hipStream_t st, OpChoice* query) {
     C1P p; int rc = fill_c1(a, &p); if (rc) return rc;
     if (!p.x || !p.dy || !a->dw) return MTBC_E_BADARG;
-    if (a->x_layout == MTBC_LAYOUT_C8) return mtbc_i_conv1x1_c8_wgrad(a, (hipStream_t)stream);
+    if (a->x_layout == MTBC_LAYOUT_C8) return mtbc_i_conv1x1_c8_wgrad(a, st, query);
     if (a->x_layout != MTBC_LAYOUT_PLANAR) return MTBC_E_BADARG;
     if (!al16(p.x) || !al16(p.dy) || (p.xbs & 3)) return MTBC_E_UNSUPPORTED;
     if (!a->workspace || a->workspace_bytes < mtbc_conv1x1_wgrad_workspace(a)) return MTBC_E_WORKSPACE;
     p.partial = reinterpret_cast<float*>(a->workspace);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(conv1x1_wgrad_kernel, dim3(a->Cin, a->N), dim3(256), 0, st, p);
-    MTBC_CHECK_LAUNCH();
+    if (query) query->add("conv1x1_wgrad_kernel");
+    else {
+        hipLaunchKernelGGL(conv1x1_wgrad_kernel, dim3(a->Cin, a->N), dim3(256), 0, st, p);
+        MTBC_CHECK_LAUNCH();
+    }
     const size_t wel = (size_t)a->Cout * a->Cin;
-    rc = mtbc_i_splitk_reduce(p.partial, a->dw, a->N, wel, a->accumulate_dw, st); if (rc) return rc;
+    rc = mtbc_i_splitk_reduce2(p.partial, a->dw, nullptr, a->N, wel, 0, a->accumulate_dw, st, query); if (rc) return rc;
     if (a->dbias) {
-        rc = mtbc_i_channel_sums(p.dy, p.partial + (size_t)a->N * wel, a->dbias, a->N, a->Cout, p.HW, a->accumulate_dw, st);
+        rc = mtbc_i_channel_sums(p.dy, p.partial + (size_t)a->N * wel, a->dbias, a->N, a->Cout, p.HW, a->accumulate_dw, st, query);
         if (rc) return rc;
     }
     return MTBC_OK;
 }
-
-}  // extern "C"
 
 // The program runner's pair: an OP_CONVT_WGRAD with the OP_CONVT_DGRAD of the same up-convolution right behind it.  Where convt2.hip's
 // fused kernel takes the pair, dy is read once: one launch writes the split partials (the plan and the workspace layout of
@@ -657,21 +682,25 @@ __global__ void head_expand_small_kernel(const mtbc_head_fuse_args a) {
 }
 }  // namespace
 
-extern "C" int mtbc_convT_head_combine(const mtbc_head_fuse_args* a, void* stream) {
+int mtbc_i_head_combine(const mtbc_head_fuse_args* a, hipStream_t st, OpChoice* query) {
     if (!a || !a->wT || !a->w1 || !a->Wc || !a->bc) return MTBC_E_BADARG;
     if (a->Cin <= 0 || a->Cmid <= 0 || a->R <= 0 || a->k <= 0) return MTBC_E_BADSHAPE;
+    if (query) { query->add("head_combine_kernel"); return MTBC_OK; }
     const int total = a->Cin * a->R * a->k * a->k;
-    hipLaunchKernelGGL(head_combine_kernel, dim3(cdiv(total > a->R ? total : a->R, 128)), dim3(128), 0, (hipStream_t)stream, *a);
+    hipLaunchKernelGGL(head_combine_kernel, dim3(cdiv(total > a->R ? total : a->R, 128)), dim3(128), 0, st, *a);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
-extern "C" int mtbc_convT_head_expand(const mtbc_head_fuse_args* a, void* stream) {
+int mtbc_i_head_expand(const mtbc_head_fuse_args* a, hipStream_t st, OpChoice* query) {
     if (!a || !a->wT || !a->w1 || !a->G || !a->gb || !a->dwT || !a->dw1) return MTBC_E_BADARG;
     if (a->Cin <= 0 || a->Cmid <= 0 || a->R <= 0 || a->k <= 0) return MTBC_E_BADSHAPE;
+    if (query) { query->add("head_expand_dwT_kernel"); query->add("head_expand_small_kernel"); return MTBC_OK; }
     const int total = a->Cin * a->Cmid * a->k * a->k;
-    hipLaunchKernelGGL(head_expand_dwT_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, *a);
+    hipLaunchKernelGGL(head_expand_dwT_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, *a);
     MTBC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(head_expand_small_kernel, dim3(a->R * a->Cmid), dim3(256), 0, (hipStream_t)stream, *a);
+    hipLaunchKernelGGL(head_expand_small_kernel, dim3(a->R * a->Cmid), dim3(256), 0, st, *a);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
+extern "C" int mtbc_convT_head_combine(const mtbc_head_fuse_args* a, void* stream) { return mtbc_i_head_combine(a, (hipStream_t)stream, nullptr); }
+extern "C" int mtbc_convT_head_expand(const mtbc_head_fuse_args* a, void* stream) { return mtbc_i_head_expand(a, (hipStream_t)stream, nullptr); }

@@ -2,6 +2,7 @@
 // per-op work inside a training step (the reference drives the same sequence op-by-op from Python autograd,
 // training_multitask.py:87-103).  Also hosts version / error-string entry points.
 #include "common.h"
+#include <cstring>
 
 extern "C" {
 
@@ -32,6 +33,30 @@ int mtbc_event_create(void** event) {
 int mtbc_event_destroy(void* event) {
     if (!event) return MTBC_E_BADARG;
     return hipEventDestroy((hipEvent_t)event) == hipSuccess ? MTBC_OK : MTBC_E_LAUNCH;
+}
+
+int mtbc_op_kernel_name(const mtbc_op* op, char* buf, int32_t len) {
+    if (!op) return MTBC_E_BADARG;
+    OpChoice ch{};
+    int rc;
+    switch (op->kind) {      // the dispatchers of the calls themselves, stopped in front of their launches
+        case MTBC_OP_POOL_FWD: rc = mtbc_i_maxpool2_fwd(&op->u.pool, nullptr, &ch); break;
+        case MTBC_OP_POOL_BWD: rc = mtbc_i_maxpool2_bwd(&op->u.pool, nullptr, &ch); break;
+        case MTBC_OP_CONV1_FWD: rc = mtbc_i_conv1x1_fwd(&op->u.conv1, nullptr, &ch); break;
+        case MTBC_OP_CONV1_DGRAD: rc = mtbc_i_conv1x1_dgrad(&op->u.conv1, nullptr, &ch); break;
+        case MTBC_OP_CONV1_WGRAD: rc = mtbc_i_conv1x1_wgrad(&op->u.conv1, nullptr, &ch); break;
+        case MTBC_OP_GAP_FWD: rc = mtbc_i_gap_fwd(&op->u.gap, nullptr, &ch); break;
+        case MTBC_OP_GAP_BWD: rc = mtbc_i_gap_bwd(&op->u.gap, nullptr, &ch); break;
+        case MTBC_OP_LINEAR_FWD: rc = mtbc_i_linear_fwd(&op->u.linear, nullptr, &ch); break;
+        case MTBC_OP_LINEAR_BWD: rc = mtbc_i_linear_bwd(&op->u.linear, nullptr, &ch); break;
+        case MTBC_OP_HEAD_COMBINE: rc = mtbc_i_head_combine(&op->u.head, nullptr, &ch); break;
+        case MTBC_OP_HEAD_EXPAND: rc = mtbc_i_head_expand(&op->u.head, nullptr, &ch); break;
+        default: return MTBC_E_BADARG;
+    }
+    if (rc) return rc;
+    if (!buf || len <= ch.len) return MTBC_E_BADARG;
+    memcpy(buf, ch.s, (size_t)ch.len + 1);
+    return MTBC_OK;
 }
 
 int mtbc_program_run(const mtbc_op* ops, int32_t first, int32_t count, void* stream, int32_t* failed_index) {

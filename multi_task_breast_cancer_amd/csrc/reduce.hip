@@ -66,10 +66,12 @@ __global__ void sum_over_n_k(const float* __restrict__ planes, float* __restrict
 }
 }  // namespace
 
-int mtbc_i_splitk_reduce2(const float* partial, float* out, float* out2, int nsplit, size_t elems1, size_t elems2, int accumulate, hipStream_t st) {
+int mtbc_i_splitk_reduce2(const float* partial, float* out, float* out2, int nsplit, size_t elems1, size_t elems2, int accumulate, hipStream_t st, OpChoice* query) {
     const size_t elems = elems1 + elems2;
-    if (nsplit >= 256 && elems <= 16384) hipLaunchKernelGGL((splitk_reduce_k<64, 16>), dim3((unsigned)cdiv64(elems, 16)), dim3(1024), 0, st, partial, out, nsplit, elems, accumulate, out2, elems1);
-    else if (nsplit > 32) hipLaunchKernelGGL(splitk_reduce_k<16>, dim3((unsigned)cdiv64(elems, 64)), dim3(1024), 0, st, partial, out, nsplit, elems, accumulate, out2, elems1);
+    const int inst = (nsplit >= 256 && elems <= 16384) ? 2 : nsplit > 32 ? 1 : 0;      // the instance: launch and query read this
+    if (query) { query->add(inst == 2 ? "splitk_reduce<64, 16>" : inst == 1 ? "splitk_reduce<16>" : "splitk_reduce<4>"); return MTBC_OK; }
+    if (inst == 2) hipLaunchKernelGGL((splitk_reduce_k<64, 16>), dim3((unsigned)cdiv64(elems, 16)), dim3(1024), 0, st, partial, out, nsplit, elems, accumulate, out2, elems1);
+    else if (inst == 1) hipLaunchKernelGGL(splitk_reduce_k<16>, dim3((unsigned)cdiv64(elems, 64)), dim3(1024), 0, st, partial, out, nsplit, elems, accumulate, out2, elems1);
     else hipLaunchKernelGGL(splitk_reduce_k<4>, dim3((unsigned)cdiv64(elems, 64)), dim3(256), 0, st, partial, out, nsplit, elems, accumulate, out2, elems1);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
@@ -78,8 +80,10 @@ int mtbc_i_splitk_reduce(const float* partial, float* out, int nsplit, size_t el
     return mtbc_i_splitk_reduce2(partial, out, nullptr, nsplit, elems, 0, accumulate, st);
 }
 // out[c] (+)= sum over n and the HW plane of x[n][c][:]; planes_ws holds N*C floats
-int mtbc_i_channel_sums(const float* x, float* planes_ws, float* out, int N, int C, int HW, int accumulate, hipStream_t st) {
-    hipLaunchKernelGGL(plane_sum_k, dim3(N * C), dim3(HW >= 4096 ? 256 : 64), 0, st, x, planes_ws, HW);
+int mtbc_i_channel_sums(const float* x, float* planes_ws, float* out, int N, int C, int HW, int accumulate, hipStream_t st, OpChoice* query) {
+    const int threads = HW >= 4096 ? 256 : 64;
+    if (query) { query->add("plane_sum_k [threads=%d]", threads); query->add("sum_over_n_k"); return MTBC_OK; }
+    hipLaunchKernelGGL(plane_sum_k, dim3(N * C), dim3(threads), 0, st, x, planes_ws, HW);
     MTBC_CHECK_LAUNCH();
     hipLaunchKernelGGL(sum_over_n_k, dim3(cdiv(C, 128)), dim3(128), 0, st, planes_ws, out, N, C, accumulate);
     MTBC_CHECK_LAUNCH();

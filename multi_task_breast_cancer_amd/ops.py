@@ -1100,3 +1100,140 @@ def convT_head_fwd_bwd(x, wT, bT, w1, b1, k, dout):
     a.dwT, a.dbT, a.dw1, a.db1 = dwT.data_ptr(), dbT.data_ptr(), dw1.data_ptr(), db1.data_ptr()
     L.check(lib.mtbc_convT_head_expand(C.byref(a), _s()), "head_expand")
     return y, dx, dwT, dbT, dw1, db1
+
+
+# ------------------------------------------------------------------ the small ops as step-program ops: plan query, argument structs, launch
+SMALL_OPS = (L.OP_POOL_FWD, L.OP_POOL_BWD, L.OP_CONV1_FWD, L.OP_CONV1_DGRAD, L.OP_CONV1_WGRAD, L.OP_GAP_FWD, L.OP_GAP_BWD,
+             L.OP_LINEAR_FWD, L.OP_LINEAR_BWD, L.OP_HEAD_COMBINE, L.OP_HEAD_EXPAND)
+
+
+def op_kernel_name(op: "L.Op") -> str:
+    """Every launch the call behind a max-pool, 1x1 convolution, GAP, Linear or fused-head op (SMALL_OPS) would make, joined with " + ":
+    mtbc_op_kernel_name, host-only (no launch, no device).  Raises what the call would."""
+    buf = C.create_string_buffer(512)
+    L.check(L.load().mtbc_op_kernel_name(C.byref(op), buf, len(buf)), "op_kernel_name")
+    return buf.value.decode()
+
+
+_SMALL_DUMMY = {n: (i + 1) << 20 for i, n in enumerate(("x", "w", "bias", "y", "dy", "dx", "dw", "dbias", "workspace", "argmax", "wT", "bT", "w1", "b1",
+                                                        "Wc", "bc", "G", "gb", "dwT", "dbT", "dw1", "db1"))}
+
+
+def _small_ptr(ptrs: Optional[dict]):
+    return (lambda name: _SMALL_DUMMY[name]) if ptrs is None else (lambda name: ptrs[name].data_ptr())
+
+
+def _small_op(kind: int) -> "L.Op":
+    op = L.Op()
+    op.kind = kind
+    return op
+
+
+def maxpool_case_args(kind: int, N: int, Cc: int, H: int, W: int, ptrs: Optional[dict] = None, compute: int = 0, argmax: bool = False,
+                      acc_dx: bool = False, strides: Optional[dict] = None) -> "L.Op":
+    """The MTBC_OP_POOL_FWD / _BWD op of ONE 2x2 max-pool call as engine.StepPlan.maxpool fills it.  ptrs: field name (x, y, dy, dx, argmax) ->
+    tensor; None = distinct 16-byte aligned dummies that nothing may dereference (for op_kernel_name).  compute: 0 = fp32 planar x / y, 1 / 2 =
+    16-bit channel-blocked x / y of that type (layout C8; dy / dx stay fp32 planes); argmax: the forward also writes the codes; acc_dx: the
+    backward adds into dx.  strides: field name (x, y, dy, dx) -> batch stride in elements of that tensor where it is a channel-range view of a
+    wider buffer; dense otherwise."""
+    strides, ptr = strides or {}, _small_ptr(ptrs)
+    op = _small_op(kind)
+    a = op.u.pool
+    a.N, a.C, a.H, a.W = N, Cc, H, W
+    if compute:
+        a.layout, a.type16 = L.LAYOUT_C8, compute
+    a.x, a.x_batch_stride = ptr("x"), strides.get("x", Cc * H * W)
+    a.y, a.y_batch_stride = ptr("y"), strides.get("y", Cc * H * W // 4)      # engine.StepPlan.maxpool's base(): both ops carry x and y
+    if kind == L.OP_POOL_FWD:
+        a.argmax = ptr("argmax") if argmax else None
+    else:
+        a.dy, a.dy_batch_stride = ptr("dy"), strides.get("dy", Cc * H * W // 4)
+        a.dx, a.dx_batch_stride, a.accumulate_dx = ptr("dx"), strides.get("dx", Cc * H * W), int(acc_dx)
+    return op
+
+
+def conv1x1_case_args(kind: int, N: int, Cin: int, Cout: int, H: int, W: int, ptrs: Optional[dict] = None, compute: int = 0, bias: bool = True,
+                      acc_dx: bool = False, acc_dw: bool = False, strides: Optional[dict] = None, workspace: bool = True) -> "L.Op":
+    """The MTBC_OP_CONV1_FWD / _DGRAD / _WGRAD op of ONE 1x1 convolution call as engine.StepPlan.conv1x1 fills it.  ptrs: field name (x, w,
+    bias, y, dy, dx, dw, dbias, workspace) -> tensor, None = dummies.  compute: 0 = fp32 planar x, 1 / 2 = 16-bit channel-blocked x of that
+    type.  bias: forward with a bias / weight gradient with dbias; acc_dx / acc_dw: accumulate.  strides: x, dx -> batch stride of a view
+    (y and dy are always dense).  workspace = False leaves the weight gradient without one."""
+    strides, ptr = strides or {}, _small_ptr(ptrs)
+    op = _small_op(kind)
+    a = op.u.conv1
+    a.N, a.H, a.W, a.Cin, a.Cout = N, H, W, Cin, Cout
+    a.x, a.x_batch_stride, a.w = ptr("x"), strides.get("x", Cin * H * W), ptr("w")
+    if compute:
+        a.x_layout, a.x_type = L.LAYOUT_C8, compute
+    if kind == L.OP_CONV1_FWD:
+        a.bias, a.y = (ptr("bias") if bias else None), ptr("y")
+        return op
+    a.dy = ptr("dy")
+    if kind == L.OP_CONV1_DGRAD:
+        a.dx, a.dx_batch_stride, a.accumulate_dx = ptr("dx"), strides.get("dx", Cin * H * W), int(acc_dx)
+        return op
+    a.dw, a.dbias, a.accumulate_dw = ptr("dw"), (ptr("dbias") if bias else None), int(acc_dw)
+    if workspace:
+        nb = int(L.load().mtbc_conv1x1_wgrad_workspace(C.byref(a)))
+        a.workspace, a.workspace_bytes = ptr("workspace"), (nb if ptrs is None else ptrs["workspace"].numel() * 4)
+    return op
+
+
+def gap_case_args(kind: int, N: int, Cc: int, H: int, W: int, ptrs: Optional[dict] = None) -> "L.Op":
+    """The MTBC_OP_GAP_FWD / _BWD op as engine.StepPlan.gap fills it (x, y / dy, dx; all dense)."""
+    ptr = _small_ptr(ptrs)
+    op = _small_op(kind)
+    a = op.u.gap
+    a.N, a.C, a.H, a.W = N, Cc, H, W
+    a.x, a.y = ptr("x"), ptr("y")           # engine.StepPlan.gap's base(): both ops carry x and y
+    if kind == L.OP_GAP_BWD:
+        a.dy, a.dx = ptr("dy"), ptr("dx")
+    return op
+
+
+def linear_case_args(kind: int, N: int, In: int, Out: int, ptrs: Optional[dict] = None, relu: bool = False, bias: bool = True, dx: bool = True,
+                     acc_dw: bool = False, workspace: bool = True) -> "L.Op":
+    """The MTBC_OP_LINEAR_FWD / _BWD op as engine.StepPlan.linear fills it.  ptrs: x, w, bias, y, dy, dx, dw, dbias, workspace.  bias: the
+    forward's bias (the backward always has dbias, as in the programs); dx = False: no input gradient; workspace: the backward with relu gets
+    its N * Out floats (the engine gives one to the ReLU layers only)."""
+    ptr = _small_ptr(ptrs)
+    op = _small_op(kind)
+    a = op.u.linear
+    a.N, a.In, a.Out, a.relu = N, In, Out, int(relu)
+    a.x, a.w, a.bias, a.y = ptr("x"), ptr("w"), (ptr("bias") if bias else None), ptr("y")
+    if kind == L.OP_LINEAR_BWD:
+        a.dy, a.dx = ptr("dy"), (ptr("dx") if dx else None)
+        a.dw, a.dbias, a.accumulate_dw = ptr("dw"), ptr("dbias"), int(acc_dw)
+        if relu and workspace:
+            a.workspace, a.workspace_bytes = ptr("workspace"), (N * Out * 4 if ptrs is None else ptrs["workspace"].numel() * 4)
+    return op
+
+
+def head_case_args(kind: int, Cin: int, Cmid: int, R: int, k: int, ptrs: Optional[dict] = None, bT: bool = True, b1: bool = True,
+                   dbT: bool = True, db1: bool = True, acc: Sequence[int] = (0, 0, 0, 0)) -> "L.Op":
+    """The MTBC_OP_HEAD_COMBINE / _EXPAND op as engine.StepPlan.convT_head fills it (every pointer in both ops).  ptrs: wT, bT, w1, b1, Wc, bc,
+    G, gb, dwT, dbT, dw1, db1.  bT / b1 = False: the layer has no bias; dbT / db1 = False: that gradient is not asked for; acc = (acc_wT,
+    acc_bT, acc_w1, acc_b1)."""
+    ptr = _small_ptr(ptrs)
+    op = _small_op(kind)
+    a = op.u.head
+    a.Cin, a.Cmid, a.R, a.k = Cin, Cmid, R, k
+    a.wT, a.bT, a.w1, a.b1 = ptr("wT"), (ptr("bT") if bT else None), ptr("w1"), (ptr("b1") if b1 else None)
+    a.Wc, a.bc, a.G, a.gb = ptr("Wc"), ptr("bc"), ptr("G"), ptr("gb")
+    if kind == L.OP_HEAD_EXPAND:
+        a.dwT, a.dbT, a.dw1, a.db1 = ptr("dwT"), (ptr("dbT") if dbT else None), ptr("dw1"), (ptr("db1") if db1 else None)
+        a.acc_wT, a.acc_bT, a.acc_w1, a.acc_b1 = (int(v) for v in acc)
+    return op
+
+
+def small_op_launch(op: "L.Op") -> None:
+    """The entry point behind a small op (SMALL_OPS) on the current stream, for an op of the *_case_args(ptrs=...) helpers above; records
+    (kind, launches) while `launched` is a list."""
+    lib = L.load()
+    fn = {L.OP_POOL_FWD: lib.mtbc_maxpool2_fwd, L.OP_POOL_BWD: lib.mtbc_maxpool2_bwd, L.OP_CONV1_FWD: lib.mtbc_conv1x1_fwd,
+          L.OP_CONV1_DGRAD: lib.mtbc_conv1x1_dgrad, L.OP_CONV1_WGRAD: lib.mtbc_conv1x1_wgrad, L.OP_GAP_FWD: lib.mtbc_gap_fwd,
+          L.OP_GAP_BWD: lib.mtbc_gap_bwd, L.OP_LINEAR_FWD: lib.mtbc_linear_fwd, L.OP_LINEAR_BWD: lib.mtbc_linear_bwd,
+          L.OP_HEAD_COMBINE: lib.mtbc_convT_head_combine, L.OP_HEAD_EXPAND: lib.mtbc_convT_head_expand}[op.kind]
+    if launched is not None:
+        launched.append((op.kind, op_kernel_name(op)))
+    L.check(fn(C.byref(getattr(op.u, L.OP_UNION_FIELD[op.kind])), _s()), f"small op {op.kind}")

@@ -498,3 +498,162 @@ def test_convT_kernel_name_refuses_what_the_call_refuses(lib):
     for op in (F_, D_, W_):
         assert lib.mtbc_convT_kernel_name(None, op, None, buf, 512) == -1                   # NULL args: what the calls return
     assert lib.mtbc_convT_kernel_name(None, W_, C.byref(dg), buf, 512) == -1
+
+
+# (helper, kind, shape, mode) -> what mtbc_op_kernel_name names: one row per dispatch decision of the max-pool, 1x1, GAP, Linear and fused-head
+# calls (pool_up.hip, c8_ops.hip, head_loss.hip) and of the two reducers behind the 1x1 weight gradient (reduce.hip).
+_RS = " + c8_rows_sum_kernel"
+_PS64, _PS256 = " + plane_sum_k [threads=64] + sum_over_n_k", " + plane_sum_k [threads=256] + sum_over_n_k"
+SMALL_OP_SELECTION = [
+    ("maxpool", L.OP_POOL_FWD, (3, 16, 16, 16), {}, "maxpool_fwd_kernel"),
+    ("maxpool", L.OP_POOL_FWD, (1, 5, 6, 10), {}, "maxpool_fwd_scalar_kernel"),                       # W % 4 != 0
+    ("maxpool", L.OP_POOL_FWD, (2, 8, 8, 8), dict(strides=dict(x=8 * 64 + 2)), "maxpool_fwd_scalar_kernel"),      # a batch stride the float4 loads cannot take
+    ("maxpool", L.OP_POOL_FWD, (3, 16, 16, 16), dict(compute=1), "maxpool_c8_fwd_kernel<false>"),
+    ("maxpool", L.OP_POOL_FWD, (3, 16, 16, 16), dict(compute=2, argmax=True), "maxpool_c8_fwd_kernel<true>"),
+    ("maxpool", L.OP_POOL_BWD, (3, 16, 16, 16), {}, "maxpool_bwd_kernel"),
+    ("maxpool", L.OP_POOL_BWD, (3, 16, 16, 16), dict(compute=1, acc_dx=True), "maxpool_c8_bwd_kernel<false>"),
+    ("maxpool", L.OP_POOL_BWD, (3, 16, 16, 16), dict(compute=2), "maxpool_c8_bwd_kernel<true>"),
+    ("conv1x1", L.OP_CONV1_FWD, (2, 16, 10, 32, 36), {}, "conv1x1_fwd_kernel"),
+    ("conv1x1", L.OP_CONV1_FWD, (2, 16, 3, 32, 36), dict(compute=1), "conv1x1_c8_fwd_kernel<false>"),
+    ("conv1x1", L.OP_CONV1_FWD, (2, 16, 3, 32, 36), dict(compute=2, bias=False), "conv1x1_c8_fwd_kernel<true>"),
+    ("conv1x1", L.OP_CONV1_DGRAD, (2, 16, 10, 32, 36), dict(acc_dx=True), "conv1x1_dgrad_kernel"),
+    ("conv1x1", L.OP_CONV1_DGRAD, (2, 16, 1, 32, 36), dict(compute=1), "conv1x1_dgrad_kernel"),        # the input gradient never reads x: no channel-blocked form
+    ("conv1x1", L.OP_CONV1_WGRAD, (3, 16, 3, 8, 8), dict(bias=False), "conv1x1_wgrad_kernel + splitk_reduce<4>"),
+    ("conv1x1", L.OP_CONV1_WGRAD, (32, 16, 3, 8, 8), {}, "conv1x1_wgrad_kernel + splitk_reduce<4>" + _PS64),       # 32 images: still four split lanes
+    ("conv1x1", L.OP_CONV1_WGRAD, (33, 16, 3, 8, 8), {}, "conv1x1_wgrad_kernel + splitk_reduce<16>" + _PS64),
+    ("conv1x1", L.OP_CONV1_WGRAD, (255, 16, 3, 4, 4), {}, "conv1x1_wgrad_kernel + splitk_reduce<16>" + _PS64),
+    ("conv1x1", L.OP_CONV1_WGRAD, (256, 16, 3, 4, 4), {}, "conv1x1_wgrad_kernel + splitk_reduce<64, 16>" + _PS64),
+    ("conv1x1", L.OP_CONV1_WGRAD, (2, 16, 1, 63, 64), {}, "conv1x1_wgrad_kernel + splitk_reduce<4>" + _PS64),       # H * W = 4032 < 4096
+    ("conv1x1", L.OP_CONV1_WGRAD, (2, 16, 1, 64, 64), {}, "conv1x1_wgrad_kernel + splitk_reduce<4>" + _PS256),
+    ("conv1x1", L.OP_CONV1_WGRAD, (2, 16, 3, 64, 64), dict(compute=1), "conv1x1_c8_wgrad_kernel<false> [nblk=1]" + _RS + _RS),
+    ("conv1x1", L.OP_CONV1_WGRAD, (2, 16, 3, 89, 92), dict(compute=2, bias=False), "conv1x1_c8_wgrad_kernel<true> [nblk=1]" + _RS),      # 8188 pixels: one block
+    ("conv1x1", L.OP_CONV1_WGRAD, (2, 16, 3, 90, 92), dict(compute=2, bias=False), "conv1x1_c8_wgrad_kernel<true> [nblk>1]" + _RS),      # 8280 = 2 chunks of 4140
+    ("conv1x1", L.OP_CONV1_WGRAD, (1, 8, 1, 248, 512), dict(compute=1), "conv1x1_c8_wgrad_kernel<false> [nblk>1]" + _RS + _RS),          # 31 blocks
+    ("conv1x1", L.OP_CONV1_WGRAD, (1, 8, 1, 256, 512), dict(compute=1), "conv1x1_c8_wgrad_kernel<false> [nblk=32]" + _RS + _RS),         # the cap, first reached
+    ("conv1x1", L.OP_CONV1_WGRAD, (1, 8, 1, 512, 512), dict(compute=2), "conv1x1_c8_wgrad_kernel<true> [nblk=32]" + _RS + _RS),
+    ("gap", L.OP_GAP_FWD, (3, 5, 5, 7), {}, "gap_fwd_kernel"),
+    ("gap", L.OP_GAP_BWD, (3, 5, 5, 7), {}, "gap_bwd_kernel"),
+    ("linear", L.OP_LINEAR_FWD, (11, 70, 13), dict(relu=True), "linear_fwd_kernel"),
+    ("linear", L.OP_LINEAR_BWD, (11, 70, 13), dict(relu=True), "linear_mask_kernel + linear_dx_kernel [Out>=8] + linear_dw_kernel [N>=8]"),
+    ("linear", L.OP_LINEAR_BWD, (7, 70, 7), {}, "linear_dx_kernel + linear_dw_kernel"),
+    ("linear", L.OP_LINEAR_BWD, (8, 70, 7), {}, "linear_dx_kernel + linear_dw_kernel [N>=8]"),
+    ("linear", L.OP_LINEAR_BWD, (7, 70, 8), {}, "linear_dx_kernel [Out>=8] + linear_dw_kernel"),
+    ("linear", L.OP_LINEAR_BWD, (16, 512, 256), dict(relu=True, dx=False), "linear_mask_kernel + linear_dw_kernel [N>=8]"),
+    ("linear", L.OP_LINEAR_BWD, (3, 256, 3), dict(dx=False), "linear_dw_kernel"),
+    ("head", L.OP_HEAD_COMBINE, (32, 16, 1, 2), {}, "head_combine_kernel"),
+    ("head", L.OP_HEAD_EXPAND, (32, 16, 3, 8), dict(bT=False, db1=False), "head_expand_dwT_kernel + head_expand_small_kernel"),
+]
+
+
+@pytest.mark.parametrize("helper,kind,shape,mode,want", SMALL_OP_SELECTION)
+def test_small_op_kernel_selection(lib, helper, kind, shape, mode, want):
+    """mtbc_op_kernel_name (host only, no device: the dummy tensor pointers are never dereferenced) names every launch of a max-pool, 1x1
+    convolution, GAP, Linear or fused-head call; a change of the selection shows up here, in review."""
+    from multi_task_breast_cancer_amd import ops
+    assert ops.op_kernel_name(getattr(ops, helper + "_case_args")(kind, *shape, **mode)) == want
+
+
+def test_small_op_selection_table_names_every_launch_the_fp64_test_reaches(lib):
+    """One row above per distinct launch -- kernel and bracketed facts -- of tests/test_ops_gpu.py::SMALL_OP_CASES (importable without a GPU)."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    try:
+        import test_ops_gpu as G
+    finally:
+        sys.path.pop(0)
+    from multi_task_breast_cancer_amd import ops
+    named = {part for *_, want in SMALL_OP_SELECTION for part in want.split(" + ")}
+    reached = {part for case in G.SMALL_OP_CASES for op in G._small_case_ops(case) for part in ops.op_kernel_name(op).split(" + ")}
+    assert len(reached) >= 30 and not reached - named, sorted(reached - named)
+    assert not named - reached, sorted(named - reached)          # ... and the fp64 table reaches every launch that has a name here
+
+
+def test_small_op_kernel_name_refuses_what_the_call_refuses(lib):
+    from multi_task_breast_cancer_amd import ops
+    buf = C.create_string_buffer(512)
+    name = lambda op: lib.mtbc_op_kernel_name(C.byref(op), buf, 512)      # noqa: E731
+    P, B = L.OP_POOL_FWD, L.OP_POOL_BWD
+    assert name(ops.maxpool_case_args(P, 2, 8, 6, 7)) == -1                                 # odd W
+    assert name(ops.maxpool_case_args(P, 0, 8, 6, 8)) == -1
+    op = ops.maxpool_case_args(P, 2, 8, 8, 8)
+    op.u.pool.y = None
+    assert name(op) == -2
+    op = ops.maxpool_case_args(P, 2, 8, 8, 8)
+    op.u.pool.layout = 2                                                                    # no such layout
+    assert name(op) == -2
+    assert name(ops.maxpool_case_args(P, 2, 12, 8, 8, compute=1)) == -2                     # channel-blocked: C % 8
+    op = ops.maxpool_case_args(P, 2, 8, 8, 8, compute=1)
+    op.u.pool.type16 = 3
+    assert name(op) == -2
+    assert name(ops.maxpool_case_args(P, 2, 8, 8, 8, compute=1, strides=dict(y=8 * 16 + 4))) == -5      # a channel-blocked view starts on 16 bytes
+    op = ops.maxpool_case_args(P, 2, 8, 8, 8)
+    op.u.pool.x += 4                                                                        # pointer values count: a misaligned x takes the scalar kernel
+    assert name(op) == 0 and buf.value == b"maxpool_fwd_scalar_kernel"
+    op = ops.maxpool_case_args(B, 2, 8, 8, 8)
+    op.u.pool.dx += 4                                                                       # ... the backward has float2 stores only
+    assert name(op) == -5
+    assert name(ops.maxpool_case_args(B, 2, 8, 8, 8, strides=dict(dx=8 * 64 + 1))) == -5
+    op = ops.maxpool_case_args(B, 2, 8, 8, 8)
+    op.u.pool.dy = None
+    assert name(op) == -2
+    F_, D_, W_ = L.OP_CONV1_FWD, L.OP_CONV1_DGRAD, L.OP_CONV1_WGRAD
+    assert name(ops.conv1x1_case_args(F_, 2, 16, 3, 5, 6)) == -5                            # H * W % 4
+    assert name(ops.conv1x1_case_args(F_, 2, 0, 3, 8, 8)) == -1
+    assert name(ops.conv1x1_case_args(F_, 2, 16, 3, 8, 8, strides=dict(x=16 * 64 + 2))) == -5
+    assert name(ops.conv1x1_case_args(F_, 2, 16, 9, 8, 8, compute=1)) == -5                 # channel-blocked x: Cout <= 8
+    assert name(ops.conv1x1_case_args(F_, 2, 12, 3, 8, 8, compute=1)) == -5                 # ... Cin % 8
+    op = ops.conv1x1_case_args(F_, 2, 16, 3, 8, 8)
+    op.u.conv1.x_layout = 2
+    assert name(op) == -2
+    op = ops.conv1x1_case_args(D_, 2, 16, 3, 8, 8)
+    op.u.conv1.dx = None
+    assert name(op) == -2
+    assert name(ops.conv1x1_case_args(D_, 2, 16, 3, 8, 8, strides=dict(dx=16 * 64 + 2))) == -5
+    assert name(ops.conv1x1_case_args(W_, 2, 16, 3, 8, 8, workspace=False)) == -3
+    for mode in ({}, dict(compute=1)):
+        op = ops.conv1x1_case_args(W_, 2, 16, 3, 8, 8, **mode)
+        assert name(op) == 0
+        op.u.conv1.workspace_bytes -= 4                                                     # one float short
+        assert name(op) == -3
+    op = ops.conv1x1_case_args(W_, 2, 16, 3, 8, 8)
+    op.u.conv1.dw = None
+    assert name(op) == -2
+    G_, GB = L.OP_GAP_FWD, L.OP_GAP_BWD
+    assert name(ops.gap_case_args(G_, 2, 8, 0, 8)) == -1
+    op = ops.gap_case_args(GB, 2, 8, 4, 4)
+    op.u.gap.dx = None
+    assert name(op) == -2
+    LF, LB = L.OP_LINEAR_FWD, L.OP_LINEAR_BWD
+    assert name(ops.linear_case_args(LF, 2, 0, 3)) == -1
+    op = ops.linear_case_args(LF, 2, 8, 3)
+    op.u.linear.w = None
+    assert name(op) == -2
+    assert name(ops.linear_case_args(LB, 4, 8, 3, relu=True, workspace=False)) == -3
+    op = ops.linear_case_args(LB, 4, 8, 3, relu=True)
+    op.u.linear.workspace_bytes -= 4
+    assert name(op) == -3
+    op = ops.linear_case_args(LB, 4, 8, 3, relu=True)
+    op.u.linear.y = None                                                                    # the mask needs the stored output
+    assert name(op) == -2
+    assert name(ops.linear_case_args(LB, 4, 8, 3, workspace=False)) == 0                    # no ReLU: no workspace needed
+    HC, HE = L.OP_HEAD_COMBINE, L.OP_HEAD_EXPAND
+    assert name(ops.head_case_args(HC, 8, 0, 1, 2)) == -1
+    op = ops.head_case_args(HC, 8, 4, 1, 2)
+    op.u.head.bc = None
+    assert name(op) == -2
+    op = ops.head_case_args(HE, 8, 4, 1, 2)
+    op.u.head.gb = None
+    assert name(op) == -2
+    assert name(ops.head_case_args(HE, 8, 4, 1, 2, bT=False, b1=False, dbT=False, db1=False)) == 0      # every optional pointer absent
+    for kind in range(0, 40):                                                               # every other op kind: not this query's
+        if kind not in ops.SMALL_OPS:
+            op = ops.gap_case_args(G_, 2, 8, 4, 4)
+            op.kind = kind
+            assert name(op) == -2, kind
+    op = ops.maxpool_case_args(P, 2, 8, 8, 8, compute=2)
+    want = b"maxpool_c8_fwd_kernel<true>"
+    assert lib.mtbc_op_kernel_name(C.byref(op), buf, len(want)) == -2                       # no room for the NUL
+    assert lib.mtbc_op_kernel_name(C.byref(op), buf, len(want) + 1) == 0 and buf.value == want
+    assert lib.mtbc_op_kernel_name(C.byref(op), None, 512) == -2
+    assert lib.mtbc_op_kernel_name(None, buf, 512) == -2

@@ -174,23 +174,6 @@ def test_instnorm_lrelu_fwd_bwd(N, C, H, W, affine, slope):
     assert (dbp.cpu().double() - want).abs().max().item() <= 1e-5 * dz.abs().sum(dim=(0, 2, 3)).max().item() + 1e-6
 
 
-@pytest.mark.parametrize("N,C,H,W", [(2, 3, 8, 8), (1, 5, 6, 10), (2, 24, 64, 64)])
-def test_maxpool_fwd_bwd(N, C, H, W):
-    g = _g(H * W)
-    x = torch.randn(N, C, H, W, generator=g)
-    x[0, 0, :2, :2] = 1.0                               # tie: gradient must go to the first element
-    dy = torch.randn(N, C, H // 2, W // 2, generator=g)
-    xr = x.clone().requires_grad_(True)
-    y = F.max_pool2d(xr, 2, 2)
-    y.backward(dy)
-    xd = x.to(DEV)
-    assert torch.equal(ops.maxpool2_fwd(xd).cpu(), y.detach())
-    assert torch.equal(ops.maxpool2_bwd(xd, dy.to(DEV)).cpu(), xr.grad)
-    pre = torch.randn(N, C, H, W, generator=g)
-    got = ops.maxpool2_bwd(xd, dy.to(DEV), dx=pre.to(DEV).clone(), accumulate=True)
-    _close(got, xr.grad + pre, 0, 1e-6, "pool bwd accumulate")
-
-
 @pytest.mark.parametrize("N,Cin,Cout,H,W,k", [(2, 48, 48, 16, 16, 2), (1, 96, 48, 8, 8, 2), (2, 20, 12, 6, 10, 2),
                                                (2, 64, 64, 8, 8, 4), (1, 128, 128, 4, 4, 8), (3, 32, 32, 5, 3, 4),
                                                (3, 40, 6, 8, 16, 2), (2, 100, 52, 16, 8, 2), (5, 48, 48, 32, 32, 2),
@@ -222,49 +205,6 @@ def test_convT_fwd_dgrad_wgrad(N, Cin, Cout, H, W, k):
             _close(ops.convT_dgrad(xd, wd, dyd, k, compute=mode), xq.grad, 2e-5, 5e-5, f"convT dgrad lp{mode}")
             dwq, _ = ops.convT_wgrad(xd, wd, dyd, k, compute=mode)
             _close(dwq, wq.grad, 1e-4, 2e-5 * max(1.0, wq.grad.abs().max().item()), f"convT wgrad lp{mode}")
-
-
-@pytest.mark.parametrize("N,Cin,Cout,H,W", [(2, 16, 1, 32, 32), (1, 24, 1, 64, 64), (2, 12, 3, 8, 8), (1, 20, 10, 4, 4)])
-def test_conv1x1(N, Cin, Cout, H, W):
-    g = _g(Cin)
-    x = torch.randn(N, Cin, H, W, generator=g)
-    w = torch.randn(Cout, Cin, 1, 1, generator=g) * 0.2
-    b = torch.randn(Cout, generator=g)
-    dy = torch.randn(N, Cout, H, W, generator=g)
-    xr, wr, br = x.clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
-    y = F.conv2d(xr, wr, br)
-    y.backward(dy)
-    xd, wd = x.to(DEV), w.to(DEV)
-    _close(ops.conv1x1_fwd(xd, wd, b.to(DEV)), y.detach(), 1e-5, 1e-5, "1x1 fwd")
-    dx, dw, db = ops.conv1x1_bwd(xd, wd, dy.to(DEV))
-    _close(dx, xr.grad, 1e-5, 1e-5, "1x1 dgrad")
-    _close(dw, wr.grad, 1e-4, 1e-4 * max(1.0, wr.grad.abs().max().item()), "1x1 wgrad")
-    _close(db, br.grad, 1e-4, 1e-4 * max(1.0, br.grad.abs().max().item()), "1x1 dbias")
-
-
-def test_gap_linear_head():
-    g = _g(5)
-    x = torch.randn(4, 512, 16, 16, generator=g)
-    w1, b1 = torch.randn(256, 512, generator=g) * 0.05, torch.randn(256, generator=g) * 0.1
-    w2, b2 = torch.randn(3, 256, generator=g) * 0.05, torch.randn(3, generator=g) * 0.1
-    dlog = torch.randn(4, 3, generator=g)
-    xr = x.clone().requires_grad_(True)
-    ws = [t.clone().requires_grad_(True) for t in (w1, b1, w2, b2)]
-    pooled = F.adaptive_avg_pool2d(xr, 1).flatten(1)
-    h = F.relu(F.linear(pooled, ws[0], ws[1]))
-    out = F.linear(h, ws[2], ws[3])
-    out.backward(dlog)
-    xd = x.to(DEV)
-    pg = ops.gap_fwd(xd)
-    _close(pg, pooled.detach(), 1e-5, 1e-6, "gap")
-    hg = ops.linear_fwd(pg, w1.to(DEV), b1.to(DEV), relu=True)
-    og = ops.linear_fwd(hg, w2.to(DEV), b2.to(DEV), relu=False)
-    _close(og, out.detach(), 1e-5, 1e-5, "linear fwd")
-    dh, dw2, db2 = ops.linear_bwd(hg, w2.to(DEV), og, dlog.to(DEV), relu=False)
-    dp, dw1, db1 = ops.linear_bwd(pg, w1.to(DEV), hg, dh, relu=True)
-    _close(dw2, ws[2].grad, 1e-4, 1e-5, "dw2"); _close(db2, ws[3].grad, 1e-4, 1e-5, "db2")
-    _close(dw1, ws[0].grad, 1e-4, 1e-5, "dw1"); _close(db1, ws[1].grad, 1e-4, 1e-5, "db1")
-    _close(ops.gap_bwd(dp, 16, 16), xr.grad, 1e-4, 1e-7, "gap bwd")
 
 
 def test_dice_multihead_matches_oracle():
@@ -2416,3 +2356,559 @@ def test_step_programs_launch_only_reference_tested_convT_instances():
     print(f"{len(total)} distinct keys in the four programs, {len(tested)} keys tested")
     assert not missing, "transposed-convolution launches of the step programs that no fp64 reference case makes: " + \
         "".join(f"\n  {p_}: {kind} {k} at (N, Cin, Cout, H, W, k) = {s}" for p_, ks in missing.items() for kind, k, s in ks)
+
+
+# ------------------------------------------------------------------ the max-pool, 1x1, GAP, Linear and fused-head launches of the step programs, element by element
+def _small_op_key(op):
+    """Coverage key of ONE small op (ops.SMALL_OPS): the launches mtbc_op_kernel_name plans + the branches the ARGUMENTS select inside those
+    kernels -- which tensors are channel-range views of wider buffers (a batch stride above dense), argmax, bias / dbias, every accumulate
+    flag, dx present, and Cout > 8 (a second channel group in the planar 1x1 kernels).  The only place that decides what "the same launch"
+    means for the guard below."""
+    L = ops.L
+    name, k, f = ops.op_kernel_name(op), op.kind, []
+
+    def views(a, dense, *names):
+        f.extend(f"{n}_strided" for n in names if getattr(a, n + "_batch_stride") != dense[n])
+
+    if k in (L.OP_POOL_FWD, L.OP_POOL_BWD):
+        a = op.u.pool
+        full = a.C * a.H * a.W
+        dense = dict(x=full, y=full // 4, dy=full // 4, dx=full)
+        if k == L.OP_POOL_FWD:
+            views(a, dense, "x", "y")
+            f += ["argmax"] if a.argmax else []
+        else:
+            views(a, dense, "x", "dy", "dx")
+            f += ["acc_dx"] if a.accumulate_dx else []
+    elif k in (L.OP_CONV1_FWD, L.OP_CONV1_DGRAD, L.OP_CONV1_WGRAD):
+        a = op.u.conv1
+        dense = dict(x=a.Cin * a.H * a.W, dx=a.Cin * a.H * a.W)
+        if k == L.OP_CONV1_FWD:
+            views(a, dense, "x")
+            f += ["bias"] if a.bias else []
+        elif k == L.OP_CONV1_DGRAD:
+            views(a, dense, "dx")
+            f += ["acc_dx"] if a.accumulate_dx else []
+        else:
+            views(a, dense, "x")
+            f += ["dbias"] if a.dbias else []
+            f += ["acc_dw"] if a.accumulate_dw else []
+        f += ["Cout>8"] if a.Cout > 8 else []
+    elif k == L.OP_LINEAR_FWD:
+        f += [n for n in ("relu", "bias") if getattr(op.u.linear, n)]
+    elif k == L.OP_LINEAR_BWD:
+        a = op.u.linear
+        f += [n for n in ("relu", "dx", "dbias") if getattr(a, n)]
+        f += ["acc_dw"] if a.accumulate_dw else []
+    elif k == L.OP_HEAD_COMBINE:
+        f += [n for n in ("bT", "b1") if getattr(op.u.head, n)]
+    elif k == L.OP_HEAD_EXPAND:
+        f += [n for n in ("bT", "dbT", "db1", "acc_wT", "acc_bT", "acc_w1", "acc_b1") if getattr(op.u.head, n)]
+    else:
+        assert k in (L.OP_GAP_FWD, L.OP_GAP_BWD), k          # (GAP: dense tensors, no flag)
+    return name, tuple(f)
+
+
+# kind -> (the *_case_args helper of ops.py, the op kind)
+_SMALL_FAMILY = {"pool_fwd": ("maxpool", ops.L.OP_POOL_FWD), "pool_bwd": ("maxpool", ops.L.OP_POOL_BWD),
+                 "c1_fwd": ("conv1x1", ops.L.OP_CONV1_FWD), "c1_dgrad": ("conv1x1", ops.L.OP_CONV1_DGRAD), "c1_wgrad": ("conv1x1", ops.L.OP_CONV1_WGRAD),
+                 "gap_fwd": ("gap", ops.L.OP_GAP_FWD), "gap_bwd": ("gap", ops.L.OP_GAP_BWD),
+                 "lin_fwd": ("linear", ops.L.OP_LINEAR_FWD), "lin_bwd": ("linear", ops.L.OP_LINEAR_BWD),
+                 "head_combine": ("head", ops.L.OP_HEAD_COMBINE), "head_expand": ("head", ops.L.OP_HEAD_EXPAND)}
+
+
+def _both16(kind, shape, mode, strided):
+    """A 16-bit case in bf16 and in fp16."""
+    return [(kind, shape, dict(mode, compute=c), strided) for c in (1, 2)]
+
+
+# (kind, shape, mode, strided).  shape: pool / GAP (N, C, H, W), 1x1 (N, Cin, Cout, H, W), Linear (N, In, Out), head (Cin, Cmid, R, k).  mode: the
+# keywords of the kind's ops.*_case_args helper; compute = 1 | 2: x (and the pool's y) 16-bit channel-blocked of that type.  strided: the
+# activation tensors that are channel ranges [8, 8 + C) of a buffer 16 channels wider.  Each row is the smallest problem that reaches its launch
+# and still has the structure that can go wrong there: more than one block of 256 threads with a ragged last one, several images, a second
+# ragged channel group.  Rows marked (P) make a key one of the four step programs has today (their tensors are all dense); every other row is
+# there because the standard is every instance the dispatchers can pick and every branch the arguments can select.
+_PV, _BV = ("x", "y"), ("x", "dy", "dx")
+SMALL_OP_CASES = [
+    # ---- max-pool forward, fp32 planes: the float4 kernel (one thread = two windows), the scalar kernel where W % 4 != 0
+    ("pool_fwd", (3, 5, 12, 40), {}, _PV),                               # 900 threads: four blocks, the last ragged; x and y views
+    ("pool_fwd", (2, 3, 8, 8), {}, ()),                                  # (P) dense, 48 threads
+    ("pool_fwd", (1, 5, 6, 10), {}, ()),                                 # scalar kernel: W % 4 != 0
+    ("pool_fwd", (3, 5, 10, 14), {}, _PV),                               # scalar kernel, 525 threads, views
+    # ---- max-pool forward, 16-bit channel-blocked, with and without the argmax codes
+    *_both16("pool_fwd", (3, 16, 16, 16), dict(argmax=True), _PV),       # 384 threads: two blocks, ragged
+    *_both16("pool_fwd", (3, 16, 16, 16), {}, _PV),
+    *_both16("pool_fwd", (2, 8, 4, 8), dict(argmax=True), ()),           # dense
+    *_both16("pool_fwd", (3, 16, 16, 16), {}, ("x",)),                   # a view of a concat buffer pooled into a dense tensor
+    *_both16("pool_fwd", (2, 8, 4, 8), {}, ()),
+    *_both16("pool_fwd", (3, 16, 16, 16), dict(argmax=True), ("x",)),
+    # ---- max-pool backward: overwrite and accumulate, views and dense
+    ("pool_bwd", (3, 5, 12, 20), {}, _BV),                               # 900 threads
+    ("pool_bwd", (3, 5, 12, 20), dict(acc_dx=True), _BV),
+    ("pool_bwd", (2, 3, 8, 8), {}, ()),                                  # (P)
+    ("pool_bwd", (2, 3, 8, 8), dict(acc_dx=True), ()),                   # (P)
+    ("pool_bwd", (3, 5, 12, 20), {}, ("x", "dx")),
+    ("pool_bwd", (3, 5, 12, 20), dict(acc_dx=True), ("x", "dx")),
+    *_both16("pool_bwd", (3, 16, 16, 16), {}, _BV),
+    *_both16("pool_bwd", (3, 16, 16, 16), dict(acc_dx=True), _BV),
+    *_both16("pool_bwd", (2, 8, 4, 8), {}, ()),
+    *_both16("pool_bwd", (2, 8, 4, 8), dict(acc_dx=True), ()),
+    # ---- 1x1 forward, fp32 planes: thread = 4 pixels x 8 output channels; 288 threads per image = two blocks, ragged; Cout = 10: a second, ragged group
+    ("c1_fwd", (2, 12, 1, 32, 36), {}, ("x",)),
+    ("c1_fwd", (2, 12, 1, 32, 36), {}, ()),                              # (P)
+    ("c1_fwd", (2, 12, 1, 32, 36), dict(bias=False), ()),
+    ("c1_fwd", (2, 12, 3, 32, 36), {}, ()),
+    ("c1_fwd", (2, 12, 3, 32, 36), dict(bias=False), ("x",)),
+    ("c1_fwd", (2, 12, 10, 32, 36), {}, ("x",)),
+    ("c1_fwd", (2, 12, 10, 32, 36), dict(bias=False), ()),
+    # ---- 1x1 input gradient: Cout = 10 adds the second group's sum to what the first stored (cog > 0)
+    ("c1_dgrad", (2, 12, 1, 32, 36), {}, ("dx",)),
+    ("c1_dgrad", (2, 12, 1, 32, 36), {}, ()),                            # (P)
+    ("c1_dgrad", (2, 12, 1, 32, 36), dict(acc_dx=True), ()),
+    ("c1_dgrad", (2, 12, 1, 32, 36), dict(acc_dx=True), ("dx",)),
+    ("c1_dgrad", (2, 12, 10, 32, 36), {}, ()),
+    ("c1_dgrad", (2, 12, 10, 32, 36), {}, ("dx",)),
+    ("c1_dgrad", (2, 12, 10, 32, 36), dict(acc_dx=True), ()),
+    ("c1_dgrad", (2, 12, 10, 32, 36), dict(acc_dx=True), ("dx",)),
+    # ---- 1x1 weight gradient, fp32 planes: one partial per image, the reducer instance by the image count, the bias gradient's plane sums
+    ("c1_wgrad", (3, 12, 3, 8, 8), {}, ("x",)),                          # splitk_reduce<4>, 64-thread plane sums
+    ("c1_wgrad", (3, 12, 3, 8, 8), dict(bias=False), ()),
+    ("c1_wgrad", (3, 12, 3, 8, 8), dict(bias=False, acc_dw=True), ("x",)),
+    ("c1_wgrad", (3, 12, 10, 8, 8), {}, ()),
+    ("c1_wgrad", (40, 12, 3, 8, 8), dict(acc_dw=True), ()),              # splitk_reduce<16>: more than 32 images
+    ("c1_wgrad", (40, 12, 1, 8, 8), {}, ("x",)),
+    ("c1_wgrad", (256, 12, 2, 4, 4), {}, ()),                            # splitk_reduce<64, 16>: 256 images
+    ("c1_wgrad", (2, 12, 1, 64, 64), {}, ("x",)),                        # H * W = 4096: 256-thread plane sums
+    ("c1_wgrad", (2, 12, 1, 64, 64), {}, ()),                            # (P)
+    ("c1_wgrad", (2, 12, 1, 63, 64), dict(acc_dw=True), ()),             # H * W = 4032: the last plane size with 64 threads
+    # ---- 1x1 on a 16-bit channel-blocked x: forward (one lane = one pixel; 320 pixels = two blocks, ragged) and weight gradient
+    *_both16("c1_fwd", (2, 8, 1, 16, 20), {}, ("x",)),                   # Cin = 8: one channel group
+    *_both16("c1_fwd", (2, 24, 1, 16, 20), {}, ()),                      # (P)
+    *_both16("c1_fwd", (2, 24, 3, 16, 20), dict(bias=False), ()),
+    *_both16("c1_fwd", (3, 16, 8, 16, 20), {}, ("x",)),                  # Cout = 8: every accumulator used
+    *_both16("c1_wgrad", (2, 8, 1, 16, 20), {}, ("x",)),                 # nblk = 1
+    *_both16("c1_wgrad", (2, 24, 1, 16, 20), {}, ()),
+    *_both16("c1_wgrad", (2, 24, 3, 16, 20), dict(bias=False, acc_dw=True), ()),
+    *_both16("c1_wgrad", (2, 16, 8, 16, 20), dict(acc_dw=True), ("x",)),
+    *_both16("c1_wgrad", (2, 16, 3, 90, 92), {}, ("x",)),                # nblk = 2: chunks of 4140 pixels = 16 rounds of 256 threads + 44
+    *_both16("c1_wgrad", (1, 8, 1, 112, 112), dict(bias=False), ()),     # nblk = 3: chunks of 4182, the last 4180
+    *_both16("c1_wgrad", (1, 8, 1, 256, 512), {}, ()),                   # nblk = 32, the cap, at the smallest plane that reaches it
+    *_both16("c1_wgrad", (1, 8, 1, 256, 512), dict(acc_dw=True), ("x",)),
+    # ---- GAP: one wave per plane, four planes per block; 15 and 12 planes, a plane shorter than a wave, H * W % 64 != 0
+    ("gap_fwd", (3, 5, 5, 7), {}, ()), ("gap_bwd", (3, 5, 5, 7), {}, ()),
+    ("gap_fwd", (2, 6, 16, 16), {}, ()), ("gap_bwd", (2, 6, 16, 16), {}, ()),
+    ("gap_fwd", (3, 5, 32, 32), {}, ()), ("gap_bwd", (3, 5, 32, 32), {}, ()),        # (P) all six
+    # ---- Linear: (11, 70, 13) = both eight-wide unrolled loops and both tails, In = 70 a ragged second round of the forward's wave
+    ("lin_fwd", (11, 70, 13), dict(relu=True), ()),                      # (P)
+    ("lin_fwd", (11, 70, 13), {}, ()),                                   # (P)
+    ("lin_fwd", (3, 256, 3), dict(bias=False), ()),
+    ("lin_fwd", (3, 256, 3), dict(relu=True, bias=False), ()),
+    ("lin_fwd", (16, 512, 256), dict(relu=True), ()),                    # (P)
+    ("lin_bwd", (11, 70, 13), dict(relu=True, acc_dw=True), ()),
+    ("lin_bwd", (11, 70, 13), {}, ()),
+    ("lin_bwd", (11, 70, 3), {}, ()),                                    # (P) the logits layer: N >= 8 with Out < 8
+    ("lin_bwd", (4, 70, 13), dict(relu=True), ()),                       # fewer than eight samples: the plain loop of linear_dw_kernel alone
+    ("lin_bwd", (3, 256, 3), {}, ()),                                    # no unrolled loop at all
+    ("lin_bwd", (3, 256, 3), dict(dx=False), ()),
+    ("lin_bwd", (3, 256, 3), dict(relu=True, dx=False, acc_dw=True), ()),
+    ("lin_bwd", (16, 512, 256), dict(relu=True), ()),                    # (P)
+    ("lin_bwd", (16, 512, 256), dict(relu=True, dx=False), ()),
+    ("lin_bwd", (16, 512, 256), dict(acc_dw=True), ()),
+    # ---- the fused ConvT + 1x1 head: Cin * k * k = 320 / 288 / 768 (the 256-thread reduction of dw1, ragged), R = 1 and 3
+    ("head_combine", (20, 7, 3, 4), {}, ()),                             # (P)
+    ("head_combine", (72, 5, 1, 2), {}, ()),                             # (P)
+    ("head_combine", (12, 6, 1, 8), {}, ()),                             # (P)
+    ("head_combine", (72, 5, 1, 2), dict(bT=False), ()),
+    ("head_combine", (12, 6, 3, 8), dict(b1=False), ()),
+    ("head_expand", (20, 7, 3, 4), {}, ()),                              # (P)
+    ("head_expand", (72, 5, 1, 2), {}, ()),                              # (P)
+    ("head_expand", (12, 6, 1, 8), {}, ()),                              # (P)
+    ("head_expand", (72, 5, 1, 2), dict(bT=False, acc=(1, 0, 0, 0)), ()),
+    ("head_expand", (12, 6, 1, 8), dict(dbT=False, acc=(0, 0, 1, 0)), ()),
+    ("head_expand", (12, 6, 3, 8), dict(db1=False, acc=(0, 1, 0, 0)), ()),
+    ("head_expand", (20, 7, 1, 4), dict(acc=(0, 0, 0, 1)), ()),
+    ("head_expand", (20, 7, 3, 2), dict(acc=(1, 1, 1, 1)), ()),
+]
+
+
+def _small_case_id(case):
+    kind, shape, mode, strided = case
+    return f"{kind}-" + "x".join(str(v) for v in shape) + "-" + ",".join(f"{n}={v if isinstance(v, tuple) else int(v)}" for n, v in sorted(mode.items())) + \
+        ("-" + "+".join(strided) if strided else "")
+
+
+def _small_case_ops(case, ptrs=None):
+    """[op] of the launches a case makes, through the kind's ops.*_case_args helper (dummy pointers without ptrs)."""
+    kind, shape, mode, strided = case
+    helper, opk = _SMALL_FAMILY[kind]
+    kw = dict(mode)
+    if helper == "maxpool":
+        _, Cc, H, W = shape
+        per = dict(x=H * W, y=H * W // 4, dy=H * W // 4, dx=H * W)
+        kw["strides"] = {n: (Cc + 2 * _CT_PAD) * per[n] for n in strided}
+    elif helper == "conv1x1":
+        _, Cin, _, H, W = shape
+        kw["strides"] = {n: (Cin + 2 * _CT_PAD) * H * W for n in strided}
+    return [getattr(ops, helper + "_case_args")(opk, *shape, ptrs=ptrs, **kw)]
+
+
+_NAN, _INF = float("nan"), float("inf")
+# 2x2 windows in (0,0), (0,1), (1,0), (1,1) order, written over the first and the last windows of every pool input: NaN at each position, two
+# NaNs, infinities, equal maxima at each pair of positions, -0 / +0 ties, and two values that are equal only once rounded to 16 bits
+_POOL_WINDOWS = [
+    [_NAN, 1, 2, 3], [1, _NAN, 2, 3], [1, 2, _NAN, 3], [1, 2, 3, _NAN], [1, _NAN, _NAN, 3], [_NAN, 5, 1, _NAN], [_INF, _NAN, 1, 2],
+    [_INF, 1, 2, 3], [1, 2, _INF, _INF], [-_INF, -_INF, -_INF, -_INF], [-_INF, -3, -_INF, -5],
+    [7, 7, 1, 2], [7, 1, 7, 2], [7, 1, 2, 7], [1, 7, 7, 2], [1, 7, 2, 7], [1, 2, 7, 7], [4, 4, 4, 4],
+    [-0.0, 0.0, 0.0, -0.0], [0.0, -0.0, -0.0, 0.0], [-1, -0.0, 0.0, -2], [-1, 0.0, -0.0, -2],
+    [0.5, 1.0, 1.0 + 2.0 ** -12, 0.25],
+]
+
+
+def _craft_pool_windows(x):
+    N, Cc, H, W = x.shape
+    oH, oW = H // 2, W // 2
+    total = N * Cc * oH * oW
+    assert total >= 2 * len(_POOL_WINDOWS), total
+    for i, wv in enumerate(_POOL_WINDOWS):
+        for f in (i, total - 1 - i):
+            ox, t = f % oW, f // oW
+            oy, t = t % oH, t // oH
+            x[t // Cc, t % Cc, 2 * oy:2 * oy + 2, 2 * ox:2 * ox + 2] = torch.tensor(wv, dtype=x.dtype).reshape(2, 2)
+    return x
+
+
+def _same_bits(a, b):
+    """Equal as stored words (a NaN equals the same NaN)."""
+    if a.dtype == torch.float32:
+        a, b = a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)
+    return a.shape == b.shape and torch.equal(a, b)
+
+
+def _identical64(got, want):
+    """fp64 values equal up to the NaN payload: NaN where NaN, else the same value with the same sign of zero."""
+    ok = ~torch.isnan(want)
+    return got.shape == want.shape and torch.equal(torch.isnan(got), torch.isnan(want)) and torch.equal(got[ok], want[ok]) and \
+        torch.equal(torch.signbit(got[ok]), torch.signbit(want[ok]))
+
+
+class _Guarded:
+    """A dense tensor on the device with a canary of 64 elements on each side; `cpu` keeps what was uploaded."""
+    PAD, MARK = 64, 1993
+
+    def __init__(self, vals):
+        self.cpu, n = vals.clone(), vals.numel()
+        flat = torch.full((n + 2 * self.PAD,), self.MARK, dtype=vals.dtype)
+        flat[self.PAD:self.PAD + n] = vals.reshape(-1)
+        self.buf = flat.to(DEV)
+        self.view = self.buf[self.PAD:self.PAD + n].view(vals.shape)
+
+    def data_ptr(self):
+        return self.view.data_ptr()
+
+    def numel(self):
+        return self.view.numel()
+
+    def read(self):
+        """(the tensor as it is now, True when both canaries still hold their mark)"""
+        got = self.buf.cpu()
+        return got[self.PAD:-self.PAD].view(self.cpu.shape), bool((got[:self.PAD] == self.MARK).all() and (got[-self.PAD:] == self.MARK).all())
+
+
+class _Bounds:
+    """Collects worst error / bound per output of a case (the bounds of test_convT_step_instances_match_fp64)."""
+
+    def __init__(self, name):
+        self.name, self.worst, self.msgs = name, {}, []
+
+    def check(self, what, got, ref, tol, floor, prefill=None):
+        want = ref if prefill is None else ref + prefill.double()
+        got = got.double()
+        assert got.shape == want.shape, (what, tuple(got.shape), tuple(want.shape))
+        assert bool(torch.isfinite(got).all()), f"{what}: non-finite"
+        scale = max(floor, ref.abs().max().item(), want.abs().max().item())
+        err = (got - want).abs().max().item()
+        self.worst[what] = err / (tol * scale)
+        self.msgs.append(f"{what} ({self.name}): max err {err:.3e} against {tol:g} x {scale:.3e}")
+
+    def fwd(self, what, got, ref, prefill=None):          # fp32 forward and dx outputs
+        self.check(what, got, ref, 1e-5, 0.0, prefill)
+
+    def param(self, what, got, ref, prefill=None):        # parameter gradients
+        self.check(what, got, ref, 1e-4, 1.0, prefill)
+
+    def out(self, what, t, ref, bound, prefill=None):
+        """A _Guarded output against its reference -- or, with ref None, untouched: it was not asked for."""
+        got, intact = t.read()
+        assert intact, f"{what}: the memory around it was written"
+        if ref is None:
+            assert _same_bits(got, t.cpu), f"{what} was written without being asked for"
+        else:
+            bound(what, got, ref, t.cpu if prefill else None)
+
+
+def _small_launch(case, T):
+    """Launches the case on the tensors T; the launches made are what the dummy arguments plan.  Returns the launches' name."""
+    planned = [(op.kind, ops.op_kernel_name(op)) for op in _small_case_ops(case)]
+    real = _small_case_ops(case, T)
+    assert [(op.kind, ops.op_kernel_name(op)) for op in real] == planned, "the real pointers plan something else than the dummies"
+    ops.launched = []
+    try:
+        for op in real:
+            ops.small_op_launch(op)
+        torch.cuda.synchronize()
+        made = list(ops.launched)
+    finally:
+        ops.launched = None
+    assert made == planned, (made, planned)
+    return planned[0][1]
+
+
+def _workspace(case):
+    """(the NaN-filled workspace the case's arguments ask for, the allocation it sits in: 1993.0 behind it)"""
+    op = _small_case_ops(case)[0]
+    nbytes = int(getattr(op.u, ops.L.OP_UNION_FIELD[op.kind]).workspace_bytes)
+    nfloat = max(4, (nbytes + 3) // 4)
+    slack = torch.full((nfloat + 4096,), float("nan"), device=DEV)
+    slack[nfloat:] = 1993.0
+    return slack[:nfloat], slack
+
+
+def _small_pool(case, g):
+    from oracle import small_ops_reference as R
+    kind, (N, Cc, H, W), mode, strided = case
+    st = mode.get("compute", 0)
+    fmt = "c8" if st else "f32"
+    pad = lambda n: _CT_PAD if n in strided else 0      # noqa: E731
+    x = _craft_pool_windows(torch.randn(N, Cc, H, W, generator=g))
+    x = _round16(x, st) if st else x
+    T = dict(x=_CtTensor(x, fmt, st, pad("x"), g))
+    T["y"] = _CtTensor(torch.randn(N, Cc, H // 2, W // 2, generator=g), fmt, st, pad("y"), g)
+    if kind == "pool_fwd":
+        T["argmax"] = _Guarded(torch.full((N, Cc // 8 if st else Cc, (H // 2) * (W // 2)), 0x5555, dtype=torch.int16))
+    else:
+        dy = torch.randn(N, Cc, H // 2, W // 2, generator=g)
+        pre = torch.randn(N, Cc, H, W, generator=g)
+        T["dy"], T["dx"] = _CtTensor(dy, "f32", 0, pad("dy"), g), _CtTensor(pre, "f32", 0, pad("dx"), g)
+    b = _Bounds(_small_launch(case, T))
+    assert _same_bits(T["x"].buf.cpu(), T["x"].cpu), "x was written"
+    got, untouched = T["y"].read()
+    if kind == "pool_fwd":
+        assert untouched, "y: the channels around the view were written"
+        assert _identical64(got, R.maxpool_fwd64(x)), f"y ({b.name}): not the first maximum of every window, bit for bit"
+        codes, intact = T["argmax"].read()
+        assert intact, "argmax: the memory around it was written"
+        if mode.get("argmax"):
+            assert torch.equal(codes.long() & 0xffff, R.maxpool_argmax_codes(x)), f"argmax codes ({b.name})"
+        else:
+            assert torch.equal(codes, T["argmax"].cpu), "argmax was written without being asked for"
+        b.worst["y exact"] = 0.0
+        return b
+    assert untouched and _same_bits(T["y"].buf.cpu(), T["y"].cpu), "the backward wrote y"
+    assert _same_bits(T["dy"].buf.cpu(), T["dy"].cpu), "dy was written"
+    got, untouched = T["dx"].read()
+    assert untouched, "dx: the channels around the view were written"
+    routed = R.maxpool_bwd64(x, dy).float()
+    want = (pre + routed) if mode.get("acc_dx") else routed          # one IEEE add
+    assert torch.equal(got.float(), want), f"dx ({b.name}): max difference {(got.float() - want).abs().max().item():.3e}"
+    b.worst["dx exact"] = 0.0
+    return b
+
+
+def _small_conv1x1(case, g):
+    from oracle import small_ops_reference as R
+    kind, (N, Cin, Cout, H, W), mode, strided = case
+    st = mode.get("compute", 0)
+    pad = lambda n: _CT_PAD if n in strided else 0      # noqa: E731
+    x = torch.randn(N, Cin, H, W, generator=g)
+    x = _round16(x, st) if st else x
+    w = torch.randn(Cout, Cin, 1, 1, generator=g) * (1.0 / Cin) ** 0.5
+    bias, dy = torch.randn(Cout, generator=g), torch.randn(N, Cout, H, W, generator=g)
+    ins = dict(w=w.to(DEV), bias=bias.to(DEV), dy=dy.to(DEV))
+    T = dict(ins, x=_CtTensor(x, "c8" if st else "f32", st, pad("x"), g))
+    T["y"] = _Guarded(torch.randn(N, Cout, H, W, generator=g))
+    T["dx"] = _CtTensor(torch.randn(N, Cin, H, W, generator=g), "f32", 0, pad("dx"), g)
+    T["dw"], T["dbias"] = _Guarded(torch.randn(Cout, Cin, 1, 1, generator=g)), _Guarded(torch.randn(Cout, generator=g))
+    slack = None
+    if kind == "c1_wgrad":
+        T["workspace"], slack = _workspace(case)
+    b = _Bounds(_small_launch(case, T))
+    assert _same_bits(T["x"].buf.cpu(), T["x"].cpu), "x was written"
+    for n, t in (("w", w), ("bias", bias), ("dy", dy)):
+        assert torch.equal(ins[n].cpu(), t), f"{n} was written"
+    b.out("y", T["y"], R.conv1x1_fwd64(x, w, bias if mode.get("bias", True) else None) if kind == "c1_fwd" else None, b.fwd)
+    got, untouched = T["dx"].read()
+    assert untouched, "dx: the channels around the view were written"
+    if kind == "c1_dgrad":
+        b.fwd("dx", got, R.conv1x1_dx64(dy, w), T["dx"].cpu[:, T["dx"]._sl] if mode.get("acc_dx") else None)
+    else:
+        assert _same_bits(T["dx"].buf.cpu(), T["dx"].cpu), "dx was written without being asked for"
+    wg, acc = kind == "c1_wgrad", mode.get("acc_dw")
+    b.out("dW", T["dw"], R.conv1x1_dw64(x, dy).reshape(Cout, Cin, 1, 1) if wg else None, b.param, acc)
+    b.out("dbias", T["dbias"], R.conv1x1_dbias64(dy) if wg and mode.get("bias", True) else None, b.param, acc)
+    if slack is not None:
+        assert bool((slack[T["workspace"].numel():] == 1993.0).all()), "the memory behind the workspace was written"
+    return b
+
+
+def _small_gap(case, g):
+    from oracle import small_ops_reference as R
+    kind, (N, Cc, H, W), mode, strided = case
+    x, dy = torch.randn(N, Cc, H, W, generator=g) + 0.5, torch.randn(N, Cc, generator=g)
+    ins = dict(x=x.to(DEV), dy=dy.to(DEV))
+    T = dict(ins, y=_Guarded(torch.randn(N, Cc, generator=g)), dx=_Guarded(torch.randn(N, Cc, H, W, generator=g)))
+    b = _Bounds(_small_launch(case, T))
+    assert torch.equal(ins["x"].cpu(), x) and torch.equal(ins["dy"].cpu(), dy), "an input was written"
+    b.out("y", T["y"], R.gap_fwd64(x) if kind == "gap_fwd" else None, b.fwd)
+    b.out("dx", T["dx"], R.gap_bwd64(dy, H, W) if kind == "gap_bwd" else None, b.fwd)
+    return b
+
+
+def _small_linear(case, g):
+    from oracle import small_ops_reference as R
+    kind, (N, In, Out), mode, strided = case
+    relu, has_bias = bool(mode.get("relu")), mode.get("bias", True)
+    x, w = torch.randn(N, In, generator=g), torch.randn(Out, In, generator=g) * (1.0 / In) ** 0.5
+    bias, dy = torch.randn(Out, generator=g) * 0.1, torch.randn(N, Out, generator=g)
+    yref = R.linear_fwd64(x, w, bias if has_bias else None, relu)
+    fwd = kind == "lin_fwd"
+    ins = dict(x=x.to(DEV), w=w.to(DEV), bias=bias.to(DEV), dy=dy.to(DEV))
+    T = dict(ins)
+    ystored = yref.float()                  # the backward masks on the stored output: exact zeros where the ReLU cut
+    T["y"] = _Guarded(torch.randn(N, Out, generator=g) if fwd else ystored)
+    T["dx"], T["dw"], T["dbias"] = _Guarded(torch.randn(N, In, generator=g)), _Guarded(torch.randn(Out, In, generator=g)), _Guarded(torch.randn(Out, generator=g))
+    slack = None
+    if not fwd and relu:
+        T["workspace"], slack = _workspace(case)
+    b = _Bounds(_small_launch(case, T))
+    for n, t in (("x", x), ("w", w), ("bias", bias), ("dy", dy)):
+        assert torch.equal(ins[n].cpu(), t), f"{n} was written"
+    if fwd:
+        b.out("y", T["y"], yref, b.fwd)
+        if relu:
+            got = T["y"].read()[0]
+            pre = R.linear_fwd64(x, w, bias if has_bias else None, False)
+            cut = pre < -1e-5 * pre.abs().max().item()
+            assert bool(cut.any()) and bool((yref > 0).any()), "the case has no output on each side of the ReLU"
+            assert bool((got[cut] == 0).all()), "a negative pre-activation was not stored as exactly 0"
+    else:
+        assert bool((ystored == 0).any()) or not relu
+        b.out("y", T["y"], None, None)
+        dx, dw, db = R.linear_bwd64(x, w, ystored, dy, relu)
+        acc = mode.get("acc_dw")
+        b.out("dx", T["dx"], dx if mode.get("dx", True) else None, b.fwd)
+        b.out("dW", T["dw"], dw, b.param, acc)
+        b.out("dbias", T["dbias"], db, b.param, acc)
+    if fwd:
+        for n in ("dx", "dw", "dbias"):
+            b.out(n, T[n], None, None)
+    if slack is not None:
+        assert bool((slack[T["workspace"].numel():] == 1993.0).all()), "the memory behind the workspace was written"
+    return b
+
+
+def _small_head(case, g):
+    from oracle import small_ops_reference as R
+    kind, (Cin, Cmid, Rr, k), mode, strided = case
+    wT, bT = torch.randn(Cin, Cmid, k, k, generator=g) * (1.0 / Cin) ** 0.5, torch.randn(Cmid, generator=g)
+    w1, b1 = torch.randn(Rr, Cmid, generator=g) * (1.0 / Cmid) ** 0.5, torch.randn(Rr, generator=g)
+    G, gb = torch.randn(Cin, Rr, k, k, generator=g), torch.randn(Rr, generator=g)
+    src = dict(wT=wT, bT=bT, w1=w1, b1=b1, G=G, gb=gb)
+    ins = {n: t.to(DEV) for n, t in src.items()}
+    T = dict(ins)
+    for n, shape in (("Wc", (Cin, Rr, k, k)), ("bc", (Rr,)), ("dwT", wT.shape), ("dbT", bT.shape), ("dw1", w1.shape), ("db1", b1.shape)):
+        T[n] = _Guarded(torch.randn(*shape, generator=g))
+    b = _Bounds(_small_launch(case, T))
+    for n, t in src.items():
+        assert torch.equal(ins[n].cpu(), t), f"{n} was written"
+    has_bT, has_b1 = mode.get("bT", True), mode.get("b1", True)
+    comb = kind == "head_combine"
+    Wc, bc = R.head_combine64(wT, bT if has_bT else None, w1, b1 if has_b1 else None)
+    b.out("Wc", T["Wc"], Wc if comb else None, b.fwd)
+    b.out("bc", T["bc"], bc if comb else None, b.fwd)
+    refs = dict(zip(("dwT", "dbT", "dw1", "db1"), R.head_expand64(wT, bT if has_bT else None, w1, G, gb)))
+    if not mode.get("dbT", True):
+        refs["dbT"] = None
+    if not mode.get("db1", True):
+        refs["db1"] = None
+    acc = dict(zip(("dwT", "dbT", "dw1", "db1"), mode.get("acc", (0, 0, 0, 0))))
+    for n in ("dwT", "dbT", "dw1", "db1"):
+        b.out(n, T[n], None if comb else refs[n], b.param, acc[n])
+    return b
+
+
+_SMALL_RUN = {"maxpool": _small_pool, "conv1x1": _small_conv1x1, "gap": _small_gap, "linear": _small_linear, "head": _small_head}
+
+
+@pytest.mark.parametrize("case", SMALL_OP_CASES, ids=_small_case_id)
+def test_small_op_step_instances_match_fp64(case):
+    """Every launch the dispatchers of the max-pool, the 1x1 convolution, GAP, Linear and the fused ConvT + 1x1 head can pick (pool_up.hip,
+    c8_ops.hip, head_loss.hip, the reducers of reduce.hip) -- the ones the benchmark's step programs make among them
+    (test_step_programs_launch_only_reference_tested_small_op_instances) -- against the plain fp64 references of oracle/small_ops_reference.py
+    on the STORED operands: inputs are drawn on the CPU and rounded RNE to the type the mode stores.  Every element of every output is compared:
+      max-pool forward, argmax codes, backward      bit for bit (a selection; NaN where NaN, the sign of zero included); the backward in
+                                                    accumulate mode against pre-fill + routed gradient formed in fp32: one IEEE add
+      fp32 forward and dx outputs                   max error <= 1e-5 x max |ref|       (1x1 y and dx, GAP, Linear y and dx, Wc, bc)
+      parameter gradients                           max error <= 1e-4 x max(1, max |ref|)      (1x1 / Linear dW and dbias, dwT, dbT, dw1, db1)
+      accumulate                                    against ref + pre-fill, the same bound on the larger of the two scales
+    the bounds of the ConvT section above; plain fp32 arithmetic on such inputs is within 1.1e-6 relative.  Every pool input carries the
+    windows of _POOL_WINDOWS at both ends.  Every output is pre-filled: what a call was not asked for (dbias, dx, argmax, the other direction's
+    outputs), the channels around a view, the canaries around every dense output, the inputs and the floats behind the workspace keep their
+    contents bit for bit.  The launches made are exactly what mtbc_op_kernel_name plans for the case's dummy arguments."""
+    kind, shape, mode, strided = case
+    g = _g(1993 + 7919 * sorted(_SMALL_FAMILY).index(kind) + sum((31 + 2 * i) * v for i, v in enumerate(shape)) + 3 * mode.get("compute", 0) + len(strided))
+    b = _SMALL_RUN[_SMALL_FAMILY[kind][0]](case, g)
+    print(f"{_small_case_id(case)}: {b.name}: worst error / bound " + ", ".join(f"{n} {v:.3f}" for n, v in b.worst.items()))
+    bad = [m for m, v in zip(b.msgs, [v for n, v in b.worst.items() if not n.endswith(" exact")]) if not v <= 1.0]
+    assert not bad, "; ".join(bad)
+
+
+def _program_small_op_keys(arch, dtype, N, size):
+    """Builds (does not run) one step program with bench.py's constructor path: {(op kind, key): the op's shape}."""
+    from multi_task_breast_cancer_amd.experiment_init import init_multitask_model, init_optimizer
+    from multi_task_breast_cancer_amd.miscellany import seed_everything
+    from multi_task_breast_cancer_amd.trainer import FusedTrainStep
+    L = ops.L
+    shape_of = {"pool": ("N", "C", "H", "W"), "conv1": ("N", "Cin", "Cout", "H", "W"), "gap": ("N", "C", "H", "W"), "linear": ("N", "In", "Out"),
+                "head": ("Cin", "Cmid", "R", "k")}
+    seed_everything(1993)
+    model = init_multitask_model(arch, sequences=1, regions=1, n_classes=3, deep_supervision=True).to(DEV)
+    model.set_compute(dtype)
+    step = FusedTrainStep(model, init_optimizer(model, "Adam", 1e-4), alpha=0.5, inversely_weighted=True)
+    st = step._compiled(N, size, size)
+    seen = {}
+    for prog in st.programs.values():
+        for i in range(getattr(prog, "n", 0)):
+            op = prog.array[i]
+            if op.kind in ops.SMALL_OPS:
+                field = L.OP_UNION_FIELD[op.kind]
+                seen.setdefault((op.kind, _small_op_key(op)), tuple(getattr(getattr(op.u, field), n) for n in shape_of[field]))
+    del st, step, model
+    torch.cuda.empty_cache()
+    return seen
+
+
+def _reference_tested_small_op_keys():
+    """(op kind, key) of every call test_small_op_step_instances_match_fp64 makes, from its case table's argument structs."""
+    return {(op.kind, _small_op_key(op)) for case in SMALL_OP_CASES for op in _small_case_ops(case)}
+
+
+def test_step_programs_launch_only_reference_tested_small_op_instances():
+    """Builds (does not run) the benchmark's four step programs and computes the coverage key of every max-pool, 1x1, GAP, Linear and fused-head
+    op: each must be the key of a call that test_small_op_step_instances_match_fp64 makes.  A plan change -- another kernel or reducer
+    instance, a tensor that became a view, a new argument-selected branch -- that no fp64 case reaches fails here; _small_op_key, SMALL_OP_CASES
+    and _reference_tested_small_op_keys are the places to edit."""
+    L = ops.L
+    tested = _reference_tested_small_op_keys()
+    missing, total = {}, set()
+    for arch, dtype, N, size in STEP_PROGRAMS:
+        seen = _program_small_op_keys(arch, dtype, N, size)
+        print(f"{arch} {dtype} N={N} {size}x{size}: {len(seen)} keys")
+        assert {L.OP_GAP_FWD, L.OP_GAP_BWD, L.OP_LINEAR_FWD, L.OP_LINEAR_BWD} <= {kind for kind, _ in seen}, f"{arch} {dtype}: no classification head found"
+        for (kind, key), shape in sorted(seen.items()):
+            print(f"  op {kind} {key} at {shape}")
+            total.add((kind, key))
+            if (kind, key) not in tested:
+                missing.setdefault((arch, dtype, N, size), []).append((kind, key, shape))
+    print(f"{len(total)} distinct keys in the four programs, {len(tested)} keys tested")
+    assert not missing, "small-op launches of the step programs that no fp64 reference case makes: " + \
+        "".join(f"\n  {p_}: op {kind} {k} at {s}" for p_, ks in missing.items() for kind, k, s in ks)
