@@ -346,6 +346,8 @@ __global__ void focal_kernel(const FocalP p) {
 }
 
 __global__ void loss_mix_kernel(const float* seg, const float* cls, float alpha, float* out4) {
+#pragma clang fp contract(off)          // two products and a sum, each rounded, as training_multitask.py:98 forms it in fp32 (contracted, one product
+                                        // went unrounded into an fma: the reported loss was 1 ulp off the expression for about every other input)
     const float s = *seg, c = *cls;
     out4[0] = alpha * s + (1.0f - alpha) * c;
     out4[1] = s; out4[2] = c;

@@ -129,29 +129,43 @@ def conv3x3_pack_lp(w: torch.Tensor, compute: int) -> Tuple[torch.Tensor, torch.
     return outs[0], outs[1]
 
 
+def conv3x3_image_elems(cout: int, cin: int, kind: int) -> int:
+    """Elements of one weight image of a (cout, cin, 3, 3) weight; kind as in mtbc_pack_desc: 0 fp32 forward, 1 fp32 dgrad (floats),
+    2 16-bit forward, 3 16-bit dgrad (16-bit words)."""
+    lib = L.load()
+    if kind >= 2:
+        return lib.mtbc_conv3x3_packed_lp_elems(cin, cout, kind - 2)
+    return lib.mtbc_conv3x3_packed_dgrad_elems(cin, cout) if kind else lib.mtbc_conv3x3_packed_elems(cin, cout)
+
+
+def conv3x3_pack_list(items, out=None):
+    """One mtbc_conv3x3_pack_many call over a free list of (w, kind, compute) -- kind as in mtbc_pack_desc, compute read for the 16-bit kinds
+    2, 3 -- in list order.  out: the destination tensor of each item (fp32 for kinds 0, 1, int16 for 2, 3), allocated here when None.
+    Returns the destinations."""
+    lib = L.load()
+    descs = (L.PackDesc * len(items))()
+    outs = []
+    for i, (w, kind, compute) in enumerate(items):
+        _chk(w)
+        cout, cin = w.shape[0], w.shape[1]
+        if out is None:
+            t = torch.empty(conv3x3_image_elems(cout, cin, kind), dtype=torch.int16 if kind >= 2 else torch.float32, device=w.device)
+        else:
+            t = out[i]
+            if t.numel() != conv3x3_image_elems(cout, cin, kind) or t.dtype != (torch.int16 if kind >= 2 else torch.float32):
+                raise ValueError(f"destination {i}: {t.numel()} x {t.dtype} for a kind {kind} image of {cout} x {cin}")
+        d = descs[i]
+        d.w, d.packed, d.Cin, d.Cout, d.kind, d.compute = w.data_ptr(), t.data_ptr(), cin, cout, kind, compute
+        outs.append(t)
+    L.check(lib.mtbc_conv3x3_pack_many(descs, len(descs), _s()), "pack_many")
+    return outs
+
+
 def conv3x3_pack_many(weights, compute: int = 0):
     """All weight images of a list of conv weights in one launch (mtbc_conv3x3_pack_many).  Returns, per weight, the
     (fwd, dgrad) images: fp32 tensors for compute 0, int16 tensors for compute 1 (bf16) / 2 (fp16)."""
-    lib = L.load()
-    descs = (L.PackDesc * (2 * len(weights)))()
-    outs = []
-    for i, w in enumerate(weights):
-        _chk(w)
-        cout, cin = w.shape[0], w.shape[1]
-        pair = []
-        for dg in (0, 1):
-            if compute:
-                t = torch.empty(lib.mtbc_conv3x3_packed_lp_elems(cin, cout, dg), dtype=torch.int16, device=w.device)
-            else:
-                n = lib.mtbc_conv3x3_packed_dgrad_elems(cin, cout) if dg else lib.mtbc_conv3x3_packed_elems(cin, cout)
-                t = torch.empty(n, dtype=torch.float32, device=w.device)
-            d = descs[2 * i + dg]
-            d.w, d.packed, d.Cin, d.Cout = w.data_ptr(), t.data_ptr(), cin, cout
-            d.kind, d.compute = (2 + dg if compute else dg), compute
-            pair.append(t)
-        outs.append(tuple(pair))
-    L.check(lib.mtbc_conv3x3_pack_many(descs, len(descs), _s()), "pack_many")
-    return outs
+    outs = conv3x3_pack_list([(w, (2 + dg if compute else dg), compute) for w in weights for dg in (0, 1)])
+    return [(outs[2 * i], outs[2 * i + 1]) for i in range(len(weights))]
 
 
 def _conv_args(xs, w, N, H, W):

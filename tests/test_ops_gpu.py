@@ -363,18 +363,6 @@ def _round16(t, compute):
     return (t.bfloat16() if compute == 1 else t.half()).float()
 
 
-@pytest.mark.parametrize("compute", [1, 2])
-def test_c8_pack_is_rne_and_unpack_is_exact(compute):
-    x = torch.randn(3, 24, 10, 12, generator=_g(5)) * 3
-    c8 = ops.C8.pack(x.to(DEV), compute)
-    assert c8.data.shape == (3, 3, 120, 8)
-    back = c8.unpack().cpu()
-    assert torch.equal(back, _round16(x, compute))
-    # layout: piece (n, g, px) holds channels 8g..8g+7 of pixel px
-    raw = c8.data.cpu().view(torch.bfloat16 if compute == 1 else torch.float16).float()
-    assert torch.equal(raw[1, 2, 37], _round16(x, compute)[1, 16:24].reshape(8, -1)[:, 37])
-
-
 C8_CASES = [
     (2, [8], 16, 32, 32),
     (1, [24, 48], 24, 40, 64),          # two segments, H not a multiple of the tile
@@ -725,33 +713,6 @@ def test_conv1x1_head_on_channel_blocked_input(N, Cin, Cout, H, W, compute):
     dw2, db2 = ops.conv1x1_wgrad_c8(x8, w, dy, accumulate=True, dw=dw.clone(), db=db.clone())
     _close(dw2, 2 * wr.grad.float(), 1e-5, 4e-5 * max(1.0, wr.grad.abs().max().item()), "conv1x1 c8 wgrad accumulate")
     _close(db2, 2 * dbr, 1e-5, 4e-5 * max(1.0, dbr.abs().max().item()), "conv1x1 c8 dbias accumulate")
-
-
-def test_weight_view_many_equals_single_views():
-    """The batched weight-view launch (one per step) writes what the per-view entry point writes."""
-    import ctypes as C
-    from multi_task_breast_cancer_amd import _lib as L
-    g = _g(17)
-    lib = L.load()
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    descs, outs_many, outs_single = [], [], []
-    cases = [(24, 144, 24, 24, 0), (24, 144, 48, 96, 0), (48, 96, 0, 48, 1), (24, 72, 24, 24, 1), (96, 288, 96, 96, 1)] * 11      # 55 > one kernel-argument batch
-    keep = []
-    for Cout, Cin, off, cnt, mode in cases:
-        w = torch.randn(Cout, Cin, 3, 3, generator=g).to(DEV)
-        K = Cout + 8
-        shape = (cnt, K, 3, 3) if mode else (Cout, cnt, 3, 3)
-        a, b = torch.zeros(shape, device=DEV), torch.zeros(shape, device=DEV)
-        keep.append(w)
-        d = L.WViewDesc()
-        d.w, d.dst, d.Cout, d.Cin, d.ci_off, d.ci_cnt, d.mode, d.k_off, d.K = w.data_ptr(), a.data_ptr(), Cout, Cin, off, cnt, mode, 8 if mode else 0, K if mode else 0
-        descs.append(d)
-        L.check(lib.mtbc_conv3x3_weight_view(w.data_ptr(), b.data_ptr(), Cout, Cin, off, cnt, mode, 8 if mode else 0, K if mode else 0, st), "wview")
-        outs_many.append(a); outs_single.append(b)
-    arr = (L.WViewDesc * len(descs))(*descs)
-    L.check(lib.mtbc_conv3x3_weight_view_many(arr, len(descs), st), "wview_many")
-    for a, b in zip(outs_many, outs_single):
-        assert torch.equal(a, b) and a.abs().sum().item() > 0
 
 
 @pytest.mark.parametrize("compute", [1, 2])
@@ -2912,3 +2873,490 @@ def test_step_programs_launch_only_reference_tested_small_op_instances():
     print(f"{len(total)} distinct keys in the four programs, {len(tested)} keys tested")
     assert not missing, "small-op launches of the step programs that no fp64 reference case makes: " + \
         "".join(f"\n  {p_}: op {kind} {k} at {s}" for p_, ks in missing.items() for kind, k, s in ks)
+
+
+# ------------------------------------------------------------------ the weight-image, weight-view and channel-blocking launches of the step programs, bit for bit
+# These kernels (csrc/conv3x3.hip) move or round values and add nothing: every word of every destination is compared with the numpy
+# scatter references of oracle/layout_reference.py (checked on their own in tests/test_layout_reference_cpu.py) as integers, no tolerance.
+# The one exception is NaN: where the reference holds a NaN pattern the device must hold one too; payload and sign are printed, not compared.
+# Every destination sits between two guard regions of _LPAD elements (512 bytes and more), destination and guards pre-filled with a fixed
+# non-zero pattern; the guards and the sources must come back unchanged.
+from oracle import layout_reference as LR  # noqa: E402
+
+PACK_CASES = LR.PACK_CASES                    # (Cout, Cin)
+WVIEW_CASES = LR.WVIEW_CASES                  # (Cout, Cin, off, cnt, mode, k_off, K)
+C8_PACK_CASES = LR.C8_PACK_CASES              # (N, C, HW, strided): mtbc_c8_pack and _unpack, both formats
+C8_PACK16_CASES = LR.C8_PACK16_CASES          # (N, C, HW, strided): mtbc_c8_pack16
+PACK_KINDS = [(0, 0), (1, 0), (2, 1), (2, 2), (3, 1), (3, 2)]          # (kind of mtbc_pack_desc, compute): the four images, the 16-bit ones in both formats
+_LPAD = 256
+_MARK = {torch.float32: 1993.0, torch.int16: 0x5a5a}
+
+
+class _LayoutDst:
+    """A pre-filled flat destination on the device between two pre-filled guard regions of _LPAD elements."""
+
+    def __init__(self, numel, dtype):
+        self.numel, self.dtype = numel, dtype
+        self.buf = torch.full((numel + 2 * _LPAD,), _MARK[dtype], dtype=dtype, device=DEV)
+        self.view = self.buf[_LPAD:_LPAD + numel]
+        assert self.view.data_ptr() % 16 == 0
+
+    def prefill(self):
+        """The destination's pre-fill as the numpy array a reference writes into."""
+        return np.full(self.numel, _MARK[self.dtype], dtype=np.float32 if self.dtype == torch.float32 else np.uint16)
+
+    def read(self, what):
+        got = self.buf.cpu()
+        assert bool((got[:_LPAD] == _MARK[self.dtype]).all() and (got[-_LPAD:] == _MARK[self.dtype]).all()), f"{what}: written outside the destination"
+        got = got[_LPAD:-_LPAD].numpy()
+        return got.view(np.uint32) if self.dtype == torch.float32 else got.view(np.uint16)
+
+
+class _LayoutSrc:
+    """A numpy source uploaded to the device; intact() tells whether the device copy still holds the same words."""
+
+    def __init__(self, vals):
+        self.np = np.ascontiguousarray(vals)
+        self.t = torch.from_numpy(self.np.view(np.int16) if self.np.dtype == np.uint16 else self.np).to(DEV)
+
+    def intact(self):
+        back = self.t.cpu().numpy()
+        return np.array_equal(back.view(np.uint32 if back.dtype == np.float32 else np.uint16), self.np.view(np.uint32 if self.np.dtype == np.float32 else np.uint16))
+
+
+def _same_words(what, got, want, compute=0):
+    """got == want as integers; for the 16-bit type of `compute` a NaN pattern of the reference matches any NaN pattern."""
+    want = np.ascontiguousarray(want).reshape(-1)
+    want = want.view(np.uint32) if want.dtype == np.float32 else want
+    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
+    ok = np.ones(want.shape, bool)
+    if compute:
+        nan = LR.is_nan16(want, compute)
+        assert bool(LR.is_nan16(got, compute)[nan].all()), f"{what}: the reference holds NaN where the device does not"
+        if nan.any():
+            print(f"    {what}: {int(nan.sum())} NaN, device patterns {sorted({hex(v) for v in got[nan].tolist()})}, reference {sorted({hex(v) for v in want[nan].tolist()})}")
+        ok = ~nan
+    bad = np.flatnonzero((got != want) & ok)
+    assert bad.size == 0, f"{what}: {bad.size} of {want.size} words differ, the first at {int(bad[0])}: {hex(int(got[bad[0]]))} for {hex(int(want[bad[0]]))}"
+
+
+_PACK_W, _PACK_REF = {}, {}
+
+
+def _pack_weight(Cout, Cin, compute):
+    """The (Cout, Cin, 3, 3) source of a shape: randn with the special values of `compute` scattered in, some in the last row and the last K."""
+    key = (Cout, Cin, compute)
+    if key not in _PACK_W:
+        w = np.random.default_rng(1993 + 131 * Cout + 17 * Cin + compute).standard_normal((Cout, Cin, 3, 3)).astype(np.float32)
+        _PACK_W[key] = LR.plant(w, compute, LR.weight_edges(Cout, Cin))
+    return _PACK_W[key]
+
+
+def _pack_ref(Cout, Cin, kind, compute):
+    """The reference image of _pack_weight, computed once and shared (read only)."""
+    key = (Cout, Cin, kind, compute)
+    if key not in _PACK_REF:
+        w = _pack_weight(Cout, Cin, compute)
+        _PACK_REF[key] = LR.pack_fwd(w) if kind == 0 else LR.pack_dgrad(w) if kind == 1 else LR.pack_lp(w, kind - 2, compute)
+        _PACK_REF[key].setflags(write=False)
+    return _PACK_REF[key]
+
+
+def _run_pack_list(what, descs):
+    """descs: (Cout, Cin, kind, compute) in list order.  ONE mtbc_conv3x3_pack_many call for a list of more than one descriptor, else the
+    single-tensor entry point of the kind; every image against its reference."""
+    src = {(Cout, Cin, c): _LayoutSrc(_pack_weight(Cout, Cin, c)) for Cout, Cin, _, c in descs}
+    dst = [_LayoutDst(ops.conv3x3_image_elems(Cout, Cin, kind), torch.int16 if kind >= 2 else torch.float32) for Cout, Cin, kind, _ in descs]
+    if len(descs) > 1:
+        ops.conv3x3_pack_list([(src[Cout, Cin, c].t, kind, c) for Cout, Cin, kind, c in descs], out=[d.view for d in dst])
+    else:
+        (Cout, Cin, kind, c), lib, L = descs[0], ops.L.load(), ops.L
+        w, p = src[Cout, Cin, c].t.data_ptr(), dst[0].view.data_ptr()
+        if kind >= 2:
+            L.check(lib.mtbc_conv3x3_pack_lp(w, p, Cin, Cout, kind - 2, c, ops._s()), "pack_lp")
+        else:
+            L.check((lib.mtbc_conv3x3_pack_dgrad if kind else lib.mtbc_conv3x3_pack_fwd)(w, p, Cin, Cout, ops._s()), "pack")
+    torch.cuda.synchronize()
+    bad = []
+    for i, ((Cout, Cin, kind, c), d) in enumerate(zip(descs, dst)):
+        name = f"{what}[{i}] {Cout}x{Cin} kind {kind} compute {c}"
+        try:
+            _same_words(name, d.read(name), _pack_ref(Cout, Cin, kind, c), c if kind >= 2 else 0)
+        except AssertionError as e:
+            bad.append(str(e))
+    assert all(s.intact() for s in src.values()), f"{what}: a source was written"
+    assert not bad, f"{len(bad)} of {len(descs)} images wrong:\n  " + "\n  ".join(bad[:8])
+    return len(descs)
+
+
+@pytest.mark.parametrize("path", ["single", "many"])
+@pytest.mark.parametrize("Cout,Cin", PACK_CASES, ids=lambda v: str(v))
+def test_weight_images_match_the_layout_reference(Cout, Cin, path):
+    """The four images of a shape -- fp32 forward and dgrad, 16-bit forward and dgrad in bf16 and in fp16 -- through the single-tensor entry
+    points (pack_fwd_kernel, pack_dgrad_kernel, pack_lp_kernel) and as ONE mtbc_conv3x3_pack_many list of the six (pack_many_kernel: the LDS
+    transpose, pack_dgrad_elem, pack_lp_unit; the list changes format three times, so it is four launches each with its own format flag)."""
+    if path == "many":
+        n = _run_pack_list(f"{Cout}x{Cin} many", [(Cout, Cin, k, c) for k, c in PACK_KINDS])
+    else:
+        n = sum(_run_pack_list(f"{Cout}x{Cin} single", [(Cout, Cin, k, c)]) for k, c in PACK_KINDS)
+    print(f"{Cout}x{Cin} {path}: {n} images bit for bit")
+
+
+def _mixed_pack_list():
+    """116 descriptors over the shapes of at most 2048 weights: 100 that mix the fp32 kinds with bf16 images (the first launch ends at the 96-descriptor
+    argument batch), then 8 with fp16 images, then 8 with bf16 again: two format breaks.  Repeated descriptors get their own destinations."""
+    small = [s for s in PACK_CASES if s[0] * s[1] <= 32 * 64]
+    descs = []
+    for n, fmt in ((100, 1), (8, 2), (8, 1)):
+        for i in range(n):
+            Cout, Cin = small[(len(descs) * 5 + 3) % len(small)]
+            kind = (2, 0, 3, 1)[i % 4]          # each run starts with a 16-bit image of its format
+            descs.append((Cout, Cin, kind, fmt if kind >= 2 else 0))
+    return descs
+
+
+def test_pack_many_over_format_breaks_and_an_argument_batch_boundary():
+    descs = _mixed_pack_list()
+    assert len(descs) > 96 and {k for _, _, k, _ in descs} == {0, 1, 2, 3}
+    fmts = [c for _, _, k, c in descs if k >= 2]
+    assert [c for i, c in enumerate(fmts) if i == 0 or fmts[i - 1] != c] == [1, 2, 1]
+    n = _run_pack_list("mixed list", descs)
+    print(f"mixed list: {n} images bit for bit")
+
+
+def test_pack_many_of_exactly_two():
+    assert _run_pack_list("two", [(7, 13, 0, 0), (17, 33, 3, 2)]) == 2
+    assert _run_pack_list("two 16-bit", [(17, 33, 2, 1), (7, 13, 3, 1)]) == 2
+
+
+# ---- weight views
+def _wview_id(case):
+    return "-".join(map(str, case))
+
+
+def _wview_desc(case, w, dst):
+    d = ops.L.WViewDesc()
+    d.w, d.dst = w.t.data_ptr(), dst.view.data_ptr()
+    d.Cout, d.Cin, d.ci_off, d.ci_cnt, d.mode, d.k_off, d.K = case
+    return d
+
+
+def _wview_numel(case):
+    Cout, Cin, off, cnt, mode, k_off, K = case
+    return (cnt * K if mode else Cout * cnt) * 9
+
+
+def _wview_weight(case, salt=0):
+    Cout, Cin = case[:2]
+    w = np.random.default_rng(17 + 131 * Cout + 17 * Cin + salt).standard_normal((Cout, Cin, 3, 3)).astype(np.float32)
+    return LR.plant(w, 0, LR.weight_edges(Cout, Cin))
+
+
+def _wview_want(cases_ws, dst):
+    """The destination's pre-fill with the views (case, weight) written into it by the reference, in order."""
+    Cout, Cin, off, cnt, mode, k_off, K = cases_ws[0][0]
+    want = dst.prefill().reshape((cnt, K, 3, 3) if mode else (Cout, cnt, 3, 3))
+    for (Cout, Cin, off, cnt, mode, k_off, K), w in cases_ws:
+        LR.weight_view(w, off, cnt, mode, k_off, K, want)
+    return want
+
+
+@pytest.mark.parametrize("case", WVIEW_CASES, ids=_wview_id)
+def test_weight_view_matches_the_layout_reference(case):
+    """mtbc_conv3x3_weight_view (wview_kernel): the whole destination -- for mode 1 all K of the (cnt, K, 3, 3) tensor, so what lies outside
+    [k_off, k_off + Cout) must keep its pre-fill -- against the reference."""
+    w, dst = _LayoutSrc(_wview_weight(case)), _LayoutDst(_wview_numel(case), torch.float32)
+    ops.L.check(ops.L.load().mtbc_conv3x3_weight_view(w.t.data_ptr(), dst.view.data_ptr(), *case, ops._s()), "weight_view")
+    torch.cuda.synchronize()
+    _same_words(_wview_id(case), dst.read(_wview_id(case)), _wview_want([(case, w.np)], dst))
+    assert w.intact()
+
+
+# three consumers' views side by side in one (8, 40, 3, 3) destination: K ranges [0, 8), [8, 20), [26, 40); [20, 26) is nobody's
+WVIEW_GROUP = [(8, 24, 16, 8, 1, 0, 40), (12, 8, 0, 8, 1, 8, 40), (14, 20, 4, 8, 1, 26, 40)]
+
+
+def test_weight_view_many_matches_the_layout_reference():
+    """mtbc_conv3x3_weight_view_many (wview_many_kernel) over 4 x every case + the group of three = 59 descriptors (more than one argument
+    batch of 48), each with its own destination -- except WVIEW_GROUP, which fills disjoint K ranges of ONE destination and leaves a fourth
+    range to its pre-fill."""
+    L = ops.L
+    items = [(case, _LayoutSrc(_wview_weight(case, rep)), _LayoutDst(_wview_numel(case), torch.float32)) for rep in range(2) for case in WVIEW_CASES]
+    gdst = _LayoutDst(_wview_numel(WVIEW_GROUP[0]), torch.float32)
+    group = [(case, _LayoutSrc(_wview_weight(case, 5)), gdst) for case in WVIEW_GROUP]
+    items += group + [(case, _LayoutSrc(_wview_weight(case, rep)), _LayoutDst(_wview_numel(case), torch.float32)) for rep in range(2, 4) for case in WVIEW_CASES]
+    assert len(items) > 48
+    arr = (L.WViewDesc * len(items))(*[_wview_desc(case, w, dst) for case, w, dst in items])
+    L.check(L.load().mtbc_conv3x3_weight_view_many(arr, len(items), ops._s()), "weight_view_many")
+    torch.cuda.synchronize()
+    bad = []
+    for i, (case, w, dst) in enumerate(items):
+        name = f"[{i}] {_wview_id(case)}"
+        try:
+            if dst is gdst:
+                want = _wview_want([(c, s.np) for c, s, _ in group], dst)
+                assert bool((want[:, 20:26] == _MARK[torch.float32]).all())
+            else:
+                want = _wview_want([(case, w.np)], dst)
+            _same_words(name, dst.read(name), want)
+            assert w.intact(), f"{name}: the source was written"
+        except AssertionError as e:
+            bad.append(str(e))
+    assert not bad, f"{len(bad)} of {len(items)} views wrong:\n  " + "\n  ".join(bad[:8])
+    print(f"{len(items)} views in one call, bit for bit")
+
+
+# ---- channel-blocked activations
+def _c8_source(N, Cc, HW, strided, compute):
+    """(the whole float32 source (N, Cfull, HW), the channel range under test, Cfull)"""
+    Cfull, c0 = (40, 8) if strided else (Cc, 0)
+    x = np.random.default_rng(5 + 7 * N + 3 * Cc + HW + compute).standard_normal((N, Cfull, HW)).astype(np.float32) * 3
+    last = ((N - 1) * Cfull + c0 + Cc - 1) * HW + HW - 1          # the last pixel of the last channel of the range
+    return LR.plant(x, compute, [last, c0 * HW]), slice(c0, c0 + Cc), Cfull
+
+
+@pytest.mark.parametrize("compute", [1, 2])
+@pytest.mark.parametrize("N,Cc,HW,strided", C8_PACK_CASES)
+def test_c8_pack_and_unpack_match_the_layout_reference(N, Cc, HW, strided, compute):
+    """mtbc_c8_pack (c8_pack_kernel<F16>), dense and on a channel range of a wider tensor (src_batch_stride = 40 HW), then mtbc_c8_unpack
+    (c8_unpack_kernel<F16>) of what it wrote: unpack(pack(x)) == round16(x) as floats, bit for bit."""
+    L, lib = ops.L, ops.L.load()
+    x, rng, Cfull = _c8_source(N, Cc, HW, strided, compute)
+    src, y, back = _LayoutSrc(x), _LayoutDst(N * Cc * HW, torch.int16), _LayoutDst(N * Cc * HW, torch.float32)
+    L.check(lib.mtbc_c8_pack(src.t.data_ptr() + 4 * rng.start * HW, Cfull * HW, y.view.data_ptr(), N, Cc, HW, compute, ops._s()), "c8_pack")
+    L.check(lib.mtbc_c8_unpack(y.view.data_ptr(), back.view.data_ptr(), N, Cc, HW, compute, ops._s()), "c8_unpack")
+    torch.cuda.synchronize()
+    want = LR.c8_pack(x[:, rng], compute)
+    _same_words("pack", y.read("pack"), want, compute)
+    h = LR.round16(x[:, rng], compute)
+    wide, got = LR.widen16(h, compute).view(np.uint32).reshape(-1), back.read("unpack")
+    nan = LR.is_nan16(h, compute).reshape(-1)
+    assert bool(np.isnan(got.view(np.float32))[nan].all()) and np.array_equal(got[~nan], wide[~nan]), "unpack(pack(x)) != round16(x)"
+    _same_words("unpack against the reference", got[~nan], LR.c8_unpack(want, compute).view(np.uint32).reshape(-1)[~nan])
+    assert src.intact()
+
+
+@pytest.mark.parametrize("N,Cc,HW,strided", C8_PACK16_CASES)
+def test_c8_pack16_matches_the_layout_reference(N, Cc, HW, strided):
+    """mtbc_c8_pack16 (c8_pack16_kernel) moves 16-bit words whatever they mean: random words, every one compared."""
+    L, lib = ops.L, ops.L.load()
+    Cfull, c0 = (40, 8) if strided else (Cc, 0)
+    x = np.random.default_rng(9 + 7 * N + 3 * Cc + HW).integers(0, 1 << 16, (N, Cfull, HW), dtype=np.uint16)
+    src, y = _LayoutSrc(x), _LayoutDst(N * Cc * HW, torch.int16)
+    L.check(lib.mtbc_c8_pack16(src.t.data_ptr() + 2 * c0 * HW, Cfull * HW, y.view.data_ptr(), N, Cc, HW, ops._s()), "c8_pack16")
+    torch.cuda.synchronize()
+    _same_words("pack16", y.read("pack16"), LR.c8_pack16(x[:, c0:c0 + Cc]))
+    assert src.intact()
+
+
+# ---- the guard
+def _pack_key(kind, Cin, Cout, dgrad, compute, path):
+    """Coverage key of one weight-image op from its arguments: what selects a kernel path (kind, format, single or batched) and the branches
+    inside it (a ragged last row tile, a ragged last K chunk -- for the fp32 forward image of the batched launch: 16 x 16 patches that
+    straddle two row tiles --, one / two / more chunks)."""
+    L = ops.L
+    if kind == L.OP_CONV3_PACK_LP:
+        rows, red = (Cin, Cout) if dgrad else (Cout, Cin)
+        return ("lp", int(bool(dgrad)), compute, rows % 16 != 0, red % 32 != 0, min(3, (red + 31) // 32), path)
+    if kind == L.OP_CONV3_PACK_FWD:
+        return ("fwd", 0, 0, Cout % 16 != 0, (9 * Cin) % 16 != 0, 0, path)
+    assert kind == L.OP_CONV3_PACK_DGRAD, kind
+    return ("dgrad", 1, 0, Cin % 16 != 0, False, 0, path)
+
+
+def _wview_key(Cout, Cin, off, cnt, mode, k_off, K, path):
+    return (mode, off > 0, off + cnt < Cin, bool(mode) and k_off > 0, bool(mode) and k_off + Cout < K, path)
+
+
+def _c8_key(kind, N, Cc, HW, compute, stride):
+    p16 = kind == ops.L.OP_C8_PACK16
+    pieces = N * (Cc // 8) * (HW // 4 if p16 else HW)
+    return ("pack16" if p16 else "pack", 0 if p16 else compute, stride != Cc * HW, pieces % 256 != 0)
+
+
+_DESC_KIND = {0: ("OP_CONV3_PACK_FWD", 0), 1: ("OP_CONV3_PACK_DGRAD", 1), 2: ("OP_CONV3_PACK_LP", 0), 3: ("OP_CONV3_PACK_LP", 1)}
+
+
+def _reference_tested_layout_keys():
+    """The key of every call the layout tests above make, from their tables."""
+    L = ops.L
+    keys = set()
+    for Cout, Cin in PACK_CASES:
+        for k, c in PACK_KINDS:
+            for path in ("single", "many"):
+                keys.add(_pack_key(getattr(L, _DESC_KIND[k][0]), Cin, Cout, _DESC_KIND[k][1], c, path))
+    for case in WVIEW_CASES:
+        keys.add(_wview_key(*case, "single"))
+    for case in WVIEW_CASES + WVIEW_GROUP:
+        keys.add(_wview_key(*case, "many"))
+    for N, Cc, HW, strided in C8_PACK_CASES:
+        keys.update(_c8_key(L.OP_C8_PACK, N, Cc, HW, c, 40 * HW if strided else Cc * HW) for c in (1, 2))
+    for N, Cc, HW, strided in C8_PACK16_CASES:
+        keys.add(_c8_key(L.OP_C8_PACK16, N, Cc, HW, 0, 40 * HW if strided else Cc * HW))
+    return keys
+
+
+_STEP_OP_RECORDS = {}
+
+
+def _step_op_records(arch, dtype, N, size):
+    """Builds (does not run) one step program with bench.py's constructor path, once per session: {program name: [(op kind, arguments)]} of every
+    program the compiled step holds -- arguments as a plain tuple for the weight-image, weight-view and channel-blocking kinds, else None."""
+    if (arch, dtype, N, size) in _STEP_OP_RECORDS:
+        return _STEP_OP_RECORDS[arch, dtype, N, size]
+    import gc
+    from multi_task_breast_cancer_amd.experiment_init import init_multitask_model, init_optimizer
+    from multi_task_breast_cancer_amd.miscellany import seed_everything
+    from multi_task_breast_cancer_amd.trainer import FusedTrainStep
+    L = ops.L
+    seed_everything(1993)
+    model = init_multitask_model(arch, sequences=1, regions=1, n_classes=3, deep_supervision=True).to(DEV)
+    model.set_compute(dtype)
+    step = FusedTrainStep(model, init_optimizer(model, "Adam", 1e-4), alpha=0.5, inversely_weighted=True)
+    st = step._compiled(N, size, size)
+    fields = {"pack": ("Cin", "Cout", "dgrad", "compute"), "wview": ("Cout", "Cin", "ci_off", "ci_cnt", "mode", "k_off", "K"),
+              "c8pack": ("N", "C", "HW", "compute", "src_batch_stride")}
+    rec = {}
+    for name, prog in st.programs.items():
+        rec[name] = []
+        for i in range(getattr(prog, "n", 0)):
+            op = prog.array[i]
+            field = L.OP_UNION_FIELD[op.kind]
+            rec[name].append((op.kind, tuple(getattr(getattr(op.u, field), n) for n in fields[field]) if field in fields else None))
+    del st, step, model, prog, op
+    gc.collect()          # a step and its model refer to each other: their tensors go only with a collection, and the four programs do not fit the device side by side
+    torch.cuda.empty_cache()
+    _STEP_OP_RECORDS[arch, dtype, N, size] = rec
+    return rec
+
+
+def _program_layout_keys(arch, dtype, N, size):
+    """{key: (program, op kind, the op's arguments)} of the weight-image, weight-view and channel-blocking ops of one step.  A pack or view op
+    in a run of more than one inside its program goes through the batched launch (mtbc_program_run_ms): path "many"."""
+    L = ops.L
+    packs, seen = (L.OP_CONV3_PACK_FWD, L.OP_CONV3_PACK_DGRAD, L.OP_CONV3_PACK_LP), {}
+    for pname, oplist in _step_op_records(arch, dtype, N, size).items():
+        kinds = [kind for kind, _ in oplist]
+        for i, (kind, args) in enumerate(oplist):
+            def in_run(family):          # an op of the same family stands next to op i
+                return "many" if (i > 0 and kinds[i - 1] in family) or (i + 1 < len(kinds) and kinds[i + 1] in family) else "single"
+            if kind in packs:
+                Cin, Cout, dgrad, compute = args
+                key = _pack_key(kind, Cin, Cout, dgrad, compute if kind == L.OP_CONV3_PACK_LP else 0, in_run(packs))
+            elif kind == L.OP_CONV3_WVIEW:
+                key = _wview_key(*args, in_run((L.OP_CONV3_WVIEW,)))
+            elif kind in (L.OP_C8_PACK, L.OP_C8_PACK16):
+                key = _c8_key(kind, *args)
+            else:
+                continue
+            seen.setdefault(key, (pname, kind, args))
+    return seen
+
+
+def test_step_programs_launch_only_reference_tested_layout_ops():
+    """Builds (does not run) the benchmark's four step programs and computes the coverage key of every weight-image, weight-view and
+    channel-blocking op in every program of the step (the views and images sit in the "pack" program): each must be the key of a call that the
+    layout tests above make.  _pack_key / _wview_key / _c8_key, the case tables and _reference_tested_layout_keys are the places to edit.
+    A missing key is named with its op's arguments: (Cin, Cout, dgrad, compute) of an image, (Cout, Cin, off, cnt, mode, k_off, K) of a view,
+    (N, C, HW, compute, src_batch_stride) of a channel-blocking op."""
+    tested = _reference_tested_layout_keys()
+    missing, total = {}, set()
+    for arch, dtype, N, size in STEP_PROGRAMS:
+        seen = _program_layout_keys(arch, dtype, N, size)
+        print(f"{arch} {dtype} N={N} {size}x{size}: {len(seen)} keys")
+        assert seen, f"{arch} {dtype}: no weight image found"
+        for key, (pname, kind, args) in sorted(seen.items(), key=repr):
+            print(f"  {pname}: op {kind} {key} at {args}")
+            total.add(key)
+            if key not in tested:
+                missing.setdefault((arch, dtype, N, size), []).append((kind, key, args))
+    print(f"{len(total)} distinct keys in the four programs, {len(tested)} tested")
+    assert not missing, "layout launches of the step programs that no bit-for-bit reference case makes: " + \
+        "".join(f"\n  {p_}: op {kind} {k} at {s}" for p_, ks in missing.items() for kind, k, s in ks)
+
+
+# ---- the loss mix
+def test_loss_mix_is_the_written_fp32_expression_and_flags_nan():
+    """mtbc_loss_mix, launched in every step: out4 == (alpha * s + (1 - alpha) * c, s, c, flag) with the first element formed in fp32 as
+    written (two products and a sum, each rounded), flag 1 for a NaN in either input and 0 for infinities.  (With the sum contracted into an
+    fma the second launch below answers 0x3ec4109d for 0x3ec4109e.)"""
+    L, lib = ops.L, ops.L.load()
+    f = np.float32
+    nan, inf = float("nan"), float("inf")
+    for s, c, alpha in ((0.7312345, 1.0986123, 0.3), (0.1234567, 2.7182817, 0.9), (3.1415927, 0.5772157, 0.7), (nan, 1.5, 0.5), (0.25, nan, 0.5),
+                        (inf, 1.5, 0.5), (0.25, -inf, 0.25)):
+        seg, cls = torch.tensor([s], dtype=torch.float32, device=DEV), torch.tensor([c], dtype=torch.float32, device=DEV)
+        out = _LayoutDst(4, torch.float32)
+        L.check(lib.mtbc_loss_mix(seg.data_ptr(), cls.data_ptr(), alpha, out.view.data_ptr(), ops._s()), "loss_mix")
+        torch.cuda.synchronize()
+        got = out.read("out4").view(np.float32)
+        with np.errstate(invalid="ignore"):
+            mix = f(f(alpha) * f(s)) + f((f(1.0) - f(alpha)) * f(c))
+        want = np.array([mix, s, c, 1.0 if (s != s or c != c) else 0.0], dtype=np.float32)
+        print(f"loss_mix({s}, {c}, {alpha}): device {got.tolist()} ({hex(int(got.view(np.uint32)[0]))}), as written {float(mix)!r} ({hex(int(want.view(np.uint32)[0]))})")
+        assert np.array_equal(np.isnan(got), np.isnan(want)), (got, want)
+        ok = ~np.isnan(want)
+        assert np.array_equal(got.view(np.uint32)[ok], want.view(np.uint32)[ok]), (s, c, alpha, got.tolist(), want.tolist())
+
+
+# ---- every op kind of the step programs has a test that answers for it
+_THIS = "tests/test_ops_gpu.py"
+_LAYOUT_GUARD = (_THIS, "test_step_programs_launch_only_reference_tested_layout_ops")
+_SMALL_GUARD = (_THIS, "test_step_programs_launch_only_reference_tested_small_op_instances")
+_CONV3_GUARD = (_THIS, "test_step_programs_launch_only_reference_tested_conv3x3_instances")
+_INORM_GUARD = (_THIS, "test_step_programs_launch_only_reference_tested_instnorm_instances")
+_CONVT_GUARD = (_THIS, "test_step_programs_launch_only_reference_tested_convT_instances")
+_STREAMS = (_THIS, "test_program_run_on_two_streams_orders_a_forked_section")
+# op kind -> (file, test): the reference test, or the guard that ties every launch of the kind to a reference case
+OP_KIND_COVERED_BY = {
+    "OP_CONV3_FWD": _CONV3_GUARD, "OP_CONV3_DGRAD": _CONV3_GUARD, "OP_CONV3_WGRAD": _CONV3_GUARD,
+    "OP_CONV3_PACK_FWD": _LAYOUT_GUARD, "OP_CONV3_PACK_DGRAD": _LAYOUT_GUARD, "OP_CONV3_PACK_LP": _LAYOUT_GUARD, "OP_CONV3_WVIEW": _LAYOUT_GUARD,
+    "OP_C8_PACK": _LAYOUT_GUARD, "OP_C8_PACK16": _LAYOUT_GUARD,
+    "OP_IN_FWD": _INORM_GUARD, "OP_IN_BWD": _INORM_GUARD, "OP_IN_DPARAM": _INORM_GUARD,
+    "OP_CONVT_FWD": _CONVT_GUARD, "OP_CONVT_DGRAD": _CONVT_GUARD, "OP_CONVT_WGRAD": _CONVT_GUARD,
+    "OP_POOL_FWD": _SMALL_GUARD, "OP_POOL_BWD": _SMALL_GUARD, "OP_CONV1_FWD": _SMALL_GUARD, "OP_CONV1_DGRAD": _SMALL_GUARD, "OP_CONV1_WGRAD": _SMALL_GUARD,
+    "OP_GAP_FWD": _SMALL_GUARD, "OP_GAP_BWD": _SMALL_GUARD, "OP_LINEAR_FWD": _SMALL_GUARD, "OP_LINEAR_BWD": _SMALL_GUARD,
+    "OP_HEAD_COMBINE": _SMALL_GUARD, "OP_HEAD_EXPAND": _SMALL_GUARD,
+    "OP_DICE_FWD": (_THIS, "test_dice_multihead_matches_oracle"), "OP_DICE_BWD": (_THIS, "test_dice_multihead_matches_oracle"),
+    "OP_FOCAL": (_THIS, "test_focal_matches_reference_goldens"),
+    "OP_LOSS_MIX": (_THIS, "test_loss_mix_is_the_written_fp32_expression_and_flags_nan"),
+    "OP_OPTIM": ("tests/test_fused_optim_gpu.py", "test_kernel_is_the_host_function_bit_for_bit"), "OP_DICE_COUNTS": (_THIS, "test_dice_counts_exact"),
+    "OP_MEMSET": (_THIS, "test_memset_op_zeroes_exactly_its_bytes"),
+    "OP_SET_STREAM": _STREAMS, "OP_EVENT_RECORD": _STREAMS, "OP_EVENT_WAIT": _STREAMS,
+}
+
+
+def test_memset_op_zeroes_exactly_its_bytes():
+    """MTBC_OP_MEMSET through mtbc_program_run: the bytes asked for become zero, the guards and the tail keep their pre-fill."""
+    import ctypes as C
+    from multi_task_breast_cancer_amd.engine import _mk
+    L = ops.L
+    dst = _LayoutDst(300, torch.float32)
+    op = _mk(L.OP_MEMSET)
+    op.u.memset0.ptr, op.u.memset0.bytes = dst.view.data_ptr(), 4 * 260
+    arr, failed = (L.Op * 1)(op), C.c_int32(-1)
+    L.check(L.load().mtbc_program_run(arr, 0, 1, ops._s(), C.byref(failed)), "program_run")
+    torch.cuda.synchronize()
+    got = dst.read("memset").view(np.float32)
+    assert not got[:260].any() and bool((got[260:] == _MARK[torch.float32]).all())
+
+
+def test_every_op_kind_of_the_step_programs_is_claimed_by_a_test():
+    """Builds (does not run) the four step programs and collects every op kind present: each must have an entry in OP_KIND_COVERED_BY, and the
+    test or guard it names must exist in the file it names.  A new op kind in a program without an entry fails here."""
+    import os
+    L = ops.L
+    name_of = {getattr(L, n): n for n in dir(L) if n.startswith("OP_") and isinstance(getattr(L, n), int)}
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for name, (path, test) in OP_KIND_COVERED_BY.items():
+        assert name in name_of.values(), f"{name} is no op kind"
+        text = open(os.path.join(root, path)).read()
+        assert re.search(rf"^def {test}\(", text, re.M), f"{name}: {path} has no {test}"
+    present = set()
+    for arch, dtype, N, size in STEP_PROGRAMS:
+        kinds = {kind for oplist in _step_op_records(arch, dtype, N, size).values() for kind, _ in oplist}
+        print(f"{arch} {dtype} N={N} {size}x{size}: {sorted(name_of[k] for k in kinds)}")
+        present |= kinds
+    unclaimed = sorted(name_of.get(k, str(k)) for k in present if name_of.get(k) not in OP_KIND_COVERED_BY)
+    print(f"{len(present)} op kinds in the four programs, {len(OP_KIND_COVERED_BY)} claimed")
+    assert not unclaimed, f"op kinds of the step programs that no test answers for: {unclaimed}"
