@@ -1,0 +1,319 @@
+"""The benchmark's step programs, surveyed once per session for the launch-coverage guards of tests/test_ops_gpu.py
+(test_step_programs_launch_only_reference_tested_*): build_step is the one copy of bench.py's constructor path, survey walks the programs of a
+built step once and keeps plain values, the collectors and the key functions say per op family what "the same launch" means, and
+assert_all_tested compares what a survey saw with what the reference cases make.  No test module: pytest does not collect it."""
+import collections
+import gc
+import re
+
+import torch
+
+from multi_task_breast_cancer_amd import ops
+
+L = ops.L
+DEV = "cuda:0"
+
+# the benchmark's step programs (bench.py run_mode): (arch, dtype, N, size) of BASELINE.json configs[1], configs[4] (its per-GPU shape),
+# configs[2], and the fp32 parity mode
+STEP_PROGRAMS = [("MTUNetPlusPlus", "bf16", 32, 256), ("MTUNetPlusPlus", "f16", 16, 512), ("MTnnUNet", "bf16", 64, 256), ("MTUNetPlusPlus", "f32", 32, 256)]
+
+
+def build_step(arch, dtype, N, size, reserve_cus=0):
+    """Builds (does not run) one step program with bench.py's constructor path: (the compiled step, what must stay referenced beside it)."""
+    from multi_task_breast_cancer_amd.experiment_init import init_multitask_model, init_optimizer
+    from multi_task_breast_cancer_amd.miscellany import seed_everything
+    from multi_task_breast_cancer_amd.trainer import FusedTrainStep
+    seed_everything(1993)
+    model = init_multitask_model(arch, sequences=1, regions=1, n_classes=3, deep_supervision=True).to(DEV)
+    model.set_compute(dtype)
+    model.coop_reserve_cus = reserve_cus          # what a data-parallel FusedTrainStep sets (trainer.py)
+    step = FusedTrainStep(model, init_optimizer(model, "Adam", 1e-4), alpha=0.5, inversely_weighted=True)
+    return step._compiled(N, size, size), (step, model)
+
+
+# ------------------------------------------------------------------ the key functions: the only places that decide what "the same launch" means
+def _instnorm_key(a, backward):
+    """Coverage key of ONE mtbc_instnorm_lrelu_fwd / _bwd call: the launches mtbc_instnorm_kernel_name plans (kernel instances, block sizes,
+    team size T; the number of rounds only as 1 or >1) + the branches the ARGUMENTS select inside those kernels.  The only place that
+    decides what "the same launch" means for the guard below."""
+    name = re.sub(r"rounds=(\d+)", lambda m: "rounds=1" if m.group(1) == "1" else "rounds>1", ops.instnorm_kernel_name(a, backward))
+    c8 = bool(a.dz8 if backward else a.y8)
+    f = []
+    if a.gamma and a.beta:
+        f.append("affine")
+    else:
+        f += [n for n in ("gamma", "beta") if getattr(a, n)]
+    if not backward:
+        if a.y16:                             # (beside y8: the 16-bit planes of the streaming pass; without y8: norm.hip in_fwd_reg_kernel `if (p.y16)`, in_cvt4)
+            f.append("y16")
+        if c8:
+            f += [n for n in ("pool_y8", "pool_arg") if getattr(a, n)]
+            if a.y and not a.y16:             # (norm_coop.hip fill_coop: `if (p->y16) p->y = nullptr`)
+                f.append("y")
+        # without y8: `y` is the output itself when y16 is NULL, and no kernel of norm.hip reads pool_y8 / pool_arg (norm.hip fill() copies neither into InP)
+        return name, tuple(f)
+    if not a.dy:
+        f.append("dy=NULL")
+    if a.n_dy_extra:
+        f.append(f"dy_extra={a.n_dy_extra}")
+    if a.dy_rank1:
+        f.append("rank1")
+        if a.dy_rank1_dw:
+            f.append("rank1_dw")
+            f += ["rank1_acc"] if a.dy_rank1_accumulate else []       # (read by in_r1_finalize_kernel only)
+            f += [] if a.dy_rank1_db else ["rank1_db=NULL"]
+    if a.dy_pool:
+        f.append("dy_pool")
+    f += [n for n in ("dgamma", "dbeta", "dbias_pre") if getattr(a, n)]
+    if a.accumulate_dparams and (a.dgamma or a.dbeta or a.dbias_pre) and not a.defer_dparams:
+        f.append("acc")                       # (with defer_dparams the flag is read by the MTBC_OP_IN_DPARAM descriptor only: _dparam_key)
+    if a.defer_dparams:
+        f.append("defer")
+    if a.dz16 and not a.dz8:                  # (norm.hip in_bwd_reg_kernel `if (p.dz16)`, in_cvt4; with dz8 norm_coop.hip fill_coop never copies a->dz16 into CoP)
+        f.append("dz16")
+    # dz in place over dy: only the fp32 kernels of norm.hip write `dz` (norm_coop.hip fill_coop never copies a->dz into CoP; with dz16
+    # norm.hip in_bwd_reg_kernel stores through p.dz16 and never through d4)
+    if a.dz and a.dz == a.dy and not a.dz8 and not a.dz16:
+        f.append("inplace")
+    return name, tuple(f)
+
+
+def _dparam_key(d):
+    """Coverage key of one descriptor of mtbc_instnorm_dparam_many (MTBC_OP_IN_DPARAM: the deferred parameter-gradient reduction)."""
+    return "in_dparam_many_kernel", tuple([n for n in ("dgamma", "dbeta", "dbias_pre") if getattr(d, n)] + [f"T={d.T}"] + (["acc"] if d.accumulate else []))
+
+
+def _convT_key(a, op, nxt=None):
+    """Coverage key of ONE mtbc_convT_fwd / _dgrad / _wgrad call, or of a program's WGRAD + DGRAD pair (nxt = the DGRAD's arguments): the
+    launches mtbc_convT_kernel_name plans + the branches the ARGUMENTS select inside those kernels -- bias / dbias, the accumulate flags,
+    which tensors are channel-range views of wider buffers (a batch stride above dense), and Cout = 1 for the generic GEMM kernels (what the
+    fused deep-supervision heads launch: a 4-, 16- or 64-row M with one output plane).  The only place that decides what "the same launch" means
+    for the guard below."""
+    L = ops.L
+    name = ops.convT_kernel_name(a, op, nxt)
+    plane, up = a.H * a.W, a.H * a.W * a.k * a.k
+    dense = dict(x=a.Cin * plane, y=a.Cout * up, dy=a.Cout * up, dx=a.Cin * plane)
+    f = []
+
+    def views(s, *names):
+        f.extend(f"{n}_strided" for n in names if getattr(s, n + "_batch_stride") != dense[n])
+
+    if op == L.OP_CONVT_FWD:
+        f += ["bias"] if a.bias else []
+        views(a, "x", "y")
+    elif op == L.OP_CONVT_DGRAD:
+        f += ["acc_dx"] if a.accumulate_dx else []
+        views(a, "dy", "dx")
+    else:
+        f += ["dbias"] if a.dbias else []
+        f += ["acc_dw"] if a.accumulate_dw else []
+        views(a, "x", "dy")
+        if nxt is not None:
+            f += ["acc_dx"] if nxt.accumulate_dx else []
+            views(nxt, "dx")
+    if re.search(r"\bconvT_(fwd|dgrad|wgrad)_kernel<", name) and a.Cout == 1:
+        f.append("Cout=1")
+    return name, tuple(f)
+
+
+def _same_upconv(wg, dg):
+    """The DGRAD behind a WGRAD belongs to the same up-convolution (engine.StepPlan.convT emits the two back to back)."""
+    return all(getattr(wg, n) == getattr(dg, n) for n in ("N", "H", "W", "Cin", "Cout", "k", "dy", "w"))
+
+
+def _small_op_key(op):
+    """Coverage key of ONE small op (ops.SMALL_OPS): the launches mtbc_op_kernel_name plans + the branches the ARGUMENTS select inside those
+    kernels -- which tensors are channel-range views of wider buffers (a batch stride above dense), argmax, bias / dbias, every accumulate
+    flag, dx present, and Cout > 8 (a second channel group in the planar 1x1 kernels).  The only place that decides what "the same launch"
+    means for the guard below."""
+    L = ops.L
+    name, k, f = ops.op_kernel_name(op), op.kind, []
+
+    def views(a, dense, *names):
+        f.extend(f"{n}_strided" for n in names if getattr(a, n + "_batch_stride") != dense[n])
+
+    if k in (L.OP_POOL_FWD, L.OP_POOL_BWD):
+        a = op.u.pool
+        full = a.C * a.H * a.W
+        dense = dict(x=full, y=full // 4, dy=full // 4, dx=full)
+        if k == L.OP_POOL_FWD:
+            views(a, dense, "x", "y")
+            f += ["argmax"] if a.argmax else []
+        else:
+            views(a, dense, "x", "dy", "dx")
+            f += ["acc_dx"] if a.accumulate_dx else []
+    elif k in (L.OP_CONV1_FWD, L.OP_CONV1_DGRAD, L.OP_CONV1_WGRAD):
+        a = op.u.conv1
+        dense = dict(x=a.Cin * a.H * a.W, dx=a.Cin * a.H * a.W)
+        if k == L.OP_CONV1_FWD:
+            views(a, dense, "x")
+            f += ["bias"] if a.bias else []
+        elif k == L.OP_CONV1_DGRAD:
+            views(a, dense, "dx")
+            f += ["acc_dx"] if a.accumulate_dx else []
+        else:
+            views(a, dense, "x")
+            f += ["dbias"] if a.dbias else []
+            f += ["acc_dw"] if a.accumulate_dw else []
+        f += ["Cout>8"] if a.Cout > 8 else []
+    elif k == L.OP_LINEAR_FWD:
+        f += [n for n in ("relu", "bias") if getattr(op.u.linear, n)]
+    elif k == L.OP_LINEAR_BWD:
+        a = op.u.linear
+        f += [n for n in ("relu", "dx", "dbias") if getattr(a, n)]
+        f += ["acc_dw"] if a.accumulate_dw else []
+    elif k == L.OP_HEAD_COMBINE:
+        f += [n for n in ("bT", "b1") if getattr(op.u.head, n)]
+    elif k == L.OP_HEAD_EXPAND:
+        f += [n for n in ("bT", "dbT", "db1", "acc_wT", "acc_bT", "acc_w1", "acc_b1") if getattr(op.u.head, n)]
+    else:
+        assert k in (L.OP_GAP_FWD, L.OP_GAP_BWD), k          # (GAP: dense tensors, no flag)
+    return name, tuple(f)
+
+
+def _pack_key(kind, Cin, Cout, dgrad, compute, path):
+    """Coverage key of one weight-image op from its arguments: what selects a kernel path (kind, format, single or batched) and the branches
+    inside it (a ragged last row tile, a ragged last K chunk -- for the fp32 forward image of the batched launch: 16 x 16 patches that
+    straddle two row tiles --, one / two / more chunks)."""
+    L = ops.L
+    if kind == L.OP_CONV3_PACK_LP:
+        rows, red = (Cin, Cout) if dgrad else (Cout, Cin)
+        return ("lp", int(bool(dgrad)), compute, rows % 16 != 0, red % 32 != 0, min(3, (red + 31) // 32), path)
+    if kind == L.OP_CONV3_PACK_FWD:
+        return ("fwd", 0, 0, Cout % 16 != 0, (9 * Cin) % 16 != 0, 0, path)
+    assert kind == L.OP_CONV3_PACK_DGRAD, kind
+    return ("dgrad", 1, 0, Cin % 16 != 0, False, 0, path)
+
+
+def _wview_key(Cout, Cin, off, cnt, mode, k_off, K, path):
+    return (mode, off > 0, off + cnt < Cin, bool(mode) and k_off > 0, bool(mode) and k_off + Cout < K, path)
+
+
+def _c8_key(kind, N, Cc, HW, compute, stride):
+    p16 = kind == ops.L.OP_C8_PACK16
+    pieces = N * (Cc // 8) * (HW // 4 if p16 else HW)
+    return ("pack16" if p16 else "pack", 0 if p16 else compute, stride != Cc * HW, pieces % 256 != 0)
+
+
+# ------------------------------------------------------------------ the collectors: (a program's ops, an index) -> None, or
+# (ops consumed, kind label, key, where); `where` is the shape or argument tuple a failure message names the op by
+def _fields(s, *names):
+    return tuple(getattr(s, n) for n in names)
+
+
+def collect_conv3x3(prog, i):
+    op = prog[i]
+    if op.kind in (L.OP_CONV3_FWD, L.OP_CONV3_DGRAD, L.OP_CONV3_WGRAD):
+        # kernel instance only: the split-K reductions behind the weight gradients are one kernel, checked with all of them
+        return 1, op.kind, ops.conv3x3_kernel_name(op.u.conv3, op.kind).split(" + ")[0], _fields(op.u.conv3, "N", "Cin", "Cout", "H", "W")
+
+
+def collect_instnorm(prog, i):
+    op = prog[i]
+    if op.kind in (L.OP_IN_FWD, L.OP_IN_BWD):
+        return 1, op.kind, (op.kind, _instnorm_key(op.u.inorm, op.kind == L.OP_IN_BWD)), _fields(op.u.inorm, "N", "C", "H", "W")
+    if op.kind == L.OP_IN_DPARAM:
+        return 1, op.kind, (op.kind, _dparam_key(op.u.dparam)), _fields(op.u.dparam, "N", "C")
+
+
+_CONVT_KINDS = {L.OP_CONVT_FWD: "fwd", L.OP_CONVT_DGRAD: "dgrad", L.OP_CONVT_WGRAD: "wgrad"}
+
+
+def collect_convT(prog, i):
+    """kind "pair" = an OP_CONVT_WGRAD with the OP_CONVT_DGRAD of the same problem right behind it in the same program, which is what the
+    program runner looks at: one entry for both ops."""
+    op = prog[i]
+    if op.kind in _CONVT_KINDS:
+        a = op.u.convT
+        shape = _fields(a, "N", "Cin", "Cout", "H", "W", "k")
+        nxt = prog[i + 1] if i + 1 < len(prog) else None
+        if op.kind == L.OP_CONVT_WGRAD and nxt is not None and nxt.kind == L.OP_CONVT_DGRAD and _same_upconv(a, nxt.u.convT):
+            return 2, "pair", ("pair", _convT_key(a, op.kind, nxt.u.convT)), shape
+        return 1, _CONVT_KINDS[op.kind], (_CONVT_KINDS[op.kind], _convT_key(a, op.kind)), shape
+
+
+_SMALL_SHAPE = {"pool": ("N", "C", "H", "W"), "conv1": ("N", "Cin", "Cout", "H", "W"), "gap": ("N", "C", "H", "W"), "linear": ("N", "In", "Out"),
+                "head": ("Cin", "Cmid", "R", "k")}
+
+
+def collect_small_op(prog, i):
+    op = prog[i]
+    if op.kind in ops.SMALL_OPS:
+        field = L.OP_UNION_FIELD[op.kind]
+        return 1, op.kind, (op.kind, _small_op_key(op)), _fields(getattr(op.u, field), *_SMALL_SHAPE[field])
+
+
+_PACKS = (L.OP_CONV3_PACK_FWD, L.OP_CONV3_PACK_DGRAD, L.OP_CONV3_PACK_LP)
+
+
+def collect_layout(prog, i):
+    """The weight-image, weight-view and channel-blocking ops; where = (Cin, Cout, dgrad, compute) of an image, (Cout, Cin, off, cnt, mode,
+    k_off, K) of a view, (N, C, HW, compute, src_batch_stride) of a channel-blocking op.  A pack or view op in a run of more than one inside
+    its program goes through the batched launch (mtbc_program_run_ms): path "many"."""
+    kind = prog[i].kind
+
+    def in_run(family):          # an op of the same family stands next to op i
+        return "many" if (i > 0 and prog[i - 1].kind in family) or (i + 1 < len(prog) and prog[i + 1].kind in family) else "single"
+
+    if kind in _PACKS:
+        args = Cin, Cout, dgrad, compute = _fields(prog[i].u.pack, "Cin", "Cout", "dgrad", "compute")
+        return 1, kind, _pack_key(kind, Cin, Cout, dgrad, compute if kind == L.OP_CONV3_PACK_LP else 0, in_run(_PACKS)), args
+    if kind == L.OP_CONV3_WVIEW:
+        args = _fields(prog[i].u.wview, "Cout", "Cin", "ci_off", "ci_cnt", "mode", "k_off", "K")
+        return 1, kind, _wview_key(*args, in_run((L.OP_CONV3_WVIEW,))), args
+    if kind in (L.OP_C8_PACK, L.OP_C8_PACK16):
+        args = _fields(prog[i].u.c8pack, "N", "C", "HW", "compute", "src_batch_stride")
+        return 1, kind, _c8_key(kind, *args), args
+
+
+COLLECTORS = {"conv3x3": collect_conv3x3, "InstanceNorm": collect_instnorm, "transposed-convolution": collect_convT, "small-op": collect_small_op,
+              "layout": collect_layout}
+
+# program: (arch, dtype, N, size); kinds: {program name: [op kind]}; seen: {family: {key: (kind label, where) of the first op that has it}}
+Survey = collections.namedtuple("Survey", "program reserve_cus kinds seen")
+_SURVEYS = {}
+
+
+def survey(program, reserve_cus=0, collectors=COLLECTORS, build=build_step):
+    """The Survey of one step program, built (not run) once per session: the first call for a (program, reserve_cus) builds the step, hands
+    the ops of each of its programs to every collector and keeps plain values only, so that the step and its model can go before the next
+    one is built -- the four programs do not fit the device side by side.  Later calls get that result, whatever collectors and build they
+    name: the guards all take the defaults; `build` is there for a test to hand in a program of its own."""
+    if (program, reserve_cus) in _SURVEYS:
+        return _SURVEYS[program, reserve_cus]
+    st, keep = build(*program, reserve_cus)
+    kinds, seen, p, prog = {}, {family: {} for family in collectors}, None, None
+    for name, p in st.programs.items():
+        prog = [p.array[i] for i in range(getattr(p, "n", 0))]
+        kinds[name] = [op.kind for op in prog]
+        for family, collect in collectors.items():
+            i = 0
+            while i < len(prog):
+                hit = collect(prog, i)
+                if hit:
+                    used, kind, key, where = hit
+                    seen[family].setdefault(key, (kind, where))
+                i += used if hit else 1
+    del st, keep, p, prog
+    gc.collect()          # a step and its model refer to each other: their tensors go only with a collection
+    torch.cuda.empty_cache()
+    _SURVEYS[program, reserve_cus] = Survey(program, reserve_cus, kinds, seen)
+    return _SURVEYS[program, reserve_cus]
+
+
+def assert_all_tested(family, tested, surveys, required=()):
+    """Every key the surveys saw of the family must be in `tested`, and every program must hold a launch of the family and of each kind label
+    in `required`.  A missing key is named with its program, kind label and where."""
+    missing, total = [], set()
+    for s in surveys:
+        seen, prog = s.seen[family], s.program + ((f"reserve {s.reserve_cus}",) if s.reserve_cus else ())
+        print(f"{prog}: {len(seen)} keys")
+        absent = set(required) - {kind for kind, _ in seen.values()}
+        assert seen and not absent, f"{prog}: no {family} launch found" + (f" of kind {sorted(absent, key=repr)}" if absent else "")
+        for key, (kind, where) in sorted(seen.items(), key=repr):
+            print(f"  {kind} {key} at {where}")
+            total.add(key)
+            if key not in tested:
+                missing.append(f"\n  {prog}: {kind} {key} at {where}")
+    print(f"{len(total)} distinct keys in the {len(surveys)} programs, {len(tested)} keys tested")
+    assert not missing, f"{family} launches of the step programs that no reference case makes:" + "".join(missing)

@@ -11,6 +11,8 @@ pytestmark = pytest.mark.gpu
 
 from multi_task_breast_cancer_amd import ops  # noqa: E402
 from oracle import torch_oracle as O  # noqa: E402
+from step_programs import (STEP_PROGRAMS, _c8_key, _convT_key, _dparam_key, _instnorm_key, _pack_key, _small_op_key,  # noqa: E402
+                           _wview_key, assert_all_tested, survey)
 
 DEV = "cuda:0"
 
@@ -524,10 +526,13 @@ def test_conv3x3_wgrad_c8_in_kernel_split_k_reduction(N, segs, Cout, H, W, compu
     assert int(sync.abs().sum().item()) == 0, "counters not back at zero"
 
 
+EXTRA16_CASES = [(2, [24, 24, 24, 24, 24, 24], 24, 256, 256),   # 144->24 @256x256: the bench's widest level-0 node
+                 (1, [384, 384, 384], 512, 16, 16),             # K = 1152 x 9: the longest accumulation of the step
+                 (16, [24, 24], 24, 256, 256)]                  # enough 16 x 32 tiles for the 8-wave (512-pixel) blocks
+
+
 @pytest.mark.parametrize("compute", [1, 2])
-@pytest.mark.parametrize("N,segs,Cout,H,W", C8_CASES + [(2, [24, 24, 24, 24, 24, 24], 24, 256, 256),   # 144->24 @256x256: the bench's widest level-0 node
-                                                        (1, [384, 384, 384], 512, 16, 16),                 # K = 1152 x 9: the longest accumulation of the step
-                                                        (16, [24, 24], 24, 256, 256)])                     # enough 16 x 32 tiles for the 8-wave (512-pixel) blocks
+@pytest.mark.parametrize("N,segs,Cout,H,W", C8_CASES + EXTRA16_CASES)
 def test_conv3x3_16bit_fwd_dgrad_match_fp64_on_rounded_operands(N, segs, Cout, H, W, compute):
     """The oracle of the 16-bit forward / dgrad kernels (channel-blocked AND planar staging): fp64 conv2d / conv2d_input
     on operands rounded (RNE) to the MFMA's 16-bit type -- x and w forward, dz and w backward -- i.e. exact products,
@@ -927,7 +932,10 @@ def test_gathered_dgrad_prepares_the_instnorm_backward(N, K, C, H, W, affine, ex
         assert torch.allclose(dba, dbb, rtol=1e-4, atol=1e-3 * max(1.0, dba.abs().max().item()))
 
 
-@pytest.mark.parametrize("N,segs,Cout,H,W", [(2, [24], 24, 256, 256), (2, [48], 48, 128, 128), (3, [96], 96, 64, 64), (2, [96, 96], 96, 16, 16), (5, [32], 80, 8, 8)])
+BF16_OUT_FP16_CASES = [(2, [24], 24, 256, 256), (2, [48], 48, 128, 128), (3, [96], 96, 64, 64), (2, [96, 96], 96, 16, 16), (5, [32], 80, 8, 8)]
+
+
+@pytest.mark.parametrize("N,segs,Cout,H,W", BF16_OUT_FP16_CASES)
 def test_bf16_mode_conv_output_stored_as_fp16(N, segs, Cout, H, W):
     """out_type = 2 / z_type = 2: in the bf16 mode the conv output z is stored as fp16 (same 2 bytes, 11 significant bits,
     saturated at +-65504) while the MFMA operands and the activation stay bf16: the stored tensor = the fp32 planar result of the
@@ -1044,8 +1052,11 @@ def test_instnorm_backward_adds_a_second_planar_gradient(N, C, H, W):
     assert bool(((ua - ub).abs() <= 2.0 ** -7 * ua.abs() + 2e-6 * ua.abs().max()).all()), (ua - ub).abs().max().item()
 
 
+STEM16_CASES = [(2, 24, 256, 256), (3, 32, 40, 24), (1, 8, 8, 12), (2, 24, 96, 96)]          # (N, Cout, H, W)
+
+
 @pytest.mark.parametrize("compute,out_fp16", [(1, True), (1, False), (2, False)])
-@pytest.mark.parametrize("N,Cout,H,W", [(2, 24, 256, 256), (3, 32, 40, 24), (1, 8, 8, 12), (2, 24, 96, 96)])
+@pytest.mark.parametrize("N,Cout,H,W", STEM16_CASES)
 def test_stem_conv_on_the_16bit_path(N, Cout, H, W, compute, out_fp16):
     """The 1-channel stem in the 16-bit modes: fp32 operands and the stem kernel's fmaf order, output channel-blocked 16-bit
     (= the fp32 stem output, clamped for fp16 storage, rounded once) + InstanceNorm statistics of the stored values; its weight
@@ -1383,140 +1394,33 @@ def _reference_tested_instances():
         calls += [(op, case[:5], kw) for op, kw in _bench_case_calls(*case)]
     for case in CONV_CASES:                                      # test_conv3x3_mfma_fwd_dgrad_wgrad (fp32)
         calls += [(F_, case, {}), (D_, case, {}), (W_, case, {}), (W_, case, dict(bias=False))]
-    extra16 = [(2, [24, 24, 24, 24, 24, 24], 24, 256, 256), (1, [384, 384, 384], 512, 16, 16), (16, [24, 24], 24, 256, 256)]
     for compute in (1, 2):
         m = dict(compute=compute, c8=True)
         for case in C8_CASES:                                    # test_conv3x3_c8_operands
             calls += [(F_, case, m), (D_, case, m), (W_, case, dict(m, in_kernel_reduce=True)), (W_, case, dict(m, bias=False, in_kernel_reduce=True))]
-        for case in C8_CASES + extra16:                          # test_conv3x3_16bit_fwd_dgrad_match_fp64_on_rounded_operands
+        for case in C8_CASES + EXTRA16_CASES:                    # test_conv3x3_16bit_fwd_dgrad_match_fp64_on_rounded_operands
             calls += [(F_, case, m), (D_, case, m), (F_, case, dict(compute=compute)), (D_, case, dict(compute=compute))]
         for case in C8W_CASES + C8I_CASES:                       # test_conv3x3_wgrad_c8_wide_blocks
             calls += [(W_, case, dict(m, in_kernel_reduce=True)), (W_, case, dict(m, bias=False, in_kernel_reduce=True))]
         for case in FIXUP_CASES:                                 # test_conv3x3_wgrad_c8_in_kernel_split_k_reduction
             calls += [(W_, case, dict(m, in_kernel_reduce=r)) for r in (True, False)]
-        for N, Cout, H, W in [(2, 24, 256, 256), (3, 32, 40, 24), (1, 8, 8, 12), (2, 24, 96, 96)]:     # test_stem_conv_on_the_16bit_path
+        for N, Cout, H, W in STEM16_CASES:                       # test_stem_conv_on_the_16bit_path
             for out_fp16 in ((True, False) if compute == 1 else (False,)):
                 calls.append((F_, (N, [1], Cout, H, W), dict(m, out_c8=True, out_fp16=out_fp16, bias=True)))
             calls.append((W_, (N, [1], Cout, H, W), dict(m, bias=False, in_kernel_reduce=True)))
-    for case in [(2, [24], 24, 256, 256), (2, [48], 48, 128, 128), (3, [96], 96, 64, 64), (2, [96, 96], 96, 16, 16), (5, [32], 80, 8, 8)]:
+    for case in BF16_OUT_FP16_CASES:
         calls.append((F_, case, dict(compute=1, c8=True, out_c8=True, out_fp16=True)))      # test_bf16_mode_conv_output_stored_as_fp16
     return {ops.conv3x3_case_kernel(op, *case, **kw).split(" + ")[0] for op, case, kw in calls}
 
 
-# the benchmark's step programs (bench.py run_mode): (arch, dtype, N, size) of BASELINE.json configs[1], configs[4] (its per-GPU shape),
-# configs[2], and the fp32 parity mode
-STEP_PROGRAMS = [("MTUNetPlusPlus", "bf16", 32, 256), ("MTUNetPlusPlus", "f16", 16, 512), ("MTnnUNet", "bf16", 64, 256), ("MTUNetPlusPlus", "f32", 32, 256)]
-
-
 def test_step_programs_launch_only_reference_tested_conv3x3_instances():
-    """Builds (does not run) the step programs of the benchmark's configurations with bench.py's constructor path and asks
-    mtbc_conv3x3_kernel_name for the instance of every 3x3 conv launch: each must be one an element-wise reference test of this
-    file launches.  A new dispatch path that no reference test reaches fails here."""
-    from multi_task_breast_cancer_amd.experiment_init import init_multitask_model, init_optimizer
-    from multi_task_breast_cancer_amd.miscellany import seed_everything
-    from multi_task_breast_cancer_amd.trainer import FusedTrainStep
-    L = ops.L
-    tested = _reference_tested_instances()
-    missing = {}
-    for arch, dtype, N, size in STEP_PROGRAMS:
-        seed_everything(1993)
-        model = init_multitask_model(arch, sequences=1, regions=1, n_classes=3, deep_supervision=True).to(DEV)
-        model.set_compute(dtype)
-        step = FusedTrainStep(model, init_optimizer(model, "Adam", 1e-4), alpha=0.5, inversely_weighted=True)
-        st = step._compiled(N, size, size)
-        seen = set()
-        for prog in st.programs.values():
-            for i in range(getattr(prog, "n", 0)):
-                op = prog.array[i]
-                if op.kind in (L.OP_CONV3_FWD, L.OP_CONV3_DGRAD, L.OP_CONV3_WGRAD):
-                    seen.add(ops.conv3x3_kernel_name(op.u.conv3, op.kind).split(" + ")[0])
-        print(f"{arch} {dtype} N={N} {size}x{size}: {sorted(seen)}")
-        assert seen, f"{arch} {dtype}: no 3x3 conv launch found"
-        if seen - tested:
-            missing[(arch, dtype, N, size)] = sorted(seen - tested)
-        del st, step, model
-        torch.cuda.empty_cache()
-    assert not missing, f"conv3x3 instances of the step programs that no element-wise reference test launches: {missing}"
+    """Surveys (builds, does not run) the step programs of the benchmark's configurations and asks mtbc_conv3x3_kernel_name for the instance
+    of every 3x3 conv launch: each must be one an element-wise reference test of this file launches.  A new dispatch path that no reference
+    test reaches fails here."""
+    assert_all_tested("conv3x3", _reference_tested_instances(), [survey(p) for p in STEP_PROGRAMS])
 
 
 # ------------------------------------------------------------------ the InstanceNorm + LeakyReLU launches of the step programs, element by element
-def _instnorm_key(a, backward):
-    """Coverage key of ONE mtbc_instnorm_lrelu_fwd / _bwd call: the launches mtbc_instnorm_kernel_name plans (kernel instances, block sizes,
-    team size T; the number of rounds only as 1 or >1) + the branches the ARGUMENTS select inside those kernels.  The only place that
-    decides what "the same launch" means for the guard below."""
-    name = re.sub(r"rounds=(\d+)", lambda m: "rounds=1" if m.group(1) == "1" else "rounds>1", ops.instnorm_kernel_name(a, backward))
-    c8 = bool(a.dz8 if backward else a.y8)
-    f = []
-    if a.gamma and a.beta:
-        f.append("affine")
-    else:
-        f += [n for n in ("gamma", "beta") if getattr(a, n)]
-    if not backward:
-        if a.y16:                             # (beside y8: the 16-bit planes of the streaming pass; without y8: norm.hip in_fwd_reg_kernel `if (p.y16)`, in_cvt4)
-            f.append("y16")
-        if c8:
-            f += [n for n in ("pool_y8", "pool_arg") if getattr(a, n)]
-            if a.y and not a.y16:             # (norm_coop.hip fill_coop: `if (p->y16) p->y = nullptr`)
-                f.append("y")
-        # without y8: `y` is the output itself when y16 is NULL, and no kernel of norm.hip reads pool_y8 / pool_arg (norm.hip fill() copies neither into InP)
-        return name, tuple(f)
-    if not a.dy:
-        f.append("dy=NULL")
-    if a.n_dy_extra:
-        f.append(f"dy_extra={a.n_dy_extra}")
-    if a.dy_rank1:
-        f.append("rank1")
-        if a.dy_rank1_dw:
-            f.append("rank1_dw")
-            f += ["rank1_acc"] if a.dy_rank1_accumulate else []       # (read by in_r1_finalize_kernel only)
-            f += [] if a.dy_rank1_db else ["rank1_db=NULL"]
-    if a.dy_pool:
-        f.append("dy_pool")
-    f += [n for n in ("dgamma", "dbeta", "dbias_pre") if getattr(a, n)]
-    if a.accumulate_dparams and (a.dgamma or a.dbeta or a.dbias_pre) and not a.defer_dparams:
-        f.append("acc")                       # (with defer_dparams the flag is read by the MTBC_OP_IN_DPARAM descriptor only: _dparam_key)
-    if a.defer_dparams:
-        f.append("defer")
-    if a.dz16 and not a.dz8:                  # (norm.hip in_bwd_reg_kernel `if (p.dz16)`, in_cvt4; with dz8 norm_coop.hip fill_coop never copies a->dz16 into CoP)
-        f.append("dz16")
-    # dz in place over dy: only the fp32 kernels of norm.hip write `dz` (norm_coop.hip fill_coop never copies a->dz into CoP; with dz16
-    # norm.hip in_bwd_reg_kernel stores through p.dz16 and never through d4)
-    if a.dz and a.dz == a.dy and not a.dz8 and not a.dz16:
-        f.append("inplace")
-    return name, tuple(f)
-
-
-def _dparam_key(d):
-    """Coverage key of one descriptor of mtbc_instnorm_dparam_many (MTBC_OP_IN_DPARAM: the deferred parameter-gradient reduction)."""
-    return "in_dparam_many_kernel", tuple([n for n in ("dgamma", "dbeta", "dbias_pre") if getattr(d, n)] + [f"T={d.T}"] + (["acc"] if d.accumulate else []))
-
-
-def _program_instnorm_keys(arch, dtype, N, size, reserve_cus=0):
-    """Builds (does not run) one step program with bench.py's constructor path: {(op kind, key): (N, C, H, W) of one op that has it}."""
-    from multi_task_breast_cancer_amd.experiment_init import init_multitask_model, init_optimizer
-    from multi_task_breast_cancer_amd.miscellany import seed_everything
-    from multi_task_breast_cancer_amd.trainer import FusedTrainStep
-    L = ops.L
-    seed_everything(1993)
-    model = init_multitask_model(arch, sequences=1, regions=1, n_classes=3, deep_supervision=True).to(DEV)
-    model.set_compute(dtype)
-    model.coop_reserve_cus = reserve_cus          # what a data-parallel FusedTrainStep sets (trainer.py)
-    step = FusedTrainStep(model, init_optimizer(model, "Adam", 1e-4), alpha=0.5, inversely_weighted=True)
-    st = step._compiled(N, size, size)
-    seen = {}
-    for prog in st.programs.values():
-        for i in range(getattr(prog, "n", 0)):
-            op = prog.array[i]
-            if op.kind in (L.OP_IN_FWD, L.OP_IN_BWD):
-                a = op.u.inorm
-                seen.setdefault((op.kind, _instnorm_key(a, op.kind == L.OP_IN_BWD)), (a.N, a.C, a.H, a.W))
-            elif op.kind == L.OP_IN_DPARAM:
-                seen.setdefault((op.kind, _dparam_key(op.u.dparam)), (op.u.dparam.N, op.u.dparam.C))
-    del st, step, model
-    torch.cuda.empty_cache()
-    return seen
-
-
 def _bits16(t, st):
     """fp32 / fp64 values -> int16 storage of their rounding (to nearest even) to the 16-bit type st (1 bf16, 2 fp16)."""
     return (t.float().bfloat16() if st == 1 else t.float().half()).view(torch.int16)
@@ -1897,98 +1801,20 @@ def _reference_tested_instnorm_keys():
 
 
 def test_step_programs_launch_only_reference_tested_instnorm_instances():
-    """Builds (does not run) the benchmark's four step programs, and the first one as a data-parallel rank builds it (coop_reserve_cus = 64),
-    and computes the coverage key of every MTBC_OP_IN_FWD / _IN_BWD / _IN_DPARAM op: each must be the key of a call that
+    """Surveys (builds, does not run) the benchmark's four step programs, and the first one as a data-parallel rank builds it
+    (coop_reserve_cus = 64), for the coverage key of every MTBC_OP_IN_FWD / _IN_BWD / _IN_DPARAM op: each must be the key of a call that
     test_instnorm_step_instances_match_fp64 makes.  A plan change -- another instance, team size, a second round, a new argument-selected
-    branch -- that no fp64 case reaches fails here; _instnorm_key / _dparam_key, INORM_CASES and _reference_tested_instnorm_keys are the places to edit."""
-    L = ops.L
+    branch -- that no fp64 case reaches fails here; _instnorm_key / _dparam_key (tests/step_programs.py), INORM_CASES and
+    _reference_tested_instnorm_keys are the places to edit.  A missing key is named with (N, C, H, W) of an op that has it ((N, C) of a
+    parameter-gradient reduction)."""
     tested = _reference_tested_instnorm_keys()
     one, many = ({(k[0].replace(r, "rounds"), k[1]) for _, k in tested if r in k[0]} for r in ("rounds=1", "rounds>1"))
     assert one & many, "no instance is tested both in one round and in several with the same arguments"
-    missing = {}
-    for (arch, dtype, N, size), reserve in [(p_, 0) for p_ in STEP_PROGRAMS] + [(STEP_PROGRAMS[0], 64)]:
-        seen = _program_instnorm_keys(arch, dtype, N, size, reserve)
-        print(f"{arch} {dtype} N={N} {size}x{size} reserve {reserve}: {len(seen)} keys")
-        assert {L.OP_IN_FWD, L.OP_IN_BWD} <= {op for op, _ in seen}, f"{arch} {dtype}: no InstanceNorm launch found"
-        for (op, key), shape in sorted(seen.items()):
-            if (op, key) not in tested:
-                missing.setdefault((arch, dtype, N, size, reserve), []).append((key, shape))
-    assert not missing, "InstanceNorm launches of the step programs that no fp64 reference case makes: " + \
-        "".join(f"\n  {p_}: {k} at (N, C, H, W) = {s}" for p_, ks in missing.items() for k, s in ks)
+    assert_all_tested("InstanceNorm", tested, [survey(p) for p in STEP_PROGRAMS] + [survey(STEP_PROGRAMS[0], 64)],
+                      required=(ops.L.OP_IN_FWD, ops.L.OP_IN_BWD))
 
 
 # ------------------------------------------------------------------ the transposed-convolution launches of the step programs, element by element
-def _convT_key(a, op, nxt=None):
-    """Coverage key of ONE mtbc_convT_fwd / _dgrad / _wgrad call, or of a program's WGRAD + DGRAD pair (nxt = the DGRAD's arguments): the
-    launches mtbc_convT_kernel_name plans + the branches the ARGUMENTS select inside those kernels -- bias / dbias, the accumulate flags,
-    which tensors are channel-range views of wider buffers (a batch stride above dense), and Cout = 1 for the generic GEMM kernels (what the
-    fused deep-supervision heads launch: a 4-, 16- or 64-row M with one output plane).  The only place that decides what "the same launch" means
-    for the guard below."""
-    L = ops.L
-    name = ops.convT_kernel_name(a, op, nxt)
-    plane, up = a.H * a.W, a.H * a.W * a.k * a.k
-    dense = dict(x=a.Cin * plane, y=a.Cout * up, dy=a.Cout * up, dx=a.Cin * plane)
-    f = []
-
-    def views(s, *names):
-        f.extend(f"{n}_strided" for n in names if getattr(s, n + "_batch_stride") != dense[n])
-
-    if op == L.OP_CONVT_FWD:
-        f += ["bias"] if a.bias else []
-        views(a, "x", "y")
-    elif op == L.OP_CONVT_DGRAD:
-        f += ["acc_dx"] if a.accumulate_dx else []
-        views(a, "dy", "dx")
-    else:
-        f += ["dbias"] if a.dbias else []
-        f += ["acc_dw"] if a.accumulate_dw else []
-        views(a, "x", "dy")
-        if nxt is not None:
-            f += ["acc_dx"] if nxt.accumulate_dx else []
-            views(nxt, "dx")
-    if re.search(r"\bconvT_(fwd|dgrad|wgrad)_kernel<", name) and a.Cout == 1:
-        f.append("Cout=1")
-    return name, tuple(f)
-
-
-def _same_upconv(wg, dg):
-    """The DGRAD behind a WGRAD belongs to the same up-convolution (engine.StepPlan.convT emits the two back to back)."""
-    return all(getattr(wg, n) == getattr(dg, n) for n in ("N", "H", "W", "Cin", "Cout", "k", "dy", "w"))
-
-
-def _program_convT_keys(arch, dtype, N, size):
-    """Builds (does not run) one step program with bench.py's constructor path: {(kind, key): (N, Cin, Cout, H, W, k) of one op that has it};
-    kind "pair" = an OP_CONVT_WGRAD with the OP_CONVT_DGRAD of the same problem right behind it in the same program."""
-    from multi_task_breast_cancer_amd.experiment_init import init_multitask_model, init_optimizer
-    from multi_task_breast_cancer_amd.miscellany import seed_everything
-    from multi_task_breast_cancer_amd.trainer import FusedTrainStep
-    L = ops.L
-    kinds = {L.OP_CONVT_FWD: "fwd", L.OP_CONVT_DGRAD: "dgrad", L.OP_CONVT_WGRAD: "wgrad"}
-    seed_everything(1993)
-    model = init_multitask_model(arch, sequences=1, regions=1, n_classes=3, deep_supervision=True).to(DEV)
-    model.set_compute(dtype)
-    step = FusedTrainStep(model, init_optimizer(model, "Adam", 1e-4), alpha=0.5, inversely_weighted=True)
-    st = step._compiled(N, size, size)
-    seen = {}
-    for prog in st.programs.values():
-        n, i = getattr(prog, "n", 0), 0
-        while i < n:
-            op = prog.array[i]
-            if op.kind in kinds:
-                a = op.u.convT
-                shape = (a.N, a.Cin, a.Cout, a.H, a.W, a.k)
-                nxt = prog.array[i + 1] if i + 1 < n else None
-                if op.kind == L.OP_CONVT_WGRAD and nxt is not None and nxt.kind == L.OP_CONVT_DGRAD and _same_upconv(a, nxt.u.convT):
-                    seen.setdefault(("pair", _convT_key(a, op.kind, nxt.u.convT)), shape)
-                    i += 1
-                else:
-                    seen.setdefault((kinds[op.kind], _convT_key(a, op.kind)), shape)
-            i += 1
-    del st, step, model
-    torch.cuda.empty_cache()
-    return seen
-
-
 # (kind, N, Cin, Cout, H, W, k, mode, strided): kind "fwd" / "dgrad" / "wgrad" = one call through ops.convT_launch, "pair" = [OP_CONVT_WGRAD,
 # OP_CONVT_DGRAD] through engine.Program (the fused kernel where the runner takes the pair, the two calls' launches otherwise).  mode: the
 # keywords of ops.convT_case_args.  strided: the activation tensors that are channel ranges [8, 8 + C) of a buffer 16 channels wider.  Each
@@ -2298,78 +2124,15 @@ def _reference_tested_convT_keys():
 
 
 def test_step_programs_launch_only_reference_tested_convT_instances():
-    """Builds (does not run) the benchmark's four step programs and computes the coverage key of every MTBC_OP_CONVT_FWD / _DGRAD / _WGRAD op
+    """Surveys (builds, does not run) the benchmark's four step programs for the coverage key of every MTBC_OP_CONVT_FWD / _DGRAD / _WGRAD op
     -- of the pair where a WGRAD has the DGRAD of the same up-convolution right behind it, which is what the program runner looks at --:
     each must be the key of a call that test_convT_step_instances_match_fp64 makes.  A plan change -- another instance, the XCD order or the
-    fused kernel where it was not, a new argument-selected branch -- that no fp64 case reaches fails here; _convT_key, CONVT_CASES and
-    _reference_tested_convT_keys are the places to edit."""
-    tested = _reference_tested_convT_keys()
-    missing, total = {}, set()
-    for arch, dtype, N, size in STEP_PROGRAMS:
-        seen = _program_convT_keys(arch, dtype, N, size)
-        print(f"{arch} {dtype} N={N} {size}x{size}: {len(seen)} keys")
-        assert {"fwd", "pair"} <= {kind for kind, _ in seen}, f"{arch} {dtype}: no transposed-convolution launch found"
-        for (kind, key), shape in sorted(seen.items()):
-            print(f"  {kind} {key} at (N, Cin, Cout, H, W, k) = {shape}")
-            total.add((kind, key))
-            if (kind, key) not in tested:
-                missing.setdefault((arch, dtype, N, size), []).append((kind, key, shape))
-    print(f"{len(total)} distinct keys in the four programs, {len(tested)} keys tested")
-    assert not missing, "transposed-convolution launches of the step programs that no fp64 reference case makes: " + \
-        "".join(f"\n  {p_}: {kind} {k} at (N, Cin, Cout, H, W, k) = {s}" for p_, ks in missing.items() for kind, k, s in ks)
+    fused kernel where it was not, a new argument-selected branch -- that no fp64 case reaches fails here; _convT_key (tests/step_programs.py),
+    CONVT_CASES and _reference_tested_convT_keys are the places to edit.  A missing key is named with (N, Cin, Cout, H, W, k) of an op that has it."""
+    assert_all_tested("transposed-convolution", _reference_tested_convT_keys(), [survey(p) for p in STEP_PROGRAMS], required=("fwd", "pair"))
 
 
 # ------------------------------------------------------------------ the max-pool, 1x1, GAP, Linear and fused-head launches of the step programs, element by element
-def _small_op_key(op):
-    """Coverage key of ONE small op (ops.SMALL_OPS): the launches mtbc_op_kernel_name plans + the branches the ARGUMENTS select inside those
-    kernels -- which tensors are channel-range views of wider buffers (a batch stride above dense), argmax, bias / dbias, every accumulate
-    flag, dx present, and Cout > 8 (a second channel group in the planar 1x1 kernels).  The only place that decides what "the same launch"
-    means for the guard below."""
-    L = ops.L
-    name, k, f = ops.op_kernel_name(op), op.kind, []
-
-    def views(a, dense, *names):
-        f.extend(f"{n}_strided" for n in names if getattr(a, n + "_batch_stride") != dense[n])
-
-    if k in (L.OP_POOL_FWD, L.OP_POOL_BWD):
-        a = op.u.pool
-        full = a.C * a.H * a.W
-        dense = dict(x=full, y=full // 4, dy=full // 4, dx=full)
-        if k == L.OP_POOL_FWD:
-            views(a, dense, "x", "y")
-            f += ["argmax"] if a.argmax else []
-        else:
-            views(a, dense, "x", "dy", "dx")
-            f += ["acc_dx"] if a.accumulate_dx else []
-    elif k in (L.OP_CONV1_FWD, L.OP_CONV1_DGRAD, L.OP_CONV1_WGRAD):
-        a = op.u.conv1
-        dense = dict(x=a.Cin * a.H * a.W, dx=a.Cin * a.H * a.W)
-        if k == L.OP_CONV1_FWD:
-            views(a, dense, "x")
-            f += ["bias"] if a.bias else []
-        elif k == L.OP_CONV1_DGRAD:
-            views(a, dense, "dx")
-            f += ["acc_dx"] if a.accumulate_dx else []
-        else:
-            views(a, dense, "x")
-            f += ["dbias"] if a.dbias else []
-            f += ["acc_dw"] if a.accumulate_dw else []
-        f += ["Cout>8"] if a.Cout > 8 else []
-    elif k == L.OP_LINEAR_FWD:
-        f += [n for n in ("relu", "bias") if getattr(op.u.linear, n)]
-    elif k == L.OP_LINEAR_BWD:
-        a = op.u.linear
-        f += [n for n in ("relu", "dx", "dbias") if getattr(a, n)]
-        f += ["acc_dw"] if a.accumulate_dw else []
-    elif k == L.OP_HEAD_COMBINE:
-        f += [n for n in ("bT", "b1") if getattr(op.u.head, n)]
-    elif k == L.OP_HEAD_EXPAND:
-        f += [n for n in ("bT", "dbT", "db1", "acc_wT", "acc_bT", "acc_w1", "acc_b1") if getattr(op.u.head, n)]
-    else:
-        assert k in (L.OP_GAP_FWD, L.OP_GAP_BWD), k          # (GAP: dense tensors, no flag)
-    return name, tuple(f)
-
-
 # kind -> (the *_case_args helper of ops.py, the op kind)
 _SMALL_FAMILY = {"pool_fwd": ("maxpool", ops.L.OP_POOL_FWD), "pool_bwd": ("maxpool", ops.L.OP_POOL_BWD),
                  "c1_fwd": ("conv1x1", ops.L.OP_CONV1_FWD), "c1_dgrad": ("conv1x1", ops.L.OP_CONV1_DGRAD), "c1_wgrad": ("conv1x1", ops.L.OP_CONV1_WGRAD),
@@ -2823,56 +2586,20 @@ def test_small_op_step_instances_match_fp64(case):
     assert not bad, "; ".join(bad)
 
 
-def _program_small_op_keys(arch, dtype, N, size):
-    """Builds (does not run) one step program with bench.py's constructor path: {(op kind, key): the op's shape}."""
-    from multi_task_breast_cancer_amd.experiment_init import init_multitask_model, init_optimizer
-    from multi_task_breast_cancer_amd.miscellany import seed_everything
-    from multi_task_breast_cancer_amd.trainer import FusedTrainStep
-    L = ops.L
-    shape_of = {"pool": ("N", "C", "H", "W"), "conv1": ("N", "Cin", "Cout", "H", "W"), "gap": ("N", "C", "H", "W"), "linear": ("N", "In", "Out"),
-                "head": ("Cin", "Cmid", "R", "k")}
-    seed_everything(1993)
-    model = init_multitask_model(arch, sequences=1, regions=1, n_classes=3, deep_supervision=True).to(DEV)
-    model.set_compute(dtype)
-    step = FusedTrainStep(model, init_optimizer(model, "Adam", 1e-4), alpha=0.5, inversely_weighted=True)
-    st = step._compiled(N, size, size)
-    seen = {}
-    for prog in st.programs.values():
-        for i in range(getattr(prog, "n", 0)):
-            op = prog.array[i]
-            if op.kind in ops.SMALL_OPS:
-                field = L.OP_UNION_FIELD[op.kind]
-                seen.setdefault((op.kind, _small_op_key(op)), tuple(getattr(getattr(op.u, field), n) for n in shape_of[field]))
-    del st, step, model
-    torch.cuda.empty_cache()
-    return seen
-
-
 def _reference_tested_small_op_keys():
     """(op kind, key) of every call test_small_op_step_instances_match_fp64 makes, from its case table's argument structs."""
     return {(op.kind, _small_op_key(op)) for case in SMALL_OP_CASES for op in _small_case_ops(case)}
 
 
 def test_step_programs_launch_only_reference_tested_small_op_instances():
-    """Builds (does not run) the benchmark's four step programs and computes the coverage key of every max-pool, 1x1, GAP, Linear and fused-head
+    """Surveys (builds, does not run) the benchmark's four step programs for the coverage key of every max-pool, 1x1, GAP, Linear and fused-head
     op: each must be the key of a call that test_small_op_step_instances_match_fp64 makes.  A plan change -- another kernel or reducer
-    instance, a tensor that became a view, a new argument-selected branch -- that no fp64 case reaches fails here; _small_op_key, SMALL_OP_CASES
-    and _reference_tested_small_op_keys are the places to edit."""
+    instance, a tensor that became a view, a new argument-selected branch -- that no fp64 case reaches fails here; _small_op_key
+    (tests/step_programs.py), SMALL_OP_CASES and _reference_tested_small_op_keys are the places to edit.  Every program must hold the
+    classification head: GAP and Linear, forward and backward."""
     L = ops.L
-    tested = _reference_tested_small_op_keys()
-    missing, total = {}, set()
-    for arch, dtype, N, size in STEP_PROGRAMS:
-        seen = _program_small_op_keys(arch, dtype, N, size)
-        print(f"{arch} {dtype} N={N} {size}x{size}: {len(seen)} keys")
-        assert {L.OP_GAP_FWD, L.OP_GAP_BWD, L.OP_LINEAR_FWD, L.OP_LINEAR_BWD} <= {kind for kind, _ in seen}, f"{arch} {dtype}: no classification head found"
-        for (kind, key), shape in sorted(seen.items()):
-            print(f"  op {kind} {key} at {shape}")
-            total.add((kind, key))
-            if (kind, key) not in tested:
-                missing.setdefault((arch, dtype, N, size), []).append((kind, key, shape))
-    print(f"{len(total)} distinct keys in the four programs, {len(tested)} keys tested")
-    assert not missing, "small-op launches of the step programs that no fp64 reference case makes: " + \
-        "".join(f"\n  {p_}: op {kind} {k} at {s}" for p_, ks in missing.items() for kind, k, s in ks)
+    assert_all_tested("small-op", _reference_tested_small_op_keys(), [survey(p) for p in STEP_PROGRAMS],
+                      required=(L.OP_GAP_FWD, L.OP_GAP_BWD, L.OP_LINEAR_FWD, L.OP_LINEAR_BWD))
 
 
 # ------------------------------------------------------------------ the weight-image, weight-view and channel-blocking launches of the step programs, bit for bit
@@ -3150,30 +2877,6 @@ def test_c8_pack16_matches_the_layout_reference(N, Cc, HW, strided):
 
 
 # ---- the guard
-def _pack_key(kind, Cin, Cout, dgrad, compute, path):
-    """Coverage key of one weight-image op from its arguments: what selects a kernel path (kind, format, single or batched) and the branches
-    inside it (a ragged last row tile, a ragged last K chunk -- for the fp32 forward image of the batched launch: 16 x 16 patches that
-    straddle two row tiles --, one / two / more chunks)."""
-    L = ops.L
-    if kind == L.OP_CONV3_PACK_LP:
-        rows, red = (Cin, Cout) if dgrad else (Cout, Cin)
-        return ("lp", int(bool(dgrad)), compute, rows % 16 != 0, red % 32 != 0, min(3, (red + 31) // 32), path)
-    if kind == L.OP_CONV3_PACK_FWD:
-        return ("fwd", 0, 0, Cout % 16 != 0, (9 * Cin) % 16 != 0, 0, path)
-    assert kind == L.OP_CONV3_PACK_DGRAD, kind
-    return ("dgrad", 1, 0, Cin % 16 != 0, False, 0, path)
-
-
-def _wview_key(Cout, Cin, off, cnt, mode, k_off, K, path):
-    return (mode, off > 0, off + cnt < Cin, bool(mode) and k_off > 0, bool(mode) and k_off + Cout < K, path)
-
-
-def _c8_key(kind, N, Cc, HW, compute, stride):
-    p16 = kind == ops.L.OP_C8_PACK16
-    pieces = N * (Cc // 8) * (HW // 4 if p16 else HW)
-    return ("pack16" if p16 else "pack", 0 if p16 else compute, stride != Cc * HW, pieces % 256 != 0)
-
-
 _DESC_KIND = {0: ("OP_CONV3_PACK_FWD", 0), 1: ("OP_CONV3_PACK_DGRAD", 1), 2: ("OP_CONV3_PACK_LP", 0), 3: ("OP_CONV3_PACK_LP", 1)}
 
 
@@ -3196,83 +2899,13 @@ def _reference_tested_layout_keys():
     return keys
 
 
-_STEP_OP_RECORDS = {}
-
-
-def _step_op_records(arch, dtype, N, size):
-    """Builds (does not run) one step program with bench.py's constructor path, once per session: {program name: [(op kind, arguments)]} of every
-    program the compiled step holds -- arguments as a plain tuple for the weight-image, weight-view and channel-blocking kinds, else None."""
-    if (arch, dtype, N, size) in _STEP_OP_RECORDS:
-        return _STEP_OP_RECORDS[arch, dtype, N, size]
-    import gc
-    from multi_task_breast_cancer_amd.experiment_init import init_multitask_model, init_optimizer
-    from multi_task_breast_cancer_amd.miscellany import seed_everything
-    from multi_task_breast_cancer_amd.trainer import FusedTrainStep
-    L = ops.L
-    seed_everything(1993)
-    model = init_multitask_model(arch, sequences=1, regions=1, n_classes=3, deep_supervision=True).to(DEV)
-    model.set_compute(dtype)
-    step = FusedTrainStep(model, init_optimizer(model, "Adam", 1e-4), alpha=0.5, inversely_weighted=True)
-    st = step._compiled(N, size, size)
-    fields = {"pack": ("Cin", "Cout", "dgrad", "compute"), "wview": ("Cout", "Cin", "ci_off", "ci_cnt", "mode", "k_off", "K"),
-              "c8pack": ("N", "C", "HW", "compute", "src_batch_stride")}
-    rec = {}
-    for name, prog in st.programs.items():
-        rec[name] = []
-        for i in range(getattr(prog, "n", 0)):
-            op = prog.array[i]
-            field = L.OP_UNION_FIELD[op.kind]
-            rec[name].append((op.kind, tuple(getattr(getattr(op.u, field), n) for n in fields[field]) if field in fields else None))
-    del st, step, model, prog, op
-    gc.collect()          # a step and its model refer to each other: their tensors go only with a collection, and the four programs do not fit the device side by side
-    torch.cuda.empty_cache()
-    _STEP_OP_RECORDS[arch, dtype, N, size] = rec
-    return rec
-
-
-def _program_layout_keys(arch, dtype, N, size):
-    """{key: (program, op kind, the op's arguments)} of the weight-image, weight-view and channel-blocking ops of one step.  A pack or view op
-    in a run of more than one inside its program goes through the batched launch (mtbc_program_run_ms): path "many"."""
-    L = ops.L
-    packs, seen = (L.OP_CONV3_PACK_FWD, L.OP_CONV3_PACK_DGRAD, L.OP_CONV3_PACK_LP), {}
-    for pname, oplist in _step_op_records(arch, dtype, N, size).items():
-        kinds = [kind for kind, _ in oplist]
-        for i, (kind, args) in enumerate(oplist):
-            def in_run(family):          # an op of the same family stands next to op i
-                return "many" if (i > 0 and kinds[i - 1] in family) or (i + 1 < len(kinds) and kinds[i + 1] in family) else "single"
-            if kind in packs:
-                Cin, Cout, dgrad, compute = args
-                key = _pack_key(kind, Cin, Cout, dgrad, compute if kind == L.OP_CONV3_PACK_LP else 0, in_run(packs))
-            elif kind == L.OP_CONV3_WVIEW:
-                key = _wview_key(*args, in_run((L.OP_CONV3_WVIEW,)))
-            elif kind in (L.OP_C8_PACK, L.OP_C8_PACK16):
-                key = _c8_key(kind, *args)
-            else:
-                continue
-            seen.setdefault(key, (pname, kind, args))
-    return seen
-
-
 def test_step_programs_launch_only_reference_tested_layout_ops():
-    """Builds (does not run) the benchmark's four step programs and computes the coverage key of every weight-image, weight-view and
+    """Surveys (builds, does not run) the benchmark's four step programs for the coverage key of every weight-image, weight-view and
     channel-blocking op in every program of the step (the views and images sit in the "pack" program): each must be the key of a call that the
-    layout tests above make.  _pack_key / _wview_key / _c8_key, the case tables and _reference_tested_layout_keys are the places to edit.
-    A missing key is named with its op's arguments: (Cin, Cout, dgrad, compute) of an image, (Cout, Cin, off, cnt, mode, k_off, K) of a view,
-    (N, C, HW, compute, src_batch_stride) of a channel-blocking op."""
-    tested = _reference_tested_layout_keys()
-    missing, total = {}, set()
-    for arch, dtype, N, size in STEP_PROGRAMS:
-        seen = _program_layout_keys(arch, dtype, N, size)
-        print(f"{arch} {dtype} N={N} {size}x{size}: {len(seen)} keys")
-        assert seen, f"{arch} {dtype}: no weight image found"
-        for key, (pname, kind, args) in sorted(seen.items(), key=repr):
-            print(f"  {pname}: op {kind} {key} at {args}")
-            total.add(key)
-            if key not in tested:
-                missing.setdefault((arch, dtype, N, size), []).append((kind, key, args))
-    print(f"{len(total)} distinct keys in the four programs, {len(tested)} tested")
-    assert not missing, "layout launches of the step programs that no bit-for-bit reference case makes: " + \
-        "".join(f"\n  {p_}: op {kind} {k} at {s}" for p_, ks in missing.items() for kind, k, s in ks)
+    layout tests above make.  _pack_key / _wview_key / _c8_key (tests/step_programs.py), the case tables and _reference_tested_layout_keys are
+    the places to edit.  A missing key is named with its op's arguments: (Cin, Cout, dgrad, compute) of an image, (Cout, Cin, off, cnt, mode,
+    k_off, K) of a view, (N, C, HW, compute, src_batch_stride) of a channel-blocking op."""
+    assert_all_tested("layout", _reference_tested_layout_keys(), [survey(p) for p in STEP_PROGRAMS])
 
 
 # ---- the loss mix
@@ -3342,7 +2975,7 @@ def test_memset_op_zeroes_exactly_its_bytes():
 
 
 def test_every_op_kind_of_the_step_programs_is_claimed_by_a_test():
-    """Builds (does not run) the four step programs and collects every op kind present: each must have an entry in OP_KIND_COVERED_BY, and the
+    """Surveys (builds, does not run) the four step programs for every op kind present: each must have an entry in OP_KIND_COVERED_BY, and the
     test or guard it names must exist in the file it names.  A new op kind in a program without an entry fails here."""
     import os
     L = ops.L
@@ -3354,7 +2987,7 @@ def test_every_op_kind_of_the_step_programs_is_claimed_by_a_test():
         assert re.search(rf"^def {test}\(", text, re.M), f"{name}: {path} has no {test}"
     present = set()
     for arch, dtype, N, size in STEP_PROGRAMS:
-        kinds = {kind for oplist in _step_op_records(arch, dtype, N, size).values() for kind, _ in oplist}
+        kinds = {kind for oplist in survey((arch, dtype, N, size)).kinds.values() for kind in oplist}
         print(f"{arch} {dtype} N={N} {size}x{size}: {sorted(name_of[k] for k in kinds)}")
         present |= kinds
     unclaimed = sorted(name_of.get(k, str(k)) for k in present if name_of.get(k) not in OP_KIND_COVERED_BY)
