@@ -2,6 +2,10 @@
 
 Used by the parity tests and as the reference-side binding example of INTEGRATION.md; the training path itself
 goes through step programs (engine.py).  Device fp32 tensors only; every wrapper raises on CPU input.
+
+Each argument struct is filled in ONE function, the family's *_case_args builder: with ptrs=None it carries dummy addresses for the host-only
+*_kernel_name queries (the launch-coverage guards of the tests), with ptrs= tensors it is what conv3x3_launch / instnorm_launch /
+convT_launch / small_op_launch hand the library.  The eager wrappers validate, allocate, call the builder and launch.
 """
 from __future__ import annotations
 
@@ -29,14 +33,24 @@ def _chk(*ts):
 
 
 def _p(t):
-    return None if t is None else t.data_ptr()
+    """The address of a tensor or of a C8 tensor's storage; None stays None (a NULL field)."""
+    return None if t is None else (t.data if isinstance(t, C8) else t).data_ptr()
 
 
-def _fill_segs(arr, tensors: Sequence[torch.Tensor], accumulate: Sequence[int] = ()):
-    for i, t in enumerate(tensors):
-        arr[i].ptr = t.data_ptr()
-        arr[i].batch_stride = t.shape[1] * t.shape[2] * t.shape[3]
-        arr[i].channels = t.shape[1]
+def _ptr(ptrs: Optional[dict], dummy):
+    """name -> the address a *_case_args builder puts into a pointer field: of ptrs[name] (a tensor, a C8, or None for NULL), or with
+    ptrs = None dummy(name), a 16-byte aligned address that nothing may dereference (for the *_kernel_name queries)."""
+    return dummy if ptrs is None else (lambda name: _p(ptrs[name]))
+
+
+def _dummies(*names) -> dict:
+    return {n: (i + 1) << 20 for i, n in enumerate(names)}
+
+
+def _segs(arr, addrs, chans: Sequence[int], HW: int, accumulate: Sequence[int] = ()):
+    """The segment array of a conv3x3 call: batch strides in elements of the segment's own type."""
+    for i, (addr, c) in enumerate(zip(addrs, chans)):
+        arr[i].ptr, arr[i].batch_stride, arr[i].channels = addr, c * HW, c
         arr[i].accumulate = accumulate[i] if i < len(accumulate) else 0
 
 
@@ -53,40 +67,58 @@ def conv3x3_kernel_name(a: "L.Conv3x3Args", op: int) -> str:
     return buf.value.decode()
 
 
-def conv3x3_case_args(op: int, N: int, segs: Sequence[int], Cout: int, H: int, W: int, compute: int = 0, c8: bool = False,
-                      out_c8: bool = False, out_fp16: bool = False, dx_c8: bool = False, bias: bool = True,
-                      in_kernel_reduce: bool = False) -> "L.Conv3x3Args":
-    """The argument struct the wrappers below fill for one call (fwd: conv3x3_fwd / conv3x3_fwd_c8 / conv3x3_stem_fwd_c8, dgrad:
-    conv3x3_dgrad / conv3x3_dgrad_c8 with the first segment overwritten and the others accumulated, wgrad: conv3x3_wgrad /
-    conv3x3_wgrad_c8), its tensor pointers distinct 16-byte aligned dummies that nothing may dereference: for conv3x3_kernel_name.
-    c8: operands in MTBC_LAYOUT_C8 (one segment of at most L.STEM_MAX_CIN channels stays fp32 planar: the stem); bias: fwd bias / wgrad dbias."""
+_C3_DUMMY = _dummies(*(f"in{i}" for i in range(L.MAX_SEGS)), "w", "w_packed", "bias", "out", "dout", "dw", "dbias", "workspace", "wgrad_sync",
+                     "stats_partial", "out_partial", "norm_z", "norm_mean", "norm_rstd", "norm_gamma", "norm_beta")
+
+
+def conv3x3_case_args(op: int, N: int, segs: Sequence[int], Cout: int, H: int, W: int, ptrs: Optional[dict] = None, compute: int = 0,
+                      c8: bool = False, out_c8: bool = False, out_fp16: bool = False, dx_c8: bool = False, bias: bool = True,
+                      in_kernel_reduce: bool = False, accumulate: Optional[Sequence[int]] = None, packed: Optional[bool] = None,
+                      force_direct: bool = False, accumulate_dw: bool = False, stats: bool = False, norm: Optional[float] = None,
+                      out_partial: bool = False) -> "L.Conv3x3Args":
+    """The argument struct of ONE 3x3 convolution call (op = L.OP_CONV3_FWD / _DGRAD / _WGRAD), the only place that fills it.  ptrs: "in" ->
+    the segments (tensors, or C8 tensors) and field name -> tensor / C8 / None for NULL; None = distinct 16-byte aligned dummies that nothing
+    may dereference (for conv3x3_kernel_name).  c8: operands in MTBC_LAYOUT_C8 (one segment of at most L.STEM_MAX_CIN channels stays fp32
+    planar: the stem, whose weight gradient reads it beside a channel-blocked dout); bias: fwd bias / wgrad dbias; packed: with w_packed
+    (default: the dgrad and every forward but the stem's); accumulate: the dgrad's per-segment codes 0 .. 3 (default: the first segment
+    overwritten, the others accumulated; dx_c8: all 3 = channel-blocked 16-bit segments).  Forward: out_c8 (+ out_fp16) = a channel-blocked
+    16-bit output, stats = the InstanceNorm statistics partials of the epilogue, norm = the slope of the norm-backward epilogue of a gathered
+    dgrad (norm_z / _mean / _rstd / _gamma / _beta), out_partial = its planar partial.  Weight gradient: accumulate_dw, in_kernel_reduce =
+    offer the counters of the in-kernel split-K reduction."""
     lib = L.load()
-    ptr = iter(range(1 << 20, 1 << 30, 1 << 20))
+    ptr = _ptr(ptrs, _C3_DUMMY.__getitem__)
     a = L.Conv3x3Args()
     a.N, a.H, a.W, a.Cin, a.Cout, a.n_in = N, H, W, sum(segs), Cout, len(segs)
-    for i, c in enumerate(segs):
-        a.in_[i].ptr, a.in_[i].batch_stride, a.in_[i].channels = next(ptr), c * H * W, c
-        if op == L.OP_CONV3_DGRAD:
-            a.in_[i].accumulate = 3 if dx_c8 else (1 if i else 0)
-    a.w, a.compute = next(ptr), compute
+    if accumulate is None:
+        accumulate = [3 if dx_c8 else int(i > 0) for i in range(len(segs))] if op == L.OP_CONV3_DGRAD else ()
+    _segs(a.in_, [ptr(f"in{i}") for i in range(len(segs))] if ptrs is None else [_p(t) for t in ptrs["in"]], segs, H * W, accumulate)
+    a.w, a.compute, a.force_direct = ptr("w"), compute, int(force_direct)
     stem = len(segs) == 1 and segs[0] <= L.STEM_MAX_CIN
     if c8 and not (stem and op == L.OP_CONV3_FWD):
         a.operand_layout = L.LAYOUT_C8
+    if (op != L.OP_CONV3_WGRAD and not (stem and op == L.OP_CONV3_FWD)) if packed is None else packed:
+        a.w_packed = ptr("w_packed")
     if op == L.OP_CONV3_FWD:
-        a.out, a.bias = next(ptr), (next(ptr) if bias else None)
-        if not stem:
-            a.w_packed = next(ptr)
+        a.out, a.bias = ptr("out"), (ptr("bias") if bias else None)
         if out_c8:
             a.out_layout = L.LAYOUT_C8
             a.out_type = 2 if out_fp16 else 0
+        if norm is not None:
+            a.norm_z, a.norm_mean, a.norm_rstd, a.norm_slope = ptr("norm_z"), ptr("norm_mean"), ptr("norm_rstd"), norm
+            a.norm_gamma, a.norm_beta = ptr("norm_gamma"), ptr("norm_beta")
+        if out_partial:
+            a.out_partial = ptr("out_partial")
+        if stats:
+            a.stats_partial = ptr("stats_partial")
     elif op == L.OP_CONV3_DGRAD:
-        a.w_packed, a.dout = next(ptr), next(ptr)
+        a.dout = ptr("dout")
     else:
-        a.dout, a.dw, a.dbias = next(ptr), next(ptr), (next(ptr) if bias else None)
-        a.workspace, a.workspace_bytes = next(ptr), int(lib.mtbc_conv3x3_wgrad_workspace(C.byref(a)))
+        a.dout, a.dw, a.dbias, a.accumulate_dw = ptr("dout"), ptr("dw"), (ptr("dbias") if bias else None), int(accumulate_dw)
+        nb = int(lib.mtbc_conv3x3_wgrad_workspace(C.byref(a)))
+        a.workspace, a.workspace_bytes = ptr("workspace"), (nb if ptrs is None else ptrs["workspace"].numel() * 4)
         nsync = int(lib.mtbc_conv3x3_wgrad_sync_bytes(C.byref(a))) if in_kernel_reduce else 0
         if nsync:
-            a.wgrad_sync, a.wgrad_sync_bytes = next(ptr), nsync
+            a.wgrad_sync, a.wgrad_sync_bytes = ptr("wgrad_sync"), (nsync if ptrs is None else ptrs["wgrad_sync"].numel() * 4)
     return a
 
 
@@ -95,14 +127,18 @@ def conv3x3_case_kernel(op: int, *shape, **mode) -> str:
     return conv3x3_kernel_name(conv3x3_case_args(op, *shape, **mode), op)
 
 
-# (op, instance) of every conv3x3 launch -- and (op, launches) of every InstanceNorm call -- made through the wrappers below while this is
-# a list (the reference tests record what they ran)
+# (op, launches) of every call made through the *_launch functions below while this is a list (the reference tests record what they ran)
 launched: Optional[list] = None
 
 
-def _note(a, op: int) -> None:
+def conv3x3_launch(a: "L.Conv3x3Args", op: int) -> None:
+    """mtbc_conv3x3_fwd / _dgrad / _wgrad on the current stream for an argument struct of conv3x3_case_args(ptrs=...)."""
     if launched is not None:
         launched.append((op, conv3x3_kernel_name(a, op)))
+    lib = L.load()
+    fn, what = {L.OP_CONV3_FWD: (lib.mtbc_conv3x3_fwd, "conv3x3_fwd"), L.OP_CONV3_DGRAD: (lib.mtbc_conv3x3_dgrad, "conv3x3_dgrad"),
+                L.OP_CONV3_WGRAD: (lib.mtbc_conv3x3_wgrad, "conv3x3_wgrad")}[op]
+    L.check(fn(C.byref(a), _s()), what)
 
 
 def conv3x3_pack(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -168,25 +204,55 @@ def conv3x3_pack_many(weights, compute: int = 0):
     return [(outs[2 * i], outs[2 * i + 1]) for i in range(len(weights))]
 
 
-def _conv_args(xs, w, N, H, W):
-    a = L.Conv3x3Args()
-    cin = sum(x.shape[1] for x in xs)
-    a.N, a.H, a.W, a.Cin, a.Cout, a.n_in = N, H, W, cin, w.shape[0], len(xs)
-    a.w = w.data_ptr()
-    return a
+def _conv_args(xs, w, N, H, W):       # (kept for the tests) a forward over planar xs, no bias, no packed weights, `out` left to the caller
+    return conv3x3_case_args(L.OP_CONV3_FWD, N, [x.shape[1] for x in xs], w.shape[0], H, W, ptrs={"in": xs, "w": w, "out": None}, bias=False, packed=False)
+
+
+def _fill_segs(arr, tensors: Sequence[torch.Tensor], accumulate: Sequence[int] = ()):       # (kept for the tests) planar segments
+    _segs(arr, [t.data_ptr() for t in tensors], [t.shape[1] for t in tensors], tensors[0].shape[2] * tensors[0].shape[3], accumulate)
+
+
+def _conv3x3_fwd(N, segs, Cout, H, W, ptrs: dict, stats: bool = False, **mode):
+    """One forward launch; stats: with the epilogue's InstanceNorm statistics partials [N][slots][Cout][2], allocated here and returned."""
+    case = lambda **kw: conv3x3_case_args(L.OP_CONV3_FWD, N, segs, Cout, H, W, **mode, **kw)      # noqa: E731
+    if stats:
+        slots = L.load().mtbc_conv3x3_stats_slots(C.byref(case()))
+        if slots <= 0:
+            raise L.MtbcError("conv3x3_fwd: no epilogue statistics for this launch")
+        ptrs["stats_partial"] = torch.full((N, slots, Cout, 2), float("nan"), dtype=torch.float32, device=ptrs["out"].device)
+    conv3x3_launch(case(ptrs=ptrs, stats=stats), L.OP_CONV3_FWD)
+    return ptrs.get("stats_partial")
+
+
+def _conv3x3_dgrad(dz, w, dxs, accumulate, packed, **mode) -> None:
+    N, _, H, W = dz.shape
+    ptrs = {"in": dxs, "w": w, "w_packed": packed, "dout": dz}
+    a = conv3x3_case_args(L.OP_CONV3_DGRAD, N, [d.shape[1] for d in dxs], w.shape[0], H, W, ptrs=ptrs, accumulate=accumulate, packed=packed is not None, **mode)
+    conv3x3_launch(a, L.OP_CONV3_DGRAD)
+
+
+def _conv3x3_wgrad(xs, dz, w_shape, want_bias, dw, accumulate, **mode):
+    N, _, H, W = dz.shape
+    dev = (dz.data if isinstance(dz, C8) else dz).device
+    if dw is None:
+        dw = torch.empty(*w_shape, dtype=torch.float32, device=dev)
+    db = torch.empty(w_shape[0], dtype=torch.float32, device=dev) if want_bias else None
+    case = lambda ptrs: conv3x3_case_args(L.OP_CONV3_WGRAD, N, [x.shape[1] for x in xs], w_shape[0], H, W, ptrs=ptrs, bias=want_bias,      # noqa: E731
+                                          accumulate_dw=accumulate, **mode)
+    want = case(None)           # (dummy pointers) the workspace and the counters this launch asks for
+    ptrs = {"in": xs, "w": None, "dout": dz, "dw": dw, "dbias": db, "workspace": _ws(want.workspace_bytes, dev),
+            "wgrad_sync": wgrad_sync_buffer(dev, want.wgrad_sync_bytes) if want.wgrad_sync_bytes else None}
+    conv3x3_launch(case(ptrs), L.OP_CONV3_WGRAD)
+    return dw, db
 
 
 def conv3x3_fwd(xs: Sequence[torch.Tensor], w: torch.Tensor, bias: Optional[torch.Tensor] = None,
                 packed: Optional[torch.Tensor] = None, force_direct: bool = False, compute: int = 0) -> torch.Tensor:
     _chk(*xs, w, bias)
     N, _, H, W = xs[0].shape
-    a = _conv_args(xs, w, N, H, W)
-    _fill_segs(a.in_, xs)
     out = torch.empty(N, w.shape[0], H, W, dtype=torch.float32, device=w.device)
-    a.w_packed, a.bias, a.out, a.force_direct = _p(packed), _p(bias), out.data_ptr(), int(force_direct)
-    a.compute = compute
-    _note(a, L.OP_CONV3_FWD)
-    L.check(L.load().mtbc_conv3x3_fwd(C.byref(a), _s()), "conv3x3_fwd")
+    _conv3x3_fwd(N, [x.shape[1] for x in xs], w.shape[0], H, W, {"in": xs, "w": w, "w_packed": packed, "bias": bias, "out": out},
+                 compute=compute, bias=bias is not None, packed=packed is not None, force_direct=force_direct)
     return out
 
 
@@ -197,21 +263,9 @@ def conv3x3_stem_fwd_c8(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.T
     if not 1 <= w.shape[1] <= L.STEM_MAX_CIN or x.shape[1] != w.shape[1]:
         raise ValueError(f"the stem takes 1 .. {L.STEM_MAX_CIN} input channels")
     N, _, H, W = x.shape
-    a = _conv_args([x], w, N, H, W)
-    _fill_segs(a.in_, [x])
     out = torch.empty(N, w.shape[0] // 8, H * W, 8, dtype=torch.int16, device=w.device)
-    a.bias, a.out, a.compute, a.out_layout = _p(bias), out.data_ptr(), compute, L.LAYOUT_C8
-    if out_fp16:
-        a.out_type = 2
-    part = None
-    if stats:
-        slots = L.load().mtbc_conv3x3_stats_slots(C.byref(a))
-        if slots <= 0:
-            raise L.MtbcError("conv3x3_fwd: no epilogue statistics for this launch")
-        part = torch.full((N, slots, w.shape[0], 2), float("nan"), dtype=torch.float32, device=w.device)
-        a.stats_partial = part.data_ptr()
-    _note(a, L.OP_CONV3_FWD)
-    L.check(L.load().mtbc_conv3x3_fwd(C.byref(a), _s()), "conv3x3_fwd(stem c8)")
+    part = _conv3x3_fwd(N, [x.shape[1]], w.shape[0], H, W, {"in": [x], "w": w, "bias": bias, "out": out}, stats,
+                        compute=compute, c8=True, out_c8=True, out_fp16=out_fp16, bias=bias is not None)
     z = C8(out, (N, w.shape[0], H, W), 2 if out_fp16 else compute)
     return (z, part) if stats else z
 
@@ -219,35 +273,14 @@ def conv3x3_stem_fwd_c8(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.T
 def conv3x3_dgrad(dz: torch.Tensor, w: torch.Tensor, dxs: Sequence[torch.Tensor], accumulate: Sequence[int] = (),
                   packed: Optional[torch.Tensor] = None, force_direct: bool = False, compute: int = 0) -> None:
     _chk(dz, w, *dxs)
-    N, _, H, W = dz.shape
-    a = _conv_args(dxs, w, N, H, W)
-    _fill_segs(a.in_, dxs, accumulate)
-    a.w_packed, a.dout, a.force_direct = _p(packed), dz.data_ptr(), int(force_direct)
-    a.compute = compute
-    _note(a, L.OP_CONV3_DGRAD)
-    L.check(L.load().mtbc_conv3x3_dgrad(C.byref(a), _s()), "conv3x3_dgrad")
+    _conv3x3_dgrad(dz, w, dxs, accumulate, packed, force_direct=force_direct, compute=compute)
 
 
 def conv3x3_wgrad(xs: Sequence[torch.Tensor], dz: torch.Tensor, w_shape, want_bias: bool = False,
                   force_direct: bool = False, dw: Optional[torch.Tensor] = None, accumulate: bool = False,
                   compute: int = 0):
     _chk(*xs, dz)
-    N, _, H, W = dz.shape
-    dev = dz.device
-    if dw is None:
-        dw = torch.empty(*w_shape, dtype=torch.float32, device=dev)
-    db = torch.empty(w_shape[0], dtype=torch.float32, device=dev) if want_bias else None
-    a = L.Conv3x3Args()
-    a.N, a.H, a.W, a.Cin, a.Cout, a.n_in = N, H, W, w_shape[1], w_shape[0], len(xs)
-    _fill_segs(a.in_, xs)
-    a.dout, a.dw, a.dbias, a.force_direct, a.accumulate_dw = dz.data_ptr(), dw.data_ptr(), _p(db), int(force_direct), int(accumulate)
-    a.compute = compute
-    nb = L.load().mtbc_conv3x3_wgrad_workspace(C.byref(a))
-    ws = _ws(nb, dev)
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    _note(a, L.OP_CONV3_WGRAD)
-    L.check(L.load().mtbc_conv3x3_wgrad(C.byref(a), _s()), "conv3x3_wgrad")
-    return dw, db
+    return _conv3x3_wgrad(xs, dz, w_shape, want_bias, dw, accumulate, force_direct=force_direct, compute=compute)
 
 
 # ------------------------------------------------------------------ conv3x3 on 16-bit channel-blocked operands
@@ -281,75 +314,37 @@ class C8:
         return y
 
 
-def _fill_segs_c8(arr, tensors: Sequence["C8"]):
-    for i, t in enumerate(tensors):
-        arr[i].ptr = t.data.data_ptr()
-        arr[i].batch_stride = t.shape[1] * t.shape[2] * t.shape[3]      # 16-bit elements
-        arr[i].channels = t.shape[1]
-        arr[i].accumulate = 0
-
-
 def conv3x3_fwd_c8(xs: Sequence["C8"], w: torch.Tensor, bias: Optional[torch.Tensor], packed: torch.Tensor, out_c8: bool = False,
                    stats: bool = False, norm=None, out_partial: Optional[torch.Tensor] = None, out_fp16: bool = False):
     """z = conv3x3(concat(xs)) with the inputs already in the MFMA's 16-bit channel-blocked layout; z comes back as fp32
-    planes, or (out_c8, `out_layout = C8` of the C-ABI) as a channel-blocked 16-bit tensor of the inputs' type."""
+    planes, or (out_c8, `out_layout = C8` of the C-ABI) as a channel-blocked 16-bit tensor of the inputs' type (out_fp16: bf16 operands,
+    the output stored as fp16).  stats: also the InstanceNorm statistics partials of the epilogue.  norm = (z8, mean, rstd, gamma, beta,
+    slope) of the output tensor: the gathered dgrad + norm-backward reductions (statistics always), out_partial its planar partial."""
     _chk(w, bias)
     N, _, H, W = xs[0].shape
-    a = L.Conv3x3Args()
-    a.N, a.H, a.W, a.Cin, a.Cout, a.n_in = N, H, W, sum(x.shape[1] for x in xs), w.shape[0], len(xs)
-    _fill_segs_c8(a.in_, xs)
-    if out_c8:
-        out = torch.empty(N, w.shape[0] // 8, H * W, 8, dtype=torch.int16, device=w.device)
-        a.out_layout = L.LAYOUT_C8
-        if out_fp16:            # bf16 operands, the output stored as fp16 (out_type of the C-ABI)
-            a.out_type = 2
-    else:
-        out = torch.empty(N, w.shape[0], H, W, dtype=torch.float32, device=w.device)
-    a.w, a.w_packed, a.bias, a.out = w.data_ptr(), packed.data_ptr(), _p(bias), out.data_ptr()
-    a.compute, a.operand_layout = xs[0].compute, L.LAYOUT_C8
-    part = None
-    if norm is not None:    # gathered dgrad + norm-backward reductions: norm = (z8, mean, rstd, gamma, beta, slope) of the output tensor
+    Cout, compute = w.shape[0], xs[0].compute
+    out = torch.empty((N, Cout // 8, H * W, 8) if out_c8 else (N, Cout, H, W), dtype=torch.int16 if out_c8 else torch.float32, device=w.device)
+    ptrs = {"in": xs, "w": w, "w_packed": packed, "bias": bias, "out": out}
+    mode = dict(compute=compute, c8=True, out_c8=out_c8, out_fp16=out_fp16, bias=bias is not None, packed=True)
+    if norm is not None:
         z8n, mean, rstd, gamma, beta, slope = norm
         _chk(mean, rstd, gamma, beta, out_partial)
-        a.norm_z, a.norm_mean, a.norm_rstd, a.norm_gamma, a.norm_beta, a.norm_slope = z8n.data.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _p(gamma), _p(beta), slope
-        a.out_partial = _p(out_partial)
+        ptrs.update(norm_z=z8n, norm_mean=mean, norm_rstd=rstd, norm_gamma=gamma, norm_beta=beta, out_partial=out_partial)
+        mode.update(norm=slope, out_partial=out_partial is not None)
         stats = True
-    if stats:       # InstanceNorm statistics from the epilogue: (partials [N][slots][Cout][2], slots)
-        slots = L.load().mtbc_conv3x3_stats_slots(C.byref(a))
-        if slots <= 0:
-            raise L.MtbcError("conv3x3_fwd: no epilogue statistics for this launch")
-        part = torch.full((N, slots, w.shape[0], 2), float("nan"), dtype=torch.float32, device=w.device)
-        a.stats_partial = part.data_ptr()
-    _note(a, L.OP_CONV3_FWD)
-    L.check(L.load().mtbc_conv3x3_fwd(C.byref(a), _s()), "conv3x3_fwd(c8)")
-    z = C8(out, (N, w.shape[0], H, W), 2 if out_fp16 else xs[0].compute) if out_c8 else out
+    part = _conv3x3_fwd(N, [x.shape[1] for x in xs], Cout, H, W, ptrs, stats, **mode)
+    z = C8(out, (N, Cout, H, W), 2 if out_fp16 else compute) if out_c8 else out
     return (z, part) if stats else z
 
 
 def conv3x3_dgrad_c8(dz: "C8", w: torch.Tensor, dxs: Sequence[torch.Tensor], accumulate: Sequence[int], packed: torch.Tensor) -> None:
     """dx segments (fp32 planar, accumulate honoured; accumulate 2 = the segment is an int16 (N,C,H,W) tensor written as
-    16-bit planar values of dz's type) from dz in the 16-bit channel-blocked layout."""
-    if any(isinstance(d, C8) for d in dxs):       # accumulate = 3: channel-blocked 16-bit segments (all of them)
-        N, _, H, W = dz.shape
-        a = L.Conv3x3Args()
-        a.N, a.H, a.W, a.Cin, a.Cout, a.n_in = N, H, W, sum(d.shape[1] for d in dxs), w.shape[0], len(dxs)
-        a.w = w.data_ptr()
-        _fill_segs_c8(a.in_, dxs)
-        for i in range(len(dxs)):
-            a.in_[i].accumulate = 3
-        a.w_packed, a.dout = packed.data_ptr(), dz.data.data_ptr()
-        a.compute, a.operand_layout = dz.compute, L.LAYOUT_C8
-        _note(a, L.OP_CONV3_DGRAD)
-        L.check(L.load().mtbc_conv3x3_dgrad(C.byref(a), _s()), "conv3x3_dgrad(c8 -> c8)")
-        return
-    _chk(w, *[d for i, d in enumerate(dxs) if not (i < len(accumulate) and accumulate[i] == 2)])
-    N, _, H, W = dz.shape
-    a = _conv_args(dxs, w, N, H, W)
-    _fill_segs(a.in_, dxs, accumulate)
-    a.w_packed, a.dout = packed.data_ptr(), dz.data.data_ptr()
-    a.compute, a.operand_layout = dz.compute, L.LAYOUT_C8
-    _note(a, L.OP_CONV3_DGRAD)
-    L.check(L.load().mtbc_conv3x3_dgrad(C.byref(a), _s()), "conv3x3_dgrad(c8)")
+    16-bit planar values of dz's type) from dz in the 16-bit channel-blocked layout.  C8 segments (all of them): accumulate = 3."""
+    if any(isinstance(d, C8) for d in dxs):
+        accumulate = [3] * len(dxs)
+    else:
+        _chk(w, *[d for i, d in enumerate(dxs) if not (i < len(accumulate) and accumulate[i] == 2)])
+    _conv3x3_dgrad(dz, w, dxs, accumulate, packed, compute=dz.compute, c8=True)
 
 
 _WGRAD_SYNC: dict = {}       # device -> zeroed int32 counters of the in-kernel split-K reduction (every launch leaves them at zero)
@@ -365,31 +360,10 @@ def wgrad_sync_buffer(dev, nbytes: int) -> torch.Tensor:
 
 def conv3x3_wgrad_c8(xs: Sequence["C8"], dz: "C8", w_shape, want_bias: bool = False, dw: Optional[torch.Tensor] = None,
                      accumulate: bool = False, in_kernel_reduce: bool = True):
-    """in_kernel_reduce: the split-K partials are summed inside the launch by the last-arriving block of each group
+    """xs: C8 tensors, or the stem's ONE fp32 planar input of 1 .. L.STEM_MAX_CIN channels (dz channel-blocked either way).
+    in_kernel_reduce: the split-K partials are summed inside the launch by the last-arriving block of each group
     (mtbc_conv3x3_args.wgrad_sync); False = the reduction launch behind the kernel (another, equally fixed, summation order)."""
-    N, _, H, W = dz.shape
-    dev = dz.data.device
-    if dw is None:
-        dw = torch.empty(*w_shape, dtype=torch.float32, device=dev)
-    db = torch.empty(w_shape[0], dtype=torch.float32, device=dev) if want_bias else None
-    a = L.Conv3x3Args()
-    a.N, a.H, a.W, a.Cin, a.Cout, a.n_in = N, H, W, w_shape[1], w_shape[0], len(xs)
-    if w_shape[1] <= L.STEM_MAX_CIN and isinstance(xs[0], torch.Tensor):      # the stem: ONE fp32 planar input of 1 .. STEM_MAX_CIN channels, channel-blocked dz
-        _fill_segs(a.in_, xs)
-    else:
-        _fill_segs_c8(a.in_, xs)
-    a.dout, a.dw, a.dbias, a.accumulate_dw = dz.data.data_ptr(), dw.data_ptr(), _p(db), int(accumulate)
-    a.compute, a.operand_layout = dz.compute, L.LAYOUT_C8
-    nb = L.load().mtbc_conv3x3_wgrad_workspace(C.byref(a))
-    ws = _ws(nb, dev)
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    nsync = int(L.load().mtbc_conv3x3_wgrad_sync_bytes(C.byref(a))) if in_kernel_reduce else 0
-    if nsync:
-        sync = wgrad_sync_buffer(dev, nsync)
-        a.wgrad_sync, a.wgrad_sync_bytes = sync.data_ptr(), sync.numel() * 4
-    _note(a, L.OP_CONV3_WGRAD)
-    L.check(L.load().mtbc_conv3x3_wgrad(C.byref(a), _s()), "conv3x3_wgrad(c8)")
-    return dw, db
+    return _conv3x3_wgrad(xs, dz, w_shape, want_bias, dw, accumulate, compute=dz.compute, c8=True, in_kernel_reduce=in_kernel_reduce)
 
 
 # ------------------------------------------------------------------ instance norm + leaky relu
@@ -407,17 +381,17 @@ def instnorm_case_args(backward: bool, N: int, Cc: int, H: int, W: int, ptrs: Op
                        dy: Optional[str] = "f32", n_extra: int = 0, rank1: bool = False, rank1_grads: bool = False, rank1_acc: bool = False,
                        dbias: bool = False, acc: bool = False, defer: bool = False, inplace: bool = False) -> "L.InstNormArgs":
     """The argument struct of ONE InstanceNorm + LeakyReLU call, every field the step programs set (engine._conv_cell / _conv_cell_backward).
-    ptrs: field name -> tensor (dy_extra0 .. dy_extra3 for the fan-in); None = distinct 16-byte aligned dummies that nothing may dereference
+    ptrs: field name -> tensor, C8 or None for NULL (dy_extra0 .. dy_extra3 for the fan-in); None = distinct 16-byte aligned dummies that nothing may dereference
     (for instnorm_kernel_name).  compute: 0 = the fp32 kernels of norm.hip, 1 / 2 = out16_type.  out: "f32" planes, "p16" 16-bit planes
-    (y16 / dz16), "c8" channel-blocked (y8 / dz8).  z: "f32" planes, "c8" channel-blocked of the output type, "c8f16" channel-blocked fp16
-    under a bf16 output.  Forward: planar / planar16 = fp32 / 16-bit planes beside y8, stats_slots > 0 = statistics from the conv epilogue,
+    (y16 / dz16), "c8" channel-blocked (y8 / dz8).  z: "f32" planes, "c8" channel-blocked of the output type, "c8f16" / "c8bf16" channel-blocked fp16 / bf16
+    under an output of the other type.  Forward: planar / planar16 = fp32 / 16-bit planes beside y8, stats_slots > 0 = statistics from the conv epilogue,
     pool (+ pool_arg) = the pooled output (+ argmax codes), chunk_ws = offer the chunked-statistics workspace.  Backward: dy "f32" / "c8" /
     None, n_extra planar partials, rank1 (+ the head's own gradients, accumulated or not), pool = the routed max-pool gradient, dbias =
     dbias_pre, acc = accumulate_dparams, defer = defer_dparams, inplace = dz over dy (fp32 planes)."""
     dummy = iter(range(1 << 20, 1 << 30, 1 << 20))
 
     def ptr(name):
-        return next(dummy) if ptrs is None else ptrs[name].data_ptr()
+        return next(dummy) if ptrs is None else _p(ptrs[name])
 
     a = L.InstNormArgs()
     a.N, a.C, a.H, a.W, a.eps, a.slope = N, Cc, H, W, eps, slope
@@ -426,7 +400,7 @@ def instnorm_case_args(backward: bool, N: int, Cc: int, H: int, W: int, ptrs: Op
         a.gamma, a.beta = ptr("gamma"), ptr("beta")
     a.out16_type, a.coop_reserve_cus = compute, reserve_cus
     if z != "f32":
-        a.z_layout, a.z_type = L.LAYOUT_C8, (2 if z == "c8f16" else 0)
+        a.z_layout, a.z_type = L.LAYOUT_C8, {"c8": 0, "c8bf16": 1, "c8f16": 2}[z]
     a.y_batch_stride = a.dy_batch_stride = Cc * H * W
     if stats_slots:
         a.stats_partial, a.stats_slots = ptr("stats_partial"), stats_slots
@@ -481,14 +455,10 @@ def instnorm_case_kernel(backward: bool, *shape, **mode) -> str:
     return instnorm_kernel_name(instnorm_case_args(backward, *shape, **mode), backward)
 
 
-def _note_norm(a, backward: bool) -> None:
-    if launched is not None:
-        launched.append((L.OP_IN_BWD if backward else L.OP_IN_FWD, instnorm_kernel_name(a, backward)))
-
-
 def instnorm_launch(a: "L.InstNormArgs", backward: bool) -> None:
     """mtbc_instnorm_lrelu_fwd / _bwd on the current stream for an argument struct of instnorm_case_args(ptrs=...)."""
-    _note_norm(a, backward)
+    if launched is not None:
+        launched.append((L.OP_IN_BWD if backward else L.OP_IN_FWD, instnorm_kernel_name(a, backward)))
     lib = L.load()
     L.check((lib.mtbc_instnorm_lrelu_bwd if backward else lib.mtbc_instnorm_lrelu_fwd)(C.byref(a), _s()), "instnorm_bwd" if backward else "instnorm_fwd")
 
@@ -515,43 +485,28 @@ def instnorm_lrelu_fwd(z, gamma=None, beta=None, eps=1e-5, slope=0.01, out16: in
     N, Cc, H, W = z.shape
     y = torch.empty_like(z, dtype=torch.int16 if out16 else torch.float32)
     mean = torch.empty(N * Cc, dtype=torch.float32, device=z.device)
-    rstd = torch.empty_like(mean)
-    a = L.InstNormArgs()
-    a.N, a.C, a.H, a.W, a.eps, a.slope = N, Cc, H, W, eps, slope
-    a.z, a.gamma, a.beta, a.y, a.y_batch_stride = z.data_ptr(), _p(gamma), _p(beta), y.data_ptr(), Cc * H * W
-    a.mean, a.rstd = mean.data_ptr(), rstd.data_ptr()
-    if out16:
-        a.y, a.y16, a.out16_type = None, y.data_ptr(), out16
-    nb = L.load().mtbc_instnorm_fwd_workspace(C.byref(a))
+    ptrs = {"z": z, "gamma": gamma, "beta": beta, "y": y, "y16": y, "mean": mean, "rstd": torch.empty_like(mean)}
+    mode = dict(compute=out16, out="p16" if out16 else "f32", affine=gamma is not None or beta is not None, eps=eps, slope=slope)
+    nb = instnorm_case_args(False, N, Cc, H, W, **mode).workspace_bytes         # (dummy pointers) the chunked-statistics workspace, if wanted
     if nb:
-        ws = _ws(nb, z.device)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    _note_norm(a, False)
-    L.check(L.load().mtbc_instnorm_lrelu_fwd(C.byref(a), _s()), "instnorm_fwd")
-    return y, mean, rstd
+        ptrs["workspace"] = _ws(nb, z.device)
+    instnorm_launch(instnorm_case_args(False, N, Cc, H, W, ptrs=ptrs, **mode), False)
+    return y, mean, ptrs["rstd"]
 
 
 def instnorm_lrelu_bwd(z, dy, mean, rstd, gamma=None, beta=None, eps=1e-5, slope=0.01, inplace=False,
                        dbias_pre=None, dy_extra=(), out16: int = 0):
     _chk(z, dy, mean, rstd, gamma, beta, dbias_pre, *dy_extra)
     N, Cc, H, W = z.shape
+    inplace = inplace and not out16
     dz = torch.empty_like(z, dtype=torch.int16) if out16 else (dy if inplace else torch.empty_like(z))
     dg = torch.empty(Cc, dtype=torch.float32, device=z.device) if gamma is not None else None
     db = torch.empty(Cc, dtype=torch.float32, device=z.device) if gamma is not None else None
-    ws = _ws(N * Cc * 12, z.device)
-    a = L.InstNormArgs()
-    a.N, a.C, a.H, a.W, a.eps, a.slope = N, Cc, H, W, eps, slope
-    a.z, a.gamma, a.beta, a.mean, a.rstd = z.data_ptr(), _p(gamma), _p(beta), mean.data_ptr(), rstd.data_ptr()
-    a.dy, a.dy_batch_stride, a.dz, a.dgamma, a.dbeta = dy.data_ptr(), Cc * H * W, dz.data_ptr(), _p(dg), _p(db)
-    a.dbias_pre = _p(dbias_pre)
-    if out16:
-        a.dz, a.dz16, a.out16_type = None, dz.data_ptr(), out16
-    a.n_dy_extra = len(dy_extra)
-    for k_, t_ in enumerate(dy_extra):
-        a.dy_extra[k_] = t_.data_ptr()
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    _note_norm(a, True)
-    L.check(L.load().mtbc_instnorm_lrelu_bwd(C.byref(a), _s()), "instnorm_bwd")
+    ptrs = {"z": z, "gamma": gamma, "beta": beta, "mean": mean, "rstd": rstd, "dy": dy, "dz": dz, "dz16": dz, "dgamma": dg, "dbeta": db,
+            "dbias_pre": dbias_pre, "workspace": _ws(N * Cc * 12, z.device), **{f"dy_extra{k_}": t_ for k_, t_ in enumerate(dy_extra)}}
+    a = instnorm_case_args(True, N, Cc, H, W, ptrs=ptrs, compute=out16, out="p16" if out16 else "f32", affine=gamma is not None or beta is not None, eps=eps, slope=slope,
+                           n_extra=len(dy_extra), dbias=dbias_pre is not None, inplace=inplace)
+    instnorm_launch(a, True)
     return dz, dg, db
 
 
@@ -567,43 +522,41 @@ def coop_state(dev) -> torch.Tensor:
     return _coop_states[key]
 
 
+def _z_kind(z, compute: int) -> str:
+    """instnorm_case_args' `z` of a wrapper's operand: fp32 planes, or a C8 tensor of the output type `compute` or of the other 16-bit type."""
+    if not isinstance(z, C8):
+        return "f32"
+    return "c8" if z.compute == compute else ("c8f16" if z.compute == 2 else "c8bf16")
+
+
 def instnorm_lrelu_fwd_c8(z, gamma=None, beta=None, eps=1e-5, slope=0.01, compute: Optional[int] = None, want_planar: bool = False,
                           stats: Optional[torch.Tensor] = None, want_pool: bool = False, planar16: bool = False, reserve_cus: int = 0):
     """InstanceNorm + LeakyReLU straight into the 16-bit channel-blocked layout (y8 of the C-ABI).  z: fp32 planes, or a
     C8 tensor (z_layout = C8: the conv output of the 16-bit modes).  planar16 (with stats): the planar copy is an int16
-    (N,C,H,W) tensor of the output type (y16 beside y8).  reserve_cus: coop_reserve_cus of the C-ABI."""
+    (N,C,H,W) tensor of the output type (y16 beside y8).  stats: [N][slots][C][2] from conv3x3_fwd_c8(stats=True).  want_pool: the
+    streaming pass also writes the activation's 2x2 max-pool + argmax codes (pool_y8 / pool_arg).  reserve_cus: coop_reserve_cus of the C-ABI."""
     z8 = z if isinstance(z, C8) else None
     if compute is None:         # output type: given, else the type of a channel-blocked z, else bf16
         compute = z8.compute if z8 is not None else 1
-    zt = z8.data if z8 is not None else z
-    _chk(zt if z8 is None else None, gamma, beta)
+    _chk(z if z8 is None else None, gamma, beta)
     N, Cc, H, W = z.shape
-    dev = zt.device
+    dev = (z8.data if z8 is not None else z).device
     y8 = torch.empty(N, Cc // 8, H * W, 8, dtype=torch.int16, device=dev)
     y = torch.empty(N, Cc, H, W, dtype=torch.int16 if planar16 else torch.float32, device=dev) if (want_planar or planar16) else None
     mean = torch.empty(N * Cc, dtype=torch.float32, device=dev)
     rstd = torch.empty_like(mean)
-    a = L.InstNormArgs()
-    a.N, a.C, a.H, a.W, a.eps, a.slope = N, Cc, H, W, eps, slope
-    a.z, a.gamma, a.beta, a.y, a.y_batch_stride = zt.data_ptr(), _p(gamma), _p(beta), (None if planar16 else _p(y)), Cc * H * W
-    if planar16:
-        a.y16 = y.data_ptr()
-    a.z_layout = L.LAYOUT_C8 if z8 is not None else L.LAYOUT_PLANAR
-    if z8 is not None and z8.compute != compute:
-        a.z_type = z8.compute           # fp16 z with bf16 outputs
-    a.mean, a.rstd = mean.data_ptr(), rstd.data_ptr()
-    a.y8, a.out16_type, a.coop_state, a.coop_reserve_cus = y8.data_ptr(), compute, coop_state(dev).data_ptr(), reserve_cus
-    if stats is not None:       # [N][slots][C][2] from conv3x3_fwd_c8(stats=True)
-        a.stats_partial, a.stats_slots = stats.data_ptr(), stats.shape[1]
     yp8 = parg = None
-    if want_pool:               # the streaming pass also writes the activation's 2x2 max-pool + argmax codes (pool_y8 / pool_arg)
+    if want_pool:
         yp8 = torch.empty(N, Cc // 8, (H // 2) * (W // 2), 8, dtype=torch.int16, device=dev)
         parg = torch.empty(N, Cc // 8, (H // 2) * (W // 2), dtype=torch.int16, device=dev)
-        a.pool_y8, a.pool_arg = yp8.data_ptr(), parg.data_ptr()
+    ptrs = {"z": z, "gamma": gamma, "beta": beta, "mean": mean, "rstd": rstd, "y8": y8, "y": y, "y16": y, "coop_state": coop_state(dev),
+            "stats_partial": stats, "pool_y8": yp8, "pool_arg": parg}
+    a = instnorm_case_args(False, N, Cc, H, W, ptrs=ptrs, compute=compute, out="c8", z=_z_kind(z, compute), affine=gamma is not None or beta is not None,
+                           eps=eps, slope=slope, reserve_cus=reserve_cus, stats_slots=stats.shape[1] if stats is not None else 0,
+                           planar=y is not None, planar16=planar16, pool=want_pool, chunk_ws=False)
     if not L.load().mtbc_instnorm_c8_supported(C.byref(a), 0):
         raise L.MtbcError("instnorm_fwd: shape not supported with a channel-blocked output")
-    _note_norm(a, False)
-    L.check(L.load().mtbc_instnorm_lrelu_fwd(C.byref(a), _s()), "instnorm_fwd(c8)")
+    instnorm_launch(a, False)
     if want_pool:
         return C8(y8, z.shape, compute), mean, rstd, y, C8(yp8, (N, Cc, H // 2, W // 2), compute), parg
     return C8(y8, z.shape, compute), mean, rstd, y
@@ -614,49 +567,34 @@ def instnorm_lrelu_bwd_c8(z, dy, mean, rstd, gamma=None, beta=None, eps=1e-5, sl
                           pool=None, defer_dparams: bool = False, reserve_cus: int = 0):
     """z / dy: fp32 planes or C8 tensors (z_layout / dy_layout = C8); dy_extra (with a C8 dy only): an fp32 planar partial
     gradient added while loading; rank1 = (dyhead (N,1,H,W), w (C)): the rank-1 gradient term of a one-output 1x1 head (dy may
-    then be None).  reserve_cus: coop_reserve_cus of the C-ABI."""
-    zt = z.data if isinstance(z, C8) else z
-    dyt = dy.data if isinstance(dy, C8) else dy
+    then be None), rank1_grads: the head's own weight / bias gradient from the same pass.  pool = (gradient of the 2x2 max-pool of this
+    activation (N,C,H/2,W/2) fp32, argmax codes from maxpool2_fwd_c8).  stats: {sum g, sum g * xhat} partials from conv3x3_fwd_c8(norm=...).
+    defer_dparams: leave the partials in the workspace, reduce them with the batched entry point afterwards.  reserve_cus:
+    coop_reserve_cus of the C-ABI."""
     if compute is None:         # output (and channel-blocked dy) type: given, else dy's, else z's, else bf16
         compute = dy.compute if isinstance(dy, C8) else (z.compute if isinstance(z, C8) else 1)
-    _chk(mean, rstd, gamma, beta, dbias_pre, dy_extra)
+    _chk(mean, rstd, gamma, beta, dbias_pre, dy_extra, *(rank1 or ()), *(pool[:1] if pool is not None else ()))
     N, Cc, H, W = z.shape
-    dev = zt.device
+    dev = (z.data if isinstance(z, C8) else z).device
     dz8 = torch.empty(N, Cc // 8, H * W, 8, dtype=torch.int16, device=dev)
     dg = torch.empty(Cc, dtype=torch.float32, device=dev) if gamma is not None else None
     db = torch.empty(Cc, dtype=torch.float32, device=dev) if gamma is not None else None
-    ws = _ws(N * (Cc + 1) * 262 * 4, dev)
-    a = L.InstNormArgs()
-    a.N, a.C, a.H, a.W, a.eps, a.slope = N, Cc, H, W, eps, slope
-    a.z, a.gamma, a.beta, a.mean, a.rstd = zt.data_ptr(), _p(gamma), _p(beta), mean.data_ptr(), rstd.data_ptr()
-    a.dy, a.dy_batch_stride, a.dgamma, a.dbeta, a.dbias_pre = (dyt.data_ptr() if dyt is not None else None), Cc * H * W, _p(dg), _p(db), _p(dbias_pre)
-    if rank1 is not None:
-        _chk(*rank1)
-        a.dy_rank1, a.dy_rank1_w = rank1[0].data_ptr(), rank1[1].data_ptr()
-    if pool is not None:        # (gradient of the 2x2 max-pool of this activation (N,C,H/2,W/2) fp32, argmax codes from maxpool2_fwd_c8)
-        _chk(pool[0])
-        a.dy_pool, a.dy_pool_arg = pool[0].data_ptr(), pool[1].data_ptr()
     hdw = hdb = None
-    if rank1_grads:             # the head's own weight / bias gradient from the same pass
+    if rank1_grads:
         hdw, hdb = torch.empty(Cc, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.float32, device=dev)
-        a.dy_rank1_dw, a.dy_rank1_db = hdw.data_ptr(), hdb.data_ptr()
-    a.z_layout = L.LAYOUT_C8 if isinstance(z, C8) else L.LAYOUT_PLANAR
-    if isinstance(z, C8) and z.compute != compute:
-        a.z_type = z.compute
-    a.dy_layout = L.LAYOUT_C8 if isinstance(dy, C8) else L.LAYOUT_PLANAR
-    if dy_extra is not None:
-        a.n_dy_extra = 1
-        a.dy_extra[0] = dy_extra.data_ptr()
-    a.dz8, a.out16_type, a.coop_state, a.coop_reserve_cus = dz8.data_ptr(), compute, coop_state(dev).data_ptr(), reserve_cus
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    if stats is not None:       # {sum g, sum g * xhat} partials from conv3x3_fwd_c8(norm=...)
-        a.stats_partial, a.stats_slots = stats.data_ptr(), stats.shape[1]
+    ws = _ws(N * (Cc + 1) * 262 * 4, dev)
+    r1, pl = rank1 or (None, None), pool or (None, None)
+    ptrs = {"z": z, "gamma": gamma, "beta": beta, "mean": mean, "rstd": rstd, "dy": dy, "dy_extra0": dy_extra, "dz8": dz8, "dgamma": dg, "dbeta": db,
+            "dbias_pre": dbias_pre, "coop_state": coop_state(dev), "workspace": ws, "stats_partial": stats, "dy_rank1": r1[0], "dy_rank1_w": r1[1],
+            "dy_rank1_dw": hdw, "dy_rank1_db": hdb, "dy_pool": pl[0], "dy_pool_arg": pl[1]}
+    a = instnorm_case_args(True, N, Cc, H, W, ptrs=ptrs, compute=compute, out="c8", z=_z_kind(z, compute), affine=gamma is not None or beta is not None,
+                           eps=eps, slope=slope, reserve_cus=reserve_cus, stats_slots=stats.shape[1] if stats is not None else 0,
+                           dy=None if dy is None else ("c8" if isinstance(dy, C8) else "f32"), n_extra=int(dy_extra is not None),
+                           rank1=rank1 is not None or rank1_grads, rank1_grads=rank1_grads, pool=pool is not None, dbias=dbias_pre is not None,
+                           defer=defer_dparams)
     if not L.load().mtbc_instnorm_c8_supported(C.byref(a), 1):
         raise L.MtbcError("instnorm_bwd: shape not supported with a channel-blocked output")
-    if defer_dparams:           # leave the partials in the workspace, reduce them with the batched entry point afterwards
-        a.defer_dparams = 1
-    _note_norm(a, True)
-    L.check(L.load().mtbc_instnorm_lrelu_bwd(C.byref(a), _s()), "instnorm_bwd(c8)")
+    instnorm_launch(a, True)
     if defer_dparams:
         instnorm_dparam_many(instnorm_dparam_desc(a, ws.data_ptr()))
     if rank1_grads:
@@ -674,24 +612,18 @@ def maxpool2_fwd(x):
     _chk(x)
     N, Cc, H, W = x.shape
     y = torch.empty(N, Cc, H // 2, W // 2, dtype=torch.float32, device=x.device)
-    a = L.MaxPoolArgs()
-    a.N, a.C, a.H, a.W = N, Cc, H, W
-    a.x, a.x_batch_stride, a.y, a.y_batch_stride = x.data_ptr(), Cc * H * W, y.data_ptr(), Cc * H * W // 4
-    L.check(L.load().mtbc_maxpool2_fwd(C.byref(a), _s()), "maxpool_fwd")
+    small_op_launch(maxpool_case_args(L.OP_POOL_FWD, N, Cc, H, W, ptrs={"x": x, "y": y}))
     return y
 
 
 def maxpool2_bwd(x, dy, dx=None, accumulate=False):
-    _chk(x, dy, dx)
+    """x: fp32 planes, or a C8 tensor (dy / dx stay fp32 planes)."""
+    _chk(None if isinstance(x, C8) else x, dy, dx)
     N, Cc, H, W = x.shape
     if dx is None:
-        dx = torch.empty_like(x)
-    a = L.MaxPoolArgs()
-    a.N, a.C, a.H, a.W = N, Cc, H, W
-    a.x, a.x_batch_stride = x.data_ptr(), Cc * H * W
-    a.dy, a.dy_batch_stride, a.dx, a.dx_batch_stride = dy.data_ptr(), Cc * H * W // 4, dx.data_ptr(), Cc * H * W
-    a.accumulate_dx = int(accumulate)
-    L.check(L.load().mtbc_maxpool2_bwd(C.byref(a), _s()), "maxpool_bwd")
+        dx = torch.empty(N, Cc, H, W, dtype=torch.float32, device=dy.device)
+    small_op_launch(maxpool_case_args(L.OP_POOL_BWD, N, Cc, H, W, ptrs={"x": x, "y": None, "dy": dy, "dx": dx},
+                                      compute=x.compute if isinstance(x, C8) else 0, acc_dx=accumulate))
     return dx
 
 
@@ -700,29 +632,13 @@ def maxpool2_fwd_c8(x8: "C8", want_argmax: bool = False):
     (N, C/8, H/2*W/2) int16 codes of where each window's maximum sits (mtbc_maxpool_args.argmax)."""
     N, Cc, H, W = x8.shape
     y = torch.empty(N, Cc // 8, (H // 2) * (W // 2), 8, dtype=torch.int16, device=x8.data.device)
-    a = L.MaxPoolArgs()
-    a.N, a.C, a.H, a.W, a.layout, a.type16 = N, Cc, H, W, L.LAYOUT_C8, x8.compute
-    a.x, a.x_batch_stride, a.y, a.y_batch_stride = x8.data.data_ptr(), Cc * H * W, y.data_ptr(), Cc * H * W // 4
     arg = torch.empty(N, Cc // 8, (H // 2) * (W // 2), dtype=torch.int16, device=x8.data.device) if want_argmax else None
-    if arg is not None:
-        a.argmax = arg.data_ptr()
-    L.check(L.load().mtbc_maxpool2_fwd(C.byref(a), _s()), "maxpool_fwd c8")
+    small_op_launch(maxpool_case_args(L.OP_POOL_FWD, N, Cc, H, W, ptrs={"x": x8, "y": y, "argmax": arg}, compute=x8.compute, argmax=want_argmax))
     out = C8(y, (N, Cc, H // 2, W // 2), x8.compute)
     return (out, arg) if want_argmax else out
 
 
-def maxpool2_bwd_c8(x8: "C8", dy, dx=None, accumulate=False):
-    _chk(dy, dx)
-    N, Cc, H, W = x8.shape
-    if dx is None:
-        dx = torch.empty(N, Cc, H, W, dtype=torch.float32, device=dy.device)
-    a = L.MaxPoolArgs()
-    a.N, a.C, a.H, a.W, a.layout, a.type16 = N, Cc, H, W, L.LAYOUT_C8, x8.compute
-    a.x, a.x_batch_stride = x8.data.data_ptr(), Cc * H * W
-    a.dy, a.dy_batch_stride, a.dx, a.dx_batch_stride = dy.data_ptr(), Cc * H * W // 4, dx.data_ptr(), Cc * H * W
-    a.accumulate_dx = int(accumulate)
-    L.check(L.load().mtbc_maxpool2_bwd(C.byref(a), _s()), "maxpool_bwd c8")
-    return dx
+maxpool2_bwd_c8 = maxpool2_bwd
 
 
 # ------------------------------------------------------------------ conv transpose (k == stride)
@@ -736,24 +652,20 @@ def convT_kernel_name(a: "L.ConvTArgs", op: int, dgrad_next: Optional["L.ConvTAr
     return buf.value.decode()
 
 
-_CT_DUMMY = {n: (i + 1) << 20 for i, n in enumerate(("x", "w", "bias", "y", "dy", "dx", "dw", "dbias", "workspace"))}
+_CT_DUMMY = _dummies("x", "w", "bias", "y", "dy", "dx", "dw", "dbias", "workspace")
 
 
 def convT_case_args(op: int, N: int, Cin: int, Cout: int, H: int, W: int, k: int = 2, ptrs: Optional[dict] = None, compute: int = 0,
                     dy16: bool = False, x16: bool = False, x_c8: bool = False, y_c8: bool = False, bias: bool = True,
                     acc_dx: bool = False, acc_dw: bool = False, strides: Optional[dict] = None, workspace: bool = True) -> "L.ConvTArgs":
     """The argument struct of ONE transposed-convolution call as the step programs fill it (engine.StepPlan.convT / convT_head).
-    ptrs: field name (x, w, bias, y, dy, dx, dw, dbias, workspace) -> tensor; None = distinct 16-byte aligned dummies that nothing may
+    ptrs: field name (x, w, bias, y, dy, dx, dw, dbias, workspace) -> tensor, C8 or None for NULL; None = distinct 16-byte aligned dummies that nothing may
     dereference (for convT_kernel_name), the same address for the same field of every call so that a WGRAD and the DGRAD behind it
     describe one problem.  Forward: x_c8 / y_c8 = 16-bit channel-blocked input / output of type `compute`; bias = with a bias.
     Backward: `compute` = the MFMA operand type, dy16 / x16 = dy / x as 16-bit planes of that type, bias = with dbias (weight gradient),
     acc_dx / acc_dw = accumulate.  strides: field name (x, y, dy, dx) -> batch stride in elements of that tensor where the tensor is a
     channel-range view of a wider buffer; dense otherwise.  workspace = False leaves the weight gradient without one."""
-    strides = strides or {}
-
-    def ptr(name):
-        return _CT_DUMMY[name] if ptrs is None else ptrs[name].data_ptr()
-
+    strides, ptr = strides or {}, _ptr(ptrs, _CT_DUMMY.__getitem__)
     a = L.ConvTArgs()
     a.N, a.H, a.W, a.Cin, a.Cout, a.k = N, H, W, Cin, Cout, k
     a.w = ptr("w")
@@ -801,70 +713,42 @@ def convT_launch(a: "L.ConvTArgs", op: int) -> None:
     L.check(fn(C.byref(a), _s()), what)
 
 
-def _ct_args(x, w, k):
-    a = L.ConvTArgs()
+def _convT_fwd(x, w, bias, k, compute: int = 0, y_c8: bool = False) -> torch.Tensor:
     N, Cin, H, W = x.shape
-    a.N, a.H, a.W, a.Cin, a.Cout, a.k = N, H, W, Cin, w.shape[1], k
-    a.x, a.x_batch_stride, a.w = x.data_ptr(), Cin * H * W, w.data_ptr()
-    return a
+    cout, x_c8 = w.shape[1], isinstance(x, C8)
+    y = torch.empty((N, cout // 8, H * k * W * k, 8) if y_c8 else (N, cout, H * k, W * k), dtype=torch.int16 if y_c8 else torch.float32, device=w.device)
+    a = convT_case_args(L.OP_CONVT_FWD, N, Cin, cout, H, W, k, ptrs={"x": x, "w": w, "bias": bias, "y": y}, compute=compute, x_c8=x_c8, y_c8=y_c8)
+    if y_c8 and not L.load().mtbc_convT_fwd_c8_supported(C.byref(a)):
+        raise L.MtbcError("convT_fwd: shape not supported with " + ("channel-blocked input and output" if x_c8 else "a channel-blocked output"))
+    convT_launch(a, L.OP_CONVT_FWD)
+    return y
 
 
 def convT_fwd(x, w, bias, k):
     _chk(x, w, bias)
-    N, Cin, H, W = x.shape
-    y = torch.empty(N, w.shape[1], H * k, W * k, dtype=torch.float32, device=x.device)
-    a = _ct_args(x, w, k)
-    a.bias, a.y, a.y_batch_stride = _p(bias), y.data_ptr(), y[0].numel()
-    convT_note(a, L.OP_CONVT_FWD)
-    L.check(L.load().mtbc_convT_fwd(C.byref(a), _s()), "convT_fwd")
-    return y
+    return _convT_fwd(x, w, bias, k)
 
 
 def convT_fwd_c8(x, w, bias, k, compute: int) -> "C8":
     """ConvTranspose2d(k = s) forward written straight into the 16-bit channel-blocked layout (y_layout = C8)."""
     _chk(x, w, bias)
-    a = _ct_args(x, w, k)
-    N, _, H, W = x.shape
-    cout = w.shape[1]
-    y = torch.empty(N, cout // 8, H * k * W * k, 8, dtype=torch.int16, device=x.device)
-    a.bias, a.y, a.y_batch_stride = _p(bias), y.data_ptr(), cout * H * k * W * k
-    a.y_layout, a.y_type = L.LAYOUT_C8, compute
-    if not L.load().mtbc_convT_fwd_c8_supported(C.byref(a)):
-        raise L.MtbcError("convT_fwd: shape not supported with a channel-blocked output")
-    convT_note(a, L.OP_CONVT_FWD)
-    L.check(L.load().mtbc_convT_fwd(C.byref(a), _s()), "convT_fwd(c8)")
-    return C8(y, (N, cout, H * k, W * k), compute)
+    return C8(_convT_fwd(x, w, bias, k, compute, True), (x.shape[0], w.shape[1], x.shape[2] * k, x.shape[3] * k), compute)
 
 
 def convT_fwd_c8_lp(x8: "C8", w, bias, k) -> "C8":
     """ConvTranspose2d(k = s = 2) forward on the 16-bit MFMA, input and output channel-blocked (x_layout = y_layout = C8)."""
     _chk(w, bias)
-    N, Cin, H, W = x8.shape
-    cout = w.shape[1]
-    a = L.ConvTArgs()
-    a.N, a.H, a.W, a.Cin, a.Cout, a.k = N, H, W, Cin, cout, k
-    a.x, a.x_batch_stride, a.w = x8.data.data_ptr(), Cin * H * W, w.data_ptr()
-    y = torch.empty(N, cout // 8, H * k * W * k, 8, dtype=torch.int16, device=w.device)
-    a.bias, a.y, a.y_batch_stride = _p(bias), y.data_ptr(), cout * H * k * W * k
-    a.y_layout, a.y_type, a.x_layout = L.LAYOUT_C8, x8.compute, L.LAYOUT_C8
-    if not L.load().mtbc_convT_fwd_c8_supported(C.byref(a)):
-        raise L.MtbcError("convT_fwd: shape not supported with channel-blocked input and output")
-    convT_note(a, L.OP_CONVT_FWD)
-    L.check(L.load().mtbc_convT_fwd(C.byref(a), _s()), "convT_fwd(c8 -> c8)")
-    return C8(y, (N, cout, H * k, W * k), x8.compute)
+    return C8(_convT_fwd(x8, w, bias, k, x8.compute, True), (x8.shape[0], w.shape[1], x8.shape[2] * k, x8.shape[3] * k), x8.compute)
 
 
 def convT_dgrad(x, w, dy, k, dx=None, accumulate=False, compute=0, dy16=False):
-    """dy16: dy is an int16 (N,Cout,kH,kW) tensor holding 16-bit planar values of the type of `compute`."""
+    """dy16: dy is an int16 (N,Cout,kH,kW) tensor holding 16-bit planar values of the type of `compute`.  (x gives the shape of dx only.)"""
     _chk(x, w, None if dy16 else dy, dx)
     if dx is None:
         dx = torch.empty_like(x)
-    a = _ct_args(x, w, k)
-    a.compute = compute
-    a.dy_type16 = compute if dy16 else 0
-    a.dy, a.dy_batch_stride, a.dx, a.dx_batch_stride, a.accumulate_dx = dy.data_ptr(), dy[0].numel(), dx.data_ptr(), x[0].numel(), int(accumulate)
-    convT_note(a, L.OP_CONVT_DGRAD)
-    L.check(L.load().mtbc_convT_dgrad(C.byref(a), _s()), "convT_dgrad")
+    N, Cin, H, W = x.shape
+    convT_launch(convT_case_args(L.OP_CONVT_DGRAD, N, Cin, w.shape[1], H, W, k, ptrs={"w": w, "dy": dy, "dx": dx}, compute=compute, dy16=dy16,
+                                 acc_dx=accumulate), L.OP_CONVT_DGRAD)
     return dx
 
 
@@ -873,62 +757,25 @@ def convT_wgrad(x, w, dy, k, want_bias=True, compute=0, dy16=False, x16=False):
     _chk(None if x16 else x, w, None if dy16 else dy)
     dw = torch.empty_like(w)
     db = torch.empty(w.shape[1], dtype=torch.float32, device=x.device) if want_bias else None
-    a = _ct_args(x, w, k)
-    a.compute = compute
-    a.dy_type16 = compute if dy16 else 0
-    a.x_type16 = compute if x16 else 0
-    a.dy, a.dy_batch_stride, a.dw, a.dbias = dy.data_ptr(), dy[0].numel(), dw.data_ptr(), _p(db)
-    ws = _ws(L.load().mtbc_convT_wgrad_workspace(C.byref(a)), x.device)
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    convT_note(a, L.OP_CONVT_WGRAD)
-    L.check(L.load().mtbc_convT_wgrad(C.byref(a), _s()), "convT_wgrad")
+    N, Cin, H, W = x.shape
+    case = lambda ptrs: convT_case_args(L.OP_CONVT_WGRAD, N, Cin, w.shape[1], H, W, k, ptrs=ptrs, compute=compute, dy16=dy16, x16=x16, bias=want_bias)      # noqa: E731
+    ptrs = {"x": x, "w": w, "dy": dy, "dw": dw, "dbias": db, "workspace": _ws(case(None).workspace_bytes, x.device)}
+    convT_launch(case(ptrs), L.OP_CONVT_WGRAD)
     return dw, db
 
 
 # ------------------------------------------------------------------ conv1x1
-def _c1_args(x, w):
-    a = L.Conv1x1Args()
-    N, Cin, H, W = x.shape
-    a.N, a.H, a.W, a.Cin, a.Cout = N, H, W, Cin, w.shape[0]
-    a.x, a.x_batch_stride, a.w = x.data_ptr(), Cin * H * W, w.data_ptr()
-    return a
-
-
 def conv1x1_fwd(x, w, bias):
-    _chk(x, w, bias)
-    N, _, H, W = x.shape
-    y = torch.empty(N, w.shape[0], H, W, dtype=torch.float32, device=x.device)
-    a = _c1_args(x, w)
-    a.bias, a.y = _p(bias), y.data_ptr()
-    L.check(L.load().mtbc_conv1x1_fwd(C.byref(a), _s()), "conv1x1_fwd")
-    return y
-
-
-def conv1x1_bwd(x, w, dy):
-    _chk(x, w, dy)
-    dx, dw = torch.empty_like(x), torch.empty_like(w)
-    db = torch.empty(w.shape[0], dtype=torch.float32, device=x.device)
-    a = _c1_args(x, w)
-    a.dy, a.dx, a.dx_batch_stride = dy.data_ptr(), dx.data_ptr(), x[0].numel()
-    L.check(L.load().mtbc_conv1x1_dgrad(C.byref(a), _s()), "conv1x1_dgrad")
-    a.dw, a.dbias = dw.data_ptr(), db.data_ptr()
-    ws = _ws(L.load().mtbc_conv1x1_wgrad_workspace(C.byref(a)), x.device)
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    L.check(L.load().mtbc_conv1x1_wgrad(C.byref(a), _s()), "conv1x1_wgrad")
-    return dx, dw, db
-
-
-def conv1x1_fwd_c8(x8: "C8", w, bias):
-    """1x1 conv reading the channel-blocked 16-bit activation (mtbc_conv1x1_args.x_layout = MTBC_LAYOUT_C8)."""
-    _chk(w, bias)
-    N, Cin, H, W = x8.shape
+    """x: fp32 planes, or a C8 tensor (mtbc_conv1x1_args.x_layout = MTBC_LAYOUT_C8)."""
+    _chk(None if isinstance(x, C8) else x, w, bias)
+    N, Cin, H, W = x.shape
     y = torch.empty(N, w.shape[0], H, W, dtype=torch.float32, device=w.device)
-    a = L.Conv1x1Args()
-    a.N, a.H, a.W, a.Cin, a.Cout = N, H, W, Cin, w.shape[0]
-    a.x, a.x_batch_stride, a.w, a.x_layout, a.x_type = x8.data.data_ptr(), Cin * H * W, w.data_ptr(), L.LAYOUT_C8, x8.compute
-    a.bias, a.y = _p(bias), y.data_ptr()
-    L.check(L.load().mtbc_conv1x1_fwd(C.byref(a), _s()), "conv1x1_fwd c8")
+    small_op_launch(conv1x1_case_args(L.OP_CONV1_FWD, N, Cin, w.shape[0], H, W, ptrs={"x": x, "w": w, "bias": bias, "y": y},
+                                      compute=x.compute if isinstance(x, C8) else 0))
     return y
+
+
+conv1x1_fwd_c8 = conv1x1_fwd
 
 
 def conv1x1_wgrad_c8(x8: "C8", w, dy, accumulate=False, dw=None, db=None):
@@ -936,59 +783,10 @@ def conv1x1_wgrad_c8(x8: "C8", w, dy, accumulate=False, dw=None, db=None):
     N, Cin, H, W = x8.shape
     dw = torch.empty_like(w) if dw is None else dw
     db = torch.empty(w.shape[0], dtype=torch.float32, device=w.device) if db is None else db
-    a = L.Conv1x1Args()
-    a.N, a.H, a.W, a.Cin, a.Cout = N, H, W, Cin, w.shape[0]
-    a.x, a.x_batch_stride, a.w, a.x_layout, a.x_type = x8.data.data_ptr(), Cin * H * W, w.data_ptr(), L.LAYOUT_C8, x8.compute
-    a.dy, a.dw, a.dbias, a.accumulate_dw = dy.data_ptr(), dw.data_ptr(), db.data_ptr(), int(accumulate)
-    ws = _ws(L.load().mtbc_conv1x1_wgrad_workspace(C.byref(a)), w.device)
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    L.check(L.load().mtbc_conv1x1_wgrad(C.byref(a), _s()), "conv1x1_wgrad c8")
+    case = lambda ptrs: conv1x1_case_args(L.OP_CONV1_WGRAD, N, Cin, w.shape[0], H, W, ptrs=ptrs, compute=x8.compute, acc_dw=accumulate)      # noqa: E731
+    ptrs = {"x": x8, "w": w, "dy": dy, "dw": dw, "dbias": db, "workspace": _ws(case(None).u.conv1.workspace_bytes, w.device)}
+    small_op_launch(case(ptrs))
     return dw, db
-
-
-# ------------------------------------------------------------------ head
-def gap_fwd(x):
-    _chk(x)
-    N, Cc, H, W = x.shape
-    y = torch.empty(N, Cc, dtype=torch.float32, device=x.device)
-    a = L.GapArgs()
-    a.N, a.C, a.H, a.W, a.x, a.y = N, Cc, H, W, x.data_ptr(), y.data_ptr()
-    L.check(L.load().mtbc_gap_fwd(C.byref(a), _s()), "gap_fwd")
-    return y
-
-
-def gap_bwd(dy, H, W):
-    _chk(dy)
-    N, Cc = dy.shape
-    dx = torch.empty(N, Cc, H, W, dtype=torch.float32, device=dy.device)
-    a = L.GapArgs()
-    a.N, a.C, a.H, a.W, a.dy, a.dx = N, Cc, H, W, dy.data_ptr(), dx.data_ptr()
-    L.check(L.load().mtbc_gap_bwd(C.byref(a), _s()), "gap_bwd")
-    return dx
-
-
-def linear_fwd(x, w, b, relu=False):
-    _chk(x, w, b)
-    y = torch.empty(x.shape[0], w.shape[0], dtype=torch.float32, device=x.device)
-    a = L.LinearArgs()
-    a.N, a.In, a.Out, a.relu = x.shape[0], x.shape[1], w.shape[0], int(relu)
-    a.x, a.w, a.bias, a.y = x.data_ptr(), w.data_ptr(), _p(b), y.data_ptr()
-    L.check(L.load().mtbc_linear_fwd(C.byref(a), _s()), "linear_fwd")
-    return y
-
-
-def linear_bwd(x, w, y, dy, relu=False):
-    _chk(x, w, y, dy)
-    dx, dw = torch.empty_like(x), torch.empty_like(w)
-    db = torch.empty(w.shape[0], dtype=torch.float32, device=x.device)
-    ws = _ws(x.shape[0] * w.shape[0] * 4, x.device)
-    a = L.LinearArgs()
-    a.N, a.In, a.Out, a.relu = x.shape[0], x.shape[1], w.shape[0], int(relu)
-    a.x, a.w, a.y, a.dy = x.data_ptr(), w.data_ptr(), y.data_ptr(), dy.data_ptr()
-    a.dx, a.dw, a.dbias = dx.data_ptr(), dw.data_ptr(), db.data_ptr()
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    L.check(L.load().mtbc_linear_bwd(C.byref(a), _s()), "linear_bwd")
-    return dx, dw, db
 
 
 # ------------------------------------------------------------------ losses / optimiser
@@ -1097,23 +895,16 @@ def convT_head_fwd_bwd(x, wT, bT, w1, b1, k, dout):
     (mtbc_convT_head_combine -> mtbc_convT_* with Cout = R -> mtbc_convT_head_expand).
     Returns (y, dx, dwT, dbT, dw1, db1)."""
     _chk(x, wT, bT, w1, b1, dout)
-    lib = L.load()
     cin, cmid, R = wT.shape[0], wT.shape[1], w1.shape[0]
     dev = x.device
-    Wc, bc = torch.empty(cin, R, k, k, device=dev), torch.empty(R, device=dev)
-    a = L.HeadFuseArgs()
-    a.Cin, a.Cmid, a.R, a.k = cin, cmid, R, k
-    a.wT, a.bT, a.w1, a.b1 = wT.data_ptr(), bT.data_ptr(), w1.data_ptr(), b1.data_ptr()
-    a.Wc, a.bc = Wc.data_ptr(), bc.data_ptr()
-    L.check(lib.mtbc_convT_head_combine(C.byref(a), _s()), "head_combine")
-    y = convT_fwd(x, Wc, bc, k)
-    dx = convT_dgrad(x, Wc, dout, k)
-    G, gb = convT_wgrad(x, Wc, dout, k)
-    dwT, dbT, dw1, db1 = torch.empty_like(wT), torch.empty_like(bT), torch.empty_like(w1), torch.empty_like(b1)
-    a.G, a.gb = G.data_ptr(), gb.data_ptr()
-    a.dwT, a.dbT, a.dw1, a.db1 = dwT.data_ptr(), dbT.data_ptr(), dw1.data_ptr(), db1.data_ptr()
-    L.check(lib.mtbc_convT_head_expand(C.byref(a), _s()), "head_expand")
-    return y, dx, dwT, dbT, dw1, db1
+    T = {"wT": wT, "bT": bT, "w1": w1, "b1": b1, "Wc": torch.empty(cin, R, k, k, device=dev), "bc": torch.empty(R, device=dev), "G": None, "gb": None}
+    small_op_launch(head_case_args(L.OP_HEAD_COMBINE, cin, cmid, R, k, ptrs=T))
+    y = convT_fwd(x, T["Wc"], T["bc"], k)
+    dx = convT_dgrad(x, T["Wc"], dout, k)
+    T["G"], T["gb"] = convT_wgrad(x, T["Wc"], dout, k)
+    T.update(dwT=torch.empty_like(wT), dbT=torch.empty_like(bT), dw1=torch.empty_like(w1), db1=torch.empty_like(b1))
+    small_op_launch(head_case_args(L.OP_HEAD_EXPAND, cin, cmid, R, k, ptrs=T))
+    return y, dx, T["dwT"], T["dbT"], T["dw1"], T["db1"]
 
 
 # ------------------------------------------------------------------ the small ops as step-program ops: plan query, argument structs, launch
@@ -1129,12 +920,12 @@ def op_kernel_name(op: "L.Op") -> str:
     return buf.value.decode()
 
 
-_SMALL_DUMMY = {n: (i + 1) << 20 for i, n in enumerate(("x", "w", "bias", "y", "dy", "dx", "dw", "dbias", "workspace", "argmax", "wT", "bT", "w1", "b1",
-                                                        "Wc", "bc", "G", "gb", "dwT", "dbT", "dw1", "db1"))}
+_SMALL_DUMMY = _dummies("x", "w", "bias", "y", "dy", "dx", "dw", "dbias", "workspace", "argmax", "wT", "bT", "w1", "b1", "Wc", "bc", "G", "gb",
+                        "dwT", "dbT", "dw1", "db1")
 
 
 def _small_ptr(ptrs: Optional[dict]):
-    return (lambda name: _SMALL_DUMMY[name]) if ptrs is None else (lambda name: ptrs[name].data_ptr())
+    return _ptr(ptrs, _SMALL_DUMMY.__getitem__)
 
 
 def _small_op(kind: int) -> "L.Op":

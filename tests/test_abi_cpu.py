@@ -657,3 +657,105 @@ def test_small_op_kernel_name_refuses_what_the_call_refuses(lib):
     assert lib.mtbc_op_kernel_name(C.byref(op), buf, len(want) + 1) == 0 and buf.value == want
     assert lib.mtbc_op_kernel_name(C.byref(op), None, 512) == -2
     assert lib.mtbc_op_kernel_name(None, buf, 512) == -2
+
+
+# ---------------------------------------------------------------- one filler, two callers: dummy pointers (the guards) against ptrs= (the launches)
+# rows beside the selection tables: the keywords only the eager wrappers of ops.py use
+_CASE_EXTRA = [
+    ("conv3x3", L.OP_CONV3_FWD, (2, [16, 8], 16, 16, 16), dict(_BF16, out_c8=True, stats=True)),                 # epilogue statistics
+    ("conv3x3", L.OP_CONV3_FWD, (2, [16], 16, 16, 16), dict(_F16_O1, bias=False, stats=True, norm=0.1, out_partial=True)),   # the gathered dgrad's norm epilogue
+    ("conv3x3", L.OP_CONV3_FWD, (2, [3], 24, 16, 16), dict(_BF16_O3, stats=True)),                               # the stem with statistics
+    ("conv3x3", L.OP_CONV3_FWD, (2, [8, 8], 16, 16, 16), dict(packed=False, force_direct=True, bias=False)),
+    ("conv3x3", L.OP_CONV3_DGRAD, (2, [8, 16], 16, 16, 16), dict(_BF16, accumulate=[1, 2])),                     # 16-bit planar second segment
+    ("conv3x3", L.OP_CONV3_DGRAD, (2, [8, 16], 16, 16, 16), dict(_F16, dx_c8=True)),
+    ("conv3x3", L.OP_CONV3_DGRAD, (2, [8, 16], 16, 16, 16), dict(packed=False, force_direct=True, accumulate=())),
+    ("conv3x3", L.OP_CONV3_WGRAD, (2, [8, 16], 16, 16, 16), dict(accumulate_dw=True, force_direct=True, bias=False)),
+    ("instnorm", True, (2, 16, 16, 16), dict(compute=1, out="c8", z="c8f16", dy="c8", pool=True, rank1=True, rank1_grads=True, rank1_acc=True, acc=True)),
+    ("instnorm", False, (2, 16, 16, 16), dict(compute=1, out="c8", planar=True, affine=False, pool=True, pool_arg=False)),
+    ("convT", L.OP_CONVT_WGRAD, (2, 16, 8, 8, 8, 4), dict(workspace=False, acc_dw=True)),
+    ("convT", L.OP_CONVT_DGRAD, (2, 16, 8, 8, 8, 2), dict(acc_dx=True, strides=dict(dx=2 * 16 * 64, dy=3 * 8 * 256))),
+    ("gap", L.OP_GAP_BWD, (2, 8, 4, 4), {}),
+    ("linear", L.OP_LINEAR_FWD, (4, 8, 3), dict(bias=False)),
+    ("linear", L.OP_LINEAR_BWD, (4, 8, 3), dict(relu=True, acc_dw=True)),
+    ("conv1x1", L.OP_CONV1_WGRAD, (2, 16, 3, 8, 8), dict(workspace=False, acc_dw=True)),
+    ("head", L.OP_HEAD_EXPAND, (8, 4, 1, 2), dict(acc=(1, 0, 1, 1))),
+]
+
+
+def _case_rows():
+    """(family, op, shape, mode, pair) of every row of the four selection tables -- InstanceNorm up to 64 x 64 planes only: larger ones with a
+    channel-blocked output ask the device for the team plan -- and of _CASE_EXTRA."""
+    kinds = {"fwd": L.OP_CONV3_FWD, "dgrad": L.OP_CONV3_DGRAD, "wgrad": L.OP_CONV3_WGRAD}
+    rows = [("conv3x3", kinds[op], (N, segs, Cout, H, W), mode, False) for op, N, segs, Cout, H, W, mode, _ in SELECTION]
+    rows += [("instnorm", bwd, (N, Cc, H, W), mode, False) for bwd, N, Cc, H, W, mode, _ in NORM_SELECTION if H * W <= 64 * 64]
+    rows += [("convT", _CT_OPS[op], shape, mode, pair) for op, shape, mode, pair, _ in CONVT_SELECTION]
+    rows += [(helper, kind, shape, mode, False) for helper, kind, shape, mode, _ in SMALL_OP_SELECTION]
+    return rows + [r + (False,) for r in _CASE_EXTRA]
+
+
+class _Tensors(dict):
+    """ptrs= of a *_case_args builder: a small CPU tensor per field, made when first asked for (only data_ptr() and numel() are read)."""
+
+    def __missing__(self, name):
+        import torch
+        self[name] = torch.empty(16, dtype=torch.float32)
+        return self[name]
+
+
+def _case_fields(a, prefix=""):
+    """{path: value} of a struct; pointers as NULL or not, the active union member of an op."""
+    if isinstance(a, L.Op):
+        return dict(_case_fields(getattr(a.u, L.OP_UNION_FIELD[a.kind])), kind=a.kind)
+    out = {}
+    for name, typ in a._fields_:
+        v = getattr(a, name)
+        if isinstance(v, C.Array):
+            for i, e in enumerate(v):
+                out.update(_case_fields(e, f"{prefix}{name}[{i}].") if isinstance(e, C.Structure) else {f"{prefix}{name}[{i}]": bool(e)})
+        else:
+            out[prefix + name] = bool(v) if typ is C.c_void_p else v
+    return out
+
+
+@pytest.mark.parametrize("family", ["conv3x3", "instnorm", "convT", "maxpool", "conv1x1", "gap", "linear", "head"])
+def test_case_args_with_tensors_equal_case_args_with_dummies(lib, family):
+    """Each *_case_args builder serves the launch-coverage guards (ptrs=None: dummy addresses) and every launch of ops.py (ptrs= tensors).  Both
+    must give one struct: every non-pointer field equal -- workspace_bytes follows the tensor handed in and may be larger --, the same pointer
+    fields NULL, the same launches named by the family's *_kernel_name (or the same refusal: a weight gradient without its workspace).  Nothing
+    is launched."""
+    import torch
+    from multi_task_breast_cancer_amd import ops
+    rows = [r for r in _case_rows() if r[0] == family]
+    assert len(rows) >= 3
+
+    def named(f, *args):
+        try:
+            return f(*args)
+        except L.MtbcError as e:
+            return str(e)
+    for _, op, shape, mode, pair in rows:
+        build = getattr(ops, family + "_case_args")
+        if family == "conv3x3":
+            name = lambda a: ops.conv3x3_kernel_name(a, op)                                             # noqa: E731
+        elif family == "instnorm":
+            name = lambda a: ops.instnorm_kernel_name(a, op)                                            # noqa: E731
+        elif family == "convT":
+            name = lambda a, nxt=None: ops.convT_kernel_name(a, op, nxt)                                # noqa: E731
+        else:
+            name = ops.op_kernel_name
+        dummy = build(op, *shape, **mode)
+        d = _case_fields(dummy)
+        T = _Tensors()
+        if family == "conv3x3":
+            T["in"] = [torch.empty(16) for _ in shape[1]]
+            T["wgrad_sync"] = torch.empty(max(1, d["wgrad_sync_bytes"] // 4), dtype=torch.int32)
+        T["workspace"] = torch.empty(d.get("workspace_bytes", 0) // 4 + 8, dtype=torch.float32)      # as the wrappers: at least what is asked for
+        real = build(op, *shape, ptrs=T, **mode)
+        r = _case_fields(real)
+        assert r.pop("workspace_bytes", 0) >= d.pop("workspace_bytes", 0), (family, op, shape, mode)
+        assert r == d, (family, op, shape, mode, {k: (d[k], r[k]) for k in d if d[k] != r[k]})
+        if pair:
+            dg = L.OP_CONVT_DGRAD
+            assert named(name, real, ops.convT_case_args(dg, *shape, ptrs=T, **mode)) == named(name, dummy, ops.convT_case_args(dg, *shape, **mode))
+        else:
+            assert named(name, real) == named(name, dummy), (family, op, shape, mode)
