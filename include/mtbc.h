@@ -729,6 +729,46 @@ typedef struct {
 } mtbc_eval_metrics_args;
 int mtbc_eval_metrics(const mtbc_eval_metrics_args* a, void* stream);
 
+/* ---- metrics of a segmentation-only step (training_segmentation.py:40-88): the pixel launch of mtbc_train_metrics -- the same kernel, the same
+ * predicate -- then a ONE-thread launch that adds N to table[cursor][3], stores loss_rows[cursor][0..3] = w * (double)loss_in[0..3] when loss_in
+ * is not NULL (w = *shard_weight, NULL = 1), and advances the cursor.  Cursor and state, capacity and the drop counter, the empty shard
+ * (N == 0 with n_seg == 0: only the cursor advances) behave exactly as in mtbc_eval_metrics; there are no class arguments and no confusion
+ * matrix.  loss_in == NULL is the training call (loss_rows is then unread).  MTBC_E_BADARG: a null pointer (the data pointers may be NULL with
+ * N == 0; loss_rows must be given with loss_in and N > 0); MTBC_E_BADSHAPE: a negative count, N == 0 without n_seg == 0.                       */
+typedef struct {
+    const float* seg_logits;         /* last segmentation head, fp32, n_seg = N*C*H*W elements */
+    const float* mask;               /* the step's mask buffer, same element count */
+    int64_t      n_seg;
+    int32_t      N;
+    int64_t*     table;              /* [capacity][4]: tp, fp, fn, samples -- one row per batch */
+    int32_t*     state;              /* [0] cursor, [1] batches dropped */
+    int32_t      capacity;
+    const float* loss_in;            /* 4 floats [total, seg, 0, nan_flag] of the batch, or NULL */
+    double*      loss_rows;          /* [capacity][4] */
+    const float* shard_weight;       /* device word, or NULL = 1 */
+} mtbc_seg_step_metrics_args;
+int mtbc_seg_step_metrics(const mtbc_seg_step_metrics_args* a, void* stream);
+
+/* ------------------------------------------------------------------ hole filling of a predicted mask
+ * scipy.ndimage.binary_fill_holes (default structure) of the raw prediction, which the segmentation driver's testing phase applies before its
+ * metrics (utils/models.py:39-100, fill_holes=True): foreground = sigmoid(seg_logits) > .5, the predicate of the Dice counters above (a NaN is
+ * not foreground).  A non-foreground pixel is background-reachable when it lies on the image border or is 4-adjacent to a reachable
+ * non-foreground pixel; the output is the complement of the reachable set, so an 8-connected ring encloses its interior.
+ * One workgroup per image, both bit planes (free, reached) in LDS; a pass is four directional sweeps (r[i] |= r[i-1] & free[i] along rows both
+ * ways, then along columns both ways), repeated until a pass sets no bit: deterministic, no atomics on global memory.  The pass loop is
+ * bounded by H*W + 1 (every non-final pass sets a bit); reaching the bound stores 1 into *error and returns what it has -- *error is never
+ * cleared by the call.  H, W: multiples of 16 in [16, 512], else MTBC_E_BADSHAPE; N >= 1.  At least one of the two outputs must be given.
+ * mtbc_fill_holes_host: host pointers, no GPU call, the same pass and predicate code compiled for the host.                                 */
+typedef struct {
+    int32_t N, H, W;
+    const float* seg_logits;         /* (N,1,H,W) */
+    float*   filled_logits;          /* (N,1,H,W): +1.f foreground after filling, -1.f otherwise; or NULL */
+    uint8_t* filled_u8;              /* (N,H,W): 255 / 0; or NULL */
+    int32_t* error;                  /* one word */
+} mtbc_fill_holes_args;
+int mtbc_fill_holes(const mtbc_fill_holes_args* a, void* stream);
+int mtbc_fill_holes_host(const mtbc_fill_holes_args* a);
+
 /* ---------------------------------------------------------------------------- step program
  * A training step is a static list of the ops above with every pointer resolved at plan
  * time; mtbc_program_run issues them back-to-back on one stream (no host work in between). */

@@ -178,6 +178,18 @@ class EvalMetricsArgs(C.Structure):
     _fields_ = TrainMetricsArgs._fields_ + [("loss_in", C.c_void_p), ("loss_rows", C.c_void_p), ("shard_weight", C.c_void_p)]
 
 
+class SegStepMetricsArgs(C.Structure):
+    """mtbc_seg_step_metrics_args (include/mtbc.h): the metrics call of a segmentation-only step."""
+    _fields_ = [("seg_logits", C.c_void_p), ("mask", C.c_void_p), ("n_seg", C.c_int64), ("N", C.c_int32), ("table", C.c_void_p),
+                ("state", C.c_void_p), ("capacity", C.c_int32), ("loss_in", C.c_void_p), ("loss_rows", C.c_void_p), ("shard_weight", C.c_void_p)]
+
+
+class FillHolesArgs(C.Structure):
+    """mtbc_fill_holes_args (include/mtbc.h)."""
+    _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("seg_logits", C.c_void_p), ("filled_logits", C.c_void_p),
+                ("filled_u8", C.c_void_p), ("error", C.c_void_p)]
+
+
 BATCH_MAX_LUTS = 4         # MTBC_BATCH_MAX_LUTS of include/mtbc.h
 
 # columns of the mtbc_seg_metrics table -- keep in sync with the MTBC_SEGM_* defines of include/mtbc.h
@@ -289,7 +301,7 @@ EXPORTS = [
     "mtbc_dice_counts", "mtbc_program_run",
     "mtbc_program_run_ms", "mtbc_event_create", "mtbc_event_destroy", "mtbc_op_kernel_name",
     "mtbc_seg_metrics_workspace_size", "mtbc_seg_metrics", "mtbc_batch_assemble", "mtbc_train_metrics",
-    "mtbc_eval_metrics",
+    "mtbc_eval_metrics", "mtbc_seg_step_metrics", "mtbc_fill_holes", "mtbc_fill_holes_host",
 ]
 
 ABI_VERSION = 203          # MTBC_VERSION of include/mtbc.h these mirrors follow
@@ -420,6 +432,12 @@ def load() -> C.CDLL:
     lib.mtbc_train_metrics.argtypes = [C.POINTER(TrainMetricsArgs), C.c_void_p]
     lib.mtbc_eval_metrics.restype = C.c_int
     lib.mtbc_eval_metrics.argtypes = [C.POINTER(EvalMetricsArgs), C.c_void_p]
+    lib.mtbc_seg_step_metrics.restype = C.c_int
+    lib.mtbc_seg_step_metrics.argtypes = [C.POINTER(SegStepMetricsArgs), C.c_void_p]
+    lib.mtbc_fill_holes.restype = C.c_int
+    lib.mtbc_fill_holes.argtypes = [C.POINTER(FillHolesArgs), C.c_void_p]
+    lib.mtbc_fill_holes_host.restype = C.c_int
+    lib.mtbc_fill_holes_host.argtypes = [C.POINTER(FillHolesArgs)]
     _lib = lib
     return lib
 

@@ -49,6 +49,14 @@ def metrics_row(epoch: int, lr: float, train_loss: float, val_loss: float, train
             f"{train_f1:.4f},{val_acc:.4f},{val_f1:.4f}")
 
 
+SEG_METRICS_HEADER = "epoch,LR,Train,Validation,Test,Train_loss,Val_loss"   # training_segmentation.py:140-141
+
+
+def seg_metrics_row(epoch: int, lr: float, train_dice: float, val_dice: float, test_dice: float, train_loss: float, val_loss: float) -> str:
+    """training_segmentation.py:192-195, the stray blank before Validation included; `lr` is the optimizer's AFTER the scheduler step."""
+    return f"{epoch},{lr:.8f},{train_dice:.4f}, {val_dice:.4f},{test_dice:.4f},{train_loss:.4f},{val_loss:.4f}"
+
+
 def write_metrics_file(path_file: str, text_to_write: str, close: bool = True) -> None:
     """src/utils/miscellany.py:155-169: append one line (the caller writes METRICS_HEADER first, as :216-217 does)."""
     with open(path_file, "a") as f:

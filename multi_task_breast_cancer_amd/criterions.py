@@ -7,6 +7,7 @@
              squared_pred=True) of :214-216 ("FocalDICE"; restated from knowledge of MONAI 1.3.0)
   FocalLoss  replaces src/utils/criterions.py:6-24
   apply_criterion_multitask_segmentation_classification mirrors criterions.py:52-76 (same signature, NaN -> exit 1)
+  apply_criterion_binary_segmentation mirrors criterions.py:27-49 (the single-task segmentation driver's)
 
 The criteria are torch.autograd.Functions over the C-ABI kernels (mtbc_dice_fwd/_bwd, mtbc_focal_fwd_bwd);
 they raise when handed CPU tensors -- there is no fallback.
@@ -161,6 +162,21 @@ def exit_on_nan() -> None:
     """criterions.py:72-76: a NaN loss ends the run -- here, and wherever the fused steps read a NaN word back from the device."""
     logging.info("NaN in model loss!!")
     sys.exit(1)
+
+
+def apply_criterion_binary_segmentation(criterion, ground_truth, segmentation, inversely_weighted=False):
+    """criterions.py:27-49: deep-supervision heads weighted 1/(j+1) from the LAST head backwards; a NaN loss ends the run."""
+    if isinstance(segmentation, list):
+        heads = list(reversed(segmentation))
+        if inversely_weighted:
+            loss = torch.sum(torch.stack([criterion(s, ground_truth) / (j + 1) for j, s in enumerate(heads)]))
+        else:
+            loss = torch.sum(torch.stack([criterion(s, ground_truth) for s in heads]))
+    else:
+        loss = criterion(segmentation, ground_truth)
+    if not torch.isnan(loss):
+        return loss
+    exit_on_nan()
 
 
 def apply_criterion_multitask_segmentation_classification(criterion_seg, ground_truth, segmentation, criterion_class,

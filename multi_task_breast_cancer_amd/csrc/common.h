@@ -121,8 +121,8 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 }
 
 // The sigmoid of the losses and of every `sigmoid(x) > .5` predicate (head_loss.hip: Dice, dice_counts_kernel; seg_metrics.hip): one
-// definition, so a pixel is tumour for all of them or for none.
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
+// definition, so a pixel is tumour for all of them or for none.  (__host__ too: mtbc_fill_holes_host compiles the same predicate.)
+__host__ __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 // Source pixel of output pixel (x, y) under RandomHorizontalFlip -> RandomVerticalFlip -> RandomRotation (torchvision: nearest, zero fill,
 // centre rotation; the derivation is at the top of augment.hip): false = outside the rotated frame (the output is 0), else (xs, ys) is the pixel to

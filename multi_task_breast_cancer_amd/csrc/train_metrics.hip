@@ -138,18 +138,8 @@ __global__ __launch_bounds__(TM_BLOCK) void train_metrics_samples_kernel(const f
     }
 }
 
-// both entry points: the argument checks they share, the pixels launch, then the samples launch of the caller's instantiation
-template <bool LOSS>
-int launch_metrics(const float* seg_logits, const float* mask, int64_t n_seg, const float* cls_logits, const float* target, int N, int n_logits,
-                   int64_t* table_, int64_t* conf, int32_t* state, int capacity, const float* loss_in, double* loss_rows, const float* shard_weight,
-                   void* stream) {
-    if (!table_ || !conf || !state) return MTBC_E_BADARG;
-    if (N < 0 || n_seg < 0 || capacity < 0 || n_logits < 1 || n_logits > 3) return MTBC_E_BADSHAPE;
-    if ((N == 0) != (n_seg == 0)) return MTBC_E_BADSHAPE;                        // an empty shard has neither samples nor pixels
-    if (N > 0 && (!seg_logits || !mask || !cls_logits || !target)) return MTBC_E_BADARG;
-    if (LOSS && N > 0 && (!loss_in || !loss_rows)) return MTBC_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    unsigned long long* table = reinterpret_cast<unsigned long long*>(table_);
+// the pixels launch of every entry point of this file (n_seg == 0: none)
+int launch_pixels(const float* seg_logits, const float* mask, int64_t n_seg, unsigned long long* table, const int32_t* state, int capacity, hipStream_t st) {
     if (n_seg > 0) {
         const long long n = (long long)n_seg;
         // memory-bound and small: one unrolled pass per thread before another block is added; past 2^40 pixels a wave's 32-bit counters
@@ -164,6 +154,42 @@ int launch_metrics(const float* seg_logits, const float* mask, int64_t n_seg, co
                                 (const int*)state, capacity);
         MTBC_CHECK_LAUNCH();
     }
+    return MTBC_OK;
+}
+
+// mtbc_seg_step_metrics' second launch, ONE thread: what thread 0 of the samples kernel does behind its class counts (loss_in NULL: no loss row)
+__global__ void seg_step_tail_kernel(int N, unsigned long long* __restrict__ table, int* __restrict__ state, int capacity,
+                                     const float* __restrict__ loss_in, double* __restrict__ loss_rows, const float* __restrict__ shard_weight) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int cursor = state[0];
+    if (N > 0) {
+        if (cursor >= 0 && cursor < capacity) {
+            atomicAdd(&table[(size_t)cursor * 4 + 3], (unsigned long long)N);
+            if (loss_in) {                                     // this row is this call's alone: plain stores
+                const double w = shard_weight ? (double)shard_weight[0] : 1.0;
+                double* row = loss_rows + (size_t)cursor * 4;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) row[j] = w * (double)loss_in[j];
+            }
+        } else state[1] += 1;
+    }
+    state[0] = cursor + 1;
+}
+
+// both entry points: the argument checks they share, the pixels launch, then the samples launch of the caller's instantiation
+template <bool LOSS>
+int launch_metrics(const float* seg_logits, const float* mask, int64_t n_seg, const float* cls_logits, const float* target, int N, int n_logits,
+                   int64_t* table_, int64_t* conf, int32_t* state, int capacity, const float* loss_in, double* loss_rows, const float* shard_weight,
+                   void* stream) {
+    if (!table_ || !conf || !state) return MTBC_E_BADARG;
+    if (N < 0 || n_seg < 0 || capacity < 0 || n_logits < 1 || n_logits > 3) return MTBC_E_BADSHAPE;
+    if ((N == 0) != (n_seg == 0)) return MTBC_E_BADSHAPE;                        // an empty shard has neither samples nor pixels
+    if (N > 0 && (!seg_logits || !mask || !cls_logits || !target)) return MTBC_E_BADARG;
+    if (LOSS && N > 0 && (!loss_in || !loss_rows)) return MTBC_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* table = reinterpret_cast<unsigned long long*>(table_);
+    const int rc = launch_pixels(seg_logits, mask, n_seg, table, state, capacity, st);
+    if (rc != MTBC_OK) return rc;
     hipLaunchKernelGGL(train_metrics_samples_kernel<LOSS>, dim3(1), dim3(TM_BLOCK), 0, st, cls_logits, target, N, n_logits, table,
                        reinterpret_cast<unsigned long long*>(conf), state, capacity, loss_in, loss_rows, shard_weight);
     MTBC_CHECK_LAUNCH();
@@ -182,4 +208,20 @@ extern "C" int mtbc_eval_metrics(const mtbc_eval_metrics_args* a, void* stream) 
     if (!a) return MTBC_E_BADARG;
     return launch_metrics<true>(a->seg_logits, a->mask, a->n_seg, a->cls_logits, a->target, a->N, a->n_logits, a->table, a->conf, a->state,
                                 a->capacity, a->loss_in, a->loss_rows, a->shard_weight, stream);
+}
+
+extern "C" int mtbc_seg_step_metrics(const mtbc_seg_step_metrics_args* a, void* stream) {
+    if (!a) return MTBC_E_BADARG;
+    if (!a->table || !a->state) return MTBC_E_BADARG;
+    if (a->N < 0 || a->n_seg < 0 || a->capacity < 0) return MTBC_E_BADSHAPE;
+    if ((a->N == 0) != (a->n_seg == 0)) return MTBC_E_BADSHAPE;                  // an empty shard has neither samples nor pixels
+    if (a->N > 0 && (!a->seg_logits || !a->mask)) return MTBC_E_BADARG;
+    if (a->N > 0 && a->loss_in && !a->loss_rows) return MTBC_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* table = reinterpret_cast<unsigned long long*>(a->table);
+    const int rc = launch_pixels(a->seg_logits, a->mask, a->n_seg, table, a->state, a->capacity, st);
+    if (rc != MTBC_OK) return rc;
+    hipLaunchKernelGGL(seg_step_tail_kernel, dim3(1), dim3(1), 0, st, a->N, table, a->state, a->capacity, a->loss_in, a->loss_rows, a->shard_weight);
+    MTBC_CHECK_LAUNCH();
+    return MTBC_OK;
 }

@@ -1099,14 +1099,18 @@ class StepPlan:
         return y
 
     # ------------------------------------------------------------------ losses (fused-step path)
-    def fused_losses(self, seg_heads: Sequence[Act], logits: Act, mask: torch.Tensor, onehot: torch.Tensor,
+    def fused_losses(self, seg_heads: Sequence[Act], logits: Optional[Act], mask: torch.Tensor, onehot: Optional[torch.Tensor],
                      alpha: float, inversely_weighted: bool, focal_weight: Optional[torch.Tensor] = None,
                      loss_scale: float = 1.0, binary: bool = False, cls_gamma: float = 2.0, seg_criterion: str = "DICE"):
         """criterions.py:52-76 + training_multitask.py:98 on device: the segmentation criterion over the heads (weights 1/(j+1) from
         the LAST head backwards), Focal on the logits, alpha-mix, NaN flag.  Gradients land in the heads' grad buffers.
         `seg_criterion`: the reference's `loss.function` name -- "DICE" | "BCE" | "FocalDICE" | "Jaccard" (_lib.SEG_CRITERIA): the same two
         ops with another mtbc_dice_args.kind.  Jaccard is a SUM over the planes (reduction="sum"): the kernel leaves the 1 / planes out,
-        the head weights are passed as they are."""
+        the head weights are passed as they are.
+        `logits` None: a segmentation-only model (training_segmentation.py:40-62) -- no classification op, alpha must be 1, and the mix reads a
+        zero word for the class loss: the loss words are [seg, seg, 0, nan_flag]."""
+        if logits is None and alpha != 1.0:
+            raise ValueError("a segmentation-only model has no classification loss to mix: alpha must be 1.0")
         nh = len(seg_heads)
         assert 1 <= nh <= 4
         N, C_, H, W = seg_heads[0].data.shape
@@ -1145,20 +1149,24 @@ class StepPlan:
         # classification criterion (experiment_init.py:232-262): "Focal" = FocalLoss(alpha 1, gamma 2); "CE" = CrossEntropyLoss = the same
         # formula with gamma 0; the ONE-logit head (n_classes == 2, `binary`) = BCEWithLogitsLoss on the {0, 1} label, which the focal
         # kernel evaluates when C == 1 (gamma 0): `onehot` then holds the (N, 1) float label itself
-        assert (logits.C == 1) == bool(binary), "one logit <=> binary head"
-        op = _mk(L.OP_FOCAL)
-        a = op.u.focal
-        a.N, a.C, a.alpha, a.gamma = N, logits.C, 1.0, (0.0 if binary else float(cls_gamma))
-        a.x, a.target, a.weight = logits.data.data_ptr(), onehot.data_ptr(), _ptr(focal_weight)
-        a.loss, a.dx, a.gscale = self.focal_loss.data_ptr(), self.grad_of(logits).data_ptr(), (1.0 - alpha) * loss_scale
-        a.gscale_dev = self.grad_weight.data_ptr()
-        logits.grad_written = True
-        self.loss_ops.append(op)
+        if logits is None:
+            self.focal_loss = torch.zeros(1, dtype=torch.float32, device=self.dev)      # the zero word the mix reads as the class loss
+            self.keep.append(self.focal_loss)
+        else:
+            assert (logits.C == 1) == bool(binary), "one logit <=> binary head"
+            op = _mk(L.OP_FOCAL)
+            a = op.u.focal
+            a.N, a.C, a.alpha, a.gamma = N, logits.C, 1.0, (0.0 if binary else float(cls_gamma))
+            a.x, a.target, a.weight = logits.data.data_ptr(), onehot.data_ptr(), _ptr(focal_weight)
+            a.loss, a.dx, a.gscale = self.focal_loss.data_ptr(), self.grad_of(logits).data_ptr(), (1.0 - alpha) * loss_scale
+            a.gscale_dev = self.grad_weight.data_ptr()
+            logits.grad_written = True
+            self.loss_ops.append(op)
         op = _mk(L.OP_LOSS_MIX)
         op.u.mix.seg = self.dice_loss.data_ptr() + 4 * nh
         op.u.mix.cls, op.u.mix.alpha, op.u.mix.out4 = self.focal_loss.data_ptr(), alpha, self.loss_out.data_ptr()
         self.loss_ops.append(op)
-        self.keep += [mask, onehot] + ([focal_weight] if focal_weight is not None else [])
+        self.keep += [mask] + ([onehot] if onehot is not None else []) + ([focal_weight] if focal_weight is not None else [])
 
     # ------------------------------------------------------------------ finalisation
     def emit_backward(self) -> None:

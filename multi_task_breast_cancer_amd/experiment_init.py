@@ -1,6 +1,6 @@
 """String -> object factory with the reference's names and signatures (src/utils/experiment_init.py:130-318),
-restricted to the multi-task training path.  Unknown names raise ValueError (the reference silently builds an
-empty nn.Module, experiment_init.py:160-163 -- stricter here)."""
+restricted to the multi-task training path and the single-task nnUNet segmentation baseline.  Unknown names raise
+ValueError (the reference silently builds an empty nn.Module, experiment_init.py:160-163 -- stricter here)."""
 from __future__ import annotations
 
 import logging
@@ -11,7 +11,7 @@ import torch
 from torch.optim.lr_scheduler import CosineAnnealingLR, ReduceLROnPlateau
 
 from .criterions import DiceFocalLoss, DiceLoss, FocalLoss
-from .nets import MTnnUNet, MTUNetPlusPlus
+from .nets import MTnnUNet, MTUNetPlusPlus, nnUNet
 from .optim import FusedAdam, FusedAdamW, FusedSGD
 
 
@@ -31,12 +31,29 @@ def init_multitask_model(architecture: str, sequences: int = 1, regions: int = 1
     else:
         raise ValueError(f"The model selected ({architecture!r}) is not on the MI355X hot path. Choose "
                          "'MTnnUNet' or 'MTUNetPlusPlus'.")
+    _describe(model, save_folder)
+    return model
+
+
+def _describe(model: torch.nn.Module, save_folder) -> None:
     if save_folder is not None:
         save_folder = Path(save_folder)
         save_folder.mkdir(parents=True, exist_ok=True)
         with (save_folder / "model.txt").open("w") as f:
             print(model, file=f)
     logging.info(f"Total number of trainable parameters: {count_parameters(model)}")
+
+
+def init_segmentation_model(architecture: str, sequences: int = 1, regions: int = 1, width: int = 48, save_folder: Path = None,
+                            deep_supervision: bool = False) -> torch.nn.Module:
+    """experiment_init.py:26-78, the single-task factory: 'nnUNet' (`nnUNet2021`, BASELINE.json configs[0]) is on HIP.  `width` and
+    `deep_supervision` are ignored, as the reference ignores them for this architecture (:62-63: it always returns its four heads)."""
+    logging.info(f"Creating {architecture} model")
+    logging.info(f"The model will be fed with {sequences} sequences")
+    if architecture != "nnUNet":
+        raise ValueError(f"The segmentation model selected ({architecture!r}) is not on the MI355X hot path. Choose 'nnUNet'.")
+    model = nnUNet(sequences=sequences, regions=regions)
+    _describe(model, save_folder)
     return model
 
 
@@ -124,6 +141,22 @@ def load_multitask_experiment_artefacts(config_data, config_model, config_opt, c
                                   t_max=int(config_opt["t_max"]), patience=int(config_opt["patience"]),
                                   min_lr=float(config_opt["min_lr"]), factor=float(config_opt["decrease_factor"]))
     return model, optimizer, segmentation_criterion, classification_criterion, scheduler
+
+
+def load_segmentation_experiment_artefacts(config_model, config_opt, config_loss, n_augments, run_path, fused: bool = False):
+    """experiment_init.py:286-298 -> (model, optimizer, criterion, scheduler).  `fused`: init_optimizer's."""
+    model = init_segmentation_model(architecture=config_model["architecture"],
+                                    sequences=config_model["sequences"] + n_augments,
+                                    width=config_model["width"], deep_supervision=config_model["deep_supervision"],
+                                    save_folder=Path(f"./{run_path}/") if run_path is not None else None)
+    if config_model.get("compute_dtype") is not None and hasattr(model, "set_compute"):      # optional key, as in the multi-task loader
+        model.set_compute(str(config_model["compute_dtype"]))
+    optimizer = init_optimizer(model=model, optimizer=config_opt["opt"], learning_rate=config_opt["lr"], fused=fused)
+    criterion = init_criterion_segmentation(loss_function=config_loss["function"])
+    scheduler = init_lr_scheduler(optimizer=optimizer, scheduler=config_opt["scheduler"], t_max=int(config_opt["t_max"]),
+                                  patience=int(config_opt["patience"]), min_lr=float(config_opt["min_lr"]),
+                                  factor=float(config_opt["decrease_factor"]))
+    return model, optimizer, criterion, scheduler
 
 
 def device_setup() -> str:

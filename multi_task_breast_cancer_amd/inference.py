@@ -16,6 +16,10 @@ count, the reference's row-wise "Haussdorf distance" and the Hausdorff distance 
 its rule -- with no host round trip per image or per batch; `metrics_from_table` turns it into the reference's columns and
 `write_csv` into its two files.  `classification_report` restates the sklearn summaries of metrics.py:387-458 in numpy.
 PNG dumps and the xlsx aggregation are not covered (the reference's own `save_*_results` reads the two CSV files).
+
+`FusedSegTestStep` is the testing phase of the single-task segmentation driver (`inference_binary_segmentation`, src/utils/models.py:39-100,
+which training_segmentation.py:179 runs after EVERY epoch): forward, `fill_holes` (csrc/fill_holes.hip =
+scipy.ndimage.binary_fill_holes of the predicted mask, the driver's default), then the same `seg_metrics` table without class rules.
 """
 from __future__ import annotations
 
@@ -108,6 +112,34 @@ def seg_metrics(seg_logits: torch.Tensor, target: torch.Tensor, cls_logits: Opti
     L.check(lib.mtbc_seg_metrics(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "seg_metrics")
     return out
 
+
+
+def fill_holes(seg_logits: torch.Tensor, error: torch.Tensor, want_logits: bool = True, want_u8: bool = False):
+    """mtbc_fill_holes: (N,1,H,W) logits of the last head -> (filled_logits (N,1,H,W) float32 of +-1 or None, filled_u8 (N,H,W) uint8 of 255 / 0
+    or None): scipy.ndimage.binary_fill_holes(sigmoid(logits) > .5), one workgroup per image, one launch on the current stream.  `error`: a
+    device int32 word the kernel sets when its pass bound was reached (never, unless the kernel is broken); the caller reads it when it reads
+    its results."""
+    import ctypes as C
+    if seg_logits.dim() != 4 or seg_logits.shape[1] != 1:
+        raise ValueError(f"expected (N,1,H,W) logits, got {tuple(seg_logits.shape)}")
+    if seg_logits.device.type != "cuda":
+        L.require_gpu()
+        raise L.MtbcError("fill_holes needs device tensors (no CPU path)")
+    if error.dtype != torch.int32 or error.numel() != 1 or error.device != seg_logits.device:
+        raise ValueError("error must be one int32 word on the logits' device")
+    if not (want_logits or want_u8):
+        raise ValueError("ask for at least one of the two outputs")
+    x = seg_logits.contiguous().float()
+    N, _, H, W = x.shape
+    out_f = torch.empty_like(x) if want_logits else None
+    out_u8 = torch.empty(N, H, W, dtype=torch.uint8, device=x.device) if want_u8 else None
+    a = L.FillHolesArgs()
+    a.N, a.H, a.W, a.seg_logits, a.error = N, H, W, x.data_ptr(), error.data_ptr()
+    a.filled_logits = out_f.data_ptr() if want_logits else None
+    a.filled_u8 = out_u8.data_ptr() if want_u8 else None
+    rc = L.load().mtbc_fill_holes(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    L.check(rc, f"fill_holes (N, H, W) = ({N}, {H}, {W}): H and W must be multiples of 16 in [16, 512]" if rc == _E_BADSHAPE else "fill_holes")
+    return out_f, out_u8
 
 
 def metrics_from_table(table) -> Dict[str, np.ndarray]:
@@ -291,3 +323,100 @@ class FusedTestStep:
     def write_csv(self, path: str) -> Tuple[str, str]:
         seg_rows, cls_rows = self.result()
         return write_result_csvs(path, seg_rows, cls_rows)
+
+
+class FusedSegTestStep:
+    """The testing phase of the single-task segmentation driver (training_segmentation.py:179, :206 -> `inference_binary_segmentation`,
+    utils/models.py:39-100) in batches on the device.  Per batch: the compiled `pack` + `fwd` programs, `fill_holes` on the last head when
+    `fill_holes` is true (the driver's default), then `seg_metrics` on the filled mask -- as logits of +-1, whose sigmoid falls on the right side
+    of .5 -- with no class logits and no rules.  `result()` reads everything back once and returns the rows of `results_segmentation.csv`
+    (the reference's columns through `metrics_from_table`; `class` is the caller's class name); `write_csv(path)` writes that one file;
+    `masks_u8()` returns the filled masks as 0 / 255 planes, what `save_binary_segmentation` writes to segs/*.png (with keep_masks=True;
+    writing the PNG files is the caller's business).  `__call__` takes the batch; `evaluate_logits` takes the last head's logits directly."""
+
+    def __init__(self, model, fill_holes: bool = True, keep_masks: bool = False):
+        self.model, self.fill_holes, self.keep_masks = model, bool(fill_holes), bool(keep_masks)
+        self._error = None
+        self.reset()
+
+    def reset(self) -> None:
+        self._tables: List[torch.Tensor] = []      # device int64 (N, SEGM_COLS) per batch
+        self._masks: List[torch.Tensor] = []       # device uint8 (N, H, W) per batch (keep_masks)
+        self._ids: list = []
+        self._classes: list = []
+        self._coop_err = None
+        if self._error is not None:
+            self._error.zero_()
+
+    @torch.no_grad()
+    def __call__(self, image: torch.Tensor, mask: torch.Tensor, patient_id=None, class_name=None) -> None:
+        N, _, H, W = image.shape
+        st = self.model.compiled(N, H, W)
+        st.x.data.copy_(image, non_blocking=True)
+        st.programs["pack"].run()
+        st.programs["fwd"].run()
+        self._coop_err = self.model.coop_error_word()
+        self.evaluate_logits(st.segs[-1].data, mask, patient_id, class_name)
+
+    @torch.no_grad()
+    def evaluate_logits(self, seg_logits: torch.Tensor, mask: torch.Tensor, patient_id=None, class_name=None) -> None:
+        """The two launches behind the forward, on (N,1,H,W) logits of the last head that are already on the device."""
+        dev, N = seg_logits.device, seg_logits.shape[0]
+        if self._error is None or self._error.device != dev:
+            self._error = torch.zeros(1, dtype=torch.int32, device=dev)
+        x, u8 = seg_logits, None
+        if self.fill_holes:
+            x, u8 = fill_holes(seg_logits, self._error, want_logits=True, want_u8=self.keep_masks)
+        elif self.keep_masks:
+            u8 = (torch.sigmoid(seg_logits[:, 0].float()) > .5).to(torch.uint8) * 255
+        self._tables.append(seg_metrics(x, mask.to(dev, non_blocking=True)))
+        if u8 is not None:
+            self._masks.append(u8)
+        first = len(self._ids)
+        self._ids += list(range(first, first + N)) if patient_id is None else FusedTestStep._as_list(patient_id, N)
+        self._classes += [None] * N if class_name is None else FusedTestStep._as_list(class_name, N)
+
+    def result(self) -> List[dict]:
+        if not self._tables:
+            raise L.MtbcError("FusedSegTestStep.result() before any batch was evaluated")
+        table = torch.cat(self._tables)
+        M = table.shape[0]
+        err = self._coop_err
+        flat = torch.cat([table.flatten(), self._error.to(torch.int64),
+                          (err if err is not None else self._error * 0).to(torch.int64).flatten()]).cpu().numpy()     # the one read-back
+        if flat[-1] != 0:
+            L.raise_coop_timeout()
+        if flat[-2] != 0:
+            raise L.MtbcError("fill_holes: the pass bound H*W + 1 was reached before the flood was stable: the filled masks are invalid")
+        self.table = flat[:M * L.SEGM_COLS].reshape(M, L.SEGM_COLS)          # the integers behind the rows
+        cols = metrics_from_table(self.table)
+        rows = []
+        for i in range(M):
+            row = {"patient_id": self._ids[i]}
+            row.update({c: float(cols[c][i]) for c in SEG_METRIC_COLUMNS})
+            row["class"] = self._classes[i]
+            row[HAUSDORFF_PIXELS] = float(cols[HAUSDORFF_PIXELS][i])
+            rows.append(row)
+        return rows
+
+    def mean_dice(self) -> float:
+        """The `Test` column of the driver's metrics.csv: the mean DICE over the test set (training_segmentation.py:179-183)."""
+        return float(np.mean([r["DICE"] for r in self.result()]))
+
+    def masks_u8(self) -> List[np.ndarray]:
+        """The (filled) predicted masks of every image so far as (H, W) uint8 arrays of 0 / 255, in order (needs keep_masks=True)."""
+        if not self.keep_masks:
+            raise ValueError("build the FusedSegTestStep with keep_masks=True")
+        return [m for batch in self._masks for m in batch.cpu().numpy()]
+
+    def write_csv(self, path: str) -> str:
+        """`results_segmentation.csv` under `path`, the reference's columns in its order (utils/models.py:52-53, :97-98)."""
+        rows = self.result()
+        os.makedirs(path, exist_ok=True)
+        file = os.path.join(path, "results_segmentation.csv")
+        with open(file, "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(SEG_CSV_COLUMNS)
+            for r in rows:
+                w.writerow([_csv_value(r[c]) for c in SEG_CSV_COLUMNS])
+        return file

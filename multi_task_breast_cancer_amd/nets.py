@@ -1,6 +1,6 @@
-"""MTnnUNet and MTUNetPlusPlus as thin nn.Module shells over HIP step programs.
+"""MTnnUNet, MTUNetPlusPlus and the single-task nnUNet as thin nn.Module shells over HIP step programs.
 
-Drop-in surface: `model(x) -> (logits, segs)` (lists under deep supervision), `.parameters()`,
+Drop-in surface: `model(x) -> (logits, segs)` (lists under deep supervision; nnUNet: the list of heads alone), `.parameters()`,
 `.state_dict()` with the reference's key names (src/models/multitask/MTnnUNet.py:79-132,
 MTUNetPlusPlus.py:47-87 on MONAI 1.3.0 blocks), `.train()`, `.to()`.  All arithmetic runs in
 libmtbc_hip.so; there is no torch / CPU fallback -- forward on a CPU tensor raises.
@@ -44,7 +44,8 @@ def _draw_linear(i: int, o: int):
     return m.weight.detach(), m.bias.detach()
 
 
-def _mtnnunet_params(sequences: int, regions: int, n_classes: int) -> List[Tuple[str, torch.Tensor]]:
+def _nnunet_params(sequences: int, regions: int) -> List[Tuple[str, torch.Tensor]]:
+    """nnUNet2021 (src/models/segmentation/nnUNet.py:74-130), which is also everything MTnnUNet creates before its classification head."""
     w = NNUNET_WIDTHS
     out: List[Tuple[str, torch.Tensor]] = []
     conv_names: List[str] = []            # every nn.Conv2d weight created before the head (re-initialised below)
@@ -76,13 +77,19 @@ def _mtnnunet_params(sequences: int, regions: int, n_classes: int) -> List[Tuple
     wt, b = _draw_conv(w[0] // 2, regions, 1, True)
     out += [("output1.weight", wt), ("output1.bias", b)]
     conv_names.append("output1.weight")
-    # weights_initialization(), MTnnUNet.py:120,134-140: kaiming-normal on the Conv2d modules that exist so far
+    # weights_initialization(), nnUNet.py:121,124-130 / MTnnUNet.py:120,134-140: kaiming-normal on the Conv2d modules that exist so far
     d = dict(out)
     for nm in conv_names:
         nn.init.kaiming_normal_(d[nm], nonlinearity="leaky_relu")
         bn = nm[:-6] + "bias"
         if bn in d:
             nn.init.constant_(d[bn], 0)
+    return out
+
+
+def _mtnnunet_params(sequences: int, regions: int, n_classes: int) -> List[Tuple[str, torch.Tensor]]:
+    w = NNUNET_WIDTHS
+    out = _nnunet_params(sequences, regions)
     # classification head (default torch init), MTnnUNet.py:123-132
     out.append(("process_encoder_5.Conv.weight", _draw_conv(w[4], w[4], 3, False)[0]))
     out.append(("process_decoder_5.Conv.weight", _draw_conv(w[3], w[4], 3, False)[0]))
@@ -141,7 +148,9 @@ def _unetpp_params(in_ch: int, out_ch: int, n_classes: int) -> List[Tuple[str, t
 # ----------------------------------------------------------------------------------------------
 # Forward graphs (emit ops into a StepPlan)
 # ----------------------------------------------------------------------------------------------
-def _graph_mtnnunet(plan: StepPlan, x: Act):
+def _graph_nnunet_parts(plan: StepPlan, x: Act, classifier: bool):
+    """nnUNet2021 (classifier=False: logits is None) and MTnnUNet, which is the same graph plus process_encoder_5, process_decoder_5,
+    classifier.*, GAP and the two Linear layers -- emitted between the decoder and the deep-supervision heads, where they always were."""
     w = NNUNET_WIDTHS
 
     def cell(inputs, cout, name):
@@ -157,6 +166,12 @@ def _graph_mtnnunet(plan: StepPlan, x: Act):
         t = plan.maxpool(e, f"pool{i + 1}")
     bott = level([t], w[4], w[4], "bottleneck")
     up5 = plan.convT(bott, w[4], 2, "upsample5.weight", "upsample5.bias", "up5")   # used twice (F10), computed once
+    if not classifier:
+        # Without classifier.0, up5 has ONE reader, and a lone 3x3 reader would hand its gradient over as 16-bit planes: at 320 output
+        # channels that selects convT2_dgrad_kernel<LP, true, 4>, an instance no MTnnUNet or U-Net++ program launches.  The gradient
+        # stays fp32, as MTnnUNet's (two readers) is: the segmentation-only programs launch only kernel instances the multi-task
+        # programs launch (an 8 x 8 map at 256 x 256 input: nothing to measure either way).
+        up5.grad16_ok = False
     dec_out = {5: w[3], 4: w[2], 3: w[1], 2: w[0], 1: w[0] // 2}
     dec_mid = {5: w[3], 4: w[2], 3: w[1], 2: w[0], 1: w[0]}
     dec, d, up = {}, None, up5
@@ -165,13 +180,15 @@ def _graph_mtnnunet(plan: StepPlan, x: Act):
             up = plan.convT(d, w[i - 1], 2, f"upsample{i}.weight", f"upsample{i}.bias", f"up{i}")
         d = level([enc[i - 1], up], dec_mid[i], dec_out[i], f"decoder{i}")
         dec[i] = d
-    pe5 = cell([enc[4]], w[4], "process_encoder_5")
-    pd5 = cell([dec[5]], w[4], "process_decoder_5")
-    feat = cell([pe5, up5, pd5], 512, "classifier.0")
-    g = plan.gap(feat, "gap")
-    h = plan.linear(g, 256, "classifier.3.weight", "classifier.3.bias", True, "fc1")
-    n_cls = plan.pv("classifier.5.weight").shape[0]
-    logits = plan.linear(h, n_cls, "classifier.5.weight", "classifier.5.bias", False, "logits")
+    logits = None
+    if classifier:
+        pe5 = cell([enc[4]], w[4], "process_encoder_5")
+        pd5 = cell([dec[5]], w[4], "process_decoder_5")
+        feat = cell([pe5, up5, pd5], 512, "classifier.0")
+        g = plan.gap(feat, "gap")
+        h = plan.linear(g, 256, "classifier.3.weight", "classifier.3.bias", True, "fc1")
+        n_cls = plan.pv("classifier.5.weight").shape[0]
+        logits = plan.linear(h, n_cls, "classifier.5.weight", "classifier.5.bias", False, "logits")
     regions = plan.pv("output1.weight").shape[0]
     # deep-supervision heads: ConvT(k = 8 / 4 / 2) + 1x1 conv with nothing in between -> one transposed conv with the
     # combined weights (StepPlan.convT_head); MTBC_NOFUSE_HEADS=1 keeps the reference's two layers (A/B, parity check)
@@ -188,6 +205,14 @@ def _graph_mtnnunet(plan: StepPlan, x: Act):
         o2 = plan.convT_head(dec[2], w[0], 2, "output2.0.weight", "output2.0.bias", "output2.1.weight", "output2.1.bias", "output2")
     o1 = plan.conv1x1(dec[1], regions, "output1.weight", "output1.bias", "output1")
     return logits, [o4, o3, o2, o1]
+
+
+def _graph_mtnnunet(plan: StepPlan, x: Act):
+    return _graph_nnunet_parts(plan, x, True)
+
+
+def _graph_nnunet(plan: StepPlan, x: Act):
+    return _graph_nnunet_parts(plan, x, False)
 
 
 def _graph_unetpp(plan: StepPlan, x: Act):
@@ -260,7 +285,7 @@ class CompiledStep:
         self.mask = self.onehot = None
         if fused_loss is not None:
             self.mask = plan.alloc(N, self.segs[0].C, H, W)
-            self.onehot = plan.alloc(N, self.logits.C)
+            self.onehot = plan.alloc(N, self.logits.C) if self.logits is not None else None      # a segmentation-only model has no class target
             heads = self.segs if net.deep_supervision_outputs else self.segs[-1:]
             self.loss_scale = float(fused_loss.get("loss_scale", net.loss_scale))     # baked into the loss ops; 1.0 under a dynamic scale (the device word carries it)
             plan.fused_losses(heads, self.logits, self.mask, self.onehot, fused_loss["alpha"],
@@ -272,8 +297,9 @@ class CompiledStep:
             for h in (self.segs if net.deep_supervision_outputs else self.segs[-1:]):
                 plan.grad_of(h)
                 h.grad_written = True
-            plan.grad_of(self.logits)
-            self.logits.grad_written = True
+            if self.logits is not None:
+                plan.grad_of(self.logits)
+                self.logits.grad_written = True
         plan.emit_backward()
         self.programs = plan.finalize()
         self.plan = plan
@@ -433,6 +459,8 @@ class HipMultiTaskNet(nn.Module):
         st = self.compiled(x.shape[0], x.shape[2], x.shape[3])
         params = [self._named()[n] for n in self._order]
         outs = _NetFunction.apply(self, st, x, *params)
+        if st.logits is None:                   # segmentation only: the list of heads (nnUNet.py:168)
+            return list(outs)
         logits, segs = outs[0], list(outs[1:])
         if self.deep_supervision_outputs:
             return [logits], segs
@@ -446,13 +474,16 @@ class _NetFunction(torch.autograd.Function):
         st.programs["pack"].run()
         st.programs["fwd"].run()
         ctx.net, ctx.st = net, st
-        logits = st.logits.data.view(st.N, -1).clone()
         segs = [s.data.clone() for s in st.segs]
+        if st.logits is None:
+            return tuple(segs)
+        logits = st.logits.data.view(st.N, -1).clone()
         return (logits, *segs)
 
     @staticmethod
-    def backward(ctx, dlogits, *dsegs):
+    def backward(ctx, *douts):
         net, st = ctx.net, ctx.st
+        dlogits, dsegs = (None, douts) if st.logits is None else (douts[0], douts[1:])
         heads = st.segs if net.deep_supervision_outputs else st.segs[-1:]
         dhead = dsegs if net.deep_supervision_outputs else dsegs[-1:]
         for h, g in zip(heads, dhead):
@@ -460,7 +491,9 @@ class _NetFunction(torch.autograd.Function):
                 h.grad.zero_()
             else:
                 h.grad.copy_(g)
-        if dlogits is None:
+        if st.logits is None:
+            pass
+        elif dlogits is None:
             st.logits.grad.zero_()
         else:
             st.logits.grad.view(st.N, -1).copy_(dlogits)
@@ -491,3 +524,13 @@ class MTUNetPlusPlus(HipMultiTaskNet):
         super().__init__(_unetpp_params(in_channels, out_channels, ncls), in_channels, deep_supervision,
                          _graph_unetpp, force_direct)
         self.n_classes = ncls
+
+
+class nnUNet(HipMultiTaskNet):
+    """src/models/segmentation/nnUNet.py:64-168 (`nnUNet2021`), the single-task segmentation baseline: MTnnUNet without its classification
+    head.  `forward(x)` returns the list [out4, out3, out2, out1] (`:168`); there are no class logits anywhere (n_classes == 0)."""
+    architecture = "nnUNet"
+
+    def __init__(self, sequences: int, regions: int, force_direct: bool = False):
+        super().__init__(_nnunet_params(sequences, regions), sequences, True, _graph_nnunet, force_direct)
+        self.n_classes = 0

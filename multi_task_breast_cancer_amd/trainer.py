@@ -267,6 +267,30 @@ def _check_heads(model, n_classes: int, cls_criterion: str, focal_weight, owner:
     return binary, 2.0 if cls_criterion == "Focal" else 0.0, None if binary else focal_weight
 
 
+def is_seg_only(model) -> bool:
+    """A single-task segmentation model (nets.nnUNet): no classification head, no class logits anywhere in its plans."""
+    return getattr(model, "n_classes", None) == 0
+
+
+def _check_seg_only(alpha, n_classes, focal_weight, cls_criterion, distributed: bool, owner: str) -> None:
+    """What FusedTrainStep and FusedEvalStep refuse of a segmentation-only model (training_segmentation.py has no class label, no mix)."""
+    if alpha is not None and float(alpha) != 1.0:
+        raise ValueError(f"{owner}: a segmentation-only model has no classification loss to mix: alpha must be 1.0, got {alpha}")
+    passed = [k for k, v in (("n_classes", n_classes), ("focal_weight", focal_weight), ("cls_criterion", cls_criterion)) if v is not None]
+    if passed:
+        raise ValueError(f"{owner}: {', '.join(passed)} given, but the model has no classification head")
+    if distributed:
+        raise NotImplementedError(f"{owner}: data parallel is not built for segmentation-only models yet")
+
+
+class SegTrainMetrics(NamedTuple):
+    """`epoch_metrics()` of a segmentation-only training step: the driver's (loss, dice) first (training_segmentation.py:59-62)."""
+    loss: float             # mean over the batches of the step's loss
+    dice: float             # mean over the batches of the per-batch Dice
+    batches: int
+    table: np.ndarray       # (batches, 4) int64: tp, fp, fn, samples of each batch
+
+
 def _fused_loss(step) -> dict:
     """The `fused_loss` settings a step compiles its plan with.  A training and an evaluation step with the same (alpha, weighting, criteria) build
     equal dicts and so share one compiled plan at equal (N, H, W); only a dynamic loss scale adds a key."""
@@ -283,17 +307,34 @@ def _check_in_channels(model, dataset) -> None:
                          f"sequences + dataset.n_augments (experiment_init.load_multitask_experiment_artefacts(n_augments=...))")
 
 
-def fill_batch(st, image: torch.Tensor, mask: torch.Tensor, label: torch.Tensor, binary: bool) -> None:
+def fill_batch(st, image: torch.Tensor, mask: torch.Tensor, label: Optional[torch.Tensor], binary: bool) -> None:
     """H2D / D2D of training_multitask.py:82-84 into the plan's static buffers; the class target is built on the device: the one-hot rows, or, for
-    the binary head, the (N, 1) float label itself (the target of the one-logit criterion)."""
+    the binary head, the (N, 1) float label itself (the target of the one-logit criterion).  A segmentation-only plan has no class target and
+    takes no label (training_segmentation.py:36-37)."""
+    if (st.onehot is None) != (label is None):
+        raise ValueError("a class label was given to a segmentation-only model" if label is not None else
+                         "this model has a classification head: the batch needs its class labels")
     st.x.data.copy_(image, non_blocking=True)
     st.mask.copy_(mask, non_blocking=True)
+    if label is None:
+        return
     lab = label.to(st.onehot.device, non_blocking=True).flatten()
     if binary:
         st.onehot.copy_(lab.view(-1, 1).to(torch.float32))
     else:
         st.onehot.zero_()
         st.onehot.scatter_(1, lab.to(torch.int64).view(-1, 1), 1.0)
+
+
+def _target_of(step, st) -> torch.Tensor:
+    """The class-target buffer the batch-assembly launch writes: the plan's, or -- a segmentation-only plan has none, the launch always
+    writes one -- an (N, 1) scratch of the step's that nothing reads."""
+    if st.onehot is not None:
+        return st.onehot
+    t = step._scratch_target
+    if t is None or t.shape[0] != st.N or t.device != st.mask.device:
+        step._scratch_target = t = torch.empty(st.N, 1, dtype=torch.float32, device=st.mask.device)
+    return t
 
 
 def _capture(body):
@@ -337,6 +378,7 @@ class MetricsTable:
     def __init__(self, model, capacity: int, validation: bool = False, distributed: bool = False):
         self.model, self.capacity, self.eval, self.distributed = model, int(capacity), bool(validation), bool(distributed)
         self.words = _EVAL if self.eval else _TRAIN
+        self.seg_only = is_seg_only(model)      # mtbc_seg_step_metrics: the same rows, no class arguments (the confusion matrix stays zero)
         self.counts = self.state = self.loss_rows = self.weight = None
         self._args = {}             # id(compiled step) -> (the step, its argument struct); None -> the empty shard's
 
@@ -361,6 +403,8 @@ class MetricsTable:
         they are.  Behind the loss program the plan's buffers hold fp32 NCHW logits of the last head, the mask, the class logits and their target,
         in every compute mode."""
         self.buffers()
+        if self.seg_only:
+            return self._seg_arguments(st)
         a = L.EvalMetricsArgs() if self.eval else L.TrainMetricsArgs()
         if st is None:
             a.N, a.n_seg, a.n_logits = 0, 0, n_logits
@@ -382,6 +426,28 @@ class MetricsTable:
             a.shard_weight = self.weight.data_ptr() if self.distributed else None
         return a
 
+    def _seg_arguments(self, st):
+        """`_arguments` of a segmentation-only step: mtbc_seg_step_metrics_args; loss_in stays NULL for training."""
+        a = L.SegStepMetricsArgs()
+        if st is None:
+            a.N, a.n_seg = 0, 0
+        else:
+            seg = st.segs[-1].data
+            loss_out = (st.plan.loss_out,) if self.eval else ()
+            for t in (seg, st.mask) + loss_out:
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    raise L.MtbcError(f"{self.words['kind']} metrics: the step's outputs are not contiguous fp32 buffers")
+            if seg.numel() != st.mask.numel() or any(t.numel() < 4 for t in loss_out):
+                raise L.MtbcError(f"{self.words['kind']} metrics: outputs and targets differ in size")
+            a.seg_logits, a.mask, a.n_seg, a.N = seg.data_ptr(), st.mask.data_ptr(), seg.numel(), st.N
+            if self.eval:
+                a.loss_in = st.plan.loss_out.data_ptr()
+        a.table, a.state, a.capacity = self.counts.data_ptr(), self.state.data_ptr(), self.capacity
+        if self.eval:
+            a.loss_rows = self.loss_rows.data_ptr()
+            a.shard_weight = self.weight.data_ptr() if self.distributed else None
+        return a
+
     def append(self, st, n_logits: int = 0) -> None:
         """The metrics call on the outputs (validation: and the loss words) of the step program that has just run; st = None: the empty shard, which
         only advances the cursor (`n_logits` = the head's width).  Two launches on the current stream, capturable."""
@@ -391,8 +457,9 @@ class MetricsTable:
         if ent is None or ent[0] is not st:
             self._args[key] = ent = (st, self._arguments(st, n_logits))
         lib = L.load()
-        L.check((lib.mtbc_eval_metrics if self.eval else lib.mtbc_train_metrics)(C.byref(ent[1]), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                "eval_metrics" if self.eval else "train_metrics")
+        fn = lib.mtbc_seg_step_metrics if self.seg_only else lib.mtbc_eval_metrics if self.eval else lib.mtbc_train_metrics
+        L.check(fn(C.byref(ent[1]), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                "seg_step_metrics" if self.seg_only else "eval_metrics" if self.eval else "train_metrics")
 
     def reduce(self, coop_err: Optional[torch.Tensor] = None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         """`_reduce_packed` of these buffers: under `distributed` one sum-all-reduce per array (row b of the sum is GLOBAL batch b), one read each."""
@@ -408,12 +475,28 @@ class FusedTrainStep:
 
     metrics=True: the counts behind the reference's Train_dice / Train_acc / Train_F1 (:105-113) are appended on the device by every step --
     `mtbc_train_metrics`, two small launches between the loss program and the backward program (which reuses the outputs' memory) --
-    one table row per batch; `begin_epoch_metrics()` starts an epoch, `epoch_metrics()` reads it back once."""
+    one table row per batch; `begin_epoch_metrics()` starts an epoch, `epoch_metrics()` reads it back once.
 
-    def __init__(self, model, optimizer, alpha: float, inversely_weighted: bool = True, n_classes: int = 3,
+    A segmentation-only model (nets.nnUNet) makes this the step of training_segmentation.py:29-62: no classification argument is taken (alpha,
+    if given, must be 1.0), `load_batch(image, mask)` / `load_indexed` fill no class target, the loss words are [seg, seg, 0, nan_flag],
+    metrics=True appends through `mtbc_seg_step_metrics`, and `epoch_metrics()` returns SegTrainMetrics, the driver's (loss, dice) first.  Data
+    parallel is not built for it."""
+
+    def __init__(self, model, optimizer, alpha: Optional[float] = None, inversely_weighted: bool = True, n_classes: Optional[int] = None,
                  distributed: bool = False, n_buckets: int = 4, focal_weight: Optional[torch.Tensor] = None,
-                 cls_criterion: str = "Focal", graph: Optional[bool] = None, loss_scale=None, metrics: bool = False,
+                 cls_criterion: Optional[str] = None, graph: Optional[bool] = None, loss_scale=None, metrics: bool = False,
                  metrics_capacity: int = 4096, seg_criterion: str = "DICE"):
+        # alpha is required, n_classes defaults to 3 and cls_criterion to "Focal" for a multi-task model; None = "not given", which is all a
+        # segmentation-only model accepts
+        self.seg_only = is_seg_only(model)
+        if self.seg_only:
+            _check_seg_only(alpha, n_classes, focal_weight, cls_criterion, distributed, "the fused step")
+            alpha = 1.0
+        else:
+            if alpha is None:
+                raise TypeError("FusedTrainStep: alpha (the weight of the segmentation loss in the mix) is required for a multi-task model")
+            n_classes = 3 if n_classes is None else n_classes
+            cls_criterion = "Focal" if cls_criterion is None else cls_criterion
         # seg_criterion: the reference's `loss.function` (experiment_init.py:199-232) -- "DICE" | "BCE" | "FocalDICE" | "Jaccard", all in the same
         # two loss ops of the step program (mtbc_dice_args.kind); the remaining names are not on HIP (experiment_init.init_criterion_segmentation).
         self.seg_criterion = _check_seg_criterion(seg_criterion, distributed)
@@ -447,7 +530,12 @@ class FusedTrainStep:
         if self.scaler is not None:
             self.scaler.attach(optimizer)
         self._graphs = {}
-        self.binary, self.cls_gamma, self.focal_weight = _check_heads(model, n_classes, cls_criterion, focal_weight, "the fused step")
+        if self.seg_only:
+            self.binary, self.cls_gamma, self.focal_weight = False, 2.0, None
+        else:
+            self.binary, self.cls_gamma, self.focal_weight = _check_heads(model, n_classes, cls_criterion, focal_weight, "the fused step")
+        self._epoch_loss = None         # segmentation only, metrics=True: device float64 [sum of the steps' loss, steps] behind epoch_metrics()
+        self._scratch_target = None     # segmentation only: where the batch-assembly launch puts the labels nobody reads
         self.model, self.opt = model, optimizer
         self.alpha, self.iw, self.n_classes = float(alpha), bool(inversely_weighted), n_classes
         self.distributed = distributed
@@ -479,7 +567,7 @@ class FusedTrainStep:
             st.buckets = plan_buckets(st.slot_ready, self.model.flat_numel, self.n_buckets)
         return st
 
-    def load_batch(self, image: torch.Tensor, mask: torch.Tensor, label: torch.Tensor, weight: Optional[float] = None):
+    def load_batch(self, image: torch.Tensor, mask: torch.Tensor, label: Optional[torch.Tensor] = None, weight: Optional[float] = None):
         """H2D / D2D of training_multitask.py:82-84 into the plan's static buffers (one-hot on the device).
         `weight` = this rank's share n_local / n_batch of the global batch (EpochIndex.weights) when shards are NOT
         equal -- the short last batch of `DataLoader(drop_last=False)`, BUSI_dataloader.py:146: the local mean-loss
@@ -507,7 +595,7 @@ class FusedTrainStep:
         In stream order in front of the step and, with graph=True, outside the replayed region, where `load_batch` sits.  `weight` as in `load_batch`."""
         _check_in_channels(self.model, dataset)
         st = self._compiled(len(index), dataset.H, dataset.W)
-        dataset.assemble(index, params, n_onehot=0 if self.binary else 3, out=(st.x.data, st.mask, st.onehot))
+        dataset.assemble(index, params, n_onehot=0 if self.binary or self.seg_only else 3, out=(st.x.data, st.mask, _target_of(self, st)))
         self._set_shard_weight(st, weight)
         return st
 
@@ -519,16 +607,30 @@ class FusedTrainStep:
 
     def _append_metrics(self, st) -> None:
         """`mtbc_train_metrics` on the outputs of the forward that has just run (st = None: the empty shard)."""
-        self._metrics_table().append(st, self._st.logits.C)
+        self._metrics_table().append(st, 0 if self.seg_only else self._st.logits.C)
 
     def begin_epoch_metrics(self) -> None:
         """Zero the table, the confusion matrix and the cursor in stream order (outside any replayed graph: the buffers stay where they are)."""
         self._metrics_table().zero()
+        if self._epoch_loss is not None:
+            self._epoch_loss.zero_()
 
-    def epoch_metrics(self) -> TrainMetrics:
+    def _count_loss(self, losses: torch.Tensor) -> None:
+        """Segmentation only, metrics=True: the step's loss into the epoch's device sum, in stream order behind the step (outside a replayed graph)."""
+        if self.seg_only and self.metrics:
+            if self._epoch_loss is None:
+                self._epoch_loss = torch.zeros(2, dtype=torch.float64, device=losses.device)
+            self._epoch_loss[0] += losses[0].double()
+            self._epoch_loss[1] += 1
+
+    def epoch_metrics(self):
         """The epoch so far as the reference's numbers: under data parallel ONE sum-all-reduce of the table and the confusion matrix (row b of the sum is
         GLOBAL batch b), then ONE device-to-host read.  MtbcError when the table was too small or the ranks' cursors disagree."""
-        return train_metrics_from_packed(self._metrics_table().reduce()[0], self.metrics_capacity, self.world)
+        m = train_metrics_from_packed(self._metrics_table().reduce()[0], self.metrics_capacity, self.world)
+        if not self.seg_only:
+            return m
+        total, steps = (0.0, 0.0) if self._epoch_loss is None else self._epoch_loss.cpu().tolist()
+        return SegTrainMetrics(total / steps if steps else 0.0, m.dice, m.batches, m.table)
 
     def _apply_update(self, st) -> None:
         """Adam on the (all-reduced) flat gradients: the static path divides the baked loss scale out, the dynamic path checks, skips or applies, and
@@ -580,6 +682,7 @@ class FusedTrainStep:
         run_or_replay(self, st, key, body)
         self.losses = st.plan.loss_out
         self._coop_err = self.model.coop_error_word()
+        self._count_loss(self.losses)
         return self.losses
 
     def run(self, st) -> torch.Tensor:
@@ -616,6 +719,7 @@ class FusedTrainStep:
         self._apply_update(st)
         self.losses = st.plan.loss_out
         self._coop_err = self.model.coop_error_word()      # ONE word per model: every compiled step's kernels set it
+        self._count_loss(self.losses)
         return self.losses
 
     def run_empty(self) -> None:
@@ -635,7 +739,7 @@ class FusedTrainStep:
             allreduce_buckets(self.model.flat_g, [b])
         self._apply_update(self._st)
 
-    def __call__(self, image, mask, label, weight: Optional[float] = None) -> torch.Tensor:
+    def __call__(self, image, mask, label=None, weight: Optional[float] = None) -> torch.Tensor:
         return self.run(self.load_batch(image, mask, label, weight))
 
     def check_nan(self) -> None:
@@ -694,9 +798,21 @@ class FusedEvalStep:
     integer rows sum to the global batch's counts exactly, the weighted loss rows to its mean losses (the criteria allowed here are means over
     samples, and total is linear in seg and cls).  The step itself issues no collective, so graph=True works under it."""
 
-    def __init__(self, model, alpha: float, inversely_weighted: bool = True, n_classes: int = 3,
-                 focal_weight: Optional[torch.Tensor] = None, cls_criterion: str = "Focal", seg_criterion: str = "DICE",
+    def __init__(self, model, alpha: Optional[float] = None, inversely_weighted: bool = True, n_classes: Optional[int] = None,
+                 focal_weight: Optional[torch.Tensor] = None, cls_criterion: Optional[str] = None, seg_criterion: str = "DICE",
                  on_device: bool = False, graph: Optional[bool] = None, distributed: bool = False, capacity: int = 4096):
+        # a segmentation-only model (nets.nnUNet): `validate_one_epoch` of training_segmentation.py:65-88 -- no label, no classification argument,
+        # the metrics launch is `mtbc_seg_step_metrics`, and `result()` is the driver's (val_loss, val_dice)
+        self.seg_only = is_seg_only(model)
+        if self.seg_only:
+            _check_seg_only(alpha, n_classes, focal_weight, cls_criterion, distributed, "FusedEvalStep")
+            alpha = 1.0
+        else:
+            if alpha is None:
+                raise TypeError("FusedEvalStep: alpha (the weight of the segmentation loss in the mix) is required for a multi-task model")
+            n_classes = 3 if n_classes is None else n_classes
+            cls_criterion = "Focal" if cls_criterion is None else cls_criterion
+        self._scratch_target = None
         self.model, self.alpha, self.iw, self.n_classes = model, float(alpha), bool(inversely_weighted), n_classes
         self.on_device, self.distributed, self.capacity = bool(on_device), bool(distributed), int(capacity)
         if self.distributed and not self.on_device:
@@ -713,7 +829,10 @@ class FusedEvalStep:
         self._graphs = {}
         self._table = MetricsTable(model, self.capacity, validation=True, distributed=self.distributed) if self.on_device else None
         self.seg_criterion = _check_seg_criterion(seg_criterion, self.distributed)      # as `cls_criterion`: the criterion the run trains with
-        self.binary, self.cls_gamma, self.focal_weight = _check_heads(model, n_classes, cls_criterion, focal_weight, "FusedEvalStep")
+        if self.seg_only:
+            self.binary, self.cls_gamma, self.focal_weight = False, 2.0, None
+        else:
+            self.binary, self.cls_gamma, self.focal_weight = _check_heads(model, n_classes, cls_criterion, focal_weight, "FusedEvalStep")
         self._coop_err = None
         self.reset()
 
@@ -729,7 +848,7 @@ class FusedEvalStep:
             self._table.zero()
 
     @torch.no_grad()
-    def __call__(self, image: torch.Tensor, mask: torch.Tensor, label: torch.Tensor, weight: Optional[float] = None) -> None:
+    def __call__(self, image: torch.Tensor, mask: torch.Tensor, label: Optional[torch.Tensor] = None, weight: Optional[float] = None) -> None:
         """`weight`: this rank's share n_local / n_batch of the global batch (distributed=True; None = 1)."""
         N, _, H, W = image.shape
         st = self._compiled(N, H, W)
@@ -745,7 +864,7 @@ class FusedEvalStep:
         transform), then the same step program and the same device accumulators.  `weight` as in `__call__`."""
         _check_in_channels(self.model, dataset)
         st = self._compiled(len(index), dataset.H, dataset.W)
-        dataset.assemble(index, None, n_onehot=0 if self.binary else 3, out=(st.x.data, st.mask, st.onehot))
+        dataset.assemble(index, None, n_onehot=0 if self.binary or self.seg_only else 3, out=(st.x.data, st.mask, _target_of(self, st)))
         self._evaluate_resident(st, weight)
 
     def _evaluate_resident(self, st, weight: Optional[float]) -> None:
@@ -770,22 +889,24 @@ class FusedEvalStep:
         empty_gt = (tp + fn) == 0
         dice = torch.where(empty_gt, torch.where((tp + fp) == 0, torch.ones_like(tp), torch.zeros_like(tp)),
                            2 * tp / torch.clamp(2 * tp + fp + fn, min=1.0))          # metrics.py:255-267
-        logit = st.logits.data.view(N, -1)
         self._acc[:3] += st.plan.loss_out[:3].double()
+        self._acc[3] += dice
+        self._acc[4] += 1
+        if self.seg_only:
+            return
+        logit = st.logits.data.view(N, -1)
         if self.binary:
             pred = (torch.sigmoid(logit[:, 0]) > 0.5).to(torch.int64)
             gt = gt_binary
         else:
             pred = logit.argmax(dim=1)
             gt = st.onehot.argmax(dim=1)
-        self._acc[3] += dice
-        self._acc[4] += 1
         self._conf.view(-1).index_add_(0, gt * 3 + pred, torch.ones_like(gt))
 
     # ---- on_device=True ------------------------------------------------------------------------------------------------------
     def _append_eval(self, st) -> None:
         """`mtbc_eval_metrics` on the outputs and the loss words of the step program that has just run (st = None: the empty shard)."""
-        self._table.append(st, 1 if self.binary else 3)
+        self._table.append(st, 0 if self.seg_only else 1 if self.binary else 3)
 
     def _evaluate_on_device(self, st, weight: Optional[float]) -> None:
         """The batch resident in the plan's buffers as launches only: pack -> forward -> losses -> mtbc_eval_metrics, eager or as one graph replay."""
@@ -815,13 +936,16 @@ class FusedEvalStep:
         if self._acc is None and (self._table is None or self._table.counts is None):
             raise L.MtbcError("FusedEvalStep.result() before any batch was evaluated")
         if self.on_device:
-            return eval_result_from_packed(*self._table.reduce(self._coop_err), self.capacity, self.world)
+            r = eval_result_from_packed(*self._table.reduce(self._coop_err), self.capacity, self.world)
+            return (r[0], r[1]) if self.seg_only else r
         err = self._coop_err
         if err is not None and int(err.item()) != 0:
             L.raise_coop_timeout()
         acc = self._acc.cpu().tolist()
         conf = self._conf.cpu().numpy().astype(np.float64)
         nb = max(acc[4], 1.0)
+        if self.seg_only:               # training_segmentation.py:88
+            return acc[0] / nb, acc[3] / nb
         accuracy, f1w = classification_scores(conf)       # sklearn accuracy_score / f1_score(labels=[0,1,2], average='weighted') (:155-156)
         return acc[0] / nb, acc[3] / nb, accuracy, f1w, acc[1] / nb, acc[2] / nb
 
@@ -830,7 +954,10 @@ def validate_one_epoch(step: FusedEvalStep, loader, device) -> tuple:
     """training_multitask.py:119-159 on the fused evaluation step; `loader` yields the reference's batch dicts."""
     step.reset()
     for data in loader:
-        step(data["image"].to(device), data["mask"].to(device), data["label"].to(device))
+        if getattr(step, "seg_only", False):
+            step(data["image"].to(device), data["mask"].to(device))
+        else:
+            step(data["image"].to(device), data["mask"].to(device), data["label"].to(device))
     return step.result()
 
 
@@ -893,6 +1020,8 @@ def train_one_epoch_with_metrics(step: FusedTrainStep, dataset, tables, lr: Opti
     step.begin_epoch_metrics()
     total, _, _ = _train_epoch(step, dataset, tables, lr)
     m = step.epoch_metrics()
+    if getattr(step, "seg_only", False):        # training_segmentation.py:62
+        return total, m.dice
     return total, m.dice, m.accuracy, m.f1
 
 
@@ -921,13 +1050,24 @@ def validate_one_epoch_indexed(step: FusedEvalStep, dataset, tables) -> tuple:
 # one fold of the reference's training script (training_multitask.py:216-280) on the indexed epochs
 # ------------------------------------------------------------------------------------------------
 def fit_fold(step: FusedTrainStep, eval_step: FusedEvalStep, dataset, train_index, val_index, scheduler, run_dir: str, epochs: int,
-             max_patience: int, transforms: Optional[dict], seed: int, plateau: bool, checkpoint_name: str = "model_best") -> List[tuple]:
+             max_patience: int, transforms: Optional[dict], seed: int, plateau: bool, checkpoint_name: str = "model_best",
+             test_step=None, test_index=None) -> List[tuple]:
     """The epoch loop of training_multitask.py:216-280: `train_index` / `val_index` are dataset_index.EpochIndex objects over the rows of
     `dataset` (a device_data.DeviceDataset), `scheduler` a torch scheduler on `step.opt` stepped once per epoch -- with the validation loss
     when `plateau` (:234-237).  Per epoch: the learning rate of the day, the epoch's device tables (`transforms`, `seed`), training with
     metrics, validation, the scheduler, a checkpoint under run_dir/checkpoint_name on a new best validation loss, the patience rule, one row of
     run_dir/metrics.csv under METRICS_HEADER and the reference's log line.  Files are written by rank 0 only under data parallel.
-    Returns the rows as tuples (epoch, lr, train_loss, val_loss, train_dice, val_dice, train_acc, train_f1, val_acc, val_f1)."""
+    Returns the rows as tuples (epoch, lr, train_loss, val_loss, train_dice, val_dice, train_acc, train_f1, val_acc, val_f1).
+
+    With the segmentation pair of steps (both built on a nets.nnUNet) this is the epoch loop of training_segmentation.py:143-201 instead:
+    `test_step` (an inference.FusedSegTestStep) and `test_index` are required, because that driver runs its testing phase after EVERY epoch
+    (:179) and writes its mean DICE into the row; metrics.csv gets the header `epoch,LR,Train,Validation,Test,Train_loss,Val_loss` and the
+    row of :192-195 (the learning rate AFTER the scheduler step); the rows returned are (epoch, lr, train_dice, val_dice, test_dice,
+    train_loss, val_loss).  Rotation: that driver draws ONE bound d = np.random.choice(range(0, 360)) per run (:118) and rotates by
+    U(-d, d): pass transforms={"horizontal_flip": .5, "vertical_flip": .5, "rotation": d / 360}."""
+    if getattr(step, "seg_only", False) or getattr(eval_step, "seg_only", False):
+        return _fit_fold_segmentation(step, eval_step, test_step, dataset, train_index, val_index, test_index, scheduler, run_dir, epochs,
+                                      max_patience, transforms, seed, plateau, checkpoint_name)
     import logging
     import time
     from . import checkpoint as CK
@@ -978,6 +1118,75 @@ def fit_fold(step: FusedTrainStep, eval_step: FusedEvalStep, dataset, train_inde
         rows.append(row)
         if writer:
             CK.write_metrics_file(metrics_path, CK.metrics_row(*row))
+        if stopper.should_stop:
+            logging.info(f"\nValidation loss did not improve over the last {stopper.patience} epochs. Stopping training")
+            break
+    return rows
+
+
+def test_one_epoch_indexed(test_step, dataset, tables) -> list:
+    """The testing phase of the segmentation driver from a device-resident dataset: the batches of `tables` (no transforms) through an
+    inference.FusedSegTestStep; the rows of results_segmentation.csv, read back once."""
+    _check_tables(dataset, tables)
+    _check_in_channels(test_step.model, dataset)
+    test_step.reset()
+    scratch = None
+    for b in range(len(tables)):
+        index, _, n_local, _ = tables.batch(b)
+        if n_local:
+            st = test_step.model.compiled(len(index), dataset.H, dataset.W)
+            if scratch is None or scratch.shape[0] != st.N:
+                scratch = torch.empty(st.N, 1, dtype=torch.float32, device=dataset.device)
+            image, mask, _ = dataset.assemble(index, None, n_onehot=0, out=(st.x.data, torch.empty_like(st.segs[-1].data), scratch))
+            test_step(image, mask)
+    return test_step.result()
+
+
+def _fit_fold_segmentation(step, eval_step, test_step, dataset, train_index, val_index, test_index, scheduler, run_dir, epochs, max_patience,
+                           transforms, seed, plateau, checkpoint_name) -> List[tuple]:
+    """`fit_fold` for the segmentation pair of steps: training_segmentation.py:143-201."""
+    import logging
+    import time
+    from . import checkpoint as CK
+    from .device_data import EpochTables
+    if not (getattr(step, "seg_only", False) and getattr(eval_step, "seg_only", False)):
+        raise ValueError("fit_fold: the training and the evaluation step must both be built on a segmentation-only model, or neither")
+    if test_step is None or test_index is None:
+        raise ValueError("fit_fold: the segmentation driver runs its testing phase after every epoch: pass test_step (inference.FusedSegTestStep) "
+                         "and test_index")
+    os.makedirs(run_dir, exist_ok=True)
+    metrics_path = os.path.join(run_dir, "metrics.csv")
+    CK.write_metrics_file(metrics_path, CK.SEG_METRICS_HEADER)
+    stopper = CK.EarlyStopping(max_patience)
+    val_tables = EpochTables(val_index, 0, None, device=dataset.device)
+    test_tables = EpochTables(test_index, 0, None, device=dataset.device)
+    rows = []
+    for epoch in range(int(epochs)):
+        t0 = time.perf_counter()
+        tables = EpochTables(train_index, epoch, transforms, seed=seed, device=dataset.device)
+        train_loss, train_dice = train_one_epoch_with_metrics(step, dataset, tables)
+        val_loss, val_dice = validate_one_epoch_indexed(eval_step, dataset, val_tables)
+        if plateau:
+            scheduler.step(val_loss)
+        else:
+            scheduler.step()
+        if stopper.update(val_loss):
+            CK.save_checkpoint(os.path.join(run_dir, checkpoint_name), epoch, step.model, step.opt, val_loss, scaler=step.scaler)
+        epoch_time = time.perf_counter() - t0
+        test_rows = test_one_epoch_indexed(test_step, dataset, test_tables)
+        test_dice = float(np.mean([r["DICE"] for r in test_rows]))
+        lr = step.opt.param_groups[0]["lr"]
+        logging.info(f'EPOCH {epoch} --> '
+                     f'|| Training loss {train_loss:.4f} '
+                     f'|| Validation loss {val_loss:.4f} '
+                     f'|| Training DICE {train_dice:.4f} '
+                     f'|| Validation DICE  {val_dice:.4f} '
+                     f'|| Patience: {stopper.patience} '
+                     f'|| Epoch time: {epoch_time:.4f} '
+                     f'|| LR: {lr:.8f}')
+        row = (epoch, lr, train_dice, val_dice, test_dice, train_loss, val_loss)
+        rows.append(row)
+        CK.write_metrics_file(metrics_path, CK.seg_metrics_row(*row))
         if stopper.should_stop:
             logging.info(f"\nValidation loss did not improve over the last {stopper.patience} epochs. Stopping training")
             break
