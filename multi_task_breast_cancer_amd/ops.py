@@ -75,7 +75,7 @@ def conv3x3_case_args(op: int, N: int, segs: Sequence[int], Cout: int, H: int, W
                       c8: bool = False, out_c8: bool = False, out_fp16: bool = False, dx_c8: bool = False, bias: bool = True,
                       in_kernel_reduce: bool = False, accumulate: Optional[Sequence[int]] = None, packed: Optional[bool] = None,
                       force_direct: bool = False, accumulate_dw: bool = False, stats: bool = False, norm: Optional[float] = None,
-                      out_partial: bool = False) -> "L.Conv3x3Args":
+                      out_partial: bool = False, out_accumulate: bool = False) -> "L.Conv3x3Args":
     """The argument struct of ONE 3x3 convolution call (op = L.OP_CONV3_FWD / _DGRAD / _WGRAD), the only place that fills it.  ptrs: "in" ->
     the segments (tensors, or C8 tensors) and field name -> tensor / C8 / None for NULL; None = distinct 16-byte aligned dummies that nothing
     may dereference (for conv3x3_kernel_name).  c8: operands in MTBC_LAYOUT_C8 (one segment of at most L.STEM_MAX_CIN channels stays fp32
@@ -83,7 +83,8 @@ def conv3x3_case_args(op: int, N: int, segs: Sequence[int], Cout: int, H: int, W
     (default: the dgrad and every forward but the stem's); accumulate: the dgrad's per-segment codes 0 .. 3 (default: the first segment
     overwritten, the others accumulated; dx_c8: all 3 = channel-blocked 16-bit segments).  Forward: out_c8 (+ out_fp16) = a channel-blocked
     16-bit output, stats = the InstanceNorm statistics partials of the epilogue, norm = the slope of the norm-backward epilogue of a gathered
-    dgrad (norm_z / _mean / _rstd / _gamma / _beta), out_partial = its planar partial.  Weight gradient: accumulate_dw, in_kernel_reduce =
+    dgrad (norm_z / _mean / _rstd / _gamma / _beta), out_partial = its planar partial, out_accumulate = the result added to fp32 planes (a
+    gathered dgrad into a gradient something else has written).  Weight gradient: accumulate_dw, in_kernel_reduce =
     offer the counters of the in-kernel split-K reduction."""
     lib = L.load()
     ptr = _ptr(ptrs, _C3_DUMMY.__getitem__)
@@ -99,7 +100,7 @@ def conv3x3_case_args(op: int, N: int, segs: Sequence[int], Cout: int, H: int, W
     if (op != L.OP_CONV3_WGRAD and not (stem and op == L.OP_CONV3_FWD)) if packed is None else packed:
         a.w_packed = ptr("w_packed")
     if op == L.OP_CONV3_FWD:
-        a.out, a.bias = ptr("out"), (ptr("bias") if bias else None)
+        a.out, a.bias, a.out_accumulate = ptr("out"), (ptr("bias") if bias else None), int(out_accumulate)
         if out_c8:
             a.out_layout = L.LAYOUT_C8
             a.out_type = 2 if out_fp16 else 0

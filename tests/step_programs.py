@@ -32,6 +32,65 @@ def build_step(arch, dtype, N, size, reserve_cus=0):
 
 
 # ------------------------------------------------------------------ the key functions: the only places that decide what "the same launch" means
+_CONV3_KC = 8          # conv3x3.hip:77, KC: input channels per LDS chunk of the fp32 kernels (the 16-bit kernels: LPKC = 32, conv3x3.hip:603)
+
+
+def _conv3_key(a, op):
+    """Coverage key of ONE mtbc_conv3x3_fwd / _dgrad / _wgrad call: the FULL string of mtbc_conv3x3_kernel_name -- the kernel instance and the
+    reduction behind a weight gradient: " + splitk_reduce", " + splitk_fixup", " + channel_sums", or nothing (blocks store straight into dw) --
+    + the branches the ARGUMENTS select inside those kernels.  The only place that decides what "the same launch" means for the guard below.
+    A field the call does not read does not enter its key (line numbers: csrc/conv3x3.hip).
+    Known blind spot: the split count and the even-dealt split plan of plan_wgrad (tiles_per_split < 0, conv3x3.hip:3969) are host plan
+    details that mtbc_conv3x3_kernel_name does not expose; they are not in the key and are not re-derived here."""
+    L = ops.L
+    name = ops.conv3x3_kernel_name(a, op)
+    c8 = a.operand_layout == L.LAYOUT_C8
+    segs = [a.in_[i] for i in range(a.n_in)]
+    chunk = 32 if a.compute in (1, 2) else _CONV3_KC
+    f = []
+    if op == L.OP_CONV3_FWD:
+        # rows = the channels written (Cout); the MFMA reduces over the segmented input (Cin)
+        if a.bias:                            # (p.bias: the igemm epilogues 1136 and 1344, the stem and direct kernels; 4160: NULL with norm_z)
+            f.append("bias")
+        if a.stats_partial:                   # (1037 `p.stats`; 4130 the stem kernels; 4167: refused with planar operands and output)
+            f.append("stats")
+        if a.out_accumulate:                  # (4112: the output segment's accumulate; 4114: channel-blocked operands only)
+            f.append("out_acc")
+        if c8 and a.out_partial:              # (3814 p.extra, with norm_z only: 4160)
+            f.append("out_partial")
+        if c8 and a.norm_z:                   # (3814 p.nz; p.ngamma / p.nbeta: both or neither, 4160)
+            f.append("norm_affine" if a.norm_gamma else "norm_plain")
+        rows, red, every = a.Cout, a.Cin, chunk
+    elif op == L.OP_CONV3_DGRAD:
+        # rows = the channels written (the dx segments, Cin); the MFMA reduces over dout (Cout: one segment, no boundary inside)
+        f.append("codes=" + ",".join(str(c) for c in sorted({s.accumulate for s in segs})))      # (4214-4223, make_segtable 4209)
+        rows, red, every = a.Cin, a.Cout, 16      # (straddle: a boundary of the WRITTEN segments inside a 16-row tile -- one tile writes two segments)
+    else:
+        # rows = the output channels of dw (Cout), columns = the segmented input (Cin) in blocks of the chunk
+        if a.dbias:                           # (4303 want_bias, 4320 BIAS, 4411 the bias row of the reduction, 4422 channel_sums; 4272: the stem refuses it)
+            f.append("dbias")
+        if a.accumulate_dw:                   # (4296, 4306, 4314, 4411, 4493)
+            f.append("acc_dw")
+        rows, red, every = a.Cout, a.Cin, chunk
+    if a.n_in > 1:
+        f.append("segs>1")
+    acc = 0
+    for s in segs[:-1]:                       # fwd / wgrad: one chunk of the reduced / column channels reads two segments
+        acc += s.channels
+        if acc % every:
+            f.append("straddle")
+            break
+    if rows % 16:
+        f.append("ragged_rows")
+    if red % chunk:
+        f.append("ragged_k")
+    if any(s.batch_stride != s.channels * a.H * a.W for s in segs):
+        f.append("strided")
+    if a.force_direct and not c8:             # (4115, 4169, 4224, plan_wgrad 3980 / 4022: the planar dispatch only)
+        f.append("force_direct")
+    return name, tuple(f)
+
+
 def _instnorm_key(a, backward):
     """Coverage key of ONE mtbc_instnorm_lrelu_fwd / _bwd call: the launches mtbc_instnorm_kernel_name plans (kernel instances, block sizes,
     team size T; the number of rounds only as 1 or >1) + the branches the ARGUMENTS select inside those kernels.  The only place that
@@ -204,8 +263,8 @@ def _fields(s, *names):
 def collect_conv3x3(prog, i):
     op = prog[i]
     if op.kind in (L.OP_CONV3_FWD, L.OP_CONV3_DGRAD, L.OP_CONV3_WGRAD):
-        # kernel instance only: the split-K reductions behind the weight gradients are one kernel, checked with all of them
-        return 1, op.kind, ops.conv3x3_kernel_name(op.u.conv3, op.kind).split(" + ")[0], _fields(op.u.conv3, "N", "Cin", "Cout", "H", "W")
+        a = op.u.conv3          # where: (N, Cin, Cout, H, W, the segments' channels)
+        return 1, op.kind, (op.kind, _conv3_key(a, op.kind)), _fields(a, "N", "Cin", "Cout", "H", "W") + (tuple(a.in_[i].channels for i in range(a.n_in)),)
 
 
 def collect_instnorm(prog, i):

@@ -665,6 +665,9 @@ _CASE_EXTRA = [
     ("conv3x3", L.OP_CONV3_FWD, (2, [16, 8], 16, 16, 16), dict(_BF16, out_c8=True, stats=True)),                 # epilogue statistics
     ("conv3x3", L.OP_CONV3_FWD, (2, [16], 16, 16, 16), dict(_F16_O1, bias=False, stats=True, norm=0.1, out_partial=True)),   # the gathered dgrad's norm epilogue
     ("conv3x3", L.OP_CONV3_FWD, (2, [3], 24, 16, 16), dict(_BF16_O3, stats=True)),                               # the stem with statistics
+    ("conv3x3", L.OP_CONV3_FWD, (2, [16, 16], 16, 16, 16), dict(_BF16, bias=False, out_accumulate=True)),        # a gathered dgrad added to fp32 planes
+    ("conv3x3", L.OP_CONV3_WGRAD, (1, [64], 48, 16, 16), dict(_BF16, bias=False)),                               # one image range: the direct store
+    ("conv3x3", L.OP_CONV3_DGRAD, (2, [8, 16], 16, 16, 16), dict(_BF16, accumulate=[0, 0])),
     ("conv3x3", L.OP_CONV3_FWD, (2, [8, 8], 16, 16, 16), dict(packed=False, force_direct=True, bias=False)),
     ("conv3x3", L.OP_CONV3_DGRAD, (2, [8, 16], 16, 16, 16), dict(_BF16, accumulate=[1, 2])),                     # 16-bit planar second segment
     ("conv3x3", L.OP_CONV3_DGRAD, (2, [8, 16], 16, 16, 16), dict(_F16, dx_c8=True)),
@@ -684,12 +687,14 @@ _CASE_EXTRA = [
 
 def _case_rows():
     """(family, op, shape, mode, pair) of every row of the four selection tables -- InstanceNorm up to 64 x 64 planes only: larger ones with a
-    channel-blocked output ask the device for the team plan -- and of _CASE_EXTRA."""
+    channel-blocked output ask the device for the team plan --, of tests/test_ops_gpu.py CONV3_STEP_CASES and of _CASE_EXTRA."""
     kinds = {"fwd": L.OP_CONV3_FWD, "dgrad": L.OP_CONV3_DGRAD, "wgrad": L.OP_CONV3_WGRAD}
     rows = [("conv3x3", kinds[op], (N, segs, Cout, H, W), mode, False) for op, N, segs, Cout, H, W, mode, _ in SELECTION]
     rows += [("instnorm", bwd, (N, Cc, H, W), mode, False) for bwd, N, Cc, H, W, mode, _ in NORM_SELECTION if H * W <= 64 * 64]
     rows += [("convT", _CT_OPS[op], shape, mode, pair) for op, shape, mode, pair, _ in CONVT_SELECTION]
     rows += [(helper, kind, shape, mode, False) for helper, kind, shape, mode, _ in SMALL_OP_SELECTION]
+    import test_ops_gpu          # (imports without a device) every row of the conv3x3 step-instance table: its modes are the engine's
+    rows += [("conv3x3", op, (N, segs, Cout, H, W), mode, False) for op, N, segs, Cout, H, W, mode in test_ops_gpu.CONV3_STEP_CASES]
     return rows + [r + (False,) for r in _CASE_EXTRA]
 
 

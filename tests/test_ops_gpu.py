@@ -1,5 +1,6 @@
 """Per-op parity of the HIP kernels (through the C-ABI) against the same torch op on the CPU in fp32.
 Tolerances are written per test; integer results are bit-exact."""
+import ctypes as C
 import re
 
 import numpy as np
@@ -11,8 +12,8 @@ pytestmark = pytest.mark.gpu
 
 from multi_task_breast_cancer_amd import ops  # noqa: E402
 from oracle import torch_oracle as O  # noqa: E402
-from step_programs import (STEP_PROGRAMS, _c8_key, _convT_key, _dparam_key, _instnorm_key, _pack_key, _small_op_key,  # noqa: E402
-                           _wview_key, assert_all_tested, survey)
+from step_programs import (STEP_PROGRAMS, _c8_key, _conv3_key, _convT_key, _dparam_key, _instnorm_key, _pack_key,  # noqa: E402
+                           _small_op_key, _wview_key, assert_all_tested, survey)
 
 DEV = "cuda:0"
 
@@ -1385,39 +1386,332 @@ def test_conv3x3_bench_instances_match_fp64(N, segs, Cout, H, W, mode, wgrad):
         _close(db, dbr.float(), 1e-5, 2e-5 * max(1.0, dbr.abs().max().item()), "dbias")
 
 
-def _reference_tested_instances():
-    """The conv3x3 instances the element-wise reference tests of this file launch, from their own case tables through
-    mtbc_conv3x3_kernel_name (kernel instance only: the split-K reductions behind the weight gradients are one kernel, checked with all of them)."""
-    F_, D_, W_ = ops.L.OP_CONV3_FWD, ops.L.OP_CONV3_DGRAD, ops.L.OP_CONV3_WGRAD
-    calls = []
-    for case in BENCH_CASES:
+# ------------------------------------------------------------------ the 3x3 convolution launches of the step programs, keyed by their arguments
+# (op, N, segs, Cout, H, W, mode): one row per coverage key (tests/step_programs.py _conv3_key) of profiles/conv3x3_step_keys.txt that no older
+# fp64 test of this file makes; mode = the keywords of ops.conv3x3_case_args, as the engine fills the struct (engine.py conv_cell,
+# _gathered_dgrad, _conv_cell_backward).  Shapes: the key holds neither N nor the map size, so each row takes the fewest pixels -- of at
+# least 2 images (3 for a weight gradient), 20 rows and 48 columns where the step's map is that large: a ragged last tile in both directions --
+# at which the dummy-pointer struct has the key of the step's launch (in brackets: that launch).
+F_, D_, W_ = ops.L.OP_CONV3_FWD, ops.L.OP_CONV3_DGRAD, ops.L.OP_CONV3_WGRAD
+CONV3_STEP_CASES = [
+    (F_, 4, [48, 48, 48], 48, 512, 48, dict(compute=1, c8=True, bias=False, out_accumulate=True)),                      # conv3x3_igemm_c8_kernel<3, 0, false, 4, 0>  [32 x 144 -> 48 @ 128 x 128 in MTUNetPlusPlus bf16]
+    (F_, 4, [48, 48], 48, 512, 48, dict(compute=1, c8=True, bias=False, out_accumulate=True)),                          # conv3x3_igemm_c8_kernel<3, 0, false, 4, 0>  [32 x 96 -> 48 @ 128 x 128 in MTUNetPlusPlus bf16]
+    (F_, 48, [96, 96], 96, 20, 48, dict(compute=1, c8=True, bias=False, out_accumulate=True)),                          # conv3x3_igemm_c8_kernel<3, 0, false, 4, 0>  [32 x 192 -> 96 @ 64 x 64 in MTUNetPlusPlus bf16]
+    (F_, 32, [320, 256], 320, 20, 16, dict(compute=1, c8=True, bias=False)),                                            # conv3x3_igemm_c8_kernel<2, 1, false, 4, 0>  [64 x 576 -> 320 @ 16 x 16 in MTnnUNet bf16]
+    (F_, 64, [24, 24, 24, 24], 24, 20, 512, dict(compute=1, c8=True, bias=False)),                                      # conv3x3_igemm_c8_kernel<2, 0, false, 8, 0>  [32 x 96 -> 24 @ 256 x 256 in MTUNetPlusPlus bf16]
+    (F_, 64, [24, 24], 24, 20, 512, dict(compute=1, c8=True, bias=False)),                                              # conv3x3_igemm_c8_kernel<2, 0, false, 8, 0>  [32 x 48 -> 24 @ 256 x 256 in MTUNetPlusPlus bf16]
+    (F_, 12, [128], 256, 20, 48, dict(compute=1, c8=True, out_c8=True, out_fp16=True, bias=False, stats=True)),         # conv3x3_igemm_c8_kernel<2, 0, false, 4, 3>  [64 x 128 -> 256 @ 32 x 32 in MTnnUNet bf16]
+    (F_, 2, [1], 32, 20, 48, dict(compute=1, c8=True, out_c8=True, out_fp16=True, bias=False, stats=True)),             # conv3x3_stem_fwd_c8_kernel<true>  [64 x 1 -> 32 @ 256 x 256 in MTnnUNet bf16]
+    (F_, 2, [320], 320, 8, 8, dict(compute=1, c8=True, out_c8=True, out_fp16=True, bias=False, stats=True)),            # conv3x3_igemm_c8_kernel<1, 2, false, 4, 3>  [64 x 320 -> 320 @ 8 x 8 in MTnnUNet bf16]
+    (F_, 2, [32], 16, 20, 48, dict(compute=1, c8=True, out_c8=True, out_fp16=True, bias=False, stats=True)),            # conv3x3_igemm_c8_kernel<1, 0, false, 4, 3>  [64 x 32 -> 16 @ 256 x 256 in MTnnUNet bf16]
+    (F_, 24, [256, 256], 128, 20, 48, dict(compute=1, c8=True, out_c8=True, out_fp16=True, bias=False, stats=True)),    # conv3x3_igemm_c8_kernel<2, 0, false, 4, 3>  [64 x 512 -> 128 @ 32 x 32 in MTnnUNet bf16]
+    (F_, 32, [256], 320, 20, 16, dict(compute=1, c8=True, out_c8=True, out_fp16=True, bias=False, stats=True)),         # conv3x3_igemm_c8_kernel<2, 1, false, 4, 3>  [64 x 256 -> 320 @ 16 x 16 in MTnnUNet bf16]
+    (F_, 32, [320, 320], 256, 20, 16, dict(compute=1, c8=True, out_c8=True, out_fp16=True, bias=False, stats=True)),    # conv3x3_igemm_c8_kernel<2, 1, false, 4, 3>  [64 x 640 -> 256 @ 16 x 16 in MTnnUNet bf16]
+    (F_, 64, [32], 32, 20, 512, dict(compute=1, c8=True, out_c8=True, out_fp16=True, bias=False, stats=True)),          # conv3x3_igemm_c8_kernel<2, 0, false, 8, 3>  [64 x 32 -> 32 @ 256 x 256 in MTnnUNet bf16]
+    (F_, 64, [64, 64], 32, 20, 512, dict(compute=1, c8=True, out_c8=True, out_fp16=True, bias=False, stats=True)),      # conv3x3_igemm_c8_kernel<2, 0, false, 8, 3>  [64 x 128 -> 32 @ 128 x 128 in MTnnUNet bf16]
+    (F_, 16, [384, 384, 384], 512, 20, 16, dict(compute=1, c8=True, out_c8=True, out_fp16=True, stats=True)),           # conv3x3_igemm_c8_kernel<2, 1, false, 4, 3>  [32 x 1152 -> 512 @ 16 x 16 in MTUNetPlusPlus bf16]
+    (F_, 16, [512], 512, 20, 16, dict(compute=1, c8=True, out_c8=True, out_fp16=True, stats=True)),                     # conv3x3_igemm_c8_kernel<2, 1, false, 4, 3>  [32 x 512 -> 512 @ 16 x 16 in MTUNetPlusPlus bf16]
+    (F_, 2, [192], 384, 16, 16, dict(compute=1, c8=True, out_c8=True, out_fp16=True, stats=True)),                      # conv3x3_igemm_c8_ring_kernel<3, 1, false, 3, 3>  [32 x 192 -> 384 @ 16 x 16 in MTUNetPlusPlus bf16]
+    (F_, 2, [1], 24, 20, 48, dict(compute=1, c8=True, out_c8=True, out_fp16=True, stats=True)),                         # conv3x3_stem_fwd_c8_kernel<true>  [32 x 1 -> 24 @ 256 x 256 in MTUNetPlusPlus bf16]
+    (F_, 32, [192], 384, 20, 16, dict(compute=1, c8=True, out_c8=True, out_fp16=True, stats=True)),                     # conv3x3_igemm_c8_kernel<3, 1, false, 4, 3>  [64 x 192 -> 384 @ 16 x 16 in MTUNetPlusPlus bf16]
+    (F_, 4, [24], 48, 512, 48, dict(compute=1, c8=True, out_c8=True, out_fp16=True, stats=True)),                       # conv3x3_igemm_c8_kernel<3, 0, false, 4, 3>  [32 x 24 -> 48 @ 128 x 128 in MTUNetPlusPlus bf16]
+    (F_, 4, [48, 48, 48], 48, 512, 48, dict(compute=1, c8=True, out_c8=True, out_fp16=True, stats=True)),               # conv3x3_igemm_c8_kernel<3, 0, false, 4, 3>  [32 x 144 -> 48 @ 128 x 128 in MTUNetPlusPlus bf16]
+    (F_, 4, [48, 48], 48, 512, 48, dict(compute=1, c8=True, out_c8=True, out_fp16=True, stats=True)),                   # conv3x3_igemm_c8_kernel<3, 0, false, 4, 3>  [32 x 96 -> 48 @ 128 x 128 in MTUNetPlusPlus bf16]
+    (F_, 48, [96, 96], 96, 20, 48, dict(compute=1, c8=True, out_c8=True, out_fp16=True, stats=True)),                   # conv3x3_igemm_c8_kernel<3, 0, false, 4, 3>  [32 x 192 -> 96 @ 64 x 64 in MTUNetPlusPlus bf16]
+    (F_, 48, [96], 96, 20, 48, dict(compute=1, c8=True, out_c8=True, out_fp16=True, stats=True)),                       # conv3x3_igemm_c8_kernel<3, 0, false, 4, 3>  [32 x 96 -> 96 @ 64 x 64 in MTUNetPlusPlus bf16]
+    (F_, 64, [24, 24, 48], 24, 20, 512, dict(compute=1, c8=True, out_c8=True, out_fp16=True, stats=True)),              # conv3x3_igemm_c8_kernel<2, 0, false, 8, 3>  [32 x 96 -> 24 @ 256 x 256 in MTUNetPlusPlus bf16]
+    (F_, 64, [24, 48], 24, 20, 512, dict(compute=1, c8=True, out_c8=True, out_fp16=True, stats=True)),                  # conv3x3_igemm_c8_kernel<2, 0, false, 8, 3>  [32 x 72 -> 24 @ 256 x 256 in MTUNetPlusPlus bf16]
+    (F_, 64, [24], 24, 20, 512, dict(compute=1, c8=True, out_c8=True, out_fp16=True, stats=True)),                      # conv3x3_igemm_c8_kernel<2, 0, false, 8, 3>  [32 x 24 -> 24 @ 256 x 256 in MTUNetPlusPlus bf16]
+    (F_, 4, [48, 48, 48], 48, 512, 48, dict(compute=2, c8=True, bias=False, out_accumulate=True)),                      # conv3x3_igemm_c8_kernel<3, 0, true, 4, 0>  [16 x 144 -> 48 @ 256 x 256 in MTUNetPlusPlus f16]
+    (F_, 4, [48, 48], 48, 512, 48, dict(compute=2, c8=True, bias=False, out_accumulate=True)),                          # conv3x3_igemm_c8_kernel<3, 0, true, 4, 0>  [16 x 96 -> 48 @ 256 x 256 in MTUNetPlusPlus f16]
+    (F_, 48, [96, 96], 96, 20, 48, dict(compute=2, c8=True, bias=False, out_accumulate=True)),                          # conv3x3_igemm_c8_kernel<3, 0, true, 4, 0>  [16 x 192 -> 96 @ 128 x 128 in MTUNetPlusPlus f16]
+    (F_, 64, [24, 24, 24, 24], 24, 20, 512, dict(compute=2, c8=True, bias=False)),                                      # conv3x3_igemm_c8_kernel<2, 0, true, 8, 0>  [16 x 96 -> 24 @ 512 x 512 in MTUNetPlusPlus f16]
+    (F_, 64, [24, 24], 24, 20, 512, dict(compute=2, c8=True, bias=False)),                                              # conv3x3_igemm_c8_kernel<2, 0, true, 8, 0>  [16 x 48 -> 24 @ 512 x 512 in MTUNetPlusPlus f16]
+    (F_, 4, [24], 48, 512, 48, dict(compute=2, c8=True, out_c8=True, stats=True)),                                      # conv3x3_igemm_c8_kernel<3, 0, true, 4, 1>  [16 x 24 -> 48 @ 256 x 256 in MTUNetPlusPlus f16]
+    (F_, 4, [48, 48, 48], 48, 512, 48, dict(compute=2, c8=True, out_c8=True, stats=True)),                              # conv3x3_igemm_c8_kernel<3, 0, true, 4, 1>  [16 x 144 -> 48 @ 256 x 256 in MTUNetPlusPlus f16]
+    (F_, 4, [48, 48], 48, 512, 48, dict(compute=2, c8=True, out_c8=True, stats=True)),                                  # conv3x3_igemm_c8_kernel<3, 0, true, 4, 1>  [16 x 96 -> 48 @ 256 x 256 in MTUNetPlusPlus f16]
+    (F_, 48, [96, 96], 96, 20, 48, dict(compute=2, c8=True, out_c8=True, stats=True)),                                  # conv3x3_igemm_c8_kernel<3, 0, true, 4, 1>  [16 x 192 -> 96 @ 128 x 128 in MTUNetPlusPlus f16]
+    (F_, 48, [96], 96, 20, 48, dict(compute=2, c8=True, out_c8=True, stats=True)),                                      # conv3x3_igemm_c8_kernel<3, 0, true, 4, 1>  [16 x 96 -> 96 @ 128 x 128 in MTUNetPlusPlus f16]
+    (F_, 6, [384, 384, 384], 512, 20, 48, dict(compute=2, c8=True, out_c8=True, stats=True)),                           # conv3x3_igemm_c8_kernel<2, 0, true, 4, 1>  [16 x 1152 -> 512 @ 32 x 32 in MTUNetPlusPlus f16]
+    (F_, 6, [512], 512, 20, 48, dict(compute=2, c8=True, out_c8=True, stats=True)),                                     # conv3x3_igemm_c8_kernel<2, 0, true, 4, 1>  [16 x 512 -> 512 @ 32 x 32 in MTUNetPlusPlus f16]
+    (F_, 64, [24, 24, 48], 24, 20, 512, dict(compute=2, c8=True, out_c8=True, stats=True)),                             # conv3x3_igemm_c8_kernel<2, 0, true, 8, 1>  [16 x 96 -> 24 @ 512 x 512 in MTUNetPlusPlus f16]
+    (F_, 64, [24, 48], 24, 20, 512, dict(compute=2, c8=True, out_c8=True, stats=True)),                                 # conv3x3_igemm_c8_kernel<2, 0, true, 8, 1>  [16 x 72 -> 24 @ 512 x 512 in MTUNetPlusPlus f16]
+    (F_, 64, [24], 24, 20, 512, dict(compute=2, c8=True, out_c8=True, stats=True)),                                     # conv3x3_igemm_c8_kernel<2, 0, true, 8, 1>  [16 x 24 -> 24 @ 512 x 512 in MTUNetPlusPlus f16]
+    (F_, 16, [512], 512, 20, 16, dict()),                                                                               # conv3x3_igemm_dma_kernel<2, 1, 2>  [32 x 512 -> 512 @ 16 x 16 in MTUNetPlusPlus f32]
+    (F_, 2, [192], 384, 16, 16, dict()),                                                                                # conv3x3_igemm_dma_kernel<1, 1, 2>  [32 x 192 -> 384 @ 16 x 16 in MTUNetPlusPlus f32]
+    (F_, 32, [192], 384, 20, 16, dict()),                                                                               # conv3x3_igemm_dma_kernel<3, 1, 2>  [64 x 192 -> 384 @ 16 x 16 in MTUNetPlusPlus f32]
+    (F_, 4, [24, 48], 24, 512, 48, dict()),                                                                             # conv3x3_igemm_dma_kernel<2, 0, 2>  [32 x 72 -> 24 @ 256 x 256 in MTUNetPlusPlus f32]
+    (F_, 4, [24], 48, 512, 48, dict()),                                                                                 # conv3x3_igemm_dma_kernel<3, 0, 2>  [32 x 24 -> 48 @ 128 x 128 in MTUNetPlusPlus f32]
+    (D_, 24, [48, 48, 48, 48], 48, 20, 48, dict(accumulate=[0, 0, 0, 0])),                                              # conv3x3_igemm_dma_kernel<3, 0, 2>  [32 x 192 -> 48 @ 128 x 128 in MTUNetPlusPlus f32]
+    (D_, 12, [384, 384, 384], 512, 20, 16, dict(accumulate=[0, 0, 0])),                                                 # conv3x3_igemm_dma_kernel<3, 1, 2>  [32 x 1152 -> 512 @ 16 x 16 in MTUNetPlusPlus f32]
+    (D_, 16, [512], 512, 20, 16, dict(accumulate=[0])),                                                                 # conv3x3_igemm_dma_kernel<2, 1, 2>  [32 x 512 -> 512 @ 16 x 16 in MTUNetPlusPlus f32]
+    (D_, 2, [192], 384, 16, 16, dict(accumulate=[0])),                                                                  # conv3x3_igemm_dma_kernel<1, 1, 2>  [64 x 192 -> 384 @ 16 x 16 in MTUNetPlusPlus f32]
+    (D_, 32, [384], 384, 20, 16, dict(accumulate=[0])),                                                                 # conv3x3_igemm_dma_kernel<3, 1, 2>  [64 x 384 -> 384 @ 16 x 16 in MTUNetPlusPlus f32]
+    (D_, 32, [48, 48, 48], 48, 20, 48, dict(accumulate=[1, 1, 0])),                                                     # conv3x3_igemm_dma_kernel<3, 0, 2>  [32 x 144 -> 48 @ 128 x 128 in MTUNetPlusPlus f32]
+    (D_, 32, [24, 24, 24, 48], 24, 20, 48, dict(accumulate=[1, 1, 1, 0])),                                              # conv3x3_igemm_dma_kernel<3, 0, 2>  [32 x 120 -> 24 @ 256 x 256 in MTUNetPlusPlus f32]
+    (D_, 2, [192], 384, 16, 16, dict(accumulate=[1])),                                                                  # conv3x3_igemm_dma_kernel<1, 1, 2>  [32 x 192 -> 384 @ 16 x 16 in MTUNetPlusPlus f32]
+    (D_, 12, [384, 384, 384], 512, 20, 16, dict(compute=1, c8=True, accumulate=[0, 0, 0])),                             # conv3x3_igemm_c8_kernel<3, 1, false, 4, 0>  [32 x 1152 -> 512 @ 16 x 16 in MTUNetPlusPlus bf16]
+    (D_, 16, [320, 320], 256, 20, 16, dict(compute=1, c8=True, accumulate=[0, 0])),                                     # conv3x3_igemm_c8_kernel<2, 1, false, 4, 0>  [64 x 640 -> 256 @ 16 x 16 in nnUNet bf16]
+    (D_, 24, [24, 48], 24, 20, 512, dict(compute=1, c8=True, accumulate=[0, 2])),                                       # conv3x3_igemm_c8_kernel<2, 0, false, 8, 0>  [32 x 72 -> 24 @ 256 x 256 in MTUNetPlusPlus bf16]
+    (D_, 24, [96, 96], 96, 20, 48, dict(compute=1, c8=True, accumulate=[0, 2])),                                        # conv3x3_igemm_c8_kernel<3, 0, false, 4, 0>  [32 x 192 -> 96 @ 64 x 64 in MTUNetPlusPlus bf16]
+    (D_, 32, [32, 32], 32, 20, 512, dict(compute=1, c8=True, accumulate=[0, 2])),                                       # conv3x3_igemm_c8_kernel<2, 0, false, 8, 0>  [64 x 64 -> 32 @ 256 x 256 in MTnnUNet bf16]
+    (D_, 48, [48, 48], 48, 20, 48, dict(compute=1, c8=True, accumulate=[0, 2])),                                        # conv3x3_igemm_c8_kernel<3, 0, false, 4, 0>  [32 x 96 -> 48 @ 128 x 128 in MTUNetPlusPlus bf16]
+    (D_, 16, [512], 512, 20, 16, dict(compute=1, c8=True, accumulate=[0])),                                             # conv3x3_igemm_c8_kernel<2, 1, false, 4, 0>  [32 x 512 -> 512 @ 16 x 16 in MTUNetPlusPlus bf16]
+    (D_, 2, [320], 320, 8, 8, dict(compute=1, c8=True, accumulate=[0])),                                                # conv3x3_igemm_c8_kernel<1, 2, false, 4, 0>  [64 x 320 -> 320 @ 8 x 8 in MTnnUNet bf16]
+    (D_, 32, [384], 384, 20, 16, dict(compute=1, c8=True, accumulate=[0])),                                             # conv3x3_igemm_c8_kernel<3, 1, false, 4, 0>  [64 x 384 -> 384 @ 16 x 16 in MTUNetPlusPlus bf16]
+    (D_, 4, [24], 48, 512, 48, dict(compute=1, c8=True, accumulate=[0])),                                               # conv3x3_igemm_c8_kernel<2, 0, false, 4, 0>  [32 x 24 -> 48 @ 128 x 128 in MTUNetPlusPlus bf16]
+    (D_, 48, [64], 64, 20, 48, dict(compute=1, c8=True, accumulate=[0])),                                               # conv3x3_igemm_c8_kernel<2, 0, false, 4, 0>  [64 x 64 -> 64 @ 64 x 64 in MTnnUNet bf16]
+    (D_, 64, [32], 16, 20, 512, dict(compute=1, c8=True, accumulate=[0])),                                              # conv3x3_igemm_c8_kernel<2, 0, false, 8, 0>  [64 x 32 -> 16 @ 256 x 256 in MTnnUNet bf16]
+    (D_, 64, [32], 32, 20, 512, dict(compute=1, c8=True, accumulate=[0])),                                              # conv3x3_igemm_c8_kernel<2, 0, false, 8, 0>  [64 x 32 -> 32 @ 128 x 128 in MTnnUNet bf16]
+    (D_, 2, [192], 384, 16, 16, dict(compute=1, c8=True, accumulate=[1])),                                              # conv3x3_igemm_c8_ring_kernel<3, 1, false, 0, 3>  [32 x 192 -> 384 @ 16 x 16 in MTUNetPlusPlus bf16]
+    (D_, 32, [320], 256, 20, 16, dict(compute=1, c8=True, accumulate=[1])),                                             # conv3x3_igemm_c8_kernel<2, 1, false, 4, 0>  [64 x 320 -> 256 @ 16 x 16 in MTnnUNet bf16]
+    (D_, 4, [48], 24, 512, 48, dict(compute=1, c8=True, accumulate=[2])),                                               # conv3x3_igemm_c8_kernel<3, 0, false, 4, 0>  [32 x 48 -> 24 @ 256 x 256 in MTUNetPlusPlus bf16]
+    (D_, 48, [96], 96, 20, 48, dict(compute=1, c8=True, accumulate=[2])),                                               # conv3x3_igemm_c8_kernel<3, 0, false, 4, 0>  [32 x 96 -> 96 @ 64 x 64 in MTUNetPlusPlus bf16]
+    (D_, 4, [384, 384, 384], 512, 20, 48, dict(compute=2, c8=True, accumulate=[0, 0, 0])),                              # conv3x3_igemm_c8_kernel<3, 0, true, 4, 0>  [16 x 1152 -> 512 @ 32 x 32 in MTUNetPlusPlus f16]
+    (D_, 24, [24, 48], 24, 20, 512, dict(compute=2, c8=True, accumulate=[0, 2])),                                       # conv3x3_igemm_c8_kernel<2, 0, true, 8, 0>  [16 x 72 -> 24 @ 512 x 512 in MTUNetPlusPlus f16]
+    (D_, 24, [96, 96], 96, 20, 48, dict(compute=2, c8=True, accumulate=[0, 2])),                                        # conv3x3_igemm_c8_kernel<3, 0, true, 4, 0>  [16 x 192 -> 96 @ 128 x 128 in MTUNetPlusPlus f16]
+    (D_, 48, [48, 48], 48, 20, 48, dict(compute=2, c8=True, accumulate=[0, 2])),                                        # conv3x3_igemm_c8_kernel<3, 0, true, 4, 0>  [16 x 96 -> 48 @ 256 x 256 in MTUNetPlusPlus f16]
+    (D_, 12, [384], 384, 20, 48, dict(compute=2, c8=True, accumulate=[0])),                                             # conv3x3_igemm_c8_kernel<3, 0, true, 4, 0>  [32 x 384 -> 384 @ 32 x 32 in MTUNetPlusPlus f16]
+    (D_, 4, [48], 48, 512, 48, dict(compute=2, c8=True, accumulate=[0])),                                               # conv3x3_igemm_c8_kernel<3, 0, true, 4, 0>  [16 x 48 -> 48 @ 256 x 256 in MTUNetPlusPlus f16]
+    (D_, 6, [512], 512, 20, 48, dict(compute=2, c8=True, accumulate=[0])),                                              # conv3x3_igemm_c8_kernel<2, 0, true, 4, 0>  [16 x 512 -> 512 @ 32 x 32 in MTUNetPlusPlus f16]
+    (D_, 2, [192], 384, 20, 32, dict(compute=2, c8=True, accumulate=[1])),                                              # conv3x3_igemm_c8_ring_kernel<3, 0, true, 0, 3>  [16 x 192 -> 384 @ 32 x 32 in MTUNetPlusPlus f16]
+    (D_, 4, [48], 24, 512, 48, dict(compute=2, c8=True, accumulate=[2])),                                               # conv3x3_igemm_c8_kernel<3, 0, true, 4, 0>  [16 x 48 -> 24 @ 512 x 512 in MTUNetPlusPlus f16]
+    (D_, 48, [96], 96, 20, 48, dict(compute=2, c8=True, accumulate=[2])),                                               # conv3x3_igemm_c8_kernel<3, 0, true, 4, 0>  [16 x 96 -> 96 @ 128 x 128 in MTUNetPlusPlus f16]
+    (W_, 3, [1], 24, 20, 48, dict(bias=False)),                                                                         # conv3x3_wgrad_smallcin_kernel + splitk_reduce  [32 x 1 -> 24 @ 256 x 256 in MTUNetPlusPlus f32]
+    (W_, 3, [24, 24, 24, 24, 48], 24, 20, 48, dict(bias=False)),                                                        # conv3x3_wgrad_mfma_kernel<0, 2, true> + splitk_reduce  [32 x 144 -> 24 @ 256 x 256 in MTUNetPlusPlus f32]
+    (W_, 3, [24, 24, 48], 24, 20, 48, dict(bias=False)),                                                                # conv3x3_wgrad_mfma_kernel<0, 2, false> + splitk_reduce  [32 x 96 -> 24 @ 256 x 256 in MTUNetPlusPlus f32]
+    (W_, 3, [24], 24, 20, 48, dict(bias=False)),                                                                        # conv3x3_wgrad_mfma_kernel<0, 2, true> + splitk_reduce  [32 x 24 -> 24 @ 256 x 256 in MTUNetPlusPlus f32]
+    (W_, 3, [384, 384, 384], 512, 16, 16, dict(bias=False)),                                                            # conv3x3_wgrad_mfma_kernel<1, 2, false> + splitk_reduce  [32 x 1152 -> 512 @ 16 x 16 in MTUNetPlusPlus f32]
+    (W_, 3, [48, 48, 48, 48], 48, 20, 48, dict(bias=False)),                                                            # conv3x3_wgrad_mfma_kernel<0, 3, false> + splitk_reduce  [32 x 192 -> 48 @ 128 x 128 in MTUNetPlusPlus f32]
+    (W_, 3, [48, 48, 48], 48, 20, 48, dict(bias=False)),                                                                # conv3x3_wgrad_mfma_kernel<0, 3, true> + splitk_reduce  [32 x 144 -> 48 @ 128 x 128 in MTUNetPlusPlus f32]
+    (W_, 3, [48], 48, 20, 48, dict(bias=False)),                                                                        # conv3x3_wgrad_mfma_kernel<0, 3, true> + splitk_reduce  [32 x 48 -> 48 @ 128 x 128 in MTUNetPlusPlus f32]
+    (W_, 3, [48], 96, 20, 48, dict(bias=False)),                                                                        # conv3x3_wgrad_mfma_kernel<0, 2, true> + splitk_reduce  [32 x 48 -> 96 @ 64 x 64 in MTUNetPlusPlus f32]
+    (W_, 3, [512], 512, 16, 16, dict(bias=False)),                                                                      # conv3x3_wgrad_mfma_kernel<1, 2, false> + splitk_reduce  [32 x 512 -> 512 @ 16 x 16 in MTUNetPlusPlus f32]
+    (W_, 3, [96, 96, 96], 96, 20, 48, dict(bias=False)),                                                                # conv3x3_wgrad_mfma_kernel<0, 2, false> + splitk_reduce  [32 x 288 -> 96 @ 64 x 64 in MTUNetPlusPlus f32]
+    (W_, 3, [96], 96, 20, 48, dict(bias=False)),                                                                        # conv3x3_wgrad_mfma_kernel<0, 2, false> + splitk_reduce  [32 x 96 -> 96 @ 64 x 64 in MTUNetPlusPlus f32]
+    (W_, 3, [1], 24, 20, 48, dict(compute=1, c8=True, bias=False)),                                                     # conv3x3_wgrad_stem_c8_kernel<false> + splitk_reduce  [32 x 1 -> 24 @ 256 x 256 in MTUNetPlusPlus bf16]
+    (W_, 3, [1], 32, 20, 48, dict(compute=1, c8=True, bias=False)),                                                     # conv3x3_wgrad_stem_c8_kernel<false> + splitk_reduce  [64 x 1 -> 32 @ 256 x 256 in MTnnUNet bf16]
+    (W_, 3, [24, 24, 24, 24, 48], 24, 20, 128, dict(compute=1, c8=True, bias=False)),                                   # conv3x3_wgrad_c8w_kernel<false, 2, false> + splitk_reduce  [32 x 144 -> 24 @ 256 x 256 in MTUNetPlusPlus bf16]
+    (W_, 3, [24, 24, 48], 24, 20, 128, dict(compute=1, c8=True, bias=False)),                                           # conv3x3_wgrad_c8w_kernel<false, 2, false> + splitk_reduce  [32 x 96 -> 24 @ 256 x 256 in MTUNetPlusPlus bf16]
+    (W_, 3, [24], 24, 20, 48, dict(compute=1, c8=True, bias=False)),                                                    # conv3x3_wgrad_c8_kernel<false, 0> + splitk_reduce  [32 x 24 -> 24 @ 256 x 256 in MTUNetPlusPlus bf16]
+    (W_, 3, [32, 32], 32, 20, 128, dict(compute=1, c8=True, bias=False)),                                               # conv3x3_wgrad_c8w_kernel<false, 2, false> + splitk_reduce  [64 x 64 -> 32 @ 256 x 256 in MTnnUNet bf16]
+    (W_, 3, [320, 320], 256, 16, 16, dict(compute=1, c8=True, bias=False)),                                             # conv3x3_wgrad_c8i_kernel<false, 2, false> + splitk_reduce  [64 x 640 -> 256 @ 16 x 16 in MTnnUNet bf16]
+    (W_, 3, [320], 320, 8, 8, dict(compute=1, c8=True, bias=False)),                                                    # conv3x3_wgrad_c8_kernel<false, 1> + splitk_reduce  [64 x 320 -> 320 @ 8 x 8 in MTnnUNet bf16]
+    (W_, 3, [384, 384, 384], 512, 16, 16, dict(compute=1, c8=True, bias=False)),                                        # conv3x3_wgrad_c8i_kernel<false, 2, false>  [32 x 1152 -> 512 @ 16 x 16 in MTUNetPlusPlus bf16]
+    (W_, 3, [384], 384, 16, 16, dict(compute=1, c8=True, bias=False)),                                                  # conv3x3_wgrad_c8i_kernel<false, 3, false> + splitk_reduce  [64 x 384 -> 384 @ 16 x 16 in MTUNetPlusPlus bf16]
+    (W_, 3, [48, 48, 48, 48], 48, 20, 128, dict(compute=1, c8=True, bias=False)),                                       # conv3x3_wgrad_c8w_kernel<false, 3, false> + splitk_reduce  [32 x 192 -> 48 @ 128 x 128 in MTUNetPlusPlus bf16]
+    (W_, 3, [48, 48, 48], 48, 20, 128, dict(compute=1, c8=True, bias=False)),                                           # conv3x3_wgrad_c8w_kernel<false, 3, false> + splitk_reduce  [32 x 144 -> 48 @ 128 x 128 in MTUNetPlusPlus bf16]
+    (W_, 3, [48], 48, 20, 48, dict(compute=1, c8=True, bias=False)),                                                    # conv3x3_wgrad_c8_kernel<false, 0> + splitk_reduce  [32 x 48 -> 48 @ 128 x 128 in MTUNetPlusPlus bf16]
+    (W_, 3, [512], 512, 16, 16, dict(compute=1, c8=True, bias=False)),                                                  # conv3x3_wgrad_c8i_kernel<false, 2, false> + splitk_reduce  [32 x 512 -> 512 @ 16 x 16 in MTUNetPlusPlus bf16]
+    (W_, 3, [64], 64, 20, 128, dict(compute=1, c8=True, bias=False)),                                                   # conv3x3_wgrad_c8w_kernel<false, 2, false> + splitk_reduce  [64 x 64 -> 64 @ 128 x 128 in MTnnUNet bf16]
+    (W_, 3, [96, 96, 96], 96, 20, 48, dict(compute=1, c8=True, bias=False)),                                            # conv3x3_wgrad_c8_kernel<false, 0> + splitk_reduce  [32 x 288 -> 96 @ 64 x 64 in MTUNetPlusPlus bf16]
+    (W_, 3, [96], 96, 20, 48, dict(compute=1, c8=True, bias=False)),                                                    # conv3x3_wgrad_c8_kernel<false, 0> + splitk_reduce  [32 x 96 -> 96 @ 64 x 64 in MTUNetPlusPlus bf16]
+    (W_, 3, [192, 192], 192, 20, 48, dict(compute=2, c8=True, bias=False)),                                             # conv3x3_wgrad_c8_kernel<true, 0> + splitk_reduce  [16 x 384 -> 192 @ 64 x 64 in MTUNetPlusPlus f16]
+    (W_, 3, [1], 24, 20, 48, dict(compute=2, c8=True, bias=False)),                                                     # conv3x3_wgrad_stem_c8_kernel<true> + splitk_reduce  [16 x 1 -> 24 @ 512 x 512 in MTUNetPlusPlus f16]
+    (W_, 3, [24, 24, 24, 24, 48], 24, 20, 128, dict(compute=2, c8=True, bias=False)),                                   # conv3x3_wgrad_c8w_kernel<true, 2, false> + splitk_reduce  [16 x 144 -> 24 @ 512 x 512 in MTUNetPlusPlus f16]
+    (W_, 3, [24, 24, 48], 24, 20, 128, dict(compute=2, c8=True, bias=False)),                                           # conv3x3_wgrad_c8w_kernel<true, 2, false> + splitk_reduce  [16 x 96 -> 24 @ 512 x 512 in MTUNetPlusPlus f16]
+    (W_, 3, [24], 24, 20, 48, dict(compute=2, c8=True, bias=False)),                                                    # conv3x3_wgrad_c8_kernel<true, 0> + splitk_reduce  [16 x 24 -> 24 @ 512 x 512 in MTUNetPlusPlus f16]
+    (W_, 3, [384, 384, 384], 512, 20, 32, dict(compute=2, c8=True, bias=False)),                                        # conv3x3_wgrad_c8_kernel<true, 0>  [16 x 1152 -> 512 @ 32 x 32 in MTUNetPlusPlus f16]
+    (W_, 3, [48, 48, 48, 48], 48, 20, 128, dict(compute=2, c8=True, bias=False)),                                       # conv3x3_wgrad_c8w_kernel<true, 3, false> + splitk_reduce  [16 x 192 -> 48 @ 256 x 256 in MTUNetPlusPlus f16]
+    (W_, 3, [48, 48, 48], 48, 20, 128, dict(compute=2, c8=True, bias=False)),                                           # conv3x3_wgrad_c8w_kernel<true, 3, false> + splitk_reduce  [16 x 144 -> 48 @ 256 x 256 in MTUNetPlusPlus f16]
+    (W_, 3, [48], 48, 20, 48, dict(compute=2, c8=True, bias=False)),                                                    # conv3x3_wgrad_c8_kernel<true, 0> + splitk_reduce  [16 x 48 -> 48 @ 256 x 256 in MTUNetPlusPlus f16]
+    (W_, 3, [512], 512, 20, 32, dict(compute=2, c8=True, bias=False)),                                                  # conv3x3_wgrad_c8_kernel<true, 0> + splitk_reduce  [16 x 512 -> 512 @ 32 x 32 in MTUNetPlusPlus f16]
+    (W_, 3, [96, 96, 96], 96, 20, 128, dict(compute=2, c8=True, bias=False)),                                           # conv3x3_wgrad_c8w_kernel<true, 3, false> + splitk_reduce  [16 x 288 -> 96 @ 128 x 128 in MTUNetPlusPlus f16]
+    (W_, 3, [96], 96, 20, 128, dict(compute=2, c8=True, bias=False)),                                                   # conv3x3_wgrad_c8w_kernel<true, 3, false> + splitk_reduce  [16 x 96 -> 96 @ 128 x 128 in MTUNetPlusPlus f16]
+]
+
+
+def _conv3_case_id(case):
+    op, N, segs, Cout, H, W, mode = case
+    flags = "-".join(k if v is True else f"{k}{v}".replace(" ", "") for k, v in mode.items() if v is not False and k not in ("c8", "compute"))
+    return f"{ {F_: 'fwd', D_: 'dgrad', W_: 'wgrad'}[op]}-{('f32', 'bf16', 'f16')[mode.get('compute', 0)]}-{N}x{'+'.join(map(str, segs))}-{Cout}@{H}x{W}" \
+        + (f"-{flags}" if flags else "") + ("-nobias" if mode.get("bias") is False and op == F_ else "")
+
+
+_NAN16 = 0x7fff          # a NaN in bf16 and in fp16: what a 16-bit destination holds before the launch
+
+
+@pytest.mark.parametrize("case", CONV3_STEP_CASES, ids=_conv3_case_id)
+def test_conv3x3_step_instances_match_fp64(case):
+    """One launch through ops.conv3x3_launch with the struct of conv3x3_case_args(ptrs=...), which must be the launch the row's dummy-pointer
+    struct plans, against a plain fp64 computation on the CPU on the operands the kernel reads: rounded RNE to the 16-bit type where it reads
+    16-bit values (channel-blocked operands, the 16-bit weight images), fp32 otherwise (the fp32 mode; the stem's image and weights).
+      forward / gathered dgrad   F.conv2d (+ bias, + the prefill with out_accumulate) on _ref_images, every other image finite; fp32 planes within
+                                 1e-5 x the output scale, 16-bit stored outputs within one ulp of the stored type + 1e-5 x scale
+                                 (test_conv3x3_bench_instances_match_fp64)
+      statistics                 summed over the slots against fp64 sum / sum of squares of the stored output read back, no NaN slot left; the
+                                 bounds of test_instnorm_statistics_from_the_conv_epilogue
+      dgrad                      conv2d_input; code 0 overwrites (NaN before), code 1 adds to a random prefill: 1e-5 x scale; code 2 (16-bit
+                                 planes) and code 3 (channel-blocked): one ulp of the type + 1e-5 x scale
+      weight gradient            conv2d_weight over the WHOLE batch, _close(dw, ref, 1e-5, 2e-5 * max(1, |ref|max)) (test_conv3x3_c8_operands),
+                                 with accumulate_dw on the sum with a random prefill; without dbias the buffer offered to nobody keeps its marker;
+                                 a name without a reduction = the direct store: the workspace keeps its pre-fill; run twice, bit-identical."""
+    op, N, segs, Cout, H, W, mode = case
+    # the norm-backward epilogue of a gathered dgrad (norm_z, out_partial) and the in-kernel split-K reduction: no step program launches them
+    # (profiles/conv3x3_step_keys.txt); test_gathered_dgrad_prepares_the_instnorm_backward and FIXUP_CASES hold their checks
+    assert not set(mode) & {"norm", "out_partial", "in_kernel_reduce", "dx_c8", "packed"}, mode
+    lib, dev = ops.L.load(), torch.device(DEV)
+    compute, c8 = mode.get("compute", 0), mode.get("c8", False)
+    Cin, HW = sum(segs), H * W
+    stem = len(segs) == 1 and segs[0] <= ops.L.STEM_MAX_CIN
+    g = torch.Generator(device=dev).manual_seed(CONV3_STEP_CASES.index(case) * 7919 + N * 31 + Cout + H)
+    rand = lambda *shape: torch.randn(*shape, generator=g, device=dev)                                        # noqa: E731
+    rnd = lambda t: _round16(t, compute)                                                                       # noqa: E731
+    dummy = ops.conv3x3_case_args(op, N, segs, Cout, H, W, **mode)
+    planned = [(op, ops.conv3x3_kernel_name(dummy, op))]
+    idx = _ref_images(N, H, W)
+    w = rand(Cout, Cin, 3, 3) * (2.0 / (9 * Cin)) ** 0.5
+    ptrs = {"w": w}
+
+    def launch(p):
+        ops.launched = []
+        try:
+            ops.conv3x3_launch(ops.conv3x3_case_args(op, N, segs, Cout, H, W, ptrs=p, **mode), op)
+            torch.cuda.synchronize()
+            assert ops.launched == planned, (ops.launched, planned)
+        finally:
+            ops.launched = None
+
+    def check16(what, got16, shape, st, want, scale, blocked):
+        """A 16-bit stored tensor (channel-blocked or planes, int16 storage of type st): finite everywhere, the images idx against `want`."""
+        got = _planes_of(got16.cpu(), shape, st) if blocked else _from16(got16.cpu(), st)
+        assert bool(torch.isfinite(got).all()), f"{what}: non-finite or unwritten value"
+        worst = ((got[idx] - want).abs() / (_ulp16(want, st) + 1e-5 * scale)).max().item()
+        print(f"{what}: {worst:.3f} x (one ulp of the stored type + 1e-5 x scale)")
+        assert worst <= 1.0, f"{what} ({planned[0][1]}): {worst:.3f} x (one ulp of the stored type + 1e-5 x scale)"
+        return got
+
+    def check32(what, got, want, scale):
+        got = got.cpu()
+        assert bool(torch.isfinite(got).all()), f"{what}: non-finite or unwritten value"
+        err = (got[idx].double() - want).abs().max().item()
+        print(f"{what}: max err {err:.3e} vs scale {scale:.3e}")
+        assert err <= 1e-5 * scale, f"{what} ({planned[0][1]}): max err {err:.3e} vs scale {scale:.3e}"
+
+    if op == F_:
+        xs = [rand(N, c, H, W) for c in segs]
+        b = rand(Cout) if mode.get("bias", True) else None
+        sixteen = c8 and not stem               # the MFMA reads 16-bit values; the stem computes in fp32 on the fp32 image and weights
+        ptrs.update({"in": [_c8_of(x, compute) for x in xs] if sixteen else xs, "bias": b})
+        if not stem:
+            ptrs["w_packed"] = ops.conv3x3_pack_lp(w, compute)[0] if compute else ops.conv3x3_pack(w)[0]
+        out_c8, st = mode.get("out_c8", False), (2 if mode.get("out_fp16") else compute)
+        pre = rand(N, Cout, H, W) if mode.get("out_accumulate") else None
+        if out_c8:
+            out = torch.full((N, Cout // 8, HW, 8), _NAN16, dtype=torch.int16, device=dev)
+        else:
+            out = pre.clone() if pre is not None else torch.full((N, Cout, H, W), float("nan"), device=dev)
+        ptrs["out"] = out
+        if mode.get("stats"):
+            slots = lib.mtbc_conv3x3_stats_slots(C.byref(dummy))
+            assert slots > 0, "no epilogue statistics for this launch"
+            ptrs["stats_partial"] = torch.full((N, slots, Cout, 2), float("nan"), device=dev)
+        launch(ptrs)
+        xr = torch.cat([x[idx] for x in xs], 1).cpu()
+        xr, wr = (rnd(xr), rnd(w.cpu())) if sixteen else (xr, w.cpu())
+        ref = F.conv2d(xr.double(), wr.double(), None if b is None else b.cpu().double(), padding=1)
+        scale = ref.abs().max().item()
+        if pre is not None:
+            ref = ref + pre[idx].cpu().double()
+            scale = max(scale, ref.abs().max().item())
+        if out_c8:
+            stored = check16("stored fwd", out, (N, Cout, H, W), st, ref, scale, True)
+        else:
+            check32("fwd", out, ref, scale)
+        if mode.get("stats"):
+            part = ptrs["stats_partial"].cpu()
+            assert not torch.isnan(part).any(), "a (image, subset, channel) entry was not written"
+            tot = part.double().sum(1)                                                            # (N, Cout, 2)
+            s_ref, q_ref = stored.sum((2, 3)), (stored * stored).sum((2, 3))
+            print(f"statistics: sum err {(tot[..., 0] - s_ref).abs().max().item():.3e}, sum of squares err {(tot[..., 1] - q_ref).abs().max().item():.3e}")
+            assert torch.allclose(tot[..., 0], s_ref, rtol=1e-5, atol=1e-5 * q_ref.abs().max().item() ** 0.5 * H * W ** 0.5), "statistics: sum"
+            assert torch.allclose(tot[..., 1], q_ref, rtol=1e-5, atol=1e-3), "statistics: sum of squares"
+    elif op == D_:
+        codes = mode["accumulate"]
+        dz = rand(N, Cout, H, W)
+        ptrs.update({"dout": _c8_of(dz, compute) if c8 else dz, "w_packed": ops.conv3x3_pack_lp(w, compute)[1] if compute else ops.conv3x3_pack(w)[1]})
+        pre, dxs = [], []
+        for c, code in zip(segs, codes):
+            pre.append(rand(N, c, H, W) if code == 1 else None)
+            if code >= 2:
+                dxs.append(torch.full((N, c // 8, HW, 8) if code == 3 else (N, c, H, W), _NAN16, dtype=torch.int16, device=dev))
+            else:
+                dxs.append(pre[-1].clone() if code == 1 else torch.full((N, c, H, W), float("nan"), device=dev))
+        ptrs["in"] = dxs
+        launch(ptrs)
+        dzr, wr = dz[idx].cpu(), w.cpu()
+        dzr, wr = (rnd(dzr), rnd(wr)) if compute else (dzr, wr)
+        ref = torch.nn.grad.conv2d_input((len(idx), Cin, H, W), wr.double(), dzr.double(), padding=1)
+        ds = ref.abs().max().item()
+        for i, (want, code) in enumerate(zip(torch.split(ref, segs, dim=1), codes)):
+            if code >= 2:
+                check16(f"dgrad seg {i} (code {code})", dxs[i], (N, segs[i], H, W), compute, want, ds, code == 3)
+            else:
+                want = want + (pre[i][idx].cpu().double() if code == 1 else 0)
+                check32(f"dgrad seg {i} (code {code})", dxs[i], want, max(ds, want.abs().max().item()))
+    else:
+        xs, dz = [rand(N, c, H, W) for c in segs], rand(N, Cout, H, W)
+        acc, want_bias = mode.get("accumulate_dw", False), mode.get("bias", True)
+        pre = rand(Cout, Cin, 3, 3) if acc else torch.full((Cout, Cin, 3, 3), float("nan"), device=dev)
+        db_pre = rand(Cout) if acc else torch.full((Cout,), float("nan"), device=dev)
+        ws_mark = torch.full((dummy.workspace_bytes // 4 + 64,), 1993.0, device=dev)
+        idle = torch.full((Cout,), 1993.0, device=dev)              # the dbias buffer of a launch without dbias: handed to nobody
+        ptrs.update({"in": xs if (stem or not c8) else [_c8_of(x, compute) for x in xs], "dout": _c8_of(dz, compute) if c8 else dz})
+        runs = []
+        for _ in range(2):
+            dw, ws = pre.clone(), ws_mark.clone()
+            db = db_pre.clone() if want_bias else None
+            ptrs.update({"dw": dw, "dbias": db, "workspace": ws, "wgrad_sync": ops.wgrad_sync_buffer(dev, dummy.wgrad_sync_bytes)})
+            launch(ptrs)
+            runs.append((dw, db, ws))
+        dw, db, ws = runs[0]
+        assert torch.equal(dw, runs[1][0]) and (db is None or torch.equal(db, runs[1][1])), "not deterministic"
+        assert torch.equal(idle, torch.full_like(idle, 1993.0))
+        if " + " not in planned[0][1]:              # the direct store: nothing was staged through the workspace
+            assert torch.equal(ws, ws_mark), "direct store: the workspace was written"
+        xr, dzr = torch.cat(xs, 1).cpu(), dz.cpu()
+        xr = rnd(xr) if compute and not stem else xr
+        dzr = rnd(dzr) if compute else dzr
+        ref = torch.nn.grad.conv2d_weight(xr.double(), (Cout, Cin, 3, 3), dzr.double(), padding=1)
+        dbr = dzr.double().sum((0, 2, 3))
+        if acc:
+            ref, dbr = ref + pre.cpu().double(), dbr + db_pre.cpu().double()
+        print(f"wgrad: max err {(dw.cpu().double() - ref).abs().max().item():.3e} vs scale {ref.abs().max().item():.3e}")
+        _close(dw, ref.float(), 1e-5, 2e-5 * max(1.0, ref.abs().max().item()), f"wgrad ({planned[0][1]})")
+        if want_bias:
+            _close(db, dbr.float(), 1e-5, 2e-5 * max(1.0, dbr.abs().max().item()), "dbias")
+
+
+def _reference_tested_conv3x3_keys():
+    """The (op, _conv3_key) of every conv3x3 call that a test of this file checks element by element against fp64, from the tests' own case
+    tables through dummy-pointer structs (ops.conv3x3_case_args).  Tests that compare two kernels with each other, or a kernel with an fp32
+    reference, do not count: test_conv3x3_mfma_fwd_dgrad_wgrad, the forward / dgrad half of test_conv3x3_c8_operands,
+    test_stem_conv_on_the_16bit_path, test_bf16_mode_conv_output_stored_as_fp16, test_instnorm_statistics_from_the_conv_epilogue."""
+    calls = [(op, (N, segs, Cout, H, W), mode) for op, N, segs, Cout, H, W, mode in CONV3_STEP_CASES]      # test_conv3x3_step_instances_match_fp64
+    for case in BENCH_CASES:                                     # test_conv3x3_bench_instances_match_fp64
         calls += [(op, case[:5], kw) for op, kw in _bench_case_calls(*case)]
-    for case in CONV_CASES:                                      # test_conv3x3_mfma_fwd_dgrad_wgrad (fp32)
-        calls += [(F_, case, {}), (D_, case, {}), (W_, case, {}), (W_, case, dict(bias=False))]
     for compute in (1, 2):
         m = dict(compute=compute, c8=True)
-        for case in C8_CASES:                                    # test_conv3x3_c8_operands
-            calls += [(F_, case, m), (D_, case, m), (W_, case, dict(m, in_kernel_reduce=True)), (W_, case, dict(m, bias=False, in_kernel_reduce=True))]
+        fix, nobias = dict(m, in_kernel_reduce=True), dict(m, in_kernel_reduce=True, bias=False)
+        for case in C8_CASES:                                    # test_conv3x3_c8_operands: the weight gradients
+            calls += [(W_, case, fix), (W_, case, dict(nobias, accumulate_dw=True))]
         for case in C8_CASES + EXTRA16_CASES:                    # test_conv3x3_16bit_fwd_dgrad_match_fp64_on_rounded_operands
             calls += [(F_, case, m), (D_, case, m), (F_, case, dict(compute=compute)), (D_, case, dict(compute=compute))]
         for case in C8W_CASES + C8I_CASES:                       # test_conv3x3_wgrad_c8_wide_blocks
-            calls += [(W_, case, dict(m, in_kernel_reduce=True)), (W_, case, dict(m, bias=False, in_kernel_reduce=True))]
+            calls += [(W_, case, fix), (W_, case, nobias), (W_, case, dict(nobias, accumulate_dw=True))]
         for case in FIXUP_CASES:                                 # test_conv3x3_wgrad_c8_in_kernel_split_k_reduction
-            calls += [(W_, case, dict(m, in_kernel_reduce=r)) for r in (True, False)]
-        for N, Cout, H, W in STEM16_CASES:                       # test_stem_conv_on_the_16bit_path
-            for out_fp16 in ((True, False) if compute == 1 else (False,)):
-                calls.append((F_, (N, [1], Cout, H, W), dict(m, out_c8=True, out_fp16=out_fp16, bias=True)))
-            calls.append((W_, (N, [1], Cout, H, W), dict(m, bias=False, in_kernel_reduce=True)))
-    for case in BF16_OUT_FP16_CASES:
-        calls.append((F_, case, dict(compute=1, c8=True, out_c8=True, out_fp16=True)))      # test_bf16_mode_conv_output_stored_as_fp16
-    return {ops.conv3x3_case_kernel(op, *case, **kw).split(" + ")[0] for op, case, kw in calls}
+            calls += [(W_, case, fix), (W_, case, m), (W_, case, nobias), (W_, case, dict(nobias, accumulate_dw=True))]
+    return {(op, _conv3_key(ops.conv3x3_case_args(op, *case, **kw), op)) for op, case, kw in calls}
 
 
 def test_step_programs_launch_only_reference_tested_conv3x3_instances():
-    """Surveys (builds, does not run) the step programs of the benchmark's configurations and asks mtbc_conv3x3_kernel_name for the instance
-    of every 3x3 conv launch: each must be one an element-wise reference test of this file launches.  A new dispatch path that no reference
-    test reaches fails here."""
-    assert_all_tested("conv3x3", _reference_tested_instances(), [survey(p) for p in STEP_PROGRAMS])
+    """Surveys (builds, does not run) the step programs of the benchmark's configurations and keys every 3x3 conv launch by
+    tests/step_programs.py _conv3_key -- the launches mtbc_conv3x3_kernel_name plans, reduction included, and the branches the arguments
+    select: each must be the key of a call that a test of this file checks against fp64.  A new dispatch path or a new combination of
+    arguments that no such test makes fails here, named with its program and shape (profiles/conv3x3_step_keys.txt: the listing)."""
+    L = ops.L
+    assert_all_tested("conv3x3", _reference_tested_conv3x3_keys(), [survey(p) for p in STEP_PROGRAMS] + [survey(STEP_PROGRAMS[0], 64)],
+                      required=(L.OP_CONV3_FWD, L.OP_CONV3_DGRAD, L.OP_CONV3_WGRAD))
 
 
 # ------------------------------------------------------------------ the InstanceNorm + LeakyReLU launches of the step programs, element by element

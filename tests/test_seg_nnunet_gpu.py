@@ -353,7 +353,7 @@ def _kernel_instances(survey):
     out = set()
     for family in _NAMED:
         for key in survey.seen[family]:
-            name = key if family == "conv3x3" else key[1][0]
+            name = key[1][0]
             out |= {re.sub(r"\s*\[[^\]]*\]", "", part).strip() for part in name.split(" + ")}
     return out
 
@@ -382,7 +382,7 @@ def test_seg_only_programs_launch_only_reference_tested_instances():
     tests/test_ops_gpu.py makes, the sets its own guards hold the MTnnUNet and U-Net++ programs to."""
     import test_ops_gpu as OPS
     _, seg = _surveys()
-    tested = {"conv3x3": OPS._reference_tested_instances(), "InstanceNorm": OPS._reference_tested_instnorm_keys(),
+    tested = {"conv3x3": OPS._reference_tested_conv3x3_keys(), "InstanceNorm": OPS._reference_tested_instnorm_keys(),
               "transposed-convolution": OPS._reference_tested_convT_keys(), "small-op": OPS._reference_tested_small_op_keys(),
               "layout": OPS._reference_tested_layout_keys()}
     extra = _keys_outside(seg, tested)

@@ -1,6 +1,6 @@
 """tests/step_programs.py -- the survey of a step program and the compare-and-report behind the launch-coverage guards of tests/test_ops_gpu.py --
-on hand-made programs: the walks that carry state (the ConvT pair, the run of layout ops), the session cache and the failure messages.
-mtbc_convT_kernel_name and mtbc_op_kernel_name are host-only; no device, no step is built."""
+on hand-made programs: the walks that carry state (the ConvT pair, the run of layout ops), the conv3x3 key flag by flag, the session cache and
+the failure messages.  mtbc_conv3x3_kernel_name, mtbc_convT_kernel_name and mtbc_op_kernel_name are host-only; no device, no step is built."""
 import types
 
 import pytest
@@ -83,6 +83,107 @@ def test_a_weight_view_between_two_packs_is_single():
     assert set(s.seen[LAYOUT]) == {SP._wview_key(8, 24, 16, 8, 1, 0, 40, "single"), SP._pack_key(L.OP_CONV3_PACK_FWD, 24, 24, 0, 0, "single"),
                                    SP._pack_key(L.OP_CONV3_PACK_DGRAD, 24, 24, 1, 0, "single")}
     assert s.seen[LAYOUT][SP._wview_key(8, 24, 16, 8, 1, 0, 40, "single")] == (L.OP_CONV3_WVIEW, (8, 24, 16, 8, 1, 0, 40))
+
+
+# ---- the conv3x3 key: the full name + the branches the arguments select (hand-made mtbc_conv3x3_args, dummy pointers)
+F_, D_, W_ = L.OP_CONV3_FWD, L.OP_CONV3_DGRAD, L.OP_CONV3_WGRAD
+_BF = dict(compute=1, c8=True)
+_PTR = 77 << 20          # a dummy address for a field the builder left NULL
+
+
+def _c3(op, N=2, segs=(32,), Cout=32, H=16, W=32, **mode):
+    return ops.conv3x3_case_args(op, N, list(segs), Cout, H, W, **mode)
+
+
+def _flags(op, **kw):
+    return SP._conv3_key(_c3(op, **kw), op)[1]
+
+
+def test_conv3_key_keeps_the_reduction_behind_the_weight_gradient():
+    name = lambda **kw: SP._conv3_key(_c3(W_, **kw), W_)[0]                                             # noqa: E731
+    assert name(**_BF).endswith("_kernel<false, 0> + splitk_reduce")
+    assert name(**_BF, in_kernel_reduce=True).endswith(" + splitk_fixup")
+    assert name().endswith(" + splitk_reduce + channel_sums") and name(bias=False).endswith(" + splitk_reduce")
+    # one image range on a 16 x 16 map, no dbias, no accumulation: the blocks store straight into dw -- no suffix, another key than with dbias
+    direct = dict(_BF, N=1, segs=(64,), Cout=48, H=16, W=16)
+    assert " + " not in name(**direct, bias=False) and name(**direct).endswith(" + splitk_reduce")
+    assert len({name(**direct, bias=False), name(**direct), name(**direct, bias=False, in_kernel_reduce=True, accumulate_dw=True)}) == 3
+
+
+@pytest.mark.parametrize("op,flag,without,with_", [
+    (F_, "bias", dict(bias=False), dict(bias=True)),
+    (F_, "stats", dict(_BF, out_c8=True), dict(_BF, out_c8=True, stats=True)),
+    (F_, "out_acc", dict(_BF, bias=False), dict(_BF, bias=False, out_accumulate=True)),
+    (F_, "out_partial", dict(_BF, out_c8=True, bias=False, stats=True, norm=0.1), dict(_BF, out_c8=True, bias=False, stats=True, norm=0.1, out_partial=True)),
+    (F_, "norm_affine", dict(_BF, out_c8=True, bias=False, stats=True), dict(_BF, out_c8=True, bias=False, stats=True, norm=0.1)),
+    (D_, "codes=0,2", dict(_BF, segs=(16, 16), accumulate=[0, 1]), dict(_BF, segs=(16, 16), accumulate=[0, 2])),
+    (D_, "codes=3", dict(_BF, segs=(16, 16), accumulate=[0, 0]), dict(_BF, segs=(16, 16), dx_c8=True)),
+    (D_, "codes=1", dict(accumulate=[0]), dict(accumulate=[1])),
+    (W_, "dbias", dict(_BF, bias=False), dict(_BF, bias=True)),
+    (W_, "acc_dw", dict(_BF, bias=False), dict(_BF, bias=False, accumulate_dw=True)),
+    (W_, "acc_dw", dict(bias=False), dict(bias=False, accumulate_dw=True)),
+    (F_, "segs>1", dict(_BF), dict(_BF, segs=(16, 16))),
+    (D_, "segs>1", dict(_BF), dict(_BF, segs=(16, 16))),
+    (W_, "segs>1", dict(), dict(segs=(16, 16))),
+    (F_, "straddle", dict(_BF, segs=(32, 32)), dict(_BF, segs=(24, 40))),               # a 32-channel chunk of the 16-bit MFMA reads two segments
+    (W_, "straddle", dict(_BF, segs=(32, 32)), dict(_BF, segs=(24, 40))),
+    (F_, "straddle", dict(segs=(8, 24)), dict(segs=(12, 20))),                          # ... an 8-channel chunk of the fp32 kernels
+    (D_, "straddle", dict(_BF, segs=(16, 32)), dict(_BF, segs=(24, 24))),               # a 16-row tile writes two segments
+    (F_, "ragged_rows", dict(_BF), dict(_BF, Cout=24)),
+    (D_, "ragged_rows", dict(_BF, segs=(48,)), dict(_BF, segs=(40,))),
+    (W_, "ragged_rows", dict(), dict(Cout=40)),
+    (F_, "ragged_k", dict(_BF, segs=(64,)), dict(_BF, segs=(48,))),
+    (F_, "ragged_k", dict(segs=(16,)), dict(segs=(12,))),
+    (D_, "ragged_k", dict(_BF, Cout=64), dict(_BF, Cout=48)),
+    (F_, "force_direct", dict(), dict(force_direct=True)),
+    (D_, "force_direct", dict(), dict(force_direct=True)),
+    (W_, "force_direct", dict(), dict(force_direct=True)),
+])
+def test_conv3_key_flag_follows_the_arguments(op, flag, without, with_):
+    a, b = _flags(op, **without), _flags(op, **with_)
+    assert flag not in a and flag in b and a != b, (a, b)
+
+
+def test_conv3_key_norm_plain_and_strided():
+    a = _c3(F_, **_BF, out_c8=True, bias=False, stats=True, norm=0.1)
+    a.norm_gamma = a.norm_beta = None
+    assert "norm_plain" in SP._conv3_key(a, F_)[1] and "norm_affine" not in SP._conv3_key(a, F_)[1]
+    for op in (F_, D_, W_):
+        a = _c3(op, **_BF, segs=(16, 16))
+        dense = SP._conv3_key(a, op)
+        a.in_[1].batch_stride += 8 * 16 * 32          # a channel-range view of a wider tensor
+        assert "strided" not in dense[1] and SP._conv3_key(a, op)[1] == dense[1] + ("strided",)
+
+
+@pytest.mark.parametrize("op,fields", [
+    (F_, ("dbias", "dw", "dout", "accumulate_dw", "wgrad_sync")),
+    (D_, ("bias", "dbias", "dw", "out", "accumulate_dw", "out_accumulate", "stats_partial", "out_partial", "norm_z")),
+    (W_, ("bias", "out", "out_accumulate", "stats_partial", "out_partial", "norm_z")),
+])
+def test_conv3_key_ignores_fields_the_call_does_not_read(op, fields):
+    for mode in (_BF, {}):
+        want = SP._conv3_key(_c3(op, **mode), op)
+        for name in fields:
+            a = _c3(op, **mode)
+            setattr(a, name, 1 if name.startswith("accumulate") or name == "out_accumulate" else _PTR)
+            assert SP._conv3_key(a, op) == want, (op, mode, name)
+    # channel-blocked operands: the dispatch never looks at force_direct
+    for op in (F_, D_, W_):
+        assert _flags(op, **_BF, force_direct=True) == _flags(op, **_BF)
+
+
+def test_conv3_collector_keys_by_kind_and_arguments_and_names_the_segments():
+    wg, fw = _mk(W_), _mk(F_)
+    wg.u.conv3, fw.u.conv3 = _c3(W_, **_BF, segs=(16, 16), bias=False), _c3(F_, **_BF, segs=(16, 16), bias=False)
+    s = _survey("conv3", {"fwd": [fw], "bwd": [wg, wg]})
+    assert s.seen["conv3x3"] == {(F_, SP._conv3_key(fw.u.conv3, F_)): (F_, (2, 32, 32, 16, 32, (16, 16))),
+                                 (W_, SP._conv3_key(wg.u.conv3, W_)): (W_, (2, 32, 32, 16, 32, (16, 16)))}
+    with pytest.raises(AssertionError) as e:
+        SP.assert_all_tested("conv3x3", {(F_, SP._conv3_key(fw.u.conv3, F_))}, [s], required=(F_, W_))
+    assert "splitk_reduce" in str(e.value) and "segs>1" in str(e.value) and "(2, 32, 32, 16, 32, (16, 16))" in str(e.value)
+    with pytest.raises(AssertionError) as e:
+        SP.assert_all_tested("conv3x3", set(s.seen["conv3x3"]), [s], required=(F_, D_, W_))
+    assert f"[{D_}]" in str(e.value)
 
 
 # ---- what a survey keeps, and for how long
