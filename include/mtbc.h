@@ -552,6 +552,25 @@ int mtbc_focal_fwd_bwd(const mtbc_focal_args* a, void* stream);
  *   out[0] = alpha*seg + (1-alpha)*cls, out[1] = seg, out[2] = cls, out[3] = nan flag (0/1)  */
 int mtbc_loss_mix(const float* seg, const float* cls, float alpha, float* out4, void* stream);
 
+/* -------------------------------------------------------------- softmax over the rows of (N, C) logits, C <= 3
+ * The output nn.Softmax(dim=1) of the single-task classifier (nnUNet_classifier.py:168-169), which the reference's criterion then reads as if
+ * the probabilities were logits.  backward == 0: p = exp(x - max x) / sum exp(x - max x), the max-subtracted form torch evaluates (an all -inf
+ * row gives NaN as it does there).  backward != 0: dz = p * (dp - sum_c p_c dp_c) from the forward's p.  One block; a thread owns whole rows,
+ * so there is no reduction across threads.  exp is the library's own (range reduction by ln 2 in two pieces, degree-7 polynomial, fused
+ * multiply-adds written out, no contraction): the row function is compiled once for host and device and gives the same bits on both.
+ * mtbc_softmax_rows_host: the same function on host pointers, no GPU call.  dz may alias dp.
+ * MTBC_E_BADSHAPE: N < 1 or C outside 1 .. 3; MTBC_E_BADARG: a null pointer the direction reads or writes.                                   */
+typedef struct {
+    int32_t N, C;
+    int32_t backward;                /* 0: x -> p; else (p, dp) -> dz */
+    const float* x;                  /* (N, C) logits (forward) */
+    float* p;                        /* (N, C) probabilities: written by the forward, read by the backward */
+    const float* dp;                 /* (N, C) d loss / d p (backward) */
+    float* dz;                       /* (N, C) d loss / d x (backward) */
+} mtbc_softmax_args;
+int mtbc_softmax_rows(const mtbc_softmax_args* a, void* stream);
+int mtbc_softmax_rows_host(const mtbc_softmax_args* a);
+
 /* ------------------------------------------------------------------------------------ dynamic loss scale
  * torch.amp.GradScaler's rule, stream-ordered on the device (no host read in the step).  One step is
  *   mtbc_loss_scale_begin -> forward, losses, backward [, all-reduce] -> mtbc_loss_scale_check -> mtbc_loss_scale_optim
@@ -749,6 +768,42 @@ typedef struct {
 } mtbc_seg_step_metrics_args;
 int mtbc_seg_step_metrics(const mtbc_seg_step_metrics_args* a, void* stream);
 
+/* ---- metrics of a classification-only step (training_classification.py:34-162): the samples launch of mtbc_train_metrics / mtbc_eval_metrics --
+ * the same kernel, the same predicate on the model's OUTPUT (for a 3-class nnUNetClassifier that is the probabilities: first of equal maxima) --
+ * and nothing else: conf[true][predicted] += 1 per sample, table[cursor][3] += N, loss_rows[cursor][0..3] = w * (double)loss_in[0..3] when
+ * loss_in is not NULL (w = *shard_weight, NULL = 1), then the cursor advances.  There is no pixel launch: table[cursor][0..2] stay zero.
+ * Cursor and state, capacity and the drop counter, the empty shard (N == 0: only the cursor advances) behave exactly as in
+ * mtbc_seg_step_metrics.  MTBC_E_BADARG: a null pointer (the data pointers may be NULL with N == 0; loss_rows must be given with loss_in and
+ * N > 0); MTBC_E_BADSHAPE: n_logits outside 1 .. 3, a negative count.                                                                        */
+typedef struct {
+    const float* cls_out;            /* (N, n_logits) fp32: what the model returns */
+    const float* target;             /* (N, n_logits): one-hot rows, or the {0,1} label when n_logits == 1 */
+    int32_t      N, n_logits;
+    int64_t*     table;              /* [capacity][4]: 0, 0, 0, samples -- one row per batch */
+    int64_t*     conf;               /* [3][3] rows = ground truth, cols = prediction */
+    int32_t*     state;              /* [0] cursor, [1] batches dropped */
+    int32_t      capacity;
+    const float* loss_in;            /* 4 floats [cls, 0, cls, nan_flag] of the batch, or NULL */
+    double*      loss_rows;          /* [capacity][4] */
+    const float* shard_weight;       /* device word, or NULL = 1 */
+} mtbc_cls_step_metrics_args;
+int mtbc_cls_step_metrics(const mtbc_cls_step_metrics_args* a, void* stream);
+
+/* ---- per-image rows of the classification driver's testing phase (utils/models.py:400-505): ONE launch of one block appends
+ * (ground_truth, predicted_label) of each of the batch's N images to rows[cursor .. cursor + N) and advances the cursor by N.  The rule is the
+ * samples rule above: first maximum of the output row against first maximum of the one-hot row; n_logits == 1: sigmoid(output) > .5 against
+ * target != 0.  A batch that does not fit (cursor + N > capacity) writes nothing, adds 1 to state[1], and the cursor still advances.
+ * MTBC_E_BADARG: a null pointer; MTBC_E_BADSHAPE: N < 1, n_logits outside 1 .. 3, a negative capacity.                                       */
+typedef struct {
+    const float* cls_out;            /* (N, n_logits) */
+    const float* target;             /* (N, n_logits) one-hot, or (N, 1) {0,1} */
+    int32_t      N, n_logits;
+    int32_t*     rows;               /* [capacity][2]: ground truth, predicted label */
+    int32_t*     state;              /* [0] cursor = images seen, [1] batches dropped */
+    int32_t      capacity;
+} mtbc_cls_test_rows_args;
+int mtbc_cls_test_rows(const mtbc_cls_test_rows_args* a, void* stream);
+
 /* ------------------------------------------------------------------ hole filling of a predicted mask
  * scipy.ndimage.binary_fill_holes (default structure) of the raw prediction, which the segmentation driver's testing phase applies before its
  * metrics (utils/models.py:39-100, fill_holes=True): foreground = sigmoid(seg_logits) > .5, the predicate of the Dice counters above (a NaN is
@@ -785,6 +840,8 @@ enum {
     MTBC_OP_SET_STREAM, MTBC_OP_EVENT_RECORD, MTBC_OP_EVENT_WAIT,
     MTBC_OP_IN_DPARAM
 };
+/* appended kinds (additive: the list above is as it was) */
+enum { MTBC_OP_SOFTMAX = 37 };       /* mtbc_softmax_rows on u.softmax, either direction */
 /* (the last three: stream control of mtbc_program_run_ms -- independent ops of a step, the weight gradient and the input
  * gradient of one layer, overlap on two HIP streams: the small latency-bound launches of the deep levels fill the chip together) */
 
@@ -863,6 +920,7 @@ typedef struct {
         mtbc_head_fuse_args head;
         struct { const float* w; float* dst; int32_t Cout, Cin, ci_off, ci_cnt, mode, k_off, K; } wview;
         struct { const float* src; int64_t src_batch_stride; void* dst; int32_t N, C, HW, compute; } c8pack;   /* C8_PACK and C8_PACK16 (src = 16-bit planar, `compute` unused) */
+        mtbc_softmax_args softmax;
         mtbc_dparam_desc dparam;         /* MTBC_OP_IN_DPARAM: a run of them is issued as one mtbc_instnorm_dparam_many launch */
         struct { void* event; int32_t index; } sync;      /* SET_STREAM: following ops go to streams[index]; EVENT_RECORD / EVENT_WAIT: on the current stream */
     } u;

@@ -184,6 +184,23 @@ class SegStepMetricsArgs(C.Structure):
                 ("state", C.c_void_p), ("capacity", C.c_int32), ("loss_in", C.c_void_p), ("loss_rows", C.c_void_p), ("shard_weight", C.c_void_p)]
 
 
+class SoftmaxArgs(C.Structure):
+    """mtbc_softmax_args (include/mtbc.h): softmax over the rows of (N, C <= 3), either direction."""
+    _fields_ = [("N", C.c_int32), ("C", C.c_int32), ("backward", C.c_int32), ("x", C.c_void_p), ("p", C.c_void_p), ("dp", C.c_void_p), ("dz", C.c_void_p)]
+
+
+class ClsStepMetricsArgs(C.Structure):
+    """mtbc_cls_step_metrics_args (include/mtbc.h): the metrics call of a classification-only step."""
+    _fields_ = [("cls_out", C.c_void_p), ("target", C.c_void_p), ("N", C.c_int32), ("n_logits", C.c_int32), ("table", C.c_void_p), ("conf", C.c_void_p),
+                ("state", C.c_void_p), ("capacity", C.c_int32), ("loss_in", C.c_void_p), ("loss_rows", C.c_void_p), ("shard_weight", C.c_void_p)]
+
+
+class ClsTestRowsArgs(C.Structure):
+    """mtbc_cls_test_rows_args (include/mtbc.h)."""
+    _fields_ = [("cls_out", C.c_void_p), ("target", C.c_void_p), ("N", C.c_int32), ("n_logits", C.c_int32), ("rows", C.c_void_p), ("state", C.c_void_p),
+                ("capacity", C.c_int32)]
+
+
 class FillHolesArgs(C.Structure):
     """mtbc_fill_holes_args (include/mtbc.h)."""
     _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("seg_logits", C.c_void_p), ("filled_logits", C.c_void_p),
@@ -247,7 +264,8 @@ class _OpUnion(C.Union):
     _fields_ = [("conv3", Conv3x3Args), ("inorm", InstNormArgs), ("pool", MaxPoolArgs), ("convT", ConvTArgs),
                 ("conv1", Conv1x1Args), ("gap", GapArgs), ("linear", LinearArgs), ("dice", DiceArgs),
                 ("focal", FocalArgs), ("optim", OptimArgs), ("pack", _PackArgs), ("mix", _MixArgs),
-                ("memset0", _MemsetArgs), ("counts", _CountsArgs), ("head", HeadFuseArgs), ("c8pack", _C8PackArgs), ("wview", _WViewArgs), ("dparam", DparamDesc), ("sync", _SyncArgs)]
+                ("memset0", _MemsetArgs), ("counts", _CountsArgs), ("head", HeadFuseArgs), ("c8pack", _C8PackArgs), ("wview", _WViewArgs), ("dparam", DparamDesc), ("sync", _SyncArgs),
+                ("softmax", SoftmaxArgs)]
 
 
 class Op(C.Structure):
@@ -261,6 +279,7 @@ class Op(C.Structure):
  OP_DICE_FWD, OP_DICE_BWD, OP_FOCAL, OP_LOSS_MIX, OP_OPTIM, OP_MEMSET, OP_DICE_COUNTS, OP_CONV3_PACK_LP,
  OP_HEAD_COMBINE, OP_HEAD_EXPAND, OP_C8_PACK, OP_C8_PACK16, OP_CONV3_WVIEW,
  OP_SET_STREAM, OP_EVENT_RECORD, OP_EVENT_WAIT, OP_IN_DPARAM) = range(1, 37)
+OP_SOFTMAX = 37            # appended (the header's second enum)
 
 OP_UNION_FIELD = {
     OP_CONV3_FWD: "conv3", OP_CONV3_DGRAD: "conv3", OP_CONV3_WGRAD: "conv3",
@@ -273,6 +292,7 @@ OP_UNION_FIELD = {
     OP_MEMSET: "memset0", OP_DICE_COUNTS: "counts", OP_CONV3_PACK_LP: "pack",
     OP_HEAD_COMBINE: "head", OP_HEAD_EXPAND: "head", OP_C8_PACK: "c8pack", OP_C8_PACK16: "c8pack", OP_CONV3_WVIEW: "wview",
     OP_SET_STREAM: "sync", OP_EVENT_RECORD: "sync", OP_EVENT_WAIT: "sync", OP_IN_DPARAM: "dparam",
+    OP_SOFTMAX: "softmax",
 }
 
 # every symbol include/mtbc.h declares (tests check the library exports all of them)
@@ -302,6 +322,7 @@ EXPORTS = [
     "mtbc_program_run_ms", "mtbc_event_create", "mtbc_event_destroy", "mtbc_op_kernel_name",
     "mtbc_seg_metrics_workspace_size", "mtbc_seg_metrics", "mtbc_batch_assemble", "mtbc_train_metrics",
     "mtbc_eval_metrics", "mtbc_seg_step_metrics", "mtbc_fill_holes", "mtbc_fill_holes_host",
+    "mtbc_softmax_rows", "mtbc_softmax_rows_host", "mtbc_cls_step_metrics", "mtbc_cls_test_rows",
 ]
 
 ABI_VERSION = 203          # MTBC_VERSION of include/mtbc.h these mirrors follow
@@ -438,6 +459,14 @@ def load() -> C.CDLL:
     lib.mtbc_fill_holes.argtypes = [C.POINTER(FillHolesArgs), C.c_void_p]
     lib.mtbc_fill_holes_host.restype = C.c_int
     lib.mtbc_fill_holes_host.argtypes = [C.POINTER(FillHolesArgs)]
+    lib.mtbc_softmax_rows.restype = C.c_int
+    lib.mtbc_softmax_rows.argtypes = [C.POINTER(SoftmaxArgs), C.c_void_p]
+    lib.mtbc_softmax_rows_host.restype = C.c_int
+    lib.mtbc_softmax_rows_host.argtypes = [C.POINTER(SoftmaxArgs)]
+    lib.mtbc_cls_step_metrics.restype = C.c_int
+    lib.mtbc_cls_step_metrics.argtypes = [C.POINTER(ClsStepMetricsArgs), C.c_void_p]
+    lib.mtbc_cls_test_rows.restype = C.c_int
+    lib.mtbc_cls_test_rows.argtypes = [C.POINTER(ClsTestRowsArgs), C.c_void_p]
     _lib = lib
     return lib
 

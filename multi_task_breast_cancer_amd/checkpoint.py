@@ -57,6 +57,14 @@ def seg_metrics_row(epoch: int, lr: float, train_dice: float, val_dice: float, t
     return f"{epoch},{lr:.8f},{train_dice:.4f}, {val_dice:.4f},{test_dice:.4f},{train_loss:.4f},{val_loss:.4f}"
 
 
+CLS_METRICS_HEADER = "epoch,LR,Train_loss,Validation_loss,Train_acc,Train_F1,Validation_acc,Validation_F1"   # training_classification.py:213-214
+
+
+def cls_metrics_row(epoch: int, lr: float, train_loss: float, val_loss: float, train_acc: float, train_f1: float, val_acc: float, val_f1: float) -> str:
+    """training_classification.py:262-266; `lr` is the optimizer's at the START of the epoch (:219)."""
+    return f"{epoch},{lr:.8f},{train_loss:.4f},{val_loss:.4f},{train_acc:.4f},{train_f1:.4f},{val_acc:.4f},{val_f1:.4f}"
+
+
 def write_metrics_file(path_file: str, text_to_write: str, close: bool = True) -> None:
     """src/utils/miscellany.py:155-169: append one line (the caller writes METRICS_HEADER first, as :216-217 does)."""
     with open(path_file, "a") as f:

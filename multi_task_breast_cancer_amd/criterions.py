@@ -8,6 +8,7 @@
   FocalLoss  replaces src/utils/criterions.py:6-24
   apply_criterion_multitask_segmentation_classification mirrors criterions.py:52-76 (same signature, NaN -> exit 1)
   apply_criterion_binary_segmentation mirrors criterions.py:27-49 (the single-task segmentation driver's)
+  apply_criterion_classification mirrors criterions.py:79-97 (the single-task classification driver's)
 
 The criteria are torch.autograd.Functions over the C-ABI kernels (mtbc_dice_fwd/_bwd, mtbc_focal_fwd_bwd);
 they raise when handed CPU tensors -- there is no fallback.
@@ -174,6 +175,19 @@ def apply_criterion_binary_segmentation(criterion, ground_truth, segmentation, i
             loss = torch.sum(torch.stack([criterion(s, ground_truth) for s in heads]))
     else:
         loss = criterion(segmentation, ground_truth)
+    if not torch.isnan(loss):
+        return loss
+    exit_on_nan()
+
+
+def apply_criterion_classification(criterion_class, label, predicted_class, inversely_weighted=False):
+    """criterions.py:79-97: the criterion on what the model returned (for the 3-class nnUNetClassifier its probabilities); with a LIST of labels
+    the sum over the reversed predictions, whatever `inversely_weighted` says (both of the reference's branches are the same sum); a NaN loss ends
+    the run."""
+    if isinstance(label, list):
+        loss = torch.sum(torch.stack([criterion_class(c, label) for c in reversed(predicted_class)]))
+    else:
+        loss = criterion_class(predicted_class, label)
     if not torch.isnan(loss):
         return loss
     exit_on_nan()

@@ -354,6 +354,56 @@ __global__ void loss_mix_kernel(const float* seg, const float* cls, float alpha,
     out4[3] = (s != s || c != c) ? 1.f : 0.f;
 }
 
+// ------------------------------------------------------------------ softmax over the rows of (N, C), C <= 3 (one block, a thread owns whole rows)
+// The row functions are compiled once for host and device (mtbc_softmax_rows_host): exp is written out -- x = n ln 2 + r with ln 2 in two pieces,
+// the degree-7 Taylor polynomial on |r| <= ln 2 / 2 (truncation 5e-9 relative), ldexp -- in explicit fused multiply-adds with contraction off,
+// so both compilations round the same operations and give the same bits.  x <= 0 here (the row maximum is subtracted first).
+__host__ __device__ inline float softmax_exp(float x) {
+#pragma clang fp contract(off)
+    if (x != x) return x;
+    if (x < -104.0f) return 0.f;                               // below half the smallest subnormal (and -inf)
+    const float n = rintf(x * 1.44269504088896341f);
+    float r = fmaf(-n, 0.693145751953125f, x);                 // ln 2, high 16 bits: n * hi is exact
+    r = fmaf(-n, 1.42860682030941723e-6f, r);                  // ... and the rest
+    float q = 1.0f / 5040.0f;
+    q = fmaf(q, r, 1.0f / 720.0f);
+    q = fmaf(q, r, 1.0f / 120.0f);
+    q = fmaf(q, r, 1.0f / 24.0f);
+    q = fmaf(q, r, 1.0f / 6.0f);
+    q = fmaf(q, r, 0.5f);
+    q = fmaf(q, r, 1.0f);
+    q = fmaf(q, r, 1.0f);
+    return ldexpf(q, (int)n);
+}
+__host__ __device__ inline void softmax_row_fwd(const float* x, float* p, int C) {
+#pragma clang fp contract(off)
+    float m = x[0];
+    for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
+    float e[3], s = 0.f;
+    for (int c = 0; c < C; ++c) { e[c] = softmax_exp(x[c] - m); s += e[c]; }
+    for (int c = 0; c < C; ++c) p[c] = e[c] / s;
+}
+__host__ __device__ inline void softmax_row_bwd(const float* p, const float* dp, float* dz, int C) {
+#pragma clang fp contract(off)
+    float s = p[0] * dp[0];
+    for (int c = 1; c < C; ++c) s = fmaf(p[c], dp[c], s);
+    float o[3];
+    for (int c = 0; c < C; ++c) o[c] = p[c] * (dp[c] - s);
+    for (int c = 0; c < C; ++c) dz[c] = o[c];                  // dz may alias dp
+}
+__global__ __launch_bounds__(64) void softmax_rows_kernel(const mtbc_softmax_args a) {
+    for (int n = threadIdx.x; n < a.N; n += blockDim.x) {
+        const size_t o = (size_t)n * a.C;
+        if (a.backward) softmax_row_bwd(a.p + o, a.dp + o, a.dz + o, a.C);
+        else softmax_row_fwd(a.x + o, a.p + o, a.C);
+    }
+}
+static int softmax_args_ok(const mtbc_softmax_args* a) {
+    if (!a || a->N < 1 || a->C < 1 || a->C > 3) return MTBC_E_BADSHAPE;
+    if (!a->p || (a->backward ? (!a->dp || !a->dz) : !a->x)) return MTBC_E_BADARG;
+    return MTBC_OK;
+}
+
 // ------------------------------------------------------------------ dynamic loss scale (torch.amp.GradScaler's rule on the device)
 // The two single-thread halves are plain functions shared by the kernels and by the host-only entry points, so that the rule a machine without a GPU
 // tests is the rule the device runs.
@@ -628,6 +678,24 @@ int mtbc_loss_mix(const float* seg, const float* cls, float alpha, float* out4, 
     if (!seg || !cls || !out4) return MTBC_E_BADARG;
     hipLaunchKernelGGL(loss_mix_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, seg, cls, alpha, out4);
     MTBC_CHECK_LAUNCH();
+    return MTBC_OK;
+}
+
+int mtbc_softmax_rows(const mtbc_softmax_args* a, void* stream) {
+    const int rc = softmax_args_ok(a);
+    if (rc != MTBC_OK) return rc;
+    hipLaunchKernelGGL(softmax_rows_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *a);
+    MTBC_CHECK_LAUNCH();
+    return MTBC_OK;
+}
+int mtbc_softmax_rows_host(const mtbc_softmax_args* a) {
+    const int rc = softmax_args_ok(a);
+    if (rc != MTBC_OK) return rc;
+    for (int n = 0; n < a->N; ++n) {
+        const size_t o = (size_t)n * a->C;
+        if (a->backward) softmax_row_bwd(a->p + o, a->dp + o, a->dz + o, a->C);
+        else softmax_row_fwd(a->x + o, a->p + o, a->C);
+    }
     return MTBC_OK;
 }
 

@@ -164,6 +164,7 @@ int mtbc_program_run_ms(const mtbc_op* ops, int32_t first, int32_t count, void* 
             case MTBC_OP_DICE_BWD: rc = mtbc_dice_bwd(&o->u.dice, stream); break;
             case MTBC_OP_FOCAL: rc = mtbc_focal_fwd_bwd(&o->u.focal, stream); break;
             case MTBC_OP_LOSS_MIX: rc = mtbc_loss_mix(o->u.mix.seg, o->u.mix.cls, o->u.mix.alpha, o->u.mix.out4, stream); break;
+            case MTBC_OP_SOFTMAX: rc = mtbc_softmax_rows(&o->u.softmax, stream); break;
             case MTBC_OP_OPTIM: rc = mtbc_optim_step(&o->u.optim, stream); break;
             case MTBC_OP_MEMSET:
                 rc = hipMemsetAsync(o->u.memset0.ptr, 0, o->u.memset0.bytes, (hipStream_t)stream) == hipSuccess ? MTBC_OK : MTBC_E_LAUNCH;

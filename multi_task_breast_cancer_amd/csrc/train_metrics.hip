@@ -196,6 +196,31 @@ int launch_metrics(const float* seg_logits, const float* mask, int64_t n_seg, co
     return MTBC_OK;
 }
 
+// mtbc_cls_test_rows: one block; sample s of the batch becomes row cursor + s = (ground truth, predicted label) by the samples rule above
+__global__ __launch_bounds__(TM_BLOCK) void cls_test_rows_kernel(const float* __restrict__ out, const float* __restrict__ target, int N, int n_logits,
+                                                                  int* __restrict__ rows, int* __restrict__ state, int capacity) {
+    const int cursor = state[0];
+    const bool fits = cursor >= 0 && N <= capacity && cursor <= capacity - N;
+    if (fits)
+        for (int s = threadIdx.x; s < N; s += TM_BLOCK) {
+            int pred, gt;
+            if (n_logits == 1) {
+                pred = sigmoidf_(out[s]) > 0.5f ? 1 : 0;
+                gt = target[s] != 0.f ? 1 : 0;
+            } else {
+                pred = first_argmax(out + (size_t)s * n_logits, n_logits);
+                gt = first_argmax(target + (size_t)s * n_logits, n_logits);
+            }
+            rows[2 * ((size_t)cursor + s)] = gt;
+            rows[2 * ((size_t)cursor + s) + 1] = pred;
+        }
+    __syncthreads();                                           // every thread has read the cursor
+    if (threadIdx.x == 0) {
+        if (!fits) state[1] += 1;
+        if (cursor <= 0x7fffffff - N) state[0] = cursor + N;
+    }
+}
+
 }  // namespace
 
 extern "C" int mtbc_train_metrics(const mtbc_train_metrics_args* a, void* stream) {
@@ -222,6 +247,33 @@ extern "C" int mtbc_seg_step_metrics(const mtbc_seg_step_metrics_args* a, void* 
     const int rc = launch_pixels(a->seg_logits, a->mask, a->n_seg, table, a->state, a->capacity, st);
     if (rc != MTBC_OK) return rc;
     hipLaunchKernelGGL(seg_step_tail_kernel, dim3(1), dim3(1), 0, st, a->N, table, a->state, a->capacity, a->loss_in, a->loss_rows, a->shard_weight);
+    MTBC_CHECK_LAUNCH();
+    return MTBC_OK;
+}
+
+extern "C" int mtbc_cls_step_metrics(const mtbc_cls_step_metrics_args* a, void* stream) {
+    if (!a) return MTBC_E_BADARG;
+    if (!a->table || !a->conf || !a->state) return MTBC_E_BADARG;
+    if (a->N < 0 || a->capacity < 0 || a->n_logits < 1 || a->n_logits > 3) return MTBC_E_BADSHAPE;
+    if (a->N > 0 && (!a->cls_out || !a->target)) return MTBC_E_BADARG;
+    if (a->N > 0 && a->loss_in && !a->loss_rows) return MTBC_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* table = reinterpret_cast<unsigned long long*>(a->table);
+    unsigned long long* conf = reinterpret_cast<unsigned long long*>(a->conf);
+    if (a->loss_in) hipLaunchKernelGGL(train_metrics_samples_kernel<true>, dim3(1), dim3(TM_BLOCK), 0, st, a->cls_out, a->target, a->N, a->n_logits, table,
+                                       conf, a->state, a->capacity, a->loss_in, a->loss_rows, a->shard_weight);
+    else hipLaunchKernelGGL(train_metrics_samples_kernel<false>, dim3(1), dim3(TM_BLOCK), 0, st, a->cls_out, a->target, a->N, a->n_logits, table,
+                            conf, a->state, a->capacity, nullptr, nullptr, nullptr);
+    MTBC_CHECK_LAUNCH();
+    return MTBC_OK;
+}
+
+extern "C" int mtbc_cls_test_rows(const mtbc_cls_test_rows_args* a, void* stream) {
+    if (!a) return MTBC_E_BADARG;
+    if (!a->cls_out || !a->target || !a->rows || !a->state) return MTBC_E_BADARG;
+    if (a->N < 1 || a->capacity < 0 || a->n_logits < 1 || a->n_logits > 3) return MTBC_E_BADSHAPE;
+    hipLaunchKernelGGL(cls_test_rows_kernel, dim3(1), dim3(TM_BLOCK), 0, (hipStream_t)stream, a->cls_out, a->target, a->N, a->n_logits, a->rows,
+                       a->state, a->capacity);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }

@@ -15,6 +15,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib as L
+from . import ops as _ops
 
 
 from . import switches as _sw
@@ -1098,6 +1099,29 @@ class StepPlan:
         self.bwd_emitters.append(emit_bwd)
         return y
 
+    def softmax(self, x: Act, out_name: str) -> Act:
+        """softmax over the C <= 3 values of each row of a (N, C, 1, 1) activation (the output nn.Softmax(dim=1) of the single-task classifier);
+        backward dz = p * (dp - sum p dp) into x's gradient, which nothing else may have written."""
+        assert x.N == self.N and x.H == 1 and x.W == 1 and x.C <= 3, (x.name, tuple(x.data.shape))
+        x.readers += 1
+        y = Act(out_name, self.alloc(self.N, x.C, 1, 1))
+        op = _mk(L.OP_SOFTMAX)
+        _ops.softmax_args(self.N, x.C, False, x=self._rd(x), p=y.data.data_ptr(), into=op.u.softmax)
+        self.fwd_ops.append(op)
+
+        def emit_bwd() -> None:
+            if not y.grad_written:
+                return
+            if x.grad_written:
+                raise NotImplementedError("softmax backward overwrites dx")
+            op = _mk(L.OP_SOFTMAX)
+            _ops.softmax_args(self.N, x.C, True, p=y.data.data_ptr(), dp=self.grad_of(y).data_ptr(), dz=self.grad_of(x).data_ptr(), into=op.u.softmax)
+            x.grad_written = True
+            self.bwd_ops.append(op)
+
+        self.bwd_emitters.append(emit_bwd)
+        return y
+
     # ------------------------------------------------------------------ losses (fused-step path)
     def fused_losses(self, seg_heads: Sequence[Act], logits: Optional[Act], mask: torch.Tensor, onehot: Optional[torch.Tensor],
                      alpha: float, inversely_weighted: bool, focal_weight: Optional[torch.Tensor] = None,
@@ -1112,6 +1136,8 @@ class StepPlan:
         if logits is None and alpha != 1.0:
             raise ValueError("a segmentation-only model has no classification loss to mix: alpha must be 1.0")
         nh = len(seg_heads)
+        if nh == 0:
+            return self._cls_only_losses(logits, onehot, alpha, focal_weight, loss_scale, binary, cls_gamma)
         assert 1 <= nh <= 4
         N, C_, H, W = seg_heads[0].data.shape
         if seg_criterion not in L.SEG_CRITERIA:
@@ -1153,20 +1179,41 @@ class StepPlan:
             self.focal_loss = torch.zeros(1, dtype=torch.float32, device=self.dev)      # the zero word the mix reads as the class loss
             self.keep.append(self.focal_loss)
         else:
-            assert (logits.C == 1) == bool(binary), "one logit <=> binary head"
-            op = _mk(L.OP_FOCAL)
-            a = op.u.focal
-            a.N, a.C, a.alpha, a.gamma = N, logits.C, 1.0, (0.0 if binary else float(cls_gamma))
-            a.x, a.target, a.weight = logits.data.data_ptr(), onehot.data_ptr(), _ptr(focal_weight)
-            a.loss, a.dx, a.gscale = self.focal_loss.data_ptr(), self.grad_of(logits).data_ptr(), (1.0 - alpha) * loss_scale
-            a.gscale_dev = self.grad_weight.data_ptr()
-            logits.grad_written = True
-            self.loss_ops.append(op)
+            self._focal_op(logits, onehot, N, focal_weight, (1.0 - alpha) * loss_scale, binary, cls_gamma)
         op = _mk(L.OP_LOSS_MIX)
         op.u.mix.seg = self.dice_loss.data_ptr() + 4 * nh
         op.u.mix.cls, op.u.mix.alpha, op.u.mix.out4 = self.focal_loss.data_ptr(), alpha, self.loss_out.data_ptr()
         self.loss_ops.append(op)
         self.keep += [mask] + ([onehot] if onehot is not None else []) + ([focal_weight] if focal_weight is not None else [])
+
+    def _focal_op(self, logits: Act, onehot: torch.Tensor, N: int, focal_weight, gscale: float, binary: bool, cls_gamma: float) -> None:
+        """The classification criterion's op of `fused_losses` on `logits` (whatever the model hands its criterion), gradient into its grad buffer."""
+        assert (logits.C == 1) == bool(binary), "one logit <=> binary head"
+        op = _mk(L.OP_FOCAL)
+        a = op.u.focal
+        a.N, a.C, a.alpha, a.gamma = N, logits.C, 1.0, (0.0 if binary else float(cls_gamma))
+        a.x, a.target, a.weight = logits.data.data_ptr(), onehot.data_ptr(), _ptr(focal_weight)
+        a.loss, a.dx, a.gscale = self.focal_loss.data_ptr(), self.grad_of(logits).data_ptr(), gscale
+        a.gscale_dev = self.grad_weight.data_ptr()
+        logits.grad_written = True
+        self.loss_ops.append(op)
+
+    def _cls_only_losses(self, logits: Act, onehot: torch.Tensor, alpha: float, focal_weight, loss_scale: float, binary: bool, cls_gamma: float) -> None:
+        """`fused_losses` of a classification-only model (training_classification.py:49-57): no segmentation op, alpha must be 0, and the mix reads
+        a zero word for the segmentation loss: the loss words are [cls, 0, cls, nan_flag].  The criterion reads the model's OUTPUT: for the 3-class
+        nnUNetClassifier the probabilities of its softmax op (the reference applies cross_entropy to them, a second log-softmax)."""
+        if logits is None or alpha != 0.0:
+            raise ValueError("a classification-only model has no segmentation loss to mix: alpha must be 0.0")
+        self.focal_loss = self.alloc(1)
+        self.loss_out = self.alloc(4)
+        self.grad_weight = torch.ones(1, dtype=torch.float32, device=self.dev)
+        self.seg_zero = torch.zeros(1, dtype=torch.float32, device=self.dev)            # the zero word the mix reads as the segmentation loss
+        self.keep += [self.grad_weight, self.seg_zero]
+        self._focal_op(logits, onehot, logits.N, focal_weight, loss_scale, binary, cls_gamma)
+        op = _mk(L.OP_LOSS_MIX)
+        op.u.mix.seg, op.u.mix.cls, op.u.mix.alpha, op.u.mix.out4 = self.seg_zero.data_ptr(), self.focal_loss.data_ptr(), 0.0, self.loss_out.data_ptr()
+        self.loss_ops.append(op)
+        self.keep += [onehot] + ([focal_weight] if focal_weight is not None else [])
 
     # ------------------------------------------------------------------ finalisation
     def emit_backward(self) -> None:

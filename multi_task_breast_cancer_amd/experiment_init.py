@@ -1,5 +1,5 @@
 """String -> object factory with the reference's names and signatures (src/utils/experiment_init.py:130-318),
-restricted to the multi-task training path and the single-task nnUNet segmentation baseline.  Unknown names raise
+restricted to the multi-task training path, the single-task nnUNet segmentation baseline and the single-task classifiers.  Unknown names raise
 ValueError (the reference silently builds an empty nn.Module, experiment_init.py:160-163 -- stricter here)."""
 from __future__ import annotations
 
@@ -11,7 +11,7 @@ import torch
 from torch.optim.lr_scheduler import CosineAnnealingLR, ReduceLROnPlateau
 
 from .criterions import DiceFocalLoss, DiceLoss, FocalLoss
-from .nets import MTnnUNet, MTUNetPlusPlus, nnUNet
+from .nets import MTnnUNet, MTUNetPlusPlus, UNetPlusPlusClassifier, nnUNet, nnUNetClassifier
 from .optim import FusedAdam, FusedAdamW, FusedSGD
 
 
@@ -53,6 +53,22 @@ def init_segmentation_model(architecture: str, sequences: int = 1, regions: int 
     if architecture != "nnUNet":
         raise ValueError(f"The segmentation model selected ({architecture!r}) is not on the MI355X hot path. Choose 'nnUNet'.")
     model = nnUNet(sequences=sequences, regions=regions)
+    _describe(model, save_folder)
+    return model
+
+
+def init_classification_model(architecture: str, sequences: int = 1, n_classes: int = 1, width: int = 48, save_folder: Path = None) -> torch.nn.Module:
+    """experiment_init.py:86-127, the single-task classification factory: 'nnUNetClassifier' and 'UNetPlusPlusClassifier' are on HIP
+    ('BTSUNetClassifier' is not).  `width` is ignored, as the reference ignores it for these two."""
+    logging.info(f"Creating {architecture} model")
+    logging.info(f"The model will be fed with {sequences} sequences")
+    if architecture == "nnUNetClassifier":
+        model = nnUNetClassifier(sequences=sequences, n_classes=n_classes)
+    elif architecture == "UNetPlusPlusClassifier":
+        model = UNetPlusPlusClassifier(spatial_dims=2, in_channels=sequences, n_classes=n_classes)
+    else:
+        raise ValueError(f"The classification model selected ({architecture!r}) is not on the MI355X hot path. Choose "
+                         "'nnUNetClassifier' or 'UNetPlusPlusClassifier'.")
     _describe(model, save_folder)
     return model
 
@@ -157,6 +173,25 @@ def load_segmentation_experiment_artefacts(config_model, config_opt, config_loss
                                   patience=int(config_opt["patience"]), min_lr=float(config_opt["min_lr"]),
                                   factor=float(config_opt["decrease_factor"]))
     return model, optimizer, criterion, scheduler
+
+
+def load_classification_experiment_artefacts(config_data, config_model, config_opt, config_loss, n_augments, run_path, fused: bool = False):
+    """experiment_init.py:321-336 -> (model, optimizer, classification_criterion, scheduler).  `fused`: init_optimizer's."""
+    model = init_classification_model(architecture=config_model["architecture"],
+                                      sequences=config_model["sequences"] + n_augments,
+                                      width=config_model["width"],
+                                      n_classes=len(config_data["classes"]),
+                                      save_folder=Path(f"{run_path}/") if run_path is not None else None)
+    if config_model.get("compute_dtype") is not None and hasattr(model, "set_compute"):      # optional key, as in the multi-task loader
+        model.set_compute(str(config_model["compute_dtype"]))
+    optimizer = init_optimizer(model=model, optimizer=config_opt["opt"], learning_rate=config_opt["lr"], fused=fused)
+    classification_criterion = init_criterion_classification(
+        n_classes=len(config_data["classes"]), classes_weighted=config_data["classes_weighted"],
+        classification_criterion=config_loss["classification_criterion"])
+    scheduler = init_lr_scheduler(optimizer=optimizer, scheduler=config_opt["scheduler"],
+                                  t_max=int(config_opt["t_max"]), patience=int(config_opt["patience"]),
+                                  min_lr=float(config_opt["min_lr"]), factor=float(config_opt["decrease_factor"]))
+    return model, optimizer, classification_criterion, scheduler
 
 
 def device_setup() -> str:

@@ -420,3 +420,136 @@ class FusedSegTestStep:
             for r in rows:
                 w.writerow([_csv_value(r[c]) for c in SEG_CSV_COLUMNS])
         return file
+
+
+def cls_rows_from_table(table, ids=None) -> List[dict]:
+    """The rows of the classification driver's results.csv (utils/models.py:448-452, :497-501) from the (M, 2) int table
+    (ground_truth, predicted_label) `mtbc_cls_test_rows` appended; `ids`: the patient ids (default 0 .. M - 1)."""
+    table = np.asarray(table).reshape(-1, 2)
+    ids = list(range(len(table))) if ids is None else list(ids)
+    if len(ids) != len(table):
+        raise ValueError(f"{len(table)} rows but {len(ids)} patient ids")
+    return [{"patient_id": i, "ground_truth": int(g), "predicted_label": int(p)} for i, (g, p) in zip(ids, table.tolist())]
+
+
+def write_cls_rows_csv(path: str, rows: List[dict]) -> None:
+    """results.csv as `metrics.to_csv(..., index=False)` writes it: `patient_id,ground_truth,predicted_label`."""
+    import csv
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, lineterminator="\n")
+        w.writerow(["patient_id", "ground_truth", "predicted_label"])
+        for r in rows:
+            w.writerow([r["patient_id"], r["ground_truth"], r["predicted_label"]])
+
+
+class FusedClsTestStep:
+    """The testing phase of the single-task classification driver (training_classification.py:284-298 -> `inference_multiclass_classification` /
+    `inference_binary_classification`, utils/models.py:400-505) in batches on the device.  Per batch: the compiled `pack` + `fwd` programs, then ONE
+    launch (`mtbc_cls_test_rows`) that appends (ground_truth, predicted_label) of every image to an int32 table at a device cursor: argmax of the
+    model's output against argmax of the one-hot label, or, for the binary head, sigmoid(output) > .5 against the {0, 1} label.  `result()` is one
+    read-back and returns the rows of results.csv; `write_csv(path)` writes that file; `report()` gives `multiclass_classification_metrics` (three
+    classes) or the five numbers of `binary_classification_metrics` (binary head) through `classification_report`.  `capacity`: images per
+    testing phase the table holds (8 bytes each)."""
+
+    cls_only = True
+
+    def __init__(self, model, capacity: int = 65536):
+        if not getattr(model, "cls_only", False):
+            raise ValueError("FusedClsTestStep takes a classification-only model (nets.nnUNetClassifier, nets.UNetPlusPlusClassifier)")
+        if int(capacity) < 1:
+            raise ValueError("capacity must be at least 1 row")
+        self.model, self.capacity = model, int(capacity)
+        self.binary = model.n_classes == 1
+        self._rows = self._state = self._target = self._scratch = None
+        self._coop_err = None
+        self._ids: list = []
+        self.table = None
+
+    def _buffers(self, dev) -> None:
+        if self._rows is None or self._rows.device != dev:
+            self._rows = torch.zeros(self.capacity, 2, dtype=torch.int32, device=dev)
+            self._state = torch.zeros(2, dtype=torch.int32, device=dev)
+
+    def reset(self) -> None:
+        self._ids = []
+        self._coop_err = None
+        if self._state is not None:
+            self._state.zero_()
+
+    def _target_buffer(self, N: int, dev) -> torch.Tensor:
+        c = 1 if self.binary else 3
+        t = self._target
+        if t is None or t.shape != (N, c) or t.device != dev:
+            self._target = t = torch.empty(N, c, dtype=torch.float32, device=dev)
+        return t
+
+    def _forward_and_append(self, st, target: torch.Tensor, patient_id) -> None:
+        st.programs["pack"].run()
+        st.programs["fwd"].run()
+        self._coop_err = self.model.coop_error_word()
+        self.append_outputs(st.logits.data.view(st.N, -1), target, patient_id)
+
+    @torch.no_grad()
+    def __call__(self, image: torch.Tensor, label: torch.Tensor, patient_id=None) -> None:
+        N, _, H, W = image.shape
+        st = self.model.compiled(N, H, W)
+        st.x.data.copy_(image, non_blocking=True)
+        dev = st.x.data.device
+        target = self._target_buffer(N, dev)
+        lab = label.to(dev, non_blocking=True).flatten()
+        if self.binary:
+            target.copy_(lab.view(-1, 1).to(torch.float32))
+        else:
+            target.zero_()
+            target.scatter_(1, lab.to(torch.int64).view(-1, 1), 1.0)
+        self._forward_and_append(st, target, patient_id)
+
+    @torch.no_grad()
+    def indexed(self, dataset, index, patient_id=None) -> None:
+        """`__call__` from a device-resident dataset (device_data.DeviceDataset): one assembly launch (identity transform) into the plan's input
+        and this step's target buffer; the mask goes to a scratch plane nothing reads."""
+        st = self.model.compiled(len(index), dataset.H, dataset.W)
+        dev = st.x.data.device
+        target = self._target_buffer(st.N, dev)
+        if self._scratch is None or self._scratch.shape != (st.N, 1, st.H, st.W) or self._scratch.device != dev:
+            self._scratch = torch.empty(st.N, 1, st.H, st.W, dtype=torch.float32, device=dev)
+        dataset.assemble(index, None, n_onehot=0 if self.binary else 3, out=(st.x.data, self._scratch, target))
+        self._forward_and_append(st, target, patient_id)
+
+    @torch.no_grad()
+    def append_outputs(self, outputs: torch.Tensor, target: torch.Tensor, patient_id=None) -> None:
+        """The one launch behind the forward, on (N, n) outputs and (N, n) targets that are already on the device (fp32, contiguous)."""
+        import ctypes as C
+        N, n = outputs.shape
+        if outputs.dtype != torch.float32 or target.dtype != torch.float32 or not outputs.is_contiguous() or not target.is_contiguous() \
+                or tuple(target.shape) != (N, n):
+            raise ValueError("FusedClsTestStep: outputs and targets must be contiguous fp32 (N, n) tensors of one shape")
+        self._buffers(outputs.device)
+        a = L.ClsTestRowsArgs()
+        a.cls_out, a.target, a.N, a.n_logits = outputs.data_ptr(), target.data_ptr(), N, n
+        a.rows, a.state, a.capacity = self._rows.data_ptr(), self._state.data_ptr(), self.capacity
+        L.check(L.load().mtbc_cls_test_rows(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "cls_test_rows")
+        first = len(self._ids)
+        self._ids += list(range(first, first + N)) if patient_id is None else FusedTestStep._as_list(patient_id, N)
+
+    def result(self) -> List[dict]:
+        if self._state is None or not self._ids:
+            raise L.MtbcError("FusedClsTestStep.result() before any batch was evaluated")
+        err = self._coop_err
+        flat = torch.cat([self._rows.flatten(), self._state, (err if err is not None else self._state[:1] * 0).to(torch.int32).flatten()]).cpu().numpy()
+        if flat[-1] != 0:
+            L.raise_coop_timeout()
+        cursor, dropped = int(flat[-3]), int(flat[-2])
+        if dropped or cursor > self.capacity or cursor != len(self._ids):
+            raise L.MtbcError(f"classification test rows: {cursor} images since reset() but capacity = {self.capacity} rows ({dropped} batches dropped): "
+                              f"build the FusedClsTestStep with a larger capacity")
+        self.table = flat[:cursor * 2].reshape(cursor, 2).astype(np.int64)      # the integers behind the rows
+        return cls_rows_from_table(self.table, self._ids)
+
+    def write_csv(self, path: str, rows: Optional[List[dict]] = None) -> None:
+        write_cls_rows_csv(path, self.result() if rows is None else rows)
+
+    def report(self, rows: Optional[List[dict]] = None) -> Dict[str, float]:
+        rows = self.result() if rows is None else rows
+        return classification_report([r["ground_truth"] for r in rows], [r["predicted_label"] for r in rows],
+                                     labels=(0, 1) if self.binary else (0, 1, 2))

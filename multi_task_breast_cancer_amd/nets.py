@@ -1,6 +1,7 @@
-"""MTnnUNet, MTUNetPlusPlus and the single-task nnUNet as thin nn.Module shells over HIP step programs.
+"""MTnnUNet, MTUNetPlusPlus, the single-task nnUNet and the single-task classifiers as thin nn.Module shells over HIP step programs.
 
-Drop-in surface: `model(x) -> (logits, segs)` (lists under deep supervision; nnUNet: the list of heads alone), `.parameters()`,
+Drop-in surface: `model(x) -> (logits, segs)` (lists under deep supervision; nnUNet: the list of heads alone; nnUNetClassifier /
+UNetPlusPlusClassifier: the (N, n_classes) tensor alone), `.parameters()`,
 `.state_dict()` with the reference's key names (src/models/multitask/MTnnUNet.py:79-132,
 MTUNetPlusPlus.py:47-87 on MONAI 1.3.0 blocks), `.train()`, `.to()`.  All arithmetic runs in
 libmtbc_hip.so; there is no torch / CPU fallback -- forward on a CPU tensor raises.
@@ -101,6 +102,77 @@ def _mtnnunet_params(sequences: int, regions: int, n_classes: int) -> List[Tuple
     return out
 
 
+NNUNET_CLS_UNTRAINED = tuple(f"decoder{i}.ConvInNormLRelu{j}.Conv.weight" for i in (4, 3, 2, 1) for j in (1, 2))
+
+
+def _nnunet_classifier_params(sequences: int, n_classes: int) -> List[Tuple[str, torch.Tensor]]:
+    """nnUNetClassifier (src/models/classification/nnUNet_classifier.py:85-130), in ITS draw order: the eleven level blocks (decoder4 .. decoder1
+    too, which its forward never reads), upsample5 alone, the kaiming re-initialisation of the Conv2d modules that exist so far (:117), then the
+    head with torch's default initialisation.  No upsample4 .. 1 and no output heads are drawn, so a filtered `_nnunet_params` would leave the
+    global RNG elsewhere."""
+    w = NNUNET_WIDTHS
+    out: List[Tuple[str, torch.Tensor]] = []
+    conv_names: List[str] = []
+
+    def level(name, cin, cmid, cout):
+        for cell, (a, b) in (("ConvInNormLRelu1", (cin, cmid)), ("ConvInNormLRelu2", (cmid, cout))):
+            out.append((f"{name}.{cell}.Conv.weight", _draw_conv(a, b, 3, False)[0]))
+            conv_names.append(f"{name}.{cell}.Conv.weight")
+
+    level("encoder1", sequences, w[0], w[0])
+    for i in range(1, 5):
+        level(f"encoder{i + 1}", w[i - 1], w[i], w[i])
+    level("bottleneck", w[4], w[4], w[4])
+    level("decoder5", 2 * w[4], w[3], w[3])
+    level("decoder4", 2 * w[3], w[2], w[2])
+    level("decoder3", 2 * w[2], w[1], w[1])
+    level("decoder2", 2 * w[1], w[0], w[0])
+    level("decoder1", 2 * w[0], w[0], w[0] // 2)
+    wt, b = _draw_convT(w[4], w[4], 2)
+    out += [("upsample5.weight", wt), ("upsample5.bias", b)]
+    d = dict(out)
+    for nm in conv_names:
+        nn.init.kaiming_normal_(d[nm], nonlinearity="leaky_relu")
+    out.append(("process_encoder_5.Conv.weight", _draw_conv(w[4], w[4], 3, False)[0]))
+    out.append(("process_decoder_5.Conv.weight", _draw_conv(w[3], w[4], 3, False)[0]))
+    out.append(("classifier.0.Conv.weight", _draw_conv(3 * w[4], 512, 3, False)[0]))
+    wt, b = _draw_linear(512, 256)
+    out += [("classifier.3.weight", wt), ("classifier.3.bias", b)]
+    wt, b = _draw_linear(256, n_classes)
+    out += [("classifier.5.weight", wt), ("classifier.5.bias", b)]
+    return out
+
+
+def _unetpp_classifier_params(in_ch: int, n_classes: int) -> List[Tuple[str, torch.Tensor]]:
+    """UNetPlusPlusClassifier (src/models/classification/UnetPlusPlus_Classifier.py): conv_0_0 .. conv_4_0, upcat_3_1, process_level_3, classifier,
+    drawn in the constructor's order with MONAI 1.3.0's TwoConv / Down / UpCat (as `_unetpp_params` restates them)."""
+    f = UNETPP_FEATURES
+    out: List[Tuple[str, torch.Tensor]] = []
+
+    def convolution(name, cin, cout):
+        wt, b = _draw_conv(cin, cout, 3, True)
+        out.extend([(f"{name}.conv.weight", wt), (f"{name}.conv.bias", b),
+                    (f"{name}.adn.N.weight", torch.ones(cout)), (f"{name}.adn.N.bias", torch.zeros(cout))])
+
+    def two_conv(name, cin, cout):
+        convolution(f"{name}.conv_0", cin, cout)
+        convolution(f"{name}.conv_1", cout, cout)
+
+    two_conv("conv_0_0", in_ch, f[0])
+    for i in range(1, 5):
+        two_conv(f"conv_{i}_0.convs", f[i - 1], f[i])
+    wt, b = _draw_convT(f[4], f[4] // 2, 2)
+    out.extend([("upcat_3_1.upsample.deconv.weight", wt), ("upcat_3_1.upsample.deconv.bias", b)])
+    two_conv("upcat_3_1.convs", f[3] + f[4] // 2, f[3])
+    two_conv("process_level_3.convs", f[3], f[4])
+    two_conv("classifier.0", f[4] * 3, 512)
+    wt, b = _draw_linear(512, 256)
+    out += [("classifier.3.weight", wt), ("classifier.3.bias", b)]
+    wt, b = _draw_linear(256, n_classes)
+    out += [("classifier.5.weight", wt), ("classifier.5.bias", b)]
+    return out
+
+
 def _unetpp_params(in_ch: int, out_ch: int, n_classes: int) -> List[Tuple[str, torch.Tensor]]:
     f = UNETPP_FEATURES
     out: List[Tuple[str, torch.Tensor]] = []
@@ -148,9 +220,11 @@ def _unetpp_params(in_ch: int, out_ch: int, n_classes: int) -> List[Tuple[str, t
 # ----------------------------------------------------------------------------------------------
 # Forward graphs (emit ops into a StepPlan)
 # ----------------------------------------------------------------------------------------------
-def _graph_nnunet_parts(plan: StepPlan, x: Act, classifier: bool):
+def _graph_nnunet_parts(plan: StepPlan, x: Act, classifier: bool, segmentation: bool = True):
     """nnUNet2021 (classifier=False: logits is None) and MTnnUNet, which is the same graph plus process_encoder_5, process_decoder_5,
-    classifier.*, GAP and the two Linear layers -- emitted between the decoder and the deep-supervision heads, where they always were."""
+    classifier.*, GAP and the two Linear layers -- emitted between the decoder and the deep-supervision heads, where they always were.
+    segmentation=False is nnUNetClassifier (nnUNet_classifier.py:141-171): the graph up to decoder5, the head, and -- with more than two classes --
+    the output softmax; nothing after decoder5 is emitted and the list of heads is empty."""
     w = NNUNET_WIDTHS
 
     def cell(inputs, cout, name):
@@ -175,7 +249,7 @@ def _graph_nnunet_parts(plan: StepPlan, x: Act, classifier: bool):
     dec_out = {5: w[3], 4: w[2], 3: w[1], 2: w[0], 1: w[0] // 2}
     dec_mid = {5: w[3], 4: w[2], 3: w[1], 2: w[0], 1: w[0]}
     dec, d, up = {}, None, up5
-    for i in (5, 4, 3, 2, 1):
+    for i in ((5, 4, 3, 2, 1) if segmentation else (5,)):
         if i != 5:
             up = plan.convT(d, w[i - 1], 2, f"upsample{i}.weight", f"upsample{i}.bias", f"up{i}")
         d = level([enc[i - 1], up], dec_mid[i], dec_out[i], f"decoder{i}")
@@ -189,6 +263,9 @@ def _graph_nnunet_parts(plan: StepPlan, x: Act, classifier: bool):
         h = plan.linear(g, 256, "classifier.3.weight", "classifier.3.bias", True, "fc1")
         n_cls = plan.pv("classifier.5.weight").shape[0]
         logits = plan.linear(h, n_cls, "classifier.5.weight", "classifier.5.bias", False, "logits")
+    if not segmentation:
+        plan.acts["logits"] = logits                    # what the softmax reads, for parity probes
+        return (plan.softmax(logits, "probabilities") if logits.C > 2 else logits), []
     regions = plan.pv("output1.weight").shape[0]
     # deep-supervision heads: ConvT(k = 8 / 4 / 2) + 1x1 conv with nothing in between -> one transposed conv with the
     # combined weights (StepPlan.convT_head); MTBC_NOFUSE_HEADS=1 keeps the reference's two layers (A/B, parity check)
@@ -215,7 +292,13 @@ def _graph_nnunet(plan: StepPlan, x: Act):
     return _graph_nnunet_parts(plan, x, False)
 
 
-def _graph_unetpp(plan: StepPlan, x: Act):
+def _graph_nnunet_classifier(plan: StepPlan, x: Act):
+    return _graph_nnunet_parts(plan, x, True, segmentation=False)
+
+
+def _graph_unetpp(plan: StepPlan, x: Act, segmentation: bool = True):
+    """MTUNetPlusPlus; segmentation=False is UNetPlusPlusClassifier (UnetPlusPlus_Classifier.py): conv_*_0, upcat_3_1, process_level_3 (planned once
+    over the batch pair, as here) and the classifier, raw logits (its softmax is commented out), an empty list of heads."""
     f = UNETPP_FEATURES
 
     def convolution(inputs, cout, name):
@@ -233,8 +316,24 @@ def _graph_unetpp(plan: StepPlan, x: Act):
         up = plan.convT(t, up_c, 2, f"{name}.upsample.deconv.weight", f"{name}.upsample.deconv.bias", f"{name}.up")
         return two_conv(list(skips) + [up], cout, f"{name}.convs")
 
+    def head(x30, x40, x31):
+        plan.maxpool(x31, "process_level_3.poolb", out=p31)
+        pa, pb = plan.split_batch(two_conv([pl3_in], f[4], "process_level_3.convs"))      # shared weights, both applications in one pass (F10)
+        feat = two_conv([pa, x40, pb], 512, "classifier.0")
+        g = plan.gap(feat, "gap")
+        h = plan.linear(g, 256, "classifier.3.weight", "classifier.3.bias", True, "fc1")
+        n_cls = plan.pv("classifier.5.weight").shape[0]
+        return plan.linear(h, n_cls, "classifier.5.weight", "classifier.5.bias", False, "logits")
+
     x00 = two_conv([x], f[0], "conv_0_0")
     x10 = down(x00, f[1], "conv_1_0")
+    if not segmentation:
+        x20 = down(x10, f[2], "conv_2_0")
+        x30 = down(x20, f[3], "conv_3_0")
+        pl3_in, (p30, p31) = plan.batch_pair("process_level_3.in", f[3], x30.H // 2, x30.W // 2)
+        x40 = two_conv([plan.maxpool(x30, "conv_4_0.pool", out=p30)], f[4], "conv_4_0.convs")
+        x31 = upcat(x40, [x30], f[3], "upcat_3_1")
+        return head(x30, x40, x31), []
     x01 = upcat(x10, [x00], f[0], "upcat_0_1", halves=False)
     x20 = down(x10, f[2], "conv_2_0")
     x11 = upcat(x20, [x10], f[1], "upcat_1_1")
@@ -255,14 +354,11 @@ def _graph_unetpp(plan: StepPlan, x: Act):
     regions = plan.pv("final_conv_0_1.weight").shape[0]
     outs = [plan.conv1x1(t, regions, f"final_conv_0_{j}.weight", f"final_conv_0_{j}.bias", f"final_conv_0_{j}")
             for j, t in ((1, x01), (2, x02), (3, x03), (4, x04))]
-    plan.maxpool(x31, "process_level_3.poolb", out=p31)
-    pa, pb = plan.split_batch(two_conv([pl3_in], f[4], "process_level_3.convs"))      # shared weights, both applications in one pass (F10)
-    feat = two_conv([pa, x40, pb], 512, "classifier.0")
-    g = plan.gap(feat, "gap")
-    h = plan.linear(g, 256, "classifier.3.weight", "classifier.3.bias", True, "fc1")
-    n_cls = plan.pv("classifier.5.weight").shape[0]
-    logits = plan.linear(h, n_cls, "classifier.5.weight", "classifier.5.bias", False, "logits")
-    return logits, outs
+    return head(x30, x40, x31), outs
+
+
+def _graph_unetpp_classifier(plan: StepPlan, x: Act):
+    return _graph_unetpp(plan, x, segmentation=False)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -284,7 +380,7 @@ class CompiledStep:
         self.logits, self.segs = net._graph(plan, self.x)
         self.mask = self.onehot = None
         if fused_loss is not None:
-            self.mask = plan.alloc(N, self.segs[0].C, H, W)
+            self.mask = plan.alloc(N, self.segs[0].C, H, W) if self.segs else None            # a classification-only model reads no mask
             self.onehot = plan.alloc(N, self.logits.C) if self.logits is not None else None      # a segmentation-only model has no class target
             heads = self.segs if net.deep_supervision_outputs else self.segs[-1:]
             self.loss_scale = float(fused_loss.get("loss_scale", net.loss_scale))     # baked into the loss ops; 1.0 under a dynamic scale (the device word carries it)
@@ -310,7 +406,8 @@ class CompiledStep:
         self.ready = sorted((max(s.ready_at, 0), s.name) for s in net.slots.values())
         # ... snapshotted per compiled step: net.slots is plan-time scratch that the NEXT StepPlan resets and rewrites
         # (another batch size, an evaluation step), and backward op indices are shape-dependent
-        self.slot_ready = [(net.slots[n].offset, net.slots[n].numel, max(net.slots[n].ready_at, 0)) for n in net._order]
+        # in LAYOUT order, which is `_order` unless never-trained parameters were moved behind the live ones
+        self.slot_ready = sorted((net.slots[n].offset, net.slots[n].numel, max(net.slots[n].ready_at, 0)) for n in net._order)
         self.buckets = None                     # trainer.plan_buckets(...) of this step, built on first use
 
 
@@ -318,7 +415,10 @@ class HipMultiTaskNet(nn.Module):
     architecture = ""
 
     def __init__(self, named_params: List[Tuple[str, torch.Tensor]], in_channels: int, deep_supervision: bool,
-                 graph: Callable, force_direct: bool = False):
+                 graph: Callable, force_direct: bool = False, untrained: Sequence[str] = ()):
+        """`untrained`: parameters the forward never reads (nnUNetClassifier's decoder4 .. decoder1).  They keep their place in `parameters()` /
+        `state_dict()` (the reference's order) but lie BEHIND the live parameters in the flat buffers, so that the fused optimizers' one launch
+        over the prefix [0, live_numel) leaves them -- and their optimizer state -- untouched, as torch's optimizers skip a `.grad` of None."""
         super().__init__()
         self.compute = 0          # 3x3-conv MFMA operand type: 0 fp32 (reference arithmetic), 1 bf16, 2 fp16; set_compute()
         self.loss_scale = 1.0     # fused step only: dL is multiplied by this, Adam's grad_scale divides it out (fp16: 65536)
@@ -330,11 +430,18 @@ class HipMultiTaskNet(nn.Module):
         self.force_direct = force_direct
         self.slots: Dict[str, ParamSlot] = {}
         self._order: List[str] = []
+        self.untrained = frozenset(untrained)
+        assert self.untrained <= {n for n, _ in named_params}
         off = 0
+        for dead in (False, True):                   # live parameters first, in construction order; then the never-trained ones
+            if dead:
+                self.live_numel = off
+            for name, t in named_params:
+                if (name in self.untrained) == dead:
+                    self.slots[name] = ParamSlot(name, tuple(t.shape), off)
+                    off += (t.numel() + 3) // 4 * 4          # 16-byte aligned slots (float4 Adam, 16-B weight loads)
         for name, t in named_params:
-            self.slots[name] = ParamSlot(name, tuple(t.shape), off)
             self._order.append(name)
-            off += (t.numel() + 3) // 4 * 4          # 16-byte aligned slots (float4 Adam, 16-B weight loads)
             node = self
             parts = name.split(".")
             for part in parts[:-1]:
@@ -405,10 +512,10 @@ class HipMultiTaskNet(nn.Module):
         self._steps.clear()
 
     def grads_as_views(self) -> None:
-        """Point every p.grad at its slot of the flat gradient buffer (fused-step path)."""
+        """Point every p.grad at its slot of the flat gradient buffer (fused-step path); a never-trained parameter's stays None."""
         params = self._named()
         for name in self._order:
-            params[name].grad = self._grad_view(name)
+            params[name].grad = None if name in self.untrained else self._grad_view(name)
 
     def _coop_state(self) -> torch.Tensor:
         """The cooperative InstanceNorm kernels' mailbox / error-word block of THIS model on its current device: every
@@ -461,6 +568,8 @@ class HipMultiTaskNet(nn.Module):
         outs = _NetFunction.apply(self, st, x, *params)
         if st.logits is None:                   # segmentation only: the list of heads (nnUNet.py:168)
             return list(outs)
+        if not st.segs:                         # classification only: the (N, n_classes) tensor itself (nnUNet_classifier.py:171)
+            return outs[0]
         logits, segs = outs[0], list(outs[1:])
         if self.deep_supervision_outputs:
             return [logits], segs
@@ -498,7 +607,7 @@ class _NetFunction(torch.autograd.Function):
         else:
             st.logits.grad.view(st.N, -1).copy_(dlogits)
         st.programs["bwd"].run()
-        grads = [net._grad_view(n) for n in net._order]
+        grads = [None if n in net.untrained else net._grad_view(n) for n in net._order]
         return (None, None, None, *grads)
 
 
@@ -534,3 +643,32 @@ class nnUNet(HipMultiTaskNet):
     def __init__(self, sequences: int, regions: int, force_direct: bool = False):
         super().__init__(_nnunet_params(sequences, regions), sequences, True, _graph_nnunet, force_direct)
         self.n_classes = 0
+
+
+class nnUNetClassifier(HipMultiTaskNet):
+    """src/models/classification/nnUNet_classifier.py:75-171, the single-task classification baseline: MTnnUNet's graph up to decoder5 plus its
+    classification head.  `forward(x)` returns ONE (N, n_classes) tensor: the raw logit of the binary head (n_classes == 2), else
+    softmax(logits, dim=1) (:168-169) -- the reference's criterion then applies cross_entropy to those probabilities, and so does the fused step.
+    decoder4 .. decoder1 are parameters the forward never reads (`untrained`): their `.grad` stays None and no optimizer moves them."""
+    architecture = "nnUNetClassifier"
+
+    def __init__(self, sequences: int, n_classes: int = 3, force_direct: bool = False):
+        ncls = 1 if n_classes == 2 else n_classes
+        super().__init__(_nnunet_classifier_params(sequences, ncls), sequences, False, _graph_nnunet_classifier, force_direct,
+                         untrained=NNUNET_CLS_UNTRAINED)
+        self.n_classes = ncls
+        self.cls_only = True
+
+
+class UNetPlusPlusClassifier(HipMultiTaskNet):
+    """src/models/classification/UnetPlusPlus_Classifier.py: MTUNetPlusPlus's conv_*_0, upcat_3_1, process_level_3 and classifier; raw logits (the
+    reference has its softmax commented out); every parameter is used."""
+    architecture = "UNetPlusPlusClassifier"
+
+    def __init__(self, spatial_dims: int = 2, in_channels: int = 1, n_classes: int = 3, force_direct: bool = False):
+        if spatial_dims != 2:
+            raise ValueError("only spatial_dims=2 is on the hot path")
+        ncls = 1 if n_classes == 2 else n_classes
+        super().__init__(_unetpp_classifier_params(in_channels, ncls), in_channels, False, _graph_unetpp_classifier, force_direct)
+        self.n_classes = ncls
+        self.cls_only = True

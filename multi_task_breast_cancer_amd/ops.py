@@ -826,6 +826,48 @@ def focal(x, t, alpha=1.0, gamma=2.0, weight=None, gscale=1.0):
     return loss, dx
 
 
+def softmax_args(N: int, Cc: int, backward: bool, x=None, p=None, dp=None, dz=None, into: Optional["L.SoftmaxArgs"] = None) -> "L.SoftmaxArgs":
+    """mtbc_softmax_args of one call, the only place that fills it: x / p / dp / dz are addresses (device ones for mtbc_softmax_rows and the plan op,
+    host ones for mtbc_softmax_rows_host).  `into`: the struct inside a step-program op."""
+    a = L.SoftmaxArgs() if into is None else into
+    a.N, a.C, a.backward = N, Cc, int(bool(backward))
+    a.x, a.p, a.dp, a.dz = x, p, dp, dz
+    return a
+
+
+def softmax_rows(x):
+    """softmax over the rows of (N, C <= 3) on the device."""
+    _chk(x)
+    p = torch.empty_like(x)
+    L.check(L.load().mtbc_softmax_rows(C.byref(softmax_args(x.shape[0], x.shape[1], False, x=x.data_ptr(), p=p.data_ptr())), _s()), "softmax_rows")
+    return p
+
+
+def softmax_rows_bwd(p, dp):
+    """dz = p * (dp - sum p dp) on the device."""
+    _chk(p, dp)
+    dz = torch.empty_like(p)
+    L.check(L.load().mtbc_softmax_rows(C.byref(softmax_args(p.shape[0], p.shape[1], True, p=p.data_ptr(), dp=dp.data_ptr(), dz=dz.data_ptr())), _s()),
+            "softmax_rows_bwd")
+    return dz
+
+
+def softmax_rows_host(x, dp=None):
+    """The same row functions compiled for the host, on CPU float32 tensors (no GPU call): p, or with `dp` (p, dz)."""
+    x = x.detach().to(torch.float32).contiguous()
+    if x.device.type != "cpu" or x.dim() != 2:
+        raise ValueError("softmax_rows_host takes a CPU (N, C) tensor")
+    p = torch.empty_like(x)
+    L.check(L.load().mtbc_softmax_rows_host(C.byref(softmax_args(x.shape[0], x.shape[1], False, x=x.data_ptr(), p=p.data_ptr()))), "softmax_rows_host")
+    if dp is None:
+        return p
+    dp = dp.detach().to(torch.float32).contiguous()
+    dz = torch.empty_like(p)
+    L.check(L.load().mtbc_softmax_rows_host(C.byref(softmax_args(x.shape[0], x.shape[1], True, p=p.data_ptr(), dp=dp.data_ptr(), dz=dz.data_ptr()))),
+            "softmax_rows_host")
+    return p, dz
+
+
 def adam_step(p, g, m, v, lr, step, beta1=0.9, beta2=0.999, eps=1e-4, grad_scale=1.0, zero_grad=False):
     """Adam on the shared optimizer launch: the AdamW rule with weight_decay 0 (a decay factor of exactly 1)."""
     optim_step(L.OPT_ADAMW, p, g, m, v, lr=lr, step=step, beta1=beta1, beta2=beta2, eps=eps, weight_decay=0.0, grad_scale=grad_scale, zero_grad=zero_grad)

@@ -62,7 +62,9 @@ class _FusedFlat(torch.optim.Optimizer):
     def _args(self) -> "L.OptimArgs":
         m, g = self.model, self.param_groups[0]
         a = L.OptimArgs()
-        a.kind, a.n, a.p, a.g = self.KIND, m.flat_numel, m.flat_p.data_ptr(), m.flat_g.data_ptr()
+        # the live prefix of the flat buffers: parameters the forward never reads (nets.nnUNetClassifier's decoder4 .. 1) lie behind it and are not
+        # touched -- torch's optimizers skip a `.grad` of None, AdamW's decay included; every other model's prefix is the whole buffer
+        a.kind, a.n, a.p, a.g = self.KIND, getattr(m, "live_numel", m.flat_numel), m.flat_p.data_ptr(), m.flat_g.data_ptr()
         bufs = self._buffers()
         a.m = bufs[0].data_ptr()
         a.v = bufs[1].data_ptr() if len(bufs) > 1 else None
@@ -129,6 +131,8 @@ class _FusedFlat(torch.optim.Optimizer):
             m = self.model
             state = {}
             for i, name in enumerate(n for n, _ in m.named_parameters()):
+                if name in getattr(m, "untrained", ()):        # never stepped: torch keeps no state for it either
+                    continue
                 s = m.slots[name]
                 state[i] = {"step": torch.tensor(float(self.step_count))} if self.HAS_STEP else {}
                 for k in self.STATE:
@@ -146,7 +150,7 @@ class _FusedFlat(torch.optim.Optimizer):
         steps = set()
         for i, name in enumerate(n for n, _ in m.named_parameters()):
             st = state.get(i, state.get(str(i)))
-            if st is None:
+            if st is None or name in getattr(m, "untrained", ()):
                 continue
             s = m.slots[name]
             for k in self.STATE:

@@ -122,6 +122,24 @@ def classification_scores(conf: np.ndarray) -> Tuple[float, float]:
     return accuracy, f1w
 
 
+def cls_driver_scores(conf: np.ndarray, binary: bool) -> Tuple[float, float]:
+    """(accuracy, F1) as the classification driver computes them (training_classification.py:88-96, :152-160) from a float64 3 x 3 confusion
+    matrix, rows = ground truth.  Three classes: sklearn's accuracy_score and f1_score(labels=[0, 1, 2], average='micro') -- precision and recall
+    over the summed counts, 0 on an empty matrix.  Binary head: `accuracy_from_tensor` / `f1_score_from_tensor` (metrics.py:270-286) on the
+    {0, 1} labels -- (tp + tn) / total and 2 tp / (2 tp + fp + fn), NaN on 0 / 0 as the reference's tensor division gives."""
+    conf = np.asarray(conf, dtype=np.float64).reshape(3, 3)
+    if binary:
+        tn, fp, fn, tp = conf[0, 0], conf[0, 1], conf[1, 0], conf[1, 1]
+        total, den = tp + tn + fp + fn, 2 * tp + fp + fn
+        return (float((tp + tn) / total) if total else float("nan")), (float(2 * tp / den) if den else float("nan"))
+    total, tp = conf.sum(), np.trace(conf)
+    accuracy = float(tp / total) if total else 0.0
+    precision = tp / conf.sum(axis=0).sum() if total else 0.0
+    recall = tp / conf.sum(axis=1).sum() if total else 0.0
+    f1 = float(2 * precision * recall / (precision + recall)) if precision + recall else 0.0
+    return accuracy, f1
+
+
 def train_metrics_from_counts(table, conf) -> TrainMetrics:
     """The reference's training-time metrics from the rows the device appended: `table` (batches, 4) = tp, fp, fn, samples per batch,
     `conf` (3, 3).  Dice: the per-batch score of `dice_score_from_tensor`, summed in batch order in float64 and divided by the number of
@@ -217,6 +235,22 @@ def eval_result_from_counts(table, conf, loss_rows) -> tuple:
     return total / nb, dice / nb, accuracy, f1w, seg / nb, cls / nb
 
 
+def cls_eval_result_from_counts(table, conf, loss_rows, binary: bool) -> tuple:
+    """The classification driver's (val_loss, val_acc, val_f1) (training_classification.py:149-162) from one row per batch: the loss words' first
+    column summed in row order in float64 and divided by the number of rows, `cls_driver_scores` of the confusion matrix; a NaN word ends the run."""
+    table = np.asarray(table, dtype=np.int64).reshape(-1, 4)
+    loss_rows = np.asarray(loss_rows, dtype=np.float64).reshape(-1, 4)
+    if len(loss_rows) != len(table):
+        raise ValueError(f"{len(table)} count rows but {len(loss_rows)} loss rows")
+    total = 0.0
+    for lt, _, _, flag in loss_rows.tolist():
+        total += lt
+        if flag != 0.0:
+            exit_on_nan()
+    accuracy, f1 = cls_driver_scores(conf, binary)
+    return (total / len(table) if len(table) else 0.0), accuracy, f1
+
+
 def reduce_eval_metrics(table: torch.Tensor, conf: torch.Tensor, state: torch.Tensor, loss_rows: torch.Tensor, coop_err: Optional[torch.Tensor] = None,
                         distributed: bool = False, group=None) -> Tuple[np.ndarray, np.ndarray]:
     """`_reduce_packed` for validation: TWO host arrays, int64 [table | conf | sum cursor, sum cursor^2, sum dropped, sum coop error word] and float64
@@ -225,14 +259,17 @@ def reduce_eval_metrics(table: torch.Tensor, conf: torch.Tensor, state: torch.Te
     return _reduce_packed(table, conf, state, loss_rows, coop_err, distributed=distributed, group=group)
 
 
-def eval_result_from_packed(packed: np.ndarray, losses: np.ndarray, capacity: int, world: int = 1) -> tuple:
+def eval_result_from_packed(packed: np.ndarray, losses: np.ndarray, capacity: int, world: int = 1, cls_only: Optional[bool] = None) -> tuple:
     """`reduce_eval_metrics`' arrays -> the 6-tuple, or MtbcError (and no number) when a cooperative kernel failed on some rank, or by the rule of
-    `_decode_packed`.  Every rank holds the same sums, so every rank raises (or exits on a NaN word) or none does."""
+    `_decode_packed`.  Every rank holds the same sums, so every rank raises (or exits on a NaN word) or none does.  `cls_only` (the head is
+    binary: True / False): the classification driver's 3-tuple of `cls_eval_result_from_counts` instead."""
     if int(packed[capacity * 4 + 12]) != 0:
         L.raise_coop_timeout()
     table, conf = _decode_packed(packed, capacity, world, _EVAL)
     if len(table) == 0:
         raise L.MtbcError("FusedEvalStep.result() before any batch was evaluated")
+    if cls_only is not None:
+        return cls_eval_result_from_counts(table, conf, np.asarray(losses, dtype=np.float64)[:len(table) * 4].reshape(len(table), 4), cls_only)
     return eval_result_from_counts(table, conf, np.asarray(losses, dtype=np.float64)[:len(table) * 4].reshape(len(table), 4))
 
 
@@ -283,6 +320,31 @@ def _check_seg_only(alpha, n_classes, focal_weight, cls_criterion, distributed: 
         raise NotImplementedError(f"{owner}: data parallel is not built for segmentation-only models yet")
 
 
+def is_cls_only(model) -> bool:
+    """A single-task classification model (nets.nnUNetClassifier, nets.UNetPlusPlusClassifier): no segmentation head anywhere in its plans."""
+    return bool(getattr(model, "cls_only", False))
+
+
+def _check_cls_only(alpha, inversely_weighted, seg_criterion, distributed: bool, owner: str) -> None:
+    """What FusedTrainStep and FusedEvalStep refuse of a classification-only model (training_classification.py has no mask, no mix)."""
+    if alpha is not None and float(alpha) != 0.0:
+        raise ValueError(f"{owner}: a classification-only model has no segmentation loss to mix: alpha must be None or 0.0, got {alpha}")
+    passed = [k for k, v in (("inversely_weighted", inversely_weighted), ("seg_criterion", seg_criterion)) if v is not None]
+    if passed:
+        raise ValueError(f"{owner}: {', '.join(passed)} given, but the model has no segmentation head")
+    if distributed:
+        raise NotImplementedError(f"{owner}: data parallel is not built for classification-only models yet")
+
+
+class ClsTrainMetrics(NamedTuple):
+    """`epoch_metrics()` of a classification-only training step: the driver's (loss, acc, f1) first (training_classification.py:98)."""
+    loss: float             # mean over the batches of the step's loss
+    accuracy: float
+    f1: float               # micro over labels [0, 1, 2]; the binary head: 2 tp / (2 tp + fp + fn)
+    batches: int
+    conf: np.ndarray        # (3, 3) int64, rows = ground truth, cols = prediction
+
+
 class SegTrainMetrics(NamedTuple):
     """`epoch_metrics()` of a segmentation-only training step: the driver's (loss, dice) first (training_segmentation.py:59-62)."""
     loss: float             # mean over the batches of the step's loss
@@ -315,7 +377,10 @@ def fill_batch(st, image: torch.Tensor, mask: torch.Tensor, label: Optional[torc
         raise ValueError("a class label was given to a segmentation-only model" if label is not None else
                          "this model has a classification head: the batch needs its class labels")
     st.x.data.copy_(image, non_blocking=True)
-    st.mask.copy_(mask, non_blocking=True)
+    if st.mask is not None:                 # a classification-only plan reads no mask (training_classification.py:41)
+        st.mask.copy_(mask, non_blocking=True)
+    elif mask is not None:
+        raise ValueError("a mask was given to a classification-only model")
     if label is None:
         return
     lab = label.to(st.onehot.device, non_blocking=True).flatten()
@@ -334,6 +399,17 @@ def _target_of(step, st) -> torch.Tensor:
     t = step._scratch_target
     if t is None or t.shape[0] != st.N or t.device != st.mask.device:
         step._scratch_target = t = torch.empty(st.N, 1, dtype=torch.float32, device=st.mask.device)
+    return t
+
+
+def _mask_of(step, st) -> torch.Tensor:
+    """The mask buffer the batch-assembly launch writes (it refuses a NULL out_mask): the plan's, or -- a classification-only plan has none --
+    an (N, 1, H, W) scratch plane of the step's that nothing reads."""
+    if st.mask is not None:
+        return st.mask
+    t = step._scratch_mask
+    if t is None or t.shape != (st.N, 1, st.H, st.W) or t.device != st.x.data.device:
+        step._scratch_mask = t = torch.empty(st.N, 1, st.H, st.W, dtype=torch.float32, device=st.x.data.device)
     return t
 
 
@@ -379,6 +455,7 @@ class MetricsTable:
         self.model, self.capacity, self.eval, self.distributed = model, int(capacity), bool(validation), bool(distributed)
         self.words = _EVAL if self.eval else _TRAIN
         self.seg_only = is_seg_only(model)      # mtbc_seg_step_metrics: the same rows, no class arguments (the confusion matrix stays zero)
+        self.cls_only = is_cls_only(model)      # mtbc_cls_step_metrics: the samples launch alone (tp / fp / fn stay zero)
         self.counts = self.state = self.loss_rows = self.weight = None
         self._args = {}             # id(compiled step) -> (the step, its argument struct); None -> the empty shard's
 
@@ -405,6 +482,8 @@ class MetricsTable:
         self.buffers()
         if self.seg_only:
             return self._seg_arguments(st)
+        if self.cls_only:
+            return self._cls_arguments(st, n_logits)
         a = L.EvalMetricsArgs() if self.eval else L.TrainMetricsArgs()
         if st is None:
             a.N, a.n_seg, a.n_logits = 0, 0, n_logits
@@ -448,6 +527,27 @@ class MetricsTable:
             a.shard_weight = self.weight.data_ptr() if self.distributed else None
         return a
 
+    def _cls_arguments(self, st, n_logits):
+        """`_arguments` of a classification-only step: mtbc_cls_step_metrics_args on the model's OUTPUT; loss_in stays NULL for training."""
+        a = L.ClsStepMetricsArgs()
+        a.N, a.n_logits = 0, n_logits
+        if st is not None:
+            out = st.logits.data
+            loss_out = (st.plan.loss_out,) if self.eval else ()
+            for t in (out, st.onehot) + loss_out:
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    raise L.MtbcError(f"{self.words['kind']} metrics: the step's outputs are not contiguous fp32 buffers")
+            if out.numel() != st.onehot.numel() or any(t.numel() < 4 for t in loss_out):
+                raise L.MtbcError(f"{self.words['kind']} metrics: outputs and targets differ in size")
+            a.cls_out, a.target, a.N, a.n_logits = out.data_ptr(), st.onehot.data_ptr(), st.N, st.logits.C
+            if self.eval:
+                a.loss_in = st.plan.loss_out.data_ptr()
+        a.table, a.conf, a.state, a.capacity = self.counts.data_ptr(), self.counts.data_ptr() + self.capacity * 32, self.state.data_ptr(), self.capacity
+        if self.eval:
+            a.loss_rows = self.loss_rows.data_ptr()
+            a.shard_weight = self.weight.data_ptr() if self.distributed else None
+        return a
+
     def append(self, st, n_logits: int = 0) -> None:
         """The metrics call on the outputs (validation: and the loss words) of the step program that has just run; st = None: the empty shard, which
         only advances the cursor (`n_logits` = the head's width).  Two launches on the current stream, capturable."""
@@ -457,9 +557,10 @@ class MetricsTable:
         if ent is None or ent[0] is not st:
             self._args[key] = ent = (st, self._arguments(st, n_logits))
         lib = L.load()
-        fn = lib.mtbc_seg_step_metrics if self.seg_only else lib.mtbc_eval_metrics if self.eval else lib.mtbc_train_metrics
+        fn = lib.mtbc_seg_step_metrics if self.seg_only else lib.mtbc_cls_step_metrics if self.cls_only else lib.mtbc_eval_metrics if self.eval \
+            else lib.mtbc_train_metrics
         L.check(fn(C.byref(ent[1]), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                "seg_step_metrics" if self.seg_only else "eval_metrics" if self.eval else "train_metrics")
+                "seg_step_metrics" if self.seg_only else "cls_step_metrics" if self.cls_only else "eval_metrics" if self.eval else "train_metrics")
 
     def reduce(self, coop_err: Optional[torch.Tensor] = None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         """`_reduce_packed` of these buffers: under `distributed` one sum-all-reduce per array (row b of the sum is GLOBAL batch b), one read each."""
@@ -480,15 +581,29 @@ class FusedTrainStep:
     A segmentation-only model (nets.nnUNet) makes this the step of training_segmentation.py:29-62: no classification argument is taken (alpha,
     if given, must be 1.0), `load_batch(image, mask)` / `load_indexed` fill no class target, the loss words are [seg, seg, 0, nan_flag],
     metrics=True appends through `mtbc_seg_step_metrics`, and `epoch_metrics()` returns SegTrainMetrics, the driver's (loss, dice) first.  Data
-    parallel is not built for it."""
+    parallel is not built for it.
 
-    def __init__(self, model, optimizer, alpha: Optional[float] = None, inversely_weighted: bool = True, n_classes: Optional[int] = None,
+    A classification-only model (nets.nnUNetClassifier, nets.UNetPlusPlusClassifier) makes it the step of training_classification.py:34-98:
+    `n_classes`, `cls_criterion` and `focal_weight` as for a multi-task model, no segmentation argument is taken (alpha, if given, must be 0.0),
+    `load_batch(image, label)` / `step(image, label)` take no mask, the criterion reads the model's OUTPUT (the 3-class nnUNetClassifier's
+    probabilities), the loss words are [cls, 0, cls, nan_flag], metrics=True appends through `mtbc_cls_step_metrics`, and `epoch_metrics()`
+    returns ClsTrainMetrics, the driver's (loss, acc, f1) first.  Parameters the forward never reads are not stepped.  Data parallel is not
+    built for it."""
+
+    def __init__(self, model, optimizer, alpha: Optional[float] = None, inversely_weighted: Optional[bool] = None, n_classes: Optional[int] = None,
                  distributed: bool = False, n_buckets: int = 4, focal_weight: Optional[torch.Tensor] = None,
                  cls_criterion: Optional[str] = None, graph: Optional[bool] = None, loss_scale=None, metrics: bool = False,
-                 metrics_capacity: int = 4096, seg_criterion: str = "DICE"):
+                 metrics_capacity: int = 4096, seg_criterion: Optional[str] = None):
         # alpha is required, n_classes defaults to 3 and cls_criterion to "Focal" for a multi-task model; None = "not given", which is all a
-        # segmentation-only model accepts
+        # segmentation-only model accepts.  inversely_weighted (default True) and seg_criterion (default "DICE") likewise: None = "not given",
+        # which is all a classification-only model accepts
         self.seg_only = is_seg_only(model)
+        self.cls_only = is_cls_only(model)
+        if self.cls_only:
+            _check_cls_only(alpha, inversely_weighted, seg_criterion, distributed, "the fused step")
+            alpha = 0.0
+        inversely_weighted = True if inversely_weighted is None else inversely_weighted
+        seg_criterion = "DICE" if seg_criterion is None else seg_criterion
         if self.seg_only:
             _check_seg_only(alpha, n_classes, focal_weight, cls_criterion, distributed, "the fused step")
             alpha = 1.0
@@ -534,8 +649,9 @@ class FusedTrainStep:
             self.binary, self.cls_gamma, self.focal_weight = False, 2.0, None
         else:
             self.binary, self.cls_gamma, self.focal_weight = _check_heads(model, n_classes, cls_criterion, focal_weight, "the fused step")
-        self._epoch_loss = None         # segmentation only, metrics=True: device float64 [sum of the steps' loss, steps] behind epoch_metrics()
+        self._epoch_loss = None         # single-task models, metrics=True: device float64 [sum of the steps' loss, steps] behind epoch_metrics()
         self._scratch_target = None     # segmentation only: where the batch-assembly launch puts the labels nobody reads
+        self._scratch_mask = None       # classification only: where it puts the masks nobody reads
         self.model, self.opt = model, optimizer
         self.alpha, self.iw, self.n_classes = float(alpha), bool(inversely_weighted), n_classes
         self.distributed = distributed
@@ -575,6 +691,8 @@ class FusedTrainStep:
         global batch's."""
         N, _, H, W = image.shape
         st = self._compiled(N, H, W)
+        if self.cls_only and label is None:     # (image, label): this driver's batches carry no mask
+            mask, label = None, mask
         fill_batch(st, image, mask, label, self.binary)
         self._set_shard_weight(st, weight)
         return st
@@ -595,7 +713,7 @@ class FusedTrainStep:
         In stream order in front of the step and, with graph=True, outside the replayed region, where `load_batch` sits.  `weight` as in `load_batch`."""
         _check_in_channels(self.model, dataset)
         st = self._compiled(len(index), dataset.H, dataset.W)
-        dataset.assemble(index, params, n_onehot=0 if self.binary or self.seg_only else 3, out=(st.x.data, st.mask, _target_of(self, st)))
+        dataset.assemble(index, params, n_onehot=0 if self.binary or self.seg_only else 3, out=(st.x.data, _mask_of(self, st), _target_of(self, st)))
         self._set_shard_weight(st, weight)
         return st
 
@@ -617,7 +735,7 @@ class FusedTrainStep:
 
     def _count_loss(self, losses: torch.Tensor) -> None:
         """Segmentation only, metrics=True: the step's loss into the epoch's device sum, in stream order behind the step (outside a replayed graph)."""
-        if self.seg_only and self.metrics:
+        if (self.seg_only or self.cls_only) and self.metrics:
             if self._epoch_loss is None:
                 self._epoch_loss = torch.zeros(2, dtype=torch.float64, device=losses.device)
             self._epoch_loss[0] += losses[0].double()
@@ -627,9 +745,12 @@ class FusedTrainStep:
         """The epoch so far as the reference's numbers: under data parallel ONE sum-all-reduce of the table and the confusion matrix (row b of the sum is
         GLOBAL batch b), then ONE device-to-host read.  MtbcError when the table was too small or the ranks' cursors disagree."""
         m = train_metrics_from_packed(self._metrics_table().reduce()[0], self.metrics_capacity, self.world)
-        if not self.seg_only:
+        if not (self.seg_only or self.cls_only):
             return m
         total, steps = (0.0, 0.0) if self._epoch_loss is None else self._epoch_loss.cpu().tolist()
+        if self.cls_only:
+            accuracy, f1 = cls_driver_scores(m.conf, self.binary)
+            return ClsTrainMetrics(total / steps if steps else 0.0, accuracy, f1, m.batches, m.conf)
         return SegTrainMetrics(total / steps if steps else 0.0, m.dice, m.batches, m.table)
 
     def _apply_update(self, st) -> None:
@@ -798,12 +919,20 @@ class FusedEvalStep:
     integer rows sum to the global batch's counts exactly, the weighted loss rows to its mean losses (the criteria allowed here are means over
     samples, and total is linear in seg and cls).  The step itself issues no collective, so graph=True works under it."""
 
-    def __init__(self, model, alpha: Optional[float] = None, inversely_weighted: bool = True, n_classes: Optional[int] = None,
-                 focal_weight: Optional[torch.Tensor] = None, cls_criterion: Optional[str] = None, seg_criterion: str = "DICE",
+    def __init__(self, model, alpha: Optional[float] = None, inversely_weighted: Optional[bool] = None, n_classes: Optional[int] = None,
+                 focal_weight: Optional[torch.Tensor] = None, cls_criterion: Optional[str] = None, seg_criterion: Optional[str] = None,
                  on_device: bool = False, graph: Optional[bool] = None, distributed: bool = False, capacity: int = 4096):
         # a segmentation-only model (nets.nnUNet): `validate_one_epoch` of training_segmentation.py:65-88 -- no label, no classification argument,
         # the metrics launch is `mtbc_seg_step_metrics`, and `result()` is the driver's (val_loss, val_dice)
+        # a classification-only model (nets.nnUNetClassifier / UNetPlusPlusClassifier): `validate_one_epoch` of training_classification.py:101-162 --
+        # `step(image, label)`, no segmentation argument, the metrics launch is `mtbc_cls_step_metrics`, `result()` is (val_loss, val_acc, val_f1)
         self.seg_only = is_seg_only(model)
+        self.cls_only = is_cls_only(model)
+        if self.cls_only:
+            _check_cls_only(alpha, inversely_weighted, seg_criterion, distributed, "FusedEvalStep")
+            alpha = 0.0
+        inversely_weighted = True if inversely_weighted is None else inversely_weighted
+        seg_criterion = "DICE" if seg_criterion is None else seg_criterion
         if self.seg_only:
             _check_seg_only(alpha, n_classes, focal_weight, cls_criterion, distributed, "FusedEvalStep")
             alpha = 1.0
@@ -812,7 +941,7 @@ class FusedEvalStep:
                 raise TypeError("FusedEvalStep: alpha (the weight of the segmentation loss in the mix) is required for a multi-task model")
             n_classes = 3 if n_classes is None else n_classes
             cls_criterion = "Focal" if cls_criterion is None else cls_criterion
-        self._scratch_target = None
+        self._scratch_target = self._scratch_mask = None
         self.model, self.alpha, self.iw, self.n_classes = model, float(alpha), bool(inversely_weighted), n_classes
         self.on_device, self.distributed, self.capacity = bool(on_device), bool(distributed), int(capacity)
         if self.distributed and not self.on_device:
@@ -852,6 +981,8 @@ class FusedEvalStep:
         """`weight`: this rank's share n_local / n_batch of the global batch (distributed=True; None = 1)."""
         N, _, H, W = image.shape
         st = self._compiled(N, H, W)
+        if self.cls_only and label is None:     # (image, label): this driver's batches carry no mask
+            mask, label = None, mask
         fill_batch(st, image, mask, label, self.binary)
         self._evaluate_resident(st, weight)
 
@@ -864,7 +995,7 @@ class FusedEvalStep:
         transform), then the same step program and the same device accumulators.  `weight` as in `__call__`."""
         _check_in_channels(self.model, dataset)
         st = self._compiled(len(index), dataset.H, dataset.W)
-        dataset.assemble(index, None, n_onehot=0 if self.binary or self.seg_only else 3, out=(st.x.data, st.mask, _target_of(self, st)))
+        dataset.assemble(index, None, n_onehot=0 if self.binary or self.seg_only else 3, out=(st.x.data, _mask_of(self, st), _target_of(self, st)))
         self._evaluate_resident(st, weight)
 
     def _evaluate_resident(self, st, weight: Optional[float]) -> None:
@@ -884,6 +1015,10 @@ class FusedEvalStep:
         if self._acc is None:
             self._acc = torch.zeros(5, dtype=torch.float64, device=dev)
             self._conf = torch.zeros(3, 3, dtype=torch.int64, device=dev)
+        if self.cls_only:               # no segmentation head: the loss words and the confusion matrix
+            self._acc[:3] += st.plan.loss_out[:3].double()
+            self._acc[4] += 1
+            return self._count_classes(st, gt_binary)
         counts = dice_counts(st.segs[-1].data, st.mask)                 # {tp, fp, fn} float64 on the device
         tp, fp, fn = counts[0], counts[1], counts[2]
         empty_gt = (tp + fn) == 0
@@ -894,7 +1029,10 @@ class FusedEvalStep:
         self._acc[4] += 1
         if self.seg_only:
             return
-        logit = st.logits.data.view(N, -1)
+        self._count_classes(st, gt_binary)
+
+    def _count_classes(self, st, gt_binary: Optional[torch.Tensor]) -> None:
+        logit = st.logits.data.view(st.N, -1)
         if self.binary:
             pred = (torch.sigmoid(logit[:, 0]) > 0.5).to(torch.int64)
             gt = gt_binary
@@ -936,7 +1074,7 @@ class FusedEvalStep:
         if self._acc is None and (self._table is None or self._table.counts is None):
             raise L.MtbcError("FusedEvalStep.result() before any batch was evaluated")
         if self.on_device:
-            r = eval_result_from_packed(*self._table.reduce(self._coop_err), self.capacity, self.world)
+            r = eval_result_from_packed(*self._table.reduce(self._coop_err), self.capacity, self.world, cls_only=self.binary if self.cls_only else None)
             return (r[0], r[1]) if self.seg_only else r
         err = self._coop_err
         if err is not None and int(err.item()) != 0:
@@ -946,6 +1084,8 @@ class FusedEvalStep:
         nb = max(acc[4], 1.0)
         if self.seg_only:               # training_segmentation.py:88
             return acc[0] / nb, acc[3] / nb
+        if self.cls_only:               # training_classification.py:162
+            return (acc[0] / nb, *cls_driver_scores(conf, self.binary))
         accuracy, f1w = classification_scores(conf)       # sklearn accuracy_score / f1_score(labels=[0,1,2], average='weighted') (:155-156)
         return acc[0] / nb, acc[3] / nb, accuracy, f1w, acc[1] / nb, acc[2] / nb
 
@@ -956,6 +1096,8 @@ def validate_one_epoch(step: FusedEvalStep, loader, device) -> tuple:
     for data in loader:
         if getattr(step, "seg_only", False):
             step(data["image"].to(device), data["mask"].to(device))
+        elif getattr(step, "cls_only", False):
+            step(data["image"].to(device), data["label"].to(device))
         else:
             step(data["image"].to(device), data["mask"].to(device), data["label"].to(device))
     return step.result()
@@ -1022,6 +1164,8 @@ def train_one_epoch_with_metrics(step: FusedTrainStep, dataset, tables, lr: Opti
     m = step.epoch_metrics()
     if getattr(step, "seg_only", False):        # training_segmentation.py:62
         return total, m.dice
+    if getattr(step, "cls_only", False):        # training_classification.py:98
+        return total, m.accuracy, m.f1
     return total, m.dice, m.accuracy, m.f1
 
 
@@ -1064,7 +1208,16 @@ def fit_fold(step: FusedTrainStep, eval_step: FusedEvalStep, dataset, train_inde
     (:179) and writes its mean DICE into the row; metrics.csv gets the header `epoch,LR,Train,Validation,Test,Train_loss,Val_loss` and the
     row of :192-195 (the learning rate AFTER the scheduler step); the rows returned are (epoch, lr, train_dice, val_dice, test_dice,
     train_loss, val_loss).  Rotation: that driver draws ONE bound d = np.random.choice(range(0, 360)) per run (:118) and rotates by
-    U(-d, d): pass transforms={"horizontal_flip": .5, "vertical_flip": .5, "rotation": d / 360}."""
+    U(-d, d): pass transforms={"horizontal_flip": .5, "vertical_flip": .5, "rotation": d / 360}.
+
+    With the classification pair of steps (both built on a nets.nnUNetClassifier / UNetPlusPlusClassifier) it is the epoch loop of
+    training_classification.py:216-271: metrics.csv gets the header `epoch,LR,Train_loss,Validation_loss,Train_acc,Train_F1,Validation_acc,
+    Validation_F1` and the row of :262-266 (the learning rate at the START of the epoch); the rows returned are (epoch, lr, train_loss, val_loss,
+    train_acc, train_f1, val_acc, val_f1).  That driver's testing phase runs once, after the loop (:284-298): `test_one_epoch_indexed` with an
+    inference.FusedClsTestStep; `test_step` / `test_index` are not used here."""
+    if getattr(step, "cls_only", False) or getattr(eval_step, "cls_only", False):
+        return _fit_fold_classification(step, eval_step, dataset, train_index, val_index, scheduler, run_dir, epochs, max_patience, transforms,
+                                        seed, plateau, checkpoint_name)
     if getattr(step, "seg_only", False) or getattr(eval_step, "seg_only", False):
         return _fit_fold_segmentation(step, eval_step, test_step, dataset, train_index, val_index, test_index, scheduler, run_dir, epochs,
                                       max_patience, transforms, seed, plateau, checkpoint_name)
@@ -1126,10 +1279,17 @@ def fit_fold(step: FusedTrainStep, eval_step: FusedEvalStep, dataset, train_inde
 
 def test_one_epoch_indexed(test_step, dataset, tables) -> list:
     """The testing phase of the segmentation driver from a device-resident dataset: the batches of `tables` (no transforms) through an
-    inference.FusedSegTestStep; the rows of results_segmentation.csv, read back once."""
+    inference.FusedSegTestStep; the rows of results_segmentation.csv, read back once.  With an inference.FusedClsTestStep: the classification
+    driver's testing phase, the (ground_truth, predicted_label) rows of its results.csv."""
     _check_tables(dataset, tables)
     _check_in_channels(test_step.model, dataset)
     test_step.reset()
+    if getattr(test_step, "cls_only", False):
+        for b in range(len(tables)):
+            index, _, n_local, _ = tables.batch(b)
+            if n_local:
+                test_step.indexed(dataset, index)
+        return test_step.result()
     scratch = None
     for b in range(len(tables)):
         index, _, n_local, _ = tables.batch(b)
@@ -1187,6 +1347,51 @@ def _fit_fold_segmentation(step, eval_step, test_step, dataset, train_index, val
         row = (epoch, lr, train_dice, val_dice, test_dice, train_loss, val_loss)
         rows.append(row)
         CK.write_metrics_file(metrics_path, CK.seg_metrics_row(*row))
+        if stopper.should_stop:
+            logging.info(f"\nValidation loss did not improve over the last {stopper.patience} epochs. Stopping training")
+            break
+    return rows
+
+
+def _fit_fold_classification(step, eval_step, dataset, train_index, val_index, scheduler, run_dir, epochs, max_patience, transforms, seed, plateau,
+                             checkpoint_name) -> List[tuple]:
+    """`fit_fold` for the classification pair of steps: training_classification.py:216-271."""
+    import logging
+    import time
+    from . import checkpoint as CK
+    from .device_data import EpochTables
+    if not (getattr(step, "cls_only", False) and getattr(eval_step, "cls_only", False)):
+        raise ValueError("fit_fold: the training and the evaluation step must both be built on a classification-only model, or neither")
+    os.makedirs(run_dir, exist_ok=True)
+    metrics_path = os.path.join(run_dir, "metrics.csv")
+    CK.write_metrics_file(metrics_path, CK.CLS_METRICS_HEADER)
+    stopper = CK.EarlyStopping(max_patience)
+    val_tables = EpochTables(val_index, 0, None, device=dataset.device)
+    rows = []
+    for epoch in range(int(epochs)):
+        current_lr = step.opt.param_groups[0]["lr"]
+        t0 = time.perf_counter()
+        tables = EpochTables(train_index, epoch, transforms, seed=seed, device=dataset.device)
+        train_loss, train_acc, train_f1 = train_one_epoch_with_metrics(step, dataset, tables)
+        val_loss, val_acc, val_f1 = validate_one_epoch_indexed(eval_step, dataset, val_tables)
+        if plateau:
+            scheduler.step(val_loss)
+        else:
+            scheduler.step()
+        if stopper.update(val_loss):
+            CK.save_checkpoint(os.path.join(run_dir, checkpoint_name), epoch, step.model, step.opt, val_loss, scaler=step.scaler)
+        logging.info(f'EPOCH {epoch} --> '
+                     f'|| Training loss {train_loss:.4f} '
+                     f'|| Validation loss {val_loss:.4f} '
+                     f'|| Training ACC {train_acc:.4f} '
+                     f'|| Training F1 {train_f1:.4f} '
+                     f'|| Validation ACC {val_acc:.4f} '
+                     f'|| Validation F1 {val_f1:.4f} '
+                     f'|| Patience: {stopper.patience} '
+                     f'|| Epoch time: {time.perf_counter() - t0:.4f}')
+        row = (epoch, current_lr, train_loss, val_loss, train_acc, train_f1, val_acc, val_f1)
+        rows.append(row)
+        CK.write_metrics_file(metrics_path, CK.cls_metrics_row(*row))
         if stopper.should_stop:
             logging.info(f"\nValidation loss did not improve over the last {stopper.patience} epochs. Stopping training")
             break
