@@ -373,6 +373,27 @@ typedef struct {
 int mtbc_maxpool2_fwd(const mtbc_maxpool_args* a, void* stream);
 int mtbc_maxpool2_bwd(const mtbc_maxpool_args* a, void* stream);
 
+/* --------------------------------------------------------------------- Upsample(scale_factor=2, mode="nearest")
+ * replaces nn.Upsample(scale_factor=2, mode="nearest"): Multi_BTS_UNet.py:100,154-158.
+ *   fwd  y[n,c,2h+a,2w+b] = x[n,c,h,w] for a, b in {0,1}: a bit copy (NaN payloads and the sign of zero travel)
+ *   bwd  dx[n,c,h,w] (+)= (dy[2h,2w] + dy[2h,2w+1]) + (dy[2h+1,2w] + dy[2h+1,2w+1]), in that order, in fp32
+ * No workspace, no atomics: every element of y / dx is written by one thread of one launch.                       */
+typedef struct {
+    int32_t N, C, H, W;              /* INPUT spatial size; output is 2H x 2W                */
+    const void* x;   int64_t x_batch_stride;
+    void* y;         int64_t y_batch_stride;
+    int32_t layout;                  /* fwd: 0 = fp32 planar x / y.  MTBC_LAYOUT_C8: x and y are 16-bit channel-blocked
+                                        [N][C/8][H*W][8] / [N][C/8][4*H*W][8], batch strides in 16-bit elements (multiples of 8),
+                                        C % 8 == 0, 16-byte aligned: a pixel's 8 channels move as one 16-byte word, so bf16 and fp16
+                                        share one kernel                                                                   */
+    int32_t type16;                  /* 1 = bf16, 2 = fp16 with layout C8 (recorded, not interpreted); 0 with fp32 planes   */
+    const float* dy; int64_t dy_batch_stride;      /* bwd: fp32 planes (N,C,2H,2W) whatever `layout` says                   */
+    float* dx;       int64_t dx_batch_stride;      /*      fp32 planes (N,C,H,W)                                            */
+    int32_t accumulate_dx;           /* bwd: 0 = dx is overwritten, 1 = read-modify-written (the tensor has another reader) */
+} mtbc_upsample2_args;
+int mtbc_upsample2_fwd(const mtbc_upsample2_args* a, void* stream);
+int mtbc_upsample2_bwd(const mtbc_upsample2_args* a, void* stream);
+
 /* --------------------------------------------- ConvTranspose2d, kernel == stride == k
  * replaces nn.ConvTranspose2d(k, stride=k): MTnnUNet.py:96-100,106-116 (k = 2, 4, 8);
  * MONAI UpSample("deconv") in UpCat.  Weight layout = torch (Cin, Cout, k, k).
@@ -475,10 +496,21 @@ typedef struct {
     const float* x; const float* w; const float* bias; float* y;
     const float* dy; float* dx;      /* dx (N,In) overwritten; may be NULL */
     float* dw; float* dbias; int32_t accumulate_dw;
-    void* workspace; size_t workspace_bytes;   /* bwd with relu: N*Out floats */
+    void* workspace; size_t workspace_bytes;   /* bwd with relu: N*Out floats; the batch-shared kernels: mtbc_linear_workspace */
 } mtbc_linear_args;
 int mtbc_linear_fwd(const mtbc_linear_args* a, void* stream);
 int mtbc_linear_bwd(const mtbc_linear_args* a, void* stream);
+/* Wide inputs (a flattened feature map: Multi_BTS_UNet.py:110, In = 16384 * width / 8): from In >= MTBC_LINEAR_WIDE_MIN_IN, with In % 4 == 0
+ * and 16-byte aligned x, w (forward) / w, dx (input gradient), the forward and the input gradient run on batch-shared kernels: a block owns a
+ * slab of W and ALL N samples (eight at a time), so W is read from memory once per launch instead of once per sample.  Split partials (over In
+ * forward, over Out for dx) go to the workspace and are summed in a fixed order by a second launch: deterministic, no atomics.  Selected by
+ * shape and alignment alone; below the threshold the launches are the per-sample ones.  dW keeps linear_dw_kernel (it writes W once already).
+ * mtbc_linear_workspace: the bytes the call needs (backward != 0: mtbc_linear_bwd) for a->N, In, Out, relu and dx -- host arithmetic; 0 = none.
+ * mtbc_linear_wide_enable: process-wide A/B switch of the batch-shared kernels (1 = on, the default); returns the previous value.  Off,
+ * every Linear call makes the per-sample launches and the workspace query answers for them.                                              */
+#define MTBC_LINEAR_WIDE_MIN_IN 4096
+size_t mtbc_linear_workspace(const mtbc_linear_args* a, int32_t backward);
+int mtbc_linear_wide_enable(int32_t on);
 
 /* ------------------------------------------------------------------------------ Dice loss
  * replaces monai.losses.DiceLoss(include_background=True, sigmoid=True, squared_pred=True,
@@ -841,7 +873,8 @@ enum {
     MTBC_OP_IN_DPARAM
 };
 /* appended kinds (additive: the list above is as it was) */
-enum { MTBC_OP_SOFTMAX = 37 };       /* mtbc_softmax_rows on u.softmax, either direction */
+enum { MTBC_OP_SOFTMAX = 37,         /* mtbc_softmax_rows on u.softmax, either direction */
+       MTBC_OP_UPSAMPLE2_FWD = 38, MTBC_OP_UPSAMPLE2_BWD = 39 };      /* mtbc_upsample2_fwd / _bwd on u.up2 */
 /* (the last three: stream control of mtbc_program_run_ms -- independent ops of a step, the weight gradient and the input
  * gradient of one layer, overlap on two HIP streams: the small latency-bound launches of the deep levels fill the chip together) */
 
@@ -921,7 +954,8 @@ typedef struct {
         struct { const float* w; float* dst; int32_t Cout, Cin, ci_off, ci_cnt, mode, k_off, K; } wview;
         struct { const float* src; int64_t src_batch_stride; void* dst; int32_t N, C, HW, compute; } c8pack;   /* C8_PACK and C8_PACK16 (src = 16-bit planar, `compute` unused) */
         mtbc_softmax_args softmax;
-        mtbc_dparam_desc dparam;         /* MTBC_OP_IN_DPARAM: a run of them is issued as one mtbc_instnorm_dparam_many launch */
+        mtbc_upsample2_args up2;
+        mtbc_dparam_desc dparam;        /* MTBC_OP_IN_DPARAM: a run of them is issued as one mtbc_instnorm_dparam_many launch */
         struct { void* event; int32_t index; } sync;      /* SET_STREAM: following ops go to streams[index]; EVENT_RECORD / EVENT_WAIT: on the current stream */
     } u;
 } mtbc_op;
@@ -939,12 +973,15 @@ int mtbc_event_create(void** event);
 int mtbc_event_destroy(void* event);
 /* Host-only plan query for the small ops: every launch the call behind op->kind would make for op->u, in order and joined with " + ",
  * written to buf (NUL-terminated).  Covers MTBC_OP_POOL_FWD / _BWD, MTBC_OP_CONV1_FWD / _DGRAD / _WGRAD, MTBC_OP_GAP_FWD / _BWD,
- * MTBC_OP_LINEAR_FWD / _BWD and MTBC_OP_HEAD_COMBINE / _EXPAND; any other kind (the 3x3, InstanceNorm and ConvT ops have queries of their
+ * MTBC_OP_LINEAR_FWD / _BWD, MTBC_OP_UPSAMPLE2_FWD / _BWD and MTBC_OP_HEAD_COMBINE / _EXPAND; any other kind (the 3x3, InstanceNorm and ConvT ops have queries of their
  * own) is MTBC_E_BADARG.  Kernels are spelled as a profiler spells the instance without namespace and argument list, e.g.
  * "maxpool_c8_fwd_kernel<true>"; what the arguments select inside a kernel follows its name in brackets:
  *   conv1x1_c8_wgrad_kernel<F16> [nblk=1] | [nblk>1] | [nblk=32]   pixel chunks per image (one / several, the last may be ragged / the cap)
  *   plane_sum_k [threads=64] | [threads=256]                       the bias gradient's plane sums (256 from H*W = 4096)
  *   linear_dx_kernel [Out>=8], linear_dw_kernel [N>=8]             the eight-wide unrolled loop runs
+ *   linear_wide_fwd_kernel + linear_wide_reduce_kernel             the batch-shared forward of a wide input and the sum of its split partials
+ *   linear_wide_dx_kernel [+ linear_wide_dx_reduce_kernel]         ... its input gradient; the reduction only with more than one range of outputs
+ *   upsample2_fwd_kernel | upsample2_fwd_scalar_kernel | upsample2_c8_fwd_kernel, upsample2_bwd_kernel | upsample2_bwd_scalar_kernel
  * and the planar 1x1 weight gradient's reduction is named with its instance: "splitk_reduce<4>", "<16>" (more than 32 images) or
  * "<64, 16>" (256 images or more), e.g. "conv1x1_wgrad_kernel + splitk_reduce<4> + plane_sum_k [threads=64] + sum_over_n_k".
  * It is the dispatcher of the real call, stopped in front of its launches: launches nothing, never synchronises, needs no device and never

@@ -70,6 +70,17 @@ class MaxPoolArgs(C.Structure):
                 ("accumulate_dx", C.c_int32), ("layout", C.c_int32), ("type16", C.c_int32), ("argmax", C.c_void_p)]
 
 
+class Upsample2Args(C.Structure):
+    """mtbc_upsample2_args (include/mtbc.h): nearest 2x up-sampling, either direction."""
+    _fields_ = [("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("x", C.c_void_p), ("x_batch_stride", C.c_int64),
+                ("y", C.c_void_p), ("y_batch_stride", C.c_int64),
+                ("layout", C.c_int32), ("type16", C.c_int32),
+                ("dy", C.c_void_p), ("dy_batch_stride", C.c_int64),
+                ("dx", C.c_void_p), ("dx_batch_stride", C.c_int64),
+                ("accumulate_dx", C.c_int32)]
+
+
 class ConvTArgs(C.Structure):
     _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32),
                 ("k", C.c_int32),
@@ -265,7 +276,7 @@ class _OpUnion(C.Union):
                 ("conv1", Conv1x1Args), ("gap", GapArgs), ("linear", LinearArgs), ("dice", DiceArgs),
                 ("focal", FocalArgs), ("optim", OptimArgs), ("pack", _PackArgs), ("mix", _MixArgs),
                 ("memset0", _MemsetArgs), ("counts", _CountsArgs), ("head", HeadFuseArgs), ("c8pack", _C8PackArgs), ("wview", _WViewArgs), ("dparam", DparamDesc), ("sync", _SyncArgs),
-                ("softmax", SoftmaxArgs)]
+                ("softmax", SoftmaxArgs), ("up2", Upsample2Args)]
 
 
 class Op(C.Structure):
@@ -280,6 +291,8 @@ class Op(C.Structure):
  OP_HEAD_COMBINE, OP_HEAD_EXPAND, OP_C8_PACK, OP_C8_PACK16, OP_CONV3_WVIEW,
  OP_SET_STREAM, OP_EVENT_RECORD, OP_EVENT_WAIT, OP_IN_DPARAM) = range(1, 37)
 OP_SOFTMAX = 37            # appended (the header's second enum)
+OP_UPSAMPLE2_FWD, OP_UPSAMPLE2_BWD = 38, 39
+LINEAR_WIDE_MIN_IN = 4096  # MTBC_LINEAR_WIDE_MIN_IN of include/mtbc.h
 
 OP_UNION_FIELD = {
     OP_CONV3_FWD: "conv3", OP_CONV3_DGRAD: "conv3", OP_CONV3_WGRAD: "conv3",
@@ -292,7 +305,7 @@ OP_UNION_FIELD = {
     OP_MEMSET: "memset0", OP_DICE_COUNTS: "counts", OP_CONV3_PACK_LP: "pack",
     OP_HEAD_COMBINE: "head", OP_HEAD_EXPAND: "head", OP_C8_PACK: "c8pack", OP_C8_PACK16: "c8pack", OP_CONV3_WVIEW: "wview",
     OP_SET_STREAM: "sync", OP_EVENT_RECORD: "sync", OP_EVENT_WAIT: "sync", OP_IN_DPARAM: "dparam",
-    OP_SOFTMAX: "softmax",
+    OP_SOFTMAX: "softmax", OP_UPSAMPLE2_FWD: "up2", OP_UPSAMPLE2_BWD: "up2",
 }
 
 # every symbol include/mtbc.h declares (tests check the library exports all of them)
@@ -323,6 +336,7 @@ EXPORTS = [
     "mtbc_seg_metrics_workspace_size", "mtbc_seg_metrics", "mtbc_batch_assemble", "mtbc_train_metrics",
     "mtbc_eval_metrics", "mtbc_seg_step_metrics", "mtbc_fill_holes", "mtbc_fill_holes_host",
     "mtbc_softmax_rows", "mtbc_softmax_rows_host", "mtbc_cls_step_metrics", "mtbc_cls_test_rows",
+    "mtbc_upsample2_fwd", "mtbc_upsample2_bwd", "mtbc_linear_workspace", "mtbc_linear_wide_enable",
 ]
 
 ABI_VERSION = 203          # MTBC_VERSION of include/mtbc.h these mirrors follow
@@ -467,6 +481,13 @@ def load() -> C.CDLL:
     lib.mtbc_cls_step_metrics.argtypes = [C.POINTER(ClsStepMetricsArgs), C.c_void_p]
     lib.mtbc_cls_test_rows.restype = C.c_int
     lib.mtbc_cls_test_rows.argtypes = [C.POINTER(ClsTestRowsArgs), C.c_void_p]
+    for name in ("mtbc_upsample2_fwd", "mtbc_upsample2_bwd"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(Upsample2Args), C.c_void_p]
+    lib.mtbc_linear_workspace.restype = C.c_size_t
+    lib.mtbc_linear_workspace.argtypes = [C.POINTER(LinearArgs), C.c_int32]
+    lib.mtbc_linear_wide_enable.restype = C.c_int
+    lib.mtbc_linear_wide_enable.argtypes = [C.c_int32]
     _lib = lib
     return lib
 

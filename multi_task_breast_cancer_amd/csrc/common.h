@@ -204,6 +204,8 @@ int mtbc_i_conv1x1_c8_wgrad(const mtbc_conv1x1_args* a, hipStream_t st, OpChoice
 // the entry points of pool_up.hip / head_loss.hip with the query (the extern "C" ones pass NULL)
 int mtbc_i_maxpool2_fwd(const mtbc_maxpool_args* a, hipStream_t st, OpChoice* query);
 int mtbc_i_maxpool2_bwd(const mtbc_maxpool_args* a, hipStream_t st, OpChoice* query);
+int mtbc_i_upsample2_fwd(const mtbc_upsample2_args* a, hipStream_t st, OpChoice* query);
+int mtbc_i_upsample2_bwd(const mtbc_upsample2_args* a, hipStream_t st, OpChoice* query);
 int mtbc_i_conv1x1_fwd(const mtbc_conv1x1_args* a, hipStream_t st, OpChoice* query);
 int mtbc_i_conv1x1_dgrad(const mtbc_conv1x1_args* a, hipStream_t st, OpChoice* query);
 int mtbc_i_conv1x1_wgrad(const mtbc_conv1x1_args* a, hipStream_t st, OpChoice* query);

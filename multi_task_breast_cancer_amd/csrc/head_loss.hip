@@ -2,6 +2,7 @@
 // fused Adam / SGD / AdamW (one kernel) and the train-loop Dice counters.  All HBM-/latency-bound; reductions use wavefront
 // shuffles (64 lanes) then LDS across waves -- deterministic, no float atomics.
 #include "common.h"
+#include <atomic>
 
 namespace {
 
@@ -78,6 +79,114 @@ __global__ void linear_dw_kernel(const float* __restrict__ g, const float* __res
         for (int n = 0; n < N; ++n) s += g[(size_t)n * Out + idx];
         db[idx] = accumulate ? db[idx] + s : s;
     }
+}
+
+// ------------------------------------------------------------------ Linear on a wide input: batch-shared kernels (mtbc.h, MTBC_LINEAR_WIDE_MIN_IN)
+// The per-sample kernels above stream the whole weight matrix once per sample (50 MB at In = 49152, Out = 256).  Here a wave owns a slab of W
+// and ALL samples, LW_NB at a time in registers: W comes from memory once per launch (further passes of a batch larger than LW_NB find their
+// slab in the cache).  Both split their reduction dimension over blockIdx.y and leave fp32 partials that a second launch sums in split
+// order: the same bits every run, no atomics.  In % 4 == 0 and 16-byte aligned rows: every W access is a float4.
+constexpr int LW_NB = 8;      // samples per pass
+constexpr int LW_OT = 4;      // forward: output rows per wave (each x float4 is used LW_OT times)
+
+// forward: block = one wave = rows [4 bx, 4 bx + 4) of W x columns [by * kchunk, + kchunk) x all samples -> part[by][n][o]
+__global__ __launch_bounds__(64) void linear_wide_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ part,
+                                                             int N, int In, int Out, int kchunk) {
+    const int lane = threadIdx.x, o0 = blockIdx.x * LW_OT, s = blockIdx.y;
+    const int k0 = s * kchunk, k1 = min(In, k0 + kchunk);
+    const float4* wr[LW_OT];
+#pragma unroll
+    for (int t = 0; t < LW_OT; ++t) wr[t] = reinterpret_cast<const float4*>(w + (size_t)min(o0 + t, Out - 1) * In);      // a row past Out re-reads the last one; never stored
+    for (int n0 = 0; n0 < N; n0 += LW_NB) {
+        float acc[LW_OT][LW_NB];
+#pragma unroll
+        for (int t = 0; t < LW_OT; ++t)
+#pragma unroll
+            for (int j = 0; j < LW_NB; ++j) acc[t][j] = 0.f;
+        for (int k = k0 + 4 * lane; k < k1; k += 256) {
+            float4 wv[LW_OT];
+#pragma unroll
+            for (int t = 0; t < LW_OT; ++t) wv[t] = wr[t][k >> 2];
+#pragma unroll
+            for (int j = 0; j < LW_NB; ++j) {
+                if (n0 + j < N) {        // uniform over the wave
+                    const float4 xv = *reinterpret_cast<const float4*>(x + (size_t)(n0 + j) * In + k);
+#pragma unroll
+                    for (int t = 0; t < LW_OT; ++t)
+                        acc[t][j] = fmaf(xv.w, wv[t].w, fmaf(xv.z, wv[t].z, fmaf(xv.y, wv[t].y, fmaf(xv.x, wv[t].x, acc[t][j]))));
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < LW_OT; ++t)
+#pragma unroll
+            for (int j = 0; j < LW_NB; ++j) {
+                const float v = wave_sum(acc[t][j]);
+                if (lane == 0 && o0 + t < Out && n0 + j < N) part[((size_t)s * N + n0 + j) * Out + o0 + t] = v;
+            }
+    }
+}
+// y[n][o] = relu?(bias[o] + sum_s part[s][n][o]), s ascending
+__global__ void linear_wide_reduce_kernel(const float* __restrict__ part, const float* __restrict__ b, float* __restrict__ y, int S, int NO,
+                                          int Out, int relu) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= NO) return;
+    float s = 0.f;
+    for (int k = 0; k < S; ++k) s += part[(size_t)k * NO + i];
+    s += b ? b[i % Out] : 0.f;
+    y[i] = (relu && s < 0.f) ? 0.f : s;
+}
+// dx: thread = one float4 column of W x outputs [by * ochunk, + ochunk) x all samples -> dst[by][n][i] (dst = dx itself when there is one split)
+__global__ __launch_bounds__(64) void linear_wide_dx_kernel(const float* __restrict__ g, const float* __restrict__ w, float* __restrict__ dst,
+                                                            int N, int In, int Out, int ochunk) {
+    const int In4 = In >> 2, i4 = blockIdx.x * 64 + threadIdx.x;
+    if (i4 >= In4) return;
+    const int s = blockIdx.y, o0 = s * ochunk, o1 = min(Out, o0 + ochunk);
+    const float4* w4 = reinterpret_cast<const float4*>(w) + i4;
+    for (int n0 = 0; n0 < N; n0 += LW_NB) {
+        float4 acc[LW_NB];
+#pragma unroll
+        for (int j = 0; j < LW_NB; ++j) acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        int o = o0;
+        for (; o + 4 <= o1; o += 4) {          // four rows of W in flight
+            float4 wv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) wv[u] = w4[(size_t)(o + u) * In4];
+#pragma unroll
+            for (int j = 0; j < LW_NB; ++j) {
+                if (n0 + j < N) {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const float gv = g[(size_t)(n0 + j) * Out + o + u];
+                        acc[j].x = fmaf(gv, wv[u].x, acc[j].x); acc[j].y = fmaf(gv, wv[u].y, acc[j].y);
+                        acc[j].z = fmaf(gv, wv[u].z, acc[j].z); acc[j].w = fmaf(gv, wv[u].w, acc[j].w);
+                    }
+                }
+            }
+        }
+        for (; o < o1; ++o) {
+            const float4 wv = w4[(size_t)o * In4];
+#pragma unroll
+            for (int j = 0; j < LW_NB; ++j) {
+                if (n0 + j < N) {
+                    const float gv = g[(size_t)(n0 + j) * Out + o];
+                    acc[j].x = fmaf(gv, wv.x, acc[j].x); acc[j].y = fmaf(gv, wv.y, acc[j].y);
+                    acc[j].z = fmaf(gv, wv.z, acc[j].z); acc[j].w = fmaf(gv, wv.w, acc[j].w);
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < LW_NB; ++j)
+            if (n0 + j < N) reinterpret_cast<float4*>(dst + ((size_t)s * N + n0 + j) * In)[i4] = acc[j];
+    }
+}
+// dx[e] = sum_s part[s][e], s ascending; e over the N * In / 4 float4 of dx
+__global__ void linear_wide_dx_reduce_kernel(const float4* __restrict__ part, float4* __restrict__ dx, int S, size_t total4) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total4) return;
+    float4 s = part[i];
+    for (int k = 1; k < S; ++k) { const float4 v = part[(size_t)k * total4 + i]; s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
+    dx[i] = s;
 }
 
 // ------------------------------------------------------------------ segmentation criteria (Dice, BCE, Dice+Focal, Jaccard)
@@ -585,9 +694,62 @@ int mtbc_i_gap_bwd(const mtbc_gap_args* a, hipStream_t st, OpChoice* query) {
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
+// ---- the batch-shared kernels' plans (mtbc.h): by shape alone; the pointers' alignment is checked where they are known
+static std::atomic<int> lw_enabled{1};
+static bool lw_al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+static bool lw_shape(const mtbc_linear_args* a) { return lw_enabled.load() != 0 && a->In >= MTBC_LINEAR_WIDE_MIN_IN && (a->In & 3) == 0; }
+// forward: S chunks of In (multiples of one wave's 256 floats) so that about 2048 waves run
+static void lw_plan_fwd(const mtbc_linear_args* a, int* S, int* kchunk) {
+    int s = 2048 / cdiv(a->Out, LW_OT);
+    const int smax = cdiv(a->In, 256);
+    if (s > smax) s = smax;
+    if (s < 1) s = 1;
+    *kchunk = cdiv(cdiv(a->In, s), 256) * 256;
+    *S = cdiv(a->In, *kchunk);
+}
+// dx: S ranges of at least 16 outputs so that about 1024 waves run
+static void lw_plan_dx(const mtbc_linear_args* a, int* S, int* ochunk) {
+    int s = cdiv(1024, cdiv(a->In / 4, 64));
+    const int smax = a->Out / 16 > 0 ? a->Out / 16 : 1;
+    if (s > smax) s = smax;
+    if (s < 1) s = 1;
+    *ochunk = cdiv(a->Out, s);
+    *S = cdiv(a->Out, *ochunk);
+}
+static size_t lw_round4(size_t n) { return (n + 3) / 4 * 4; }
+extern "C" int mtbc_linear_wide_enable(int32_t on) { return lw_enabled.exchange(on ? 1 : 0); }
+extern "C" size_t mtbc_linear_workspace(const mtbc_linear_args* a, int32_t backward) {
+    if (!a || a->N <= 0 || a->In <= 0 || a->Out <= 0) return 0;
+    int S, chunk;
+    if (!backward) {
+        if (!lw_shape(a)) return 0;
+        lw_plan_fwd(a, &S, &chunk);
+        return (size_t)S * a->N * a->Out * sizeof(float);
+    }
+    size_t floats = a->relu ? (size_t)a->N * a->Out : 0;             // the masked gradient
+    if (lw_shape(a) && a->dx) {
+        lw_plan_dx(a, &S, &chunk);
+        if (S > 1) floats = lw_round4(floats) + (size_t)S * a->N * a->In;      // ... then, 16-byte aligned, the split partials of dx
+    }
+    return floats * sizeof(float);
+}
+
 int mtbc_i_linear_fwd(const mtbc_linear_args* a, hipStream_t st, OpChoice* query) {
     if (!a || a->N <= 0 || a->In <= 0 || a->Out <= 0) return MTBC_E_BADSHAPE;
     if (!a->x || !a->w || !a->y) return MTBC_E_BADARG;
+    const bool wide = lw_shape(a) && lw_al16(a->x) && lw_al16(a->w);
+    if (wide) {
+        int S, kchunk; lw_plan_fwd(a, &S, &kchunk);
+        if (!a->workspace || !lw_al16(a->workspace) || a->workspace_bytes < (size_t)S * a->N * a->Out * sizeof(float)) return MTBC_E_WORKSPACE;
+        if (query) { query->add("linear_wide_fwd_kernel"); query->add("linear_wide_reduce_kernel"); return MTBC_OK; }
+        float* part = reinterpret_cast<float*>(a->workspace);
+        hipLaunchKernelGGL(linear_wide_fwd_kernel, dim3(cdiv(a->Out, LW_OT), S), dim3(64), 0, st, a->x, a->w, part, a->N, a->In, a->Out, kchunk);
+        MTBC_CHECK_LAUNCH();
+        hipLaunchKernelGGL(linear_wide_reduce_kernel, dim3(cdiv(a->N * a->Out, 256)), dim3(256), 0, st, part, a->bias, a->y, S, a->N * a->Out,
+                           a->Out, a->relu);
+        MTBC_CHECK_LAUNCH();
+        return MTBC_OK;
+    }
     if (query) { query->add("linear_fwd_kernel"); return MTBC_OK; }
     hipLaunchKernelGGL(linear_fwd_kernel, dim3(cdiv(a->N * a->Out, 4)), dim3(256), 0, st, a->x, a->w, a->bias, a->y, a->N, a->In, a->Out, a->relu);
     MTBC_CHECK_LAUNCH();
@@ -602,9 +764,20 @@ int mtbc_i_linear_bwd(const mtbc_linear_args* a, hipStream_t st, OpChoice* query
         if (!a->y) return MTBC_E_BADARG;
         if (!a->workspace || a->workspace_bytes < (size_t)a->N * a->Out * sizeof(float)) return MTBC_E_WORKSPACE;
     }
+    const bool wide = dx && lw_shape(a) && lw_al16(a->w) && lw_al16(a->dx);
+    int S = 1, ochunk = a->Out;
+    float* dxpart = nullptr;
+    if (wide) {
+        lw_plan_dx(a, &S, &ochunk);
+        if (S > 1) {
+            if (!a->workspace || !lw_al16(a->workspace) || a->workspace_bytes < mtbc_linear_workspace(a, 1)) return MTBC_E_WORKSPACE;
+            dxpart = reinterpret_cast<float*>(a->workspace) + lw_round4(mask ? (size_t)a->N * a->Out : 0);
+        }
+    }
     if (query) {      // [Out>=8] / [N>=8]: the eight-wide unrolled loops of linear_dx_kernel / linear_dw_kernel run
         if (mask) query->add("linear_mask_kernel");
-        if (dx) query->add(a->Out >= 8 ? "linear_dx_kernel [Out>=8]" : "linear_dx_kernel");
+        if (wide) { query->add("linear_wide_dx_kernel"); if (S > 1) query->add("linear_wide_dx_reduce_kernel"); }
+        else if (dx) query->add(a->Out >= 8 ? "linear_dx_kernel [Out>=8]" : "linear_dx_kernel");
         query->add(a->N >= 8 ? "linear_dw_kernel [N>=8]" : "linear_dw_kernel");
         return MTBC_OK;
     }
@@ -614,7 +787,17 @@ int mtbc_i_linear_bwd(const mtbc_linear_args* a, hipStream_t st, OpChoice* query
         MTBC_CHECK_LAUNCH();
         g = gm;
     }
-    if (dx) {
+    if (wide) {
+        hipLaunchKernelGGL(linear_wide_dx_kernel, dim3(cdiv(a->In / 4, 64), S), dim3(64), 0, st, g, a->w, S > 1 ? dxpart : a->dx, a->N, a->In,
+                           a->Out, ochunk);
+        MTBC_CHECK_LAUNCH();
+        if (S > 1) {
+            const size_t total4 = (size_t)a->N * a->In / 4;
+            hipLaunchKernelGGL(linear_wide_dx_reduce_kernel, dim3((unsigned)cdiv64(total4, 256)), dim3(256), 0, st,
+                               reinterpret_cast<const float4*>(dxpart), reinterpret_cast<float4*>(a->dx), S, total4);
+            MTBC_CHECK_LAUNCH();
+        }
+    } else if (dx) {
         hipLaunchKernelGGL(linear_dx_kernel, dim3(cdiv(a->N * a->In, 256)), dim3(256), 0, st, g, a->w, a->dx, a->N, a->In, a->Out);
         MTBC_CHECK_LAUNCH();
     }

@@ -258,6 +258,81 @@ __global__ void maxpool_bwd_kernel(const MpP p) {
     *reinterpret_cast<float2*>(o + p.W) = d1;
 }
 
+// ------------------------------------------------------------------ nearest 2x up-sampling (Multi_BTS_UNet.py:100)
+// y[n,c,2h+a,2w+b] = x[n,c,h,w]: a copy, 5x the input bytes move.  MpP's N, C, H, W are the INPUT's.
+// fp32 planes: one thread = 4 input pixels of a row -> two float4 in each of the two output rows
+__global__ void upsample2_fwd_kernel(const MpP p) {
+    const int w4 = p.W >> 2, oW = p.W * 2;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t total = (size_t)p.N * p.C * p.H * w4;
+    if (idx >= total) return;
+    const int q = idx % w4; size_t t = idx / w4;
+    const int h = t % p.H; t /= p.H;
+    const int c = t % p.C, n = t / p.C;
+    const float4 v = *reinterpret_cast<const float4*>(p.x + (size_t)n * p.xbs + ((size_t)c * p.H + h) * p.W + 4 * q);
+    const float4 lo = make_float4(v.x, v.x, v.y, v.y), hi = make_float4(v.z, v.z, v.w, v.w);
+    float* o = p.y + (size_t)n * p.ybs + ((size_t)c * 2 * p.H + 2 * h) * oW + 8 * q;
+    reinterpret_cast<float4*>(o)[0] = lo; reinterpret_cast<float4*>(o)[1] = hi;
+    reinterpret_cast<float4*>(o + oW)[0] = lo; reinterpret_cast<float4*>(o + oW)[1] = hi;
+}
+// one thread = one input pixel (W % 4 != 0, or a stride / pointer the 16-byte accesses cannot take)
+__global__ void upsample2_fwd_scalar_kernel(const MpP p) {
+    const int oW = p.W * 2;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t total = (size_t)p.N * p.C * p.H * p.W;
+    if (idx >= total) return;
+    const int w = idx % p.W; size_t t = idx / p.W;
+    const int h = t % p.H; t /= p.H;
+    const int c = t % p.C, n = t / p.C;
+    const float v = p.x[(size_t)n * p.xbs + ((size_t)c * p.H + h) * p.W + w];
+    float* o = p.y + (size_t)n * p.ybs + ((size_t)c * 2 * p.H + 2 * h) * oW + 2 * w;
+    o[0] = v; o[1] = v; o[oW] = v; o[oW + 1] = v;
+}
+// 16-bit channel-blocked [N][C/8][H*W][8]: a pixel's 8 channels are one 16-byte word -- one load, four stores, no arithmetic (bf16 and fp16 alike)
+__global__ void upsample2_c8_fwd_kernel(const uint4* __restrict__ x, long long xbs8, uint4* __restrict__ y, long long ybs8, int N, int G, int H, int W) {
+    const int oW = W * 2;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t total = (size_t)N * G * H * W;
+    if (idx >= total) return;
+    const int w = idx % W; size_t t = idx / W;
+    const int h = t % H; t /= H;
+    const int g = t % G, n = t / G;
+    const uint4 v = x[(size_t)n * xbs8 + ((size_t)g * H + h) * W + w];
+    uint4* o = y + (size_t)n * ybs8 + ((size_t)g * 2 * H + 2 * h) * oW + 2 * w;
+    o[0] = v; o[1] = v; o[oW] = v; o[oW + 1] = v;
+}
+// bwd: dx[h][w] (+)= (dy[2h][2w] + dy[2h][2w+1]) + (dy[2h+1][2w] + dy[2h+1][2w+1]); one thread = 4 dx pixels of a row
+__global__ void upsample2_bwd_kernel(const MpP p) {
+    const int w4 = p.W >> 2, oW = p.W * 2;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t total = (size_t)p.N * p.C * p.H * w4;
+    if (idx >= total) return;
+    const int q = idx % w4; size_t t = idx / w4;
+    const int h = t % p.H; t /= p.H;
+    const int c = t % p.C, n = t / p.C;
+    const float* g = p.dy + (size_t)n * p.dybs + ((size_t)c * 2 * p.H + 2 * h) * oW + 8 * q;
+    const float4 a0 = reinterpret_cast<const float4*>(g)[0], a1 = reinterpret_cast<const float4*>(g)[1];
+    const float4 b0 = reinterpret_cast<const float4*>(g + oW)[0], b1 = reinterpret_cast<const float4*>(g + oW)[1];
+    float4 s = make_float4((a0.x + a0.y) + (b0.x + b0.y), (a0.z + a0.w) + (b0.z + b0.w), (a1.x + a1.y) + (b1.x + b1.y), (a1.z + a1.w) + (b1.z + b1.w));
+    float4* o = reinterpret_cast<float4*>(p.dx + (size_t)n * p.dxbs + ((size_t)c * p.H + h) * p.W + 4 * q);
+    if (p.acc) { const float4 e = *o; s.x += e.x; s.y += e.y; s.z += e.z; s.w += e.w; }
+    *o = s;
+}
+__global__ void upsample2_bwd_scalar_kernel(const MpP p) {
+    const int oW = p.W * 2;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t total = (size_t)p.N * p.C * p.H * p.W;
+    if (idx >= total) return;
+    const int w = idx % p.W; size_t t = idx / p.W;
+    const int h = t % p.H; t /= p.H;
+    const int c = t % p.C, n = t / p.C;
+    const float* g = p.dy + (size_t)n * p.dybs + ((size_t)c * 2 * p.H + 2 * h) * oW + 2 * w;
+    float s = (g[0] + g[1]) + (g[oW] + g[oW + 1]);
+    float* o = p.dx + (size_t)n * p.dxbs + ((size_t)c * p.H + h) * p.W + w;
+    if (p.acc) s += *o;
+    *o = s;
+}
+
 // ------------------------------------------------------------------ conv1x1 (few output channels)
 struct C1P {
     int N, HW, Cin, Cout;
@@ -553,6 +628,52 @@ int mtbc_i_maxpool2_bwd(const mtbc_maxpool_args* a, hipStream_t st, OpChoice* qu
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
+
+// ---------------------------------------------------------------- nearest 2x up-sampling: the dispatchers
+static int fill_up(const mtbc_upsample2_args* a, MpP* p) {
+    if (!a || a->N <= 0 || a->C <= 0 || a->H <= 0 || a->W <= 0) return MTBC_E_BADSHAPE;
+    p->N = a->N; p->C = a->C; p->H = a->H; p->W = a->W; p->x = reinterpret_cast<const float*>(a->x); p->xbs = a->x_batch_stride;
+    p->y = reinterpret_cast<float*>(a->y); p->ybs = a->y_batch_stride; p->dy = a->dy; p->dybs = a->dy_batch_stride; p->dx = a->dx;
+    p->dxbs = a->dx_batch_stride; p->acc = a->accumulate_dx;
+    return MTBC_OK;
+}
+int mtbc_i_upsample2_fwd(const mtbc_upsample2_args* a, hipStream_t st, OpChoice* query) {
+    MpP p; int rc = fill_up(a, &p); if (rc) return rc;
+    if (!a->x || !a->y) return MTBC_E_BADARG;
+    if (a->layout == MTBC_LAYOUT_C8) {
+        if (a->C & 7) return MTBC_E_BADSHAPE;
+        if (a->type16 != 1 && a->type16 != 2) return MTBC_E_BADARG;
+        if (!al16(a->x) || !al16(a->y) || (p.xbs & 7) || (p.ybs & 7)) return MTBC_E_UNSUPPORTED;
+        if (query) { query->add("upsample2_c8_fwd_kernel"); return MTBC_OK; }
+        const size_t total = (size_t)a->N * (a->C / 8) * a->H * a->W;
+        hipLaunchKernelGGL(upsample2_c8_fwd_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, reinterpret_cast<const uint4*>(a->x),
+                           p.xbs / 8, reinterpret_cast<uint4*>(a->y), p.ybs / 8, a->N, a->C / 8, a->H, a->W);
+        MTBC_CHECK_LAUNCH();
+        return MTBC_OK;
+    }
+    if (a->layout != MTBC_LAYOUT_PLANAR) return MTBC_E_BADARG;
+    const bool vec = (a->W & 3) == 0 && al16(p.x) && al16(p.y) && (p.xbs & 3) == 0 && (p.ybs & 3) == 0;
+    if (query) { query->add(vec ? "upsample2_fwd_kernel" : "upsample2_fwd_scalar_kernel"); return MTBC_OK; }
+    const size_t total = (size_t)a->N * a->C * a->H * (vec ? a->W / 4 : a->W);
+    if (vec) hipLaunchKernelGGL(upsample2_fwd_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(upsample2_fwd_scalar_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, p);
+    MTBC_CHECK_LAUNCH();
+    return MTBC_OK;
+}
+int mtbc_i_upsample2_bwd(const mtbc_upsample2_args* a, hipStream_t st, OpChoice* query) {
+    MpP p; int rc = fill_up(a, &p); if (rc) return rc;
+    if (!p.dy || !p.dx) return MTBC_E_BADARG;
+    if (a->accumulate_dx != 0 && a->accumulate_dx != 1) return MTBC_E_BADARG;
+    const bool vec = (a->W & 3) == 0 && al16(p.dy) && al16(p.dx) && (p.dybs & 3) == 0 && (p.dxbs & 3) == 0;
+    if (query) { query->add(vec ? "upsample2_bwd_kernel" : "upsample2_bwd_scalar_kernel"); return MTBC_OK; }
+    const size_t total = (size_t)a->N * a->C * a->H * (vec ? a->W / 4 : a->W);
+    if (vec) hipLaunchKernelGGL(upsample2_bwd_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(upsample2_bwd_scalar_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, p);
+    MTBC_CHECK_LAUNCH();
+    return MTBC_OK;
+}
+extern "C" int mtbc_upsample2_fwd(const mtbc_upsample2_args* a, void* stream) { return mtbc_i_upsample2_fwd(a, (hipStream_t)stream, nullptr); }
+extern "C" int mtbc_upsample2_bwd(const mtbc_upsample2_args* a, void* stream) { return mtbc_i_upsample2_bwd(a, (hipStream_t)stream, nullptr); }
 
 static int fill_c1(const mtbc_conv1x1_args* a, C1P* p) {
     if (!a || a->N <= 0 || a->H <= 0 || a->W <= 0 || a->Cin <= 0 || a->Cout <= 0) return MTBC_E_BADSHAPE;

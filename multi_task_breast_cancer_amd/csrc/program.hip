@@ -49,6 +49,8 @@ int mtbc_op_kernel_name(const mtbc_op* op, char* buf, int32_t len) {
         case MTBC_OP_GAP_BWD: rc = mtbc_i_gap_bwd(&op->u.gap, nullptr, &ch); break;
         case MTBC_OP_LINEAR_FWD: rc = mtbc_i_linear_fwd(&op->u.linear, nullptr, &ch); break;
         case MTBC_OP_LINEAR_BWD: rc = mtbc_i_linear_bwd(&op->u.linear, nullptr, &ch); break;
+        case MTBC_OP_UPSAMPLE2_FWD: rc = mtbc_i_upsample2_fwd(&op->u.up2, nullptr, &ch); break;
+        case MTBC_OP_UPSAMPLE2_BWD: rc = mtbc_i_upsample2_bwd(&op->u.up2, nullptr, &ch); break;
         case MTBC_OP_HEAD_COMBINE: rc = mtbc_i_head_combine(&op->u.head, nullptr, &ch); break;
         case MTBC_OP_HEAD_EXPAND: rc = mtbc_i_head_expand(&op->u.head, nullptr, &ch); break;
         default: return MTBC_E_BADARG;
@@ -165,6 +167,8 @@ int mtbc_program_run_ms(const mtbc_op* ops, int32_t first, int32_t count, void* 
             case MTBC_OP_FOCAL: rc = mtbc_focal_fwd_bwd(&o->u.focal, stream); break;
             case MTBC_OP_LOSS_MIX: rc = mtbc_loss_mix(o->u.mix.seg, o->u.mix.cls, o->u.mix.alpha, o->u.mix.out4, stream); break;
             case MTBC_OP_SOFTMAX: rc = mtbc_softmax_rows(&o->u.softmax, stream); break;
+            case MTBC_OP_UPSAMPLE2_FWD: rc = mtbc_upsample2_fwd(&o->u.up2, stream); break;
+            case MTBC_OP_UPSAMPLE2_BWD: rc = mtbc_upsample2_bwd(&o->u.up2, stream); break;
             case MTBC_OP_OPTIM: rc = mtbc_optim_step(&o->u.optim, stream); break;
             case MTBC_OP_MEMSET:
                 rc = hipMemsetAsync(o->u.memset0.ptr, 0, o->u.memset0.bytes, (hipStream_t)stream) == hipSuccess ? MTBC_OK : MTBC_E_LAUNCH;

@@ -818,6 +818,38 @@ class StepPlan:
         self.bwd_emitters.append(emit_bwd)
         return y
 
+    def upsample2(self, x: Act, out_name: str) -> Act:
+        """nn.Upsample(scale_factor=2, mode="nearest") (Multi_BTS_UNet.py:100): a copy forward, the 2 x 2 window sums of dy backward.  The
+        gradient of x goes through grad_slot(x), like the ConvT input gradient: under deep supervision x also feeds a head."""
+        assert x.N == self.N, f"{x.name}: only conv cells and max-pools are planned over a batch-concatenated (2N) tensor"
+        x.readers += 1
+        y = self.new_act(out_name, x.C, 2 * x.H, 2 * x.W)
+        # 16-bit modes: the up-sampled tensor feeds 3x3 convs only -- move the channel-blocked 16-bit copy of x (the one the 3x3 convs read)
+        # into a channel-blocked y, 2 instead of 4 bytes per element and no pack; y then has no fp32 planes, as a pooled tensor has none.
+        # Only where the convs that read y can take the layout (StepPlan.conv_cell's c8 condition on the plane)
+        c8 = bool(self.compute) and not self.force_direct and x.C % 8 == 0 and (2 * x.W) % 4 == 0 and 2 * x.H >= 8 and 2 * x.W >= 8
+        strides = dict(x=x.bstride, y=y.bstride, dy=y.bstride, dx=x.bstride)
+        if c8:
+            y.c8 = self.alloc(self.N, x.C // 8, y.H * y.W, 8, dtype=torch.int16)
+            y.c8_filled = True
+            y.planar_valid = False
+            ptrs = dict(x=self.c8_of(x), y=y.c8)
+        else:
+            self._rd(x)
+            ptrs = dict(x=x.data, y=y.data)
+        self.fwd_ops.append(_ops.upsample2_case_args(L.OP_UPSAMPLE2_FWD, self.N, x.C, x.H, x.W, ptrs=ptrs, compute=self.compute if c8 else 0, strides=strides))
+        # y.grad16_ok stays False: the consumer's dgrad hands fp32 planes over (16-bit gradient planes into this op are not built)
+
+        def emit_bwd() -> None:
+            if not y.grad_written or not x.needs_grad:
+                return
+            gx, acc = self.grad_slot(x)
+            self.bwd_ops.append(_ops.upsample2_case_args(L.OP_UPSAMPLE2_BWD, self.N, x.C, x.H, x.W, ptrs=dict(dy=self.grad_of(y), dx=gx), acc_dx=bool(acc),
+                                                         strides=strides))
+
+        self.bwd_emitters.append(emit_bwd)
+        return y
+
     def convT(self, x: Act, cout: int, k: int, wname: str, bname: Optional[str], out_name: str) -> Act:
         assert x.N == self.N, f"{x.name}: only conv cells and max-pools are planned over a batch-concatenated (2N) tensor"
         w = self.pv(wname)
@@ -1076,6 +1108,9 @@ class StepPlan:
 
         op = base()
         op.kind = L.OP_LINEAR_FWD
+        nb = int(self.lib.mtbc_linear_workspace(C.byref(op.u.linear), 0))      # > 0 only for the batch-shared kernels of a wide input (mtbc.h)
+        if nb:
+            self._need_ws(op, "linear", nb)
         self.fwd_ops.append(op)
 
         def emit_bwd() -> None:
@@ -1091,8 +1126,9 @@ class StepPlan:
             a.accumulate_dw = self._mark_param(wname)
             self._mark_param(bname)
             a.dw, a.dbias = self.gv(wname).data_ptr(), self.gv(bname).data_ptr()
-            if relu:
-                self._need_ws(op, "linear", self.N * out_f * 4)
+            nb = int(self.lib.mtbc_linear_workspace(C.byref(a), 1))      # relu: N * Out floats; a wide input: the split partials of dx behind them
+            if nb:
+                self._need_ws(op, "linear", nb)
             x.grad_written = True
             self.bwd_ops.append(op)
 

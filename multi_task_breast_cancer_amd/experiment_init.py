@@ -11,7 +11,7 @@ import torch
 from torch.optim.lr_scheduler import CosineAnnealingLR, ReduceLROnPlateau
 
 from .criterions import DiceFocalLoss, DiceLoss, FocalLoss
-from .nets import MTnnUNet, MTUNetPlusPlus, UNetPlusPlusClassifier, nnUNet, nnUNetClassifier
+from .nets import MTnnUNet, MTUNetPlusPlus, Multi_BTSUNet, UNetPlusPlusClassifier, nnUNet, nnUNetClassifier
 from .optim import FusedAdam, FusedAdamW, FusedSGD
 
 
@@ -28,9 +28,11 @@ def init_multitask_model(architecture: str, sequences: int = 1, regions: int = 1
                                deep_supervision=deep_supervision)
     elif architecture == "MTnnUNet":
         model = MTnnUNet(sequences=sequences, regions=regions, n_classes=n_classes)
+    elif architecture == "Multi_BTSUNet":       # experiment_init.py:157-159: the one architecture that honours `width` and `deep_supervision`
+        model = Multi_BTSUNet(sequences=sequences, regions=regions, n_classes=n_classes, width=width, deep_supervision=deep_supervision)
     else:
         raise ValueError(f"The model selected ({architecture!r}) is not on the MI355X hot path. Choose "
-                         "'MTnnUNet' or 'MTUNetPlusPlus'.")
+                         "'MTnnUNet', 'MTUNetPlusPlus' or 'Multi_BTSUNet'.")
     _describe(model, save_folder)
     return model
 

@@ -1,4 +1,4 @@
-"""MTnnUNet, MTUNetPlusPlus, the single-task nnUNet and the single-task classifiers as thin nn.Module shells over HIP step programs.
+"""MTnnUNet, MTUNetPlusPlus, Multi_BTSUNet, the single-task nnUNet and the single-task classifiers as thin nn.Module shells over HIP step programs.
 
 Drop-in surface: `model(x) -> (logits, segs)` (lists under deep supervision; nnUNet: the list of heads alone; nnUNetClassifier /
 UNetPlusPlusClassifier: the (N, n_classes) tensor alone), `.parameters()`,
@@ -99,6 +99,58 @@ def _mtnnunet_params(sequences: int, regions: int, n_classes: int) -> List[Tuple
     out += [("classifier.3.weight", wt), ("classifier.3.bias", b)]
     wt, b = _draw_linear(256, n_classes)
     out += [("classifier.5.weight", wt), ("classifier.5.bias", b)]
+    return out
+
+
+def _multi_btsunet_params(sequences: int, regions: int, n_classes: int, width: int, deep_supervision: bool) -> List[Tuple[str, torch.Tensor]]:
+    """Multi_BTS_UNet (src/models/multitask/Multi_BTS_UNet.py:74-137) in its constructor's draw order, every layer with torch's default
+    initialisation (the 16384 * width / 8 x 256 Linear included); then `weights_initialization` (:131-137): kaiming-normal over the nn.Conv2d
+    modules in `modules()` order -- the 3x3 convs and the 1x1 heads -- and zero for their biases; ConvTranspose2d and Linear keep their draw.
+    `n_classes` is the number of logits (the caller maps 2 classes to 1).  output3 / output2 exist only under deep supervision."""
+    w = [width * 2 ** i for i in range(4)]
+    out: List[Tuple[str, torch.Tensor]] = []
+    conv_names: List[str] = []
+
+    def cell(name, cin, cout):
+        out.append((f"{name}.Conv.weight", _draw_conv(cin, cout, 3, False)[0]))
+        conv_names.append(f"{name}.Conv.weight")
+
+    def level(name, cin, cmid, cout):
+        cell(f"{name}.ConvInNormLRelu1", cin, cmid)
+        cell(f"{name}.ConvInNormLRelu2", cmid, cout)
+
+    def head1x1(name, cin):
+        wt, b = _draw_conv(cin, regions, 1, True)
+        out.extend([(f"{name}.weight", wt), (f"{name}.bias", b)])
+        conv_names.append(f"{name}.weight")
+
+    level("encoder1", sequences, w[0] // 2, w[0])
+    level("encoder2", w[0], w[1] // 2, w[1])
+    level("encoder3", w[1], w[2] // 2, w[2])
+    level("encoder4", w[2], w[3] // 2, w[3])
+    level("bottleneck", w[3], w[3], w[3])
+    cell("bottleneck2", w[3] * 2, w[2])
+    level("decoder3", w[2] * 2, w[2], w[1])
+    level("decoder2", w[1] * 2, w[1], w[0])
+    level("decoder1", w[0] * 2, w[0], w[0] // 2)
+    cell("process_bottleneck2", w[2], w[3])
+    cell("process_features_map", w[3] * 3, w[3])
+    wt, b = _draw_linear(w[3] * 16 * 16, 256)
+    out += [("classifier.1.weight", wt), ("classifier.1.bias", b)]
+    wt, b = _draw_linear(256, n_classes)
+    out += [("classifier.3.weight", wt), ("classifier.3.bias", b)]
+    if deep_supervision:
+        for name, c, k in (("output3", w[1], 4), ("output2", w[0], 2)):
+            wt, b = _draw_convT(c, c, k)
+            out += [(f"{name}.0.weight", wt), (f"{name}.0.bias", b)]
+            head1x1(f"{name}.1", c)
+    head1x1("output1", w[0] // 2)
+    d = dict(out)
+    for nm in conv_names:
+        nn.init.kaiming_normal_(d[nm], nonlinearity="leaky_relu")
+        bn = nm[:-6] + "bias"
+        if bn in d:
+            nn.init.constant_(d[bn], 0)
     return out
 
 
@@ -359,6 +411,48 @@ def _graph_unetpp(plan: StepPlan, x: Act, segmentation: bool = True):
 
 def _graph_unetpp_classifier(plan: StepPlan, x: Act):
     return _graph_unetpp(plan, x, segmentation=False)
+
+
+BTSUNET_INPUT = 128        # Multi_BTS_UNet.py:110: the head's Linear is sized for a 16 x 16 bottleneck, three poolings below the input
+
+
+def _graph_multi_btsunet(plan: StepPlan, x: Act):
+    """Multi_BTS_UNet.forward (Multi_BTS_UNet.py:139-176): three poolings, nearest up-sampling (StepPlan.upsample2) in place of the other
+    models' transposed convs, the reference's concat orders, and a head that flattens a (8 * width, 16, 16) map into a Linear."""
+    if (x.H, x.W) != (BTSUNET_INPUT, BTSUNET_INPUT):
+        raise ValueError(f"Multi_BTSUNet takes {BTSUNET_INPUT} x {BTSUNET_INPUT} inputs only, got {x.H} x {x.W}: its classifier's Linear is "
+                         f"hard-coded for the 16 x 16 feature map of that size (Multi_BTS_UNet.py:110)")
+
+    def cell(inputs, name):
+        return plan.conv_cell(inputs, plan.pv(f"{name}.Conv.weight").shape[0], f"{name}.Conv.weight", None, None, None, 0.01, name)
+
+    def level(inputs, name):
+        return cell([cell(inputs, f"{name}.ConvInNormLRelu1")], f"{name}.ConvInNormLRelu2")
+
+    e1 = level([x], "encoder1")
+    e2 = level([plan.maxpool(e1, "pool1")], "encoder2")
+    e3 = level([plan.maxpool(e2, "pool2")], "encoder3")
+    e4 = level([plan.maxpool(e3, "pool3")], "encoder4")
+    bott = level([e4], "bottleneck")
+    bott2 = cell([e4, bott], "bottleneck2")
+    d3 = level([e3, plan.upsample2(bott2, "up3")], "decoder3")
+    d2 = level([e2, plan.upsample2(d3, "up2")], "decoder2")
+    d1 = level([e1, plan.upsample2(d2, "up1")], "decoder1")
+    pb2 = cell([bott2], "process_bottleneck2")
+    feat = cell([e4, bott, pb2], "process_features_map")
+    h = plan.linear(feat, 256, "classifier.1.weight", "classifier.1.bias", True, "fc1")
+    logits = plan.linear(h, plan.pv("classifier.3.weight").shape[0], "classifier.3.weight", "classifier.3.bias", False, "logits")
+    regions = plan.pv("output1.weight").shape[0]
+    heads = []
+    if "output3.0.weight" in plan.slots:          # deep supervision: ConvT(k = 4 / 2) + 1x1, as MTnnUNet's heads
+        for name, t, k in (("output3", d3, 4), ("output2", d2, 2)):
+            if _sw.flag("MTBC_NOFUSE_HEADS"):
+                heads.append(plan.conv1x1(plan.convT(t, t.C, k, f"{name}.0.weight", f"{name}.0.bias", f"{name}.up"), regions,
+                                          f"{name}.1.weight", f"{name}.1.bias", name))
+            else:
+                heads.append(plan.convT_head(t, t.C, k, f"{name}.0.weight", f"{name}.0.bias", f"{name}.1.weight", f"{name}.1.bias", name))
+    heads.append(plan.conv1x1(d1, regions, "output1.weight", "output1.bias", "output1"))
+    return logits, heads
 
 
 # ----------------------------------------------------------------------------------------------
@@ -633,6 +727,24 @@ class MTUNetPlusPlus(HipMultiTaskNet):
         super().__init__(_unetpp_params(in_channels, out_channels, ncls), in_channels, deep_supervision,
                          _graph_unetpp, force_direct)
         self.n_classes = ncls
+
+
+class Multi_BTSUNet(HipMultiTaskNet):
+    """src/models/multitask/Multi_BTS_UNet.py:64-176 (`Multi_BTS_UNet`): `forward(x)` returns ([logits], [out3, out2, out1]) under deep
+    supervision and (logits, out1) without it (:167-176).  128 x 128 inputs only (the head's Linear is sized for them): any other size raises
+    ValueError.  Single device: FusedTrainStep / FusedEvalStep refuse distributed=True for it."""
+    architecture = "Multi_BTSUNet"
+    single_device_only = True
+
+    def __init__(self, sequences: int, regions: int, n_classes: int = 3, width: int = 48, deep_supervision: bool = False,
+                 force_direct: bool = False):
+        if width < 2 or width % 2:
+            raise ValueError(f"width must be a positive even number (encoder1's first cell has width // 2 channels), got {width}")
+        ncls = 1 if n_classes == 2 else n_classes
+        super().__init__(_multi_btsunet_params(sequences, regions, ncls, width, bool(deep_supervision)), sequences, bool(deep_supervision),
+                         _graph_multi_btsunet, force_direct)
+        self.n_classes = ncls
+        self.width = width
 
 
 class nnUNet(HipMultiTaskNet):

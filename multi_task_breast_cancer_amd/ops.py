@@ -952,7 +952,7 @@ def convT_head_fwd_bwd(x, wT, bT, w1, b1, k, dout):
 
 # ------------------------------------------------------------------ the small ops as step-program ops: plan query, argument structs, launch
 SMALL_OPS = (L.OP_POOL_FWD, L.OP_POOL_BWD, L.OP_CONV1_FWD, L.OP_CONV1_DGRAD, L.OP_CONV1_WGRAD, L.OP_GAP_FWD, L.OP_GAP_BWD,
-             L.OP_LINEAR_FWD, L.OP_LINEAR_BWD, L.OP_HEAD_COMBINE, L.OP_HEAD_EXPAND)
+             L.OP_LINEAR_FWD, L.OP_LINEAR_BWD, L.OP_HEAD_COMBINE, L.OP_HEAD_EXPAND, L.OP_UPSAMPLE2_FWD, L.OP_UPSAMPLE2_BWD)
 
 
 def op_kernel_name(op: "L.Op") -> str:
@@ -1042,8 +1042,10 @@ def gap_case_args(kind: int, N: int, Cc: int, H: int, W: int, ptrs: Optional[dic
 def linear_case_args(kind: int, N: int, In: int, Out: int, ptrs: Optional[dict] = None, relu: bool = False, bias: bool = True, dx: bool = True,
                      acc_dw: bool = False, workspace: bool = True) -> "L.Op":
     """The MTBC_OP_LINEAR_FWD / _BWD op as engine.StepPlan.linear fills it.  ptrs: x, w, bias, y, dy, dx, dw, dbias, workspace.  bias: the
-    forward's bias (the backward always has dbias, as in the programs); dx = False: no input gradient; workspace: the backward with relu gets
-    its N * Out floats (the engine gives one to the ReLU layers only)."""
+    forward's bias (the backward always has dbias, as in the programs); dx = False: no input gradient; workspace: the call gets what
+    mtbc_linear_workspace asks for -- N * Out floats for the backward with relu (the engine gives one to the ReLU layers only), the split
+    partials of the batch-shared kernels from In = LINEAR_WIDE_MIN_IN on, nothing otherwise.  ptrs without a "workspace" where one is needed:
+    one is allocated here, beside ptrs["x"], and kept alive by the op."""
     ptr = _small_ptr(ptrs)
     op = _small_op(kind)
     a = op.u.linear
@@ -1052,9 +1054,67 @@ def linear_case_args(kind: int, N: int, In: int, Out: int, ptrs: Optional[dict] 
     if kind == L.OP_LINEAR_BWD:
         a.dy, a.dx = ptr("dy"), (ptr("dx") if dx else None)
         a.dw, a.dbias, a.accumulate_dw = ptr("dw"), ptr("dbias"), int(acc_dw)
-        if relu and workspace:
-            a.workspace, a.workspace_bytes = ptr("workspace"), (N * Out * 4 if ptrs is None else ptrs["workspace"].numel() * 4)
+    nb = int(L.load().mtbc_linear_workspace(C.byref(a), int(kind == L.OP_LINEAR_BWD)))
+    if nb and workspace:
+        if ptrs is None:
+            a.workspace, a.workspace_bytes = ptr("workspace"), nb
+        else:
+            if "workspace" not in ptrs:
+                op.own_workspace = _ws(nb, ptrs["x"].device)
+            ws = ptrs["workspace"] if "workspace" in ptrs else op.own_workspace
+            a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
     return op
+
+
+def linear_wide(enabled: bool) -> bool:
+    """Process-wide A/B switch of the batch-shared Linear kernels (mtbc_linear_wide_enable); returns what it was.  Off, every Linear call makes
+    the per-sample launches it made before those kernels existed.  Plans built while it is off keep their (smaller) workspace: rebuild them."""
+    return bool(L.load().mtbc_linear_wide_enable(int(bool(enabled))))
+
+
+def upsample2_case_args(kind: int, N: int, Cc: int, H: int, W: int, ptrs: Optional[dict] = None, compute: int = 0, acc_dx: bool = False,
+                        strides: Optional[dict] = None) -> "L.Op":
+    """The MTBC_OP_UPSAMPLE2_FWD / _BWD op of ONE nearest 2x up-sampling call as engine.StepPlan.upsample2 fills it (H, W: the INPUT's).  ptrs:
+    x, y (forward), dy, dx (backward); None = dummies.  compute: 0 = fp32 planes, 1 / 2 = the forward moves 16-bit channel-blocked tensors of
+    that type (dy / dx are fp32 planes always).  strides: field name -> batch stride in elements of that tensor; dense otherwise."""
+    strides, ptr = strides or {}, _small_ptr(ptrs)
+    op = _small_op(kind)
+    a = op.u.up2
+    a.N, a.C, a.H, a.W = N, Cc, H, W
+    if kind == L.OP_UPSAMPLE2_FWD:
+        if compute:
+            a.layout, a.type16 = L.LAYOUT_C8, compute
+        a.x, a.x_batch_stride = ptr("x"), strides.get("x", Cc * H * W)
+        a.y, a.y_batch_stride = ptr("y"), strides.get("y", 4 * Cc * H * W)
+    else:
+        a.dy, a.dy_batch_stride = ptr("dy"), strides.get("dy", 4 * Cc * H * W)
+        a.dx, a.dx_batch_stride, a.accumulate_dx = ptr("dx"), strides.get("dx", Cc * H * W), int(acc_dx)
+    return op
+
+
+def upsample2_fwd(x):
+    """nn.Upsample(scale_factor=2, mode="nearest") of fp32 planes (N, C, H, W), or of a C8 tensor into a C8 tensor."""
+    N, Cc, H, W = x.shape
+    if isinstance(x, C8):
+        y = torch.empty(N, Cc // 8, 4 * H * W, 8, dtype=torch.int16, device=x.data.device)
+        small_op_launch(upsample2_case_args(L.OP_UPSAMPLE2_FWD, N, Cc, H, W, ptrs={"x": x, "y": y}, compute=x.compute))
+        return C8(y, (N, Cc, 2 * H, 2 * W), x.compute)
+    _chk(x)
+    y = torch.empty(N, Cc, 2 * H, 2 * W, dtype=torch.float32, device=x.device)
+    small_op_launch(upsample2_case_args(L.OP_UPSAMPLE2_FWD, N, Cc, H, W, ptrs={"x": x, "y": y}))
+    return y
+
+
+def upsample2_bwd(dy, dx=None, accumulate=False):
+    """dx (N, C, H, W) (+)= the 2 x 2 window sums of dy (N, C, 2H, 2W)."""
+    _chk(dy, dx)
+    N, Cc, H2, W2 = dy.shape
+    if dx is None:
+        if accumulate:
+            raise ValueError("accumulate needs the dx to add into")
+        dx = torch.empty(N, Cc, H2 // 2, W2 // 2, dtype=torch.float32, device=dy.device)
+    small_op_launch(upsample2_case_args(L.OP_UPSAMPLE2_BWD, N, Cc, H2 // 2, W2 // 2, ptrs={"dy": dy, "dx": dx}, acc_dx=accumulate))
+    return dx
 
 
 def head_case_args(kind: int, Cin: int, Cmid: int, R: int, k: int, ptrs: Optional[dict] = None, bT: bool = True, b1: bool = True,
@@ -1081,7 +1141,8 @@ def small_op_launch(op: "L.Op") -> None:
     fn = {L.OP_POOL_FWD: lib.mtbc_maxpool2_fwd, L.OP_POOL_BWD: lib.mtbc_maxpool2_bwd, L.OP_CONV1_FWD: lib.mtbc_conv1x1_fwd,
           L.OP_CONV1_DGRAD: lib.mtbc_conv1x1_dgrad, L.OP_CONV1_WGRAD: lib.mtbc_conv1x1_wgrad, L.OP_GAP_FWD: lib.mtbc_gap_fwd,
           L.OP_GAP_BWD: lib.mtbc_gap_bwd, L.OP_LINEAR_FWD: lib.mtbc_linear_fwd, L.OP_LINEAR_BWD: lib.mtbc_linear_bwd,
-          L.OP_HEAD_COMBINE: lib.mtbc_convT_head_combine, L.OP_HEAD_EXPAND: lib.mtbc_convT_head_expand}[op.kind]
+          L.OP_HEAD_COMBINE: lib.mtbc_convT_head_combine, L.OP_HEAD_EXPAND: lib.mtbc_convT_head_expand,
+          L.OP_UPSAMPLE2_FWD: lib.mtbc_upsample2_fwd, L.OP_UPSAMPLE2_BWD: lib.mtbc_upsample2_bwd}[op.kind]
     if launched is not None:
         launched.append((op.kind, op_kernel_name(op)))
     L.check(fn(C.byref(getattr(op.u, L.OP_UNION_FIELD[op.kind])), _s()), f"small op {op.kind}")

@@ -320,6 +320,12 @@ def _check_seg_only(alpha, n_classes, focal_weight, cls_criterion, distributed: 
         raise NotImplementedError(f"{owner}: data parallel is not built for segmentation-only models yet")
 
 
+def _check_single_device(model, distributed: bool, owner: str) -> None:
+    """A model whose data-parallel step is not built or tested (nets.Multi_BTSUNet) refuses distributed=True, as the single-task models do."""
+    if distributed and getattr(model, "single_device_only", False):
+        raise NotImplementedError(f"{owner}: data parallel is not built for {getattr(model, 'architecture', type(model).__name__)} yet")
+
+
 def is_cls_only(model) -> bool:
     """A single-task classification model (nets.nnUNetClassifier, nets.UNetPlusPlusClassifier): no segmentation head anywhere in its plans."""
     return bool(getattr(model, "cls_only", False))
@@ -599,6 +605,7 @@ class FusedTrainStep:
         # which is all a classification-only model accepts
         self.seg_only = is_seg_only(model)
         self.cls_only = is_cls_only(model)
+        _check_single_device(model, distributed, "the fused step")
         if self.cls_only:
             _check_cls_only(alpha, inversely_weighted, seg_criterion, distributed, "the fused step")
             alpha = 0.0
@@ -928,6 +935,7 @@ class FusedEvalStep:
         # `step(image, label)`, no segmentation argument, the metrics launch is `mtbc_cls_step_metrics`, `result()` is (val_loss, val_acc, val_f1)
         self.seg_only = is_seg_only(model)
         self.cls_only = is_cls_only(model)
+        _check_single_device(model, distributed, "FusedEvalStep")
         if self.cls_only:
             _check_cls_only(alpha, inversely_weighted, seg_criterion, distributed, "FusedEvalStep")
             alpha = 0.0
