@@ -32,7 +32,8 @@ PLAN_SWITCHES: Dict[str, tuple] = {
                           "tests/test_model_gpu.py::test_mtnnunet_two_layer_heads_match_the_fused_heads_and_the_oracle"),
     "MTBC_GRAPH": ("0", "trainer.FusedTrainStep (single process) captures each compiled step -- weight images, forward, losses, backward, Adam -- into ONE hipGraph at its third call "
                         "and replays it from then on: the host issues a step in 0.1 ms instead of 8.4 (profiles/r04_graph_replay.txt); the GPU time is the same, the results are the same bits "
-                        "(the optimizer's per-step scalars travel through device memory, mtbc_optim_args.dynamic)",
+                        "(the optimizer's per-step scalars travel through device memory, mtbc_optim_args.dynamic); under data parallel (distributed=True) a chain of "
+                        "graphs, one per backward range between two bucket all-reduces plus the update, the collectives eager between them (profiles/dp_graph_replay.txt)",
                    "tests/test_model_gpu.py::test_graph_replayed_steps_are_the_eager_steps"),
     "MTBC_DYN_SCALE": ("0", "trainer.FusedTrainStep(loss_scale=None) trains with the device-side dynamic loss scale (loss_scale.DynamicLossScale(): start 2^16, found-inf check "
                             "over the flat gradients, skip + halve on overflow, double after 2000 clean steps) instead of the static scale baked into the loss ops: three more "

@@ -65,6 +65,22 @@ def plan_buckets(slots: Sequence[Tuple[int, int, int]], flat_numel: int, n_bucke
     return out
 
 
+def plan_segments(buckets: Sequence[Bucket], n_bwd_ops: int) -> List[Tuple[int, int, Tuple[int, ...]]]:
+    """Where the data-parallel step cuts its backward program of `n_bwd_ops` ops: (first, count, bucket indices) in issue order -- the ops
+    [first, first + count) are issued, then the all-reduces of the named buckets (indices into `buckets`, in that order).  One entry per bucket,
+    ending behind its `ready_op` (clamped to the program's end); a bucket whose `ready_op` has been passed already gets an EMPTY range (count 0):
+    its all-reduce follows its predecessor's back to back.  Ops behind the last bucket form a closing entry without buckets.  The ranges tile
+    [0, n_bwd_ops) in order and every bucket appears exactly once."""
+    out, done = [], 0
+    for i, b in enumerate(buckets):
+        upto = max(done, min(n_bwd_ops, b.ready_op + 1))
+        out.append((done, upto - done, (i,)))
+        done = upto
+    if done < n_bwd_ops or not out:
+        out.append((done, n_bwd_ops - done, ()))
+    return out
+
+
 def shard_positions(positions: np.ndarray, rank: int, world: int, global_batch: int, step: int) -> np.ndarray:
     """Batch `step` of a global index list, cut into `world` equal contiguous shards: rank r takes
     rows [r*G/world, (r+1)*G/world) of the global batch, so the union over ranks IS the single-GPU batch."""
@@ -419,16 +435,24 @@ def _mask_of(step, st) -> torch.Tensor:
     return t
 
 
-def _capture(body):
-    """`body`'s launches as ONE hipGraph, captured on a fresh side stream that joins the current one on both sides."""
+def _capture(body, error_mode: str = "global"):
+    """`body`'s launches as ONE hipGraph, captured on a fresh side stream that joins the current one on both sides.  `error_mode`: torch's
+    capture_error_mode ("global", its default, for every single-device capture)."""
     cur = torch.cuda.current_stream()
     side = torch.cuda.Stream()
     side.wait_stream(cur)
     g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
+    with torch.cuda.graph(g, stream=side, capture_error_mode=error_mode):
         body()
     cur.wait_stream(side)
     return g
+
+
+def _capture_segment(body):
+    """`_capture` for one segment of the data-parallel step.  A process group is alive beside these captures, and its watchdog thread polls events of
+    earlier collectives whenever it likes: under the global mode such a call from ANOTHER thread invalidates a capture in flight.  The thread-local mode
+    still refuses every unsafe call of the capturing thread itself, which is all a segment body could get wrong."""
+    return _capture(body, error_mode="thread_local")
 
 
 def run_or_replay(owner, st, key, body, capture=_capture) -> None:
@@ -449,6 +473,42 @@ def run_or_replay(owner, st, key, body, capture=_capture) -> None:
     else:
         ent[1] += 1
         body()
+
+
+class SegmentGraphs:
+    """The hipGraphs of one compiled step replayed in segments (`run_or_replay_segments`), in issue order: ONE object in the entry's graph slot."""
+
+    def __init__(self, graphs):
+        self.graphs = list(graphs)
+
+    def __len__(self) -> int:
+        return len(self.graphs)
+
+
+def run_or_replay_segments(owner, st, key, bodies, between, capture=_capture_segment, quiesce=None) -> None:
+    """`run_or_replay` for a step that is a LIST of static bodies with eager work between them (the data-parallel step: the bucket all-reduces stay
+    with the host): `between(i)` runs right behind segment i, exactly once per segment per call, whether segment i ran eager or as a replay.  The
+    same entry [key, eager calls, graph] in the same two places; the graph slot holds one SegmentGraphs.  Eager for the first two calls; the third
+    calls `quiesce()` (nothing of an earlier step may still be in flight on another stream of ours while a capture is open), captures EVERY body --
+    a capture executes nothing, so no `between` is due yet -- and then replays like every later call."""
+    ents = st.__dict__.setdefault("_graph_ents", {})
+    ent = ents.get(id(owner))
+    if ent is None or ent[0] != key:
+        ents[id(owner)] = ent = [key, 0, None]
+    owner._graphs[id(st)] = ent
+    if ent[2] is None and ent[1] >= 2:
+        if quiesce is not None:
+            quiesce()
+        ent[2] = SegmentGraphs(capture(body) for body in bodies)
+    if ent[2] is not None:
+        for i, g in enumerate(ent[2].graphs):
+            g.replay()
+            between(i)
+    else:
+        ent[1] += 1
+        for i, body in enumerate(bodies):
+            body()
+            between(i)
 
 
 class MetricsTable:
@@ -631,8 +691,11 @@ class FusedTrainStep:
         self._table = MetricsTable(model, self.metrics_capacity, distributed=distributed) if self.metrics else None
         # graph: replay each compiled step as ONE hipGraph from its third call on (None: the MTBC_GRAPH switch).  The step is a static list of ~380
         # launches with every pointer resolved at plan time -- exactly what a graph holds; what changes from step to step (the batch, the learning
-        # rate, Adam's bias corrections, the shard weight) lives in device buffers written BEFORE the replay.  Not under data parallel (the bucket
-        # all-reduces are issued between program ranges by the host).
+        # rate, Adam's bias corrections, the shard weight) lives in device buffers written BEFORE the replay.  Under data parallel the bucket
+        # all-reduces are issued between ranges of the backward program by the host, and they stay there: the step is replayed as a short CHAIN of
+        # hipGraphs, one per range (`plan_segments`, `run_or_replay_segments`) plus one for the update, with the event records, the waits and the
+        # collectives eager between them -- no collective is captured, no graph depends on the communication stream.  Bit-equal to the eager
+        # distributed step (which a step with distributed=True, graph=True used to be: the switch was ignored there).
         self.graph = _sw.flag("MTBC_GRAPH") if graph is None else bool(graph)
         # loss_scale: None = the model's static scale baked into the loss ops (65536 in fp16 mode, 1 otherwise; None + the MTBC_DYN_SCALE switch = "dynamic");
         # "dynamic" or a loss_scale.DynamicLossScale = torch.amp.GradScaler's rule on the device: three more launches per step (begin, found-inf check over
@@ -813,10 +876,84 @@ class FusedTrainStep:
         self._count_loss(self.losses)
         return self.losses
 
+    def _dp_segments(self, st, update):
+        """The data-parallel step as (bodies, between, ranges): `bodies` are its static runs of launches on the compute stream -- the dynamic scale's
+        `begin`, pack, forward, losses, metrics and the first backward range; one body per further NON-EMPTY backward range of `plan_segments`; then
+        `update` -- and `between(i)` is the host's work behind body i: per bucket that became ready, an event record on the compute stream and, on the
+        communication stream, the wait and the all-reduce; behind the last backward range also the join.  A bucket with an empty range rides with
+        the range in front of it.  `begin` stands in front, where the eager step has always had it: the loss ops read the word it writes."""
+        P, sc = st.programs, self.scaler
+        ranges = plan_segments(st.buckets, P["bwd"].n)
+        groups = []                     # [first, count, bucket indices]: entry 0 always opens one, an empty range joins its predecessor
+        for first, count, bks in ranges:
+            if groups and count == 0:
+                groups[-1][2].extend(bks)
+            else:
+                groups.append([first, count, list(bks)])
+        events = st.__dict__.get("_dp_events")
+        if events is None or len(events) != len(st.buckets):          # one event per bucket, for the life of the compiled step
+            events = st.__dict__["_dp_events"] = [torch.cuda.Event() for _ in st.buckets]
+
+        def front():
+            if sc is not None:
+                self._begin_dynamic(st, fills=False)
+            P["pack"].run()
+            P["fwd"].run()
+            P["loss"].run()
+            if self.metrics:            # before the first range of the backward, which reuses the outputs' memory; on the compute stream
+                self._append_metrics(st)
+            P["bwd"].run(groups[0][0], groups[0][1])
+
+        def backward_range(first, count):
+            return lambda: P["bwd"].run(first, count)
+
+        def between(i):
+            if i >= len(groups):        # behind the update: nothing
+                return
+            cur = torch.cuda.current_stream()
+            for k in groups[i][2]:
+                events[k].record(cur)
+                with torch.cuda.stream(self.comm_stream):
+                    self.comm_stream.wait_event(events[k])
+                    allreduce_buckets(self.model.flat_g, [st.buckets[k]])
+            if i == len(groups) - 1:
+                cur.wait_stream(self.comm_stream)
+
+        bodies = [front] + [backward_range(first, count) for first, count, _ in groups[1:]] + [update]
+        return bodies, between, tuple((first, count) for first, count, _ in ranges)
+
+    def _run_distributed(self, st) -> torch.Tensor:
+        """The data-parallel step: its segments (`_dp_segments`) issued one after the other, or -- graph=True -- replayed as a chain of hipGraphs
+        (`run_or_replay_segments`) with the same eager work between them.  What `_run_graph` keeps outside its captured body stays outside here."""
+        opt, sc = self.opt, self.scaler
+        if not self.graph:
+            if sc is not None:
+                self._begin_dynamic(st)
+            bodies, between, _ = self._dp_segments(st, lambda: self._apply_update(st))
+            for i, body in enumerate(bodies):
+                body()
+                between(i)
+        else:
+            if sc is None:
+                opt.grad_scale = (1.0 / self.world) / getattr(st, "loss_scale", 1.0)
+                opt.advance_dynamic()
+            else:
+                opt._ensure_state()
+                self._begin_dynamic(st)
+            bodies, between, ranges = self._dp_segments(st, opt.launch_dynamic if sc is None else (lambda: self._apply_update(st)))
+            key = (id(self), opt.graph_key() if sc is None else (opt.graph_key(dynamic=False), sc.graph_key()), self.metrics, ranges, len(st.buckets))
+            run_or_replay_segments(self, st, key, bodies, between, quiesce=self.comm_stream.synchronize)
+        self.losses = st.plan.loss_out
+        self._coop_err = self.model.coop_error_word()      # ONE word per model: every compiled step's kernels set it
+        self._count_loss(self.losses)
+        return self.losses
+
     def run(self, st) -> torch.Tensor:
         """One optimisation step on the batch already resident in the plan's buffers."""
         if self.graph and not self.distributed:
             return self._run_graph(st)
+        if self.distributed:
+            return self._run_distributed(st)
         P = st.programs
         if self.scaler is not None:
             self._begin_dynamic(st)
@@ -824,26 +961,9 @@ class FusedTrainStep:
         P["pack"].run()
         P["fwd"].run()
         P["loss"].run()
-        if self.metrics:            # before the (first range of the) backward, which reuses the outputs' memory; on the compute stream
+        if self.metrics:            # before the backward, which reuses the outputs' memory
             self._append_metrics(st)
-        if not self.distributed:
-            P["bwd"].run()
-        else:
-            cur = torch.cuda.current_stream()
-            done = 0
-            for b in st.buckets:
-                upto = min(P["bwd"].n, b.ready_op + 1)
-                if upto > done:
-                    P["bwd"].run(done, upto - done)
-                    done = upto
-                ev = torch.cuda.Event()
-                ev.record(cur)
-                with torch.cuda.stream(self.comm_stream):
-                    self.comm_stream.wait_event(ev)
-                    allreduce_buckets(self.model.flat_g, [b])
-            if done < P["bwd"].n:
-                P["bwd"].run(done, P["bwd"].n - done)
-            cur.wait_stream(self.comm_stream)
+        P["bwd"].run()
         self._apply_update(st)
         self.losses = st.plan.loss_out
         self._coop_err = self.model.coop_error_word()      # ONE word per model: every compiled step's kernels set it
