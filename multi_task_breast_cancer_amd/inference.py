@@ -336,7 +336,7 @@ class FusedSegTestStep:
 
     def __init__(self, model, fill_holes: bool = True, keep_masks: bool = False):
         self.model, self.fill_holes, self.keep_masks = model, bool(fill_holes), bool(keep_masks)
-        self._error = None
+        self._error = self._scratch = None
         self.reset()
 
     def reset(self) -> None:
@@ -357,6 +357,16 @@ class FusedSegTestStep:
         st.programs["fwd"].run()
         self._coop_err = self.model.coop_error_word()
         self.evaluate_logits(st.segs[-1].data, mask, patient_id, class_name)
+
+    @torch.no_grad()
+    def indexed(self, dataset, index) -> None:
+        """`__call__` from a device-resident dataset (device_data.DeviceDataset): one assembly launch (identity transform) into the plan's input
+        and a mask plane of the batch's own; the labels go to a scratch column nothing reads."""
+        st = self.model.compiled(len(index), dataset.H, dataset.W)
+        if self._scratch is None or self._scratch.shape[0] != st.N:
+            self._scratch = torch.empty(st.N, 1, dtype=torch.float32, device=dataset.device)
+        image, mask, _ = dataset.assemble(index, None, n_onehot=0, out=(st.x.data, torch.empty_like(st.segs[-1].data), self._scratch))
+        self(image, mask)
 
     @torch.no_grad()
     def evaluate_logits(self, seg_logits: torch.Tensor, mask: torch.Tensor, patient_id=None, class_name=None) -> None:

@@ -11,7 +11,7 @@ No host synchronisation happens inside a step: the loss scalars and the NaN flag
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, NamedTuple, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import os
 
@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import checkpoint as CK
 from . import switches as _sw
 from .criterions import exit_on_nan
 from .loss_scale import betas_of
@@ -375,6 +376,114 @@ class SegTrainMetrics(NamedTuple):
     table: np.ndarray       # (batches, 4) int64: tp, fp, fn, samples of each batch
 
 
+# ---- the task of a model, decided once: everything the multi-task, the segmentation and the classification driver do differently, as data
+@dataclass(frozen=True)
+class Task:
+    name: str                           # as the refusals say it: "a {name}-only model"
+    seg: bool                           # a segmentation head: batches carry a mask, the metrics call fills the Dice rows
+    cls: bool                           # a classification head: batches carry a label, the metrics call fills the confusion matrix
+    metrics_fn: Tuple[str, str]         # the metrics entry point of _lib (training, validation); L.check is told the name without its prefix
+    metrics_args: Tuple[type, type]     # its argument struct (training, validation)
+    cls_field: Optional[str]            # that struct's name for the class output
+    scores: Callable                    # (float64 confusion matrix, binary) -> (accuracy, F1) as this driver computes them
+    epoch_metrics: Callable             # (TrainMetrics, mean loss of the steps, binary) -> what FusedTrainStep.epoch_metrics() returns
+    train_fields: Tuple[str, ...]       # the fields of that result behind the loss in the training epoch's tuple
+    val_fields: Tuple[str, ...]         # the validation epoch's tuple, out of loss, dice, accuracy, f1, seg_loss, cls_loss
+    header: str                         # metrics.csv: its header, the formatter of a row and the row's values, out of epoch, lr, test_dice,
+    row: Callable                       # train_loss, train_<train_fields> and val_<val_fields>
+    row_fields: Tuple[str, ...]
+    log: str                            # the epoch's log line over the same names plus patience, epoch_time and best
+    lr_at_start: bool                   # the row's learning rate is read before the epoch (else behind the scheduler step)
+    tests_every_epoch: bool             # fit_fold runs a testing phase behind every epoch and writes its mean DICE into the row
+
+    @property
+    def single(self) -> bool:
+        return not (self.seg and self.cls)
+
+    @property
+    def batch_fields(self) -> Tuple[str, ...]:
+        """What a batch dict of this driver's loader carries beside the image, in the order the steps take it."""
+        return tuple(k for k, has in (("mask", self.seg), ("label", self.cls)) if has)
+
+
+def _cls_epoch_metrics(m: TrainMetrics, loss: float, binary: bool) -> ClsTrainMetrics:
+    accuracy, f1 = cls_driver_scores(m.conf, binary)
+    return ClsTrainMetrics(loss, accuracy, f1, m.batches, m.conf)
+
+
+MULTI_TASK = Task(          # training_multitask.py
+    "multi-task", True, True, ("mtbc_train_metrics", "mtbc_eval_metrics"), (L.TrainMetricsArgs, L.EvalMetricsArgs), "cls_logits",
+    scores=lambda conf, binary: classification_scores(conf), epoch_metrics=lambda m, loss, binary: m,
+    train_fields=("dice", "accuracy", "f1"), val_fields=("loss", "dice", "accuracy", "f1", "seg_loss", "cls_loss"),
+    header=CK.METRICS_HEADER, row=CK.metrics_row,
+    row_fields=("epoch", "lr", "train_loss", "val_loss", "train_dice", "val_dice", "train_accuracy", "train_f1", "val_accuracy", "val_f1"),
+    log="EPOCH {epoch} --> || Training loss {train_loss:.4f} || Validation loss {val_loss:.4f} || Segmentation val loss {val_seg_loss:.4f} "
+        "|| Classification val loss {val_cls_loss:.4f} || Training DICE {train_dice:.4f} || Validation DICE  {val_dice:.4f} "
+        "|| Training ACC {train_accuracy:.4f} || Training F1 {train_f1:.4f} || Validation ACC {val_accuracy:.4f} || Validation F1 {val_f1:.4f} "
+        "|| Patience: {patience} || Epoch time: {epoch_time:.4f}|| Best validation performance: {best:.4f}",
+    lr_at_start=True, tests_every_epoch=False)
+SEGMENTATION = Task(        # training_segmentation.py: the confusion matrix stays zero, the struct has neither `conf` nor `n_logits`
+    "segmentation", True, False, ("mtbc_seg_step_metrics",) * 2, (L.SegStepMetricsArgs,) * 2, None,
+    scores=MULTI_TASK.scores, epoch_metrics=lambda m, loss, binary: SegTrainMetrics(loss, m.dice, m.batches, m.table),
+    train_fields=("dice",), val_fields=("loss", "dice"), header=CK.SEG_METRICS_HEADER, row=CK.seg_metrics_row,
+    row_fields=("epoch", "lr", "train_dice", "val_dice", "test_dice", "train_loss", "val_loss"),
+    log="EPOCH {epoch} --> || Training loss {train_loss:.4f} || Validation loss {val_loss:.4f} || Training DICE {train_dice:.4f} "
+        "|| Validation DICE  {val_dice:.4f} || Patience: {patience} || Epoch time: {epoch_time:.4f} || LR: {lr:.8f}",
+    lr_at_start=False, tests_every_epoch=True)
+CLASSIFICATION = Task(      # training_classification.py: the samples launch alone, tp / fp / fn stay zero; the struct reads the model's OUTPUT
+    "classification", False, True, ("mtbc_cls_step_metrics",) * 2, (L.ClsStepMetricsArgs,) * 2, "cls_out",
+    scores=cls_driver_scores, epoch_metrics=_cls_epoch_metrics,
+    train_fields=("accuracy", "f1"), val_fields=("loss", "accuracy", "f1"), header=CK.CLS_METRICS_HEADER, row=CK.cls_metrics_row,
+    row_fields=("epoch", "lr", "train_loss", "val_loss", "train_accuracy", "train_f1", "val_accuracy", "val_f1"),
+    log="EPOCH {epoch} --> || Training loss {train_loss:.4f} || Validation loss {val_loss:.4f} || Training ACC {train_accuracy:.4f} "
+        "|| Training F1 {train_f1:.4f} || Validation ACC {val_accuracy:.4f} || Validation F1 {val_f1:.4f} || Patience: {patience} "
+        "|| Epoch time: {epoch_time:.4f}",
+    lr_at_start=True, tests_every_epoch=False)
+
+
+def task_of(model) -> Task:
+    return CLASSIFICATION if is_cls_only(model) else SEGMENTATION if is_seg_only(model) else MULTI_TASK
+
+
+def step_task(step) -> Task:
+    """The task of a training, evaluation or test step by its public attributes; an object without them (a stand-in) is multi-task."""
+    return CLASSIFICATION if getattr(step, "cls_only", False) else SEGMENTATION if getattr(step, "seg_only", False) else MULTI_TASK
+
+
+def _resolve_step(model, owner: str, cls_name: str, distributed: bool, alpha, inversely_weighted, n_classes, focal_weight, cls_criterion,
+                  seg_criterion, before_criterion: Callable = lambda: None) -> tuple:
+    """The prologue FusedTrainStep and FusedEvalStep share -> (task, alpha, inversely_weighted, n_classes, seg_criterion, binary, cls_gamma,
+    focal_weight).  None = "not given": alpha is required, n_classes defaults to 3 and cls_criterion to "Focal" for a model with a classification
+    head, and not given is all a segmentation-only model accepts; inversely_weighted (default True) and seg_criterion (default "DICE") likewise,
+    and not given is all a classification-only model accepts.  `before_criterion`: the caller's own refusals that come in front of the criterion's."""
+    task = task_of(model)
+    _check_single_device(model, distributed, owner)
+    if not task.seg:
+        _check_cls_only(alpha, inversely_weighted, seg_criterion, distributed, owner)
+        alpha = 0.0
+    inversely_weighted = True if inversely_weighted is None else inversely_weighted
+    seg_criterion = "DICE" if seg_criterion is None else seg_criterion
+    if not task.cls:
+        _check_seg_only(alpha, n_classes, focal_weight, cls_criterion, distributed, owner)
+        alpha = 1.0
+    else:
+        if alpha is None:
+            raise TypeError(f"{cls_name}: alpha (the weight of the segmentation loss in the mix) is required for a multi-task model")
+        n_classes = 3 if n_classes is None else n_classes
+        cls_criterion = "Focal" if cls_criterion is None else cls_criterion
+    before_criterion()
+    # seg_criterion: the reference's `loss.function` (experiment_init.py:199-232) -- "DICE" | "BCE" | "FocalDICE" | "Jaccard", all in the same
+    # two loss ops of the step program (mtbc_dice_args.kind); the remaining names are not on HIP (experiment_init.init_criterion_segmentation).
+    seg_criterion = _check_seg_criterion(seg_criterion, distributed)
+    heads = _check_heads(model, n_classes, cls_criterion, focal_weight, owner) if task.cls else (False, 2.0, None)
+    return (task, float(alpha), bool(inversely_weighted), n_classes, seg_criterion) + heads
+
+
+def _n_onehot(step) -> int:
+    """The width of the one-hot class target the batch-assembly launch writes: none for the binary head (the label itself) or without a head."""
+    return 0 if step.binary or not step.task.cls else 3
+
+
 def _fused_loss(step) -> dict:
     """The `fused_loss` settings a step compiles its plan with.  A training and an evaluation step with the same (alpha, weighting, criteria) build
     equal dicts and so share one compiled plan at equal (N, H, W); only a dynamic loss scale adds a key."""
@@ -520,10 +629,11 @@ class MetricsTable:
     def __init__(self, model, capacity: int, validation: bool = False, distributed: bool = False):
         self.model, self.capacity, self.eval, self.distributed = model, int(capacity), bool(validation), bool(distributed)
         self.words = _EVAL if self.eval else _TRAIN
-        self.seg_only = is_seg_only(model)      # mtbc_seg_step_metrics: the same rows, no class arguments (the confusion matrix stays zero)
-        self.cls_only = is_cls_only(model)      # mtbc_cls_step_metrics: the samples launch alone (tp / fp / fn stay zero)
+        self.task = task_of(model)
+        self.entry = self.task.metrics_fn[self.eval]     # the metrics call of _lib; L.check is told its name without the prefix
+        self.label = self.entry[len("mtbc_"):]
         self.counts = self.state = self.loss_rows = self.weight = None
-        self._args = {}             # id(compiled step) -> (the step, its argument struct); None -> the empty shard's
+        self._args = {}             # id(compiled step) -> (the step, its argument struct, the entry point); None -> the empty shard's
 
     def buffers(self) -> "MetricsTable":
         if self.counts is None:
@@ -543,72 +653,33 @@ class MetricsTable:
 
     def _arguments(self, st, n_logits):
         """The argument struct of one compiled step (st = None: of the empty shard, N = 0), which never changes: outputs and accumulators stay where
-        they are.  Behind the loss program the plan's buffers hold fp32 NCHW logits of the last head, the mask, the class logits and their target,
-        in every compute mode."""
+        they are.  Behind the loss program the plan's buffers hold fp32 NCHW logits of the last head, the mask, the class output and its target,
+        in every compute mode; the struct carries the pair of each head the task has, and `loss_in` stays NULL for training."""
         self.buffers()
-        if self.seg_only:
-            return self._seg_arguments(st)
-        if self.cls_only:
-            return self._cls_arguments(st, n_logits)
-        a = L.EvalMetricsArgs() if self.eval else L.TrainMetricsArgs()
-        if st is None:
-            a.N, a.n_seg, a.n_logits = 0, 0, n_logits
-        else:
-            seg, logits = st.segs[-1].data, st.logits.data
-            loss_out = (st.plan.loss_out,) if self.eval else ()
-            for t in (seg, st.mask, logits, st.onehot) + loss_out:
-                if t.dtype != torch.float32 or not t.is_contiguous():
-                    raise L.MtbcError(f"{self.words['kind']} metrics: the step's outputs are not contiguous fp32 buffers")
-            if seg.numel() != st.mask.numel() or logits.numel() != st.onehot.numel() or any(t.numel() < 4 for t in loss_out):
-                raise L.MtbcError(f"{self.words['kind']} metrics: outputs and targets differ in size")
-            a.seg_logits, a.mask, a.n_seg = seg.data_ptr(), st.mask.data_ptr(), seg.numel()
-            a.cls_logits, a.target, a.N, a.n_logits = logits.data_ptr(), st.onehot.data_ptr(), st.N, st.logits.C
-            if self.eval:
-                a.loss_in = st.plan.loss_out.data_ptr()
-        a.table, a.conf, a.state, a.capacity = self.counts.data_ptr(), self.counts.data_ptr() + self.capacity * 32, self.state.data_ptr(), self.capacity
-        if self.eval:
-            a.loss_rows = self.loss_rows.data_ptr()
-            a.shard_weight = self.weight.data_ptr() if self.distributed else None
-        return a
-
-    def _seg_arguments(self, st):
-        """`_arguments` of a segmentation-only step: mtbc_seg_step_metrics_args; loss_in stays NULL for training."""
-        a = L.SegStepMetricsArgs()
-        if st is None:
-            a.N, a.n_seg = 0, 0
-        else:
-            seg = st.segs[-1].data
-            loss_out = (st.plan.loss_out,) if self.eval else ()
-            for t in (seg, st.mask) + loss_out:
-                if t.dtype != torch.float32 or not t.is_contiguous():
-                    raise L.MtbcError(f"{self.words['kind']} metrics: the step's outputs are not contiguous fp32 buffers")
-            if seg.numel() != st.mask.numel() or any(t.numel() < 4 for t in loss_out):
-                raise L.MtbcError(f"{self.words['kind']} metrics: outputs and targets differ in size")
-            a.seg_logits, a.mask, a.n_seg, a.N = seg.data_ptr(), st.mask.data_ptr(), seg.numel(), st.N
-            if self.eval:
-                a.loss_in = st.plan.loss_out.data_ptr()
-        a.table, a.state, a.capacity = self.counts.data_ptr(), self.state.data_ptr(), self.capacity
-        if self.eval:
-            a.loss_rows = self.loss_rows.data_ptr()
-            a.shard_weight = self.weight.data_ptr() if self.distributed else None
-        return a
-
-    def _cls_arguments(self, st, n_logits):
-        """`_arguments` of a classification-only step: mtbc_cls_step_metrics_args on the model's OUTPUT; loss_in stays NULL for training."""
-        a = L.ClsStepMetricsArgs()
-        a.N, a.n_logits = 0, n_logits
+        task = self.task
+        a = task.metrics_args[self.eval]()
+        seg = cls = None
         if st is not None:
-            out = st.logits.data
+            seg = (st.segs[-1].data, st.mask) if task.seg else None
+            cls = (st.logits.data, st.onehot) if task.cls else None
+            pairs = [p for p in (seg, cls) if p is not None]
             loss_out = (st.plan.loss_out,) if self.eval else ()
-            for t in (out, st.onehot) + loss_out:
+            for t in (*(t for p in pairs for t in p), *loss_out):
                 if t.dtype != torch.float32 or not t.is_contiguous():
                     raise L.MtbcError(f"{self.words['kind']} metrics: the step's outputs are not contiguous fp32 buffers")
-            if out.numel() != st.onehot.numel() or any(t.numel() < 4 for t in loss_out):
+            if any(x.numel() != y.numel() for x, y in pairs) or any(t.numel() < 4 for t in loss_out):
                 raise L.MtbcError(f"{self.words['kind']} metrics: outputs and targets differ in size")
-            a.cls_out, a.target, a.N, a.n_logits = out.data_ptr(), st.onehot.data_ptr(), st.N, st.logits.C
+            a.N = st.N
             if self.eval:
                 a.loss_in = st.plan.loss_out.data_ptr()
-        a.table, a.conf, a.state, a.capacity = self.counts.data_ptr(), self.counts.data_ptr() + self.capacity * 32, self.state.data_ptr(), self.capacity
+        if seg is not None:
+            a.seg_logits, a.mask, a.n_seg = seg[0].data_ptr(), seg[1].data_ptr(), seg[0].numel()
+        if task.cls:
+            a.n_logits, a.conf = n_logits if st is None else st.logits.C, self.counts.data_ptr() + self.capacity * 32
+            if cls is not None:
+                setattr(a, task.cls_field, cls[0].data_ptr())
+                a.target = cls[1].data_ptr()
+        a.table, a.state, a.capacity = self.counts.data_ptr(), self.state.data_ptr(), self.capacity
         if self.eval:
             a.loss_rows = self.loss_rows.data_ptr()
             a.shard_weight = self.weight.data_ptr() if self.distributed else None
@@ -621,17 +692,27 @@ class MetricsTable:
         key = None if st is None else id(st)
         ent = self._args.get(key)
         if ent is None or ent[0] is not st:
-            self._args[key] = ent = (st, self._arguments(st, n_logits))
-        lib = L.load()
-        fn = lib.mtbc_seg_step_metrics if self.seg_only else lib.mtbc_cls_step_metrics if self.cls_only else lib.mtbc_eval_metrics if self.eval \
-            else lib.mtbc_train_metrics
-        L.check(fn(C.byref(ent[1]), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                "seg_step_metrics" if self.seg_only else "cls_step_metrics" if self.cls_only else "eval_metrics" if self.eval else "train_metrics")
+            self._args[key] = ent = (st, self._arguments(st, n_logits), getattr(L.load(), self.entry))
+        L.check(ent[2](C.byref(ent[1]), C.c_void_p(torch.cuda.current_stream().cuda_stream)), self.label)
 
     def reduce(self, coop_err: Optional[torch.Tensor] = None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         """`_reduce_packed` of these buffers: under `distributed` one sum-all-reduce per array (row b of the sum is GLOBAL batch b), one read each."""
         cap = self.capacity
         return _reduce_packed(self.counts[:cap * 4], self.counts[cap * 4:], self.state, self.loss_rows, coop_err, distributed=self.distributed)
+
+
+def _issue_forward(step, st) -> None:
+    """What every path of the training step issues in front of its backward program, a static list of launches on the current stream (capturable):
+    the dynamic scale's `begin` (the loss ops read the word it writes), pack, forward, losses and -- before the backward, which reuses the
+    outputs' memory -- the metrics call, appending at the device cursor."""
+    P = st.programs
+    if step.scaler is not None:
+        step._begin_dynamic(st, fills=False)
+    P["pack"].run()
+    P["fwd"].run()
+    P["loss"].run()
+    if step.metrics:
+        step._append_metrics(st)
 
 
 class FusedTrainStep:
@@ -660,28 +741,10 @@ class FusedTrainStep:
                  distributed: bool = False, n_buckets: int = 4, focal_weight: Optional[torch.Tensor] = None,
                  cls_criterion: Optional[str] = None, graph: Optional[bool] = None, loss_scale=None, metrics: bool = False,
                  metrics_capacity: int = 4096, seg_criterion: Optional[str] = None):
-        # alpha is required, n_classes defaults to 3 and cls_criterion to "Focal" for a multi-task model; None = "not given", which is all a
-        # segmentation-only model accepts.  inversely_weighted (default True) and seg_criterion (default "DICE") likewise: None = "not given",
-        # which is all a classification-only model accepts
-        self.seg_only = is_seg_only(model)
-        self.cls_only = is_cls_only(model)
-        _check_single_device(model, distributed, "the fused step")
-        if self.cls_only:
-            _check_cls_only(alpha, inversely_weighted, seg_criterion, distributed, "the fused step")
-            alpha = 0.0
-        inversely_weighted = True if inversely_weighted is None else inversely_weighted
-        seg_criterion = "DICE" if seg_criterion is None else seg_criterion
-        if self.seg_only:
-            _check_seg_only(alpha, n_classes, focal_weight, cls_criterion, distributed, "the fused step")
-            alpha = 1.0
-        else:
-            if alpha is None:
-                raise TypeError("FusedTrainStep: alpha (the weight of the segmentation loss in the mix) is required for a multi-task model")
-            n_classes = 3 if n_classes is None else n_classes
-            cls_criterion = "Focal" if cls_criterion is None else cls_criterion
-        # seg_criterion: the reference's `loss.function` (experiment_init.py:199-232) -- "DICE" | "BCE" | "FocalDICE" | "Jaccard", all in the same
-        # two loss ops of the step program (mtbc_dice_args.kind); the remaining names are not on HIP (experiment_init.init_criterion_segmentation).
-        self.seg_criterion = _check_seg_criterion(seg_criterion, distributed)
+        # the task of the model, the defaults of the arguments not given and what each task refuses: `_resolve_step`, shared with FusedEvalStep
+        (self.task, self.alpha, self.iw, self.n_classes, self.seg_criterion, self.binary, self.cls_gamma, self.focal_weight) = _resolve_step(
+            model, "the fused step", "FusedTrainStep", distributed, alpha, inversely_weighted, n_classes, focal_weight, cls_criterion, seg_criterion)
+        self.seg_only, self.cls_only = not self.task.cls, not self.task.seg
         # metrics: off = exactly the launches of a step without it.  metrics_capacity: rows (= batches per epoch) of the device table, 32 bytes each;
         # allocated once and never moved, so a captured graph stays valid across epochs.
         self.metrics = bool(metrics)
@@ -715,15 +778,11 @@ class FusedTrainStep:
         if self.scaler is not None:
             self.scaler.attach(optimizer)
         self._graphs = {}
-        if self.seg_only:
-            self.binary, self.cls_gamma, self.focal_weight = False, 2.0, None
-        else:
-            self.binary, self.cls_gamma, self.focal_weight = _check_heads(model, n_classes, cls_criterion, focal_weight, "the fused step")
+        self._sums_loss = self.task.single and self.metrics
         self._epoch_loss = None         # single-task models, metrics=True: device float64 [sum of the steps' loss, steps] behind epoch_metrics()
         self._scratch_target = None     # segmentation only: where the batch-assembly launch puts the labels nobody reads
         self._scratch_mask = None       # classification only: where it puts the masks nobody reads
         self.model, self.opt = model, optimizer
-        self.alpha, self.iw, self.n_classes = float(alpha), bool(inversely_weighted), n_classes
         self.distributed = distributed
         self.n_buckets = n_buckets
         self.world = 1
@@ -761,7 +820,7 @@ class FusedTrainStep:
         global batch's."""
         N, _, H, W = image.shape
         st = self._compiled(N, H, W)
-        if self.cls_only and label is None:     # (image, label): this driver's batches carry no mask
+        if label is None and not self.task.seg:     # (image, label): the batches of a driver without a segmentation head carry no mask
             mask, label = None, mask
         fill_batch(st, image, mask, label, self.binary)
         self._set_shard_weight(st, weight)
@@ -783,7 +842,7 @@ class FusedTrainStep:
         In stream order in front of the step and, with graph=True, outside the replayed region, where `load_batch` sits.  `weight` as in `load_batch`."""
         _check_in_channels(self.model, dataset)
         st = self._compiled(len(index), dataset.H, dataset.W)
-        dataset.assemble(index, params, n_onehot=0 if self.binary or self.seg_only else 3, out=(st.x.data, _mask_of(self, st), _target_of(self, st)))
+        dataset.assemble(index, params, n_onehot=_n_onehot(self), out=(st.x.data, _mask_of(self, st), _target_of(self, st)))
         self._set_shard_weight(st, weight)
         return st
 
@@ -795,7 +854,7 @@ class FusedTrainStep:
 
     def _append_metrics(self, st) -> None:
         """`mtbc_train_metrics` on the outputs of the forward that has just run (st = None: the empty shard)."""
-        self._metrics_table().append(st, 0 if self.seg_only else self._st.logits.C)
+        self._metrics_table().append(st, self._st.logits.C if self.task.cls else 0)
 
     def begin_epoch_metrics(self) -> None:
         """Zero the table, the confusion matrix and the cursor in stream order (outside any replayed graph: the buffers stay where they are)."""
@@ -804,8 +863,8 @@ class FusedTrainStep:
             self._epoch_loss.zero_()
 
     def _count_loss(self, losses: torch.Tensor) -> None:
-        """Segmentation only, metrics=True: the step's loss into the epoch's device sum, in stream order behind the step (outside a replayed graph)."""
-        if (self.seg_only or self.cls_only) and self.metrics:
+        """Single-task models, metrics=True: the step's loss into the epoch's device sum, in stream order behind the step (outside a replayed graph)."""
+        if self._sums_loss:
             if self._epoch_loss is None:
                 self._epoch_loss = torch.zeros(2, dtype=torch.float64, device=losses.device)
             self._epoch_loss[0] += losses[0].double()
@@ -815,13 +874,8 @@ class FusedTrainStep:
         """The epoch so far as the reference's numbers: under data parallel ONE sum-all-reduce of the table and the confusion matrix (row b of the sum is
         GLOBAL batch b), then ONE device-to-host read.  MtbcError when the table was too small or the ranks' cursors disagree."""
         m = train_metrics_from_packed(self._metrics_table().reduce()[0], self.metrics_capacity, self.world)
-        if not (self.seg_only or self.cls_only):
-            return m
-        total, steps = (0.0, 0.0) if self._epoch_loss is None else self._epoch_loss.cpu().tolist()
-        if self.cls_only:
-            accuracy, f1 = cls_driver_scores(m.conf, self.binary)
-            return ClsTrainMetrics(total / steps if steps else 0.0, accuracy, f1, m.batches, m.conf)
-        return SegTrainMetrics(total / steps if steps else 0.0, m.dice, m.batches, m.table)
+        total, steps = (0.0, 0.0) if self._epoch_loss is None else self._epoch_loss.cpu().tolist()      # no sum, no read for a multi-task model
+        return self.task.epoch_metrics(m, total / steps if steps else 0.0, self.binary)
 
     def _apply_update(self, st) -> None:
         """Adam on the (all-reduced) flat gradients: the static path divides the baked loss scale out, the dynamic path checks, skips or applies, and
@@ -845,6 +899,13 @@ class FusedTrainStep:
         allreduce_buckets(self.model.flat_g, self._st.buckets if self._st is not None and self._st.buckets else
                           plan_buckets([(0, self.model.flat_numel, 0)], self.model.flat_numel, 1))
 
+    def _finish(self, st) -> torch.Tensor:
+        """Behind every path of the step, outside any replayed graph: where its loss words and the cooperative kernels' error word are."""
+        self.losses = st.plan.loss_out
+        self._coop_err = self.model.coop_error_word()      # ONE word per model: every compiled step's kernels set it
+        self._count_loss(self.losses)
+        return self.losses
+
     def _run_graph(self, st) -> torch.Tensor:
         """The step as a hipGraph replay (`run_or_replay`), keyed by the optimizer's buffers and dropped when they move."""
         opt = self.opt
@@ -856,14 +917,9 @@ class FusedTrainStep:
             opt._ensure_state()
             self._begin_dynamic(st)               # lr -> the scaler's state; step count, scale and bias corrections are the device's own business
 
-        def body():
-            P = st.programs
-            if sc is not None:
-                self._begin_dynamic(st, fills=False)
-            P["pack"].run(); P["fwd"].run(); P["loss"].run()
-            if self.metrics:                      # a linear chain on the capturing stream: replayed with the step, appending at the device cursor
-                self._append_metrics(st)
-            P["bwd"].run()
+        def body():                               # a linear chain on the capturing stream, the metrics call included: replayed with the step
+            _issue_forward(self, st)
+            st.programs["bwd"].run()
             if sc is None:
                 opt.launch_dynamic()
             else:
@@ -871,10 +927,7 @@ class FusedTrainStep:
 
         key = (id(self), opt.graph_key() if sc is None else (opt.graph_key(dynamic=False), sc.graph_key()), self.metrics)
         run_or_replay(self, st, key, body)
-        self.losses = st.plan.loss_out
-        self._coop_err = self.model.coop_error_word()
-        self._count_loss(self.losses)
-        return self.losses
+        return self._finish(st)
 
     def _dp_segments(self, st, update):
         """The data-parallel step as (bodies, between, ranges): `bodies` are its static runs of launches on the compute stream -- the dynamic scale's
@@ -882,7 +935,7 @@ class FusedTrainStep:
         `update` -- and `between(i)` is the host's work behind body i: per bucket that became ready, an event record on the compute stream and, on the
         communication stream, the wait and the all-reduce; behind the last backward range also the join.  A bucket with an empty range rides with
         the range in front of it.  `begin` stands in front, where the eager step has always had it: the loss ops read the word it writes."""
-        P, sc = st.programs, self.scaler
+        P = st.programs
         ranges = plan_segments(st.buckets, P["bwd"].n)
         groups = []                     # [first, count, bucket indices]: entry 0 always opens one, an empty range joins its predecessor
         for first, count, bks in ranges:
@@ -894,14 +947,8 @@ class FusedTrainStep:
         if events is None or len(events) != len(st.buckets):          # one event per bucket, for the life of the compiled step
             events = st.__dict__["_dp_events"] = [torch.cuda.Event() for _ in st.buckets]
 
-        def front():
-            if sc is not None:
-                self._begin_dynamic(st, fills=False)
-            P["pack"].run()
-            P["fwd"].run()
-            P["loss"].run()
-            if self.metrics:            # before the first range of the backward, which reuses the outputs' memory; on the compute stream
-                self._append_metrics(st)
+        def front():                    # on the compute stream, the metrics call too
+            _issue_forward(self, st)
             P["bwd"].run(groups[0][0], groups[0][1])
 
         def backward_range(first, count):
@@ -943,10 +990,7 @@ class FusedTrainStep:
             bodies, between, ranges = self._dp_segments(st, opt.launch_dynamic if sc is None else (lambda: self._apply_update(st)))
             key = (id(self), opt.graph_key() if sc is None else (opt.graph_key(dynamic=False), sc.graph_key()), self.metrics, ranges, len(st.buckets))
             run_or_replay_segments(self, st, key, bodies, between, quiesce=self.comm_stream.synchronize)
-        self.losses = st.plan.loss_out
-        self._coop_err = self.model.coop_error_word()      # ONE word per model: every compiled step's kernels set it
-        self._count_loss(self.losses)
-        return self.losses
+        return self._finish(st)
 
     def run(self, st) -> torch.Tensor:
         """One optimisation step on the batch already resident in the plan's buffers."""
@@ -954,21 +998,12 @@ class FusedTrainStep:
             return self._run_graph(st)
         if self.distributed:
             return self._run_distributed(st)
-        P = st.programs
         if self.scaler is not None:
             self._begin_dynamic(st)
-            self._begin_dynamic(st, fills=False)
-        P["pack"].run()
-        P["fwd"].run()
-        P["loss"].run()
-        if self.metrics:            # before the backward, which reuses the outputs' memory
-            self._append_metrics(st)
-        P["bwd"].run()
+        _issue_forward(self, st)
+        st.programs["bwd"].run()
         self._apply_update(st)
-        self.losses = st.plan.loss_out
-        self._coop_err = self.model.coop_error_word()      # ONE word per model: every compiled step's kernels set it
-        self._count_loss(self.losses)
-        return self.losses
+        return self._finish(st)
 
     def run_empty(self) -> None:
         """This rank's shard of the (short, last) global batch is EMPTY: contribute a zero gradient to the same
@@ -1053,31 +1088,22 @@ class FusedEvalStep:
         # the metrics launch is `mtbc_seg_step_metrics`, and `result()` is the driver's (val_loss, val_dice)
         # a classification-only model (nets.nnUNetClassifier / UNetPlusPlusClassifier): `validate_one_epoch` of training_classification.py:101-162 --
         # `step(image, label)`, no segmentation argument, the metrics launch is `mtbc_cls_step_metrics`, `result()` is (val_loss, val_acc, val_f1)
-        self.seg_only = is_seg_only(model)
-        self.cls_only = is_cls_only(model)
-        _check_single_device(model, distributed, "FusedEvalStep")
-        if self.cls_only:
-            _check_cls_only(alpha, inversely_weighted, seg_criterion, distributed, "FusedEvalStep")
-            alpha = 0.0
-        inversely_weighted = True if inversely_weighted is None else inversely_weighted
-        seg_criterion = "DICE" if seg_criterion is None else seg_criterion
-        if self.seg_only:
-            _check_seg_only(alpha, n_classes, focal_weight, cls_criterion, distributed, "FusedEvalStep")
-            alpha = 1.0
-        else:
-            if alpha is None:
-                raise TypeError("FusedEvalStep: alpha (the weight of the segmentation loss in the mix) is required for a multi-task model")
-            n_classes = 3 if n_classes is None else n_classes
-            cls_criterion = "Focal" if cls_criterion is None else cls_criterion
         self._scratch_target = self._scratch_mask = None
-        self.model, self.alpha, self.iw, self.n_classes = model, float(alpha), bool(inversely_weighted), n_classes
-        self.on_device, self.distributed, self.capacity = bool(on_device), bool(distributed), int(capacity)
-        if self.distributed and not self.on_device:
-            raise ValueError("FusedEvalStep(distributed=True) needs on_device=True: the ranks' rows are merged from the device table")
-        if graph and not self.on_device:
-            raise ValueError("FusedEvalStep(graph=True) needs on_device=True: the default path's per-batch torch ops are not a static launch list")
-        if self.on_device and self.capacity < 1:
-            raise ValueError("capacity must be at least 1 row")
+        self.model, self.on_device, self.distributed, self.capacity = model, bool(on_device), bool(distributed), int(capacity)
+
+        def on_device_rules():          # behind the task's own refusals, in front of the criterion's
+            if self.distributed and not self.on_device:
+                raise ValueError("FusedEvalStep(distributed=True) needs on_device=True: the ranks' rows are merged from the device table")
+            if graph and not self.on_device:
+                raise ValueError("FusedEvalStep(graph=True) needs on_device=True: the default path's per-batch torch ops are not a static launch list")
+            if self.on_device and self.capacity < 1:
+                raise ValueError("capacity must be at least 1 row")
+
+        # seg_criterion, as `cls_criterion`: the criterion the run trains with
+        (self.task, self.alpha, self.iw, self.n_classes, self.seg_criterion, self.binary, self.cls_gamma, self.focal_weight) = _resolve_step(
+            model, "FusedEvalStep", "FusedEvalStep", distributed, alpha, inversely_weighted, n_classes, focal_weight, cls_criterion, seg_criterion,
+            before_criterion=on_device_rules)
+        self.seg_only, self.cls_only = not self.task.cls, not self.task.seg
         self.graph = self.on_device and (_sw.flag("MTBC_GRAPH") if graph is None else bool(graph))
         self.world = 1
         if self.distributed:
@@ -1085,11 +1111,6 @@ class FusedEvalStep:
             self.world = dist.get_world_size()
         self._graphs = {}
         self._table = MetricsTable(model, self.capacity, validation=True, distributed=self.distributed) if self.on_device else None
-        self.seg_criterion = _check_seg_criterion(seg_criterion, self.distributed)      # as `cls_criterion`: the criterion the run trains with
-        if self.seg_only:
-            self.binary, self.cls_gamma, self.focal_weight = False, 2.0, None
-        else:
-            self.binary, self.cls_gamma, self.focal_weight = _check_heads(model, n_classes, cls_criterion, focal_weight, "FusedEvalStep")
         self._coop_err = None
         self.reset()
 
@@ -1109,7 +1130,7 @@ class FusedEvalStep:
         """`weight`: this rank's share n_local / n_batch of the global batch (distributed=True; None = 1)."""
         N, _, H, W = image.shape
         st = self._compiled(N, H, W)
-        if self.cls_only and label is None:     # (image, label): this driver's batches carry no mask
+        if label is None and not self.task.seg:     # (image, label), as FusedTrainStep.load_batch
             mask, label = None, mask
         fill_batch(st, image, mask, label, self.binary)
         self._evaluate_resident(st, weight)
@@ -1123,7 +1144,7 @@ class FusedEvalStep:
         transform), then the same step program and the same device accumulators.  `weight` as in `__call__`."""
         _check_in_channels(self.model, dataset)
         st = self._compiled(len(index), dataset.H, dataset.W)
-        dataset.assemble(index, None, n_onehot=0 if self.binary or self.seg_only else 3, out=(st.x.data, _mask_of(self, st), _target_of(self, st)))
+        dataset.assemble(index, None, n_onehot=_n_onehot(self), out=(st.x.data, _mask_of(self, st), _target_of(self, st)))
         self._evaluate_resident(st, weight)
 
     def _evaluate_resident(self, st, weight: Optional[float]) -> None:
@@ -1143,21 +1164,16 @@ class FusedEvalStep:
         if self._acc is None:
             self._acc = torch.zeros(5, dtype=torch.float64, device=dev)
             self._conf = torch.zeros(3, 3, dtype=torch.int64, device=dev)
-        if self.cls_only:               # no segmentation head: the loss words and the confusion matrix
-            self._acc[:3] += st.plan.loss_out[:3].double()
-            self._acc[4] += 1
-            return self._count_classes(st, gt_binary)
-        counts = dice_counts(st.segs[-1].data, st.mask)                 # {tp, fp, fn} float64 on the device
-        tp, fp, fn = counts[0], counts[1], counts[2]
-        empty_gt = (tp + fn) == 0
-        dice = torch.where(empty_gt, torch.where((tp + fp) == 0, torch.ones_like(tp), torch.zeros_like(tp)),
-                           2 * tp / torch.clamp(2 * tp + fp + fn, min=1.0))          # metrics.py:255-267
+        if self.task.seg:
+            counts = dice_counts(st.segs[-1].data, st.mask)             # {tp, fp, fn} float64 on the device
+            tp, fp, fn = counts[0], counts[1], counts[2]
+            empty_gt = (tp + fn) == 0
+            self._acc[3] += torch.where(empty_gt, torch.where((tp + fp) == 0, torch.ones_like(tp), torch.zeros_like(tp)),
+                                        2 * tp / torch.clamp(2 * tp + fp + fn, min=1.0))          # metrics.py:255-267
         self._acc[:3] += st.plan.loss_out[:3].double()
-        self._acc[3] += dice
         self._acc[4] += 1
-        if self.seg_only:
-            return
-        self._count_classes(st, gt_binary)
+        if self.task.cls:
+            self._count_classes(st, gt_binary)
 
     def _count_classes(self, st, gt_binary: Optional[torch.Tensor]) -> None:
         logit = st.logits.data.view(st.N, -1)
@@ -1172,7 +1188,7 @@ class FusedEvalStep:
     # ---- on_device=True ------------------------------------------------------------------------------------------------------
     def _append_eval(self, st) -> None:
         """`mtbc_eval_metrics` on the outputs and the loss words of the step program that has just run (st = None: the empty shard)."""
-        self._table.append(st, 0 if self.seg_only else 1 if self.binary else 3)
+        self._table.append(st, (1 if self.binary else 3) if self.task.cls else 0)
 
     def _evaluate_on_device(self, st, weight: Optional[float]) -> None:
         """The batch resident in the plan's buffers as launches only: pack -> forward -> losses -> mtbc_eval_metrics, eager or as one graph replay."""
@@ -1201,33 +1217,27 @@ class FusedEvalStep:
     def result(self):
         if self._acc is None and (self._table is None or self._table.counts is None):
             raise L.MtbcError("FusedEvalStep.result() before any batch was evaluated")
-        if self.on_device:
-            r = eval_result_from_packed(*self._table.reduce(self._coop_err), self.capacity, self.world, cls_only=self.binary if self.cls_only else None)
-            return (r[0], r[1]) if self.seg_only else r
+        task = self.task
+        if self.on_device:              # the 6-tuple, or the classification driver's 3-tuple; the segmentation driver's pair opens the 6-tuple
+            r = eval_result_from_packed(*self._table.reduce(self._coop_err), self.capacity, self.world, cls_only=None if task.seg else self.binary)
+            return r[:len(task.val_fields)]
         err = self._coop_err
         if err is not None and int(err.item()) != 0:
             L.raise_coop_timeout()
         acc = self._acc.cpu().tolist()
-        conf = self._conf.cpu().numpy().astype(np.float64)
         nb = max(acc[4], 1.0)
-        if self.seg_only:               # training_segmentation.py:88
-            return acc[0] / nb, acc[3] / nb
-        if self.cls_only:               # training_classification.py:162
-            return (acc[0] / nb, *cls_driver_scores(conf, self.binary))
-        accuracy, f1w = classification_scores(conf)       # sklearn accuracy_score / f1_score(labels=[0,1,2], average='weighted') (:155-156)
-        return acc[0] / nb, acc[3] / nb, accuracy, f1w, acc[1] / nb, acc[2] / nb
+        # multi-task: sklearn accuracy_score / f1_score(labels=[0,1,2], average='weighted') (:155-156); training_classification.py:162: `cls_driver_scores`
+        accuracy, f1 = task.scores(self._conf.cpu().numpy().astype(np.float64), self.binary)
+        v = {"loss": acc[0] / nb, "dice": acc[3] / nb, "accuracy": accuracy, "f1": f1, "seg_loss": acc[1] / nb, "cls_loss": acc[2] / nb}
+        return tuple(v[k] for k in task.val_fields)
 
 
 def validate_one_epoch(step: FusedEvalStep, loader, device) -> tuple:
     """training_multitask.py:119-159 on the fused evaluation step; `loader` yields the reference's batch dicts."""
     step.reset()
+    fields = ("image",) + step_task(step).batch_fields
     for data in loader:
-        if getattr(step, "seg_only", False):
-            step(data["image"].to(device), data["mask"].to(device))
-        elif getattr(step, "cls_only", False):
-            step(data["image"].to(device), data["label"].to(device))
-        else:
-            step(data["image"].to(device), data["mask"].to(device), data["label"].to(device))
+        step(*(data[k].to(device) for k in fields))
     return step.result()
 
 
@@ -1289,12 +1299,8 @@ def train_one_epoch_with_metrics(step: FusedTrainStep, dataset, tables, lr: Opti
         raise ValueError("train_one_epoch_with_metrics needs a FusedTrainStep built with metrics=True")
     step.begin_epoch_metrics()
     total, _, _ = _train_epoch(step, dataset, tables, lr)
-    m = step.epoch_metrics()
-    if getattr(step, "seg_only", False):        # training_segmentation.py:62
-        return total, m.dice
-    if getattr(step, "cls_only", False):        # training_classification.py:98
-        return total, m.accuracy, m.f1
-    return total, m.dice, m.accuracy, m.f1
+    m = step.epoch_metrics()            # (loss, dice) for training_segmentation.py:62, (loss, acc, f1) for training_classification.py:98
+    return (total,) + tuple(getattr(m, k) for k in step_task(step).train_fields)
 
 
 def validate_one_epoch_indexed(step: FusedEvalStep, dataset, tables) -> tuple:
@@ -1343,62 +1349,57 @@ def fit_fold(step: FusedTrainStep, eval_step: FusedEvalStep, dataset, train_inde
     Validation_F1` and the row of :262-266 (the learning rate at the START of the epoch); the rows returned are (epoch, lr, train_loss, val_loss,
     train_acc, train_f1, val_acc, val_f1).  That driver's testing phase runs once, after the loop (:284-298): `test_one_epoch_indexed` with an
     inference.FusedClsTestStep; `test_step` / `test_index` are not used here."""
-    if getattr(step, "cls_only", False) or getattr(eval_step, "cls_only", False):
-        return _fit_fold_classification(step, eval_step, dataset, train_index, val_index, scheduler, run_dir, epochs, max_patience, transforms,
-                                        seed, plateau, checkpoint_name)
-    if getattr(step, "seg_only", False) or getattr(eval_step, "seg_only", False):
-        return _fit_fold_segmentation(step, eval_step, test_step, dataset, train_index, val_index, test_index, scheduler, run_dir, epochs,
-                                      max_patience, transforms, seed, plateau, checkpoint_name)
     import logging
     import time
-    from . import checkpoint as CK
     from .device_data import EpochTables
-    writer = True
+    task, eval_task = step_task(step), step_task(eval_step)
+    if task is not eval_task:
+        odd = CLASSIFICATION if CLASSIFICATION in (task, eval_task) else SEGMENTATION
+        raise ValueError(f"fit_fold: the training and the evaluation step must both be built on a {odd.name}-only model, or neither")
+    if task.tests_every_epoch and (test_step is None or test_index is None):
+        raise ValueError("fit_fold: the segmentation driver runs its testing phase after every epoch: pass test_step (inference.FusedSegTestStep) "
+                         "and test_index")
     if step.distributed and not getattr(eval_step, "distributed", False):
         # every rank must read the SAME val_loss: the scheduler, the checkpoint rule and early stopping below act on it, and a rank that
         # leaves the epoch loop alone leaves the others waiting in a collective
         raise ValueError("fit_fold: the training step is data parallel, the evaluation step is not: build it with "
                          "FusedEvalStep(..., on_device=True, distributed=True) so that every rank sees the same validation numbers")
+    writer = True
     if step.distributed:
         import torch.distributed as dist
         writer = dist.get_rank() == 0
     os.makedirs(run_dir, exist_ok=True)
     metrics_path = os.path.join(run_dir, "metrics.csv")
     if writer:
-        CK.write_metrics_file(metrics_path, CK.METRICS_HEADER)
+        CK.write_metrics_file(metrics_path, task.header)
     stopper = CK.EarlyStopping(max_patience)
     val_tables = EpochTables(val_index, 0, None, device=dataset.device)        # no shuffle that matters, no transforms (:199-201)
+    test_tables = EpochTables(test_index, 0, None, device=dataset.device) if task.tests_every_epoch else None
+    train_names = ("train_loss",) + tuple("train_" + k for k in task.train_fields)
+    val_names = tuple("val_" + k for k in task.val_fields)
     rows = []
     for epoch in range(int(epochs)):
-        current_lr = step.opt.param_groups[0]["lr"]
+        v = {"epoch": epoch, "lr": step.opt.param_groups[0]["lr"]}
         t0 = time.perf_counter()
         tables = EpochTables(train_index, epoch, transforms, seed=seed, device=dataset.device)
-        train_loss, train_dice, train_acc, train_f1 = train_one_epoch_with_metrics(step, dataset, tables)
-        val_loss, val_dice, val_acc, val_f1, seg_val_loss, cls_val_loss = validate_one_epoch_indexed(eval_step, dataset, val_tables)
+        v.update(zip(train_names, train_one_epoch_with_metrics(step, dataset, tables), strict=True))
+        v.update(zip(val_names, validate_one_epoch_indexed(eval_step, dataset, val_tables), strict=True))
         if plateau:
-            scheduler.step(val_loss)
+            scheduler.step(v["val_loss"])
         else:
             scheduler.step()
-        if stopper.update(val_loss) and writer:
-            CK.save_checkpoint(os.path.join(run_dir, checkpoint_name), epoch, step.model, step.opt, val_loss, scaler=step.scaler)
-        logging.info(f'EPOCH {epoch} --> '
-                     f'|| Training loss {train_loss:.4f} '
-                     f'|| Validation loss {val_loss:.4f} '
-                     f'|| Segmentation val loss {seg_val_loss:.4f} '
-                     f'|| Classification val loss {cls_val_loss:.4f} '
-                     f'|| Training DICE {train_dice:.4f} '
-                     f'|| Validation DICE  {val_dice:.4f} '
-                     f'|| Training ACC {train_acc:.4f} '
-                     f'|| Training F1 {train_f1:.4f} '
-                     f'|| Validation ACC {val_acc:.4f} '
-                     f'|| Validation F1 {val_f1:.4f} '
-                     f'|| Patience: {stopper.patience} '
-                     f'|| Epoch time: {time.perf_counter() - t0:.4f}'
-                     f'|| Best validation performance: {stopper.best:.4f}')
-        row = (epoch, current_lr, train_loss, val_loss, train_dice, val_dice, train_acc, train_f1, val_acc, val_f1)
+        if stopper.update(v["val_loss"]) and writer:
+            CK.save_checkpoint(os.path.join(run_dir, checkpoint_name), epoch, step.model, step.opt, v["val_loss"], scaler=step.scaler)
+        v.update(patience=stopper.patience, epoch_time=time.perf_counter() - t0, best=stopper.best)
+        if task.tests_every_epoch:          # behind the checkpoint decision, outside the epoch's time (training_segmentation.py:179)
+            v["test_dice"] = float(np.mean([r["DICE"] for r in test_one_epoch_indexed(test_step, dataset, test_tables)]))
+        if not task.lr_at_start:
+            v["lr"] = step.opt.param_groups[0]["lr"]
+        logging.info(task.log.format(**v))
+        row = tuple(v[k] for k in task.row_fields)
         rows.append(row)
         if writer:
-            CK.write_metrics_file(metrics_path, CK.metrics_row(*row))
+            CK.write_metrics_file(metrics_path, task.row(*row))
         if stopper.should_stop:
             logging.info(f"\nValidation loss did not improve over the last {stopper.patience} epochs. Stopping training")
             break
@@ -1412,115 +1413,8 @@ def test_one_epoch_indexed(test_step, dataset, tables) -> list:
     _check_tables(dataset, tables)
     _check_in_channels(test_step.model, dataset)
     test_step.reset()
-    if getattr(test_step, "cls_only", False):
-        for b in range(len(tables)):
-            index, _, n_local, _ = tables.batch(b)
-            if n_local:
-                test_step.indexed(dataset, index)
-        return test_step.result()
-    scratch = None
     for b in range(len(tables)):
         index, _, n_local, _ = tables.batch(b)
         if n_local:
-            st = test_step.model.compiled(len(index), dataset.H, dataset.W)
-            if scratch is None or scratch.shape[0] != st.N:
-                scratch = torch.empty(st.N, 1, dtype=torch.float32, device=dataset.device)
-            image, mask, _ = dataset.assemble(index, None, n_onehot=0, out=(st.x.data, torch.empty_like(st.segs[-1].data), scratch))
-            test_step(image, mask)
+            test_step.indexed(dataset, index)
     return test_step.result()
-
-
-def _fit_fold_segmentation(step, eval_step, test_step, dataset, train_index, val_index, test_index, scheduler, run_dir, epochs, max_patience,
-                           transforms, seed, plateau, checkpoint_name) -> List[tuple]:
-    """`fit_fold` for the segmentation pair of steps: training_segmentation.py:143-201."""
-    import logging
-    import time
-    from . import checkpoint as CK
-    from .device_data import EpochTables
-    if not (getattr(step, "seg_only", False) and getattr(eval_step, "seg_only", False)):
-        raise ValueError("fit_fold: the training and the evaluation step must both be built on a segmentation-only model, or neither")
-    if test_step is None or test_index is None:
-        raise ValueError("fit_fold: the segmentation driver runs its testing phase after every epoch: pass test_step (inference.FusedSegTestStep) "
-                         "and test_index")
-    os.makedirs(run_dir, exist_ok=True)
-    metrics_path = os.path.join(run_dir, "metrics.csv")
-    CK.write_metrics_file(metrics_path, CK.SEG_METRICS_HEADER)
-    stopper = CK.EarlyStopping(max_patience)
-    val_tables = EpochTables(val_index, 0, None, device=dataset.device)
-    test_tables = EpochTables(test_index, 0, None, device=dataset.device)
-    rows = []
-    for epoch in range(int(epochs)):
-        t0 = time.perf_counter()
-        tables = EpochTables(train_index, epoch, transforms, seed=seed, device=dataset.device)
-        train_loss, train_dice = train_one_epoch_with_metrics(step, dataset, tables)
-        val_loss, val_dice = validate_one_epoch_indexed(eval_step, dataset, val_tables)
-        if plateau:
-            scheduler.step(val_loss)
-        else:
-            scheduler.step()
-        if stopper.update(val_loss):
-            CK.save_checkpoint(os.path.join(run_dir, checkpoint_name), epoch, step.model, step.opt, val_loss, scaler=step.scaler)
-        epoch_time = time.perf_counter() - t0
-        test_rows = test_one_epoch_indexed(test_step, dataset, test_tables)
-        test_dice = float(np.mean([r["DICE"] for r in test_rows]))
-        lr = step.opt.param_groups[0]["lr"]
-        logging.info(f'EPOCH {epoch} --> '
-                     f'|| Training loss {train_loss:.4f} '
-                     f'|| Validation loss {val_loss:.4f} '
-                     f'|| Training DICE {train_dice:.4f} '
-                     f'|| Validation DICE  {val_dice:.4f} '
-                     f'|| Patience: {stopper.patience} '
-                     f'|| Epoch time: {epoch_time:.4f} '
-                     f'|| LR: {lr:.8f}')
-        row = (epoch, lr, train_dice, val_dice, test_dice, train_loss, val_loss)
-        rows.append(row)
-        CK.write_metrics_file(metrics_path, CK.seg_metrics_row(*row))
-        if stopper.should_stop:
-            logging.info(f"\nValidation loss did not improve over the last {stopper.patience} epochs. Stopping training")
-            break
-    return rows
-
-
-def _fit_fold_classification(step, eval_step, dataset, train_index, val_index, scheduler, run_dir, epochs, max_patience, transforms, seed, plateau,
-                             checkpoint_name) -> List[tuple]:
-    """`fit_fold` for the classification pair of steps: training_classification.py:216-271."""
-    import logging
-    import time
-    from . import checkpoint as CK
-    from .device_data import EpochTables
-    if not (getattr(step, "cls_only", False) and getattr(eval_step, "cls_only", False)):
-        raise ValueError("fit_fold: the training and the evaluation step must both be built on a classification-only model, or neither")
-    os.makedirs(run_dir, exist_ok=True)
-    metrics_path = os.path.join(run_dir, "metrics.csv")
-    CK.write_metrics_file(metrics_path, CK.CLS_METRICS_HEADER)
-    stopper = CK.EarlyStopping(max_patience)
-    val_tables = EpochTables(val_index, 0, None, device=dataset.device)
-    rows = []
-    for epoch in range(int(epochs)):
-        current_lr = step.opt.param_groups[0]["lr"]
-        t0 = time.perf_counter()
-        tables = EpochTables(train_index, epoch, transforms, seed=seed, device=dataset.device)
-        train_loss, train_acc, train_f1 = train_one_epoch_with_metrics(step, dataset, tables)
-        val_loss, val_acc, val_f1 = validate_one_epoch_indexed(eval_step, dataset, val_tables)
-        if plateau:
-            scheduler.step(val_loss)
-        else:
-            scheduler.step()
-        if stopper.update(val_loss):
-            CK.save_checkpoint(os.path.join(run_dir, checkpoint_name), epoch, step.model, step.opt, val_loss, scaler=step.scaler)
-        logging.info(f'EPOCH {epoch} --> '
-                     f'|| Training loss {train_loss:.4f} '
-                     f'|| Validation loss {val_loss:.4f} '
-                     f'|| Training ACC {train_acc:.4f} '
-                     f'|| Training F1 {train_f1:.4f} '
-                     f'|| Validation ACC {val_acc:.4f} '
-                     f'|| Validation F1 {val_f1:.4f} '
-                     f'|| Patience: {stopper.patience} '
-                     f'|| Epoch time: {time.perf_counter() - t0:.4f}')
-        row = (epoch, current_lr, train_loss, val_loss, train_acc, train_f1, val_acc, val_f1)
-        rows.append(row)
-        CK.write_metrics_file(metrics_path, CK.cls_metrics_row(*row))
-        if stopper.should_stop:
-            logging.info(f"\nValidation loss did not improve over the last {stopper.patience} epochs. Stopping training")
-            break
-    return rows

@@ -1,5 +1,7 @@
 """What FusedTrainStep and FusedEvalStep share, without a GPU: the decode of the packed metrics arrays in both flavours, the batch fill
-on a stand-in compiled step, the bookkeeping of the graph-replay helper with the capture step replaced, and the `fused_loss` settings."""
+on a stand-in compiled step, the bookkeeping of the graph-replay helper with the capture step replaced, the `fused_loss` settings, and the argument struct of the
+metrics call for each of the three tasks on CPU tensors."""
+import ctypes
 import types
 
 import numpy as np
@@ -120,6 +122,87 @@ def test_train_and_eval_steps_build_the_same_fused_loss_settings():
     assert list(train) == list(evaluate)
     dynamic = T._fused_loss(types.SimpleNamespace(scaler=object(), **settings))
     assert {k: v for k, v in dynamic.items() if k != "loss_scale"} == evaluate and dynamic["loss_scale"] == 1.0 and len(dynamic) == len(evaluate) + 1
+
+
+# ------------------------------------------------------------------------------------------------ the metrics call's argument struct
+class _Net(torch.nn.Linear):
+    """As much of a model as MetricsTable reads: where its parameters live, and the attributes that tell the three tasks apart."""
+
+    def __init__(self, task):
+        super().__init__(1, 1)
+        self.n_classes = 0 if task == "seg" else 3
+        self.cls_only = task == "cls"
+
+
+def metrics_step(task, n=2, n_logits=3):
+    """A compiled step's outputs and targets on the CPU; the plan of a single-task model has no buffers of the head it lacks."""
+    seg = task != "cls"
+    cls = task != "seg"
+    return types.SimpleNamespace(
+        N=n, segs=[types.SimpleNamespace(data=torch.zeros(n, 1, 4, 5))] if seg else [], mask=torch.zeros(n, 1, 4, 5) if seg else None,
+        logits=types.SimpleNamespace(data=torch.zeros(n, n_logits), C=n_logits) if cls else None, onehot=torch.zeros(n, n_logits) if cls else None,
+        plan=types.SimpleNamespace(loss_out=torch.zeros(4)))
+
+
+STRUCTS = {"multi": (L.TrainMetricsArgs, L.EvalMetricsArgs), "seg": (L.SegStepMetricsArgs,) * 2, "cls": (L.ClsStepMetricsArgs,) * 2}
+
+
+@pytest.mark.parametrize("distributed", [False, True], ids=["local", "distributed"])
+@pytest.mark.parametrize("given", [True, False], ids=["step", "empty shard"])
+@pytest.mark.parametrize("validation", [False, True], ids=["train", "eval"])
+@pytest.mark.parametrize("task", ["multi", "seg", "cls"])
+def test_metrics_arguments_hold_exactly_the_pointers_and_counts_of_the_step(task, validation, given, distributed):
+    t = T.MetricsTable(_Net(task), CAP, validation=validation, distributed=distributed)
+    st = metrics_step(task) if given else None
+    a = t._arguments(st, 0 if task == "seg" else 3)
+    assert type(a) is STRUCTS[task][validation]
+    want = {name: (None if ctype is ctypes.c_void_p else 0) for name, ctype in a._fields_}
+    if task != "cls":
+        want["n_seg"] = 0
+        if given:
+            want.update(seg_logits=st.segs[-1].data.data_ptr(), mask=st.mask.data_ptr(), n_seg=2 * 4 * 5)
+    if task != "seg":
+        want["n_logits"] = 3
+        if given:
+            want.update({"cls_out" if task == "cls" else "cls_logits": st.logits.data.data_ptr(), "target": st.onehot.data_ptr()})
+        want["conf"] = t.counts.data_ptr() + CAP * 32
+    want.update(N=2 if given else 0, table=t.counts.data_ptr(), state=t.state.data_ptr(), capacity=CAP)
+    if validation:
+        want.update(loss_in=st.plan.loss_out.data_ptr() if given else None, loss_rows=t.loss_rows.data_ptr(),
+                    shard_weight=t.weight.data_ptr() if distributed else None)
+    else:
+        assert t.loss_rows is None and t.weight is None
+    assert {name: getattr(a, name) for name, _ in a._fields_} == want
+    assert t.counts.numel() == CAP * 4 + 9 and t.counts.dtype == torch.int64 and t.state.dtype == torch.int32
+
+
+@pytest.mark.parametrize("validation", [False, True], ids=["train", "eval"])
+@pytest.mark.parametrize("task", ["multi", "seg", "cls"])
+def test_metrics_arguments_refuse_buffers_the_kernels_cannot_read(task, validation):
+    def table():
+        return T.MetricsTable(_Net(task), CAP, validation=validation)
+
+    def spoil(field, how):
+        st = metrics_step(task)
+        holder, name = {"seg": (st.segs[-1], "data") if st.segs else None, "mask": (st, "mask"), "logits": (st.logits, "data"),
+                        "onehot": (st, "onehot"), "loss_out": (st.plan, "loss_out")}[field]
+        setattr(holder, name, how(getattr(holder, name)))
+        return st
+
+    fields = {"multi": ["seg", "mask", "logits", "onehot"], "seg": ["seg", "mask"], "cls": ["logits", "onehot"]}[task]
+    for field in fields + (["loss_out"] if validation else []):
+        for how in (lambda x: x.double(), lambda x: x.half(), lambda x: torch.zeros(*x.shape, 2)[..., 0]):          # not fp32; not contiguous
+            with pytest.raises(L.MtbcError, match="not contiguous fp32 buffers"):
+                table()._arguments(spoil(field, how), 3)
+    for field in fields:                                                                                            # a pair of unequal sizes
+        with pytest.raises(L.MtbcError, match="outputs and targets differ in size"):
+            table()._arguments(spoil(field, lambda x: torch.zeros(x.numel() + 1)), 3)
+    if validation:                                                                                                  # fewer than 4 loss words
+        with pytest.raises(L.MtbcError, match="outputs and targets differ in size"):
+            table()._arguments(spoil("loss_out", lambda x: torch.zeros(3)), 3)
+    else:                                                                                                           # training reads no loss words
+        table()._arguments(spoil("loss_out", lambda x: torch.zeros(3).double()), 3)
+    table()._arguments(metrics_step(task), 3)
 
 
 def test_head_and_criterion_rules_are_the_same_for_both_steps():
