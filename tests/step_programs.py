@@ -183,7 +183,8 @@ def _same_upconv(wg, dg):
 def _small_op_key(op):
     """Coverage key of ONE small op (ops.SMALL_OPS): the launches mtbc_op_kernel_name plans + the branches the ARGUMENTS select inside those
     kernels -- which tensors are channel-range views of wider buffers (a batch stride above dense), argmax, bias / dbias, every accumulate
-    flag, dx present, and Cout > 8 (a second channel group in the planar 1x1 kernels).  The only place that decides what "the same launch"
+    flag, dx present, and Cout > 8 (a second channel group in the planar 1x1 kernels); for the nearest 2x up-sampling its strided tensors and
+    acc_dx.  The only place that decides what "the same launch"
     means for the guard below."""
     L = ops.L
     name, k, f = ops.op_kernel_name(op), op.kind, []
@@ -225,6 +226,17 @@ def _small_op_key(op):
         f += [n for n in ("bT", "b1") if getattr(op.u.head, n)]
     elif k == L.OP_HEAD_EXPAND:
         f += [n for n in ("bT", "dbT", "db1", "acc_wT", "acc_bT", "acc_w1", "acc_b1") if getattr(op.u.head, n)]
+    elif k in (L.OP_UPSAMPLE2_FWD, L.OP_UPSAMPLE2_BWD):
+        # (pool_up.hip: the name carries the layout -- upsample2_c8_fwd_kernel moves 16-byte words and never looks at type16, and the backward
+        # reads neither layout nor type16: dy / dx are fp32 planes always.  Batch strides in elements of the tensor: 16-bit ones for C8.)
+        a = op.u.up2
+        full = a.C * a.H * a.W
+        dense = dict(x=full, y=4 * full, dy=4 * full, dx=full)
+        if k == L.OP_UPSAMPLE2_FWD:
+            views(a, dense, "x", "y")
+        else:
+            views(a, dense, "dy", "dx")
+            f += ["acc_dx"] if a.accumulate_dx else []
     else:
         assert k in (L.OP_GAP_FWD, L.OP_GAP_BWD), k          # (GAP: dense tensors, no flag)
     return name, tuple(f)
@@ -292,7 +304,7 @@ def collect_convT(prog, i):
 
 
 _SMALL_SHAPE = {"pool": ("N", "C", "H", "W"), "conv1": ("N", "Cin", "Cout", "H", "W"), "gap": ("N", "C", "H", "W"), "linear": ("N", "In", "Out"),
-                "head": ("Cin", "Cmid", "R", "k")}
+                "head": ("Cin", "Cmid", "R", "k"), "up2": ("N", "C", "H", "W")}
 
 
 def collect_small_op(prog, i):

@@ -49,6 +49,19 @@ def _unstrided(flat, shape, stride):
 PLANAR = [((2, 16, 16, 16), None, "upsample2_fwd_kernel", "upsample2_bwd_kernel"),                    # the float4 forms; 2048 threads
           ((1, 5, 3, 5), None, "upsample2_fwd_scalar_kernel", "upsample2_bwd_scalar_kernel"),        # odd W
           ((2, 8, 8, 8), "in", "upsample2_fwd_scalar_kernel", "upsample2_bwd_scalar_kernel")]        # the scalar forms by the batch stride
+C8_SHAPES = [(2, 8, 4, 4), (3, 24, 8, 12)]                                                            # channel-blocked forward, bf16 and fp16
+
+
+def up2_case_ops():
+    """The op (dummy pointers) of every up-sampling call the three tests below make on the rows of PLANAR and C8_SHAPES: what the launch-coverage
+    guard of tests/test_mt_btsunet_launches_gpu.py keys these cases by (tests/step_programs.py _small_op_key)."""
+    made = []
+    for (N, Cc, H, W), strided, _, _ in PLANAR:
+        xs = Cc * H * W + (2 if strided else 0)
+        made.append(ops.upsample2_case_args(L.OP_UPSAMPLE2_FWD, N, Cc, H, W, strides=dict(x=xs)))
+        made += [ops.upsample2_case_args(L.OP_UPSAMPLE2_BWD, N, Cc, H, W, acc_dx=acc, strides=dict(dx=xs)) for acc in (False, True)]
+    made += [ops.upsample2_case_args(L.OP_UPSAMPLE2_FWD, *shape, compute=compute) for shape in C8_SHAPES for compute in (1, 2)]
+    return made
 
 
 @pytest.mark.parametrize("shape,strided,kf,kb", PLANAR, ids=["float4", "oddW", "stride"])
@@ -76,7 +89,7 @@ def test_planar_forward_is_repeat_interleave_bit_for_bit(shape, strided, kf, kb)
 
 
 @pytest.mark.parametrize("compute", [1, 2], ids=["bf16", "f16"])
-@pytest.mark.parametrize("shape", [(2, 8, 4, 4), (3, 24, 8, 12)])
+@pytest.mark.parametrize("shape", C8_SHAPES)
 def test_c8_forward_is_the_pack_of_the_upsampled_planes(shape, compute):
     OPS = _ops_gpu()
     N, Cc, H, W = shape

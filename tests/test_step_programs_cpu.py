@@ -186,6 +186,52 @@ def test_conv3_collector_keys_by_kind_and_arguments_and_names_the_segments():
     assert f"[{D_}]" in str(e.value)
 
 
+# ---- the nearest 2x up-sampling key: the launch string + the strided tensors + acc_dx (hand-made ops, dummy pointers)
+UF_, UB_ = L.OP_UPSAMPLE2_FWD, L.OP_UPSAMPLE2_BWD
+_UP = (3, 24, 8, 12)          # N, C, H, W of the input: dense x / dx = 2304 elements an image, y / dy = 9216
+
+
+def _up2(kind, shape=_UP, **kw):
+    return SP._small_op_key(ops.upsample2_case_args(kind, *shape, **kw))
+
+
+def test_up2_key_is_the_launch_string_of_the_dispatcher():
+    assert _up2(UF_) == ("upsample2_fwd_kernel", ()) and _up2(UB_) == ("upsample2_bwd_kernel", ())
+    assert _up2(UF_, (1, 5, 3, 5)) == ("upsample2_fwd_scalar_kernel", ()) and _up2(UB_, (1, 5, 3, 5)) == ("upsample2_bwd_scalar_kernel", ())
+    assert _up2(UF_, compute=1) == _up2(UF_, compute=2) == ("upsample2_c8_fwd_kernel", ())          # one kernel: the type is never looked at
+
+
+@pytest.mark.parametrize("kind,flag,with_", [
+    (UF_, "x_strided", dict(strides=dict(x=2304 + 16 * 96))),
+    (UF_, "y_strided", dict(strides=dict(y=9216 + 16 * 384))),
+    (UF_, "x_strided", dict(compute=1, strides=dict(x=2304 + 16 * 96))),                 # channel-blocked: strides in 16-bit elements
+    (UF_, "y_strided", dict(compute=2, strides=dict(y=9216 + 16 * 384))),
+    (UB_, "dy_strided", dict(strides=dict(dy=9216 + 16 * 384))),
+    (UB_, "dx_strided", dict(strides=dict(dx=2304 + 16 * 96))),
+    (UB_, "acc_dx", dict(acc_dx=True)),
+])
+def test_up2_key_flag_follows_the_arguments(kind, flag, with_):
+    mode = {k: v for k, v in with_.items() if k == "compute"}
+    a, b = _up2(kind, **mode), _up2(kind, **with_)
+    assert a[0] == b[0] and a[1] == () and b[1] == (flag,), (a, b)
+
+
+def test_up2_key_holds_every_flag_at_once_and_ignores_fields_the_call_does_not_read():
+    assert _up2(UF_, compute=1, strides=dict(x=4608, y=18432)) == ("upsample2_c8_fwd_kernel", ("x_strided", "y_strided"))
+    assert _up2(UB_, acc_dx=True, strides=dict(dy=18432, dx=4608)) == ("upsample2_bwd_kernel", ("dy_strided", "dx_strided", "acc_dx"))
+    fwd, bwd = ops.upsample2_case_args(UF_, *_UP), ops.upsample2_case_args(UB_, *_UP)
+    want_f, want_b = SP._small_op_key(fwd), SP._small_op_key(bwd)
+    fwd.u.up2.accumulate_dx, fwd.u.up2.dy_batch_stride, fwd.u.up2.dx_batch_stride = 1, 5, 5        # the forward reads none of the backward's fields
+    bwd.u.up2.x_batch_stride, bwd.u.up2.y_batch_stride, bwd.u.up2.layout, bwd.u.up2.type16 = 5, 5, L.LAYOUT_C8, 1        # ... and the reverse
+    assert SP._small_op_key(fwd) == want_f and SP._small_op_key(bwd) == want_b
+
+
+def test_up2_ops_are_surveyed_with_their_shape():
+    fwd, bwd = ops.upsample2_case_args(UF_, *_UP, compute=1, strides=dict(y=18432)), ops.upsample2_case_args(UB_, *_UP, acc_dx=True)
+    s = _survey("up2", {"fwd": [fwd], "bwd": [bwd, bwd]})
+    assert s.seen[SMALL] == {(UF_, ("upsample2_c8_fwd_kernel", ("y_strided",))): (UF_, _UP), (UB_, ("upsample2_bwd_kernel", ("acc_dx",))): (UB_, _UP)}
+
+
 # ---- what a survey keeps, and for how long
 def _plain(v):
     if isinstance(v, (tuple, list)):
