@@ -932,6 +932,30 @@ typedef struct {
 } mtbc_batch_args;
 int mtbc_batch_assemble(const mtbc_batch_args* a, void* stream);
 
+/* The same launch with E stored planes per image next to the image store: the spatial variants of `data.augmentation` (CLAHE, SOBEL:
+ * BUSI_dataset.py:114-122), which are no function of the pixel value and are therefore data the caller computed once per image.
+ *   out_image (N, 1 + E + K, H, W)   channel 0 = the raw image, channel 1 + e = planes[e] of the sample's store row, channel
+ *                                    1 + E + k = luts[k][pixel] -- the reference's append order with CLAHE, SOBEL stored in that order
+ * A stored plane is treated as the image plane is: row index[n], the same source pixel under params, 0 outside the rotated frame, 0 for
+ * an index outside [0, M), the uint8 value converted to float.  Mask, target and LUT channels are those of mtbc_batch_assemble, and with
+ * E == 0 every output word is.  Refused like mtbc_batch_assemble, plus MTBC_E_BADSHAPE: E outside [0, MTBC_BATCH_MAX_PLANES];
+ * MTBC_E_BADARG: planes NULL with E > 0, or planes (E * M * H * W bytes) overlapping an output.                               */
+#define MTBC_BATCH_MAX_PLANES 2
+typedef struct {
+    int32_t M, N, H, W;              /* store rows, batch size, plane size */
+    int32_t K, n_onehot;             /* as in mtbc_batch_args */
+    int32_t E;                       /* stored planes per image (0 .. MTBC_BATCH_MAX_PLANES) */
+    const uint8_t* images;           /* (M, H, W) */
+    const uint8_t* masks;            /* (M, H, W), values {0, 1} */
+    const uint8_t* planes;           /* (E, M, H, W), one contiguous store */
+    const int32_t* labels;           /* (M) */
+    const int32_t* index;            /* (N) device array of store rows */
+    const float* params;             /* (N, 4) or NULL */
+    const uint8_t* luts;             /* (K, 256) */
+    float* out_image; float* out_mask; float* out_target;
+} mtbc_batch_planes_args;
+int mtbc_batch_assemble_planes(const mtbc_batch_planes_args* a, void* stream);
+
 typedef struct {
     int32_t kind;
     int32_t tag;                     /* free for the caller (layer id) */

@@ -177,6 +177,15 @@ class BatchArgs(C.Structure):
                 ("out_image", C.c_void_p), ("out_mask", C.c_void_p), ("out_target", C.c_void_p)]
 
 
+class BatchPlanesArgs(C.Structure):
+    """mtbc_batch_planes_args (include/mtbc.h): mtbc_batch_args plus E stored planes per image."""
+    _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("K", C.c_int32), ("n_onehot", C.c_int32),
+                ("E", C.c_int32),
+                ("images", C.c_void_p), ("masks", C.c_void_p), ("planes", C.c_void_p), ("labels", C.c_void_p), ("index", C.c_void_p),
+                ("params", C.c_void_p), ("luts", C.c_void_p),
+                ("out_image", C.c_void_p), ("out_mask", C.c_void_p), ("out_target", C.c_void_p)]
+
+
 class TrainMetricsArgs(C.Structure):
     """mtbc_train_metrics_args (include/mtbc.h)."""
     _fields_ = [("seg_logits", C.c_void_p), ("mask", C.c_void_p), ("n_seg", C.c_int64), ("cls_logits", C.c_void_p), ("target", C.c_void_p),
@@ -219,6 +228,7 @@ class FillHolesArgs(C.Structure):
 
 
 BATCH_MAX_LUTS = 4         # MTBC_BATCH_MAX_LUTS of include/mtbc.h
+BATCH_MAX_PLANES = 2       # MTBC_BATCH_MAX_PLANES of include/mtbc.h: the CLAHE and SOBEL planes of data.augmentation
 
 # columns of the mtbc_seg_metrics table -- keep in sync with the MTBC_SEGM_* defines of include/mtbc.h
 SEGM_COLS = 9
@@ -333,7 +343,7 @@ EXPORTS = [
     "mtbc_loss_scale_update_host", "mtbc_loss_scale_begin_host", "mtbc_optim_step", "mtbc_optim_dynamic", "mtbc_loss_scale_optim", "mtbc_optim_step_host",
     "mtbc_dice_counts", "mtbc_program_run",
     "mtbc_program_run_ms", "mtbc_event_create", "mtbc_event_destroy", "mtbc_op_kernel_name",
-    "mtbc_seg_metrics_workspace_size", "mtbc_seg_metrics", "mtbc_batch_assemble", "mtbc_train_metrics",
+    "mtbc_seg_metrics_workspace_size", "mtbc_seg_metrics", "mtbc_batch_assemble", "mtbc_batch_assemble_planes", "mtbc_train_metrics",
     "mtbc_eval_metrics", "mtbc_seg_step_metrics", "mtbc_fill_holes", "mtbc_fill_holes_host",
     "mtbc_softmax_rows", "mtbc_softmax_rows_host", "mtbc_cls_step_metrics", "mtbc_cls_test_rows",
     "mtbc_upsample2_fwd", "mtbc_upsample2_bwd", "mtbc_linear_workspace", "mtbc_linear_wide_enable",
@@ -463,6 +473,8 @@ def load() -> C.CDLL:
     lib.mtbc_seg_metrics.argtypes = [C.POINTER(SegMetricsArgs), C.c_void_p]
     lib.mtbc_batch_assemble.restype = C.c_int
     lib.mtbc_batch_assemble.argtypes = [C.POINTER(BatchArgs), C.c_void_p]
+    lib.mtbc_batch_assemble_planes.restype = C.c_int
+    lib.mtbc_batch_assemble_planes.argtypes = [C.POINTER(BatchPlanesArgs), C.c_void_p]
     lib.mtbc_train_metrics.restype = C.c_int
     lib.mtbc_train_metrics.argtypes = [C.POINTER(TrainMetricsArgs), C.c_void_p]
     lib.mtbc_eval_metrics.restype = C.c_int

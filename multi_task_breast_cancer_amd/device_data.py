@@ -3,7 +3,9 @@
 The reference keeps the whole dataset in RAM as uint8 (BUSI_dataset.py:47-92: curated BUSI is 450 images, 29 MB at 256 x 256) and
 builds every item on the CPU with 0 workers (:97-158).  Here the uint8 stores live on the GPU and `mtbc_batch_assemble`
 (csrc/batch_loader.hip) goes from a device index array straight to the fp32 buffers a step reads: image (+ the intensity variants
-of `data.augmentation` as look-up tables), mask, class target, all under one joint flip / rotation.
+of `data.augmentation` as look-up tables), mask, class target, all under one joint flip / rotation.  The two spatial variants (CLAHE,
+SOBEL) are OpenCV filters with no oracle here: the caller computes them once per image and hands them over as uint8 planes
+(`spatial_planes`), which are stored next to the images and gathered like them (`mtbc_batch_assemble_planes`).
 
     ds = DeviceDataset(images_u8, masks_u8, labels, augmentation=config["data"]["augmentation"])
     tables = EpochTables(EpochIndex(train_positions, 32, seed), epoch, transforms={"horizontal_flip": .5, "vertical_flip": .5, "rotation": 1.0})
@@ -21,7 +23,42 @@ from .dataset_index import EpochIndex
 
 # the reference's append order (BUSI_dataset.py:123-139): channel 1 + k of the image is LUT_KEYS-order entry k of those switched on
 LUT_KEYS = ("brightness_brighter", "brightness_darker", "contrast_low", "contrast_high")
-_SPATIAL_KEYS = ("CLAHE", "SOBEL")
+SPATIAL_KEYS = _SPATIAL_KEYS = ("CLAHE", "SOBEL")        # ... in front of them (:114-122), as stored planes the caller supplies
+
+
+def channel_names(augmentation: Optional[dict]) -> Tuple[str, ...]:
+    """The model-input channels a DeviceDataset emits for `data.augmentation`, in order: "image", then every flag that is on in the
+    reference's append order (BUSI_dataset.py:114-139) -- the stored planes CLAHE, SOBEL, then the look-up-table channels."""
+    aug = dict(augmentation or {})
+    unknown = set(aug) - set(LUT_KEYS) - set(SPATIAL_KEYS)
+    if unknown:
+        raise ValueError(f"unknown data.augmentation keys {sorted(unknown)}")
+    return ("image",) + tuple(k for k in SPATIAL_KEYS + LUT_KEYS if aug.get(k, False))
+
+
+def _check_spatial_planes(augmentation: Optional[dict], spatial_planes: Optional[dict], shape) -> List:
+    """The stored planes of the spatial flags that are on, in SPATIAL_KEYS order; ValueError for a flag without its plane, a plane
+    without its flag, an unknown key, a plane that is not uint8 or not of the image store's shape."""
+    aug, planes = dict(augmentation or {}), dict(spatial_planes or {})
+    unknown = set(planes) - set(SPATIAL_KEYS)
+    if unknown:
+        raise ValueError(f"unknown spatial_planes keys {sorted(unknown)}: the stored planes are {', '.join(SPATIAL_KEYS)}")
+    out = []
+    for key in SPATIAL_KEYS:
+        on = bool(aug.get(key, False))
+        if on and key not in planes:
+            raise ValueError(f"data.augmentation.{key} is a spatial OpenCV filter: the device-resident dataset does not compute it, it takes "
+                             f"the filtered images as spatial_planes[{key!r}] (uint8, one plane per image)")
+        if key in planes and not on:
+            raise ValueError(f"spatial_planes[{key!r}] given but data.augmentation.{key} is off: the plane would be ignored")
+        if on:
+            pl = planes[key] if getattr(planes[key], "is_cuda", False) else _as_numpy(planes[key])
+            if str(pl.dtype).split(".")[-1] != "uint8":
+                raise ValueError(f"spatial_planes[{key!r}] must be uint8, got {pl.dtype}")
+            if tuple(pl.shape) != tuple(shape):
+                raise ValueError(f"spatial_planes[{key!r}] must have the image store's shape {tuple(shape)}, got {tuple(pl.shape)}")
+            out.append(pl)
+    return out
 
 
 def intensity_luts(augmentation: Optional[dict]) -> np.ndarray:
@@ -64,10 +101,14 @@ def _as_numpy(a) -> np.ndarray:
 
 
 class DeviceDataset:
-    """uint8 image / mask stores (M, H, W) and int32 labels (M) on the device, uploaded once.  `assemble` is the kernel call."""
+    """uint8 image / mask stores (M, H, W) and int32 labels (M) on the device, uploaded once.  `assemble` is the kernel call.
+    spatial_planes = {"CLAHE": (M, H, W) uint8, "SOBEL": ...}: the filtered images of the spatial flags that are on in `augmentation`,
+    computed by the caller, on the host or on the device; exactly the flags that are on, nothing is ignored."""
 
-    def __init__(self, images_u8, masks_u8, labels, augmentation: Optional[dict] = None, device="cuda:0"):
-        luts = intensity_luts(augmentation)
+    def __init__(self, images_u8, masks_u8, labels, augmentation: Optional[dict] = None, device="cuda:0",
+                 spatial_planes: Optional[dict] = None):
+        names = channel_names(augmentation)
+        luts = intensity_luts({k: True for k in names if k in LUT_KEYS})
         on_device = all(getattr(a, "is_cuda", False) for a in (images_u8, masks_u8))
         img, msk, lab = images_u8, masks_u8, labels
         if not on_device:
@@ -89,6 +130,7 @@ class DeviceDataset:
             raise ValueError("labels must be in {0, 1, 2}")
         if int(msk.max()) > 1:
             raise ValueError("mask values must be in {0, 1} (the reference maps 255 to 1 at load time, BUSI_dataset.py:55)")
+        planes = _check_spatial_planes(augmentation, spatial_planes, (M, H, W))
         L.require_gpu()
         import torch
         self.device = torch.device(device)
@@ -99,7 +141,12 @@ class DeviceDataset:
         self.labels = torch.from_numpy(lab.astype(np.int32)).to(self.device)
         self.luts = torch.from_numpy(luts).to(self.device)
         self.M, self.H, self.W = M, H, W
-        self.n_augments = int(luts.shape[0])        # what load_multitask_experiment_artefacts(n_augments=...) adds to the model's input layer
+        # ONE (E, M, H, W) store, CLAHE before SOBEL: the kernel's channel 1 + e
+        self.planes = torch.stack([(pl if getattr(pl, "is_cuda", False) else torch.from_numpy(np.ascontiguousarray(pl))).to(self.device)
+                                   for pl in planes]).contiguous() if planes else None
+        self.n_planes, self.n_luts = len(planes), int(luts.shape[0])
+        self.channels = names
+        self.n_augments = self.n_planes + self.n_luts   # what load_multitask_experiment_artefacts(n_augments=...) adds to the model's input layer
 
     def __len__(self) -> int:
         return self.M
@@ -116,7 +163,7 @@ class DeviceDataset:
 
     def assemble(self, index, params=None, n_onehot: int = 3, out: Optional[Sequence] = None) -> Tuple:
         """index (N) int32 device tensor (a host array is validated against M and uploaded), params (N, 4) device tensor from
-        `augment.random_params` or None = identity -> (image (N, 1 + K, H, W), mask (N, 1, H, W), target) fp32, written by ONE launch on
+        `augment.random_params` or None = identity -> (image (N, 1 + E + K, H, W), mask (N, 1, H, W), target) fp32, written by ONE launch on
         the current stream.  target: one-hot (N, 3) with n_onehot=3, the float label (N, 1) with n_onehot=0 (binary head).
         `out`: that triple preallocated (a step's static buffers)."""
         import torch
@@ -145,14 +192,19 @@ class DeviceDataset:
             for t, s in zip(out, shapes):
                 if tuple(t.shape) != s or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
                     raise ValueError(f"out buffer {tuple(t.shape)} {t.dtype}: expected contiguous float32 {s} on {self.device}")
-        a = L.BatchArgs()
-        a.M, a.N, a.H, a.W, a.K, a.n_onehot = self.M, N, self.H, self.W, self.n_augments, n_onehot
+        a = L.BatchPlanesArgs() if self.n_planes else L.BatchArgs()
+        a.M, a.N, a.H, a.W, a.K, a.n_onehot = self.M, N, self.H, self.W, self.n_luts, n_onehot
         a.images, a.masks, a.labels = self.images.data_ptr(), self.masks.data_ptr(), self.labels.data_ptr()
         a.index = index.data_ptr()
         a.params = params.data_ptr() if params is not None else None
-        a.luts = self.luts.data_ptr() if self.n_augments else None
+        a.luts = self.luts.data_ptr() if self.n_luts else None
         a.out_image, a.out_mask, a.out_target = (t.data_ptr() for t in out)
-        L.check(L.load().mtbc_batch_assemble(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "batch_assemble")
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if self.n_planes:       # with stored planes: the entry point that gathers them; without: the call as it always was
+            a.E, a.planes = self.n_planes, self.planes.data_ptr()
+            L.check(L.load().mtbc_batch_assemble_planes(C.byref(a), stream), "batch_assemble_planes")
+        else:
+            L.check(L.load().mtbc_batch_assemble(C.byref(a), stream), "batch_assemble")
         return out
 
 

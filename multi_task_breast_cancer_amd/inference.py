@@ -278,7 +278,22 @@ class FusedTestStep:
         N, _, H, W = image.shape
         st = self.model.compiled(N, H, W)
         st.x.data.copy_(image, non_blocking=True)
+        self._evaluate(st, mask, label, patient_id, class_name)
+
+    @torch.no_grad()
+    def indexed(self, dataset, index, patient_id=None, class_name=None) -> None:
+        """`__call__` from a device-resident dataset (device_data.DeviceDataset): one assembly launch (identity transform) straight into the
+        plan's input, a mask plane and a float label column of the batch's own."""
+        st = self.model.compiled(len(index), dataset.H, dataset.W)
         dev = st.x.data.device
+        mask = torch.empty(st.N, 1, st.H, st.W, dtype=torch.float32, device=dev)
+        label = torch.empty(st.N, 1, dtype=torch.float32, device=dev)
+        dataset.assemble(index, None, n_onehot=0, out=(st.x.data, mask, label))
+        self._evaluate(st, mask, label, patient_id, class_name)
+
+    def _evaluate(self, st, mask: torch.Tensor, label: torch.Tensor, patient_id, class_name) -> None:
+        """Everything behind the filled input buffer: the programs, the metrics launch, the batch's rows."""
+        N, dev = st.N, st.x.data.device
         st.programs["pack"].run()
         st.programs["fwd"].run()
         self._coop_err = self.model.coop_error_word()

@@ -1409,7 +1409,8 @@ def fit_fold(step: FusedTrainStep, eval_step: FusedEvalStep, dataset, train_inde
 def test_one_epoch_indexed(test_step, dataset, tables) -> list:
     """The testing phase of the segmentation driver from a device-resident dataset: the batches of `tables` (no transforms) through an
     inference.FusedSegTestStep; the rows of results_segmentation.csv, read back once.  With an inference.FusedClsTestStep: the classification
-    driver's testing phase, the (ground_truth, predicted_label) rows of its results.csv."""
+    driver's testing phase, the (ground_truth, predicted_label) rows of its results.csv.  With an inference.FusedTestStep: the multi-task testing
+    phase, its (segmentation_rows, classification_rows)."""
     _check_tables(dataset, tables)
     _check_in_channels(test_step.model, dataset)
     test_step.reset()
