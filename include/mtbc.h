@@ -997,7 +997,8 @@ int mtbc_event_create(void** event);
 int mtbc_event_destroy(void* event);
 /* Host-only plan query for the small ops: every launch the call behind op->kind would make for op->u, in order and joined with " + ",
  * written to buf (NUL-terminated).  Covers MTBC_OP_POOL_FWD / _BWD, MTBC_OP_CONV1_FWD / _DGRAD / _WGRAD, MTBC_OP_GAP_FWD / _BWD,
- * MTBC_OP_LINEAR_FWD / _BWD, MTBC_OP_UPSAMPLE2_FWD / _BWD and MTBC_OP_HEAD_COMBINE / _EXPAND; any other kind (the 3x3, InstanceNorm and ConvT ops have queries of their
+ * MTBC_OP_LINEAR_FWD / _BWD, MTBC_OP_UPSAMPLE2_FWD / _BWD, MTBC_OP_HEAD_COMBINE / _EXPAND and the ops of a step's loss program, MTBC_OP_DICE_FWD / _BWD,
+ * MTBC_OP_FOCAL, MTBC_OP_LOSS_MIX and MTBC_OP_SOFTMAX; any other kind (the 3x3, InstanceNorm and ConvT ops have queries of their
  * own) is MTBC_E_BADARG.  Kernels are spelled as a profiler spells the instance without namespace and argument list, e.g.
  * "maxpool_c8_fwd_kernel<true>"; what the arguments select inside a kernel follows its name in brackets:
  *   conv1x1_c8_wgrad_kernel<F16> [nblk=1] | [nblk>1] | [nblk=32]   pixel chunks per image (one / several, the last may be ragged / the cap)
@@ -1006,6 +1007,15 @@ int mtbc_event_destroy(void* event);
  *   linear_wide_fwd_kernel + linear_wide_reduce_kernel             the batch-shared forward of a wide input and the sum of its split partials
  *   linear_wide_dx_kernel [+ linear_wide_dx_reduce_kernel]         ... its input gradient; the reduction only with more than one range of outputs
  *   upsample2_fwd_kernel | upsample2_fwd_scalar_kernel | upsample2_c8_fwd_kernel, upsample2_bwd_kernel | upsample2_bwd_scalar_kernel
+ *   dice_stats_kernel<kind> [threads=256|1024 paths=vsvv rounds=0|=1|>1 rest part] + dice_finalize_kernel<kind> [planes>256]
+ *                                                                  paths: per head the 16-byte (v) or the scalar (s) loop (H*W % 4 and the alignment of
+ *                                                                  x[h] / target); then, for the 16-byte loop, the unrolled rounds of four loads a
+ *                                                                  thread takes, `rest`: the loop behind them runs, `part`: some round or trip is taken by
+ *                                                                  a part of the block only; [planes>256]: a finalize thread sums several planes
+ *   dice_bwd_kernel<kind> [paths=vsvv loop]                        paths: as above, with dx[h]; loop: the grid is capped (4096 blocks) below a head's
+ *                                                                  items, so the grid-stride loop takes a second trip
+ *   focal_kernel [N>256], softmax_rows_kernel [N>64]               a thread of the one block owns more than one sample / row
+ *   loss_mix_kernel
  * and the planar 1x1 weight gradient's reduction is named with its instance: "splitk_reduce<4>", "<16>" (more than 32 images) or
  * "<64, 16>" (256 images or more), e.g. "conv1x1_wgrad_kernel + splitk_reduce<4> + plane_sum_k [threads=64] + sum_over_n_k".
  * It is the dispatcher of the real call, stopped in front of its launches: launches nothing, never synchronises, needs no device and never

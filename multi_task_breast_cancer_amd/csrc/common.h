@@ -176,7 +176,7 @@ struct NormChoice {
 extern "C" int mtbc_i_instnorm_fwd_c8(const mtbc_instnorm_args* a, hipStream_t st, NormChoice* query);
 extern "C" int mtbc_i_instnorm_bwd_c8(const mtbc_instnorm_args* a, float* part, hipStream_t st, NormChoice* query);
 extern "C" int mtbc_i_instnorm_bwd_c8_team(const mtbc_instnorm_args* a);
-// Which launches a max-pool, 1x1 convolution, GAP, Linear or fused-head call makes: the dispatchers of pool_up.hip, c8_ops.hip, head_loss.hip
+// Which launches a max-pool, 1x1 convolution, GAP, Linear, fused-head, loss or softmax call makes: the dispatchers of pool_up.hip, c8_ops.hip, head_loss.hip
 // and the two reducers of reduce.hip take a `query`; with it they validate as the call does, append every launch they would make -- the
 // kernel as a profiler spells the instance, then in brackets what the arguments select inside it -- and return without touching the stream
 // or the device.  Each decision (the kernel, its template argument, the reducer instance, a block size) is ONE local value that both the
@@ -215,6 +215,11 @@ int mtbc_i_gap_fwd(const mtbc_gap_args* a, hipStream_t st, OpChoice* query);
 int mtbc_i_gap_bwd(const mtbc_gap_args* a, hipStream_t st, OpChoice* query);
 int mtbc_i_linear_fwd(const mtbc_linear_args* a, hipStream_t st, OpChoice* query);
 int mtbc_i_linear_bwd(const mtbc_linear_args* a, hipStream_t st, OpChoice* query);
+int mtbc_i_dice_fwd(const mtbc_dice_args* a, hipStream_t st, OpChoice* query);
+int mtbc_i_dice_bwd(const mtbc_dice_args* a, hipStream_t st, OpChoice* query);
+int mtbc_i_focal_fwd_bwd(const mtbc_focal_args* a, hipStream_t st, OpChoice* query);
+int mtbc_i_loss_mix(const float* seg, const float* cls, float alpha, float* out4, hipStream_t st, OpChoice* query);
+int mtbc_i_softmax_rows(const mtbc_softmax_args* a, hipStream_t st, OpChoice* query);
 // internal (C++) helpers implemented in reduce.hip; query != NULL: append the launch(es) and return
 int mtbc_i_splitk_reduce(const float* partial, float* out, int nsplit, size_t elems, int accumulate, hipStream_t st);
 // rows of elems1 + elems2 floats per split: [0, elems1) summed into out, the rest into out2

@@ -3,6 +3,7 @@
 // shuffles (64 lanes) then LDS across waves -- deterministic, no float atomics.
 #include "common.h"
 #include <atomic>
+#include <cstring>
 
 namespace {
 
@@ -210,6 +211,11 @@ struct DiceP {
     float gamma;
 };
 enum { SEG_DICE = 0, SEG_BCE = 1, SEG_FOCALDICE = 2, SEG_JACCARD = 3 };
+// The 16-byte path of the two Dice kernels: whole float4 per plane and every base 16-byte aligned (with HW % 4 == 0 a plane starts aligned
+// where its tensor does).  One function for the kernels and for the dispatchers' query (mtbc_op_kernel_name).
+__host__ __device__ inline bool dice_vec16(int HW, const void* a, const void* b, const void* c = nullptr) {
+    return (HW & 3) == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
+}
 template <int K> struct SegStride { static constexpr int v = K == SEG_BCE ? 1 : (K == SEG_FOCALDICE ? 4 : 3); };
 
 // softplus(-|x|) = log1p(exp(-|x|)) and exp(-|x|) itself.  The focal term needs five of these per element over 4 x N x H x W elements a step, so
@@ -276,7 +282,7 @@ __global__ void dice_stats_kernel(const DiceP p) {
     const float* xs = p.x[h] + (size_t)plane * p.HW;
     const float* ts = p.target + (size_t)plane * p.HW;
     float si = 0.f, sp = 0.f, stt = 0.f, sf = 0.f;
-    if ((p.HW & 3) == 0 && ((reinterpret_cast<uintptr_t>(xs) | reinterpret_cast<uintptr_t>(ts)) & 15) == 0) {
+    if (dice_vec16(p.HW, xs, ts)) {
         // 16-byte loads, four rounds in flight per thread (the scalar loop below was one dependent 4-byte round trip per element pair:
         // 40 us for the four 256 x 256 heads of a step -- 128 blocks pulling 512 KB each)
         const float4* x4 = reinterpret_cast<const float4*>(xs);
@@ -370,7 +376,7 @@ __global__ void dice_bwd_kernel(const DiceP p) {
     const float scale = K == SEG_JACCARD ? p.gscale * (p.gscale_dev ? *p.gscale_dev : 1.f) * p.hw[h]
                                          : p.gscale * (p.gscale_dev ? *p.gscale_dev : 1.f) * p.hw[h] / (float)p.planes;
     const float scale_e = scale / (float)p.HW;
-    if ((p.HW & 3) == 0 && ((reinterpret_cast<uintptr_t>(p.x[h]) | reinterpret_cast<uintptr_t>(p.target) | reinterpret_cast<uintptr_t>(p.dx[h])) & 15) == 0) {
+    if (dice_vec16(p.HW, p.x[h], p.target, p.dx[h])) {
         // four pixels of one plane per thread: 16-byte loads / stores, the plane's constants once per four elements (same formula per element)
         const float4* x4 = reinterpret_cast<const float4*>(p.x[h]);
         const float4* t4 = reinterpret_cast<const float4*>(p.target);
@@ -655,20 +661,64 @@ __global__ void counts_to_double_kernel(double* out3) {
     }
 }
 
+// ---- the loss launches.  query != NULL: append the launches to *query and return without touching the stream or the device.
+constexpr int DICE_FIN_BLOCK = 256, DICE_BWD_BLOCK = 256, DICE_BWD_MAX_BLOCKS = 4096, FOCAL_BLOCK = 256, SOFTMAX_BLOCK = 64;
+// What dice_stats_kernel's two loops do on the 16-byte path for n4 float4 a plane and B threads: the unrolled rounds of thread 0 (no thread
+// takes more), whether any thread takes a trip of the rest loop, and whether some round or trip is taken by a part of the block only.
+struct DiceLoop { int rounds; bool rest, part; };
+DiceLoop dice_stats_loop(int n4, int B) {
+    DiceLoop s{0, false, false};
+    int u0 = 0, r0 = 0;
+    for (int t = 0; t < B; ++t) {
+        int i = t, u = 0, r = 0;
+        for (; i + 3 * B < n4; i += 4 * B) ++u;
+        for (; i < n4; i += B) ++r;
+        if (t == 0) { u0 = u; r0 = r; }
+        s.rest |= r > 0;
+        s.part |= u != u0 || r != r0;
+    }
+    s.rounds = u0;
+    return s;
+}
+void dice_paths(const DiceP& p, bool bwd, char out[5]) {        // per head: v = the 16-byte path, s = the scalar path
+    for (int h = 0; h < 4; ++h) out[h] = h >= p.n_heads ? 0 : (dice_vec16(p.HW, p.x[h], p.target, bwd ? p.dx[h] : nullptr) ? 'v' : 's');
+    out[4] = 0;
+}
 template <int K>
-int dice_fwd_launch(const DiceP& p, hipStream_t st) {
-    hipLaunchKernelGGL(dice_stats_kernel<K>, dim3(p.planes, p.n_heads), dim3(p.HW >= 16384 ? 1024 : 256), 0, st, p);
+int dice_fwd_launch(const DiceP& p, hipStream_t st, OpChoice* query) {
+    const int block = p.HW >= 16384 ? 1024 : 256;
+    const bool fin_loop = p.planes > DICE_FIN_BLOCK;            // a thread of the finalize block sums more than one plane
+    if (query) {
+        char paths[5]; dice_paths(p, false, paths);
+        const DiceLoop lp = dice_stats_loop(p.HW >> 2, block);
+        if (strchr(paths, 'v'))
+            query->add("dice_stats_kernel<%d> [threads=%d paths=%s rounds%s%s%s]", K, block, paths, lp.rounds > 1 ? ">1" : lp.rounds ? "=1" : "=0",
+                       lp.rest ? " rest" : "", lp.part ? " part" : "");
+        else
+            query->add("dice_stats_kernel<%d> [threads=%d paths=%s]", K, block, paths);
+        query->add(fin_loop ? "dice_finalize_kernel<%d> [planes>256]" : "dice_finalize_kernel<%d>", K);
+        return MTBC_OK;
+    }
+    hipLaunchKernelGGL(dice_stats_kernel<K>, dim3(p.planes, p.n_heads), dim3(block), 0, st, p);
     MTBC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(dice_finalize_kernel<K>, dim3(1), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(dice_finalize_kernel<K>, dim3(1), dim3(DICE_FIN_BLOCK), 0, st, p);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
 template <int K>
-int dice_bwd_launch(const DiceP& p, hipStream_t st) {
+int dice_bwd_launch(const DiceP& p, hipStream_t st, OpChoice* query) {
     const size_t total = (size_t)p.planes * p.HW;
-    size_t blocks = cdiv64(total, 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(dice_bwd_kernel<K>, dim3((unsigned)blocks, p.n_heads), dim3(256), 0, st, p);
+    const size_t want = cdiv64(total, DICE_BWD_BLOCK);
+    const bool capped = want > (size_t)DICE_BWD_MAX_BLOCKS;
+    const size_t blocks = capped ? (size_t)DICE_BWD_MAX_BLOCKS : want;
+    if (query) {          // [loop]: the capped grid has fewer threads than a head has items (float4 on the 16-byte path), so the stride loop takes a second trip
+        char paths[5]; dice_paths(p, true, paths);
+        bool loop = false;
+        for (int h = 0; h < p.n_heads; ++h) loop |= capped && (paths[h] == 'v' ? total >> 2 : total) > blocks * DICE_BWD_BLOCK;
+        query->add("dice_bwd_kernel<%d> [paths=%s%s]", K, paths, loop ? " loop" : "");
+        return MTBC_OK;
+    }
+    hipLaunchKernelGGL(dice_bwd_kernel<K>, dim3((unsigned)blocks, p.n_heads), dim3(DICE_BWD_BLOCK), 0, st, p);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
@@ -807,13 +857,7 @@ int mtbc_i_linear_bwd(const mtbc_linear_args* a, hipStream_t st, OpChoice* query
     return MTBC_OK;
 }
 
-extern "C" {
-
-int mtbc_gap_fwd(const mtbc_gap_args* a, void* stream) { return mtbc_i_gap_fwd(a, (hipStream_t)stream, nullptr); }
-int mtbc_gap_bwd(const mtbc_gap_args* a, void* stream) { return mtbc_i_gap_bwd(a, (hipStream_t)stream, nullptr); }
-int mtbc_linear_fwd(const mtbc_linear_args* a, void* stream) { return mtbc_i_linear_fwd(a, (hipStream_t)stream, nullptr); }
-int mtbc_linear_bwd(const mtbc_linear_args* a, void* stream) { return mtbc_i_linear_bwd(a, (hipStream_t)stream, nullptr); }
-
+// ---------------------------------------------------------------- the losses and the softmax: the dispatchers (query: as above)
 static int fill_dice(const mtbc_dice_args* a, DiceP* p) {
     if (!a || a->n_heads < 1 || a->n_heads > 4 || a->N <= 0 || a->C <= 0 || a->H <= 0 || a->W <= 0) return MTBC_E_BADSHAPE;
     if (!a->target || !a->stats) return MTBC_E_BADARG;
@@ -825,52 +869,67 @@ static int fill_dice(const mtbc_dice_args* a, DiceP* p) {
     for (int h = 0; h < a->n_heads; ++h) if (!a->x[h]) return MTBC_E_BADARG;
     return MTBC_OK;
 }
-int mtbc_dice_fwd(const mtbc_dice_args* a, void* stream) {
+int mtbc_i_dice_fwd(const mtbc_dice_args* a, hipStream_t st, OpChoice* query) {
     DiceP p; int rc = fill_dice(a, &p); if (rc) return rc;
     if (!p.loss) return MTBC_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
     switch (a->kind) {
-        case MTBC_SEG_BCE: return dice_fwd_launch<SEG_BCE>(p, st);
-        case MTBC_SEG_FOCALDICE: return dice_fwd_launch<SEG_FOCALDICE>(p, st);
-        case MTBC_SEG_JACCARD: return dice_fwd_launch<SEG_JACCARD>(p, st);
-        default: return dice_fwd_launch<SEG_DICE>(p, st);
+        case MTBC_SEG_BCE: return dice_fwd_launch<SEG_BCE>(p, st, query);
+        case MTBC_SEG_FOCALDICE: return dice_fwd_launch<SEG_FOCALDICE>(p, st, query);
+        case MTBC_SEG_JACCARD: return dice_fwd_launch<SEG_JACCARD>(p, st, query);
+        default: return dice_fwd_launch<SEG_DICE>(p, st, query);
     }
 }
-int mtbc_dice_bwd(const mtbc_dice_args* a, void* stream) {
+int mtbc_i_dice_bwd(const mtbc_dice_args* a, hipStream_t st, OpChoice* query) {
     DiceP p; int rc = fill_dice(a, &p); if (rc) return rc;
     for (int h = 0; h < a->n_heads; ++h) if (!a->dx[h]) return MTBC_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
     switch (a->kind) {
-        case MTBC_SEG_BCE: return dice_bwd_launch<SEG_BCE>(p, st);
-        case MTBC_SEG_FOCALDICE: return dice_bwd_launch<SEG_FOCALDICE>(p, st);
-        case MTBC_SEG_JACCARD: return dice_bwd_launch<SEG_JACCARD>(p, st);
-        default: return dice_bwd_launch<SEG_DICE>(p, st);
+        case MTBC_SEG_BCE: return dice_bwd_launch<SEG_BCE>(p, st, query);
+        case MTBC_SEG_FOCALDICE: return dice_bwd_launch<SEG_FOCALDICE>(p, st, query);
+        case MTBC_SEG_JACCARD: return dice_bwd_launch<SEG_JACCARD>(p, st, query);
+        default: return dice_bwd_launch<SEG_DICE>(p, st, query);
     }
 }
-
-int mtbc_focal_fwd_bwd(const mtbc_focal_args* a, void* stream) {
+int mtbc_i_focal_fwd_bwd(const mtbc_focal_args* a, hipStream_t st, OpChoice* query) {
     if (!a || a->N <= 0 || a->C <= 0) return MTBC_E_BADSHAPE;
     if (!a->x || !a->target || !a->loss) return MTBC_E_BADARG;
+    const int block = FOCAL_BLOCK;                              // one block: from N = block + 1 on a thread owns more than one sample
+    if (query) { query->add(a->N > block ? "focal_kernel [N>%d]" : "focal_kernel", block); return MTBC_OK; }
     FocalP p{a->N, a->C, a->alpha, a->gamma, a->x, a->target, a->weight, a->loss, a->dx, a->gscale, a->gscale_dev};
-    hipLaunchKernelGGL(focal_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(focal_kernel, dim3(1), dim3(block), 0, st, p);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
-
-int mtbc_loss_mix(const float* seg, const float* cls, float alpha, float* out4, void* stream) {
+int mtbc_i_loss_mix(const float* seg, const float* cls, float alpha, float* out4, hipStream_t st, OpChoice* query) {
     if (!seg || !cls || !out4) return MTBC_E_BADARG;
-    hipLaunchKernelGGL(loss_mix_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, seg, cls, alpha, out4);
+    if (query) { query->add("loss_mix_kernel"); return MTBC_OK; }
+    hipLaunchKernelGGL(loss_mix_kernel, dim3(1), dim3(1), 0, st, seg, cls, alpha, out4);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
-
-int mtbc_softmax_rows(const mtbc_softmax_args* a, void* stream) {
+int mtbc_i_softmax_rows(const mtbc_softmax_args* a, hipStream_t st, OpChoice* query) {
     const int rc = softmax_args_ok(a);
     if (rc != MTBC_OK) return rc;
-    hipLaunchKernelGGL(softmax_rows_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *a);
+    const int block = SOFTMAX_BLOCK;                            // one wave: from N = block + 1 on a thread owns more than one row
+    if (query) { query->add(a->N > block ? "softmax_rows_kernel [N>%d]" : "softmax_rows_kernel", block); return MTBC_OK; }
+    hipLaunchKernelGGL(softmax_rows_kernel, dim3(1), dim3(block), 0, st, *a);
     MTBC_CHECK_LAUNCH();
     return MTBC_OK;
 }
+
+extern "C" {
+
+int mtbc_gap_fwd(const mtbc_gap_args* a, void* stream) { return mtbc_i_gap_fwd(a, (hipStream_t)stream, nullptr); }
+int mtbc_gap_bwd(const mtbc_gap_args* a, void* stream) { return mtbc_i_gap_bwd(a, (hipStream_t)stream, nullptr); }
+int mtbc_linear_fwd(const mtbc_linear_args* a, void* stream) { return mtbc_i_linear_fwd(a, (hipStream_t)stream, nullptr); }
+int mtbc_linear_bwd(const mtbc_linear_args* a, void* stream) { return mtbc_i_linear_bwd(a, (hipStream_t)stream, nullptr); }
+
+int mtbc_dice_fwd(const mtbc_dice_args* a, void* stream) { return mtbc_i_dice_fwd(a, (hipStream_t)stream, nullptr); }
+int mtbc_dice_bwd(const mtbc_dice_args* a, void* stream) { return mtbc_i_dice_bwd(a, (hipStream_t)stream, nullptr); }
+int mtbc_focal_fwd_bwd(const mtbc_focal_args* a, void* stream) { return mtbc_i_focal_fwd_bwd(a, (hipStream_t)stream, nullptr); }
+int mtbc_loss_mix(const float* seg, const float* cls, float alpha, float* out4, void* stream) {
+    return mtbc_i_loss_mix(seg, cls, alpha, out4, (hipStream_t)stream, nullptr);
+}
+int mtbc_softmax_rows(const mtbc_softmax_args* a, void* stream) { return mtbc_i_softmax_rows(a, (hipStream_t)stream, nullptr); }
 int mtbc_softmax_rows_host(const mtbc_softmax_args* a) {
     const int rc = softmax_args_ok(a);
     if (rc != MTBC_OK) return rc;

@@ -53,6 +53,11 @@ int mtbc_op_kernel_name(const mtbc_op* op, char* buf, int32_t len) {
         case MTBC_OP_UPSAMPLE2_BWD: rc = mtbc_i_upsample2_bwd(&op->u.up2, nullptr, &ch); break;
         case MTBC_OP_HEAD_COMBINE: rc = mtbc_i_head_combine(&op->u.head, nullptr, &ch); break;
         case MTBC_OP_HEAD_EXPAND: rc = mtbc_i_head_expand(&op->u.head, nullptr, &ch); break;
+        case MTBC_OP_DICE_FWD: rc = mtbc_i_dice_fwd(&op->u.dice, nullptr, &ch); break;
+        case MTBC_OP_DICE_BWD: rc = mtbc_i_dice_bwd(&op->u.dice, nullptr, &ch); break;
+        case MTBC_OP_FOCAL: rc = mtbc_i_focal_fwd_bwd(&op->u.focal, nullptr, &ch); break;
+        case MTBC_OP_LOSS_MIX: rc = mtbc_i_loss_mix(op->u.mix.seg, op->u.mix.cls, op->u.mix.alpha, op->u.mix.out4, nullptr, &ch); break;
+        case MTBC_OP_SOFTMAX: rc = mtbc_i_softmax_rows(&op->u.softmax, nullptr, &ch); break;
         default: return MTBC_E_BADARG;
     }
     if (rc) return rc;

@@ -1189,25 +1189,16 @@ class StepPlan:
         self.keep.append(self.grad_weight)
         weights = [(1.0 / (nh - i)) if inversely_weighted else 1.0 for i in range(nh)]   # head i is reversed index nh-1-i
 
-        def dice_base(kind: int) -> L.Op:
+        ptrs = {"x": [h.data for h in seg_heads], "dx": [self.grad_of(h) for h in seg_heads], "target": mask, "stats": self.dice_stats,
+                "loss": self.dice_loss, "gscale_dev": self.grad_weight}
+        for kind in (L.OP_DICE_FWD, L.OP_DICE_BWD):
             op = _mk(kind)
-            a = op.u.dice
-            a.n_heads, a.N, a.C, a.H, a.W, a.smooth_nr, a.smooth_dr = nh, N, C_, H, W, seg_nr, seg_dr
-            a.kind, a.focal_gamma = seg_kind, seg_gamma
-            for i, h in enumerate(seg_heads):
-                a.x[i] = h.data.data_ptr()
-                a.head_weight[i] = weights[i]
-            a.target, a.stats, a.loss = mask.data_ptr(), self.dice_stats.data_ptr(), self.dice_loss.data_ptr()
-            return op
-
-        self.loss_ops.append(dice_base(L.OP_DICE_FWD))
-        op = dice_base(L.OP_DICE_BWD)
-        for i, h in enumerate(seg_heads):
-            op.u.dice.dx[i] = self.grad_of(h).data_ptr()
+            # gscale (read by the backward only) carries loss_scale: fp16 mode keeps dz inside the fp16 range; Adam divides it out
+            _ops.dice_case_args(kind, nh, N, C_, H, W, ptrs=ptrs, seg_kind=seg_kind, weights=weights, smooth=(seg_nr, seg_dr), focal_gamma=seg_gamma,
+                                gscale=alpha * loss_scale, gscale_dev=True, into=op.u.dice)
+            self.loss_ops.append(op)
+        for h in seg_heads:
             h.grad_written = True
-        op.u.dice.gscale_dev = self.grad_weight.data_ptr()
-        op.u.dice.gscale = alpha * loss_scale      # loss_scale: fp16 mode keeps dz inside the fp16 range; Adam divides it out
-        self.loss_ops.append(op)
         # classification criterion (experiment_init.py:232-262): "Focal" = FocalLoss(alpha 1, gamma 2); "CE" = CrossEntropyLoss = the same
         # formula with gamma 0; the ONE-logit head (n_classes == 2, `binary`) = BCEWithLogitsLoss on the {0, 1} label, which the focal
         # kernel evaluates when C == 1 (gamma 0): `onehot` then holds the (N, 1) float label itself
@@ -1226,11 +1217,10 @@ class StepPlan:
         """The classification criterion's op of `fused_losses` on `logits` (whatever the model hands its criterion), gradient into its grad buffer."""
         assert (logits.C == 1) == bool(binary), "one logit <=> binary head"
         op = _mk(L.OP_FOCAL)
-        a = op.u.focal
-        a.N, a.C, a.alpha, a.gamma = N, logits.C, 1.0, (0.0 if binary else float(cls_gamma))
-        a.x, a.target, a.weight = logits.data.data_ptr(), onehot.data_ptr(), _ptr(focal_weight)
-        a.loss, a.dx, a.gscale = self.focal_loss.data_ptr(), self.grad_of(logits).data_ptr(), gscale
-        a.gscale_dev = self.grad_weight.data_ptr()
+        ptrs = {"x": logits.data, "target": onehot, "weight": focal_weight, "loss": self.focal_loss, "dx": self.grad_of(logits),
+                "gscale_dev": self.grad_weight}
+        _ops.focal_case_args(N, logits.C, ptrs=ptrs, alpha=1.0, gamma=(0.0 if binary else float(cls_gamma)), weight=focal_weight is not None,
+                             gscale=gscale, gscale_dev=True, into=op.u.focal)
         logits.grad_written = True
         self.loss_ops.append(op)
 

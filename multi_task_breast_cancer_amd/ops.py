@@ -5,7 +5,7 @@ goes through step programs (engine.py).  Device fp32 tensors only; every wrapper
 
 Each argument struct is filled in ONE function, the family's *_case_args builder: with ptrs=None it carries dummy addresses for the host-only
 *_kernel_name queries (the launch-coverage guards of the tests), with ptrs= tensors it is what conv3x3_launch / instnorm_launch /
-convT_launch / small_op_launch hand the library.  The eager wrappers validate, allocate, call the builder and launch.
+convT_launch / small_op_launch / loss_op_launch hand the library.  The eager wrappers validate, allocate, call the builder and launch.
 """
 from __future__ import annotations
 
@@ -791,10 +791,80 @@ def conv1x1_wgrad_c8(x8: "C8", w, dy, accumulate=False, dw=None, db=None):
 
 
 # ------------------------------------------------------------------ losses / optimiser
+LOSS_OPS = (L.OP_DICE_FWD, L.OP_DICE_BWD, L.OP_FOCAL, L.OP_LOSS_MIX, L.OP_SOFTMAX)      # op_kernel_name covers these beside SMALL_OPS
+_LOSS_DUMMY = _dummies("x0", "x1", "x2", "x3", "dx0", "dx1", "dx2", "dx3", "target", "stats", "loss", "gscale_dev", "x", "weight", "dx")
+_SEG_DEFAULTS = {kind: (nr, dr, gamma) for kind, nr, dr, gamma, _ in L.SEG_CRITERIA.values()}
+
+
+def dice_case_args(kind_op: int, n_heads: int, N: int, Cc: int, H: int, W: int, ptrs: Optional[dict] = None, seg_kind: int = L.SEG_DICE,
+                   weights: Optional[Sequence[float]] = None, smooth: Optional[Tuple[float, float]] = None, focal_gamma: Optional[float] = None,
+                   gscale: float = 1.0, gscale_dev: bool = False, into: Optional["L.DiceArgs"] = None):
+    """The MTBC_OP_DICE_FWD / _BWD op of ONE segmentation-criterion call as engine.StepPlan.fused_losses fills it, and the only place that
+    fills a mtbc_dice_args.  ptrs: x and dx -> a list of n_heads tensors, target, stats, loss, gscale_dev -> a tensor; None = distinct 16-byte
+    aligned dummies that nothing may dereference (for op_kernel_name).  seg_kind: L.SEG_*; weights: the heads' weights (default 1);
+    smooth = (nr, dr) and focal_gamma default to the criterion's of L.SEG_CRITERIA (focal_gamma is 0 outside FocalDICE whatever is passed).
+    Both ops carry x, the weights, target, stats and loss; only the backward carries dx, gscale and -- with gscale_dev -- the address of the
+    device word multiplied into the gradient.  `into`: the struct inside a step-program op, returned instead of a new op."""
+    op = None
+    if into is None:
+        op = _small_op(kind_op)
+        into = op.u.dice
+    a, nr, dr, gamma = into, *_SEG_DEFAULTS[seg_kind]
+    if smooth is not None:
+        nr, dr = smooth
+    if focal_gamma is not None and seg_kind == L.SEG_FOCALDICE:
+        gamma = focal_gamma
+    a.n_heads, a.N, a.C, a.H, a.W, a.smooth_nr, a.smooth_dr = n_heads, N, Cc, H, W, nr, dr
+    a.kind, a.focal_gamma = seg_kind, gamma
+
+    def ptr(name, i=None):
+        if ptrs is None:
+            return _LOSS_DUMMY[name if i is None else f"{name}{i}"]
+        return _p(ptrs[name] if i is None else ptrs[name][i])
+
+    for i in range(n_heads):
+        a.x[i] = ptr("x", i)
+        a.head_weight[i] = 1.0 if weights is None else weights[i]
+    a.target, a.stats, a.loss = ptr("target"), ptr("stats"), ptr("loss")
+    if kind_op == L.OP_DICE_BWD:
+        for i in range(n_heads):
+            a.dx[i] = ptr("dx", i)
+        a.gscale_dev = ptr("gscale_dev") if gscale_dev else None
+        a.gscale = gscale
+    return a if op is None else op
+
+
+def focal_case_args(N: int, Cc: int, ptrs: Optional[dict] = None, alpha: float = 1.0, gamma: float = 2.0, weight: bool = False, dx: bool = True,
+                    gscale: float = 1.0, gscale_dev: bool = False, into: Optional["L.FocalArgs"] = None):
+    """The MTBC_OP_FOCAL op of ONE classification-criterion call as engine.StepPlan._focal_op fills it, and the only place that fills a
+    mtbc_focal_args.  ptrs: x, target, loss and -- where the flag of the same name is set -- weight, dx, gscale_dev -> a tensor; None = dummies.
+    `into`: the struct inside a step-program op, returned instead of a new op."""
+    op = None
+    if into is None:
+        op = _small_op(L.OP_FOCAL)
+        into = op.u.focal
+    a, ptr = into, _ptr(ptrs, _LOSS_DUMMY.__getitem__)
+    a.N, a.C, a.alpha, a.gamma = N, Cc, alpha, gamma
+    a.x, a.target, a.weight = ptr("x"), ptr("target"), (ptr("weight") if weight else None)
+    a.loss, a.dx, a.gscale = ptr("loss"), (ptr("dx") if dx else None), gscale
+    a.gscale_dev = ptr("gscale_dev") if gscale_dev else None
+    return a if op is None else op
+
+
+def loss_op_launch(op: "L.Op") -> None:
+    """The entry point behind a Dice / Focal / softmax op (of dice_case_args, focal_case_args or an op around softmax_args) on the current
+    stream; records (kind, launches) while `launched` is a list."""
+    lib = L.load()
+    fn = {L.OP_DICE_FWD: lib.mtbc_dice_fwd, L.OP_DICE_BWD: lib.mtbc_dice_bwd, L.OP_FOCAL: lib.mtbc_focal_fwd_bwd, L.OP_SOFTMAX: lib.mtbc_softmax_rows}[op.kind]
+    if launched is not None:
+        launched.append((op.kind, op_kernel_name(op)))
+    L.check(fn(C.byref(getattr(op.u, L.OP_UNION_FIELD[op.kind])), _s()), f"loss op {op.kind}")
+
+
 def dice_multihead(xs: Sequence[torch.Tensor], target, weights: Sequence[float], gscale: float = 1.0, kind: int = 0,
                    smooth: Optional[Tuple[float, float]] = None, focal_gamma: float = 2.0):
     """returns (loss[n_heads+1], [dx per head]).  kind: L.SEG_DICE (0, the default) | SEG_BCE | SEG_FOCALDICE | SEG_JACCARD; `smooth` = (nr, dr),
-    default the reference's for the kind (1 / 1; Jaccard: MONAI's 1e-5 / 1e-5)."""
+    default the reference's for the kind (1 / 1; Jaccard: MONAI's 1e-5 / 1e-5; BCE reads neither)."""
     _chk(*xs, target)
     nh = len(xs)
     N, Cc, H, W = xs[0].shape
@@ -802,16 +872,10 @@ def dice_multihead(xs: Sequence[torch.Tensor], target, weights: Sequence[float],
     stats = torch.empty(nh * N * Cc * L.SEG_STATS_STRIDE[kind], dtype=torch.float32, device=dev)
     loss = torch.empty(nh + 1, dtype=torch.float32, device=dev)
     dxs = [torch.empty_like(x) for x in xs]
-    a = L.DiceArgs()
-    nr, dr = smooth if smooth is not None else ((1e-5, 1e-5) if kind == L.SEG_JACCARD else (1.0, 1.0))
-    a.n_heads, a.N, a.C, a.H, a.W, a.smooth_nr, a.smooth_dr = nh, N, Cc, H, W, nr, dr
-    if kind != L.SEG_DICE:
-        a.kind, a.focal_gamma = kind, (focal_gamma if kind == L.SEG_FOCALDICE else 0.0)
-    for i in range(nh):
-        a.x[i], a.dx[i], a.head_weight[i] = xs[i].data_ptr(), dxs[i].data_ptr(), weights[i]
-    a.target, a.stats, a.loss, a.gscale = target.data_ptr(), stats.data_ptr(), loss.data_ptr(), gscale
-    L.check(L.load().mtbc_dice_fwd(C.byref(a), _s()), "dice_fwd")
-    L.check(L.load().mtbc_dice_bwd(C.byref(a), _s()), "dice_bwd")
+    ptrs = {"x": list(xs), "dx": dxs, "target": target, "stats": stats, "loss": loss}
+    for kind_op in (L.OP_DICE_FWD, L.OP_DICE_BWD):
+        loss_op_launch(dice_case_args(kind_op, nh, N, Cc, H, W, ptrs=ptrs, seg_kind=kind, weights=weights, smooth=smooth, focal_gamma=focal_gamma,
+                                      gscale=gscale))
     return loss, dxs
 
 
@@ -819,10 +883,8 @@ def focal(x, t, alpha=1.0, gamma=2.0, weight=None, gscale=1.0):
     _chk(x, t, weight)
     loss = torch.empty(1, dtype=torch.float32, device=x.device)
     dx = torch.empty_like(x)
-    a = L.FocalArgs()
-    a.N, a.C, a.alpha, a.gamma = x.shape[0], x.shape[1], alpha, gamma
-    a.x, a.target, a.weight, a.loss, a.dx, a.gscale = x.data_ptr(), t.data_ptr(), _p(weight), loss.data_ptr(), dx.data_ptr(), gscale
-    L.check(L.load().mtbc_focal_fwd_bwd(C.byref(a), _s()), "focal")
+    loss_op_launch(focal_case_args(x.shape[0], x.shape[1], ptrs={"x": x, "target": t, "weight": weight, "loss": loss, "dx": dx}, alpha=alpha,
+                                   gamma=gamma, weight=weight is not None, gscale=gscale))
     return loss, dx
 
 
@@ -956,8 +1018,8 @@ SMALL_OPS = (L.OP_POOL_FWD, L.OP_POOL_BWD, L.OP_CONV1_FWD, L.OP_CONV1_DGRAD, L.O
 
 
 def op_kernel_name(op: "L.Op") -> str:
-    """Every launch the call behind a max-pool, 1x1 convolution, GAP, Linear or fused-head op (SMALL_OPS) would make, joined with " + ":
-    mtbc_op_kernel_name, host-only (no launch, no device).  Raises what the call would."""
+    """Every launch the call behind a max-pool, 1x1 convolution, GAP, Linear or fused-head op (SMALL_OPS) or behind a Dice, Focal, loss-mix or
+    softmax op (LOSS_OPS) would make, joined with " + ": mtbc_op_kernel_name, host-only (no launch, no device).  Raises what the call would."""
     buf = C.create_string_buffer(512)
     L.check(L.load().mtbc_op_kernel_name(C.byref(op), buf, len(buf)), "op_kernel_name")
     return buf.value.decode()

@@ -242,6 +242,34 @@ def _small_op_key(op):
     return name, tuple(f)
 
 
+def _loss_key(op):
+    """Coverage key of ONE op of a step's loss program (ops.LOSS_OPS: Dice forward / backward, Focal, the loss mix, the classifier's softmax):
+    the launches mtbc_op_kernel_name plans -- block size, per head the 16-byte or the scalar path, the shape of the statistics loop, a looping
+    finalize / backward grid / focal block -- + the branches the ARGUMENTS select inside those kernels that the name does not carry.  A field
+    the call does not read does not enter its key (head_loss.hip): the Dice forward reads neither gscale nor gscale_dev nor dx, focal_gamma
+    is read by the FocalDICE kind only (its value is no branch), smooth_nr / smooth_dr and the head weights are values."""
+    L = ops.L
+    name, k, f = ops.op_kernel_name(op), op.kind, []
+    if k in (L.OP_DICE_FWD, L.OP_DICE_BWD):
+        a = op.u.dice
+        f += [f"kind={a.kind}", f"n_heads={a.n_heads}"]
+        if k == L.OP_DICE_BWD and a.gscale_dev:       # (dice_bwd_kernel: `p.gscale_dev ? *p.gscale_dev : 1.f`)
+            f.append("gscale_dev")
+        f += ["C>1"] if a.C > 1 else []               # (planes = N * C: a plane index is no image index)
+    elif k == L.OP_FOCAL:
+        a = op.u.focal                                # (focal_kernel: `p.C == 1`, `p.w ?`, `if (p.dx)`, `p.gscale_dev ?`, gamma == 0 / >= 1)
+        f.append(f"C={a.C}")
+        f += [n for n in ("weight", "dx") if getattr(a, n)]
+        if a.dx and a.gscale_dev:                     # (read only where a gradient is written)
+            f.append("gscale_dev")
+        f.append("gamma=0" if a.gamma == 0.0 else "0<gamma<1" if a.gamma < 1.0 else "gamma>=1")
+    elif k == L.OP_SOFTMAX:
+        f += ["bwd" if op.u.softmax.backward else "fwd", f"C={op.u.softmax.C}"]
+    else:
+        assert k == L.OP_LOSS_MIX, k                  # (no branch on an argument)
+    return name, tuple(f)
+
+
 def _pack_key(kind, Cin, Cout, dgrad, compute, path):
     """Coverage key of one weight-image op from its arguments: what selects a kernel path (kind, format, single or batched) and the branches
     inside it (a ragged last row tile, a ragged last K chunk -- for the fp32 forward image of the batched launch: 16 x 16 patches that
@@ -337,8 +365,20 @@ def collect_layout(prog, i):
         return 1, kind, _c8_key(kind, *args), args
 
 
+_LOSS_SHAPE = {"dice": ("n_heads", "N", "C", "H", "W"), "focal": ("N", "C"), "softmax": ("N", "C"), "mix": ()}
+
+
+def collect_loss(prog, i):
+    """The ops of the loss program and the classifier's softmax pair; where = (n_heads, N, C, H, W) of a Dice op, (N, C) of a Focal or softmax
+    op, () of the mix."""
+    op = prog[i]
+    if op.kind in ops.LOSS_OPS:
+        field = L.OP_UNION_FIELD[op.kind]
+        return 1, op.kind, (op.kind, _loss_key(op)), _fields(getattr(op.u, field), *_LOSS_SHAPE[field])
+
+
 COLLECTORS = {"conv3x3": collect_conv3x3, "InstanceNorm": collect_instnorm, "transposed-convolution": collect_convT, "small-op": collect_small_op,
-              "layout": collect_layout}
+              "layout": collect_layout, "loss": collect_loss}
 
 # program: (arch, dtype, N, size); kinds: {program name: [op kind]}; seen: {family: {key: (kind label, where) of the first op that has it}}
 Survey = collections.namedtuple("Survey", "program reserve_cus kinds seen")

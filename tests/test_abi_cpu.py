@@ -647,7 +647,7 @@ def test_small_op_kernel_name_refuses_what_the_call_refuses(lib):
     assert name(op) == -2
     assert name(ops.head_case_args(HE, 8, 4, 1, 2, bT=False, b1=False, dbT=False, db1=False)) == 0      # every optional pointer absent
     for kind in range(0, 40):                                                               # every other op kind: not this query's
-        if kind not in ops.SMALL_OPS:
+        if kind not in ops.SMALL_OPS + ops.LOSS_OPS:
             op = ops.gap_case_args(G_, 2, 8, 4, 4)
             op.kind = kind
             assert name(op) == -2, kind
@@ -657,6 +657,134 @@ def test_small_op_kernel_name_refuses_what_the_call_refuses(lib):
     assert lib.mtbc_op_kernel_name(C.byref(op), buf, len(want) + 1) == 0 and buf.value == want
     assert lib.mtbc_op_kernel_name(C.byref(op), None, 512) == -2
     assert lib.mtbc_op_kernel_name(None, buf, 512) == -2
+
+
+# (what, arguments, mode) -> what mtbc_op_kernel_name names: one row per dispatch decision of the Dice, Focal, loss-mix and softmax calls
+# (head_loss.hip), each boundary from both sides.  Dice: (n_heads, N, C, H, W), mode = keywords of ops.dice_case_args + `poke`: field -> bytes
+# added to head 0's dummy address; Focal: (N, C); softmax: (N, C, backward).
+_DF, _DB = L.OP_DICE_FWD, L.OP_DICE_BWD
+_FIN = " + dice_finalize_kernel"
+LOSS_OP_SELECTION = [
+    (_DF, (1, 1, 1, 4095, 4), {}, "dice_stats_kernel<0> [threads=256 paths=v rounds>1 rest part]" + _FIN + "<0>"),            # H * W = 16380: the last 256-thread plane
+    (_DF, (1, 1, 1, 4096, 4), {}, "dice_stats_kernel<0> [threads=1024 paths=v rounds=1]" + _FIN + "<0>"),                     # 16384; n4 = 4096: one round, nothing else
+    (_DF, (1, 1, 1, 4097, 4), {}, "dice_stats_kernel<0> [threads=1024 paths=v rounds=1 rest part]" + _FIN + "<0>"),           # n4 = 4097: thread 0 alone takes a rest trip
+    (_DF, (1, 1, 1, 7168, 4), {}, "dice_stats_kernel<0> [threads=1024 paths=v rounds=1 rest]" + _FIN + "<0>"),                # n4 = 7168: three rest trips each
+    (_DF, (1, 1, 1, 7169, 4), {}, "dice_stats_kernel<0> [threads=1024 paths=v rounds>1 rest part]" + _FIN + "<0>"),           # n4 = 7169: thread 0 alone takes a second round
+    (_DF, (4, 2, 1, 256, 256), {}, "dice_stats_kernel<0> [threads=1024 paths=vvvv rounds>1]" + _FIN + "<0>"),
+    (_DF, (2, 1, 1, 2, 4), {}, "dice_stats_kernel<0> [threads=256 paths=vv rounds=0 rest part]" + _FIN + "<0>"),              # fewer float4 than threads
+    (_DF, (2, 2, 1, 6, 5), dict(seg_kind=L.SEG_BCE), "dice_stats_kernel<1> [threads=256 paths=ss]" + _FIN + "<1>"),           # H * W % 4 != 0
+    (_DF, (3, 2, 1, 16, 16), dict(seg_kind=L.SEG_FOCALDICE, poke=dict(x=4)), "dice_stats_kernel<2> [threads=256 paths=svv rounds=0 rest part]" + _FIN + "<2>"),
+    (_DF, (1, 2, 1, 16, 16), dict(seg_kind=L.SEG_JACCARD, poke=dict(target=4)), "dice_stats_kernel<3> [threads=256 paths=s]" + _FIN + "<3>"),
+    (_DF, (1, 2, 1, 16, 16), dict(poke=dict(dx=4)), "dice_stats_kernel<0> [threads=256 paths=v rounds=0 rest part]" + _FIN + "<0>"),      # the forward does not read dx
+    (_DF, (1, 256, 1, 4, 4), {}, "dice_stats_kernel<0> [threads=256 paths=v rounds=0 rest part]" + _FIN + "<0>"),
+    (_DF, (1, 257, 1, 4, 4), {}, "dice_stats_kernel<0> [threads=256 paths=v rounds=0 rest part]" + _FIN + "<0> [planes>256]"),
+    (_DF, (1, 129, 2, 4, 4), dict(seg_kind=L.SEG_JACCARD), "dice_stats_kernel<3> [threads=256 paths=v rounds=0 rest part]" + _FIN + "<3> [planes>256]"),
+    (_DB, (4, 2, 1, 256, 256), {}, "dice_bwd_kernel<0> [paths=vvvv]"),
+    (_DB, (2, 2, 1, 6, 5), dict(seg_kind=L.SEG_BCE), "dice_bwd_kernel<1> [paths=ss]"),
+    (_DB, (2, 2, 1, 16, 16), dict(seg_kind=L.SEG_FOCALDICE, poke=dict(dx=4)), "dice_bwd_kernel<2> [paths=sv]"),
+    (_DB, (2, 2, 1, 16, 16), dict(seg_kind=L.SEG_JACCARD, poke=dict(x=8)), "dice_bwd_kernel<3> [paths=sv]"),
+    (_DB, (1, 16, 1, 512, 512), {}, "dice_bwd_kernel<0> [paths=v]"),                          # 4 194 304 elements: 4096 x 256 threads, one float4 each
+    (_DB, (1, 1, 1, 1048577, 4), {}, "dice_bwd_kernel<0> [paths=v loop]"),                    # 4 194 308: one float4 more
+    (_DB, (1, 1, 1, 1048575, 1), {}, "dice_bwd_kernel<0> [paths=s]"),                         # the scalar loop: 4096 blocks are not capped
+    (_DB, (1, 1, 1, 1048577, 1), {}, "dice_bwd_kernel<0> [paths=s loop]"),
+    (_DB, (2, 1, 1, 1048577, 4), dict(poke=dict(dx=4)), "dice_bwd_kernel<0> [paths=sv loop]"),
+    (L.OP_FOCAL, (256, 3), {}, "focal_kernel"),
+    (L.OP_FOCAL, (257, 3), dict(weight=True, dx=False), "focal_kernel [N>256]"),
+    (L.OP_FOCAL, (5, 1), dict(gamma=0.0), "focal_kernel"),
+    (L.OP_SOFTMAX, (64, 3, False), {}, "softmax_rows_kernel"),
+    (L.OP_SOFTMAX, (65, 3, False), {}, "softmax_rows_kernel [N>64]"),
+    (L.OP_SOFTMAX, (64, 2, True), {}, "softmax_rows_kernel"),
+    (L.OP_SOFTMAX, (65, 1, True), {}, "softmax_rows_kernel [N>64]"),
+    (L.OP_LOSS_MIX, (), {}, "loss_mix_kernel"),
+]
+
+
+def _loss_op(kind, shape, mode):
+    """The op of a row of LOSS_OP_SELECTION through its struct's filler (dummy pointers)."""
+    from multi_task_breast_cancer_amd import ops
+    mode = dict(mode)
+    poke = mode.pop("poke", {})
+    if kind in (_DF, _DB):
+        op = ops.dice_case_args(kind, *shape, **mode)
+        for name, nbytes in poke.items():
+            if name == "target":
+                op.u.dice.target += nbytes
+            else:
+                getattr(op.u.dice, name)[0] = (getattr(op.u.dice, name)[0] or 0) + nbytes
+        return op
+    if kind == L.OP_FOCAL:
+        return ops.focal_case_args(*shape, **mode)
+    op = L.Op()
+    op.kind = kind
+    if kind == L.OP_SOFTMAX:
+        N, Cc, backward = shape
+        ops.softmax_args(N, Cc, backward, x=1 << 20, p=2 << 20, dp=3 << 20, dz=4 << 20, into=op.u.softmax)
+    else:
+        op.u.mix.seg, op.u.mix.cls, op.u.mix.alpha, op.u.mix.out4 = 1 << 20, 2 << 20, 0.5, 3 << 20
+    return op
+
+
+@pytest.mark.parametrize("kind,shape,mode,want", LOSS_OP_SELECTION)
+def test_loss_op_kernel_selection(lib, kind, shape, mode, want):
+    """mtbc_op_kernel_name (host only: the dummy pointers are never dereferenced) names every launch of a Dice, Focal, loss-mix or softmax
+    call and what the arguments -- pointer VALUES included -- select inside it."""
+    from multi_task_breast_cancer_amd import ops
+    assert ops.op_kernel_name(_loss_op(kind, shape, mode)) == want
+
+
+def test_loss_op_kernel_name_refuses_what_the_call_refuses(lib):
+    from multi_task_breast_cancer_amd import ops
+    buf = C.create_string_buffer(512)
+    name = lambda op: lib.mtbc_op_kernel_name(C.byref(op), buf, 512)      # noqa: E731
+    for kind in (_DF, _DB):
+        assert name(ops.dice_case_args(kind, 0, 2, 1, 8, 8)) == -1                          # no head
+        op = ops.dice_case_args(kind, 4, 2, 1, 8, 8)
+        op.u.dice.n_heads = 5                                                               # more heads than the struct holds
+        assert name(op) == -1
+        assert name(ops.dice_case_args(kind, 2, 2, 1, 0, 8)) == -1
+        op = ops.dice_case_args(kind, 3, 2, 1, 8, 8)
+        op.u.dice.x[1] = None                                                               # a NULL head
+        assert name(op) == -2
+        op = ops.dice_case_args(kind, 3, 2, 1, 8, 8)
+        op.u.dice.x[3] = None                                                               # ... behind the last one: not read
+        assert name(op) == 0
+        op = ops.dice_case_args(kind, 2, 2, 1, 8, 8)
+        op.u.dice.kind = 4                                                                  # no such criterion
+        assert name(op) == -5
+        op = ops.dice_case_args(kind, 2, 2, 1, 8, 8)
+        op.u.dice.stats = None
+        assert name(op) == -2
+    op = ops.dice_case_args(_DF, 2, 2, 1, 8, 8)
+    op.u.dice.loss = None
+    assert name(op) == -2
+    op = ops.dice_case_args(_DB, 2, 2, 1, 8, 8)
+    op.u.dice.loss = None                                                                   # the backward writes no loss
+    assert name(op) == 0
+    op = ops.dice_case_args(_DB, 2, 2, 1, 8, 8)
+    op.u.dice.dx[1] = None
+    assert name(op) == -2
+    op = ops.dice_case_args(_DF, 2, 2, 1, 8, 8)
+    assert not op.u.dice.dx[0] and name(op) == 0                                            # the forward needs no dx
+    assert name(ops.focal_case_args(0, 3)) == -1 and name(ops.focal_case_args(4, 0)) == -1
+    for field in ("x", "target", "loss"):
+        op = ops.focal_case_args(4, 3)
+        setattr(op.u.focal, field, None)
+        assert name(op) == -2, field
+    assert name(ops.focal_case_args(4, 3, dx=False)) == 0                                   # weight, dx and gscale_dev are optional
+    assert name(_loss_op(L.OP_SOFTMAX, (4, 4, False), {})) == -1                            # C outside 1 .. 3
+    assert name(_loss_op(L.OP_SOFTMAX, (0, 3, False), {})) == -1
+    op = _loss_op(L.OP_SOFTMAX, (4, 3, True), {})
+    op.u.softmax.dp = None
+    assert name(op) == -2
+    op = _loss_op(L.OP_SOFTMAX, (4, 3, False), {})
+    op.u.softmax.dp = op.u.softmax.dz = None                                                # the forward reads neither
+    assert name(op) == 0
+    op.u.softmax.x = None
+    assert name(op) == -2
+    for field in ("seg", "cls", "out4"):
+        op = _loss_op(L.OP_LOSS_MIX, (), {})
+        setattr(op.u.mix, field, None)
+        assert name(op) == -2, field
 
 
 # ---------------------------------------------------------------- one filler, two callers: dummy pointers (the guards) against ptrs= (the launches)

@@ -218,11 +218,13 @@ def _borrowed_small_op_keys():
 
 
 def _tested():
-    """{family: (the keys of tests/test_ops_gpu.py's tables, the keys this module adds)}"""
+    """{family: (the keys of the older tables -- tests/test_ops_gpu.py's, for the loss family tests/test_loss_launches_gpu.py's --, the keys this
+    module adds)}"""
+    import test_loss_launches_gpu as LOSS
     OPS, own = _ops_gpu(), _own_keys()
     old = {"conv3x3": OPS._reference_tested_conv3x3_keys(), "InstanceNorm": OPS._reference_tested_instnorm_keys(),
            "transposed-convolution": OPS._reference_tested_convT_keys(), "small-op": OPS._reference_tested_small_op_keys(),
-           "layout": OPS._reference_tested_layout_keys()}
+           "layout": OPS._reference_tested_layout_keys(), "loss": LOSS._reference_tested_loss_keys()}
     new = {family: set(keys) for family, keys in own.items()}
     new["small-op"] |= _borrowed_small_op_keys()
     return {family: (old[family], new[family]) for family in old}
@@ -231,17 +233,18 @@ def _tested():
 @pytest.mark.parametrize("program", PROGRAMS, ids=[p[1] for p in PROGRAMS])
 def test_mt_btsunet_programs_launch_only_reference_tested_instances(program):
     """Every coverage key of the Multi_BTSUNet step program -- kernel instances AND the branches the arguments select, as
-    tests/step_programs.py keys them -- is the key of a call that an element-wise reference test makes: the tables of tests/test_ops_gpu.py,
-    the rows of this module, and for the up-sampling and the wide Linear the cases of tests/test_mt_btsunet_ops_gpu.py."""
+    tests/step_programs.py keys them -- is the key of a call that an element-wise reference test makes: the tables of tests/test_ops_gpu.py
+    and tests/test_loss_launches_gpu.py, the rows of this module, and for the up-sampling and the wide Linear the cases of tests/test_mt_btsunet_ops_gpu.py."""
     import step_programs as SP
     s, tested, own, missing = _survey(program), _tested(), _own_keys(), []
     for family in SP.COLLECTORS:
         seen, (old, new) = s.seen[family], tested[family]
         assert seen, f"{program}: no {family} launch found"
-        print(f"{program} {family}: {len(seen)} keys, {sum(k in old for k in seen)} tested by tests/test_ops_gpu.py's tables, "
+        table = "tests/test_loss_launches_gpu.py" if family == "loss" else "tests/test_ops_gpu.py"
+        print(f"{program} {family}: {len(seen)} keys, {sum(k in old for k in seen)} tested by {table}'s tables, "
               f"{sum(k in new and k not in old for k in seen)} by the rows added for this model, {sum(k not in old and k not in new for k in seen)} missing")
         for key, (kind, where) in sorted(seen.items(), key=repr):
-            by = "tests/test_ops_gpu.py" if key in old else "MISSING" if key not in new else \
+            by = table if key in old else "MISSING" if key not in new else \
                 f"row {own[family][key][0]}" if key in own[family] else "tests/test_mt_btsunet_ops_gpu.py"
             print(f"  {kind} {key} at {where}  <- {by}")
             if by == "MISSING":

@@ -3236,6 +3236,8 @@ _CONV3_GUARD = (_THIS, "test_step_programs_launch_only_reference_tested_conv3x3_
 _INORM_GUARD = (_THIS, "test_step_programs_launch_only_reference_tested_instnorm_instances")
 _CONVT_GUARD = (_THIS, "test_step_programs_launch_only_reference_tested_convT_instances")
 _STREAMS = (_THIS, "test_program_run_on_two_streams_orders_a_forked_section")
+# (the loss mix has ONE key; the guard's key set names test_loss_mix_is_the_written_fp32_expression_and_flags_nan above as the test that makes it)
+_LOSS_GUARD = ("tests/test_loss_launches_gpu.py", "test_step_programs_launch_only_reference_tested_loss_instances")
 # op kind -> (file, test): the reference test, or the guard that ties every launch of the kind to a reference case
 OP_KIND_COVERED_BY = {
     "OP_CONV3_FWD": _CONV3_GUARD, "OP_CONV3_DGRAD": _CONV3_GUARD, "OP_CONV3_WGRAD": _CONV3_GUARD,
@@ -3246,9 +3248,7 @@ OP_KIND_COVERED_BY = {
     "OP_POOL_FWD": _SMALL_GUARD, "OP_POOL_BWD": _SMALL_GUARD, "OP_CONV1_FWD": _SMALL_GUARD, "OP_CONV1_DGRAD": _SMALL_GUARD, "OP_CONV1_WGRAD": _SMALL_GUARD,
     "OP_GAP_FWD": _SMALL_GUARD, "OP_GAP_BWD": _SMALL_GUARD, "OP_LINEAR_FWD": _SMALL_GUARD, "OP_LINEAR_BWD": _SMALL_GUARD,
     "OP_HEAD_COMBINE": _SMALL_GUARD, "OP_HEAD_EXPAND": _SMALL_GUARD,
-    "OP_DICE_FWD": (_THIS, "test_dice_multihead_matches_oracle"), "OP_DICE_BWD": (_THIS, "test_dice_multihead_matches_oracle"),
-    "OP_FOCAL": (_THIS, "test_focal_matches_reference_goldens"),
-    "OP_LOSS_MIX": (_THIS, "test_loss_mix_is_the_written_fp32_expression_and_flags_nan"),
+    "OP_DICE_FWD": _LOSS_GUARD, "OP_DICE_BWD": _LOSS_GUARD, "OP_FOCAL": _LOSS_GUARD, "OP_LOSS_MIX": _LOSS_GUARD, "OP_SOFTMAX": _LOSS_GUARD,
     "OP_OPTIM": ("tests/test_fused_optim_gpu.py", "test_kernel_is_the_host_function_bit_for_bit"), "OP_DICE_COUNTS": (_THIS, "test_dice_counts_exact"),
     "OP_MEMSET": (_THIS, "test_memset_op_zeroes_exactly_its_bytes"),
     "OP_SET_STREAM": _STREAMS, "OP_EVENT_RECORD": _STREAMS, "OP_EVENT_WAIT": _STREAMS,

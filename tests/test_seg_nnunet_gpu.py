@@ -342,7 +342,7 @@ def _keys_outside(seg, allowed):
     return extra
 
 
-_NAMED = ("conv3x3", "InstanceNorm", "transposed-convolution", "small-op")      # the families whose keys carry a kernel-name string
+_NAMED = ("conv3x3", "InstanceNorm", "transposed-convolution", "small-op", "loss")      # the families whose keys carry a kernel-name string
 
 
 def _kernel_instances(survey):
@@ -380,10 +380,11 @@ def test_seg_only_programs_launch_only_reference_tested_instances():
     """No untested launch enters: every coverage key of the segmentation-only step programs at the benchmark shape -- kernel instances AND
     the branches the arguments select, as tests/step_programs.py keys them -- is the key of a call that an element-wise reference test of
     tests/test_ops_gpu.py makes, the sets its own guards hold the MTnnUNet and U-Net++ programs to."""
+    import test_loss_launches_gpu as LOSS
     import test_ops_gpu as OPS
     _, seg = _surveys()
     tested = {"conv3x3": OPS._reference_tested_conv3x3_keys(), "InstanceNorm": OPS._reference_tested_instnorm_keys(),
               "transposed-convolution": OPS._reference_tested_convT_keys(), "small-op": OPS._reference_tested_small_op_keys(),
-              "layout": OPS._reference_tested_layout_keys()}
+              "layout": OPS._reference_tested_layout_keys(), "loss": LOSS._reference_tested_loss_keys()}
     extra = _keys_outside(seg, tested)
     assert not extra, "launches of the segmentation-only programs that no reference case makes:" + "".join(extra)

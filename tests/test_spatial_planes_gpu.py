@@ -416,7 +416,8 @@ def test_16bit_seven_channel_model_against_the_emulation(arch, dtype, size, N):
 
 
 # ---- the programs of a model with at most 5 channels are what they were: tests/golden/step_programs_5ch.json is the listing of the commit
-# before this feature (op kinds per program, coverage keys per family as tests/step_programs.py spells them)
+# before this feature (op kinds per program, coverage keys per family as tests/step_programs.py spells them; the keys of the "loss" family
+# were added to it with that family, from the same four loss ops its "kinds" already listed)
 FIVE = [(arch, dtype) for arch in ("MTUNetPlusPlus", "MTnnUNet") for dtype in ("f32", "bf16", "f16")]
 
 
@@ -484,6 +485,11 @@ def _ops_gpu():
     return OPS
 
 
+def _loss_gpu():
+    import test_loss_launches_gpu as LOSS
+    return LOSS
+
+
 @pytest.mark.parametrize("case", CONV3_CASES, ids=lambda c: _ops_gpu()._conv3_case_id(c))
 def test_seven_channel_conv3x3_launches_match_fp64(case):
     _ops_gpu().test_conv3x3_step_instances_match_fp64(case)
@@ -515,19 +521,21 @@ def _older_keys():
     OPS = _ops_gpu()
     return {"conv3x3": OPS._reference_tested_conv3x3_keys(), "InstanceNorm": OPS._reference_tested_instnorm_keys(),
             "transposed-convolution": OPS._reference_tested_convT_keys(), "small-op": OPS._reference_tested_small_op_keys(),
-            "layout": OPS._reference_tested_layout_keys()}
+            "layout": OPS._reference_tested_layout_keys(), "loss": _loss_gpu()._reference_tested_loss_keys()}
 
 
 @pytest.mark.parametrize("program", PROGRAMS7, ids=["-".join(map(str, p)) for p in PROGRAMS7])
 def test_seven_channel_programs_launch_only_reference_tested_instances(program):
     """Every coverage key of the 7-channel step program -- kernel instances AND the branches the arguments select, as tests/step_programs.py
-    keys them -- is the key of a call that an element-wise reference test makes: the tables of tests/test_ops_gpu.py or the rows above."""
+    keys them -- is the key of a call that an element-wise reference test makes: the tables of tests/test_ops_gpu.py and
+    tests/test_loss_launches_gpu.py or the rows above."""
     s, old, own, missing = _survey7(program), _older_keys(), _own_keys(), []
     assert any(where[1] == 7 for (kind, where) in s.seen["conv3x3"].values()), "no 7-channel conv in the program"
     for family in SP.COLLECTORS:
         seen = s.seen[family]
         assert seen, f"{program}: no {family} launch found"
-        print(f"{program} {family}: {len(seen)} keys, {sum(k in old[family] for k in seen)} tested by tests/test_ops_gpu.py's tables, "
+        print(f"{program} {family}: {len(seen)} keys, {sum(k in old[family] for k in seen)} tested by the tables of "
+              f"{'tests/test_loss_launches_gpu.py' if family == 'loss' else 'tests/test_ops_gpu.py'}, "
               f"{sum(k in own[family] and k not in old[family] for k in seen)} by the rows of this module")
         for key, (kind, where) in sorted(seen.items(), key=repr):
             if key not in old[family] and key not in own[family]:

@@ -1,5 +1,5 @@
 """tests/step_programs.py -- the survey of a step program and the compare-and-report behind the launch-coverage guards of tests/test_ops_gpu.py --
-on hand-made programs: the walks that carry state (the ConvT pair, the run of layout ops), the conv3x3 key flag by flag, the session cache and
+on hand-made programs: the walks that carry state (the ConvT pair, the run of layout ops), the conv3x3, up-sampling and loss keys flag by flag, the session cache and
 the failure messages.  mtbc_conv3x3_kernel_name, mtbc_convT_kernel_name and mtbc_op_kernel_name are host-only; no device, no step is built."""
 import types
 
@@ -230,6 +230,142 @@ def test_up2_ops_are_surveyed_with_their_shape():
     fwd, bwd = ops.upsample2_case_args(UF_, *_UP, compute=1, strides=dict(y=18432)), ops.upsample2_case_args(UB_, *_UP, acc_dx=True)
     s = _survey("up2", {"fwd": [fwd], "bwd": [bwd, bwd]})
     assert s.seen[SMALL] == {(UF_, ("upsample2_c8_fwd_kernel", ("y_strided",))): (UF_, _UP), (UB_, ("upsample2_bwd_kernel", ("acc_dx",))): (UB_, _UP)}
+
+
+# ---- the loss key: the launch string + the branches the arguments select (ops of the structs' fillers, dummy pointers)
+DF_, DB_, FO_ = L.OP_DICE_FWD, L.OP_DICE_BWD, L.OP_FOCAL
+_DICE = (4, 2, 1, 16, 16)          # n_heads, N, C, H, W
+
+
+def _dice(kind, shape=_DICE, **kw):
+    return SP._loss_key(ops.dice_case_args(kind, *shape, **kw))
+
+
+def _focal(shape=(8, 3), **kw):
+    return SP._loss_key(ops.focal_case_args(*shape, **kw))
+
+
+def _softmax(N, Cc, backward):
+    op = _mk(L.OP_SOFTMAX)
+    ops.softmax_args(N, Cc, backward, x=1 << 20, p=2 << 20, dp=3 << 20, dz=4 << 20, into=op.u.softmax)
+    return op
+
+
+def _mix():
+    op = _mk(L.OP_LOSS_MIX)
+    op.u.mix.seg, op.u.mix.cls, op.u.mix.alpha, op.u.mix.out4 = 1 << 20, 2 << 20, 0.5, 3 << 20
+    return op
+
+
+def test_loss_key_is_the_launch_string_and_the_argument_flags():
+    assert _dice(DF_) == ("dice_stats_kernel<0> [threads=256 paths=vvvv rounds=0 rest part] + dice_finalize_kernel<0>", ("kind=0", "n_heads=4"))
+    assert _dice(DB_, gscale_dev=True, seg_kind=L.SEG_JACCARD, shape=(1, 2, 3, 16, 16)) == \
+        ("dice_bwd_kernel<3> [paths=v]", ("kind=3", "n_heads=1", "gscale_dev", "C>1"))
+    assert _focal() == ("focal_kernel", ("C=3", "dx", "gamma>=1"))
+    assert _focal((300, 1), gamma=0.0, weight=True, gscale_dev=True) == ("focal_kernel [N>256]", ("C=1", "weight", "dx", "gscale_dev", "gamma=0"))
+    assert SP._loss_key(_softmax(5, 3, False)) == ("softmax_rows_kernel", ("fwd", "C=3"))
+    assert SP._loss_key(_softmax(70, 2, True)) == ("softmax_rows_kernel [N>64]", ("bwd", "C=2"))
+    assert SP._loss_key(_mix()) == ("loss_mix_kernel", ())
+
+
+@pytest.mark.parametrize("make,flag,without,with_", [
+    (lambda **kw: _dice(DB_, **kw), "gscale_dev", dict(), dict(gscale_dev=True)),
+    (lambda **kw: _dice(DB_, **kw), "kind=2", dict(), dict(seg_kind=L.SEG_FOCALDICE)),
+    (lambda **kw: _dice(DF_, **kw), "kind=1", dict(), dict(seg_kind=L.SEG_BCE)),
+    (lambda **kw: _dice(DF_, **kw), "n_heads=3", dict(), dict(shape=(3, 2, 1, 16, 16))),
+    (lambda **kw: _dice(DF_, **kw), "C>1", dict(), dict(shape=(4, 2, 2, 16, 16))),
+    (lambda **kw: _dice(DB_, **kw), "C>1", dict(), dict(shape=(4, 1, 3, 16, 16))),
+    (lambda **kw: _focal(**kw), "C=1", dict(gamma=0.0), dict(gamma=0.0, shape=(8, 1))),
+    (lambda **kw: _focal(**kw), "weight", dict(), dict(weight=True)),
+    (lambda **kw: _focal(**kw), "dx", dict(dx=False), dict()),
+    (lambda **kw: _focal(**kw), "gscale_dev", dict(), dict(gscale_dev=True)),
+    (lambda **kw: _focal(**kw), "gamma=0", dict(), dict(gamma=0.0)),
+    (lambda **kw: _focal(**kw), "0<gamma<1", dict(), dict(gamma=0.5)),
+    (lambda **kw: _focal(**kw), "gamma>=1", dict(gamma=0.999), dict(gamma=1.0)),
+    (lambda backward=False, Cc=3: SP._loss_key(_softmax(5, Cc, backward)), "bwd", dict(), dict(backward=True)),
+    (lambda backward=False, Cc=3: SP._loss_key(_softmax(5, Cc, backward)), "C=2", dict(), dict(Cc=2)),
+])
+def test_loss_key_flag_follows_the_arguments(make, flag, without, with_):
+    a, b = make(**without), make(**with_)
+    assert flag not in a[1] and flag in b[1] and a != b, (a, b)
+
+
+def test_loss_key_ignores_fields_the_call_does_not_read():
+    """The forward reads neither gscale_dev nor gscale nor dx; focal_gamma is read by the FocalDICE kind alone, and there as a value; smooth
+    and the head weights are values; Focal reads gscale_dev only where it writes a gradient."""
+    fwd = ops.dice_case_args(DF_, *_DICE)
+    want = SP._loss_key(fwd)
+    fwd.u.dice.gscale_dev, fwd.u.dice.gscale = 77 << 20, 3.0
+    fwd.u.dice.dx[0] = (78 << 20) + 4                      # misaligned, even
+    assert SP._loss_key(fwd) == want
+    for kind in (DF_, DB_):
+        for seg_kind in (L.SEG_DICE, L.SEG_BCE, L.SEG_FOCALDICE, L.SEG_JACCARD):
+            op = ops.dice_case_args(kind, *_DICE, seg_kind=seg_kind, gscale_dev=True)
+            want = SP._loss_key(op)
+            op.u.dice.focal_gamma, op.u.dice.smooth_nr, op.u.dice.smooth_dr, op.u.dice.gscale = 0.5, 0.25, 0.125, 7.0
+            op.u.dice.head_weight[2] = 9.0
+            assert SP._loss_key(op) == want, (kind, seg_kind)
+    assert _focal(dx=False, gscale_dev=True) == _focal(dx=False)
+    assert _focal(alpha=0.25, gscale=3.0) == _focal()
+
+
+def test_loss_ops_are_surveyed_with_their_shape():
+    fwd, bwd = ops.dice_case_args(DF_, *_DICE), ops.dice_case_args(DB_, *_DICE, gscale_dev=True)
+    foc, sm = ops.focal_case_args(8, 3, gscale_dev=True), _softmax(8, 3, False)
+    s = _survey("loss", {"fwd": [sm], "loss": [fwd, bwd, foc, _mix()], "bwd": [_softmax(8, 3, True)]})
+    assert s.seen["loss"] == {(DF_, SP._loss_key(fwd)): (DF_, _DICE), (DB_, SP._loss_key(bwd)): (DB_, _DICE), (FO_, SP._loss_key(foc)): (FO_, (8, 3)),
+                              (L.OP_LOSS_MIX, ("loss_mix_kernel", ())): (L.OP_LOSS_MIX, ()),
+                              (L.OP_SOFTMAX, ("softmax_rows_kernel", ("fwd", "C=3"))): (L.OP_SOFTMAX, (8, 3)),
+                              (L.OP_SOFTMAX, ("softmax_rows_kernel", ("bwd", "C=3"))): (L.OP_SOFTMAX, (8, 3))}
+    assert not s.seen[SMALL] and _plain(s.seen)
+    with pytest.raises(AssertionError) as e:
+        SP.assert_all_tested("loss", set(s.seen["loss"]) - {(DB_, SP._loss_key(bwd))}, [s], required=(DF_, DB_, FO_, L.OP_LOSS_MIX))
+    assert "dice_bwd_kernel<0>" in str(e.value) and "gscale_dev" in str(e.value) and str(_DICE) in str(e.value)
+
+
+def test_loss_fillers_fill_what_the_engine_filled_by_hand():
+    """ops.dice_case_args / focal_case_args with into= leave in a program op, byte for byte, what engine.StepPlan.fused_losses and _focal_op
+    wrote field by field before the fillers existed (restated here)."""
+    import ctypes as C
+
+    import torch
+    nh, N, C_, H, W = 4, 2, 1, 16, 16
+    heads, grads = [torch.empty(8) for _ in range(nh)], [torch.empty(8) for _ in range(nh)]
+    mask, stats, loss, gw = (torch.empty(8) for _ in range(4))
+    weights = [1.0 / (nh - i) for i in range(nh)]
+    ptrs = {"x": heads, "dx": grads, "target": mask, "stats": stats, "loss": loss, "gscale_dev": gw}
+    for name, (seg_kind, nr, dr, gamma, _) in L.SEG_CRITERIA.items():
+        for kind in (DF_, DB_):
+            want = _mk(kind)
+            a = want.u.dice
+            a.n_heads, a.N, a.C, a.H, a.W, a.smooth_nr, a.smooth_dr = nh, N, C_, H, W, nr, dr
+            a.kind, a.focal_gamma = seg_kind, gamma
+            for i in range(nh):
+                a.x[i] = heads[i].data_ptr()
+                a.head_weight[i] = weights[i]
+            a.target, a.stats, a.loss = mask.data_ptr(), stats.data_ptr(), loss.data_ptr()
+            if kind == DB_:
+                for i in range(nh):
+                    a.dx[i] = grads[i].data_ptr()
+                a.gscale_dev = gw.data_ptr()
+                a.gscale = 0.5 * 65536.0
+            got = _mk(kind)
+            ops.dice_case_args(kind, nh, N, C_, H, W, ptrs=ptrs, seg_kind=seg_kind, weights=weights, smooth=(nr, dr), focal_gamma=gamma,
+                               gscale=0.5 * 65536.0, gscale_dev=True, into=got.u.dice)
+            assert bytes(got) == bytes(want), (name, kind)
+    x, onehot, fl, dx = (torch.empty(8) for _ in range(4))
+    for Cc, gamma, fw in ((3, 2.0, None), (3, 0.0, None), (3, 2.0, torch.empty(3)), (1, 0.0, None)):
+        want = _mk(FO_)
+        a = want.u.focal
+        a.N, a.C, a.alpha, a.gamma = N, Cc, 1.0, gamma
+        a.x, a.target, a.weight = x.data_ptr(), onehot.data_ptr(), None if fw is None else fw.data_ptr()
+        a.loss, a.dx, a.gscale = fl.data_ptr(), dx.data_ptr(), 0.65
+        a.gscale_dev = gw.data_ptr()
+        got = _mk(FO_)
+        ops.focal_case_args(N, Cc, ptrs={"x": x, "target": onehot, "weight": fw, "loss": fl, "dx": dx, "gscale_dev": gw}, alpha=1.0, gamma=gamma,
+                            weight=fw is not None, gscale=0.65, gscale_dev=True, into=got.u.focal)
+        assert bytes(got) == bytes(want), (Cc, gamma, fw is not None)
+    assert C.sizeof(L.Op) == len(bytes(got))
 
 
 # ---- what a survey keeps, and for how long
