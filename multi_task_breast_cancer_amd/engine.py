@@ -16,7 +16,7 @@ import torch
 
 from . import _lib as L
 from . import ops as _ops
-
+from .ops import _small_op as _mk       # a zeroed op of a kind (+ tag)
 
 from . import switches as _sw
 
@@ -151,13 +151,6 @@ class Program:
         if rc != 0:
             i = self._failed.value
             L.check(rc, f"program op #{i} (kind {self.array[i].kind}, tag {self.array[i].tag})")
-
-
-def _mk(kind: int, tag: int = 0) -> L.Op:
-    op = L.Op()
-    op.kind = kind
-    op.tag = tag
-    return op
 
 
 class StepPlan:
@@ -734,6 +727,8 @@ class StepPlan:
             a.w_packed = _ptr(cell.wp_d)
             self.bwd_ops.append(op)
 
+    # ---- the small layers: each method decides (layout, fold, 16-bit operands, accumulate flags, allocation order) and has its ops filled by
+    # the fillers of ops.py (workspace=False: the workspace is the shared one, _need_ws / finalize) -- the fillers the reference cases use
     def _c8_small_ok(self, x: Act) -> bool:
         """16-bit modes: may a small consumer (max-pool, 1x1 head) read the channel-blocked copy of x instead of fp32 planes?"""
         return bool(self.compute) and not self.force_direct and x.C % 8 == 0 and (x.H * x.W) % 4 == 0
@@ -774,19 +769,9 @@ class StepPlan:
             # slab -- no 4x larger, three-quarters-zero fp32 tensor written, read-modify-written by the fan-in and read back
             fold = x.z16 and x.needs_grad
         arg = self.alloc(x.N, x.C // 8, y.H * y.W, dtype=torch.int16) if fold else None
-
-        def base() -> L.Op:
-            op = _mk(0)
-            a = op.u.pool
-            a.N, a.C, a.H, a.W = x.N, x.C, x.H, x.W
-            if c8:
-                a.layout, a.type16 = L.LAYOUT_C8, self.compute
-                a.x, a.x_batch_stride = x8.data_ptr(), x.bstride
-                a.y, a.y_batch_stride = y.c8.data_ptr(), y.bstride
-            else:
-                a.x, a.x_batch_stride = self._rd(x), x.bstride
-                a.y, a.y_batch_stride = y.data.data_ptr(), y.bstride
-            return op
+        shape = (x.N, x.C, x.H, x.W)
+        mode = dict(compute=self.compute if c8 else 0, strides=dict(x=x.bstride, y=y.bstride, dy=y.bstride, dx=x.bstride))
+        ptrs = dict(x=x8, y=y.c8, argmax=arg) if c8 else dict(x=x.data, y=y.data)
 
         if c8 and x.in_op is not None and x.in_op.u.inorm.stats_slots > 0 and not x.in_op.u.inorm.pool_y8:
             # x's InstanceNorm forward is the streaming pass: it writes the pooled tensor (and the argmax codes) while it has the window
@@ -794,11 +779,9 @@ class StepPlan:
             x.in_op.u.inorm.pool_y8 = y.c8.data_ptr()
             x.in_op.u.inorm.pool_arg = arg.data_ptr() if fold else None
         else:
-            op = base()
-            op.kind = L.OP_POOL_FWD
-            if fold:
-                op.u.pool.argmax = arg.data_ptr()
-            self.fwd_ops.append(op)
+            if not c8:
+                self._rd(x)
+            self.fwd_ops.append(_ops.maxpool_case_args(L.OP_POOL_FWD, *shape, ptrs=ptrs, argmax=fold, **mode))
 
         def emit_bwd() -> None:
             if not y.grad_written or not x.needs_grad:
@@ -807,13 +790,11 @@ class StepPlan:
                 assert x.pool is None, f"{x.name}: a second max-pool backward folded into one InstanceNorm backward"
                 x.pool = (self.grad_of(y), arg)
                 return
-            op = base()
-            op.kind = L.OP_POOL_BWD
-            a = op.u.pool
-            a.dy, a.dy_batch_stride = self.grad_of(y).data_ptr(), y.bstride
+            if not c8:
+                self._rd(x)
+            dy = self.grad_of(y)
             gx, acc = self.grad_slot(x)
-            a.dx, a.dx_batch_stride, a.accumulate_dx = gx.data_ptr(), x.bstride, acc
-            self.bwd_ops.append(op)
+            self.bwd_ops.append(_ops.maxpool_case_args(L.OP_POOL_BWD, *shape, ptrs=dict(ptrs, dy=dy, dx=gx), acc_dx=bool(acc), **mode))
 
         self.bwd_emitters.append(emit_bwd)
         return y
@@ -857,38 +838,31 @@ class StepPlan:
         x.readers += 1
         y = self.new_act(out_name, cout, x.H * k, x.W * k)
 
-        def base(reads_x: bool = True) -> L.Op:
-            op = _mk(0)
-            a = op.u.convT
-            a.N, a.H, a.W, a.Cin, a.Cout, a.k = self.N, x.H, x.W, x.C, cout, k
-            a.x, a.x_batch_stride = (self._rd(x) if reads_x else x.data.data_ptr()), x.bstride
-            a.w = w.data_ptr()
-            a.bias = _ptr(self.pv(bname)) if bname else None
-            a.y, a.y_batch_stride = y.data.data_ptr(), y.bstride
-            return op
-
-        op = base(reads_x=False)
-        op.kind = L.OP_CONVT_FWD
+        shape = (self.N, x.C, cout, x.H, x.W, k)
+        strides = dict(x=x.bstride, y=y.bstride, dy=y.bstride, dx=x.bstride)
+        planar = dict(x=x.data, w=w, bias=self.pv(bname) if bname else None, y=y.data)      # what the gradient ops carry, whatever the forward reads
+        ptrs, mode = planar, dict(strides=strides)
         if self.compute and cout % 8 == 0:
             # 16-bit modes: the up-sampled tensor feeds 3x3 convs only -- write it straight into their channel-blocked
             # 16-bit layout; y.data then stays unwritten.  First choice: the 16-bit MFMA forward that also READS the
             # channel-blocked copy of x (the same one the 3x3 convs read); else the fp32-MFMA forward on fp32 x (same
             # arithmetic as planar forward + pack); else planar output + pack.
-            a = op.u.convT
             y.c8 = self.alloc(self.N, cout // 8, y.H * y.W, 8, dtype=torch.int16)
-            a.y, a.y_batch_stride, a.y_layout, a.y_type = y.c8.data_ptr(), y.bstride, L.LAYOUT_C8, self.compute
-            a.x_layout = L.LAYOUT_C8
-            if k == 2 and x.C % 8 == 0 and self.lib.mtbc_convT_fwd_c8_supported(C.byref(a)):
-                a.x = self.c8_of(x).data_ptr()
+            to_c8, m8 = dict(planar, y=y.c8), dict(mode, compute=self.compute, y_c8=True)
+
+            def takes(**kw) -> bool:
+                return bool(self.lib.mtbc_convT_fwd_c8_supported(C.byref(_ops.convT_case_args(L.OP_CONVT_FWD, *shape, ptrs=to_c8, **m8, **kw))))
+
+            if k == 2 and x.C % 8 == 0 and takes(x_c8=True):
+                ptrs, mode = dict(to_c8, x=self.c8_of(x)), dict(m8, x_c8=True)
+            elif takes():
+                ptrs, mode = to_c8, m8
             else:
-                a.x_layout = L.LAYOUT_PLANAR
-                if not self.lib.mtbc_convT_fwd_c8_supported(C.byref(a)):
-                    y.c8 = None
-                    a.y, a.y_layout, a.y_type = y.data.data_ptr(), L.LAYOUT_PLANAR, 0
+                y.c8 = None
             y.planar_valid = y.c8 is None
-        if op.u.convT.x_layout != L.LAYOUT_C8:
-            op.u.convT.x = self._rd(x)
-        self.fwd_ops.append(op)
+        if not mode.get("x_c8"):
+            self._rd(x)
+        self.fwd_ops.append(_ops.convT_case_op(L.OP_CONVT_FWD, *shape, ptrs=ptrs, **mode))
         # 16-bit modes: the backward MFMAs of the k = 2 up-convolutions take rounded operands too (they are fp32-MFMA
         # bound otherwise); only where BOTH direct-to-fragment kernels of convt2.hip take the shape
         lp = self.compute if (k == 2 and (x.H * x.W) % 32 == 0 and x.W % 8 == 0 and cout % 2 == 0) else 0
@@ -905,29 +879,21 @@ class StepPlan:
             # nothing else wants fp32 planes of x (decided in _narrow_activations, once every reader is known)
             x16 = (g16 and x.in_op is not None and bool(x.in_op.u.inorm.y8) and x.in_op.u.inorm.stats_slots > 0
                    and (x.H * x.W) % 8 == 0 and x.bstride % 8 == 0)
-            op = base(reads_x=not x16)
-            if x16:
-                x.p16_users.append(op)
-            op.kind = L.OP_CONVT_WGRAD
-            a = op.u.convT
-            a.compute = lp
-            a.dy, a.dy_batch_stride, a.dy_type16 = dy.data_ptr(), y.bstride, (lp if g16 else 0)
-            a.accumulate_dw = self._mark_param(wname)
-            a.dw = self.gv(wname).data_ptr()
+            if not x16:
+                self._rd(x)
+            bwd = dict(compute=lp, dy16=g16, strides=strides)
+            acc = self._mark_param(wname)
             if bname:
                 self._mark_param(bname)
-                a.dbias = self.gv(bname).data_ptr()
-            self._need_ws(op, "convT", self.lib.mtbc_convT_wgrad_workspace(C.byref(a)))
+            grads = dict(planar, dy=dy, dw=self.gv(wname), dbias=self.gv(bname) if bname else None)
+            op = _ops.convT_case_op(L.OP_CONVT_WGRAD, *shape, ptrs=grads, acc_dw=bool(acc), workspace=False, **bwd)
+            if x16:             # x / x_type16 of this op: _narrow_activations
+                x.p16_users.append(op)
+            self._need_ws(op, "convT", self.lib.mtbc_convT_wgrad_workspace(C.byref(op.u.convT)))
             self.bwd_ops.append(op)
             if x.needs_grad:
-                op = base(reads_x=False)
-                op.kind = L.OP_CONVT_DGRAD
-                a = op.u.convT
-                a.compute = lp
-                a.dy, a.dy_batch_stride, a.dy_type16 = dy.data_ptr(), y.bstride, (lp if g16 else 0)
                 gx, acc = self.grad_slot(x)
-                a.dx, a.dx_batch_stride, a.accumulate_dx = gx.data_ptr(), x.bstride, acc
-                self.bwd_ops.append(op)
+                self.bwd_ops.append(_ops.convT_case_op(L.OP_CONVT_DGRAD, *shape, ptrs=dict(grads, dx=gx), acc_dx=bool(acc), **bwd))
 
         self.bwd_emitters.append(emit_bwd)
         return y
@@ -945,57 +911,29 @@ class StepPlan:
         G, gb = self.alloc(x.C, R, k, k), self.alloc(R)
         y = self.new_act(out_name, R, x.H * k, x.W * k)
 
-        def head() -> L.Op:
-            op = _mk(0)
-            a = op.u.head
-            a.Cin, a.Cmid, a.R, a.k = x.C, cmid, R, k
-            a.wT, a.bT, a.w1, a.b1 = wT.data_ptr(), _ptr(self.pv(bTname)), w1.data_ptr(), _ptr(self.pv(b1name))
-            a.Wc, a.bc, a.G, a.gb = Wc.data_ptr(), bc.data_ptr(), G.data_ptr(), gb.data_ptr()
-            return op
-
-        def base() -> L.Op:
-            op = _mk(0)
-            a = op.u.convT
-            a.N, a.H, a.W, a.Cin, a.Cout, a.k = self.N, x.H, x.W, x.C, R, k
-            a.x, a.x_batch_stride = self._rd(x), x.bstride
-            a.w, a.bias = Wc.data_ptr(), bc.data_ptr()
-            a.y, a.y_batch_stride = y.data.data_ptr(), y.bstride
-            return op
-
-        op = head()
-        op.kind = L.OP_HEAD_COMBINE
-        self.fwd_ops.append(op)
-        op = base()
-        op.kind = L.OP_CONVT_FWD
-        self.fwd_ops.append(op)
+        names = (wTname, bTname, w1name, b1name)
+        fuse = dict(wT=wT, bT=self.pv(bTname), w1=w1, b1=self.pv(b1name), Wc=Wc, bc=bc, G=G, gb=gb)
+        shape = (self.N, x.C, R, x.H, x.W, k)
+        strides = dict(x=x.bstride, y=y.bstride, dy=y.bstride, dx=x.bstride)
+        ptrs = dict(x=x.data, w=Wc, bias=bc, y=y.data)
+        self._rd(x)
+        self.fwd_ops.append(_ops.head_case_args(L.OP_HEAD_COMBINE, x.C, cmid, R, k, ptrs=fuse))
+        self.fwd_ops.append(_ops.convT_case_op(L.OP_CONVT_FWD, *shape, ptrs=ptrs, strides=strides))
 
         def emit_bwd() -> None:
             if not y.grad_written:
                 return
-            dy = self.grad_of(y)
-            op = base()
-            op.kind = L.OP_CONVT_WGRAD
-            a = op.u.convT
-            a.dy, a.dy_batch_stride = dy.data_ptr(), y.bstride
-            a.dw, a.dbias, a.accumulate_dw = G.data_ptr(), gb.data_ptr(), 0
-            self._need_ws(op, "convT", self.lib.mtbc_convT_wgrad_workspace(C.byref(a)))
+            grads = dict(ptrs, dy=self.grad_of(y), dw=G, dbias=gb)
+            op = _ops.convT_case_op(L.OP_CONVT_WGRAD, *shape, ptrs=grads, strides=strides, workspace=False)
+            self._need_ws(op, "convT", self.lib.mtbc_convT_wgrad_workspace(C.byref(op.u.convT)))
             self.bwd_ops.append(op)
-            op = head()
-            op.kind = L.OP_HEAD_EXPAND
-            a = op.u.head
-            a.acc_wT, a.acc_bT = self._mark_param(wTname), self._mark_param(bTname)
-            a.acc_w1, a.acc_b1 = self._mark_param(w1name), self._mark_param(b1name)
-            a.dwT, a.dbT = self.gv(wTname).data_ptr(), self.gv(bTname).data_ptr()
-            a.dw1, a.db1 = self.gv(w1name).data_ptr(), self.gv(b1name).data_ptr()
-            self.bwd_ops.append(op)
+            acc = [self._mark_param(name) for name in names]
+            dnames = ("dwT", "dbT", "dw1", "db1")
+            self.bwd_ops.append(_ops.head_case_args(L.OP_HEAD_EXPAND, x.C, cmid, R, k, ptrs=dict(fuse, **{d: self.gv(n) for d, n in zip(dnames, names)}),
+                                                    acc=acc))
             if x.needs_grad:
-                op = base()
-                op.kind = L.OP_CONVT_DGRAD
-                a = op.u.convT
-                a.dy, a.dy_batch_stride = dy.data_ptr(), y.bstride
-                gx, acc = self.grad_slot(x)
-                a.dx, a.dx_batch_stride, a.accumulate_dx = gx.data_ptr(), x.bstride, acc
-                self.bwd_ops.append(op)
+                gx, acc_dx = self.grad_slot(x)
+                self.bwd_ops.append(_ops.convT_case_op(L.OP_CONVT_DGRAD, *shape, ptrs=dict(grads, dx=gx), strides=strides, acc_dx=bool(acc_dx)))
 
         self.bwd_emitters.append(emit_bwd)
         return y
@@ -1009,22 +947,12 @@ class StepPlan:
         # 16-bit modes: the head reads the channel-blocked 16-bit activation the 3x3 convs read (fp32 weights, products
         # and sums): x then needs no fp32 planes on the head's account
         c8 = self._c8_small_ok(x) and cout <= 8
-        x8 = self.c8_of(x) if c8 else None
-
-        def base() -> L.Op:
-            op = _mk(0)
-            a = op.u.conv1
-            a.N, a.H, a.W, a.Cin, a.Cout = self.N, x.H, x.W, x.C, cout
-            if c8:
-                a.x, a.x_batch_stride, a.x_layout, a.x_type = x8.data_ptr(), x.bstride, L.LAYOUT_C8, self.compute
-            else:
-                a.x, a.x_batch_stride = self._rd(x), x.bstride
-            a.w, a.bias, a.y = w.data_ptr(), _ptr(self.pv(bname)), y.data.data_ptr()
-            return op
-
-        op = base()
-        op.kind = L.OP_CONV1_FWD
-        self.fwd_ops.append(op)
+        if not c8:
+            self._rd(x)
+        ptrs = dict(x=self.c8_of(x) if c8 else x.data, w=w, bias=self.pv(bname), y=y.data)
+        shape = (self.N, x.C, cout, x.H, x.W)
+        mode = dict(compute=self.compute if c8 else 0, strides=dict(x=x.bstride, dx=x.bstride))
+        self.fwd_ops.append(_ops.conv1x1_case_args(L.OP_CONV1_FWD, *shape, ptrs=ptrs, **mode))
 
         def emit_bwd() -> None:
             if not y.grad_written:
@@ -1040,23 +968,15 @@ class StepPlan:
                 self._mark_param(bname)
                 x.r1 = (dy, w, self.gv(wname), self.gv(bname), acc, (wname, bname))
                 return
-            op = base()
-            op.kind = L.OP_CONV1_WGRAD
-            a = op.u.conv1
-            a.dy = dy.data_ptr()
-            a.accumulate_dw = self._mark_param(wname)
+            acc = self._mark_param(wname)
             self._mark_param(bname)
-            a.dw, a.dbias = self.gv(wname).data_ptr(), self.gv(bname).data_ptr()
-            self._need_ws(op, "conv1", self.lib.mtbc_conv1x1_wgrad_workspace(C.byref(a)))
+            grads = dict(ptrs, dy=dy, dw=self.gv(wname), dbias=self.gv(bname))
+            op = _ops.conv1x1_case_args(L.OP_CONV1_WGRAD, *shape, ptrs=grads, acc_dw=bool(acc), workspace=False, **mode)
+            self._need_ws(op, "conv1", self.lib.mtbc_conv1x1_wgrad_workspace(C.byref(op.u.conv1)))
             self.bwd_ops.append(op)
             if x.needs_grad:
-                op = base()
-                op.kind = L.OP_CONV1_DGRAD
-                a = op.u.conv1
-                a.dy = dy.data_ptr()
                 gx, acc = self.grad_slot(x)
-                a.dx, a.dx_batch_stride, a.accumulate_dx = gx.data_ptr(), x.bstride, acc
-                self.bwd_ops.append(op)
+                self.bwd_ops.append(_ops.conv1x1_case_args(L.OP_CONV1_DGRAD, *shape, ptrs=dict(grads, dx=gx), acc_dx=bool(acc), **mode))
 
         self.bwd_emitters.append(emit_bwd)
         return y
@@ -1066,27 +986,17 @@ class StepPlan:
         x.readers += 1
         y = Act(out_name, self.alloc(self.N, x.C, 1, 1))
 
-        def base() -> L.Op:
-            op = _mk(0)
-            a = op.u.gap
-            a.N, a.C, a.H, a.W = self.N, x.C, x.H, x.W
-            a.x, a.y = self._rd(x), y.data.data_ptr()
-            return op
-
-        op = base()
-        op.kind = L.OP_GAP_FWD
-        self.fwd_ops.append(op)
+        self._rd(x)
+        shape, ptrs = (self.N, x.C, x.H, x.W), dict(x=x.data, y=y.data)
+        self.fwd_ops.append(_ops.gap_case_args(L.OP_GAP_FWD, *shape, ptrs=ptrs))
 
         def emit_bwd() -> None:
             if not y.grad_written:
                 return
             if x.grad_written:
                 raise NotImplementedError("gap backward overwrites dx")
-            op = base()
-            op.kind = L.OP_GAP_BWD
-            op.u.gap.dy, op.u.gap.dx = self.grad_of(y).data_ptr(), self.grad_of(x).data_ptr()
+            self.bwd_ops.append(_ops.gap_case_args(L.OP_GAP_BWD, *shape, ptrs=dict(ptrs, dy=self.grad_of(y), dx=self.grad_of(x))))
             x.grad_written = True
-            self.bwd_ops.append(op)
 
         self.bwd_emitters.append(emit_bwd)
         return y
@@ -1099,38 +1009,30 @@ class StepPlan:
         assert tuple(w.shape) == (out_f, in_f), (wname, tuple(w.shape))
         y = Act(out_name, self.alloc(self.N, out_f, 1, 1))
 
-        def base() -> L.Op:
-            op = _mk(0)
-            a = op.u.linear
-            a.N, a.In, a.Out, a.relu = self.N, in_f, out_f, 1 if relu else 0
-            a.x, a.w, a.bias, a.y = self._rd(x), w.data_ptr(), _ptr(self.pv(bname)), y.data.data_ptr()
-            return op
+        self._rd(x)
+        ptrs = dict(x=x.data, w=w, bias=self.pv(bname), y=y.data)
 
-        op = base()
-        op.kind = L.OP_LINEAR_FWD
-        nb = int(self.lib.mtbc_linear_workspace(C.byref(op.u.linear), 0))      # > 0 only for the batch-shared kernels of a wide input (mtbc.h)
-        if nb:
-            self._need_ws(op, "linear", nb)
-        self.fwd_ops.append(op)
+        def emit(ops: List[L.Op], kind: int, ptrs: dict, **mode) -> None:
+            op = _ops.linear_case_args(kind, self.N, in_f, out_f, ptrs=ptrs, relu=relu, workspace=False, **mode)
+            # forward: > 0 only for the batch-shared kernels of a wide input (mtbc.h); backward: relu = N * Out floats, a wide input = the
+            # split partials of dx behind them
+            nb = int(self.lib.mtbc_linear_workspace(C.byref(op.u.linear), int(kind == L.OP_LINEAR_BWD)))
+            if nb:
+                self._need_ws(op, "linear", nb)
+            ops.append(op)
+
+        emit(self.fwd_ops, L.OP_LINEAR_FWD, ptrs)
 
         def emit_bwd() -> None:
             if not y.grad_written:
                 return
             if x.grad_written:
                 raise NotImplementedError("linear backward overwrites dx")
-            op = base()
-            op.kind = L.OP_LINEAR_BWD
-            a = op.u.linear
-            a.dy = self.grad_of(y).data_ptr()
-            a.dx = self.grad_of(x).data_ptr() if x.needs_grad else None
-            a.accumulate_dw = self._mark_param(wname)
+            grads = dict(ptrs, dy=self.grad_of(y), dx=self.grad_of(x) if x.needs_grad else None)
+            acc = self._mark_param(wname)
             self._mark_param(bname)
-            a.dw, a.dbias = self.gv(wname).data_ptr(), self.gv(bname).data_ptr()
-            nb = int(self.lib.mtbc_linear_workspace(C.byref(a), 1))      # relu: N * Out floats; a wide input: the split partials of dx behind them
-            if nb:
-                self._need_ws(op, "linear", nb)
+            emit(self.bwd_ops, L.OP_LINEAR_BWD, dict(grads, dw=self.gv(wname), dbias=self.gv(bname)), acc_dw=bool(acc))
             x.grad_written = True
-            self.bwd_ops.append(op)
 
         self.bwd_emitters.append(emit_bwd)
         return y

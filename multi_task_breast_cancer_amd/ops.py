@@ -5,7 +5,8 @@ goes through step programs (engine.py).  Device fp32 tensors only; every wrapper
 
 Each argument struct is filled in ONE function, the family's *_case_args builder: with ptrs=None it carries dummy addresses for the host-only
 *_kernel_name queries (the launch-coverage guards of the tests), with ptrs= tensors it is what conv3x3_launch / instnorm_launch /
-convT_launch / small_op_launch / loss_op_launch hand the library.  The eager wrappers validate, allocate, call the builder and launch.
+convT_launch / small_op_launch / loss_op_launch hand the library.  The eager wrappers validate, allocate, call the builder and launch; the
+step programs' pool, 1x1, GAP, Linear, ConvT, fused-head, up-sampling and loss ops are filled by the same builders (engine.StepPlan).
 """
 from __future__ import annotations
 
@@ -659,13 +660,14 @@ _CT_DUMMY = _dummies("x", "w", "bias", "y", "dy", "dx", "dw", "dbias", "workspac
 def convT_case_args(op: int, N: int, Cin: int, Cout: int, H: int, W: int, k: int = 2, ptrs: Optional[dict] = None, compute: int = 0,
                     dy16: bool = False, x16: bool = False, x_c8: bool = False, y_c8: bool = False, bias: bool = True,
                     acc_dx: bool = False, acc_dw: bool = False, strides: Optional[dict] = None, workspace: bool = True) -> "L.ConvTArgs":
-    """The argument struct of ONE transposed-convolution call as the step programs fill it (engine.StepPlan.convT / convT_head).
+    """The argument struct of ONE transposed-convolution call, the filler engine.StepPlan.convT / convT_head call (through convT_case_op).
     ptrs: field name (x, w, bias, y, dy, dx, dw, dbias, workspace) -> tensor, C8 or None for NULL; None = distinct 16-byte aligned dummies that nothing may
     dereference (for convT_kernel_name), the same address for the same field of every call so that a WGRAD and the DGRAD behind it
     describe one problem.  Forward: x_c8 / y_c8 = 16-bit channel-blocked input / output of type `compute`; bias = with a bias.
     Backward: `compute` = the MFMA operand type, dy16 / x16 = dy / x as 16-bit planes of that type, bias = with dbias (weight gradient),
     acc_dx / acc_dw = accumulate.  strides: field name (x, y, dy, dx) -> batch stride in elements of that tensor where the tensor is a
-    channel-range view of a wider buffer; dense otherwise.  workspace = False leaves the weight gradient without one."""
+    channel-range view of a wider buffer; dense otherwise.  workspace = False leaves the weight gradient without one.  Carried where
+    ptrs names them, though the call reads neither: bias and y by both gradients, x by the DGRAD."""
     strides, ptr = strides or {}, _ptr(ptrs, _CT_DUMMY.__getitem__)
     a = L.ConvTArgs()
     a.N, a.H, a.W, a.Cin, a.Cout, a.k = N, H, W, Cin, Cout, k
@@ -681,7 +683,9 @@ def convT_case_args(op: int, N: int, Cin: int, Cout: int, H: int, W: int, k: int
         return a
     a.compute = compute
     a.dy, a.dy_batch_stride, a.dy_type16 = ptr("dy"), strides.get("dy", Cout * H * k * W * k), (compute if dy16 else 0)
+    _carry(a, ptrs, "bias", "y")
     if op == L.OP_CONVT_DGRAD:
+        _carry(a, ptrs, "x")
         a.dx, a.dx_batch_stride, a.accumulate_dx = ptr("dx"), strides.get("dx", Cin * H * W), int(acc_dx)
         return a
     a.x, a.x_type16 = ptr("x"), (compute if x16 else 0)
@@ -690,6 +694,13 @@ def convT_case_args(op: int, N: int, Cin: int, Cout: int, H: int, W: int, k: int
         nb = int(L.load().mtbc_convT_wgrad_workspace(C.byref(a)))
         a.workspace, a.workspace_bytes = ptr("workspace"), (nb if ptrs is None else ptrs["workspace"].numel() * 4)
     return a
+
+
+def convT_case_op(op: int, *shape, **mode) -> "L.Op":
+    """convT_case_args(op, *shape, **mode) as the step-program op of that kind, which is what the fillers of the small ops return."""
+    o = _small_op(op)
+    o.u.convT = convT_case_args(op, *shape, **mode)
+    return o
 
 
 def convT_case_kernel(op: int, *shape, pair: bool = False, **mode) -> str:
@@ -799,7 +810,7 @@ _SEG_DEFAULTS = {kind: (nr, dr, gamma) for kind, nr, dr, gamma, _ in L.SEG_CRITE
 def dice_case_args(kind_op: int, n_heads: int, N: int, Cc: int, H: int, W: int, ptrs: Optional[dict] = None, seg_kind: int = L.SEG_DICE,
                    weights: Optional[Sequence[float]] = None, smooth: Optional[Tuple[float, float]] = None, focal_gamma: Optional[float] = None,
                    gscale: float = 1.0, gscale_dev: bool = False, into: Optional["L.DiceArgs"] = None):
-    """The MTBC_OP_DICE_FWD / _BWD op of ONE segmentation-criterion call as engine.StepPlan.fused_losses fills it, and the only place that
+    """The MTBC_OP_DICE_FWD / _BWD op of ONE segmentation-criterion call, the filler engine.StepPlan.fused_losses calls and the only place that
     fills a mtbc_dice_args.  ptrs: x and dx -> a list of n_heads tensors, target, stats, loss, gscale_dev -> a tensor; None = distinct 16-byte
     aligned dummies that nothing may dereference (for op_kernel_name).  seg_kind: L.SEG_*; weights: the heads' weights (default 1);
     smooth = (nr, dr) and focal_gamma default to the criterion's of L.SEG_CRITERIA (focal_gamma is 0 outside FocalDICE whatever is passed).
@@ -836,7 +847,7 @@ def dice_case_args(kind_op: int, n_heads: int, N: int, Cc: int, H: int, W: int, 
 
 def focal_case_args(N: int, Cc: int, ptrs: Optional[dict] = None, alpha: float = 1.0, gamma: float = 2.0, weight: bool = False, dx: bool = True,
                     gscale: float = 1.0, gscale_dev: bool = False, into: Optional["L.FocalArgs"] = None):
-    """The MTBC_OP_FOCAL op of ONE classification-criterion call as engine.StepPlan._focal_op fills it, and the only place that fills a
+    """The MTBC_OP_FOCAL op of ONE classification-criterion call, the filler engine.StepPlan._focal_op calls and the only place that fills a
     mtbc_focal_args.  ptrs: x, target, loss and -- where the flag of the same name is set -- weight, dx, gscale_dev -> a tensor; None = dummies.
     `into`: the struct inside a step-program op, returned instead of a new op."""
     op = None
@@ -1033,15 +1044,24 @@ def _small_ptr(ptrs: Optional[dict]):
     return _ptr(ptrs, _SMALL_DUMMY.__getitem__)
 
 
-def _small_op(kind: int) -> "L.Op":
+def _small_op(kind: int, tag: int = 0) -> "L.Op":
+    """A step-program op of `kind` with an all-zero argument struct (the engine knows it as _mk)."""
     op = L.Op()
-    op.kind = kind
+    op.kind, op.tag = kind, tag
     return op
+
+
+def _carry(a, ptrs: Optional[dict], *names) -> None:
+    """Fields an op does not read but the step programs carry: set where the caller hands the pointer in, NULL where ptrs has no such key
+    (and with the dummies of ptrs = None)."""
+    for name in names:
+        if ptrs is not None and name in ptrs:
+            setattr(a, name, _p(ptrs[name]))
 
 
 def maxpool_case_args(kind: int, N: int, Cc: int, H: int, W: int, ptrs: Optional[dict] = None, compute: int = 0, argmax: bool = False,
                       acc_dx: bool = False, strides: Optional[dict] = None) -> "L.Op":
-    """The MTBC_OP_POOL_FWD / _BWD op of ONE 2x2 max-pool call as engine.StepPlan.maxpool fills it.  ptrs: field name (x, y, dy, dx, argmax) ->
+    """The MTBC_OP_POOL_FWD / _BWD op of ONE 2x2 max-pool call, the filler engine.StepPlan.maxpool calls.  ptrs: field name (x, y, dy, dx, argmax) ->
     tensor; None = distinct 16-byte aligned dummies that nothing may dereference (for op_kernel_name).  compute: 0 = fp32 planar x / y, 1 / 2 =
     16-bit channel-blocked x / y of that type (layout C8; dy / dx stay fp32 planes); argmax: the forward also writes the codes; acc_dx: the
     backward adds into dx.  strides: field name (x, y, dy, dx) -> batch stride in elements of that tensor where it is a channel-range view of a
@@ -1053,7 +1073,7 @@ def maxpool_case_args(kind: int, N: int, Cc: int, H: int, W: int, ptrs: Optional
     if compute:
         a.layout, a.type16 = L.LAYOUT_C8, compute
     a.x, a.x_batch_stride = ptr("x"), strides.get("x", Cc * H * W)
-    a.y, a.y_batch_stride = ptr("y"), strides.get("y", Cc * H * W // 4)      # engine.StepPlan.maxpool's base(): both ops carry x and y
+    a.y, a.y_batch_stride = ptr("y"), strides.get("y", Cc * H * W // 4)      # both ops carry x and y (the backward reads x alone)
     if kind == L.OP_POOL_FWD:
         a.argmax = ptr("argmax") if argmax else None
     else:
@@ -1064,10 +1084,11 @@ def maxpool_case_args(kind: int, N: int, Cc: int, H: int, W: int, ptrs: Optional
 
 def conv1x1_case_args(kind: int, N: int, Cin: int, Cout: int, H: int, W: int, ptrs: Optional[dict] = None, compute: int = 0, bias: bool = True,
                       acc_dx: bool = False, acc_dw: bool = False, strides: Optional[dict] = None, workspace: bool = True) -> "L.Op":
-    """The MTBC_OP_CONV1_FWD / _DGRAD / _WGRAD op of ONE 1x1 convolution call as engine.StepPlan.conv1x1 fills it.  ptrs: field name (x, w,
+    """The MTBC_OP_CONV1_FWD / _DGRAD / _WGRAD op of ONE 1x1 convolution call, the filler engine.StepPlan.conv1x1 calls.  ptrs: field name (x, w,
     bias, y, dy, dx, dw, dbias, workspace) -> tensor, None = dummies.  compute: 0 = fp32 planar x, 1 / 2 = 16-bit channel-blocked x of that
     type.  bias: forward with a bias / weight gradient with dbias; acc_dx / acc_dw: accumulate.  strides: x, dx -> batch stride of a view
-    (y and dy are always dense).  workspace = False leaves the weight gradient without one."""
+    (y and dy are always dense).  workspace = False leaves the weight gradient without one.  Both gradients carry bias and y where ptrs
+    names them, though neither call reads them."""
     strides, ptr = strides or {}, _small_ptr(ptrs)
     op = _small_op(kind)
     a = op.u.conv1
@@ -1079,6 +1100,7 @@ def conv1x1_case_args(kind: int, N: int, Cin: int, Cout: int, H: int, W: int, pt
         a.bias, a.y = (ptr("bias") if bias else None), ptr("y")
         return op
     a.dy = ptr("dy")
+    _carry(a, ptrs, "bias", "y")
     if kind == L.OP_CONV1_DGRAD:
         a.dx, a.dx_batch_stride, a.accumulate_dx = ptr("dx"), strides.get("dx", Cin * H * W), int(acc_dx)
         return op
@@ -1090,12 +1112,12 @@ def conv1x1_case_args(kind: int, N: int, Cin: int, Cout: int, H: int, W: int, pt
 
 
 def gap_case_args(kind: int, N: int, Cc: int, H: int, W: int, ptrs: Optional[dict] = None) -> "L.Op":
-    """The MTBC_OP_GAP_FWD / _BWD op as engine.StepPlan.gap fills it (x, y / dy, dx; all dense)."""
+    """The MTBC_OP_GAP_FWD / _BWD op, the filler engine.StepPlan.gap calls (x, y / dy, dx; all dense)."""
     ptr = _small_ptr(ptrs)
     op = _small_op(kind)
     a = op.u.gap
     a.N, a.C, a.H, a.W = N, Cc, H, W
-    a.x, a.y = ptr("x"), ptr("y")           # engine.StepPlan.gap's base(): both ops carry x and y
+    a.x, a.y = ptr("x"), ptr("y")           # both ops carry x and y (the backward reads neither)
     if kind == L.OP_GAP_BWD:
         a.dy, a.dx = ptr("dy"), ptr("dx")
     return op
@@ -1103,8 +1125,8 @@ def gap_case_args(kind: int, N: int, Cc: int, H: int, W: int, ptrs: Optional[dic
 
 def linear_case_args(kind: int, N: int, In: int, Out: int, ptrs: Optional[dict] = None, relu: bool = False, bias: bool = True, dx: bool = True,
                      acc_dw: bool = False, workspace: bool = True) -> "L.Op":
-    """The MTBC_OP_LINEAR_FWD / _BWD op as engine.StepPlan.linear fills it.  ptrs: x, w, bias, y, dy, dx, dw, dbias, workspace.  bias: the
-    forward's bias (the backward always has dbias, as in the programs); dx = False: no input gradient; workspace: the call gets what
+    """The MTBC_OP_LINEAR_FWD / _BWD op, the filler engine.StepPlan.linear calls.  ptrs: x, w, bias, y, dy, dx, dw, dbias, workspace.  bias: the
+    forward's bias, which the backward carries beside y (it always has dbias, as in the programs); dx = False: no input gradient; workspace: the call gets what
     mtbc_linear_workspace asks for -- N * Out floats for the backward with relu (the engine gives one to the ReLU layers only), the split
     partials of the batch-shared kernels from In = LINEAR_WIDE_MIN_IN on, nothing otherwise.  ptrs without a "workspace" where one is needed:
     one is allocated here, beside ptrs["x"], and kept alive by the op."""
@@ -1136,7 +1158,7 @@ def linear_wide(enabled: bool) -> bool:
 
 def upsample2_case_args(kind: int, N: int, Cc: int, H: int, W: int, ptrs: Optional[dict] = None, compute: int = 0, acc_dx: bool = False,
                         strides: Optional[dict] = None) -> "L.Op":
-    """The MTBC_OP_UPSAMPLE2_FWD / _BWD op of ONE nearest 2x up-sampling call as engine.StepPlan.upsample2 fills it (H, W: the INPUT's).  ptrs:
+    """The MTBC_OP_UPSAMPLE2_FWD / _BWD op of ONE nearest 2x up-sampling call, the filler engine.StepPlan.upsample2 calls (H, W: the INPUT's).  ptrs:
     x, y (forward), dy, dx (backward); None = dummies.  compute: 0 = fp32 planes, 1 / 2 = the forward moves 16-bit channel-blocked tensors of
     that type (dy / dx are fp32 planes always).  strides: field name -> batch stride in elements of that tensor; dense otherwise."""
     strides, ptr = strides or {}, _small_ptr(ptrs)
@@ -1181,7 +1203,7 @@ def upsample2_bwd(dy, dx=None, accumulate=False):
 
 def head_case_args(kind: int, Cin: int, Cmid: int, R: int, k: int, ptrs: Optional[dict] = None, bT: bool = True, b1: bool = True,
                    dbT: bool = True, db1: bool = True, acc: Sequence[int] = (0, 0, 0, 0)) -> "L.Op":
-    """The MTBC_OP_HEAD_COMBINE / _EXPAND op as engine.StepPlan.convT_head fills it (every pointer in both ops).  ptrs: wT, bT, w1, b1, Wc, bc,
+    """The MTBC_OP_HEAD_COMBINE / _EXPAND op, the filler engine.StepPlan.convT_head calls (every pointer in both ops).  ptrs: wT, bT, w1, b1, Wc, bc,
     G, gb, dwT, dbT, dw1, db1.  bT / b1 = False: the layer has no bias; dbT / db1 = False: that gradient is not asked for; acc = (acc_wT,
     acc_bT, acc_w1, acc_b1)."""
     ptr = _small_ptr(ptrs)
