@@ -203,6 +203,35 @@ size_t mtbc_conv3x3_wgrad_sync_bytes(const mtbc_conv3x3_args* a);
  * Launches nothing, never synchronises, never dereferences a tensor pointer; returns the code the real call would return when it
  * refuses the arguments, MTBC_E_BADARG for an unknown op or a buffer shorter than the name. */
 int mtbc_conv3x3_kernel_name(const mtbc_conv3x3_args* a, int32_t op, char* buf, int32_t len);
+/* Host-only plan query of the weight gradient: the numbers mtbc_conv3x3_wgrad hands the kernel that mtbc_conv3x3_kernel_name names -- how
+ * the kernel walks its pixels is decided from N and the map size, which the name does not carry.  Filled on the path that launches (the
+ * same dispatcher called without a stream).  A field the family does not read is 0.
+ *   tile-walking kernels (conv3x3_wgrad_c8_kernel, _mfma_, _lp_, _lp2_): nsplit blocks walk total_tiles = tiles_x * tiles_y * images
+ *     (geo 2: one tile = two images); split s owns tiles [s * tiles_per_split, ...) -- or, tiles_per_split < 0: dealt evenly,
+ *     [s * total_tiles / nsplit, (s + 1) * total_tiles / nsplit);
+ *   conv3x3_wgrad_c8w_kernel: tiles_x strips per image x segs row segments of seg_tiles 4-row steps (tiles_y steps per strip), a ring
+ *     of 6 + 4 * depth rows; coblocks x ciblocks channel blocks of cit 16-channel input tiles;
+ *   conv3x3_wgrad_c8i_kernel: segs image ranges of seg_tiles images; coblocks, ciblocks, cit as above;
+ *   stem / small-Cin kernels: bands row bands per image (nsplit = N * bands);
+ *   direct kernel: split s takes images s, s + nsplit, ...: images_per_split = the most one split takes.
+ * reduce: what sums the nsplit partial rows -- MTBC_WGRAD_REDUCE_NONE (one split stores into dw), _LAUNCH (reduce_kernel = the
+ * splitk_reduce instance, "splitk_reduce<16>"), _FIXUP (inside the kernel: a tree of fix_levels levels of fan-in fix_fanin). */
+typedef struct {
+    int32_t nsplit, total_tiles, tiles_per_split, tiles_x, tiles_y;
+    int32_t coblocks, ciblocks, cit, segs, seg_tiles, depth;
+    int32_t geo;
+    int32_t bands;
+    int32_t images_per_split;
+    int32_t reduce;
+    int32_t fix_levels, fix_fanin;
+    char reduce_kernel[28];
+} mtbc_wgrad_plan;
+#define MTBC_WGRAD_REDUCE_NONE 0
+#define MTBC_WGRAD_REDUCE_LAUNCH 1
+#define MTBC_WGRAD_REDUCE_FIXUP 2
+/* Launches nothing, never dereferences a tensor pointer; returns what mtbc_conv3x3_wgrad would return when it refuses the arguments
+ * (a short workspace included), MTBC_E_BADARG for plan = NULL. */
+int mtbc_conv3x3_wgrad_plan(const mtbc_conv3x3_args* a, mtbc_wgrad_plan* plan);
 int mtbc_conv3x3_fwd(const mtbc_conv3x3_args* a, void* stream);
 int mtbc_conv3x3_dgrad(const mtbc_conv3x3_args* a, void* stream);
 int mtbc_conv3x3_wgrad(const mtbc_conv3x3_args* a, void* stream);

@@ -331,8 +331,17 @@ class WViewDesc(C.Structure):
                 ("ci_cnt", C.c_int32), ("mode", C.c_int32), ("k_off", C.c_int32), ("K", C.c_int32)]
 
 
+class WgradPlan(C.Structure):
+    """mtbc_wgrad_plan (include/mtbc.h): what mtbc_conv3x3_wgrad_plan answers."""
+    _fields_ = [(n, C.c_int32) for n in ("nsplit", "total_tiles", "tiles_per_split", "tiles_x", "tiles_y", "coblocks", "ciblocks", "cit", "segs",
+                                         "seg_tiles", "depth", "geo", "bands", "images_per_split", "reduce", "fix_levels", "fix_fanin")] + \
+               [("reduce_kernel", C.c_char * 28)]
+
+
+WGRAD_REDUCE_NONE, WGRAD_REDUCE_LAUNCH, WGRAD_REDUCE_FIXUP = 0, 1, 2
+
 EXPORTS = [
-    "mtbc_version", "mtbc_strerror", "mtbc_arch",
+    "mtbc_version", "mtbc_strerror", "mtbc_arch", "mtbc_conv3x3_wgrad_plan",
     "mtbc_conv3x3_packed_elems", "mtbc_conv3x3_packed_dgrad_elems", "mtbc_conv3x3_pack_fwd",
     "mtbc_conv3x3_pack_dgrad", "mtbc_conv3x3_packed_lp_elems", "mtbc_conv3x3_pack_lp", "mtbc_conv3x3_pack_many", "mtbc_c8_pack", "mtbc_c8_unpack", "mtbc_c8_pack16", "mtbc_conv3x3_weight_view", "mtbc_conv3x3_weight_view_many", "mtbc_augment_flip_rotate", "mtbc_convT_head_combine", "mtbc_convT_head_expand", "mtbc_conv3x3_wgrad_workspace", "mtbc_conv3x3_wgrad_sync_bytes", "mtbc_conv3x3_stats_slots", "mtbc_conv3x3_kernel_name", "mtbc_conv3x3_fwd", "mtbc_conv3x3_dgrad",
     "mtbc_conv3x3_wgrad", "mtbc_instnorm_fwd_workspace", "mtbc_instnorm_coop_state_bytes", "mtbc_instnorm_coop_error_offset", "mtbc_instnorm_c8_supported", "mtbc_instnorm_bwd_team", "mtbc_instnorm_dparam_many", "mtbc_instnorm_kernel_name", "mtbc_instnorm_lrelu_fwd", "mtbc_instnorm_lrelu_bwd", "mtbc_maxpool2_fwd",
@@ -387,6 +396,8 @@ def load() -> C.CDLL:
     lib.mtbc_conv3x3_stats_slots.argtypes = [C.POINTER(Conv3x3Args)]
     lib.mtbc_conv3x3_kernel_name.restype = C.c_int
     lib.mtbc_conv3x3_kernel_name.argtypes = [C.POINTER(Conv3x3Args), C.c_int32, C.c_char_p, C.c_int32]
+    lib.mtbc_conv3x3_wgrad_plan.restype = C.c_int
+    lib.mtbc_conv3x3_wgrad_plan.argtypes = [C.POINTER(Conv3x3Args), C.POINTER(WgradPlan)]
     lib.mtbc_instnorm_kernel_name.restype = C.c_int
     lib.mtbc_instnorm_kernel_name.argtypes = [C.POINTER(InstNormArgs), C.c_int32, C.c_char_p, C.c_int32]
     lib.mtbc_convT_kernel_name.restype = C.c_int

@@ -4258,7 +4258,9 @@ size_t mtbc_conv3x3_wgrad_sync_bytes(const mtbc_conv3x3_args* a) {
     return (size_t)splitk_fix_plan(w.nsplit, &f) * w.coblocks * w.ciblocks * sizeof(int);
 }
 
-static int conv_wgrad(const mtbc_conv3x3_args* a, hipStream_t st, KernelChoice* query) {
+// query / plan != NULL: validate, fill in the kernel choice / the plan numbers the kernel would receive and return without touching the device
+// (mtbc_conv3x3_kernel_name, mtbc_conv3x3_wgrad_plan)
+static int conv_wgrad(const mtbc_conv3x3_args* a, hipStream_t st, KernelChoice* query, mtbc_wgrad_plan* plan = nullptr) {
     int rc = check_conv(a); if (rc) return rc;
     if (!a->dout || !a->dw) return MTBC_E_BADARG;
     SegTable in;
@@ -4267,6 +4269,29 @@ static int conv_wgrad(const mtbc_conv3x3_args* a, hipStream_t st, KernelChoice* 
     if (!a->workspace || a->workspace_bytes < (w.partial_elems + w.dbias_elems) * sizeof(float)) return MTBC_E_WORKSPACE;
     float* partial = reinterpret_cast<float*>(a->workspace);
     const size_t wel = (size_t)a->Cout * a->Cin * 9;
+    // the reduction launch behind a kernel (rows of wel + elems2 floats) -- or, with q, the name of its instance: one argument list for both
+    auto reduce = [&](size_t elems2, OpChoice* q) {
+        return mtbc_i_splitk_reduce2(partial, a->dw, elems2 ? a->dbias : nullptr, w.nsplit, wel, elems2, a->accumulate_dw, st, q);
+    };
+    // the answer of a query, given where the launch code below starts to read k and w: bands per image (stem, small-Cin kernel), images per
+    // split (direct kernel), the bias floats behind each partial row, the in-kernel reduction's tree
+    auto answer = [&](const KernelChoice& k, int bands, int imgs, size_t elems2, const SplitKFix* fix) {
+        if (query) *query = k;
+        if (!plan) return (int)MTBC_OK;
+        *plan = mtbc_wgrad_plan{};
+        plan->nsplit = w.nsplit; plan->total_tiles = w.total_tiles; plan->tiles_per_split = w.tiles_per_split;
+        plan->tiles_x = w.tiles_x; plan->tiles_y = w.tiles_y; plan->coblocks = w.coblocks; plan->ciblocks = w.ciblocks;
+        plan->cit = w.cit; plan->segs = w.segs; plan->seg_tiles = w.seg_tiles; plan->depth = w.depth; plan->geo = w.geo;
+        plan->bands = bands; plan->images_per_split = imgs;
+        plan->reduce = (k.red & KR_FIXUP) ? MTBC_WGRAD_REDUCE_FIXUP : (k.red & KR_SPLITK) ? MTBC_WGRAD_REDUCE_LAUNCH : MTBC_WGRAD_REDUCE_NONE;
+        if (plan->reduce == MTBC_WGRAD_REDUCE_LAUNCH) {
+            OpChoice oc{};
+            const int r = reduce(elems2, &oc); if (r) return r;
+            snprintf(plan->reduce_kernel, sizeof plan->reduce_kernel, "%s", oc.s);
+        }
+        if (plan->reduce == MTBC_WGRAD_REDUCE_FIXUP) { plan->fix_levels = fix->levels; plan->fix_fanin = fix->G; }
+        return (int)MTBC_OK;
+    };
     if (a->operand_layout == MTBC_LAYOUT_C8 && a->Cin <= MTBC_STEM_MAX_CIN) {
         // the stem: dz channel-blocked 16-bit, the input (the image + up to four intensity channels, one segment) fp32 planar (it has no channel-blocked form)
         if ((a->compute != 1 && a->compute != 2) || a->n_in != 1 || a->Cout % 8 || a->W % 4 || a->dbias || a->in[0].batch_stride % 4 ||
@@ -4276,7 +4301,7 @@ static int conv_wgrad(const mtbc_conv3x3_args* a, hipStream_t st, KernelChoice* 
         const unsigned short* dz8 = reinterpret_cast<const unsigned short*>(a->dout);
         KernelChoice k = a->Cin == 1 ? kchoice(KF_WGRAD_STEM_C8, a->compute == 2) : kchoice(KF_WGRAD_STEM_MC_C8, a->Cin, a->compute == 2);
         k.red = KR_SPLITK;
-        if (query) { *query = k; return MTBC_OK; }
+        if (query || plan) return answer(k, S, 0, 0, nullptr);
         if (k.fam == KF_WGRAD_STEM_MC_C8) {
 #define MTBC_WG_STEM_MC(CIN_)                                                                                                                  \
             do {                                                                                                                               \
@@ -4293,7 +4318,7 @@ static int conv_wgrad(const mtbc_conv3x3_args* a, hipStream_t st, KernelChoice* 
         } else if (k.t[0]) hipLaunchKernelGGL(conv3x3_wgrad_stem_c8_kernel<true>, grid, dim3(256), 0, st, a->in[0].ptr, (long long)a->in[0].batch_stride, dz8, partial, a->N, a->H, a->W, a->Cout, S);
         else hipLaunchKernelGGL(conv3x3_wgrad_stem_c8_kernel<false>, grid, dim3(256), 0, st, a->in[0].ptr, (long long)a->in[0].batch_stride, dz8, partial, a->N, a->H, a->W, a->Cout, S);
         MTBC_CHECK_LAUNCH();
-        return mtbc_i_splitk_reduce(partial, a->dw, w.nsplit, wel, a->accumulate_dw, st);
+        return reduce(0, nullptr);
     }
     if (a->operand_layout == MTBC_LAYOUT_C8) {
         mtbc_seg g{const_cast<float*>(a->dout), (int64_t)a->Cout * a->H * a->W, a->Cout, 0};
@@ -4320,7 +4345,8 @@ static int conv_wgrad(const mtbc_conv3x3_args* a, hipStream_t st, KernelChoice* 
         const bool f16 = a->compute == 2, bias = a->dbias != nullptr;
         KernelChoice k = w.c8i ? kchoice(KF_WGRAD_C8I, f16, w.cot, bias) : w.c8w ? kchoice(KF_WGRAD_C8W, f16, w.cot, bias) : kchoice(KF_WGRAD_C8, f16, w.geo);
         k.red = direct ? 0 : p.fix.ctr ? KR_FIXUP : KR_SPLITK;
-        if (query) { *query = k; return MTBC_OK; }
+        const size_t bias_el = a->dbias ? (size_t)a->Cout : 0;      // one row per split = the weight-gradient partial followed by the bias-gradient partial
+        if (query || plan) return answer(k, 0, 0, bias_el, &p.fix);
 #ifdef MTBC_PROBES
         // MTBC_WG_TS=1: phase timestamps of every block (thread 0) of the 32 x 32 / wide-block weight-gradient kernels, printed after the launch
         static const int wts_env = mtbc_probe_int("MTBC_WG_TS", 0);
@@ -4407,8 +4433,7 @@ static int conv_wgrad(const mtbc_conv3x3_args* a, hipStream_t st, KernelChoice* 
         }
 #endif
         if (!(k.red & KR_SPLITK)) return MTBC_OK;
-        // one row per split = the weight-gradient partial followed by the bias-gradient partial: ONE reduction launch for both
-        return mtbc_i_splitk_reduce2(partial, a->dw, a->dbias, w.nsplit, wel, a->dbias ? (size_t)a->Cout : 0, a->accumulate_dw, st);
+        return reduce(bias_el, nullptr);      // ONE reduction launch for both parts of the rows
     }
     if (a->operand_layout != MTBC_LAYOUT_PLANAR) return MTBC_E_BADARG;
     static const int lowp_env = mtbc_probe_int("MTBC_LOWP", -1);
@@ -4420,7 +4445,7 @@ static int conv_wgrad(const mtbc_conv3x3_args* a, hipStream_t st, KernelChoice* 
     else if (lowp == 1 || lowp == 2) k = kchoice(KF_WGRAD_LP, w.geo, w.cot, lowp == 2);
     else k = kchoice(KF_WGRAD_MFMA, w.geo, w.cot, w.pack24);
     k.red = KR_SPLITK | (a->dbias ? KR_CHANNEL_SUMS : 0);
-    if (query) { *query = k; return MTBC_OK; }
+    if (query || plan) return answer(k, k.fam == KF_WGRAD_SMALLCIN ? w.nsplit / a->N : 0, k.fam == KF_WGRAD_DIRECT ? cdiv(a->N, w.nsplit) : 0, 0, nullptr);
     if (w.mfma) {
         WgP p; p.N = a->N; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout; p.in = in; p.dz = a->dout;
         p.partial = partial; p.tiles_x = w.tiles_x; p.tiles_y = w.tiles_y; p.total_tiles = w.total_tiles;
@@ -4490,7 +4515,7 @@ static int conv_wgrad(const mtbc_conv3x3_args* a, hipStream_t st, KernelChoice* 
             hipLaunchKernelGGL(conv3x3_wgrad_direct_kernel, dim3(a->Cout * a->Cin, w.nsplit), dim3(256), 0, st, p);
         MTBC_CHECK_LAUNCH();
     }
-    rc = mtbc_i_splitk_reduce(partial, a->dw, w.nsplit, wel, a->accumulate_dw, st); if (rc) return rc;
+    rc = reduce(0, nullptr); if (rc) return rc;
     if (k.red & KR_CHANNEL_SUMS) {
         rc = mtbc_i_channel_sums(a->dout, partial + w.partial_elems, a->dbias, a->N, a->Cout, a->H * a->W, a->accumulate_dw, st);
         if (rc) return rc;
@@ -4509,6 +4534,11 @@ int mtbc_conv3x3_kernel_name(const mtbc_conv3x3_args* a, int32_t op, char* buf, 
     else return MTBC_E_BADARG;
     if (rc) return rc;
     return kernel_name(k, buf, len);
+}
+
+int mtbc_conv3x3_wgrad_plan(const mtbc_conv3x3_args* a, mtbc_wgrad_plan* plan) {
+    if (!plan) return MTBC_E_BADARG;
+    return conv_wgrad(a, nullptr, nullptr, plan);
 }
 
 int mtbc_c8_pack(const float* src, int64_t src_batch_stride, void* dst, int32_t N, int32_t C, int32_t HW, int32_t compute, void* stream) {

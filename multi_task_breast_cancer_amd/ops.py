@@ -68,6 +68,14 @@ def conv3x3_kernel_name(a: "L.Conv3x3Args", op: int) -> str:
     return buf.value.decode()
 
 
+def conv3x3_wgrad_plan(a: "L.Conv3x3Args") -> "L.WgradPlan":
+    """The plan numbers mtbc_conv3x3_wgrad would hand its kernel for `a` (splits, tiles per split, row segments, image ranges, bands, the
+    reduction behind it): mtbc_conv3x3_wgrad_plan, host-only (no launch, no device access); raises what the call would."""
+    plan = L.WgradPlan()
+    L.check(L.load().mtbc_conv3x3_wgrad_plan(C.byref(a), C.byref(plan)), "conv3x3_wgrad_plan")
+    return plan
+
+
 _C3_DUMMY = _dummies(*(f"in{i}" for i in range(L.MAX_SEGS)), "w", "w_packed", "bias", "out", "dout", "dw", "dbias", "workspace", "wgrad_sync",
                      "stats_partial", "out_partial", "norm_z", "norm_mean", "norm_rstd", "norm_gamma", "norm_beta")
 

@@ -39,9 +39,8 @@ def _conv3_key(a, op):
     """Coverage key of ONE mtbc_conv3x3_fwd / _dgrad / _wgrad call: the FULL string of mtbc_conv3x3_kernel_name -- the kernel instance and the
     reduction behind a weight gradient: " + splitk_reduce", " + splitk_fixup", " + channel_sums", or nothing (blocks store straight into dw) --
     + the branches the ARGUMENTS select inside those kernels.  The only place that decides what "the same launch" means for the guard below.
-    A field the call does not read does not enter its key (line numbers: csrc/conv3x3.hip).
-    Known blind spot: the split count and the even-dealt split plan of plan_wgrad (tiles_per_split < 0, conv3x3.hip:3969) are host plan
-    details that mtbc_conv3x3_kernel_name does not expose; they are not in the key and are not re-derived here."""
+    A field the call does not read does not enter its key (line numbers: csrc/conv3x3.hip).  How a weight gradient walks its pixels -- what
+    plan_wgrad decides from N and the map size -- is the business of _wgrad_plan_key, a family of its own."""
     L = ops.L
     name = ops.conv3x3_kernel_name(a, op)
     c8 = a.operand_layout == L.LAYOUT_C8
@@ -67,9 +66,9 @@ def _conv3_key(a, op):
         rows, red, every = a.Cin, a.Cout, 16      # (straddle: a boundary of the WRITTEN segments inside a 16-row tile -- one tile writes two segments)
     else:
         # rows = the output channels of dw (Cout), columns = the segmented input (Cin) in blocks of the chunk
-        if a.dbias:                           # (4303 want_bias, 4320 BIAS, 4411 the bias row of the reduction, 4422 channel_sums; 4272: the stem refuses it)
+        if a.dbias:                           # (4328 want_bias, 4345 BIAS, 4436 the bias row of the reduction, 4447 channel_sums; 4297: the stem refuses it)
             f.append("dbias")
-        if a.accumulate_dw:                   # (4296, 4306, 4314, 4411, 4493)
+        if a.accumulate_dw:                   # (4274 the reduction launch, 4331, 4339)
             f.append("acc_dw")
         rows, red, every = a.Cout, a.Cin, chunk
     if a.n_in > 1:
@@ -88,6 +87,97 @@ def _conv3_key(a, op):
         f.append("strided")
     if a.force_direct and not c8:             # (4115, 4169, 4224, plan_wgrad 3980 / 4022: the planar dispatch only)
         f.append("force_direct")
+    return name, tuple(f)
+
+
+_WG_TILE_WALKERS = ("conv3x3_wgrad_c8_kernel", "conv3x3_wgrad_mfma_kernel", "conv3x3_wgrad_lp_kernel", "conv3x3_wgrad_lp2_kernel")
+_WG_BANDED = ("conv3x3_wgrad_stem_c8_kernel", "conv3x3_wgrad_stem_mc_c8_kernel", "conv3x3_wgrad_smallcin_kernel")
+
+
+def _splitk_reduce_phases(nsplit, G):
+    """Which of the three row loops of splitk_reduce_k<G, E> some split lane g runs (reduce.hip:25 eight rows in flight per round, :32 pairs,
+    :33 the odd tail), walked as the kernel walks them."""
+    ph = set()
+    for g in range(G):
+        k = g
+        while k + 7 * G < nsplit:
+            ph.add("x8")
+            k += 8 * G
+        while k + G < nsplit:
+            ph.add("x2")
+            k += 2 * G
+        if k < nsplit:
+            ph.add("x1")
+    return [n for n in ("x8", "x2", "x1") if n in ph]
+
+
+def _wgrad_plan_key(a):
+    """Plan key of ONE mtbc_conv3x3_wgrad call: the FULL string of mtbc_conv3x3_kernel_name + the class of the plan mtbc_conv3x3_wgrad_plan
+    reports -- what plan_wgrad decides from N and the map size, which neither the name nor _conv3_key carries.  The argument flags of
+    _conv3_key are NOT repeated here: the two keys are not multiplied with each other.  The only place that turns plan numbers into classes
+    (line numbers: csrc/conv3x3.hip unless reduce.hip is named); a kernel family it does not know raises.  Covered now: per kernel family how
+    a block walks its share of the pixels (the tile loop's trip count, even or fixed dealing, ragged shares, shares that cross an image
+    boundary; the wide-block kernel's row segments, block mapping and ring; the image-tile kernel's ranges; the bands of the stem and
+    small-Cin kernels; the direct kernel's image stride) and the reduction behind it (the splitk_reduce_k instance with the row loops it
+    runs; the in-kernel tree's depth and a ragged last group)."""
+    name = ops.conv3x3_kernel_name(a, L.OP_CONV3_WGRAD)
+    p = ops.conv3x3_wgrad_plan(a)
+    fam = name.split(" + ")[0].split("<")[0]
+    f = []
+    if fam in _WG_TILE_WALKERS:
+        T, S = p.total_tiles, p.nsplit
+        if p.tiles_per_split < 0:             # (2225 / 2226: split s owns [s T / S, (s + 1) T / S); the fp32 and planar 16-bit kernels only deal fixed: 1535, 1755, 1903)
+            share = [(s * T // S, (s + 1) * T // S) for s in range(S)]
+        else:
+            share = [(s * p.tiles_per_split, min(T, (s + 1) * p.tiles_per_split)) for s in range(S)]
+        assert share[0][0] == 0 and share[-1][1] == T and all(b < e for b, e in share), (name, T, S, p.tiles_per_split)
+        f.append("even" if p.tiles_per_split < 0 else "fixed")
+        longest = max(e - b for b, e in share)            # (the tile loop 2283 / 1536 / 1756 / 1904: one trip, two, or a steady state between first and last)
+        f.append(f"tiles={longest}" if longest < 3 else "tiles>=3")
+        if len({e - b for b, e in share}) > 1:            # (a short last split: `min(p.total_tiles, ...)` 2226; T % S != 0 of the even deal)
+            f.append("ragged")
+        per_image = p.tiles_x * p.tiles_y                 # (2241-2243: tile -> (tx, ty, n); geo 2 of the planar kernels: a tile IS an image pair)
+        if any(b // per_image != (e - 1) // per_image for b, e in share):
+            f.append("crosses")
+        if p.geo == 2 and fam != "conv3x3_wgrad_c8_kernel" and a.N % 2:      # (plan_wgrad 3988 tn = cdiv(N, 2): the last tile holds one image)
+            f.append("odd_N")
+    elif fam == "conv3x3_wgrad_c8w_kernel":
+        f.append("segs=1" if p.segs == 1 else "segs>1")                       # (2463 / 2473: a block walks the whole strip, or rows [seg * seg_tiles, ...))
+        if p.tiles_y % p.seg_tiles:                                           # (2473 nt = min(seg_tiles, tiles_y - ty0))
+            f.append("short_last_seg")
+        if a.N % 8 == 0:                                                      # (2460 the image-major block mapping; 2669 its partial rows)
+            f.append("img8")
+        f.append("steps>=ring" if 4 * p.seg_tiles + 2 > 6 + 4 * p.depth else "steps<ring")      # (2447 RING rows; 2521 / 2606 the slot wraps)
+        if p.ciblocks > 1:                                                    # (2466 cib, 2549 the bias wave of block 0)
+            f.append("ciblocks>1")
+        if ((a.Cin + 15) // 16) % p.cit:                                      # (2467 ncit = min(cit, tiles - cit0): a shorter last input-channel block)
+            f.append("ragged_cit")
+    elif fam == "conv3x3_wgrad_c8i_kernel":
+        f.append(f"images={p.seg_tiles}" if p.seg_tiles < 3 else "images>=3")      # (2805 / 2808: no prefetch, one, or both stages in turn)
+        if a.N % p.seg_tiles:                                                 # (2734 n_end = min(N, ...))
+            f.append("short_last_range")
+        if p.ciblocks > 1:                                                    # (2732 cib)
+            f.append("ciblocks>1")
+    elif fam in _WG_BANDED:
+        assert p.bands in (1, 4, 16), (name, p.bands)                         # (3184 / 3378 / 3480 band = b % S; plan_wgrad 3896, 4023)
+        f.append(f"bands={p.bands}")
+    elif fam == "conv3x3_wgrad_direct_kernel":
+        if p.images_per_split > 1:                                            # (3452 `for (n = split; n < N; n += nsplit)`)
+            f.append("images>1")
+    else:
+        raise AssertionError(f"_wgrad_plan_key does not know the kernel family of {name!r}")
+    if p.reduce == L.WGRAD_REDUCE_LAUNCH:
+        inst = p.reduce_kernel.decode()
+        m = re.fullmatch(r"splitk_reduce<(\d+)(?:, (\d+))?>", inst)
+        assert m, inst
+        f.append(inst + " " + "+".join(_splitk_reduce_phases(p.nsplit, int(m.group(1)))))
+    elif p.reduce == L.WGRAD_REDUCE_FIXUP:
+        f.append(f"fixup levels={p.fix_levels}")                              # (2115 splitk_fix_plan; 2139 the walk up the tree)
+        if p.nsplit % p.fix_fanin:
+            f.append("fixup ragged_group")
+    else:
+        assert p.reduce == L.WGRAD_REDUCE_NONE and p.nsplit == 1, (name, p.reduce, p.nsplit)      # (4331: one split stores into dw)
+        f.append("store")
     return name, tuple(f)
 
 
@@ -307,6 +397,14 @@ def collect_conv3x3(prog, i):
         return 1, op.kind, (op.kind, _conv3_key(a, op.kind)), _fields(a, "N", "Cin", "Cout", "H", "W") + (tuple(a.in_[i].channels for i in range(a.n_in)),)
 
 
+def collect_wgrad_plan(prog, i):
+    """Every OP_CONV3_WGRAD op, keyed by _wgrad_plan_key alone; where as collect_conv3x3's."""
+    op = prog[i]
+    if op.kind == L.OP_CONV3_WGRAD:
+        a = op.u.conv3
+        return 1, op.kind, (op.kind, _wgrad_plan_key(a)), _fields(a, "N", "Cin", "Cout", "H", "W") + (tuple(a.in_[i].channels for i in range(a.n_in)),)
+
+
 def collect_instnorm(prog, i):
     op = prog[i]
     if op.kind in (L.OP_IN_FWD, L.OP_IN_BWD):
@@ -377,11 +475,12 @@ def collect_loss(prog, i):
         return 1, op.kind, (op.kind, _loss_key(op)), _fields(getattr(op.u, field), *_LOSS_SHAPE[field])
 
 
-COLLECTORS = {"conv3x3": collect_conv3x3, "InstanceNorm": collect_instnorm, "transposed-convolution": collect_convT, "small-op": collect_small_op,
+COLLECTORS = {"conv3x3": collect_conv3x3, "conv3x3-wgrad-plan": collect_wgrad_plan, "InstanceNorm": collect_instnorm, "transposed-convolution": collect_convT, "small-op": collect_small_op,
               "layout": collect_layout, "loss": collect_loss}
 
-# program: (arch, dtype, N, size); kinds: {program name: [op kind]}; seen: {family: {key: (kind label, where) of the first op that has it}}
-Survey = collections.namedtuple("Survey", "program reserve_cus kinds seen")
+# program: (arch, dtype, N, size); kinds: {program name: [op kind]}; seen: {family: {key: (kind label, where) of the first op that has it}};
+# launches: {family: {key: [where of every op that has it, in program order]}}
+Survey = collections.namedtuple("Survey", "program reserve_cus kinds seen launches")
 _SURVEYS = {}
 
 
@@ -394,6 +493,7 @@ def survey(program, reserve_cus=0, collectors=COLLECTORS, build=build_step):
         return _SURVEYS[program, reserve_cus]
     st, keep = build(*program, reserve_cus)
     kinds, seen, p, prog = {}, {family: {} for family in collectors}, None, None
+    launches = {family: {} for family in collectors}
     for name, p in st.programs.items():
         prog = [p.array[i] for i in range(getattr(p, "n", 0))]
         kinds[name] = [op.kind for op in prog]
@@ -404,17 +504,19 @@ def survey(program, reserve_cus=0, collectors=COLLECTORS, build=build_step):
                 if hit:
                     used, kind, key, where = hit
                     seen[family].setdefault(key, (kind, where))
+                    launches[family].setdefault(key, []).append(where)
                 i += used if hit else 1
     del st, keep, p, prog
     gc.collect()          # a step and its model refer to each other: their tensors go only with a collection
     torch.cuda.empty_cache()
-    _SURVEYS[program, reserve_cus] = Survey(program, reserve_cus, kinds, seen)
+    _SURVEYS[program, reserve_cus] = Survey(program, reserve_cus, kinds, seen, launches)
     return _SURVEYS[program, reserve_cus]
 
 
-def assert_all_tested(family, tested, surveys, required=()):
+def assert_all_tested(family, tested, surveys, required=(), answers=None):
     """Every key the surveys saw of the family must be in `tested`, and every program must hold a launch of the family and of each kind label
-    in `required`.  A missing key is named with its program, kind label and where."""
+    in `required`.  A missing key is named with its program, kind label and where.  answers: {key: the case table that makes it} -- the
+    listing then names, per key, every launch of the program that has it and the table that answers for them."""
     missing, total = [], set()
     for s in surveys:
         seen, prog = s.seen[family], s.program + ((f"reserve {s.reserve_cus}",) if s.reserve_cus else ())
@@ -422,7 +524,12 @@ def assert_all_tested(family, tested, surveys, required=()):
         absent = set(required) - {kind for kind, _ in seen.values()}
         assert seen and not absent, f"{prog}: no {family} launch found" + (f" of kind {sorted(absent, key=repr)}" if absent else "")
         for key, (kind, where) in sorted(seen.items(), key=repr):
-            print(f"  {kind} {key} at {where}")
+            if answers is None:
+                print(f"  {kind} {key} at {where}")
+            else:
+                print(f"  {kind} {key}  <- {answers.get(key, 'MISSING')}")
+                for w in s.launches[family][key]:
+                    print(f"      at {w}")
             total.add(key)
             if key not in tested:
                 missing.append(f"\n  {prog}: {kind} {key} at {where}")

@@ -40,7 +40,8 @@ def test_ctypes_layout_matches_header(tmp_path):
                "mtbc_maxpool_args": L.MaxPoolArgs, "mtbc_convT_args": L.ConvTArgs, "mtbc_conv1x1_args": L.Conv1x1Args,
                "mtbc_gap_args": L.GapArgs, "mtbc_linear_args": L.LinearArgs, "mtbc_dice_args": L.DiceArgs,
                "mtbc_focal_args": L.FocalArgs, "mtbc_op": L.Op,
-               "mtbc_pack_desc": L.PackDesc, "mtbc_head_fuse_args": L.HeadFuseArgs, "mtbc_wview_desc": L.WViewDesc}
+               "mtbc_pack_desc": L.PackDesc, "mtbc_head_fuse_args": L.HeadFuseArgs, "mtbc_wview_desc": L.WViewDesc,
+               "mtbc_wgrad_plan": L.WgradPlan}
     offs = [("mtbc_conv3x3_args", "workspace_bytes", L.Conv3x3Args.workspace_bytes.offset),
             ("mtbc_conv3x3_args", "w_packed", L.Conv3x3Args.w_packed.offset),
             ("mtbc_instnorm_args", "dgamma", L.InstNormArgs.dgamma.offset),
@@ -52,6 +53,8 @@ def test_ctypes_layout_matches_header(tmp_path):
             ("mtbc_conv3x3_args", "out_accumulate", L.Conv3x3Args.out_accumulate.offset),
             ("mtbc_pack_desc", "kind", L.PackDesc.kind.offset),
             ("mtbc_dice_args", "gscale_dev", L.DiceArgs.gscale_dev.offset),
+            ("mtbc_wgrad_plan", "reduce", L.WgradPlan.reduce.offset),
+            ("mtbc_wgrad_plan", "reduce_kernel", L.WgradPlan.reduce_kernel.offset),
             ("mtbc_op", "u", L.Op.u.offset)]
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){"]
     for name in structs:
@@ -231,6 +234,72 @@ def test_conv3x3_kernel_name_refuses_what_the_call_refuses(lib):
     assert lib.mtbc_conv3x3_kernel_name(C.byref(a), L.OP_CONV3_PACK_FWD, buf, 256) == -2
     assert lib.mtbc_conv3x3_kernel_name(C.byref(a), L.OP_CONV3_FWD, buf, 8) == -2        # shorter than the name
     assert lib.mtbc_conv3x3_kernel_name(None, L.OP_CONV3_FWD, buf, 256) == -2
+
+
+# (N, segs, Cout, H, W, mode) -> the fields of mtbc_wgrad_plan that the kernel family reads, worked out by hand from plan_wgrad
+# (csrc/conv3x3.hip) for one launch of each family; a field not named must be 0 (reduce_kernel: empty)
+_F = dict(compute=1, c8=True, bias=False)
+WGRAD_PLANS = [
+    # 32 x 32 kernel: 2 x 11 tiles x 3 images = 66; 6 x 12 channel blocks -> 1024 / 72 = 14 splits asked (< 16: dealt fixed), 5 tiles each, the last split 1
+    (3, [192, 192], 192, 44, 64, _F, "conv3x3_wgrad_c8_kernel<false, 0> + splitk_reduce",
+     dict(nsplit=14, total_tiles=66, tiles_per_split=5, tiles_x=2, tiles_y=11, coblocks=6, ciblocks=12, reduce=1, reduce_kernel=b"splitk_reduce<4>")),
+    # ... 1024 tiles, 3 x 2 channel blocks -> 170 splits asked: 168 (a multiple of 8), dealt evenly
+    (8, [48], 96, 128, 128, _F, "conv3x3_wgrad_c8_kernel<false, 0> + splitk_reduce",
+     dict(nsplit=168, total_tiles=1024, tiles_per_split=-1, tiles_x=4, tiles_y=32, coblocks=3, ciblocks=2, reduce=1, reduce_kernel=b"splitk_reduce<16>")),
+    # ... the in-kernel reduction: 16 tiles, 36 channel blocks -> 28 splits asked, 16 there are; a tree of 2 levels, fan-in 4
+    (2, [192], 192, 32, 32, dict(compute=1, c8=True, in_kernel_reduce=True), "conv3x3_wgrad_c8_kernel<false, 0> + splitk_fixup",
+     dict(nsplit=16, total_tiles=16, tiles_per_split=1, tiles_x=1, tiles_y=8, coblocks=6, ciblocks=6, reduce=2, fix_levels=2, fix_fanin=4)),
+    # wide-block kernel: 12 strips x 8 images = 96 > the budget of 512 / (2 x 3) = 85 blocks: ONE segment of all 5 steps per strip
+    (8, [192], 96, 20, 384, _F, "conv3x3_wgrad_c8w_kernel<false, 3, false> + splitk_reduce",
+     dict(nsplit=96, total_tiles=96, tiles_per_split=1, tiles_x=12, tiles_y=5, coblocks=2, ciblocks=3, cit=4, segs=1, seg_tiles=5, depth=1, reduce=1,
+          reduce_kernel=b"splitk_reduce<16>")),
+    # image-tile kernel: 8 x 5 channel blocks -> 256 / 40 = 6 ranges of 3 images, the last one 1
+    (16, [384], 384, 16, 16, _F, "conv3x3_wgrad_c8i_kernel<false, 3, false> + splitk_reduce",
+     dict(nsplit=6, total_tiles=16, tiles_per_split=3, coblocks=8, ciblocks=5, cit=5, segs=6, seg_tiles=3, geo=1, reduce=1, reduce_kernel=b"splitk_reduce<4>")),
+    # ... 16 x 15 channel blocks fill the chip: ONE range of all 12 images, stored straight into dw
+    (12, [384, 384, 384], 512, 16, 16, _F, "conv3x3_wgrad_c8i_kernel<false, 2, false>",
+     dict(nsplit=1, total_tiles=12, tiles_per_split=12, coblocks=16, ciblocks=15, cit=5, segs=1, seg_tiles=12, geo=1, reduce=0)),
+    # the stem: 16 bands per 256 x 256 image
+    (2, [1], 24, 256, 256, _F, "conv3x3_wgrad_stem_c8_kernel<false> + splitk_reduce", dict(nsplit=32, bands=16, reduce=1, reduce_kernel=b"splitk_reduce<4>")),
+    # fp32 MFMA kernel: 2 x 16 tiles x 8 images = 256; 48-channel output blocks, 3 input blocks -> 512 / 3 = 170 splits asked: 2 tiles each, 128 splits
+    (8, [96], 48, 64, 64, dict(), "conv3x3_wgrad_mfma_kernel<0, 3, false> + splitk_reduce + channel_sums",
+     dict(nsplit=128, total_tiles=256, tiles_per_split=2, tiles_x=2, tiles_y=16, coblocks=1, ciblocks=3, reduce=1, reduce_kernel=b"splitk_reduce<16>")),
+    # small-Cin kernel: 4 bands per image from 128 x 128 on
+    (4, [1], 24, 256, 256, dict(), "conv3x3_wgrad_smallcin_kernel + splitk_reduce + channel_sums", dict(nsplit=16, bands=4, reduce=1, reduce_kernel=b"splitk_reduce<4>")),
+    # direct kernel: at most 16 splits; split s takes images s, s + 16
+    (24, [7], 8, 8, 8, dict(bias=False), "conv3x3_wgrad_direct_kernel + splitk_reduce", dict(nsplit=16, images_per_split=2, reduce=1, reduce_kernel=b"splitk_reduce<4>")),
+]
+
+
+@pytest.mark.parametrize("N,segs,Cout,H,W,mode,name,want", WGRAD_PLANS, ids=[f"{r[6].split('<')[0].split(' ')[0]}-{r[0]}x{sum(r[1])}-{r[2]}@{r[3]}x{r[4]}" for r in WGRAD_PLANS])
+def test_conv3x3_wgrad_plan_is_the_hand_computed_plan(lib, N, segs, Cout, H, W, mode, name, want):
+    """mtbc_conv3x3_wgrad_plan (host only) reports what the launch hands its kernel: against plans worked out by hand, field by field."""
+    from multi_task_breast_cancer_amd import ops
+    a = ops.conv3x3_case_args(L.OP_CONV3_WGRAD, N, segs, Cout, H, W, **mode)
+    assert ops.conv3x3_kernel_name(a, L.OP_CONV3_WGRAD) == name
+    plan = ops.conv3x3_wgrad_plan(a)
+    got = {f: getattr(plan, f) for f, _ in L.WgradPlan._fields_}
+    assert got == dict({f: (b"" if f == "reduce_kernel" else 0) for f in got}, **want)
+
+
+def test_conv3x3_wgrad_plan_refuses_what_the_call_refuses(lib):
+    from multi_task_breast_cancer_amd import ops
+    plan = L.WgradPlan()
+    good = ops.conv3x3_case_args(L.OP_CONV3_WGRAD, 2, [48], 48, 32, 32, **_BF16)
+    assert lib.mtbc_conv3x3_wgrad_plan(C.byref(good), C.byref(plan)) == 0 and plan.nsplit > 0
+    assert lib.mtbc_conv3x3_wgrad_plan(None, C.byref(plan)) == -2
+    assert lib.mtbc_conv3x3_wgrad_plan(C.byref(good), None) == -2
+    a = ops.conv3x3_case_args(L.OP_CONV3_WGRAD, 2, [48], 48, 32, 32, **_BF16)
+    a.H = 0
+    assert lib.mtbc_conv3x3_wgrad_plan(C.byref(a), C.byref(plan)) == -1                # bad shape
+    a = ops.conv3x3_case_args(L.OP_CONV3_WGRAD, 2, [48], 48, 32, 32, **_BF16)
+    a.workspace_bytes -= 4                                                              # one float short
+    assert lib.mtbc_conv3x3_wgrad_plan(C.byref(a), C.byref(plan)) == -3
+    for op in (L.OP_CONV3_FWD, L.OP_CONV3_DGRAD):                                       # not a weight gradient's arguments: no dw (and no dout)
+        a = ops.conv3x3_case_args(op, 2, [48], 48, 32, 32, **_BF16)
+        assert lib.mtbc_conv3x3_wgrad_plan(C.byref(a), C.byref(plan)) == -2
+    a = ops.conv3x3_case_args(L.OP_CONV3_WGRAD, 2, [1], 24, 32, 32, **_BF16)           # the stem's weight gradient has no dbias
+    assert lib.mtbc_conv3x3_wgrad_plan(C.byref(a), C.byref(plan)) == lib.mtbc_conv3x3_kernel_name(C.byref(a), L.OP_CONV3_WGRAD, C.create_string_buffer(256), 256) == -5
 
 
 # (backward, N, C, H, W, mode) -> what mtbc_instnorm_kernel_name names: the selection of norm.hip / norm_coop.hip made visible where it needs

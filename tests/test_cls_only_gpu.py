@@ -510,7 +510,7 @@ def test_refusals():
 
 
 # ------------------------------------------------------------------------------------------------ 11
-_NAMED = ("conv3x3", "InstanceNorm", "transposed-convolution", "small-op", "loss")      # the families whose keys carry a kernel-name string
+_NAMED = ("conv3x3", "conv3x3-wgrad-plan", "InstanceNorm", "transposed-convolution", "small-op", "loss")      # the families whose keys carry a kernel-name string
 _PROGRAMS = {"nnUNetClassifier": "MTnnUNet", "UNetPlusPlusClassifier": "MTUNetPlusPlus"}
 
 
@@ -599,7 +599,8 @@ def test_cls_only_programs_launch_only_reference_tested_instances(arch):
     import test_ops_gpu as OPS
     _, cl = _surveys(arch)
     own = {(op, key) for case in _pool_only_cases() for op, _, key in OPS._inorm_case_calls(case)}
-    tested = {"conv3x3": OPS._reference_tested_conv3x3_keys(), "InstanceNorm": OPS._reference_tested_instnorm_keys() | own,
+    tested = {"conv3x3": OPS._reference_tested_conv3x3_keys(), "conv3x3-wgrad-plan": OPS._reference_tested_wgrad_plan_keys(),
+              "InstanceNorm": OPS._reference_tested_instnorm_keys() | own,
               "transposed-convolution": OPS._reference_tested_convT_keys(), "small-op": OPS._reference_tested_small_op_keys(),
               "layout": OPS._reference_tested_layout_keys(), "loss": LOSS._reference_tested_loss_keys()}
     extra = []

@@ -125,6 +125,52 @@ def test_conv3x3_launches_match_fp64(case):
     _ops_gpu().test_conv3x3_step_instances_match_fp64(case)
 
 
+# ------------------------------------------------------------------------------------------------ the split plans of the 3x3 weight gradients
+# (N, segs, Cout, H, W, mode) as in WGRAD_PLAN_CASES of tests/test_ops_gpu.py, and by its shape rule (the fewest multiply-adds at which the
+# dummy-pointer struct has the plan key): one row per plan key (tests/step_programs.py _wgrad_plan_key) of the three programs that no table of
+# that file makes -- at N 16 / 2 on maps of 128 x 128 and below the tile-walking kernels get ONE tile per split behind the many-split
+# reductions, which the benchmark's batches never do.  Behind each row: its plan key, and in brackets the first launch it stands for.
+_PB, _PH, _P32 = dict(compute=1, c8=True, bias=False), dict(compute=2, c8=True, bias=False), dict(bias=False)
+_LB, _LH = dict(compute=1, bias=False), dict(compute=2, bias=False)          # 16-bit MFMA on fp32 planes (a 12-channel neighbour: no channel-blocked tensors)
+WGRAD_PLAN_CASES = [
+    (32, [8], 8, 96, 48, _LB),        # conv3x3_wgrad_lp2_kernel<false> + splitk_reduce (fixed, tiles>=3, splitk_reduce<64, 16> x8)  [16 x 24 -> 12 @ 128 x 128 in bf16]
+    (1, [8], 8, 256, 48, _PB),        # conv3x3_wgrad_c8_kernel<false, 0> + splitk_reduce (fixed, tiles=1, splitk_reduce<16> x8)  [16 x 96 -> 48 @ 32 x 32 in bf16 and 2 more]
+    (2, [8], 8, 512, 48, _PB),        # conv3x3_wgrad_c8_kernel<false, 0> + splitk_reduce (fixed, tiles=1, splitk_reduce<64, 16> x8)  [16 x 48 -> 24 @ 64 x 64 in bf16 and 2 more]
+    (8, [8], 192, 96, 48, _PB),       # conv3x3_wgrad_c8_kernel<false, 0> + splitk_reduce (fixed, tiles>=3, splitk_reduce<16> x8)  [16 x 48+48 -> 48 @ 64 x 64 in bf16]
+    (8, [96], 48, 16, 16, _PB),       # conv3x3_wgrad_c8i_kernel<false, 3, false> + splitk_reduce (images=1, ciblocks>1, splitk_reduce<4> x2)  [16 x 96 -> 192 @ 16 x 16 in bf16 and 3 more]
+    (48, [96], 192, 16, 16, _PB),     # conv3x3_wgrad_c8i_kernel<false, 3, false> + splitk_reduce (images=2, ciblocks>1, splitk_reduce<4> x2)  [16 x 192+192+192 -> 192 @ 16 x 16 in bf16]
+    (32, [8], 8, 96, 48, _LH),        # conv3x3_wgrad_lp2_kernel<true> + splitk_reduce (fixed, tiles>=3, splitk_reduce<64, 16> x8)  [16 x 24 -> 12 @ 128 x 128 in f16]
+    (1, [8], 8, 256, 48, _PH),        # conv3x3_wgrad_c8_kernel<true, 0> + splitk_reduce (fixed, tiles=1, splitk_reduce<16> x8)  [16 x 96 -> 48 @ 32 x 32 in f16 and 2 more]
+    (2, [8], 8, 512, 48, _PH),        # conv3x3_wgrad_c8_kernel<true, 0> + splitk_reduce (fixed, tiles=1, splitk_reduce<64, 16> x8)  [16 x 48 -> 24 @ 64 x 64 in f16 and 2 more]
+    (8, [8], 192, 96, 48, _PH),       # conv3x3_wgrad_c8_kernel<true, 0> + splitk_reduce (fixed, tiles>=3, splitk_reduce<16> x8)  [16 x 48+48 -> 48 @ 64 x 64 in f16]
+    (8, [96], 48, 16, 16, _PH),       # conv3x3_wgrad_c8i_kernel<true, 3, false> + splitk_reduce (images=1, ciblocks>1, splitk_reduce<4> x2)  [16 x 96 -> 192 @ 16 x 16 in f16 and 3 more]
+    (48, [96], 192, 16, 16, _PH),     # conv3x3_wgrad_c8i_kernel<true, 3, false> + splitk_reduce (images=2, ciblocks>1, splitk_reduce<4> x2)  [16 x 192+192+192 -> 192 @ 16 x 16 in f16]
+    (1, [7], 8, 8, 8, _P32),          # conv3x3_wgrad_direct_kernel + splitk_reduce (splitk_reduce<4> x1)  [2 x 12 -> 24 @ 128 x 128 in f32]
+    (8, [7], 8, 8, 8, _P32),          # conv3x3_wgrad_direct_kernel + splitk_reduce (splitk_reduce<4> x2)  [16 x 12 -> 24 @ 128 x 128 in bf16 and 1 more]
+    (1, [8], 8, 16, 48, _P32),        # conv3x3_wgrad_mfma_kernel<0, 2, false> + splitk_reduce (fixed, tiles=1, splitk_reduce<4> x2)  [2 x 96+96 -> 96 @ 32 x 32 in f32]
+    (1, [24], 8, 128, 48, _P32),      # conv3x3_wgrad_mfma_kernel<0, 2, true> + splitk_reduce (fixed, tiles=1, splitk_reduce<16> x2)  [2 x 48 -> 24 @ 64 x 64 in f32 and 1 more]
+    (1, [24], 8, 16, 48, _P32),       # conv3x3_wgrad_mfma_kernel<0, 2, true> + splitk_reduce (fixed, tiles=1, splitk_reduce<4> x2)  [2 x 48 -> 96 @ 32 x 32 in f32]
+    (1, [24], 8, 512, 48, _P32),      # conv3x3_wgrad_mfma_kernel<0, 2, true> + splitk_reduce (fixed, tiles=1, splitk_reduce<64, 16> x2)  [2 x 24 -> 12 @ 128 x 128 in f32 and 1 more]
+    (1, [8], 40, 128, 48, _P32),      # conv3x3_wgrad_mfma_kernel<0, 3, false> + splitk_reduce (fixed, tiles=1, splitk_reduce<16> x2)  [2 x 48+48 -> 48 @ 64 x 64 in f32]
+    (1, [8], 40, 16, 48, _P32),       # conv3x3_wgrad_mfma_kernel<0, 3, false> + splitk_reduce (fixed, tiles=1, splitk_reduce<4> x2)  [2 x 96 -> 48 @ 32 x 32 in f32]
+    (1, [24], 40, 128, 48, _P32),     # conv3x3_wgrad_mfma_kernel<0, 3, true> + splitk_reduce (fixed, tiles=1, splitk_reduce<16> x2)  [2 x 24 -> 48 @ 64 x 64 in f32]
+    (1, [24], 40, 16, 48, _P32),      # conv3x3_wgrad_mfma_kernel<0, 3, true> + splitk_reduce (fixed, tiles=1, splitk_reduce<4> x2)  [2 x 48 -> 48 @ 32 x 32 in f32]
+    (1, [8], 8, 12, 8, _P32),         # conv3x3_wgrad_mfma_kernel<1, 2, false> + splitk_reduce (fixed, tiles=1, splitk_reduce<4> x1)  [2 x 192+192+192 -> 192 @ 16 x 16 in f32 and 4 more]
+    (16, [1], 8, 32, 512, _P32),      # conv3x3_wgrad_smallcin_kernel + splitk_reduce (bands=4, splitk_reduce<16> x2)  [16 x 1 -> 12 @ 128 x 128 in bf16 and 1 more]
+    (2, [1], 8, 32, 512, _P32),       # conv3x3_wgrad_smallcin_kernel + splitk_reduce (bands=4, splitk_reduce<4> x2)  [2 x 1 -> 12 @ 128 x 128 in f32]
+]
+PLAN = "conv3x3-wgrad-plan"
+
+
+def _wgrad_plan_ids():
+    return [_ops_gpu()._wgrad_plan_case_id(c) for c in WGRAD_PLAN_CASES]
+
+
+@pytest.mark.parametrize("case", WGRAD_PLAN_CASES, ids=_wgrad_plan_ids())
+def test_conv3x3_wgrad_plans_match_fp64(case):
+    _ops_gpu().test_conv3x3_wgrad_plan_cases_match_fp64(case)
+
+
 # ------------------------------------------------------------------------------------------------ InstanceNorm + LeakyReLU
 # (backward, N, C, H, W, mode) as in INORM_CASES of tests/test_ops_gpu.py.  Every cell of this model is without affine parameters and without a
 # conv bias (slope 0.01): no dgamma / dbeta / dbias_pre, nothing deferred.  The 12-channel cells (no group of 8 channels) and the whole f32
@@ -200,6 +246,8 @@ def _own_keys():
     for case in CONV3_CASES:
         op, N, segs, Cout, H, W, mode = case
         own["conv3x3"].setdefault((op, SP._conv3_key(ops.conv3x3_case_args(op, N, segs, Cout, H, W, **mode), op)), []).append(case)
+    for case in WGRAD_PLAN_CASES:
+        own[PLAN].setdefault((W_, SP._wgrad_plan_key(ops.conv3x3_case_args(W_, *case[:5], **case[5]))), []).append(case)
     for case in INORM_CASES:
         for op, _, key in OPS._inorm_case_calls(case):
             own["InstanceNorm"].setdefault((op, key), []).append(case)
@@ -222,7 +270,7 @@ def _tested():
     module adds)}"""
     import test_loss_launches_gpu as LOSS
     OPS, own = _ops_gpu(), _own_keys()
-    old = {"conv3x3": OPS._reference_tested_conv3x3_keys(), "InstanceNorm": OPS._reference_tested_instnorm_keys(),
+    old = {"conv3x3": OPS._reference_tested_conv3x3_keys(), PLAN: OPS._reference_tested_wgrad_plan_keys(), "InstanceNorm": OPS._reference_tested_instnorm_keys(),
            "transposed-convolution": OPS._reference_tested_convT_keys(), "small-op": OPS._reference_tested_small_op_keys(),
            "layout": OPS._reference_tested_layout_keys(), "loss": LOSS._reference_tested_loss_keys()}
     new = {family: set(keys) for family, keys in own.items()}
@@ -269,7 +317,7 @@ def test_mt_btsunet_cases_are_all_needed():
             if not any(k in launched and k not in tested[family][0] for k in ks):
                 bad.append(f"\n  {family}: no program launches, or an older table already makes, {ks} of row {row}")
         print(f"{family}: {len(rows)} rows, {len(keys)} keys")
-    assert len(CONV3_CASES) + len(INORM_CASES) + len(WVIEW_CASES) > 0 and set(_own_keys()) == set(SP.COLLECTORS)
+    assert len(CONV3_CASES) + len(WGRAD_PLAN_CASES) + len(INORM_CASES) + len(WVIEW_CASES) > 0 and set(_own_keys()) == set(SP.COLLECTORS)
     assert not bad, "rows of tests/test_mt_btsunet_launches_gpu.py that are not needed:" + "".join(bad)
 
 

@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 from multi_task_breast_cancer_amd import ops  # noqa: E402
 from oracle import torch_oracle as O  # noqa: E402
 from step_programs import (STEP_PROGRAMS, _c8_key, _conv3_key, _convT_key, _dparam_key, _instnorm_key, _pack_key,  # noqa: E402
-                           _small_op_key, _wview_key, assert_all_tested, survey)
+                           _small_op_key, _wgrad_plan_key, _wview_key, assert_all_tested, survey)
 
 DEV = "cuda:0"
 
@@ -424,20 +424,20 @@ def test_conv3x3_c8_operands(N, segs, Cout, H, W, compute):
 
 # shapes that take the wide-block / rolling-row weight-gradient kernel (conv3x3_wgrad_c8w_kernel: Cin >= 64 on maps >= 128 wide)
 C8W_CASES = [
-    (8, [24, 24, 24], 24, 20, 128),            # image -> XCD block mapping (N % 8 == 0); Cin = 72: a half-empty last input tile; 5 row steps
-    (2, [24, 24, 24, 24, 48], 24, 256, 256),   # 144 -> 24 @256x256: two input-channel blocks (5 + 4 tiles), 64 steps per strip
-    (1, [48, 48], 48, 130, 128),               # 48 outputs = 3 tiles in one block; H not a multiple of the 4-row step; one image
-    (2, [96, 96], 96, 32, 160),                # 2 output-channel blocks x 3 input-channel blocks; 5 strips
-    (2, [64], 40, 36, 144),                    # Cout = 40: blocks of 32 + 8 channels; W not a multiple of the 32-column strip
-    (3, [96, 48, 48], 48, 12, 256),            # 192 -> 48: three input-channel blocks; rows < one ring (3 steps); N % 8 != 0
+    (8, [24, 24, 24], 24, 20, 128),            # image -> XCD block mapping (N % 8 == 0); Cin = 72: a half-empty last input tile; 5 row steps in segments of 2, 2 and 1
+    (2, [24, 24, 24, 24, 48], 24, 256, 256),   # 144 -> 24 @256x256: two input-channel blocks (5 + 4 tiles), 64 steps per strip in 16 segments of 4
+    (1, [48, 48], 48, 130, 128),               # 48 outputs = 3 tiles in one block; H not a multiple of the 4-row step; one image; 33 steps in 17 segments of 2 (the last: 1)
+    (2, [96, 96], 96, 32, 160),                # 2 output-channel blocks x 3 input-channel blocks; 5 strips of 4 segments of 2 steps
+    (2, [64], 40, 36, 144),                    # Cout = 40: blocks of 32 + 8 channels; W not a multiple of the 32-column strip; 9 steps in 5 segments of 2 (the last: 1)
+    (3, [96, 48, 48], 48, 12, 256),            # 192 -> 48: three input-channel blocks; 3 steps in segments of 2 and 1: no segment fills the ring; N % 8 != 0
 ]
 
 
 # ... and the image-tile kernel of the 16 x 16 maps (conv3x3_wgrad_c8i_kernel: Cin >= 64, Cout >= 32)
 C8I_CASES = [
     (5, [64], 40, 16, 16),                     # Cout = 40: blocks of 32 + 8 channels; 5 image ranges of one image
-    (9, [96, 48, 48], 48, 16, 16),             # three segments, 192 -> 48: three input-channel blocks of 4 tiles; 48 outputs in one block
-    (16, [264], 64, 16, 16),                   # 16.5 input tiles: four blocks, the last tile half empty; two images per range
+    (9, [96, 48, 48], 48, 16, 16),             # three segments, 192 -> 48: three input-channel blocks of 4 tiles; 48 outputs in one block; 9 ranges of one image
+    (16, [264], 64, 16, 16),                   # 16.5 input tiles: four blocks, the last tile half empty; 16 ranges of one image
     (3, [72], 96, 16, 16),                     # 4.5 input tiles in one block; 2 output-channel blocks of 48
     (1, [64], 48, 16, 16),                     # ONE image range: without bias / accumulation the blocks store straight into dw (no reduction launch)
 ]
@@ -471,17 +471,17 @@ def test_conv3x3_wgrad_c8_wide_blocks(N, segs, Cout, H, W, compute):
     assert torch.equal(again, dw1), "not deterministic"
 
 
-# the in-kernel split-K reduction across its tree shapes: (N, segs, Cout, H, W) -> splits per (co, ci) tile / levels
+# the in-kernel split-K reduction across its tree shapes: (N, segs, Cout, H, W) -> channel blocks x splits / levels, as mtbc_conv3x3_wgrad_plan reports them
 FIXUP_CASES = [
-    (16, [24], 24, 256, 256),                  # 32 x 32 kernel, ONE tile, 1024 splits: three levels of fan-in 11
-    (8, [48], 48, 128, 128),                   # 4 tiles x 256 splits: three levels of 7
-    (4, [96], 96, 64, 64),                     # 9 tiles x 113 splits (not a multiple of 8: ragged (split % 8) classes)
-    (8, [96], 96, 128, 128),                   # 1024 pixel tiles, 9 channel blocks: 112 splits (a multiple of 8: one XCD per split) of 9 or 10 tiles each
-    (2, [192], 192, 32, 32),                   # 36 tiles x 28 splits: two levels of 6, ragged last group
-    (2, [384], 192, 32, 32),                   # 72 tiles x 14 splits
-    (8, [24, 24, 24], 24, 256, 256),           # wide-block kernel: 512 row-segment splits of image-major leaves (N % 8 == 0)
-    (3, [96, 48, 48], 48, 128, 128),           # wide-block kernel, N % 8 != 0: leaf = split
-    (32, [192], 384, 16, 16),                  # image-tile kernel: 24 channel blocks x 8 image ranges = one level
+    (16, [24], 24, 256, 256),                  # 32 x 32 kernel, ONE channel block, 8192 tiles dealt evenly over 1024 splits: three levels of fan-in 11
+    (8, [48], 48, 128, 128),                   # 4 channel blocks x 256 splits (1024 tiles dealt evenly, 4 each): three levels of 7
+    (4, [96], 96, 64, 64),                     # 9 channel blocks x 64 splits of 2 tiles (128 tiles: below the 1024 of the even deal): two levels of 8
+    (8, [96], 96, 128, 128),                   # wide-block kernel (W = 128, Cin >= 64), 2 x 2 channel blocks: 4 strips x 4 row segments of 8 steps x 8 images = 128 splits, three levels of 6, ragged last group
+    (2, [192], 192, 32, 32),                   # 36 channel blocks x 16 splits of one tile: two levels of 4
+    (2, [384], 192, 32, 32),                   # 72 channel blocks x 8 splits of 2 tiles: one level
+    (8, [24, 24, 24], 24, 256, 256),           # wide-block kernel: 8 strips x 8 row segments of 8 steps x 8 images = 512 splits of image-major leaves (N % 8 == 0), three levels of 8
+    (3, [96, 48, 48], 48, 128, 128),           # wide-block kernel, N % 8 != 0: leaf = split; 4 strips x 11 segments of 3 steps (the last: 2) x 3 images = 132 splits, three levels of 6
+    (32, [192], 384, 16, 16),                  # image-tile kernel: 24 channel blocks x 8 ranges of 4 images = one level
     (6, [384], 384, 16, 16),                   # image-tile kernel: 6 ranges of one image
     (1, [64], 48, 16, 16),                     # ONE split: with bias / accumulation the single row goes through the top level
 ]
@@ -1684,26 +1684,32 @@ def test_conv3x3_step_instances_match_fp64(case):
             _close(db, dbr.float(), 1e-5, 2e-5 * max(1.0, dbr.abs().max().item()), "dbias")
 
 
-def _reference_tested_conv3x3_keys():
-    """The (op, _conv3_key) of every conv3x3 call that a test of this file checks element by element against fp64, from the tests' own case
-    tables through dummy-pointer structs (ops.conv3x3_case_args).  Tests that compare two kernels with each other, or a kernel with an fp32
-    reference, do not count: test_conv3x3_mfma_fwd_dgrad_wgrad, the forward / dgrad half of test_conv3x3_c8_operands,
+def _reference_tested_conv3x3_calls():
+    """(op, (N, segs, Cout, H, W), mode, table) of every conv3x3 call that a test of this file checks element by element against fp64 -- the
+    rows of WGRAD_PLAN_CASES aside --, from the tests' own case tables.  Tests that compare two kernels with each other, or a kernel with an
+    fp32 reference, do not count: test_conv3x3_mfma_fwd_dgrad_wgrad, the forward / dgrad half of test_conv3x3_c8_operands,
     test_stem_conv_on_the_16bit_path, test_bf16_mode_conv_output_stored_as_fp16, test_instnorm_statistics_from_the_conv_epilogue."""
-    calls = [(op, (N, segs, Cout, H, W), mode) for op, N, segs, Cout, H, W, mode in CONV3_STEP_CASES]      # test_conv3x3_step_instances_match_fp64
+    calls = [(op, (N, segs, Cout, H, W), mode, "CONV3_STEP_CASES") for op, N, segs, Cout, H, W, mode in CONV3_STEP_CASES]      # test_conv3x3_step_instances_match_fp64
     for case in BENCH_CASES:                                     # test_conv3x3_bench_instances_match_fp64
-        calls += [(op, case[:5], kw) for op, kw in _bench_case_calls(*case)]
+        calls += [(op, case[:5], kw, "BENCH_CASES") for op, kw in _bench_case_calls(*case)]
     for compute in (1, 2):
         m = dict(compute=compute, c8=True)
         fix, nobias = dict(m, in_kernel_reduce=True), dict(m, in_kernel_reduce=True, bias=False)
         for case in C8_CASES:                                    # test_conv3x3_c8_operands: the weight gradients
-            calls += [(W_, case, fix), (W_, case, dict(nobias, accumulate_dw=True))]
+            calls += [(W_, case, fix, "C8_CASES"), (W_, case, dict(nobias, accumulate_dw=True), "C8_CASES")]
         for case in C8_CASES + EXTRA16_CASES:                    # test_conv3x3_16bit_fwd_dgrad_match_fp64_on_rounded_operands
-            calls += [(F_, case, m), (D_, case, m), (F_, case, dict(compute=compute)), (D_, case, dict(compute=compute))]
-        for case in C8W_CASES + C8I_CASES:                       # test_conv3x3_wgrad_c8_wide_blocks
-            calls += [(W_, case, fix), (W_, case, nobias), (W_, case, dict(nobias, accumulate_dw=True))]
+            calls += [(op, case, kw, "C8_CASES + EXTRA16_CASES") for op in (F_, D_) for kw in (m, dict(compute=compute))]
+        for table, cases in (("C8W_CASES", C8W_CASES), ("C8I_CASES", C8I_CASES)):      # test_conv3x3_wgrad_c8_wide_blocks
+            for case in cases:
+                calls += [(W_, case, fix, table), (W_, case, nobias, table), (W_, case, dict(nobias, accumulate_dw=True), table)]
         for case in FIXUP_CASES:                                 # test_conv3x3_wgrad_c8_in_kernel_split_k_reduction
-            calls += [(W_, case, fix), (W_, case, m), (W_, case, nobias), (W_, case, dict(nobias, accumulate_dw=True))]
-    return {(op, _conv3_key(ops.conv3x3_case_args(op, *case, **kw), op)) for op, case, kw in calls}
+            calls += [(W_, case, kw, "FIXUP_CASES") for kw in (fix, m, nobias, dict(nobias, accumulate_dw=True))]
+    return calls
+
+
+def _reference_tested_conv3x3_keys():
+    """The (op, _conv3_key) of _reference_tested_conv3x3_calls, through dummy-pointer structs (ops.conv3x3_case_args)."""
+    return {(op, _conv3_key(ops.conv3x3_case_args(op, *case, **kw), op)) for op, case, kw, _ in _reference_tested_conv3x3_calls()}
 
 
 def test_step_programs_launch_only_reference_tested_conv3x3_instances():
@@ -1714,6 +1720,133 @@ def test_step_programs_launch_only_reference_tested_conv3x3_instances():
     L = ops.L
     assert_all_tested("conv3x3", _reference_tested_conv3x3_keys(), [survey(p) for p in STEP_PROGRAMS] + [survey(STEP_PROGRAMS[0], 64)],
                       required=(L.OP_CONV3_FWD, L.OP_CONV3_DGRAD, L.OP_CONV3_WGRAD))
+
+
+# ------------------------------------------------------------------ the 3x3 weight gradients of the step programs, keyed by their split plans
+# (N, segs, Cout, H, W, mode): one row per plan key (tests/step_programs.py _wgrad_plan_key: the kernel_name string + the class of the plan
+# mtbc_conv3x3_wgrad_plan reports) that the surveyed step programs launch and no older weight-gradient case of this file makes, run through
+# test_conv3x3_step_instances_match_fp64.  Shapes: of the channel counts and map sizes at which the dummy-pointer struct has the plan key of the
+# step's launch, the one with the fewest multiply-adds N * H * W * Cin * Cout (the fp64 reference on the CPU is the cost of a case), then the
+# fewest pixels; one segment (the plan reads Cin, not the segments: the _conv3_key rows above hold those).  Behind each row: its plan key, and in
+# brackets the first launch it stands for (profiles/conv3x3_step_keys.txt lists them all).
+_PB, _PH, _P32 = dict(compute=1, c8=True, bias=False), dict(compute=2, c8=True, bias=False), dict(bias=False)
+WGRAD_PLAN_CASES = [
+    (32, [8], 384, 64, 48, _PB),          # conv3x3_wgrad_c8_kernel<false, 0> + splitk_reduce (even, tiles>=3, ragged, crosses, splitk_reduce<16> x2+x1)  [32 x 96 -> 96 @ 64 x 64 in MTUNetPlusPlus bf16]
+    (16, [144], 8, 128, 48, _PB),         # conv3x3_wgrad_c8_kernel<false, 0> + splitk_reduce (even, tiles>=3, ragged, crosses, splitk_reduce<16> x8+x2+x1)  [32 x 48 -> 96 @ 64 x 64 in MTUNetPlusPlus bf16]
+    (48, [8], 320, 44, 48, _PB),          # conv3x3_wgrad_c8_kernel<false, 0> + splitk_reduce (even, tiles>=3, splitk_reduce<16> x2)  [64 x 128+128 -> 64 @ 64 x 64 in MTnnUNet bf16]
+    (32, [840], 8, 64, 64, _PB),          # conv3x3_wgrad_c8_kernel<false, 0> + splitk_reduce (even, tiles>=3, splitk_reduce<4> x8)  [32 x 96+96+96 -> 96 @ 64 x 64 in MTUNetPlusPlus bf16: 32 splits need 27 .. 32 channel blocks]
+    (9, [512], 40, 16, 48, _PB),          # conv3x3_wgrad_c8_kernel<false, 0> + splitk_reduce (fixed, tiles>=3, crosses, splitk_reduce<4> x2)  [64 x 256+256 -> 128 @ 32 x 32 in MTnnUNet bf16]
+    (3, [384], 40, 64, 48, _PB),          # conv3x3_wgrad_c8_kernel<false, 0> + splitk_reduce (fixed, tiles>=3, crosses, splitk_reduce<4> x8)  [64 x 128 -> 256 @ 32 x 32 in MTnnUNet bf16]
+    (2, [72], 512, 44, 48, _PB),          # conv3x3_wgrad_c8_kernel<false, 0> + splitk_reduce (fixed, tiles>=3, ragged, crosses, splitk_reduce<4> x2+x1)  [32 x 192 -> 192 @ 32 x 32 in MTUNetPlusPlus bf16]
+    (4, [8], 384, 96, 48, _PB),           # conv3x3_wgrad_c8_kernel<false, 0> + splitk_reduce (fixed, tiles>=3, splitk_reduce<16> x2)  [64 x 128 -> 128 @ 32 x 32 in MTnnUNet bf16]
+    (40, [512], 40, 12, 8, _PB),          # conv3x3_wgrad_c8_kernel<false, 1> + splitk_reduce (fixed, tiles>=3, ragged, crosses, splitk_reduce<4> x2+x1)  [64 x 320 -> 320 @ 8 x 8 in MTnnUNet bf16]
+    (9, [256], 512, 16, 16, _PB),         # conv3x3_wgrad_c8i_kernel<false, 2, false> + splitk_reduce (images>=3, ciblocks>1, splitk_reduce<4> x1)  [32 x 512 -> 512 @ 16 x 16 in MTUNetPlusPlus bf16]
+    (24, [96], 320, 16, 16, _PB),         # conv3x3_wgrad_c8i_kernel<false, 2, false> + splitk_reduce (images>=3, ciblocks>1, splitk_reduce<4> x2)  [64 x 256 -> 256 @ 16 x 16 in MTnnUNet bf16]
+    (40, [512], 40, 16, 16, _PB),         # conv3x3_wgrad_c8i_kernel<false, 2, false> + splitk_reduce (images>=3, short_last_range, ciblocks>1, splitk_reduce<4> x2+x1)  [64 x 256 -> 320 @ 16 x 16 in MTnnUNet bf16]
+    (24, [192], 384, 16, 16, _PB),        # conv3x3_wgrad_c8i_kernel<false, 3, false> + splitk_reduce (images>=3, ciblocks>1, splitk_reduce<4> x2)  [64 x 192 -> 384 @ 16 x 16 in MTUNetPlusPlus bf16]
+    (40, [96], 384, 16, 16, _PB),         # conv3x3_wgrad_c8i_kernel<false, 3, false> + splitk_reduce (images>=3, short_last_range, ciblocks>1, splitk_reduce<4> x2+x1)  [64 x 384 -> 384 @ 16 x 16 in MTUNetPlusPlus bf16]
+    (8, [384], 8, 12, 512, _PB),          # conv3x3_wgrad_c8w_kernel<false, 2, false> + splitk_reduce (segs=1, img8, steps>=ring, ciblocks>1, ragged_cit, splitk_reduce<16> x8)  [32 x 24+24+24+24+48 -> 24 @ 256 x 256 in MTUNetPlusPlus bf16]
+    (8, [192], 8, 12, 512, _PB),          # conv3x3_wgrad_c8w_kernel<false, 2, false> + splitk_reduce (segs=1, img8, steps>=ring, ciblocks>1, splitk_reduce<16> x8)  [32 x 24+24+24+48 -> 24 @ 256 x 256 in MTUNetPlusPlus bf16]
+    (16, [64], 40, 12, 512, _PB),         # conv3x3_wgrad_c8w_kernel<false, 2, false> + splitk_reduce (segs=1, img8, steps>=ring, splitk_reduce<16> x8)  [64 x 32+32 -> 32 @ 256 x 256 in MTnnUNet bf16]
+    (8, [64], 8, 48, 512, _PB),           # conv3x3_wgrad_c8w_kernel<false, 2, false> + splitk_reduce (segs>1, img8, steps>=ring, splitk_reduce<64, 16> x8)  [32 x 24+48 -> 24 @ 256 x 256 in MTUNetPlusPlus bf16]
+    (8, [96], 96, 12, 512, _PB),          # conv3x3_wgrad_c8w_kernel<false, 3, false> + splitk_reduce (segs=1, img8, steps>=ring, ciblocks>1, splitk_reduce<16> x8)  [32 x 48+48+48+48 -> 48 @ 128 x 128 in MTUNetPlusPlus bf16]
+    (8, [144], 96, 24, 256, _PB),         # conv3x3_wgrad_c8w_kernel<false, 3, false> + splitk_reduce (segs>1, img8, steps>=ring, ciblocks>1, ragged_cit, splitk_reduce<16> x8)  [32 x 48+48+48 -> 48 @ 128 x 128 in MTUNetPlusPlus bf16]
+    (8, [96], 96, 24, 256, _PB),          # conv3x3_wgrad_c8w_kernel<false, 3, false> + splitk_reduce (segs>1, img8, steps>=ring, ciblocks>1, splitk_reduce<16> x8)  [32 x 48+48 -> 48 @ 128 x 128 in MTUNetPlusPlus bf16]
+    (32, [1], 8, 128, 512, _PB),          # conv3x3_wgrad_stem_c8_kernel<false> + splitk_reduce (bands=16, splitk_reduce<64, 16> x8)  [32 x 1 -> 24 @ 256 x 256 in MTUNetPlusPlus bf16]
+    (16, [144], 8, 128, 48, _PH),         # conv3x3_wgrad_c8_kernel<true, 0> + splitk_reduce (even, tiles>=3, ragged, crosses, splitk_reduce<16> x8+x2+x1)  [16 x 48 -> 96 @ 128 x 128 in MTUNetPlusPlus f16]
+    (3, [384], 512, 8, 48, _PH),          # conv3x3_wgrad_c8_kernel<true, 0> + splitk_reduce (fixed, tiles>=3, crosses, splitk_reduce<4> x1)  [16 x 512 -> 512 @ 32 x 32 in MTUNetPlusPlus f16]
+    (2, [72], 512, 44, 48, _PH),          # conv3x3_wgrad_c8_kernel<true, 0> + splitk_reduce (fixed, tiles>=3, ragged, crosses, splitk_reduce<4> x2+x1)  [32 x 384 -> 384 @ 32 x 32 in MTUNetPlusPlus f16]
+    (8, [384], 8, 12, 512, _PH),          # conv3x3_wgrad_c8w_kernel<true, 2, false> + splitk_reduce (segs=1, img8, steps>=ring, ciblocks>1, ragged_cit, splitk_reduce<16> x8)  [16 x 24+24+24+24+48 -> 24 @ 512 x 512 in MTUNetPlusPlus f16]
+    (8, [192], 8, 12, 512, _PH),          # conv3x3_wgrad_c8w_kernel<true, 2, false> + splitk_reduce (segs=1, img8, steps>=ring, ciblocks>1, splitk_reduce<16> x8)  [16 x 24+24+24+48 -> 24 @ 512 x 512 in MTUNetPlusPlus f16]
+    (8, [64], 8, 48, 512, _PH),           # conv3x3_wgrad_c8w_kernel<true, 2, false> + splitk_reduce (segs>1, img8, steps>=ring, splitk_reduce<64, 16> x8)  [16 x 24+48 -> 24 @ 512 x 512 in MTUNetPlusPlus f16]
+    (8, [384], 48, 12, 256, _PH),         # conv3x3_wgrad_c8w_kernel<true, 3, false> + splitk_reduce (segs=1, img8, steps>=ring, ciblocks>1, ragged_cit, splitk_reduce<16> x2)  [16 x 96+96+96 -> 96 @ 128 x 128 in MTUNetPlusPlus f16]
+    (8, [96], 96, 12, 384, _PH),          # conv3x3_wgrad_c8w_kernel<true, 3, false> + splitk_reduce (segs=1, img8, steps>=ring, ciblocks>1, splitk_reduce<16> x2)  [16 x 96+96 -> 96 @ 128 x 128 in MTUNetPlusPlus f16]
+    (8, [96], 96, 12, 512, _PH),          # conv3x3_wgrad_c8w_kernel<true, 3, false> + splitk_reduce (segs=1, img8, steps>=ring, ciblocks>1, splitk_reduce<16> x8)  [16 x 48+48+48+48 -> 48 @ 256 x 256 in MTUNetPlusPlus f16]
+    (8, [144], 96, 24, 256, _PH),         # conv3x3_wgrad_c8w_kernel<true, 3, false> + splitk_reduce (segs>1, img8, steps>=ring, ciblocks>1, ragged_cit, splitk_reduce<16> x8)  [16 x 48+48+48 -> 48 @ 256 x 256 in MTUNetPlusPlus f16]
+    (8, [96], 96, 24, 256, _PH),          # conv3x3_wgrad_c8w_kernel<true, 3, false> + splitk_reduce (segs>1, img8, steps>=ring, ciblocks>1, splitk_reduce<16> x8)  [16 x 96 -> 96 @ 128 x 128 in MTUNetPlusPlus f16]
+    (16, [1], 8, 128, 512, _PH),          # conv3x3_wgrad_stem_c8_kernel<true> + splitk_reduce (bands=16, splitk_reduce<64, 16> x2)  [16 x 1 -> 24 @ 512 x 512 in MTUNetPlusPlus f16]
+    (7, [8], 320, 44, 48, _P32),          # conv3x3_wgrad_mfma_kernel<0, 2, false> + splitk_reduce (fixed, tiles>=3, ragged, crosses, splitk_reduce<16> x2+x1)  [32 x 96 -> 96 @ 64 x 64 in MTUNetPlusPlus f32]
+    (2, [96], 384, 44, 48, _P32),         # conv3x3_wgrad_mfma_kernel<0, 2, false> + splitk_reduce (fixed, tiles>=3, ragged, crosses, splitk_reduce<4> x2+x1)  [32 x 96+96+96 -> 96 @ 64 x 64 in MTUNetPlusPlus f32]
+    (8, [8], 192, 96, 48, _P32),          # conv3x3_wgrad_mfma_kernel<0, 2, false> + splitk_reduce (fixed, tiles>=3, splitk_reduce<16> x8)  [32 x 24+24+48 -> 24 @ 256 x 256 in MTUNetPlusPlus f32]
+    (5, [72], 8, 256, 48, _P32),          # conv3x3_wgrad_mfma_kernel<0, 2, true> + splitk_reduce (fixed, tiles>=3, ragged, crosses, splitk_reduce<16> x8+x2+x1)  [32 x 24+24+24+48 -> 24 @ 256 x 256 in MTUNetPlusPlus f32]
+    (7, [24], 8, 512, 48, _P32),          # conv3x3_wgrad_mfma_kernel<0, 2, true> + splitk_reduce (fixed, tiles>=3, ragged, crosses, splitk_reduce<64, 16> x8+x2+x1)  [32 x 24 -> 24 @ 256 x 256 in MTUNetPlusPlus f32]
+    (8, [144], 8, 96, 48, _P32),          # conv3x3_wgrad_mfma_kernel<0, 2, true> + splitk_reduce (fixed, tiles>=3, splitk_reduce<16> x8)  [32 x 24+24+24+24+48 -> 24 @ 256 x 256 in MTUNetPlusPlus f32]
+    (16, [72], 8, 96, 48, _P32),          # conv3x3_wgrad_mfma_kernel<0, 2, true> + splitk_reduce (fixed, tiles>=3, splitk_reduce<64, 16> x2)  [32 x 24+48 -> 24 @ 256 x 256 in MTUNetPlusPlus f32]
+    (8, [192], 40, 44, 48, _P32),         # conv3x3_wgrad_mfma_kernel<0, 3, false> + splitk_reduce (fixed, tiles>=3, ragged, crosses, splitk_reduce<16> x2+x1)  [32 x 48+48+48+48 -> 48 @ 128 x 128 in MTUNetPlusPlus f32]
+    (11, [96], 40, 64, 48, _P32),         # conv3x3_wgrad_mfma_kernel<0, 3, false> + splitk_reduce (fixed, tiles>=3, ragged, crosses, splitk_reduce<16> x8+x2+x1)  [32 x 48+48 -> 48 @ 128 x 128 in MTUNetPlusPlus f32]
+    (8, [144], 40, 44, 48, _P32),         # conv3x3_wgrad_mfma_kernel<0, 3, true> + splitk_reduce (fixed, tiles>=3, ragged, crosses, splitk_reduce<16> x2+x1)  [32 x 48+48+48 -> 48 @ 128 x 128 in MTUNetPlusPlus f32]
+    (8, [72], 40, 96, 48, _P32),          # conv3x3_wgrad_mfma_kernel<0, 3, true> + splitk_reduce (fixed, tiles>=3, splitk_reduce<16> x8)  [32 x 48 -> 48 @ 128 x 128 in MTUNetPlusPlus f32]
+    (32, [24], 40, 96, 48, _P32),         # conv3x3_wgrad_mfma_kernel<0, 3, true> + splitk_reduce (fixed, tiles>=3, splitk_reduce<64, 16> x8)  [32 x 24 -> 48 @ 128 x 128 in MTUNetPlusPlus f32]
+    (5, [320], 512, 12, 8, _P32),         # conv3x3_wgrad_mfma_kernel<1, 2, false> + splitk_reduce (fixed, tiles>=3, ragged, crosses, splitk_reduce<4> x1)  [32 x 512 -> 512 @ 16 x 16 in MTUNetPlusPlus f32]
+    (8, [320], 320, 12, 8, _P32),         # conv3x3_wgrad_mfma_kernel<1, 2, false> + splitk_reduce (fixed, tiles>=3, ragged, crosses, splitk_reduce<4> x2+x1)  [64 x 384 -> 384 @ 16 x 16 in MTUNetPlusPlus f32]
+    (32, [1], 8, 32, 512, _P32),          # conv3x3_wgrad_smallcin_kernel + splitk_reduce (bands=4, splitk_reduce<16> x8)  [32 x 1 -> 24 @ 256 x 256 in MTUNetPlusPlus f32]
+]
+
+
+def _wgrad_plan_case_id(case):
+    return _conv3_case_id((W_,) + tuple(case))
+
+
+@pytest.mark.parametrize("case", WGRAD_PLAN_CASES, ids=_wgrad_plan_case_id)
+def test_conv3x3_wgrad_plan_cases_match_fp64(case):
+    """The weight-gradient check of test_conv3x3_step_instances_match_fp64 -- the whole batch against fp64 conv2d_weight on the operands the
+    kernel reads, _close(dw, ref, 1e-5, 2e-5 * max(1, |ref|max)), run twice bit-identically, launched == planned -- at the shape of the row."""
+    test_conv3x3_step_instances_match_fp64((W_,) + tuple(case))
+
+
+def _wgrad_plan_tables():
+    """{table name: {(W_, plan key): the first row that makes it}} of every weight-gradient call this file checks against fp64, the older tables
+    first (C8_CASES, C8W_CASES, C8I_CASES, FIXUP_CASES, the wgrad rows of BENCH_CASES and CONV3_STEP_CASES), WGRAD_PLAN_CASES last."""
+    tables = {}
+    for op, case, kw, table in _reference_tested_conv3x3_calls():
+        if op == W_:
+            tables.setdefault(table, {}).setdefault((W_, _wgrad_plan_key(ops.conv3x3_case_args(W_, *case, **kw))), (case, kw))
+    for case in WGRAD_PLAN_CASES:
+        tables.setdefault("WGRAD_PLAN_CASES", {}).setdefault((W_, _wgrad_plan_key(ops.conv3x3_case_args(W_, *case[:5], **case[5]))), case)
+    return tables
+
+
+def _older_wgrad_plan_keys():
+    return {key for table, keys in _wgrad_plan_tables().items() if table != "WGRAD_PLAN_CASES" for key in keys}
+
+
+def _reference_tested_wgrad_plan_keys():
+    """The (W_, _wgrad_plan_key) of every weight-gradient call that a test of this file checks against fp64: all the tables of _wgrad_plan_tables."""
+    return {key for keys in _wgrad_plan_tables().values() for key in keys}
+
+
+def _wgrad_plan_surveys():
+    return [survey(p) for p in STEP_PROGRAMS] + [survey(STEP_PROGRAMS[0], 64)]
+
+
+def test_step_programs_launch_only_reference_tested_wgrad_plans():
+    """Keys every OP_CONV3_WGRAD op of the surveyed step programs by tests/step_programs.py _wgrad_plan_key -- the kernel_name string + the
+    class of the plan mtbc_conv3x3_wgrad_plan reports for the op's own arguments: how the kernel walks its pixels and what reduces its
+    partials, which plan_wgrad decides from N and the map size -- : each must be the plan key of a weight-gradient call that a test of this
+    file checks against fp64.  A change of plan_wgrad, of the batch or of a map size that gives a launch a plan class no case has fails here,
+    named with its program, plan key and shape.  The print-out lists every weight-gradient launch under its plan key with the table that
+    answers for it (profiles/conv3x3_step_keys.txt)."""
+    answers = {}
+    for table, keys in _wgrad_plan_tables().items():
+        for key in keys:
+            answers.setdefault(key, table)
+    assert_all_tested("conv3x3-wgrad-plan", set(answers), _wgrad_plan_surveys(), required=(W_,), answers=answers)
+
+
+def test_wgrad_plan_cases_are_all_needed():
+    """Every row of WGRAD_PLAN_CASES makes a plan key that a surveyed program launches, that no older table makes and that no other row
+    makes: no dead and no double rows, and deleting one fails the guard above."""
+    launched = set().union(*(s.seen["conv3x3-wgrad-plan"] for s in _wgrad_plan_surveys()))
+    older, rows, bad = _older_wgrad_plan_keys(), {}, []
+    for case in WGRAD_PLAN_CASES:
+        rows.setdefault((W_, _wgrad_plan_key(ops.conv3x3_case_args(W_, *case[:5], **case[5]))), []).append(case)
+    for key, cases in rows.items():
+        if len(cases) > 1:
+            bad.append(f"\n  {len(cases)} rows make {key}: {cases}")
+        if key not in launched or key in older:
+            bad.append(f"\n  {'no program launches' if key not in launched else 'an older table already makes'} {key} of row {cases[0]}")
+    print(f"{len(WGRAD_PLAN_CASES)} rows, {len(rows)} plan keys, {len(launched)} launched, {len(older)} made by the older tables")
+    assert WGRAD_PLAN_CASES and not bad, "rows of WGRAD_PLAN_CASES that are not needed:" + "".join(bad)
 
 
 # ------------------------------------------------------------------ the InstanceNorm + LeakyReLU launches of the step programs, element by element

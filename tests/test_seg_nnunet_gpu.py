@@ -342,7 +342,7 @@ def _keys_outside(seg, allowed):
     return extra
 
 
-_NAMED = ("conv3x3", "InstanceNorm", "transposed-convolution", "small-op", "loss")      # the families whose keys carry a kernel-name string
+_NAMED = ("conv3x3", "conv3x3-wgrad-plan", "InstanceNorm", "transposed-convolution", "small-op", "loss")      # the families whose keys carry a kernel-name string
 
 
 def _kernel_instances(survey):
@@ -383,7 +383,7 @@ def test_seg_only_programs_launch_only_reference_tested_instances():
     import test_loss_launches_gpu as LOSS
     import test_ops_gpu as OPS
     _, seg = _surveys()
-    tested = {"conv3x3": OPS._reference_tested_conv3x3_keys(), "InstanceNorm": OPS._reference_tested_instnorm_keys(),
+    tested = {"conv3x3": OPS._reference_tested_conv3x3_keys(), "conv3x3-wgrad-plan": OPS._reference_tested_wgrad_plan_keys(), "InstanceNorm": OPS._reference_tested_instnorm_keys(),
               "transposed-convolution": OPS._reference_tested_convT_keys(), "small-op": OPS._reference_tested_small_op_keys(),
               "layout": OPS._reference_tested_layout_keys(), "loss": LOSS._reference_tested_loss_keys()}
     extra = _keys_outside(seg, tested)

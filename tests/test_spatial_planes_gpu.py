@@ -467,6 +467,14 @@ CONV3_CASES = [
     (W_, 3, [7], 24, 20, 48, dict(bias=False)),        # conv3x3_wgrad_direct_kernel + splitk_reduce (ragged_rows, ragged_k)  [N x 7 -> 24 in MTUNetPlusPlus bf16 / f16 / f32]
     (W_, 3, [7], 32, 20, 48, dict(bias=False)),        # conv3x3_wgrad_direct_kernel + splitk_reduce (ragged_k)  [64 x 7 -> 32 @ 256 x 256 in MTnnUNet bf16]
 ]
+# (N, segs, Cout, H, W, mode) as in WGRAD_PLAN_CASES of tests/test_ops_gpu.py, and by its shape rule: the plan keys (tests/step_programs.py
+# _wgrad_plan_key) of the 7-channel first cell's weight gradient that no table of that file makes -- the direct kernel deals a batch of 16
+# images one per split and a larger one two or four (`images>1`).  In brackets: the launch of the step.
+WGRAD_PLAN_CASES = [
+    (24, [7], 8, 8, 8, dict(bias=False)),              # conv3x3_wgrad_direct_kernel + splitk_reduce (images>1, splitk_reduce<4> x2)  [32 x 7 -> 24 @ 256 x 256 in MTUNetPlusPlus bf16 / f32, 64 x 7 -> 32 in MTnnUNet bf16]
+    (8, [7], 8, 8, 8, dict(bias=False)),               # conv3x3_wgrad_direct_kernel + splitk_reduce (splitk_reduce<4> x2)  [16 x 7 -> 24 @ 512 x 512 in MTUNetPlusPlus f16]
+]
+PLAN = "conv3x3-wgrad-plan"
 # (backward, N, C, H, W, mode) as in INORM_CASES.  The team size follows the plane (T = 32 at 256 x 256, 128 at 512 x 512); reserve_cus leaves one
 # team resident so that two items take two rounds, as that file's backward team cases do.  The fp32 backward: the largest plane of the register
 # kernel (65000 elements) without parameters, the smallest above it (66560) with them.
@@ -495,6 +503,11 @@ def test_seven_channel_conv3x3_launches_match_fp64(case):
     _ops_gpu().test_conv3x3_step_instances_match_fp64(case)
 
 
+@pytest.mark.parametrize("case", WGRAD_PLAN_CASES, ids=lambda c: _ops_gpu()._wgrad_plan_case_id(c))
+def test_seven_channel_wgrad_plans_match_fp64(case):
+    _ops_gpu().test_conv3x3_wgrad_plan_cases_match_fp64(case)
+
+
 @pytest.mark.parametrize("case", INORM_CASES, ids=lambda c: _ops_gpu()._inorm_case_id(c))
 def test_seven_channel_instnorm_launches_match_fp64(case):
     _ops_gpu().test_instnorm_step_instances_match_fp64(case)
@@ -511,6 +524,8 @@ def _own_keys():
     for case in CONV3_CASES:
         op, N, segs, Cout, H, W, mode = case
         own["conv3x3"].setdefault((op, SP._conv3_key(ops.conv3x3_case_args(op, N, segs, Cout, H, W, **mode), op)), []).append(case)
+    for case in WGRAD_PLAN_CASES:
+        own[PLAN].setdefault((W_, SP._wgrad_plan_key(ops.conv3x3_case_args(W_, *case[:5], **case[5]))), []).append(case)
     for case in INORM_CASES:
         for op, _, key in OPS._inorm_case_calls(case):
             own["InstanceNorm"].setdefault((op, key), []).append(case)
@@ -519,8 +534,8 @@ def _own_keys():
 
 def _older_keys():
     OPS = _ops_gpu()
-    return {"conv3x3": OPS._reference_tested_conv3x3_keys(), "InstanceNorm": OPS._reference_tested_instnorm_keys(),
-            "transposed-convolution": OPS._reference_tested_convT_keys(), "small-op": OPS._reference_tested_small_op_keys(),
+    return {"conv3x3": OPS._reference_tested_conv3x3_keys(), PLAN: OPS._reference_tested_wgrad_plan_keys(),
+            "InstanceNorm": OPS._reference_tested_instnorm_keys(), "transposed-convolution": OPS._reference_tested_convT_keys(), "small-op": OPS._reference_tested_small_op_keys(),
             "layout": OPS._reference_tested_layout_keys(), "loss": _loss_gpu()._reference_tested_loss_keys()}
 
 
@@ -559,5 +574,5 @@ def test_seven_channel_rows_are_all_needed():
             if not any(k in launched and k not in old[family] for k in ks):
                 bad.append(f"\n  {family}: no program launches, or an older table already makes, {ks} of row {row}")
         print(f"{family}: {len(rows)} rows, {len(keys)} keys")
-    assert len(CONV3_CASES) + len(INORM_CASES) == sum(len({repr(c) for cs in keys.values() for c in cs}) for keys in _own_keys().values())
+    assert len(CONV3_CASES) + len(WGRAD_PLAN_CASES) + len(INORM_CASES) == sum(len({repr(c) for cs in keys.values() for c in cs}) for keys in _own_keys().values())
     assert not bad, "rows of this module that are not needed:" + "".join(bad)

@@ -186,6 +186,114 @@ def test_conv3_collector_keys_by_kind_and_arguments_and_names_the_segments():
     assert f"[{D_}]" in str(e.value)
 
 
+# ---- the weight-gradient plan key: the full name + the class of the plan mtbc_conv3x3_wgrad_plan reports (host only, dummy pointers)
+PLAN = "conv3x3-wgrad-plan"
+_WB = dict(compute=1, c8=True, bias=False)
+
+
+def _plan(N, segs, Cout, H, W, **mode):
+    return SP._wgrad_plan_key(ops.conv3x3_case_args(W_, N, list(segs), Cout, H, W, **mode))
+
+
+@pytest.mark.parametrize("flag,without,with_", [
+    # the tile-walking kernels: 32 x 32 channel blocks (bf16, channel-blocked) ...
+    ("even", (3, (192, 192), 192, 44, 64, _WB), (8, (48,), 96, 128, 128, _WB)),             # 66 tiles in 14 splits of 5 | 1024 tiles dealt over 168 splits
+    ("fixed", (8, (48,), 96, 128, 128, _WB), (3, (192, 192), 192, 44, 64, _WB)),
+    ("tiles=1", (4, (96,), 96, 64, 64, _WB), (3, (24,), 24, 20, 48, _WB)),                  # 128 tiles in 64 splits | 30 tiles in 30 splits
+    ("tiles=2", (3, (24,), 24, 20, 48, _WB), (4, (96,), 96, 64, 64, _WB)),
+    ("tiles>=3", (4, (96,), 96, 64, 64, _WB), (3, (192, 192), 192, 44, 64, _WB)),
+    ("ragged", (4, (96,), 96, 64, 64, _WB), (3, (192, 192), 192, 44, 64, _WB)),             # 13 splits of 5 tiles and one of 1
+    ("ragged", (32, (840,), 8, 64, 64, _WB), (8, (48,), 96, 128, 128, _WB)),                # dealt evenly: 1024 / 32 | 1024 / 168 = 6 or 7
+    ("crosses", (4, (96,), 96, 64, 64, _WB), (3, (192, 192), 192, 44, 64, _WB)),            # 22 tiles an image in shares of 5
+    # ... and the fp32 kernel on 8 x 8 maps: a tile is two images
+    ("odd_N", (2, (192,), 192, 8, 8, dict(bias=False)), (3, (192,), 192, 8, 8, dict(bias=False))),
+    # the wide-block kernel
+    ("segs=1", (8, (24, 24, 24), 24, 20, 128, _WB), (8, (192,), 96, 20, 384, _WB)),         # 96 strips fill the block budget: one block per strip
+    ("segs>1", (8, (192,), 96, 20, 384, _WB), (8, (24, 24, 24), 24, 20, 128, _WB)),
+    ("short_last_seg", (8, (24, 24, 24), 24, 256, 256, _WB), (8, (24, 24, 24), 24, 20, 128, _WB)),       # 5 steps in segments of 2
+    ("img8", (3, (24, 24, 48), 24, 20, 128, _WB), (8, (24, 24, 24), 24, 20, 128, _WB)),
+    ("steps>=ring", (8, (24, 24, 24), 24, 20, 128, _WB), (8, (24, 24, 24), 24, 256, 256, _WB)),
+    ("steps<ring", (8, (24, 24, 24), 24, 256, 256, _WB), (8, (24, 24, 24), 24, 20, 128, _WB)),
+    ("ciblocks>1", (3, (32, 32), 32, 20, 128, _WB), (3, (24, 24, 48), 24, 20, 128, _WB)),
+    ("ragged_cit", (3, (24, 24, 48), 24, 20, 128, _WB), (3, (24, 24, 24, 24, 48), 24, 20, 128, _WB)),      # 9 input tiles in blocks of 5 and 4
+    # the image-tile kernel
+    ("images=1", (16, (384,), 384, 16, 16, _WB), (3, (384,), 384, 16, 16, _WB)),
+    ("images=2", (3, (384,), 384, 16, 16, _WB), (3, (512,), 512, 16, 16, _WB)),
+    ("images>=3", (3, (384,), 384, 16, 16, _WB), (16, (384,), 384, 16, 16, _WB)),           # 16 images in 6 ranges of 3: the last one 1
+    ("short_last_range", (3, (384,), 384, 16, 16, _WB), (16, (384,), 384, 16, 16, _WB)),
+    ("ciblocks>1", (5, (64,), 40, 16, 16, _WB), (3, (384,), 384, 16, 16, _WB)),
+    # the stem, the small-Cin kernel, the direct kernel
+    ("bands=1", (3, (1,), 24, 128, 128, _WB), (3, (1,), 24, 20, 48, _WB)),
+    ("bands=4", (3, (1,), 24, 20, 48, _WB), (3, (1,), 24, 128, 128, _WB)),
+    ("bands=16", (3, (1,), 24, 128, 128, _WB), (2, (1,), 24, 256, 256, _WB)),
+    ("bands=4", (3, (1,), 24, 20, 48, dict(bias=False)), (4, (1,), 24, 256, 256, dict(bias=False))),
+    ("images>1", (8, (7,), 8, 8, 8, dict(bias=False)), (24, (7,), 8, 8, 8, dict(bias=False))),
+    # the reduction
+    ("store", (12, (384, 384, 384), 512, 16, 16, dict(compute=1, c8=True)), (12, (384, 384, 384), 512, 16, 16, _WB)),
+    ("fixup levels=2", (2, (192,), 192, 32, 32, _WB), (2, (192,), 192, 32, 32, dict(_WB, in_kernel_reduce=True))),
+    ("fixup levels=3", (2, (192,), 192, 32, 32, dict(_WB, in_kernel_reduce=True)), (8, (48,), 96, 128, 128, dict(_WB, in_kernel_reduce=True))),
+    ("fixup ragged_group", (2, (192,), 192, 32, 32, dict(_WB, in_kernel_reduce=True)), (3, (192, 192), 192, 44, 64, dict(_WB, in_kernel_reduce=True))),      # 16 | 14 leaves in groups of 4
+    ("splitk_reduce<4> x2+x1", (8, (48,), 96, 128, 128, _WB), (3, (192, 192), 192, 44, 64, _WB)),          # 14 splits | 168
+    ("splitk_reduce<16> x8+x2+x1", (3, (192, 192), 192, 44, 64, _WB), (8, (48,), 96, 128, 128, _WB)),
+    ("splitk_reduce<64, 16> x8", (3, (1,), 24, 128, 128, _WB), (32, (1,), 8, 128, 512, _WB)),              # 512 splits of 72 floats
+])
+def test_wgrad_plan_key_flag_follows_the_arguments(flag, without, with_):
+    a, b = _plan(*without[:5], **without[5]), _plan(*with_[:5], **with_[5])
+    assert a[0].split("<")[0] == b[0].split("<")[0], (a, b)          # the same kernel family: the class is what differs
+    assert flag not in a[1] and flag in b[1], (a, b)
+
+
+def test_splitk_reduce_phases_are_the_loops_of_the_kernel():
+    ph = SP._splitk_reduce_phases
+    assert ph(1, 4) == ["x1"] and ph(4, 4) == ["x1"] and ph(5, 4) == ["x2", "x1"] and ph(8, 4) == ["x2"]
+    assert ph(28, 4) == ["x2", "x1"] and ph(29, 4) == ["x8", "x2", "x1"] and ph(32, 4) == ["x8"]          # the first round of 8 rows: nsplit > 7 G
+    assert ph(112, 16) == ["x2", "x1"] and ph(128, 16) == ["x8"] and ph(168, 16) == ["x8", "x2", "x1"] and ph(512, 64) == ["x8"]
+
+
+def test_wgrad_plan_key_carries_the_name_and_not_the_argument_flags():
+    name, flags = _plan(3, (24, 24, 48), 24, 20, 128, **_WB)
+    assert name == "conv3x3_wgrad_c8w_kernel<false, 2, false> + splitk_reduce" == SP._conv3_key(_c3(W_, N=3, segs=(24, 24, 48), Cout=24, H=20, W=128, **_WB), W_)[0]
+    assert flags == ("segs>1", "short_last_seg", "steps<ring", "ciblocks>1", "splitk_reduce<16> x2+x1")
+    # segments, strides and the accumulate flag are _conv3_key's business: the plan reads none of them
+    assert _plan(3, (96,), 24, 20, 128, **_WB) == (name, flags) == _plan(3, (24, 24, 48), 24, 20, 128, **_WB, accumulate_dw=True)
+    a = ops.conv3x3_case_args(W_, 3, [24, 24, 48], 24, 20, 128, **_WB)
+    a.in_[1].batch_stride += 8 * 20 * 128
+    assert SP._wgrad_plan_key(a) == (name, flags)
+
+
+def test_wgrad_plan_key_raises_on_a_kernel_family_it_does_not_know(monkeypatch):
+    monkeypatch.setattr(ops, "conv3x3_kernel_name", lambda a, op: "conv3x3_wgrad_new_kernel<1> + splitk_reduce")
+    with pytest.raises(AssertionError, match="does not know the kernel family"):
+        _plan(3, (24,), 24, 20, 48, **_WB)
+
+
+def test_wgrad_plan_collector_keys_every_wgrad_op_once_and_the_message_names_program_key_and_shape():
+    big, small, fw = _mk(W_), _mk(W_), _mk(F_)
+    big.u.conv3, small.u.conv3 = _c3(W_, N=8, segs=(48,), Cout=96, H=128, W=128, **_WB), _c3(W_, N=3, segs=(16, 8), Cout=24, H=20, W=48, **_WB)
+    fw.u.conv3 = _c3(F_, **_BF, bias=False)
+    s = _survey("wgrad plan", {"fwd": [fw], "bwd": [big, small, small]})
+    kb, ks = (W_, SP._wgrad_plan_key(big.u.conv3)), (W_, SP._wgrad_plan_key(small.u.conv3))
+    assert s.seen[PLAN] == {kb: (W_, (8, 48, 96, 128, 128, (48,))), ks: (W_, (3, 24, 24, 20, 48, (16, 8)))}
+    assert s.launches[PLAN] == {kb: [(8, 48, 96, 128, 128, (48,))], ks: [(3, 24, 24, 20, 48, (16, 8))] * 2}          # every op under exactly one key
+    assert kb[1][1][0] == "even" and ks[1][1][:2] == ("fixed", "tiles=1") and kb[1][0] == ks[1][0]          # one kernel instance, two plans
+    SP.assert_all_tested(PLAN, {kb, ks}, [s], required=(W_,), answers={kb: "TABLE_A", ks: "TABLE_B"})
+    with pytest.raises(AssertionError) as e:
+        SP.assert_all_tested(PLAN, {ks}, [s], required=(W_,))
+    msg = str(e.value)
+    assert "('hand-made', 'wgrad plan', 0, 0)" in msg and "'even', 'tiles>=3', 'ragged'" in msg and "(8, 48, 96, 128, 128, (48,))" in msg
+    assert "tiles=1" not in msg
+
+
+def test_wgrad_plan_listing_names_every_launch_and_its_table(capsys):
+    wg = _mk(W_)
+    wg.u.conv3 = _c3(W_, N=3, segs=(24,), Cout=24, H=20, W=48, **_WB)
+    s = _survey("wgrad listing", {"bwd": [wg, wg]})
+    key = (W_, SP._wgrad_plan_key(wg.u.conv3))
+    SP.assert_all_tested(PLAN, {key}, [s], answers={key: "CONV3_STEP_CASES"})
+    out = capsys.readouterr().out
+    assert "<- CONV3_STEP_CASES" in out and out.count("at (3, 24, 24, 20, 48, (24,))") == 2
+
+
 # ---- the nearest 2x up-sampling key: the launch string + the strided tensors + acc_dx (hand-made ops, dummy pointers)
 UF_, UB_ = L.OP_UPSAMPLE2_FWD, L.OP_UPSAMPLE2_BWD
 _UP = (3, 24, 8, 12)          # N, C, H, W of the input: dense x / dx = 2304 elements an image, y / dy = 9216
