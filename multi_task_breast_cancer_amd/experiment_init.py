@@ -1,5 +1,5 @@
 """String -> object factory with the reference's names and signatures (src/utils/experiment_init.py:130-318),
-restricted to the multi-task training path, the single-task nnUNet segmentation baseline and the single-task classifiers.  Unknown names raise
+restricted to the multi-task training path, the single-task nnUNet and UnetPlusPlus segmentation models and the single-task classifiers.  Unknown names raise
 ValueError (the reference silently builds an empty nn.Module, experiment_init.py:160-163 -- stricter here)."""
 from __future__ import annotations
 
@@ -11,7 +11,7 @@ import torch
 from torch.optim.lr_scheduler import CosineAnnealingLR, ReduceLROnPlateau
 
 from .criterions import DiceFocalLoss, DiceLoss, FocalLoss
-from .nets import MTnnUNet, MTUNetPlusPlus, Multi_BTSUNet, UNetPlusPlusClassifier, nnUNet, nnUNetClassifier
+from .nets import BasicUnetPlusPlus, MTnnUNet, MTUNetPlusPlus, Multi_BTSUNet, UNetPlusPlusClassifier, nnUNet, nnUNetClassifier
 from .optim import FusedAdam, FusedAdamW, FusedSGD
 
 
@@ -48,13 +48,17 @@ def _describe(model: torch.nn.Module, save_folder) -> None:
 
 def init_segmentation_model(architecture: str, sequences: int = 1, regions: int = 1, width: int = 48, save_folder: Path = None,
                             deep_supervision: bool = False) -> torch.nn.Module:
-    """experiment_init.py:26-78, the single-task factory: 'nnUNet' (`nnUNet2021`, BASELINE.json configs[0]) is on HIP.  `width` and
-    `deep_supervision` are ignored, as the reference ignores them for this architecture (:62-63: it always returns its four heads)."""
+    """experiment_init.py:26-78, the single-task factory: 'nnUNet' (`nnUNet2021`, BASELINE.json configs[0]) and 'UnetPlusPlus' (MONAI's
+    BasicUNetPlusPlus at its default widths, :61-63) are on HIP.  nnUNet ignores `width` and `deep_supervision`, as the reference ignores them
+    for it (it always returns its four heads); UnetPlusPlus ignores `width` and honours `deep_supervision`, as the reference does."""
     logging.info(f"Creating {architecture} model")
     logging.info(f"The model will be fed with {sequences} sequences")
-    if architecture != "nnUNet":
-        raise ValueError(f"The segmentation model selected ({architecture!r}) is not on the MI355X hot path. Choose 'nnUNet'.")
-    model = nnUNet(sequences=sequences, regions=regions)
+    if architecture == "nnUNet":
+        model = nnUNet(sequences=sequences, regions=regions)
+    elif architecture == "UnetPlusPlus":
+        model = BasicUnetPlusPlus(spatial_dims=2, in_channels=sequences, out_channels=regions, deep_supervision=deep_supervision)
+    else:
+        raise ValueError(f"The segmentation model selected ({architecture!r}) is not on the MI355X hot path. Choose 'nnUNet' or 'UnetPlusPlus'.")
     _describe(model, save_folder)
     return model
 

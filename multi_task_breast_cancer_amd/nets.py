@@ -1,6 +1,6 @@
-"""MTnnUNet, MTUNetPlusPlus, Multi_BTSUNet, the single-task nnUNet and the single-task classifiers as thin nn.Module shells over HIP step programs.
+"""MTnnUNet, MTUNetPlusPlus, Multi_BTSUNet, the single-task nnUNet and BasicUnetPlusPlus and the single-task classifiers as thin nn.Module shells over HIP step programs.
 
-Drop-in surface: `model(x) -> (logits, segs)` (lists under deep supervision; nnUNet: the list of heads alone; nnUNetClassifier /
+Drop-in surface: `model(x) -> (logits, segs)` (lists under deep supervision; nnUNet / BasicUnetPlusPlus: the list of heads alone; nnUNetClassifier /
 UNetPlusPlusClassifier: the (N, n_classes) tensor alone), `.parameters()`,
 `.state_dict()` with the reference's key names (src/models/multitask/MTnnUNet.py:79-132,
 MTUNetPlusPlus.py:47-87 on MONAI 1.3.0 blocks), `.train()`, `.to()`.  All arithmetic runs in
@@ -11,6 +11,7 @@ data-parallel all-reduce works on contiguous buckets; each nn.Parameter is a vie
 """
 from __future__ import annotations
 
+import functools
 import os
 
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
@@ -195,10 +196,10 @@ def _nnunet_classifier_params(sequences: int, n_classes: int) -> List[Tuple[str,
     return out
 
 
-def _unetpp_classifier_params(in_ch: int, n_classes: int) -> List[Tuple[str, torch.Tensor]]:
+def _unetpp_classifier_params(in_ch: int, n_classes: int, features: Sequence[int] = UNETPP_FEATURES) -> List[Tuple[str, torch.Tensor]]:
     """UNetPlusPlusClassifier (src/models/classification/UnetPlusPlus_Classifier.py): conv_0_0 .. conv_4_0, upcat_3_1, process_level_3, classifier,
     drawn in the constructor's order with MONAI 1.3.0's TwoConv / Down / UpCat (as `_unetpp_params` restates them)."""
-    f = UNETPP_FEATURES
+    f = tuple(features)
     out: List[Tuple[str, torch.Tensor]] = []
 
     def convolution(name, cin, cout):
@@ -225,8 +226,10 @@ def _unetpp_classifier_params(in_ch: int, n_classes: int) -> List[Tuple[str, tor
     return out
 
 
-def _unetpp_params(in_ch: int, out_ch: int, n_classes: int) -> List[Tuple[str, torch.Tensor]]:
-    f = UNETPP_FEATURES
+def _unetpp_params(in_ch: int, out_ch: int, n_classes: int, features: Sequence[int] = UNETPP_FEATURES) -> List[Tuple[str, torch.Tensor]]:
+    """MTUNetPlusPlus in its constructor's draw order; n_classes = 0 is MONAI's BasicUNetPlusPlus (`architecture: UnetPlusPlus`), which is
+    everything MTUNetPlusPlus creates before its classification head: the draw stops behind final_conv_0_4."""
+    f = tuple(features)
     out: List[Tuple[str, torch.Tensor]] = []
 
     def convolution(name, cin, cout):       # MONAI Convolution: conv(k3, bias) + ADN(N: InstanceNorm affine)
@@ -260,6 +263,8 @@ def _unetpp_params(in_ch: int, out_ch: int, n_classes: int) -> List[Tuple[str, t
     for j, c in ((1, f[0]), (2, f[0]), (3, f[0]), (4, f[5])):
         wt, b = _draw_conv(c, out_ch, 1, True)
         out += [(f"final_conv_0_{j}.weight", wt), (f"final_conv_0_{j}.bias", b)]
+    if not n_classes:
+        return out
     two_conv("process_level_3.convs", f[3], f[4])
     two_conv("classifier.0", f[4] * 3, 512)
     wt, b = _draw_linear(512, 256)
@@ -348,10 +353,17 @@ def _graph_nnunet_classifier(plan: StepPlan, x: Act):
     return _graph_nnunet_parts(plan, x, True, segmentation=False)
 
 
-def _graph_unetpp(plan: StepPlan, x: Act, segmentation: bool = True):
+def _graph_unetpp(plan: StepPlan, x: Act, segmentation: bool = True, classifier: bool = True, features: Sequence[int] = UNETPP_FEATURES,
+                  heads: Sequence[int] = (1, 2, 3, 4)):
     """MTUNetPlusPlus; segmentation=False is UNetPlusPlusClassifier (UnetPlusPlus_Classifier.py): conv_*_0, upcat_3_1, process_level_3 (planned once
-    over the batch pair, as here) and the classifier, raw logits (its softmax is commented out), an empty list of heads."""
-    f = UNETPP_FEATURES
+    over the batch pair, as here) and the classifier, raw logits (its softmax is commented out), an empty list of heads.
+    classifier=False is BasicUnetPlusPlus (MONAI's BasicUNetPlusPlus.forward): the trunk and the heads alone -- no process_level_3, no batch pair
+    (x_3_0 is pooled for conv_4_0 only), no classifier, GAP or Linear; logits is None.  Of the heads, those whose weights are never-trained
+    parameters of the model (final_conv_0_1 .. 0_3 without deep supervision) are left out of `heads` and not emitted: the list is [output_0_4]."""
+    f = tuple(features)
+    if not classifier and (x.H % 16 or x.W % 16):
+        raise ValueError(f"BasicUnetPlusPlus takes inputs whose sides are multiples of 16, got {x.H} x {x.W}: four poolings, and MONAI's UpCat "
+                         f"replicate-pads an up-sampled map that came out smaller than its skip, which is not planned here")
 
     def convolution(inputs, cout, name):
         return plan.conv_cell(inputs, cout, f"{name}.conv.weight", f"{name}.conv.bias", f"{name}.adn.N.weight",
@@ -397,16 +409,19 @@ def _graph_unetpp(plan: StepPlan, x: Act, segmentation: bool = True):
     # process_level_3 (shared weights) is applied to pool(x_3_0) AND pool(x_3_1) (MTUNetPlusPlus.py:79,128): planned ONCE over their
     # batch concatenation (InstanceNorm is per sample: exact).  The two pooled tensors are the halves of one 2N-image tensor; conv_4_0
     # reads the first half (x_3_0 is pooled once, for both of its consumers)
-    pl3_in, (p30, p31) = plan.batch_pair("process_level_3.in", f[3], x30.H // 2, x30.W // 2)
-    x40 = two_conv([plan.maxpool(x30, "conv_4_0.pool", out=p30)], f[4], "conv_4_0.convs")
+    if classifier:
+        pl3_in, (p30, p31) = plan.batch_pair("process_level_3.in", f[3], x30.H // 2, x30.W // 2)
+        x40 = two_conv([plan.maxpool(x30, "conv_4_0.pool", out=p30)], f[4], "conv_4_0.convs")
+    else:
+        x40 = down(x30, f[4], "conv_4_0")
     x31 = upcat(x40, [x30], f[3], "upcat_3_1")
     x22 = upcat(x31, [x20, x21], f[2], "upcat_2_2")
     x13 = upcat(x22, [x10, x11, x12], f[1], "upcat_1_3")
     x04 = upcat(x13, [x00, x01, x02, x03], f[5], "upcat_0_4", halves=False)
     regions = plan.pv("final_conv_0_1.weight").shape[0]
     outs = [plan.conv1x1(t, regions, f"final_conv_0_{j}.weight", f"final_conv_0_{j}.bias", f"final_conv_0_{j}")
-            for j, t in ((1, x01), (2, x02), (3, x03), (4, x04))]
-    return head(x30, x40, x31), outs
+            for j, t in ((1, x01), (2, x02), (3, x03), (4, x04)) if j in heads]
+    return (head(x30, x40, x31) if classifier else None), outs
 
 
 def _graph_unetpp_classifier(plan: StepPlan, x: Act):
@@ -755,6 +770,35 @@ class nnUNet(HipMultiTaskNet):
     def __init__(self, sequences: int, regions: int, force_direct: bool = False):
         super().__init__(_nnunet_params(sequences, regions), sequences, True, _graph_nnunet, force_direct)
         self.n_classes = 0
+
+
+BASIC_UNETPP_FEATURES = (32, 32, 64, 128, 256, 32)   # MONAI's BasicUNetPlusPlus: its default `features`, which experiment_init.py:61-63 leaves as they are
+UNETPP_SEG_UNTRAINED = tuple(f"final_conv_0_{j}.{p}" for j in (1, 2, 3) for p in ("weight", "bias"))
+
+
+class BasicUnetPlusPlus(HipMultiTaskNet):
+    """`architecture: UnetPlusPlus` of src/training_segmentation.py, the single-task segmentation row of the U-Net++ backbone: MONAI's
+    BasicUNetPlusPlus (src/utils/experiment_init.py:61-63), which is MTUNetPlusPlus without its classification head, at MONAI's default widths.
+    `forward(x)` always returns a list, as MONAI's does: the four heads under deep supervision, [output_0_4] without; there are no class
+    logits anywhere (n_classes == 0).  Without deep supervision final_conv_0_1 .. 0_3 are parameters the forward's result never reads
+    (`untrained`): their `.grad` stays None and no optimizer moves them.  Every width is a multiple of 8 (the channel-blocked 16-bit layout)."""
+    architecture = "UnetPlusPlus"
+
+    def __init__(self, spatial_dims: int = 2, in_channels: int = 1, out_channels: int = 1,
+                 features: Sequence[int] = BASIC_UNETPP_FEATURES, deep_supervision: bool = False, force_direct: bool = False):
+        if spatial_dims != 2:
+            raise ValueError("only spatial_dims=2 is on the hot path")
+        f = tuple(features)
+        if len(f) != 6 or any(isinstance(c, bool) or not isinstance(c, int) or c <= 0 for c in f):
+            raise ValueError(f"features must be six positive integers, got {features!r}")
+        if any(c % 8 for c in f):
+            raise ValueError(f"every width must be a multiple of 8 (the channel-blocked 16-bit layout holds channels in groups of 8), got {f}")
+        ds = bool(deep_supervision)
+        graph = functools.partial(_graph_unetpp, classifier=False, features=f, heads=(1, 2, 3, 4) if ds else (4,))
+        super().__init__(_unetpp_params(in_channels, out_channels, 0, f), in_channels, ds, graph, force_direct,
+                         untrained=() if ds else UNETPP_SEG_UNTRAINED)
+        self.n_classes = 0
+        self.features = f
 
 
 class nnUNetClassifier(HipMultiTaskNet):

@@ -322,7 +322,7 @@ def _check_heads(model, n_classes: int, cls_criterion: str, focal_weight, owner:
 
 
 def is_seg_only(model) -> bool:
-    """A single-task segmentation model (nets.nnUNet): no classification head, no class logits anywhere in its plans."""
+    """A single-task segmentation model (nets.nnUNet, nets.BasicUnetPlusPlus): no classification head, no class logits anywhere in its plans."""
     return getattr(model, "n_classes", None) == 0
 
 
