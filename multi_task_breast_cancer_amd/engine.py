@@ -35,10 +35,6 @@ _IN_KERNEL_SPLITK = False   # see _conv_cell_backward: the in-kernel split-K red
 _DPARAM_BATCH = 12          # cells per batched InstanceNorm parameter-gradient reduction (36 launches of 5 us -> 3)
 
 
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
 @dataclass
 class Act:
     """An NCHW activation living in its own contiguous arena tensor (virtual concat = list of Acts)."""
@@ -311,7 +307,7 @@ class StepPlan:
             self.fwd_ops.append(a.pack_op)
         return a.c8
 
-    def _coop_state(self) -> int:
+    def _coop_state(self) -> torch.Tensor:
         """The zeroed mailbox block of the cooperative InstanceNorm kernels.  ONE per model, shared by every step plan the
         model compiles (training batch, short last batch, evaluation batch: they run one after the other on one stream),
         so that the sticky error word any of them sets is the word `check_nan()` / `result()` read, whichever plan ran
@@ -322,7 +318,7 @@ class StepPlan:
             else:
                 self._coop_buf = torch.zeros(self.lib.mtbc_instnorm_coop_state_bytes() // 4, dtype=torch.int32, device=self.dev)
             self.keep.append(self._coop_buf)
-        return self._coop_buf.data_ptr()
+        return self._coop_buf
 
     def coop_error_word(self) -> Optional[torch.Tensor]:
         """Device view (1 x int32) of the sticky error word of this plan's cooperative kernels, or None when the plan has
@@ -364,24 +360,25 @@ class StepPlan:
         s.ready_at = len(self.bwd_ops)      # index of the op about to be appended
         return acc
 
-    def _segs(self, arr, acts: Sequence[Act], grads: bool = False, g16: bool = False) -> None:
-        for i, a in enumerate(acts):
+    def _segs(self, acts: Sequence[Act], c8: bool = False, grads: bool = False, g16: bool = False) -> Tuple[list, List[int]]:
+        """The segment tensors of a conv cell's 3x3 op and their accumulate codes: the activations (channel-blocked copies with c8), or with
+        `grads` where the next contribution to each gradient goes."""
+        out = []
+        for a in acts:
             if grads and g16 and a.grad16_ok and a.readers == 1 and not a.grad_written:
                 # the only gradient this tensor will ever get, and its reader (the ConvT backward) rounds it to 16 bits
                 # while loading: written as 16-bit planes by this dgrad launch (mtbc_seg.accumulate = 2)
                 a.grad16 = self.alloc(*a.data.shape, dtype=torch.int16)
                 a.grad_written = True
-                arr[i].ptr = a.grad16.data_ptr()
-                arr[i].accumulate = 2
+                out.append((a.grad16, 2))
             elif grads:
-                g, acc = self.grad_slot(a)
-                arr[i].ptr = g.data_ptr()
-                arr[i].accumulate = acc
+                out.append(self.grad_slot(a))
+            elif c8:
+                out.append((self.c8_of(a), 0))
             else:
-                arr[i].ptr = self._rd(a)
-                arr[i].accumulate = 0
-            arr[i].batch_stride = a.bstride
-            arr[i].channels = a.C
+                self._rd(a)
+                out.append((a.data, 0))
+        return [t for t, _ in out], [acc for _, acc in out]
 
     # ------------------------------------------------------------------ layers
     def conv_cell(self, inputs: Sequence[Act], cout: int, wname: str, bname: Optional[str],
@@ -398,21 +395,12 @@ class StepPlan:
         assert tuple(w.shape) == (cout, cin, 3, 3), (wname, tuple(w.shape), cout, cin)
         use_packed = cin % 8 == 0 and all(a.C % 8 == 0 for a in inputs)
         wp_f = wp_d = wp_d_op = None
-        if use_packed and self.compute:
-            # 16-bit operand images, re-converted from the fp32 master weights every step
-            wp_f, _ = self._pack_lp(w, cin, cout, 0)
+        if use_packed:
+            # fp32 images, or 16-bit operand images re-converted from the fp32 master weights every step
+            pack = self._pack_lp if self.compute else self._pack_f32
+            wp_f, _ = pack(w, cin, cout, 0)
             if any(a.needs_grad for a in inputs) and cout % 8 == 0:
-                wp_d, wp_d_op = self._pack_lp(w, cin, cout, 1)
-        elif use_packed:
-            wp_f = self.alloc(self.lib.mtbc_conv3x3_packed_elems(cin, cout))
-            op = _mk(L.OP_CONV3_PACK_FWD)
-            op.u.pack.w, op.u.pack.packed, op.u.pack.Cin, op.u.pack.Cout = w.data_ptr(), wp_f.data_ptr(), cin, cout
-            self.pack_ops.append(op)
-            if any(a.needs_grad for a in inputs) and cout % 8 == 0:
-                wp_d = self.alloc(self.lib.mtbc_conv3x3_packed_dgrad_elems(cin, cout))
-                op = _mk(L.OP_CONV3_PACK_DGRAD)
-                op.u.pack.w, op.u.pack.packed, op.u.pack.Cin, op.u.pack.Cout = w.data_ptr(), wp_d.data_ptr(), cin, cout
-                self.pack_ops.append(op)
+                wp_d, wp_d_op = pack(w, cin, cout, 1)
         y = self.new_act(out_name, cout, H, W, N=N)
         mean, rstd = self.alloc(N * cout), self.alloc(N * cout)
         self._tag += 1
@@ -434,11 +422,8 @@ class StepPlan:
         cell.old_mc = old_mc
         stem16 = bool(self.compute) and 1 <= cin <= L.STEM_MAX_CIN and not old_mc and len(inputs) == 1 and cout % 8 == 0 and not self.force_direct and W % 4 == 0 \
             and H >= 8 and W >= 8 and inputs[0].planar_valid and not inputs[0].needs_grad
-        z16 = False
-        if (c8_bwd or stem16) and not _NO_Z16 and not _NO_COOP:      # (the one-plane InstanceNorm kernels read fp32 planes)
-            q = L.InstNormArgs()
-            q.N, q.C, q.H, q.W, q.out16_type, q.z_layout, q.coop_reserve_cus = N, cout, H, W, self.compute, L.LAYOUT_C8, self.coop_reserve_cus
-            z16 = bool(self.lib.mtbc_instnorm_c8_supported(C.byref(q), 0)) and bool(self.lib.mtbc_instnorm_c8_supported(C.byref(q), 1))
+        # (the one-plane InstanceNorm kernels read fp32 planes)
+        z16 = (c8_bwd or stem16) and not _NO_Z16 and not _NO_COOP and self._c8_norm_ok(cell, False, z16=True) and self._c8_norm_ok(cell, True, z16=True)
         z = self.alloc(N, cout // 8, H * W, 8, dtype=torch.int16) if z16 else self.alloc(N, cout, H, W)
         # ... as fp16 also in the bf16 mode: a conv output in front of a norm is O(1), and fp16 keeps 11 significant bits of it in the
         # same 2 bytes (bf16: 8) -- measured on the held-out Dice of 3000-step runs (profiles/r02b_quality_sweep.md); the MFMA
@@ -457,44 +442,28 @@ class StepPlan:
             else:
                 a_.no_gather = True
 
-        op = self._cell_conv_op(cell, L.OP_CONV3_FWD)
-        if c8:
-            self._segs_c8(op.u.conv3.in_, inputs)
-            op.u.conv3.operand_layout = L.LAYOUT_C8
-        else:
-            self._segs(op.u.conv3.in_, inputs)
-        op.u.conv3.w_packed = _ptr(wp_f)
-        op.u.conv3.bias = _ptr(self.pv(bname)) if bname else None
-        op.u.conv3.out = z.data_ptr()
-        if old_mc:
-            op.u.conv3.force_direct = 1
+        ptrs = {"in": self._segs(inputs, c8=c8)[0], "w": w, "w_packed": wp_f, "bias": self.pv(bname) if bname else None, "out": z}
+        op = self._conv3_op(cell, L.OP_CONV3_FWD, inputs, ptrs, c8=c8, out_c8=z16, out_fp16=zf16, force_direct=self.force_direct or old_mc)
         stats_slots = 0
-        if stem16:
-            op.u.conv3.compute = self.compute
         if z16:
-            op.u.conv3.out_layout = L.LAYOUT_C8
-            if zf16:
-                op.u.conv3.out_type = 2
             # InstanceNorm statistics from the conv epilogue ({sum, sum of squares} of the stored values per wave): the
             # normalisation that follows is then one streaming pass with no reduction / team exchange of its own
-            stats_slots = int(self.lib.mtbc_conv3x3_stats_slots(C.byref(op.u.conv3)))
-            if stats_slots > 0:
+            stats_slots = max(0, int(self.lib.mtbc_conv3x3_stats_slots(C.byref(op.u.conv3))))
+            if stats_slots:
                 self._stat_users.append((op, "conv3"))
                 self._stat_bytes = max(self._stat_bytes, N * stats_slots * cout * 2 * 4)
         self.fwd_ops.append(op)
 
-        op = self._cell_norm_op(cell, L.OP_IN_FWD)
-        op.u.inorm.y, op.u.inorm.y_batch_stride = y.data.data_ptr(), y.bstride
-        y.in_op = op
-        if stats_slots > 0:
-            op.u.inorm.stats_slots = stats_slots
-            self._stat_users.append((op, "inorm"))
+        ptrs = dict(self._norm_ptrs(cell), y=y.data, stats_partial=None)
         if z16 or (self.compute and not _NO_COOP and not self.force_direct and cout % 8 == 0 and H * W >= _COOP_MIN_FWD
-                   and self.lib.mtbc_instnorm_c8_supported(C.byref(op.u.inorm), 0)):
+                   and self._c8_norm_ok(cell, False)):
             # 16-bit modes: the channel-group / cooperative kernel writes the channel-blocked operand tensor itself (and fp32 planes
             # only if something reads them -- decided in finalize(), when all consumers are known)
             y.c8 = self.alloc(N, cout // 8, H * W, 8, dtype=torch.int16)
-            op.u.inorm.y8, op.u.inorm.out16_type, op.u.inorm.coop_state = y.c8.data_ptr(), self.compute, self._coop_state()
+            ptrs.update(y8=y.c8, coop_state=self._coop_state())
+        op = y.in_op = self._norm_op(cell, False, ptrs, out="c8" if y.c8 is not None else "f32", planar=True, stats_slots=stats_slots)
+        if stats_slots:
+            self._stat_users.append((op, "inorm"))
         nb = self.lib.mtbc_instnorm_fwd_workspace(C.byref(op.u.inorm))      # > 0 only for planes larger than 64K elements
         if nb:
             self._need_ws(op, "inorm", nb)
@@ -512,38 +481,47 @@ class StepPlan:
         self.pack_ops.append(op)
         return t, op
 
+    def _pack_f32(self, wsrc: torch.Tensor, ci: int, co: int, dg: int) -> Tuple[torch.Tensor, L.Op]:
+        """The fp32 MFMA image of a weight tensor (forward image dg = 0, dgrad image dg = 1), rebuilt every step."""
+        t = self.alloc(self.lib.mtbc_conv3x3_packed_dgrad_elems(ci, co) if dg else self.lib.mtbc_conv3x3_packed_elems(ci, co))
+        op = _mk(L.OP_CONV3_PACK_DGRAD if dg else L.OP_CONV3_PACK_FWD)
+        op.u.pack.w, op.u.pack.packed, op.u.pack.Cin, op.u.pack.Cout = wsrc.data_ptr(), t.data_ptr(), ci, co
+        self.pack_ops.append(op)
+        return t, op
+
     def _wview(self, wsrc, dst, co, ci_total, off, cnt, mode, koff, K) -> None:
         op = _mk(L.OP_CONV3_WVIEW)
         v = op.u.wview
         v.w, v.dst, v.Cout, v.Cin, v.ci_off, v.ci_cnt, v.mode, v.k_off, v.K = wsrc.data_ptr(), dst.data_ptr(), co, ci_total, off, cnt, mode, koff, K
         self.wview_ops.append(op)
 
-    def _segs_c8(self, arr, acts: Sequence[Act]) -> None:
-        for i, a_ in enumerate(acts):
-            arr[i].ptr = self.c8_of(a_).data_ptr()
-            arr[i].batch_stride, arr[i].channels, arr[i].accumulate = a_.bstride, a_.C, 0
+    def _conv3_op(self, cell: "_Cell", kind: int, segs: Sequence, ptrs: dict, **mode) -> L.Op:
+        """A 3x3 convolution op of `cell` (the shape, the operand type and the tag are the cell's) over segments of `segs`' channels (Acts, or
+        channel counts), filled by ops.conv3x3_case_args."""
+        chans = [s if isinstance(s, int) else s.C for s in segs]
+        mode = dict(dict(compute=self.compute if (cell.use_packed or cell.stem16) else 0, force_direct=self.force_direct), **mode)
+        return _ops.conv3x3_case_op(kind, cell.N, chans, cell.cout, cell.H, cell.W, tag=cell.tag, ptrs=ptrs, workspace=False, **mode)
 
-    def _cell_conv_op(self, cell: "_Cell", kind: int) -> L.Op:
-        op = _mk(kind, cell.tag)
-        a = op.u.conv3
-        a.N, a.H, a.W, a.Cin, a.Cout, a.n_in = cell.N, cell.H, cell.W, cell.cin, cell.cout, len(cell.inputs)
-        a.w = cell.w.data_ptr()
-        a.force_direct = self.force_direct
-        a.compute = self.compute if cell.use_packed else 0
-        return op
+    def _norm_shape(self, cell: "_Cell", z16: bool) -> Tuple[tuple, dict]:
+        """What the InstanceNorm filler takes of a cell whose conv output is channel-blocked 16-bit (z16) or fp32 planes: (shape, mode)."""
+        return (cell.N, cell.cout, cell.H, cell.W), dict(z=("c8f16" if cell.zf16 else "c8") if z16 else "f32", reserve_cus=self.coop_reserve_cus)
 
-    def _cell_norm_op(self, cell: "_Cell", kind: int) -> L.Op:
-        op = _mk(kind, cell.tag)
-        a = op.u.inorm
-        a.N, a.C, a.H, a.W, a.eps, a.slope = cell.N, cell.cout, cell.H, cell.W, 1e-5, cell.slope
-        a.z = cell.z.data_ptr()
-        a.z_layout = L.LAYOUT_C8 if cell.z16 else L.LAYOUT_PLANAR
-        a.z_type = 2 if cell.zf16 else 0
-        a.gamma = _ptr(self.pv(cell.gname)) if cell.gname else None
-        a.beta = _ptr(self.pv(cell.betaname)) if cell.betaname else None
-        a.mean, a.rstd = cell.mean.data_ptr(), cell.rstd.data_ptr()
-        a.coop_reserve_cus = self.coop_reserve_cus
-        return op
+    def _c8_norm_ok(self, cell: "_Cell", backward: bool, z16: bool = False) -> bool:
+        """Do the channel-group / cooperative InstanceNorm kernels take this cell's planes (above 64 x 64: can the teams be resident)?  Asked
+        before the output is decided: of a channel-blocked z with the output type, of fp32 planes without one."""
+        shape, mode = self._norm_shape(cell, z16)
+        q = _ops.instnorm_case_args(backward, *shape, compute=self.compute if z16 else 0, out="c8" if z16 else "f32", workspace=False, **mode)
+        return bool(self.lib.mtbc_instnorm_c8_supported(C.byref(q), int(backward)))
+
+    def _norm_ptrs(self, cell: "_Cell") -> dict:
+        return dict(z=cell.z, mean=cell.mean, rstd=cell.rstd, gamma=self.pv(cell.gname) if cell.gname else None,
+                    beta=self.pv(cell.betaname) if cell.betaname else None)
+
+    def _norm_op(self, cell: "_Cell", backward: bool, ptrs: dict, workspace: bool = False, **mode) -> L.Op:
+        """The InstanceNorm + LeakyReLU op of `cell` in one direction, filled by ops.instnorm_case_args."""
+        shape, zmode = self._norm_shape(cell, cell.z16)
+        return _ops.instnorm_case_op(backward, *shape, tag=cell.tag, ptrs=ptrs, compute=self.compute, affine=bool(cell.gname), eps=1e-5, slope=cell.slope,
+                                     workspace=workspace, **zmode, **mode)
 
     def _gathered_dgrad(self, cell: "_Cell") -> None:
         """The gradient of y with respect to ALL its 3x3 consumers in ONE forward-type launch over their channel-blocked dz (K = sum
@@ -565,16 +543,9 @@ class StepPlan:
             gbuf, acc = y.grad8, 0
         else:
             gbuf, acc = self.grad_slot(y)
-        op = _mk(L.OP_CONV3_FWD, cell.tag)
-        a = op.u.conv3
-        a.N, a.H, a.W, a.Cin, a.Cout, a.n_in = N, H, W, K, cout, len(y.pending)
-        for i_, (dzj, wj, offj, cinj, coutj) in enumerate(y.pending):
-            a.in_[i_].ptr, a.in_[i_].batch_stride, a.in_[i_].channels, a.in_[i_].accumulate = dzj.data_ptr(), coutj * H * W, coutj, 0
-        a.w, a.w_packed, a.out = wg.data_ptr(), wpg.data_ptr(), gbuf.data_ptr()
-        a.compute, a.operand_layout, a.out_accumulate = self.compute, L.LAYOUT_C8, acc
-        if y.dy8_ok:
-            a.out_layout = L.LAYOUT_C8
-        self.bwd_ops.append(op)
+        ptrs = {"in": [pj[0] for pj in y.pending], "w": wg, "w_packed": wpg, "out": gbuf}
+        self.bwd_ops.append(self._conv3_op(cell, L.OP_CONV3_FWD, [pj[4] for pj in y.pending], ptrs, compute=self.compute, c8=True, bias=False,
+                                           out_c8=y.dy8_ok, out_accumulate=acc, force_direct=False))
 
     def _conv_cell_backward(self, cell: "_Cell") -> None:
         """Backward of a conv cell: [gathered dgrad of y] -> InstanceNorm + LeakyReLU backward (dz channel-blocked, or in place over dy)
@@ -589,19 +560,18 @@ class StepPlan:
             self._gathered_dgrad(cell)
         only_folded = (y.r1 is not None or y.pool is not None) and not g8 and not y.grad_written       # no gradient TENSOR: only folded terms
         dy = y.grad8 if g8 else (None if only_folded else self.grad_of(y))
-        op = self._cell_norm_op(cell, L.OP_IN_BWD)
-        a = op.u.inorm
-        a.dy, a.dy_batch_stride, a.dz = _ptr(dy), y.bstride, _ptr(dy)      # dz in place over dy unless a 16-bit output is asked for below
+        ptrs = dict(self._norm_ptrs(cell), dy=dy)
+        # dz in place over dy unless a 16-bit output is asked for below (dy's address stays in `dz` beside it, unless dy is channel-blocked)
+        mode = dict(dy=None if dy is None else ("c8" if g8 else "f32"), inplace=not g8)
         if y.pool is not None:
-            a.dy_pool, a.dy_pool_arg = y.pool[0].data_ptr(), y.pool[1].data_ptr()
+            ptrs.update(dy_pool=y.pool[0], dy_pool_arg=y.pool[1])
+            mode.update(pool=True)
         if y.r1 is not None:
-            a.dy_rank1, a.dy_rank1_w = y.r1[0].data_ptr(), y.r1[1].data_ptr()
-            a.dy_rank1_dw, a.dy_rank1_db, a.dy_rank1_accumulate = y.r1[2].data_ptr(), y.r1[3].data_ptr(), y.r1[4]
-        if g8:
-            a.dy_layout, a.dz = L.LAYOUT_C8, None
-            if written_before:                    # the other readers' fp32 planar partial, added while loading
-                a.n_dy_extra = 1
-                a.dy_extra[0] = y.grad.data_ptr()
+            ptrs.update(dy_rank1=y.r1[0], dy_rank1_w=y.r1[1], dy_rank1_dw=y.r1[2], dy_rank1_db=y.r1[3])
+            mode.update(rank1=True, rank1_grads=True, rank1_acc=bool(y.r1[4]))
+        if g8 and written_before:                 # the other readers' fp32 planar partial, added while loading
+            ptrs.update(dy_extra0=y.grad)
+            mode.update(n_extra=1)
         # inputs whose gradient is gathered later (by THEIR backward) from all their 3x3 consumers: a prefix of the
         # segment list, so that this conv's own dgrad covers a contiguous suffix of its input channels
         defer: List[Act] = []
@@ -615,45 +585,46 @@ class StepPlan:
         def dz8_buffer() -> torch.Tensor:      # the gathered launches read it later: it cannot be the shared scratch
             return self.alloc(N * cout * H * W, dtype=torch.int16) if defer else self._scratch16("_dz8_buf", N * cout * H * W)
 
-        coop = z16 or (c8_bwd and not _NO_COOP and H * W >= _COOP_MIN_BWD and bool(self.lib.mtbc_instnorm_c8_supported(C.byref(a), 1)))
+        coop = z16 or (c8_bwd and not _NO_COOP and H * W >= _COOP_MIN_BWD and self._c8_norm_ok(cell, True))
         dz8 = dz16 = None
         if coop:        # one pass straight into the channel-blocked dz the wgrad / dgrad MFMAs read
             dz8 = dz8_buffer()
-            a.dz8, a.out16_type, a.coop_state = dz8.data_ptr(), self.compute, self._coop_state()
+            ptrs.update(dz8=dz8, coop_state=self._coop_state())
         p16 = c8_bwd and not coop and (H * W) % 4 == 0 and H * W <= 65536
         if p16:         # dz feeds MFMAs only: 16-bit planar here, channel-blocked by the pack below
             dz16 = self._scratch16("_dz16_buf", N * cout * H * W)
-            a.dz16, a.out16_type = dz16.data_ptr(), self.compute
+            ptrs.update(dz16=dz16)
+        need, acc = 0, None       # bytes of the shared workspace
+        if gname:
+            acc = self._mark_param(gname)
+            self._mark_param(betaname)
+            ptrs.update(dgamma=self.gv(gname), dbeta=self.gv(betaname))
+        if bname:                       # conv bias gradient = sum of dz, produced by the same pass
+            accb = self._mark_param(bname)
+            acc = accb if acc is None else acc
+            assert acc == accb
+            ptrs.update(dbias_pre=self.gv(bname))
         if gname or bname:
-            acc = None
-            if gname:
-                acc = self._mark_param(gname)
-                self._mark_param(betaname)
-                a.dgamma, a.dbeta = self.gv(gname).data_ptr(), self.gv(betaname).data_ptr()
-            if bname:                       # conv bias gradient = sum of dz, produced by the same pass
-                accb = self._mark_param(bname)
-                acc = accb if acc is None else acc
-                assert acc == accb
-                a.dbias_pre = self.gv(bname).data_ptr()
-            a.accumulate_dparams = acc
-            self._need_ws(op, "inorm", N * cout * (131 if coop else 3) * 4)
+            need = N * cout * (131 if coop else 3) * 4
         if y.r1 is not None:
-            self._need_ws(op, "inorm", N * (cout + 1) * 262 * 4)
-        dop = None
-        if (gname or bname) and z16 and self.dev.type == "cuda":
-            # the per-plane partial sums of dgamma / dbeta / dbias stay in a (small) buffer of this cell's own and are reduced later,
-            # many cells per launch (a step has 36 of these 5 us reductions): after every _DPARAM_BATCH cells and at the end
-            if a.accumulate_dparams:
+            need = max(need, N * (cout + 1) * 262 * 4)
+        # the per-plane partial sums of dgamma / dbeta / dbias stay in a (small) buffer of this cell's own and are reduced later,
+        # many cells per launch (a step has 36 of these 5 us reductions): after every _DPARAM_BATCH cells and at the end
+        deferred = bool(gname or bname) and z16 and self.dev.type == "cuda"
+        if deferred:
+            if acc:
                 self.flush_dparams()            # an earlier contribution to the same parameters lands first
-            buf = self.alloc(N * (cout + 1) * 262)
-            self.ws_users = [u for u in self.ws_users if u[0] is not op]
-            a.workspace, a.workspace_bytes, a.defer_dparams = buf.data_ptr(), buf.numel() * 4, 1
+            ptrs.update(workspace=self.alloc(N * (cout + 1) * 262))
+        op = self._norm_op(cell, True, ptrs, out="c8" if coop else ("p16" if p16 else "f32"), dbias=bool(bname), acc=bool(acc), defer=deferred,
+                           workspace=deferred, **mode)
+        if deferred:                    # (the shared workspace stays as large as this op would have needed it)
+            self.ws_bytes = max(self.ws_bytes, need)
             dop = _mk(L.OP_IN_DPARAM, cell.tag)
-            d = dop.u.dparam
-            d.part, d.dgamma, d.dbeta, d.dbias_pre = buf.data_ptr(), a.dgamma, a.dbeta, a.dbias_pre
-            d.N, d.C, d.T, d.accumulate = N, cout, int(self.lib.mtbc_instnorm_bwd_team(C.byref(a))), a.accumulate_dparams
+            dop.u.dparam = _ops.instnorm_dparam_desc(op.u.inorm, ptrs["workspace"].data_ptr())[0]
+        elif need:
+            self._need_ws(op, "inorm", need)
         self.bwd_ops.append(op)
-        if dop is not None:
+        if deferred:
             self._pending_dparams.append((dop, tuple(n_ for n_ in (gname, betaname, bname) if n_)))
             if len(self._pending_dparams) >= _DPARAM_BATCH:
                 self.flush_dparams()
@@ -666,22 +637,13 @@ class StepPlan:
             if p16:
                 pk.kind = L.OP_C8_PACK16
             self.bwd_ops.append(pk)
-        # weight gradient
-        op = self._cell_conv_op(cell, L.OP_CONV3_WGRAD)
+        # weight gradient: channel-blocked operands, or the stem's fp32 planar input of 1 .. STEM_MAX_CIN channels beside a channel-blocked dz, or planar
+        c8w = c8_bwd or cell.stem16
+        ptrs = {"in": self._segs(inputs, c8=c8_bwd)[0], "w": cell.w, "dout": dz8 if c8w else dy, "dw": self.gv(cell.wname)}
+        # (MTBC_NO_STEM_MC: the small-Cin kernel stopped at 4 channels)
+        op = self._conv3_op(cell, L.OP_CONV3_WGRAD, inputs, ptrs, c8=c8w, bias=False, accumulate_dw=bool(self._mark_param(cell.wname)),
+                            force_direct=self.force_direct or (cell.old_mc and cell.cin > 4))
         a = op.u.conv3
-        if c8_bwd:
-            self._segs_c8(a.in_, inputs)
-            a.dout, a.operand_layout = dz8.data_ptr(), L.LAYOUT_C8
-        elif cell.stem16:          # fp32 planar input of 1 .. STEM_MAX_CIN channels, channel-blocked dz
-            self._segs(a.in_, inputs)
-            a.dout, a.operand_layout, a.compute = dz8.data_ptr(), L.LAYOUT_C8, self.compute
-        else:
-            self._segs(a.in_, inputs)
-            a.dout = dy.data_ptr()
-            if cell.old_mc and cell.cin > 4:      # (the small-Cin kernel stopped at 4 channels)
-                a.force_direct = 1
-        a.accumulate_dw = self._mark_param(cell.wname)
-        a.dw = self.gv(cell.wname).data_ptr()
         # (batching the ~40 split-K reductions of a step into a few launches was built and measured: 15.20 vs 14.54 ms -- the
         #  partials then live in buffers of their own and travel to HBM and back instead of being reduced out of the cache)
         self._need_ws(op, "conv3", self.lib.mtbc_conv3x3_wgrad_workspace(C.byref(a)))
@@ -709,23 +671,16 @@ class StepPlan:
                 ws = self.alloc(cout, crest, 3, 3)
                 self._wview(cell.w, ws, cout, cell.cin, off, crest, 0, 0, 0)
                 wps, _ = self._pack_lp(ws, crest, cout, 1)
-                op = self._cell_conv_op(cell, L.OP_CONV3_DGRAD)
-                a = op.u.conv3
-                a.Cin, a.n_in, a.w = crest, len(rest), ws.data_ptr()
-                self._segs(a.in_, rest, grads=True, g16=True)
-                a.dout, a.operand_layout, a.w_packed = dz8.data_ptr(), L.LAYOUT_C8, wps.data_ptr()
-                self.bwd_ops.append(op)
+                grads, codes = self._segs(rest, grads=True, g16=True)
+                ptrs = {"in": grads, "w": ws, "w_packed": wps, "dout": dz8}
+                self.bwd_ops.append(self._conv3_op(cell, L.OP_CONV3_DGRAD, rest, ptrs, c8=True, accumulate=codes))
         elif need:
             if len(need) != len(inputs):
                 raise NotImplementedError("mixed grad / no-grad concat inputs")
-            op = self._cell_conv_op(cell, L.OP_CONV3_DGRAD)
-            a = op.u.conv3
-            self._segs(a.in_, inputs, grads=True, g16=bool(c8_bwd and cell.wp_d is not None))
-            a.dout = _ptr(dy)
-            if c8_bwd and cell.wp_d is not None:
-                a.dout, a.operand_layout = dz8.data_ptr(), L.LAYOUT_C8
-            a.w_packed = _ptr(cell.wp_d)
-            self.bwd_ops.append(op)
+            c8d = c8_bwd and cell.wp_d is not None
+            grads, codes = self._segs(inputs, grads=True, g16=c8d)
+            ptrs = {"in": grads, "w": cell.w, "w_packed": cell.wp_d, "dout": dz8 if c8d else dy}
+            self.bwd_ops.append(self._conv3_op(cell, L.OP_CONV3_DGRAD, inputs, ptrs, c8=c8d, accumulate=codes))
 
     # ---- the small layers: each method decides (layout, fold, 16-bit operands, accumulate flags, allocation order) and has its ops filled by
     # the fillers of ops.py (workspace=False: the workspace is the shared one, _need_ws / finalize) -- the fillers the reference cases use

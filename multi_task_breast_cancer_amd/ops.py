@@ -6,7 +6,8 @@ goes through step programs (engine.py).  Device fp32 tensors only; every wrapper
 Each argument struct is filled in ONE function, the family's *_case_args builder: with ptrs=None it carries dummy addresses for the host-only
 *_kernel_name queries (the launch-coverage guards of the tests), with ptrs= tensors it is what conv3x3_launch / instnorm_launch /
 convT_launch / small_op_launch / loss_op_launch hand the library.  The eager wrappers validate, allocate, call the builder and launch; the
-step programs' pool, 1x1, GAP, Linear, ConvT, fused-head, up-sampling and loss ops are filled by the same builders (engine.StepPlan).
+step programs' ops -- the conv cells' 3x3 convolutions and InstanceNorms, pool, 1x1, GAP, Linear, ConvT, fused head, up-sampling, losses -- are
+filled by the same builders (engine.StepPlan).
 """
 from __future__ import annotations
 
@@ -84,8 +85,10 @@ def conv3x3_case_args(op: int, N: int, segs: Sequence[int], Cout: int, H: int, W
                       c8: bool = False, out_c8: bool = False, out_fp16: bool = False, dx_c8: bool = False, bias: bool = True,
                       in_kernel_reduce: bool = False, accumulate: Optional[Sequence[int]] = None, packed: Optional[bool] = None,
                       force_direct: bool = False, accumulate_dw: bool = False, stats: bool = False, norm: Optional[float] = None,
-                      out_partial: bool = False, out_accumulate: bool = False) -> "L.Conv3x3Args":
-    """The argument struct of ONE 3x3 convolution call (op = L.OP_CONV3_FWD / _DGRAD / _WGRAD), the only place that fills it.  ptrs: "in" ->
+                      out_partial: bool = False, out_accumulate: bool = False, workspace: bool = True,
+                      into: Optional["L.Conv3x3Args"] = None) -> "L.Conv3x3Args":
+    """The argument struct of ONE 3x3 convolution call (op = L.OP_CONV3_FWD / _DGRAD / _WGRAD), the only place that fills it: the filler
+    engine.StepPlan.conv_cell, _gathered_dgrad and _conv_cell_backward call (through conv3x3_case_op).  ptrs: "in" ->
     the segments (tensors, or C8 tensors) and field name -> tensor / C8 / None for NULL; None = distinct 16-byte aligned dummies that nothing
     may dereference (for conv3x3_kernel_name).  c8: operands in MTBC_LAYOUT_C8 (one segment of at most L.STEM_MAX_CIN channels stays fp32
     planar: the stem, whose weight gradient reads it beside a channel-blocked dout); bias: fwd bias / wgrad dbias; packed: with w_packed
@@ -94,10 +97,11 @@ def conv3x3_case_args(op: int, N: int, segs: Sequence[int], Cout: int, H: int, W
     16-bit output, stats = the InstanceNorm statistics partials of the epilogue, norm = the slope of the norm-backward epilogue of a gathered
     dgrad (norm_z / _mean / _rstd / _gamma / _beta), out_partial = its planar partial, out_accumulate = the result added to fp32 planes (a
     gathered dgrad into a gradient something else has written).  Weight gradient: accumulate_dw, in_kernel_reduce =
-    offer the counters of the in-kernel split-K reduction."""
+    offer the counters of the in-kernel split-K reduction, workspace = False leaves it without a workspace (the step programs point it at
+    their shared one).  into: the (zeroed) struct to fill, a step-program op's union member."""
     lib = L.load()
     ptr = _ptr(ptrs, _C3_DUMMY.__getitem__)
-    a = L.Conv3x3Args()
+    a = L.Conv3x3Args() if into is None else into
     a.N, a.H, a.W, a.Cin, a.Cout, a.n_in = N, H, W, sum(segs), Cout, len(segs)
     if accumulate is None:
         accumulate = [3 if dx_c8 else int(i > 0) for i in range(len(segs))] if op == L.OP_CONV3_DGRAD else ()
@@ -124,12 +128,20 @@ def conv3x3_case_args(op: int, N: int, segs: Sequence[int], Cout: int, H: int, W
         a.dout = ptr("dout")
     else:
         a.dout, a.dw, a.dbias, a.accumulate_dw = ptr("dout"), ptr("dw"), (ptr("dbias") if bias else None), int(accumulate_dw)
-        nb = int(lib.mtbc_conv3x3_wgrad_workspace(C.byref(a)))
-        a.workspace, a.workspace_bytes = ptr("workspace"), (nb if ptrs is None else ptrs["workspace"].numel() * 4)
+        if workspace:
+            nb = int(lib.mtbc_conv3x3_wgrad_workspace(C.byref(a)))
+            a.workspace, a.workspace_bytes = ptr("workspace"), (nb if ptrs is None else ptrs["workspace"].numel() * 4)
         nsync = int(lib.mtbc_conv3x3_wgrad_sync_bytes(C.byref(a))) if in_kernel_reduce else 0
         if nsync:
             a.wgrad_sync, a.wgrad_sync_bytes = ptr("wgrad_sync"), (nsync if ptrs is None else ptrs["wgrad_sync"].numel() * 4)
     return a
+
+
+def conv3x3_case_op(op: int, *shape, tag: int = 0, **mode) -> "L.Op":
+    """conv3x3_case_args(op, *shape, **mode) as the step-program op of that kind (+ tag), filled in place."""
+    o = _small_op(op, tag)
+    conv3x3_case_args(op, *shape, into=o.u.conv3, **mode)
+    return o
 
 
 def conv3x3_case_kernel(op: int, *shape, **mode) -> str:
@@ -389,29 +401,38 @@ def instnorm_case_args(backward: bool, N: int, Cc: int, H: int, W: int, ptrs: Op
                        z: str = "f32", affine: bool = True, eps: float = 1e-5, slope: float = 0.01, reserve_cus: int = 0, stats_slots: int = 0,
                        planar: bool = False, planar16: bool = False, pool: bool = False, pool_arg: bool = True, chunk_ws: bool = True,
                        dy: Optional[str] = "f32", n_extra: int = 0, rank1: bool = False, rank1_grads: bool = False, rank1_acc: bool = False,
-                       dbias: bool = False, acc: bool = False, defer: bool = False, inplace: bool = False) -> "L.InstNormArgs":
-    """The argument struct of ONE InstanceNorm + LeakyReLU call, every field the step programs set (engine._conv_cell / _conv_cell_backward).
+                       dbias: bool = False, acc: bool = False, defer: bool = False, inplace: bool = False, workspace: bool = True,
+                       into: Optional["L.InstNormArgs"] = None) -> "L.InstNormArgs":
+    """The argument struct of ONE InstanceNorm + LeakyReLU call, the filler engine.StepPlan.conv_cell / _conv_cell_backward call (through
+    instnorm_case_op).
     ptrs: field name -> tensor, C8 or None for NULL (dy_extra0 .. dy_extra3 for the fan-in); None = distinct 16-byte aligned dummies that nothing may dereference
     (for instnorm_kernel_name).  compute: 0 = the fp32 kernels of norm.hip, 1 / 2 = out16_type.  out: "f32" planes, "p16" 16-bit planes
     (y16 / dz16), "c8" channel-blocked (y8 / dz8).  z: "f32" planes, "c8" channel-blocked of the output type, "c8f16" / "c8bf16" channel-blocked fp16 / bf16
     under an output of the other type.  Forward: planar / planar16 = fp32 / 16-bit planes beside y8, stats_slots > 0 = statistics from the conv epilogue,
     pool (+ pool_arg) = the pooled output (+ argmax codes), chunk_ws = offer the chunked-statistics workspace.  Backward: dy "f32" / "c8" /
     None, n_extra planar partials, rank1 (+ the head's own gradients, accumulated or not), pool = the routed max-pool gradient, dbias =
-    dbias_pre, acc = accumulate_dparams, defer = defer_dparams, inplace = dz over dy (fp32 planes)."""
+    dbias_pre, acc = accumulate_dparams, defer = defer_dparams, inplace = dz over dy (fp32 planes; beside dz8 / dz16 the step programs leave
+    dy's address in dz all the same, though no kernel reads it there).  workspace = False leaves either direction without a workspace (the
+    step programs point it at their shared one).  into: the (zeroed) struct to fill, a step-program op's union member."""
     dummy = iter(range(1 << 20, 1 << 30, 1 << 20))
 
     def ptr(name):
         return next(dummy) if ptrs is None else _p(ptrs[name])
 
-    a = L.InstNormArgs()
+    a = L.InstNormArgs() if into is None else into
     a.N, a.C, a.H, a.W, a.eps, a.slope = N, Cc, H, W, eps, slope
     a.z, a.mean, a.rstd = ptr("z"), ptr("mean"), ptr("rstd")
     if affine:
         a.gamma, a.beta = ptr("gamma"), ptr("beta")
-    a.out16_type, a.coop_reserve_cus = compute, reserve_cus
+    a.coop_reserve_cus = reserve_cus
+    if out != "f32":        # (the type of the 16-bit output: read with y8 / y16 / dz8 / dz16 only)
+        a.out16_type = compute
     if z != "f32":
         a.z_layout, a.z_type = L.LAYOUT_C8, {"c8": 0, "c8bf16": 1, "c8f16": 2}[z]
-    a.y_batch_stride = a.dy_batch_stride = Cc * H * W
+    if backward:            # (each direction reads its own stride only)
+        a.dy_batch_stride = Cc * H * W
+    else:
+        a.y_batch_stride = Cc * H * W
     if stats_slots:
         a.stats_partial, a.stats_slots = ptr("stats_partial"), stats_slots
     if out == "c8":
@@ -429,7 +450,7 @@ def instnorm_case_args(backward: bool, N: int, Cc: int, H: int, W: int, ptrs: Op
             a.y16 = ptr("y16")
         else:
             a.y = ptr("y")
-        nb = L.load().mtbc_instnorm_fwd_workspace(C.byref(a))
+        nb = L.load().mtbc_instnorm_fwd_workspace(C.byref(a)) if workspace else 0
         if nb and chunk_ws:
             a.workspace, a.workspace_bytes = ptr("workspace"), (nb if ptrs is None else ptrs["workspace"].numel() * 4)
         return a
@@ -443,8 +464,10 @@ def instnorm_case_args(backward: bool, N: int, Cc: int, H: int, W: int, ptrs: Op
         a.dz8 = ptr("dz8")
     elif out == "p16":
         a.dz16 = ptr("dz16")
-    else:
-        a.dz = a.dy if inplace else ptr("dz")
+    if inplace:
+        a.dz = a.dy
+    elif out == "f32":
+        a.dz = ptr("dz")
     if rank1:
         a.dy_rank1, a.dy_rank1_w = ptr("dy_rank1"), ptr("dy_rank1_w")
         if rank1_grads:
@@ -456,8 +479,16 @@ def instnorm_case_args(backward: bool, N: int, Cc: int, H: int, W: int, ptrs: Op
     if dbias:
         a.dbias_pre = ptr("dbias_pre")
     a.accumulate_dparams, a.defer_dparams = int(acc), int(defer)
-    a.workspace, a.workspace_bytes = ptr("workspace"), (N * (Cc + 1) * 262 * 4 if ptrs is None else ptrs["workspace"].numel() * 4)
+    if workspace:
+        a.workspace, a.workspace_bytes = ptr("workspace"), (N * (Cc + 1) * 262 * 4 if ptrs is None else ptrs["workspace"].numel() * 4)
     return a
+
+
+def instnorm_case_op(backward: bool, *shape, tag: int = 0, **mode) -> "L.Op":
+    """instnorm_case_args(backward, *shape, **mode) as the MTBC_OP_IN_FWD / _BWD op (+ tag), filled in place."""
+    o = _small_op(L.OP_IN_BWD if backward else L.OP_IN_FWD, tag)
+    instnorm_case_args(backward, *shape, into=o.u.inorm, **mode)
+    return o
 
 
 def instnorm_case_kernel(backward: bool, *shape, **mode) -> str:
@@ -475,7 +506,7 @@ def instnorm_launch(a: "L.InstNormArgs", backward: bool) -> None:
 
 def instnorm_dparam_desc(a: "L.InstNormArgs", part: int):
     """The descriptor (an array of one) that reduces the partials a backward call with defer_dparams left at address `part` (= its workspace),
-    as the step programs build it (MTBC_OP_IN_DPARAM, engine._conv_cell_backward)."""
+    as the step programs build it (MTBC_OP_IN_DPARAM: engine.StepPlan._conv_cell_backward copies it into the op)."""
     d = (L.DparamDesc * 1)()
     d[0].part, d[0].dgamma, d[0].dbeta, d[0].dbias_pre = part, a.dgamma, a.dbeta, a.dbias_pre
     d[0].N, d[0].C, d[0].T, d[0].accumulate = a.N, a.C, L.load().mtbc_instnorm_bwd_team(C.byref(a)), a.accumulate_dparams

@@ -3,13 +3,15 @@
 (buffer ordinal, byte offset) -- buffer 0 = the flat parameters, 1 = the flat gradients, 2 + i = plan.keep[i] -- so that two builds of the
 same plan list the same text whatever the allocator handed out.  Nothing is launched; on --device cpu no GPU is needed.
 
-    python tools/step_program_listing.py [--package DIR] [--set cpu|gpu] [--device cpu|cuda:0] [--short | --summary] [--combos]
+    python tools/step_program_listing.py [--package DIR] [--set cpu|gpu|cells] [--device cpu|cuda:0] [--short | --summary] [--combos]
 
 --package: the directory of the package to list (default: this tree's); a copy of another commit's package takes this tree's built library
 (MTBC_LIB) unless it has its own.  --set cpu: the configurations of tests/golden/step_program_listing.json; gpu: the benchmark's four step
-programs and one data-parallel variant.  --short: JSON {configuration: {program: ["kind:digest of the canonical fields", ...]}}; --summary:
-per program the op count and one digest; --combos: the (kind, layout / flag) combinations of the pool, 1x1, GAP, Linear, ConvT and fused-head
-ops that the set reaches.  A plan on CPU tensors still depends on whether a device is visible where planes exceed 64 x 64 in the 16-bit
+programs and one data-parallel variant; cells: the configurations of tests/golden/conv_cell_listing.json, small plans that reach the branches
+of StepPlan.conv_cell and its backward the cpu set does not (several sets: --set cpu --set cells).  --short: JSON {configuration:
+{program: ["kind:digest of the canonical fields", ...]}}; --summary: per program the op count and one digest; --combos: the (kind, layout /
+flag) combinations of the pool, 1x1, GAP, Linear, ConvT, fused-head, 3x3 convolution and InstanceNorm ops that the set reaches.  A plan on
+CPU tensors still depends on whether a device is visible where planes exceed 64 x 64 in the 16-bit
 modes (the InstanceNorm team query asks the runtime): the golden holds those configurations from both kinds of machine."""
 import argparse
 import bisect
@@ -55,7 +57,53 @@ def _gpu_set():
     return out
 
 
-CONSTRUCT = {"MTUNetPlusPlus": lambda nets, kw: nets.MTUNetPlusPlus(2, 1, 1, 3, **kw), "MTnnUNet": lambda nets, kw: nets.MTnnUNet(1, 1, 3),
+def _cells_set():
+    """The cpu set's tuple + the plan switches of engine.py (module attributes, read when a plan is built) that hold for this build."""
+    pp = {"deep_supervision": True}
+    mc = lambda c, **kw: dict(in_channels=c, out_channels=1, n_classes=3, **kw)         # noqa: E731
+    rows = [
+        # a first conv of 2 .. 5 channels: fp32, and the multi-channel stem kernels of the 16-bit modes
+        ("stem2-f32", "MTUNetPlusPlus*", mc(2), "f32", 64, {}, {}),
+        ("stem5-f32", "MTUNetPlusPlus*", mc(5), "f32", 64, {}, {}),
+        ("stem3-bf16", "MTUNetPlusPlus*", mc(3, **pp), "bf16", 64, {}, {}),
+        ("stem5-f16", "MTnnUNet*", dict(sequences=5, regions=1, n_classes=3), "f16", 64, {}, {}),
+        # ... on the launches from before those kernels; Cin = 5: the direct weight gradient
+        ("stem3-bf16-nostemmc", "MTUNetPlusPlus*", mc(3, **pp), "bf16", 64, {}, {"_NO_STEM_MC": True}),
+        ("stem5-bf16-nostemmc", "MTUNetPlusPlus*", mc(5), "bf16", 64, {}, {"_NO_STEM_MC": True}),
+        ("stem5-f32-nostemmc", "MTnnUNet*", dict(sequences=5, regions=1, n_classes=3), "f32", 64, {}, {"_NO_STEM_MC": True}),
+        ("direct-f32", "MTUNetPlusPlus*", mc(1, force_direct=True, **pp), "f32", 64, {}, {}),
+        # (16-bit modes: only a graph without a transposed convolution can be planned with force_direct)
+        ("direct-bf16", "nnUNetClassifier*", dict(sequences=1, n_classes=3, force_direct=True), "bf16", 64, {}, {}),
+        ("nocoop-bf16", "MTUNetPlusPlus*", mc(1, **pp), "bf16", 64, {}, {"_NO_COOP": True}),
+        ("nocoop-f16-128", "MTnnUNet*", dict(sequences=1, regions=1, n_classes=3), "f16", 128, {}, {"_NO_COOP": True}),
+        # a plane above 256 x 256 on the one-plane kernels: the channel-blocked dz packed from fp32 planes
+        ("nocoop-bf16-512", "MTnnUNet*", dict(sequences=1, regions=1, n_classes=3), "bf16", 512, {}, {"_NO_COOP": True}),
+        ("nogather-bf16", "MTUNetPlusPlus*", mc(1, **pp), "bf16", 64, {}, {"_NO_GATHER": True}),
+        ("noz16-bf16", "MTUNetPlusPlus*", mc(1, **pp), "bf16", 64, {}, {"_NO_Z16": True}),
+        ("noz16-f16-128", "MTUNetPlusPlus*", mc(1), "f16", 128, {}, {"_NO_Z16": True}),
+        ("zbf16-bf16", "MTUNetPlusPlus*", mc(1, **pp), "bf16", 64, {}, {"_Z_BF16": True}),
+        # 16-bit gathered activation gradients: a channel-blocked dy, and dy_extra where something else wrote the fp32 gradient
+        ("da16-bf16", "MTUNetPlusPlus*", mc(1, **pp), "bf16", 64, {}, {"_DA16": True}),
+        ("da16-f16-nn", "MTnnUNet*", dict(sequences=1, regions=1, n_classes=3), "f16", 64, {}, {"_DA16": True}),
+        ("da16-bf16-bts-128", "Multi_BTSUNet", pp, "bf16", 128, {}, {"_DA16": True}),
+        # a first cell of 10 channels: channel-blocked operands without the channel-blocked backward, then a conv that is not packed
+        ("bts-w20-bf16-128", "Multi_BTSUNet", dict(width=20), "bf16", 128, {}, {}),
+        ("reserve64-bf16", "MTUNetPlusPlus*", mc(1, **pp), "bf16", 64, {"coop_reserve_cus": 64}, {}),
+        ("reserve64-bf16-128", "MTnnUNet*", dict(sequences=1, regions=1, n_classes=3), "bf16", 128, {"coop_reserve_cus": 64}, {}),
+    ]
+    # the single-task U-Net++ (MONAI's widths 32 / 32 / 64 / 128 / 256, every conv with a bias), with and without deep supervision
+    for dtype in ("f32", "bf16"):
+        for ds in (True, False):
+            rows.append((f"UnetPlusPlus-{dtype}-{'ds' if ds else 'nods'}", "UnetPlusPlus", {"deep_supervision": ds}, dtype, 64, {}, {}))
+    alpha = {"UnetPlusPlus": 1.0, "nnUNetClassifier*": 0.0}          # a segmentation-only and a classification-only model
+    return [(label, arch, kw, dtype, 2, size, dict(FUSED, alpha=alpha.get(arch, FUSED["alpha"])), attrs, {}, flags)
+            for label, arch, kw, dtype, size, attrs, flags in rows]
+
+
+SETS = {"cpu": _cpu_set, "gpu": _gpu_set, "cells": _cells_set}
+CONSTRUCT = {"MTUNetPlusPlus*": lambda nets, kw: nets.MTUNetPlusPlus(2, **kw), "MTnnUNet*": lambda nets, kw: nets.MTnnUNet(**kw),
+             "UnetPlusPlus": lambda nets, kw: nets.BasicUnetPlusPlus(2, **kw), "nnUNetClassifier*": lambda nets, kw: nets.nnUNetClassifier(**kw),
+             "MTUNetPlusPlus": lambda nets, kw: nets.MTUNetPlusPlus(2, 1, 1, 3, **kw), "MTnnUNet": lambda nets, kw: nets.MTnnUNet(1, 1, 3),
              "Multi_BTSUNet": lambda nets, kw: nets.Multi_BTSUNet(1, 1, 3, **kw), "nnUNet": lambda nets, kw: nets.nnUNet(1, 1),
              "nnUNetClassifier": lambda nets, kw: nets.nnUNetClassifier(1, 3), "UNetPlusPlusClassifier": lambda nets, kw: nets.UNetPlusPlusClassifier(2, 1, 3)}
 
@@ -63,10 +111,15 @@ CONSTRUCT = {"MTUNetPlusPlus": lambda nets, kw: nets.MTUNetPlusPlus(2, 1, 1, 3, 
 def build(nets, config, device):
     """The compiled step of one configuration on zeroed flat buffers: programs and plan, nothing launched."""
     import torch
-    label, arch, kw, dtype, N, size, fused, attrs, env = config
+    label, arch, kw, dtype, N, size, fused, attrs, env, *flags = config
     env = dict({"MTBC_NOFUSE_HEADS": "0"}, **env)          # (the one plan switch read while a graph is built)
     saved = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
+    engine = sys.modules[nets.__name__.rsplit(".", 1)[0] + ".engine"]
+    flags = flags[0] if flags else {}
+    saved_flags = {k: getattr(engine, k) for k in flags}          # (a name the engine does not have is an error)
+    for k, v in flags.items():
+        setattr(engine, k, v)
     try:
         torch.manual_seed(1993)
         model = CONSTRUCT[arch](nets, kw)
@@ -77,6 +130,8 @@ def build(nets, config, device):
         model.flat_g = torch.zeros_like(model.flat_p)
         return model, nets.CompiledStep(model, N, size, size, fused_loss=fused)
     finally:
+        for k, v in saved_flags.items():
+            setattr(engine, k, v)
         for k, v in saved.items():
             os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
 
@@ -131,8 +186,9 @@ def short(lines):
     return [f"{kind}:{hashlib.sha1(text.encode()).hexdigest()[:12]}" for kind, text in lines]
 
 
-def combos(L, program):
-    """The (kind, layout / flag) combinations of the pool, 1x1, GAP, Linear, ConvT and fused-head ops of a program."""
+def combos(L, program, name=""):
+    """The (kind, layout / flag) combinations of the pool, 1x1, GAP, Linear, ConvT, fused-head, 3x3 convolution and InstanceNorm ops of a
+    program (`name`: which of PROGRAMS, listed with the 3x3 convolutions -- a forward-type op of the backward program is a gathered dgrad)."""
     seen = set()
     for i in range(program.n):
         op = program.array[i]
@@ -151,8 +207,18 @@ def combos(L, program):
             f = (f"acc={a.acc_wT}{a.acc_bT}{a.acc_w1}{a.acc_b1}",)
         elif member == "gap":
             f = ()
-        elif member == "inorm" and (a.pool_y8 or a.dy_pool or a.dy_rank1):      # the pool and the 1x1 head folded into an InstanceNorm op
-            f = (f"pool_y8={bool(a.pool_y8)}", f"pool_arg={bool(a.pool_arg)}", f"dy_pool={bool(a.dy_pool)}", f"dy_rank1={bool(a.dy_rank1)}")
+        elif member == "inorm":       # (with the pool and the 1x1 head folded into it)
+            out = "+".join(n for n in ("y", "y8", "y16", "dz", "dz8", "dz16") if getattr(a, n))
+            f = (f"pool_y8={bool(a.pool_y8)}", f"pool_arg={bool(a.pool_arg)}", f"dy_pool={bool(a.dy_pool)}", f"dy_rank1={bool(a.dy_rank1)}",
+                 f"z_layout={a.z_layout}", f"z_type={a.z_type}", f"out16={a.out16_type}", f"out={out}", f"stats={a.stats_slots > 0}",
+                 f"reserve={a.coop_reserve_cus}", f"affine={bool(a.gamma)}", f"dy={bool(a.dy)}", f"dy_layout={a.dy_layout}",
+                 f"n_extra={a.n_dy_extra}", f"dbias={bool(a.dbias_pre)}", f"acc={a.accumulate_dparams}", f"defer={a.defer_dparams}",
+                 f"ws={bool(a.workspace)}")
+        elif member == "conv3":
+            f = (f"in={name}", f"cin={a.Cin}" if a.Cin <= L.STEM_MAX_CIN else "cin>5", f"compute={a.compute}", f"operand_layout={a.operand_layout}",
+                 f"out_layout={a.out_layout}", f"out_type={a.out_type}", f"force_direct={a.force_direct}", f"packed={bool(a.w_packed)}",
+                 f"bias={bool(a.bias)}", f"stats={bool(a.stats_partial)}", f"out_acc={a.out_accumulate}",
+                 "seg_acc=" + "".join(str(c) for c in sorted({a.in_[i].accumulate for i in range(a.n_in)})), f"acc_dw={a.accumulate_dw}")
         else:
             continue
         seen.add((op.kind, member) + f)
@@ -162,7 +228,7 @@ def combos(L, program):
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--package", default=OWN_PACKAGE)
-    ap.add_argument("--set", choices=("cpu", "gpu"), default="cpu")
+    ap.add_argument("--set", choices=sorted(SETS), action="append")
     ap.add_argument("--device", default="cpu")
     ap.add_argument("--short", action="store_true")
     ap.add_argument("--summary", action="store_true")
@@ -176,12 +242,12 @@ def main(argv=None):
     nets = importlib.import_module(os.path.basename(package) + ".nets")
     L = importlib.import_module(os.path.basename(package) + "._lib")
     result, reached = {}, set()
-    for config in (_cpu_set() if args.set == "cpu" else _gpu_set()):
+    for config in [c for name in (args.set or ["cpu"]) for c in SETS[name]()]:
         model, step = build(nets, config, args.device)
         canon = Canon(model, step)
         listing = {name: op_lines(L, canon, step.programs[name]) for name in PROGRAMS}
         for name in PROGRAMS:
-            reached |= combos(L, step.programs[name])
+            reached |= combos(L, step.programs[name], name)
         if args.short:
             result[config[0]] = {name: short(lines) for name, lines in listing.items()}
         elif args.summary:
