@@ -1,8 +1,17 @@
 """The benchmark's step programs, surveyed once per session for the launch-coverage guards of tests/test_ops_gpu.py
 (test_step_programs_launch_only_reference_tested_*): build_step is the one copy of bench.py's constructor path, survey walks the programs of a
 built step once and keeps plain values, the collectors and the key functions say per op family what "the same launch" means, and
-assert_all_tested compares what a survey saw with what the reference cases make.  No test module: pytest does not collect it."""
+assert_all_tested compares what a survey saw with what the reference cases make.  No test module: pytest does not collect it.
+
+The launch module of a further model (tests/test_unetpp_seg_launches_gpu.py is the shortest) holds what is the model's alone:
+  * PROGRAMS, a make_model(arch) for step_builder, and the case tables: one row per coverage key of the model's programs that no older table
+    makes, in the formats of tests/test_ops_gpu.py's tables, with the key and the launch each row stands for in a comment behind it;
+  * the thin parametrised wrappers that run the rows through tests/test_ops_gpu.py's own fp64 tests;
+  * three calls: assert_only_tested(survey, reference_tested_keys(), table_keys(...)) per program, assert_rows_needed(...) once over the
+    tables, assert_op_kinds_claimed(surveys) -- beside them whatever only this model can assert (an op kind that must or must not be there).
+kernel_instances and assert_keys_subset serve a model that is a part of an older one and should launch nothing of its own."""
 import collections
+import functools
 import gc
 import re
 
@@ -18,17 +27,32 @@ DEV = "cuda:0"
 STEP_PROGRAMS = [("MTUNetPlusPlus", "bf16", 32, 256), ("MTUNetPlusPlus", "f16", 16, 512), ("MTnnUNet", "bf16", 64, 256), ("MTUNetPlusPlus", "f32", 32, 256)]
 
 
-def build_step(arch, dtype, N, size, reserve_cus=0):
-    """Builds (does not run) one step program with bench.py's constructor path: (the compiled step, what must stay referenced beside it)."""
-    from multi_task_breast_cancer_amd.experiment_init import init_multitask_model, init_optimizer
-    from multi_task_breast_cancer_amd.miscellany import seed_everything
-    from multi_task_breast_cancer_amd.trainer import FusedTrainStep
-    seed_everything(1993)
-    model = init_multitask_model(arch, sequences=1, regions=1, n_classes=3, deep_supervision=True).to(DEV)
-    model.set_compute(dtype)
-    model.coop_reserve_cus = reserve_cus          # what a data-parallel FusedTrainStep sets (trainer.py)
-    step = FusedTrainStep(model, init_optimizer(model, "Adam", 1e-4), alpha=0.5, inversely_weighted=True)
-    return step._compiled(N, size, size), (step, model)
+PLAN = "conv3x3-wgrad-plan"
+NAMED = ("conv3x3", PLAN, "InstanceNorm", "transposed-convolution", "small-op", "loss")      # the families whose keys carry a kernel-name string
+
+
+def step_builder(make_model, **step_kwargs):
+    """build(arch, dtype, N, size, reserve_cus=0) for survey: builds (does not run) one fused training step of make_model(arch), seeded
+    1993, with Adam(1e-4) and step_kwargs: (the compiled step, what must stay referenced beside it)."""
+    def build(arch, dtype, N, size, reserve_cus=0):
+        from multi_task_breast_cancer_amd.experiment_init import init_optimizer
+        from multi_task_breast_cancer_amd.miscellany import seed_everything
+        from multi_task_breast_cancer_amd.trainer import FusedTrainStep
+        seed_everything(1993)
+        model = make_model(arch).to(DEV)
+        model.set_compute(dtype)
+        model.coop_reserve_cus = reserve_cus          # what a data-parallel FusedTrainStep sets (trainer.py)
+        step = FusedTrainStep(model, init_optimizer(model, "Adam", 1e-4), **step_kwargs)
+        return step._compiled(N, size, size), (step, model)
+    return build
+
+
+def multitask_model(arch, sequences=1, **kwargs):
+    from multi_task_breast_cancer_amd.experiment_init import init_multitask_model
+    return init_multitask_model(arch, sequences=sequences, regions=1, n_classes=3, deep_supervision=True, **kwargs)
+
+
+build_step = step_builder(multitask_model, alpha=0.5, inversely_weighted=True)          # bench.py's constructor path
 
 
 # ------------------------------------------------------------------ the key functions: the only places that decide what "the same launch" means
@@ -535,3 +559,128 @@ def assert_all_tested(family, tested, surveys, required=(), answers=None):
                 missing.append(f"\n  {prog}: {kind} {key} at {where}")
     print(f"{len(total)} distinct keys in the {len(surveys)} programs, {len(tested)} keys tested")
     assert not missing, f"{family} launches of the step programs that no reference case makes:" + "".join(missing)
+
+
+# ------------------------------------------------------------------ the guards of a further model's launch module (the header says how they go together)
+@functools.lru_cache(maxsize=None)
+def reference_tested_keys():
+    """{family: the keys of the older tables -- tests/test_ops_gpu.py's, for the loss family tests/test_loss_launches_gpu.py's}, the sets the
+    benchmark programs' guards hold those programs to.  A function of the case tables: computed once per session, not to be written to."""
+    import test_loss_launches_gpu as LOSS
+    import test_ops_gpu as OPS
+    return {"conv3x3": OPS._reference_tested_conv3x3_keys(), PLAN: OPS._reference_tested_wgrad_plan_keys(), "InstanceNorm": OPS._reference_tested_instnorm_keys(),
+            "transposed-convolution": OPS._reference_tested_convT_keys(), "small-op": OPS._reference_tested_small_op_keys(),
+            "layout": OPS._reference_tested_layout_keys(), "loss": LOSS._reference_tested_loss_keys()}
+
+
+def table_keys(conv3=(), wgrad_plan=(), inorm=(), convT=(), wview=()):
+    """{family: {key: [row]}} of the calls the rows of a module's tables make, from dummy-pointer structs (nothing is launched).  The tables
+    are in the formats of CONV3_STEP_CASES, WGRAD_PLAN_CASES, INORM_CASES and CONVT_CASES of tests/test_ops_gpu.py and of WVIEW_CASES of
+    oracle/layout_reference.py; a view row goes through the single and through the batched launch."""
+    import test_ops_gpu as OPS
+    W_ = L.OP_CONV3_WGRAD
+    own = {family: {} for family in COLLECTORS}
+    for case in conv3:
+        op, N, segs, Cout, H, W, mode = case
+        own["conv3x3"].setdefault((op, _conv3_key(ops.conv3x3_case_args(op, N, segs, Cout, H, W, **mode), op)), []).append(case)
+    for case in wgrad_plan:
+        own[PLAN].setdefault((W_, _wgrad_plan_key(ops.conv3x3_case_args(W_, *case[:5], **case[5]))), []).append(case)
+    for case in inorm:
+        for op, _, key in OPS._inorm_case_calls(case):
+            own["InstanceNorm"].setdefault((op, key), []).append(case)
+    for case in convT:
+        for kind, op, a, nxt in OPS._convT_case_calls(case):
+            own["transposed-convolution"].setdefault((kind, _convT_key(a, op, nxt)), []).append(case)
+    for case in wview:
+        for path in ("single", "many"):
+            own["layout"].setdefault(_wview_key(*case, path), []).append(case)
+    return own
+
+
+def assert_only_tested(survey, older, own, borrowed=None, borrowed_from=None):
+    """Every coverage key of the surveyed program is the key of a call that a reference case makes: in older[family] (reference_tested_keys),
+    in own[family] (table_keys of the model's rows) or in borrowed[family], the keys of the cases of the test file borrowed_from; and the
+    program holds a launch of every family.  Prints per family the counts and every key with its first launch and what answers for it (the
+    listings profiles/*_step_keys.txt record); a missing key is named with its family, kind label, key and where."""
+    program, borrowed, missing = survey.program, borrowed or {}, []
+    for family in COLLECTORS:
+        seen, old, rows, lent = survey.seen[family], older[family], own[family], borrowed.get(family, ())
+        assert seen, f"{program}: no {family} launch found"
+        table = "tests/test_loss_launches_gpu.py" if family == "loss" else "tests/test_ops_gpu.py"
+        print(f"{program} {family}: {len(seen)} keys, {sum(k in old for k in seen)} tested by {table}'s tables, "
+              f"{sum((k in rows or k in lent) and k not in old for k in seen)} by the rows added for this model, "
+              f"{sum(k not in old and k not in rows and k not in lent for k in seen)} missing")
+        for key, (kind, where) in sorted(seen.items(), key=repr):
+            by = table if key in old else f"row {rows[key][0]}" if key in rows else borrowed_from if key in lent else "MISSING"
+            print(f"  {kind} {key} at {where}  <- {by}")
+            if by == "MISSING":
+                missing.append(f"\n  {family}: {kind} {key} at {where}")
+    assert not missing, f"launches of {program} that no reference case makes:" + "".join(missing)
+
+
+def assert_rows_needed(module, surveys, older, own, tables):
+    """Every row of `tables` (the lists own = table_keys(...) was made from) makes a key that a surveyed program launches, that no older table
+    makes and that no other row makes: no dead row, no double row, no row without a key and no empty table -- deleting a row fails
+    assert_only_tested.  `module` names the tables in the message."""
+    assert set(own) == set(COLLECTORS), sorted(set(own) ^ set(COLLECTORS))
+    bad, made = [], 0
+    for family, keys in own.items():
+        launched = set().union(*(s.seen[family] for s in surveys))
+        rows = {}
+        for key, cases in keys.items():
+            for case in cases:
+                rows.setdefault(repr(case), []).append(key)
+            if len(cases) > 1:
+                bad.append(f"\n  {family}: {len(cases)} rows make {key}: {cases}")
+        for row, ks in rows.items():
+            if not any(k in launched and k not in older[family] for k in ks):
+                why = "; ".join(f"{'no program launches' if k not in launched else 'an older table already makes'} {k}" for k in ks)
+                bad.append(f"\n  {family}: {why} of row {row}")
+        print(f"{family}: {len(rows)} rows, {len(keys)} keys")
+        made += len(rows)
+    with_key = {repr(case) for keys in own.values() for cases in keys.values() for case in cases}
+    bad += [f"\n  table {i + 1} of {len(tables)} is empty" for i, table in enumerate(tables) if not table]
+    bad += [f"\n  no key is made by row {case}" for table in tables for case in table if repr(case) not in with_key]
+    if sum(len(table) for table in tables) != made:
+        bad.append(f"\n  {sum(len(table) for table in tables)} rows in the tables, {made} distinct rows that make a key")
+    assert not bad, f"rows of {module} that are not needed:" + "".join(bad)
+
+
+def kernel_instances(survey):
+    """The set of kernel instances a surveyed step's programs launch, from the strings of mtbc_conv3x3_kernel_name / _instnorm_ / _convT_ /
+    _op_kernel_name that the keys of the NAMED families keep: launches are joined by " + ", and what stands in brackets behind an instance
+    is what the arguments select inside it (common.h, OpChoice), not part of the instance."""
+    out = set()
+    for family in NAMED:
+        for key in survey.seen[family]:
+            out |= {re.sub(r"\s*\[[^\]]*\]", "", part).strip() for part in key[1][0].split(" + ")}
+    return out
+
+
+def assert_keys_subset(survey, of, families=COLLECTORS):
+    """The surveyed program launches something of every family of `families`, and no coverage key of those that the program of the survey
+    `of` does not launch; an extra key is named with its family, kind label, key and where."""
+    extra = []
+    for family in families:
+        seen = survey.seen[family]
+        assert seen, f"{survey.program}: no {family} launch found"
+        print(f"{survey.program} {family}: {len(seen)} keys, {len(of.seen[family])} in {of.program}")
+        for key, (kind, where) in sorted(seen.items(), key=repr):
+            if key not in of.seen[family]:
+                extra.append(f"\n  {family}: {kind} {key} at {where}")
+    assert not extra, f"launches of {survey.program} that {of.program} does not make:" + "".join(extra)
+
+
+def assert_op_kinds_claimed(surveys, claimed_also=(), required=()):
+    """The op kinds of each surveyed program are among those tests/test_ops_gpu.py's OP_KIND_COVERED_BY claims or the names in claimed_also
+    (kinds the calling module's own guard answers for), and each program holds every op kind of `required`."""
+    import test_ops_gpu as OPS
+    name_of = {getattr(L, n): n for n in dir(L) if n.startswith("OP_") and isinstance(getattr(L, n), int)}
+    claimed = set(OPS.OP_KIND_COVERED_BY) | set(claimed_also)
+    for s in surveys:
+        kinds = {kind for oplist in s.kinds.values() for kind in oplist}
+        print(f"{s.program}: {sorted(name_of.get(k, str(k)) for k in kinds)}")
+        absent = sorted(name_of.get(k, str(k)) for k in set(required) - kinds)
+        assert not absent, f"{s.program}: no op of kind {absent}"
+        unclaimed = sorted(name_of.get(k, str(k)) for k in kinds if name_of.get(k) not in claimed)
+        assert not unclaimed, f"op kinds of {s.program} that no test answers for: {unclaimed}"

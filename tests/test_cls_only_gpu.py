@@ -22,6 +22,7 @@ from multi_task_breast_cancer_amd.nets import MTnnUNet, MTUNetPlusPlus, UNetPlus
 from multi_task_breast_cancer_amd.optim import FusedAdam, FusedAdamW, FusedSGD  # noqa: E402
 from multi_task_breast_cancer_amd.trainer import ClsTrainMetrics, FusedEvalStep, FusedTrainStep  # noqa: E402
 from oracle import torch_oracle as O  # noqa: E402
+import step_programs as SP  # noqa: E402
 from test_cls_only_cpu import softmax_cases, softmax_references, within  # noqa: E402
 
 DEV = torch.device("cuda:0")
@@ -510,35 +511,19 @@ def test_refusals():
 
 
 # ------------------------------------------------------------------------------------------------ 11
-_NAMED = ("conv3x3", "conv3x3-wgrad-plan", "InstanceNorm", "transposed-convolution", "small-op", "loss")      # the families whose keys carry a kernel-name string
 _PROGRAMS = {"nnUNetClassifier": "MTnnUNet", "UNetPlusPlusClassifier": "MTUNetPlusPlus"}
+
+
+def _make_model(arch):
+    from multi_task_breast_cancer_amd.experiment_init import init_classification_model
+    return init_classification_model(arch, sequences=1, n_classes=3)
 
 
 def _surveys(arch):
     """(the multi-task survey, the classification-only survey) at the multi-task model's benchmark shape (bf16; nnUNetClassifier 64 x 256^2,
     UNetPlusPlusClassifier 32 x 256^2), each built (not run) once per session by tests/step_programs.py."""
-    import step_programs as SP
-
-    def build_cls(arch_, dtype, N, size, reserve_cus=0):
-        from multi_task_breast_cancer_amd.experiment_init import init_classification_model, init_optimizer
-        seed_everything(1993)
-        model = init_classification_model(arch_, sequences=1, n_classes=3).to(DEV)
-        model.set_compute(dtype)
-        model.coop_reserve_cus = reserve_cus
-        step = FusedTrainStep(model, init_optimizer(model, "Adam", 1e-4), n_classes=3)
-        return step._compiled(N, size, size), (step, model)
-
     program = next(p for p in SP.STEP_PROGRAMS if p[0] == _PROGRAMS[arch])
-    return SP.survey(program), SP.survey((arch,) + program[1:], build=build_cls)
-
-
-def _kernel_instances(survey):
-    import re
-    out = set()
-    for family in _NAMED:
-        for key in survey.seen[family]:
-            out |= {re.sub(r"\s*\[[^\]]*\]", "", part).strip() for part in key[1][0].split(" + ")}
-    return out
+    return SP.survey(program), SP.survey((arch,) + program[1:], build=SP.step_builder(_make_model, n_classes=3))
 
 
 @pytest.mark.parametrize("arch", list(_PROGRAMS))
@@ -546,20 +531,18 @@ def test_cls_only_programs_launch_a_subset_of_the_multitask_programs(arch):
     """The kernel instances the classification-only step programs launch at the benchmark shape are a subset of the multi-task programs'; what
     they add is the softmax op (3-class nnUNetClassifier: one forward and one backward launch of softmax_rows_kernel) and, outside the programs,
     the two metrics kernels this file tests above (train_metrics_samples_kernel through mtbc_cls_step_metrics, cls_test_rows_kernel)."""
-    import step_programs as SP
     mt, cl = _surveys(arch)
     for name in ("pack", "fwd", "loss", "bwd"):
         assert 0 < len(cl.kinds[name]) <= len(mt.kinds[name]), name
     softmax = [k for name in ("fwd", "bwd") for k in cl.kinds[name] if k == L.OP_SOFTMAX]
     assert len(softmax) == (2 if arch == "nnUNetClassifier" else 0) and L.OP_SOFTMAX not in mt.kinds["fwd"] + mt.kinds["bwd"]
     assert cl.kinds["loss"] == [L.OP_FOCAL, L.OP_LOSS_MIX]
-    have, allowed = _kernel_instances(cl), _kernel_instances(mt)
+    have, allowed = SP.kernel_instances(cl), SP.kernel_instances(mt)
     print(arch, len(have), "kernel instances of", len(allowed))
     assert len(have) >= 20, sorted(have)
     added = {"softmax_rows_kernel"} if arch == "nnUNetClassifier" else set()          # the one instance the docstring names, for the 3-class nnUNetClassifier only
     assert have - allowed == added, f"kernel instances of the classification-only programs that the multi-task programs do not launch: {sorted(have - allowed)}"
-    for family in set(SP.COLLECTORS) - set(_NAMED):
-        assert cl.seen[family] and set(cl.seen[family]) <= set(mt.seen[family]), (family, set(cl.seen[family]) - set(mt.seen[family]))
+    SP.assert_keys_subset(cl, mt, [f for f in SP.COLLECTORS if f not in SP.NAMED])
 
 
 def _pool_only_cases():
@@ -594,19 +577,4 @@ def test_cls_only_programs_launch_only_reference_tested_instances(arch):
     """Every coverage key of the classification-only step programs at the benchmark shape -- kernel instances AND the branches the arguments
     select, as tests/step_programs.py keys them -- is the key of a call that an element-wise fp64 reference test makes: the tables of
     tests/test_ops_gpu.py, plus the cases of `_pool_only_cases` above."""
-    import step_programs as SP
-    import test_loss_launches_gpu as LOSS
-    import test_ops_gpu as OPS
-    _, cl = _surveys(arch)
-    own = {(op, key) for case in _pool_only_cases() for op, _, key in OPS._inorm_case_calls(case)}
-    tested = {"conv3x3": OPS._reference_tested_conv3x3_keys(), "conv3x3-wgrad-plan": OPS._reference_tested_wgrad_plan_keys(),
-              "InstanceNorm": OPS._reference_tested_instnorm_keys() | own,
-              "transposed-convolution": OPS._reference_tested_convT_keys(), "small-op": OPS._reference_tested_small_op_keys(),
-              "layout": OPS._reference_tested_layout_keys(), "loss": LOSS._reference_tested_loss_keys()}
-    extra = []
-    for family in SP.COLLECTORS:
-        assert cl.seen[family], family
-        for key, (kind, where) in sorted(cl.seen[family].items(), key=repr):
-            if key not in tested[family]:
-                extra.append(f"\n  {family}: {kind} {key} at {where}")
-    assert not extra, "launches of the classification-only programs that no reference case makes:" + "".join(extra)
+    SP.assert_only_tested(_surveys(arch)[1], SP.reference_tested_keys(), SP.table_keys(inorm=_pool_only_cases()))

@@ -14,10 +14,10 @@ pytestmark = pytest.mark.gpu
 
 sys.path[:0] = [p for p in (os.path.dirname(os.path.abspath(__file__)),) if p not in sys.path]
 
+import step_programs as SP  # noqa: E402
 from multi_task_breast_cancer_amd import ops  # noqa: E402
 
 L = ops.L
-DEV = "cuda:0"
 PROGRAMS = [("Multi_BTSUNet-w24", "bf16", 16, 128), ("Multi_BTSUNet-w24", "f16", 16, 128), ("Multi_BTSUNet-w24", "f32", 2, 128)]
 F_, D_, W_ = L.OP_CONV3_FWD, L.OP_CONV3_DGRAD, L.OP_CONV3_WGRAD
 
@@ -34,20 +34,7 @@ def _bts_ops():
 
 def _survey(program):
     """The survey of one Multi_BTSUNet program, built (not run) once per session by tests/step_programs.py."""
-    import step_programs as SP
-
-    def build(arch, dtype, N, size, reserve_cus=0):
-        from multi_task_breast_cancer_amd.experiment_init import init_multitask_model, init_optimizer
-        from multi_task_breast_cancer_amd.miscellany import seed_everything
-        from multi_task_breast_cancer_amd.trainer import FusedTrainStep
-        seed_everything(1993)
-        model = init_multitask_model("Multi_BTSUNet", sequences=1, regions=1, n_classes=3, width=24, deep_supervision=True).to(DEV)
-        model.set_compute(dtype)
-        model.coop_reserve_cus = reserve_cus
-        step = FusedTrainStep(model, init_optimizer(model, "Adam", 1e-4), alpha=0.5, inversely_weighted=True)
-        return step._compiled(N, size, size), (step, model)
-
-    return SP.survey(program, build=build)
+    return SP.survey(program, build=SP.step_builder(lambda arch: SP.multitask_model("Multi_BTSUNet", width=24), alpha=0.5, inversely_weighted=True))
 
 
 # ------------------------------------------------------------------------------------------------ 3x3 convolution
@@ -159,7 +146,6 @@ WGRAD_PLAN_CASES = [
     (16, [1], 8, 32, 512, _P32),      # conv3x3_wgrad_smallcin_kernel + splitk_reduce (bands=4, splitk_reduce<16> x2)  [16 x 1 -> 12 @ 128 x 128 in bf16 and 1 more]
     (2, [1], 8, 32, 512, _P32),       # conv3x3_wgrad_smallcin_kernel + splitk_reduce (bands=4, splitk_reduce<4> x2)  [2 x 1 -> 12 @ 128 x 128 in f32]
 ]
-PLAN = "conv3x3-wgrad-plan"
 
 
 def _wgrad_plan_ids():
@@ -239,97 +225,34 @@ def test_weight_view_launches_match_the_layout_reference(case):
 
 # ------------------------------------------------------------------------------------------------ the guards
 def _own_keys():
-    """{family: {key: row}} of the calls the rows of this module's tables make, from dummy-pointer structs (nothing is launched)."""
-    import step_programs as SP
-    OPS = _ops_gpu()
-    own = {family: {} for family in SP.COLLECTORS}
-    for case in CONV3_CASES:
-        op, N, segs, Cout, H, W, mode = case
-        own["conv3x3"].setdefault((op, SP._conv3_key(ops.conv3x3_case_args(op, N, segs, Cout, H, W, **mode), op)), []).append(case)
-    for case in WGRAD_PLAN_CASES:
-        own[PLAN].setdefault((W_, SP._wgrad_plan_key(ops.conv3x3_case_args(W_, *case[:5], **case[5]))), []).append(case)
-    for case in INORM_CASES:
-        for op, _, key in OPS._inorm_case_calls(case):
-            own["InstanceNorm"].setdefault((op, key), []).append(case)
-    for case in WVIEW_CASES:
-        for path in ("single", "many"):
-            own["layout"].setdefault(SP._wview_key(*case, path), []).append(case)
-    return own
+    return SP.table_keys(conv3=CONV3_CASES, wgrad_plan=WGRAD_PLAN_CASES, inorm=INORM_CASES, wview=WVIEW_CASES)
 
 
-def _borrowed_small_op_keys():
-    """(op kind, key) of the up-sampling and wide-Linear calls that the fp64 / bit-for-bit cases of tests/test_mt_btsunet_ops_gpu.py make."""
-    import step_programs as SP
+def _borrowed_keys():
+    """{"small-op": (op kind, key) of the up-sampling and wide-Linear calls that the fp64 / bit-for-bit cases of tests/test_mt_btsunet_ops_gpu.py make}"""
     OPS, BTS = _ops_gpu(), _bts_ops()
     made = BTS.up2_case_ops() + [op for case in BTS._WIDE_CASES for op in OPS._small_case_ops(case)]
-    return {(op.kind, SP._small_op_key(op)) for op in made}
-
-
-def _tested():
-    """{family: (the keys of the older tables -- tests/test_ops_gpu.py's, for the loss family tests/test_loss_launches_gpu.py's --, the keys this
-    module adds)}"""
-    import test_loss_launches_gpu as LOSS
-    OPS, own = _ops_gpu(), _own_keys()
-    old = {"conv3x3": OPS._reference_tested_conv3x3_keys(), PLAN: OPS._reference_tested_wgrad_plan_keys(), "InstanceNorm": OPS._reference_tested_instnorm_keys(),
-           "transposed-convolution": OPS._reference_tested_convT_keys(), "small-op": OPS._reference_tested_small_op_keys(),
-           "layout": OPS._reference_tested_layout_keys(), "loss": LOSS._reference_tested_loss_keys()}
-    new = {family: set(keys) for family, keys in own.items()}
-    new["small-op"] |= _borrowed_small_op_keys()
-    return {family: (old[family], new[family]) for family in old}
+    return {"small-op": {(op.kind, SP._small_op_key(op)) for op in made}}
 
 
 @pytest.mark.parametrize("program", PROGRAMS, ids=[p[1] for p in PROGRAMS])
 def test_mt_btsunet_programs_launch_only_reference_tested_instances(program):
     """Every coverage key of the Multi_BTSUNet step program -- kernel instances AND the branches the arguments select, as
     tests/step_programs.py keys them -- is the key of a call that an element-wise reference test makes: the tables of tests/test_ops_gpu.py
-    and tests/test_loss_launches_gpu.py, the rows of this module, and for the up-sampling and the wide Linear the cases of tests/test_mt_btsunet_ops_gpu.py."""
-    import step_programs as SP
-    s, tested, own, missing = _survey(program), _tested(), _own_keys(), []
-    for family in SP.COLLECTORS:
-        seen, (old, new) = s.seen[family], tested[family]
-        assert seen, f"{program}: no {family} launch found"
-        table = "tests/test_loss_launches_gpu.py" if family == "loss" else "tests/test_ops_gpu.py"
-        print(f"{program} {family}: {len(seen)} keys, {sum(k in old for k in seen)} tested by {table}'s tables, "
-              f"{sum(k in new and k not in old for k in seen)} by the rows added for this model, {sum(k not in old and k not in new for k in seen)} missing")
-        for key, (kind, where) in sorted(seen.items(), key=repr):
-            by = table if key in old else "MISSING" if key not in new else \
-                f"row {own[family][key][0]}" if key in own[family] else "tests/test_mt_btsunet_ops_gpu.py"
-            print(f"  {kind} {key} at {where}  <- {by}")
-            if by == "MISSING":
-                missing.append(f"\n  {family}: {kind} {key} at {where}")
-    assert not missing, f"launches of {program} that no reference case makes:" + "".join(missing)
+    and tests/test_loss_launches_gpu.py, the rows of this module, and for the up-sampling and the wide Linear the cases of tests/test_mt_btsunet_ops_gpu.py.
+    The print-out is profiles/mt_btsunet_step_keys.txt."""
+    SP.assert_only_tested(_survey(program), SP.reference_tested_keys(), _own_keys(), _borrowed_keys(), "tests/test_mt_btsunet_ops_gpu.py")
 
 
 def test_mt_btsunet_cases_are_all_needed():
     """Every row of this module's tables makes a key that a surveyed program launches, that no table of tests/test_ops_gpu.py makes and that no
     other row makes: no dead and no double rows, and deleting one fails the guard above."""
-    import step_programs as SP
-    surveys, tested, bad = [_survey(p) for p in PROGRAMS], _tested(), []
-    for family, keys in _own_keys().items():
-        launched = set().union(*(s.seen[family] for s in surveys))
-        rows = {}
-        for key, cases in keys.items():
-            for case in cases:
-                rows.setdefault(repr(case), []).append(key)
-            if len(cases) > 1:
-                bad.append(f"\n  {family}: {len(cases)} rows make {key}: {cases}")
-        for row, ks in rows.items():
-            if not any(k in launched and k not in tested[family][0] for k in ks):
-                bad.append(f"\n  {family}: no program launches, or an older table already makes, {ks} of row {row}")
-        print(f"{family}: {len(rows)} rows, {len(keys)} keys")
-    assert len(CONV3_CASES) + len(WGRAD_PLAN_CASES) + len(INORM_CASES) + len(WVIEW_CASES) > 0 and set(_own_keys()) == set(SP.COLLECTORS)
-    assert not bad, "rows of tests/test_mt_btsunet_launches_gpu.py that are not needed:" + "".join(bad)
+    SP.assert_rows_needed("tests/test_mt_btsunet_launches_gpu.py", [_survey(p) for p in PROGRAMS], SP.reference_tested_keys(), _own_keys(),
+                          [CONV3_CASES, WGRAD_PLAN_CASES, INORM_CASES, WVIEW_CASES])
 
 
 def test_every_op_kind_of_the_mt_btsunet_programs_is_claimed():
     """The op kinds of the three programs are those tests/test_ops_gpu.py's OP_KIND_COVERED_BY claims, plus the two up-sampling kinds, which
-    the first guard of this module claims."""
-    OPS = _ops_gpu()
-    name_of = {getattr(L, n): n for n in dir(L) if n.startswith("OP_") and isinstance(getattr(L, n), int)}
-    claimed = set(OPS.OP_KIND_COVERED_BY) | {"OP_UPSAMPLE2_FWD", "OP_UPSAMPLE2_BWD"}
-    for program in PROGRAMS:
-        kinds = {kind for oplist in _survey(program).kinds.values() for kind in oplist}
-        print(f"{program}: {sorted(name_of.get(k, str(k)) for k in kinds)}")
-        assert {L.OP_UPSAMPLE2_FWD, L.OP_UPSAMPLE2_BWD} <= kinds, f"{program}: no up-sampling op"
-        unclaimed = sorted(name_of.get(k, str(k)) for k in kinds if name_of.get(k) not in claimed)
-        assert not unclaimed, f"op kinds of {program} that no test answers for: {unclaimed}"
+    the first guard of this module claims and every program must hold."""
+    SP.assert_op_kinds_claimed([_survey(p) for p in PROGRAMS], claimed_also=("OP_UPSAMPLE2_FWD", "OP_UPSAMPLE2_BWD"),
+                               required=(L.OP_UPSAMPLE2_FWD, L.OP_UPSAMPLE2_BWD))

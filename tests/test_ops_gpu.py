@@ -12,8 +12,9 @@ pytestmark = pytest.mark.gpu
 
 from multi_task_breast_cancer_amd import ops  # noqa: E402
 from oracle import torch_oracle as O  # noqa: E402
-from step_programs import (STEP_PROGRAMS, _c8_key, _conv3_key, _convT_key, _dparam_key, _instnorm_key, _pack_key,  # noqa: E402
-                           _small_op_key, _wgrad_plan_key, _wview_key, assert_all_tested, survey)
+from step_programs import (COLLECTORS, PLAN, STEP_PROGRAMS, _c8_key, _conv3_key, _convT_key, _dparam_key, _instnorm_key, _pack_key,  # noqa: E402
+                           _small_op_key, _wgrad_plan_key, _wview_key, assert_all_tested, assert_op_kinds_claimed, assert_rows_needed, survey,
+                           table_keys)
 
 DEV = "cuda:0"
 
@@ -1836,17 +1837,8 @@ def test_step_programs_launch_only_reference_tested_wgrad_plans():
 def test_wgrad_plan_cases_are_all_needed():
     """Every row of WGRAD_PLAN_CASES makes a plan key that a surveyed program launches, that no older table makes and that no other row
     makes: no dead and no double rows, and deleting one fails the guard above."""
-    launched = set().union(*(s.seen["conv3x3-wgrad-plan"] for s in _wgrad_plan_surveys()))
-    older, rows, bad = _older_wgrad_plan_keys(), {}, []
-    for case in WGRAD_PLAN_CASES:
-        rows.setdefault((W_, _wgrad_plan_key(ops.conv3x3_case_args(W_, *case[:5], **case[5]))), []).append(case)
-    for key, cases in rows.items():
-        if len(cases) > 1:
-            bad.append(f"\n  {len(cases)} rows make {key}: {cases}")
-        if key not in launched or key in older:
-            bad.append(f"\n  {'no program launches' if key not in launched else 'an older table already makes'} {key} of row {cases[0]}")
-    print(f"{len(WGRAD_PLAN_CASES)} rows, {len(rows)} plan keys, {len(launched)} launched, {len(older)} made by the older tables")
-    assert WGRAD_PLAN_CASES and not bad, "rows of WGRAD_PLAN_CASES that are not needed:" + "".join(bad)
+    older = {**dict.fromkeys(COLLECTORS, ()), PLAN: _older_wgrad_plan_keys()}
+    assert_rows_needed("WGRAD_PLAN_CASES", _wgrad_plan_surveys(), older, table_keys(wgrad_plan=WGRAD_PLAN_CASES), [WGRAD_PLAN_CASES])
 
 
 # ------------------------------------------------------------------ the InstanceNorm + LeakyReLU launches of the step programs, element by element
@@ -3414,11 +3406,4 @@ def test_every_op_kind_of_the_step_programs_is_claimed_by_a_test():
         assert name in name_of.values(), f"{name} is no op kind"
         text = open(os.path.join(root, path)).read()
         assert re.search(rf"^def {test}\(", text, re.M), f"{name}: {path} has no {test}"
-    present = set()
-    for arch, dtype, N, size in STEP_PROGRAMS:
-        kinds = {kind for oplist in survey((arch, dtype, N, size)).kinds.values() for kind in oplist}
-        print(f"{arch} {dtype} N={N} {size}x{size}: {sorted(name_of[k] for k in kinds)}")
-        present |= kinds
-    unclaimed = sorted(name_of.get(k, str(k)) for k in present if name_of.get(k) not in OP_KIND_COVERED_BY)
-    print(f"{len(present)} op kinds in the four programs, {len(OP_KIND_COVERED_BY)} claimed")
-    assert not unclaimed, f"op kinds of the step programs that no test answers for: {unclaimed}"
+    assert_op_kinds_claimed([survey(p) for p in STEP_PROGRAMS])

@@ -18,6 +18,7 @@ from multi_task_breast_cancer_amd.nets import MTnnUNet, nnUNet  # noqa: E402
 from multi_task_breast_cancer_amd.optim import FusedAdam, FusedAdamW, FusedSGD  # noqa: E402
 from multi_task_breast_cancer_amd.trainer import FusedEvalStep, FusedTrainStep, SegTrainMetrics, _dice  # noqa: E402
 from oracle import torch_oracle as O  # noqa: E402
+import step_programs as SP  # noqa: E402
 
 DEV = torch.device("cuda:0")
 TOL = 1e-4          # tests/test_model_gpu.py
@@ -311,51 +312,16 @@ def test_refusals():
 
 
 # ------------------------------------------------------------------------------------------------ 8
+def _make_model(arch):
+    from multi_task_breast_cancer_amd.experiment_init import init_segmentation_model
+    return init_segmentation_model(arch, sequences=1, regions=1)
+
+
 def _surveys():
     """(the MTnnUNet survey, the segmentation-only survey) of the benchmark shape (BASELINE.json configs[2]: bf16, N 64, 256 x 256), each built
     (not run) once per session by tests/step_programs.py."""
-    import step_programs as SP
-
-    def build_seg(arch, dtype, N, size, reserve_cus=0):
-        from multi_task_breast_cancer_amd.experiment_init import init_optimizer, init_segmentation_model
-        seed_everything(1993)
-        model = init_segmentation_model(arch, sequences=1, regions=1).to(DEV)
-        model.set_compute(dtype)
-        model.coop_reserve_cus = reserve_cus
-        step = FusedTrainStep(model, init_optimizer(model, "Adam", 1e-4), inversely_weighted=True)
-        return step._compiled(N, size, size), (step, model)
-
     program = next(p for p in SP.STEP_PROGRAMS if p[0] == "MTnnUNet")
-    return SP.survey(program), SP.survey(("nnUNet",) + program[1:], build=build_seg)
-
-
-def _keys_outside(seg, allowed):
-    """The launches of the segmentation-only survey whose coverage key is not in allowed[family], one line each."""
-    import step_programs as SP
-    extra = []
-    for family in SP.COLLECTORS:
-        assert seg.seen[family], family
-        for key, (kind, where) in sorted(seg.seen[family].items(), key=repr):
-            if key not in allowed[family]:
-                extra.append(f"\n  {family}: {kind} {key} at {where}")
-        print(family, len(seg.seen[family]), "keys, allowed", len(allowed[family]))
-    return extra
-
-
-_NAMED = ("conv3x3", "conv3x3-wgrad-plan", "InstanceNorm", "transposed-convolution", "small-op", "loss")      # the families whose keys carry a kernel-name string
-
-
-def _kernel_instances(survey):
-    """The set of kernel instances a surveyed step's programs launch, from the strings of mtbc_conv3x3_kernel_name / _instnorm_ / _convT_ /
-    _op_kernel_name that tests/step_programs.py keeps in its keys: launches are joined by " + ", and what stands in brackets behind an
-    instance is what the arguments select inside it (common.h, OpChoice), not part of the instance."""
-    import re
-    out = set()
-    for family in _NAMED:
-        for key in survey.seen[family]:
-            name = key[1][0]
-            out |= {re.sub(r"\s*\[[^\]]*\]", "", part).strip() for part in name.split(" + ")}
-    return out
+    return SP.survey(program), SP.survey(("nnUNet",) + program[1:], build=SP.step_builder(_make_model, inversely_weighted=True))
 
 
 def test_seg_only_programs_launch_a_subset_of_the_mtnnunet_programs():
@@ -367,24 +333,15 @@ def test_seg_only_programs_launch_a_subset_of_the_mtnnunet_programs():
     mt, seg = _surveys()
     for name in ("pack", "fwd", "loss", "bwd"):
         assert 0 < len(seg.kinds[name]) <= len(mt.kinds[name]), name
-    have, allowed = _kernel_instances(seg), _kernel_instances(mt)
+    have, allowed = SP.kernel_instances(seg), SP.kernel_instances(mt)
     print(len(have), "kernel instances of", len(allowed))
     assert len(have) >= 30, sorted(have)                       # the names did parse into instances
     assert have <= allowed, f"kernel instances of the segmentation-only programs that the MTnnUNet programs do not launch: {sorted(have - allowed)}"
-    import step_programs as SP
-    for family in set(SP.COLLECTORS) - set(_NAMED):            # the layout ops have no kernel-name function: their keys, as they are
-        assert seg.seen[family] and set(seg.seen[family]) <= set(mt.seen[family]), (family, set(seg.seen[family]) - set(mt.seen[family]))
+    SP.assert_keys_subset(seg, mt, [f for f in SP.COLLECTORS if f not in SP.NAMED])          # the layout ops have no kernel-name function: their keys, as they are
 
 
 def test_seg_only_programs_launch_only_reference_tested_instances():
     """No untested launch enters: every coverage key of the segmentation-only step programs at the benchmark shape -- kernel instances AND
     the branches the arguments select, as tests/step_programs.py keys them -- is the key of a call that an element-wise reference test of
     tests/test_ops_gpu.py makes, the sets its own guards hold the MTnnUNet and U-Net++ programs to."""
-    import test_loss_launches_gpu as LOSS
-    import test_ops_gpu as OPS
-    _, seg = _surveys()
-    tested = {"conv3x3": OPS._reference_tested_conv3x3_keys(), "conv3x3-wgrad-plan": OPS._reference_tested_wgrad_plan_keys(), "InstanceNorm": OPS._reference_tested_instnorm_keys(),
-              "transposed-convolution": OPS._reference_tested_convT_keys(), "small-op": OPS._reference_tested_small_op_keys(),
-              "layout": OPS._reference_tested_layout_keys(), "loss": LOSS._reference_tested_loss_keys()}
-    extra = _keys_outside(seg, tested)
-    assert not extra, "launches of the segmentation-only programs that no reference case makes:" + "".join(extra)
+    SP.assert_only_tested(_surveys()[1], SP.reference_tested_keys(), SP.table_keys())

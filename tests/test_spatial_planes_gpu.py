@@ -422,16 +422,11 @@ FIVE = [(arch, dtype) for arch in ("MTUNetPlusPlus", "MTnnUNet") for dtype in ("
 
 
 def _build_with_channels(cin):
-    def build(arch, dtype, N, size, reserve_cus=0):
-        from multi_task_breast_cancer_amd.experiment_init import init_multitask_model, init_optimizer
-        seed_everything(1993)
-        model = init_multitask_model(arch.split("-")[0], sequences=cin, regions=1, n_classes=3, deep_supervision=True).to(DEV)
+    def make_model(arch):
+        model = SP.multitask_model(arch.split("-")[0], sequences=cin)
         assert model.in_channels == cin
-        model.set_compute(dtype)
-        model.coop_reserve_cus = reserve_cus
-        step = FusedTrainStep(model, init_optimizer(model, "Adam", 1e-4), alpha=0.5, inversely_weighted=True)
-        return step._compiled(N, size, size), (step, model)
-    return build
+        return model
+    return SP.step_builder(make_model, alpha=0.5, inversely_weighted=True)
 
 
 def five_channel_listing(arch, dtype):
@@ -474,7 +469,6 @@ WGRAD_PLAN_CASES = [
     (24, [7], 8, 8, 8, dict(bias=False)),              # conv3x3_wgrad_direct_kernel + splitk_reduce (images>1, splitk_reduce<4> x2)  [32 x 7 -> 24 @ 256 x 256 in MTUNetPlusPlus bf16 / f32, 64 x 7 -> 32 in MTnnUNet bf16]
     (8, [7], 8, 8, 8, dict(bias=False)),               # conv3x3_wgrad_direct_kernel + splitk_reduce (splitk_reduce<4> x2)  [16 x 7 -> 24 @ 512 x 512 in MTUNetPlusPlus f16]
 ]
-PLAN = "conv3x3-wgrad-plan"
 # (backward, N, C, H, W, mode) as in INORM_CASES.  The team size follows the plane (T = 32 at 256 x 256, 128 at 512 x 512); reserve_cus leaves one
 # team resident so that two items take two rounds, as that file's backward team cases do.  The fp32 backward: the largest plane of the register
 # kernel (65000 elements) without parameters, the smallest above it (66560) with them.
@@ -491,11 +485,6 @@ INORM_CASES = [
 def _ops_gpu():
     import test_ops_gpu as OPS
     return OPS
-
-
-def _loss_gpu():
-    import test_loss_launches_gpu as LOSS
-    return LOSS
 
 
 @pytest.mark.parametrize("case", CONV3_CASES, ids=lambda c: _ops_gpu()._conv3_case_id(c))
@@ -518,25 +507,7 @@ def _survey7(program):
 
 
 def _own_keys():
-    """{family: {key: [row]}} of the calls the rows above make, from dummy-pointer structs (nothing is launched)."""
-    OPS = _ops_gpu()
-    own = {family: {} for family in SP.COLLECTORS}
-    for case in CONV3_CASES:
-        op, N, segs, Cout, H, W, mode = case
-        own["conv3x3"].setdefault((op, SP._conv3_key(ops.conv3x3_case_args(op, N, segs, Cout, H, W, **mode), op)), []).append(case)
-    for case in WGRAD_PLAN_CASES:
-        own[PLAN].setdefault((W_, SP._wgrad_plan_key(ops.conv3x3_case_args(W_, *case[:5], **case[5]))), []).append(case)
-    for case in INORM_CASES:
-        for op, _, key in OPS._inorm_case_calls(case):
-            own["InstanceNorm"].setdefault((op, key), []).append(case)
-    return own
-
-
-def _older_keys():
-    OPS = _ops_gpu()
-    return {"conv3x3": OPS._reference_tested_conv3x3_keys(), PLAN: OPS._reference_tested_wgrad_plan_keys(),
-            "InstanceNorm": OPS._reference_tested_instnorm_keys(), "transposed-convolution": OPS._reference_tested_convT_keys(), "small-op": OPS._reference_tested_small_op_keys(),
-            "layout": OPS._reference_tested_layout_keys(), "loss": _loss_gpu()._reference_tested_loss_keys()}
+    return SP.table_keys(conv3=CONV3_CASES, wgrad_plan=WGRAD_PLAN_CASES, inorm=INORM_CASES)
 
 
 @pytest.mark.parametrize("program", PROGRAMS7, ids=["-".join(map(str, p)) for p in PROGRAMS7])
@@ -544,35 +515,13 @@ def test_seven_channel_programs_launch_only_reference_tested_instances(program):
     """Every coverage key of the 7-channel step program -- kernel instances AND the branches the arguments select, as tests/step_programs.py
     keys them -- is the key of a call that an element-wise reference test makes: the tables of tests/test_ops_gpu.py and
     tests/test_loss_launches_gpu.py or the rows above."""
-    s, old, own, missing = _survey7(program), _older_keys(), _own_keys(), []
+    s = _survey7(program)
     assert any(where[1] == 7 for (kind, where) in s.seen["conv3x3"].values()), "no 7-channel conv in the program"
-    for family in SP.COLLECTORS:
-        seen = s.seen[family]
-        assert seen, f"{program}: no {family} launch found"
-        print(f"{program} {family}: {len(seen)} keys, {sum(k in old[family] for k in seen)} tested by the tables of "
-              f"{'tests/test_loss_launches_gpu.py' if family == 'loss' else 'tests/test_ops_gpu.py'}, "
-              f"{sum(k in own[family] and k not in old[family] for k in seen)} by the rows of this module")
-        for key, (kind, where) in sorted(seen.items(), key=repr):
-            if key not in old[family] and key not in own[family]:
-                missing.append(f"\n  {family}: {kind} {key} at {where}")
-    assert not missing, f"launches of {program} that no reference case makes:" + "".join(missing)
+    SP.assert_only_tested(s, SP.reference_tested_keys(), _own_keys())
 
 
 def test_seven_channel_rows_are_all_needed():
     """Every row above makes a key that a surveyed program launches, that no table of tests/test_ops_gpu.py makes and that no other row makes:
     no dead and no double rows, and deleting one fails the guard above."""
-    surveys, old, bad = [_survey7(p) for p in PROGRAMS7], _older_keys(), []
-    for family, keys in _own_keys().items():
-        launched = set().union(*(s.seen[family] for s in surveys))
-        rows = {}
-        for key, cases in keys.items():
-            for case in cases:
-                rows.setdefault(repr(case), []).append(key)
-            if len(cases) > 1:
-                bad.append(f"\n  {family}: {len(cases)} rows make {key}: {cases}")
-        for row, ks in rows.items():
-            if not any(k in launched and k not in old[family] for k in ks):
-                bad.append(f"\n  {family}: no program launches, or an older table already makes, {ks} of row {row}")
-        print(f"{family}: {len(rows)} rows, {len(keys)} keys")
-    assert len(CONV3_CASES) + len(WGRAD_PLAN_CASES) + len(INORM_CASES) == sum(len({repr(c) for cs in keys.values() for c in cs}) for keys in _own_keys().values())
-    assert not bad, "rows of this module that are not needed:" + "".join(bad)
+    SP.assert_rows_needed("tests/test_spatial_planes_gpu.py", [_survey7(p) for p in PROGRAMS7], SP.reference_tested_keys(), _own_keys(),
+                          [CONV3_CASES, WGRAD_PLAN_CASES, INORM_CASES])

@@ -1,6 +1,8 @@
 """tests/step_programs.py -- the survey of a step program and the compare-and-report behind the launch-coverage guards of tests/test_ops_gpu.py --
 on hand-made programs: the walks that carry state (the ConvT pair, the run of layout ops), the conv3x3, up-sampling and loss keys flag by flag, the session cache and
-the failure messages.  mtbc_conv3x3_kernel_name, mtbc_convT_kernel_name and mtbc_op_kernel_name are host-only; no device, no step is built."""
+the failure messages; and the guards of the further models' launch modules (assert_only_tested, assert_rows_needed, table_keys, kernel_instances,
+assert_keys_subset, assert_op_kinds_claimed), one test per way each can fail.  mtbc_conv3x3_kernel_name, mtbc_convT_kernel_name and
+mtbc_op_kernel_name are host-only, mtbc_instnorm_kernel_name is for one-workgroup launches; no device, no step is built."""
 import types
 
 import pytest
@@ -531,3 +533,178 @@ def test_report_names_the_program_without_a_required_kind():
 def test_report_passes_when_every_key_is_tested():
     whole = _survey("report: whole", {"fwd": [_convT(L.OP_CONVT_FWD)], "bwd": [_convT(L.OP_CONVT_WGRAD), _convT(L.OP_CONVT_DGRAD)]})
     SP.assert_all_tested(CONVT, set(whole.seen[CONVT]) | {("fwd", "another key")}, [whole], required=("fwd", "pair"))
+
+
+# ---- the guards of a further model's launch module, on a hand-made program with one launch of every family and hand-made tables
+_FP = dict(compute=2, out="c8", z="c8", affine=False)          # the fp16 mode without affine parameters: one-workgroup launches at 12 x 20
+
+
+def _whole(label, without=()):
+    """The survey of a hand-made step with a launch of every family but those of `without`."""
+    wg, norm = _mk(W_), _mk(L.OP_IN_BWD)
+    wg.u.conv3 = _c3(W_, **_WB)
+    ops.instnorm_case_args(True, 2, 16, 12, 20, **_FP, into=norm.u.inorm)
+    made = {"conv3x3": wg, "InstanceNorm": norm, CONVT: _convT(L.OP_CONVT_FWD), SMALL: ops.gap_case_args(L.OP_GAP_FWD, 2, 8, 4, 4),
+            LAYOUT: _pack(L.OP_CONV3_PACK_FWD), "loss": ops.dice_case_args(DF_, *_DICE)}
+    s = _survey(label, {"fwd": [op for family, op in made.items() if family not in without]})
+    assert all(bool(s.seen[family]) == (family not in without and not (family == PLAN and "conv3x3" in without)) for family in SP.COLLECTORS)
+    return s
+
+
+def _older(s, but=()):
+    """{family: the keys the survey saw}, the families of `but` empty: older tables that answer for everything else."""
+    return {family: set() if family in but else set(seen) for family, seen in s.seen.items()}
+
+
+def _rows(**made):
+    """{family: {key: [row]}} over every family, as table_keys gives it."""
+    return {family: dict(made.get(family, {})) for family in SP.COLLECTORS}
+
+
+def _only(s, family):
+    (key, (kind, where)), = s.seen[family].items()
+    return key, kind, where
+
+
+def test_only_tested_passes_and_names_the_row_that_answers(capsys):
+    s = _whole("guard: passes")
+    key, kind, where = _only(s, CONVT)
+    SP.assert_only_tested(s, _older(s, but=[CONVT]), _rows(**{CONVT: {key: [("fwd", "row A"), ("fwd", "row B")]}}))
+    out = capsys.readouterr().out
+    assert f"{s.program} {CONVT}: 1 keys, 0 tested by tests/test_ops_gpu.py's tables, 1 by the rows added for this model, 0 missing\n" in out
+    assert f"  {kind} {key} at {where}  <- row ('fwd', 'row A')\n" in out
+    assert f"{s.program} loss: 1 keys, 1 tested by tests/test_loss_launches_gpu.py's tables, 0 by the rows added for this model, 0 missing\n" in out
+    assert out.count("<- tests/test_ops_gpu.py\n") == 5 and out.count("<- tests/test_loss_launches_gpu.py\n") == 1 and "MISSING" not in out
+
+
+def test_only_tested_names_a_launch_in_no_table_with_family_kind_key_and_where(capsys):
+    s = _whole("guard: missing")
+    key, kind, where = _only(s, CONVT)
+    with pytest.raises(AssertionError) as e:
+        SP.assert_only_tested(s, _older(s, but=[CONVT]), _rows())
+    assert str(e.value) == f"launches of {s.program} that no reference case makes:\n  {CONVT}: {kind} {key} at {where}"
+    assert f"  {kind} {key} at {where}  <- MISSING\n" in capsys.readouterr().out
+
+
+def test_only_tested_names_a_family_without_a_launch():
+    s = _whole("guard: no layout op", without=[LAYOUT])
+    with pytest.raises(AssertionError) as e:
+        SP.assert_only_tested(s, _older(s), _rows())
+    assert str(e.value) == f"{s.program}: no {LAYOUT} launch found"
+
+
+def test_only_tested_attributes_a_borrowed_key_to_its_file(capsys):
+    s = _whole("guard: borrowed")
+    key, kind, where = _only(s, SMALL)
+    SP.assert_only_tested(s, _older(s, but=[SMALL]), _rows(), borrowed={SMALL: {key}}, borrowed_from="tests/test_of_the_model_gpu.py")
+    out = capsys.readouterr().out
+    assert f"  {kind} {key} at {where}  <- tests/test_of_the_model_gpu.py\n" in out and "1 by the rows added for this model, 0 missing" in out
+    with pytest.raises(AssertionError, match="no reference case"):          # ... and to nothing without it
+        SP.assert_only_tested(s, _older(s, but=[SMALL]), _rows())
+
+
+def test_rows_needed_passes_for_one_row_per_launched_key_no_older_table_makes():
+    s = _whole("guard: rows")
+    row, view = ("fwd", "row A"), ("a view", 1)
+    own = _rows(**{CONVT: {_only(s, CONVT)[0]: [row]}, LAYOUT: {_only(s, LAYOUT)[0]: [view], "a key of the other path": [view]}})
+    SP.assert_rows_needed("the tables", [s], _older(s, but=[CONVT, LAYOUT]), own, [[row], [view]])          # one of a row's keys is enough
+    with pytest.raises(AssertionError):          # every family, as table_keys gives them
+        SP.assert_rows_needed("the tables", [s], _older(s, but=[CONVT, LAYOUT]), {CONVT: own[CONVT]}, [[row]])
+
+
+def _rows_needed_message(label, keys, tables, older_has=False):
+    s = _whole(label)
+    with pytest.raises(AssertionError) as e:
+        SP.assert_rows_needed("the tables", [s], _older(s, but=[] if older_has else [CONVT]), _rows(**{CONVT: keys(_only(s, CONVT)[0])}), tables)
+    assert str(e.value).startswith("rows of the tables that are not needed:\n"), str(e.value)
+    return str(e.value)
+
+
+def test_rows_needed_reports_a_row_whose_key_no_program_launches():
+    row, dead = ("fwd", "row A"), ("fwd", "a dead row")
+    msg = _rows_needed_message("guard: dead row", lambda key: {key: [row], ("fwd", "another key"): [dead]}, [[row, dead]])
+    assert f"{CONVT}: no program launches ('fwd', 'another key') of row {dead}" in msg and "row A" not in msg and "already" not in msg
+
+
+def test_rows_needed_reports_a_row_whose_key_an_older_table_makes():
+    row = ("fwd", "row A")
+    msg = _rows_needed_message("guard: older row", lambda key: {key: [row]}, [[row]], older_has=True)
+    assert f"{CONVT}: an older table already makes ('fwd', " in msg and f"of row {row}" in msg and "no program launches" not in msg
+
+
+def test_rows_needed_reports_two_rows_with_one_key():
+    rows = [("fwd", "row A"), ("fwd", "row B")]
+    msg = _rows_needed_message("guard: double row", lambda key: {key: rows}, [rows])
+    assert f"{CONVT}: 2 rows make ('fwd', " in msg and str(rows) in msg
+    msg = _rows_needed_message("guard: double row", lambda key: {key: rows[:1] * 2}, [rows[:1] * 2])          # the same row twice
+    assert f"{CONVT}: 2 rows make ('fwd', " in msg and "2 rows in the tables, 1 distinct rows that make a key" in msg
+
+
+def test_rows_needed_reports_a_row_that_makes_no_key():
+    row, mute = ("fwd", "row A"), ("fwd", "a row without a key")
+    msg = _rows_needed_message("guard: mute row", lambda key: {key: [row]}, [[row, mute]])
+    assert f"no key is made by row {mute}" in msg and "2 rows in the tables, 1 distinct rows that make a key" in msg and "row A" not in msg
+
+
+def test_rows_needed_reports_an_empty_table():
+    row = ("fwd", "row A")
+    msg = _rows_needed_message("guard: empty table", lambda key: {key: [row]}, [[row], []])
+    assert msg.endswith("\n  table 2 of 2 is empty")
+
+
+def test_table_keys_are_the_key_functions_on_the_rows():
+    """Three rows per family against the key functions called directly (the InstanceNorm rows: one-workgroup launches, which the name query
+    answers without a device)."""
+    import test_ops_gpu as OPS
+    conv3 = [(F_, 4, [32, 32], 32, 512, 48, dict(compute=1, c8=True, bias=False, out_accumulate=True)), (D_, 2, [24], 12, 20, 48, dict(accumulate=[0])),
+             (W_, 3, [1], 32, 8, 8, dict(bias=False))]
+    plans = [(4, [32], 64, 512, 48, _WB), (1, [7], 8, 8, 8, dict(bias=False)), (48, [96], 128, 16, 16, _WB)]
+    inorm = [(False, 2, 16, 12, 20, dict(_FP, stats_slots=64, pool=True)), (True, 2, 16, 12, 20, _FP), (True, 2, 3, 12, 20, dict(affine=False, inplace=True))]
+    convT = [("fwd", 2, 64, 32, 8, 8, 2, {}, ()), ("dgrad", 2, 48, 24, 8, 8, 2, dict(acc_dx=True), ()), ("pair", 3, 48, 48, 16, 24, 2, {}, ())]
+    wview = [(12, 8, 0, 8, 1, 28, 40), (8, 24, 16, 8, 1, 0, 40), (8, 24, 0, 24, 0, 0, 8)]
+    own = SP.table_keys(conv3=conv3, wgrad_plan=plans, inorm=inorm, convT=convT, wview=wview)
+    assert set(own) == set(SP.COLLECTORS) and not own[SMALL] and not own["loss"]
+    assert own["conv3x3"] == {(c[0], SP._conv3_key(_c3(c[0], c[1], c[2], c[3], c[4], c[5], **c[6]), c[0])): [c] for c in conv3}
+    assert own[PLAN] == {(W_, _plan(*c[:5], **c[5])): [c] for c in plans}
+    assert own["InstanceNorm"] == {(L.OP_IN_BWD if c[0] else L.OP_IN_FWD, SP._instnorm_key(OPS._inorm_args(*c), c[0])): [c] for c in inorm}
+    ct = {"fwd": L.OP_CONVT_FWD, "dgrad": L.OP_CONVT_DGRAD}
+    assert own[CONVT] == {
+        **{(c[0], SP._convT_key(ops.convT_case_args(ct[c[0]], *c[1:7], **c[7]), ct[c[0]])): [c] for c in convT[:2]},
+        ("pair", SP._convT_key(ops.convT_case_args(L.OP_CONVT_WGRAD, 3, 48, 48, 16, 24, 2), L.OP_CONVT_WGRAD, ops.convT_case_args(L.OP_CONVT_DGRAD, 3, 48, 48, 16, 24, 2))): [convT[2]]}
+    assert own[LAYOUT] == {SP._wview_key(*c, path): [c] for c in wview for path in ("single", "many")}
+    assert all(len(keys) == (6 if family == LAYOUT else 3) for family, keys in own.items() if keys)
+    assert SP.table_keys() == _rows()
+
+
+def test_kernel_instances_are_the_launches_of_the_name_strings_without_their_brackets():
+    seen = {family: {} for family in SP.COLLECTORS}
+    seen["InstanceNorm"] = {(7, ("a<1, 2> [T=8 rounds=1] + b", ("affine",))): (7, (2, 8))}
+    seen["conv3x3"] = {(1, ("c<false, 0> + b", ())): (1, ()), (2, ("c<false, 0> + d [threads=64]", ("segs>1",))): (2, ())}
+    seen[LAYOUT] = {("fwd", 0, 0, False, False, 0, "single"): (3, ())}          # no name string: not looked at
+    assert SP.kernel_instances(SP.Survey(("hand-made",), 0, {}, seen, {})) == {"a<1, 2>", "b", "c<false, 0>", "d"}
+    s = _whole("guard: instances")          # ... and on the name queries' own strings: a launch and the reduction behind it
+    assert {"conv3x3_wgrad_c8_kernel<false, 0>", "splitk_reduce"} <= SP.kernel_instances(s) and not any("[" in i or "+" in i for i in SP.kernel_instances(s))
+
+
+def test_keys_subset_names_the_extra_key_and_a_family_without_a_launch():
+    whole, part = _whole("guard: whole"), _whole("guard: part", without=[LAYOUT])
+    SP.assert_keys_subset(part, whole, [f for f in SP.COLLECTORS if f != LAYOUT])
+    SP.assert_keys_subset(whole, whole)
+    with pytest.raises(AssertionError) as e:
+        SP.assert_keys_subset(whole, part)
+    key, kind, where = _only(whole, LAYOUT)
+    assert str(e.value) == f"launches of {whole.program} that {part.program} does not make:\n  {LAYOUT}: {kind} {key} at {where}"
+    with pytest.raises(AssertionError) as e:
+        SP.assert_keys_subset(part, whole)
+    assert str(e.value) == f"{part.program}: no {LAYOUT} launch found"
+
+
+def test_op_kinds_claimed_names_the_unclaimed_and_the_missing_required_kind():
+    s = _survey("guard: kinds", {"fwd": [_convT(L.OP_CONVT_FWD), ops.upsample2_case_args(UF_, *_UP)]})
+    with pytest.raises(AssertionError) as e:
+        SP.assert_op_kinds_claimed([_whole("guard: whole"), s])
+    assert str(e.value) == f"op kinds of {s.program} that no test answers for: ['OP_UPSAMPLE2_FWD']"
+    SP.assert_op_kinds_claimed([s], claimed_also=("OP_UPSAMPLE2_FWD",), required=(UF_, L.OP_CONVT_FWD))
+    with pytest.raises(AssertionError) as e:
+        SP.assert_op_kinds_claimed([s], claimed_also=("OP_UPSAMPLE2_FWD",), required=(UF_, UB_))
+    assert str(e.value) == f"{s.program}: no op of kind ['OP_UPSAMPLE2_BWD']"

@@ -14,10 +14,10 @@ pytestmark = pytest.mark.gpu
 
 sys.path[:0] = [p for p in (os.path.dirname(os.path.abspath(__file__)),) if p not in sys.path]
 
+import step_programs as SP  # noqa: E402
 from multi_task_breast_cancer_amd import nets, ops  # noqa: E402
 
 L = ops.L
-DEV = "cuda:0"
 PROGRAMS = [("UnetPlusPlus", "bf16", 32, 256), ("UnetPlusPlus", "f32", 32, 256), ("UnetPlusPlus", "f16", 16, 512)]
 NARROW = [("UnetPlusPlus-f24", "bf16", 32, 256), ("UnetPlusPlus-f24", "f32", 32, 256)]          # features=nets.UNETPP_FEATURES
 F_, D_, W_ = L.OP_CONV3_FWD, L.OP_CONV3_DGRAD, L.OP_CONV3_WGRAD
@@ -28,27 +28,16 @@ def _ops_gpu():
     return OPS
 
 
-def _build(arch, dtype, N, size, reserve_cus=0):
-    """Builds (does not run) one fused training step of the model through the factory's constructor path."""
-    from multi_task_breast_cancer_amd.experiment_init import init_optimizer, init_segmentation_model
-    from multi_task_breast_cancer_amd.miscellany import seed_everything
-    from multi_task_breast_cancer_amd.trainer import FusedTrainStep
-    seed_everything(1993)
+def _make_model(arch):
+    from multi_task_breast_cancer_amd.experiment_init import init_segmentation_model
     if arch == "UnetPlusPlus":
-        model = init_segmentation_model("UnetPlusPlus", sequences=1, regions=1, deep_supervision=True)
-    else:
-        model = nets.BasicUnetPlusPlus(2, 1, 1, features=nets.UNETPP_FEATURES, deep_supervision=True)
-    model = model.to(DEV)
-    model.set_compute(dtype)
-    model.coop_reserve_cus = reserve_cus
-    step = FusedTrainStep(model, init_optimizer(model, "Adam", 1e-4), alpha=1.0)
-    return step._compiled(N, size, size), (step, model)
+        return init_segmentation_model("UnetPlusPlus", sequences=1, regions=1, deep_supervision=True)
+    return nets.BasicUnetPlusPlus(2, 1, 1, features=nets.UNETPP_FEATURES, deep_supervision=True)
 
 
 def _survey(program):
-    """The survey of one program of this model, built once per session by tests/step_programs.py."""
-    import step_programs as SP
-    return SP.survey(program, build=_build)
+    """The survey of one program of this model, built (not run) once per session through the factory's constructor path."""
+    return SP.survey(program, build=SP.step_builder(_make_model, alpha=1.0))
 
 
 # ------------------------------------------------------------------------------------------------ 3x3 convolution
@@ -127,7 +116,6 @@ WGRAD_PLAN_CASES = [
     (8, [128], 16, 128, 128, _PH),   # conv3x3_wgrad_c8w_kernel<true, 2, false> + splitk_reduce (segs>1, img8, steps>=ring, ciblocks>1, splitk_reduce<16> x8)  [16 x 32+32+32+32 -> 32 @ 256 x 256 in f16 and 2 more]
     (8, [64], 40, 128, 128, _PH),    # conv3x3_wgrad_c8w_kernel<true, 2, false> + splitk_reduce (segs>1, img8, steps>=ring, splitk_reduce<16> x8)  [16 x 64 -> 64 @ 128 x 128 in f16 and 4 more]
 ]
-PLAN = "conv3x3-wgrad-plan"
 
 
 def _wgrad_plan_ids():
@@ -156,28 +144,7 @@ def test_convT_launches_match_fp64(case):
 
 # ------------------------------------------------------------------------------------------------ the guards
 def _own_keys():
-    """{family: {key: [row]}} of the calls the rows of this module's tables make, from dummy-pointer structs (nothing is launched)."""
-    import step_programs as SP
-    OPS = _ops_gpu()
-    own = {family: {} for family in SP.COLLECTORS}
-    for case in CONV3_CASES:
-        op, N, segs, Cout, H, W, mode = case
-        own["conv3x3"].setdefault((op, SP._conv3_key(ops.conv3x3_case_args(op, N, segs, Cout, H, W, **mode), op)), []).append(case)
-    for case in WGRAD_PLAN_CASES:
-        own[PLAN].setdefault((W_, SP._wgrad_plan_key(ops.conv3x3_case_args(W_, *case[:5], **case[5]))), []).append(case)
-    for case in CONVT_CASES:
-        for kind, op, a, nxt in OPS._convT_case_calls(case):
-            own["transposed-convolution"].setdefault((kind, SP._convT_key(a, op, nxt)), []).append(case)
-    return own
-
-
-def _older_keys():
-    """{family: the keys of the tables of tests/test_ops_gpu.py -- for the loss family tests/test_loss_launches_gpu.py's}"""
-    import test_loss_launches_gpu as LOSS
-    OPS = _ops_gpu()
-    return {"conv3x3": OPS._reference_tested_conv3x3_keys(), PLAN: OPS._reference_tested_wgrad_plan_keys(), "InstanceNorm": OPS._reference_tested_instnorm_keys(),
-            "transposed-convolution": OPS._reference_tested_convT_keys(), "small-op": OPS._reference_tested_small_op_keys(),
-            "layout": OPS._reference_tested_layout_keys(), "loss": LOSS._reference_tested_loss_keys()}
+    return SP.table_keys(conv3=CONV3_CASES, wgrad_plan=WGRAD_PLAN_CASES, convT=CONVT_CASES)
 
 
 @pytest.mark.parametrize("program", PROGRAMS, ids=[p[1] for p in PROGRAMS])
@@ -185,22 +152,9 @@ def test_unetpp_seg_programs_launch_only_reference_tested_instances(program):
     """Every coverage key of the step program -- kernel instances AND the branches the arguments select, as tests/step_programs.py keys them --
     is the key of a call that an element-wise reference test makes: the tables of tests/test_ops_gpu.py and tests/test_loss_launches_gpu.py,
     or the rows of this module.  The print-out is profiles/unetpp_seg_step_keys.txt."""
-    import step_programs as SP
-    s, old, own, missing = _survey(program), _older_keys(), _own_keys(), []
+    s = _survey(program)
     assert not any(kind in (L.OP_LINEAR_FWD, L.OP_GAP_FWD, L.OP_FOCAL) for kinds in s.kinds.values() for kind in kinds), "a classification op in a segmentation-only program"
-    for family in SP.COLLECTORS:
-        seen = s.seen[family]
-        assert seen, f"{program}: no {family} launch found"
-        table = "tests/test_loss_launches_gpu.py" if family == "loss" else "tests/test_ops_gpu.py"
-        print(f"{program} {family}: {len(seen)} keys, {sum(k in old[family] for k in seen)} tested by {table}'s tables, "
-              f"{sum(k in own[family] and k not in old[family] for k in seen)} by the rows added for this model, "
-              f"{sum(k not in old[family] and k not in own[family] for k in seen)} missing")
-        for key, (kind, where) in sorted(seen.items(), key=repr):
-            by = table if key in old[family] else f"row {own[family][key][0]}" if key in own[family] else "MISSING"
-            print(f"  {kind} {key} at {where}  <- {by}")
-            if by == "MISSING":
-                missing.append(f"\n  {family}: {kind} {key} at {where}")
-    assert not missing, f"launches of {program} that no reference case makes:" + "".join(missing)
+    SP.assert_only_tested(s, SP.reference_tested_keys(), _own_keys())
 
 
 @pytest.mark.parametrize("program", NARROW, ids=[p[1] for p in NARROW])
@@ -208,47 +162,18 @@ def test_narrow_unetpp_seg_programs_launch_a_subset_of_the_multitask_programs(pr
     """With features=nets.UNETPP_FEATURES the program launches no coverage key that the MTUNetPlusPlus program of the same mode and shape (the
     benchmark's, tests/step_programs.py STEP_PROGRAMS) does not launch: taking the classification head away brings no kernel instance and
     no argument branch of its own."""
-    import step_programs as SP
     mt_program = ("MTUNetPlusPlus",) + program[1:]
     assert mt_program in SP.STEP_PROGRAMS
-    s, mt, extra = _survey(program), SP.survey(mt_program), []
-    for family in SP.COLLECTORS:
-        seen = s.seen[family]
-        assert seen, f"{program}: no {family} launch found"
-        print(f"{program} {family}: {len(seen)} keys, {len(mt.seen[family])} in {mt_program}")
-        for key, (kind, where) in sorted(seen.items(), key=repr):
-            if key not in mt.seen[family]:
-                extra.append(f"\n  {family}: {kind} {key} at {where}")
-    assert not extra, f"launches of {program} that {mt_program} does not make:" + "".join(extra)
+    SP.assert_keys_subset(_survey(program), SP.survey(mt_program))
 
 
 def test_unetpp_seg_cases_are_all_needed():
     """Every row of this module's tables makes a key that a surveyed program launches, that no table of tests/test_ops_gpu.py makes and that no
     other row makes: no dead and no double rows, and deleting one fails the first guard."""
-    import step_programs as SP
-    surveys, old, bad = [_survey(p) for p in PROGRAMS], _older_keys(), []
-    for family, keys in _own_keys().items():
-        launched = set().union(*(s.seen[family] for s in surveys))
-        rows = {}
-        for key, cases in keys.items():
-            for case in cases:
-                rows.setdefault(repr(case), []).append(key)
-            if len(cases) > 1:
-                bad.append(f"\n  {family}: {len(cases)} rows make {key}: {cases}")
-        for row, ks in rows.items():
-            if not any(k in launched and k not in old[family] for k in ks):
-                bad.append(f"\n  {family}: no program launches, or an older table already makes, {ks} of row {row}")
-        print(f"{family}: {len(rows)} rows, {len(keys)} keys")
-    assert CONV3_CASES and WGRAD_PLAN_CASES and CONVT_CASES and set(_own_keys()) == set(SP.COLLECTORS)
-    assert not bad, "rows of tests/test_unetpp_seg_launches_gpu.py that are not needed:" + "".join(bad)
+    SP.assert_rows_needed("tests/test_unetpp_seg_launches_gpu.py", [_survey(p) for p in PROGRAMS], SP.reference_tested_keys(), _own_keys(),
+                          [CONV3_CASES, WGRAD_PLAN_CASES, CONVT_CASES])
 
 
 def test_every_op_kind_of_the_unetpp_seg_programs_is_claimed():
     """The op kinds of the three programs are among those tests/test_ops_gpu.py's OP_KIND_COVERED_BY claims."""
-    OPS = _ops_gpu()
-    name_of = {getattr(L, n): n for n in dir(L) if n.startswith("OP_") and isinstance(getattr(L, n), int)}
-    for program in PROGRAMS:
-        kinds = {kind for oplist in _survey(program).kinds.values() for kind in oplist}
-        print(f"{program}: {sorted(name_of.get(k, str(k)) for k in kinds)}")
-        unclaimed = sorted(name_of.get(k, str(k)) for k in kinds if name_of.get(k) not in OPS.OP_KIND_COVERED_BY)
-        assert not unclaimed, f"op kinds of {program} that no test answers for: {unclaimed}"
+    SP.assert_op_kinds_claimed([_survey(p) for p in PROGRAMS])
